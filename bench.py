@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — decode (and prefill) throughput of the MI355X-native GGUF backend on BASELINE.json's headline config.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[2], the one the metric is quoted on): Llama-3-8B-Instruct Q4_K_M, flash_attn,
 KV cache q8_0, n_ctx 4096, synthetic GGUF (exact shapes / type mix, seeded random valid blocks), synthetic prompt
@@ -14,7 +14,9 @@ The same launch then measures the ROW SPLIT of the same model over the N GPUs (S
 holds 1/N of each projection, two RCCL all-reduces per layer inside the decode graph) and reports it next to the
 replicas number as `row_split` (single-stream tok/s: what one request sees; strong scaling).  That section is fenced
 by a watchdog so that a communication problem cannot take the headline line with it.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR: rank 0 writes what the last timed step returned to its caller - the logits row (DIR/logits.npy,
+float32 [n_vocab]) and the greedy token fed to the next step (DIR/next_token.npy, float64 [1]) - so that two builds can be compared output for output
+(model, prompt and token path are seeded: the same arguments give the same inputs).
 """
 from __future__ import annotations
 
@@ -248,7 +250,10 @@ def main() -> int:
     ap.add_argument("--simulate", action="store_true",
                     help="no GPU: the same rank bookkeeping (rendezvous over gloo, barriers, MAX over ranks, rank-0 JSON) around a "
                          "sleep standing in for the decode step; used by the two-rank CPU test")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's logits row and next token as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # --gpus N must mean N ranks.  Started without a launcher (no WORLD_SIZE) and N > 1: start N FRESH child processes under torch.distributed.run - as the
     # very first thing, before any import that could initialise the GPU (never an exec of a process that has) - and relay their output (rank 0 prints the
     # line); started under a launcher whose world size is not N: refuse.  One rank printing "n_gpus": N can then not happen.
@@ -347,6 +352,10 @@ def main() -> int:
     ctx.synchronize()
     dt = time.perf_counter() - t0
     sync_all()
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), ctx.logits().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "next_token.npy"), np.array([tok], np.float64))
     # the same K steps under the same contract (mi355_decode of one token, its logits row host-visible, the arg-max fed back) driven from the C side
     # (mi355_greedy_steps: the inner loop of the reference's C++ slot loop) instead of from this script - `value` stays the script-driven loop; the difference is
     # the per-step cost of the scripting caller (numpy marshalling + three ctypes calls), which the C++ host of north_star does not pay

@@ -13,18 +13,26 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # The whole-step kernel (csrc/decode_mega.hip) and the layer engine (csrc/decode_engine.hip) lost their A/Bs against the per-launch path: they are
-# experiments, compiled into the library only on request; the product library holds csrc/experiments_absent.cc in their place.
+# experiments: the product library holds csrc/experiments_absent.cc in their place (MI355_BUILD_EXPERIMENTS=1 puts them back into it); they are always linked
+# into a library of their own, EXPERIMENTS_LIB, which the tests that exercise them load in a process of their own (tests/test_gpu_model.py).
 EXPERIMENTS = os.environ.get("MI355_BUILD_EXPERIMENTS", "0") == "1"
-SRC = [
-    "csrc/mmvq.hip", "csrc/mmvq_fast.hip", "csrc/mmvq_stream.hip", "csrc/mmq.hip", "csrc/mmq_q80.hip", "csrc/act.hip", "csrc/misc.hip", "csrc/mmf.hip", "csrc/attn.hip", "csrc/attn_out.hip", "csrc/attn_prefill.hip", "csrc/clip.hip",
-] + (["csrc/decode_engine.hip", "csrc/decode_mega.hip"] if EXPERIMENTS else ["csrc/experiments_absent.cc"]) + [
-    "host/gguf.cc", "host/runtime.cc", "host/tp_comm.cc", "host/vocab.cc", "host/sampling.cc", "host/grammar.cc", "host/json_schema.cc", "host/log.cc", "host/server_context.cc", "host/engine.cc",
-    "host/hip_backend.cc", "host/tp_split.cc", "host/clip.cc", "host/image_decode.cc", "csrc/c_api.cc",
-]
+
+
+def sources(experiments: bool) -> list:
+    return [
+        "csrc/mmvq.hip", "csrc/mmvq_fast.hip", "csrc/mmvq_stream.hip", "csrc/mmq.hip", "csrc/mmq_q80.hip", "csrc/act.hip", "csrc/misc.hip", "csrc/mmf.hip", "csrc/attn.hip", "csrc/attn_out.hip", "csrc/attn_prefill.hip", "csrc/clip.hip",
+    ] + (["csrc/decode_engine.hip", "csrc/decode_mega.hip"] if experiments else ["csrc/experiments_absent.cc"]) + [
+        "host/gguf.cc", "host/runtime.cc", "host/tp_comm.cc", "host/vocab.cc", "host/sampling.cc", "host/grammar.cc", "host/json_schema.cc", "host/log.cc", "host/server_context.cc", "host/engine.cc",
+        "host/hip_backend.cc", "host/tp_split.cc", "host/clip.cc", "host/image_decode.cc", "csrc/c_api.cc",
+    ]
+
+
+SRC = sources(EXPERIMENTS)
 HDRS = ["csrc/dev_common.h", "csrc/kernels.h", "csrc/quant_dev.h", "csrc/mmvq_fast_dev.h", "csrc/mmvq_stream_dev.h", "csrc/attn_decode_dev.h", "host/gguf.h", "host/runtime.h", "host/tp_comm.h", "host/json.h", "host/vocab.h",
         "host/sampling.h", "host/grammar.h", "host/log.h", "host/backend_iface.h", "host/server_context.h", "host/engine.h", "host/hip_backend.h", "host/clip.h", "host/parallel_rows.h", "host/tp_split.h", "host/shm_exchange.h",
         "../include/mi355_llama.h"]
 LIB = os.path.join(HERE, "lib", "libmi355_llama.so")
+EXPERIMENTS_LIB = os.path.join(HERE, "lib", "libmi355_llama_experiments.so")
 TP_WORKER = os.path.join(HERE, "bin", "mi355_tp_worker")  # a further rank of an engine-formed row split (server/mi355_tp_worker.cc; started by host/tp_split.cc)
 SERVER = os.path.join(HERE, "bin", "mi355_server")          # the HTTP host: plain C++, dlopen()s LIB at run time (server/mi355_server.cc)
 # -ffp-contract=off: the CPU restatement this backend is checked against does not fuse mul+add
@@ -56,7 +64,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdr_m = max(os.path.getmtime(os.path.join(HERE, h)) for h in HDRS)
     hipcc = _hipcc()
     jobs = []
-    for s in SRC:
+    for s in sorted(set(SRC) | set(sources(True))):
         src = os.path.join(HERE, s)
         obj = os.path.join(objdir, s.replace("/", "_") + ".o")
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hdr_m):
@@ -77,17 +85,18 @@ def build(force: bool = False, verbose: bool = False) -> str:
         for warn in ex.map(cc, jobs):
             if verbose and warn:
                 print(warn)
-    objs = [os.path.join(objdir, s.replace("/", "_") + ".o") for s in SRC]
-    stamp = os.path.join(objdir, "linked_objects.txt")       # which objects the library on disk was linked from (the experiments switch changes the set)
-    want = "\n".join(objs)
-    have = open(stamp).read() if os.path.exists(stamp) else ""
-    if jobs or not os.path.exists(LIB) or have != want:
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-pthread", "-o", LIB] + objs + ["-ldl"]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"link failed:\n{r.stderr}")
-        with open(stamp, "w") as f:
-            f.write(want)
+    for lib, src, stamp_name in ((LIB, SRC, "linked_objects.txt"), (EXPERIMENTS_LIB, sources(True), "linked_objects_experiments.txt")):
+        objs = [os.path.join(objdir, s.replace("/", "_") + ".o") for s in src]
+        stamp = os.path.join(objdir, stamp_name)                # which objects the library on disk was linked from (the experiments switch changes the set)
+        want = "\n".join(objs)
+        have = open(stamp).read() if os.path.exists(stamp) else ""
+        if jobs or not os.path.exists(lib) or have != want:
+            cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-pthread", "-o", lib] + objs + ["-ldl"]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"link failed:\n{r.stderr}")
+            with open(stamp, "w") as f:
+                f.write(want)
     build_server(force)
     return LIB
 

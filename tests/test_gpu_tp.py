@@ -9,6 +9,7 @@
   issued through librccl on the context's stream and captured into the decode graphs; results must equal the unsplit run
   bit for bit.
 """
+import dataclasses
 import os
 import socket
 import subprocess
@@ -25,6 +26,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KV = {"f16": 1, "q8_0": 8}
 FLIP_TOL = 3e-2     # see test_gpu_model.py: one flipped int8 rounding moves these tiny models' logits by up to ~1e-2
 TIGHT_TOL = 2e-5
+# The shared device admits at most 6 processes with it open: this test's own, its ranks and (test_reduce_scatter_case_in_a_fresh_process) a child pytest.
+# So at most 4 ranks.  A rank's geometry in a split of Llama-3-8B / Llama-3-70B over 8 GPUs is carried by 4 ranks of a model half as wide: the same query and
+# kv heads, attn_output and ffn_down columns per rank.  name: (full-width config, n_embd, n_head, n_head_kv, n_ff)
+HALF_WIDTH = {
+    "tiny-8b-half-2l": ("tiny-8b-2l", 2048, 16, 4, 7168),
+    "tiny-70b-half-2l": ("tiny-70b-2l", 4096, 32, 4, 14336),
+}
+
+
+def config(pkg, cfg):
+    if cfg in pkg.gguf_synth.CONFIGS:
+        return pkg.gguf_synth.CONFIGS[cfg]
+    base, n_embd, n_head, n_head_kv, n_ff = HALF_WIDTH[cfg]
+    return dataclasses.replace(pkg.gguf_synth.CONFIGS[base], name=cfg, n_embd=n_embd, n_head=n_head, n_head_kv=n_head_kv, n_ff=n_ff)
 
 
 def _free_port() -> int:
@@ -97,7 +112,7 @@ def _run_ranks_once(world, plan_path, out_path, timeout):
 def make_plan(pkg, tmp_models, cfg, ftype, kv, n_prompt, transport, n_steps=6, n_tail=3, seed=21, p2p_floats=0, p2p_prompt_floats=0):
     path = str(tmp_models / f"tp-{cfg}-{ftype}.gguf")
     if not os.path.exists(path):
-        pkg.gguf_synth.write_synthetic_llama(path, cfg, ftype, seed=seed)
+        pkg.gguf_synth.write_synthetic_llama(path, config(pkg, cfg), ftype, seed=seed)
     om = oq.OracleModel(path)
     oc = oq.OracleContext(om, 256, KV[kv], KV[kv], True, oq.threads())
     if kv == "f16":
@@ -150,10 +165,10 @@ def unsplit_logits(pkg, plan_path):
     ("tiny-e2048", "q5_k_m", "q8_0", 40, 2),      # 40-token prompt: the MFMA prompt path on a slice; fused prologues on the steps
     ("tiny-e2048", "q4_k_m", "q8_0", 8, 4),       # four ranks: one KV head each
     ("tiny-8b-2l", "q4_k_m", "q8_0", 8, 2),       # Llama-3-8B's layer geometry
-    ("tiny-8b-2l", "q4_k_m", "q8_0", 8, 8),       # north_star's rank count: 4 query heads + 1 KV head and 1792 = 7 x 256 feed-forward columns per rank
+    ("tiny-8b-half-2l", "q4_k_m", "q8_0", 8, 4),  # north_star's rank geometry: 4 query heads + 1 KV head and 1792 = 7 x 256 feed-forward columns per rank
     # BASELINE config 5's per-rank geometry (Llama-3-70B over 8 GPUs): 8 query heads on ONE kv head, attn_output columns of 1024 = 4 super-blocks, ffn_down
-    # columns of 3584 = 14 super-blocks of the 28672-wide tensor (whose single-GPU form is two column halves: the slicing must not meet them); and over 4
-    ("tiny-70b-2l", "q4_k_m", "q8_0", 8, 8),
+    # columns of 3584 = 14 super-blocks; and Llama-3-70B's own layers over 4 ranks: slices of the 28672-wide ffn_down (whose single-GPU form is two column halves)
+    ("tiny-70b-half-2l", "q4_k_m", "q8_0", 8, 4),
     ("tiny-70b-2l", "q4_k_m", "q8_0", 8, 4),
 ])
 def test_ranks_sharing_one_gpu_match_oracle_and_unsplit(pkg, tmp_models, cfg, ftype, kv, n_prompt, world):
@@ -185,7 +200,7 @@ def test_ranks_sharing_one_gpu_match_oracle_and_unsplit(pkg, tmp_models, cfg, ft
             assert int(a.argmax()) == int(b.argmax())
 
 
-@pytest.mark.parametrize("cfg,ftype,kv,world", [("tiny-e2048", "q4_k_m", "q8_0", 2), ("tiny-8b-2l", "q4_k_m", "q8_0", 2), ("tiny-e2048", "q4_k_m", "q8_0", 4), ("tiny-70b-2l", "q4_k_m", "q8_0", 8)])
+@pytest.mark.parametrize("cfg,ftype,kv,world", [("tiny-e2048", "q4_k_m", "q8_0", 2), ("tiny-8b-2l", "q4_k_m", "q8_0", 2), ("tiny-e2048", "q4_k_m", "q8_0", 4), ("tiny-70b-half-2l", "q4_k_m", "q8_0", 4)])
 def test_peer_to_peer_all_reduce_matches_the_host_exchange(pkg, tmp_models, cfg, ftype, kv, world):
     """The one-shot peer-to-peer all-reduce (host/tp_comm.cc: every rank writes its partial into slot `rank` of every rank's IPC-mapped buffer, flags,
     rank-order sum) takes the decode-sized exchanges; the prompt batch and the logits gather keep the host transport.  IPC mapping works between
@@ -193,12 +208,12 @@ def test_peer_to_peer_all_reduce_matches_the_host_exchange(pkg, tmp_models, cfg,
     transport, so every logits row is bit-identical to the pure host-exchange run; four ranks: the rank-order sum differs from gloo's by re-association
     only - oracle bound, and the same bits on a second run."""
     pkg.Backend()
-    E = pkg.gguf_synth.CONFIGS[cfg].n_embd
+    E = config(pkg, cfg).n_embd
     path, plan_host, ref = make_plan(pkg, tmp_models, cfg, ftype, kv, 8, "host")
     _, plan_p2p, _ = make_plan(pkg, tmp_models, cfg, ftype, kv, 8, "host", p2p_floats=4 * E)
     host = run_ranks(world, plan_host, str(tmp_models / f"tp-out-host-{cfg}-{world}.npz"))
     p2p = run_ranks(world, plan_p2p, str(tmp_models / f"tp-out-p2p-{cfg}-{world}.npz"))
-    n_layer = pkg.gguf_synth.CONFIGS[cfg].n_layer
+    n_layer = config(pkg, cfg).n_layer
     assert int(host["p2p_exchanges"]) == 0
     assert int(p2p["p2p_exchanges"]) >= 2 * n_layer * 6            # the six single-token steps (and the three-token tail: 3 E <= 4 E)
     errs = [rel_err(a, b) for a, b in zip(p2p["logits"], ref)]
@@ -212,7 +227,7 @@ def test_peer_to_peer_all_reduce_matches_the_host_exchange(pkg, tmp_models, cfg,
 
 
 @pytest.mark.parametrize("cfg,ftype,kv,world,wgs", [("tiny-e2048", "q4_k_m", "q8_0", 2, 0), ("tiny-8b-2l", "q4_k_m", "q8_0", 2, 7), ("tiny-e2048", "q4_k_m", "q8_0", 4, 0),
-                                                    ("tiny-e2048", "q5_k_m", "f16", 4, 5), ("tiny-8b-2l", "q4_k_m", "q8_0", 8, 0), ("tiny-70b-2l", "q4_k_m", "q8_0", 8, 0)])
+                                                    ("tiny-e2048", "q5_k_m", "f16", 4, 5), ("tiny-8b-half-2l", "q4_k_m", "q8_0", 4, 0), ("tiny-70b-half-2l", "q4_k_m", "q8_0", 4, 0)])
 def test_prompt_sized_exchange_as_reduce_scatter_all_gather(pkg, tmp_models, cfg, ftype, kv, world, wgs, monkeypatch):
     """Prompt batches: the n_embd x n_ubatch partial sums go through ONE reduce-scatter + all-gather kernel (host/tp_comm.cc p2p_rsag_kernel:
     a segment per rank, every rank stores its part of segment q into rank q's IPC-mapped buffer, the owner adds in rank order and stores the sum
@@ -220,12 +235,10 @@ def test_prompt_sized_exchange_as_reduce_scatter_all_gather(pkg, tmp_models, cfg
     per layer; the single-token steps keep the one-shot kernel.  Two ranks: bit-identical to the pure host-exchange run (p0 + p1 either way);
     four ranks: the rank-order sum is the one-shot kernel's association - oracle bound, the host run within the flip tolerance, the same bits
     again on a second run.  `wgs` cuts the segments into an odd number of slices (ragged last slice)."""
-    if (cfg, world) == ("tiny-70b-2l", 8) and os.environ.get("MI355_TP_FRESH_PROCESS") != "1":
-        pytest.skip("this case runs alone in a process of its own: test_eight_rank_reduce_scatter_case_in_a_fresh_process")
     pkg.Backend()
     if wgs:
         monkeypatch.setenv("MI355_TP_RSAG_WGS", str(wgs))
-    C_ = pkg.gguf_synth.CONFIGS[cfg]
+    C_ = config(pkg, cfg)
     E, n_layer = C_.n_embd, C_.n_layer
     path, plan_host, ref = make_plan(pkg, tmp_models, cfg, ftype, kv, 100, "host")
     _, plan_rs, _ = make_plan(pkg, tmp_models, cfg, ftype, kv, 100, "host", p2p_floats=4 * E, p2p_prompt_floats=64 * E)
@@ -246,15 +259,15 @@ def test_prompt_sized_exchange_as_reduce_scatter_all_gather(pkg, tmp_models, cfg
         assert max(rel_err(a, b) for a, b in zip(rs["logits"], host["logits"])) <= FLIP_TOL
 
 
-def test_eight_rank_reduce_scatter_case_in_a_fresh_process():
-    """The 8-rank reduce-scatter + all-gather case as the FIRST and ONLY multi-rank test of its own pytest process: its colour must not depend on what ran
+def test_reduce_scatter_case_in_a_fresh_process():
+    """The reduce-scatter + all-gather case of BASELINE config 5's per-rank geometry (it ran over 8 ranks until the shared device's process limit; see
+    HALF_WIDTH) as the FIRST and ONLY multi-rank test of its own pytest process (it runs in file order as well): its colour must not depend on what ran
     before it (it was red whenever it ran alone - cold box or warm - and green in file order).  Round 6 found two causes, neither in the exchange kernel:
     the ranks of this rig reached their first exchange seconds apart (nothing stepped them in lock-step: tests/tp_worker.py now meets at a barrier, as a row
     split's driver does), and the one-launch attention + attn_output kernel - workgroups that wait for each other - ran in eight processes on ONE device
     (host/runtime.cc keeps it off now where the ranks exchange through the host callback, i.e. share a device).  profiles/r6_tp_shared_device_trace.txt."""
-    case = "tests/test_gpu_tp.py::test_prompt_sized_exchange_as_reduce_scatter_all_gather[tiny-70b-2l-q4_k_m-q8_0-8-0]"
-    r = subprocess.run([sys.executable, "-m", "pytest", case, "-x", "-q", "-p", "no:cacheprovider"], cwd=ROOT, capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, MI355_TP_FRESH_PROCESS="1"))
+    case = "tests/test_gpu_tp.py::test_prompt_sized_exchange_as_reduce_scatter_all_gather[tiny-70b-half-2l-q4_k_m-q8_0-4-0]"
+    r = subprocess.run([sys.executable, "-m", "pytest", case, "-x", "-q", "-p", "no:cacheprovider"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-6000:]
     assert "1 passed" in r.stdout
 
