@@ -107,6 +107,8 @@ SYMBOLS = {
     "mi355_op_flash_attn": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32, _vp]),
     "mi355_op_attn_step": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _i64, _vp, _i32,
                                      _vp, _vp, _vp, _vp]),
+    "mi355_op_attn_decode_neox": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _f32, _i32,
+                                            _vp, _vp, _vp]),
     "mi355_bench_hbm_read": (C.c_double, [_sz, C.c_int]),
     "mi355_profile_last_decode": (_i32, [_vp, C.POINTER(_cp), C.POINTER(_f32), _i32]),
     "mi355_profile_enable": (None, [_vp, _i32]),
@@ -321,6 +323,23 @@ class Backend:
                                               _ptr(cell_pos), int(tok_pos), int(tok_cell), float(rope_base), int(n_rot), float(scale), type_o, _ptr(W_o), n_embd,
                                               _ptr(resid), int(bool(fused)), _ptr(att), _ptr(out), _ptr(kr), _ptr(vr)), "op_attn_step")
         return att, out, kr, vr
+
+    def attn_decode_neox(self, q, k_new, v_new, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows, type_v: int, v_rows, cell_pos, tok_pos: int,
+                         tok_cell: int, rope_base: float, scale: float, q_norm, k_norm, eps: float, mode: int, k_row_bytes: int, v_row_bytes: int):
+        """The decode attention of one token with NEOX rope and optional per-head q / k RMSNorm weights (mi355_op_attn_decode_neox; q_norm / k_norm: [hd]
+        f32 or None): returns (att [H * D], k_row, v_row).  mode 1: single-launch step, 0: store-fused batched form, 2: generic rope_kv_store path."""
+        q = np.ascontiguousarray(q, np.float32); k_new = np.ascontiguousarray(k_new, np.float32); v_new = np.ascontiguousarray(v_new, np.float32)
+        cell_pos = np.ascontiguousarray(cell_pos, np.int32)
+        k_rows = np.ascontiguousarray(k_rows.view(np.uint8)); v_rows = np.ascontiguousarray(v_rows.view(np.uint8))
+        qn = None if q_norm is None else np.ascontiguousarray(q_norm, np.float32)
+        kn = None if k_norm is None else np.ascontiguousarray(k_norm, np.float32)
+        att = np.zeros(n_head * hd, np.float32)
+        kr = np.zeros(k_row_bytes, np.uint8); vr = np.zeros(v_row_bytes, np.uint8)
+        self._chk(self.lib.mi355_op_attn_decode_neox(_ptr(q), _ptr(k_new), _ptr(v_new), n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v, _ptr(v_rows),
+                                                     cell_pos.size, _ptr(cell_pos), int(tok_pos), int(tok_cell), float(rope_base), float(scale),
+                                                     None if qn is None else _ptr(qn), None if kn is None else _ptr(kn), float(eps), int(mode),
+                                                     _ptr(att), _ptr(kr), _ptr(vr)), "op_attn_decode_neox")
+        return att, kr, vr
 
     def hbm_read_gbps(self, nbytes: int = 1 << 30, iters: int = 10) -> float:
         return float(self.lib.mi355_bench_hbm_read(nbytes, iters))

@@ -50,6 +50,30 @@ __device__ __forceinline__ void rope_heads_lds(float *buf, int n_head, int D, in
     }
 }
 
+// qwen3 (llm_build_qwen3): RMSNorm of every head over its own D values, times the [D] weight w, then the rotation - in place, whole heads (n_rot == D,
+// D = 64 or 128).  Thread = rope pair; a head's D / 2 pairs are consecutive lanes of one wave, whose sum of squares is a reduction across them.
+// Every thread of the workgroup runs every pass (the shuffles); the arithmetic per element is rms_norm -> mul -> rope as the CPU graph orders it.
+__device__ __forceinline__ void norm_rope_heads(float *buf, int n_head, int D, int neox, const float *cs, const float *w, float eps, int tid, int nthr) {
+    const int HP = D >> 1, n = n_head * HP;
+    for (int b0 = 0; b0 < n; b0 += nthr) {
+        const int idx = b0 + tid;
+        const bool ok = idx < n;
+        const int h = ok ? idx / HP : 0, i = ok ? idx - h * HP : 0;
+        float *p = buf + (size_t)h * D;
+        const int a = neox ? i : 2 * i, b = neox ? i + HP : 2 * i + 1;
+        float x0 = ok ? p[a] : 0.0f, x1 = ok ? p[b] : 0.0f;
+        float ss = x0 * x0 + x1 * x1;
+        for (int o = 1; o < HP; o <<= 1) ss += __shfl_xor(ss, o, 64);
+        if (ok) {
+            const float sc = 1.0f / sqrtf(ss / (float)D + eps);
+            x0 = x0 * sc * w[a]; x1 = x1 * sc * w[b];
+            const float c = cs[2 * i], s = cs[2 * i + 1];
+            p[a] = x0 * c - x1 * s;
+            p[b] = x0 * s + x1 * c;
+        }
+    }
+}
+
 // store one row of n = G*D f32 values (LDS or global) into cache planes at `cell`; 32 consecutive threads per block
 __device__ __forceinline__ void store_row(const float *src, int G, int D, int type, uint8_t *plane, uint16_t *dplane,
                                           int n_ctx, int cell, int tid, int nthr) {
@@ -200,9 +224,12 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(float *q, const floa
     if (k) for (int e = tid; e < G * D; e += 256) kbuf[e] = k[(size_t)t * G * D + e];
     __syncthreads();
     float *qr = q + (size_t)t * n_head * D;
-    rope_heads_lds(qr, n_head, D, ra.n_rot, ra.neox, cs, tid, 256);   // q rotated in global memory
+    // q rotated in global memory (qwen3: each head normalised first, launch_rope_kv_store checks n_rot == D)
+    if (ra.q_norm) norm_rope_heads(qr, n_head, D, ra.neox, cs, ra.q_norm, ra.qk_eps, tid, 256);
+    else rope_heads_lds(qr, n_head, D, ra.n_rot, ra.neox, cs, tid, 256);
     if (k) {
-        rope_heads_lds(kbuf, G, D, ra.n_rot, ra.neox, cs, tid, 256);
+        if (ra.k_norm) norm_rope_heads(kbuf, G, D, ra.neox, cs, ra.k_norm, ra.qk_eps, tid, 256);
+        else rope_heads_lds(kbuf, G, D, ra.n_rot, ra.neox, cs, tid, 256);
         __syncthreads();
         const int cell = tok_cell[t];
         store_row(kbuf, G, D, type_k, kv.k, kv.kd, n_ctx, cell, tid, 256);
@@ -213,6 +240,7 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(float *q, const floa
 hipError_t launch_rope_kv_store(float *q, const float *k, const float *v, int T, int n_head, int G, int D,
                                 const int32_t *tok_pos, const int32_t *tok_cell, RopeArgs ra, KVLayerView kv,
                                 int type_k, int type_v, int n_ctx, const float *cs_table, hipStream_t st) {
+    if (ra.qk_norm() && (ra.n_rot != D || (D != 64 && D != 128))) return hipErrorInvalidValue;   // (the norm works on whole heads of 64 or 128)
     const float theta_scale = powf(ra.freq_base, -2.0f / (float)ra.n_rot);
     const size_t lds = sizeof(float) * ((size_t)ra.n_rot + (size_t)G * D);
     hipLaunchKernelGGL(rope_kv_store_kernel, dim3(T), dim3(256), lds, st, q, k, v, n_head, G, D, tok_pos, tok_cell, ra,
@@ -658,6 +686,7 @@ __global__ __launch_bounds__(256) void rope_q_kv_store_fast_kernel(float *q, int
 }
 
 bool rope_q_kv_store_fast_applicable(int H, int G, int D, int type_k, int type_v, const RopeArgs &ra) {
+    if (ra.qk_norm()) return false;                  // no per-head q / k RMSNorm here (qwen3 takes rope_kv_store_kernel)
     return kv_store_fast_applicable(G, D, type_k, type_v, ra) && (H * D) % 1024 == 0 && D % 4 == 0;
 }
 hipError_t launch_rope_q_kv_store_fast(float *q, const float *k, const float *v, int T, int H, int G, int D, const float *cs_table, RopeArgs ra,
@@ -675,10 +704,12 @@ hipError_t launch_rope_q_kv_store_fast(float *q, const float *k, const float *v,
 }
 
 bool kv_store_fast_applicable(int G, int D, int type_k, int type_v, const RopeArgs &ra) {
+    if (ra.qk_norm()) return false;                  // no per-head k RMSNorm here
     return !ra.neox && (G * D) % 1024 == 0 && D % 32 == 0 && (ra.n_rot % 4) == 0 && (type_k == T_F16 || type_k == T_Q8_0) && (type_v == T_F16 || type_v == T_Q8_0);
 }
 hipError_t launch_kv_store_fast(const float *k, const float *v, int T, int G, int D, const float *cs_table, RopeArgs ra,
                                 const int32_t *tok_cell, KVLayerView kv, int type_k, int type_v, int n_ctx, hipStream_t st) {
+    if (ra.qk_norm()) return hipErrorInvalidValue;
 #define KVS(TK, TV) hipLaunchKernelGGL((kv_store_fast_kernel<TK, TV>), dim3(T), dim3(256), 0, st, k, v, G * D, D, cs_table, ra.n_rot, tok_cell, kv, n_ctx)
     if (type_k == T_F16 && type_v == T_F16) KVS(T_F16, T_F16);
     else if (type_k == T_Q8_0 && type_v == T_Q8_0) KVS(T_Q8_0, T_Q8_0);
@@ -697,8 +728,8 @@ bool flash_attn_decode_applicable(const AttnArgs &a, const RopeArgs &ra) {
     const bool pow2 = R == 1 || R == 2 || R == 4 || R == 8;
     // 3, 5, 6, 7 query heads per kv head (Llama-3.2-3B, Qwen2-1.5B / 7B, Yi-34B): head_dim 128 and one cache type for K and V only (fewer instantiations)
     const bool odd = (R == 3 || R == 5 || R == 6 || R == 7) && a.D == 128 && a.type_k == a.type_v;
-    // NEOX pairing (qwen2): the kernel rotates whole heads only
-    if (ra.neox && ra.n_rot != a.D) return false;
+    // NEOX pairing (qwen2): the kernel rotates whole heads only; so does the per-head q / k RMSNorm (qwen3)
+    if ((ra.neox || ra.qk_norm()) && ra.n_rot != a.D) return false;
     // a q4_0 cache (K and V): head_dim 128, the power-of-two head ratios
     if (a.type_k == T_Q4_0 || a.type_v == T_Q4_0) return a.type_k == a.type_v && a.D == 128 && pow2 && a.T <= 64 && a.n_kv_max <= 64 * 2048;
     return (a.D == 128 || a.D == 64) && (pow2 || odd) && a.T <= 64 && a.n_kv_max <= 64 * 2048 &&
@@ -715,6 +746,7 @@ hipError_t launch_flash_attn_decode(const AttnArgs &a, const float *cs_table, Ro
     const dim3 grid(a.G, a.splits, a.T);
     DecodeFuse nofz{};
     nofz.neox = ra.neox;
+    nofz.q_norm = ra.q_norm; nofz.k_norm = ra.k_norm; nofz.qk_eps = ra.qk_eps;
     const bool store = knew && vnew && tok_cell;
     if (store) { nofz.knew = knew; nofz.vnew = vnew; nofz.tok_cell = tok_cell; }
 #define FAD_D(RR, TK, TV, DD) do { if (store) hipLaunchKernelGGL((flash_attn_decode_kernel<RR, TK, TV, true, false, DD>), grid, dim3(256), 0, st, a, cs_table, ra.n_rot, nofz); \
@@ -802,6 +834,7 @@ hipError_t launch_flash_attn_decode_fused(const AttnArgs &a, const float *cs_tab
     DecodeFuse fz{};
     fz.knew = knew; fz.vnew = vnew; fz.tok_cell = tok_cell; fz.counters = counters;
     fz.neox = ra.neox;
+    fz.q_norm = ra.q_norm; fz.k_norm = ra.k_norm; fz.qk_eps = ra.qk_eps;
     if (a.out_q) fz.q = *a.out_q;
     fz.want_q8k = (int)(a.out_q && a.out_q8k); fz.want_q80 = (int)(a.out_q && a.out_q80);
     fz.probe = attn_probe_buffer();

@@ -58,6 +58,10 @@ struct DecodeFuse {
     ActQuant q;
     int want_q8k, want_q80;
     int neox;                      // rotary pairing (i, i + D / 2) instead of (2i, 2i + 1): qwen2-type files; the whole head rotates (n_rot == D)
+    // qwen3: [D] f32 weights of the per-head RMSNorm of q / of the token's K row, applied before the rotation (RopeArgs::q_norm / k_norm); null: none.
+    // Workgroup-uniform branches: a file without the norm runs exactly the instructions it ran before.
+    const float *q_norm, *k_norm;
+    float qk_eps;
     // diagnosis (MI355_ATTN_PROBE=1): 100 MHz wall-clock stamps.  [2 * wg], [2 * wg + 1] = start / partials-stored of every
     // workgroup (wg = sp * G + g); [4096 + 8 * g + k] = the merging workgroup of kv head g: ticket taken, weights done,
     // partials summed, outputs stored
@@ -181,6 +185,18 @@ __device__ __forceinline__ void flash_attn_decode_item(const AttnArgs &a, const 
                 const coh_u32x4 xx = cld16<COH>(isk ? fz.knew : fz.vnew, ((t * a.G + g) * D + dd) * 4);
                 x4 = make_float4(__uint_as_float(xx.x), __uint_as_float(xx.y), __uint_as_float(xx.z), __uint_as_float(xx.w));
             }
+            if (fz.k_norm) {
+                // qwen3: RMSNorm of the kv head's D values (the DQ lanes of the K half of the wave hold them, 4 each), times the weight, before the rotation
+                // (the V lanes run the same exchange on their own values and discard it)
+                float ss = x4.x * x4.x + x4.y * x4.y + x4.z * x4.z + x4.w * x4.w;
+#pragma unroll
+                for (int o = 1; o < DQ; o <<= 1) ss += __shfl_xor(ss, o, 64);
+                if (isk) {
+                    const float sc = 1.0f / sqrtf(ss / (float)D + fz.qk_eps);
+                    const float4 w4 = *reinterpret_cast<const float4 *>(fz.k_norm + dd);
+                    x4.x = x4.x * sc * w4.x; x4.y = x4.y * sc * w4.y; x4.z = x4.z * sc * w4.z; x4.w = x4.w * sc * w4.w;
+                }
+            }
             if (fz.neox) {
                 // NEOX pairing: element e < D / 2 rotates with e + D / 2, which sits DQ / 2 lanes further on (both K lanes and V lanes run the exchange)
                 const float p0 = __shfl_xor(x4.x, DQ / 2), p1 = __shfl_xor(x4.y, DQ / 2), p2 = __shfl_xor(x4.z, DQ / 2), p3 = __shfl_xor(x4.w, DQ / 2);
@@ -232,9 +248,27 @@ __device__ __forceinline__ void flash_attn_decode_item(const AttnArgs &a, const 
         }
     }
 
-    // ---- q: rotate, convert
+    // ---- q: (qwen3: normalise,) rotate, convert
     if (tid < C) vis[tid] = (cpos >= 0 && cpos <= tpos && ((cseq >> tseq) & 1ull)) ? 1 : 0;
     if (tid < C * NB / 2) { ksc[tid] = ks2; vsc[tid] = vs2; }
+    if (fz.q_norm) {
+        // per-head RMSNorm: a head's HP pairs are HP consecutive lanes of one wave (HP = 64 or 32 divides the wave; NPAIR is a multiple of HP), so the sum
+        // of squares is a reduction across those lanes; lanes past NPAIR add zeros among themselves
+#pragma unroll
+        for (int j = 0; j < PPT; j++) {
+            const int pp = tid + 256 * j;
+            const bool ok = pp < NPAIR;
+            float ss = ok ? qv[j].x * qv[j].x + qv[j].y * qv[j].y : 0.0f;
+#pragma unroll
+            for (int o = 1; o < HP; o <<= 1) ss += __shfl_xor(ss, o, 64);
+            if (ok) {
+                const int i = pp % HP;
+                const float sc = 1.0f / sqrtf(ss / (float)D + fz.qk_eps);
+                const float w0 = fz.q_norm[fz.neox ? i : 2 * i], w1 = fz.q_norm[fz.neox ? i + HP : 2 * i + 1];
+                qv[j].x = qv[j].x * sc * w0; qv[j].y = qv[j].y * sc * w1;
+            }
+        }
+    }
 #pragma unroll
     for (int j = 0; j < PPT; j++) {
         const int pp = tid + 256 * j;

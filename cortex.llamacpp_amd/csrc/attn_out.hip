@@ -1473,6 +1473,7 @@ int attn_out_fused_splits(const AttnArgs &a) {
 bool attn_out_fused_applicable(const AttnArgs &a, const RopeArgs &ra, const MMVQSeg &wo, int K, int epi) {
     if (!attn_out_fused_enabled()) return false;
     if (a.T != 1 || a.D != AO_D || ra.neox || (ra.n_rot % 4) != 0 || ra.n_rot > a.D) return false;
+    if (ra.qk_norm()) return false;      // no per-head q / k RMSNorm in this kernel's rope (qwen3 layers take the single-launch decode attention)
     const int R = a.G > 0 ? a.H / a.G : 0;
     if (R * a.G != a.H || !(R == 1 || R == 2 || R == 4 || R == 8)) return false;
     const bool q8 = a.type_k == T_Q8_0 && a.type_v == T_Q8_0, f16 = a.type_k == T_F16 && a.type_v == T_F16;
@@ -1690,6 +1691,7 @@ size_t qkv_attn_out_plan_lds(int type_q, int type_k, int type_v, int type_o, int
     return p.lds_total;
 }
 bool qkv_attn_out_applicable(const AttnArgs &a, const RopeArgs &ra, const MMVQSeg &wo, int K, int epi, const QKVFuse &q) {
+    if (ra.qk_norm()) return false;      // (explicit: a NEOX form of the one-launch block must not drop the q / k norm silently)
     return attn_out_fused_applicable(a, ra, wo, K, epi) && qf_plan(a, wo, K, q).blocks > 0;
 }
 hipError_t launch_qkv_attn_out(const AttnArgs &a, const float *cs_table, RopeArgs ra, const int32_t *tok_cell, unsigned *counters, unsigned *flags, unsigned long long *gran,

@@ -426,6 +426,50 @@ int hip_fail(hipError_t e, const char *what) {
     fail(std::string(what) + ": " + hipGetErrorString(e));
     return MI355_ERR_HIP;
 }
+// ggml-layout cache rows [n_cells][G * D] (f16, q8_0 or q4_0 blocks) -> the device's head-major planes: codes [G][n_cells][...] and f16 block scales
+void cache_planes_from_rows(int type, const void *rows, int G, int D, int n_cells, std::vector<uint8_t> &codes, std::vector<uint16_t> &scales) {
+    const uint8_t *src = (const uint8_t *)rows;
+    const size_t rb = ggml_row_bytes(type, (int64_t)G * D);
+    if (type == T_F16) {
+        codes.resize((size_t)G * n_cells * D * 2);
+        for (int c = 0; c < n_cells; c++)
+            for (int g = 0; g < G; g++) memcpy(&codes[(((size_t)g * n_cells + c) * D) * 2], src + (size_t)c * rb + (size_t)g * D * 2, (size_t)D * 2);
+    } else {
+        const int bb = type == T_Q8_0 ? 34 : 18, cb = type == T_Q8_0 ? 32 : 16;
+        codes.resize((size_t)G * n_cells * (D / 32) * cb);
+        scales.resize((size_t)G * n_cells * (D / 32));
+        for (int c = 0; c < n_cells; c++)
+            for (int g = 0; g < G; g++)
+                for (int b = 0; b < D / 32; b++) {
+                    const uint8_t *blk = src + (size_t)c * rb + ((size_t)g * (D / 32) + b) * bb;
+                    memcpy(&scales[((size_t)g * n_cells + c) * (D / 32) + b], blk, 2);
+                    memcpy(&codes[(((size_t)g * n_cells + c) * (D / 32) + b) * cb], blk + 2, (size_t)cb);
+                }
+    }
+}
+// ... and back: the cache row at `cell` in ggml block layout (dst: G * D elements' worth; null: nothing to do)
+bool cache_row_to_ggml(int type, DevBuf &codes, DevBuf &scales, int G, int D, int n_cells, int cell, void *dst) {
+    if (!dst) return true;
+    uint8_t *o8 = (uint8_t *)dst;
+    for (int g = 0; g < G; g++) {
+        const size_t rowi = (size_t)g * n_cells + cell;
+        if (type == T_F16) {
+            if (hipMemcpy(o8 + (size_t)g * D * 2, (uint8_t *)codes.p + rowi * D * 2, (size_t)D * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        } else {
+            const int bb = type == T_Q8_0 ? 34 : 18, cb = type == T_Q8_0 ? 32 : 16;
+            std::vector<uint8_t> c((size_t)(D / 32) * cb);
+            std::vector<uint16_t> sc((size_t)D / 32);
+            if (hipMemcpy(c.data(), (uint8_t *)codes.p + rowi * (D / 32) * cb, c.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
+            if (hipMemcpy(sc.data(), (uint8_t *)scales.p + rowi * (D / 32) * 2, sc.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
+            for (int b = 0; b < D / 32; b++) {
+                uint8_t *blk = o8 + ((size_t)g * (D / 32) + b) * bb;
+                memcpy(blk, &sc[(size_t)b], 2);
+                memcpy(blk + 2, &c[(size_t)b * cb], (size_t)cb);
+            }
+        }
+    }
+    return true;
+}
 }  // namespace
 
 extern "C" double hbm_read_probe(size_t bytes, int iters);
@@ -733,26 +777,7 @@ int mi355_op_attn_step(const float *q, const float *k_new, const float *v_new, i
     if ((D != 64 && D != 128) || G < 1 || H % G || n_cells < 1 || tok_cell < 0 || tok_cell >= n_cells) { fail("bad geometry"); return MI355_ERR_ARG; }
     const int64_t K = (int64_t)H * D;
     const size_t kv_dim = (size_t)G * D;
-    auto fill = [&](int type, const void *rows, std::vector<uint8_t> &codes, std::vector<uint16_t> &scales) {
-        const uint8_t *src = (const uint8_t *)rows;
-        const size_t rb = ggml_row_bytes(type, (int64_t)kv_dim);
-        if (type == T_F16) {
-            codes.resize((size_t)G * n_cells * D * 2);
-            for (int c = 0; c < n_cells; c++)
-                for (int g = 0; g < G; g++) memcpy(&codes[(((size_t)g * n_cells + c) * D) * 2], src + (size_t)c * rb + (size_t)g * D * 2, (size_t)D * 2);
-        } else {
-            const int bb = type == T_Q8_0 ? 34 : 18, cb = type == T_Q8_0 ? 32 : 16;
-            codes.resize((size_t)G * n_cells * (D / 32) * cb);
-            scales.resize((size_t)G * n_cells * (D / 32));
-            for (int c = 0; c < n_cells; c++)
-                for (int g = 0; g < G; g++)
-                    for (int b = 0; b < D / 32; b++) {
-                        const uint8_t *blk = src + (size_t)c * rb + ((size_t)g * (D / 32) + b) * bb;
-                        memcpy(&scales[((size_t)g * n_cells + c) * (D / 32) + b], blk, 2);
-                        memcpy(&codes[(((size_t)g * n_cells + c) * (D / 32) + b) * cb], blk + 2, (size_t)cb);
-                    }
-        }
-    };
+    auto fill = [&](int type, const void *rows, std::vector<uint8_t> &codes, std::vector<uint16_t> &scales) { cache_planes_from_rows(type, rows, G, D, n_cells, codes, scales); };
     if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("bad cache type"); return MI355_ERR_ARG; }
     std::vector<uint8_t> kc, vc;
     std::vector<uint16_t> ks, vs;
@@ -816,29 +841,71 @@ int mi355_op_attn_step(const float *q, const float *k_new, const float *v_new, i
     if (att_out && !datt.down(att_out, (size_t)K * 4)) return MI355_ERR_HIP;
     if (out && !dout.down(out, (size_t)E * 4)) return MI355_ERR_HIP;
     // the cache row the step wrote, back in ggml block layout
-    auto row_back = [&](int type, DevBuf &codes, DevBuf &scales, void *dst) -> bool {
-        if (!dst) return true;
-        uint8_t *o8 = (uint8_t *)dst;
-        for (int g = 0; g < G; g++) {
-            const size_t rowi = (size_t)g * n_cells + tok_cell;
-            if (type == T_F16) {
-                if (hipMemcpy(o8 + (size_t)g * D * 2, (uint8_t *)codes.p + rowi * D * 2, (size_t)D * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
-            } else {
-                const int bb = type == T_Q8_0 ? 34 : 18, cb = type == T_Q8_0 ? 32 : 16;
-                std::vector<uint8_t> c((size_t)(D / 32) * cb);
-                std::vector<uint16_t> sc((size_t)D / 32);
-                if (hipMemcpy(c.data(), (uint8_t *)codes.p + rowi * (D / 32) * cb, c.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
-                if (hipMemcpy(sc.data(), (uint8_t *)scales.p + rowi * (D / 32) * 2, sc.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
-                for (int b = 0; b < D / 32; b++) {
-                    uint8_t *blk = o8 + ((size_t)g * (D / 32) + b) * bb;
-                    memcpy(blk, &sc[(size_t)b], 2);
-                    memcpy(blk + 2, &c[(size_t)b * cb], (size_t)cb);
-                }
-            }
-        }
-        return true;
-    };
+    auto row_back = [&](int type, DevBuf &codes, DevBuf &scales, void *dst) -> bool { return cache_row_to_ggml(type, codes, scales, G, D, n_cells, tok_cell, dst); };
     if (!row_back(type_k, dk, dks, k_row_out) || !row_back(type_v, dv, dvs, v_row_out)) return MI355_ERR_HIP;
+    return MI355_OK;
+}
+
+// The decode attention of ONE token of a qwen2 / qwen3 file as the decode path launches it (test entry): NEOX rope of q and of the token's K row - each head
+// RMS-normalised and multiplied by q_norm / k_norm first where they are given (qwen3; null: no norm, the qwen2 path) - the K / V row quantised into the cache,
+// attention over the visible cells and the merge of the chunk partials.  mode 1: the single-launch form of a single-token step (tickets, the last workgroup
+// merges); 0: the store-fused form of a batched step (K / V stored inside the attention launch, merged by its own launch); 2: the generic path of prompt
+// batches (rope_kv_store, then the split attention on the rotated q).  Cache arguments and outputs as mi355_op_attn_step.
+int mi355_op_attn_decode_neox(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
+                              const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos, int32_t tok_cell, float rope_base, float scale,
+                              const float *q_norm, const float *k_norm, float eps, int32_t mode, float *att_out, void *k_row_out, void *v_row_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if ((D != 64 && D != 128) || G < 1 || H % G || n_cells < 1 || tok_cell < 0 || tok_cell >= n_cells || mode < 0 || mode > 2) { fail("bad geometry / mode"); return MI355_ERR_ARG; }
+    if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("bad cache type"); return MI355_ERR_ARG; }
+    const size_t K = (size_t)H * D, kv_dim = (size_t)G * D;
+    std::vector<uint8_t> kc, vc;
+    std::vector<uint16_t> ks, vs;
+    cache_planes_from_rows(type_k, k, G, D, n_cells, kc, ks);
+    cache_planes_from_rows(type_v, v, G, D, n_cells, vc, vs);
+    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dv(vc.size()), dvs(vs.size() * 2 + 16), dqn((size_t)D * 4), dkn_w((size_t)D * 4);
+    DevBuf dq(K * 4), dkn(kv_dim * 4), dvn(kv_dim * 4), datt(K * 4), dcp((size_t)n_cells * 4), dcs((size_t)n_cells * 8), dtp(16), dts(16), dn(16), dcell(16);
+    DevBuf dcnt(64 * ATT_SYNC_STRIDE * 4), dcsb((size_t)D * 4 + 64);
+    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dq.up(q, K * 4) || !dkn.up(k_new, kv_dim * 4) || !dvn.up(v_new, kv_dim * 4) || !datt.p ||
+        (q_norm && !dqn.up(q_norm, (size_t)D * 4)) || (k_norm && !dkn_w.up(k_norm, (size_t)D * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    if (!ks.empty()) dks.up(ks.data(), ks.size() * 2);
+    if (!vs.empty()) dvs.up(vs.data(), vs.size() * 2);
+    std::vector<uint64_t> seqm((size_t)n_cells, 1ull);
+    const int32_t tseq = 0, nkv = n_cells;
+    dcp.up(cell_pos, (size_t)n_cells * 4); dcs.up(seqm.data(), (size_t)n_cells * 8); dtp.up(&tok_pos, 4); dts.up(&tseq, 4); dn.up(&nkv, 4); dcell.up(&tok_cell, 4);
+    RopeArgs ra{};
+    ra.n_rot = D; ra.freq_base = rope_base; ra.freq_scale = 1.0f; ra.freq_factors = nullptr; ra.neox = 1;
+    ra.q_norm = q_norm ? dqn.as<float>() : nullptr; ra.k_norm = k_norm ? dkn_w.as<float>() : nullptr; ra.qk_eps = eps;
+    hipError_t e = launch_rope_table(dtp.as<int32_t>(), 1, ra, dcsb.as<float>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "rope_table");
+    AttnArgs a{};
+    a.q = dq.as<float>(); a.out = datt.as<float>();
+    a.kv.k = dk.as<uint8_t>(); a.kv.kd = dks.as<uint16_t>(); a.kv.v = dv.as<uint8_t>(); a.kv.vd = dvs.as<uint16_t>();
+    a.type_k = type_k; a.type_v = type_v; a.T = 1; a.H = H; a.G = G; a.D = D; a.n_ctx = n_cells;
+    a.cell_pos = dcp.as<int32_t>(); a.cell_seq = dcs.as<uint64_t>(); a.tok_pos = dtp.as<int32_t>(); a.tok_seq = dts.as<int32_t>();
+    a.n_kv_dev = dn.as<int32_t>(); a.n_kv_max = n_cells; a.scale = scale;
+    if (mode == 2) {
+        e = launch_rope_kv_store(dq.as<float>(), dkn.as<float>(), dvn.as<float>(), 1, H, G, D, dtp.as<int32_t>(), dcell.as<int32_t>(), ra, a.kv, type_k, type_v, n_cells,
+                                 dcsb.as<float>(), nullptr);
+        if (e != hipSuccess) return hip_fail(e, "rope_kv_store");
+        a.splits = flash_attn_pick_splits(1, G, n_cells);
+        a.pf_splits = flash_attn_prefill_splits(1, H, G, D, n_cells);
+        DevBuf part(flash_attn_workspace_floats(1, H, D, std::max(a.splits, a.pf_splits)) * 4);
+        a.part = part.as<float>();
+        e = launch_flash_attn(a, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) return hip_fail(e, "flash_attn");
+    } else {
+        a.splits = flash_attn_decode_splits(n_cells);
+        DevBuf part(flash_attn_workspace_floats(1, H, D, a.splits) * 4);
+        a.part = part.as<float>();
+        if (!flash_attn_decode_applicable(a, ra) || (mode == 1 && !flash_attn_decode_fused_applicable(a, ra))) { fail("the decode attention has no form for this shape"); return MI355_ERR_ARG; }
+        if (mode == 1) e = launch_flash_attn_decode_fused(a, dcsb.as<float>(), ra, dkn.as<float>(), dvn.as<float>(), dcell.as<int32_t>(), dcnt.as<unsigned>(), nullptr);
+        else e = launch_flash_attn_decode(a, dcsb.as<float>(), ra, nullptr, dkn.as<float>(), dvn.as<float>(), dcell.as<int32_t>());
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) return hip_fail(e, "flash_attn_decode");
+    }
+    if (att_out && !datt.down(att_out, K * 4)) return MI355_ERR_HIP;
+    if (!cache_row_to_ggml(type_k, dk, dks, G, D, n_cells, tok_cell, k_row_out) || !cache_row_to_ggml(type_v, dv, dvs, G, D, n_cells, tok_cell, v_row_out)) return MI355_ERR_HIP;
     return MI355_OK;
 }
 

@@ -380,6 +380,7 @@ size_t decode_engine_granule_words(int E, int FF) {      // 8-byte words of the 
 // the shapes the launch exists for: dense llama layer, K-quant tensors the stream kernel has forms for, E <= 4096 (the f32 vector and ffn_down's codes share
 // 16 KiB of LDS behind the ring)
 bool decode_engine_applicable(const EngineLayer &l, int E, int FF) {
+    if (l.qk_norm) return false;                        // (its Q | K | V hand-over has no place for the per-head q / k RMSNorm of qwen3 files)
     if (E % 2048 != 0 || E > 4096 || FF % 1024 != 0) return false;
     const int kbe = E >> 11, kbf = (FF + 2047) >> 11;
     if (!(kbe == 2 && kbf == 7)) return false;          // (FF 11008 / 5632 are no multiples of 1024: those ffn_down tensors have no stream form)

@@ -161,15 +161,16 @@ __global__ __launch_bounds__(MEGA_NT, 2) void decode_mega_kernel(const MegaLayer
 bool experiments_built() { return true; }      // (this file and decode_engine.hip are compiled together or not at all: build.py)
 int mega_blocks() { return 2 * num_cu(); }
 
-bool decode_mega_applicable(int kb_e, int kb_ff, int R, int type_k, int type_v) {
-    return kb_e == 2 && kb_ff == 7 && R == 4 && (type_k == T_Q8_0 || type_k == T_F16) && type_k == type_v;
+bool decode_mega_applicable(int kb_e, int kb_ff, int R, int type_k, int type_v, bool qk_norm) {
+    // (the attention phase rotates q / K without the per-head q / k RMSNorm of qwen3 files)
+    return !qk_norm && kb_e == 2 && kb_ff == 7 && R == 4 && (type_k == T_Q8_0 || type_k == T_F16) && type_k == type_v;
 }
 
 hipError_t launch_decode_mega(const MegaLayer *layers_dev, int n_layer, int kb_e, int kb_ff, const AttnArgs &a, const float *cs_table,
                               int n_rot, const float *knew, const float *vnew, const int32_t *tok_cell, unsigned *counters,
                               unsigned *sync, int *host_flag, unsigned long long *probe, size_t lds_mmvq, hipStream_t st) {
     const int R = a.H / a.G;
-    if (!decode_mega_applicable(kb_e, kb_ff, R, a.type_k, a.type_v) || a.T != 1 || !counters) return hipErrorInvalidValue;
+    if (!decode_mega_applicable(kb_e, kb_ff, R, a.type_k, a.type_v, false) || a.T != 1 || !counters) return hipErrorInvalidValue;
     DecodeFuse fz{};
     fz.knew = knew; fz.vnew = vnew; fz.tok_cell = tok_cell; fz.counters = counters;
     if (a.out_q) fz.q = *a.out_q;

@@ -9,7 +9,7 @@ namespace mi355 {
 bool experiments_built() { return false; }
 
 int mega_blocks() { return 0; }
-bool decode_mega_applicable(int, int, int, int, int) { return false; }
+bool decode_mega_applicable(int, int, int, int, int, bool) { return false; }
 hipError_t launch_decode_mega(const MegaLayer *, int, int, int, const AttnArgs &, const float *, int, const float *, const float *, const int32_t *, unsigned *, unsigned *,
                               int *, unsigned long long *, size_t, hipStream_t) {
     return hipErrorNotSupported;

@@ -96,6 +96,7 @@ bool experiments_built();
 struct EngineLayer {
     MMVQArgs wo, gu, dn, qkv;
     int has_qkv;
+    int qk_norm;     // the layer normalises q / K per head before the rope (qwen3): the engine has no form for it (decode_engine_applicable refuses)
 };
 bool decode_engine_applicable(const EngineLayer &l, int E, int FF);   // on UNPLANNED descriptors (as launch_mmvq_stream would get them)
 void decode_engine_plan(EngineLayer &l);                                // mmvq_stream_plan of the four mat-vecs for num_cu() workgroups
@@ -273,6 +274,12 @@ struct RopeArgs {
     // YaRN: ext_factor 1 mixes the interpolated angle (freq_scale * theta) with the original one per pair, by a ramp over the pair index that falls from 1 at
     // corr_lo to 0 at corr_hi, and multiplies cos / sin by attn_factor * (1 + 0.1 ln(1 / freq_scale)); ext_factor 0 leaves plain (linear) scaling
     float ext_factor = 0.0f, attn_factor = 1.0f, corr_lo = 0.0f, corr_hi = 0.0f;
+    // qwen3 (llm_build_qwen3): every query head and every kv head is RMS-normalised over its own head_dim values and multiplied by these [head_dim] f32
+    // weights BEFORE it is rotated (eps: layer_norm_rms_epsilon).  Null: no norm - the layer's rope is the plain one.  Per layer (runtime.cc sets them);
+    // the kernels that rotate q or K either implement the norm (rope_kv_store, the single-launch / store-fused decode attention) or refuse a layer with it
+    const float *q_norm = nullptr, *k_norm = nullptr;
+    float qk_eps = 0.0f;
+    bool qk_norm() const { return q_norm != nullptr || k_norm != nullptr; }
 };
 
 // rope(q) in place, rope(k) -> K cache, v -> V cache for T tokens
@@ -378,7 +385,7 @@ struct MegaLayer {
 };
 constexpr int MEGA_SYNC_WORDS = 32 * 9;
 int mega_blocks();                                           // grid size: 2 workgroups of 256 threads per CU
-bool decode_mega_applicable(int kb_e, int kb_ff, int R, int type_k, int type_v);
+bool decode_mega_applicable(int kb_e, int kb_ff, int R, int type_k, int type_v, bool qk_norm);   // qk_norm: a layer normalises q / K per head (refused)
 // a: the single-token AttnArgs of launch_flash_attn_decode_fused (kv is taken from the layer descriptors);
 // sync: MEGA_SYNC_WORDS words; [0] and [32 * (1 + g)], g < 8 = barrier counters (0 at launch: launch_kv_meta_set zeroes them),
 // sync[1] = sticky time-out flag (stays 0 on a healthy run; copied to the

@@ -166,13 +166,16 @@ class LlamaConfig:
     n_expert: int = 0
     n_expert_used: int = 0
     big_model: bool = False          # 70B-class rule: attn_v Q4_K -> Q5_K on the non-Q6_K layers
-    arch: str = "llama"              # general.architecture: "qwen2" is the same graph with NEOX rope pairing and (qkv_bias) attention biases
+    arch: str = "llama"              # general.architecture: "qwen2" is the same graph with NEOX rope pairing and (qkv_bias) attention biases;
+                                     # "qwen3" is qwen2's without biases, with a per-head RMSNorm of Q and K before the rope and its own head size
     qkv_bias: bool = False
     extra: dict = field(default_factory=dict)
+    n_head_dim: int = 0              # attention head size (attention.key_length / value_length); 0: n_embd / n_head
+    tied_output: bool = False        # no output.weight: the head reuses token_embd.weight
 
     @property
     def head_dim(self) -> int:
-        return self.n_embd // self.n_head
+        return self.n_head_dim or self.n_embd // self.n_head
 
 
 CONFIGS = {
@@ -185,6 +188,10 @@ CONFIGS = {
                                big_model=True),
     # qwen2 architecture (NEOX rope, Q / K / V biases), 7 query heads per kv head, hidden size and feed-forward width that are no multiples of 1024
     "qwen2-7b": LlamaConfig("Qwen2-7B-Instruct", 3584, 28, 28, 4, 18944, 152064, 1e6, 1e-6, 32768, arch="qwen2", qkv_bias=True),
+    # qwen3 architecture (qwen2's graph without biases, per-head q / k RMSNorm, head size 128): Qwen3-8B's geometry, and Qwen3-4B's (attention width 4096 > n_embd
+    # 2560, tied output)
+    "qwen3-8b": LlamaConfig("Qwen3-8B", 4096, 36, 32, 8, 12288, 151936, 1e6, 1e-6, 40960, arch="qwen3", n_head_dim=128),
+    "qwen3-4b": LlamaConfig("Qwen3-4B", 2560, 36, 32, 8, 9728, 151936, 1e6, 1e-6, 40960, arch="qwen3", n_head_dim=128, tied_output=True),
     # the reference's embedding smoke model (Makefile:6): nomic-embed-text-v1.5's geometry, a bidirectional encoder (general.architecture nomic-bert)
     "nomic-embed": LlamaConfig("nomic-embed-text-v1.5", 768, 12, 12, 12, 3072, 30522, 1000.0, 1e-12, 2048, arch="nomic-bert"),
     # test-sized
@@ -233,6 +240,12 @@ CONFIGS = {
     # a mixture-of-experts file whose expert tensors are wide enough for the weight-stream mat-vec (hidden 2048, rows of >= 1 KiB): 8 experts, 2 used
     "tiny-moe-e2048": LlamaConfig("tiny-moe-e2048", 2048, 2, 16, 4, 4096, 512, 1e6, 1e-5, 1024, 8, 2),
     "tiny-8b-3l": LlamaConfig("tiny-8b-3l", 4096, 3, 32, 8, 14336, 512, 500000.0, 1e-5, 1024),
+    # general.architecture "qwen3": head size 128 whatever n_embd / n_head is (attention width H * D above, equal to or below n_embd), q / k norms, no biases.
+    # tiny-qwen3: H * D = 1024 > E = 512; the -2l configs: two layers of Qwen3-0.6B's, -4B's and -8B's geometry (the first two with tied output)
+    "tiny-qwen3": LlamaConfig("tiny-qwen3", 512, 3, 8, 2, 1536, 768, 1e6, 1e-6, 1024, arch="qwen3", n_head_dim=128, tied_output=True),
+    "tiny-qwen3-0.6b-2l": LlamaConfig("tiny-qwen3-0.6b-2l", 1024, 2, 16, 8, 3072, 512, 1e6, 1e-6, 1024, arch="qwen3", n_head_dim=128, tied_output=True),
+    "tiny-qwen3-4b-2l": LlamaConfig("tiny-qwen3-4b-2l", 2560, 2, 32, 8, 9728, 512, 1e6, 1e-6, 1024, arch="qwen3", n_head_dim=128, tied_output=True),
+    "tiny-qwen3-8b-2l": LlamaConfig("tiny-qwen3-8b-2l", 4096, 2, 32, 8, 12288, 512, 1e6, 1e-6, 1024, arch="qwen3", n_head_dim=128),
 }
 
 FTYPE_ID = {"f16": 1, "q4_0": 2, "q5_0": 8, "iq4_nl": 25, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18}
@@ -321,17 +334,21 @@ def model_tensors(cfg: LlamaConfig, ftype: str):
             out.append((p + "layer_output_norm.weight", (E,), F32, None))
             out.append((p + "layer_output_norm.bias", (E,), F32, None))
         return out
+    QW = cfg.n_head * cfg.head_dim                 # attention width: n_embd unless the file sets its own head size
     for il in range(cfg.n_layer):
         p = f"blk.{il}."
         out.append((p + "attn_norm.weight", (E,), F32, None))
-        out.append((p + "attn_q.weight", (E, E), tensor_type(cfg, ftype, "attn_q", il), E))
+        out.append((p + "attn_q.weight", (E, QW), tensor_type(cfg, ftype, "attn_q", il), E))
         out.append((p + "attn_k.weight", (E, kv), tensor_type(cfg, ftype, "attn_k", il), E))
         out.append((p + "attn_v.weight", (E, kv), tensor_type(cfg, ftype, "attn_v", il), E))
         if cfg.qkv_bias:
-            out.append((p + "attn_q.bias", (E,), F32, None))
+            out.append((p + "attn_q.bias", (QW,), F32, None))
             out.append((p + "attn_k.bias", (kv,), F32, None))
             out.append((p + "attn_v.bias", (kv,), F32, None))
-        out.append((p + "attn_output.weight", (E, E), tensor_type(cfg, ftype, "attn_output", il), E))
+        if cfg.arch == "qwen3":
+            out.append((p + "attn_q_norm.weight", (cfg.head_dim,), F32, None))
+            out.append((p + "attn_k_norm.weight", (cfg.head_dim,), F32, None))
+        out.append((p + "attn_output.weight", (QW, E), tensor_type(cfg, ftype, "attn_output", il), QW))
         out.append((p + "ffn_norm.weight", (E,), F32, None))
         if cfg.n_expert:
             X = cfg.n_expert
@@ -344,7 +361,8 @@ def model_tensors(cfg: LlamaConfig, ftype: str):
             out.append((p + "ffn_down.weight", (F, E), tensor_type(cfg, ftype, "ffn_down", il), F))
             out.append((p + "ffn_up.weight", (E, F), tensor_type(cfg, ftype, "ffn_up", il), E))
     out.append(("output_norm.weight", (E,), F32, None))
-    out.append(("output.weight", (E, V), tensor_type(cfg, ftype, "output", 0), E))
+    if not cfg.tied_output:
+        out.append(("output.weight", (E, V), tensor_type(cfg, ftype, "output", 0), E))
     return out
 
 
@@ -356,7 +374,7 @@ def weight_bytes_per_token(cfg: LlamaConfig, ftype: str) -> int:
         n = int(np.prod(ne))
         b = row_bytes(t, ne[0]) * (n // ne[0])
         if name == "token_embd.weight":
-            b = row_bytes(t, ne[0])
+            b = row_bytes(t, ne[0]) if not cfg.tied_output else b       # (a tied head reads the whole table)
         elif "_exps." in name:
             b = b // cfg.n_expert * cfg.n_expert_used
         total += b
@@ -386,6 +404,9 @@ def write_synthetic_llama(path: str, cfg: LlamaConfig | str, ftype: str = "q4_k_
     else:
         w.add(f"{a}.attention.layer_norm_rms_epsilon", "f32", cfg.eps)
     w.add(f"{a}.rope.dimension_count", "u32", cfg.head_dim)
+    if cfg.n_head_dim:
+        w.add(f"{a}.attention.key_length", "u32", cfg.head_dim)
+        w.add(f"{a}.attention.value_length", "u32", cfg.head_dim)
     w.add(f"{a}.rope.freq_base", "f32", cfg.rope_base)
     w.add(f"{a}.vocab_size", "u32", cfg.n_vocab)
     if cfg.n_expert:
@@ -466,6 +487,9 @@ def write_synthetic_llama(path: str, cfg: LlamaConfig | str, ftype: str = "q4_k_
             rng = np.random.default_rng([seed, idx])
             if name.endswith(".bias"):
                 return (rng.standard_normal(n) * 0.25).astype("<f4").view(np.uint8)
+            if name.endswith("_q_norm.weight") or name.endswith("_k_norm.weight"):
+                # a wide band: a skipped weight multiply, a norm over the wrong span or after the rope lands far outside every tolerance
+                return rng.uniform(0.25, 2.0, size=n).astype("<f4").view(np.uint8)
             if len(ne) == 1:  # norm weights
                 return rng.uniform(0.9, 1.1, size=n).astype("<f4").view(np.uint8)
             if name == "token_embd.weight":

@@ -51,6 +51,15 @@ static RopeArgs rope_args(const Model &m, bool with_ff) {
     return ra;
 }
 
+// ... and those of one layer: qwen3 layers add their per-head q / k RMSNorm weights (null: none - every other file)
+static RopeArgs layer_rope(const RopeArgs &ra, const LayerWeights &L, float eps) {
+    RopeArgs r = ra;
+    r.q_norm = L.q_norm.valid() ? (const float *)L.q_norm.data : nullptr;
+    r.k_norm = L.k_norm.valid() ? (const float *)L.k_norm.data : nullptr;
+    r.qk_eps = eps;
+    return r;
+}
+
 static bool type_supported(int t) {
     return t == T_F32 || t == T_F16 || t == T_Q8_0 || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q2_K || t == T_Q3_K || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL;
 }
@@ -66,11 +75,15 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
     HParams &hp = m->hp;
     hp.arch = f.get_s("general.architecture", "");
     if (hp.arch.empty()) { err = "general.architecture missing"; status = -102; return nullptr; }
-    // the graph built here is llm_build_llama's: "llama" files (Llama, Mistral, TinyLlama, Mixtral ... all carry that name) and "qwen2"
-    // (the same op order with NEOX rope pairing and Q / K / V biases).  Gemma, Phi-3, BERT-type encoders etc. are other graphs: refused, never run as llama
+    // the graph built here is llm_build_llama's: "llama" files (Llama, Mistral, TinyLlama, Mixtral ... all carry that name), "qwen2"
+    // (the same op order with NEOX rope pairing and Q / K / V biases) and "qwen3" (llm_build_qwen3: qwen2's order without biases, a per-head RMSNorm of Q and K
+    // before the rope, the head size from attention.key_length - the attention width H * D need not be n_embd).  Gemma, Phi-3, qwen3moe, BERT-type encoders
+    // etc. are other graphs: refused, never run as llama.
     // "nomic-bert" (the reference's embedding smoke model, Makefile:6) is the one encoder graph: llm_build_bert's NOMIC_BERT branches (run_layers_encoder)
-    if (hp.arch != "llama" && hp.arch != "qwen2" && hp.arch != "nomic-bert") { err = "unsupported general.architecture '" + hp.arch + "' (this backend builds the llama graph - llama, qwen2 - and the nomic-bert encoder)"; status = -102; return nullptr; }
+    if (hp.arch == "qwen3moe") { err = "unsupported general.architecture 'qwen3moe' (Qwen3 mixture-of-experts files: the qwen3 graph with a routed feed-forward is not built; dense qwen3 is)"; status = -102; return nullptr; }
+    if (hp.arch != "llama" && hp.arch != "qwen2" && hp.arch != "qwen3" && hp.arch != "nomic-bert") { err = "unsupported general.architecture '" + hp.arch + "' (this backend builds the llama graph - llama, qwen2, qwen3 - and the nomic-bert encoder)"; status = -102; return nullptr; }
     hp.encoder = hp.arch == "nomic-bert";
+    hp.qk_norm = hp.arch == "qwen3";
     const std::string a = hp.arch + ".";
     hp.n_embd = (int)f.get_u(a + "embedding_length", 0);
     hp.n_layer = (int)f.get_u(a + "block_count", 0);
@@ -92,11 +105,21 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
         // (1, 2, 4, 8 have the tuned single-launch decode attention and the matrix-core prompt attention; 3, 5, 6, 7 take the general split kernel)
         if (ratio < 1 || ratio > 8) { err = "unsupported query / kv head ratio " + std::to_string(ratio) + " (the attention kernels are built for 1 .. 8)"; status = -102; return nullptr; }
     }
-    if (hp.n_embd % hp.n_head) { err = "embedding_length is not a multiple of attention.head_count"; status = -102; return nullptr; }
+    // (qwen3 sets its head size itself: n_embd / n_head need not be whole)
+    if (!hp.qk_norm && hp.n_embd % hp.n_head) { err = "embedding_length is not a multiple of attention.head_count"; status = -102; return nullptr; }
     if (hp.n_expert < 0 || hp.n_expert > 256 || hp.n_expert_used < 0 || hp.n_expert_used > hp.n_expert || (hp.n_expert > 0 && hp.n_expert_used == 0)) {
         err = "bad expert_count / expert_used_count"; status = -102; return nullptr;
     }
+    // llama / qwen2: n_embd / n_head, whatever attention.key_length says (a llama file whose key_length disagrees - Mistral-Nemo style - is read exactly as
+    // before; the width handling below is the groundwork for it).  qwen3: attention.key_length, which value_length must equal.
     hp.head_dim = hp.n_embd / hp.n_head;
+    if (hp.qk_norm) {
+        const uint64_t kl = f.get_u(a + "attention.key_length", 0), vl = f.get_u(a + "attention.value_length", kl);
+        if (kl == 0) { err = "qwen3 file without attention.key_length"; status = -102; return nullptr; }
+        if (vl != kl) { err = "attention.value_length (" + std::to_string(vl) + ") differs from attention.key_length (" + std::to_string(kl) + "): not supported"; status = -102; return nullptr; }
+        if (kl > 4096) { err = "implausible attention.key_length"; status = -102; return nullptr; }
+        hp.head_dim = (int)kl;
+    }
     hp.n_rot = (int)f.get_u(a + "rope.dimension_count", (uint64_t)hp.head_dim);
     hp.rope_neox = hp.arch != "llama";
     const std::string scaling = f.get_s(a + "rope.scaling.type", "none");
@@ -118,6 +141,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
     } else if (scaling != "none" && scaling != "linear") { err = "unsupported rope.scaling.type " + scaling; status = -102; return nullptr; }
     if (hp.head_dim != 64 && hp.head_dim != 128) { err = "unsupported head_dim " + std::to_string(hp.head_dim); status = -102; return nullptr; }
     if (hp.n_embd % 256) { err = "n_embd must be a multiple of 256"; status = -102; return nullptr; }
+    if (hp.qk_norm && ((int64_t)hp.n_head * hp.head_dim) % 256) { err = "the attention width (head_count x key_length) must be a multiple of 256"; status = -102; return nullptr; }
     // ---- row split: this rank's share of the heads and of the feed-forward width
     const int P = tp_size > 1 ? tp_size : 1, R = tp_size > 1 ? tp_rank : 0;
     hp.n_head_full = hp.n_head; hp.n_head_kv_full = hp.n_head_kv; hp.n_ff_full = hp.n_ff;
@@ -125,6 +149,8 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
     // the exchange steps run whenever the process has a group of that size — also a group of ONE rank, which is how the
     // RCCL calls (and their capture into graphs) are exercised on a single GPU
     hp.tp_exchange = tp_active() && mi355::tp_size() == P && mi355::tp_rank() == R;
+    // (the q / k norm weights and the per-rank path of a qwen3 file are untested under a row split; Qwen3-32B Q4_K_M fits one device)
+    if (P > 1 && hp.qk_norm) { err = "row split (split_mode \"row\" / tp_size > 1) of qwen3 files is not supported: load it on one device"; status = -102; return nullptr; }
     if (P > 1 && !hp.tp_exchange) { err = "tp_size > 1 needs the process's row-split group first (mi355_tp_init with the same rank / size)"; status = -102; return nullptr; }
     if (P > 1) {
         if (R < 0 || R >= P) { err = "tp_rank out of range"; status = -102; return nullptr; }
@@ -234,6 +260,10 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
         want(p + "attn_q.bias", L.bq, false, SPLIT_ROWS);
         want(p + "attn_k.bias", L.bk, false, SPLIT_ROWS);
         want(p + "attn_v.bias", L.bv, false, SPLIT_ROWS);
+        if (hp.qk_norm) {
+            want(p + "attn_q_norm.weight", L.q_norm, true);
+            want(p + "attn_k_norm.weight", L.k_norm, true);
+        }
         want(p + "ffn_norm.weight", L.ffn_norm, true);
         if (hp.n_expert > 0) {
             want(p + "ffn_gate_inp.weight", L.gate_inp, true);
@@ -297,6 +327,9 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
         if (!m->output.name.empty()) shape(m->output, E, f.tensor("output.weight")->ne[1] % P == 0 ? V / P : V, 1, false);
         if (!m->rope_freqs.name.empty() && (m->rope_freqs.K != hp.n_rot / 2 || m->rope_freqs.type != T_F32)) { err = "rope_freqs.weight must hold rope.dimension_count / 2 f32 factors"; fail = true; }
         if (hp.n_rot <= 0 || hp.n_rot > D || (hp.n_rot & 1)) { err = "bad rope.dimension_count"; fail = true; }
+        // (the q / k norm kernels rotate whole heads)
+        if (!fail && hp.qk_norm && hp.n_rot != D) { err = "qwen3 files must rotate whole heads (rope.dimension_count must equal attention.key_length)"; fail = true; }
+        if (!fail && hp.qk_norm && hp.n_expert > 0) { err = "qwen3 files with experts are not supported"; fail = true; }
         int64_t FF = 0;
         for (int il = 0; il < hp.n_layer && !fail; il++) {
             const LayerWeights &L = m->layers[(size_t)il];
@@ -304,6 +337,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             shape(L.wq, E, QW, 1, false); shape(L.wk, E, KVW, 1, false); shape(L.wv, E, KVW, 1, false);
             shape(L.wo, QW, E, 1, false);
             shape(L.bq, QW, 0, 0, true); shape(L.bk, KVW, 0, 0, true); shape(L.bv, KVW, 0, 0, true);
+            shape(L.q_norm, D, 0, 0, true); shape(L.k_norm, D, 0, 0, true);
             if (hp.n_expert > 0) {
                 if (il == 0) FF = L.gate_exps.N;
                 shape(L.gate_inp, E, hp.n_expert, 1, false);
@@ -316,7 +350,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             }
             if (!fail && (FF <= 0 || (hp.n_ff_full > 0 && FF * P != hp.n_ff_full))) { err = "feed-forward tensors do not match feed_forward_length"; fail = true; }
             // norms and biases are read as f32 vectors by the kernels
-            for (const DevTensor *t : {&L.attn_norm, &L.ffn_norm, &L.bq, &L.bk, &L.bv})
+            for (const DevTensor *t : {&L.attn_norm, &L.ffn_norm, &L.bq, &L.bk, &L.bv, &L.q_norm, &L.k_norm})
                 if (!fail && !t->name.empty() && t->type != T_F32) { err = "tensor " + t->name + " must be f32"; fail = true; }
         }
         if (!fail && m->out_norm.type != T_F32) { err = "output_norm.weight must be f32"; fail = true; }
@@ -625,12 +659,15 @@ bool Context::init(std::string &err) {
     d_outrow_ = d_cell_ + Tp;
     d_seqmask_ = (uint64_t *)(d_outrow_ + Tp);
 
+    // rows that hold Q or the attention output are H * D wide, which is n_embd for llama / qwen2 files, less on a row-split rank, and may be more for qwen3
+    // (Qwen3-0.6B: 2048 against 1024; Qwen3-4B: 4096 against 2560).  q_ also takes E-wide results (the encoder's attn_output / ffn_down).
+    const size_t QA = std::max(E, (size_t)hp.n_head * D);
     x_ = (float *)dalloc(T * E * 4);
     xn_ = (float *)dalloc(T * E * 4);
-    q_ = (float *)dalloc(T * E * 4);
+    q_ = (float *)dalloc(T * QA * 4);
     k_ = (float *)dalloc(T * G * D * 4);
     v_ = (float *)dalloc(T * G * D * 4);
-    att_ = (float *)dalloc(T * E * 4);
+    att_ = (float *)dalloc(T * QA * 4);
     ffn_ = (float *)dalloc(T * FF * 4);
     ffn_u_ = (float *)dalloc(T * FF * 4);
     xo_ = (float *)dalloc(T * E * 4);
@@ -662,17 +699,17 @@ bool Context::init(std::string &err) {
     }
     bool ok = true;
     alloc_actq(aq_e_, E, T, true, true, allocs_, device_bytes, ok);
-    alloc_actq(aq_o_, E, T, true, true, allocs_, device_bytes, ok);
+    alloc_actq(aq_o_, QA, T, true, true, allocs_, device_bytes, ok);      // (the attention output's codes: attn_output contracts over H * D)
     alloc_actq(aq_ff_, FF, T, true, true, allocs_, device_bytes, ok);
     const int prep_rows = (int)T * (hp.n_expert > 0 ? std::max(1, (int)hp.n_expert_used) : 1);   // (expert batches: every (token, rank) pair is a row)
-    mmq_bh_ = (int8_t *)dalloc(mmq_prep_bytes((int)std::max(E, FF), prep_rows));
-    mmq_bl_ = (int8_t *)dalloc(mmq_prep_bytes((int)std::max(E, FF), prep_rows));
+    mmq_bh_ = (int8_t *)dalloc(mmq_prep_bytes((int)std::max({E, FF, QA}), prep_rows));     // (block sums of the widest contraction: n_embd, n_ff or H * D)
+    mmq_bl_ = (int8_t *)dalloc(mmq_prep_bytes((int)std::max({E, FF, QA}), prep_rows));
     // partial sums of the K-split prompt contraction: only tensors with few rows split (Q | K | V, attention output, FFN down),
     // up to four ways; tensors that do not fit fall back to an unsplit kernel
     // A launch only splits while its 128 x 256 tiles number fewer than 3/4 of the CUs, and then into ceil(CUs / tiles) <= 4 parts (mmq.hip planes2_split):
     // n_split * tiles < CUs + tiles < 7/4 CUs, i.e. never more than 7/4 * CUs tiles' worth of partial sums whatever the model (58.7 MB on 256 CUs;
     // sized by the widest tensor instead it was 335 MB per context for Llama-3-70B at n_ubatch 2048)
-    mmq_ws_.bytes = std::min((size_t)4 * T * std::max<size_t>(E, (size_t)(hp.n_head + 2 * hp.n_head_kv) * D) * sizeof(float),
+    mmq_ws_.bytes = std::min((size_t)4 * T * std::max<size_t>(QA, (size_t)(hp.n_head + 2 * hp.n_head_kv) * D) * sizeof(float),
                              (size_t)(num_cu() * 7 / 4) * 128 * 256 * sizeof(float));
     mmq_ws_.p = T >= 128 ? (float *)dalloc(mmq_ws_.bytes) : nullptr;
     if (!mmq_ws_.p) mmq_ws_.bytes = 0;
@@ -1056,7 +1093,7 @@ bool Context::mega_prepare() {
     const int E = hp.n_embd, FF = hp.n_ff, H = hp.n_head, G = hp.n_head_kv, D = hp.head_dim;
     if (!mega_env || hp.n_expert > 0 || G <= 0 || H % G != 0 || H * D != E) return false;
     const int kb_e = (E + 2047) >> 11, kb_ff = (FF + 2047) >> 11;
-    if ((E % 2048) != 0 || (FF % 256) != 0 || !decode_mega_applicable(kb_e, kb_ff, H / G, cp.type_k, cp.type_v)) return false;
+    if ((E % 2048) != 0 || (FF % 256) != 0 || !decode_mega_applicable(kb_e, kb_ff, H / G, cp.type_k, cp.type_v, hp.qk_norm)) return false;
     RopeArgs ra = rope_args(*model, false);
     if (ra.neox || (ra.n_rot % 4) != 0 || D != 128 || !kv_store_fast_applicable(G, D, cp.type_k, cp.type_v, ra)) return false;
     auto kq = [](int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K; };
@@ -1213,6 +1250,7 @@ bool Context::engine_prepare() {
         if (L.bq.valid() || L.bk.valid() || L.bv.valid()) return false;
         if (!is_quant(L.wo.type) || act_is_q80(L.wo.type)) return false;
         EngineLayer &m = el[(size_t)il];
+        m.qk_norm = L.q_norm.valid() || L.k_norm.valid() || (il + 1 < hp.n_layer && (model->layers[(size_t)il + 1].q_norm.valid() || model->layers[(size_t)il + 1].k_norm.valid()));
         auto base = [&](MMVQArgs &a, int n_seg, int K, int epi, int fuse, const float *nx, const float *nw, const ActQuant &aq) {
             a = MMVQArgs{};
             a.n_seg = n_seg; a.K = K; a.T = 1; a.epi = epi;
@@ -1335,7 +1373,7 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
     cur_T_ = T;
     const HParams &hp = model->hp;
     const int E = hp.n_embd, FF = hp.n_ff, H = hp.n_head, G = hp.n_head_kv, D = hp.head_dim;
-    RopeArgs ra = rope_args(*model, true);
+    const RopeArgs ra_step = rope_args(*model, true);     // (each layer's: layer_rope)
     const float kq_scale = 1.0f / sqrtf((float)D);
     const int n_kv_max = std::max(n_kv_cap, 1);   // upper bound of occupied cells the kernels are sized for
     att_splits_ = flash_attn_pick_splits(T, G, n_kv_max);
@@ -1355,25 +1393,26 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
             ma.tok_chunks = d_chunks_; ma.tok_nchunks = d_chunks_ + (size_t)64 * chunk_stride_; ma.chunk_stride = chunk_stride_;
             ma.splits = std::max(chunk_cap_, chunk_lmax_);
         }
-        mega = flash_attn_decode_fused_applicable(ma, ra);      // (more than 64 chunks: the per-launch path merges them)
+        mega = flash_attn_decode_fused_applicable(ma, ra_step);      // (more than 64 chunks: the per-launch path merges them)
     }
     // ... or one persistent launch per layer for the mat-vecs between two attention calls (decode_engine.hip)
     const bool engine = T == 1 && !mega && !profile_ && !debug_taps_ && !ub_embd_ && engine_prepare();
     last_layers_engine_ = engine;
     // cos / sin table, cell metadata and the tokens' embedding rows: one launch
-    HIP_TRY(launch_step_setup_embed(d_pos_, T, ra, rope_cs_, d_cell_pos_, d_cell_seq_, d_cell_, d_seqmask_, mega ? d_mega_sync_ : nullptr,
+    HIP_TRY(launch_step_setup_embed(d_pos_, T, ra_step, rope_cs_, d_cell_pos_, d_cell_seq_, d_cell_, d_seqmask_, mega ? d_mega_sync_ : nullptr,
                                     d_step_serial_, model->tok_embd.type, model->tok_embd.data, E, d_tok_, x_, stream_));
     // an embeddings batch: the caller's rows take the place of the looked-up ones (never inside a captured graph: decode_ubatch)
     if (ub_embd_) HIP_TRY(hipMemcpyAsync(x_, ub_embd_, (size_t)T * E * sizeof(float), hipMemcpyHostToDevice, stream_));
     prof_mark("embed");
     last_layers_mega_ = mega;
     if (mega)
-        return launch_decode_mega(d_mega_layers_, hp.n_layer, (E + 2047) >> 11, (FF + 2047) >> 11, ma, rope_cs_, ra.n_rot, k_, v_, d_cell_,
+        return launch_decode_mega(d_mega_layers_, hp.n_layer, (E + 2047) >> 11, (FF + 2047) >> 11, ma, rope_cs_, ra_step.n_rot, k_, v_, d_cell_,
                                   att_counters_, d_mega_sync_, h_mega_flag_, d_mega_probe_, mega_lds_, stream_);
 
     const bool tp = hp.tp_exchange;
     for (int il = 0; il < hp.n_layer; il++) {
         const LayerWeights &L = model->layers[(size_t)il];
+        const RopeArgs ra = layer_rope(ra_step, L, hp.eps);   // (qwen3: with the layer's q / k norm weights; every kernel below either applies them or refuses)
         // --- attention block
         const bool any_f = !is_quant(L.wq.type) || !is_quant(L.wk.type) || !is_quant(L.wv.type);
         const bool need_k = is_quant(L.wq.type) && !act_is_q80(L.wq.type) || is_quant(L.wk.type) && !act_is_q80(L.wk.type) || is_quant(L.wv.type) && !act_is_q80(L.wv.type);
@@ -2250,7 +2289,7 @@ double Context::bench_weight_sweep(int iters, uint64_t *bytes_out, int *launches
         af.type_k = cp.type_k; af.type_v = cp.type_v; af.T = 1; af.H = hp.n_head; af.G = hp.n_head_kv; af.D = hp.head_dim; af.n_ctx = (int)cp.n_ctx;
         af.n_kv_max = 64; af.splits = 1; af.out_q = &aq_o_; af.out_q8k = !act_is_q80(L.wo.type); af.out_q80 = act_is_q80(L.wo.type);
         const MMVQSeg so = make_seg(L.wo, x_, E, x_, nullptr);
-        return !hp.tp_exchange && is_quant(L.wo.type) && attn_out_fused_applicable(af, rope_args(*model, true), so, (int)L.wo.K, EPI_ADD);
+        return !hp.tp_exchange && is_quant(L.wo.type) && attn_out_fused_applicable(af, layer_rope(rope_args(*model, true), L, hp.eps), so, (int)L.wo.K, EPI_ADD);
     };
     // round 6: ... and Q | K | V too where attn_out.hip takes them (run_layers): the sweep then holds neither
     auto qkv_in_attention = [&](const LayerWeights &L) {
@@ -2263,7 +2302,7 @@ double Context::bench_weight_sweep(int iters, uint64_t *bytes_out, int *launches
         QKVFuse qf{};
         qf.seg[0] = make_seg(L.wq, q_, (int)L.wq.N, nullptr, nullptr); qf.seg[1] = make_seg(L.wk, k_, (int)L.wk.N, nullptr, nullptr); qf.seg[2] = make_seg(L.wv, v_, (int)L.wv.N, nullptr, nullptr);
         qf.nx = x_; qf.nw = (const float *)L.attn_norm.data; qf.neps = hp.eps; qf.K = E; qf.gran = d_qkv_gran_;
-        return qkv_attn_out_applicable(af, rope_args(*model, true), so, (int)L.wo.K, EPI_ADD, qf);
+        return qkv_attn_out_applicable(af, layer_rope(rope_args(*model, true), L, hp.eps), so, (int)L.wo.K, EPI_ADD, qf);
     };
     auto sweep = [&](bool count) -> hipError_t {
         for (int il = 0; il < hp.n_layer; il++) {

@@ -35,6 +35,7 @@ struct DevTensor {
 
 struct LayerWeights {
     DevTensor attn_norm, wq, wk, wv, wo, bq, bk, bv;
+    DevTensor q_norm, k_norm;     // qwen3: [head_dim] f32 weights of the per-head RMSNorm of Q and K before the rope (empty otherwise)
     DevTensor ffn_norm, gate, up, down;
     // single-token steps of a feed-forward width the weight stream has no form for (K = 28672: a 16 KB row does not fit the ring pairwise) while half of
     // it has one: the column halves of ffn_down as two tensors of their own, contracted by two launches (x += W_lo a_lo; x += W_hi a_hi).  A second copy
@@ -53,6 +54,7 @@ struct HParams {
     float eps = 1e-5f, rope_base = 10000.0f, rope_scale = 1.0f;
     int rope_neox = 0;
     bool encoder = false;          // bidirectional attention, embeddings only (general.architecture nomic-bert: llm_build_bert)
+    bool qk_norm = false;          // qwen3: per-head RMSNorm of Q and K before the rope (LayerWeights::q_norm / k_norm); head_dim from attention.key_length
     float yarn_ext = 0.0f, yarn_attn = 1.0f, yarn_lo = 0.0f, yarn_hi = 0.0f;   // rope.scaling.type "yarn" (RopeArgs, kernels.h)
     // row split: n_head, n_head_kv and n_ff above are THIS RANK's share; the file's values are kept here.
     // A shard is the same graph with fewer heads and a narrower feed-forward, attn_output and ffn_down contracting over

@@ -24,6 +24,7 @@
 #include <thread>
 #include <vector>
 
+#include "gguf.h"
 #include "hip_backend.h"
 #include "log.h"
 #include "shm_exchange.h"
@@ -328,6 +329,15 @@ std::unique_ptr<IBackend> make_split_backend(const Json &body, BackendInfo &info
     if (body["split_ranks"].is_number()) ranks = (int)body["split_ranks"].as_int();
     if (ranks < 2 || ranks > 8) { err = "split_mode row: needs 2 to 8 ranks (visible devices: " + std::to_string(devices) + "; split_ranks makes ranks share devices, for validation)"; return nullptr; }
     if (tp_active()) { err = "split_mode row: a row-split model is already loaded in this process (one group per process)"; return nullptr; }
+    {   // refused before any worker starts: the architectures whose row split is not built (model_load refuses them too, per rank)
+        std::string path = body.value<std::string>("llama_model_path", "");
+        if (path.empty()) path = body.value<std::string>("model_path", "");
+        GGUFFile f;
+        if (!path.empty() && f.open(path).empty() && f.get_s("general.architecture", "") == "qwen3") {
+            err = "split_mode row: row split of qwen3 files is not supported (load it on one device)";
+            return nullptr;
+        }
+    }
     const int main_gpu = body.value<int>("main_gpu", 0);
     const bool shared = ranks > devices;
     if (shared) log_line(LOG_WARN, "split_mode row: %d ranks on %d device(s) - ranks SHARE devices and exchange through shared memory: a validation set-up, not a deployment", ranks, devices);

@@ -237,6 +237,15 @@ MI355_API int mi355_op_attn_step(const float *q, const float *k_new, const float
                                  const void *k, int32_t type_v, const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos, int32_t tok_cell,
                                  float rope_base, int32_t n_rot, float scale, int32_t type_o, const void *W_o, int64_t n_embd, const float *resid, int32_t fused,
                                  float *att_out, float *out, void *k_row_out, void *v_row_out);
+/* The decode attention of ONE token of a qwen2 / qwen3 file (NEOX rope pairing, head_dim 64 or 128, the whole head rotated): q_norm / k_norm ([head_dim] f32,
+ * either may be NULL = no norm) RMS-normalise every query head / the token's kv heads over their own head_dim values (eps) and multiply by the weight BEFORE the
+ * rope, as llm_build_qwen3 orders it; then the K / V row is quantised into the cache and the token attends over the visible cells.  q, k_new, v_new are
+ * un-rotated.  mode 1: the single-launch form of a single-token step; 0: the store-fused form of a batched step; 2: the generic path of prompt batches
+ * (rope_kv_store + split attention).  k / v, cell_pos, att_out, k_row_out / v_row_out as mi355_op_attn_step. */
+MI355_API int mi355_op_attn_decode_neox(const float *q, const float *k_new, const float *v_new, int32_t n_head, int32_t n_head_kv, int32_t head_dim,
+                                        int32_t type_k, const void *k, int32_t type_v, const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos,
+                                        int32_t tok_cell, float rope_base, float scale, const float *q_norm, const float *k_norm, float eps, int32_t mode,
+                                        float *att_out, void *k_row_out, void *v_row_out);
 
 /* ------------------------------------------------------------------ tokenizer
  * llama_tokenize / llama_token_to_piece as reached through common_tokenize / common_token_to_piece
