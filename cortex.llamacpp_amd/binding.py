@@ -104,6 +104,7 @@ SYMBOLS = {
     "mi355_op_swiglu": (C.c_int, [_vp, _vp, _i64, _vp]),
     "mi355_op_soft_max": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp]),
     "mi355_op_moe_route": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "mi355_op_moe_router": (C.c_int, [_i32, _vp, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mi355_op_flash_attn": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32, _vp]),
     "mi355_op_attn_step": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _i64, _vp, _i32,
                                      _vp, _vp, _vp, _vp]),
@@ -296,6 +297,17 @@ class Backend:
         ids = np.zeros((T, k), np.int32); w = np.zeros((T, k), np.float32)
         self._chk(self.lib.mi355_op_moe_route(_ptr(x), T, ne, k, _ptr(ids), _ptr(w)), "op_moe_route")
         return ids, w
+
+    def moe_router(self, t: int, gate_inp: np.ndarray, n_expert: int, K: int, x: np.ndarray, k: int, fused: bool = True, forced=None):
+        """gate_inp: f32 or f16 rows [n_expert][K] (t = F32 / F16); x [T][K] -> (logits [T][n_expert], ids [T][k], w [T][k])."""
+        gate_inp = np.ascontiguousarray(gate_inp).view(np.uint8).reshape(-1)
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+        T = x.shape[0]
+        f = None if forced is None else np.ascontiguousarray(forced, np.int32).reshape(T, k)
+        logits = np.zeros((T, n_expert), np.float32); ids = np.zeros((T, k), np.int32); w = np.zeros((T, k), np.float32)
+        self._chk(self.lib.mi355_op_moe_router(t, _ptr(gate_inp), n_expert, K, _ptr(x), T, k, int(fused), _ptr(f), _ptr(logits), _ptr(ids), _ptr(w)),
+                  "op_moe_router")
+        return logits, ids, w
 
     def flash_attn(self, q: np.ndarray, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows: np.ndarray, type_v: int,
                    v_rows: np.ndarray, cell_pos, q_pos, scale: float) -> np.ndarray:

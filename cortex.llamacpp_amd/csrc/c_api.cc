@@ -690,13 +690,34 @@ int mi355_op_soft_max(const float *x, const float *mask, int64_t n, int64_t rows
 
 int mi355_op_moe_route(const float *logits, int64_t T, int32_t n_expert, int32_t k, int32_t *ids, float *w) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (T <= 0 || n_expert <= 0 || n_expert > 64 || k <= 0 || k > n_expert) { fail("moe_route: bad shape"); return MI355_ERR_ARG; }
+    if (T <= 0 || n_expert <= 0 || n_expert > 256 || k <= 0 || k > 64 || k > n_expert) { fail("moe_route: bad shape"); return MI355_ERR_ARG; }
     DevBuf dl((size_t)T * n_expert * 4), di((size_t)T * k * 4), dw((size_t)T * k * 4);
     if (!dl.up(logits, (size_t)T * n_expert * 4) || !di.p || !dw.p) return MI355_ERR_OOM;
     hipError_t e = launch_moe_route(dl.as<float>(), (int)T, n_expert, k, di.as<int32_t>(), dw.as<float>(), nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "moe_route");
     return di.down(ids, (size_t)T * k * 4) && dw.down(w, (size_t)T * k * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_moe_router(int32_t type, const void *gate_inp, int32_t n_expert, int64_t K, const float *x, int64_t T, int32_t k, int32_t fused,
+                        const int32_t *forced, float *logits, int32_t *ids, float *w) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if ((type != T_F32 && type != T_F16) || T <= 0 || K <= 0 || n_expert <= 0 || n_expert > 256 || k <= 0 || k > 64 || k > n_expert) {
+        fail("moe_router: bad type or shape"); return MI355_ERR_ARG;
+    }
+    const size_t wb = (size_t)n_expert * K * (type == T_F32 ? 4 : 2), nl = (size_t)T * n_expert * 4, ns = (size_t)T * k * 4;
+    DevBuf dW(wb), dx((size_t)T * K * 4), dl(nl), di(ns), dw(ns), df(forced ? ns : 16);
+    if (!dW.up(gate_inp, wb) || !dx.up(x, (size_t)T * K * 4) || !dl.p || !di.p || !dw.p) return MI355_ERR_OOM;
+    if (forced && !df.up(forced, ns)) return MI355_ERR_OOM;
+    const int32_t *fd = forced ? df.as<int32_t>() : nullptr;
+    // fused: the one-launch router the single-token and prompt steps take for f32 / f16 gate_inp; else mmv_float, then the selection on its logits
+    hipError_t e = fused ? launch_moe_router(type, dW.as<uint8_t>(), n_expert, (int)K, dx.as<float>(), (int)T, k, dl.as<float>(), di.as<int32_t>(), dw.as<float>(), nullptr, fd)
+                         : launch_mmv_float(type, dW.as<uint8_t>(), n_expert, (int)K, dx.as<float>(), (int)T, dl.as<float>(), n_expert, nullptr, nullptr);
+    if (!fused && e == hipSuccess) e = launch_moe_route(dl.as<float>(), (int)T, n_expert, k, di.as<int32_t>(), dw.as<float>(), nullptr, fd);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "moe_router");
+    if (logits && !dl.down(logits, nl)) return MI355_ERR_HIP;
+    return di.down(ids, ns) && dw.down(w, ns) ? MI355_OK : MI355_ERR_HIP;
 }
 
 int mi355_op_flash_attn(const float *q, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,

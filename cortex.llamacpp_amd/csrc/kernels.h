@@ -236,7 +236,7 @@ hipError_t launch_mmf16_xh(const uint8_t *W, int n_rows, int K, const void *xh, 
 hipError_t launch_mmv_float(int type, const uint8_t *W, int n_rows, int K, const float *x, int T, float *y, int ld_out,
                             const float *resid, hipStream_t st);
 
-// MoE router: softmax over n_expert logits per token, top-k (first index wins ties), weights renormalised
+// MoE router: softmax over n_expert <= 256 logits per token, top-k (first index wins ties), weights renormalised; one wave per token
 // forced (nullable, tests): [T][k] expert ids to take instead of the k most probable (weights = this side's probabilities of them, renormalised)
 hipError_t launch_moe_route(const float *logits, int T, int n_expert, int k, int32_t *ids, float *w, hipStream_t st, const int32_t *forced = nullptr);
 // the two above in one launch (f32 / f16 gate_inp), same arithmetic; logits_out may be null

@@ -325,44 +325,85 @@ hipError_t launch_mmv_float(int type, const uint8_t *W, int n_rows, int K, const
 }
 
 // ---------------------------------------------------------------- MoE routing (build_moe_ffn: softmax -> top-k -> renormalise)
+// The selection of one token runs on one wave, for 1 <= n_expert <= 256 and 1 <= k <= 8: lane l owns experts l, l + 64, l + 128, l + 192 (slot i holds
+// expert l + 64 i).  It gives the bits of the single-lane loop it replaced (and of oq_moe_route) for every n_expert:
+//  - mx: a wave max of fmaxf, which is exact and order-free;
+//  - p = expf(lg - mx) per lane; the softmax denominator is the double sum of p in expert order, 0 .. n_expert - 1, which every lane forms from readlanes
+//    (a serial chain of n_expert double adds: the one step whose order fixes its bits);
+//  - inv = (float)(1.0 / sum), p *= inv;
+//  - each of the k picks is a wave arg-max over (p, -e) of the experts not chosen yet: the largest p, the lowest index among equal ones - what a scan in
+//    expert order that replaces its best only on a strictly larger p finds.  The chosen flags are bits of the owning lane, not a 64-bit mask;
+//  - wsum adds the picked p in rank order in f32, and lane j writes rank j's id and p / wsum.
 // forced (test hook, mi355_debug_force_moe_ids): the experts of token t are forced[t * k + j] instead of the k most probable; the weights are still this
 // side's probabilities of those experts, renormalised
-__global__ void moe_route_kernel(const float *logits, int T, int n_expert, int k, int32_t *ids, float *w, const int32_t *forced) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+constexpr int MOE_MAX_EXPERT = 256, MOE_MAX_K = 64;      // (k: one rank per lane; the files in use take 1 .. 8)
+__device__ __forceinline__ void moe_select_wave(const float (&lg)[4], int n_expert, int k, const int32_t *forced, int32_t *ids, float *w) {
+    const int lane = threadIdx.x & 63;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 4; i++) if (lane + 64 * i < n_expert) mx = fmaxf(mx, lg[i]);
+    mx = wave_max(mx);
+    float p[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) p[i] = lane + 64 * i < n_expert ? expf(lg[i] - mx) : 0.0f;
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int n = min(64, n_expert - 64 * i);
+        for (int l = 0; l < n; l++) sum += (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(p[i]), l));
+    }
+    const float inv = (float)(1.0 / sum);
+#pragma unroll
+    for (int i = 0; i < 4; i++) p[i] *= inv;
+    unsigned used = 0;
+    float wsum = 0.0f, my_w = 0.0f;
+    int my_id = 0;
+    for (int j = 0; j < k; j++) {
+        // key: p's bits above (p >= 0, so they order as the floats do), 1024 - e below (a lower index wins a tie); 0: no candidate in this lane
+        unsigned long long key = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int e = lane + 64 * i;
+            const unsigned long long c = ((unsigned long long)__float_as_uint(p[i]) << 32) | (unsigned)(1024 - e);
+            if (e < n_expert && !((used >> i) & 1u) && c > key) key = c;
+        }
+        key = wave_max_u64(key);
+        int best = 1024 - (int)(unsigned)(key & 0xffffffffull);
+        float pb = __uint_as_float((unsigned)(key >> 32));
+        if (forced) {
+            best = forced[j];
+            best = best < 0 ? 0 : best >= n_expert ? n_expert - 1 : best;
+            const int slot = best >> 6;
+            const float v = slot == 0 ? p[0] : slot == 1 ? p[1] : slot == 2 ? p[2] : p[3];
+            pb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), best & 63));
+        }
+        if (lane == (best & 63)) used |= 1u << (best >> 6);
+        if (lane == j) { my_id = best; my_w = pb; }
+        wsum += pb;
+    }
+    if (lane < k) { ids[lane] = my_id; w[lane] = my_w / wsum; }
+}
+// one wave per token, four tokens per workgroup
+__global__ __launch_bounds__(256) void moe_route_kernel(const float *logits, int T, int n_expert, int k, int32_t *ids, float *w, const int32_t *forced) {
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= T) return;
     const float *x = logits + (size_t)t * n_expert;
-    float p[64];
-    float mx = -INFINITY;
-    for (int e = 0; e < n_expert; e++) mx = fmaxf(mx, x[e]);
-    double sum = 0.0;
-    for (int e = 0; e < n_expert; e++) { p[e] = expf(x[e] - mx); sum += (double)p[e]; }
-    const float inv = (float)(1.0 / sum);
-    for (int e = 0; e < n_expert; e++) p[e] *= inv;
-    unsigned long long used = 0;
-    float wsum = 0.0f;
-    for (int j = 0; j < k; j++) {
-        int best = -1;
-        for (int e = 0; e < n_expert; e++)
-            if (!((used >> e) & 1ull) && (best < 0 || p[e] > p[best])) best = e;
-        if (forced) { best = forced[(size_t)t * k + j]; best = best < 0 ? 0 : best >= n_expert ? n_expert - 1 : best; }
-        used |= 1ull << best;
-        ids[(size_t)t * k + j] = best;
-        w[(size_t)t * k + j] = p[best];
-        wsum += p[best];
-    }
-    for (int j = 0; j < k; j++) w[(size_t)t * k + j] /= wsum;
+    float lg[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) lg[i] = lane + 64 * i < n_expert ? x[lane + 64 * i] : 0.0f;
+    moe_select_wave(lg, n_expert, k, forced ? forced + (size_t)t * k : nullptr, ids + (size_t)t * k, w + (size_t)t * k);
 }
 hipError_t launch_moe_route(const float *logits, int T, int n_expert, int k, int32_t *ids, float *w, hipStream_t st, const int32_t *forced) {
-    if (n_expert > 64) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(moe_route_kernel, dim3((T + 63) / 64), dim3(64), 0, st, logits, T, n_expert, k, ids, w, forced);
+    if (n_expert < 1 || n_expert > MOE_MAX_EXPERT || k < 1 || k > MOE_MAX_K || k > n_expert || T <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(moe_route_kernel, dim3((T + 3) / 4), dim3(256), 0, st, logits, T, n_expert, k, ids, w, forced);
     return hipGetLastError();
 }
 // Router of a mixture-of-experts layer in ONE launch: logits = gate_inp . x (the arithmetic of mmv_float_kernel: lane l adds
 // the products k = l, l + 64, ... in a double, waves reduced the same way), then the selection of moe_route_kernel, per
-// token.  Workgroup = token; wave w computes experts w, w + 4, ...; thread 0 selects.  Same bits as the two launches.
+// token.  Workgroup = token; wave w computes experts w, w + 4, ...; wave 0 selects.  Same bits as the two launches.
 __global__ __launch_bounds__(256) void moe_router_kernel(int type, const uint8_t *W, int n_expert, int K, const float *x, int k, float *logits_out,
                                                          int32_t *ids, float *w, const int32_t *forced) {
-    __shared__ float lg[64];
+    __shared__ float lg[MOE_MAX_EXPERT];
     const int t = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float *xr = x + (size_t)t * K;
     constexpr int UN = 16;
@@ -391,31 +432,16 @@ __global__ __launch_bounds__(256) void moe_router_kernel(int type, const uint8_t
         if (lane == 0) { lg[e] = (float)s; if (logits_out) logits_out[(size_t)t * n_expert + e] = (float)s; }
     }
     __syncthreads();
-    if (threadIdx.x != 0) return;
-    float p[64];
-    float mx = -INFINITY;
-    for (int e = 0; e < n_expert; e++) mx = fmaxf(mx, lg[e]);
-    double sum = 0.0;
-    for (int e = 0; e < n_expert; e++) { p[e] = expf(lg[e] - mx); sum += (double)p[e]; }
-    const float inv = (float)(1.0 / sum);
-    for (int e = 0; e < n_expert; e++) p[e] *= inv;
-    unsigned long long used = 0;
-    float wsum = 0.0f;
-    for (int j = 0; j < k; j++) {
-        int best = -1;
-        for (int e = 0; e < n_expert; e++)
-            if (!((used >> e) & 1ull) && (best < 0 || p[e] > p[best])) best = e;
-        if (forced) { best = forced[(size_t)t * k + j]; best = best < 0 ? 0 : best >= n_expert ? n_expert - 1 : best; }
-        used |= 1ull << best;
-        ids[(size_t)t * k + j] = best;
-        w[(size_t)t * k + j] = p[best];
-        wsum += p[best];
-    }
-    for (int j = 0; j < k; j++) w[(size_t)t * k + j] /= wsum;
+    if (wave != 0) return;
+    float v[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) v[i] = lane + 64 * i < n_expert ? lg[lane + 64 * i] : 0.0f;
+    moe_select_wave(v, n_expert, k, forced ? forced + (size_t)t * k : nullptr, ids + (size_t)t * k, w + (size_t)t * k);
 }
 hipError_t launch_moe_router(int type, const uint8_t *W, int n_expert, int K, const float *x, int T, int k, float *logits_out, int32_t *ids, float *w,
                              hipStream_t st, const int32_t *forced) {
-    if (n_expert > 64 || (type != T_F32 && type != T_F16) || T <= 0) return hipErrorInvalidValue;
+    if (n_expert < 1 || n_expert > MOE_MAX_EXPERT || k < 1 || k > MOE_MAX_K || k > n_expert || (type != T_F32 && type != T_F16) || T <= 0)
+        return hipErrorInvalidValue;
     hipLaunchKernelGGL(moe_router_kernel, dim3(T), dim3(256), 0, st, type, W, n_expert, K, x, k, logits_out, ids, w, forced);
     return hipGetLastError();
 }
@@ -433,14 +459,15 @@ hipError_t launch_moe_combine(float *x, const float *eo, const float *w, int T, 
     return hipGetLastError();
 }
 // ---------------------------------------------------------------- grouping by expert (ggml_mul_mat_id with a batch of tokens)
-// One workgroup of 4 waves.  The selections are staged in LDS; wave w owns experts w, w + 4, ...: it walks the selections
+// One workgroup of 4 waves.  The selections are staged in LDS, one byte each (expert indices are below 256: 16 KB for a 2048-token batch at k = 8);
+// wave w owns experts w, w + 4, ...: it walks the selections
 // 64 at a time in (token, rank) order, a ballot marks the ones that chose its expert and a prefix count of the ballot
 // gives each its row: stable, deterministic, no atomics.  (Runs once per layer of a prompt batch: a few microseconds.)
 __global__ __launch_bounds__(256) void moe_group_kernel(const int32_t *ids, int n_sel, int k, int n_expert, int32_t *meta, int32_t *slot_of, int32_t *tok_of) {
-    extern __shared__ int32_t sid[];               // [n_sel]
-    __shared__ int cnt[64], off[65];
+    extern __shared__ uint8_t sid[];               // [n_sel]
+    __shared__ int cnt[MOE_MAX_EXPERT], off[MOE_MAX_EXPERT + 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < n_sel; i += 256) sid[i] = ids[i];
+    for (int i = tid; i < n_sel; i += 256) sid[i] = (uint8_t)ids[i];
     __syncthreads();
     for (int e = wave; e < n_expert; e += 4) {
         int c = 0;
@@ -474,8 +501,8 @@ __global__ __launch_bounds__(256) void moe_group_kernel(const int32_t *ids, int 
     }
 }
 hipError_t launch_moe_group(const int32_t *ids, int T, int k, int n_expert, int32_t *meta, int32_t *slot_of, int32_t *tok_of, hipStream_t st) {
-    if (n_expert > 64 || T * k <= 0 || (size_t)T * k * 4 > 60 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(256), (size_t)T * k * 4, st, ids, T * k, k, n_expert, meta, slot_of, tok_of);
+    if (n_expert < 1 || n_expert > MOE_MAX_EXPERT || T * k <= 0 || (size_t)T * k > 60 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(256), (size_t)T * k, st, ids, T * k, k, n_expert, meta, slot_of, tok_of);
     return hipGetLastError();
 }
 // one workgroup per grouped row: 16-byte copies of the code plane(s), then the small per-block planes

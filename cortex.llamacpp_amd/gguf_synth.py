@@ -167,11 +167,13 @@ class LlamaConfig:
     n_expert_used: int = 0
     big_model: bool = False          # 70B-class rule: attn_v Q4_K -> Q5_K on the non-Q6_K layers
     arch: str = "llama"              # general.architecture: "qwen2" is the same graph with NEOX rope pairing and (qkv_bias) attention biases;
-                                     # "qwen3" is qwen2's without biases, with a per-head RMSNorm of Q and K before the rope and its own head size
+                                     # "qwen3" is qwen2's without biases, with a per-head RMSNorm of Q and K before the rope and its own head size;
+                                     # "qwen3moe" is qwen3's attention with routed experts (n_expert > 0) of width n_ff_exp
     qkv_bias: bool = False
     extra: dict = field(default_factory=dict)
     n_head_dim: int = 0              # attention head size (attention.key_length / value_length); 0: n_embd / n_head
     tied_output: bool = False        # no output.weight: the head reuses token_embd.weight
+    n_ff_exp: int = 0                # width of one expert ({arch}.expert_feed_forward_length, written when set); 0: n_ff
 
     @property
     def head_dim(self) -> int:
@@ -246,6 +248,17 @@ CONFIGS = {
     "tiny-qwen3-0.6b-2l": LlamaConfig("tiny-qwen3-0.6b-2l", 1024, 2, 16, 8, 3072, 512, 1e6, 1e-6, 1024, arch="qwen3", n_head_dim=128, tied_output=True),
     "tiny-qwen3-4b-2l": LlamaConfig("tiny-qwen3-4b-2l", 2560, 2, 32, 8, 9728, 512, 1e6, 1e-6, 1024, arch="qwen3", n_head_dim=128, tied_output=True),
     "tiny-qwen3-8b-2l": LlamaConfig("tiny-qwen3-8b-2l", 4096, 2, 32, 8, 12288, 512, 1e6, 1e-6, 1024, arch="qwen3", n_head_dim=128),
+    # general.architecture "qwen3moe": qwen3's attention, 128 routed experts of which 8 are used, no shared expert; feed_forward_length is the dense width the
+    # file does not use, expert_feed_forward_length the experts'.  Qwen3-30B-A3B's geometry (attention width 32 x 128 = 4096 > n_embd 2048, 8 query heads per
+    # kv head); tiny-qwen3moe: H * D = 1024 > E = 512; tiny-qwen3moe-160e: more experts than 128 and not a multiple of 64; the -2l configs: two layers of
+    # Qwen3-30B-A3B's and Qwen3-235B-A22B's (4096, 64 / 4 heads of 128, experts of 1536) geometry
+    "qwen3-30b-a3b": LlamaConfig("Qwen3-30B-A3B", 2048, 48, 32, 4, 6144, 151936, 1e6, 1e-6, 40960, 128, 8, arch="qwen3moe", n_head_dim=128, n_ff_exp=768),
+    "tiny-qwen3moe": LlamaConfig("tiny-qwen3moe", 512, 3, 8, 2, 1536, 768, 1e6, 1e-6, 1024, 128, 8, arch="qwen3moe", n_head_dim=128, n_ff_exp=256),
+    "tiny-qwen3moe-160e": LlamaConfig("tiny-qwen3moe-160e", 512, 2, 8, 2, 1536, 512, 1e6, 1e-6, 1024, 160, 8, arch="qwen3moe", n_head_dim=128, n_ff_exp=256),
+    "tiny-qwen3moe-30b-2l": LlamaConfig("tiny-qwen3moe-30b-2l", 2048, 2, 32, 4, 6144, 512, 1e6, 1e-6, 1024, 128, 8, arch="qwen3moe", n_head_dim=128,
+                                        n_ff_exp=768),
+    "tiny-qwen3moe-235b-2l": LlamaConfig("tiny-qwen3moe-235b-2l", 4096, 2, 64, 4, 12288, 512, 1e6, 1e-6, 1024, 128, 8, arch="qwen3moe", n_head_dim=128,
+                                         n_ff_exp=1536),
 }
 
 FTYPE_ID = {"f16": 1, "q4_0": 2, "q5_0": 8, "iq4_nl": 25, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18}
@@ -345,13 +358,13 @@ def model_tensors(cfg: LlamaConfig, ftype: str):
             out.append((p + "attn_q.bias", (QW,), F32, None))
             out.append((p + "attn_k.bias", (kv,), F32, None))
             out.append((p + "attn_v.bias", (kv,), F32, None))
-        if cfg.arch == "qwen3":
+        if cfg.arch in ("qwen3", "qwen3moe"):
             out.append((p + "attn_q_norm.weight", (cfg.head_dim,), F32, None))
             out.append((p + "attn_k_norm.weight", (cfg.head_dim,), F32, None))
         out.append((p + "attn_output.weight", (QW, E), tensor_type(cfg, ftype, "attn_output", il), QW))
         out.append((p + "ffn_norm.weight", (E,), F32, None))
         if cfg.n_expert:
-            X = cfg.n_expert
+            X, F = cfg.n_expert, cfg.n_ff_exp or cfg.n_ff
             out.append((p + "ffn_gate_inp.weight", (E, X), F32, E))
             out.append((p + "ffn_gate_exps.weight", (E, F, X), tensor_type(cfg, ftype, "ffn_gate", il), E))
             out.append((p + "ffn_down_exps.weight", (F, E, X), tensor_type(cfg, ftype, "ffn_down", il), F))
@@ -412,6 +425,8 @@ def write_synthetic_llama(path: str, cfg: LlamaConfig | str, ftype: str = "q4_k_
     if cfg.n_expert:
         w.add(f"{a}.expert_count", "u32", cfg.n_expert)
         w.add(f"{a}.expert_used_count", "u32", cfg.n_expert_used)
+    if cfg.n_ff_exp:
+        w.add(f"{a}.expert_feed_forward_length", "u32", cfg.n_ff_exp)
     for k, v in cfg.extra.items():                 # e.g. {"pooling_type": 1, "rope.scaling.type": "yarn", "rope.scaling.factor": 4.0}: extra keys under the architecture prefix
         w.add(f"{a}.{k}", "str" if isinstance(v, str) else "f32" if isinstance(v, float) else "u32", v)
     if with_vocab and cfg.arch == "nomic-bert":

@@ -77,13 +77,14 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
     if (hp.arch.empty()) { err = "general.architecture missing"; status = -102; return nullptr; }
     // the graph built here is llm_build_llama's: "llama" files (Llama, Mistral, TinyLlama, Mixtral ... all carry that name), "qwen2"
     // (the same op order with NEOX rope pairing and Q / K / V biases) and "qwen3" (llm_build_qwen3: qwen2's order without biases, a per-head RMSNorm of Q and K
-    // before the rope, the head size from attention.key_length - the attention width H * D need not be n_embd).  Gemma, Phi-3, qwen3moe, BERT-type encoders
-    // etc. are other graphs: refused, never run as llama.
+    // before the rope, the head size from attention.key_length - the attention width H * D need not be n_embd) and "qwen3moe" (llm_build_qwen3moe: qwen3's
+    // attention with build_moe_ffn's routed feed-forward - softmax gating, top-k, weights renormalised - and no shared expert).  Gemma, Phi-3, BERT-type
+    // encoders etc. are other graphs: refused, never run as llama.
     // "nomic-bert" (the reference's embedding smoke model, Makefile:6) is the one encoder graph: llm_build_bert's NOMIC_BERT branches (run_layers_encoder)
-    if (hp.arch == "qwen3moe") { err = "unsupported general.architecture 'qwen3moe' (Qwen3 mixture-of-experts files: the qwen3 graph with a routed feed-forward is not built; dense qwen3 is)"; status = -102; return nullptr; }
-    if (hp.arch != "llama" && hp.arch != "qwen2" && hp.arch != "qwen3" && hp.arch != "nomic-bert") { err = "unsupported general.architecture '" + hp.arch + "' (this backend builds the llama graph - llama, qwen2, qwen3 - and the nomic-bert encoder)"; status = -102; return nullptr; }
+    if (hp.arch != "llama" && hp.arch != "qwen2" && hp.arch != "qwen3" && hp.arch != "qwen3moe" && hp.arch != "nomic-bert") { err = "unsupported general.architecture '" + hp.arch + "' (this backend builds the llama graph - llama, qwen2, qwen3, qwen3moe - and the nomic-bert encoder)"; status = -102; return nullptr; }
     hp.encoder = hp.arch == "nomic-bert";
-    hp.qk_norm = hp.arch == "qwen3";
+    const bool qwen3moe = hp.arch == "qwen3moe";
+    hp.qk_norm = hp.arch == "qwen3" || qwen3moe;
     const std::string a = hp.arch + ".";
     hp.n_embd = (int)f.get_u(a + "embedding_length", 0);
     hp.n_layer = (int)f.get_u(a + "block_count", 0);
@@ -96,6 +97,14 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
     hp.n_expert_used = (int)f.get_u(a + "expert_used_count", 0);
     hp.n_ctx_train = (int)f.get_u(a + "context_length", 0);
     hp.pooling_type = (int)f.get_u(a + "pooling_type", 0);
+    // qwen3moe: feed_forward_length is the width of a dense layer the file does not have; the experts' width is expert_feed_forward_length (optional: the
+    // tensors' own width stands when it is absent)
+    const std::string ff_key = qwen3moe ? "expert_feed_forward_length" : "feed_forward_length";
+    if (qwen3moe) hp.n_ff = (int)f.get_u(a + ff_key, 0);
+    if (qwen3moe && hp.n_expert <= 0) { err = "qwen3moe file without experts (expert_count missing or 0): dense feed-forward layers under the qwen3moe name are not supported"; status = -102; return nullptr; }
+    if (qwen3moe && (f.tensor("blk.0.ffn_gate.weight") || f.tensor("blk.0.ffn_up.weight") || f.tensor("blk.0.ffn_down.weight"))) {
+        err = "qwen3moe file with dense ffn_gate / ffn_up / ffn_down tensors: not supported (a qwen3moe layer is routed: ffn_gate_inp and *_exps)"; status = -102; return nullptr;
+    }
     if (hp.n_embd <= 0 || hp.n_layer <= 0 || hp.n_head <= 0) { err = "missing hyper-parameters for arch " + hp.arch; status = -102; return nullptr; }
     if (hp.n_layer > 1024 || hp.n_embd > (1 << 20) || hp.n_head > 4096) { err = "implausible hyper-parameters for arch " + hp.arch; status = -102; return nullptr; }
     // the head counts size buffers and pick kernels: check them here, not at the first decode
@@ -149,8 +158,8 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
     // the exchange steps run whenever the process has a group of that size — also a group of ONE rank, which is how the
     // RCCL calls (and their capture into graphs) are exercised on a single GPU
     hp.tp_exchange = tp_active() && mi355::tp_size() == P && mi355::tp_rank() == R;
-    // (the q / k norm weights and the per-rank path of a qwen3 file are untested under a row split; Qwen3-32B Q4_K_M fits one device)
-    if (P > 1 && hp.qk_norm) { err = "row split (split_mode \"row\" / tp_size > 1) of qwen3 files is not supported: load it on one device"; status = -102; return nullptr; }
+    // (the q / k norm weights and the per-rank path of a qwen3 file are untested under a row split; Qwen3-32B Q4_K_M and Qwen3-30B-A3B fit one device)
+    if (P > 1 && hp.qk_norm) { err = "row split (split_mode \"row\" / tp_size > 1) of " + hp.arch + " files is not supported: load it on one device"; status = -102; return nullptr; }
     if (P > 1 && !hp.tp_exchange) { err = "tp_size > 1 needs the process's row-split group first (mi355_tp_init with the same rank / size)"; status = -102; return nullptr; }
     if (P > 1) {
         if (R < 0 || R >= P) { err = "tp_rank out of range"; status = -102; return nullptr; }
@@ -329,7 +338,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
         if (hp.n_rot <= 0 || hp.n_rot > D || (hp.n_rot & 1)) { err = "bad rope.dimension_count"; fail = true; }
         // (the q / k norm kernels rotate whole heads)
         if (!fail && hp.qk_norm && hp.n_rot != D) { err = "qwen3 files must rotate whole heads (rope.dimension_count must equal attention.key_length)"; fail = true; }
-        if (!fail && hp.qk_norm && hp.n_expert > 0) { err = "qwen3 files with experts are not supported"; fail = true; }
+        if (!fail && hp.arch == "qwen3" && hp.n_expert > 0) { err = "qwen3 files with experts are not supported"; fail = true; }
         int64_t FF = 0;
         for (int il = 0; il < hp.n_layer && !fail; il++) {
             const LayerWeights &L = m->layers[(size_t)il];
@@ -348,7 +357,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
                 shape(L.gate, E, FF, 1, false); shape(L.up, E, FF, 1, false);
                 shape(L.down, FF, E, 1, false);
             }
-            if (!fail && (FF <= 0 || (hp.n_ff_full > 0 && FF * P != hp.n_ff_full))) { err = "feed-forward tensors do not match feed_forward_length"; fail = true; }
+            if (!fail && (FF <= 0 || (hp.n_ff_full > 0 && FF * P != hp.n_ff_full))) { err = "feed-forward tensors do not match " + ff_key; fail = true; }
             // norms and biases are read as f32 vectors by the kernels
             for (const DevTensor *t : {&L.attn_norm, &L.ffn_norm, &L.bq, &L.bk, &L.bv, &L.q_norm, &L.k_norm})
                 if (!fail && !t->name.empty() && t->type != T_F32) { err = "tensor " + t->name + " must be f32"; fail = true; }
@@ -1555,7 +1564,9 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
                                          !act_is_q80(L.gate_exps.type) || !act_is_q80(L.up_exps.type), act_is_q80(L.gate_exps.type) || act_is_q80(L.up_exps.type), stream_));
             prep_owner_ = nullptr;
             prof_mark("norm_quant");
-            if (L.gate_inp.type == T_F32 || L.gate_inp.type == T_F16) {
+            // the fused router computes a token's logits in ONE workgroup: the fastest form at 8 experts (4.9 us against 7.0 for the two launches below,
+            // one token, K 2048), the slowest from 64 on (22 / 42 / 82 us at 64 / 128 / 256 experts against 9.4 / 9.5 / 13.2); the two give the same bits
+            if ((L.gate_inp.type == T_F32 || L.gate_inp.type == T_F16) && hp.n_expert <= 8) {
                 HIP_TRY(launch_moe_router(L.gate_inp.type, L.gate_inp.data, hp.n_expert, E, xn_, T, hp.n_expert_used, router_, moe_ids_, moe_w_, stream_,
                                           moe_forced_T_ == T ? d_moe_forced_ + (size_t)il * T * hp.n_expert_used : nullptr));
             } else {

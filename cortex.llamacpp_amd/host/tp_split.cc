@@ -333,8 +333,9 @@ std::unique_ptr<IBackend> make_split_backend(const Json &body, BackendInfo &info
         std::string path = body.value<std::string>("llama_model_path", "");
         if (path.empty()) path = body.value<std::string>("model_path", "");
         GGUFFile f;
-        if (!path.empty() && f.open(path).empty() && f.get_s("general.architecture", "") == "qwen3") {
-            err = "split_mode row: row split of qwen3 files is not supported (load it on one device)";
+        const std::string arch = !path.empty() && f.open(path).empty() ? f.get_s("general.architecture", "") : "";
+        if (arch == "qwen3" || arch == "qwen3moe") {
+            err = "split_mode row: row split of " + arch + " files is not supported (load it on one device)";
             return nullptr;
         }
     }

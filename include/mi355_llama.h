@@ -221,6 +221,12 @@ MI355_API int mi355_op_soft_max(const float *x, const float *mask, int64_t n, in
 /* build_moe_ffn's expert selection: softmax over n_expert router logits per token, the k largest (first index wins ties), weights
    renormalised; ids [T][k], w [T][k] */
 MI355_API int mi355_op_moe_route(const float *logits, int64_t T, int32_t n_expert, int32_t k, int32_t *ids, float *w);
+/* build_moe_ffn's router and selection together: logits = ggml_mul_mat(ffn_gate_inp, cur) for T tokens of x [T][K] against gate_inp [n_expert][K]
+   (type f32 or f16), then the selection of mi355_op_moe_route; n_expert <= 256.  fused = 1: the one launch the decode path takes; 0: the mat-vec, then the
+   selection (the same bits).  forced (nullable): [T][k] expert ids to take instead (weights: their probabilities, renormalised).  logits [T][n_expert]
+   (nullable), ids [T][k], w [T][k] */
+MI355_API int mi355_op_moe_router(int32_t type, const void *gate_inp, int32_t n_expert, int64_t K, const float *x, int64_t T, int32_t k, int32_t fused,
+                                  const int32_t *forced, float *logits, int32_t *ids, float *w);
 /* flash_attn_ext for T query tokens: K/V given as ggml-layout rows [n_cells][n_head_kv*head_dim] of type_k/type_v;
  * visibility: cell c is visible to token t iff cell_pos[c] >= 0 && cell_pos[c] <= q_pos[t]. */
 MI355_API int mi355_op_flash_attn(const float *q, int64_t T, int32_t n_head, int32_t n_head_kv, int32_t head_dim,
