@@ -10,6 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 2, 8, 12, 13, 14, 15
 Q2_K, Q3_K = 10, 11
 Q5_0, IQ4_NL = 6, 20
+IQ4_XS = 23
 
 
 class MI355Error(RuntimeError):

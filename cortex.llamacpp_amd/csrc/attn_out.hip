@@ -1221,6 +1221,7 @@ __device__ __forceinline__ void ao_body(const AttnArgs &a, const float *cs_table
                 case T_Q5_K: qf_decode<T_Q5_K, KB>(qr, f, smem + lay.qkv, AL, sy, tag, wave, lane); break;
                 case T_Q6_K: qf_decode<T_Q6_K, KB>(qr, f, smem + lay.qkv, AL, sy, tag, wave, lane); break;
                 case T_Q8_0: qf_decode<T_Q8_0, KB>(qr, f, smem + lay.qkv, AL, sy, tag, wave, lane); break;
+                case T_IQ4_XS: qf_decode<T_IQ4_XS, KB>(qr, f, smem + lay.qkv, AL, sy, tag, wave, lane); break;
                 default: break;
             }
         }
@@ -1297,6 +1298,7 @@ __device__ __forceinline__ void ao_body(const AttnArgs &a, const float *cs_table
             case T_Q4_K: ao_decode<T_Q4_K>(o, smem + lay.wo, AL, b0, nrw, wave, lane, rs0, rs1); break;
             case T_Q5_K: ao_decode<T_Q5_K>(o, smem + lay.wo, AL, b0, nrw, wave, lane, rs0, rs1); break;
             case T_Q6_K: ao_decode<T_Q6_K>(o, smem + lay.wo, AL, b0, nrw, wave, lane, rs0, rs1); break;
+            case T_IQ4_XS: ao_decode<T_IQ4_XS>(o, smem + lay.wo, AL, b0, nrw, wave, lane, rs0, rs1); break;
             default: break;
         }
     }
@@ -1414,6 +1416,7 @@ __global__ __launch_bounds__(AO_NT) void attn_out_kernel(const AttnArgs a, const
             case T_Q4_K: ao_decode<T_Q4_K>(o, smem, AL, b0, nrw, wave, lane, rs0, rs1); break;
             case T_Q5_K: ao_decode<T_Q5_K>(o, smem, AL, b0, nrw, wave, lane, rs0, rs1); break;
             case T_Q6_K: ao_decode<T_Q6_K>(o, smem, AL, b0, nrw, wave, lane, rs0, rs1); break;
+            case T_IQ4_XS: ao_decode<T_IQ4_XS>(o, smem, AL, b0, nrw, wave, lane, rs0, rs1); break;
             default: break;
         }
     }
@@ -1481,7 +1484,7 @@ bool attn_out_fused_applicable(const AttnArgs &a, const RopeArgs &ra, const MMVQ
     const int gp = (R * a.D) % 256 == 0 ? 1 : 2;
     if (a.G % gp != 0 || a.G / gp > 64) return false;
     if (!a.out_q || !a.out_q8k || a.out_q80) return false;
-    if (wo.type != T_Q4_K && wo.type != T_Q5_K && wo.type != T_Q6_K) return false;
+    if (wo.type != T_Q4_K && wo.type != T_Q5_K && wo.type != T_Q6_K && wo.type != T_IQ4_XS) return false;
     if (K != a.H * a.D || (K % 256) != 0 || K > 8192 || wo.expert_sel) return false;
     if ((wo.row_bytes % 16) != 0 || (reinterpret_cast<uintptr_t>(wo.W) & 15) != 0) return false;
     if (epi != EPI_ADD && epi != EPI_STORE) return false;
@@ -1619,7 +1622,7 @@ static QFPlan qf_plan(const AttnArgs &a, const MMVQSeg &wo, int K, const QKVFuse
     if ((reinterpret_cast<uintptr_t>(q.nx) & 15) != 0 || (reinterpret_cast<uintptr_t>(q.nw) & 15) != 0) return p;
     for (int s = 0; s < 3; s++) {
         const MMVQSeg &g = q.seg[s];
-        if (g.type != T_Q4_K && g.type != T_Q5_K && g.type != T_Q6_K && g.type != T_Q8_0) return p;    // (Q8_0: attn_k / attn_v of 8-expert files)
+        if (g.type != T_Q4_K && g.type != T_Q5_K && g.type != T_Q6_K && g.type != T_Q8_0 && g.type != T_IQ4_XS) return p;    // (Q8_0: attn_k / attn_v of 8-expert files)
         if (g.expert_sel || (g.row_bytes % 16) != 0 || g.row_bytes > 0xffffffffull || (reinterpret_cast<uintptr_t>(g.W) & 15) != 0) return p;
     }
     const int nwg0 = std::min(num_cu(), (wo.n_rows + 1) / 2);

@@ -46,6 +46,17 @@ __global__ void repack_q3k_kernel(const uint8_t *src, uint8_t *dst, int nb, size
     else if (i < 108) d[(size_t)nb * 96 + (size_t)sb * 12 + (i - 96)] = v;
     else d[(size_t)nb * 108 + (size_t)sb * 2 + (i - 108)] = v;
 }
+// IQ4_XS block: d 2 | scales_h 2 | scales_l 4 | qs 128 -> planes qs | scales_l | scales_h | d
+__global__ void repack_iq4xs_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
+    const int row = blockIdx.y, sb = blockIdx.x, i = threadIdx.x;   // 192 threads, 136 used
+    if (i >= 136) return;
+    const uint8_t v = src[((size_t)row * nb + sb) * 136 + i];
+    uint8_t *d = dst + (size_t)row * dst_row;
+    if (i < 2) d[(size_t)nb * 134 + (size_t)sb * 2 + i] = v;
+    else if (i < 4) d[(size_t)nb * 132 + (size_t)sb * 2 + (i - 2)] = v;
+    else if (i < 8) d[(size_t)nb * 128 + (size_t)sb * 4 + (i - 4)] = v;
+    else d[(size_t)sb * 128 + (i - 8)] = v;
+}
 // 32-element blocks with a 16-byte nibble field: Q4_0 / IQ4_NL (d | qs) and Q5_0 (d | qh | qs) -> planes qs | [qh] | d
 __global__ void repack_nib32_kernel(const uint8_t *src, uint8_t *dst, int nblk, int K, size_t dst_row, int bsz) {
     const int row = blockIdx.y;
@@ -80,6 +91,12 @@ hipError_t launch_repack_rows(int type, const uint8_t *src, uint8_t *dst, int64_
                                                    src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
             else hipLaunchKernelGGL(repack_q3k_kernel, dim3((unsigned)(K >> 8), nr), dim3(128), 0, st,
                                     src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
+        }
+    } else if (type == T_IQ4_XS) {
+        for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
+            const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);
+            hipLaunchKernelGGL(repack_iq4xs_kernel, dim3((unsigned)(K >> 8), nr), dim3(192), 0, st,
+                               src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
         }
     } else if (type == T_Q6_K) {
         for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {

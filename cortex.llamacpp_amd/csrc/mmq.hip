@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "quant_dev.h"
 
 namespace mi355 {
 
@@ -774,6 +775,46 @@ __global__ __launch_bounds__(256) void mmq_expand_small_kernel(const uint8_t *W,
         u32x4 m = {0, 0, 0, 0};
         if (TYPE == T_Q2_K) { m.x = *reinterpret_cast<const uint32_t *>(r + (size_t)nb * 80 + (size_t)sb * 4); m.y = mn_lo; m.z = mn_hi; m.w = 1u; }
         else m.x = *reinterpret_cast<const uint16_t *>(r + (size_t)nb * 108 + (size_t)sb * 2);
+        *reinterpret_cast<u32x4 *>(blk + 16384 + n * 16) = m;
+    }
+}
+// IQ4_XS into the signed (Q6_K) plane format: p = (ls - 32) * level, within +-4064 (32 * 127), 32-weight sub-blocks with one scale, no mins.  Lane (n, kg)
+// takes elements 32 J + 16 kg .. + 15 of K-step J: nibble kg of code bytes 16 J .. 16 J + 15; the f16 d goes where the fold reads Q6_K's.
+// device rows (dev_common.h): [qs nb*128][scales_l nb*4][scales_h nb*2][d nb*2]
+__global__ __launch_bounds__(256) void mmq_expand_iq4xs_kernel(const uint8_t *W, size_t row_bytes, int n_rows, int nb, int n_rt, uint8_t *planes) {
+    const int lane = threadIdx.x & 63;
+    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);     // (row tile, super-block)
+    if (idx >= n_rt * nb) return;
+    const int rt = idx / nb, sb = idx - rt * nb;
+    const int n = lane & 31, kg = lane >> 5;
+    int row = rt * 32 + n;
+    if (row >= n_rows) row = n_rows - 1;
+    const uint8_t *r = W + (size_t)row * row_bytes;
+    uint8_t *blk = planes + (size_t)idx * PL_BLOCK;
+    const uint32_t sl = *reinterpret_cast<const uint32_t *>(r + (size_t)nb * 128 + (size_t)sb * 4);
+    const uint32_t sh = *reinterpret_cast<const uint16_t *>(r + (size_t)nb * 132 + (size_t)sb * 2);
+#pragma unroll
+    for (int J = 0; J < 8; J++) {
+        const u32x4 qv = ldg16(r + (size_t)sb * 128 + 16 * J);
+        const int s = iq4xs_scale(sl, sh, J);
+        const uint32_t cw[4] = {qv.x, qv.y, qv.z, qv.w};
+        uint32_t hv[4], lv[4];
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            uint32_t hx = 0, lx = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int p = s * iq4nl_value((int)((cw[w] >> (8 * b + 4 * kg)) & 0xfu));
+                hx |= (uint32_t)((p >> 6) & 0xff) << (8 * b); lx |= (uint32_t)(p & 63) << (8 * b);
+            }
+            hv[w] = hx; lv[w] = lx;
+        }
+        *reinterpret_cast<u32x4 *>(blk + (J * 2) * 1024 + lane * 16) = u32x4{hv[0], hv[1], hv[2], hv[3]};
+        *reinterpret_cast<u32x4 *>(blk + (J * 2 + 1) * 1024 + lane * 16) = u32x4{lv[0], lv[1], lv[2], lv[3]};
+    }
+    if (kg == 0) {
+        u32x4 m = {0, 0, 0, 0};
+        m.x = *reinterpret_cast<const uint16_t *>(r + (size_t)nb * 134 + (size_t)sb * 2);
         *reinterpret_cast<u32x4 *>(blk + 16384 + n * 16) = m;
     }
 }
@@ -1693,7 +1734,7 @@ hipError_t launch_mmq_ksplit(int type, const uint8_t *W, size_t row_bytes, int n
 }
 
 size_t mmq_planes_bytes(int type, int64_t n_rows, int K) {
-    if ((type != T_Q4_K && type != T_Q5_K && type != T_Q6_K && type != T_Q2_K && type != T_Q3_K) || (K % 256) != 0) return 0;
+    if ((type != T_Q4_K && type != T_Q5_K && type != T_Q6_K && type != T_Q2_K && type != T_Q3_K && type != T_IQ4_XS) || (K % 256) != 0) return 0;
     return (size_t)((n_rows + 31) / 32) * (size_t)(K >> 8) * PL_BLOCK;
 }
 
@@ -1706,6 +1747,7 @@ hipError_t launch_mmq_expand(int type, const uint8_t *W, size_t row_bytes, int n
         case T_Q6_K: hipLaunchKernelGGL(mmq_expand_kernel<T_Q6_K>, grid, dim3(256), 0, st, W, row_bytes, n_rows, nb, n_rt, planes); break;
         case T_Q2_K: hipLaunchKernelGGL(mmq_expand_small_kernel<T_Q2_K>, grid, dim3(256), 0, st, W, row_bytes, n_rows, nb, n_rt, planes); break;
         case T_Q3_K: hipLaunchKernelGGL(mmq_expand_small_kernel<T_Q3_K>, grid, dim3(256), 0, st, W, row_bytes, n_rows, nb, n_rt, planes); break;
+        case T_IQ4_XS: hipLaunchKernelGGL(mmq_expand_iq4xs_kernel, grid, dim3(256), 0, st, W, row_bytes, n_rows, nb, n_rt, planes); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -1778,7 +1820,7 @@ hipError_t launch_mmq_planes_swiglu(int type, const uint8_t *planes_gate, const 
 // the grouped (all experts, one launch) forms: `rows_max` = rows of the grouped arrays (tokens x experts used), meta = moe_group_kernel's counts and offsets
 bool mmq_planes_moe_ok(int type, int n_rows, int K) {
     static const bool env_on = !(getenv("MI355_MOE_GROUPED_LAUNCH") && getenv("MI355_MOE_GROUPED_LAUNCH")[0] == '0');
-    return env_on && (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K) && mmq_planes_bytes(type, n_rows, K) != 0 && (n_rows % 128) == 0 && (K % 256) == 0;
+    return env_on && (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_IQ4_XS) && mmq_planes_bytes(type, n_rows, K) != 0 && (n_rows % 128) == 0 && (K % 256) == 0;
 }
 hipError_t launch_mmq_planes_swiglu_moe(int type, const uint8_t *planes_gate, const uint8_t *planes_up, size_t plane_stride, int n_expert, const int32_t *meta,
                                         int n_rows, int K, int rows_max, const ActQuant &q, float *out, int ld_out, hipStream_t st) {

@@ -356,6 +356,52 @@ template <> struct Item<T_Q3_K> {
     }
 };
 
+// ---- IQ4_XS : device row planes [qs nb*128][scales_l nb*4][scales_h nb*2][d nb*2].  Lane v of a super-block owns sub-block v (32 elements): its 16 code
+// bytes (elements 0..15 in the low nibbles, 16..31 in the high ones) against activation codes 32 v .. 32 v + 31; levels from IQ4_NL's code book (v_perm);
+// per sub-block the integer (ls - 32) * sum level * q8, no mins (ggml_vec_dot_iq4_xs_q8_K) ----------
+template <> struct Item<T_IQ4_XS> {
+    uint4 hdr;                        // x: scales_l (4 bytes), y: scales_h, z: d (f16)
+    static constexpr int EPP = 2048;
+    uint4 q;
+    int ls;                           // (6-bit scale - 32) of this lane's sub-block
+    float d;
+    int sb;
+    bool valid;
+    __device__ __forceinline__ void load(const uint8_t *row, int K, int pass, int lane) {
+        const int nb = K >> 8;
+        sb = pass * 8 + (lane >> 3);
+        valid = sb < nb;
+        if (valid) {
+            q = ld16w(row + (size_t)sb * 128 + 16 * (lane & 7));
+            hdr.x = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 128 + (size_t)sb * 4);
+            hdr.y = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 132 + (size_t)sb * 2);
+            hdr.z = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 134 + (size_t)sb * 2);
+        }
+    }
+    __device__ __forceinline__ void prep(int lane) {
+        if (!valid) return;
+        d = h2f((uint16_t)hdr.z);
+        ls = iq4xs_scale(hdr.x, hdr.y, lane & 7);
+    }
+    __device__ __forceinline__ void ints(const ActLds &A, int t, int lane, int &isum, int &msum) const {
+        const int8_t *a = A.qs + (size_t)t * A.K + sb * 256 + 32 * (lane & 7);
+        const uint4 lo = ld16(a), hi = ld16(a + 16);
+        int s = 0;
+        s = dot4(iq4nl_levels4(q.x & 0x0f0f0f0fu), lo.x, s); s = dot4(iq4nl_levels4((q.x >> 4) & 0x0f0f0f0fu), hi.x, s);
+        s = dot4(iq4nl_levels4(q.y & 0x0f0f0f0fu), lo.y, s); s = dot4(iq4nl_levels4((q.y >> 4) & 0x0f0f0f0fu), hi.y, s);
+        s = dot4(iq4nl_levels4(q.z & 0x0f0f0f0fu), lo.z, s); s = dot4(iq4nl_levels4((q.z >> 4) & 0x0f0f0f0fu), hi.z, s);
+        s = dot4(iq4nl_levels4(q.w & 0x0f0f0f0fu), lo.w, s); s = dot4(iq4nl_levels4((q.w >> 4) & 0x0f0f0f0fu), hi.w, s);
+        isum = ls * s; msum = 0;
+    }
+    __device__ __forceinline__ float dot(const ActLds &A, int t, int lane) const {
+        if (!valid) return 0.0f;
+        int isum, msum;
+        ints(A, t, lane, isum, msum);
+        const float yd = A.d[(size_t)t * (A.K >> 8) + sb];
+        return (d * yd) * (float)isum;
+    }
+};
+
 // ---- Q8_0 : device row planes [qs K][d K/32 f16] -------------------------------------------------
 // 32-element formats with a nibble field (Q4_0, Q5_0, IQ4_NL; activation Q8_0): two lanes per block as for Q8_0, lane half h = (e >> 4) & 1 takes
 // nibble h of the block's 16 code bytes (element j in the low nibbles, j + 16 in the high ones).  Integer sums exact:
@@ -688,6 +734,7 @@ __global__ __launch_bounds__(BS) void mmvq_kernel(const MMVQArgs a) {
         case T_Q4_0: run_segment<T_Q4_0, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_Q5_0: run_segment<T_Q5_0, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_IQ4_NL: run_segment<T_IQ4_NL, NT, BS>(a, a.seg[s], smem, bis); break;
+        case T_IQ4_XS: run_segment<T_IQ4_XS, NT, BS>(a, a.seg[s], smem, bis); break;
         default: break;
     }
 }
@@ -819,6 +866,7 @@ __global__ __launch_bounds__(256, 2) void mmvq_tiled_kernel(const MMVQArgs a) {
         case T_Q4_0: run_tiled<T_Q4_0, NT>(a, a.seg[s], smem, bis); break;
         case T_Q5_0: run_tiled<T_Q5_0, NT>(a, a.seg[s], smem, bis); break;
         case T_IQ4_NL: run_tiled<T_IQ4_NL, NT>(a, a.seg[s], smem, bis); break;
+        case T_IQ4_XS: run_tiled<T_IQ4_XS, NT>(a, a.seg[s], smem, bis); break;
         default: break;
     }
 }
@@ -988,6 +1036,7 @@ hipError_t launch_mmvq_ints(MMVQArgs a, int32_t *isum, int32_t *msum, hipStream_
         case T_Q4_0: hipLaunchKernelGGL(mmvq_ints_kernel<T_Q4_0>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_Q5_0: hipLaunchKernelGGL(mmvq_ints_kernel<T_Q5_0>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_IQ4_NL: hipLaunchKernelGGL(mmvq_ints_kernel<T_IQ4_NL>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
+        case T_IQ4_XS: hipLaunchKernelGGL(mmvq_ints_kernel<T_IQ4_XS>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -295,6 +295,29 @@ template <> struct Raw<T_Q4_0> : RawNib32<T_Q4_0> {};
 template <> struct Raw<T_Q5_0> : RawNib32<T_Q5_0> {};
 template <> struct Raw<T_IQ4_NL> : RawNib32<T_IQ4_NL> {};
 
+// ---------------------------------------------------------------- IQ4_XS (device row planes: qs | scales_l | scales_h | d)
+// narrow role with its own activation slice: lane v of a super-block owns sub-block v, its 16 code bytes (elements 32 v + j in the low nibbles, 32 v + 16 + j
+// in the high ones) against activation codes 32 v .. 32 v + 15 (lo) and 32 v + 16 .. 32 v + 31 (hi); levels from IQ4_NL's code book, no mins
+template <> struct Raw<T_IQ4_XS> {
+    u32x4_t q;
+    uint32_t sl, sh16, dh16;
+    __device__ __forceinline__ float probe() const { return (float)(q.x ^ q.y ^ q.z ^ q.w ^ sl ^ sh16 ^ dh16); }
+    __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
+        q = ldw(row + (size_t)sb * 128 + L.v * 16);
+        sl = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 128 + (size_t)sb * 4);
+        sh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 132 + (size_t)sb * 2);
+        dh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 134 + (size_t)sb * 2);
+    }
+    __device__ __forceinline__ float dot(const ActSlice &A, const LaneRole &L) const {
+        int s = 0;
+        s = dot4(iq4nl_levels4(q.x & 0x0f0f0f0fu), A.lo.x, s); s = dot4(iq4nl_levels4((q.x >> 4) & 0x0f0f0f0fu), A.hi.x, s);
+        s = dot4(iq4nl_levels4(q.y & 0x0f0f0f0fu), A.lo.y, s); s = dot4(iq4nl_levels4((q.y >> 4) & 0x0f0f0f0fu), A.hi.y, s);
+        s = dot4(iq4nl_levels4(q.z & 0x0f0f0f0fu), A.lo.z, s); s = dot4(iq4nl_levels4((q.z >> 4) & 0x0f0f0f0fu), A.hi.z, s);
+        s = dot4(iq4nl_levels4(q.w & 0x0f0f0f0fu), A.lo.w, s); s = dot4(iq4nl_levels4((q.w >> 4) & 0x0f0f0f0fu), A.hi.w, s);
+        return (h2f((uint16_t)dh16) * A.yd) * (float)(iq4xs_scale(sl, sh16, L.v) * s);
+    }
+};
+
 template <int TYPE> __device__ __forceinline__ LaneRole make_role(int lane) {
     LaneRole L;
     if (role_wide<TYPE>()) { L.sbl = lane >> 2; L.c = lane & 3; L.v = 2 * L.c; L.h = 0; }
@@ -323,6 +346,10 @@ __device__ __forceinline__ ActSlice read_slice(const ActL &A, int sb, const Lane
         s.lo = lds16(a); s.lo1 = lds16(a + 16); s.hi = lds16(a + 32); s.hi1 = lds16(a + 48);
         const uint32_t *bw = reinterpret_cast<const uint32_t *>(A.bs + sb * 16 + 4 * L.c);      // four int16 sums, 8-byte aligned
         s.bs_lo = sum2_i16(bw[0]); s.bs_hi = sum2_i16(bw[1]);
+    } else if (TYPE == T_IQ4_XS) {     // sub-block v's 32 codes (no block sums needed)
+        const int8_t *a = A.qs + sb * 256 + 32 * L.v;
+        s.lo = lds16(a); s.hi = lds16(a + 16);
+        s.bs_lo = 0; s.bs_hi = 0;
     } else if (TYPE == T_Q6_K) {
         const int8_t *a = A.qs + sb * 256 + 128 * L.n + 16 * L.w;
         s.lo = lds16(a); s.hi = lds16(a + 64);
@@ -361,6 +388,10 @@ __device__ __forceinline__ ActSlice global_slice(const MMVQArgs &a, int sb, cons
         s.lo = cld16<COH>(a.aq, qo); s.lo1 = cld16<COH>(a.aq, qo + 16); s.hi = cld16<COH>(a.aq, qo + 32); s.hi1 = cld16<COH>(a.aq, qo + 48);
         const int bo = (sb * 16 + 4 * L.c) * 2;
         s.bs_lo = cld2s<COH>(a.abs, bo) + cld2s<COH>(a.abs, bo + 2); s.bs_hi = cld2s<COH>(a.abs, bo + 4) + cld2s<COH>(a.abs, bo + 6);
+    } else if (TYPE == T_IQ4_XS) {
+        const int qo = sb * 256 + 32 * L.v;
+        s.lo = cld16<COH>(a.aq, qo); s.hi = cld16<COH>(a.aq, qo + 16);
+        s.bs_lo = 0; s.bs_hi = 0;
     } else if (TYPE == T_Q6_K) {
         const int qo = sb * 256 + 128 * L.n + 16 * L.w;
         s.lo = cld16<COH>(a.aq, qo); s.hi = cld16<COH>(a.aq, qo + 64);

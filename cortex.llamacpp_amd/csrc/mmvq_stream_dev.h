@@ -157,6 +157,12 @@ template <bool IL, int TYPE> __device__ __forceinline__ void ring_load_nib32(Raw
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q4_0> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) { ring_load_nib32<IL, T_Q4_0>(r, ring, base, row_off, nb, sb, L); }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q5_0> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) { ring_load_nib32<IL, T_Q5_0>(r, ring, base, row_off, nb, sb, L); }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_IQ4_NL> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) { ring_load_nib32<IL, T_IQ4_NL>(r, ring, base, row_off, nb, sb, L); }
+template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_IQ4_XS> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
+    r.q = lds16(RO(row_off + (unsigned)sb * 128u + (unsigned)L.v * 16u));
+    r.sl = *reinterpret_cast<const uint32_t *>(RO(row_off + (unsigned)nb * 128u + (unsigned)sb * 4u));
+    r.sh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 132u + (unsigned)sb * 2u));
+    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 134u + (unsigned)sb * 2u));
+}
 #undef RO
 
 // ---- LDS layout (bytes from smem): sync words | reduction scratch | ring | activation of the current mat-vec
@@ -759,6 +765,8 @@ __device__ __forceinline__ void consumer_dispatch(const StOp &a, uint8_t *smem, 
         case T_Q4_0: if constexpr (ENG == 0 && (FUSE == 1 || FUSE == 2)) RUN(T_Q4_0); break;
         case T_Q5_0: if constexpr (ENG == 0 && (FUSE == 1 || FUSE == 2)) RUN(T_Q5_0); break;
         case T_IQ4_NL: if constexpr (ENG == 0 && (FUSE == 1 || FUSE == 2)) RUN(T_IQ4_NL); break;
+        // IQ4_XS: every form Q4_K takes in a launch of its own (gate | up, row pairs, single rows, the head); not in the layer engine
+        case T_IQ4_XS: if constexpr (ENG == 0) RUN(T_IQ4_XS); break;
         default: break;
     }
 #undef RUN

@@ -108,6 +108,18 @@ __device__ __forceinline__ int iq4nl_value(int nib) {
     return (int)(int8_t)((w >> (8 * (nib & 3))) & 0xffu);
 }
 
+// four IQ4_NL levels (one int8 per byte) from four nibble indices (one per byte): two v_perm_b32 over the packed code book and a select on bit 3
+__device__ __forceinline__ uint32_t iq4nl_levels4(uint32_t idx) {
+    const uint32_t lo = __builtin_amdgcn_perm(0xf6eaddcfu, 0xbfad9881u, idx & 0x07070707u);
+    const uint32_t hi = __builtin_amdgcn_perm(0x71594535u, 0x26190d01u, idx & 0x07070707u);
+    const uint32_t m = ((idx >> 3) & 0x01010101u) * 0xffu;
+    return (hi & m) | (lo & ~m);
+}
+// IQ4_XS: the 6-bit scale of sub-block ib (0..7) from the super-block's scales_l word (nibble ib) and scales_h (bit pair ib), minus 32
+__device__ __forceinline__ int iq4xs_scale(uint32_t scales_l, uint32_t scales_h, int ib) {
+    return (int)(((scales_l >> (4 * ib)) & 0xfu) | (((scales_h >> (2 * ib)) & 3u) << 4)) - 32;
+}
+
 __device__ __forceinline__ float dequant_elem(int type, const uint8_t *row, int K, int e) {
     switch (type) {
         case T_F32: return reinterpret_cast<const float *>(row)[e];
@@ -156,6 +168,14 @@ __device__ __forceinline__ float dequant_elem(int type, const uint8_t *row, int 
             const float d = h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 108 + (size_t)sb * 2));
             const int code = (int)((q >> (2 * j)) & 3) - (((hm >> (4 * n + j)) & 1) ? 0 : 4);
             return __fmul_rn(__fmul_rn(d, (float)((low | (high << 4)) - 32)), (float)code);
+        }
+        case T_IQ4_XS: {   // element j of sub-block ib: nibble j / 16 of qs[16 ib + j % 16]; dequantize_row_iq4_xs: dl = d * (ls - 32), y = dl * level
+            const int nb = K >> 8, sb = e >> 8, r = e & 255, ib = r >> 5, j = r & 31;
+            const int nib = (row[(size_t)sb * 128 + 16 * ib + (j & 15)] >> (4 * (j >> 4))) & 0x0f;
+            const uint32_t sl = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 128 + (size_t)sb * 4);
+            const uint32_t sh = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 132 + (size_t)sb * 2);
+            const float d = h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 134 + (size_t)sb * 2));
+            return __fmul_rn(__fmul_rn(d, (float)iq4xs_scale(sl, sh, ib)), (float)iq4nl_value(nib));
         }
         case T_Q6_K: {
             const int nb = K >> 8, sb = e >> 8, r = e & 255, n = r >> 7, rr = r & 127, k = rr >> 5, l = rr & 31;

@@ -61,7 +61,7 @@ static RopeArgs layer_rope(const RopeArgs &ra, const LayerWeights &L, float eps)
 }
 
 static bool type_supported(int t) {
-    return t == T_F32 || t == T_F16 || t == T_Q8_0 || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q2_K || t == T_Q3_K || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL;
+    return t == T_F32 || t == T_F16 || t == T_Q8_0 || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q2_K || t == T_Q3_K || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL || t == T_IQ4_XS;
 }
 
 Model *model_load(const std::string &path, int main_gpu, std::string &err, int &status, int prefill_planes, int tp_rank, int tp_size) {
@@ -189,6 +189,11 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             fail = true;
             return;
         }
+        if (P > 1 && ti->type == T_IQ4_XS) {               // (the row split's column cuts and exchange steps are untested with it)
+            err = "row split (split_mode \"row\" / tp_size > 1) of iq4_xs tensors is not supported (tensor " + name + "): load the file on one device";
+            fail = true;
+            return;
+        }
         dst.name = name;
         dst.type = ti->type;
         dst.K = ti->ne[0];
@@ -226,7 +231,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
         dst.ggml_bytes = pl.src_bytes;
         plan.push_back(pl);
         total += (dst.bytes + 255) & ~(size_t)255;
-        if (dst.type == T_Q6_K || dst.type == T_Q8_0 || dst.type == T_Q2_K || dst.type == T_Q3_K || dst.type == T_Q4_0 || dst.type == T_Q5_0 || dst.type == T_IQ4_NL || dst.row_bytes != ggml_row_bytes(dst.type, dst.K)) max_stage = std::max(max_stage, pl.src_bytes);
+        if (dst.type == T_Q6_K || dst.type == T_Q8_0 || dst.type == T_Q2_K || dst.type == T_Q3_K || dst.type == T_Q4_0 || dst.type == T_Q5_0 || dst.type == T_IQ4_NL || dst.type == T_IQ4_XS || dst.row_bytes != ggml_row_bytes(dst.type, dst.K)) max_stage = std::max(max_stage, pl.src_bytes);
     };
     want("token_embd.weight", m->tok_embd, true);
     if (hp.encoder) {
@@ -383,7 +388,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
     for (const Plan &pl : plan) {
         DevTensor &d = *pl.dst;
         d.data = arena + pl.off;
-        const bool direct = !(d.type == T_Q6_K || d.type == T_Q8_0 || d.type == T_Q2_K || d.type == T_Q3_K || d.type == T_Q4_0 || d.type == T_Q5_0 || d.type == T_IQ4_NL) && (pl.ti->n_dims == 1 || d.row_bytes == ggml_row_bytes(d.type, d.K));
+        const bool direct = !(d.type == T_Q6_K || d.type == T_Q8_0 || d.type == T_Q2_K || d.type == T_Q3_K || d.type == T_Q4_0 || d.type == T_Q5_0 || d.type == T_IQ4_NL || d.type == T_IQ4_XS) && (pl.ti->n_dims == 1 || d.row_bytes == ggml_row_bytes(d.type, d.K));
         hipError_t e;
         const uint8_t *src = (const uint8_t *)pl.ti->data + pl.src_off;
         uint8_t *to = direct ? d.data : stage;
@@ -930,7 +935,7 @@ void Context::prof_end() {
 }
 
 // ------------------------------------------------------------------------------------------ linear layers
-static bool is_quant(int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0 || t == T_Q2_K || t == T_Q3_K || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL; }
+static bool is_quant(int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0 || t == T_Q2_K || t == T_Q3_K || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL || t == T_IQ4_XS; }
 
 static MMVQSeg make_seg(const DevTensor &w, float *out, int ld_out, const float *resid, const int32_t *esel) {
     MMVQSeg s{};
@@ -979,11 +984,11 @@ hipError_t Context::ensure_prep(const ActQuant &aq, int K, int T) {
     return hipSuccess;
 }
 
-// Q2_K / Q3_K tensors reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
+// Q2_K / Q3_K / IQ4_XS tensors reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
 static bool q80_copy(const DevTensor &w, int K, int T) {
     return (w.type == T_Q4_0 || w.type == T_Q5_0 || w.type == T_IQ4_NL) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
 }
-static bool planes_small(const DevTensor &w, int K, int T) { return (w.type == T_Q2_K || w.type == T_Q3_K) && w.planes && T >= 32 && (K % 256) == 0; }
+static bool planes_small(const DevTensor &w, int K, int T) { return (w.type == T_Q2_K || w.type == T_Q3_K || w.type == T_IQ4_XS) && w.planes && T >= 32 && (K % 256) == 0; }
 
 hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *x_f32, int K, int T, float *out, int ld_out,
                            const float *resid, int epi) {
@@ -1004,7 +1009,7 @@ hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *
         if (q80_copy(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs0)      // prompt processing of Q4_0 / Q5_0 / IQ4_NL tensors: their exact Q8_0-layout copy
             return launch_mmq_q80(w.planes, dev_row_bytes(T_Q8_0, K), (int)w.N, K, T, aq, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
         if (planes_small(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs) {
-            // prompt processing of Q2_K / Q3_K tensors: their plane sets (expanded at load in the Q4_K / Q6_K plane formats, mmq.hip) on the same kernels
+            // prompt processing of Q2_K / Q3_K / IQ4_XS tensors: their plane sets (expanded at load in the Q4_K / Q6_K plane formats, mmq.hip) on the same kernels
             if (w.type == T_Q2_K && !bh_over_) HIP_TRY(ensure_prep(aq, K, T));
             return launch_mmq_planes(w.type, w.planes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_ws_);
         }
@@ -1021,7 +1026,8 @@ hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs,
     for (int i = 0; i < n; i++) all_q &= is_quant(ws[i]->type);
     const int K = (int)ws[0]->K;
     bool all_mmq = true, all_ks = true;
-    for (int i = 0; i < n; i++) { all_mmq &= mmq_applicable(ws[i]->type, K, T); all_ks &= mmq_ksplit_applicable(ws[i]->type, K, T); }
+    // (IQ4_XS: through its plane set, the signed format - Q | K | V of the IQ4_XS mixes run as one launch like the K-quants')
+    for (int i = 0; i < n; i++) { all_mmq &= mmq_applicable(ws[i]->type, K, T) || (ws[i]->type == T_IQ4_XS && planes_small(*ws[i], K, T)); all_ks &= mmq_ksplit_applicable(ws[i]->type, K, T); }
     if (all_ks && pending_fuse_.mode == 0 && n <= 3) {         // batched decode step: Q, K, V in one launch
         HIP_TRY(ensure_prep(aq, K, T));
         MMQSeg sg[3];
@@ -1032,7 +1038,7 @@ hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs,
         HIP_TRY(ensure_prep(aq, K, T));
         // Q | K | V (or Q | K) as one launch over the concatenated rows where their plane sets are adjacent in the arena and
         // of one plane format (Q4_K and Q5_K share it; the Q6_K attn_v of the "more bits" layers runs on its own)
-        auto mins = [](int t) { return t != T_Q6_K; };
+        auto mins = [](int t) { return t != T_Q6_K && t != T_IQ4_XS; };
         auto adjacent = [&](int i) { return ws[i]->planes && ws[i - 1]->planes && ws[i]->planes == ws[i - 1]->planes + ws[i - 1]->planes_bytes &&
                                             (ws[i - 1]->N % 32) == 0 && ws[i]->n_expert == 1; };
         int nf = 1;
@@ -1778,7 +1784,7 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
             // quantise inside the down-projection's prologue (once per CU, overlapped with its first weight loads)
             // (the widths listed are the ones the register-ring and weight-stream kernels take; the generic mat-vec's fused prologue would refuse others)
             const bool fuse_down = fuse_down_env && T == 1 && (L.down.type == T_Q4_K || L.down.type == T_Q5_K || L.down.type == T_Q6_K || act_is_q80(L.down.type) ||
-                                                               L.down.type == T_Q2_K || L.down.type == T_Q3_K) &&
+                                                               L.down.type == T_Q2_K || L.down.type == T_Q3_K || L.down.type == T_IQ4_XS) &&
                                    (FF % 256) == 0 && mmvq_fast_kb_ok((FF + 2047) / 2048);
             if (fuse_down && !tp && L.down_lo.valid() && L.down_hi.valid()) {
                 // the column halves of ffn_down, each quantising its half of the SwiGLU output in its prologue: x += W_lo a_lo; x += W_hi a_hi

@@ -44,7 +44,7 @@ enum mi355_status {
 /* ggml type ids as stored in GGUF (upstream ggml.h enum ggml_type; used at llama_engine.cc:272-281) */
 enum mi355_type {
     MI355_TYPE_F32 = 0, MI355_TYPE_F16 = 1, MI355_TYPE_Q4_0 = 2, MI355_TYPE_Q8_0 = 8,
-    MI355_TYPE_Q4_K = 12, MI355_TYPE_Q5_K = 13, MI355_TYPE_Q6_K = 14, MI355_TYPE_Q8_K = 15,
+    MI355_TYPE_Q4_K = 12, MI355_TYPE_Q5_K = 13, MI355_TYPE_Q6_K = 14, MI355_TYPE_Q8_K = 15, MI355_TYPE_IQ4_XS = 23,
 };
 
 /* ------------------------------------------------------------------ backend */
@@ -200,10 +200,11 @@ MI355_API int32_t mi355_debug_layer_out(mi355_context *ctx, int32_t il, float *d
 /* quantize_row_q8_K / quantize_row_q8_0 (activation side).  out receives ggml-layout blocks. */
 MI355_API int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n_per_row, int64_t n_rows, void *out_blocks);
 /* y[T][N] = W[N][K] . x[T][K]; W is ggml-layout blocks of `type`.  isum/msum (nullable):
- * per (token, row, block) integer partial sums for bit-exact checks. */
+ * per (token, row, block) integer partial sums for bit-exact checks.  IQ4_XS (type 23, Q8_K activations): isum is the
+ * super-block's sum over sub-blocks of (ls - 32) * sum(level * q8), msum is 0. */
 MI355_API int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T,
                                float *y, int32_t *isum, int32_t *msum);
-/* ffn_gate and ffn_up (one K-quant type, N rows each, N % 32 == 0) against the same T activation rows with SwiGLU in the
+/* ffn_gate and ffn_up (one K-quant type or IQ4_XS, N rows each, N % 32 == 0) against the same T activation rows with SwiGLU in the
  * epilogue, as the prompt path launches them (mmq_planes2_swiglu_kernel): y[t][n] = silu(Wg[n] . x[t]) * (Wu[n] . x[t]).
  * Shapes too small for that launch are refused unless the debug option "mmq_tiles" = 4 forces the kernel. */
 MI355_API int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y);
@@ -303,7 +304,8 @@ typedef void (*mi355_log_callback)(int level, const char *line, void *user);
 MI355_API void mi355_engine_set_log_callback(mi355_engine *e, mi355_log_callback cb, void *user);
 
 /* Test / tool switches of the per-op entry points: "mmq_planes" (1: mi355_op_mul_mat with T >= 32 expands the weight
- * into MFMA planes first, as a loaded model does; 0: expands on the fly inside the kernel), "mmq_tiles" (0 | 1 | 2
+ * into MFMA planes first, as a loaded model does; 0: expands on the fly inside the kernel - Q2_K / Q3_K / IQ4_XS have
+ * no on-the-fly form and take the mat-vec then), "mmq_tiles" (0 | 1 | 2
  * token tiles per wave), "mmq_ksplit" (1: 8 <= T <= 64 uses the K-split small-batch kernel, as the runtime does; 0: the
  * kernels the other T ranges use); and of contexts created afterwards: "decode_mega" (1: single-token steps of a dense
  * K-quant model with Llama-3-8B's layer geometry run every layer in one launch; 0, the default: one launch per operation
