@@ -11,6 +11,7 @@ F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 2, 8, 12, 13, 14, 15
 Q2_K, Q3_K = 10, 11
 Q5_0, IQ4_NL = 6, 20
 IQ4_XS = 23
+BF16 = 30
 
 
 class MI355Error(RuntimeError):
@@ -97,6 +98,8 @@ SYMBOLS = {
     "mi355_debug_layer_out": (_i32, [_vp, _i32, _vp, _sz]),
     "mi355_op_quantize_act": (C.c_int, [_i32, _vp, _i64, _i64, _vp]),
     "mi355_op_mul_mat": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "mi355_op_f32_to_bf16": (C.c_int, [_vp, _i64, _vp]),
+    "mi355_op_mul_mat_bf16": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mi355_op_ffn_gate_up": (C.c_int, [_i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
     "mi355_op_rms_norm_mul": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp]),
     "mi355_op_rope": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _f32, _f32, _vp, _i32]),
@@ -236,6 +239,28 @@ class Backend:
             msum = np.zeros((T, N, nblk), np.int32)
         self._chk(self.lib.mi355_op_mul_mat(t, _ptr(W), N, K, _ptr(x), T, _ptr(y), _ptr(isum), _ptr(msum)), "op_mul_mat")
         return (y, isum, msum) if want_ints else y
+
+    def f32_to_bf16(self, x: np.ndarray) -> np.ndarray:
+        """bf16 bits (uint16) of the f32 values, as the bf16 kernels round their activation rows; x.size % 8 == 0."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros(x.shape, np.uint16)
+        self._chk(self.lib.mi355_op_f32_to_bf16(_ptr(x), x.size, _ptr(out)), "op_f32_to_bf16")
+        return out
+
+    def mul_mat_bf16(self, Ws, K: int, x: np.ndarray, bias=None, resid=None, epi: int = 0, path: int = 0, tokens_per_launch: int = 0, graph: bool = False):
+        """Ws: 1..3 bf16 tensors as uint16 arrays [N][K]; x [T][K] f32 -> list of y [T][N] (one entry for epi 2, SwiGLU).  See mi355_op_mul_mat_bf16."""
+        Ws = [np.ascontiguousarray(w).view(np.uint16).reshape(-1, K) for w in Ws]
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+        T, n = x.shape[0], len(Ws)
+        Ns = np.array([w.shape[0] for w in Ws], np.int64)
+        ys = [np.zeros((T, int(N)), np.float32) for N in (Ns[:1] if epi == 2 else Ns)]
+        bs = [None if bias is None or b is None else np.ascontiguousarray(b, np.float32) for b in (bias or [None] * n)]
+        r = None if resid is None else np.ascontiguousarray(resid, np.float32)
+        parr = lambda xs: (C.c_void_p * len(xs))(*[None if a is None else a.ctypes.data for a in xs])
+        wp, bp, yp = parr(Ws), parr(bs), parr(ys + [None] * (n - len(ys)))
+        self._chk(self.lib.mi355_op_mul_mat_bf16(n, wp, _ptr(Ns), K, _ptr(x), T, bp if bias is not None else None, _ptr(r), epi, path, tokens_per_launch,
+                                                 int(graph), yp), "op_mul_mat_bf16")
+        return ys
 
     def ffn_gate_up(self, t: int, Wg: np.ndarray, Wu: np.ndarray, N: int, K: int, x: np.ndarray) -> np.ndarray:
         Wg = np.ascontiguousarray(Wg.view(np.uint8).reshape(-1))

@@ -600,6 +600,24 @@ int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const fl
             }
         }
     } else {
+        if (type == T_BF16) {
+            // (the model path's choice for a bf16 tensor: the rows rounded to bf16 once, then the matrix cores from 8 tokens on, else the weight stream)
+            DevBuf xb((size_t)K * T * 2);
+            if (!xb.p) return MI355_ERR_OOM;
+            e = launch_f32_to_bf16(dx.as<float>(), xb.p, (size_t)K * T, nullptr);
+            if (e == hipSuccess) {
+                if (mmbf16_applicable(type, (int)N, (int)K, (int)T, wdev.p, xb.p, dy.p) && (N & 3) == 0)
+                    e = launch_mmbf16(wdev.as<uint8_t>(), (int)N, (int)K, xb.p, (int)T, dy.as<float>(), (int)N, nullptr, nullptr, 1.0f, false, nullptr);
+                else {
+                    MMVBF16Args a{};
+                    a.n_seg = 1; a.K = (int)K; a.epi = EPI_STORE; a.xb = xb.as<uint16_t>();
+                    a.seg[0] = MMVBF16Seg{wdev.as<uint8_t>(), dy.as<float>(), nullptr, (int)N, (int)N, drow};
+                    e = launch_mmv_bf16_tokens(a, (int)T, nullptr);
+                }
+            }
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            if (e != hipSuccess) return hip_fail(e, "mul_mat (bf16)");
+        } else
         // (the model path's choice: batches against f16 tensors on the matrix cores, everything else one wave per row and token)
         if (mmf16_applicable(type, (int)N, (int)K, (int)T, wdev.p, dx.p, dy.p) && (N & 3) == 0)
             e = launch_mmf16(wdev.as<uint8_t>(), (int)N, (int)K, dx.as<float>(), (int)T, dy.as<float>(), (int)N, nullptr, nullptr);
@@ -610,6 +628,95 @@ int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const fl
     e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "mul_mat");
     return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (n <= 0 || n % 8) { fail("f32_to_bf16: n must be a positive multiple of 8"); return MI355_ERR_ARG; }
+    DevBuf dx((size_t)n * 4), dy((size_t)n * 2);
+    if (!dx.up(x, (size_t)n * 4) || !dy.p) return MI355_ERR_OOM;
+    hipError_t e = launch_f32_to_bf16(dx.as<float>(), dy.p, (size_t)n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "f32_to_bf16");
+    return dy.down(out, (size_t)n * 2) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, const float *const *bias, const float *resid,
+                          int32_t epi, int32_t path, int32_t tokens_per_launch, int32_t use_graph, float *const *y) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (n_seg < 1 || n_seg > 3 || !W || !N || !x || !y || K < 8 || K % 8 || (path == 2 && K % 16) || T < 1 || (epi != EPI_STORE && epi != EPI_ADD && epi != EPI_SWIGLU) || path < 0 || path > 2 ||
+        (epi == EPI_ADD && (n_seg != 1 || !resid)) || (epi == EPI_SWIGLU && (n_seg != 2 || N[0] != N[1])) ||
+        (tokens_per_launch != 0 && tokens_per_launch != 1 && tokens_per_launch != 2 && tokens_per_launch != 4 && tokens_per_launch != 8 && tokens_per_launch != 16)) {
+        fail("mul_mat_bf16: bad arguments"); return MI355_ERR_ARG;
+    }
+    const size_t row = (size_t)K * 2;
+    const int n_out = epi == EPI_SWIGLU ? 1 : n_seg;
+    std::vector<std::unique_ptr<DevBuf>> dw, db, dy;
+    for (int s = 0; s < n_seg; s++) {
+        if (N[s] < 1 || !W[s]) { fail("mul_mat_bf16: bad segment"); return MI355_ERR_ARG; }
+        dw.emplace_back(new DevBuf(row * (size_t)N[s]));
+        db.emplace_back(new DevBuf(bias && bias[s] ? (size_t)N[s] * 4 : 16));
+        dy.emplace_back(new DevBuf((size_t)N[s] * T * 4));
+        if (!dw.back()->up(W[s], row * (size_t)N[s]) || !dy.back()->p || !db.back()->p) return MI355_ERR_OOM;
+        if (bias && bias[s] && !db.back()->up(bias[s], (size_t)N[s] * 4)) return MI355_ERR_OOM;
+    }
+    DevBuf dx((size_t)K * T * 4), xb((size_t)K * T * 2), dr(resid ? (size_t)N[0] * T * 4 : 16);
+    if (!dx.up(x, (size_t)K * T * 4) || !xb.p || !dr.p || (resid && !dr.up(resid, (size_t)N[0] * T * 4))) return MI355_ERR_OOM;
+    hipStream_t st = nullptr;
+    if (hipStreamCreate(&st) != hipSuccess) return MI355_ERR_HIP;
+    auto run = [&]() -> hipError_t {
+        hipError_t e = launch_f32_to_bf16(dx.as<float>(), xb.p, (size_t)K * T, st);
+        if (e != hipSuccess) return e;
+        bool mfma = path == 2;
+        if (path == 0) {                                      // the model path's choice (Context::linear_bf16)
+            mfma = true;
+            for (int s = 0; s < n_seg; s++) mfma = mfma && mmbf16_applicable(T_BF16, (int)N[s], (int)K, (int)T, dw[(size_t)s]->p, xb.p, dy[(size_t)s]->p) && (N[s] & 3) == 0;
+        }
+        if (mfma) {
+            for (int s = 0; s < n_seg && e == hipSuccess; s++)
+                e = launch_mmbf16(dw[(size_t)s]->as<uint8_t>(), (int)N[s], (int)K, xb.p, (int)T, dy[(size_t)s]->as<float>(), (int)N[s], epi == EPI_ADD ? dr.as<float>() : nullptr,
+                                  bias && bias[s] ? db[(size_t)s]->as<float>() : nullptr, 1.0f, false, st);
+            if (e == hipSuccess && epi == EPI_SWIGLU) e = launch_swiglu(dy[0]->as<float>(), dy[1]->as<float>(), dy[0]->as<float>(), (int64_t)T * N[0], st);
+            return e;
+        }
+        MMVBF16Args a{};
+        a.n_seg = n_seg; a.K = (int)K; a.epi = epi; a.resid = epi == EPI_ADD ? dr.as<float>() : nullptr; a.xb = xb.as<uint16_t>();
+        for (int s = 0; s < n_seg; s++)
+            a.seg[s] = MMVBF16Seg{dw[(size_t)s]->as<uint8_t>(), dy[(size_t)s]->as<float>(), bias && bias[s] ? db[(size_t)s]->as<float>() : nullptr, (int)N[s], (int)N[s], row};
+        if (tokens_per_launch == 0) return launch_mmv_bf16_tokens(a, (int)T, st);
+        for (int64_t t0 = 0; t0 < T && e == hipSuccess; t0 += tokens_per_launch) {       // (tests: a fixed launch width; T must be a multiple of it)
+            if (T - t0 < tokens_per_launch) return hipErrorInvalidValue;
+            MMVBF16Args c = a;
+            c.T = tokens_per_launch; c.xb = a.xb + t0 * K;
+            if (a.resid) c.resid = a.resid + t0 * N[0];
+            for (int s = 0; s < n_seg; s++) c.seg[s].out = a.seg[s].out + t0 * N[s];
+            e = launch_mmv_bf16(c, st);
+        }
+        return e;
+    };
+    hipError_t e = hipSuccess;
+    if (use_graph) {                                          // captured once, replayed twice: what a decode step's graph does with these launches
+        hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
+        e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+        if (e == hipSuccess) {
+            const hipError_t er = run();
+            const hipError_t ec = hipStreamEndCapture(st, &g);
+            e = er != hipSuccess ? er : ec;
+        }
+        if (e == hipSuccess) e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+        for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipGraphLaunch(ge, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (ge) (void)hipGraphExecDestroy(ge);
+        if (g) (void)hipGraphDestroy(g);
+    } else {
+        e = run();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    (void)hipStreamDestroy(st);
+    if (e != hipSuccess) return hip_fail(e, "mul_mat_bf16");
+    for (int s = 0; s < n_out; s++)
+        if (!dy[(size_t)s]->down(y[s], (size_t)N[s] * T * 4)) return MI355_ERR_HIP;
+    return MI355_OK;
 }
 
 int mi355_op_rms_norm_mul(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y) {

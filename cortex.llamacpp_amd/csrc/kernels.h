@@ -236,6 +236,36 @@ hipError_t launch_mmf16_xh(const uint8_t *W, int n_rows, int K, const void *xh, 
 hipError_t launch_mmv_float(int type, const uint8_t *W, int n_rows, int K, const float *x, int T, float *y, int ld_out,
                             const float *resid, hipStream_t st);
 
+// ---------------------------------------------------------------- BF16 weight tensors (ggml type 30): mmv_bf16.hip (weight stream, 1 <= T <= 16) and mmf_bf16.hip (matrix cores)
+// y[t][n] = sum_k W[n][k] * bf16(x[t][k]): the activation rows are rounded once (ggml's f32 -> bf16: nearest, ties to even, NaN quieted, subnormals kept), n % 8 == 0
+hipError_t launch_f32_to_bf16(const float *x, void *y, size_t n, hipStream_t st);
+struct MMVBF16Seg {
+    const uint8_t *W;     // bf16 rows
+    float *out;           // out[t * ld_out + row]
+    const float *bias;    // nullable: added per row before the residual
+    int n_rows;
+    int ld_out;
+    size_t row_bytes;
+};
+// up to three segments over one activation (Q | K | V); EPI_ADD: one segment, out = resid + (y + bias); EPI_SWIGLU: seg[0] = ffn_gate, seg[1] = ffn_up,
+// seg[0].out = silu(gate) * up.  An output's summation order is the same in every form and for every T (mmv_bf16.hip): fused and separate launches agree bit for bit.
+struct MMVBF16Args {
+    MMVBF16Seg seg[3];
+    int n_seg;
+    int K;                // K % 8 == 0
+    int T;                // tokens of this launch: 1, 2, 4, 8 or 16
+    int epi;
+    const float *resid;   // EPI_ADD: [T][seg[0].ld_out]
+    const uint16_t *xb;   // [T][K] bf16 activations (launch_f32_to_bf16)
+};
+hipError_t launch_mmv_bf16(const MMVBF16Args &a, hipStream_t st);
+// any T >= 1 in chunks of 16, 8, 4, 2, 1 tokens (a.T is ignored; xb / out / resid point at the first token)
+hipError_t launch_mmv_bf16_tokens(const MMVBF16Args &a, int T, hipStream_t st);
+// batches on v_mfma_f32_32x32x16_bf16: y = resid + (W xb + bias) * scale, every part optional; the rule of mmf16_applicable with the type changed
+bool mmbf16_applicable(int type, int n_rows, int K, int T, const void *W, const void *xb, const void *y);
+hipError_t launch_mmbf16(const uint8_t *W, int n_rows, int K, const void *xb, int T, float *y, int ld_out, const float *resid, const float *bias, float scale, bool do_scale,
+                         hipStream_t st);
+
 // MoE router: softmax over n_expert <= 256 logits per token, top-k (first index wins ties), weights renormalised; one wave per token
 // forced (nullable, tests): [T][k] expert ids to take instead of the k most probable (weights = this side's probabilities of them, renormalised)
 hipError_t launch_moe_route(const float *logits, int T, int n_expert, int k, int32_t *ids, float *w, hipStream_t st, const int32_t *forced = nullptr);

@@ -336,6 +336,7 @@ __global__ __launch_bounds__(256) void mmv_float_kernel(int type, const uint8_t 
 }
 hipError_t launch_mmv_float(int type, const uint8_t *W, int n_rows, int K, const float *x, int T, float *y, int ld_out,
                             const float *resid, hipStream_t st) {
+    if (type != T_F32 && type != T_F16) return hipErrorInvalidValue;      // (bf16 tensors have kernels of their own: mmv_bf16.hip)
     const int waves = n_rows * T;
     hipLaunchKernelGGL(mmv_float_kernel, dim3((waves + 3) / 4), dim3(256), 0, st, type, W, n_rows, K, x, T, y, ld_out, resid);
     return hipGetLastError();

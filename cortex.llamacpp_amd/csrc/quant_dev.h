@@ -124,6 +124,7 @@ __device__ __forceinline__ float dequant_elem(int type, const uint8_t *row, int 
     switch (type) {
         case T_F32: return reinterpret_cast<const float *>(row)[e];
         case T_F16: return h2f(reinterpret_cast<const uint16_t *>(row)[e]);
+        case T_BF16: return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t *>(row)[e] << 16);   // the upper half of an f32: exact for every bit pattern
         case T_Q8_0: {
             const float d = h2f(*reinterpret_cast<const uint16_t *>(row + K + (e >> 5) * 2));
             return __fmul_rn((float)(int8_t)row[e], d);

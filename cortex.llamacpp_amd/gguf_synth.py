@@ -21,9 +21,10 @@ F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 2, 8, 12, 13, 14
 Q2_K, Q3_K = 10, 11
 Q5_0, IQ4_NL = 6, 20
 IQ4_XS = 23
-TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K", Q2_K: "q2_K", Q3_K: "q3_K", Q5_0: "q5_0", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs"}
-BLOCK_ELEMS = {F32: 1, F16: 1, Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q2_K: 256, Q3_K: 256, Q5_0: 32, IQ4_NL: 32, IQ4_XS: 256}
-BLOCK_BYTES = {F32: 4, F16: 2, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q2_K: 84, Q3_K: 110, Q5_0: 22, IQ4_NL: 18, IQ4_XS: 136}
+BF16 = 30
+TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K", Q2_K: "q2_K", Q3_K: "q3_K", Q5_0: "q5_0", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", BF16: "bf16"}
+BLOCK_ELEMS = {F32: 1, F16: 1, Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q2_K: 256, Q3_K: 256, Q5_0: 32, IQ4_NL: 32, IQ4_XS: 256, BF16: 1}
+BLOCK_BYTES = {F32: 4, F16: 2, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q2_K: 84, Q3_K: 110, Q5_0: 22, IQ4_NL: 18, IQ4_XS: 136, BF16: 2}
 
 DT_Q4_0 = np.dtype([("d", "<f2"), ("qs", "u1", 16)])
 DT_Q8_0 = np.dtype([("d", "<f2"), ("qs", "i1", 32)])
@@ -52,12 +53,22 @@ def row_bytes(t: int, n: int) -> int:
     return n // BLOCK_ELEMS[t] * BLOCK_BYTES[t]
 
 
+def round_bf16(x: np.ndarray) -> np.ndarray:
+    """f32 -> bf16 bits (uint16) as ggml_compute_fp32_to_bf16 does: nearest, ties to even; a NaN keeps its upper bits and gets the quiet bit; subnormals are kept."""
+    u = np.ascontiguousarray(x, "<f4").view(np.uint32)
+    r = ((u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)).astype(np.uint16)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, ((u >> np.uint32(16)) | np.uint32(64)).astype(np.uint16), r).astype("<u2")
+
+
 def random_blocks(rng: np.random.Generator, t: int, n_elems: int, std: float) -> np.ndarray:
     """n_elems weights of ggml type t as raw bytes; dequantised std ~= `std`, mean ~= 0."""
     if t == F32:
         return (rng.standard_normal(n_elems, dtype=np.float32) * np.float32(std)).astype("<f4").view(np.uint8)
     if t == F16:
         return (rng.standard_normal(n_elems, dtype=np.float32) * np.float32(std)).astype("<f2").view(np.uint8)
+    if t == BF16:                                            # the f32 draws that F16 rounds to half, rounded to bf16 instead
+        return round_bf16(rng.standard_normal(n_elems, dtype=np.float32) * np.float32(std)).view(np.uint8)
     nb = n_elems // BLOCK_ELEMS[t]
     raw = rng.integers(0, 256, size=nb * BLOCK_BYTES[t], dtype=np.uint8)
     blk = raw.view(BLOCK_DTYPE[t])
@@ -265,7 +276,7 @@ CONFIGS = {
                                          n_ff_exp=1536),
 }
 
-FTYPE_ID = {"f16": 1, "q4_0": 2, "q5_0": 8, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18}
+FTYPE_ID = {"f16": 1, "bf16": 32, "q4_0": 2, "q5_0": 8, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18}
 
 
 def use_more_bits(i: int, n: int) -> bool:
@@ -285,6 +296,8 @@ def tensor_type(cfg: LlamaConfig, ftype: str, kind: str, il: int) -> int:
     """ggml type of a 2-D weight per llama-quantize's `*_K_M` mix."""
     if ftype == "f16":
         return F16
+    if ftype == "bf16":                                      # LLAMA_FTYPE_MOSTLY_BF16: every 2-D weight
+        return BF16
     if ftype == "q8_0":
         return Q8_0
     if ftype in ("q2_k", "q3_k_m"):

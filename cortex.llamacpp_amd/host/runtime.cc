@@ -61,7 +61,7 @@ static RopeArgs layer_rope(const RopeArgs &ra, const LayerWeights &L, float eps)
 }
 
 static bool type_supported(int t) {
-    return t == T_F32 || t == T_F16 || t == T_Q8_0 || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q2_K || t == T_Q3_K || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL || t == T_IQ4_XS;
+    return t == T_F32 || t == T_F16 || t == T_Q8_0 || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q2_K || t == T_Q3_K || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL || t == T_IQ4_XS || t == T_BF16;
 }
 
 Model *model_load(const std::string &path, int main_gpu, std::string &err, int &status, int prefill_planes, int tp_rank, int tp_size) {
@@ -193,6 +193,15 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             err = "row split (split_mode \"row\" / tp_size > 1) of iq4_xs tensors is not supported (tensor " + name + "): load the file on one device";
             fail = true;
             return;
+        }
+        if (ti->type == T_BF16) {
+            // bf16 is a type of the dense 2-D weights (and of token_embd / output): the norm and bias vectors are read as f32 by the kernels, the routed experts,
+            // the encoder graph and the row split's column cuts have no bf16 kernels.  Rows are loaded as 16-byte pieces: 8 weights.
+            const bool expert = name.size() > 12 && (name.compare(name.size() - 12, 12, "_exps.weight") == 0 || name.find("ffn_gate_inp") != std::string::npos);
+            const char *why = ti->n_dims == 1 ? "norm and bias vectors must be f32" : expert ? "bf16 expert tensors are not supported" :
+                              hp.encoder ? "the encoder graph has no bf16 kernels" : P > 1 ? "a row split (split_mode \"row\" / tp_size > 1) of bf16 tensors is not supported: load the file on one device" :
+                              (ti->ne[0] % 8) ? "bf16 rows must hold a multiple of 8 weights" : nullptr;
+            if (why) { err = "tensor " + name + " has type bf16: " + why; fail = true; return; }
         }
         dst.name = name;
         dst.type = ti->type;
@@ -685,6 +694,7 @@ bool Context::init(std::string &err) {
     ffn_ = (float *)dalloc(T * FF * 4);
     ffn_u_ = (float *)dalloc(T * FF * 4);
     xo_ = (float *)dalloc(T * E * 4);
+    xb_ = (uint16_t *)dalloc(T * std::max({E, FF, QA}) * 2);     // the rows of a contraction against a bf16 tensor, rounded to bf16 (widest: n_embd, n_ff or H * D)
     if (hp.tp_exchange) {
         if (!tp_active() || tp_size() != hp.tp_size || tp_rank() != hp.tp_rank) { err = "model was loaded as rank " + std::to_string(hp.tp_rank) + " of " + std::to_string(hp.tp_size) + " but the process has no matching row-split group (mi355_tp_init)"; return false; }
         tp_part_ = (float *)dalloc(T * E * 4);
@@ -727,7 +737,7 @@ bool Context::init(std::string &err) {
                              (size_t)(num_cu() * 7 / 4) * 128 * 256 * sizeof(float));
     mmq_ws_.p = T >= 128 ? (float *)dalloc(mmq_ws_.bytes) : nullptr;
     if (!mmq_ws_.p) mmq_ws_.bytes = 0;
-    if (!ok || !x_ || !ffn_u_) { err = "activation buffer allocation failed"; return false; }
+    if (!ok || !x_ || !ffn_u_ || !xb_) { err = "activation buffer allocation failed"; return false; }
 
     size_t ws = 0;
     for (int t = 1; t <= (int)T; t++) {
@@ -1016,15 +1026,50 @@ hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *
         MMVQSeg s = make_seg(w, out, ld_out, resid, nullptr);
         return mmvq_tokens(&s, 1, K, T, epi, aq, stream_, pending_fuse_);
     }
+    if (w.type == T_BF16) {                                      // the activation rows rounded to bf16 once, then the weight stream or the matrix cores
+        const DevTensor *ws1[1] = {&w};
+        float *outs1[1] = {out};
+        HIP_TRY(launch_f32_to_bf16(x_f32, xb_, (size_t)T * K, stream_));
+        return linear_bf16(ws1, outs1, nullptr, 1, K, T, ld_out, resid, epi);
+    }
     if (mmf16_applicable(w.type, (int)w.N, K, T, w.data, x_f32, out) && w.n_expert == 1 && (ld_out & 3) == 0)      // a batch against an f16 tensor: matrix cores
         return launch_mmf16(w.data, (int)w.N, K, x_f32, T, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
     return launch_mmv_float(w.type, w.data, (int)w.N, K, x_f32, T, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
 }
 
-hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs, int n, const ActQuant &aq, const float *x_f32, int T) {
-    bool all_q = true;
-    for (int i = 0; i < n; i++) all_q &= is_quant(ws[i]->type);
+// up to three bf16 tensors over the activation rows in xb_ (already rounded): fewer than 8 tokens and narrow tensors take the weight stream - all segments in
+// one launch, bias / residual / SwiGLU in its epilogue - the rest the matrix cores, one launch per tensor.  EPI_SWIGLU: ws = {gate, up}, outs[0] gets silu(g) * u
+// (outs[1] is scratch for the matrix-core form).  ld_out: of outs[0] when there is one tensor, else every tensor's own row count.
+// (the one place that decides between the two bf16 kernels: every tensor of the launch must take the matrix cores, else all take the stream)
+static bool bf16_takes_mfma(const DevTensor *const *ws, float *const *outs, int n, int K, int T, int ld_out, const void *xb) {
+    bool mfma = true;
+    for (int i = 0; i < n; i++) mfma &= mmbf16_applicable(T_BF16, (int)ws[i]->N, K, T, ws[i]->data, xb, outs[i]) && ws[i]->n_expert == 1 && ((n == 1 ? ld_out : (int)ws[i]->N) & 3) == 0;
+    return mfma;
+}
+
+hipError_t Context::linear_bf16(const DevTensor *const *ws, float *const *outs, const float *const *bias, int n, int K, int T, int ld_out, const float *resid, int epi) {
+    if (bf16_takes_mfma(ws, outs, n, K, T, ld_out, xb_)) {
+        for (int i = 0; i < n; i++)
+            HIP_TRY(launch_mmbf16(ws[i]->data, (int)ws[i]->N, K, xb_, T, outs[i], n == 1 ? ld_out : (int)ws[i]->N, epi == EPI_ADD ? resid : nullptr, bias ? bias[i] : nullptr, 1.0f, false, stream_));
+        if (epi == EPI_SWIGLU) HIP_TRY(launch_swiglu(outs[0], outs[1], outs[0], (int64_t)T * ws[0]->N, stream_));
+        return hipSuccess;
+    }
+    MMVBF16Args a{};
+    a.n_seg = n; a.K = K; a.epi = epi; a.resid = epi == EPI_ADD ? resid : nullptr; a.xb = xb_;
+    for (int i = 0; i < n; i++) a.seg[i] = MMVBF16Seg{ws[i]->data, outs[i], bias ? bias[i] : nullptr, (int)ws[i]->N, n == 1 ? ld_out : (int)ws[i]->N, ws[i]->row_bytes};
+    return launch_mmv_bf16_tokens(a, T, stream_);
+}
+
+hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs, int n, const ActQuant &aq, const float *x_f32, int T, const float *const *bias, bool *bias_done) {
+    bool all_q = true, all_bf = n <= 3;
+    for (int i = 0; i < n; i++) { all_q &= is_quant(ws[i]->type); all_bf &= ws[i]->type == T_BF16 && ws[i]->n_expert == 1; }
     const int K = (int)ws[0]->K;
+    if (all_bf) {                                                // Q | K | V of a bf16 layer: one rounding of the rows, one launch, the qwen2 biases in its epilogue
+        HIP_TRY(launch_f32_to_bf16(x_f32, xb_, (size_t)T * K, stream_));
+        HIP_TRY(linear_bf16(ws, outs, bias, n, K, T, 0, nullptr, EPI_STORE));
+        if (bias_done) *bias_done = true;
+        return hipSuccess;
+    }
     bool all_mmq = true, all_ks = true;
     // (IQ4_XS: through its plane set, the signed format - Q | K | V of the IQ4_XS mixes run as one launch like the K-quants')
     for (int i = 0; i < n; i++) { all_mmq &= mmq_applicable(ws[i]->type, K, T) || (ws[i]->type == T_IQ4_XS && planes_small(*ws[i], K, T)); all_ks &= mmq_ksplit_applicable(ws[i]->type, K, T); }
@@ -1264,6 +1309,7 @@ bool Context::engine_prepare() {
         const LayerWeights &L = model->layers[(size_t)il];
         if (L.bq.valid() || L.bk.valid() || L.bv.valid()) return false;
         if (!is_quant(L.wo.type) || act_is_q80(L.wo.type)) return false;
+        for (const DevTensor *t : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down}) if (t->type == T_BF16) return false;   // (the engine has no bf16 form)
         EngineLayer &m = el[(size_t)il];
         m.qk_norm = L.q_norm.valid() || L.k_norm.valid() || (il + 1 < hp.n_layer && (model->layers[(size_t)il + 1].q_norm.valid() || model->layers[(size_t)il + 1].k_norm.valid()));
         auto base = [&](MMVQArgs &a, int n_seg, int K, int epi, int fuse, const float *nx, const float *nw, const ActQuant &aq) {
@@ -1504,9 +1550,11 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
         }
         const DevTensor *ws[3] = {&L.wq, &L.wk, &L.wv};
         float *outs[3] = {q_, k_, v_};
-        if (!(engine && il > 0) && !qkv_in_attn) HIP_TRY(linear_multi(ws, outs, 3, aq_e_, xn_, T));
+        const float *qkv_bias[3] = {L.bq.valid() ? (const float *)L.bq.data : nullptr, L.bk.valid() ? (const float *)L.bk.data : nullptr, L.bv.valid() ? (const float *)L.bv.data : nullptr};
+        bool bias_done = false;                                  // (a bf16 layer adds the biases in its launch's epilogue: the same f32 add)
+        if (!(engine && il > 0) && !qkv_in_attn) HIP_TRY(linear_multi(ws, outs, 3, aq_e_, xn_, T, qkv_bias, &bias_done));
         pending_fuse_ = Fuse();
-        if (!qkv_in_attn && (L.bq.valid() || L.bk.valid() || L.bv.valid()))       // qwen2-style attention biases: all T rows of the three projections in one launch
+        if (!qkv_in_attn && !bias_done && (L.bq.valid() || L.bk.valid() || L.bv.valid()))       // qwen2-style attention biases: all T rows of the three projections in one launch
             HIP_TRY(launch_add_qkv_bias(q_, k_, v_, L.bq.valid() ? (const float *)L.bq.data : nullptr, L.bk.valid() ? (const float *)L.bk.data : nullptr,
                                         L.bv.valid() ? (const float *)L.bv.data : nullptr, H * D, G * D, T, stream_));
         if (!qkv_in_attn) prof_mark("qkv");
@@ -1734,6 +1782,23 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
             if (gq && uq && L.gate.type == L.up.type && !ffn_mmq) {
                 MMVQSeg segs[2] = {make_seg(L.gate, ffn_, FF, nullptr, nullptr), make_seg(L.up, ffn_u_, FF, nullptr, nullptr)};
                 HIP_TRY(mmvq_tokens(segs, 2, E, T, EPI_SWIGLU, aq_e_, stream_, fz));
+            } else if (L.gate.type == T_BF16 && L.up.type == T_BF16 && L.gate.N == L.up.N) {
+                // bf16 gate | up: one rounding of the rows; the weight stream computes both in one launch with SwiGLU in its epilogue, a prompt batch runs the
+                // two matrix-core products and the SwiGLU pass (quantising for a quantised ffn_down in that pass, as below)
+                const DevTensor *gu[2] = {&L.gate, &L.up};
+                float *go[2] = {ffn_, ffn_u_};
+                HIP_TRY(launch_f32_to_bf16(xn_, xb_, (size_t)T * E, stream_));
+                if (T > 1 && is_quant(L.down.type) && (FF % 256) == 0 && bf16_takes_mfma(gu, go, 2, E, T, 0, xb_)) {
+                    HIP_TRY(linear_bf16(gu, go, nullptr, 2, E, T, 0, nullptr, EPI_STORE));
+                    const bool pl = !act_is_q80(L.down.type) && T >= 3;
+                    HIP_TRY(launch_swiglu_quant(ffn_, ffn_u_, FF, T, aq_ff_, !act_is_q80(L.down.type), act_is_q80(L.down.type), stream_,
+                                                pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
+                    prep_owner_ = nullptr;
+                    if (pl) prep_written(aq_ff_, FF, T);
+                    swiglu_quantised = true;
+                } else {
+                    HIP_TRY(linear_bf16(gu, go, nullptr, 2, E, T, 0, nullptr, EPI_SWIGLU));
+                }
             } else if (ffn_ks) {                               // batched decode step: gate and up in one launch
                 if (L.gate.type != T_Q6_K || L.up.type != T_Q6_K) HIP_TRY(ensure_prep(aq_e_, E, T));
                 MMQSeg sg[2] = {{L.gate.data, L.gate.row_bytes, (int)L.gate.N, L.gate.type, ffn_, FF, nullptr, 0},
@@ -2372,6 +2437,11 @@ double Context::bench_weight_sweep(int iters, uint64_t *bytes_out, int *launches
                 Fuse fz;
                 if (can_fuse(E, 1)) { fz.mode = 1; fz.x = x_; fz.w = (const float *)L.ffn_norm.data; fz.eps = hp.eps; }
                 HIP_TRY(mmvq_tokens(segs, 2, E, 1, EPI_SWIGLU, aq_e_, stream_, fz));
+            } else if (L.gate.type == T_BF16 && L.up.type == T_BF16 && L.gate.N == L.up.N) {
+                const DevTensor *gu[2] = {&L.gate, &L.up};
+                float *go[2] = {ffn_, ffn_u_};
+                HIP_TRY(launch_f32_to_bf16(xn_, xb_, (size_t)E, stream_));
+                HIP_TRY(linear_bf16(gu, go, nullptr, 2, E, 1, 0, nullptr, EPI_SWIGLU));
             }
             const bool halves = L.down_lo.valid() && L.down_hi.valid() && !hp.tp_exchange;      // (run_layers: the column halves, two launches)
             if (halves) {

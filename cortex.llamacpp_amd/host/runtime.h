@@ -174,7 +174,10 @@ class Context {
     hipError_t run_output(int n_out, int out_base);
     hipError_t linear(const DevTensor &w, const ActQuant &aq, const float *x_f32, int K, int T, float *out, int ld_out,
                       const float *resid, int epi);
-    hipError_t linear_multi(const DevTensor *const *ws, float *const *outs, int n, const ActQuant &aq, const float *x_f32, int T);
+    // bias / bias_done (optional): per-tensor bias vectors a launch may add in its epilogue; *bias_done says it did (else the caller adds them)
+    hipError_t linear_multi(const DevTensor *const *ws, float *const *outs, int n, const ActQuant &aq, const float *x_f32, int T, const float *const *bias = nullptr,
+                            bool *bias_done = nullptr);
+    hipError_t linear_bf16(const DevTensor *const *ws, float *const *outs, const float *const *bias, int n, int K, int T, int ld_out, const float *resid, int epi);
     void prof_mark(const char *name);
     void prof_begin();
     void prof_end();
@@ -204,6 +207,7 @@ class Context {
     // activations
     float *x_ = nullptr, *xn_ = nullptr, *q_ = nullptr, *k_ = nullptr, *v_ = nullptr, *att_ = nullptr, *ffn_ = nullptr, *ffn_u_ = nullptr;
     float *xo_ = nullptr, *router_ = nullptr, *moe_out_ = nullptr;
+    uint16_t *xb_ = nullptr;      // activation rows rounded to bf16 for a contraction against a bf16 tensor
     float *tp_part_ = nullptr, *tp_logits_ = nullptr;   // row split: this rank's partial sums / logits slices before the exchange
     size_t tp_logits_rows_ = 0;
     hipError_t tp_reduce_into_x(int T);                 // x_ = sum over ranks of tp_part_

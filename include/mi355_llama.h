@@ -44,7 +44,7 @@ enum mi355_status {
 /* ggml type ids as stored in GGUF (upstream ggml.h enum ggml_type; used at llama_engine.cc:272-281) */
 enum mi355_type {
     MI355_TYPE_F32 = 0, MI355_TYPE_F16 = 1, MI355_TYPE_Q4_0 = 2, MI355_TYPE_Q8_0 = 8,
-    MI355_TYPE_Q4_K = 12, MI355_TYPE_Q5_K = 13, MI355_TYPE_Q6_K = 14, MI355_TYPE_Q8_K = 15, MI355_TYPE_IQ4_XS = 23,
+    MI355_TYPE_Q4_K = 12, MI355_TYPE_Q5_K = 13, MI355_TYPE_Q6_K = 14, MI355_TYPE_Q8_K = 15, MI355_TYPE_IQ4_XS = 23, MI355_TYPE_BF16 = 30,
 };
 
 /* ------------------------------------------------------------------ backend */
@@ -201,9 +201,20 @@ MI355_API int32_t mi355_debug_layer_out(mi355_context *ctx, int32_t il, float *d
 MI355_API int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n_per_row, int64_t n_rows, void *out_blocks);
 /* y[T][N] = W[N][K] . x[T][K]; W is ggml-layout blocks of `type`.  isum/msum (nullable):
  * per (token, row, block) integer partial sums for bit-exact checks.  IQ4_XS (type 23, Q8_K activations): isum is the
- * super-block's sum over sub-blocks of (ls - 32) * sum(level * q8), msum is 0. */
+ * super-block's sum over sub-blocks of (ls - 32) * sum(level * q8), msum is 0.  BF16 (type 30): the rows of x are rounded to bf16
+ * (ggml's f32 -> bf16) and the model path's kernel runs: the matrix cores from 8 tokens on, else the bf16 weight stream. */
 MI355_API int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T,
                                float *y, int32_t *isum, int32_t *msum);
+/* ggml's f32 -> bf16 rounding as the bf16 kernels' activation pass does it (nearest, ties to even; NaN quieted; subnormals kept); n % 8 == 0 */
+MI355_API int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out);
+/* Up to three BF16 tensors W[s] ([N[s]][K] bf16 rows, K % 8 == 0; the matrix cores want K % 16 == 0) against the same T rows of x, as a decoder layer launches them:
+ *   y[s][t][n] = W[s][n] . bf16(x[t]) + bias[s][n]                                  (bias and its entries nullable)
+ *   epi 1 (one tensor): y[0] = resid + that, resid [T][N[0]];  epi 2 (two tensors of equal N: ffn_gate, ffn_up): y[0] = silu(y0) * y1, y[1] is not written.
+ * path 0: the model path's choice; 1: the weight stream (all tensors in ONE launch per token chunk, the epilogue fused); 2: the matrix cores (one launch per
+ * tensor, SwiGLU as its own pass).  tokens_per_launch (stream only): 0 = chunks of 16, 8, 4, 2, 1; else every launch takes that many tokens (1, 2, 4, 8, 16;
+ * T a multiple of it).  use_graph 1: the launches are captured into a graph and replayed. */
+MI355_API int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, const float *const *bias,
+                                    const float *resid, int32_t epi, int32_t path, int32_t tokens_per_launch, int32_t use_graph, float *const *y);
 /* ffn_gate and ffn_up (one K-quant type or IQ4_XS, N rows each, N % 32 == 0) against the same T activation rows with SwiGLU in the
  * epilogue, as the prompt path launches them (mmq_planes2_swiglu_kernel): y[t][n] = silu(Wg[n] . x[t]) * (Wu[n] . x[t]).
  * Shapes too small for that launch are refused unless the debug option "mmq_tiles" = 4 forces the kernel. */
