@@ -524,7 +524,7 @@ int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const fl
     if (!wsrc.up(W, grow * N) || !wdev.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
     hipError_t e = launch_repack_rows(type, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, N, nullptr);
     if (e != hipSuccess) return hip_fail(e, "repack");
-    const bool quant = type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0 || type == T_Q2_K || type == T_Q3_K || type == T_Q4_0 || type == T_Q5_0 || type == T_IQ4_NL || type == T_IQ4_XS;
+    const bool quant = type_is_quant(type);
     if (quant) {
         e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, !act_is_q80(type), act_is_q80(type), nullptr);
         if (e != hipSuccess) return hip_fail(e, "quantize");
@@ -549,7 +549,7 @@ int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const fl
             if (e == hipSuccess) e = hipDeviceSynchronize();
             if (e != hipSuccess) return hip_fail(e, "mmq_ksplit");
         } else
-        if (mmq_applicable(type, (int)K, (int)T) || ((type == T_Q2_K || type == T_Q3_K || type == T_IQ4_XS) && T >= 32 && g_op_mmq_planes)) {   // (Q2_K / Q3_K / IQ4_XS: planes only)
+        if (mmq_applicable(type, (int)K, (int)T) || (type_is_planes_only(type) && T >= 32 && g_op_mmq_planes)) {   // (Q2_K / Q3_K / IQ4_XS: planes only)
             DevBuf bh(mmq_prep_bytes((int)K, (int)T)), bl(mmq_prep_bytes((int)K, (int)T));
             if (!bh.p || !bl.p) return MI355_ERR_OOM;
             e = launch_mmq_prep(ab.q, (int)K, (int)T, bh.as<int8_t>(), bl.as<int8_t>(), nullptr);

@@ -30,6 +30,15 @@ __host__ __device__ inline size_t ggml_row_bytes(int t, int64_t n) {
 // the CPU backend's activation format for a weight type: Q8_0 blocks for the 32-element formats, Q8_K for the K-quants
 __host__ __device__ constexpr bool act_is_q80(int t) { return t == T_Q8_0 || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL; }
 
+// ---- type sets the host code asks about (what a kernel implements is stated by that kernel's own *_applicable) ----
+constexpr bool type_is_kq456(int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K; }
+// reach the matrix cores only through their plane sets (no expand-on-the-fly kernel)
+constexpr bool type_is_planes_only(int t) { return t == T_Q2_K || t == T_Q3_K || t == T_IQ4_XS; }
+// the quantised weight types: contracted against a quantised copy of the activation (Q8_0 where act_is_q80, else Q8_K)
+constexpr bool type_is_quant(int t) { return type_is_kq456(t) || type_is_planes_only(t) || act_is_q80(t); }
+// blocks that are not 16-byte aligned on disk: the upload regroups each row into aligned planes (launch_repack_rows)
+constexpr bool type_is_repacked(int t) { return t == T_Q6_K || type_is_planes_only(t) || act_is_q80(t); }
+
 // ---- device-resident weight row layouts --------------------------------------------------
 // Q4_K / Q5_K rows stay in ggml order (144 / 176 B super-blocks are 16-B aligned: header | [qh] | qs).
 // Q6_K (210 B) and Q8_0 (34 B) blocks are not 16-B aligned, so at upload each ROW is regrouped into

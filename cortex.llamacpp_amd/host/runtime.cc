@@ -61,7 +61,7 @@ static RopeArgs layer_rope(const RopeArgs &ra, const LayerWeights &L, float eps)
 }
 
 static bool type_supported(int t) {
-    return t == T_F32 || t == T_F16 || t == T_Q8_0 || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q2_K || t == T_Q3_K || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL || t == T_IQ4_XS || t == T_BF16;
+    return t == T_F32 || t == T_F16 || t == T_BF16 || type_is_quant(t);
 }
 
 Model *model_load(const std::string &path, int main_gpu, std::string &err, int &status, int prefill_planes, int tp_rank, int tp_size) {
@@ -240,7 +240,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
         dst.ggml_bytes = pl.src_bytes;
         plan.push_back(pl);
         total += (dst.bytes + 255) & ~(size_t)255;
-        if (dst.type == T_Q6_K || dst.type == T_Q8_0 || dst.type == T_Q2_K || dst.type == T_Q3_K || dst.type == T_Q4_0 || dst.type == T_Q5_0 || dst.type == T_IQ4_NL || dst.type == T_IQ4_XS || dst.row_bytes != ggml_row_bytes(dst.type, dst.K)) max_stage = std::max(max_stage, pl.src_bytes);
+        if (type_is_repacked(dst.type) || dst.row_bytes != ggml_row_bytes(dst.type, dst.K)) max_stage = std::max(max_stage, pl.src_bytes);
     };
     want("token_embd.weight", m->tok_embd, true);
     if (hp.encoder) {
@@ -302,7 +302,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             static const bool halves_on = !(getenv("MI355_DOWN_HALVES") && getenv("MI355_DOWN_HALVES")[0] == '0');
             auto kb_ok = [](int64_t K) { const int64_t kb = (K + 2047) >> 11; return kb == 1 || kb == 2 || kb == 3 || kb == 4 || kb == 6 || kb == 7 || kb == 10; };
             const int64_t Kd = L.down.K;
-            if (halves_on && !fail && (L.down.type == T_Q4_K || L.down.type == T_Q5_K || L.down.type == T_Q6_K) && !kb_ok(Kd) && Kd % 512 == 0 && kb_ok(Kd / 2)) {
+            if (halves_on && !fail && type_is_kq456(L.down.type) && !kb_ok(Kd) && Kd % 512 == 0 && kb_ok(Kd / 2)) {
                 want(p + "ffn_down.weight", L.down_lo, true, SPLIT_COLS, 0, 2);
                 want(p + "ffn_down.weight", L.down_hi, true, SPLIT_COLS, 1, 2);
             }
@@ -397,7 +397,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
     for (const Plan &pl : plan) {
         DevTensor &d = *pl.dst;
         d.data = arena + pl.off;
-        const bool direct = !(d.type == T_Q6_K || d.type == T_Q8_0 || d.type == T_Q2_K || d.type == T_Q3_K || d.type == T_Q4_0 || d.type == T_Q5_0 || d.type == T_IQ4_NL || d.type == T_IQ4_XS) && (pl.ti->n_dims == 1 || d.row_bytes == ggml_row_bytes(d.type, d.K));
+        const bool direct = !type_is_repacked(d.type) && (pl.ti->n_dims == 1 || d.row_bytes == ggml_row_bytes(d.type, d.K));
         hipError_t e;
         const uint8_t *src = (const uint8_t *)pl.ti->data + pl.src_off;
         uint8_t *to = direct ? d.data : stage;
@@ -945,7 +945,6 @@ void Context::prof_end() {
 }
 
 // ------------------------------------------------------------------------------------------ linear layers
-static bool is_quant(int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0 || t == T_Q2_K || t == T_Q3_K || t == T_Q4_0 || t == T_Q5_0 || t == T_IQ4_NL || t == T_IQ4_XS; }
 
 static MMVQSeg make_seg(const DevTensor &w, float *out, int ld_out, const float *resid, const int32_t *esel) {
     MMVQSeg s{};
@@ -960,6 +959,15 @@ static void chunk_act(MMVQArgs &a, const ActQuant &aq, int K, int t0) {
     a.abs = aq.bsums ? aq.bsums + (size_t)t0 * (K / 16) : nullptr;
     a.aq0 = aq.qs0 ? aq.qs0 + (size_t)t0 * K : nullptr;
     a.ad0 = aq.d0 ? aq.d0 + (size_t)t0 * (K / 32) : nullptr;
+}
+
+// a single-token mat-vec launch's description without its segments: the activation codes, the epilogue, the fused activation prologue (Fuse::mode)
+static MMVQArgs single_token_desc(int n_seg, int K, int epi, int fuse, const float *nx, const float *nw, float eps, const ActQuant &aq) {
+    MMVQArgs a{};
+    a.n_seg = n_seg; a.K = K; a.T = 1; a.epi = epi;
+    a.fuse_mode = fuse; a.nx = nx; a.nw = nw; a.neps = eps;
+    chunk_act(a, aq, K, 0);
+    return a;
 }
 
 // up to 3 quantised weight tensors sharing one activation (fused Q/K/V), or one tensor with an epilogue
@@ -995,14 +1003,15 @@ hipError_t Context::ensure_prep(const ActQuant &aq, int K, int T) {
 }
 
 // Q2_K / Q3_K / IQ4_XS tensors reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
+// (the types with an exact Q8_0-layout copy: act_is_q80 without Q8_0 itself, which needs none - so the chain stays spelled out)
 static bool q80_copy(const DevTensor &w, int K, int T) {
     return (w.type == T_Q4_0 || w.type == T_Q5_0 || w.type == T_IQ4_NL) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
 }
-static bool planes_small(const DevTensor &w, int K, int T) { return (w.type == T_Q2_K || w.type == T_Q3_K || w.type == T_IQ4_XS) && w.planes && T >= 32 && (K % 256) == 0; }
+static bool planes_small(const DevTensor &w, int K, int T) { return type_is_planes_only(w.type) && w.planes && T >= 32 && (K % 256) == 0; }
 
 hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *x_f32, int K, int T, float *out, int ld_out,
                            const float *resid, int epi) {
-    if (is_quant(w.type)) {
+    if (type_is_quant(w.type)) {
         if (mmq_q80_applicable(w.type, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs0)   // prompt processing, Q8_0 weights
             return launch_mmq_q80(w.data, w.row_bytes, (int)w.N, K, T, aq, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
         // (bh_over_ / bl_over_: the caller prepared the block-sum planes of a larger batch that aq's rows are a slice of - the expert loop)
@@ -1062,7 +1071,7 @@ hipError_t Context::linear_bf16(const DevTensor *const *ws, float *const *outs, 
 
 hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs, int n, const ActQuant &aq, const float *x_f32, int T, const float *const *bias, bool *bias_done) {
     bool all_q = true, all_bf = n <= 3;
-    for (int i = 0; i < n; i++) { all_q &= is_quant(ws[i]->type); all_bf &= ws[i]->type == T_BF16 && ws[i]->n_expert == 1; }
+    for (int i = 0; i < n; i++) { all_q &= type_is_quant(ws[i]->type); all_bf &= ws[i]->type == T_BF16 && ws[i]->n_expert == 1; }
     const int K = (int)ws[0]->K;
     if (all_bf) {                                                // Q | K | V of a bf16 layer: one rounding of the rows, one launch, the qwen2 biases in its epilogue
         HIP_TRY(launch_f32_to_bf16(x_f32, xb_, (size_t)T * K, stream_));
@@ -1156,32 +1165,25 @@ bool Context::mega_prepare() {
     if ((E % 2048) != 0 || (FF % 256) != 0 || !decode_mega_applicable(kb_e, kb_ff, H / G, cp.type_k, cp.type_v, hp.qk_norm)) return false;
     RopeArgs ra = rope_args(*model, false);
     if (ra.neox || (ra.n_rot % 4) != 0 || D != 128 || !kv_store_fast_applicable(G, D, cp.type_k, cp.type_v, ra)) return false;
-    auto kq = [](int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K; };
     std::vector<MegaLayer> ml((size_t)hp.n_layer);
     const int blocks = mega_blocks();
     size_t lds = 0;
     for (int il = 0; il < hp.n_layer; il++) {
         const LayerWeights &L = model->layers[(size_t)il];
-        if (!kq(L.wq.type) || !kq(L.wk.type) || !kq(L.wv.type) || !kq(L.wo.type) || !kq(L.gate.type) || !kq(L.up.type) || !kq(L.down.type)) return false;
+        if (!type_is_kq456(L.wq.type) || !type_is_kq456(L.wk.type) || !type_is_kq456(L.wv.type) || !type_is_kq456(L.wo.type) || !type_is_kq456(L.gate.type) || !type_is_kq456(L.up.type) || !type_is_kq456(L.down.type)) return false;
         if (L.gate.type != L.up.type || L.gate.N != L.up.N || L.bq.valid() || L.bk.valid() || L.bv.valid()) return false;
         if ((int)L.wq.K != E || (int)L.wo.K != E || (int)L.gate.K != E || (int)L.down.K != FF) return false;
         MegaLayer &m = ml[(size_t)il];
-        auto base = [&](MMVQArgs &a, int n_seg, int K, int epi, int fuse, const float *nx, const float *nw, const ActQuant &aq) {
-            a = MMVQArgs{};
-            a.n_seg = n_seg; a.K = K; a.T = 1; a.epi = epi;
-            a.fuse_mode = fuse; a.nx = nx; a.nw = nw; a.neps = hp.eps;
-            chunk_act(a, aq, K, 0);
-        };
-        base(m.qkv, 3, E, EPI_STORE, 1, x_, (const float *)L.attn_norm.data, aq_e_);
+        m.qkv = single_token_desc(3, E, EPI_STORE, 1, x_, (const float *)L.attn_norm.data, hp.eps, aq_e_);
         m.qkv.seg[0] = make_seg(L.wq, q_, (int)L.wq.N, nullptr, nullptr);
         m.qkv.seg[1] = make_seg(L.wk, k_, (int)L.wk.N, nullptr, nullptr);
         m.qkv.seg[2] = make_seg(L.wv, v_, (int)L.wv.N, nullptr, nullptr);
-        base(m.wo, 1, E, EPI_ADD, 0, nullptr, nullptr, aq_o_);
+        m.wo = single_token_desc(1, E, EPI_ADD, 0, nullptr, nullptr, hp.eps, aq_o_);
         m.wo.seg[0] = make_seg(L.wo, x_, E, x_, nullptr);
-        base(m.gate_up, 2, E, EPI_SWIGLU, 1, x_, (const float *)L.ffn_norm.data, aq_e_);
+        m.gate_up = single_token_desc(2, E, EPI_SWIGLU, 1, x_, (const float *)L.ffn_norm.data, hp.eps, aq_e_);
         m.gate_up.seg[0] = make_seg(L.gate, ffn_, FF, nullptr, nullptr);
         m.gate_up.seg[1] = make_seg(L.up, ffn_u_, FF, nullptr, nullptr);
-        base(m.down, 1, FF, EPI_ADD, 2, ffn_, nullptr, aq_ff_);
+        m.down = single_token_desc(1, FF, EPI_ADD, 2, ffn_, nullptr, hp.eps, aq_ff_);
         m.down.seg[0] = make_seg(L.down, x_, E, x_, nullptr);
         for (MMVQArgs *a : {&m.qkv, &m.wo, &m.gate_up, &m.down}) {
             if (!mmvq_fast_applicable(*a)) return false;
@@ -1308,28 +1310,22 @@ bool Context::engine_prepare() {
     for (int il = 0; il < hp.n_layer; il++) {
         const LayerWeights &L = model->layers[(size_t)il];
         if (L.bq.valid() || L.bk.valid() || L.bv.valid()) return false;
-        if (!is_quant(L.wo.type) || act_is_q80(L.wo.type)) return false;
+        if (!type_is_quant(L.wo.type) || act_is_q80(L.wo.type)) return false;
         for (const DevTensor *t : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down}) if (t->type == T_BF16) return false;   // (the engine has no bf16 form)
         EngineLayer &m = el[(size_t)il];
         m.qk_norm = L.q_norm.valid() || L.k_norm.valid() || (il + 1 < hp.n_layer && (model->layers[(size_t)il + 1].q_norm.valid() || model->layers[(size_t)il + 1].k_norm.valid()));
-        auto base = [&](MMVQArgs &a, int n_seg, int K, int epi, int fuse, const float *nx, const float *nw, const ActQuant &aq) {
-            a = MMVQArgs{};
-            a.n_seg = n_seg; a.K = K; a.T = 1; a.epi = epi;
-            a.fuse_mode = fuse; a.nx = nx; a.nw = nw; a.neps = hp.eps;
-            chunk_act(a, aq, K, 0);
-        };
-        base(m.wo, 1, E, EPI_ADD, 0, nullptr, nullptr, aq_o_);
+        m.wo = single_token_desc(1, E, EPI_ADD, 0, nullptr, nullptr, hp.eps, aq_o_);
         m.wo.seg[0] = make_seg(L.wo, x_, E, x_, nullptr);
-        base(m.gu, 2, E, EPI_SWIGLU, 1, x_, (const float *)L.ffn_norm.data, aq_e_);
+        m.gu = single_token_desc(2, E, EPI_SWIGLU, 1, x_, (const float *)L.ffn_norm.data, hp.eps, aq_e_);
         m.gu.seg[0] = make_seg(L.gate, ffn_, FF, nullptr, nullptr);
         m.gu.seg[1] = make_seg(L.up, ffn_u_, FF, nullptr, nullptr);
-        base(m.dn, 1, FF, EPI_ADD, 2, ffn_, nullptr, aq_ff_);
+        m.dn = single_token_desc(1, FF, EPI_ADD, 2, ffn_, nullptr, hp.eps, aq_ff_);
         m.dn.seg[0] = make_seg(L.down, x_, E, x_, nullptr);
         m.has_qkv = il + 1 < hp.n_layer ? 1 : 0;
         m.qkv = MMVQArgs{};
         if (m.has_qkv) {
             const LayerWeights &N = model->layers[(size_t)il + 1];
-            base(m.qkv, 3, E, EPI_STORE, 1, x_, (const float *)N.attn_norm.data, aq_e_);
+            m.qkv = single_token_desc(3, E, EPI_STORE, 1, x_, (const float *)N.attn_norm.data, hp.eps, aq_e_);
             m.qkv.seg[0] = make_seg(N.wq, q_, (int)N.wq.N, nullptr, nullptr);
             m.qkv.seg[1] = make_seg(N.wk, k_, (int)N.wk.N, nullptr, nullptr);
             m.qkv.seg[2] = make_seg(N.wv, v_, (int)N.wv.N, nullptr, nullptr);
@@ -1370,7 +1366,6 @@ hipError_t Context::run_layers_encoder(int T, int n_kv_cap) {
     const HParams &hp = model->hp;
     const int E = hp.n_embd, FF = hp.n_ff, H = hp.n_head, G = hp.n_head_kv, D = hp.head_dim;
     RopeArgs ra = rope_args(*model, true);
-    const float kq_scale = 1.0f / sqrtf((float)D);
     const int n_kv_max = std::max(n_kv_cap, 1);
     att_splits_ = flash_attn_pick_splits(T, G, n_kv_max);
     last_layers_mega_ = false; last_layers_engine_ = false;
@@ -1383,7 +1378,7 @@ hipError_t Context::run_layers_encoder(int T, int n_kv_cap) {
     // quantised weight tensors contract against a quantised copy of their input (Q8_K for K-quants, Q8_0 otherwise), float tensors against the f32 rows
     auto quantise_for = [&](const float *x, int K, ActQuant &aq, std::initializer_list<const DevTensor *> ws) -> hipError_t {
         bool k = false, z = false;
-        for (const DevTensor *w : ws) if (is_quant(w->type)) { if (act_is_q80(w->type)) z = true; else k = true; }
+        for (const DevTensor *w : ws) if (type_is_quant(w->type)) { if (act_is_q80(w->type)) z = true; else k = true; }
         if (!k && !z) return hipSuccess;
         prep_owner_ = nullptr;
         return launch_quantize(x, K, T, aq, k, z, stream_);
@@ -1397,12 +1392,7 @@ hipError_t Context::run_layers_encoder(int T, int n_kv_cap) {
         prof_mark("qkv");
         HIP_TRY(launch_rope_kv_store(q_, k_, v_, T, H, G, D, d_pos_, d_cell_, ra, kv_[(size_t)il], cp.type_k, cp.type_v, (int)cp.n_ctx, rope_cs_, stream_));
         prof_mark("rope_kv");
-        AttnArgs aa{};
-        aa.q = q_; aa.out = att_; aa.kv = kv_[(size_t)il]; aa.type_k = cp.type_k; aa.type_v = cp.type_v;
-        aa.T = T; aa.H = H; aa.G = G; aa.D = D; aa.n_ctx = (int)cp.n_ctx;
-        aa.cell_pos = d_cell_pos_; aa.cell_seq = d_cell_seq_; aa.tok_pos = d_pos_open_; aa.tok_seq = d_seq_;
-        aa.n_kv_dev = d_nkv_; aa.n_kv_max = n_kv_max; aa.scale = kq_scale; aa.part = att_part_;
-        aa.out_q = nullptr; aa.out_q8k = false; aa.out_q80 = false;
+        AttnArgs aa = attn_args(il, T, n_kv_max, d_pos_open_);    // (no quantised copy of the output: out_q stays null)
         aa.splits = att_splits_;
         aa.pf_splits = flash_attn_prefill_splits(T, H, G, D, n_kv_max);
         while (aa.pf_splits > 1 && flash_attn_workspace_floats(T, H, D, aa.pf_splits) > att_part_floats_) aa.pf_splits >>= 1;
@@ -1429,458 +1419,518 @@ hipError_t Context::run_layers_encoder(int T, int n_kv_cap) {
     return hipSuccess;
 }
 
+// ---- the llama-graph layer, block by block.  run_layers (below) is the loop; every choice of launch form is stated once, in the block that makes it, and
+// bench_weight_sweep asks the same functions.
+
+// what one run_layers call fixes for all its layers (the environment is read once per process)
+Context::Step Context::step_constants(int T, int n_kv_cap) const {
+    static const int attn_mode = getenv("MI355_ATTN_MODE") ? atoi(getenv("MI355_ATTN_MODE")) : 2;
+    static const bool rope_fast_env = !(getenv("MI355_ROPE_FAST") && getenv("MI355_ROPE_FAST")[0] == '0');
+    static const bool fuse_down_env = !(getenv("MI355_FUSE_DOWN") && getenv("MI355_FUSE_DOWN")[0] == '0');
+    const HParams &hp = model->hp;
+    Step st;
+    st.T = T;
+    st.n_kv_max = std::max(n_kv_cap, 1);   // upper bound of occupied cells the kernels are sized for
+    st.ra_step = rope_args(*model, true);  // (each layer's: layer_rope)
+    st.tp = hp.tp_exchange;
+    st.chunk_lists = chunk_lmax_ > 0;
+    st.attn_mode = attn_mode; st.rope_fast = rope_fast_env && g_rope_fast; st.fuse_down_env = fuse_down_env;
+    // attn_output and ffn_down add their result to the residual stream in place; under a row split they leave this rank's partial sum (rank 0 carries the
+    // residual) for the exchange: x = sum over ranks
+    st.out = st.tp ? tp_part_ : x_;
+    st.resid = !st.tp || hp.tp_rank == 0 ? x_ : nullptr;
+    return st;
+}
+
+// the fields of an attention launch's description that no launch form changes (tok_pos: d_pos_; the encoder's open positions)
+AttnArgs Context::attn_args(int il, int T, int n_kv_max, const int32_t *tok_pos) const {
+    const HParams &hp = model->hp;
+    AttnArgs aa{};
+    aa.q = q_; aa.out = att_; aa.kv = kv_[(size_t)il]; aa.type_k = cp.type_k; aa.type_v = cp.type_v;
+    aa.T = T; aa.H = hp.n_head; aa.G = hp.n_head_kv; aa.D = hp.head_dim; aa.n_ctx = (int)cp.n_ctx;
+    aa.cell_pos = d_cell_pos_; aa.cell_seq = d_cell_seq_; aa.tok_pos = tok_pos; aa.tok_seq = d_seq_;
+    aa.n_kv_dev = d_nkv_; aa.n_kv_max = n_kv_max; aa.scale = 1.0f / sqrtf((float)hp.head_dim); aa.part = att_part_;
+    return aa;
+}
+// per-token chunk lists (decode_ubatch): batched steps, or regions in use
+void Context::attn_chunk_lists(AttnArgs &aa) const {
+    aa.tok_chunks = d_chunks_; aa.tok_nchunks = d_chunks_ + (size_t)64 * chunk_stride_; aa.chunk_stride = chunk_stride_;
+    aa.splits = std::max(chunk_cap_, chunk_lmax_);
+}
+
+// Which launches run layer il's attention block.  Launches nothing.
+Context::AttnPlan Context::plan_attn(int il, const Step &st) const {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, T = st.T;
+    AttnPlan p{};
+    p.ra = layer_rope(st.ra_step, L, hp.eps);   // (qwen3: with the layer's q / k norm weights; every kernel either applies them or refuses)
+    p.qkv_float = !type_is_quant(L.wq.type) || !type_is_quant(L.wk.type) || !type_is_quant(L.wv.type);
+    p.qkv_prologue = !p.qkv_float && can_fuse(E, T);
+    AttnArgs &aa = p.aa;
+    aa = attn_args(il, T, st.n_kv_max, d_pos_);
+    const bool o_q = type_is_quant(L.wo.type);
+    aa.out_q = o_q ? &aq_o_ : nullptr; aa.out_q8k = !act_is_q80(L.wo.type); aa.out_q80 = act_is_q80(L.wo.type);   // merged + quantised in one pass
+    p.o_planes = o_q && aa.out_q8k && T >= 3;             // the batched kernels will want the block-sum planes: the merge writes them too
+    if (p.o_planes) { aa.out_bh = mmq_bh_; aa.out_bl = mmq_bl_; }
+    // (parity mode for an f16 cache: the generic launch dispatches to the cell-by-cell kernel with fp16 V accumulation)
+    const bool v16 = fa_v_acc_f16_enabled() && cp.type_k == T_F16 && cp.type_v == T_F16;
+    p.decode_attn = !v16 && flash_attn_decode_applicable(aa, p.ra);
+    if (p.decode_attn) {
+        aa.splits = flash_attn_decode_splits(st.n_kv_max);
+        if (st.chunk_lists) attn_chunk_lists(aa);
+        p.fused_step = st.attn_mode > 0 && flash_attn_decode_fused_applicable(aa, p.ra);
+    }
+    // single-token step: attention + attn_output in one launch (attn_out.hip) where it has a form for the shape
+    // (not where the ranks of a row split exchange through the host callback - the transport of a rig whose ranks SHARE one device: this kernel's
+    // workgroups wait for each other (consumers for the item workgroups' flags), and two processes' copies placed on the same CUs at the same time can
+    // hold each other's item workgroups out - every wait then runs into its bound (round 6: 0x8 on three of eight ranks behind one MI355X at the first
+    // single-token step, profiles/r6_tp_shared_device_trace.txt).  A rank that owns its GPU has the chip to itself.)
+    p.ao_seg = make_seg(L.wo, st.out, E, st.resid, nullptr);
+    p.ao_epi = st.resid ? EPI_ADD : EPI_STORE;
+    p.af = aa;
+    if (p.decode_attn && p.fused_step && st.attn_mode == 2 && !st.engine && il < 255 && !attn_out_off_ && !attn_out_skip_step_ && !(st.tp && tp_uses_host())) {
+        p.af.splits = attn_out_fused_splits(p.af);
+        if (st.chunk_lists) p.af.splits = aa.splits;
+        p.ao_form = attn_out_fused_applicable(p.af, p.ra, p.ao_seg, (int)L.wo.K, p.ao_epi);
+    }
+    // ... and the layer's Q | K | V in front of it in that launch: the RMSNorm -> Q8_K prologue, the three mat-vecs, rope, KV store, attention, merge,
+    // Q8_K and attn_output + residual are ONE launch per layer (outputs bit-identical to the two launches)
+    if (p.ao_form && p.qkv_prologue && !st.tp && d_qkv_gran_ && !(L.bq.valid() || L.bk.valid() || L.bv.valid())) {
+        QKVFuse &qf = p.qf;
+        qf.seg[0] = make_seg(L.wq, q_, (int)L.wq.N, nullptr, nullptr);
+        qf.seg[1] = make_seg(L.wk, k_, (int)L.wk.N, nullptr, nullptr);
+        qf.seg[2] = make_seg(L.wv, v_, (int)L.wv.N, nullptr, nullptr);
+        qf.nx = x_; qf.nw = (const float *)L.attn_norm.data; qf.neps = hp.eps; qf.K = E; qf.gran = d_qkv_gran_;
+        p.qkv_in_attn = qkv_attn_out_applicable(p.af, p.ra, p.ao_seg, (int)L.wo.K, p.ao_epi, qf);
+    }
+    return p;
+}
+
+// Q | K | V as launches of their own: q_, k_, v_ from the layer input (nothing where the plan has them inside the attention launch, or the engine made them)
+hipError_t Context::attn_qkv(int il, const Step &st, const AttnPlan &p) {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, T = st.T;
+    if (p.qkv_in_attn) return hipSuccess;
+    if (st.engine && il > 0) return hipSuccess;               // computed at the end of the previous layer's engine launch
+    if (p.qkv_prologue) {
+        pending_fuse_.mode = 1; pending_fuse_.x = x_; pending_fuse_.w = (const float *)L.attn_norm.data; pending_fuse_.eps = hp.eps;
+    } else {
+        const bool need_k = (type_is_quant(L.wq.type) && !act_is_q80(L.wq.type)) || (type_is_quant(L.wk.type) && !act_is_q80(L.wk.type)) || (type_is_quant(L.wv.type) && !act_is_q80(L.wv.type));
+        const bool need_0 = act_is_q80(L.wq.type) || act_is_q80(L.wk.type) || act_is_q80(L.wv.type);
+        const bool pl = need_k && T >= 3;                      // the batched kernels will want the block-sum planes
+        HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.attn_norm.data, E, T, hp.eps, p.qkv_float ? xn_ : nullptr, &aq_e_, need_k, need_0, stream_,
+                                     pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
+        prep_owner_ = nullptr;
+        if (pl) prep_written(aq_e_, E, T);
+        prof_mark("norm_quant");
+    }
+    const DevTensor *ws[3] = {&L.wq, &L.wk, &L.wv};
+    float *outs[3] = {q_, k_, v_};
+    const float *bias[3] = {L.bq.valid() ? (const float *)L.bq.data : nullptr, L.bk.valid() ? (const float *)L.bk.data : nullptr, L.bv.valid() ? (const float *)L.bv.data : nullptr};
+    bool bias_done = false;                                      // (a bf16 layer adds the biases in its launch's epilogue: the same f32 add)
+    HIP_TRY(linear_multi(ws, outs, 3, aq_e_, xn_, T, bias, &bias_done));
+    pending_fuse_ = Fuse();
+    if (!bias_done && (bias[0] || bias[1] || bias[2]))          // qwen2-style attention biases: all T rows of the three projections in one launch
+        HIP_TRY(launch_add_qkv_bias(q_, k_, v_, bias[0], bias[1], bias[2], hp.n_head * hp.head_dim, hp.n_head_kv * hp.head_dim, T, stream_));
+    prof_mark("qkv");
+    return hipSuccess;
+}
+
+// rope, KV store and the attention itself in the plan's launch form: att_ (and its quantised copy for attn_output) - or, with p.ao_form, attn_output as well
+hipError_t Context::attn_core(int il, const Step &st, const AttnPlan &p) {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int H = hp.n_head, G = hp.n_head_kv, D = hp.head_dim, T = st.T;
+    const KVLayerView &kv = kv_[(size_t)il];
+    unsigned *ao_flags = d_ao_flags_ + (size_t)il * 64 * ATT_SYNC_STRIDE;
+    if (p.qkv_in_attn) {
+        HIP_TRY(launch_qkv_attn_out(p.af, rope_cs_, p.ra, d_cell_, att_counters_, ao_flags, d_ao_gran_, il, d_step_serial_, p.ao_seg, (int)L.wo.K, p.ao_epi, p.qf, stream_));
+        qkv_attn_launches++;
+        prof_mark("qkv");
+    } else if (p.fused_step) {
+        // single-token step: K rope + KV store + attention + split merge + quantise in ONE launch - and, where attn_out.hip has a form for the shape,
+        // the attn_output mat-vec with its residual add in that launch too
+        if (p.ao_form)
+            HIP_TRY(launch_attn_out_fused(p.af, rope_cs_, p.ra, k_, v_, d_cell_, att_counters_, ao_flags, d_ao_gran_, il, d_step_serial_, p.ao_seg, (int)L.wo.K, p.ao_epi, stream_));
+        else
+            HIP_TRY(launch_flash_attn_decode_fused(p.aa, rope_cs_, p.ra, k_, v_, d_cell_, st.attn_mode == 2 ? att_counters_ : nullptr, stream_));
+    } else if (p.decode_attn && batch_distinct_ && store_fuse_enabled()) {
+        // batched step, every token of a different sequence: K rope + KV store inside the attention launch (no token reads another's new cell)
+        HIP_TRY(launch_flash_attn_decode(p.aa, rope_cs_, p.ra, stream_, k_, v_, d_cell_));
+    } else if (p.decode_attn && kv_store_fast_applicable(G, D, cp.type_k, cp.type_v, p.ra)) {
+        // small-batch step: K rope + KV store in one small kernel; q is rotated inside the attention kernel
+        HIP_TRY(launch_kv_store_fast(k_, v_, T, G, D, rope_cs_, p.ra, d_cell_, kv, cp.type_k, cp.type_v, (int)cp.n_ctx, stream_));
+        prof_mark("rope_kv");
+        HIP_TRY(launch_flash_attn_decode(p.aa, rope_cs_, p.ra, stream_));
+    } else {
+        if (st.rope_fast && rope_cs_ && rope_q_kv_store_fast_applicable(H, G, D, cp.type_k, cp.type_v, p.ra))
+            HIP_TRY(launch_rope_q_kv_store_fast(q_, k_, v_, T, H, G, D, rope_cs_, p.ra, d_cell_, kv, cp.type_k, cp.type_v, (int)cp.n_ctx, stream_));
+        else
+            HIP_TRY(launch_rope_kv_store(q_, k_, v_, T, H, G, D, d_pos_, d_cell_, p.ra, kv, cp.type_k, cp.type_v, (int)cp.n_ctx, rope_cs_, stream_));
+        prof_mark("rope_kv");
+        AttnArgs aa = p.aa;
+        aa.splits = att_splits_;
+        // (splits balance the causal tiles of ONE long sequence: sized by what a query of this batch can see - its position + 1 -
+        // not by the cache's high-water mark: 32 sequences of 50-token prompts in a 32000-cell cache need none, and every
+        // extra workgroup would scan the whole cell table)
+        aa.pf_splits = flash_attn_prefill_splits(T, H, G, D, std::min(st.n_kv_max, cur_max_pos_ + 1));
+        while (aa.pf_splits > 1 && flash_attn_workspace_floats(T, H, D, aa.pf_splits) > att_part_floats_) aa.pf_splits >>= 1;
+        HIP_TRY(launch_flash_attn(aa, stream_));
+    }
+    prof_mark("attn");
+    if (p.o_planes) prep_written(aq_o_, (int)L.wo.K, T);       // the attention just re-quantised its output, planes included
+    else if (prep_owner_ == aq_o_.qs) prep_owner_ = nullptr;
+    return hipSuccess;
+}
+
+// attn_output + residual into st.out (nothing where it ran inside the attention launch)
+hipError_t Context::attn_output(int il, const Step &st, const AttnPlan &p) {
+    const LayerWeights &L = model->layers[(size_t)il];
+    if (p.ao_form) return hipSuccess;
+    return linear(L.wo, aq_o_, att_, (int)L.wo.K, st.T, st.out, model->hp.n_embd, st.resid, p.ao_epi);
+}
+
+// "SwiGLU, then quantise for a quantised ffn_down", in one pass: aq_ff_ from gate | up's result.  combined: ffn_ already holds silu(gate) * up (the
+// planes-SwiGLU launch's epilogue), only the quantisation is left.  The block-sum planes the batched ffn_down kernels take are written with the codes from
+// 3 tokens on - planes_any_T: also below that (the K-split branch has always written them with every batch it runs for).
+hipError_t Context::quantise_for_down(int il, int T, bool combined, bool planes_any_T) {
+    const int FF = model->hp.n_ff;
+    const bool k = !act_is_q80(model->layers[(size_t)il].down.type), pl = k && (planes_any_T || T >= 3);
+    int8_t *bh = pl ? mmq_bh_ : nullptr, *bl = pl ? mmq_bl_ : nullptr;
+    if (combined) HIP_TRY(launch_quantize(ffn_, FF, T, aq_ff_, k, !k, stream_, bh, bl));
+    else HIP_TRY(launch_swiglu_quant(ffn_, ffn_u_, FF, T, aq_ff_, k, !k, stream_, bh, bl));
+    prep_owner_ = nullptr;
+    if (pl) prep_written(aq_ff_, FF, T);
+    return hipSuccess;
+}
+
+// dense feed-forward, first half: ffn_ = silu(gate x') * (up x') with x' = RMSNorm(x).  quantised: aq_ff_ already holds it quantised for ffn_down
+hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, FF = hp.n_ff, T = st.T;
+    quantised = false;
+    const bool gq = type_is_quant(L.gate.type), uq = type_is_quant(L.up.type);
+    const bool fk = (gq && !act_is_q80(L.gate.type)) || (uq && !act_is_q80(L.up.type));
+    const bool f0 = act_is_q80(L.gate.type) || act_is_q80(L.up.type);
+    const bool fuse_ffn = gq && uq && L.gate.type == L.up.type && can_fuse(E, T);
+    Fuse fz;
+    if (fuse_ffn) {
+        fz.mode = 1; fz.x = x_; fz.w = (const float *)L.ffn_norm.data; fz.eps = hp.eps;
+    } else {
+        const bool pl = fk && T >= 3;
+        HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.ffn_norm.data, E, T, hp.eps, (!gq || !uq) ? xn_ : nullptr, &aq_e_, fk, f0, stream_,
+                                     pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
+        prep_owner_ = nullptr;
+        if (pl) prep_written(aq_e_, E, T);
+        prof_mark("norm_quant");
+    }
+    const bool down_q = type_is_quant(L.down.type) && (FF % 256) == 0;     // SwiGLU and the quantisation for ffn_down can share a pass
+    const bool ffn_mmq = (mmq_q80_applicable(L.gate.type, E, T) && mmq_q80_applicable(L.up.type, E, T)) ||
+                         (mmq_applicable(L.gate.type, E, T) && mmq_applicable(L.up.type, E, T)) ||
+                         (mmq_ksplit_applicable(L.gate.type, E, T) && mmq_ksplit_applicable(L.up.type, E, T)) ||
+                         (planes_small(L.gate, E, T) && planes_small(L.up, E, T)) || (q80_copy(L.gate, E, T) && q80_copy(L.up, E, T));
+    const bool ffn_ks = mmq_ksplit_preferred(L.gate.type, (int)L.gate.N, E, T, L.gate.planes != nullptr, true) &&
+                        mmq_ksplit_preferred(L.up.type, (int)L.up.N, E, T, L.up.planes != nullptr, true) && !fuse_ffn;
+    if (gq && uq && L.gate.type == L.up.type && !ffn_mmq) {
+        MMVQSeg segs[2] = {make_seg(L.gate, ffn_, FF, nullptr, nullptr), make_seg(L.up, ffn_u_, FF, nullptr, nullptr)};
+        HIP_TRY(mmvq_tokens(segs, 2, E, T, EPI_SWIGLU, aq_e_, stream_, fz));
+    } else if (L.gate.type == T_BF16 && L.up.type == T_BF16 && L.gate.N == L.up.N) {
+        // bf16 gate | up: one rounding of the rows; the weight stream computes both in one launch with SwiGLU in its epilogue, a prompt batch runs the
+        // two matrix-core products and the SwiGLU pass
+        const DevTensor *gu[2] = {&L.gate, &L.up};
+        float *go[2] = {ffn_, ffn_u_};
+        HIP_TRY(launch_f32_to_bf16(xn_, xb_, (size_t)T * E, stream_));
+        quantised = T > 1 && down_q && bf16_takes_mfma(gu, go, 2, E, T, 0, xb_);
+        HIP_TRY(linear_bf16(gu, go, nullptr, 2, E, T, 0, nullptr, quantised ? EPI_STORE : EPI_SWIGLU));
+        if (quantised) HIP_TRY(quantise_for_down(il, T, false, false));
+    } else if (ffn_ks) {                                   // batched decode step: gate and up in one launch
+        if (L.gate.type != T_Q6_K || L.up.type != T_Q6_K) HIP_TRY(ensure_prep(aq_e_, E, T));
+        MMQSeg sg[2] = {{L.gate.data, L.gate.row_bytes, (int)L.gate.N, L.gate.type, ffn_, FF, nullptr, 0},
+                        {L.up.data, L.up.row_bytes, (int)L.up.N, L.up.type, ffn_u_, FF, nullptr, 0}};
+        const bool pair = T <= 32 && L.gate.type == L.up.type && L.gate.N == L.up.N;     // SwiGLU in the epilogue
+        HIP_TRY(launch_mmq_ksplit_multi(sg, 2, E, T, aq_e_, mmq_bh_, mmq_bl_, pair, stream_));
+        quantised = !pair && down_q;
+        if (quantised) HIP_TRY(quantise_for_down(il, T, false, true));
+        else if (!pair) HIP_TRY(launch_swiglu(ffn_, ffn_u_, ffn_, (int64_t)T * FF, stream_));
+    } else if (T > 1 && !fuse_ffn && L.gate.planes && L.up.planes && L.gate.N == L.up.N && (mmq_applicable(L.gate.type, E, T) || planes_small(L.gate, E, T)) &&
+               mmq_planes_swiglu_ok(L.gate.type, L.up.type, (int)L.gate.N, E, T)) {
+        // prompt batch on the LDS kernel: gate and up in one launch, 64 rows of each per workgroup, SwiGLU in the epilogue (one
+        // f32 result of T x FF instead of two); the quantiser for the down projection then reads half as much
+        HIP_TRY(launch_mmq_planes_swiglu(L.gate.type, L.gate.planes, L.up.planes, (int)L.gate.N, E, T, aq_e_, ffn_, FF, stream_));
+        quantised = down_q;
+        if (quantised) HIP_TRY(quantise_for_down(il, T, true, false));
+    } else {
+        HIP_TRY(linear(L.gate, aq_e_, xn_, E, T, ffn_, FF, nullptr, EPI_STORE));
+        HIP_TRY(linear(L.up, aq_e_, xn_, E, T, ffn_u_, FF, nullptr, EPI_STORE));
+        // prompt batch: SwiGLU and the quantisation for the down projection in one pass (no f32 round trip of T x FF)
+        quantised = T > 1 && down_q;
+        if (quantised) HIP_TRY(quantise_for_down(il, T, false, false));
+        else HIP_TRY(launch_swiglu(ffn_, ffn_u_, ffn_, (int64_t)T * FF, stream_));
+    }
+    prof_mark("ffn_gate_up");
+    return hipSuccess;
+}
+
+// dense feed-forward, second half: ffn_down + residual into st.out.  n_matvec (optional): the mat-vec launches it took (2: the column halves)
+hipError_t Context::ffn_down(int il, const Step &st, bool quantised, int *n_matvec) {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, FF = hp.n_ff, T = st.T;
+    const int epi = st.resid ? EPI_ADD : EPI_STORE;
+    // quantise inside the down-projection's prologue (once per CU, overlapped with its first weight loads)
+    // (the widths listed are the ones the register-ring and weight-stream kernels take; the generic mat-vec's fused prologue would refuse others)
+    const bool fuse_down = st.fuse_down_env && T == 1 && type_is_quant(L.down.type) && (FF % 256) == 0 && mmvq_fast_kb_ok((FF + 2047) / 2048);
+    if (fuse_down && !st.tp && L.down_lo.valid() && L.down_hi.valid()) {
+        // the column halves of ffn_down, each quantising its half of the SwiGLU output in its prologue: x += W_lo a_lo; x += W_hi a_hi
+        const int Kh = (int)L.down_lo.K;
+        pending_fuse_.mode = 2; pending_fuse_.x = ffn_;
+        HIP_TRY(linear(L.down_lo, aq_ff_, ffn_, Kh, T, st.out, E, st.resid, epi));
+        pending_fuse_.mode = 2; pending_fuse_.x = ffn_ + Kh;
+        HIP_TRY(linear(L.down_hi, aq_ff_, ffn_ + Kh, Kh, T, st.out, E, st.out, EPI_ADD));
+        pending_fuse_ = Fuse();
+        if (n_matvec) *n_matvec = 2;
+        return hipSuccess;
+    }
+    if (n_matvec) *n_matvec = 1;
+    if (fuse_down) {
+        pending_fuse_.mode = 2; pending_fuse_.x = ffn_;
+    } else if (type_is_quant(L.down.type) && !quantised) {
+        HIP_TRY(launch_quantize(ffn_, FF, T, aq_ff_, !act_is_q80(L.down.type), act_is_q80(L.down.type), stream_));
+        prep_owner_ = nullptr;
+        prof_mark("quant");
+    }
+    HIP_TRY(linear(L.down, aq_ff_, ffn_, FF, T, st.out, E, st.resid, epi));
+    pending_fuse_ = Fuse();
+    return hipSuccess;
+}
+
+// single-token step of a mixture-of-experts layer: the token's selected experts share one launch per projection (the workgroups are divided among them;
+// each reads its own expert index on the device): gate | up with SwiGLU (a), then down with the Q8_K quantisation of its own expert's activation in the
+// prologue (d).  False where the layer has no such form.
+bool Context::moe_selected_desc(int il, MMVQArgs &a, MMVQArgs &d) const {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, FF = hp.n_ff, KU = hp.n_expert_used;
+    if (KU < 2 || KU > 8 || (int)cp.n_ubatch < KU || L.gate_exps.type != L.up_exps.type) return false;
+    // (RMSNorm + quantise again in the launch's prologue - the same arithmetic as the norm_quant launch that fed the router, so the same codes: the
+    // weight stream's gate | up form takes its activation that way, and with it the selected experts stream like the dense feed-forward does)
+    const bool prologue = can_fuse(E, 1) && !act_is_q80(L.gate_exps.type);
+    a = single_token_desc(2, E, EPI_SWIGLU, prologue ? 1 : 0, prologue ? x_ : nullptr, prologue ? (const float *)L.ffn_norm.data : nullptr, prologue ? hp.eps : 0.0f, aq_e_);
+    a.n_sel = KU; a.sel_out_stride = FF;
+    a.seg[0] = make_seg(L.gate_exps, ffn_, FF, nullptr, moe_ids_);
+    a.seg[1] = make_seg(L.up_exps, ffn_u_, FF, nullptr, moe_ids_);
+    d = single_token_desc(1, FF, EPI_STORE, 2, ffn_, nullptr, 0.0f, aq_ff_);
+    d.n_sel = KU; d.sel_nx_stride = FF; d.sel_out_stride = E;
+    d.seg[0] = make_seg(L.down_exps, moe_out_, E, nullptr, moe_ids_);
+    return mmvq_fast_applicable(a) && mmvq_fast_applicable(d);
+}
+
+// mixture-of-experts feed-forward, prompt batch on plane sets: every expert's batch in ONE launch per projection (the workgroups find their expert and
+// token tile from the counts on the device): no host synchronisation in the layer, and ~128-token batches that half-fill a launch each become one launch
+// that fills the chip
+hipError_t Context::moe_grouped_one_launch(int il, int T) {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, FF = hp.n_ff, KU = hp.n_expert_used, NE = hp.n_expert, GR = T * KU;
+    HIP_TRY(launch_moe_gather_act(aq_e_, moe_tok_, GR, E, aq_eg_, stream_));
+    prep_owner_ = nullptr;
+    const size_t ps_gu = L.gate_exps.planes_bytes / (size_t)L.gate_exps.n_expert, ps_d = L.down_exps.planes_bytes / (size_t)L.down_exps.n_expert;
+    HIP_TRY(launch_mmq_planes_swiglu_moe(L.gate_exps.type, L.gate_exps.planes, L.up_exps.planes, ps_gu, NE, moe_meta_, (int)L.gate_exps.N, E, GR, aq_eg_, ffn_g_, FF, stream_));
+    HIP_TRY(launch_quantize(ffn_g_, FF, GR, aq_ffg_, true, false, stream_));
+    HIP_TRY(launch_mmq_planes_moe(L.down_exps.type, L.down_exps.planes, ps_d, NE, moe_meta_, (int)L.down_exps.N, FF, GR, aq_ffg_, y_g_, E, stream_));
+    return launch_moe_scatter_combine(x_, y_g_, moe_w_, moe_slot_, T, E, KU, stream_);
+}
+
+// ... grouped, one batched contraction per expert and projection through linear(): the batch sizes come back to the host first (prompt batches only: never
+// inside a graph)
+hipError_t Context::moe_grouped_per_expert(int il, int T) {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, FF = hp.n_ff, KU = hp.n_expert_used, NE = hp.n_expert, GR = T * KU;
+    HIP_TRY(hipMemcpyAsync(h_moe_meta_, moe_meta_, (size_t)(2 * NE + 1) * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(launch_moe_gather_act(aq_e_, moe_tok_, GR, E, aq_eg_, stream_));
+    prep_owner_ = nullptr;                             // the grouped rows were just rewritten
+    HIP_TRY(hipStreamSynchronize(stream_));            // the batch sizes size the launches
+    auto view = [](const DevTensor &w, int e) {
+        DevTensor v = w;
+        v.data = w.data + (size_t)e * w.row_bytes * (size_t)w.N;
+        v.n_expert = 1;
+        v.planes = w.planes ? w.planes + (size_t)e * (w.planes_bytes / (size_t)w.n_expert) : nullptr;
+        return v;
+    };
+    auto rows = [](const ActQuant &q, int r0, int K) {
+        ActQuant v;
+        if (q.qs) { v.qs = q.qs + (size_t)r0 * K; v.d = q.d + (size_t)r0 * (K / 256); v.bsums = q.bsums + (size_t)r0 * (K / 16); }
+        if (q.qs0) { v.qs0 = q.qs0 + (size_t)r0 * K; v.d0 = q.d0 + (size_t)r0 * (K / 32); }
+        return v;
+    };
+    // the block-sum planes of ALL grouped rows in one launch (they were one launch per expert and projection: 16 a layer);
+    // an expert's batch takes its slice of them
+    const bool pl_gu = !act_is_q80(L.gate_exps.type) || !act_is_q80(L.up_exps.type), pl_d = !act_is_q80(L.down_exps.type);
+    if (pl_gu) HIP_TRY(launch_mmq_prep(aq_eg_, E, GR, mmq_bh_, mmq_bl_, stream_));
+    hipError_t e_exp = hipSuccess;
+    for (int e = 0; e < NE && e_exp == hipSuccess; e++) {
+        const int n_e = h_moe_meta_[e], r0 = h_moe_meta_[NE + e];
+        if (n_e <= 0) continue;
+        if (pl_gu) { bh_over_ = mmq_bh_ + (size_t)r0 * (E >> 4); bl_over_ = mmq_bl_ + (size_t)r0 * (E >> 4); }
+        e_exp = linear(view(L.gate_exps, e), rows(aq_eg_, r0, E), nullptr, E, n_e, ffn_g_ + (size_t)r0 * FF, FF, nullptr, EPI_STORE);
+        if (e_exp == hipSuccess) e_exp = linear(view(L.up_exps, e), rows(aq_eg_, r0, E), nullptr, E, n_e, ffn_ug_ + (size_t)r0 * FF, FF, nullptr, EPI_STORE);
+    }
+    bh_over_ = bl_over_ = nullptr;
+    HIP_TRY(e_exp);
+    HIP_TRY(launch_swiglu_quant(ffn_g_, ffn_ug_, FF, GR, aq_ffg_, !act_is_q80(L.down_exps.type), act_is_q80(L.down_exps.type), stream_,
+                                pl_d ? mmq_bh_ : nullptr, pl_d ? mmq_bl_ : nullptr));
+    prep_owner_ = nullptr;
+    for (int e = 0; e < NE && e_exp == hipSuccess; e++) {
+        const int n_e = h_moe_meta_[e], r0 = h_moe_meta_[NE + e];
+        if (n_e <= 0) continue;
+        if (pl_d) { bh_over_ = mmq_bh_ + (size_t)r0 * (FF >> 4); bl_over_ = mmq_bl_ + (size_t)r0 * (FF >> 4); }
+        e_exp = linear(view(L.down_exps, e), rows(aq_ffg_, r0, FF), nullptr, FF, n_e, y_g_ + (size_t)r0 * E, E, nullptr, EPI_STORE);
+    }
+    bh_over_ = bl_over_ = nullptr;
+    HIP_TRY(e_exp);
+    return launch_moe_scatter_combine(x_, y_g_, moe_w_, moe_slot_, T, E, KU, stream_);
+}
+
+// ... and a few tokens: the selected experts of a single token in one launch per projection (moe_selected_desc), else a mat-vec per (token, expert)
+hipError_t Context::moe_selected(int il, int T) {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, FF = hp.n_ff, KU = hp.n_expert_used;
+    MMVQArgs a{}, d{};
+    if (T == 1 && moe_selected_desc(il, a, d)) {
+        HIP_TRY(launch_mmvq(a, stream_));          // the weight stream where it has a form for the shape, else the register ring (bit-identical)
+        HIP_TRY(launch_mmvq(d, stream_));
+        return launch_moe_combine(x_, moe_out_, moe_w_, T, E, KU, (size_t)T * E, stream_);
+    }
+    // quantise inside the down projection's prologue where the persistent mat-vec takes this shape (as the dense feed-forward does), else as its own launch
+    const bool fuse_q = type_is_kq456(L.down_exps.type) && (FF % 256) == 0 && mmvq_fast_kb_ok((FF + 2047) / 2048);
+    for (int t = 0; t < T; t++) {
+        for (int j = 0; j < KU; j++) {
+            const int32_t *esel = moe_ids_ + (size_t)t * KU + j;
+            a = MMVQArgs{};
+            a.n_seg = 2; a.K = E; a.T = 1; a.epi = EPI_SWIGLU;
+            a.seg[0] = make_seg(L.gate_exps, ffn_ + (size_t)t * FF, FF, nullptr, esel);
+            a.seg[1] = make_seg(L.up_exps, ffn_u_ + (size_t)t * FF, FF, nullptr, esel);
+            chunk_act(a, aq_e_, E, t);
+            if (L.gate_exps.type == L.up_exps.type) {
+                HIP_TRY(launch_mmvq(a, stream_));
+            } else {
+                a.epi = EPI_STORE;
+                HIP_TRY(launch_mmvq(a, stream_));
+                HIP_TRY(launch_swiglu(ffn_ + (size_t)t * FF, ffn_u_ + (size_t)t * FF, ffn_ + (size_t)t * FF, FF, stream_));
+            }
+            if (!fuse_q) { HIP_TRY(launch_quantize(ffn_ + (size_t)t * FF, FF, 1, aq_ff_, !act_is_q80(L.down_exps.type), act_is_q80(L.down_exps.type), stream_)); prep_owner_ = nullptr; }
+            d = MMVQArgs{};
+            d.n_seg = 1; d.K = FF; d.T = 1; d.epi = EPI_STORE;
+            if (fuse_q) { d.fuse_mode = 2; d.nx = ffn_ + (size_t)t * FF; }
+            d.seg[0] = make_seg(L.down_exps, moe_out_ + ((size_t)j * T + t) * E, E, nullptr, esel);
+            chunk_act(d, aq_ff_, FF, 0);
+            HIP_TRY(launch_mmvq(d, stream_));
+        }
+    }
+    return launch_moe_combine(x_, moe_out_, moe_w_, T, E, KU, (size_t)T * E, stream_);
+}
+
+// mixture-of-experts feed-forward: RMSNorm, router, then the experts in the form the batch size picks (the result is added to x_ by the combine launch)
+hipError_t Context::ffn_moe(int il, const Step &st) {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, FF = hp.n_ff, T = st.T, KU = hp.n_expert_used;
+    HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.ffn_norm.data, E, T, hp.eps, xn_, &aq_e_,
+                                 !act_is_q80(L.gate_exps.type) || !act_is_q80(L.up_exps.type), act_is_q80(L.gate_exps.type) || act_is_q80(L.up_exps.type), stream_));
+    prep_owner_ = nullptr;
+    prof_mark("norm_quant");
+    const int32_t *forced = moe_forced_T_ == T ? d_moe_forced_ + (size_t)il * T * KU : nullptr;
+    // the fused router computes a token's logits in ONE workgroup: the fastest form at 8 experts (4.9 us against 7.0 for the two launches below,
+    // one token, K 2048), the slowest from 64 on (22 / 42 / 82 us at 64 / 128 / 256 experts against 9.4 / 9.5 / 13.2); the two give the same bits
+    if ((L.gate_inp.type == T_F32 || L.gate_inp.type == T_F16) && hp.n_expert <= 8) {
+        HIP_TRY(launch_moe_router(L.gate_inp.type, L.gate_inp.data, hp.n_expert, E, xn_, T, KU, router_, moe_ids_, moe_w_, stream_, forced));
+    } else {
+        HIP_TRY(launch_mmv_float(L.gate_inp.type, L.gate_inp.data, hp.n_expert, E, xn_, T, router_, hp.n_expert, nullptr, stream_));
+        HIP_TRY(launch_moe_route(router_, T, hp.n_expert, KU, moe_ids_, moe_w_, stream_, forced));
+    }
+    prof_mark("moe_route");
+    const bool exps_q = type_is_quant(L.gate_exps.type) && type_is_quant(L.up_exps.type) && type_is_quant(L.down_exps.type);
+    if (exps_q && T >= g_moe_group_min && aq_eg_.qs) {
+        // ggml_mul_mat_id on a batch: group the (token, rank) pairs by expert, one contiguous activation batch per
+        // expert (its weights are read once per batch, through the same batched kernels as the dense projections)
+        HIP_TRY(launch_moe_group(moe_ids_, T, KU, hp.n_expert, moe_meta_, moe_slot_, moe_tok_, stream_));
+        const bool one_launch = T >= 32 && L.gate_exps.planes && L.up_exps.planes && L.down_exps.planes && L.gate_exps.type == L.up_exps.type &&
+                                L.gate_exps.N == L.up_exps.N && mmq_planes_moe_ok(L.gate_exps.type, (int)L.gate_exps.N, E) &&
+                                mmq_planes_moe_ok(L.down_exps.type, (int)L.down_exps.N, FF) && (L.gate_exps.N % 64) == 0;
+        HIP_TRY(one_launch ? moe_grouped_one_launch(il, T) : moe_grouped_per_expert(il, T));
+    } else {
+        HIP_TRY(moe_selected(il, T));
+    }
+    prof_mark("moe_ffn");
+    return hipSuccess;
+}
+
+hipError_t Context::ffn_block(int il, const Step &st) {
+    if (model->hp.n_expert > 0) return ffn_moe(il, st);
+    bool quantised = false;
+    HIP_TRY(ffn_dense_gate_up(il, st, quantised));
+    HIP_TRY(ffn_down(il, st, quantised));
+    if (st.tp) HIP_TRY(tp_reduce_into_x(st.T));
+    prof_mark("ffn_down");
+    return hipSuccess;
+}
+
+// debug taps: the layer's output rows
+hipError_t Context::tap_layer(int il, int T) {
+    if (!debug_taps_ || !dbg_) return hipSuccess;
+    return hipMemcpyAsync(dbg_ + (size_t)il * cp.n_ubatch * model->hp.n_embd, x_, (size_t)T * model->hp.n_embd * 4, hipMemcpyDeviceToDevice, stream_);
+}
+
 hipError_t Context::run_layers(int T, int n_kv_cap) {
     if (model->hp.encoder) return run_layers_encoder(T, n_kv_cap);
     cur_T_ = T;
     const HParams &hp = model->hp;
-    const int E = hp.n_embd, FF = hp.n_ff, H = hp.n_head, G = hp.n_head_kv, D = hp.head_dim;
-    const RopeArgs ra_step = rope_args(*model, true);     // (each layer's: layer_rope)
-    const float kq_scale = 1.0f / sqrtf((float)D);
-    const int n_kv_max = std::max(n_kv_cap, 1);   // upper bound of occupied cells the kernels are sized for
-    att_splits_ = flash_attn_pick_splits(T, G, n_kv_max);
+    const int E = hp.n_embd, FF = hp.n_ff;
+    Step st = step_constants(T, n_kv_cap);
+    att_splits_ = flash_attn_pick_splits(T, hp.n_head_kv, st.n_kv_max);
 
     // single-token step on a dense K-quant model: all layers in one launch (decode_mega.hip)
     bool mega = T == 1 && !profile_ && !debug_taps_ && !ub_embd_ && mega_prepare();
     AttnArgs ma{};
     if (mega) {
-        ma.q = q_; ma.out = att_; ma.type_k = cp.type_k; ma.type_v = cp.type_v;
-        ma.T = 1; ma.H = H; ma.G = G; ma.D = D; ma.n_ctx = (int)cp.n_ctx;
-        ma.cell_pos = d_cell_pos_; ma.cell_seq = d_cell_seq_; ma.tok_pos = d_pos_; ma.tok_seq = d_seq_;
-        ma.n_kv_dev = d_nkv_; ma.n_kv_max = n_kv_max; ma.scale = kq_scale; ma.part = att_part_;
-        const DevTensor &wo0 = model->layers[0].wo;
-        ma.out_q = &aq_o_; ma.out_q8k = !act_is_q80(wo0.type); ma.out_q80 = false;
-        ma.splits = flash_attn_decode_splits(n_kv_max);
-        if (chunk_lmax_ > 0) {
-            ma.tok_chunks = d_chunks_; ma.tok_nchunks = d_chunks_ + (size_t)64 * chunk_stride_; ma.chunk_stride = chunk_stride_;
-            ma.splits = std::max(chunk_cap_, chunk_lmax_);
-        }
-        mega = flash_attn_decode_fused_applicable(ma, ra_step);      // (more than 64 chunks: the per-launch path merges them)
+        ma = attn_args(0, 1, st.n_kv_max, d_pos_);             // (the kernel takes each layer's cache from its own descriptor)
+        ma.out_q = &aq_o_; ma.out_q8k = !act_is_q80(model->layers[0].wo.type); ma.out_q80 = false;
+        ma.splits = flash_attn_decode_splits(st.n_kv_max);
+        if (st.chunk_lists) attn_chunk_lists(ma);
+        mega = flash_attn_decode_fused_applicable(ma, st.ra_step);      // (more than 64 chunks: the per-launch path merges them)
     }
     // ... or one persistent launch per layer for the mat-vecs between two attention calls (decode_engine.hip)
-    const bool engine = T == 1 && !mega && !profile_ && !debug_taps_ && !ub_embd_ && engine_prepare();
-    last_layers_engine_ = engine;
+    st.engine = T == 1 && !mega && !profile_ && !debug_taps_ && !ub_embd_ && engine_prepare();
+    last_layers_engine_ = st.engine;
     // cos / sin table, cell metadata and the tokens' embedding rows: one launch
-    HIP_TRY(launch_step_setup_embed(d_pos_, T, ra_step, rope_cs_, d_cell_pos_, d_cell_seq_, d_cell_, d_seqmask_, mega ? d_mega_sync_ : nullptr,
+    HIP_TRY(launch_step_setup_embed(d_pos_, T, st.ra_step, rope_cs_, d_cell_pos_, d_cell_seq_, d_cell_, d_seqmask_, mega ? d_mega_sync_ : nullptr,
                                     d_step_serial_, model->tok_embd.type, model->tok_embd.data, E, d_tok_, x_, stream_));
     // an embeddings batch: the caller's rows take the place of the looked-up ones (never inside a captured graph: decode_ubatch)
     if (ub_embd_) HIP_TRY(hipMemcpyAsync(x_, ub_embd_, (size_t)T * E * sizeof(float), hipMemcpyHostToDevice, stream_));
     prof_mark("embed");
     last_layers_mega_ = mega;
     if (mega)
-        return launch_decode_mega(d_mega_layers_, hp.n_layer, (E + 2047) >> 11, (FF + 2047) >> 11, ma, rope_cs_, ra_step.n_rot, k_, v_, d_cell_,
+        return launch_decode_mega(d_mega_layers_, hp.n_layer, (E + 2047) >> 11, (FF + 2047) >> 11, ma, rope_cs_, st.ra_step.n_rot, k_, v_, d_cell_,
                                   att_counters_, d_mega_sync_, h_mega_flag_, d_mega_probe_, mega_lds_, stream_);
 
-    const bool tp = hp.tp_exchange;
     for (int il = 0; il < hp.n_layer; il++) {
-        const LayerWeights &L = model->layers[(size_t)il];
-        const RopeArgs ra = layer_rope(ra_step, L, hp.eps);   // (qwen3: with the layer's q / k norm weights; every kernel below either applies them or refuses)
-        // --- attention block
-        const bool any_f = !is_quant(L.wq.type) || !is_quant(L.wk.type) || !is_quant(L.wv.type);
-        const bool need_k = is_quant(L.wq.type) && !act_is_q80(L.wq.type) || is_quant(L.wk.type) && !act_is_q80(L.wk.type) || is_quant(L.wv.type) && !act_is_q80(L.wv.type);
-        const bool need_0 = act_is_q80(L.wq.type) || act_is_q80(L.wk.type) || act_is_q80(L.wv.type);
-        const bool fuse_attn = !any_f && can_fuse(E, T);
-        // the attention launch's description first: where attn_out.hip takes Q | K | V as well (round 6), no projection launch is made at all
-        AttnArgs aa{};
-        aa.q = q_; aa.out = att_; aa.kv = kv_[(size_t)il]; aa.type_k = cp.type_k; aa.type_v = cp.type_v;
-        aa.T = T; aa.H = H; aa.G = G; aa.D = D; aa.n_ctx = (int)cp.n_ctx;
-        aa.cell_pos = d_cell_pos_; aa.cell_seq = d_cell_seq_; aa.tok_pos = d_pos_; aa.tok_seq = d_seq_;
-        aa.n_kv_dev = d_nkv_; aa.n_kv_max = n_kv_max; aa.scale = kq_scale; aa.part = att_part_;
-        const bool o_q = is_quant(L.wo.type);
-        aa.out_q = o_q ? &aq_o_ : nullptr; aa.out_q8k = !act_is_q80(L.wo.type); aa.out_q80 = act_is_q80(L.wo.type);   // merged + quantised in one pass
-        const bool o_pl = o_q && aa.out_q8k && T >= 3;         // the batched kernels will want the block-sum planes: the merge writes them too
-        if (o_pl) { aa.out_bh = mmq_bh_; aa.out_bl = mmq_bl_; }
-        // (the single-launch step and the store-fused batched step write the new K / V rows themselves; only the third branch needs the fast store kernel)
-        const bool fast_store = kv_store_fast_applicable(G, D, cp.type_k, cp.type_v, ra);
-        static const int attn_mode = getenv("MI355_ATTN_MODE") ? atoi(getenv("MI355_ATTN_MODE")) : 2;
-        bool fused_step = false, attn_out_done = false;
-        // (parity mode for an f16 cache: the generic launch below dispatches to the cell-by-cell kernel with fp16 V accumulation)
-        const bool v16 = fa_v_acc_f16_enabled() && cp.type_k == T_F16 && cp.type_v == T_F16;
-        const bool decode_attn = !v16 && flash_attn_decode_applicable(aa, ra);
-        if (decode_attn) {
-            aa.splits = flash_attn_decode_splits(n_kv_max);
-            if (chunk_lmax_ > 0) {                             // per-token chunk lists (decode_ubatch): batched steps, or regions in use
-                aa.tok_chunks = d_chunks_; aa.tok_nchunks = d_chunks_ + (size_t)64 * chunk_stride_; aa.chunk_stride = chunk_stride_;
-                aa.splits = std::max(chunk_cap_, chunk_lmax_);
-            }
-            fused_step = attn_mode > 0 && flash_attn_decode_fused_applicable(aa, ra);
-        }
-        // single-token step: attention + attn_output in one launch (attn_out.hip) where it has a form for the shape
-        // (not where the ranks of a row split exchange through the host callback - the transport of a rig whose ranks SHARE one device: this kernel's
-        // workgroups wait for each other (consumers for the item workgroups' flags), and two processes' copies placed on the same CUs at the same time can
-        // hold each other's item workgroups out - every wait then runs into its bound (round 6: 0x8 on three of eight ranks behind one MI355X at the first
-        // single-token step, profiles/r6_tp_shared_device_trace.txt).  A rank that owns its GPU has the chip to itself.)
-        const bool ao_add = !tp || hp.tp_rank == 0;
-        const MMVQSeg ao_seg = make_seg(L.wo, tp ? tp_part_ : x_, E, ao_add ? x_ : nullptr, nullptr);
-        AttnArgs af = aa;
-        bool ao_form = false;
-        if (decode_attn && fused_step && attn_mode == 2 && !engine && il < 255 && !attn_out_off_ && !attn_out_skip_step_ && !(tp && tp_uses_host())) {
-            af.splits = attn_out_fused_splits(af);
-            if (chunk_lmax_ > 0) af.splits = aa.splits;
-            ao_form = attn_out_fused_applicable(af, ra, ao_seg, (int)L.wo.K, ao_add ? EPI_ADD : EPI_STORE);
-        }
-        // ... and the layer's Q | K | V in front of it in that launch: the RMSNorm -> Q8_K prologue, the three mat-vecs, rope, KV store, attention, merge,
-        // Q8_K and attn_output + residual are ONE launch per layer (outputs bit-identical to the two launches)
-        bool qkv_in_attn = false;
-        if (ao_form && fuse_attn && !tp && d_qkv_gran_ && !(L.bq.valid() || L.bk.valid() || L.bv.valid())) {
-            QKVFuse qf{};
-            qf.seg[0] = make_seg(L.wq, q_, (int)L.wq.N, nullptr, nullptr);
-            qf.seg[1] = make_seg(L.wk, k_, (int)L.wk.N, nullptr, nullptr);
-            qf.seg[2] = make_seg(L.wv, v_, (int)L.wv.N, nullptr, nullptr);
-            qf.nx = x_; qf.nw = (const float *)L.attn_norm.data; qf.neps = hp.eps; qf.K = E; qf.gran = d_qkv_gran_;
-            if (qkv_attn_out_applicable(af, ra, ao_seg, (int)L.wo.K, EPI_ADD, qf)) {
-                HIP_TRY(launch_qkv_attn_out(af, rope_cs_, ra, d_cell_, att_counters_, d_ao_flags_ + (size_t)il * 64 * ATT_SYNC_STRIDE, d_ao_gran_, il, d_step_serial_, ao_seg,
-                                            (int)L.wo.K, EPI_ADD, qf, stream_));
-                qkv_in_attn = true; attn_out_done = true; qkv_attn_launches++;
-                prof_mark("qkv");
-            }
-        }
-        if (qkv_in_attn) {
-            // nothing to launch
-        } else if (engine && il > 0) {
-            // Q | K | V of this layer were computed at the end of the previous layer's engine launch
-        } else if (fuse_attn) {
-            pending_fuse_.mode = 1; pending_fuse_.x = x_; pending_fuse_.w = (const float *)L.attn_norm.data; pending_fuse_.eps = hp.eps;
-        } else {
-            const bool pl = need_k && T >= 3;                  // the batched kernels will want the block-sum planes
-            HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.attn_norm.data, E, T, hp.eps, any_f ? xn_ : nullptr, &aq_e_, need_k, need_0, stream_,
-                                         pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
-            prep_owner_ = nullptr;
-            if (pl) prep_written(aq_e_, E, T);
-            prof_mark("norm_quant");
-        }
-        const DevTensor *ws[3] = {&L.wq, &L.wk, &L.wv};
-        float *outs[3] = {q_, k_, v_};
-        const float *qkv_bias[3] = {L.bq.valid() ? (const float *)L.bq.data : nullptr, L.bk.valid() ? (const float *)L.bk.data : nullptr, L.bv.valid() ? (const float *)L.bv.data : nullptr};
-        bool bias_done = false;                                  // (a bf16 layer adds the biases in its launch's epilogue: the same f32 add)
-        if (!(engine && il > 0) && !qkv_in_attn) HIP_TRY(linear_multi(ws, outs, 3, aq_e_, xn_, T, qkv_bias, &bias_done));
-        pending_fuse_ = Fuse();
-        if (!qkv_in_attn && !bias_done && (L.bq.valid() || L.bk.valid() || L.bv.valid()))       // qwen2-style attention biases: all T rows of the three projections in one launch
-            HIP_TRY(launch_add_qkv_bias(q_, k_, v_, L.bq.valid() ? (const float *)L.bq.data : nullptr, L.bk.valid() ? (const float *)L.bk.data : nullptr,
-                                        L.bv.valid() ? (const float *)L.bv.data : nullptr, H * D, G * D, T, stream_));
-        if (!qkv_in_attn) prof_mark("qkv");
-        if (qkv_in_attn) {
-            // the whole block ran in the launch above
-        } else if (decode_attn && (fast_store || fused_step || (batch_distinct_ && store_fuse_enabled()))) {
-            if (fused_step) {
-                // single-token step: K rope + KV store + attention + split merge + quantise in ONE launch - and, where attn_out.hip has a form for the shape,
-                // the attn_output mat-vec with its residual add in that launch too
-                if (ao_form) {
-                    HIP_TRY(launch_attn_out_fused(af, rope_cs_, ra, k_, v_, d_cell_, att_counters_, d_ao_flags_ + (size_t)il * 64 * ATT_SYNC_STRIDE, d_ao_gran_, il, d_step_serial_, ao_seg,
-                                                  (int)L.wo.K, ao_add ? EPI_ADD : EPI_STORE, stream_));
-                    attn_out_done = true;
-                }
-                if (!attn_out_done)
-                    HIP_TRY(launch_flash_attn_decode_fused(aa, rope_cs_, ra, k_, v_, d_cell_, attn_mode == 2 ? att_counters_ : nullptr, stream_));
-            } else if (batch_distinct_ && store_fuse_enabled()) {
-                // batched step, every token of a different sequence: K rope + KV store inside the attention launch (no token reads another's new cell)
-                HIP_TRY(launch_flash_attn_decode(aa, rope_cs_, ra, stream_, k_, v_, d_cell_));
-            } else {
-                // small-batch step: K rope + KV store in one small kernel; q is rotated inside the attention kernel
-                HIP_TRY(launch_kv_store_fast(k_, v_, T, G, D, rope_cs_, ra, d_cell_, kv_[(size_t)il], cp.type_k, cp.type_v, (int)cp.n_ctx, stream_));
-                prof_mark("rope_kv");
-                HIP_TRY(launch_flash_attn_decode(aa, rope_cs_, ra, stream_));
-            }
-        } else {
-            static const bool rope_fast = !(getenv("MI355_ROPE_FAST") && getenv("MI355_ROPE_FAST")[0] == '0');
-            if (rope_fast && g_rope_fast && rope_cs_ && rope_q_kv_store_fast_applicable(H, G, D, cp.type_k, cp.type_v, ra))
-                HIP_TRY(launch_rope_q_kv_store_fast(q_, k_, v_, T, H, G, D, rope_cs_, ra, d_cell_, kv_[(size_t)il], cp.type_k, cp.type_v, (int)cp.n_ctx, stream_));
-            else
-                HIP_TRY(launch_rope_kv_store(q_, k_, v_, T, H, G, D, d_pos_, d_cell_, ra, kv_[(size_t)il], cp.type_k, cp.type_v, (int)cp.n_ctx, rope_cs_, stream_));
-            prof_mark("rope_kv");
-            aa.splits = att_splits_;
-            // (splits balance the causal tiles of ONE long sequence: sized by what a query of this batch can see - its position + 1 -
-            // not by the cache's high-water mark: 32 sequences of 50-token prompts in a 32000-cell cache need none, and every
-            // extra workgroup would scan the whole cell table)
-            aa.pf_splits = flash_attn_prefill_splits(T, H, G, D, std::min(n_kv_max, cur_max_pos_ + 1));
-            while (aa.pf_splits > 1 && flash_attn_workspace_floats(T, H, D, aa.pf_splits) > att_part_floats_) aa.pf_splits >>= 1;
-            HIP_TRY(launch_flash_attn(aa, stream_));
-        }
-        prof_mark("attn");
-        if (o_pl) prep_written(aq_o_, (int)L.wo.K, T);          // the attention just re-quantised its output, planes included
-        else if (prep_owner_ == aq_o_.qs) prep_owner_ = nullptr;
-        if (engine) {   // attn_output, gate | up, down and the next layer's Q | K | V in one launch
+        const AttnPlan ap = plan_attn(il, st);
+        HIP_TRY(attn_qkv(il, st, ap));
+        HIP_TRY(attn_core(il, st, ap));
+        if (st.engine) {   // attn_output, gate | up, down and the next layer's Q | K | V in one launch
             HIP_TRY(launch_decode_engine(d_engine_layers_ + il, E, FF, d_engine_gran_, d_engine_epoch_, il, il == engine_probe_layer_ ? d_engine_probe_ : nullptr, stream_));
-            continue;
-        }
-        if (attn_out_done) {   // the mat-vec ran inside the attention launch (attn_out.hip)
-            if (tp) HIP_TRY(tp_reduce_into_x(T));
-        } else if (tp) {   // this rank's partial sum (rank 0 carries the residual), then the exchange: x = sum over ranks
-            HIP_TRY(linear(L.wo, aq_o_, att_, (int)L.wo.K, T, tp_part_, E, hp.tp_rank == 0 ? x_ : nullptr, hp.tp_rank == 0 ? EPI_ADD : EPI_STORE));
-            HIP_TRY(tp_reduce_into_x(T));
         } else {
-            HIP_TRY(linear(L.wo, aq_o_, att_, (int)L.wo.K, T, x_, E, x_, EPI_ADD));
+            HIP_TRY(attn_output(il, st, ap));
+            if (st.tp) HIP_TRY(tp_reduce_into_x(T));
+            prof_mark("attn_out");
+            HIP_TRY(ffn_block(il, st));
         }
-        prof_mark("attn_out");
-
-        // --- feed-forward block
-        if (hp.n_expert > 0) {
-            HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.ffn_norm.data, E, T, hp.eps, xn_, &aq_e_,
-                                         !act_is_q80(L.gate_exps.type) || !act_is_q80(L.up_exps.type), act_is_q80(L.gate_exps.type) || act_is_q80(L.up_exps.type), stream_));
-            prep_owner_ = nullptr;
-            prof_mark("norm_quant");
-            // the fused router computes a token's logits in ONE workgroup: the fastest form at 8 experts (4.9 us against 7.0 for the two launches below,
-            // one token, K 2048), the slowest from 64 on (22 / 42 / 82 us at 64 / 128 / 256 experts against 9.4 / 9.5 / 13.2); the two give the same bits
-            if ((L.gate_inp.type == T_F32 || L.gate_inp.type == T_F16) && hp.n_expert <= 8) {
-                HIP_TRY(launch_moe_router(L.gate_inp.type, L.gate_inp.data, hp.n_expert, E, xn_, T, hp.n_expert_used, router_, moe_ids_, moe_w_, stream_,
-                                          moe_forced_T_ == T ? d_moe_forced_ + (size_t)il * T * hp.n_expert_used : nullptr));
-            } else {
-                HIP_TRY(launch_mmv_float(L.gate_inp.type, L.gate_inp.data, hp.n_expert, E, xn_, T, router_, hp.n_expert, nullptr, stream_));
-                HIP_TRY(launch_moe_route(router_, T, hp.n_expert, hp.n_expert_used, moe_ids_, moe_w_, stream_,
-                                         moe_forced_T_ == T ? d_moe_forced_ + (size_t)il * T * hp.n_expert_used : nullptr));
-            }
-            prof_mark("moe_route");
-            const int KU = hp.n_expert_used;
-            const bool exps_q = is_quant(L.gate_exps.type) && is_quant(L.up_exps.type) && is_quant(L.down_exps.type);
-            const int group_min = g_moe_group_min;
-            if (exps_q && T >= group_min && aq_eg_.qs) {
-                // ggml_mul_mat_id on a batch: group the (token, rank) pairs by expert, one contiguous activation batch per
-                // expert (its weights are read once per batch, through the same batched kernels as the dense projections)
-                const int NE = hp.n_expert, GR = T * KU;
-                HIP_TRY(launch_moe_group(moe_ids_, T, KU, NE, moe_meta_, moe_slot_, moe_tok_, stream_));
-                // round 5: every expert's batch in ONE launch per projection (the workgroups find their expert and token tile from the counts on the device):
-                // no host synchronisation in the layer, and ~128-token batches that half-fill a launch each become one launch that fills the chip
-                const bool grouped = T >= 32 && L.gate_exps.planes && L.up_exps.planes && L.down_exps.planes && L.gate_exps.type == L.up_exps.type &&
-                                     L.gate_exps.N == L.up_exps.N && mmq_planes_moe_ok(L.gate_exps.type, (int)L.gate_exps.N, E) &&
-                                     mmq_planes_moe_ok(L.down_exps.type, (int)L.down_exps.N, FF) && (L.gate_exps.N % 64) == 0;
-                if (grouped) {
-                    HIP_TRY(launch_moe_gather_act(aq_e_, moe_tok_, GR, E, aq_eg_, stream_));
-                    prep_owner_ = nullptr;
-                    const size_t ps_gu = L.gate_exps.planes_bytes / (size_t)L.gate_exps.n_expert, ps_d = L.down_exps.planes_bytes / (size_t)L.down_exps.n_expert;
-                    HIP_TRY(launch_mmq_planes_swiglu_moe(L.gate_exps.type, L.gate_exps.planes, L.up_exps.planes, ps_gu, NE, moe_meta_, (int)L.gate_exps.N, E, GR, aq_eg_,
-                                                         ffn_g_, FF, stream_));
-                    HIP_TRY(launch_quantize(ffn_g_, FF, GR, aq_ffg_, true, false, stream_));
-                    HIP_TRY(launch_mmq_planes_moe(L.down_exps.type, L.down_exps.planes, ps_d, NE, moe_meta_, (int)L.down_exps.N, FF, GR, aq_ffg_, y_g_, E, stream_));
-                    HIP_TRY(launch_moe_scatter_combine(x_, y_g_, moe_w_, moe_slot_, T, E, KU, stream_));
-                    prof_mark("moe_ffn");
-                    if (debug_taps_ && dbg_) HIP_TRY(hipMemcpyAsync(dbg_ + (size_t)il * cp.n_ubatch * E, x_, (size_t)T * E * 4, hipMemcpyDeviceToDevice, stream_));
-                    continue;
-                }
-                HIP_TRY(hipMemcpyAsync(h_moe_meta_, moe_meta_, (size_t)(2 * NE + 1) * 4, hipMemcpyDeviceToHost, stream_));
-                HIP_TRY(launch_moe_gather_act(aq_e_, moe_tok_, GR, E, aq_eg_, stream_));
-                prep_owner_ = nullptr;                             // the grouped rows were just rewritten
-                HIP_TRY(hipStreamSynchronize(stream_));            // the batch sizes size the launches (prompt batches only: never inside a graph)
-                auto view = [](const DevTensor &w, int e) {
-                    DevTensor v = w;
-                    v.data = w.data + (size_t)e * w.row_bytes * (size_t)w.N;
-                    v.n_expert = 1;
-                    v.planes = w.planes ? w.planes + (size_t)e * (w.planes_bytes / (size_t)w.n_expert) : nullptr;
-                    return v;
-                };
-                auto rows = [](const ActQuant &q, int r0, int K) {
-                    ActQuant v;
-                    if (q.qs) { v.qs = q.qs + (size_t)r0 * K; v.d = q.d + (size_t)r0 * (K / 256); v.bsums = q.bsums + (size_t)r0 * (K / 16); }
-                    if (q.qs0) { v.qs0 = q.qs0 + (size_t)r0 * K; v.d0 = q.d0 + (size_t)r0 * (K / 32); }
-                    return v;
-                };
-                // the block-sum planes of ALL grouped rows in one launch (they were one launch per expert and projection: 16 a layer);
-                // an expert's batch takes its slice of them
-                const bool pl_gu = !act_is_q80(L.gate_exps.type) || !act_is_q80(L.up_exps.type), pl_d = !act_is_q80(L.down_exps.type);
-                if (pl_gu) HIP_TRY(launch_mmq_prep(aq_eg_, E, GR, mmq_bh_, mmq_bl_, stream_));
-                hipError_t e_exp = hipSuccess;
-                for (int e = 0; e < NE && e_exp == hipSuccess; e++) {
-                    const int n_e = h_moe_meta_[e], r0 = h_moe_meta_[NE + e];
-                    if (n_e <= 0) continue;
-                    if (pl_gu) { bh_over_ = mmq_bh_ + (size_t)r0 * (E >> 4); bl_over_ = mmq_bl_ + (size_t)r0 * (E >> 4); }
-                    e_exp = linear(view(L.gate_exps, e), rows(aq_eg_, r0, E), nullptr, E, n_e, ffn_g_ + (size_t)r0 * FF, FF, nullptr, EPI_STORE);
-                    if (e_exp == hipSuccess) e_exp = linear(view(L.up_exps, e), rows(aq_eg_, r0, E), nullptr, E, n_e, ffn_ug_ + (size_t)r0 * FF, FF, nullptr, EPI_STORE);
-                }
-                bh_over_ = bl_over_ = nullptr;
-                HIP_TRY(e_exp);
-                HIP_TRY(launch_swiglu_quant(ffn_g_, ffn_ug_, FF, GR, aq_ffg_, !act_is_q80(L.down_exps.type), act_is_q80(L.down_exps.type), stream_,
-                                            pl_d ? mmq_bh_ : nullptr, pl_d ? mmq_bl_ : nullptr));
-                prep_owner_ = nullptr;
-                for (int e = 0; e < NE && e_exp == hipSuccess; e++) {
-                    const int n_e = h_moe_meta_[e], r0 = h_moe_meta_[NE + e];
-                    if (n_e <= 0) continue;
-                    if (pl_d) { bh_over_ = mmq_bh_ + (size_t)r0 * (FF >> 4); bl_over_ = mmq_bl_ + (size_t)r0 * (FF >> 4); }
-                    e_exp = linear(view(L.down_exps, e), rows(aq_ffg_, r0, FF), nullptr, FF, n_e, y_g_ + (size_t)r0 * E, E, nullptr, EPI_STORE);
-                }
-                bh_over_ = bl_over_ = nullptr;
-                HIP_TRY(e_exp);
-                HIP_TRY(launch_moe_scatter_combine(x_, y_g_, moe_w_, moe_slot_, T, E, KU, stream_));
-                prof_mark("moe_ffn");
-                if (debug_taps_ && dbg_) HIP_TRY(hipMemcpyAsync(dbg_ + (size_t)il * cp.n_ubatch * E, x_, (size_t)T * E * 4, hipMemcpyDeviceToDevice, stream_));
-                continue;
-            }
-            // single-token step: the token's selected experts share one launch per projection (the workgroups are divided
-            // among them; each reads its own expert index on the device): gate/up with SwiGLU, then down with the Q8_K
-            // quantisation of its own expert's activation in the prologue
-            bool experts_done = false;
-            if (T == 1 && KU >= 2 && KU <= 8 && (int)cp.n_ubatch >= KU && L.gate_exps.type == L.up_exps.type) {
-                MMVQArgs a{};
-                a.n_seg = 2; a.K = E; a.T = 1; a.epi = EPI_SWIGLU; a.n_sel = KU; a.sel_out_stride = FF;
-                a.seg[0] = make_seg(L.gate_exps, ffn_, FF, nullptr, moe_ids_);
-                a.seg[1] = make_seg(L.up_exps, ffn_u_, FF, nullptr, moe_ids_);
-                chunk_act(a, aq_e_, E, 0);
-                // (RMSNorm + quantise again in the launch's prologue - the same arithmetic as the norm_quant launch that fed the router, so the same codes: the
-                // weight stream's gate | up form takes its activation that way, and with it the selected experts stream like the dense feed-forward does)
-                if (can_fuse(E, 1) && !act_is_q80(L.gate_exps.type)) { a.fuse_mode = 1; a.nx = x_; a.nw = (const float *)L.ffn_norm.data; a.neps = hp.eps; }
-                MMVQArgs d{};
-                d.n_seg = 1; d.K = FF; d.T = 1; d.epi = EPI_STORE; d.fuse_mode = 2; d.nx = ffn_; d.n_sel = KU; d.sel_nx_stride = FF; d.sel_out_stride = E;
-                d.seg[0] = make_seg(L.down_exps, moe_out_, E, nullptr, moe_ids_);
-                chunk_act(d, aq_ff_, FF, 0);
-                if (mmvq_fast_applicable(a) && mmvq_fast_applicable(d)) {
-                    HIP_TRY(launch_mmvq(a, stream_));          // the weight stream where it has a form for the shape, else the register ring (bit-identical)
-                    HIP_TRY(launch_mmvq(d, stream_));
-                    experts_done = true;
-                }
-            }
-            for (int t = 0; t < T && !experts_done; t++) {
-                for (int j = 0; j < KU; j++) {
-                    const int32_t *esel = moe_ids_ + (size_t)t * KU + j;
-                    MMVQArgs a{};
-                    a.n_seg = 2; a.K = E; a.T = 1; a.epi = EPI_SWIGLU;
-                    a.seg[0] = make_seg(L.gate_exps, ffn_ + (size_t)t * FF, FF, nullptr, esel);
-                    a.seg[1] = make_seg(L.up_exps, ffn_u_ + (size_t)t * FF, FF, nullptr, esel);
-                    chunk_act(a, aq_e_, E, t);
-                    if (L.gate_exps.type == L.up_exps.type) {
-                        HIP_TRY(launch_mmvq(a, stream_));
-                    } else {
-                        a.n_seg = 2; a.epi = EPI_STORE;
-                        HIP_TRY(launch_mmvq(a, stream_));
-                        HIP_TRY(launch_swiglu(ffn_ + (size_t)t * FF, ffn_u_ + (size_t)t * FF, ffn_ + (size_t)t * FF, FF, stream_));
-                    }
-                    // quantise inside the down projection's prologue where the persistent mat-vec takes this shape (as the
-                    // dense feed-forward does), else as its own launch
-                    const int kbf = (FF + 2047) / 2048;
-                    const bool fuse_q = (L.down_exps.type == T_Q4_K || L.down_exps.type == T_Q5_K || L.down_exps.type == T_Q6_K) && (FF % 256) == 0 &&
-                                        mmvq_fast_kb_ok(kbf);
-                    if (!fuse_q) { HIP_TRY(launch_quantize(ffn_ + (size_t)t * FF, FF, 1, aq_ff_, !act_is_q80(L.down_exps.type), act_is_q80(L.down_exps.type), stream_)); prep_owner_ = nullptr; }
-                    MMVQArgs d{};
-                    d.n_seg = 1; d.K = FF; d.T = 1; d.epi = EPI_STORE;
-                    if (fuse_q) { d.fuse_mode = 2; d.nx = ffn_ + (size_t)t * FF; }
-                    d.seg[0] = make_seg(L.down_exps, moe_out_ + ((size_t)j * T + t) * E, E, nullptr, esel);
-                    chunk_act(d, aq_ff_, FF, 0);
-                    HIP_TRY(launch_mmvq(d, stream_));
-                }
-            }
-            HIP_TRY(launch_moe_combine(x_, moe_out_, moe_w_, T, E, KU, (size_t)T * E, stream_));
-            prof_mark("moe_ffn");
-        } else {
-            const bool gq = is_quant(L.gate.type), uq = is_quant(L.up.type);
-            const bool fk = (gq && !act_is_q80(L.gate.type)) || (uq && !act_is_q80(L.up.type));
-            const bool f0 = act_is_q80(L.gate.type) || act_is_q80(L.up.type);
-            const bool fuse_ffn = gq && uq && L.gate.type == L.up.type && can_fuse(E, T);
-            Fuse fz;
-            if (fuse_ffn) {
-                fz.mode = 1; fz.x = x_; fz.w = (const float *)L.ffn_norm.data; fz.eps = hp.eps;
-            } else {
-                const bool pl = fk && T >= 3;
-                HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.ffn_norm.data, E, T, hp.eps, (!gq || !uq) ? xn_ : nullptr, &aq_e_, fk, f0, stream_,
-                                             pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
-                prep_owner_ = nullptr;
-                if (pl) prep_written(aq_e_, E, T);
-                prof_mark("norm_quant");
-            }
-            bool swiglu_quantised = false;
-            const bool ffn_mmq = (mmq_q80_applicable(L.gate.type, E, T) && mmq_q80_applicable(L.up.type, E, T)) ||
-                                 (mmq_applicable(L.gate.type, E, T) && mmq_applicable(L.up.type, E, T)) ||
-                                 (mmq_ksplit_applicable(L.gate.type, E, T) && mmq_ksplit_applicable(L.up.type, E, T)) ||
-                                 (planes_small(L.gate, E, T) && planes_small(L.up, E, T)) || (q80_copy(L.gate, E, T) && q80_copy(L.up, E, T));
-            const bool ffn_ks = mmq_ksplit_preferred(L.gate.type, (int)L.gate.N, E, T, L.gate.planes != nullptr, true) &&
-                                mmq_ksplit_preferred(L.up.type, (int)L.up.N, E, T, L.up.planes != nullptr, true) && !fuse_ffn;
-            if (gq && uq && L.gate.type == L.up.type && !ffn_mmq) {
-                MMVQSeg segs[2] = {make_seg(L.gate, ffn_, FF, nullptr, nullptr), make_seg(L.up, ffn_u_, FF, nullptr, nullptr)};
-                HIP_TRY(mmvq_tokens(segs, 2, E, T, EPI_SWIGLU, aq_e_, stream_, fz));
-            } else if (L.gate.type == T_BF16 && L.up.type == T_BF16 && L.gate.N == L.up.N) {
-                // bf16 gate | up: one rounding of the rows; the weight stream computes both in one launch with SwiGLU in its epilogue, a prompt batch runs the
-                // two matrix-core products and the SwiGLU pass (quantising for a quantised ffn_down in that pass, as below)
-                const DevTensor *gu[2] = {&L.gate, &L.up};
-                float *go[2] = {ffn_, ffn_u_};
-                HIP_TRY(launch_f32_to_bf16(xn_, xb_, (size_t)T * E, stream_));
-                if (T > 1 && is_quant(L.down.type) && (FF % 256) == 0 && bf16_takes_mfma(gu, go, 2, E, T, 0, xb_)) {
-                    HIP_TRY(linear_bf16(gu, go, nullptr, 2, E, T, 0, nullptr, EPI_STORE));
-                    const bool pl = !act_is_q80(L.down.type) && T >= 3;
-                    HIP_TRY(launch_swiglu_quant(ffn_, ffn_u_, FF, T, aq_ff_, !act_is_q80(L.down.type), act_is_q80(L.down.type), stream_,
-                                                pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
-                    prep_owner_ = nullptr;
-                    if (pl) prep_written(aq_ff_, FF, T);
-                    swiglu_quantised = true;
-                } else {
-                    HIP_TRY(linear_bf16(gu, go, nullptr, 2, E, T, 0, nullptr, EPI_SWIGLU));
-                }
-            } else if (ffn_ks) {                               // batched decode step: gate and up in one launch
-                if (L.gate.type != T_Q6_K || L.up.type != T_Q6_K) HIP_TRY(ensure_prep(aq_e_, E, T));
-                MMQSeg sg[2] = {{L.gate.data, L.gate.row_bytes, (int)L.gate.N, L.gate.type, ffn_, FF, nullptr, 0},
-                                {L.up.data, L.up.row_bytes, (int)L.up.N, L.up.type, ffn_u_, FF, nullptr, 0}};
-                const bool pair = T <= 32 && L.gate.type == L.up.type && L.gate.N == L.up.N;     // SwiGLU in the epilogue
-                HIP_TRY(launch_mmq_ksplit_multi(sg, 2, E, T, aq_e_, mmq_bh_, mmq_bl_, pair, stream_));
-                if (!pair) {
-                    if (is_quant(L.down.type) && (FF % 256) == 0) {
-                        const bool pl = !act_is_q80(L.down.type);
-                        HIP_TRY(launch_swiglu_quant(ffn_, ffn_u_, FF, T, aq_ff_, !act_is_q80(L.down.type), act_is_q80(L.down.type), stream_,
-                                                    pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
-                        prep_owner_ = nullptr;
-                        if (pl) prep_written(aq_ff_, FF, T);
-                        swiglu_quantised = true;
-                    } else {
-                        HIP_TRY(launch_swiglu(ffn_, ffn_u_, ffn_, (int64_t)T * FF, stream_));
-                    }
-                }
-            } else if (T > 1 && !fuse_ffn && L.gate.planes && L.up.planes && L.gate.N == L.up.N && (mmq_applicable(L.gate.type, E, T) || planes_small(L.gate, E, T)) &&
-                       mmq_planes_swiglu_ok(L.gate.type, L.up.type, (int)L.gate.N, E, T)) {
-                // prompt batch on the LDS kernel: gate and up in one launch, 64 rows of each per workgroup, SwiGLU in the epilogue (one
-                // f32 result of T x FF instead of two); the quantiser for the down projection then reads half as much
-                HIP_TRY(launch_mmq_planes_swiglu(L.gate.type, L.gate.planes, L.up.planes, (int)L.gate.N, E, T, aq_e_, ffn_, FF, stream_));
-                if (is_quant(L.down.type) && (FF % 256) == 0) {
-                    const bool pl = !act_is_q80(L.down.type) && T >= 3;
-                    HIP_TRY(launch_quantize(ffn_, FF, T, aq_ff_, !act_is_q80(L.down.type), act_is_q80(L.down.type), stream_, pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
-                    prep_owner_ = nullptr;
-                    if (pl) prep_written(aq_ff_, FF, T);
-                    swiglu_quantised = true;
-                }
-            } else {
-                HIP_TRY(linear(L.gate, aq_e_, xn_, E, T, ffn_, FF, nullptr, EPI_STORE));
-                HIP_TRY(linear(L.up, aq_e_, xn_, E, T, ffn_u_, FF, nullptr, EPI_STORE));
-                // prompt batch: SwiGLU and the quantisation for the down projection in one pass (no f32 round trip of T x FF)
-                if (T > 1 && is_quant(L.down.type) && (FF % 256) == 0) {
-                    const bool pl = !act_is_q80(L.down.type) && T >= 3;
-                    HIP_TRY(launch_swiglu_quant(ffn_, ffn_u_, FF, T, aq_ff_, !act_is_q80(L.down.type), act_is_q80(L.down.type), stream_,
-                                                pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
-                    prep_owner_ = nullptr;
-                    if (pl) prep_written(aq_ff_, FF, T);
-                    swiglu_quantised = true;
-                } else {
-                    HIP_TRY(launch_swiglu(ffn_, ffn_u_, ffn_, (int64_t)T * FF, stream_));
-                }
-            }
-            prof_mark("ffn_gate_up");
-            static const bool fuse_down_env = !(getenv("MI355_FUSE_DOWN") && getenv("MI355_FUSE_DOWN")[0] == '0');
-            // quantise inside the down-projection's prologue (once per CU, overlapped with its first weight loads)
-            // (the widths listed are the ones the register-ring and weight-stream kernels take; the generic mat-vec's fused prologue would refuse others)
-            const bool fuse_down = fuse_down_env && T == 1 && (L.down.type == T_Q4_K || L.down.type == T_Q5_K || L.down.type == T_Q6_K || act_is_q80(L.down.type) ||
-                                                               L.down.type == T_Q2_K || L.down.type == T_Q3_K || L.down.type == T_IQ4_XS) &&
-                                   (FF % 256) == 0 && mmvq_fast_kb_ok((FF + 2047) / 2048);
-            if (fuse_down && !tp && L.down_lo.valid() && L.down_hi.valid()) {
-                // the column halves of ffn_down, each quantising its half of the SwiGLU output in its prologue: x += W_lo a_lo; x += W_hi a_hi
-                const int Kh = (int)L.down_lo.K;
-                pending_fuse_.mode = 2; pending_fuse_.x = ffn_;
-                HIP_TRY(linear(L.down_lo, aq_ff_, ffn_, Kh, T, x_, E, x_, EPI_ADD));
-                pending_fuse_.mode = 2; pending_fuse_.x = ffn_ + Kh;
-                HIP_TRY(linear(L.down_hi, aq_ff_, ffn_ + Kh, Kh, T, x_, E, x_, EPI_ADD));
-                pending_fuse_ = Fuse();
-                prof_mark("ffn_down");
-                if (debug_taps_ && dbg_) HIP_TRY(hipMemcpyAsync(dbg_ + (size_t)il * cp.n_ubatch * E, x_, (size_t)T * E * 4, hipMemcpyDeviceToDevice, stream_));
-                continue;
-            }
-            if (fuse_down) {
-                pending_fuse_.mode = 2; pending_fuse_.x = ffn_;       // quantise inside the mat-vec prologue
-            } else if (is_quant(L.down.type) && !swiglu_quantised) {
-                HIP_TRY(launch_quantize(ffn_, FF, T, aq_ff_, !act_is_q80(L.down.type), act_is_q80(L.down.type), stream_));
-                prep_owner_ = nullptr;
-                prof_mark("quant");
-            }
-            if (tp) {
-                HIP_TRY(linear(L.down, aq_ff_, ffn_, FF, T, tp_part_, E, hp.tp_rank == 0 ? x_ : nullptr, hp.tp_rank == 0 ? EPI_ADD : EPI_STORE));
-                pending_fuse_ = Fuse();
-                HIP_TRY(tp_reduce_into_x(T));
-            } else {
-                HIP_TRY(linear(L.down, aq_ff_, ffn_, FF, T, x_, E, x_, EPI_ADD));
-            }
-            pending_fuse_ = Fuse();
-            prof_mark("ffn_down");
-        }
-        if (debug_taps_ && dbg_) HIP_TRY(hipMemcpyAsync(dbg_ + (size_t)il * cp.n_ubatch * E, x_, (size_t)T * E * 4, hipMemcpyDeviceToDevice, stream_));
+        HIP_TRY(tap_layer(il, T));
     }
     return hipSuccess;
 }
@@ -1908,7 +1958,7 @@ hipError_t Context::run_output(int n_out, int out_base) {
         prof_mark("embd");
         return hipSuccess;
     }
-    const bool oq = is_quant(model->output.type);
+    const bool oq = type_is_quant(model->output.type);
     // a single-token step whose logits row is wanted on the host: the head's launch stores it into the pinned row itself (the row crosses PCIe under the
     // launch; a copy node behind it cost 9 - 12 us of every step, tools/host_gap.py)
     static const bool zc_env = !(getenv("MI355_LOGITS_ZERO_COPY") && getenv("MI355_LOGITS_ZERO_COPY")[0] == '0');
@@ -2357,110 +2407,57 @@ int Context::debug_layer_out(int il, float *dst, size_t cap) {
     return dbg_tokens_;
 }
 
-// every weight tensor once, as one decoded token reads them (no attention, no norms): the dominant kernel
-// launches_out: mat-vec launches per sweep.  Where the step runs attn_output inside its attention launch (attn_out.hip) the sweep holds no attn_output
-// launch either: it times the launches of the dominant kernel class as the step issues them, and counts their bytes only.
+// every weight tensor once, as one decoded token reads them (no attention): the dominant kernel class, issued by the functions run_layers issues it with
+// launches_out: mat-vec launches per sweep.  Where the step runs attn_output (and Q | K | V) inside its attention launch (attn_out.hip) the sweep holds no
+// such launch either: it times the launches of the dominant kernel class as the step issues them, and counts their bytes only.
 double Context::bench_weight_sweep(int iters, uint64_t *bytes_out, int *launches_out) {
     const HParams &hp = model->hp;
-    const int E = hp.n_embd, FF = hp.n_ff;
+    const int E = hp.n_embd;
+    if (hp.encoder) return -1.0;                               // (the encoder graph has no single-token step)
     (void)hipMemsetAsync(x_, 0, (size_t)E * 4, stream_);
-    uint64_t bytes = 0;
-    int launches = 0;
-    auto wo_in_attention = [&](const LayerWeights &L) {
-        AttnArgs af{};
-        af.type_k = cp.type_k; af.type_v = cp.type_v; af.T = 1; af.H = hp.n_head; af.G = hp.n_head_kv; af.D = hp.head_dim; af.n_ctx = (int)cp.n_ctx;
-        af.n_kv_max = 64; af.splits = 1; af.out_q = &aq_o_; af.out_q8k = !act_is_q80(L.wo.type); af.out_q80 = act_is_q80(L.wo.type);
-        const MMVQSeg so = make_seg(L.wo, x_, E, x_, nullptr);
-        return !hp.tp_exchange && is_quant(L.wo.type) && attn_out_fused_applicable(af, layer_rope(rope_args(*model, true), L, hp.eps), so, (int)L.wo.K, EPI_ADD);
-    };
-    // round 6: ... and Q | K | V too where attn_out.hip takes them (run_layers): the sweep then holds neither
-    auto qkv_in_attention = [&](const LayerWeights &L) {
-        if (!wo_in_attention(L) || !d_qkv_gran_ || L.bq.valid() || L.bk.valid() || L.bv.valid()) return false;
-        if (!is_quant(L.wq.type) || !is_quant(L.wk.type) || !is_quant(L.wv.type) || !can_fuse(E, 1)) return false;
-        AttnArgs af{};
-        af.type_k = cp.type_k; af.type_v = cp.type_v; af.T = 1; af.H = hp.n_head; af.G = hp.n_head_kv; af.D = hp.head_dim; af.n_ctx = (int)cp.n_ctx;
-        af.n_kv_max = 64; af.splits = 1; af.out_q = &aq_o_; af.out_q8k = !act_is_q80(L.wo.type); af.out_q80 = act_is_q80(L.wo.type);
-        const MMVQSeg so = make_seg(L.wo, x_, E, x_, nullptr);
-        QKVFuse qf{};
-        qf.seg[0] = make_seg(L.wq, q_, (int)L.wq.N, nullptr, nullptr); qf.seg[1] = make_seg(L.wk, k_, (int)L.wk.N, nullptr, nullptr); qf.seg[2] = make_seg(L.wv, v_, (int)L.wv.N, nullptr, nullptr);
-        qf.nx = x_; qf.nw = (const float *)L.attn_norm.data; qf.neps = hp.eps; qf.K = E; qf.gran = d_qkv_gran_;
-        return qkv_attn_out_applicable(af, layer_rope(rope_args(*model, true), L, hp.eps), so, (int)L.wo.K, EPI_ADD, qf);
-    };
+    uint64_t bytes = 0; int launches = 0;
+    // a single-token step over 64 cells of one sequence, outside the engine; the results go to xo_ so that the layer input stays as it is, and nothing is
+    // exchanged between the ranks of a row split
+    // (the residual choice stays the step's own: plan_attn is asked the step's question on every rank.  Of the prep state only prep_owner_ is dropped)
+    Step st = step_constants(1, 64);
+    st.chunk_lists = false;
+    st.out = xo_;
+    struct ProfileOff { bool &p; bool was; ~ProfileOff() { p = was; } } profile_off{profile_, profile_};   // the step's functions mark profile events:
+    profile_ = false;                                                                                      // none inside the sweep's capture
     auto sweep = [&](bool count) -> hipError_t {
         for (int il = 0; il < hp.n_layer; il++) {
             const LayerWeights &L = model->layers[(size_t)il];
+            const AttnPlan ap = plan_attn(il, st);
+            HIP_TRY(attn_qkv(il, st, ap));
+            HIP_TRY(attn_output(il, st, ap));
+            if (count) {
+                bytes += (ap.qkv_in_attn ? 0 : L.wq.ggml_bytes + L.wk.ggml_bytes + L.wv.ggml_bytes) + (ap.ao_form ? 0 : L.wo.ggml_bytes);
+                launches += (ap.qkv_in_attn ? 0 : 1) + (ap.ao_form ? 0 : 1);
+            }
             if (hp.n_expert > 0) {
-                // mixture of experts: the attention projections and the token's n_expert_used experts (indices 0..k-1 stand in
-                // for a selection; every expert has the same shape and bytes)
+                // mixture of experts: the token's n_expert_used experts (indices 0..k-1 stand in for a selection; every expert has the same shape and bytes)
                 const int KU = hp.n_expert_used;
-                if (!moe_ids_ || KU < 1 || KU > 8 || (int)cp.n_ubatch < KU || L.gate_exps.type != L.up_exps.type) continue;
+                MMVQArgs a{}, d{};
+                if (!moe_ids_ || !moe_selected_desc(il, a, d)) continue;
                 if (count) { std::vector<int32_t> ids((size_t)KU); for (int j = 0; j < KU; j++) ids[(size_t)j] = j; HIP_TRY(hipMemcpy(moe_ids_, ids.data(), ids.size() * 4, hipMemcpyHostToDevice)); }
-                const DevTensor *wsm[3] = {&L.wq, &L.wk, &L.wv};
-                float *outm[3] = {q_, k_, v_};
-                const bool qkv_fused = qkv_in_attention(L);
-                pending_fuse_.mode = 1; pending_fuse_.x = x_; pending_fuse_.w = (const float *)L.attn_norm.data; pending_fuse_.eps = hp.eps;
-                if (!qkv_fused) HIP_TRY(linear_multi(wsm, outm, 3, aq_e_, xn_, 1));
-                pending_fuse_ = Fuse();
-                const bool wo_fused = wo_in_attention(L);
-                if (!wo_fused) HIP_TRY(linear(L.wo, aq_o_, att_, (int)L.wo.K, 1, xo_, E, nullptr, EPI_STORE));
-                MMVQArgs a{};
-                a.n_seg = 2; a.K = E; a.T = 1; a.epi = EPI_SWIGLU; a.n_sel = KU; a.sel_out_stride = FF;
-                a.seg[0] = make_seg(L.gate_exps, ffn_, FF, nullptr, moe_ids_);
-                a.seg[1] = make_seg(L.up_exps, ffn_u_, FF, nullptr, moe_ids_);
-                chunk_act(a, aq_e_, E, 0);
-                MMVQArgs d{};
-                d.n_seg = 1; d.K = FF; d.T = 1; d.epi = EPI_STORE; d.fuse_mode = 2; d.nx = ffn_; d.n_sel = KU; d.sel_nx_stride = FF; d.sel_out_stride = E;
-                d.seg[0] = make_seg(L.down_exps, moe_out_, E, nullptr, moe_ids_);
-                chunk_act(d, aq_ff_, FF, 0);
-                if (!mmvq_fast_applicable(a) || !mmvq_fast_applicable(d)) continue;
-                HIP_TRY(launch_mmvq_fast(a, stream_));
-                HIP_TRY(launch_mmvq_fast(d, stream_));
+                HIP_TRY(launch_mmvq(a, stream_));
+                HIP_TRY(launch_mmvq(d, stream_));
                 if (count) {
-                    bytes += (qkv_fused ? 0 : L.wq.ggml_bytes + L.wk.ggml_bytes + L.wv.ggml_bytes) + (wo_fused ? 0 : L.wo.ggml_bytes) +
-                             (L.gate_exps.ggml_bytes + L.up_exps.ggml_bytes + L.down_exps.ggml_bytes) / (uint64_t)L.gate_exps.n_expert * (uint64_t)KU;
-                    launches += (wo_fused ? 3 : 4) - (qkv_fused ? 1 : 0);
+                    bytes += (L.gate_exps.ggml_bytes + L.up_exps.ggml_bytes + L.down_exps.ggml_bytes) / (uint64_t)L.gate_exps.n_expert * (uint64_t)KU;
+                    launches += 2;
                 }
                 continue;
             }
-            // the launches of a single-token step as run_layers issues them (same fused prologues, same epilogues)
-            const DevTensor *ws[3] = {&L.wq, &L.wk, &L.wv};
-            float *outs[3] = {q_, k_, v_};
-            const bool qkv_q = is_quant(L.wq.type) && is_quant(L.wk.type) && is_quant(L.wv.type);
-            const bool qkv_fused = qkv_in_attention(L);
-            if (qkv_q && can_fuse(E, 1)) { pending_fuse_.mode = 1; pending_fuse_.x = x_; pending_fuse_.w = (const float *)L.attn_norm.data; pending_fuse_.eps = hp.eps; }
-            if (!qkv_fused) HIP_TRY(linear_multi(ws, outs, 3, aq_e_, xn_, 1));
-            pending_fuse_ = Fuse();
-            const bool wo_fused = wo_in_attention(L);
-            if (!wo_fused) HIP_TRY(linear(L.wo, aq_o_, att_, (int)L.wo.K, 1, xo_, E, xo_, EPI_ADD));
-            if (is_quant(L.gate.type) && L.gate.type == L.up.type) {
-                MMVQSeg segs[2] = {make_seg(L.gate, ffn_, FF, nullptr, nullptr), make_seg(L.up, ffn_u_, FF, nullptr, nullptr)};
-                Fuse fz;
-                if (can_fuse(E, 1)) { fz.mode = 1; fz.x = x_; fz.w = (const float *)L.ffn_norm.data; fz.eps = hp.eps; }
-                HIP_TRY(mmvq_tokens(segs, 2, E, 1, EPI_SWIGLU, aq_e_, stream_, fz));
-            } else if (L.gate.type == T_BF16 && L.up.type == T_BF16 && L.gate.N == L.up.N) {
-                const DevTensor *gu[2] = {&L.gate, &L.up};
-                float *go[2] = {ffn_, ffn_u_};
-                HIP_TRY(launch_f32_to_bf16(xn_, xb_, (size_t)E, stream_));
-                HIP_TRY(linear_bf16(gu, go, nullptr, 2, E, 1, 0, nullptr, EPI_SWIGLU));
-            }
-            const bool halves = L.down_lo.valid() && L.down_hi.valid() && !hp.tp_exchange;      // (run_layers: the column halves, two launches)
-            if (halves) {
-                const int Kh = (int)L.down_lo.K;
-                pending_fuse_.mode = 2; pending_fuse_.x = ffn_;
-                HIP_TRY(linear(L.down_lo, aq_ff_, ffn_, Kh, 1, xo_, E, xo_, EPI_ADD));
-                pending_fuse_.mode = 2; pending_fuse_.x = ffn_ + Kh;
-                HIP_TRY(linear(L.down_hi, aq_ff_, ffn_ + Kh, Kh, 1, xo_, E, xo_, EPI_ADD));
-            } else {
-                if (is_quant(L.down.type) && (FF % 256) == 0) { pending_fuse_.mode = 2; pending_fuse_.x = ffn_; }
-                HIP_TRY(linear(L.down, aq_ff_, ffn_, FF, 1, xo_, E, xo_, EPI_ADD));
-            }
-            pending_fuse_ = Fuse();
+            bool quantised = false;
+            int n_down = 0;
+            HIP_TRY(ffn_dense_gate_up(il, st, quantised));
+            HIP_TRY(ffn_down(il, st, quantised, &n_down));
             if (count) {
-                bytes += (qkv_fused ? 0 : L.wq.ggml_bytes + L.wk.ggml_bytes + L.wv.ggml_bytes) + (wo_fused ? 0 : L.wo.ggml_bytes) + L.gate.ggml_bytes + L.up.ggml_bytes + L.down.ggml_bytes;
-                launches += (wo_fused ? 3 : 4) - (qkv_fused ? 1 : 0) + (halves ? 1 : 0);
+                bytes += L.gate.ggml_bytes + L.up.ggml_bytes + L.down.ggml_bytes;
+                launches += 1 + n_down;
             }
         }
-        if (is_quant(model->output.type) && can_fuse(E, 1)) { pending_fuse_.mode = 1; pending_fuse_.x = x_; pending_fuse_.w = (const float *)model->out_norm.data; pending_fuse_.eps = hp.eps; }
+        if (type_is_quant(model->output.type) && can_fuse(E, 1)) { pending_fuse_.mode = 1; pending_fuse_.x = x_; pending_fuse_.w = (const float *)model->out_norm.data; pending_fuse_.eps = hp.eps; }
         HIP_TRY(linear(model->output, aq_e_, xn_, E, 1, d_logits_, (int)model->output.N, nullptr, EPI_STORE));
         pending_fuse_ = Fuse();
         if (count) { bytes += model->output.ggml_bytes; launches += 1; }

@@ -169,6 +169,47 @@ class Context {
     bool alloc_cells(int n, const uint64_t *seqmask, std::vector<int> &out);
     std::vector<int> region_next_;     // per sequence: where its next cell is looked for first
     void apply_k_shift();
+    // ---- the layer forward pass: run_layers is the loop (set-up, the whole-step early return, then per layer attention block -> attn_output -> feed-forward
+    // block -> tap); each block states its choice of launch form once, and bench_weight_sweep issues a step's mat-vecs through the same functions
+    struct Step {                      // what one run_layers call fixes for all its layers (step_constants)
+        int T = 0, n_kv_max = 0;
+        RopeArgs ra_step{};            // the model's rope (a layer's own: layer_rope)
+        bool engine = false;           // the layer engine runs everything between two attention launches
+        bool tp = false;               // row split: partial sums are exchanged after attn_output and ffn_down
+        bool chunk_lists = false;      // the attention walks per-token chunk lists (decode_ubatch)
+        int attn_mode = 2;             // MI355_ATTN_MODE
+        bool rope_fast = true, fuse_down_env = true;   // MI355_ROPE_FAST (and set_rope_fast), MI355_FUSE_DOWN
+        float *out = nullptr;          // where attn_output and ffn_down leave their rows: x_ (in place), tp_part_ under a row split
+        const float *resid = nullptr;  // ... and the residual they add: x_, or none on the ranks after the first
+    };
+    struct AttnPlan {                  // the launches of one layer's attention block (plan_attn: launches nothing)
+        RopeArgs ra;                   // the layer's rope
+        AttnArgs aa, af;               // the attention launch; the attention + attn_output launch (its own split count)
+        MMVQSeg ao_seg;                // attn_output as a segment of that launch
+        int ao_epi;
+        QKVFuse qf;                    // Q | K | V inside it
+        bool qkv_float, qkv_prologue;  // a float projection (takes xn_); RMSNorm -> Q8_K in the Q | K | V launch's prologue
+        bool o_planes;                 // the attention writes the block-sum planes of its quantised output too
+        bool decode_attn, fused_step;  // the decode attention kernel; its one-launch single-token form
+        bool ao_form, qkv_in_attn;     // attn_output inside the attention launch; Q | K | V too
+    };
+    Step step_constants(int T, int n_kv_cap) const;
+    AttnArgs attn_args(int il, int T, int n_kv_max, const int32_t *tok_pos) const;
+    void attn_chunk_lists(AttnArgs &aa) const;
+    AttnPlan plan_attn(int il, const Step &st) const;
+    hipError_t attn_qkv(int il, const Step &st, const AttnPlan &p);
+    hipError_t attn_core(int il, const Step &st, const AttnPlan &p);
+    hipError_t attn_output(int il, const Step &st, const AttnPlan &p);
+    hipError_t ffn_block(int il, const Step &st);
+    hipError_t ffn_moe(int il, const Step &st);
+    bool moe_selected_desc(int il, MMVQArgs &a, MMVQArgs &d) const;
+    hipError_t moe_grouped_one_launch(int il, int T);
+    hipError_t moe_grouped_per_expert(int il, int T);
+    hipError_t moe_selected(int il, int T);
+    hipError_t ffn_dense_gate_up(int il, const Step &st, bool &quantised);
+    hipError_t quantise_for_down(int il, int T, bool combined, bool planes_any_T);
+    hipError_t ffn_down(int il, const Step &st, bool quantised, int *n_matvec = nullptr);
+    hipError_t tap_layer(int il, int T);
     hipError_t run_layers(int T, int n_kv_cap);
     hipError_t run_layers_encoder(int T, int n_kv_cap);
     hipError_t run_output(int n_out, int out_base);
