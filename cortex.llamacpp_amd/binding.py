@@ -10,6 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 2, 8, 12, 13, 14, 15
 Q2_K, Q3_K = 10, 11
 Q5_0, IQ4_NL = 6, 20
+Q4_1, Q5_1 = 3, 7
 IQ4_XS = 23
 BF16 = 30
 
@@ -98,6 +99,7 @@ SYMBOLS = {
     "mi355_debug_layer_out": (_i32, [_vp, _i32, _vp, _sz]),
     "mi355_op_quantize_act": (C.c_int, [_i32, _vp, _i64, _i64, _vp]),
     "mi355_op_mul_mat": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "mi355_op_mul_mat_add": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "mi355_op_f32_to_bf16": (C.c_int, [_vp, _i64, _vp]),
     "mi355_op_mul_mat_bf16": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mi355_op_ffn_gate_up": (C.c_int, [_i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
@@ -234,11 +236,20 @@ class Backend:
         y = np.zeros((T, N), np.float32)
         isum = msum = None
         if want_ints:
-            nblk = K // 32 if t in (Q8_0, Q4_0, Q5_0, IQ4_NL) else K // 256
+            nblk = K // 32 if t in (Q8_0, Q4_0, Q5_0, IQ4_NL, Q4_1, Q5_1) else K // 256
             isum = np.zeros((T, N, nblk), np.int32)
             msum = np.zeros((T, N, nblk), np.int32)
         self._chk(self.lib.mi355_op_mul_mat(t, _ptr(W), N, K, _ptr(x), T, _ptr(y), _ptr(isum), _ptr(msum)), "op_mul_mat")
         return (y, isum, msum) if want_ints else y
+
+    def mul_mat_add(self, t: int, W: np.ndarray, N: int, K: int, x: np.ndarray, resid: np.ndarray) -> np.ndarray:
+        """resid + W . x on the Q8_0 prompt kernel (see mi355_op_mul_mat_add)."""
+        W = np.ascontiguousarray(W.view(np.uint8).reshape(-1))
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+        resid = np.ascontiguousarray(resid, np.float32).reshape(x.shape[0], N)
+        y = np.zeros((x.shape[0], N), np.float32)
+        self._chk(self.lib.mi355_op_mul_mat_add(t, _ptr(W), N, K, _ptr(x), x.shape[0], _ptr(resid), _ptr(y)), "op_mul_mat_add")
+        return y
 
     def f32_to_bf16(self, x: np.ndarray) -> np.ndarray:
         """bf16 bits (uint16) of the f32 values, as the bf16 kernels round their activation rows; x.size % 8 == 0."""

@@ -47,6 +47,9 @@ EXTRA = {
     # (round 6: the fused Q | K | V + attention + attn_output kernel requests the layer input from its first five argument dwords,
     # csrc/attn_out.hip qkv_attn_out_kernel)
     "csrc/attn_out.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=5"],
+    # the generic mat-vec kernel holds every weight type's decoder and reads its argument struct in more places than the 300 up to which the compiler still
+    # reads a by-value struct in place: beyond them it copies the struct to scratch first (csrc/mmvq.hip mmvq_kernel)
+    "csrc/mmvq.hip": ["-mllvm", "-instcombine-max-copied-from-constant-users=2000"],
 }
 
 

@@ -470,6 +470,7 @@ bool cache_row_to_ggml(int type, DevBuf &codes, DevBuf &scales, int G, int D, in
     }
     return true;
 }
+int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y);
 }  // namespace
 
 extern "C" double hbm_read_probe(size_t bytes, int iters);
@@ -494,6 +495,7 @@ int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n, int64_t r
 
 int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (nib32_has_min(type)) return op_ffn_gate_up_nib32(type, Wg, Wu, N, K, x, T, y);
     const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
     const size_t pb = mmq_planes_bytes(type, N, (int)K);
     if (!grow || K % 256 || !pb || N % 32) { fail("bad type / K / N"); return MI355_ERR_ARG; }
@@ -515,29 +517,54 @@ int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N
     return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
 }
 
-int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, float *y, int32_t *isum, int32_t *msum) {
+}  // extern "C"
+
+namespace {
+// Q8_0 planes of T rows of K (K % 32 == 0) where K is no multiple of 256, the unit the quantiser works in: the rows are padded with zeros to whole
+// 256-blocks, quantised, and the planes of the first K / 32 blocks of each row compacted - a Q8_0 block depends on its own 32 values only
+hipError_t quantize_q80_padded(const float *dx, int K, int T, const ActQuant &q) {
+    const int Kp = (K + 255) & ~255;
+    DevBuf xp((size_t)Kp * T * 4);
+    ActBufs abp((size_t)Kp, (size_t)T);
+    if (!xp.p || !abp.ok()) return hipErrorOutOfMemory;
+    hipError_t e = hipMemset(xp.p, 0, (size_t)Kp * T * 4);
+    if (e == hipSuccess) e = hipMemcpy2D(xp.p, (size_t)Kp * 4, dx, (size_t)K * 4, (size_t)K * 4, (size_t)T, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = launch_quantize(xp.as<float>(), Kp, T, abp.q, false, true, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy2D(q.qs0, (size_t)K, abp.q.qs0, (size_t)Kp, (size_t)K, (size_t)T, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy2D(q.d0, (size_t)(K / 32) * 2, abp.q.d0, (size_t)(Kp / 32) * 2, (size_t)(K / 32) * 2, (size_t)T, hipMemcpyDeviceToDevice);
+    return e;
+}
+
+int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y, int32_t *isum, int32_t *msum) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    if (!grow || K % 256) { fail("bad type / K"); return MI355_ERR_ARG; }
-    DevBuf wsrc(grow * N), wdev(drow * N), dx((size_t)K * T * 4), dy((size_t)N * T * 4);
+    // whole 256-blocks, as the models' hidden sizes are; Q4_1 / Q5_1 (32-element blocks) take any whole number of blocks
+    if (!grow || K <= 0 || (nib32_has_min(type) ? K % 32 : K % 256)) { fail("bad type / K"); return MI355_ERR_ARG; }
+    DevBuf wsrc(grow * N), wdev(drow * N), dx((size_t)K * T * 4), dy((size_t)N * T * 4), dres(resid ? (size_t)N * T * 4 : 16);
     ActBufs ab((size_t)K, (size_t)T);
-    if (!wsrc.up(W, grow * N) || !wdev.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    if (!wsrc.up(W, grow * N) || !wdev.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !ab.ok() || !dres.p || (resid && !dres.up(resid, (size_t)N * T * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    const float *rs = resid ? dres.as<float>() : nullptr;
     hipError_t e = launch_repack_rows(type, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, N, nullptr);
     if (e != hipSuccess) return hip_fail(e, "repack");
     const bool quant = type_is_quant(type);
+    if (resid && !(quant && ((mmq_q80_applicable(type, (int)K, (int)T)) || (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes)))) {
+        fail("resid: only the Q8_0 prompt kernel's launches take one here"); return MI355_ERR_ARG;
+    }
     if (quant) {
-        e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, !act_is_q80(type), act_is_q80(type), nullptr);
+        if (K % 256) e = quantize_q80_padded(dx.as<float>(), (int)K, (int)T, ab.q);
+        else e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, !act_is_q80(type), act_is_q80(type), nullptr);
         if (e != hipSuccess) return hip_fail(e, "quantize");
         if (mmq_q80_applicable(type, (int)K, (int)T)) {
-            e = launch_mmq_q80(wdev.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, nullptr, nullptr);
+            e = launch_mmq_q80(wdev.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, rs, nullptr);
             if (e == hipSuccess) e = hipDeviceSynchronize();
             if (e != hipSuccess) return hip_fail(e, "mmq_q80");
         } else
-        if (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes) {   // Q4_0 / Q5_0 / IQ4_NL prompt batches: exact Q8_0-layout copy
+        if (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes) {   // Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 prompt batches: exact Q8_0-layout copy
             DevBuf cp(mmq_q80_copy_bytes(type, N, (int)K));
             if (!cp.p) return MI355_ERR_OOM;
             e = launch_expand_q80_copy(type, wdev.as<uint8_t>(), drow, (int)N, (int)K, cp.as<uint8_t>(), nullptr);
-            if (e == hipSuccess) e = launch_mmq_q80(cp.as<uint8_t>(), dev_row_bytes(T_Q8_0, K), (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, nullptr, nullptr);
+            if (e == hipSuccess) e = launch_mmq_q80(cp.as<uint8_t>(), mmq_q80_copy_row_bytes(type, (int)K), (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, rs, nullptr, nib32_has_min(type));
             if (e == hipSuccess) e = hipDeviceSynchronize();
             if (e != hipSuccess) return hip_fail(e, "mmq_q80 (copy)");
         } else
@@ -579,6 +606,9 @@ int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const fl
             a.seg[0].ld_out = (int)N; a.seg[0].row_bytes = drow;
             a.aq = ab.q.qs + t0 * K; a.ad = ab.q.d + t0 * (K / 256); a.abs = ab.q.bsums + t0 * (K / 16);
             a.aq0 = ab.q.qs0 + t0 * K; a.ad0 = ab.q.d0 + t0 * (K / 32);
+            // Q4_1 / Q5_1, one token: quantised in the mat-vec's prologue, as a decode step's ffn_down and head are - the weight stream takes Q8_0-activation
+            // types only in that form (row pairs, single rows), the register ring with "mmvq_stream" 0; the same blocks, so the same result
+            if (nt == 1 && nib32_has_min(type) && (K % 256) == 0) { a.fuse_mode = 2; a.nx = dx.as<float>() + t0 * K; }
             e = launch_mmvq(a, nullptr);
             if (e != hipSuccess) return hip_fail(e, "mmvq");
             t0 += nt;
@@ -628,6 +658,63 @@ int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const fl
     e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "mul_mat");
     return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+// ffn_gate | ffn_up of a Q4_1 / Q5_1 layer with SwiGLU, as Context::ffn_gate_up runs them: prompt batches through the two tensors' Q8_0-layout copies
+// and the SwiGLU pass ("mmq_planes" 1, T >= 32), else the mat-vec with SwiGLU in its epilogue in chunks of 16, 8, 4, 2, 1 tokens
+int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) {
+    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
+    if (!grow || K % 256) { fail("bad type / K"); return MI355_ERR_ARG; }
+    DevBuf wsrc(grow * N), wg(drow * N), wu(drow * N), dx((size_t)K * T * 4), dy((size_t)N * T * 4), du((size_t)N * T * 4);
+    ActBufs ab((size_t)K, (size_t)T);
+    if (!wsrc.p || !wg.p || !wu.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !du.p || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; i++) {
+        if (!wsrc.up(i ? Wu : Wg, grow * N)) { fail("device copy failed"); return MI355_ERR_OOM; }
+        e = launch_repack_rows(type, wsrc.as<uint8_t>(), (i ? wu : wg).as<uint8_t>(), K, N, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e == hipSuccess) e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, false, true, nullptr);
+    if (e != hipSuccess) return hip_fail(e, "ffn_gate_up (set-up)");
+    if (g_op_mmq_planes && mmq_q80_applicable(T_Q8_0, (int)K, (int)T)) {
+        const size_t cb = mmq_q80_copy_bytes(type, N, (int)K), crow = mmq_q80_copy_row_bytes(type, (int)K);
+        DevBuf cg(cb), cu(cb);
+        if (!cg.p || !cu.p) return MI355_ERR_OOM;
+        e = launch_expand_q80_copy(type, wg.as<uint8_t>(), drow, (int)N, (int)K, cg.as<uint8_t>(), nullptr);
+        if (e == hipSuccess) e = launch_expand_q80_copy(type, wu.as<uint8_t>(), drow, (int)N, (int)K, cu.as<uint8_t>(), nullptr);
+        if (e == hipSuccess) e = launch_mmq_q80(cg.as<uint8_t>(), crow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, nullptr, nullptr, true);
+        if (e == hipSuccess) e = launch_mmq_q80(cu.as<uint8_t>(), crow, (int)N, (int)K, (int)T, ab.q, du.as<float>(), (int)N, nullptr, nullptr, true);
+        if (e == hipSuccess) e = launch_swiglu(dy.as<float>(), du.as<float>(), dy.as<float>(), N * T, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    } else {
+        for (int64_t t0 = 0; t0 < T && e == hipSuccess;) {
+            const int64_t rem = T - t0;
+            const int nt = rem >= 16 ? 16 : rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1;
+            MMVQArgs a{};
+            a.n_seg = 2; a.K = (int)K; a.T = nt; a.epi = EPI_SWIGLU;
+            for (int i = 0; i < 2; i++) {
+                a.seg[i].W = (i ? wu : wg).as<uint8_t>(); a.seg[i].out = (i ? du : dy).as<float>() + t0 * N; a.seg[i].type = type; a.seg[i].n_rows = (int)N;
+                a.seg[i].ld_out = (int)N; a.seg[i].row_bytes = drow;
+            }
+            a.aq0 = ab.q.qs0 + t0 * K; a.ad0 = ab.q.d0 + t0 * (K / 32);
+            e = launch_mmvq(a, nullptr);
+            t0 += nt;
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess) return hip_fail(e, "ffn_gate_up");
+    return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+}  // namespace
+
+extern "C" {
+
+int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, float *y, int32_t *isum, int32_t *msum) {
+    return op_mul_mat(type, W, N, K, x, T, nullptr, y, isum, msum);
+}
+int mi355_op_mul_mat_add(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y) {
+    if (!resid) { fail("mul_mat_add: resid is null"); return MI355_ERR_ARG; }
+    return op_mul_mat(type, W, N, K, x, T, resid, y, nullptr, nullptr);
 }
 
 int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out) {
@@ -1041,6 +1128,7 @@ int mi355_debug_set_option(const char *name, int32_t value) {
     if (!name) return MI355_ERR_ARG;
     if (!strcmp(name, "mmq_planes")) { g_op_mmq_planes = value != 0; return MI355_OK; }
     if (!strcmp(name, "mmq_tiles")) { mmq_set_tiles(value); return MI355_OK; }
+    if (!strcmp(name, "mmq_q80_tiles")) { mmq_q80_set_tiles(value); return MI355_OK; }
     if (!strcmp(name, "mmq_split")) { mmq_set_split(value); return MI355_OK; }
     if (!strcmp(name, "mmq_lds_form")) { mmq_set_lds_form(value); return MI355_OK; }
     if (!strcmp(name, "mmq_ksplit")) { g_op_mmq_ksplit = value != 0; return MI355_OK; }

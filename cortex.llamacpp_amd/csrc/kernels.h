@@ -114,8 +114,10 @@ bool mmq_applicable(int type, int K, int T);
 void mmq_set_tiles(int mt);                                // tools: force 1 / 2 / 4 token tiles per wave (0 = by T)
 // pre-expanded MFMA operand planes of a weight tensor (2 B / weight, built once at load; mmq.hip)
 size_t mmq_planes_bytes(int type, int64_t n_rows, int K);   // 0 if the type has no planes form
-// Q4_0 / Q5_0 / IQ4_NL: an exact Q8_0-layout copy of the tensor for prompt batches (mmq_q80.hip); 0 for other types
+// Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1: an exact Q8_0-layout copy of the tensor for prompt batches (mmq_q80.hip); 0 for other types.
+// A row of the copy is [codes K][scales K/32 f16], for Q4_1 / Q5_1 followed by [mins K/32 f16]; padded to 16 bytes.
 size_t mmq_q80_copy_bytes(int type, int64_t n_rows, int K);
+size_t mmq_q80_copy_row_bytes(int type, int K);
 hipError_t launch_expand_q80_copy(int type, const uint8_t *W, size_t row_bytes, int n_rows, int K, uint8_t *dst, hipStream_t st);
 hipError_t launch_mmq_expand(int type, const uint8_t *W, size_t row_bytes, int n_rows, int K, uint8_t *planes, hipStream_t st);
 // workspace for the K-split form of the planes kernel (tensors with few rows): n_split * T * n_rows floats; none = no split
@@ -140,8 +142,10 @@ struct MMQSeg {
 };
 // prompt batches against Q8_0 weights (mmq_q80.hip): int8 MFMA per 32-block, f32 fold in block order (bit-exact with the CPU)
 bool mmq_q80_applicable(int type, int K, int T);
+// mins: W is the copy of a Q4_1 / Q5_1 tensor (a min plane behind the scales): each block adds m_w * (d_a * sum of the block's activation codes) as well
 hipError_t launch_mmq_q80(const uint8_t *W, size_t row_bytes, int n_rows, int K, int T, const ActQuant &q, float *out, int ld_out,
-                          const float *resid, hipStream_t st);
+                          const float *resid, hipStream_t st, bool mins = false);
+void mmq_q80_set_tiles(int mt);      // tests: 1 / 2 / 4 token tiles per wave whatever the shape; 0: the launcher's choice
 // up to three tensors of one plane format (Q4_K / Q5_K together, or Q6_K) whose plane sets are contiguous in memory, as one
 // launch over the concatenated rows; seg_rows[i] rows go to outs[i] (leading dimension lds_out[i])
 hipError_t launch_mmq_planes_multi(int type, const uint8_t *planes, const int *seg_rows, float *const *outs, const int *lds_out, int n_seg, int K, int T,

@@ -13,6 +13,15 @@
 // 16 x (convert, scale product, multiply-add): the fold is the bound (VALU), ~1/8 of the int8 matrix peak — against one
 // pass over the weights per 16 tokens with the tiled mat-vec this replaces for T >= 32.
 // Workgroup = 4 waves = 128 weight rows x 32 tokens; the four waves share the token tile (L1 hits on the activations).
+//
+// MINS (the copies of Q4_1 / Q5_1 tensors, device rows [codes K][scales K/32][mins K/32]; codes 0..15 / 0..31): a block adds
+//
+//   t = (float)isum_b * (d_w * d_a) + m_w[r][b] * s_a[t][b],   s_a = d_a * (float)sum_{k in b} a[t][k],   out += t
+//
+// every product and sum rounded on its own, each output's chain in block order.  s_a does not depend on the weight row: it is staged in LDS
+// beside d_a, once per workgroup and chunk (the staging thread of a (block, token) sums the block's 32 activation codes - exact - and
+// multiplies once).  The fold then costs 16 x (one more multiply, one more add) per block: five packed-pair instructions per output pair
+// instead of three, so the bound estimate above becomes ~1/13 of the int8 matrix peak for these two types.
 #include "kernels.h"
 #include "quant_dev.h"
 
@@ -31,11 +40,12 @@ constexpr int Q80_UNROLL = 4;
 // (with MT = 1 an 8B-shaped prompt is bound by those re-reads out of L2: 8.5k tok/s).  The activation scales are staged per chunk of Q80_KC blocks.
 constexpr int Q80_KC = 64;
 
-template <int MT>
+template <int MT, bool MINS>
 __global__ __launch_bounds__(256) void mmq_q80_kernel(const uint8_t *__restrict__ W, size_t row_bytes, int n_rows, int K, int T,
                                                       const int8_t *__restrict__ aq, const uint16_t *__restrict__ ad, float *__restrict__ out,
                                                       int ld_out, const float *__restrict__ resid) {
-    __shared__ __attribute__((aligned(16))) float s_da[Q80_KC * 32 * MT];      // [block of the chunk][token of the workgroup's tile]
+    __shared__ __attribute__((aligned(16))) float s_da[(MINS ? 2 : 1) * Q80_KC * 32 * MT];      // [block of the chunk][token of the workgroup's tile]; MINS: s_a behind it
+    const float *s_sa = s_da + Q80_KC * 32 * MT;
     constexpr int TT = 32 * MT;
     const int nb = K >> 5;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -45,6 +55,7 @@ __global__ __launch_bounds__(256) void mmq_q80_kernel(const uint8_t *__restrict_
     const int row = r0 + n < n_rows ? r0 + n : n_rows - 1;
     const uint8_t *wrow = W + (size_t)row * row_bytes + 16 * kg;
     const uint16_t *wd = reinterpret_cast<const uint16_t *>(W + (size_t)row * row_bytes + K);
+    const uint16_t *wm = wd + nb;                                      // (MINS) the row's min plane
     const int8_t *arow[MT];
 #pragma unroll
     for (int m = 0; m < MT; m++) {
@@ -62,17 +73,26 @@ __global__ __launch_bounds__(256) void mmq_q80_kernel(const uint8_t *__restrict_
 
     // per output and block: scale = d_w * d_a (exact: two f16 values), product = (float)isum * scale, sum += product - the CPU's three roundings in the CPU's
     // order; written on pairs so that the multiplies and the add become v_pk_mul_f32 / v_pk_add_f32 (two outputs per instruction, same IEEE results)
-    auto fold = [&](const i32x16 &c, float dw, int bl, int m) {        // bl: block within the chunk
+    // MINS: term = product + m_w * s_a (one more multiply, one more add, each rounded: the build has contraction off), sum += term
+    auto fold = [&](const i32x16 &c, float dw, float mw, int bl, int m) {        // bl: block within the chunk
         const f32x2 dw2 = {dw, dw};
+        const f32x2 mw2 = {mw, mw};
 #pragma unroll
         for (int rq = 0; rq < 4; rq++) {
             const f32x4 da4 = *reinterpret_cast<const f32x4 *>(s_da + bl * TT + 32 * m + 8 * rq + 4 * kg);    // tokens 8 rq + 4 kg + (0..3) of tile m
+            f32x4 sa4;
+            if constexpr (MINS) sa4 = *reinterpret_cast<const f32x4 *>(s_sa + bl * TT + 32 * m + 8 * rq + 4 * kg);
 #pragma unroll
             for (int rp = 0; rp < 2; rp++) {
                 const f32x2 da2 = {da4[2 * rp], da4[2 * rp + 1]};
                 const f32x2 cf = {(float)c[rq * 4 + 2 * rp], (float)c[rq * 4 + 2 * rp + 1]};
                 const f32x2 sc = dw2 * da2;
-                const f32x2 pr = cf * sc;
+                f32x2 pr = cf * sc;
+                if constexpr (MINS) {
+                    const f32x2 sa2 = {sa4[2 * rp], sa4[2 * rp + 1]};
+                    const f32x2 ms = mw2 * sa2;
+                    pr = pr + ms;
+                }
                 f32x2 acc = {facc[m][rq * 4 + 2 * rp], facc[m][rq * 4 + 2 * rp + 1]};
                 acc = acc + pr;
                 facc[m][rq * 4 + 2 * rp] = acc.x; facc[m][rq * 4 + 2 * rp + 1] = acc.y;
@@ -85,18 +105,28 @@ __global__ __launch_bounds__(256) void mmq_q80_kernel(const uint8_t *__restrict_
         for (int i = tid; i < nbc * TT; i += 256) {
             const int b = i / TT, m = i - b * TT;
             const int t = t0 + m < T ? t0 + m : T - 1;
-            s_da[i] = h2f(ad[(size_t)t * nb + b0 + b]);
+            const float da = h2f(ad[(size_t)t * nb + b0 + b]);
+            s_da[i] = da;
+            if constexpr (MINS) {                                      // d_a * (float)(sum of the block's 32 codes): exact integer, one rounding
+                const i32x4 *ap = reinterpret_cast<const i32x4 *>(aq + (size_t)t * K + (size_t)(b0 + b) * 32);
+                const i32x4 a0 = ap[0], a1 = ap[1];
+                int sum = 0;
+#pragma unroll
+                for (int j = 0; j < 4; j++) { sum = dot4(0x01010101u, (uint32_t)a0[j], sum); sum = dot4(0x01010101u, (uint32_t)a1[j], sum); }
+                s_da[Q80_KC * TT + i] = da * (float)sum;
+            }
         }
         __syncthreads();
         if (!rows_ok) continue;
         int b = 0;
         for (; b + Q80_UNROLL <= nbc; b += Q80_UNROLL) {               // the loads of a group are issued before its first MFMA
             i32x4 w[Q80_UNROLL];
-            uint16_t dh[Q80_UNROLL];
+            uint16_t dh[Q80_UNROLL], mh[Q80_UNROLL];
 #pragma unroll
             for (int u = 0; u < Q80_UNROLL; u++) {
                 w[u] = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(wrow + (size_t)(b0 + b + u) * 32));
                 dh[u] = wd[b0 + b + u];
+                if constexpr (MINS) mh[u] = wm[b0 + b + u];
             }
 #pragma unroll
             for (int m = 0; m < MT; m++) {
@@ -106,18 +136,18 @@ __global__ __launch_bounds__(256) void mmq_q80_kernel(const uint8_t *__restrict_
 #pragma unroll
                 for (int u = 0; u < Q80_UNROLL; u++) {
                     const i32x16 c = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[u], w[u], z, 0, 0, 0);
-                    fold(c, h2f(dh[u]), b + u, m);
+                    fold(c, h2f(dh[u]), MINS ? h2f(mh[u]) : 0.0f, b + u, m);
                 }
             }
         }
         for (; b < nbc; b++) {
             const i32x4 w = *reinterpret_cast<const i32x4 *>(wrow + (size_t)(b0 + b) * 32);
-            const float dw = h2f(wd[b0 + b]);
+            const float dw = h2f(wd[b0 + b]), mw = MINS ? h2f(wm[b0 + b]) : 0.0f;
 #pragma unroll
             for (int m = 0; m < MT; m++) {
                 const i32x4 a = *reinterpret_cast<const i32x4 *>(arow[m] + (size_t)(b0 + b) * 32);
                 const i32x16 c = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, w, z, 0, 0, 0);
-                fold(c, dw, b, m);
+                fold(c, dw, mw, b, m);
             }
         }
     }
@@ -140,6 +170,8 @@ __global__ __launch_bounds__(256) void mmq_q80_kernel(const uint8_t *__restrict_
 // Q4_0 / Q5_0 / IQ4_NL rows as Q8_0 device rows ([codes K][scales K/32]): code = nibble - 8, (nibble | fifth bit) - 16, level[nibble] - all int8 -
 // with the block's own f16 scale.  The copy is EXACT (same integers, same scales), so the kernel above computes the same block sums as the format's
 // own vec_dot; it is made once at load for prompt batches (1.06 B per weight beside the file's 0.56 - 0.69).
+// Q4_1 / Q5_1: the code is q itself (0..15 / 0..31) and the row gains the blocks' f16 minimums as a third plane ([codes K][scales K/32][mins K/32],
+// 1.125 B per weight), for the MINS form of the kernel.
 __global__ __launch_bounds__(256) void expand_nib32_q80_kernel(int type, const uint8_t *__restrict__ W, size_t row_bytes, int n_rows, int K, uint8_t *__restrict__ dst,
                                                                size_t dst_row) {
     const int row = blockIdx.y;
@@ -152,48 +184,59 @@ __global__ __launch_bounds__(256) void expand_nib32_q80_kernel(int type, const u
         const int nib = (r[(size_t)b * 16 + (j & 15)] >> (4 * (j >> 4))) & 0x0f;
         int code;
         if (type == T_Q4_0) code = nib - 8;
-        else if (type == T_Q5_0) {
+        else if (type == T_Q5_0 || type == T_Q5_1) {
             const uint32_t qh = *reinterpret_cast<const uint32_t *>(r + half + (size_t)b * 4);
-            code = (nib | (int)(((qh >> j) & 1u) << 4)) - 16;
-        } else code = iq4nl_value(nib);
+            code = (nib | (int)(((qh >> j) & 1u) << 4)) - (type == T_Q5_0 ? 16 : 0);
+        } else if (type == T_Q4_1) code = nib;
+        else code = iq4nl_value(nib);
         o[e] = (uint8_t)(int8_t)code;
         if (j == 0) {
-            const uint16_t d = *reinterpret_cast<const uint16_t *>(r + half + (type == T_Q5_0 ? (size_t)nblk * 4 : 0) + (size_t)b * 2);
-            *reinterpret_cast<uint16_t *>(o + (size_t)K + (size_t)b * 2) = d;
+            const uint16_t *dp = reinterpret_cast<const uint16_t *>(r + nib32_d_off(type, (size_t)K));
+            *reinterpret_cast<uint16_t *>(o + (size_t)K + (size_t)b * 2) = dp[b];
+            if (nib32_has_min(type)) *reinterpret_cast<uint16_t *>(o + (size_t)K + (size_t)nblk * 2 + (size_t)b * 2) = dp[nblk + b];
         }
     }
 }
+size_t mmq_q80_copy_row_bytes(int type, int K) {
+    const size_t b = (size_t)K + (size_t)(K >> 5) * (nib32_has_min(type) ? 4 : 2);
+    return (b + 15) & ~(size_t)15;
+}
 size_t mmq_q80_copy_bytes(int type, int64_t n_rows, int K) {
-    if ((type != T_Q4_0 && type != T_Q5_0 && type != T_IQ4_NL) || (K % 32) != 0 || K > 16384) return 0;
-    return (size_t)n_rows * dev_row_bytes(T_Q8_0, K);
+    if ((type != T_Q4_0 && type != T_Q5_0 && type != T_IQ4_NL && !nib32_has_min(type)) || (K % 32) != 0 || K > 16384) return 0;
+    return (size_t)n_rows * mmq_q80_copy_row_bytes(type, K);
 }
 hipError_t launch_expand_q80_copy(int type, const uint8_t *W, size_t row_bytes, int n_rows, int K, uint8_t *dst, hipStream_t st) {
     if (!mmq_q80_copy_bytes(type, n_rows, K)) return hipErrorInvalidValue;
     for (int r0 = 0; r0 < n_rows; r0 += 65535) {
         const int nr = n_rows - r0 < 65535 ? n_rows - r0 : 65535;
         hipLaunchKernelGGL(expand_nib32_q80_kernel, dim3((unsigned)((K + 255) / 256 < 8 ? (K + 255) / 256 : 8), nr), dim3(256), 0, st, type, W + (size_t)r0 * row_bytes, row_bytes, nr, K,
-                           dst + (size_t)r0 * dev_row_bytes(T_Q8_0, K), dev_row_bytes(T_Q8_0, K));
+                           dst + (size_t)r0 * mmq_q80_copy_row_bytes(type, K), mmq_q80_copy_row_bytes(type, K));
     }
     return hipGetLastError();
 }
 
 bool mmq_q80_applicable(int type, int K, int T) { return type == T_Q8_0 && T >= 32 && K >= 32 && (K % 32) == 0 && K <= 16384; }
 
+static int g_q80_mt = 0;      // 0: pick per launch; 1 / 2 / 4: the tests force a form (every form gives the same bits)
+void mmq_q80_set_tiles(int mt) { g_q80_mt = (mt == 1 || mt == 2 || mt == 4) ? mt : 0; }
+
+template <bool MINS>
+static void launch_q80_form(int mt, const uint8_t *W, size_t row_bytes, int n_rows, int K, int T, const ActQuant &q, float *out, int ld_out, const float *resid, hipStream_t st) {
+    const dim3 grid((unsigned)((n_rows + 127) / 128), (unsigned)((T + 32 * mt - 1) / (32 * mt)));
+    if (mt == 4) hipLaunchKernelGGL((mmq_q80_kernel<4, MINS>), grid, dim3(256), 0, st, W, row_bytes, n_rows, K, T, q.qs0, q.d0, out, ld_out, resid);
+    else if (mt == 2) hipLaunchKernelGGL((mmq_q80_kernel<2, MINS>), grid, dim3(256), 0, st, W, row_bytes, n_rows, K, T, q.qs0, q.d0, out, ld_out, resid);
+    else hipLaunchKernelGGL((mmq_q80_kernel<1, MINS>), grid, dim3(256), 0, st, W, row_bytes, n_rows, K, T, q.qs0, q.d0, out, ld_out, resid);
+}
+
 hipError_t launch_mmq_q80(const uint8_t *W, size_t row_bytes, int n_rows, int K, int T, const ActQuant &q, float *out, int ld_out,
-                          const float *resid, hipStream_t st) {
+                          const float *resid, hipStream_t st, bool mins) {
     if (!mmq_q80_applicable(T_Q8_0, K, T) || !q.qs0 || !q.d0) return hipErrorInvalidValue;
     // four token tiles per wave once that still leaves a workgroup per CU; each output keeps its own block order, so the result does not depend on MT
     const long wg4 = (long)((n_rows + 127) / 128) * ((T + 127) / 128);
-    if (T >= 128 && wg4 >= num_cu()) {
-        const dim3 grid((unsigned)((n_rows + 127) / 128), (unsigned)((T + 127) / 128));
-        hipLaunchKernelGGL((mmq_q80_kernel<4>), grid, dim3(256), 0, st, W, row_bytes, n_rows, K, T, q.qs0, q.d0, out, ld_out, resid);
-    } else if (T >= 64 && wg4 * 2 >= num_cu()) {
-        const dim3 grid((unsigned)((n_rows + 127) / 128), (unsigned)((T + 63) / 64));
-        hipLaunchKernelGGL((mmq_q80_kernel<2>), grid, dim3(256), 0, st, W, row_bytes, n_rows, K, T, q.qs0, q.d0, out, ld_out, resid);
-    } else {
-        const dim3 grid((unsigned)((n_rows + 127) / 128), (unsigned)((T + 31) / 32));
-        hipLaunchKernelGGL((mmq_q80_kernel<1>), grid, dim3(256), 0, st, W, row_bytes, n_rows, K, T, q.qs0, q.d0, out, ld_out, resid);
-    }
+    int mt = (T >= 128 && wg4 >= num_cu()) ? 4 : (T >= 64 && wg4 * 2 >= num_cu()) ? 2 : 1;
+    if (g_q80_mt) mt = g_q80_mt;
+    if (mins) launch_q80_form<true>(mt, W, row_bytes, n_rows, K, T, q, out, ld_out, resid, st);
+    else launch_q80_form<false>(mt, W, row_bytes, n_rows, K, T, q, out, ld_out, resid, st);
     return hipGetLastError();
 }
 

@@ -408,12 +408,13 @@ template <> struct Item<T_IQ4_XS> {
 //   Q4_0:   sum (nib - 8) a      = dot(nib, a) - 8 sum a
 //   Q5_0:   sum (nib | b << 4 - 16) a = dot(nib + 16 b, a) - 16 sum a
 //   IQ4_NL: sum level[nib] a     (levels looked up with v_perm from the 16-byte code book)
+//   Q4_1 / Q5_1: sum q a with q = nib (| b << 4) unsigned, and the block's sum a kept beside it (msum): the minimum's factor
 template <int TYPE> struct ItemNib32 {
     uint4 hdr;
     static constexpr int EPP = 1024;
     uint4 q;          // the block's 16 code bytes
     uint32_t qh;
-    float d;
+    float d, m;       // m: the block minimum (Q4_1 / Q5_1)
     int e;
     bool valid;
     __device__ __forceinline__ void load(const uint8_t *row, int K, int pass, int lane) {
@@ -426,13 +427,18 @@ template <int TYPE> struct ItemNib32 {
             if (TYPE == T_Q5_0) {
                 qh = *reinterpret_cast<const uint32_t *>(row + half + (size_t)b * 4);
                 hdr.x = *reinterpret_cast<const uint16_t *>(row + half + (size_t)(K >> 5) * 4 + (size_t)b * 2);
+            } else if (nib32_has_min(TYPE)) {
+                const size_t doff = nib32_d_off(TYPE, (size_t)K);
+                if (TYPE == T_Q5_1) qh = *reinterpret_cast<const uint32_t *>(row + half + (size_t)b * 4);
+                hdr.x = *reinterpret_cast<const uint16_t *>(row + doff + (size_t)b * 2);
+                hdr.y = *reinterpret_cast<const uint16_t *>(row + doff + (size_t)(K >> 5) * 2 + (size_t)b * 2);
             } else {
                 hdr.x = *reinterpret_cast<const uint16_t *>(row + half + (size_t)b * 2);
             }
         }
     }
     __device__ __forceinline__ void prep(int lane) {
-        if (valid) d = h2f((uint16_t)hdr.x);
+        if (valid) { d = h2f((uint16_t)hdr.x); if (nib32_has_min(TYPE)) m = h2f((uint16_t)hdr.y); }
     }
     static __device__ __forceinline__ uint32_t levels(uint32_t idx) {      // four IQ4_NL levels from four nibble indices (one per byte)
         const uint32_t lo = __builtin_amdgcn_perm(0xf6eaddcfu, 0xbfad9881u, idx & 0x07070707u);
@@ -441,17 +447,16 @@ template <int TYPE> struct ItemNib32 {
         return (hi & m) | (lo & ~m);
     }
     __device__ __forceinline__ void ints(const ActLds &A, int t, int lane, int &isum, int &msum) const {
-        int s = 0;
+        int s = 0, asum = 0;
         if (valid) {
             const int h = (e >> 4) & 1;
             const uint4 a = ld16(A.qs0 + (size_t)t * A.K + e);
             const uint32_t qq[4] = {q.x, q.y, q.z, q.w}, aa[4] = {a.x, a.y, a.z, a.w};
-            int asum = 0;
 #pragma unroll
             for (int w = 0; w < 4; w++) {
                 uint32_t v = (qq[w] >> (4 * h)) & 0x0f0f0f0fu;
                 if (TYPE == T_IQ4_NL) { s = dot4(levels(v), aa[w], s); continue; }
-                if (TYPE == T_Q5_0) {
+                if (nib32_has_qh(TYPE)) {
                     const uint32_t bits = (qh >> (16 * h + 4 * w)) & 0xfu;              // fifth bits of these four elements
                     v |= ((bits * 0x00204081u) & 0x01010101u) << 4;
                 }
@@ -463,12 +468,15 @@ template <int TYPE> struct ItemNib32 {
         }
         isum = s + __shfl_xor(s, 1, 64);   // both halves of the 32-element block
         msum = 0;
+        if (nib32_has_min(TYPE)) msum = asum + __shfl_xor(asum, 1, 64);    // the block's activation sum, the factor of its minimum
     }
     __device__ __forceinline__ float dot(const ActLds &A, int t, int lane) const {
         int isum, msum;
         ints(A, t, lane, isum, msum);     // shuffle executed by all lanes
         if (!valid || (lane & 1)) return 0.0f;
         const float da = h2f(A.d0[(size_t)t * (A.K >> 5) + (e >> 5)]);
+        if (nib32_has_min(TYPE))                                    // (d_x * d_y) * sumi + m * (d_y * suma): two rounded products, one add, no fma
+            return __fadd_rn(__fmul_rn(__fmul_rn(d, da), (float)isum), __fmul_rn(m, __fmul_rn(da, (float)msum)));
         if (TYPE == T_Q4_0) return ((float)isum * d) * da;          // ggml_vec_dot_q4_0_q8_0: sumi * d_x * d_y, left to right
         return (d * da) * (float)isum;                              // q5_0 / iq4_nl: (d_x * d_y) * sumi
     }
@@ -476,6 +484,8 @@ template <int TYPE> struct ItemNib32 {
 template <> struct Item<T_Q4_0> : ItemNib32<T_Q4_0> {};
 template <> struct Item<T_Q5_0> : ItemNib32<T_Q5_0> {};
 template <> struct Item<T_IQ4_NL> : ItemNib32<T_IQ4_NL> {};
+template <> struct Item<T_Q4_1> : ItemNib32<T_Q4_1> {};
+template <> struct Item<T_Q5_1> : ItemNib32<T_Q5_1> {};
 
 template <> struct Item<T_Q8_0> {
     uint4 hdr;
@@ -717,6 +727,9 @@ __device__ __forceinline__ void run_segment(const MMVQArgs &a, const MMVQSeg &sg
 
 // Blocks [seg_block0[s], seg_block0[s+1]) work on segment s, so the weight TYPE is block-uniform and
 // each type's code path keeps its own register footprint.
+// (The argument struct is read where it lies, in the kernel-argument segment.  The compiler gives up on that - and copies the 328-byte struct to scratch, 336
+// bytes per lane - once a kernel reads it in more than instcombine-max-copied-from-constant-users places, 300 by default; with twelve type cases the one-token
+// form does, so build.py raises the limit for this file.)
 template <int NT, int BS>
 __global__ __launch_bounds__(BS) void mmvq_kernel(const MMVQArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -734,6 +747,8 @@ __global__ __launch_bounds__(BS) void mmvq_kernel(const MMVQArgs a) {
         case T_Q4_0: run_segment<T_Q4_0, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_Q5_0: run_segment<T_Q5_0, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_IQ4_NL: run_segment<T_IQ4_NL, NT, BS>(a, a.seg[s], smem, bis); break;
+        case T_Q4_1: run_segment<T_Q4_1, NT, BS>(a, a.seg[s], smem, bis); break;
+        case T_Q5_1: run_segment<T_Q5_1, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_IQ4_XS: run_segment<T_IQ4_XS, NT, BS>(a, a.seg[s], smem, bis); break;
         default: break;
     }
@@ -866,6 +881,8 @@ __global__ __launch_bounds__(256, 2) void mmvq_tiled_kernel(const MMVQArgs a) {
         case T_Q4_0: run_tiled<T_Q4_0, NT>(a, a.seg[s], smem, bis); break;
         case T_Q5_0: run_tiled<T_Q5_0, NT>(a, a.seg[s], smem, bis); break;
         case T_IQ4_NL: run_tiled<T_IQ4_NL, NT>(a, a.seg[s], smem, bis); break;
+        case T_Q4_1: run_tiled<T_Q4_1, NT>(a, a.seg[s], smem, bis); break;
+        case T_Q5_1: run_tiled<T_Q5_1, NT>(a, a.seg[s], smem, bis); break;
         case T_IQ4_XS: run_tiled<T_IQ4_XS, NT>(a, a.seg[s], smem, bis); break;
         default: break;
     }
@@ -1008,7 +1025,7 @@ __global__ __launch_bounds__(256) void mmvq_ints_kernel(const MMVQArgs a, int32_
             int is = 0, ms = 0;
             if constexpr (act_is_q80(TYPE)) {
                 it.ints(A, 0, lane, is, ms);
-                if (it.valid && !(lane & 1)) { isum_out[(size_t)r * nblk + (it.e >> 5)] = is; msum_out[(size_t)r * nblk + (it.e >> 5)] = 0; }
+                if (it.valid && !(lane & 1)) { isum_out[(size_t)r * nblk + (it.e >> 5)] = is; msum_out[(size_t)r * nblk + (it.e >> 5)] = ms; }
             } else {
                 if (it.valid) it.ints(A, 0, lane, is, ms);
                 is += __shfl_xor(is, 1, 64); ms += __shfl_xor(ms, 1, 64);
@@ -1036,6 +1053,8 @@ hipError_t launch_mmvq_ints(MMVQArgs a, int32_t *isum, int32_t *msum, hipStream_
         case T_Q4_0: hipLaunchKernelGGL(mmvq_ints_kernel<T_Q4_0>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_Q5_0: hipLaunchKernelGGL(mmvq_ints_kernel<T_Q5_0>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_IQ4_NL: hipLaunchKernelGGL(mmvq_ints_kernel<T_IQ4_NL>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
+        case T_Q4_1: hipLaunchKernelGGL(mmvq_ints_kernel<T_Q4_1>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
+        case T_Q5_1: hipLaunchKernelGGL(mmvq_ints_kernel<T_Q5_1>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_IQ4_XS: hipLaunchKernelGGL(mmvq_ints_kernel<T_IQ4_XS>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         default: return hipErrorInvalidValue;
     }

@@ -55,6 +55,12 @@ __global__ __launch_bounds__(NT) void mmvq_fast_kernel(const MMVQArgs a) {
         case T_IQ4_NL:
             if constexpr (FUSE != 0 || KB <= 2) run_fast<T_IQ4_NL, KB, NT, FUSE>(a, a.seg[s], smem, gw, nw, NoSync(), sel_j);
             break;
+        case T_Q4_1:
+            if constexpr (FUSE != 0 || KB <= 2) run_fast<T_Q4_1, KB, NT, FUSE>(a, a.seg[s], smem, gw, nw, NoSync(), sel_j);
+            break;
+        case T_Q5_1:
+            if constexpr (FUSE != 0 || KB <= 2) run_fast<T_Q5_1, KB, NT, FUSE>(a, a.seg[s], smem, gw, nw, NoSync(), sel_j);
+            break;
         default: break;
     }
 }

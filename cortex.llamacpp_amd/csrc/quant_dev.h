@@ -142,6 +142,15 @@ __device__ __forceinline__ float dequant_elem(int type, const uint8_t *row, int 
             if (type == T_Q4_0) return __fmul_rn((float)(nib - 8), d);
             return __fmul_rn(d, (float)iq4nl_value(nib));
         }
+        case T_Q4_1: case T_Q5_1: {   // the same nibble field with unsigned codes and a per-block minimum: y = q d + m, the product rounded before the add
+            const int b = e >> 5, r = e & 31;
+            int q = (row[(size_t)b * 16 + (r & 15)] >> (4 * (r >> 4))) & 0x0f;
+            const size_t half = (size_t)K >> 1, doff = nib32_d_off(type, (size_t)K);
+            if (type == T_Q5_1) q |= (int)(((*reinterpret_cast<const uint32_t *>(row + half + (size_t)b * 4) >> r) & 1u) << 4);
+            const float d = h2f(*reinterpret_cast<const uint16_t *>(row + doff + (size_t)b * 2));
+            const float m = h2f(*reinterpret_cast<const uint16_t *>(row + doff + (size_t)(K >> 5) * 2 + (size_t)b * 2));
+            return __fadd_rn(__fmul_rn((float)q, d), m);
+        }
         case T_Q4_K: case T_Q5_K: {
             const int bsz = type == T_Q4_K ? 144 : 176;
             const uint8_t *b = row + (size_t)(e >> 8) * bsz;

@@ -20,11 +20,12 @@ import numpy as np
 F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 2, 8, 12, 13, 14
 Q2_K, Q3_K = 10, 11
 Q5_0, IQ4_NL = 6, 20
+Q4_1, Q5_1 = 3, 7
 IQ4_XS = 23
 BF16 = 30
-TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K", Q2_K: "q2_K", Q3_K: "q3_K", Q5_0: "q5_0", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", BF16: "bf16"}
-BLOCK_ELEMS = {F32: 1, F16: 1, Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q2_K: 256, Q3_K: 256, Q5_0: 32, IQ4_NL: 32, IQ4_XS: 256, BF16: 1}
-BLOCK_BYTES = {F32: 4, F16: 2, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q2_K: 84, Q3_K: 110, Q5_0: 22, IQ4_NL: 18, IQ4_XS: 136, BF16: 2}
+TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K", Q2_K: "q2_K", Q3_K: "q3_K", Q5_0: "q5_0", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", BF16: "bf16", Q4_1: "q4_1", Q5_1: "q5_1"}
+BLOCK_ELEMS = {F32: 1, F16: 1, Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q2_K: 256, Q3_K: 256, Q5_0: 32, IQ4_NL: 32, IQ4_XS: 256, BF16: 1, Q4_1: 32, Q5_1: 32}
+BLOCK_BYTES = {F32: 4, F16: 2, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q2_K: 84, Q3_K: 110, Q5_0: 22, IQ4_NL: 18, IQ4_XS: 136, BF16: 2, Q4_1: 20, Q5_1: 24}
 
 DT_Q4_0 = np.dtype([("d", "<f2"), ("qs", "u1", 16)])
 DT_Q8_0 = np.dtype([("d", "<f2"), ("qs", "i1", 32)])
@@ -34,18 +35,24 @@ DT_Q6_K = np.dtype([("ql", "u1", 128), ("qh", "u1", 64), ("scales", "i1", 16), (
 DT_Q2_K = np.dtype([("scales", "u1", 16), ("qs", "u1", 64), ("d", "<f2"), ("dmin", "<f2")])
 DT_Q3_K = np.dtype([("hmask", "u1", 32), ("qs", "u1", 64), ("scales", "u1", 12), ("d", "<f2")])
 DT_Q5_0 = np.dtype([("d", "<f2"), ("qh", "u1", 4), ("qs", "u1", 16)])
+# Q4_1 / Q5_1: unsigned codes q (0..15; 0..31 with the fifth bit of element j in bit j of qh) and a per-block minimum, weight = q * d + m
+DT_Q4_1 = np.dtype([("d", "<f2"), ("m", "<f2"), ("qs", "u1", 16)])
+DT_Q5_1 = np.dtype([("d", "<f2"), ("m", "<f2"), ("qh", "u1", 4), ("qs", "u1", 16)])
 # IQ4_XS: 6-bit sub-block scales ls (low nibbles in scales_l, high bit pairs in scales_h), weight = d * (ls - 32) * kvalues_iq4nl[nibble]
 DT_IQ4_XS = np.dtype([("d", "<f2"), ("scales_h", "<u2"), ("scales_l", "u1", 4), ("qs", "u1", 128)])
-BLOCK_DTYPE = {Q4_0: DT_Q4_0, Q8_0: DT_Q8_0, Q4_K: DT_Q4_K, Q5_K: DT_Q5_K, Q6_K: DT_Q6_K, Q2_K: DT_Q2_K, Q3_K: DT_Q3_K, Q5_0: DT_Q5_0, IQ4_NL: DT_Q4_0, IQ4_XS: DT_IQ4_XS}
+BLOCK_DTYPE = {Q4_0: DT_Q4_0, Q8_0: DT_Q8_0, Q4_K: DT_Q4_K, Q5_K: DT_Q5_K, Q6_K: DT_Q6_K, Q2_K: DT_Q2_K, Q3_K: DT_Q3_K, Q5_0: DT_Q5_0, IQ4_NL: DT_Q4_0, IQ4_XS: DT_IQ4_XS, Q4_1: DT_Q4_1, Q5_1: DT_Q5_1}
 for _t, _dt in BLOCK_DTYPE.items():
     assert _dt.itemsize == BLOCK_BYTES[_t], (_t, _dt.itemsize)
 
 # std of (dequantised weight / d) for uniformly random block payloads (derived in DESIGN.md)
 # (Q2_K: w / d = sc * q - r * m with sc, m uniform 0..15, q uniform 0..3, r = 1.5: variance 144.7 + 2.25 * 21.25; Q3_K: (sc - 32) * q, sc 0..63, q -4..3)
 _UNIT_STD = {Q4_0: 4.6, Q8_0: 73.9, Q4_K: 258.0, Q5_K: 527.0, Q6_K: 1367.0, Q2_K: 13.9, Q3_K: 43.3, Q5_0: 9.23, IQ4_NL: 67.2,
-             IQ4_XS: 1246.3}   # (Q5_0: codes 0..31 minus 16; IQ4_NL: the sixteen code-book levels; IQ4_XS: (ls - 32) * level, ls 0..63: sqrt(341.5 * 4548))
+             IQ4_XS: 1246.3,   # (Q5_0: codes 0..31 minus 16; IQ4_NL: the sixteen code-book levels; IQ4_XS: (ls - 32) * level, ls 0..63: sqrt(341.5 * 4548))
+             Q4_1: 4.61, Q5_1: 9.23}   # (codes uniform 0..15 / 0..31 around the minimum below: sqrt((16^2 - 1) / 12), sqrt((32^2 - 1) / 12))
 # dmin/d ratio that centres the weights of a random block on zero
 _DMIN_RATIO = {Q4_K: 7.5, Q5_K: 15.5, Q2_K: 1.5}
+# m/d ratio doing the same for the per-block minimum of Q4_1 / Q5_1 (weight = q d + m: minus the mean code)
+_MIN_RATIO = {Q4_1: -7.5, Q5_1: -15.5}
 
 
 def row_bytes(t: int, n: int) -> int:
@@ -76,7 +83,30 @@ def random_blocks(rng: np.random.Generator, t: int, n_elems: int, std: float) ->
     blk["d"] = d.astype("<f2")
     if t in _DMIN_RATIO:
         blk["dmin"] = (d * _DMIN_RATIO[t]).astype("<f2")
+    if t in _MIN_RATIO:
+        blk["m"] = (d * _MIN_RATIO[t]).astype("<f2")
     return raw
+
+
+def quantize_min32(t: int, x: np.ndarray) -> np.ndarray:
+    """x (f32, a multiple of 32 values) as Q4_1 / Q5_1 blocks (raw bytes), by ggml's reference quantisers quantize_row_q4_1_ref / quantize_row_q5_1_ref:
+    per block d = (max - min) / 15 (Q5_1: / 31), m = min, q = min(15 | 31, (int)((x - min) * (1 / d) + 0.5)) in f32 (1 / d = 0 for a constant block); d and m are
+    stored as f16.  Element j < 16 goes to the low nibble of qs[j], element j + 16 to the high one; Q5_1's fifth bit of element j is bit j of qh."""
+    assert t in (Q4_1, Q5_1), t
+    top = 15 if t == Q4_1 else 31
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 32)
+    mn, mx = x.min(axis=1), x.max(axis=1)
+    d = ((mx - mn) / np.float32(top)).astype(np.float32)
+    with np.errstate(divide="ignore"):
+        inv = np.where(d != 0, np.float32(1.0) / d, np.float32(0.0)).astype(np.float32)
+    q = np.minimum(top, (((x - mn[:, None]) * inv[:, None]).astype(np.float32) + np.float32(0.5)).astype(np.int32)).astype(np.uint32)
+    blk = np.zeros(x.shape[0], BLOCK_DTYPE[t])
+    blk["d"], blk["m"] = d.astype("<f2"), mn.astype("<f2")
+    blk["qs"] = ((q[:, :16] & 15) | ((q[:, 16:] & 15) << 4)).astype(np.uint8)
+    if t == Q5_1:
+        qh = (((q >> 4) & 1) << np.arange(32, dtype=np.uint32)).sum(axis=1, dtype=np.uint32)
+        blk["qh"] = qh.astype("<u4").view(np.uint8).reshape(-1, 4)
+    return blk.view(np.uint8).reshape(-1)
 
 
 # ---------------------------------------------------------------- container
@@ -276,7 +306,7 @@ CONFIGS = {
                                          n_ff_exp=1536),
 }
 
-FTYPE_ID = {"f16": 1, "bf16": 32, "q4_0": 2, "q5_0": 8, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18}
+FTYPE_ID = {"f16": 1, "bf16": 32, "q4_0": 2, "q4_1": 3, "q5_0": 8, "q5_1": 9, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18}
 
 
 def use_more_bits(i: int, n: int) -> bool:
@@ -316,14 +346,14 @@ def tensor_type(cfg: LlamaConfig, ftype: str, kind: str, il: int) -> int:
         if kind == "attn_output":
             return Q3_K if q2 else Q4_K
         return Q2_K if q2 else Q3_K
-    if ftype in ("q4_0", "q5_0", "iq4_nl"):
+    if ftype in ("q4_0", "q5_0", "iq4_nl", "q4_1", "q5_1"):
         # the 32-element formats (llama-quantize's legacy types and the fallbacks it takes for rows that are not a multiple of 256): output Q6_K;
         # IQ4_NL promotes attn_v (grouped-query models) and the first eighth of ffn_down to Q5_K, as upstream does for IQ4_NL / IQ4_XS
         if kind == "output":
             return Q6_K
         if ftype == "iq4_nl" and ((kind == "attn_v" and cfg.n_head // cfg.n_head_kv >= 4) or (kind == "ffn_down" and il < max(1, cfg.n_layer // 8))):
             return Q5_K
-        return {"q4_0": Q4_0, "q5_0": Q5_0, "iq4_nl": IQ4_NL}[ftype]
+        return {"q4_0": Q4_0, "q5_0": Q5_0, "iq4_nl": IQ4_NL, "q4_1": Q4_1, "q5_1": Q5_1}[ftype]
     if ftype == "iq4_xs":
         # upstream's mix for IQ4_XS (the IQ4_NL one above): output Q6_K; attn_v Q5_K with a query / kv head ratio >= 4 and the first eighth of ffn_down
         # Q5_K; a tensor whose rows are not a multiple of 256 falls back to IQ4_NL; everything else IQ4_XS, expert tensors included.  token_embd stays

@@ -189,8 +189,8 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             fail = true;
             return;
         }
-        if (P > 1 && ti->type == T_IQ4_XS) {               // (the row split's column cuts and exchange steps are untested with it)
-            err = "row split (split_mode \"row\" / tp_size > 1) of iq4_xs tensors is not supported (tensor " + name + "): load the file on one device";
+        if (P > 1 && (ti->type == T_IQ4_XS || nib32_has_min(ti->type))) {   // (the row split's column cuts and exchange steps are untested with them)
+            err = std::string("row split (split_mode \"row\" / tp_size > 1) of ") + ggml_type_name(ti->type) + " tensors is not supported (tensor " + name + "): load the file on one device";
             fail = true;
             return;
         }
@@ -445,7 +445,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             for (DevTensor *d : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down, &L.gate_exps, &L.up_exps, &L.down_exps})
                 if (d->valid() && (mmq_planes_bytes(d->type, d->N, (int)d->K) || mmq_q80_copy_bytes(d->type, d->N, (int)d->K))) want.push_back(d);
         // (an *_exps tensor holds one plane set per expert, back to back: a prompt batch runs one contraction per expert)
-        // (K-quants: the two int8 MFMA planes; Q4_0 / Q5_0 / IQ4_NL: an exact Q8_0-layout copy for the Q8_0 prompt kernel)
+        // (K-quants: the two int8 MFMA planes; Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1: an exact Q8_0-layout copy for the Q8_0 prompt kernel, with a min plane for the last two)
         auto planes_of = [](const DevTensor *d) {
             const size_t b = mmq_planes_bytes(d->type, d->N, (int)d->K);
             return ((b ? b : mmq_q80_copy_bytes(d->type, d->N, (int)d->K)) + 255) & ~(size_t)255;
@@ -1005,7 +1005,7 @@ hipError_t Context::ensure_prep(const ActQuant &aq, int K, int T) {
 // Q2_K / Q3_K / IQ4_XS tensors reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
 // (the types with an exact Q8_0-layout copy: act_is_q80 without Q8_0 itself, which needs none - so the chain stays spelled out)
 static bool q80_copy(const DevTensor &w, int K, int T) {
-    return (w.type == T_Q4_0 || w.type == T_Q5_0 || w.type == T_IQ4_NL) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
+    return (w.type == T_Q4_0 || w.type == T_Q5_0 || w.type == T_IQ4_NL || nib32_has_min(w.type)) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
 }
 static bool planes_small(const DevTensor &w, int K, int T) { return type_is_planes_only(w.type) && w.planes && T >= 32 && (K % 256) == 0; }
 
@@ -1025,8 +1025,8 @@ hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *
             if (w.planes) return launch_mmq_planes(w.type, w.planes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_ws_);
             return launch_mmq(w.type, w.data, w.row_bytes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
         }
-        if (q80_copy(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs0)      // prompt processing of Q4_0 / Q5_0 / IQ4_NL tensors: their exact Q8_0-layout copy
-            return launch_mmq_q80(w.planes, dev_row_bytes(T_Q8_0, K), (int)w.N, K, T, aq, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
+        if (q80_copy(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs0)      // prompt processing of Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 tensors: their exact Q8_0-layout copy
+            return launch_mmq_q80(w.planes, mmq_q80_copy_row_bytes(w.type, K), (int)w.N, K, T, aq, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, nib32_has_min(w.type));
         if (planes_small(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs) {
             // prompt processing of Q2_K / Q3_K / IQ4_XS tensors: their plane sets (expanded at load in the Q4_K / Q6_K plane formats, mmq.hip) on the same kernels
             if (w.type == T_Q2_K && !bh_over_) HIP_TRY(ensure_prep(aq, K, T));

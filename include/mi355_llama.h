@@ -202,9 +202,17 @@ MI355_API int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n_
 /* y[T][N] = W[N][K] . x[T][K]; W is ggml-layout blocks of `type`.  isum/msum (nullable):
  * per (token, row, block) integer partial sums for bit-exact checks.  IQ4_XS (type 23, Q8_K activations): isum is the
  * super-block's sum over sub-blocks of (ls - 32) * sum(level * q8), msum is 0.  BF16 (type 30): the rows of x are rounded to bf16
- * (ggml's f32 -> bf16) and the model path's kernel runs: the matrix cores from 8 tokens on, else the bf16 weight stream. */
+ * (ggml's f32 -> bf16) and the model path's kernel runs: the matrix cores from 8 tokens on, else the bf16 weight stream.
+ * Q4_1 / Q5_1 (types 3 / 7, Q8_0 activations): K may be any multiple of 32 (for the tests' one-block and odd-block-count shapes: the rows are padded to whole
+ * 256-blocks for the quantiser and the planes compacted; a model's hidden sizes are multiples of 256); one token with K % 256 == 0 is quantised in the mat-vec's
+ * prologue, the form the weight stream takes these types in; isum is the block's sum of q * a (q the unsigned code), msum the block's
+ * sum of a - the block contributes (d * d8) * isum + m * (d8 * msum).  With "mmq_planes" 1 and T >= 32 the tensor's Q8_0-layout copy runs on the
+ * matrix cores, in the form "mmq_q80_tiles" forces (1 | 2 | 4 token tiles per wave; 0: the launcher's choice). */
 MI355_API int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T,
                                float *y, int32_t *isum, int32_t *msum);
+/* Test hook: y = resid + W . x (resid, y: [T][N]) on the launches that take a residual in their epilogue through this entry point: the Q8_0 prompt kernel
+ * (Q8_0 tensors, and the Q8_0-layout copies of Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 tensors with "mmq_planes" 1), T >= 32; MI355_ERR_ARG otherwise. */
+MI355_API int mi355_op_mul_mat_add(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y);
 /* ggml's f32 -> bf16 rounding as the bf16 kernels' activation pass does it (nearest, ties to even; NaN quieted; subnormals kept); n % 8 == 0 */
 MI355_API int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out);
 /* Up to three BF16 tensors W[s] ([N[s]][K] bf16 rows, K % 8 == 0; the matrix cores want K % 16 == 0) against the same T rows of x, as a decoder layer launches them:
@@ -217,7 +225,9 @@ MI355_API int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const i
                                     const float *resid, int32_t epi, int32_t path, int32_t tokens_per_launch, int32_t use_graph, float *const *y);
 /* ffn_gate and ffn_up (one K-quant type or IQ4_XS, N rows each, N % 32 == 0) against the same T activation rows with SwiGLU in the
  * epilogue, as the prompt path launches them (mmq_planes2_swiglu_kernel): y[t][n] = silu(Wg[n] . x[t]) * (Wu[n] . x[t]).
- * Shapes too small for that launch are refused unless the debug option "mmq_tiles" = 4 forces the kernel. */
+ * Shapes too small for that launch are refused unless the debug option "mmq_tiles" = 4 forces the kernel.
+ * Q4_1 / Q5_1 (any N, K % 256 == 0) run as a layer of such a file does: T >= 32 with "mmq_planes" 1 through the two Q8_0-layout copies and the SwiGLU
+ * pass, else the mat-vec with SwiGLU in its epilogue. */
 MI355_API int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y);
 MI355_API int mi355_op_rms_norm_mul(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y);
 MI355_API int mi355_op_rope(float *x, int32_t n_head, int32_t head_dim, int32_t n_rot, const int32_t *pos, int64_t T,
@@ -317,7 +327,7 @@ MI355_API void mi355_engine_set_log_callback(mi355_engine *e, mi355_log_callback
 /* Test / tool switches of the per-op entry points: "mmq_planes" (1: mi355_op_mul_mat with T >= 32 expands the weight
  * into MFMA planes first, as a loaded model does; 0: expands on the fly inside the kernel - Q2_K / Q3_K / IQ4_XS have
  * no on-the-fly form and take the mat-vec then), "mmq_tiles" (0 | 1 | 2
- * token tiles per wave), "mmq_ksplit" (1: 8 <= T <= 64 uses the K-split small-batch kernel, as the runtime does; 0: the
+ * token tiles per wave), "mmq_q80_tiles" (test hook: 0 | 1 | 2 | 4 token tiles per wave of the Q8_0 prompt kernel whatever the shape; every form gives the same bits), "mmq_ksplit" (1: 8 <= T <= 64 uses the K-split small-batch kernel, as the runtime does; 0: the
  * kernels the other T ranges use); and of contexts created afterwards: "decode_mega" (1: single-token steps of a dense
  * K-quant model with Llama-3-8B's layer geometry run every layer in one launch; 0, the default: one launch per operation
  * — both produce the same bits; the single launch measured slower); "moe_group_min" (batches of at least
