@@ -13,6 +13,7 @@ Q5_0, IQ4_NL = 6, 20
 Q4_1, Q5_1 = 3, 7
 IQ4_XS = 23
 BF16 = 30
+MXFP4 = 39
 
 
 class MI355Error(RuntimeError):
@@ -236,7 +237,7 @@ class Backend:
         y = np.zeros((T, N), np.float32)
         isum = msum = None
         if want_ints:
-            nblk = K // 32 if t in (Q8_0, Q4_0, Q5_0, IQ4_NL, Q4_1, Q5_1) else K // 256
+            nblk = K // 32 if t in (Q8_0, Q4_0, Q5_0, IQ4_NL, Q4_1, Q5_1, MXFP4) else K // 256
             isum = np.zeros((T, N, nblk), np.int32)
             msum = np.zeros((T, N, nblk), np.int32)
         self._chk(self.lib.mi355_op_mul_mat(t, _ptr(W), N, K, _ptr(x), T, _ptr(y), _ptr(isum), _ptr(msum)), "op_mul_mat")

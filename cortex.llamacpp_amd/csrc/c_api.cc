@@ -495,7 +495,7 @@ int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n, int64_t r
 
 int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (nib32_has_min(type)) return op_ffn_gate_up_nib32(type, Wg, Wu, N, K, x, T, y);
+    if (nib32_has_min(type) || nib32_has_e8(type)) return op_ffn_gate_up_nib32(type, Wg, Wu, N, K, x, T, y);
     const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
     const size_t pb = mmq_planes_bytes(type, N, (int)K);
     if (!grow || K % 256 || !pb || N % 32) { fail("bad type / K / N"); return MI355_ERR_ARG; }
@@ -539,8 +539,8 @@ hipError_t quantize_q80_padded(const float *dx, int K, int T, const ActQuant &q)
 int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y, int32_t *isum, int32_t *msum) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    // whole 256-blocks, as the models' hidden sizes are; Q4_1 / Q5_1 (32-element blocks) take any whole number of blocks
-    if (!grow || K <= 0 || (nib32_has_min(type) ? K % 32 : K % 256)) { fail("bad type / K"); return MI355_ERR_ARG; }
+    // whole 256-blocks, as the models' hidden sizes are; Q4_1 / Q5_1 / MXFP4 (32-element blocks) take any whole number of blocks
+    if (!grow || K <= 0 || ((nib32_has_min(type) || nib32_has_e8(type)) ? K % 32 : K % 256)) { fail("bad type / K"); return MI355_ERR_ARG; }
     DevBuf wsrc(grow * N), wdev(drow * N), dx((size_t)K * T * 4), dy((size_t)N * T * 4), dres(resid ? (size_t)N * T * 4 : 16);
     ActBufs ab((size_t)K, (size_t)T);
     if (!wsrc.up(W, grow * N) || !wdev.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !ab.ok() || !dres.p || (resid && !dres.up(resid, (size_t)N * T * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
@@ -560,11 +560,11 @@ int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x
             if (e == hipSuccess) e = hipDeviceSynchronize();
             if (e != hipSuccess) return hip_fail(e, "mmq_q80");
         } else
-        if (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes) {   // Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 prompt batches: exact Q8_0-layout copy
+        if (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes) {   // Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4 prompt batches: exact Q8_0-layout copy
             DevBuf cp(mmq_q80_copy_bytes(type, N, (int)K));
             if (!cp.p) return MI355_ERR_OOM;
             e = launch_expand_q80_copy(type, wdev.as<uint8_t>(), drow, (int)N, (int)K, cp.as<uint8_t>(), nullptr);
-            if (e == hipSuccess) e = launch_mmq_q80(cp.as<uint8_t>(), mmq_q80_copy_row_bytes(type, (int)K), (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, rs, nullptr, nib32_has_min(type));
+            if (e == hipSuccess) e = launch_mmq_q80(cp.as<uint8_t>(), mmq_q80_copy_row_bytes(type, (int)K), (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, rs, nullptr, mmq_q80_copy_form(type));
             if (e == hipSuccess) e = hipDeviceSynchronize();
             if (e != hipSuccess) return hip_fail(e, "mmq_q80 (copy)");
         } else
@@ -606,9 +606,9 @@ int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x
             a.seg[0].ld_out = (int)N; a.seg[0].row_bytes = drow;
             a.aq = ab.q.qs + t0 * K; a.ad = ab.q.d + t0 * (K / 256); a.abs = ab.q.bsums + t0 * (K / 16);
             a.aq0 = ab.q.qs0 + t0 * K; a.ad0 = ab.q.d0 + t0 * (K / 32);
-            // Q4_1 / Q5_1, one token: quantised in the mat-vec's prologue, as a decode step's ffn_down and head are - the weight stream takes Q8_0-activation
+            // Q4_1 / Q5_1 / MXFP4, one token: quantised in the mat-vec's prologue, as a decode step's ffn_down and head are - the weight stream takes Q8_0-activation
             // types only in that form (row pairs, single rows), the register ring with "mmvq_stream" 0; the same blocks, so the same result
-            if (nt == 1 && nib32_has_min(type) && (K % 256) == 0) { a.fuse_mode = 2; a.nx = dx.as<float>() + t0 * K; }
+            if (nt == 1 && (nib32_has_min(type) || nib32_has_e8(type)) && (K % 256) == 0) { a.fuse_mode = 2; a.nx = dx.as<float>() + t0 * K; }
             e = launch_mmvq(a, nullptr);
             if (e != hipSuccess) return hip_fail(e, "mmvq");
             t0 += nt;
@@ -660,7 +660,7 @@ int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x
     return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
 }
 
-// ffn_gate | ffn_up of a Q4_1 / Q5_1 layer with SwiGLU, as Context::ffn_gate_up runs them: prompt batches through the two tensors' Q8_0-layout copies
+// ffn_gate | ffn_up of a Q4_1 / Q5_1 / MXFP4 layer with SwiGLU, as Context::ffn_gate_up runs them: prompt batches through the two tensors' Q8_0-layout copies
 // and the SwiGLU pass ("mmq_planes" 1, T >= 32), else the mat-vec with SwiGLU in its epilogue in chunks of 16, 8, 4, 2, 1 tokens
 int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) {
     const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
@@ -682,8 +682,8 @@ int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N
         if (!cg.p || !cu.p) return MI355_ERR_OOM;
         e = launch_expand_q80_copy(type, wg.as<uint8_t>(), drow, (int)N, (int)K, cg.as<uint8_t>(), nullptr);
         if (e == hipSuccess) e = launch_expand_q80_copy(type, wu.as<uint8_t>(), drow, (int)N, (int)K, cu.as<uint8_t>(), nullptr);
-        if (e == hipSuccess) e = launch_mmq_q80(cg.as<uint8_t>(), crow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, nullptr, nullptr, true);
-        if (e == hipSuccess) e = launch_mmq_q80(cu.as<uint8_t>(), crow, (int)N, (int)K, (int)T, ab.q, du.as<float>(), (int)N, nullptr, nullptr, true);
+        if (e == hipSuccess) e = launch_mmq_q80(cg.as<uint8_t>(), crow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, nullptr, nullptr, mmq_q80_copy_form(type));
+        if (e == hipSuccess) e = launch_mmq_q80(cu.as<uint8_t>(), crow, (int)N, (int)K, (int)T, ab.q, du.as<float>(), (int)N, nullptr, nullptr, mmq_q80_copy_form(type));
         if (e == hipSuccess) e = launch_swiglu(dy.as<float>(), du.as<float>(), dy.as<float>(), N * T, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     } else {
@@ -1146,6 +1146,7 @@ int mi355_debug_set_option(const char *name, int32_t value) {
     if (!strcmp(name, "attn_out_fused")) { set_attn_out_fused(value); return MI355_OK; }     // (contexts created afterwards)
     if (!strcmp(name, "qkv_attn_fused")) { set_qkv_attn_fused(value); return MI355_OK; }     // Q | K | V inside the attention launch (applies from the next step's launches on; graphs captured earlier keep their form)
     if (!strcmp(name, "moe_group_min")) { set_moe_group_min(value); return MI355_OK; }
+    if (!strcmp(name, "moe_q80_grouped")) { set_moe_q80_grouped(value != 0); return MI355_OK; }
     if (!strcmp(name, "fa_v_acc_f16")) { set_fa_v_acc_f16(value); return MI355_OK; }              // f16 cache: the CPU path's fp16 V accumulation (parity mode)
     if (!strcmp(name, "raise_stream_error")) { debug_raise_stream_error((unsigned)value); return MI355_OK; }   // tests: what a timed-out in-kernel wait does
     if (!strcmp(name, "tp_null_group")) { tp_set_null_group(0, value); return MI355_OK; }

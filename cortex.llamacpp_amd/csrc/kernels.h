@@ -114,8 +114,8 @@ bool mmq_applicable(int type, int K, int T);
 void mmq_set_tiles(int mt);                                // tools: force 1 / 2 / 4 token tiles per wave (0 = by T)
 // pre-expanded MFMA operand planes of a weight tensor (2 B / weight, built once at load; mmq.hip)
 size_t mmq_planes_bytes(int type, int64_t n_rows, int K);   // 0 if the type has no planes form
-// Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1: an exact Q8_0-layout copy of the tensor for prompt batches (mmq_q80.hip); 0 for other types.
-// A row of the copy is [codes K][scales K/32 f16], for Q4_1 / Q5_1 followed by [mins K/32 f16]; padded to 16 bytes.
+// Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4: an exact Q8_0-layout copy of the tensor for prompt batches (mmq_q80.hip); 0 for other types.
+// A row of the copy is [codes K][scales K/32 f16], for Q4_1 / Q5_1 followed by [mins K/32 f16]; for MXFP4 [codes K][e K/32 bytes]; padded to 16 bytes.
 size_t mmq_q80_copy_bytes(int type, int64_t n_rows, int K);
 size_t mmq_q80_copy_row_bytes(int type, int K);
 hipError_t launch_expand_q80_copy(int type, const uint8_t *W, size_t row_bytes, int n_rows, int K, uint8_t *dst, hipStream_t st);
@@ -142,9 +142,18 @@ struct MMQSeg {
 };
 // prompt batches against Q8_0 weights (mmq_q80.hip): int8 MFMA per 32-block, f32 fold in block order (bit-exact with the CPU)
 bool mmq_q80_applicable(int type, int K, int T);
-// mins: W is the copy of a Q4_1 / Q5_1 tensor (a min plane behind the scales): each block adds m_w * (d_a * sum of the block's activation codes) as well
+// form Q80_FORM_MINS: W is the copy of a Q4_1 / Q5_1 tensor (a min plane behind the scales): each block adds m_w * (d_a * sum of the block's activation codes) as well
 hipError_t launch_mmq_q80(const uint8_t *W, size_t row_bytes, int n_rows, int K, int T, const ActQuant &q, float *out, int ld_out,
-                          const float *resid, hipStream_t st, bool mins = false);
+                          const float *resid, hipStream_t st, int form = 0, bool any_T = false);
+// form: the scale planes behind the codes - Q80_FORM_F16 (Q8_0 rows and the Q4_0 / Q5_0 / IQ4_NL copies), Q80_FORM_MINS (the Q4_1 / Q5_1 copies), Q80_FORM_E8 (the
+// MXFP4 copies: one E8M0 byte per block).  any_T: also batches below 32 tokens (the per-expert launches of MXFP4 expert tensors, so that they give the grouped launch's bits)
+enum : int { Q80_FORM_F16 = 0, Q80_FORM_MINS = 1, Q80_FORM_E8 = 2 };
+int mmq_q80_copy_form(int type);
+// the grouped-expert form of the kernel (MXFP4 copies): every expert's batch of ffn_gate | ffn_up (n_seg 2) or of ffn_down (n_seg 1) in one launch; W[i] is expert 0's
+// copy of tensor i, expert_stride the bytes from one expert's copy to the next, meta / rows_max as for launch_mmq_planes_moe
+bool mmq_q80_moe_ok(int type, int n_rows, int K);
+hipError_t launch_mmq_q80_moe(int type, const uint8_t *const *W, float *const *outs, int n_seg, size_t expert_stride, int n_expert, const int32_t *meta, int n_rows,
+                              int K, int rows_max, const ActQuant &q, int ld_out, hipStream_t st);
 void mmq_q80_set_tiles(int mt);      // tests: 1 / 2 / 4 token tiles per wave whatever the shape; 0: the launcher's choice
 // up to three tensors of one plane format (Q4_K / Q5_K together, or Q6_K) whose plane sets are contiguous in memory, as one
 // launch over the concatenated rows; seg_rows[i] rows go to outs[i] (leading dimension lds_out[i])

@@ -58,7 +58,7 @@ __global__ void repack_iq4xs_kernel(const uint8_t *src, uint8_t *dst, int nb, si
     else d[(size_t)sb * 128 + (i - 8)] = v;
 }
 // 32-element blocks with a 16-byte nibble field: Q4_0 / IQ4_NL (d | qs), Q5_0 (d | qh | qs), Q4_1 (d | m | qs), Q5_1 (d | m | qh | qs)
-// -> planes qs | [qh] | d | [m]
+// -> planes qs | [qh] | d | [m]; MXFP4 (e | qs) -> planes qs | e (one scale byte per block)
 __global__ void repack_nib32_kernel(const uint8_t *src, uint8_t *dst, int nblk, int K, size_t dst_row, int bsz) {
     const int row = blockIdx.y;
     const int b = blockIdx.x * 8 + (threadIdx.x >> 5), j = threadIdx.x & 31;
@@ -66,7 +66,9 @@ __global__ void repack_nib32_kernel(const uint8_t *src, uint8_t *dst, int nblk, 
     const uint8_t v = src[((size_t)row * nblk + b) * bsz + j];
     uint8_t *d = dst + (size_t)row * dst_row;
     const size_t half = (size_t)K >> 1;
-    if (bsz == 18) {
+    if (bsz == 17) {    // MXFP4: e | qs
+        if (j < 1) d[half + (size_t)b] = v; else d[(size_t)b * 16 + (j - 1)] = v;
+    } else if (bsz == 18) {
         if (j < 2) d[half + (size_t)b * 2 + j] = v; else d[(size_t)b * 16 + (j - 2)] = v;
     } else if (bsz == 22) {
         if (j < 2) d[half + (size_t)nblk * 4 + (size_t)b * 2 + j] = v;
@@ -85,7 +87,7 @@ __global__ void repack_nib32_kernel(const uint8_t *src, uint8_t *dst, int nblk, 
 }
 hipError_t launch_repack_rows(int type, const uint8_t *src, uint8_t *dst, int64_t K, int64_t n_rows, hipStream_t st) {
     const size_t drow = dev_row_bytes(type, K);
-    if (type == T_Q4_0 || type == T_Q5_0 || type == T_IQ4_NL || nib32_has_min(type)) {
+    if (type == T_Q4_0 || type == T_Q5_0 || type == T_IQ4_NL || nib32_has_min(type) || nib32_has_e8(type)) {
         const int nblk = (int)(K >> 5);
         for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
             const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);

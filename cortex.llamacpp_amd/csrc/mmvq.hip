@@ -408,6 +408,7 @@ template <> struct Item<T_IQ4_XS> {
 //   Q4_0:   sum (nib - 8) a      = dot(nib, a) - 8 sum a
 //   Q5_0:   sum (nib | b << 4 - 16) a = dot(nib + 16 b, a) - 16 sum a
 //   IQ4_NL: sum level[nib] a     (levels looked up with v_perm from the 16-byte code book)
+//   MXFP4:  sum level[nib] a     (its own sixteen levels, the same lookup; the block scale from the E8M0 byte)
 //   Q4_1 / Q5_1: sum q a with q = nib (| b << 4) unsigned, and the block's sum a kept beside it (msum): the minimum's factor
 template <int TYPE> struct ItemNib32 {
     uint4 hdr;
@@ -432,13 +433,15 @@ template <int TYPE> struct ItemNib32 {
                 if (TYPE == T_Q5_1) qh = *reinterpret_cast<const uint32_t *>(row + half + (size_t)b * 4);
                 hdr.x = *reinterpret_cast<const uint16_t *>(row + doff + (size_t)b * 2);
                 hdr.y = *reinterpret_cast<const uint16_t *>(row + doff + (size_t)(K >> 5) * 2 + (size_t)b * 2);
+            } else if (nib32_has_e8(TYPE)) {
+                hdr.x = row[half + (size_t)b];                   // the block's E8M0 byte
             } else {
                 hdr.x = *reinterpret_cast<const uint16_t *>(row + half + (size_t)b * 2);
             }
         }
     }
     __device__ __forceinline__ void prep(int lane) {
-        if (valid) { d = h2f((uint16_t)hdr.x); if (nib32_has_min(TYPE)) m = h2f((uint16_t)hdr.y); }
+        if (valid) { d = nib32_has_e8(TYPE) ? e8f(hdr.x) : h2f((uint16_t)hdr.x); if (nib32_has_min(TYPE)) m = h2f((uint16_t)hdr.y); }
     }
     static __device__ __forceinline__ uint32_t levels(uint32_t idx) {      // four IQ4_NL levels from four nibble indices (one per byte)
         const uint32_t lo = __builtin_amdgcn_perm(0xf6eaddcfu, 0xbfad9881u, idx & 0x07070707u);
@@ -456,6 +459,7 @@ template <int TYPE> struct ItemNib32 {
             for (int w = 0; w < 4; w++) {
                 uint32_t v = (qq[w] >> (4 * h)) & 0x0f0f0f0fu;
                 if (TYPE == T_IQ4_NL) { s = dot4(levels(v), aa[w], s); continue; }
+                if (TYPE == T_MXFP4) { s = dot4(mxfp4_levels4(v), aa[w], s); continue; }
                 if (nib32_has_qh(TYPE)) {
                     const uint32_t bits = (qh >> (16 * h + 4 * w)) & 0xfu;              // fifth bits of these four elements
                     v |= ((bits * 0x00204081u) & 0x01010101u) << 4;
@@ -478,7 +482,7 @@ template <int TYPE> struct ItemNib32 {
         if (nib32_has_min(TYPE))                                    // (d_x * d_y) * sumi + m * (d_y * suma): two rounded products, one add, no fma
             return __fadd_rn(__fmul_rn(__fmul_rn(d, da), (float)isum), __fmul_rn(m, __fmul_rn(da, (float)msum)));
         if (TYPE == T_Q4_0) return ((float)isum * d) * da;          // ggml_vec_dot_q4_0_q8_0: sumi * d_x * d_y, left to right
-        return (d * da) * (float)isum;                              // q5_0 / iq4_nl: (d_x * d_y) * sumi
+        return (d * da) * (float)isum;                              // q5_0 / iq4_nl / mxfp4: (d_x * d_y) * sumi
     }
 };
 template <> struct Item<T_Q4_0> : ItemNib32<T_Q4_0> {};
@@ -486,6 +490,7 @@ template <> struct Item<T_Q5_0> : ItemNib32<T_Q5_0> {};
 template <> struct Item<T_IQ4_NL> : ItemNib32<T_IQ4_NL> {};
 template <> struct Item<T_Q4_1> : ItemNib32<T_Q4_1> {};
 template <> struct Item<T_Q5_1> : ItemNib32<T_Q5_1> {};
+template <> struct Item<T_MXFP4> : ItemNib32<T_MXFP4> {};
 
 template <> struct Item<T_Q8_0> {
     uint4 hdr;
@@ -749,6 +754,7 @@ __global__ __launch_bounds__(BS) void mmvq_kernel(const MMVQArgs a) {
         case T_IQ4_NL: run_segment<T_IQ4_NL, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_Q4_1: run_segment<T_Q4_1, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_Q5_1: run_segment<T_Q5_1, NT, BS>(a, a.seg[s], smem, bis); break;
+        case T_MXFP4: run_segment<T_MXFP4, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_IQ4_XS: run_segment<T_IQ4_XS, NT, BS>(a, a.seg[s], smem, bis); break;
         default: break;
     }
@@ -883,6 +889,7 @@ __global__ __launch_bounds__(256, 2) void mmvq_tiled_kernel(const MMVQArgs a) {
         case T_IQ4_NL: run_tiled<T_IQ4_NL, NT>(a, a.seg[s], smem, bis); break;
         case T_Q4_1: run_tiled<T_Q4_1, NT>(a, a.seg[s], smem, bis); break;
         case T_Q5_1: run_tiled<T_Q5_1, NT>(a, a.seg[s], smem, bis); break;
+        case T_MXFP4: run_tiled<T_MXFP4, NT>(a, a.seg[s], smem, bis); break;
         case T_IQ4_XS: run_tiled<T_IQ4_XS, NT>(a, a.seg[s], smem, bis); break;
         default: break;
     }
@@ -1055,6 +1062,7 @@ hipError_t launch_mmvq_ints(MMVQArgs a, int32_t *isum, int32_t *msum, hipStream_
         case T_IQ4_NL: hipLaunchKernelGGL(mmvq_ints_kernel<T_IQ4_NL>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_Q4_1: hipLaunchKernelGGL(mmvq_ints_kernel<T_Q4_1>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_Q5_1: hipLaunchKernelGGL(mmvq_ints_kernel<T_Q5_1>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
+        case T_MXFP4: hipLaunchKernelGGL(mmvq_ints_kernel<T_MXFP4>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_IQ4_XS: hipLaunchKernelGGL(mmvq_ints_kernel<T_IQ4_XS>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         default: return hipErrorInvalidValue;
     }

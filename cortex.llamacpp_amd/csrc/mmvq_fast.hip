@@ -61,6 +61,9 @@ __global__ __launch_bounds__(NT) void mmvq_fast_kernel(const MMVQArgs a) {
         case T_Q5_1:
             if constexpr (FUSE != 0 || KB <= 2) run_fast<T_Q5_1, KB, NT, FUSE>(a, a.seg[s], smem, gw, nw, NoSync(), sel_j);
             break;
+        case T_MXFP4:
+            if constexpr (FUSE != 0 || KB <= 2) run_fast<T_MXFP4, KB, NT, FUSE>(a, a.seg[s], smem, gw, nw, NoSync(), sel_j);
+            break;
         default: break;
     }
 }

@@ -248,6 +248,7 @@ template <> struct Raw<T_Q8_0> {
 };
 
 // ---------------------------------------------------------------- Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 (device rows: nibbles K/2 | [qh K/32*4] | f16 scales K/32*2 | [f16 mins K/32*2])
+// and MXFP4 (nibbles K/2 | E8M0 scale bytes K/32: dh16 holds the byte, levels from mxfp4_levels4)
 // lane v of a super-block owns 32-block v as for Q8_0: its 16 nibble bytes (elements j in the low nibbles, j + 16 in the high ones: the two halves of
 // the activation slice), the fifth bits (Q5_0, Q5_1), the block scale and the block minimum (Q4_1, Q5_1: unsigned codes, the lane keeps the sum of its
 // 32 activation codes for the minimum term); dot products as the formats' scalar ggml_vec_dot_*_q8_0
@@ -266,6 +267,9 @@ template <int TYPE> struct RawNib32 {
             qh = TYPE == T_Q5_1 ? *reinterpret_cast<const uint32_t *>(row + half + blk * 4) : 0;
             dh16 = *reinterpret_cast<const uint16_t *>(row + doff + blk * 2);
             mh16 = *reinterpret_cast<const uint16_t *>(row + doff + nblk * 2 + blk * 2);
+        } else if (nib32_has_e8(TYPE)) {
+            qh = 0;
+            dh16 = row[half + blk];                              // MXFP4: the block's E8M0 byte
         } else {
             qh = 0;
             dh16 = *reinterpret_cast<const uint16_t *>(row + half + blk * 2);
@@ -285,6 +289,7 @@ template <int TYPE> struct RawNib32 {
         for (int w = 0; w < 4; w++) {
             uint32_t v0 = qq[w] & 0x0f0f0f0fu, v1 = (qq[w] >> 4) & 0x0f0f0f0fu;
             if (TYPE == T_IQ4_NL) { s = dot4(levels(v0), al[w], s); s = dot4(levels(v1), ah[w], s); continue; }
+            if (TYPE == T_MXFP4) { s = dot4(mxfp4_levels4(v0), al[w], s); s = dot4(mxfp4_levels4(v1), ah[w], s); continue; }
             if (nib32_has_qh(TYPE)) {
                 v0 |= ((((qh >> (4 * w)) & 0xfu) * 0x00204081u) & 0x01010101u) << 4;
                 v1 |= ((((qh >> (16 + 4 * w)) & 0xfu) * 0x00204081u) & 0x01010101u) << 4;
@@ -296,6 +301,7 @@ template <int TYPE> struct RawNib32 {
         if (TYPE == T_Q5_0) s -= 16 * asum;
         if (nib32_has_min(TYPE))                                                                       // (d_x * d_y) * sumi + m * (d_y * suma), no fma
             return __fadd_rn(__fmul_rn(__fmul_rn(h2f((uint16_t)dh16), A.yd), (float)s), __fmul_rn(h2f((uint16_t)mh16), __fmul_rn(A.yd, (float)asum)));
+        if (nib32_has_e8(TYPE)) return (e8f(dh16) * A.yd) * (float)s;                                  // MXFP4: (d_x * d_y) * sumi, d_x from the E8M0 byte
         return (h2f((uint16_t)dh16) * A.yd) * (float)s;                                                // (d_x * d_y) * sumi
     }
 };
@@ -304,6 +310,7 @@ template <> struct Raw<T_Q5_0> : RawNib32<T_Q5_0> {};
 template <> struct Raw<T_IQ4_NL> : RawNib32<T_IQ4_NL> {};
 template <> struct Raw<T_Q4_1> : RawNib32<T_Q4_1> {};
 template <> struct Raw<T_Q5_1> : RawNib32<T_Q5_1> {};
+template <> struct Raw<T_MXFP4> : RawNib32<T_MXFP4> {};
 
 // ---------------------------------------------------------------- IQ4_XS (device row planes: qs | scales_l | scales_h | d)
 // narrow role with its own activation slice: lane v of a super-block owns sub-block v, its 16 code bytes (elements 32 v + j in the low nibbles, 32 v + 16 + j

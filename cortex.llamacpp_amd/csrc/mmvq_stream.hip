@@ -254,7 +254,7 @@ bool mmvq_stream_applicable(const MMVQArgs &a) {
     for (int s = 0; s < (swiglu ? 2 : n); s++) {
         const MMVQSeg &g = a.seg[s];
         const int t = g.type;
-        if (t != T_Q4_K && t != T_Q5_K && t != T_Q6_K && t != T_Q8_0 && t != T_Q2_K && t != T_Q3_K && t != T_Q4_0 && t != T_Q5_0 && t != T_IQ4_NL && t != T_IQ4_XS && !nib32_has_min(t)) return false;
+        if (t != T_Q4_K && t != T_Q5_K && t != T_Q6_K && t != T_Q8_0 && t != T_Q2_K && t != T_Q3_K && t != T_Q4_0 && t != T_Q5_0 && t != T_IQ4_NL && t != T_IQ4_XS && !nib32_has_min(t) && t != T_MXFP4) return false;
         if (g.expert_sel && (s != 0 && !(swiglu && s == 1))) return false;      // experts on segment 0 (and the up tensor of its pair) only
         if ((g.row_bytes % 16) != 0 || g.row_bytes < 512) return false;         // (512: a Q2_K row of K = 2048 - TinyLlama's hidden size in the smoke model's file - is 672 B)
         if (g.row_bytes > (size_t)ST_MAX_STEP) return false;

@@ -154,6 +154,9 @@ template <bool IL, int TYPE> __device__ __forceinline__ void ring_load_nib32(Raw
         r.qh = TYPE == T_Q5_1 ? *reinterpret_cast<const uint32_t *>(RO(row_off + half + blk * 4u)) : 0u;
         r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + doff + blk * 2u));
         r.mh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + doff + nblk * 2u + blk * 2u));
+    } else if (nib32_has_e8(TYPE)) {
+        r.qh = 0;
+        r.dh16 = *reinterpret_cast<const uint8_t *>(RO(row_off + half + blk));
     } else {
         r.qh = 0;
         r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + half + blk * 2u));
@@ -164,6 +167,7 @@ template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q5_0> &r, con
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_IQ4_NL> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) { ring_load_nib32<IL, T_IQ4_NL>(r, ring, base, row_off, nb, sb, L); }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q4_1> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) { ring_load_nib32<IL, T_Q4_1>(r, ring, base, row_off, nb, sb, L); }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q5_1> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) { ring_load_nib32<IL, T_Q5_1>(r, ring, base, row_off, nb, sb, L); }
+template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_MXFP4> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) { ring_load_nib32<IL, T_MXFP4>(r, ring, base, row_off, nb, sb, L); }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_IQ4_XS> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
     r.q = lds16(RO(row_off + (unsigned)sb * 128u + (unsigned)L.v * 16u));
     r.sl = *reinterpret_cast<const uint32_t *>(RO(row_off + (unsigned)nb * 128u + (unsigned)sb * 4u));
@@ -774,6 +778,7 @@ __device__ __forceinline__ void consumer_dispatch(const StOp &a, uint8_t *smem, 
         case T_IQ4_NL: if constexpr (ENG == 0 && (FUSE == 1 || FUSE == 2)) RUN(T_IQ4_NL); break;
         case T_Q4_1: if constexpr (ENG == 0 && (FUSE == 1 || FUSE == 2)) RUN(T_Q4_1); break;
         case T_Q5_1: if constexpr (ENG == 0 && (FUSE == 1 || FUSE == 2)) RUN(T_Q5_1); break;
+        case T_MXFP4: if constexpr (ENG == 0 && (FUSE == 1 || FUSE == 2)) RUN(T_MXFP4); break;
         // IQ4_XS: every form Q4_K takes in a launch of its own (gate | up, row pairs, single rows, the head); not in the layer engine
         case T_IQ4_XS: if constexpr (ENG == 0) RUN(T_IQ4_XS); break;
         default: break;

@@ -115,6 +115,21 @@ __device__ __forceinline__ uint32_t iq4nl_levels4(uint32_t idx) {
     const uint32_t m = ((idx >> 3) & 0x01010101u) * 0xffu;
     return (hi & m) | (lo & ~m);
 }
+// MXFP4's levels (kvalues_mxfp4: the e2m1 values doubled; index bit 3 is the sign): {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12}
+__device__ __forceinline__ int mxfp4_value(int nib) {
+    const uint32_t w = nib < 8 ? (nib < 4 ? 0x03020100u : 0x0c080604u) : (nib < 12 ? 0xfdfeff00u : 0xf4f8fafcu);
+    return (int)(int8_t)((w >> (8 * (nib & 3))) & 0xffu);
+}
+// four MXFP4 levels from four nibble indices, as iq4nl_levels4: 7 VALU operations per four weights (and, two v_perm_b32, shift, and, multiply, v_bfi_b32).
+// The arithmetic decode of the e2m1 code (m < 4 ? m : (4 + 2 (m & 1)) << ((m >> 1) - 2), then the sign) has no packed-byte form here - there is no per-byte
+// variable shift, compare or negate - so on four codes in one register it needs at least a compare mask (3), the two branches (2 + 4), a select (1) and a
+// per-byte negate (xor, add with carries masked off: 4): 14 and more.  The lookup is the cheaper one and is used everywhere.
+__device__ __forceinline__ uint32_t mxfp4_levels4(uint32_t idx) {
+    const uint32_t lo = __builtin_amdgcn_perm(0x0c080604u, 0x03020100u, idx & 0x07070707u);
+    const uint32_t hi = __builtin_amdgcn_perm(0xf4f8fafcu, 0xfdfeff00u, idx & 0x07070707u);
+    const uint32_t m = ((idx >> 3) & 0x01010101u) * 0xffu;
+    return (hi & m) | (lo & ~m);
+}
 // IQ4_XS: the 6-bit scale of sub-block ib (0..7) from the super-block's scales_l word (nibble ib) and scales_h (bit pair ib), minus 32
 __device__ __forceinline__ int iq4xs_scale(uint32_t scales_l, uint32_t scales_h, int ib) {
     return (int)(((scales_l >> (4 * ib)) & 0xfu) | (((scales_h >> (2 * ib)) & 3u) << 4)) - 32;
@@ -141,6 +156,11 @@ __device__ __forceinline__ float dequant_elem(int type, const uint8_t *row, int 
             const float d = h2f(*reinterpret_cast<const uint16_t *>(row + half + (size_t)b * 2));
             if (type == T_Q4_0) return __fmul_rn((float)(nib - 8), d);
             return __fmul_rn(d, (float)iq4nl_value(nib));
+        }
+        case T_MXFP4: {   // dequantize_row_mxfp4: y = level * d, one product; d from the block's E8M0 byte
+            const int b = e >> 5, r = e & 31;
+            const int nib = (row[(size_t)b * 16 + (r & 15)] >> (4 * (r >> 4))) & 0x0f;
+            return __fmul_rn((float)mxfp4_value(nib), e8f(row[((size_t)K >> 1) + (size_t)b]));
         }
         case T_Q4_1: case T_Q5_1: {   // the same nibble field with unsigned codes and a per-block minimum: y = q d + m, the product rounded before the add
             const int b = e >> 5, r = e & 31;

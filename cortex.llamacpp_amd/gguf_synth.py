@@ -23,9 +23,10 @@ Q5_0, IQ4_NL = 6, 20
 Q4_1, Q5_1 = 3, 7
 IQ4_XS = 23
 BF16 = 30
-TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K", Q2_K: "q2_K", Q3_K: "q3_K", Q5_0: "q5_0", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", BF16: "bf16", Q4_1: "q4_1", Q5_1: "q5_1"}
-BLOCK_ELEMS = {F32: 1, F16: 1, Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q2_K: 256, Q3_K: 256, Q5_0: 32, IQ4_NL: 32, IQ4_XS: 256, BF16: 1, Q4_1: 32, Q5_1: 32}
-BLOCK_BYTES = {F32: 4, F16: 2, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q2_K: 84, Q3_K: 110, Q5_0: 22, IQ4_NL: 18, IQ4_XS: 136, BF16: 2, Q4_1: 20, Q5_1: 24}
+MXFP4 = 39
+TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K", Q2_K: "q2_K", Q3_K: "q3_K", Q5_0: "q5_0", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", BF16: "bf16", Q4_1: "q4_1", Q5_1: "q5_1", MXFP4: "mxfp4"}
+BLOCK_ELEMS = {F32: 1, F16: 1, Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q2_K: 256, Q3_K: 256, Q5_0: 32, IQ4_NL: 32, IQ4_XS: 256, BF16: 1, Q4_1: 32, Q5_1: 32, MXFP4: 32}
+BLOCK_BYTES = {F32: 4, F16: 2, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q2_K: 84, Q3_K: 110, Q5_0: 22, IQ4_NL: 18, IQ4_XS: 136, BF16: 2, Q4_1: 20, Q5_1: 24, MXFP4: 17}
 
 DT_Q4_0 = np.dtype([("d", "<f2"), ("qs", "u1", 16)])
 DT_Q8_0 = np.dtype([("d", "<f2"), ("qs", "i1", 32)])
@@ -38,9 +39,12 @@ DT_Q5_0 = np.dtype([("d", "<f2"), ("qh", "u1", 4), ("qs", "u1", 16)])
 # Q4_1 / Q5_1: unsigned codes q (0..15; 0..31 with the fifth bit of element j in bit j of qh) and a per-block minimum, weight = q * d + m
 DT_Q4_1 = np.dtype([("d", "<f2"), ("m", "<f2"), ("qs", "u1", 16)])
 DT_Q5_1 = np.dtype([("d", "<f2"), ("m", "<f2"), ("qh", "u1", 4), ("qs", "u1", 16)])
+# MXFP4: one E8M0 scale byte e and sixteen level indices per half block, weight = KVALUES_MXFP4[nibble] * d with d = half of 2^(e - 127) (mxfp4_scale)
+DT_MXFP4 = np.dtype([("e", "u1"), ("qs", "u1", 16)])
+KVALUES_MXFP4 = np.array([0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12], np.int8)      # the e2m1 values doubled
 # IQ4_XS: 6-bit sub-block scales ls (low nibbles in scales_l, high bit pairs in scales_h), weight = d * (ls - 32) * kvalues_iq4nl[nibble]
 DT_IQ4_XS = np.dtype([("d", "<f2"), ("scales_h", "<u2"), ("scales_l", "u1", 4), ("qs", "u1", 128)])
-BLOCK_DTYPE = {Q4_0: DT_Q4_0, Q8_0: DT_Q8_0, Q4_K: DT_Q4_K, Q5_K: DT_Q5_K, Q6_K: DT_Q6_K, Q2_K: DT_Q2_K, Q3_K: DT_Q3_K, Q5_0: DT_Q5_0, IQ4_NL: DT_Q4_0, IQ4_XS: DT_IQ4_XS, Q4_1: DT_Q4_1, Q5_1: DT_Q5_1}
+BLOCK_DTYPE = {Q4_0: DT_Q4_0, Q8_0: DT_Q8_0, Q4_K: DT_Q4_K, Q5_K: DT_Q5_K, Q6_K: DT_Q6_K, Q2_K: DT_Q2_K, Q3_K: DT_Q3_K, Q5_0: DT_Q5_0, IQ4_NL: DT_Q4_0, IQ4_XS: DT_IQ4_XS, Q4_1: DT_Q4_1, Q5_1: DT_Q5_1, MXFP4: DT_MXFP4}
 for _t, _dt in BLOCK_DTYPE.items():
     assert _dt.itemsize == BLOCK_BYTES[_t], (_t, _dt.itemsize)
 
@@ -48,7 +52,8 @@ for _t, _dt in BLOCK_DTYPE.items():
 # (Q2_K: w / d = sc * q - r * m with sc, m uniform 0..15, q uniform 0..3, r = 1.5: variance 144.7 + 2.25 * 21.25; Q3_K: (sc - 32) * q, sc 0..63, q -4..3)
 _UNIT_STD = {Q4_0: 4.6, Q8_0: 73.9, Q4_K: 258.0, Q5_K: 527.0, Q6_K: 1367.0, Q2_K: 13.9, Q3_K: 43.3, Q5_0: 9.23, IQ4_NL: 67.2,
              IQ4_XS: 1246.3,   # (Q5_0: codes 0..31 minus 16; IQ4_NL: the sixteen code-book levels; IQ4_XS: (ls - 32) * level, ls 0..63: sqrt(341.5 * 4548))
-             Q4_1: 4.61, Q5_1: 9.23}   # (codes uniform 0..15 / 0..31 around the minimum below: sqrt((16^2 - 1) / 12), sqrt((32^2 - 1) / 12))
+             Q4_1: 4.61, Q5_1: 9.23,   # (codes uniform 0..15 / 0..31 around the minimum below: sqrt((16^2 - 1) / 12), sqrt((32^2 - 1) / 12))
+             MXFP4: 5.85}              # (the sixteen levels, uniform: sqrt(2 * 274 / 16))
 # dmin/d ratio that centres the weights of a random block on zero
 _DMIN_RATIO = {Q4_K: 7.5, Q5_K: 15.5, Q2_K: 1.5}
 # m/d ratio doing the same for the per-block minimum of Q4_1 / Q5_1 (weight = q d + m: minus the mean code)
@@ -79,6 +84,12 @@ def random_blocks(rng: np.random.Generator, t: int, n_elems: int, std: float) ->
     nb = n_elems // BLOCK_ELEMS[t]
     raw = rng.integers(0, 256, size=nb * BLOCK_BYTES[t], dtype=np.uint8)
     blk = raw.view(BLOCK_DTYPE[t])
+    if t == MXFP4:
+        # power-of-two scales: e in a band of three around the exponent whose scale gives the requested std (d = 2^(e - 128) = std / 5.85: e = 127 - 10 .. 127 - 6
+        # for the model tensors' std of 0.01 .. 0.1)
+        c = int(np.clip(np.rint(np.log2(std / _UNIT_STD[t])) + 128, 2, 253))
+        blk["e"] = rng.integers(c - 1, c + 2, size=nb).astype(np.uint8)
+        return raw
     d = (rng.uniform(0.5, 1.5, size=nb) * (std / _UNIT_STD[t])).astype(np.float32)
     blk["d"] = d.astype("<f2")
     if t in _DMIN_RATIO:
@@ -106,6 +117,30 @@ def quantize_min32(t: int, x: np.ndarray) -> np.ndarray:
     if t == Q5_1:
         qh = (((q >> 4) & 1) << np.arange(32, dtype=np.uint32)).sum(axis=1, dtype=np.uint32)
         blk["qh"] = qh.astype("<u4").view(np.uint8).reshape(-1, 4)
+    return blk.view(np.uint8).reshape(-1)
+
+
+def mxfp4_scale(e: np.ndarray) -> np.ndarray:
+    """The f32 block scale of E8M0 byte e: half of 2^(e - 127), as a bit pattern (0x00200000 << e below 2, else (e - 1) << 23; e = 255 gives 2^127)."""
+    e = np.asarray(e).astype(np.uint32)
+    return np.where(e < 2, np.uint32(0x00200000) << e, (np.maximum(e, 1) - np.uint32(1)) << np.uint32(23)).astype("<u4").view(np.float32)
+
+
+def quantize_mxfp4(x: np.ndarray) -> np.ndarray:
+    """x (f32, a multiple of 32 values) as MXFP4 blocks (raw bytes) by ggml's reference quantiser quantize_row_mxfp4_ref: per block amax = max |x|,
+    e = amax > 0 ? (u8)(floor(log2f(amax)) - 2 + 127) : 0, d = mxfp4_scale(e); each weight takes the level index with the smallest |level * d - x|, the lowest
+    index on a tie (strict < scanning 0..15).  Element j < 16 goes to the low nibble of qs[j], element j + 16 to the high one."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 32)
+    amax = np.abs(x).max(axis=1)
+    with np.errstate(divide="ignore"):
+        lg = np.floor(np.log2(np.where(amax > 0, amax, np.float32(1.0)).astype(np.float32))).astype(np.float32)
+    e = np.where(amax > 0, (lg - np.float32(2) + np.float32(127)).astype(np.int32) & 0xff, 0).astype(np.uint8)
+    d = mxfp4_scale(e)
+    err = np.abs((KVALUES_MXFP4.astype(np.float32)[None, None, :] * d[:, None, None]).astype(np.float32) - x[:, :, None])      # [block][element][level]
+    q = np.argmin(err, axis=2).astype(np.uint8)               # (argmin returns the first minimum: the lowest index on a tie)
+    blk = np.zeros(x.shape[0], DT_MXFP4)
+    blk["e"] = e
+    blk["qs"] = (q[:, :16] & 15) | ((q[:, 16:] & 15) << 4)
     return blk.view(np.uint8).reshape(-1)
 
 
@@ -306,7 +341,7 @@ CONFIGS = {
                                          n_ff_exp=1536),
 }
 
-FTYPE_ID = {"f16": 1, "bf16": 32, "q4_0": 2, "q4_1": 3, "q5_0": 8, "q5_1": 9, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18}
+FTYPE_ID = {"f16": 1, "bf16": 32, "q4_0": 2, "q4_1": 3, "q5_0": 8, "q5_1": 9, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18, "mxfp4": 38, "mxfp4_moe": 38}
 
 
 def use_more_bits(i: int, n: int) -> bool:
@@ -330,6 +365,14 @@ def tensor_type(cfg: LlamaConfig, ftype: str, kind: str, il: int) -> int:
         return BF16
     if ftype == "q8_0":
         return Q8_0
+    if ftype == "mxfp4_moe":
+        # LLAMA_FTYPE_MOSTLY_MXFP4_MOE: the tensors with a third dimension (ffn_gate_exps, ffn_up_exps, ffn_down_exps) MXFP4, every other 2-D weight Q8_0,
+        # token_embd and output included (a dense config has no expert tensors: all Q8_0)
+        return MXFP4 if cfg.n_expert and kind in ("ffn_gate", "ffn_up", "ffn_down") else Q8_0
+    if ftype == "mxfp4":
+        # every 2-D weight MXFP4 with an F16 head (what `--tensor-type` overrides give; the dense decoders' test file): the id is MXFP4_MOE's, the one ftype
+        # upstream has for the type
+        return F16 if kind == "output" else MXFP4
     if ftype in ("q2_k", "q3_k_m"):
         # llama-quantize's rules for LLAMA_FTYPE_MOSTLY_Q2_K / Q3_K_M on the llama architecture (the reference's e2e smoke model is a TinyLlama Q2_K
         # file, /root/reference/Makefile:5): output Q6_K; Q2_K: attn_v Q4_K with a query / kv head ratio >= 4 (else Q3_K), ffn_down and attn_output

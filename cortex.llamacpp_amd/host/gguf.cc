@@ -63,6 +63,7 @@ size_t ggml_type_row_bytes(int type, int64_t n) {
         case 20: be = 32; bb = 18; break;   // iq4_nl
         case 23: be = 256; bb = 136; break; // iq4_xs
         case 30: be = 1; bb = 2; break;     // bf16
+        case 39: be = 32; bb = 17; break;   // mxfp4
         case 12: be = 256; bb = 144; break; // q4_K
         case 13: be = 256; bb = 176; break; // q5_K
         case 14: be = 256; bb = 210; break; // q6_K
@@ -77,7 +78,7 @@ const char *ggml_type_name(int type) {
         case 0: return "f32"; case 1: return "f16"; case 2: return "q4_0"; case 3: return "q4_1";
         case 6: return "q5_0"; case 7: return "q5_1"; case 8: return "q8_0"; case 10: return "q2_K";
         case 11: return "q3_K"; case 12: return "q4_K"; case 13: return "q5_K"; case 14: return "q6_K";
-        case 15: return "q8_K"; case 23: return "iq4_xs"; case 30: return "bf16";
+        case 15: return "q8_K"; case 23: return "iq4_xs"; case 30: return "bf16"; case 39: return "mxfp4";
     }
     return "unknown";
 }

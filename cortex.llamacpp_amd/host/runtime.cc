@@ -194,6 +194,13 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             fail = true;
             return;
         }
+        if (ti->type == T_MXFP4) {
+            // mxfp4 is a type of the 2-D and expert weights of the decoder graphs: the kernels read norm and bias vectors as f32, the encoder graph's launches
+            // and the row split's column cuts and exchange steps are untested with it
+            const char *why = ti->n_dims == 1 ? "norm and bias vectors must be f32" : hp.encoder ? "the encoder graph is not supported with mxfp4 tensors" :
+                              P > 1 ? "a row split (split_mode \"row\" / tp_size > 1) of mxfp4 tensors is not supported: load the file on one device" : nullptr;
+            if (why) { err = "tensor " + name + " has type mxfp4: " + why; fail = true; return; }
+        }
         if (ti->type == T_BF16) {
             // bf16 is a type of the dense 2-D weights (and of token_embd / output): the norm and bias vectors are read as f32 by the kernels, the routed experts,
             // the encoder graph and the row split's column cuts have no bf16 kernels.  Rows are loaded as 16-byte pieces: 8 weights.
@@ -445,7 +452,7 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             for (DevTensor *d : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down, &L.gate_exps, &L.up_exps, &L.down_exps})
                 if (d->valid() && (mmq_planes_bytes(d->type, d->N, (int)d->K) || mmq_q80_copy_bytes(d->type, d->N, (int)d->K))) want.push_back(d);
         // (an *_exps tensor holds one plane set per expert, back to back: a prompt batch runs one contraction per expert)
-        // (K-quants: the two int8 MFMA planes; Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1: an exact Q8_0-layout copy for the Q8_0 prompt kernel, with a min plane for the last two)
+        // (K-quants: the two int8 MFMA planes; Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4: an exact Q8_0-layout copy for the Q8_0 prompt kernel, with a min plane for Q4_1 / Q5_1 and E8M0 scale bytes for MXFP4)
         auto planes_of = [](const DevTensor *d) {
             const size_t b = mmq_planes_bytes(d->type, d->N, (int)d->K);
             return ((b ? b : mmq_q80_copy_bytes(d->type, d->N, (int)d->K)) + 255) & ~(size_t)255;
@@ -1005,7 +1012,7 @@ hipError_t Context::ensure_prep(const ActQuant &aq, int K, int T) {
 // Q2_K / Q3_K / IQ4_XS tensors reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
 // (the types with an exact Q8_0-layout copy: act_is_q80 without Q8_0 itself, which needs none - so the chain stays spelled out)
 static bool q80_copy(const DevTensor &w, int K, int T) {
-    return (w.type == T_Q4_0 || w.type == T_Q5_0 || w.type == T_IQ4_NL || nib32_has_min(w.type)) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
+    return (w.type == T_Q4_0 || w.type == T_Q5_0 || w.type == T_IQ4_NL || nib32_has_min(w.type) || nib32_has_e8(w.type)) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
 }
 static bool planes_small(const DevTensor &w, int K, int T) { return type_is_planes_only(w.type) && w.planes && T >= 32 && (K % 256) == 0; }
 
@@ -1025,8 +1032,8 @@ hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *
             if (w.planes) return launch_mmq_planes(w.type, w.planes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_ws_);
             return launch_mmq(w.type, w.data, w.row_bytes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
         }
-        if (q80_copy(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs0)      // prompt processing of Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 tensors: their exact Q8_0-layout copy
-            return launch_mmq_q80(w.planes, mmq_q80_copy_row_bytes(w.type, K), (int)w.N, K, T, aq, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, nib32_has_min(w.type));
+        if (q80_copy(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs0)      // prompt processing of Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4 tensors: their exact Q8_0-layout copy
+            return launch_mmq_q80(w.planes, mmq_q80_copy_row_bytes(w.type, K), (int)w.N, K, T, aq, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_q80_copy_form(w.type));
         if (planes_small(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs) {
             // prompt processing of Q2_K / Q3_K / IQ4_XS tensors: their plane sets (expanded at load in the Q4_K / Q6_K plane formats, mmq.hip) on the same kernels
             if (w.type == T_Q2_K && !bh_over_) HIP_TRY(ensure_prep(aq, K, T));
@@ -1140,6 +1147,9 @@ hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs,
 // batched contraction per expert); fewer tokens loop over (token, expert) with the mat-vec.  Tests move it to compare both.
 static int g_moe_group_min = getenv("MI355_MOE_GROUP_MIN") ? atoi(getenv("MI355_MOE_GROUP_MIN")) : 8;
 void set_moe_group_min(int t) { g_moe_group_min = t < 1 ? 1 : t; }
+// MXFP4 expert tensors, prompt batches: every expert's batch in one launch (false: a launch per expert, the same bits; the variable is for the benchmark's A/B)
+static bool g_moe_q80_grouped = !(getenv("MI355_MOE_Q80_GROUPED") && getenv("MI355_MOE_Q80_GROUPED")[0] == '0');
+void set_moe_q80_grouped(bool on) { g_moe_q80_grouped = on; }
 static int g_decode_mega = -1;           // -1: take the environment
 static bool g_store_fuse = true;
 void set_attn_store_fuse(bool on) { g_store_fuse = on; }
@@ -1744,9 +1754,27 @@ hipError_t Context::moe_grouped_one_launch(int il, int T) {
     return launch_moe_scatter_combine(x_, y_g_, moe_w_, moe_slot_, T, E, KU, stream_);
 }
 
+// ... the same for expert tensors with Q8_0-layout copies (MXFP4): gather, gate | up in one launch of two segments, SwiGLU + Q8_0 quantisation, down,
+// scatter-combine - five launches a layer whatever the number of experts, no host synchronisation
+hipError_t Context::moe_grouped_q80(int il, int T) {
+    const HParams &hp = model->hp;
+    const LayerWeights &L = model->layers[(size_t)il];
+    const int E = hp.n_embd, FF = hp.n_ff, KU = hp.n_expert_used, NE = hp.n_expert, GR = T * KU;
+    HIP_TRY(launch_moe_gather_act(aq_e_, moe_tok_, GR, E, aq_eg_, stream_));
+    prep_owner_ = nullptr;
+    const uint8_t *w_gu[2] = {L.gate_exps.planes, L.up_exps.planes}, *w_d[1] = {L.down_exps.planes};
+    float *o_gu[2] = {ffn_g_, ffn_ug_}, *o_d[1] = {y_g_};
+    HIP_TRY(launch_mmq_q80_moe(L.gate_exps.type, w_gu, o_gu, 2, L.gate_exps.planes_bytes / (size_t)L.gate_exps.n_expert, NE, moe_meta_, (int)L.gate_exps.N, E, GR, aq_eg_, FF, stream_));
+    HIP_TRY(launch_swiglu_quant(ffn_g_, ffn_ug_, FF, GR, aq_ffg_, false, true, stream_, nullptr, nullptr));
+    HIP_TRY(launch_mmq_q80_moe(L.down_exps.type, w_d, o_d, 1, L.down_exps.planes_bytes / (size_t)L.down_exps.n_expert, NE, moe_meta_, (int)L.down_exps.N, FF, GR, aq_ffg_, E, stream_));
+    return launch_moe_scatter_combine(x_, y_g_, moe_w_, moe_slot_, T, E, KU, stream_);
+}
+
 // ... grouped, one batched contraction per expert and projection through linear(): the batch sizes come back to the host first (prompt batches only: never
 // inside a graph)
-hipError_t Context::moe_grouped_per_expert(int il, int T) {
+// q80_any: the layer qualifies for moe_grouped_q80 and the "moe_q80_grouped" switch is off - every expert's batch, also one below 32 tokens, then runs the Q8_0
+// prompt kernel on the expert's copy, so that the two settings of the switch give the same bits
+hipError_t Context::moe_grouped_per_expert(int il, int T, bool q80_any) {
     const HParams &hp = model->hp;
     const LayerWeights &L = model->layers[(size_t)il];
     const int E = hp.n_embd, FF = hp.n_ff, KU = hp.n_expert_used, NE = hp.n_expert, GR = T * KU;
@@ -1767,6 +1795,10 @@ hipError_t Context::moe_grouped_per_expert(int il, int T) {
         if (q.qs0) { v.qs0 = q.qs0 + (size_t)r0 * K; v.d0 = q.d0 + (size_t)r0 * (K / 32); }
         return v;
     };
+    auto copy_batch = [&](const DevTensor &w, int e, const ActQuant &q, int K, int n_e, float *out, int ld_out) {
+        return launch_mmq_q80(w.planes + (size_t)e * (w.planes_bytes / (size_t)w.n_expert), mmq_q80_copy_row_bytes(w.type, K), (int)w.N, K, n_e, q, out, ld_out, nullptr, stream_,
+                              mmq_q80_copy_form(w.type), true);
+    };
     // the block-sum planes of ALL grouped rows in one launch (they were one launch per expert and projection: 16 a layer);
     // an expert's batch takes its slice of them
     const bool pl_gu = !act_is_q80(L.gate_exps.type) || !act_is_q80(L.up_exps.type), pl_d = !act_is_q80(L.down_exps.type);
@@ -1776,6 +1808,11 @@ hipError_t Context::moe_grouped_per_expert(int il, int T) {
         const int n_e = h_moe_meta_[e], r0 = h_moe_meta_[NE + e];
         if (n_e <= 0) continue;
         if (pl_gu) { bh_over_ = mmq_bh_ + (size_t)r0 * (E >> 4); bl_over_ = mmq_bl_ + (size_t)r0 * (E >> 4); }
+        if (q80_any) {
+            e_exp = copy_batch(L.gate_exps, e, rows(aq_eg_, r0, E), E, n_e, ffn_g_ + (size_t)r0 * FF, FF);
+            if (e_exp == hipSuccess) e_exp = copy_batch(L.up_exps, e, rows(aq_eg_, r0, E), E, n_e, ffn_ug_ + (size_t)r0 * FF, FF);
+            continue;
+        }
         e_exp = linear(view(L.gate_exps, e), rows(aq_eg_, r0, E), nullptr, E, n_e, ffn_g_ + (size_t)r0 * FF, FF, nullptr, EPI_STORE);
         if (e_exp == hipSuccess) e_exp = linear(view(L.up_exps, e), rows(aq_eg_, r0, E), nullptr, E, n_e, ffn_ug_ + (size_t)r0 * FF, FF, nullptr, EPI_STORE);
     }
@@ -1788,6 +1825,7 @@ hipError_t Context::moe_grouped_per_expert(int il, int T) {
         const int n_e = h_moe_meta_[e], r0 = h_moe_meta_[NE + e];
         if (n_e <= 0) continue;
         if (pl_d) { bh_over_ = mmq_bh_ + (size_t)r0 * (FF >> 4); bl_over_ = mmq_bl_ + (size_t)r0 * (FF >> 4); }
+        if (q80_any) { e_exp = copy_batch(L.down_exps, e, rows(aq_ffg_, r0, FF), FF, n_e, y_g_ + (size_t)r0 * E, E); continue; }
         e_exp = linear(view(L.down_exps, e), rows(aq_ffg_, r0, FF), nullptr, FF, n_e, y_g_ + (size_t)r0 * E, E, nullptr, EPI_STORE);
     }
     bh_over_ = bl_over_ = nullptr;
@@ -1862,7 +1900,12 @@ hipError_t Context::ffn_moe(int il, const Step &st) {
         const bool one_launch = T >= 32 && L.gate_exps.planes && L.up_exps.planes && L.down_exps.planes && L.gate_exps.type == L.up_exps.type &&
                                 L.gate_exps.N == L.up_exps.N && mmq_planes_moe_ok(L.gate_exps.type, (int)L.gate_exps.N, E) &&
                                 mmq_planes_moe_ok(L.down_exps.type, (int)L.down_exps.N, FF) && (L.gate_exps.N % 64) == 0;
-        HIP_TRY(one_launch ? moe_grouped_one_launch(il, T) : moe_grouped_per_expert(il, T));
+        // MXFP4 expert tensors (Q8_0-layout copies, Q8_0 activations): the grouped-expert form of the Q8_0 prompt kernel
+        const bool q80_ok = T >= 32 && L.gate_exps.planes && L.up_exps.planes && L.down_exps.planes && L.gate_exps.type == T_MXFP4 && L.up_exps.type == T_MXFP4 &&
+                            L.down_exps.type == T_MXFP4 && L.gate_exps.N == L.up_exps.N && mmq_q80_moe_ok(T_MXFP4, (int)L.gate_exps.N, E) &&
+                            mmq_q80_moe_ok(T_MXFP4, (int)L.down_exps.N, FF) && aq_eg_.qs0 && aq_ffg_.qs0;
+        if (q80_ok && g_moe_q80_grouped) HIP_TRY(moe_grouped_q80(il, T));
+        else HIP_TRY(one_launch ? moe_grouped_one_launch(il, T) : moe_grouped_per_expert(il, T, q80_ok));
     } else {
         HIP_TRY(moe_selected(il, T));
     }

@@ -106,6 +106,7 @@ struct Fuse {   // fused activation prologue of the single-token mat-vec (mmvq.h
     float *out_host = nullptr;   // the launch also stores its results here (pinned host memory; the output head of a single-token step) - weight stream only
 };
 
+void set_moe_q80_grouped(bool on);  // tests / tools: MXFP4 expert tensors, prompt batches: one launch for all experts (default) or one per expert - the same bits
 void set_moe_group_min(int tokens);   // tests: batch size from which a mixture-of-experts feed-forward is grouped by expert
 void set_attn_store_fuse(bool on);   // tests: 0 = batched steps store K / V in their own launch before the attention
 void set_rope_fast(bool on);         // tests: 0 = prompt batches rotate q / store K, V with the one-workgroup-per-token kernel
@@ -204,7 +205,8 @@ class Context {
     hipError_t ffn_moe(int il, const Step &st);
     bool moe_selected_desc(int il, MMVQArgs &a, MMVQArgs &d) const;
     hipError_t moe_grouped_one_launch(int il, int T);
-    hipError_t moe_grouped_per_expert(int il, int T);
+    hipError_t moe_grouped_per_expert(int il, int T, bool q80_any = false);
+    hipError_t moe_grouped_q80(int il, int T);
     hipError_t moe_selected(int il, int T);
     hipError_t ffn_dense_gate_up(int il, const Step &st, bool &quantised);
     hipError_t quantise_for_down(int il, int T, bool combined, bool planes_any_T);

@@ -339,7 +339,7 @@ std::unique_ptr<IBackend> make_split_backend(const Json &body, BackendInfo &info
             return nullptr;
         }
         for (const GGUFTensorInfo &t : f.tensors)
-            if (t.type == 3 || t.type == 7) { err = std::string("split_mode row: row split of ") + ggml_type_name(t.type) + " tensors is not supported (tensor " + t.name + "; load the file on one device)"; return nullptr; }
+            if (t.type == 3 || t.type == 7 || t.type == 39) { err = std::string("split_mode row: row split of ") + ggml_type_name(t.type) + " tensors is not supported (tensor " + t.name + "; load the file on one device)"; return nullptr; }
             else if (t.type == 23) { err = "split_mode row: row split of iq4_xs tensors is not supported (tensor " + t.name + "; load the file on one device)"; return nullptr; }
     }
     const int main_gpu = body.value<int>("main_gpu", 0);

@@ -207,11 +207,13 @@ MI355_API int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n_
  * 256-blocks for the quantiser and the planes compacted; a model's hidden sizes are multiples of 256); one token with K % 256 == 0 is quantised in the mat-vec's
  * prologue, the form the weight stream takes these types in; isum is the block's sum of q * a (q the unsigned code), msum the block's
  * sum of a - the block contributes (d * d8) * isum + m * (d8 * msum).  With "mmq_planes" 1 and T >= 32 the tensor's Q8_0-layout copy runs on the
- * matrix cores, in the form "mmq_q80_tiles" forces (1 | 2 | 4 token tiles per wave; 0: the launcher's choice). */
+ * matrix cores, in the form "mmq_q80_tiles" forces (1 | 2 | 4 token tiles per wave; 0: the launcher's choice).
+ * MXFP4 (type 39, Q8_0 activations): as Q4_1 / Q5_1 for K, the one-token form and the copy; isum is the block's sum of level * a, msum is 0 - the block
+ * contributes (d * d8) * isum with d from its E8M0 byte. */
 MI355_API int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T,
                                float *y, int32_t *isum, int32_t *msum);
 /* Test hook: y = resid + W . x (resid, y: [T][N]) on the launches that take a residual in their epilogue through this entry point: the Q8_0 prompt kernel
- * (Q8_0 tensors, and the Q8_0-layout copies of Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 tensors with "mmq_planes" 1), T >= 32; MI355_ERR_ARG otherwise. */
+ * (Q8_0 tensors, and the Q8_0-layout copies of Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4 tensors with "mmq_planes" 1), T >= 32; MI355_ERR_ARG otherwise. */
 MI355_API int mi355_op_mul_mat_add(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y);
 /* ggml's f32 -> bf16 rounding as the bf16 kernels' activation pass does it (nearest, ties to even; NaN quieted; subnormals kept); n % 8 == 0 */
 MI355_API int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out);
@@ -226,7 +228,7 @@ MI355_API int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const i
 /* ffn_gate and ffn_up (one K-quant type or IQ4_XS, N rows each, N % 32 == 0) against the same T activation rows with SwiGLU in the
  * epilogue, as the prompt path launches them (mmq_planes2_swiglu_kernel): y[t][n] = silu(Wg[n] . x[t]) * (Wu[n] . x[t]).
  * Shapes too small for that launch are refused unless the debug option "mmq_tiles" = 4 forces the kernel.
- * Q4_1 / Q5_1 (any N, K % 256 == 0) run as a layer of such a file does: T >= 32 with "mmq_planes" 1 through the two Q8_0-layout copies and the SwiGLU
+ * Q4_1 / Q5_1 / MXFP4 (any N, K % 256 == 0) run as a layer of such a file does: T >= 32 with "mmq_planes" 1 through the two Q8_0-layout copies and the SwiGLU
  * pass, else the mat-vec with SwiGLU in its epilogue. */
 MI355_API int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y);
 MI355_API int mi355_op_rms_norm_mul(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y);
@@ -332,7 +334,9 @@ MI355_API void mi355_engine_set_log_callback(mi355_engine *e, mi355_log_callback
  * K-quant model with Llama-3-8B's layer geometry run every layer in one launch; 0, the default: one launch per operation
  * — both produce the same bits; the single launch measured slower); "moe_group_min" (batches of at least
  * this many tokens run a mixture-of-experts feed-forward grouped by expert, default 8; smaller ones loop over (token,
- * expert) with the mat-vec); "tp_null_group" (measurement aid: the process becomes rank 0 of a row-split group of `value`
+ * expert) with the mat-vec); "moe_q80_grouped" (1, the default: a prompt batch of a file with MXFP4 expert tensors runs every
+ * expert's batch of a projection in one launch; 0: one launch per expert after a host synchronisation - the same bits);
+ * "tp_null_group" (measurement aid: the process becomes rank 0 of a row-split group of `value`
  * ranks whose other members do not exist — every exchange is a device copy of this rank's own part, so a model loaded with
  * tp_rank 0 / tp_size value times ONE rank's compute without communication; its outputs are not the model's).
  * Returns MI355_OK or MI355_ERR_ARG for an unknown name. */
