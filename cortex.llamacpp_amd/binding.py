@@ -117,6 +117,8 @@ SYMBOLS = {
                                      _vp, _vp, _vp, _vp]),
     "mi355_op_attn_decode_neox": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _f32, _i32,
                                             _vp, _vp, _vp]),
+    "mi355_op_kv_store": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp]),
+    "mi355_op_k_shift": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _f32, _f32, _vp, _f32, _f32, _f32, _f32, _vp]),
     "mi355_bench_hbm_read": (C.c_double, [_sz, C.c_int]),
     "mi355_profile_last_decode": (_i32, [_vp, C.POINTER(_cp), C.POINTER(_f32), _i32]),
     "mi355_profile_enable": (None, [_vp, _i32]),
@@ -390,6 +392,35 @@ class Backend:
                                                      None if qn is None else _ptr(qn), None if kn is None else _ptr(kn), float(eps), int(mode),
                                                      _ptr(att), _ptr(kr), _ptr(vr)), "op_attn_decode_neox")
         return att, kr, vr
+
+    def kv_store(self, form: int, q, k, v, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows, type_v: int, v_rows, tok_pos, tok_cell, rope_base: float,
+                 n_rot=None, neox: bool = False, freq_scale: float = 1.0, freq_factors=None, q_norm=None, k_norm=None, eps: float = 0.0):
+        """The K / V cache write of a batch on its own (mi355_op_kv_store; form 0 / 1: the generic kernel without / with the cos / sin table, 2: the vectorised
+        prompt store, 3: the small-batch decode store, q may be None).  k_rows / v_rows: the whole cache before the launch, [n_cells][row bytes]; returns
+        (q rotated [T][H * D] or None, the whole K cache after the launch, the whole V cache).  The inputs are not modified."""
+        tok_pos = np.ascontiguousarray(tok_pos, np.int32).reshape(-1)
+        tok_cell = np.ascontiguousarray(tok_cell, np.int32).reshape(-1)
+        T = tok_pos.size
+        qo = None if q is None else np.array(q, np.float32, copy=True).reshape(T, n_head * hd)
+        k = np.ascontiguousarray(k, np.float32).reshape(T, n_head_kv * hd); v = np.ascontiguousarray(v, np.float32).reshape(T, n_head_kv * hd)
+        kc = np.array(k_rows, order="C", copy=True).view(np.uint8); vc = np.array(v_rows, order="C", copy=True).view(np.uint8)
+        assert tok_cell.size == T and kc.ndim == 2 and vc.ndim == 2 and kc.shape[0] == vc.shape[0]
+        ff, qn, kn = (None if a is None else np.ascontiguousarray(a, np.float32) for a in (freq_factors, q_norm, k_norm))
+        self._chk(self.lib.mi355_op_kv_store(int(form), _ptr(qo), _ptr(k), _ptr(v), T, n_head, n_head_kv, hd, int(n_rot or hd), int(bool(neox)), type_k, type_v,
+                                             kc.shape[0], _ptr(tok_pos), _ptr(tok_cell), float(rope_base), float(freq_scale), _ptr(ff), _ptr(qn), _ptr(kn),
+                                             float(eps), _ptr(kc), _ptr(vc)), "op_kv_store")
+        return qo, kc, vc
+
+    def k_shift(self, type_k: int, n_head_kv: int, hd: int, k_rows, delta, rope_base: float, n_rot=None, neox: bool = False, freq_scale: float = 1.0,
+                freq_factors=None, ext_factor: float = 0.0, attn_factor: float = 1.0, corr_lo: float = 0.0, corr_hi: float = 0.0) -> np.ndarray:
+        """One K-shift launch over a whole K cache (mi355_op_k_shift): k_rows [n_cells][row bytes], delta [n_cells]; returns the cache after the launch."""
+        delta = np.ascontiguousarray(delta, np.int32).reshape(-1)
+        kc = np.array(k_rows, order="C", copy=True).view(np.uint8)
+        assert kc.ndim == 2 and kc.shape[0] == delta.size
+        ff = None if freq_factors is None else np.ascontiguousarray(freq_factors, np.float32)
+        self._chk(self.lib.mi355_op_k_shift(type_k, n_head_kv, hd, int(n_rot or hd), int(bool(neox)), delta.size, _ptr(delta), float(rope_base), float(freq_scale),
+                                            _ptr(ff), float(ext_factor), float(attn_factor), float(corr_lo), float(corr_hi), _ptr(kc)), "op_k_shift")
+        return kc
 
     def hbm_read_gbps(self, nbytes: int = 1 << 30, iters: int = 10) -> float:
         return float(self.lib.mi355_bench_hbm_read(nbytes, iters))

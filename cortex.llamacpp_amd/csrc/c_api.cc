@@ -470,6 +470,24 @@ bool cache_row_to_ggml(int type, DevBuf &codes, DevBuf &scales, int G, int D, in
     }
     return true;
 }
+// ... and the whole cache: every cell of the device's planes back into ggml-layout rows [n_cells][G * D] (the inverse of cache_planes_from_rows)
+bool cache_rows_from_planes(int type, DevBuf &codes, DevBuf &scales, int G, int D, int n_cells, void *rows) {
+    uint8_t *dst = (uint8_t *)rows;
+    const size_t rb = ggml_row_bytes(type, (int64_t)G * D);
+    const int cb = type == T_F16 ? 64 : type == T_Q8_0 ? 32 : 16, bb = type == T_F16 ? 64 : cb + 2;   // code bytes of 32 elements; bytes of their ggml block
+    std::vector<uint8_t> c((size_t)G * n_cells * (D / 32) * cb);
+    std::vector<uint16_t> sc(type == T_F16 ? 0 : (size_t)G * n_cells * (D / 32));
+    if (!codes.down(c.data(), c.size()) || (!sc.empty() && !scales.down(sc.data(), sc.size() * 2))) return false;
+    for (int cell = 0; cell < n_cells; cell++)
+        for (int g = 0; g < G; g++)
+            for (int b = 0; b < D / 32; b++) {
+                const size_t bi = ((size_t)g * n_cells + cell) * (D / 32) + b;
+                uint8_t *blk = dst + (size_t)cell * rb + ((size_t)g * (D / 32) + b) * bb;
+                if (type != T_F16) { memcpy(blk, &sc[bi], 2); blk += 2; }
+                memcpy(blk, &c[bi * cb], (size_t)cb);
+            }
+    return true;
+}
 int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y);
 }  // namespace
 
@@ -1122,6 +1140,84 @@ int mi355_op_attn_decode_neox(const float *q, const float *k_new, const float *v
     if (att_out && !datt.down(att_out, K * 4)) return MI355_ERR_HIP;
     if (!cache_row_to_ggml(type_k, dk, dks, G, D, n_cells, tok_cell, k_row_out) || !cache_row_to_ggml(type_v, dv, dvs, G, D, n_cells, tok_cell, v_row_out)) return MI355_ERR_HIP;
     return MI355_OK;
+}
+
+// The K / V cache write of a batch on its own (test entry): the four launches that rotate K and write K / V rows into the cache,
+// on a caller-supplied cache that crosses the boundary whole, in and out, as ggml-layout rows.  form 0: launch_rope_kv_store computing its angles, 1: on the
+// table of launch_rope_table, 2: launch_rope_q_kv_store_fast, 3: launch_kv_store_fast.  A form that has no kernel for the arguments is refused, never launched.
+int mi355_op_kv_store(int32_t form, float *q, const float *k, const float *v, int64_t T, int32_t H, int32_t G, int32_t D, int32_t n_rot, int32_t neox,
+                      int32_t type_k, int32_t type_v, int32_t n_cells, const int32_t *tok_pos, const int32_t *tok_cell, float rope_base, float freq_scale,
+                      const float *freq_factors, const float *q_norm, const float *k_norm, float eps, void *k_cache, void *v_cache) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (form < 0 || form > 3 || !k || !v || !tok_pos || !tok_cell || !k_cache || !v_cache || (form != 3 && !q)) { fail("bad form / null argument"); return MI355_ERR_ARG; }
+    if (T < 1 || T > 4096 || H < 1 || G < 1 || D < 32 || D % 32 || n_rot < 2 || n_rot > D || n_rot % 2 || n_cells < 1) { fail("bad geometry"); return MI355_ERR_ARG; }
+    if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("bad cache type"); return MI355_ERR_ARG; }
+    for (int64_t t = 0; t < T; t++)
+        if (tok_cell[t] < 0 || tok_cell[t] >= n_cells) { fail("tok_cell outside the cache"); return MI355_ERR_ARG; }
+    const size_t q_dim = (size_t)H * D, kv_dim = (size_t)G * D;
+    if (form < 2 && ((size_t)n_rot + kv_dim) * 4 > 48 * 1024) { fail("n_head_kv * head_dim too wide for the generic kernel's LDS"); return MI355_ERR_ARG; }
+    if (form < 2 && (q_norm || k_norm) && (n_rot != D || (D != 64 && D != 128))) { fail("the q / k norm works on whole heads of 64 or 128"); return MI355_ERR_ARG; }
+    std::vector<uint8_t> kc, vc;
+    std::vector<uint16_t> ks, vs;
+    cache_planes_from_rows(type_k, k_cache, G, D, n_cells, kc, ks);
+    cache_planes_from_rows(type_v, v_cache, G, D, n_cells, vc, vs);
+    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dv(vc.size()), dvs(vs.size() * 2 + 16), dqn((size_t)D * 4), dkn_w((size_t)D * 4), dff((size_t)n_rot * 2 + 16);
+    DevBuf dq((size_t)T * q_dim * 4), dkn((size_t)T * kv_dim * 4), dvn((size_t)T * kv_dim * 4), dtp((size_t)T * 4), dcell((size_t)T * 4), dcsb((size_t)T * n_rot * 4 + 64);
+    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dks.p || !dvs.p || !dq.p || (q && !dq.up(q, (size_t)T * q_dim * 4)) ||
+        !dkn.up(k, (size_t)T * kv_dim * 4) || !dvn.up(v, (size_t)T * kv_dim * 4) || !dtp.up(tok_pos, (size_t)T * 4) || !dcell.up(tok_cell, (size_t)T * 4) || !dcsb.p ||
+        (q_norm && !dqn.up(q_norm, (size_t)D * 4)) || (k_norm && !dkn_w.up(k_norm, (size_t)D * 4)) ||
+        (freq_factors && !dff.up(freq_factors, (size_t)(n_rot / 2) * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    if (!ks.empty() && !dks.up(ks.data(), ks.size() * 2)) return MI355_ERR_OOM;
+    if (!vs.empty() && !dvs.up(vs.data(), vs.size() * 2)) return MI355_ERR_OOM;
+    RopeArgs ra{};
+    ra.n_rot = n_rot; ra.freq_base = rope_base; ra.freq_scale = freq_scale; ra.freq_factors = freq_factors ? dff.as<float>() : nullptr; ra.neox = neox ? 1 : 0;
+    ra.q_norm = q_norm ? dqn.as<float>() : nullptr; ra.k_norm = k_norm ? dkn_w.as<float>() : nullptr; ra.qk_eps = eps;
+    if (form == 2 && !rope_q_kv_store_fast_applicable(H, G, D, type_k, type_v, ra)) { fail("the vectorised prompt store has no form for these arguments"); return MI355_ERR_ARG; }
+    if (form == 3 && !kv_store_fast_applicable(G, D, type_k, type_v, ra)) { fail("the small-batch decode store has no form for these arguments"); return MI355_ERR_ARG; }
+    KVLayerView kv{};
+    kv.k = dk.as<uint8_t>(); kv.kd = dks.as<uint16_t>(); kv.v = dv.as<uint8_t>(); kv.vd = dvs.as<uint16_t>();
+    hipError_t e = hipSuccess;
+    if (form != 0) e = launch_rope_table(dtp.as<int32_t>(), (int)T, ra, dcsb.as<float>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "rope_table");
+    if (form < 2)
+        e = launch_rope_kv_store(dq.as<float>(), dkn.as<float>(), dvn.as<float>(), (int)T, H, G, D, dtp.as<int32_t>(), dcell.as<int32_t>(), ra, kv, type_k, type_v, n_cells,
+                                 form == 1 ? dcsb.as<float>() : nullptr, nullptr);
+    else if (form == 2)
+        e = launch_rope_q_kv_store_fast(dq.as<float>(), dkn.as<float>(), dvn.as<float>(), (int)T, H, G, D, dcsb.as<float>(), ra, dcell.as<int32_t>(), kv, type_k, type_v,
+                                        n_cells, nullptr);
+    else
+        e = launch_kv_store_fast(dkn.as<float>(), dvn.as<float>(), (int)T, G, D, dcsb.as<float>(), ra, dcell.as<int32_t>(), kv, type_k, type_v, n_cells, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "kv_store");
+    if (form != 3 && !dq.down(q, (size_t)T * q_dim * 4)) return MI355_ERR_HIP;
+    if (!cache_rows_from_planes(type_k, dk, dks, G, D, n_cells, k_cache) || !cache_rows_from_planes(type_v, dv, dvs, G, D, n_cells, v_cache)) return MI355_ERR_HIP;
+    return MI355_OK;
+}
+
+// The K-shift on its own (test entry): one launch_k_shift over a caller-supplied K cache that crosses the boundary whole, in and out.
+int mi355_op_k_shift(int32_t type_k, int32_t G, int32_t D, int32_t n_rot, int32_t neox, int32_t n_cells, const int32_t *delta, float rope_base, float freq_scale,
+                     const float *freq_factors, float ext_factor, float attn_factor, float corr_lo, float corr_hi, void *k_cache) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!delta || !k_cache || G < 1 || D < 32 || D % 32 || n_rot < 2 || n_rot > D || n_rot % 2 || n_cells < 1) { fail("bad geometry / null argument"); return MI355_ERR_ARG; }
+    if (type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) { fail("bad cache type"); return MI355_ERR_ARG; }
+    if (((size_t)n_rot + (size_t)G * D) * 4 > 48 * 1024) { fail("n_head_kv * head_dim too wide for the kernel's LDS"); return MI355_ERR_ARG; }
+    std::vector<uint8_t> kc;
+    std::vector<uint16_t> ks;
+    cache_planes_from_rows(type_k, k_cache, G, D, n_cells, kc, ks);
+    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dd((size_t)n_cells * 4), dff((size_t)n_rot * 2 + 16);
+    if (!dk.up(kc.data(), kc.size()) || !dks.p || !dd.up(delta, (size_t)n_cells * 4) || (freq_factors && !dff.up(freq_factors, (size_t)(n_rot / 2) * 4))) {
+        fail("device alloc/copy failed"); return MI355_ERR_OOM;
+    }
+    if (!ks.empty() && !dks.up(ks.data(), ks.size() * 2)) return MI355_ERR_OOM;
+    RopeArgs ra{};
+    ra.n_rot = n_rot; ra.freq_base = rope_base; ra.freq_scale = freq_scale; ra.freq_factors = freq_factors ? dff.as<float>() : nullptr; ra.neox = neox ? 1 : 0;
+    ra.ext_factor = ext_factor; ra.attn_factor = attn_factor; ra.corr_lo = corr_lo; ra.corr_hi = corr_hi;
+    KVLayerView kv{};
+    kv.k = dk.as<uint8_t>(); kv.kd = dks.as<uint16_t>();
+    hipError_t e = launch_k_shift(kv, type_k, G, D, n_cells, dd.as<int32_t>(), ra, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "k_shift");
+    return cache_rows_from_planes(type_k, dk, dks, G, D, n_cells, k_cache) ? MI355_OK : MI355_ERR_HIP;
 }
 
 int mi355_debug_set_option(const char *name, int32_t value) {

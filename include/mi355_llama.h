@@ -276,6 +276,22 @@ MI355_API int mi355_op_attn_decode_neox(const float *q, const float *k_new, cons
                                         int32_t type_k, const void *k, int32_t type_v, const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos,
                                         int32_t tok_cell, float rope_base, float scale, const float *q_norm, const float *k_norm, float eps, int32_t mode,
                                         float *att_out, void *k_row_out, void *v_row_out);
+/* The K / V cache write of a batch of T tokens on its own (test entry): q [T][n_head * head_dim] is rotated in place, k [T][n_head_kv * head_dim] is rotated
+ * and quantised into k_cache at tok_cell[t], v is quantised into v_cache.  k_cache / v_cache: the whole cache as ggml-layout rows [n_cells][n_head_kv *
+ * head_dim] of type_k / type_v, read before the launch and written back whole after it (cells outside tok_cell come back as they went in; tok_cell distinct).
+ * form 0: the generic kernel, angles computed from tok_pos inside it; 1: the same kernel on the cos / sin table of the batch; 2: the vectorised prompt store
+ * (q, k and v); 3: the small-batch decode store (k and v only; q may be NULL and is not touched).  Forms 2 and 3 take NORM rope, f16 / q8_0 caches, no q / k
+ * norm and n_head_kv * head_dim % 1024 == 0 (form 2: n_head * head_dim % 1024 == 0 too): MI355_ERR_ARG otherwise, nothing is launched.  freq_factors
+ * [n_rot / 2] and q_norm / k_norm [head_dim] (qwen3: n_rot == head_dim, 64 or 128) may be NULL. */
+MI355_API int mi355_op_kv_store(int32_t form, float *q, const float *k, const float *v, int64_t T, int32_t n_head, int32_t n_head_kv, int32_t head_dim,
+                                int32_t n_rot, int32_t neox, int32_t type_k, int32_t type_v, int32_t n_cells, const int32_t *tok_pos, const int32_t *tok_cell,
+                                float rope_base, float freq_scale, const float *freq_factors, const float *q_norm, const float *k_norm, float eps,
+                                void *k_cache, void *v_cache);
+/* The K-shift of llama_kv_cache_seq_add on its own (test entry): every row of k_cache (layout as above) whose delta[cell] != 0 is dequantised, rotated by
+ * delta[cell] positions and quantised again, in one launch; rows with delta 0 are not touched.  The YaRN parameters as mi355_op_rope_yarn takes them. */
+MI355_API int mi355_op_k_shift(int32_t type_k, int32_t n_head_kv, int32_t head_dim, int32_t n_rot, int32_t neox, int32_t n_cells, const int32_t *delta,
+                               float rope_base, float freq_scale, const float *freq_factors, float ext_factor, float attn_factor, float corr_lo,
+                               float corr_hi, void *k_cache);
 
 /* ------------------------------------------------------------------ tokenizer
  * llama_tokenize / llama_token_to_piece as reached through common_tokenize / common_token_to_piece

@@ -41,6 +41,16 @@ def test_no_cpu_fallback(pkg):
     out = np.zeros(292, np.uint8)
     rc = lib.mi355_op_quantize_act(15, x.ctypes.data, 256, 1, out.ctypes.data)
     assert rc == -100
+    # the K / V cache write and the K-shift test entries: one cell of one 32-element f16 head
+    q = np.zeros(32, np.float32)
+    cache = np.zeros(64, np.uint8)
+    zero = np.zeros(1, np.int32)
+    for form in range(4):
+        rc = lib.mi355_op_kv_store(form, q.ctypes.data, q.ctypes.data, q.ctypes.data, 1, 1, 1, 32, 32, 0, 1, 1, 1, zero.ctypes.data, zero.ctypes.data,
+                                   1e4, 1.0, None, None, None, 0.0, cache.ctypes.data, cache.ctypes.data)
+        assert rc == -100, form
+    rc = lib.mi355_op_k_shift(1, 1, 32, 32, 0, 1, zero.ctypes.data, 1e4, 1.0, None, 0.0, 1.0, 0.0, 0.0, cache.ctypes.data)
+    assert rc == -100
 
 
 def test_product_does_not_touch_oracle():

@@ -482,6 +482,17 @@ def test_flash_attn_prefill_second_micro_batch_of_a_filled_context(be, tkv, tol)
                                              (8, 2, 70, Q5_K), (4, 4, 300, Q4_K),             # one query head per kv head: two kv heads per merge ticket
                                              (16, 2, 2100, Q4_K), (8, 4, 130, Q6_K)])        # 8 and 2 query heads per kv head
 def test_attn_step_decode_block(be, fused, tkv, H, G, n_cells, t_o):
+    attn_step_decode_block(be, fused, tkv, H, G, n_cells, t_o)
+
+
+@pytest.mark.parametrize("H,G,n_cells,t_o", [(8, 2, 70, Q5_K), (8, 4, 130, Q6_K)])
+def test_attn_step_decode_block_q4_0_cache(be, H, G, n_cells, t_o):
+    """The same block over a q4_0 cache, at the two smallest geometries: NORM rope and the q4_0 K / V row quantised inside the single-launch decode attention
+    (fused = 0; attn_out.hip has no q4_0 form).  Same assertions; a q4_0 step is |max| / 8 of the block."""
+    attn_step_decode_block(be, 0, Q4_0, H, G, n_cells, t_o)
+
+
+def attn_step_decode_block(be, fused, tkv, H, G, n_cells, t_o):
     """The attention block of a single-token step as the decode path launches it - rope of q and of the token's K row, the K / V row quantised into the cache,
     flash_attn_ext over the visible cells (holes, cells of later positions), the merge of the chunk partials, Q8_K quantisation, attn_output mat-vec + residual -
     against the oracle's ops chained the same way; fused = 1 is attn_out.hip (one launch), 0 the single-launch attention + the weight-stream mat-vec.
@@ -515,7 +526,10 @@ def test_attn_step_decode_block(be, fused, tkv, H, G, n_cells, t_o):
     assert (vr == v_row).all()                                      # no arithmetic before the V row's quantisation: bit-exact
     # the K row goes through the rope first (device cosf / sinf: 4e-6): its codes may sit one step off on a rounding tie
     dk_ref, dk_got = oq.dequantize(tkv, k_row, G * D), oq.dequantize(tkv, kr, G * D)
-    step = np.abs(kn).reshape(-1, 32).max(axis=1).repeat(32) / 127 if tkv == Q8_0 else np.abs(kn) * 2.0 ** -10
+    if tkv == F16:
+        step = np.abs(kn) * 2.0 ** -10
+    else:
+        step = np.abs(kn).reshape(-1, 32).max(axis=1).repeat(32) / (127 if tkv == Q8_0 else 8)
     assert (np.abs(dk_ref - dk_got) <= 1.01 * step + 1e-7).all()
     assert (dk_ref == dk_got).mean() >= 0.99
     kc2, vc2 = kc.copy(), vc.copy()
