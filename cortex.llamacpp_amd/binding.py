@@ -99,8 +99,11 @@ SYMBOLS = {
     "mi355_debug_enable_taps": (None, [_vp, _i32]),
     "mi355_debug_layer_out": (_i32, [_vp, _i32, _vp, _sz]),
     "mi355_op_quantize_act": (C.c_int, [_i32, _vp, _i64, _i64, _vp]),
+    "mi355_op_rms_norm_quant": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp, _vp]),
+    "mi355_op_swiglu_quant": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
     "mi355_op_mul_mat": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "mi355_op_mul_mat_add": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "mi355_op_mul_mat_fused": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _vp, _f32, _vp]),
     "mi355_op_f32_to_bf16": (C.c_int, [_vp, _i64, _vp]),
     "mi355_op_mul_mat_bf16": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mi355_op_ffn_gate_up": (C.c_int, [_i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
@@ -231,6 +234,34 @@ class Backend:
         out = np.zeros(rows * bb, np.uint8)
         self._chk(self.lib.mi355_op_quantize_act(act_type, _ptr(x), n, rows, _ptr(out)), "op_quantize_act")
         return out.reshape(rows, bb)
+
+    def rms_norm_quant(self, x: np.ndarray, w: np.ndarray, eps: float):
+        """(Q8_0 blocks [T][34 n / 32], y_f32 [T][n]) of RMSNorm(x) * w: the fused norm + quantise launch (see mi355_op_rms_norm_quant)."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(w, np.float32)
+        T, n = (1, x.size) if x.ndim == 1 else x.shape
+        out = np.zeros((T, 34 * (n // 32)), np.uint8)
+        y = np.zeros((T, n), np.float32)
+        self._chk(self.lib.mi355_op_rms_norm_quant(_ptr(x), _ptr(w), n, T, eps, _ptr(y), _ptr(out)), "op_rms_norm_quant")
+        return out, y
+
+    def swiglu_quant(self, gate: np.ndarray, up: np.ndarray) -> np.ndarray:
+        """Q8_0 blocks [T][34 n / 32] of silu(gate) * up (see mi355_op_swiglu_quant)."""
+        gate = np.ascontiguousarray(gate, np.float32)
+        up = np.ascontiguousarray(up, np.float32)
+        T, n = (1, gate.size) if gate.ndim == 1 else gate.shape
+        out = np.zeros((T, 34 * (n // 32)), np.uint8)
+        self._chk(self.lib.mi355_op_swiglu_quant(_ptr(gate), _ptr(up), n, T, _ptr(out)), "op_swiglu_quant")
+        return out
+
+    def mul_mat_fused(self, t: int, W: np.ndarray, N: int, K: int, x: np.ndarray, norm_w=None, eps: float = 0.0) -> np.ndarray:
+        """One token's W . act with the activation quantised in the launch's prologue (see mi355_op_mul_mat_fused)."""
+        W = np.ascontiguousarray(W.view(np.uint8).reshape(-1))
+        x = np.ascontiguousarray(x, np.float32).reshape(K)
+        nw = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32).reshape(K)
+        y = np.zeros(N, np.float32)
+        self._chk(self.lib.mi355_op_mul_mat_fused(t, _ptr(W), N, K, _ptr(x), _ptr(nw), eps, _ptr(y)), "op_mul_mat_fused")
+        return y
 
     def mul_mat(self, t: int, W: np.ndarray, N: int, K: int, x: np.ndarray, want_ints: bool = False):
         W = np.ascontiguousarray(W.view(np.uint8).reshape(-1))

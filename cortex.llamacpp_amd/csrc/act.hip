@@ -15,6 +15,11 @@
 namespace mi355 {
 
 // One workgroup per row.  do_norm: y = (x * rsqrt(mean(x^2)+eps)) * w, else y = x.
+// TAIL: n is a whole number of 32-element blocks but not of 256-groups (Qwen2.5-0.5B's 896, SmolLM2's 576, gpt-oss's 2880): 1 .. 7 blocks follow the last whole
+// group.  A block is 8 lanes, so in that last group a lane group of 8 is all data or none: the lanes without data carry zeros through the wave-wide steps of
+// wave_quant_q80 and store nothing, the others do the per-block arithmetic of every other block.  Q8_0 only (a Q8_K block is the whole group).  The kernels
+// for whole groups are the TAIL = false instantiations, whose code the parameter does not touch.
+template <bool TAIL>
 __global__ __launch_bounds__(256) void norm_quant_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                          int n, float eps, int do_norm, float *__restrict__ yf,
                                                          ActQuant q, int want_q8k, int want_q80, int8_t *__restrict__ bh, int8_t *__restrict__ bl) {
@@ -36,17 +41,19 @@ __global__ __launch_bounds__(256) void norm_quant_kernel(const float *__restrict
         const float mean = (float)(tot / (double)n);
         scale = 1.0f / sqrtf(mean + eps);
     }
-    const int nblk = n >> 8;
+    const int nblk = TAIL ? (n + 255) >> 8 : n >> 8;
     for (int b = blockIdx.y * 4 + wave; b < nblk; b += 4 * gridDim.y) {
         const int e0 = b * 256 + lane * 4;
-        float4 v = *reinterpret_cast<const float4 *>(xr + e0);
-        if (do_norm) {
+        const bool ok = !TAIL || e0 < n;                    // (whole groups: constant)
+        float4 v = float4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (ok) v = *reinterpret_cast<const float4 *>(xr + e0);
+        if (do_norm && ok) {
             const float4 ww = *reinterpret_cast<const float4 *>(w + e0);
             v.x = (v.x * scale) * ww.x; v.y = (v.y * scale) * ww.y; v.z = (v.z * scale) * ww.z; v.w = (v.w * scale) * ww.w;
         }
-        if (yf) *reinterpret_cast<float4 *>(yf + (size_t)row * n + e0) = v;
+        if (yf && ok) *reinterpret_cast<float4 *>(yf + (size_t)row * n + e0) = v;
         const float vv[4] = {v.x, v.y, v.z, v.w};
-        if (want_q8k) {
+        if (!TAIL && want_q8k) {
             uint32_t packed; int bs; float dq;
             wave_quant_q8k(vv, lane, packed, bs, dq);
             *reinterpret_cast<uint32_t *>(q.qs + (size_t)row * n + e0) = packed;
@@ -59,9 +66,9 @@ __global__ __launch_bounds__(256) void norm_quant_kernel(const float *__restrict
         }
         if (want_q80) {
             uint32_t packed; float d;
-            wave_quant_q80(vv, packed, d);
-            *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)row * n + e0) = packed;
-            if ((lane & 7) == 0) q.d0[(size_t)row * (n >> 5) + b * 8 + (lane >> 3)] = f2h(d);
+            wave_quant_q80(vv, packed, d);                  // (all lanes: its 8-lane steps are wave-wide instructions)
+            if (ok) *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)row * n + e0) = packed;
+            if (ok && (lane & 7) == 0) q.d0[(size_t)row * (n >> 5) + b * 8 + (lane >> 3)] = f2h(d);
         }
     }
 }
@@ -71,14 +78,16 @@ __global__ __launch_bounds__(256) void norm_quant_kernel(const float *__restrict
 // do_norm: the row's sum of squares must come out with the bits of the kernel above (whose thread tid adds the squares of float4 tid, tid + 256, tid + 512 ..
 // to ONE double, element by element): every thread leaves its products in LDS and the first 256 threads add them up in exactly that order, then the same wave sums
 // and the same four partial sums.  grid = (rows, parts): a part is 16 blocks of the row; do_norm needs the whole row in one workgroup (n <= 16 * 256 * NV).
-template <int NV>
+// TAIL: as in norm_quant_kernel; the last group's wave loads, squares and stores only where the row has data (do_norm then wants at least the four waves of
+// the summation in the workgroup, whatever the row's length: launch_wide).
+template <int NV, bool TAIL>
 __global__ __launch_bounds__(1024) void norm_quant_wide_kernel(const float *__restrict__ x, const float *__restrict__ w, int n, float eps, int do_norm,
                                                                 float *__restrict__ yf, ActQuant q, int want_q8k, int want_q80, int8_t *__restrict__ bh, int8_t *__restrict__ bl) {
     extern __shared__ float prod[];                       // do_norm: [n] squares, float4 index major
     __shared__ double red[4];
     __shared__ float s_scale;
     const int row = blockIdx.x, u = threadIdx.x, lane = u & 63, wave = u >> 6, nw = blockDim.x >> 6;
-    const int nblk = n >> 8;
+    const int nblk = TAIL ? (n + 255) >> 8 : n >> 8;
     const float *xr = x + (size_t)row * n;
     float4 v[NV];
     int blk[NV];
@@ -86,13 +95,14 @@ __global__ __launch_bounds__(1024) void norm_quant_wide_kernel(const float *__re
     for (int j = 0; j < NV; j++) {
         blk[j] = (do_norm ? 0 : blockIdx.y * 16 * NV) + wave + nw * j;
         const int bc = blk[j] < nblk ? blk[j] : nblk - 1;
-        v[j] = *reinterpret_cast<const float4 *>(xr + bc * 256 + lane * 4);
+        v[j] = float4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (!TAIL || bc * 256 + lane * 4 < n) v[j] = *reinterpret_cast<const float4 *>(xr + bc * 256 + lane * 4);
     }
     float scale = 1.0f;
     if (do_norm) {
 #pragma unroll
         for (int j = 0; j < NV; j++)
-            if (blk[j] < nblk) *reinterpret_cast<float4 *>(prod + ((size_t)blk[j] * 64 + lane) * 4) = float4{v[j].x * v[j].x, v[j].y * v[j].y, v[j].z * v[j].z, v[j].w * v[j].w};
+            if (blk[j] < nblk && (!TAIL || blk[j] * 256 + lane * 4 < n)) *reinterpret_cast<float4 *>(prod + ((size_t)blk[j] * 64 + lane) * 4) = float4{v[j].x * v[j].x, v[j].y * v[j].y, v[j].z * v[j].z, v[j].w * v[j].w};
         __syncthreads();
         if (u < 256) {
             double s = 0.0;
@@ -117,14 +127,15 @@ __global__ __launch_bounds__(1024) void norm_quant_wide_kernel(const float *__re
         const int b = blk[j];
         if (b >= nblk) continue;                           // wave-uniform
         const int e0 = b * 256 + lane * 4;
+        const bool ok = !TAIL || e0 < n;
         float4 t = v[j];
-        if (do_norm) {
+        if (do_norm && ok) {
             const float4 ww = *reinterpret_cast<const float4 *>(w + e0);
             t.x = (t.x * scale) * ww.x; t.y = (t.y * scale) * ww.y; t.z = (t.z * scale) * ww.z; t.w = (t.w * scale) * ww.w;
         }
-        if (yf) *reinterpret_cast<float4 *>(yf + (size_t)row * n + e0) = t;
+        if (yf && ok) *reinterpret_cast<float4 *>(yf + (size_t)row * n + e0) = t;
         const float vv[4] = {t.x, t.y, t.z, t.w};
-        if (want_q8k) {
+        if (!TAIL && want_q8k) {
             uint32_t packed; int bs; float dq;
             wave_quant_q8k(vv, lane, packed, bs, dq);
             *reinterpret_cast<uint32_t *>(q.qs + (size_t)row * n + e0) = packed;
@@ -138,26 +149,33 @@ __global__ __launch_bounds__(1024) void norm_quant_wide_kernel(const float *__re
         if (want_q80) {
             uint32_t packed; float d;
             wave_quant_q80(vv, packed, d);
-            *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)row * n + e0) = packed;
-            if ((lane & 7) == 0) q.d0[(size_t)row * (n >> 5) + b * 8 + (lane >> 3)] = f2h(d);
+            if (ok) *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)row * n + e0) = packed;
+            if (ok && (lane & 7) == 0) q.d0[(size_t)row * (n >> 5) + b * 8 + (lane >> 3)] = f2h(d);
         }
     }
 }
 // true: launched.  Rows of a prompt batch only (T >= 32); with the norm the row must fit one workgroup
 static bool launch_wide(const float *x, const float *w, int n, int T, float eps, int do_norm, float *yf, const ActQuant &qq, int k, int z, int8_t *bh, int8_t *bl, hipStream_t st) {
     static const bool off = getenv("MI355_QUANT_WIDE") && getenv("MI355_QUANT_WIDE")[0] == '0';
-    const int nblk = n >> 8;
-    if (off || T < 32 || (n & 255) || nblk < 1) return false;
+    const int nblk = (n + 255) >> 8;                        // 256-groups, the last one partial where the row ends inside it
+    const bool tail = (n & 255) != 0;
+    if (off || T < 32 || (n & 31) || nblk < 1) return false;
     if (do_norm) {
-        if (nblk > 32 || (n & 1023)) return false;
-        const int nv = nblk > 16 ? 2 : 1, nwv = (nblk + nv - 1) / nv;
+        if (nblk > 32 || (!tail && (n & 1023))) return false;
+        const int nv = nblk > 16 ? 2 : 1;
+        int nwv = (nblk + nv - 1) / nv;
+        if (nwv < 4) nwv = 4;                               // (the summation's 256 threads; only a row with a tail can be this short)
         const size_t lds = (size_t)n * sizeof(float);
-        if (nv == 1) hipLaunchKernelGGL(norm_quant_wide_kernel<1>, dim3(T, 1), dim3(64 * nwv), lds, st, x, w, n, eps, 1, yf, qq, k, z, bh, bl);
-        else hipLaunchKernelGGL(norm_quant_wide_kernel<2>, dim3(T, 1), dim3(64 * nwv), lds, st, x, w, n, eps, 1, yf, qq, k, z, bh, bl);
+        if (tail) {
+            if (nv == 1) hipLaunchKernelGGL((norm_quant_wide_kernel<1, true>), dim3(T, 1), dim3(64 * nwv), lds, st, x, w, n, eps, 1, yf, qq, k, z, bh, bl);
+            else hipLaunchKernelGGL((norm_quant_wide_kernel<2, true>), dim3(T, 1), dim3(64 * nwv), lds, st, x, w, n, eps, 1, yf, qq, k, z, bh, bl);
+        } else if (nv == 1) hipLaunchKernelGGL((norm_quant_wide_kernel<1, false>), dim3(T, 1), dim3(64 * nwv), lds, st, x, w, n, eps, 1, yf, qq, k, z, bh, bl);
+        else hipLaunchKernelGGL((norm_quant_wide_kernel<2, false>), dim3(T, 1), dim3(64 * nwv), lds, st, x, w, n, eps, 1, yf, qq, k, z, bh, bl);
         return true;
     }
     const int parts = (nblk + 15) / 16, nwv = nblk < 16 ? nblk : 16;
-    hipLaunchKernelGGL(norm_quant_wide_kernel<1>, dim3(T, parts), dim3(64 * nwv), 0, st, x, w, n, eps, 0, yf, qq, k, z, bh, bl);
+    if (tail) hipLaunchKernelGGL((norm_quant_wide_kernel<1, true>), dim3(T, parts), dim3(64 * nwv), 0, st, x, w, n, eps, 0, yf, qq, k, z, bh, bl);
+    else hipLaunchKernelGGL((norm_quant_wide_kernel<1, false>), dim3(T, parts), dim3(64 * nwv), 0, st, x, w, n, eps, 0, yf, qq, k, z, bh, bl);
     return true;
 }
 
@@ -167,46 +185,57 @@ static bool launch_wide(const float *x, const float *w, int n, int T, float eps,
 #define MI355_QUANT_SPLIT_BLOCKS 8
 #endif
 static int quant_splits(int T, int n) {
-    if (T < 8) return ((n >> 8) + 3) / 4;
-    const int nblk = n >> 8;
+    const int nblk = (n + 255) >> 8;                        // (a partial last group counts)
+    if (T < 8) return (nblk + 3) / 4;
     int s = (nblk + MI355_QUANT_SPLIT_BLOCKS - 1) / MI355_QUANT_SPLIT_BLOCKS;      // blocks per workgroup <= 8 (two per wave)
     if (T < 64 && s < 2) s = 2;
     while (s > 1 && (long long)T * s > 16384) s >>= 1;
     return s < 1 ? 1 : s;
 }
 
+// rows of any whole number of 32-element blocks; Q8_K blocks are whole 256-groups
+static bool quant_args_ok(int n, int T, bool q8k, bool q80) { return n > 0 && T > 0 && (n & 3) == 0 && !((q8k || q80) && (n & 31)) && !(q8k && (n & 255)); }
+
 hipError_t launch_rmsnorm_quant(const float *x, const float *w, int n, int T, float eps, float *y_f32,
                                 const ActQuant *q, bool want_q8k, bool want_q80, hipStream_t st, int8_t *bh, int8_t *bl) {
     ActQuant qq;
     if (q) qq = *q;
+    if (!quant_args_ok(n, T, q && want_q8k, q && want_q80)) return hipErrorInvalidValue;
     if (launch_wide(x, w, n, T, eps, 1, y_f32, qq, (int)(q && want_q8k), (int)(q && want_q80), (q && want_q8k) ? bh : nullptr, bl, st)) return hipGetLastError();
     const int splits = quant_splits(T, n);
-    hipLaunchKernelGGL(norm_quant_kernel, dim3(T, splits), dim3(256), 0, st, x, w, n, eps, 1, y_f32, qq,
-                       (int)(q && want_q8k), (int)(q && want_q80), (q && want_q8k) ? bh : nullptr, bl);
+    if (n & 255) hipLaunchKernelGGL(norm_quant_kernel<true>, dim3(T, splits), dim3(256), 0, st, x, w, n, eps, 1, y_f32, qq, 0, (int)(q && want_q80), (int8_t *)nullptr, (int8_t *)nullptr);
+    else hipLaunchKernelGGL(norm_quant_kernel<false>, dim3(T, splits), dim3(256), 0, st, x, w, n, eps, 1, y_f32, qq,
+                            (int)(q && want_q8k), (int)(q && want_q80), (q && want_q8k) ? bh : nullptr, bl);
     return hipGetLastError();
 }
 
 hipError_t launch_quantize(const float *x, int n, int T, const ActQuant &q, bool want_q8k, bool want_q80, hipStream_t st, int8_t *bh, int8_t *bl) {
+    if (!quant_args_ok(n, T, want_q8k, want_q80)) return hipErrorInvalidValue;
     if (launch_wide(x, nullptr, n, T, 0.0f, 0, nullptr, q, (int)want_q8k, (int)want_q80, want_q8k ? bh : nullptr, bl, st)) return hipGetLastError();
     const int splits = quant_splits(T, n);
-    hipLaunchKernelGGL(norm_quant_kernel, dim3(T, splits), dim3(256), 0, st, x, (const float *)nullptr, n, 0.0f, 0,
-                       (float *)nullptr, q, (int)want_q8k, (int)want_q80, want_q8k ? bh : nullptr, bl);
+    if (n & 255) hipLaunchKernelGGL(norm_quant_kernel<true>, dim3(T, splits), dim3(256), 0, st, x, (const float *)nullptr, n, 0.0f, 0,
+                                    (float *)nullptr, q, 0, (int)want_q80, (int8_t *)nullptr, (int8_t *)nullptr);
+    else hipLaunchKernelGGL(norm_quant_kernel<false>, dim3(T, splits), dim3(256), 0, st, x, (const float *)nullptr, n, 0.0f, 0,
+                            (float *)nullptr, q, (int)want_q8k, (int)want_q80, want_q8k ? bh : nullptr, bl);
     return hipGetLastError();
 }
 
 // SwiGLU and the quantisation of its result for the down projection in one pass (prompt batches): y = silu(g) * u is
 // quantised block by block as norm_quant_kernel does and never written as f32 — the arithmetic of swiglu_kernel followed by
 // the quantiser, so the blocks are bit-identical to the two launches it replaces.
+template <bool TAIL>                                        // (as norm_quant_kernel)
 __global__ __launch_bounds__(256) void swiglu_quant_kernel(const float *__restrict__ g, const float *__restrict__ u, int n, ActQuant q,
                                                            int want_q8k, int want_q80, int8_t *__restrict__ bh, int8_t *__restrict__ bl) {
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nblk = n >> 8;
+    const int nblk = TAIL ? (n + 255) >> 8 : n >> 8;
     for (int b = blockIdx.y * 4 + wave; b < nblk; b += 4 * gridDim.y) {
         const int e0 = b * 256 + lane * 4;
-        const float4 a = *reinterpret_cast<const float4 *>(g + (size_t)row * n + e0), c = *reinterpret_cast<const float4 *>(u + (size_t)row * n + e0);
+        const bool ok = !TAIL || e0 < n;
+        float4 a = float4{0.0f, 0.0f, 0.0f, 0.0f}, c = a;   // (silu(0) * 0 = 0: a lane without data carries zeros)
+        if (ok) { a = *reinterpret_cast<const float4 *>(g + (size_t)row * n + e0); c = *reinterpret_cast<const float4 *>(u + (size_t)row * n + e0); }
         const float vv[4] = {(a.x / (1.0f + expf(-a.x))) * c.x, (a.y / (1.0f + expf(-a.y))) * c.y, (a.z / (1.0f + expf(-a.z))) * c.z,
                              (a.w / (1.0f + expf(-a.w))) * c.w};
-        if (want_q8k) {
+        if (!TAIL && want_q8k) {
             uint32_t packed; int bs; float dq;
             wave_quant_q8k(vv, lane, packed, bs, dq);
             *reinterpret_cast<uint32_t *>(q.qs + (size_t)row * n + e0) = packed;
@@ -220,16 +249,17 @@ __global__ __launch_bounds__(256) void swiglu_quant_kernel(const float *__restri
         if (want_q80) {
             uint32_t packed; float d;
             wave_quant_q80(vv, packed, d);
-            *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)row * n + e0) = packed;
-            if ((lane & 7) == 0) q.d0[(size_t)row * (n >> 5) + b * 8 + (lane >> 3)] = f2h(d);
+            if (ok) *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)row * n + e0) = packed;
+            if (ok && (lane & 7) == 0) q.d0[(size_t)row * (n >> 5) + b * 8 + (lane >> 3)] = f2h(d);
         }
     }
 }
 hipError_t launch_swiglu_quant(const float *g, const float *u, int n, int T, const ActQuant &q, bool want_q8k, bool want_q80, hipStream_t st,
                                int8_t *bh, int8_t *bl) {
-    if ((n % 256) != 0 || T <= 0) return hipErrorInvalidValue;
+    if (!quant_args_ok(n, T, want_q8k, want_q80) || (n & 31)) return hipErrorInvalidValue;
     const int splits = quant_splits(T, n);
-    hipLaunchKernelGGL(swiglu_quant_kernel, dim3(T, splits), dim3(256), 0, st, g, u, n, q, (int)want_q8k, (int)want_q80, want_q8k ? bh : nullptr, bl);
+    if (n & 255) hipLaunchKernelGGL(swiglu_quant_kernel<true>, dim3(T, splits), dim3(256), 0, st, g, u, n, q, 0, (int)want_q80, (int8_t *)nullptr, (int8_t *)nullptr);
+    else hipLaunchKernelGGL(swiglu_quant_kernel<false>, dim3(T, splits), dim3(256), 0, st, g, u, n, q, (int)want_q8k, (int)want_q80, want_q8k ? bh : nullptr, bl);
     return hipGetLastError();
 }
 

@@ -527,7 +527,9 @@ __global__ __launch_bounds__(256) void flash_attn_combine_kernel(const float *pa
     if (tok_nsplits) splits = tok_nsplits[t];
     const int hpb = 256 / D;                       // heads per block (D = 64 -> 4, D = 128 -> 2)
     const int h0 = b * hpb;
-    if (wave < hpb) {
+    // (H need not be a whole number of blocks - 14, 9 or 5 heads of 64: the row's last block then holds fewer heads, and the lanes past the row's end
+    // merge nothing, carry zeros through the quantiser's wave-wide steps and store nothing; Q8_K codes want whole blocks)
+    if (wave < hpb && h0 + wave < H) {
         const float *p = part + ((size_t)t * H + h0 + wave) * stride_s * (D + 2);
         float M = -INFINITY;
         for (int s0 = 0; s0 < splits; s0 += 64) {
@@ -553,20 +555,22 @@ __global__ __launch_bounds__(256) void flash_attn_combine_kernel(const float *pa
     __syncthreads();
     {
         const int e = tid, hl = e / D, d = e - hl * D;
+        const bool okh = h0 + hl < H;
         const float *p = part + ((size_t)t * H + h0 + hl) * stride_s * (D + 2) + d;
         float acc = 0.0f;
-        for (int s = 0; s < splits; s++) {
+        for (int s = 0; okh && s < splits; s++) {
             const float w = wgt[hl * stride_s + s];
             if (w != 0.0f) acc += w * p[(size_t)s * (D + 2)];        // chunks with no visible cell publish only (m, l)
         }
         merged[e] = acc;
-        out[(size_t)t * E + b * 256 + e] = acc;
+        if (okh) out[(size_t)t * E + b * 256 + e] = acc;
     }
     __syncthreads();
     if (wave == 0 && (want_q8k || want_q80)) {
         const float4 v4 = *reinterpret_cast<const float4 *>(merged + lane * 4);
         const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
         const int e0 = b * 256 + lane * 4;
+        const bool ok = e0 < E;
         if (want_q8k) {
             uint32_t packed; int bs; float dq;
             wave_quant_q8k(vv, lane, packed, bs, dq);
@@ -581,8 +585,8 @@ __global__ __launch_bounds__(256) void flash_attn_combine_kernel(const float *pa
         if (want_q80) {
             uint32_t packed; float dd;
             wave_quant_q80(vv, packed, dd);
-            *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)t * E + e0) = packed;
-            if ((lane & 7) == 0) q.d0[(size_t)t * (E >> 5) + b * 8 + (lane >> 3)] = f2h(dd);
+            if (ok) *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)t * E + e0) = packed;
+            if (ok && (lane & 7) == 0) q.d0[(size_t)t * (E >> 5) + b * 8 + (lane >> 3)] = f2h(dd);
         }
     }
 }
@@ -776,7 +780,7 @@ hipError_t launch_flash_attn_decode(const AttnArgs &a, const float *cs_table, Ro
 #undef FAD_D
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const int nblk = (a.H * a.D) >> 8;
+    const int nblk = (a.H * a.D + 255) >> 8;          // (the last block partial where H * D ends inside it)
     ActQuant qq;
     if (a.out_q) qq = *a.out_q;
     hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, a.T), dim3(256), (size_t)(256 / a.D) * a.splits * 4, st, a.part, a.out, a.H, a.D, a.splits,
@@ -870,7 +874,7 @@ hipError_t launch_flash_attn_decode_fused(const AttnArgs &a, const float *cs_tab
 #undef FAD_D
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || counters) return e;
-    const int nblk = (a.H * a.D) >> 8;
+    const int nblk = (a.H * a.D + 255) >> 8;          // (the last block partial where H * D ends inside it)
     hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, 1), dim3(256), (size_t)(256 / a.D) * a.splits * 4, st, a.part, a.out, a.H, a.D, a.splits,
                        fz.q, fz.want_q8k, fz.want_q80, (const int32_t *)nullptr, (int8_t *)nullptr, (int8_t *)nullptr);
     return hipGetLastError();
@@ -890,18 +894,19 @@ __global__ __launch_bounds__(256) void flash_attn_combine_wave_kernel(const floa
     float wv[HPB];                                               // lane s: the weight of split s, per head of the block
 #pragma unroll
     for (int hh = 0; hh < HPB; hh++) {
+        const bool okh = h0 + hh < H;                            // (wave-uniform: the row's last block may hold fewer heads; such a head weighs nothing)
         const float *p = part + ((size_t)t * H + h0 + hh) * splits * (D + 2);
-        const float m = lane < splits ? p[(size_t)lane * (D + 2) + D] : -INFINITY;
+        const float m = okh && lane < splits ? p[(size_t)lane * (D + 2) + D] : -INFINITY;
         const float M = fmaxf(-INFINITY, wave_max(m));
         float w = 0.0f, l = 0.0f;
-        if (lane < splits) {
+        if (okh && lane < splits) {
             l = p[(size_t)lane * (D + 2) + D + 1];
             w = (m == -INFINITY) ? 0.0f : expf(m - M);
         }
         float den = 0.0f;
         den += wave_sum(w * l);
         const float inv = 1.0f / den;
-        wv[hh] = w * inv;
+        wv[hh] = okh ? w * inv : 0.0f;
     }
     const int e = lane * 4, hl = e / D, d = e - hl * D;
     const float *pr = part + ((size_t)t * H + h0 + hl) * splits * (D + 2) + d;
@@ -916,8 +921,9 @@ __global__ __launch_bounds__(256) void flash_attn_combine_wave_kernel(const floa
         }
     }
     const int e0 = b * 256 + e;
-    *reinterpret_cast<float4 *>(out + (size_t)t * E + e0) = float4{acc[0], acc[1], acc[2], acc[3]};
-    if (want_q8k) {
+    const bool ok = e0 < E;
+    if (ok) *reinterpret_cast<float4 *>(out + (size_t)t * E + e0) = float4{acc[0], acc[1], acc[2], acc[3]};
+    if (want_q8k && ok) {                                        // (Q8_K: whole blocks only, so ok is wave-uniform here)
         uint32_t packed; int bs; float dq;
         wave_quant_q8k(acc, lane, packed, bs, dq);
         *reinterpret_cast<uint32_t *>(q.qs + (size_t)t * E + e0) = packed;
@@ -931,8 +937,8 @@ __global__ __launch_bounds__(256) void flash_attn_combine_wave_kernel(const floa
     if (want_q80) {
         uint32_t packed; float dd;
         wave_quant_q80(acc, packed, dd);
-        *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)t * E + e0) = packed;
-        if ((lane & 7) == 0) q.d0[(size_t)t * (E >> 5) + b * 8 + (lane >> 3)] = f2h(dd);
+        if (ok) *reinterpret_cast<uint32_t *>(q.qs0 + (size_t)t * E + e0) = packed;
+        if (ok && (lane & 7) == 0) q.d0[(size_t)t * (E >> 5) + b * 8 + (lane >> 3)] = f2h(dd);
     }
 }
 
@@ -941,7 +947,7 @@ size_t flash_attn_workspace_floats(int T, int H, int D, int splits) { return (si
 
 hipError_t launch_flash_attn_combine(const AttnArgs &a, int splits, hipStream_t st) {
     if (a.D != 64 && a.D != 128) return hipErrorInvalidValue;
-    const int nblk = (a.H * a.D) >> 8;
+    const int nblk = (a.H * a.D + 255) >> 8;          // (the last block partial where H * D ends inside it)
     ActQuant qq;
     if (a.out_q) qq = *a.out_q;
     static const bool wave_off = getenv("MI355_ATTN_COMBINE_WAVE") && getenv("MI355_ATTN_COMBINE_WAVE")[0] == '0';
@@ -1136,7 +1142,7 @@ hipError_t launch_flash_attn(const AttnArgs &a, hipStream_t st) {
     FA_CASE(64, 3) FA_CASE(64, 5) FA_CASE(64, 6) FA_CASE(64, 7)
 #undef FA_CASE
     if (e != hipSuccess) return e;
-    const int nblk = (a.H * a.D) >> 8;
+    const int nblk = (a.H * a.D + 255) >> 8;          // (the last block partial where H * D ends inside it)
     ActQuant qq;
     if (a.out_q) qq = *a.out_q;
     hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, a.T), dim3(256), (size_t)(256 / a.D) * a.splits * 4, st, a.part, a.out, a.H, a.D, a.splits,

@@ -422,6 +422,19 @@ struct ActBufs {
     }
     bool ok() const { return qs.p && d.p && bs.p && qs0.p && d0.p; }
 };
+// The quantiser hooks give the planes one row more than they ask for, filled with a pattern first and checked afterwards: a kernel that walks past the end
+// of a row (its partial last 256-group) or of the last row lands there.
+const int Q80_GUARD = 0xA5;
+bool q80_guard_set(ActBufs &ab, size_t n, size_t rows) {
+    return hipMemset(ab.q.qs0 + rows * n, Q80_GUARD, n) == hipSuccess && hipMemset(ab.q.d0 + rows * (n / 32), Q80_GUARD, (n / 32) * 2) == hipSuccess;
+}
+bool q80_guard_intact(ActBufs &ab, size_t n, size_t rows) {
+    std::vector<uint8_t> g(n + (n / 32) * 2);
+    if (hipMemcpy(g.data(), ab.q.qs0 + rows * n, n, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (hipMemcpy(g.data() + n, ab.q.d0 + rows * (n / 32), (n / 32) * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (uint8_t b : g) if (b != Q80_GUARD) return false;
+    return true;
+}
 int hip_fail(hipError_t e, const char *what) {
     fail(std::string(what) + ": " + hipGetErrorString(e));
     return MI355_ERR_HIP;
@@ -497,23 +510,58 @@ extern "C" {
 
 int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n, int64_t rows, void *out_blocks) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if ((act_type != MI355_TYPE_Q8_K && act_type != MI355_TYPE_Q8_0) || n % 256) { fail("bad args"); return MI355_ERR_ARG; }
+    // Q8_0: any whole number of 32-element blocks; a Q8_K block is 256 elements
+    if ((act_type != MI355_TYPE_Q8_K && act_type != MI355_TYPE_Q8_0) || n <= 0 || rows <= 0 || n % (act_type == MI355_TYPE_Q8_K ? 256 : 32)) { fail("bad args"); return MI355_ERR_ARG; }
     DevBuf dx((size_t)n * rows * 4);
-    ActBufs ab((size_t)n, (size_t)rows);
+    ActBufs ab((size_t)n, (size_t)rows + 1);
     const size_t ob = act_type == MI355_TYPE_Q8_K ? (size_t)(n / 256) * 292 * rows : (size_t)(n / 32) * 34 * rows;
     DevBuf dout(ob);
-    if (!dx.up(x, (size_t)n * rows * 4) || !ab.ok() || !dout.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    if (!dx.up(x, (size_t)n * rows * 4) || !ab.ok() || !dout.p || !q80_guard_set(ab, (size_t)n, (size_t)rows)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
     hipError_t e = launch_quantize(dx.as<float>(), (int)n, (int)rows, ab.q, act_type == MI355_TYPE_Q8_K, act_type == MI355_TYPE_Q8_0, nullptr);
     if (e == hipSuccess) e = act_type == MI355_TYPE_Q8_K ? launch_pack_q8k_blocks(ab.q, (int)n, (int)rows, dout.as<uint8_t>(), nullptr)
                                                          : launch_pack_q80_blocks(ab.q, (int)n, (int)rows, dout.as<uint8_t>(), nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "quantize_act");
+    if (act_type == MI355_TYPE_Q8_0 && !q80_guard_intact(ab, (size_t)n, (size_t)rows)) { fail("quantize_act: the quantiser wrote past the last row"); return MI355_ERR_HIP; }
     return dout.down(out_blocks, ob) ? MI355_OK : MI355_ERR_HIP;
+}
+
+// RMSNorm * weight and the Q8_0 quantisation of its rows in one launch, as a layer's norm_quant step runs it: the per-row kernel, from 32 rows on the wide
+// prompt-batch one.  out_blocks: T rows of n / 32 ggml block_q8_0; y_f32 (optional): the f32 rows the blocks were made from.  n: any multiple of 32.
+int mi355_op_rms_norm_quant(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y_f32, void *out_blocks) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!x || !w || !out_blocks || n <= 0 || T <= 0 || n % 32) { fail("bad args"); return MI355_ERR_ARG; }
+    DevBuf dx((size_t)n * T * 4), dw((size_t)n * 4), dy((size_t)n * T * 4), dout((size_t)(n / 32) * 34 * T);
+    ActBufs ab((size_t)n, (size_t)T + 1);
+    if (!dx.up(x, (size_t)n * T * 4) || !dw.up(w, (size_t)n * 4) || !dy.p || !dout.p || !ab.ok() || !q80_guard_set(ab, (size_t)n, (size_t)T)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_rmsnorm_quant(dx.as<float>(), dw.as<float>(), (int)n, (int)T, eps, y_f32 ? dy.as<float>() : nullptr, &ab.q, false, true, nullptr);
+    if (e == hipSuccess) e = launch_pack_q80_blocks(ab.q, (int)n, (int)T, dout.as<uint8_t>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "rms_norm_quant");
+    if (!q80_guard_intact(ab, (size_t)n, (size_t)T)) { fail("rms_norm_quant: the quantiser wrote past the last row"); return MI355_ERR_HIP; }
+    if (y_f32 && !dy.down(y_f32, (size_t)n * T * 4)) return MI355_ERR_HIP;
+    return dout.down(out_blocks, (size_t)(n / 32) * 34 * T) ? MI355_OK : MI355_ERR_HIP;
+}
+
+// silu(gate) * up and the Q8_0 quantisation of the result in one launch (a prompt batch's step between ffn_gate | ffn_up and ffn_down).  n: any multiple of 32.
+int mi355_op_swiglu_quant(const float *gate, const float *up, int64_t n, int64_t T, void *out_blocks) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!gate || !up || !out_blocks || n <= 0 || T <= 0 || n % 32) { fail("bad args"); return MI355_ERR_ARG; }
+    DevBuf dg((size_t)n * T * 4), du((size_t)n * T * 4), dout((size_t)(n / 32) * 34 * T);
+    ActBufs ab((size_t)n, (size_t)T + 1);
+    if (!dg.up(gate, (size_t)n * T * 4) || !du.up(up, (size_t)n * T * 4) || !dout.p || !ab.ok() || !q80_guard_set(ab, (size_t)n, (size_t)T)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_swiglu_quant(dg.as<float>(), du.as<float>(), (int)n, (int)T, ab.q, false, true, nullptr, nullptr, nullptr);
+    if (e == hipSuccess) e = launch_pack_q80_blocks(ab.q, (int)n, (int)T, dout.as<uint8_t>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "swiglu_quant");
+    if (!q80_guard_intact(ab, (size_t)n, (size_t)T)) { fail("swiglu_quant: the quantiser wrote past the last row"); return MI355_ERR_HIP; }
+    return dout.down(out_blocks, (size_t)(n / 32) * 34 * T) ? MI355_OK : MI355_ERR_HIP;
 }
 
 int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (nib32_has_min(type) || nib32_has_e8(type)) return op_ffn_gate_up_nib32(type, Wg, Wu, N, K, x, T, y);
+    // the 32-element formats: any whole number of blocks (the K-quants below: their plane sets, whole 256-blocks); f16 as two products and the SwiGLU pass
+    if (act_is_q80(type) || type == T_F16) return op_ffn_gate_up_nib32(type, Wg, Wu, N, K, x, T, y);
     const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
     const size_t pb = mmq_planes_bytes(type, N, (int)K);
     if (!grow || K % 256 || !pb || N % 32) { fail("bad type / K / N"); return MI355_ERR_ARG; }
@@ -538,27 +586,11 @@ int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N
 }  // extern "C"
 
 namespace {
-// Q8_0 planes of T rows of K (K % 32 == 0) where K is no multiple of 256, the unit the quantiser works in: the rows are padded with zeros to whole
-// 256-blocks, quantised, and the planes of the first K / 32 blocks of each row compacted - a Q8_0 block depends on its own 32 values only
-hipError_t quantize_q80_padded(const float *dx, int K, int T, const ActQuant &q) {
-    const int Kp = (K + 255) & ~255;
-    DevBuf xp((size_t)Kp * T * 4);
-    ActBufs abp((size_t)Kp, (size_t)T);
-    if (!xp.p || !abp.ok()) return hipErrorOutOfMemory;
-    hipError_t e = hipMemset(xp.p, 0, (size_t)Kp * T * 4);
-    if (e == hipSuccess) e = hipMemcpy2D(xp.p, (size_t)Kp * 4, dx, (size_t)K * 4, (size_t)K * 4, (size_t)T, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = launch_quantize(xp.as<float>(), Kp, T, abp.q, false, true, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy2D(q.qs0, (size_t)K, abp.q.qs0, (size_t)Kp, (size_t)K, (size_t)T, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy2D(q.d0, (size_t)(K / 32) * 2, abp.q.d0, (size_t)(Kp / 32) * 2, (size_t)(K / 32) * 2, (size_t)T, hipMemcpyDeviceToDevice);
-    return e;
-}
-
 int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y, int32_t *isum, int32_t *msum) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    // whole 256-blocks, as the models' hidden sizes are; Q4_1 / Q5_1 / MXFP4 (32-element blocks) take any whole number of blocks
-    if (!grow || K <= 0 || ((nib32_has_min(type) || nib32_has_e8(type)) ? K % 32 : K % 256)) { fail("bad type / K"); return MI355_ERR_ARG; }
+    // the K-quants and IQ4_XS: whole 256-blocks; the 32-element formats and f16 take any whole number of 32-element blocks
+    if (!grow || K <= 0 || ((act_is_q80(type) || type == T_F16) ? K % 32 : K % 256)) { fail("bad type / K"); return MI355_ERR_ARG; }
     DevBuf wsrc(grow * N), wdev(drow * N), dx((size_t)K * T * 4), dy((size_t)N * T * 4), dres(resid ? (size_t)N * T * 4 : 16);
     ActBufs ab((size_t)K, (size_t)T);
     if (!wsrc.up(W, grow * N) || !wdev.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !ab.ok() || !dres.p || (resid && !dres.up(resid, (size_t)N * T * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
@@ -570,8 +602,7 @@ int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x
         fail("resid: only the Q8_0 prompt kernel's launches take one here"); return MI355_ERR_ARG;
     }
     if (quant) {
-        if (K % 256) e = quantize_q80_padded(dx.as<float>(), (int)K, (int)T, ab.q);
-        else e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, !act_is_q80(type), act_is_q80(type), nullptr);
+        e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, !act_is_q80(type), act_is_q80(type), nullptr);
         if (e != hipSuccess) return hip_fail(e, "quantize");
         if (mmq_q80_applicable(type, (int)K, (int)T)) {
             e = launch_mmq_q80(wdev.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, rs, nullptr);
@@ -682,7 +713,7 @@ int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x
 // and the SwiGLU pass ("mmq_planes" 1, T >= 32), else the mat-vec with SwiGLU in its epilogue in chunks of 16, 8, 4, 2, 1 tokens
 int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) {
     const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    if (!grow || K % 256) { fail("bad type / K"); return MI355_ERR_ARG; }
+    if (!grow || K <= 0 || K % 32 || N <= 0 || T <= 0) { fail("bad type / K"); return MI355_ERR_ARG; }
     DevBuf wsrc(grow * N), wg(drow * N), wu(drow * N), dx((size_t)K * T * 4), dy((size_t)N * T * 4), du((size_t)N * T * 4);
     ActBufs ab((size_t)K, (size_t)T);
     if (!wsrc.p || !wg.p || !wu.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !du.p || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
@@ -692,9 +723,27 @@ int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N
         e = launch_repack_rows(type, wsrc.as<uint8_t>(), (i ? wu : wg).as<uint8_t>(), K, N, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
+    if (type == T_F16) {                                          // (Context::ffn_dense_gate_up's float branch: two products, then SwiGLU)
+        for (int i = 0; i < 2 && e == hipSuccess; i++) {
+            const uint8_t *w = (i ? wu : wg).as<uint8_t>();
+            float *o = (i ? du : dy).as<float>();
+            if (mmf16_applicable(type, (int)N, (int)K, (int)T, w, dx.p, o) && (N & 3) == 0) e = launch_mmf16(w, (int)N, (int)K, dx.as<float>(), (int)T, o, (int)N, nullptr, nullptr);
+            else e = launch_mmv_float(type, w, (int)N, (int)K, dx.as<float>(), (int)T, o, (int)N, nullptr, nullptr);
+        }
+        if (e == hipSuccess) e = launch_swiglu(dy.as<float>(), du.as<float>(), dy.as<float>(), N * T, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) return hip_fail(e, "ffn_gate_up (f16)");
+        return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
+    }
     if (e == hipSuccess) e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, false, true, nullptr);
     if (e != hipSuccess) return hip_fail(e, "ffn_gate_up (set-up)");
-    if (g_op_mmq_planes && mmq_q80_applicable(T_Q8_0, (int)K, (int)T)) {
+    if (type == T_Q8_0 && mmq_q80_applicable(type, (int)K, (int)T)) {      // the prompt kernel on the weights themselves
+        e = launch_mmq_q80(wg.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, nullptr, nullptr);
+        if (e == hipSuccess) e = launch_mmq_q80(wu.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, du.as<float>(), (int)N, nullptr, nullptr);
+        if (e == hipSuccess) e = launch_swiglu(dy.as<float>(), du.as<float>(), dy.as<float>(), N * T, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    } else
+    if (type != T_Q8_0 && g_op_mmq_planes && mmq_q80_applicable(T_Q8_0, (int)K, (int)T)) {
         const size_t cb = mmq_q80_copy_bytes(type, N, (int)K), crow = mmq_q80_copy_row_bytes(type, (int)K);
         DevBuf cg(cb), cu(cb);
         if (!cg.p || !cu.p) return MI355_ERR_OOM;
@@ -733,6 +782,26 @@ int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const fl
 int mi355_op_mul_mat_add(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y) {
     if (!resid) { fail("mul_mat_add: resid is null"); return MI355_ERR_ARG; }
     return op_mul_mat(type, W, N, K, x, T, resid, y, nullptr, nullptr);
+}
+
+// One token's mat-vec with the activation made in the launch's prologue, as a decode step's launches take it: norm_w set - RMSNorm(x) * norm_w, then Q8_0
+// (fuse mode 1: Q | K | V, ffn_gate | ffn_up, the head); norm_w null - Q8_0 of x (mode 2: ffn_down).  The 32-element weight formats, K any multiple of 32 up
+// to 8192.  The result has the bits of the quantiser's launch followed by mi355_op_mul_mat's.
+int mi355_op_mul_mat_fused(int32_t type, const void *W, int64_t N, int64_t K, const float *x, const float *norm_w, float eps, float *y) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
+    if (!act_is_q80(type) || !grow || !W || !x || !y || N <= 0 || K <= 0 || K % 32 || K > 8192) { fail("bad type / K"); return MI355_ERR_ARG; }
+    DevBuf wsrc(grow * N), wdev(drow * N), dx((size_t)K * 4), dw((size_t)K * 4), dy((size_t)N * 4);
+    if (!wsrc.up(W, grow * N) || !wdev.p || !dx.up(x, (size_t)K * 4) || !dw.p || !dy.p || (norm_w && !dw.up(norm_w, (size_t)K * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_repack_rows(type, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, N, nullptr);
+    MMVQArgs a{};
+    a.n_seg = 1; a.K = (int)K; a.T = 1; a.epi = EPI_STORE;
+    a.seg[0].W = wdev.as<uint8_t>(); a.seg[0].out = dy.as<float>(); a.seg[0].type = type; a.seg[0].n_rows = (int)N; a.seg[0].ld_out = (int)N; a.seg[0].row_bytes = drow;
+    a.fuse_mode = norm_w ? 1 : 2; a.nx = dx.as<float>(); a.nw = norm_w ? dw.as<float>() : nullptr; a.neps = eps;
+    if (e == hipSuccess) e = launch_mmvq(a, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "mul_mat_fused");
+    return dy.down(y, (size_t)N * 4) ? MI355_OK : MI355_ERR_HIP;
 }
 
 int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out) {
@@ -826,7 +895,7 @@ int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const int64_t *N,
 
 int mi355_op_rms_norm_mul(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n % 256) { fail("n must be a multiple of 256"); return MI355_ERR_ARG; }
+    if (n <= 0 || T <= 0 || n % 32) { fail("n must be a multiple of 32"); return MI355_ERR_ARG; }
     DevBuf dx((size_t)n * T * 4), dw((size_t)n * 4), dy((size_t)n * T * 4);
     if (!dx.up(x, (size_t)n * T * 4) || !dw.up(w, (size_t)n * 4) || !dy.p) return MI355_ERR_OOM;
     hipError_t e = launch_rmsnorm_quant(dx.as<float>(), dw.as<float>(), (int)n, (int)T, eps, dy.as<float>(), nullptr, false, false, nullptr);

@@ -573,17 +573,24 @@ __device__ __forceinline__ ActLds stage_act(const MMVQArgs &a, uint8_t *smem) {
         const int sweep = nthr * 4;                      // elements covered by one sweep of the workgroup
         constexpr int MAXJ = 8192 / (BS * 4);            // K <= 8192 (host-checked)
         float4 xv[MAXJ];
-        const int nj = K / sweep;                        // K % sweep == 0 host-checked
+        // K is any whole number of 32-element blocks (host-checked; Q8_K wants whole 256-groups): a wave whose 256-group ends past the row - the row's
+        // partial last group, or the groups of a last sweep the row does not fill - loads zeros for the lanes without data and stores nothing for them.  A
+        // block of 32 is 8 lanes, so a lane group of 8 is all data or none, as in act.hip's quantisers.
+        const int nblk = (K + 255) >> 8;
+        const int nj = (nblk + nwv - 1) / nwv;           // <= MAXJ for K <= 8192
 #pragma unroll
         for (int j = 0; j < MAXJ; j++)
-            if (j < nj) xv[j] = *reinterpret_cast<const float4 *>(a.nx + j * sweep + tid * 4);
+            if (j < nj) {
+                const int e = j * sweep + tid * 4;
+                xv[j] = e < K ? *reinterpret_cast<const float4 *>(a.nx + e) : float4{0.0f, 0.0f, 0.0f, 0.0f};
+            }
         float scale = 1.0f;
         if (a.fuse_mode == 1) {
             double s = 0.0;
 #pragma unroll
             for (int j = 0; j < MAXJ; j++)
                 if (j < nj) {
-                    const float4 v = xv[j];
+                    const float4 v = xv[j];              // (a lane without data adds + 0.0: the sum keeps its bits)
                     s += (double)(v.x * v.x); s += (double)(v.y * v.y); s += (double)(v.z * v.z); s += (double)(v.w * v.w);
                 }
             s = wave_sum(s);
@@ -599,8 +606,9 @@ __device__ __forceinline__ ActLds stage_act(const MMVQArgs &a, uint8_t *smem) {
             if (j >= nj) continue;
             const int b = wave + nwv * j;                 // 256-block handled by this wave
             const int e0 = b * 256 + lane * 4;
+            const bool ok = e0 < K;
             float4 v = xv[j];
-            if (a.fuse_mode == 1) {
+            if (a.fuse_mode == 1 && ok) {
                 const float4 ww = *reinterpret_cast<const float4 *>(a.nw + e0);
                 v.x = (v.x * scale) * ww.x; v.y = (v.y * scale) * ww.y; v.z = (v.z * scale) * ww.z; v.w = (v.w * scale) * ww.w;
             }
@@ -608,15 +616,15 @@ __device__ __forceinline__ ActLds stage_act(const MMVQArgs &a, uint8_t *smem) {
             if (a.need_q8k) {
                 uint32_t packed; int bsum; float dq;
                 wave_quant_q8k(vv, lane, packed, bsum, dq);
-                *reinterpret_cast<uint32_t *>(qs + e0) = packed;
-                if ((lane & 3) == 0) bs[b * 16 + (lane >> 2)] = (int16_t)bsum;
-                if (lane == 0) d[b] = dq;
+                if (ok) *reinterpret_cast<uint32_t *>(qs + e0) = packed;
+                if (ok && (lane & 3) == 0) bs[b * 16 + (lane >> 2)] = (int16_t)bsum;
+                if (ok && lane == 0) d[b] = dq;
             }
             if (a.need_q80) {
                 uint32_t packed; float dd;
                 wave_quant_q80(vv, packed, dd);
-                *reinterpret_cast<uint32_t *>(qs0 + e0) = packed;
-                if ((lane & 7) == 0) d0[b * 8 + (lane >> 3)] = f2h(dd);
+                if (ok) *reinterpret_cast<uint32_t *>(qs0 + e0) = packed;
+                if (ok && (lane & 7) == 0) d0[b * 8 + (lane >> 3)] = f2h(dd);
             }
         }
     }
@@ -982,9 +990,10 @@ hipError_t launch_mmvq(MMVQArgs a, hipStream_t st) {
     // big launches use 1024-thread workgroups (one activation staging per 16 waves)
     int bs = ((long)total_pairs * nck >= (long)g_num_cu * 32) ? 1024 : 256;
     if (a.fuse_mode != 0) {
-        if (a.T != 1 || (a.K % (bs * 4)) != 0 || a.K / (bs * 4) > 8) {
-            if (bs == 1024 && a.T == 1 && (a.K % 1024) == 0 && a.K / 1024 <= 8) bs = 256; else return hipErrorInvalidValue;
-        }
+        // the prologue holds the row in registers (stage_act): K <= 8192, a whole number of 32-element blocks, whole 256-groups where Q8_K codes are wanted.
+        // A row that is not whole sweeps of 1024 threads takes 256: the sum of squares then has the order of norm_quant_kernel's, tail included
+        if (a.T != 1 || a.K > 8192 || (a.K & 31) || ((a.K & 255) && a.need_q8k)) return hipErrorInvalidValue;
+        if (bs == 1024 && (a.K % 4096) != 0) bs = 256;
     }
     const int nw = bs / 64;
     const int ppb = nw / nck;                    // pairs per workgroup

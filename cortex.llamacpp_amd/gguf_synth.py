@@ -339,6 +339,15 @@ CONFIGS = {
                                         n_ff_exp=768),
     "tiny-qwen3moe-235b-2l": LlamaConfig("tiny-qwen3moe-235b-2l", 4096, 2, 64, 4, 12288, 512, 1e6, 1e-6, 1024, 128, 8, arch="qwen3moe", n_head_dim=128,
                                          n_ff_exp=1536),
+    # hidden sizes that are whole 32-element blocks but no multiple of 256: a K-quant mix falls back to 32-element types there (FALLBACK_32), tensor by tensor.
+    # Qwen2.5-0.5B (896 = 3.5 x 256, 14 / 2 heads of 64, ffn_down rows of 4864 = 19 x 256 keep their K-quants) and SmolLM2-135M (576, 9 / 3 heads of 64)
+    "qwen2.5-0.5b": LlamaConfig("Qwen2.5-0.5B-Instruct", 896, 24, 14, 2, 4864, 151936, 1e6, 1e-6, 32768, arch="qwen2", qkv_bias=True, tied_output=True),
+    "smollm2-135m": LlamaConfig("SmolLM2-135M-Instruct", 576, 30, 9, 3, 1536, 49152, 100000.0, 1e-5, 8192, tied_output=True),
+    "tiny-w896-2l": LlamaConfig("tiny-w896-2l", 896, 2, 14, 2, 4864, 512, 1e6, 1e-6, 1024, arch="qwen2", qkv_bias=True, tied_output=True),
+    "tiny-w896-2l-untied": LlamaConfig("tiny-w896-2l-untied", 896, 2, 14, 2, 4864, 512, 1e6, 1e-6, 1024, arch="qwen2", qkv_bias=True),
+    "tiny-w576-2l": LlamaConfig("tiny-w576-2l", 576, 2, 9, 3, 1536, 512, 100000.0, 1e-5, 1024, tied_output=True),
+    # both n_embd (320) and n_ff (608) end inside a 256-group; five query heads on one kv head
+    "tiny-w320": LlamaConfig("tiny-w320", 320, 2, 5, 1, 608, 512, 1e6, 1e-6, 1024, arch="qwen2", qkv_bias=True),
 }
 
 FTYPE_ID = {"f16": 1, "bf16": 32, "q4_0": 2, "q4_1": 3, "q5_0": 8, "q5_1": 9, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18, "mxfp4": 38, "mxfp4_moe": 38}
@@ -357,8 +366,23 @@ def _row_len(cfg: LlamaConfig, kind: str) -> int:
     return cfg.n_embd
 
 
+# llama-quantize's fallback for a tensor whose rows are not a whole number of 256-element super-blocks: the 32-element type nearest in bits per weight.
+# (Upstream's source is not available where this was written: the table is restated from its documented behaviour - the message "tensor cols not divisible
+# by 256, required for q4_K - using fallback quantization q5_0" - and cannot be pinned against it here.)
+FALLBACK_32 = {Q4_K: Q5_0, Q5_K: Q5_1, Q6_K: Q8_0, Q2_K: IQ4_NL, Q3_K: IQ4_NL, IQ4_XS: IQ4_NL}
+
+
 def tensor_type(cfg: LlamaConfig, ftype: str, kind: str, il: int) -> int:
-    """ggml type of a 2-D weight per llama-quantize's `*_K_M` mix."""
+    """ggml type of a 2-D weight: the mix's choice (mix_tensor_type), or its 32-element fallback where the tensor's rows are not a multiple of 256 - output and a
+    tied token_embd included.  No config with such a row existed before the fallback did, so every older file is written byte for byte as it was."""
+    t = mix_tensor_type(cfg, ftype, kind, il)
+    if BLOCK_ELEMS[t] == 256 and _row_len(cfg, kind) % 256:
+        return FALLBACK_32[t]
+    return t
+
+
+def mix_tensor_type(cfg: LlamaConfig, ftype: str, kind: str, il: int) -> int:
+    """ggml type of a 2-D weight per llama-quantize's `*_K_M` mix, before the row-length fallback."""
     if ftype == "f16":
         return F16
     if ftype == "bf16":                                      # LLAMA_FTYPE_MOSTLY_BF16: every 2-D weight

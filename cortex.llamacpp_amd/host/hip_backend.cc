@@ -209,6 +209,8 @@ std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, 
                   "). Make sure that you use the correct mmproj file.";
             return nullptr;
         }
+        // (image rows enter the model as embeddings: untested at a hidden size that is not a whole number of 256-blocks, so refused by name)
+        if (model->hp.n_embd % 256) { err = "mmproj: a multimodal projector beside a model whose embedding_length (" + std::to_string(model->hp.n_embd) + ") is not a multiple of 256 is not supported"; return nullptr; }
         // LLaVA-1.6 (an image grid: up to five encoded images a picture) needs more room than LLaVA-1.5; the reference tells the two apart by the model's
         // file name (IsLlava_1_6, :170-175, :195) - here the projector file's own image grid counts as well
         const bool v16 = path.find("llava-v1.6") != std::string::npos || clip->max_image_rows() > clip->n_patches();

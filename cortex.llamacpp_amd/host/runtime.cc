@@ -149,8 +149,9 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
         hp.yarn_hi = hi < (float)(hp.n_rot - 1) ? hi : (float)(hp.n_rot - 1);
     } else if (scaling != "none" && scaling != "linear") { err = "unsupported rope.scaling.type " + scaling; status = -102; return nullptr; }
     if (hp.head_dim != 64 && hp.head_dim != 128) { err = "unsupported head_dim " + std::to_string(hp.head_dim); status = -102; return nullptr; }
-    if (hp.n_embd % 256) { err = "n_embd must be a multiple of 256"; status = -102; return nullptr; }
-    if (hp.qk_norm && ((int64_t)hp.n_head * hp.head_dim) % 256) { err = "the attention width (head_count x key_length) must be a multiple of 256"; status = -102; return nullptr; }
+    // Row lengths - n_embd, the attention width H * D, n_ff - are whole numbers of 32-element blocks; what each TENSOR's type makes of its own row length is
+    // checked tensor by tensor below (want), and the graphs that still want whole 256-blocks say so by name once the widths are known (widths_256).
+    if (hp.n_embd % 32) { err = "embedding_length (" + std::to_string(hp.n_embd) + ") must be a multiple of 32"; status = -102; return nullptr; }
     // ---- row split: this rank's share of the heads and of the feed-forward width
     const int P = tp_size > 1 ? tp_size : 1, R = tp_size > 1 ? tp_rank : 0;
     hp.n_head_full = hp.n_head; hp.n_head_kv_full = hp.n_head_kv; hp.n_ff_full = hp.n_ff;
@@ -207,7 +208,9 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
             const bool expert = name.size() > 12 && (name.compare(name.size() - 12, 12, "_exps.weight") == 0 || name.find("ffn_gate_inp") != std::string::npos);
             const char *why = ti->n_dims == 1 ? "norm and bias vectors must be f32" : expert ? "bf16 expert tensors are not supported" :
                               hp.encoder ? "the encoder graph has no bf16 kernels" : P > 1 ? "a row split (split_mode \"row\" / tp_size > 1) of bf16 tensors is not supported: load the file on one device" :
-                              (ti->ne[0] % 8) ? "bf16 rows must hold a multiple of 8 weights" : nullptr;
+                              (ti->ne[0] % 8) ? "bf16 rows must hold a multiple of 8 weights" :
+                              // (the bf16 weight stream has a tail form, the matrix-core prompt path is untested at such a width: refused rather than run unchecked)
+                              (hp.n_embd % 256) ? "bf16 tensors in a file whose embedding_length is not a multiple of 256 are not supported" : nullptr;
             if (why) { err = "tensor " + name + " has type bf16: " + why; fail = true; return; }
         }
         dst.name = name;
@@ -215,7 +218,13 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
         dst.K = ti->ne[0];
         dst.N = ti->ne[1];
         dst.n_expert = ti->ne[2];
-        if (ggml_block_elems(dst.type) > 1 && dst.K % ggml_block_elems(dst.type)) { err = "tensor " + name + ": row length not a block multiple"; fail = true; return; }
+        // a row is a whole number of its type's blocks: 256 elements for the K-quants and IQ4_XS, 32 for Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL / MXFP4
+        // (llama-quantize writes a tensor whose rows are no multiple of 256 in one of the latter)
+        const int64_t row_unit = std::max<int64_t>(ggml_block_elems(dst.type), 1);
+        if (dst.K % row_unit) {
+            err = "tensor " + name + " (" + ggml_type_name(dst.type) + "): its row length " + std::to_string(dst.K) + " is not a whole number of " + std::to_string(row_unit) + "-element blocks";
+            fail = true; return;
+        }
         const size_t full_row = ggml_row_bytes(dst.type, dst.K);
         Plan pl{ti, &dst, total, 0, full_row, full_row, ti->n_dims == 1 ? 1 : dst.N * dst.n_expert, (size_t)ti->bytes, cparts > 1};
         if (P > 1 && split != SPLIT_NONE) {
@@ -391,6 +400,16 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
     hp.n_ff = (int)(hp.n_expert ? m->layers[0].gate_exps.N : m->layers[0].gate.N);     // this rank's width under a row split
     if (!hp.n_ff_full) hp.n_ff_full = hp.n_ff * P;
     hp.n_vocab_local = !m->output.name.empty() ? (int)m->output.N : hp.n_vocab;      // (planned, not uploaded yet)
+    {
+        // Where whole 256-blocks are still wanted: graphs whose kernels have no general form to fall back to at such a width.  The dense llama / qwen2 / qwen3
+        // graph runs every width that is a multiple of 32 (the quantisers, the generic mat-vec and the Q8_0 prompt kernel take a row that ends inside a 256-group).
+        const int64_t aw = (int64_t)hp.n_head_full * hp.head_dim;
+        const bool odd = (hp.n_embd % 256) || (aw % 256) || (hp.n_ff_full % 256);
+        const std::string widths = "embedding_length " + std::to_string(hp.n_embd) + ", attention width " + std::to_string(aw) + ", feed-forward width " + std::to_string(hp.n_ff_full);
+        const char *what = !odd ? nullptr : hp.n_expert > 0 ? "mixture-of-experts files (the expert gather and the expert mat-vecs work on whole 256-blocks)" :
+                           hp.encoder ? "encoder files" : P > 1 ? "a row split (split_mode \"row\" / tp_size > 1)" : nullptr;
+        if (what) { err = std::string(what) + " need widths that are multiples of 256 (" + widths + ")"; status = -102; return nullptr; }
+    }
 
     // (the file has been validated without touching the device: a malformed file fails the same way with and without a GPU)
     if (hipSetDevice(main_gpu) != hipSuccess) { err = "hipSetDevice failed"; status = -100; return nullptr; }
@@ -630,8 +649,8 @@ static void alloc_actq(ActQuant &q, size_t K, size_t T, bool k, bool z, std::vec
     };
     if (k) {
         q.qs = (int8_t *)al(T * K);
-        q.d = (float *)al(T * (K / 256) * 4);
-        q.bsums = (int16_t *)al(T * (K / 16) * 2);
+        q.d = (float *)al(T * ((K + 255) / 256) * 4);         // (rounded up: a width that ends inside a 256-group never shrinks a plane)
+        q.bsums = (int16_t *)al(T * ((K + 15) / 16) * 2);
     }
     if (z) {
         q.qs0 = (int8_t *)al(T * K);
@@ -980,7 +999,9 @@ static MMVQArgs single_token_desc(int n_seg, int K, int epi, int fuse, const flo
 // up to 3 quantised weight tensors sharing one activation (fused Q/K/V), or one tensor with an epilogue
 // (any whole number of super-blocks: the register-ring kernel's prologue stops at the row's end inside its last pass; the weight stream wants K % 1024 == 0
 // and leaves the other hidden sizes - Qwen2-7B's 3584, Llama-30B's 6656 - to the register ring)
-static bool can_fuse(int K, int T) { return T == 1 && K <= 8192 && (K & 255) == 0; }
+// (a width that is no multiple of 256 - whole 32-element blocks, so every quantised tensor over it takes Q8_0 activations - goes to the generic mat-vec,
+// whose prologue takes a row that ends inside a 256-group: a step of such a file has as many launches as any other on that path)
+static bool can_fuse(int K, int T) { return T == 1 && K <= 8192 && (K & 31) == 0; }
 
 static hipError_t mmvq_tokens(MMVQSeg *segs, int n_seg, int K, int T, int epi, const ActQuant &aq, hipStream_t st, const Fuse &fz = Fuse()) {
     for (int t0 = 0; t0 < T;) {
@@ -1637,7 +1658,7 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
         if (pl) prep_written(aq_e_, E, T);
         prof_mark("norm_quant");
     }
-    const bool down_q = type_is_quant(L.down.type) && (FF % 256) == 0;     // SwiGLU and the quantisation for ffn_down can share a pass
+    const bool down_q = type_is_quant(L.down.type) && (FF % 32) == 0;      // SwiGLU and the quantisation for ffn_down can share a pass
     const bool ffn_mmq = (mmq_q80_applicable(L.gate.type, E, T) && mmq_q80_applicable(L.up.type, E, T)) ||
                          (mmq_applicable(L.gate.type, E, T) && mmq_applicable(L.up.type, E, T)) ||
                          (mmq_ksplit_applicable(L.gate.type, E, T) && mmq_ksplit_applicable(L.up.type, E, T)) ||
@@ -1692,7 +1713,9 @@ hipError_t Context::ffn_down(int il, const Step &st, bool quantised, int *n_matv
     const int epi = st.resid ? EPI_ADD : EPI_STORE;
     // quantise inside the down-projection's prologue (once per CU, overlapped with its first weight loads)
     // (the widths listed are the ones the register-ring and weight-stream kernels take; the generic mat-vec's fused prologue would refuse others)
-    const bool fuse_down = st.fuse_down_env && T == 1 && type_is_quant(L.down.type) && (FF % 256) == 0 && mmvq_fast_kb_ok((FF + 2047) / 2048);
+    // (... and an n_ff that ends inside a 256-group: the generic mat-vec's prologue, Q8_0 activations)
+    const bool fuse_down = st.fuse_down_env && T == 1 && type_is_quant(L.down.type) &&
+                           (((FF % 256) == 0 && mmvq_fast_kb_ok((FF + 2047) / 2048)) || ((FF % 256) != 0 && (FF % 32) == 0 && FF <= 8192 && act_is_q80(L.down.type)));
     if (fuse_down && !st.tp && L.down_lo.valid() && L.down_hi.valid()) {
         // the column halves of ffn_down, each quantising its half of the SwiGLU output in its prologue: x += W_lo a_lo; x += W_hi a_hi
         const int Kh = (int)L.down_lo.K;

@@ -197,14 +197,20 @@ MI355_API int32_t mi355_debug_layer_out(mi355_context *ctx, int32_t il, float *d
  * Host-buffer wrappers around the individual HIP kernels, for parity tests and rocprof.
  * Each copies inputs to the device, runs the same kernel the decode graph uses, copies back. */
 
-/* quantize_row_q8_K / quantize_row_q8_0 (activation side).  out receives ggml-layout blocks. */
+/* quantize_row_q8_K / quantize_row_q8_0 (activation side).  out receives ggml-layout blocks.  Q8_K: n_per_row % 256 == 0; Q8_0: any multiple of 32 (a row
+ * may end inside a 256-group).  From 32 rows on the prompt-batch form of the kernel runs. */
 MI355_API int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n_per_row, int64_t n_rows, void *out_blocks);
+/* RMSNorm(x) * w and the Q8_0 quantisation of the result in one launch, as a layer's norm step runs it (n any multiple of 32; from T = 32 on the prompt-batch
+ * form).  out_blocks: T rows of n / 32 block_q8_0; y_f32 (nullable): the f32 rows [T][n] the blocks were made from. */
+MI355_API int mi355_op_rms_norm_quant(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y_f32, void *out_blocks);
+/* silu(gate) * up and its Q8_0 quantisation in one launch (gate, up: [T][n], n any multiple of 32); out_blocks as above. */
+MI355_API int mi355_op_swiglu_quant(const float *gate, const float *up, int64_t n, int64_t T, void *out_blocks);
 /* y[T][N] = W[N][K] . x[T][K]; W is ggml-layout blocks of `type`.  isum/msum (nullable):
  * per (token, row, block) integer partial sums for bit-exact checks.  IQ4_XS (type 23, Q8_K activations): isum is the
  * super-block's sum over sub-blocks of (ls - 32) * sum(level * q8), msum is 0.  BF16 (type 30): the rows of x are rounded to bf16
  * (ggml's f32 -> bf16) and the model path's kernel runs: the matrix cores from 8 tokens on, else the bf16 weight stream.
- * Q4_1 / Q5_1 (types 3 / 7, Q8_0 activations): K may be any multiple of 32 (for the tests' one-block and odd-block-count shapes: the rows are padded to whole
- * 256-blocks for the quantiser and the planes compacted; a model's hidden sizes are multiples of 256); one token with K % 256 == 0 is quantised in the mat-vec's
+ * The 32-element formats (Q8_0, Q4_0, Q5_0, IQ4_NL, Q4_1, Q5_1, MXFP4: Q8_0 activations) and F16 take any K % 32 == 0, the other types K % 256 == 0.
+ * Q4_1 / Q5_1 (types 3 / 7): one token with K % 256 == 0 is quantised in the mat-vec's
  * prologue, the form the weight stream takes these types in; isum is the block's sum of q * a (q the unsigned code), msum the block's
  * sum of a - the block contributes (d * d8) * isum + m * (d8 * msum).  With "mmq_planes" 1 and T >= 32 the tensor's Q8_0-layout copy runs on the
  * matrix cores, in the form "mmq_q80_tiles" forces (1 | 2 | 4 token tiles per wave; 0: the launcher's choice).
@@ -215,6 +221,10 @@ MI355_API int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K
 /* Test hook: y = resid + W . x (resid, y: [T][N]) on the launches that take a residual in their epilogue through this entry point: the Q8_0 prompt kernel
  * (Q8_0 tensors, and the Q8_0-layout copies of Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4 tensors with "mmq_planes" 1), T >= 32; MI355_ERR_ARG otherwise. */
 MI355_API int mi355_op_mul_mat_add(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y);
+/* One token's mat-vec (a 32-element format, K % 32 == 0, K <= 8192) with the activation made in the launch's prologue, as a decode step's launches take it:
+ * norm_w set: RMSNorm(x) * norm_w, then Q8_0 (Q | K | V, ffn_gate | ffn_up, the head); norm_w null: Q8_0 of x (ffn_down).  y[N] has the bits of the
+ * quantiser's launch followed by mi355_op_mul_mat. */
+MI355_API int mi355_op_mul_mat_fused(int32_t type, const void *W, int64_t N, int64_t K, const float *x, const float *norm_w, float eps, float *y);
 /* ggml's f32 -> bf16 rounding as the bf16 kernels' activation pass does it (nearest, ties to even; NaN quieted; subnormals kept); n % 8 == 0 */
 MI355_API int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out);
 /* Up to three BF16 tensors W[s] ([N[s]][K] bf16 rows, K % 8 == 0; the matrix cores want K % 16 == 0) against the same T rows of x, as a decoder layer launches them:
@@ -228,8 +238,8 @@ MI355_API int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const i
 /* ffn_gate and ffn_up (one K-quant type or IQ4_XS, N rows each, N % 32 == 0) against the same T activation rows with SwiGLU in the
  * epilogue, as the prompt path launches them (mmq_planes2_swiglu_kernel): y[t][n] = silu(Wg[n] . x[t]) * (Wu[n] . x[t]).
  * Shapes too small for that launch are refused unless the debug option "mmq_tiles" = 4 forces the kernel.
- * Q4_1 / Q5_1 / MXFP4 (any N, K % 256 == 0) run as a layer of such a file does: T >= 32 with "mmq_planes" 1 through the two Q8_0-layout copies and the SwiGLU
- * pass, else the mat-vec with SwiGLU in its epilogue. */
+ * The 32-element formats (any N, K % 32 == 0) run as a layer of such a file does: T >= 32 on the Q8_0 prompt kernel (Q8_0 tensors directly, the others with
+ * "mmq_planes" 1 through their two Q8_0-layout copies) and the SwiGLU pass, else the mat-vec with SwiGLU in its epilogue.  F16: two products and the SwiGLU pass. */
 MI355_API int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y);
 MI355_API int mi355_op_rms_norm_mul(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y);
 MI355_API int mi355_op_rope(float *x, int32_t n_head, int32_t head_dim, int32_t n_rot, const int32_t *pos, int64_t T,
