@@ -87,7 +87,7 @@ __global__ void repack_nib32_kernel(const uint8_t *src, uint8_t *dst, int nblk, 
 }
 hipError_t launch_repack_rows(int type, const uint8_t *src, uint8_t *dst, int64_t K, int64_t n_rows, hipStream_t st) {
     const size_t drow = dev_row_bytes(type, K);
-    if (type == T_Q4_0 || type == T_Q5_0 || type == T_IQ4_NL || nib32_has_min(type) || nib32_has_e8(type)) {
+    if (type_has_q80_copy(type)) {
         const int nblk = (int)(K >> 5);
         for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
             const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);

@@ -248,7 +248,7 @@ size_t mmq_q80_copy_row_bytes(int type, int K) {
 }
 int mmq_q80_copy_form(int type) { return nib32_has_min(type) ? Q80_FORM_MINS : nib32_has_e8(type) ? Q80_FORM_E8 : Q80_FORM_F16; }
 size_t mmq_q80_copy_bytes(int type, int64_t n_rows, int K) {
-    if ((type != T_Q4_0 && type != T_Q5_0 && type != T_IQ4_NL && !nib32_has_min(type) && !nib32_has_e8(type)) || (K % 32) != 0 || K > 16384) return 0;
+    if (!type_has_q80_copy(type) || (K % 32) != 0 || K > 16384) return 0;
     return (size_t)n_rows * mmq_q80_copy_row_bytes(type, K);
 }
 hipError_t launch_expand_q80_copy(int type, const uint8_t *W, size_t row_bytes, int n_rows, int K, uint8_t *dst, hipStream_t st) {

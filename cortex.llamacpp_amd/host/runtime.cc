@@ -60,367 +60,16 @@ static RopeArgs layer_rope(const RopeArgs &ra, const LayerWeights &L, float eps)
     return r;
 }
 
-static bool type_supported(int t) {
-    return t == T_F32 || t == T_F16 || t == T_BF16 || type_is_quant(t);
-}
-
-Model *model_load(const std::string &path, int main_gpu, std::string &err, int &status, int prefill_planes, int tp_rank, int tp_size) {
-    status = 0;
-    std::unique_ptr<Model> m(new Model());
-    m->file.reset(new GGUFFile());
-    m->path = path;
-    err = m->file->open(path);
-    if (!err.empty()) { status = err.rfind("cannot", 0) == 0 ? -101 : -102; return nullptr; }
-    GGUFFile &f = *m->file;
-    HParams &hp = m->hp;
-    hp.arch = f.get_s("general.architecture", "");
-    if (hp.arch.empty()) { err = "general.architecture missing"; status = -102; return nullptr; }
-    // the graph built here is llm_build_llama's: "llama" files (Llama, Mistral, TinyLlama, Mixtral ... all carry that name), "qwen2"
-    // (the same op order with NEOX rope pairing and Q / K / V biases) and "qwen3" (llm_build_qwen3: qwen2's order without biases, a per-head RMSNorm of Q and K
-    // before the rope, the head size from attention.key_length - the attention width H * D need not be n_embd) and "qwen3moe" (llm_build_qwen3moe: qwen3's
-    // attention with build_moe_ffn's routed feed-forward - softmax gating, top-k, weights renormalised - and no shared expert).  Gemma, Phi-3, BERT-type
-    // encoders etc. are other graphs: refused, never run as llama.
-    // "nomic-bert" (the reference's embedding smoke model, Makefile:6) is the one encoder graph: llm_build_bert's NOMIC_BERT branches (run_layers_encoder)
-    if (hp.arch != "llama" && hp.arch != "qwen2" && hp.arch != "qwen3" && hp.arch != "qwen3moe" && hp.arch != "nomic-bert") { err = "unsupported general.architecture '" + hp.arch + "' (this backend builds the llama graph - llama, qwen2, qwen3, qwen3moe - and the nomic-bert encoder)"; status = -102; return nullptr; }
-    hp.encoder = hp.arch == "nomic-bert";
-    const bool qwen3moe = hp.arch == "qwen3moe";
-    hp.qk_norm = hp.arch == "qwen3" || qwen3moe;
-    const std::string a = hp.arch + ".";
-    hp.n_embd = (int)f.get_u(a + "embedding_length", 0);
-    hp.n_layer = (int)f.get_u(a + "block_count", 0);
-    hp.n_ff = (int)f.get_u(a + "feed_forward_length", 0);
-    hp.n_head = (int)f.get_u(a + "attention.head_count", 0);
-    hp.n_head_kv = (int)f.get_u(a + "attention.head_count_kv", (uint64_t)hp.n_head);
-    hp.eps = (float)f.get_f(a + (hp.encoder ? "attention.layer_norm_epsilon" : "attention.layer_norm_rms_epsilon"), hp.encoder ? 1e-12 : 1e-5);
-    hp.rope_base = (float)f.get_f(a + "rope.freq_base", 10000.0);
-    hp.n_expert = (int)f.get_u(a + "expert_count", 0);
-    hp.n_expert_used = (int)f.get_u(a + "expert_used_count", 0);
-    hp.n_ctx_train = (int)f.get_u(a + "context_length", 0);
-    hp.pooling_type = (int)f.get_u(a + "pooling_type", 0);
-    // qwen3moe: feed_forward_length is the width of a dense layer the file does not have; the experts' width is expert_feed_forward_length (optional: the
-    // tensors' own width stands when it is absent)
-    const std::string ff_key = qwen3moe ? "expert_feed_forward_length" : "feed_forward_length";
-    if (qwen3moe) hp.n_ff = (int)f.get_u(a + ff_key, 0);
-    if (qwen3moe && hp.n_expert <= 0) { err = "qwen3moe file without experts (expert_count missing or 0): dense feed-forward layers under the qwen3moe name are not supported"; status = -102; return nullptr; }
-    if (qwen3moe && (f.tensor("blk.0.ffn_gate.weight") || f.tensor("blk.0.ffn_up.weight") || f.tensor("blk.0.ffn_down.weight"))) {
-        err = "qwen3moe file with dense ffn_gate / ffn_up / ffn_down tensors: not supported (a qwen3moe layer is routed: ffn_gate_inp and *_exps)"; status = -102; return nullptr;
-    }
-    if (hp.n_embd <= 0 || hp.n_layer <= 0 || hp.n_head <= 0) { err = "missing hyper-parameters for arch " + hp.arch; status = -102; return nullptr; }
-    if (hp.n_layer > 1024 || hp.n_embd > (1 << 20) || hp.n_head > 4096) { err = "implausible hyper-parameters for arch " + hp.arch; status = -102; return nullptr; }
-    // the head counts size buffers and pick kernels: check them here, not at the first decode
-    if (hp.n_head_kv <= 0 || hp.n_head % hp.n_head_kv) { err = "attention.head_count_kv (" + std::to_string(hp.n_head_kv) + ") must be positive and divide attention.head_count (" + std::to_string(hp.n_head) + ")"; status = -102; return nullptr; }
-    {
-        const int ratio = hp.n_head / hp.n_head_kv;
-        // (1, 2, 4, 8 have the tuned single-launch decode attention and the matrix-core prompt attention; 3, 5, 6, 7 take the general split kernel)
-        if (ratio < 1 || ratio > 8) { err = "unsupported query / kv head ratio " + std::to_string(ratio) + " (the attention kernels are built for 1 .. 8)"; status = -102; return nullptr; }
-    }
-    // (qwen3 sets its head size itself: n_embd / n_head need not be whole)
-    if (!hp.qk_norm && hp.n_embd % hp.n_head) { err = "embedding_length is not a multiple of attention.head_count"; status = -102; return nullptr; }
-    if (hp.n_expert < 0 || hp.n_expert > 256 || hp.n_expert_used < 0 || hp.n_expert_used > hp.n_expert || (hp.n_expert > 0 && hp.n_expert_used == 0)) {
-        err = "bad expert_count / expert_used_count"; status = -102; return nullptr;
-    }
-    // llama / qwen2: n_embd / n_head, whatever attention.key_length says (a llama file whose key_length disagrees - Mistral-Nemo style - is read exactly as
-    // before; the width handling below is the groundwork for it).  qwen3: attention.key_length, which value_length must equal.
-    hp.head_dim = hp.n_embd / hp.n_head;
-    if (hp.qk_norm) {
-        const uint64_t kl = f.get_u(a + "attention.key_length", 0), vl = f.get_u(a + "attention.value_length", kl);
-        if (kl == 0) { err = "qwen3 file without attention.key_length"; status = -102; return nullptr; }
-        if (vl != kl) { err = "attention.value_length (" + std::to_string(vl) + ") differs from attention.key_length (" + std::to_string(kl) + "): not supported"; status = -102; return nullptr; }
-        if (kl > 4096) { err = "implausible attention.key_length"; status = -102; return nullptr; }
-        hp.head_dim = (int)kl;
-    }
-    hp.n_rot = (int)f.get_u(a + "rope.dimension_count", (uint64_t)hp.head_dim);
-    hp.rope_neox = hp.arch != "llama";
-    const std::string scaling = f.get_s(a + "rope.scaling.type", "none");
-    if (scaling == "linear") hp.rope_scale = 1.0f / (float)f.get_f(a + "rope.scaling.factor", 1.0);
-    if (scaling == "yarn") {
-        // YaRN (llama.cpp: rope_yarn / ggml_rope_yarn_corr_dims with the context defaults beta_fast 32, beta_slow 1, ext_factor 1): pairs that turn more than
-        // beta_fast times over the ORIGINAL context keep their angle, pairs that turn less than beta_slow times are interpolated by 1/factor, a linear ramp between
-        const float factor = (float)f.get_f(a + "rope.scaling.factor", 1.0);
-        if (!(factor > 0.0f)) { err = "rope.scaling.factor must be positive"; status = -102; return nullptr; }
-        const float n_orig = (float)f.get_u(a + "rope.scaling.original_context_length", f.get_u(a + "context_length", 4096));
-        hp.rope_scale = 1.0f / factor;
-        hp.yarn_ext = 1.0f;
-        hp.yarn_attn = (float)f.get_f(a + "rope.scaling.attn_factor", 1.0);
-        const float two_log_base = 2.0f * logf(hp.rope_base);
-        const float lo = floorf((float)hp.n_rot * logf(n_orig / (32.0f * 2.0f * 3.14159265358979323846f)) / two_log_base);
-        const float hi = ceilf((float)hp.n_rot * logf(n_orig / (1.0f * 2.0f * 3.14159265358979323846f)) / two_log_base);
-        hp.yarn_lo = lo > 0.0f ? lo : 0.0f;
-        hp.yarn_hi = hi < (float)(hp.n_rot - 1) ? hi : (float)(hp.n_rot - 1);
-    } else if (scaling != "none" && scaling != "linear") { err = "unsupported rope.scaling.type " + scaling; status = -102; return nullptr; }
-    if (hp.head_dim != 64 && hp.head_dim != 128) { err = "unsupported head_dim " + std::to_string(hp.head_dim); status = -102; return nullptr; }
-    // Row lengths - n_embd, the attention width H * D, n_ff - are whole numbers of 32-element blocks; what each TENSOR's type makes of its own row length is
-    // checked tensor by tensor below (want), and the graphs that still want whole 256-blocks say so by name once the widths are known (widths_256).
-    if (hp.n_embd % 32) { err = "embedding_length (" + std::to_string(hp.n_embd) + ") must be a multiple of 32"; status = -102; return nullptr; }
-    // ---- row split: this rank's share of the heads and of the feed-forward width
-    const int P = tp_size > 1 ? tp_size : 1, R = tp_size > 1 ? tp_rank : 0;
-    hp.n_head_full = hp.n_head; hp.n_head_kv_full = hp.n_head_kv; hp.n_ff_full = hp.n_ff;
-    hp.tp_rank = R; hp.tp_size = P;
-    // the exchange steps run whenever the process has a group of that size — also a group of ONE rank, which is how the
-    // RCCL calls (and their capture into graphs) are exercised on a single GPU
-    hp.tp_exchange = tp_active() && mi355::tp_size() == P && mi355::tp_rank() == R;
-    // (the q / k norm weights and the per-rank path of a qwen3 file are untested under a row split; Qwen3-32B Q4_K_M and Qwen3-30B-A3B fit one device)
-    if (P > 1 && hp.qk_norm) { err = "row split (split_mode \"row\" / tp_size > 1) of " + hp.arch + " files is not supported: load it on one device"; status = -102; return nullptr; }
-    if (P > 1 && !hp.tp_exchange) { err = "tp_size > 1 needs the process's row-split group first (mi355_tp_init with the same rank / size)"; status = -102; return nullptr; }
-    if (P > 1) {
-        if (R < 0 || R >= P) { err = "tp_rank out of range"; status = -102; return nullptr; }
-        if (hp.n_expert > 0) { err = "row split of mixture-of-experts files is not supported"; status = -102; return nullptr; }
-        if (hp.n_head % P || hp.n_head_kv % P) { err = "tp_size must divide the head counts (" + std::to_string(hp.n_head) + " / " + std::to_string(hp.n_head_kv) + ")"; status = -102; return nullptr; }
-        if (((hp.n_head / P) * hp.head_dim) % 256) { err = "a rank's attention width must be a multiple of 256"; status = -102; return nullptr; }
-        hp.n_head /= P; hp.n_head_kv /= P;
-    }
-
-    // plan the arena
-    // where a tensor's bytes come from: the whole tensor, or this rank's rows (a contiguous range), or this rank's
-    // columns (the same block range of every row: a strided copy)
-    enum { SPLIT_NONE = 0, SPLIT_ROWS = 1, SPLIT_COLS = 2 };
-    struct Plan { const GGUFTensorInfo *ti; DevTensor *dst; size_t off; size_t src_off, src_pitch, src_width; int64_t src_rows; size_t src_bytes; bool extra_copy; };
-    std::vector<Plan> plan;
-    size_t total = 0, max_stage = 0;
-    bool fail = false;
-    // cpart / cparts: column part cpart of cparts of THIS RANK's tensor as a tensor of its own (a second copy for the single-token steps, see LayerWeights::down_lo)
-    auto want = [&](const std::string &name, DevTensor &dst, bool required, int split = SPLIT_NONE, int cpart = 0, int cparts = 1) {
-        const GGUFTensorInfo *ti = f.tensor(name);
-        if (!ti) {
-            if (required) { err = "missing tensor " + name; fail = true; }
-            return;
-        }
-        if (!type_supported(ti->type)) {
-            err = "tensor " + name + " has unsupported type " + ggml_type_name(ti->type);
-            fail = true;
-            return;
-        }
-        if (P > 1 && (ti->type == T_IQ4_XS || nib32_has_min(ti->type))) {   // (the row split's column cuts and exchange steps are untested with them)
-            err = std::string("row split (split_mode \"row\" / tp_size > 1) of ") + ggml_type_name(ti->type) + " tensors is not supported (tensor " + name + "): load the file on one device";
-            fail = true;
-            return;
-        }
-        if (ti->type == T_MXFP4) {
-            // mxfp4 is a type of the 2-D and expert weights of the decoder graphs: the kernels read norm and bias vectors as f32, the encoder graph's launches
-            // and the row split's column cuts and exchange steps are untested with it
-            const char *why = ti->n_dims == 1 ? "norm and bias vectors must be f32" : hp.encoder ? "the encoder graph is not supported with mxfp4 tensors" :
-                              P > 1 ? "a row split (split_mode \"row\" / tp_size > 1) of mxfp4 tensors is not supported: load the file on one device" : nullptr;
-            if (why) { err = "tensor " + name + " has type mxfp4: " + why; fail = true; return; }
-        }
-        if (ti->type == T_BF16) {
-            // bf16 is a type of the dense 2-D weights (and of token_embd / output): the norm and bias vectors are read as f32 by the kernels, the routed experts,
-            // the encoder graph and the row split's column cuts have no bf16 kernels.  Rows are loaded as 16-byte pieces: 8 weights.
-            const bool expert = name.size() > 12 && (name.compare(name.size() - 12, 12, "_exps.weight") == 0 || name.find("ffn_gate_inp") != std::string::npos);
-            const char *why = ti->n_dims == 1 ? "norm and bias vectors must be f32" : expert ? "bf16 expert tensors are not supported" :
-                              hp.encoder ? "the encoder graph has no bf16 kernels" : P > 1 ? "a row split (split_mode \"row\" / tp_size > 1) of bf16 tensors is not supported: load the file on one device" :
-                              (ti->ne[0] % 8) ? "bf16 rows must hold a multiple of 8 weights" :
-                              // (the bf16 weight stream has a tail form, the matrix-core prompt path is untested at such a width: refused rather than run unchecked)
-                              (hp.n_embd % 256) ? "bf16 tensors in a file whose embedding_length is not a multiple of 256 are not supported" : nullptr;
-            if (why) { err = "tensor " + name + " has type bf16: " + why; fail = true; return; }
-        }
-        dst.name = name;
-        dst.type = ti->type;
-        dst.K = ti->ne[0];
-        dst.N = ti->ne[1];
-        dst.n_expert = ti->ne[2];
-        // a row is a whole number of its type's blocks: 256 elements for the K-quants and IQ4_XS, 32 for Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL / MXFP4
-        // (llama-quantize writes a tensor whose rows are no multiple of 256 in one of the latter)
-        const int64_t row_unit = std::max<int64_t>(ggml_block_elems(dst.type), 1);
-        if (dst.K % row_unit) {
-            err = "tensor " + name + " (" + ggml_type_name(dst.type) + "): its row length " + std::to_string(dst.K) + " is not a whole number of " + std::to_string(row_unit) + "-element blocks";
-            fail = true; return;
-        }
-        const size_t full_row = ggml_row_bytes(dst.type, dst.K);
-        Plan pl{ti, &dst, total, 0, full_row, full_row, ti->n_dims == 1 ? 1 : dst.N * dst.n_expert, (size_t)ti->bytes, cparts > 1};
-        if (P > 1 && split != SPLIT_NONE) {
-            const int64_t blk = std::max<int64_t>(ggml_block_elems(dst.type), 1);
-            if (ti->n_dims == 1 || split == SPLIT_COLS) {          // a bias vector is cut like the rows it is added to
-                const int64_t unit = split == SPLIT_COLS && blk > 1 ? std::max<int64_t>(blk, 256) : blk;
-                if (dst.K % P || (dst.K / P) % unit) { err = "tensor " + name + ": row length " + std::to_string(dst.K) + " cannot be cut " + std::to_string(P) + " ways on block boundaries"; fail = true; return; }
-                dst.K /= P;
-                pl.src_width = ggml_row_bytes(dst.type, dst.K);
-                pl.src_off = (size_t)R * pl.src_width;
-            } else {
-                if (dst.N % P) { err = "tensor " + name + ": " + std::to_string(dst.N) + " rows cannot be cut " + std::to_string(P) + " ways"; fail = true; return; }
-                dst.N /= P;
-                pl.src_rows = dst.N;
-                pl.src_off = (size_t)R * (size_t)dst.N * full_row;
-            }
-            pl.src_bytes = pl.src_width * (size_t)pl.src_rows;
-        }
-        if (cparts > 1) {                                          // (on 256-element boundaries, checked by the caller)
-            dst.name = name + "[cols " + std::to_string(cpart) + "/" + std::to_string(cparts) + "]";
-            dst.K /= cparts;
-            pl.src_width = ggml_row_bytes(dst.type, dst.K);
-            pl.src_off += (size_t)cpart * pl.src_width;
-            pl.src_bytes = pl.src_width * (size_t)pl.src_rows;
-        }
-        dst.row_bytes = ti->n_dims == 1 ? ggml_row_bytes(dst.type, dst.K) : dev_row_bytes(dst.type, dst.K);
-        const int64_t rows = ti->n_dims == 1 ? 1 : dst.N * dst.n_expert;
-        dst.bytes = dst.row_bytes * (size_t)rows;
-        dst.ggml_bytes = pl.src_bytes;
-        plan.push_back(pl);
-        total += (dst.bytes + 255) & ~(size_t)255;
-        if (type_is_repacked(dst.type) || dst.row_bytes != ggml_row_bytes(dst.type, dst.K)) max_stage = std::max(max_stage, pl.src_bytes);
-    };
-    want("token_embd.weight", m->tok_embd, true);
-    if (hp.encoder) {
-        if (P > 1) { err = "row split of encoder files is not supported"; status = -102; return nullptr; }
-        if (hp.n_expert > 0) { err = "mixture-of-experts encoder files are not supported"; status = -102; return nullptr; }
-        want("token_types.weight", m->tok_types, false);
-        want("token_embd_norm.weight", m->tok_norm, true);
-        want("token_embd_norm.bias", m->tok_norm_b, true);
-        m->layers.resize((size_t)hp.n_layer);
-        for (int il = 0; il < hp.n_layer && !fail; il++) {
-            LayerWeights &L = m->layers[(size_t)il];
-            const std::string p = "blk." + std::to_string(il) + ".";
-            want(p + "attn_qkv.weight", L.wqkv, true);
-            want(p + "attn_output.weight", L.wo, true);
-            want(p + "attn_output.bias", L.bo, false);
-            want(p + "attn_output_norm.weight", L.attn_out_norm, true);
-            want(p + "attn_output_norm.bias", L.attn_out_norm_b, true);
-            want(p + "ffn_gate.weight", L.gate, true);
-            want(p + "ffn_up.weight", L.up, true);
-            want(p + "ffn_down.weight", L.down, true);
-            want(p + "layer_output_norm.weight", L.layer_out_norm, true);
-            want(p + "layer_output_norm.bias", L.layer_out_norm_b, true);
-        }
-    } else {
-    want("output_norm.weight", m->out_norm, true);
-    {   // the output projection is cut by vocabulary rows when they divide evenly (logits are gathered), else every rank keeps it whole
-        const GGUFTensorInfo *ot = f.tensor("output.weight");
-        want("output.weight", m->output, false, ot && ot->ne[1] % P == 0 ? SPLIT_ROWS : SPLIT_NONE);
-    }
-    want("rope_freqs.weight", m->rope_freqs, false);
-    m->layers.resize((size_t)hp.n_layer);
-    for (int il = 0; il < hp.n_layer && !fail; il++) {
-        LayerWeights &L = m->layers[(size_t)il];
-        const std::string p = "blk." + std::to_string(il) + ".";
-        want(p + "attn_norm.weight", L.attn_norm, true);
-        want(p + "attn_q.weight", L.wq, true, SPLIT_ROWS);
-        want(p + "attn_k.weight", L.wk, true, SPLIT_ROWS);
-        want(p + "attn_v.weight", L.wv, true, SPLIT_ROWS);
-        want(p + "attn_output.weight", L.wo, true, SPLIT_COLS);
-        want(p + "attn_q.bias", L.bq, false, SPLIT_ROWS);
-        want(p + "attn_k.bias", L.bk, false, SPLIT_ROWS);
-        want(p + "attn_v.bias", L.bv, false, SPLIT_ROWS);
-        if (hp.qk_norm) {
-            want(p + "attn_q_norm.weight", L.q_norm, true);
-            want(p + "attn_k_norm.weight", L.k_norm, true);
-        }
-        want(p + "ffn_norm.weight", L.ffn_norm, true);
-        if (hp.n_expert > 0) {
-            want(p + "ffn_gate_inp.weight", L.gate_inp, true);
-            want(p + "ffn_gate_exps.weight", L.gate_exps, true);
-            want(p + "ffn_up_exps.weight", L.up_exps, true);
-            want(p + "ffn_down_exps.weight", L.down_exps, true);
-        } else {
-            want(p + "ffn_gate.weight", L.gate, true, SPLIT_ROWS);
-            want(p + "ffn_up.weight", L.up, true, SPLIT_ROWS);
-            want(p + "ffn_down.weight", L.down, true, SPLIT_COLS);
-            // a contraction length without a weight-stream form whose half has one (mmvq_stream_applicable: 1, 2, 3, 4, 6, 7 or 10 passes of 2048):
-            // Llama-3-70B's 28672 -> 2 x 14336
-            static const bool halves_on = !(getenv("MI355_DOWN_HALVES") && getenv("MI355_DOWN_HALVES")[0] == '0');
-            auto kb_ok = [](int64_t K) { const int64_t kb = (K + 2047) >> 11; return kb == 1 || kb == 2 || kb == 3 || kb == 4 || kb == 6 || kb == 7 || kb == 10; };
-            const int64_t Kd = L.down.K;
-            if (halves_on && !fail && type_is_kq456(L.down.type) && !kb_ok(Kd) && Kd % 512 == 0 && kb_ok(Kd / 2)) {
-                want(p + "ffn_down.weight", L.down_lo, true, SPLIT_COLS, 0, 2);
-                want(p + "ffn_down.weight", L.down_hi, true, SPLIT_COLS, 1, 2);
-            }
-        }
-    }
-    }
-    if (fail) { status = -102; return nullptr; }
-    // ---- every tensor against the shape the hyper-parameters imply (per rank under a row split).  The activation buffers
-    // are sized from the hyper-parameters and the kernels write one value per weight ROW: a file whose tensors disagree
-    // with its own metadata must fail here, not write out of bounds at the first decode (upstream create_tensor does the
-    // same).  Per-rank sizes: hp.n_head / n_head_kv are already this rank's.
-    {
-        const int64_t E = hp.n_embd, D = hp.head_dim, QW = (int64_t)hp.n_head * D, KVW = (int64_t)hp.n_head_kv * D;
-        auto shape = [&](const DevTensor &t, int64_t K, int64_t N, int64_t NE, bool vec) {
-            if (fail || t.name.empty()) return;                    // (absent optional tensor)
-            const bool ok = vec ? (t.K == K && t.N == 1 && t.n_expert == 1) : (t.K == K && t.N == N && t.n_expert == NE);
-            if (!ok) {
-                err = "tensor " + t.name + " has shape [" + std::to_string(t.K) + ", " + std::to_string(t.N) + ", " + std::to_string(t.n_expert) + "], expected [" +
-                      std::to_string(K) + (vec ? "]" : ", " + std::to_string(N) + ", " + std::to_string(NE) + "]");
-                fail = true;
-            }
-        };
-        if (m->tok_embd.K != E || m->tok_embd.N <= 0 || m->tok_embd.n_expert != 1) { err = "token_embd.weight does not have embedding_length columns"; fail = true; }
-        const int64_t V = m->tok_embd.N;
-        if (hp.encoder) {
-            if (!m->tok_types.name.empty() && (m->tok_types.K != E || m->tok_types.N < 1 || m->tok_types.type != T_F32)) { err = "token_types.weight must hold f32 rows of embedding_length"; fail = true; }
-            shape(m->tok_norm, E, 0, 0, true); shape(m->tok_norm_b, E, 0, 0, true);
-            if (hp.n_rot != D) { err = "encoder files rotate whole heads (rope.dimension_count must equal the head size)"; fail = true; }
-            int64_t FFe = 0;
-            for (int il = 0; il < hp.n_layer && !fail; il++) {
-                const LayerWeights &L = m->layers[(size_t)il];
-                if (il == 0) FFe = L.gate.N;
-                shape(L.wqkv, E, QW + 2 * KVW, 1, false); shape(L.wo, QW, E, 1, false); shape(L.bo, E, 0, 0, true);
-                shape(L.attn_out_norm, E, 0, 0, true); shape(L.attn_out_norm_b, E, 0, 0, true);
-                shape(L.layer_out_norm, E, 0, 0, true); shape(L.layer_out_norm_b, E, 0, 0, true);
-                shape(L.gate, E, FFe, 1, false); shape(L.up, E, FFe, 1, false); shape(L.down, FFe, E, 1, false);
-                if (!fail && (FFe <= 0 || (hp.n_ff_full > 0 && FFe != hp.n_ff_full))) { err = "feed-forward tensors do not match feed_forward_length"; fail = true; }
-                for (const DevTensor *t : {&L.bo, &L.attn_out_norm, &L.attn_out_norm_b, &L.layer_out_norm, &L.layer_out_norm_b})
-                    if (!fail && !t->name.empty() && t->type != T_F32) { err = "tensor " + t->name + " must be f32"; fail = true; }
-            }
-            if (!fail && (m->tok_norm.type != T_F32 || m->tok_norm_b.type != T_F32)) { err = "token_embd_norm must be f32"; fail = true; }
-            if (fail) { status = -102; return nullptr; }
-        } else {
-        shape(m->out_norm, E, 0, 0, true);
-        if (!m->output.name.empty()) shape(m->output, E, f.tensor("output.weight")->ne[1] % P == 0 ? V / P : V, 1, false);
-        if (!m->rope_freqs.name.empty() && (m->rope_freqs.K != hp.n_rot / 2 || m->rope_freqs.type != T_F32)) { err = "rope_freqs.weight must hold rope.dimension_count / 2 f32 factors"; fail = true; }
-        if (hp.n_rot <= 0 || hp.n_rot > D || (hp.n_rot & 1)) { err = "bad rope.dimension_count"; fail = true; }
-        // (the q / k norm kernels rotate whole heads)
-        if (!fail && hp.qk_norm && hp.n_rot != D) { err = "qwen3 files must rotate whole heads (rope.dimension_count must equal attention.key_length)"; fail = true; }
-        if (!fail && hp.arch == "qwen3" && hp.n_expert > 0) { err = "qwen3 files with experts are not supported"; fail = true; }
-        int64_t FF = 0;
-        for (int il = 0; il < hp.n_layer && !fail; il++) {
-            const LayerWeights &L = m->layers[(size_t)il];
-            shape(L.attn_norm, E, 0, 0, true); shape(L.ffn_norm, E, 0, 0, true);
-            shape(L.wq, E, QW, 1, false); shape(L.wk, E, KVW, 1, false); shape(L.wv, E, KVW, 1, false);
-            shape(L.wo, QW, E, 1, false);
-            shape(L.bq, QW, 0, 0, true); shape(L.bk, KVW, 0, 0, true); shape(L.bv, KVW, 0, 0, true);
-            shape(L.q_norm, D, 0, 0, true); shape(L.k_norm, D, 0, 0, true);
-            if (hp.n_expert > 0) {
-                if (il == 0) FF = L.gate_exps.N;
-                shape(L.gate_inp, E, hp.n_expert, 1, false);
-                shape(L.gate_exps, E, FF, hp.n_expert, false); shape(L.up_exps, E, FF, hp.n_expert, false);
-                shape(L.down_exps, FF, E, hp.n_expert, false);
-            } else {
-                if (il == 0) FF = L.gate.N;
-                shape(L.gate, E, FF, 1, false); shape(L.up, E, FF, 1, false);
-                shape(L.down, FF, E, 1, false);
-            }
-            if (!fail && (FF <= 0 || (hp.n_ff_full > 0 && FF * P != hp.n_ff_full))) { err = "feed-forward tensors do not match " + ff_key; fail = true; }
-            // norms and biases are read as f32 vectors by the kernels
-            for (const DevTensor *t : {&L.attn_norm, &L.ffn_norm, &L.bq, &L.bk, &L.bv, &L.q_norm, &L.k_norm})
-                if (!fail && !t->name.empty() && t->type != T_F32) { err = "tensor " + t->name + " must be f32"; fail = true; }
-        }
-        if (!fail && m->out_norm.type != T_F32) { err = "output_norm.weight must be f32"; fail = true; }
-        if (fail) { status = -102; return nullptr; }
-        }
-    }
-    hp.n_vocab = (int)m->tok_embd.N;
-    hp.n_ff = (int)(hp.n_expert ? m->layers[0].gate_exps.N : m->layers[0].gate.N);     // this rank's width under a row split
-    if (!hp.n_ff_full) hp.n_ff_full = hp.n_ff * P;
-    hp.n_vocab_local = !m->output.name.empty() ? (int)m->output.N : hp.n_vocab;      // (planned, not uploaded yet)
-    {
-        // Where whole 256-blocks are still wanted: graphs whose kernels have no general form to fall back to at such a width.  The dense llama / qwen2 / qwen3
-        // graph runs every width that is a multiple of 32 (the quantisers, the generic mat-vec and the Q8_0 prompt kernel take a row that ends inside a 256-group).
-        const int64_t aw = (int64_t)hp.n_head_full * hp.head_dim;
-        const bool odd = (hp.n_embd % 256) || (aw % 256) || (hp.n_ff_full % 256);
-        const std::string widths = "embedding_length " + std::to_string(hp.n_embd) + ", attention width " + std::to_string(aw) + ", feed-forward width " + std::to_string(hp.n_ff_full);
-        const char *what = !odd ? nullptr : hp.n_expert > 0 ? "mixture-of-experts files (the expert gather and the expert mat-vecs work on whole 256-blocks)" :
-                           hp.encoder ? "encoder files" : P > 1 ? "a row split (split_mode \"row\" / tp_size > 1)" : nullptr;
-        if (what) { err = std::string(what) + " need widths that are multiples of 256 (" + widths + ")"; status = -102; return nullptr; }
-    }
-
-    // (the file has been validated without touching the device: a malformed file fails the same way with and without a GPU)
-    if (hipSetDevice(main_gpu) != hipSuccess) { err = "hipSetDevice failed"; status = -100; return nullptr; }
-    m->device = main_gpu;
+// ---- model_load: plan on the host (model_plan.cc), then upload, then the views and the tied output, then the prefill planes
+static bool upload_tensors(Model &m, const LoadPlan &plan, std::string &err, int &status) {
     uint8_t *arena = nullptr, *stage = nullptr;
-    if (hipMalloc(&arena, total) != hipSuccess) { err = "hipMalloc of " + std::to_string(total) + " weight bytes failed"; status = -104; return nullptr; }
-    m->arenas.push_back(arena);
-    if (max_stage && hipMalloc(&stage, max_stage) != hipSuccess) { err = "hipMalloc of staging buffer failed"; status = -104; return nullptr; }
+    if (hipMalloc(&arena, plan.total) != hipSuccess) { err = "hipMalloc of " + std::to_string(plan.total) + " weight bytes failed"; status = -104; return false; }
+    m.arenas.push_back(arena);
+    if (plan.max_stage && hipMalloc(&stage, plan.max_stage) != hipSuccess) { err = "hipMalloc of staging buffer failed"; status = -104; return false; }
     hipStream_t st = nullptr;
     (void)hipStreamCreate(&st);
-    for (const Plan &pl : plan) {
+    bool ok = true;
+    for (const TensorPlan &pl : plan.tensors) {
         DevTensor &d = *pl.dst;
         d.data = arena + pl.off;
         const bool direct = !type_is_repacked(d.type) && (pl.ti->n_dims == 1 || d.row_bytes == ggml_row_bytes(d.type, d.K));
@@ -434,90 +83,102 @@ Model *model_load(const std::string &path, int main_gpu, std::string &err, int &
         if (e != hipSuccess) {
             err = std::string("upload of ") + d.name + " failed: " + hipGetErrorString(e);
             status = -105;
-            if (stage) (void)hipFree(stage);
-            (void)hipStreamDestroy(st);
-            return nullptr;
+            ok = false;
+            break;
         }
-        if (!pl.extra_copy) m->file_tensor_bytes += pl.src_bytes;
     }
     if (stage) (void)hipFree(stage);
     (void)hipStreamDestroy(st);
-    if (!m->output.valid()) m->output = m->tok_embd;   // tied embeddings
-    if (hp.encoder) {
-        // Q, K and V are row ranges of the fused projection: views into its device rows (one launch each; the rows are contiguous per output)
-        for (auto &L : m->layers) {
-            const int64_t qw = (int64_t)hp.n_head * hp.head_dim, kvw = (int64_t)hp.n_head_kv * hp.head_dim;
-            auto view = [&](DevTensor &v, int64_t row0, int64_t rows, const char *what) {
-                v = L.wqkv;
-                v.name = L.wqkv.name + "[" + what + "]";
-                v.N = rows;
-                v.data = L.wqkv.data + (size_t)row0 * L.wqkv.row_bytes;
-                v.bytes = (size_t)rows * L.wqkv.row_bytes;
-                v.planes = nullptr; v.planes_bytes = 0;
-            };
-            view(L.wq, 0, qw, "q"); view(L.wk, qw, kvw, "k"); view(L.wv, qw + kvw, kvw, "v");
-        }
-    }
-    m->device_bytes = total;
-    m->host_bytes = 0;
+    return ok;
+}
 
-    // prompt-processing copy of the per-layer projection weights: both int8 MFMA operand planes of every K-step,
-    // expanded once here (2 B per weight) so that the prefill kernel spends nothing per weight (mmq.hip).  288 GB of HBM
-    // is what makes this the default; it is skipped (the prefill kernel then expands on the fly) when memory is short.
-    if (const char *e = getenv("MI355_PREFILL_PLANES")) prefill_planes = atoi(e);
-    if (prefill_planes != 0) {
-        std::vector<DevTensor *> want;
-        for (auto &L : m->layers)
-            for (DevTensor *d : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down, &L.gate_exps, &L.up_exps, &L.down_exps})
-                if (d->valid() && (mmq_planes_bytes(d->type, d->N, (int)d->K) || mmq_q80_copy_bytes(d->type, d->N, (int)d->K))) want.push_back(d);
-        // (an *_exps tensor holds one plane set per expert, back to back: a prompt batch runs one contraction per expert)
-        // (K-quants: the two int8 MFMA planes; Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4: an exact Q8_0-layout copy for the Q8_0 prompt kernel, with a min plane for Q4_1 / Q5_1 and E8M0 scale bytes for MXFP4)
-        auto planes_of = [](const DevTensor *d) {
-            const size_t b = mmq_planes_bytes(d->type, d->N, (int)d->K);
-            return ((b ? b : mmq_q80_copy_bytes(d->type, d->N, (int)d->K)) + 255) & ~(size_t)255;
+// tied embeddings: the output head is the embedding table.  Encoder files: Q, K and V are row ranges of the fused projection - views into its device
+// rows (one launch each; the rows are contiguous per output)
+static void alias_tensors(Model &m) {
+    const HParams &hp = m.hp;
+    if (!m.output.valid()) m.output = m.tok_embd;
+    if (!hp.encoder) return;
+    for (auto &L : m.layers) {
+        const int64_t qw = (int64_t)hp.n_head * hp.head_dim, kvw = (int64_t)hp.n_head_kv * hp.head_dim;
+        auto view = [&](DevTensor &v, int64_t row0, int64_t rows, const char *what) {
+            v = L.wqkv;
+            v.name = L.wqkv.name + "[" + what + "]";
+            v.N = rows;
+            v.data = L.wqkv.data + (size_t)row0 * L.wqkv.row_bytes;
+            v.bytes = (size_t)rows * L.wqkv.row_bytes;
+            v.planes = nullptr; v.planes_bytes = 0;
         };
-        size_t need = 0;
-        for (DevTensor *d : want) need += planes_of(d) * (size_t)d->n_expert;
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        const size_t reserve = (size_t)24 << 30;             // KV cache, activations, other contexts
-        const bool fits = need > 0 && free_b > need + reserve;
-        if (need > 0 && !fits && prefill_planes == 1) { err = "not enough device memory for the prefill planes (" + std::to_string(need >> 20) + " MiB)"; status = -104; return nullptr; }
-        if (fits) {
-            uint8_t *parena = nullptr;
-            if (hipMalloc(&parena, need) != hipSuccess) { err = "hipMalloc of the prefill planes failed"; status = -104; return nullptr; }
-            m->arenas.push_back(parena);
-            size_t off = 0;
-            for (DevTensor *d : want) {
-                d->planes = parena + off;
-                d->planes_bytes = planes_of(d) * (size_t)d->n_expert;
-                off += d->planes_bytes;
-                for (int64_t x = 0; x < d->n_expert; x++) {
-                    const uint8_t *src = d->data + (size_t)x * d->row_bytes * (size_t)d->N;
-                    uint8_t *dst = d->planes + (size_t)x * planes_of(d);
-                    const hipError_t e = mmq_planes_bytes(d->type, d->N, (int)d->K) ? launch_mmq_expand(d->type, src, d->row_bytes, (int)d->N, (int)d->K, dst, nullptr)
-                                                                                   : launch_expand_q80_copy(d->type, src, d->row_bytes, (int)d->N, (int)d->K, dst, nullptr);
-                    if (e != hipSuccess) { err = std::string("plane expansion of ") + d->name + " failed: " + hipGetErrorString(e); status = -105; return nullptr; }
-                }
-            }
-            if (hipDeviceSynchronize() != hipSuccess) { err = "plane expansion failed"; status = -105; return nullptr; }
-            m->planes_bytes = need;
-            m->device_bytes += need;
+        view(L.wq, 0, qw, "q"); view(L.wk, qw, kvw, "k"); view(L.wv, qw + kvw, kvw, "v");
+    }
+}
+
+// prompt-processing copy of the per-layer projection weights: both int8 MFMA operand planes of every K-step,
+// expanded once here (2 B per weight) so that the prefill kernel spends nothing per weight (mmq.hip).  288 GB of HBM
+// is what makes this the default; it is skipped (the prefill kernel then expands on the fly) when memory is short.
+static bool expand_prefill_planes(Model &m, int prefill_planes, std::string &err, int &status) {
+    if (const char *e = getenv("MI355_PREFILL_PLANES")) prefill_planes = atoi(e);
+    if (prefill_planes == 0) return true;
+    std::vector<DevTensor *> want;
+    for (auto &L : m.layers)
+        for (DevTensor *d : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down, &L.gate_exps, &L.up_exps, &L.down_exps})
+            if (d->valid() && (mmq_planes_bytes(d->type, d->N, (int)d->K) || mmq_q80_copy_bytes(d->type, d->N, (int)d->K))) want.push_back(d);
+    // (an *_exps tensor holds one plane set per expert, back to back: a prompt batch runs one contraction per expert)
+    // (K-quants: the two int8 MFMA planes; Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4: an exact Q8_0-layout copy for the Q8_0 prompt kernel, with a min plane for Q4_1 / Q5_1 and E8M0 scale bytes for MXFP4)
+    auto planes_of = [](const DevTensor *d) {
+        const size_t b = mmq_planes_bytes(d->type, d->N, (int)d->K);
+        return ((b ? b : mmq_q80_copy_bytes(d->type, d->N, (int)d->K)) + 255) & ~(size_t)255;
+    };
+    size_t need = 0;
+    for (DevTensor *d : want) need += planes_of(d) * (size_t)d->n_expert;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const size_t reserve = (size_t)24 << 30;             // KV cache, activations, other contexts
+    const bool fits = need > 0 && free_b > need + reserve;
+    if (need > 0 && !fits && prefill_planes == 1) { err = "not enough device memory for the prefill planes (" + std::to_string(need >> 20) + " MiB)"; status = -104; return false; }
+    if (!fits) return true;
+    uint8_t *parena = nullptr;
+    if (hipMalloc(&parena, need) != hipSuccess) { err = "hipMalloc of the prefill planes failed"; status = -104; return false; }
+    m.arenas.push_back(parena);
+    size_t off = 0;
+    for (DevTensor *d : want) {
+        d->planes = parena + off;
+        d->planes_bytes = planes_of(d) * (size_t)d->n_expert;
+        off += d->planes_bytes;
+        for (int64_t x = 0; x < d->n_expert; x++) {
+            const uint8_t *src = d->data + (size_t)x * d->row_bytes * (size_t)d->N;
+            uint8_t *dst = d->planes + (size_t)x * planes_of(d);
+            const hipError_t e = mmq_planes_bytes(d->type, d->N, (int)d->K) ? launch_mmq_expand(d->type, src, d->row_bytes, (int)d->N, (int)d->K, dst, nullptr)
+                                                                           : launch_expand_q80_copy(d->type, src, d->row_bytes, (int)d->N, (int)d->K, dst, nullptr);
+            if (e != hipSuccess) { err = std::string("plane expansion of ") + d->name + " failed: " + hipGetErrorString(e); status = -105; return false; }
         }
     }
+    if (hipDeviceSynchronize() != hipSuccess) { err = "plane expansion failed"; status = -105; return false; }
+    m.planes_bytes = need;
+    m.device_bytes += need;
+    return true;
+}
 
-    // algorithmic bytes per decoded token: each tensor once, one embedding row, used experts only
-    uint64_t bpt = 0;
-    for (const Plan &pl : plan) {
-        if (pl.extra_copy) continue;                               // (the column halves of ffn_down: the same bytes a second time)
-        const DevTensor &d = *pl.dst;
-        uint64_t b = pl.src_bytes;
-        if (&d == &m->tok_embd) b = ggml_row_bytes(d.type, d.K);
-        else if (d.n_expert > 1 && hp.n_expert_used > 0) b = b / (uint64_t)d.n_expert * (uint64_t)hp.n_expert_used;
-        bpt += b;
-    }
-    if (m->output.data == m->tok_embd.data) bpt += m->tok_embd.ggml_bytes;
-    m->bytes_per_token = bpt;
+Model *model_load(const std::string &path, int main_gpu, std::string &err, int &status, int prefill_planes, int tp_rank, int tp_size) {
+    status = 0;
+    std::unique_ptr<Model> m(new Model());
+    m->file.reset(new GGUFFile());
+    m->path = path;
+    err = m->file->open(path);
+    if (!err.empty()) { status = err.rfind("cannot", 0) == 0 ? -101 : -102; return nullptr; }
+    // every refusal of a file and the whole arena layout: host arithmetic (model_plan.cc), so a malformed file fails the same way with and without a GPU
+    const int P = tp_size > 1 ? tp_size : 1, R = tp_size > 1 ? tp_rank : 0;
+    LoadPlan plan;
+    if (!plan_model(*m->file, tp_rank, tp_size, tp_active() && mi355::tp_size() == P && mi355::tp_rank() == R, *m, plan, err, status)) return nullptr;
+    if (hipSetDevice(main_gpu) != hipSuccess) { err = "hipSetDevice failed"; status = -100; return nullptr; }
+    m->device = main_gpu;
+    if (!upload_tensors(*m, plan, err, status)) return nullptr;
+    alias_tensors(*m);
+    m->file_tensor_bytes = plan.file_tensor_bytes;
+    m->device_bytes = plan.total;
+    m->host_bytes = 0;
+    if (!expand_prefill_planes(*m, prefill_planes, err, status)) return nullptr;
+    m->bytes_per_token = plan.bytes_per_token;
+    const HParams &hp = m->hp;
     char desc[256];
     snprintf(desc, sizeof desc, "%s %dL E%d H%d/%d FF%d V%d%s", hp.arch.c_str(), hp.n_layer, hp.n_embd, hp.n_head, hp.n_head_kv, hp.n_ff,
              hp.n_vocab, hp.n_expert ? " MoE" : "");
@@ -1031,9 +692,9 @@ hipError_t Context::ensure_prep(const ActQuant &aq, int K, int T) {
 }
 
 // Q2_K / Q3_K / IQ4_XS tensors reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
-// (the types with an exact Q8_0-layout copy: act_is_q80 without Q8_0 itself, which needs none - so the chain stays spelled out)
+// (the types with an exact Q8_0-layout copy: act_is_q80 without Q8_0 itself, which needs none)
 static bool q80_copy(const DevTensor &w, int K, int T) {
-    return (w.type == T_Q4_0 || w.type == T_Q5_0 || w.type == T_IQ4_NL || nib32_has_min(w.type) || nib32_has_e8(w.type)) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
+    return type_has_q80_copy(w.type) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
 }
 static bool planes_small(const DevTensor &w, int K, int T) { return type_is_planes_only(w.type) && w.planes && T >= 32 && (K % 256) == 0; }
 

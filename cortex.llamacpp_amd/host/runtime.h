@@ -15,69 +15,22 @@
 
 #include "../csrc/kernels.h"
 #include "gguf.h"
+#include "model_plan.h"
 
 namespace mi355 {
 
-struct DevTensor {
-    std::string name;
-    int type = 0;
-    int64_t K = 0;          // ne[0]: contraction / row length
-    int64_t N = 0;          // rows per expert (ne[1])
-    int64_t n_expert = 1;   // ne[2] for *_exps tensors
-    uint8_t *data = nullptr;
-    size_t row_bytes = 0;   // device row stride
-    size_t bytes = 0;       // device bytes
-    size_t ggml_bytes = 0;  // on-disk bytes
-    uint8_t *planes = nullptr;   // pre-expanded MFMA operand planes for prompt processing (mmq.hip), optional
-    size_t planes_bytes = 0;
-    bool valid() const { return data != nullptr; }
-};
-
-struct LayerWeights {
-    DevTensor attn_norm, wq, wk, wv, wo, bq, bk, bv;
-    DevTensor q_norm, k_norm;     // qwen3: [head_dim] f32 weights of the per-head RMSNorm of Q and K before the rope (empty otherwise)
-    DevTensor ffn_norm, gate, up, down;
-    // single-token steps of a feed-forward width the weight stream has no form for (K = 28672: a 16 KB row does not fit the ring pairwise) while half of
-    // it has one: the column halves of ffn_down as two tensors of their own, contracted by two launches (x += W_lo a_lo; x += W_hi a_hi).  A second copy
-    // of the tensor in HBM; prompt batches keep the whole tensor (and its planes).  Empty otherwise.
-    DevTensor down_lo, down_hi;
-    DevTensor gate_inp, gate_exps, up_exps, down_exps;
-    // encoder files (nomic-bert): the fused Q | K | V projection (wq / wk / wv are row ranges of it), LayerNorms with biases after the attention and the feed-forward block
-    DevTensor wqkv, bo, attn_out_norm, attn_out_norm_b, layer_out_norm, layer_out_norm_b;
-};
-
-struct HParams {
-    std::string arch;
-    int n_embd = 0, n_layer = 0, n_ff = 0, n_head = 0, n_head_kv = 0, n_rot = 0, n_vocab = 0;
-    int n_expert = 0, n_expert_used = 0, head_dim = 0, n_ctx_train = 0;
-    int pooling_type = 0;          // {arch}.pooling_type: 0 none, 1 mean, 2 cls, 3 last (what llama_get_embeddings_seq pools over a sequence's tokens)
-    float eps = 1e-5f, rope_base = 10000.0f, rope_scale = 1.0f;
-    int rope_neox = 0;
-    bool encoder = false;          // bidirectional attention, embeddings only (general.architecture nomic-bert: llm_build_bert)
-    bool qk_norm = false;          // qwen3: per-head RMSNorm of Q and K before the rope (LayerWeights::q_norm / k_norm); head_dim from attention.key_length
-    float yarn_ext = 0.0f, yarn_attn = 1.0f, yarn_lo = 0.0f, yarn_hi = 0.0f;   // rope.scaling.type "yarn" (RopeArgs, kernels.h)
-    // row split: n_head, n_head_kv and n_ff above are THIS RANK's share; the file's values are kept here.
-    // A shard is the same graph with fewer heads and a narrower feed-forward, attn_output and ffn_down contracting over
-    // the local slice only: their partial sums are the one thing exchanged (tp_comm.h).
-    int tp_rank = 0, tp_size = 1;
-    bool tp_exchange = false;    // the process has a matching group: partial sums and logits slices go through it
-    int n_head_full = 0, n_head_kv_full = 0, n_ff_full = 0;
-    int n_vocab_local = 0;       // rows of the output projection held here (n_vocab when it is not split)
-};
-
-struct Model {
-    HParams hp;
+// the model as its file describes it (ModelLayout: hyper-parameters and tensors, model_plan.h) plus what holding it on a device adds
+struct Model : ModelLayout {
     std::unique_ptr<GGUFFile> file;
     std::string path, desc;
     int device = 0;
     std::vector<uint8_t *> arenas;      // hipMalloc'd blocks
-    DevTensor tok_embd, out_norm, output, rope_freqs;
-    DevTensor tok_types, tok_norm, tok_norm_b;       // encoder files: token-type table (row 0 is added to every token), LayerNorm of the embeddings
-    std::vector<LayerWeights> layers;
     uint64_t device_bytes = 0, host_bytes = 0, file_tensor_bytes = 0, bytes_per_token = 0, planes_bytes = 0;
     ~Model();
 };
 
+// The file is validated and the arena laid out by plan_model (model_plan.h) before the device is touched: a malformed file fails the same way with and
+// without a GPU.  What follows uploads the plan (repacking rows on the way), sets up the encoder's views and the tied output, and expands the prefill planes.
 // prefill_planes: 0 = never, 1 = always (fails when memory is short), -1 = when device memory allows (default)
 // tp_size > 1: load rank tp_rank's slice of every projection (rows of attn_q/k/v, ffn_gate/up and output; the matching
 // super-block columns of attn_output and ffn_down), cut on head and 256-element boundaries

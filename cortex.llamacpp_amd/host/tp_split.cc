@@ -24,6 +24,7 @@
 #include <thread>
 #include <vector>
 
+#include "../csrc/ggml_types.h"
 #include "gguf.h"
 #include "hip_backend.h"
 #include "log.h"
@@ -339,8 +340,7 @@ std::unique_ptr<IBackend> make_split_backend(const Json &body, BackendInfo &info
             return nullptr;
         }
         for (const GGUFTensorInfo &t : f.tensors)
-            if (t.type == 3 || t.type == 7 || t.type == 39) { err = std::string("split_mode row: row split of ") + ggml_type_name(t.type) + " tensors is not supported (tensor " + t.name + "; load the file on one device)"; return nullptr; }
-            else if (t.type == 23) { err = "split_mode row: row split of iq4_xs tensors is not supported (tensor " + t.name + "; load the file on one device)"; return nullptr; }
+            if (type_row_split_unsupported(t.type)) { err = std::string("split_mode row: row split of ") + ggml_type_name(t.type) + " tensors is not supported (tensor " + t.name + "; load the file on one device)"; return nullptr; }
     }
     const int main_gpu = body.value<int>("main_gpu", 0);
     const bool shared = ranks > devices;

@@ -17,6 +17,7 @@
 #include "../../cortex.llamacpp_amd/host/engine.h"
 #include "../../cortex.llamacpp_amd/host/gguf.h"
 #include "../../cortex.llamacpp_amd/host/json.h"
+#include "../../cortex.llamacpp_amd/host/model_plan.h"
 #include "../../cortex.llamacpp_amd/host/sampling.h"
 #include "../../cortex.llamacpp_amd/host/grammar.h"
 #include "../../cortex.llamacpp_amd/host/server_context.h"
@@ -1392,11 +1393,60 @@ static int api_shapes_cli() {
     return 0;
 }
 
+// `host_tests --plan model.gguf [tp_rank tp_size [no-group]]` : what the loader would do with the file, without a device (model_plan.h) - the
+// hyper-parameters, every tensor of the arena with the source range its bytes come from, and the totals; {"status":, "err":} when the file is refused.
+// The group of a row split is taken as formed unless the word no-group follows (any other word there is a usage error).  Compared with a Python restatement of the layout rules by
+// test_model_plan_cpu.py.
+static int plan_cli(const char *gguf, int tp_rank, int tp_size, bool tp_group) {
+    GGUFFile f;
+    std::string err = f.open(gguf);
+    if (!err.empty()) { fprintf(stderr, "gguf: %s\n", err.c_str()); return 2; }
+    ModelLayout m;
+    LoadPlan plan;
+    int status = 0;
+    Json out = Json::object();
+    if (!plan_model(f, tp_rank, tp_size, tp_group, m, plan, err, status)) {
+        out["status"] = status; out["err"] = err;
+        printf("%s\n", out.dump().c_str());
+        return 0;
+    }
+    const HParams &h = m.hp;
+    Json hp = Json::object();
+    hp["arch"] = h.arch;
+    const std::pair<const char *, int> ints[] = {{"n_embd", h.n_embd}, {"n_layer", h.n_layer}, {"n_ff", h.n_ff}, {"n_head", h.n_head}, {"n_head_kv", h.n_head_kv}, {"n_rot", h.n_rot},
+        {"n_vocab", h.n_vocab}, {"n_expert", h.n_expert}, {"n_expert_used", h.n_expert_used}, {"head_dim", h.head_dim}, {"n_ctx_train", h.n_ctx_train}, {"pooling_type", h.pooling_type},
+        {"rope_neox", h.rope_neox}, {"encoder", h.encoder}, {"qk_norm", h.qk_norm}, {"tp_rank", h.tp_rank}, {"tp_size", h.tp_size}, {"n_head_full", h.n_head_full},
+        {"n_head_kv_full", h.n_head_kv_full}, {"n_ff_full", h.n_ff_full}, {"n_vocab_local", h.n_vocab_local}};
+    for (const auto &kv : ints) hp[kv.first] = kv.second;
+    const std::pair<const char *, float> floats[] = {{"eps", h.eps}, {"rope_base", h.rope_base}, {"rope_scale", h.rope_scale}, {"yarn_ext", h.yarn_ext}, {"yarn_attn", h.yarn_attn},
+        {"yarn_lo", h.yarn_lo}, {"yarn_hi", h.yarn_hi}};
+    for (const auto &kv : floats) hp[kv.first] = (double)kv.second;
+    Json tensors = Json::array();
+    for (const TensorPlan &pl : plan.tensors) {
+        const DevTensor &d = *pl.dst;
+        Json t = Json::object();
+        t["name"] = d.name; t["file_name"] = pl.ti->name; t["type"] = d.type; t["K"] = d.K; t["N"] = d.N; t["n_expert"] = d.n_expert; t["n_dims"] = pl.ti->n_dims;
+        t["row_bytes"] = (int64_t)d.row_bytes; t["bytes"] = (int64_t)d.bytes; t["offset"] = (int64_t)pl.off;
+        t["src_off"] = (int64_t)pl.src_off; t["src_pitch"] = (int64_t)pl.src_pitch; t["src_width"] = (int64_t)pl.src_width; t["src_rows"] = pl.src_rows;
+        t["src_bytes"] = (int64_t)pl.src_bytes; t["file_bytes"] = (int64_t)pl.ti->bytes; t["extra_copy"] = pl.extra_copy;
+        tensors.push_back(t);
+    }
+    out["hp"] = hp; out["tensors"] = tensors;
+    out["total"] = (int64_t)plan.total; out["max_stage"] = (int64_t)plan.max_stage;
+    out["file_tensor_bytes"] = (int64_t)plan.file_tensor_bytes; out["bytes_per_token"] = (int64_t)plan.bytes_per_token;
+    printf("%s\n", out.dump().c_str());
+    return 0;
+}
+
 static const char *volatile g_stage = "start";
 
 int main(int argc, char **argv) {
     if (argc == 4 && std::string(argv[1]) == "--tokenize") return tokenize_cli(argv[2], argv[3]);
     if (argc == 2 && std::string(argv[1]) == "--api-shapes") return api_shapes_cli();
+    if (argc >= 2 && std::string(argv[1]) == "--plan") {
+        if (argc != 3 && argc != 5 && !(argc == 6 && std::string(argv[5]) == "no-group")) { fprintf(stderr, "usage: --plan FILE [tp_rank tp_size [no-group]]\n"); return 2; }
+        return plan_cli(argv[2], argc >= 5 ? atoi(argv[3]) : 0, argc >= 5 ? atoi(argv[4]) : 1, argc != 6);
+    }
     // a run that hangs is ended from outside (timeout's SIGTERM): say which group of checks it was in
     signal(SIGTERM, [](int) { const char *m = g_stage; if (write(2, "hung in: ", 9) < 0 || write(2, m, strlen(m)) < 0 || write(2, "\n", 1) < 0) {} _exit(124); });
 #define STAGE(f) do { g_stage = #f; f(); } while (0)
