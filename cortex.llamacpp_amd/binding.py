@@ -13,6 +13,7 @@ Q5_0, IQ4_NL = 6, 20
 Q4_1, Q5_1 = 3, 7
 IQ4_XS = 23
 BF16 = 30
+TQ1_0, TQ2_0 = 34, 35
 MXFP4 = 39
 
 

@@ -589,7 +589,7 @@ namespace {
 int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y, int32_t *isum, int32_t *msum) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    // the K-quants and IQ4_XS: whole 256-blocks; the 32-element formats and f16 take any whole number of 32-element blocks
+    // the K-quants, IQ4_XS, TQ1_0 and TQ2_0: whole 256-blocks; the 32-element formats and f16 take any whole number of 32-element blocks
     if (!grow || K <= 0 || ((act_is_q80(type) || type == T_F16) ? K % 32 : K % 256)) { fail("bad type / K"); return MI355_ERR_ARG; }
     DevBuf wsrc(grow * N), wdev(drow * N), dx((size_t)K * T * 4), dy((size_t)N * T * 4), dres(resid ? (size_t)N * T * 4 : 16);
     ActBufs ab((size_t)K, (size_t)T);
@@ -625,7 +625,7 @@ int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x
             if (e == hipSuccess) e = hipDeviceSynchronize();
             if (e != hipSuccess) return hip_fail(e, "mmq_ksplit");
         } else
-        if (mmq_applicable(type, (int)K, (int)T) || (type_is_planes_only(type) && T >= 32 && g_op_mmq_planes)) {   // (Q2_K / Q3_K / IQ4_XS: planes only)
+        if (mmq_applicable(type, (int)K, (int)T) || (type_is_planes_only(type) && T >= 32 && g_op_mmq_planes)) {   // (Q2_K / Q3_K / IQ4_XS / TQ1_0 / TQ2_0: planes only)
             DevBuf bh(mmq_prep_bytes((int)K, (int)T)), bl(mmq_prep_bytes((int)K, (int)T));
             if (!bh.p || !bl.p) return MI355_ERR_OOM;
             e = launch_mmq_prep(ab.q, (int)K, (int)T, bh.as<int8_t>(), bl.as<int8_t>(), nullptr);

@@ -57,6 +57,24 @@ __global__ void repack_iq4xs_kernel(const uint8_t *src, uint8_t *dst, int nb, si
     else if (i < 8) d[(size_t)nb * 128 + (size_t)sb * 4 + (i - 4)] = v;
     else d[(size_t)sb * 128 + (i - 8)] = v;
 }
+// TQ2_0 block: qs 64 | d 2 -> planes qs | d;  TQ1_0 block: qs 48 | qh 4 | d 2 -> planes qs | qh | d (the packed trits as the file holds them)
+__global__ void repack_tq2_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
+    const int row = blockIdx.y, sb = blockIdx.x, i = threadIdx.x;   // 128 threads, 66 used
+    if (i >= 66) return;
+    const uint8_t v = src[((size_t)row * nb + sb) * 66 + i];
+    uint8_t *d = dst + (size_t)row * dst_row;
+    if (i < 64) d[(size_t)sb * 64 + i] = v;
+    else d[(size_t)nb * 64 + (size_t)sb * 2 + (i - 64)] = v;
+}
+__global__ void repack_tq1_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
+    const int row = blockIdx.y, sb = blockIdx.x, i = threadIdx.x;   // 64 threads, 54 used
+    if (i >= 54) return;
+    const uint8_t v = src[((size_t)row * nb + sb) * 54 + i];
+    uint8_t *d = dst + (size_t)row * dst_row;
+    if (i < 48) d[(size_t)sb * 48 + i] = v;
+    else if (i < 52) d[(size_t)nb * 48 + (size_t)sb * 4 + (i - 48)] = v;
+    else d[(size_t)nb * 52 + (size_t)sb * 2 + (i - 52)] = v;
+}
 // 32-element blocks with a 16-byte nibble field: Q4_0 / IQ4_NL (d | qs), Q5_0 (d | qh | qs), Q4_1 (d | m | qs), Q5_1 (d | m | qh | qs)
 // -> planes qs | [qh] | d | [m]; MXFP4 (e | qs) -> planes qs | e (one scale byte per block)
 __global__ void repack_nib32_kernel(const uint8_t *src, uint8_t *dst, int nblk, int K, size_t dst_row, int bsz) {
@@ -109,6 +127,14 @@ hipError_t launch_repack_rows(int type, const uint8_t *src, uint8_t *dst, int64_
             const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);
             hipLaunchKernelGGL(repack_iq4xs_kernel, dim3((unsigned)(K >> 8), nr), dim3(192), 0, st,
                                src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
+        }
+    } else if (type_is_ternary(type)) {
+        for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
+            const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);
+            if (type == T_TQ2_0) hipLaunchKernelGGL(repack_tq2_kernel, dim3((unsigned)(K >> 8), nr), dim3(128), 0, st,
+                                                    src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
+            else hipLaunchKernelGGL(repack_tq1_kernel, dim3((unsigned)(K >> 8), nr), dim3(64), 0, st,
+                                    src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
         }
     } else if (type == T_Q6_K) {
         for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {

@@ -818,6 +818,50 @@ __global__ __launch_bounds__(256) void mmq_expand_iq4xs_kernel(const uint8_t *W,
         *reinterpret_cast<u32x4 *>(blk + 16384 + n * 16) = m;
     }
 }
+// TQ1_0 / TQ2_0 into the signed (Q6_K) plane format: p = code - 1 (- 1 .. 1; 2 where a hostile TQ2_0 byte holds code 3), hi = p >> 6 floored, lo = p & 63, one
+// scale per super-block and no mins; lane (n, kg) takes elements 32 J + 16 kg .. + 15 of K-step J, element by element (a load-time kernel).
+// device rows: TQ2_0 [qs nb*64][d nb*2]; TQ1_0 [qs nb*48][qh nb*4][d nb*2]
+template <int TYPE>
+__global__ __launch_bounds__(256) void mmq_expand_ternary_kernel(const uint8_t *W, size_t row_bytes, int n_rows, int nb, int n_rt, uint8_t *planes) {
+    const int lane = threadIdx.x & 63;
+    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);     // (row tile, super-block)
+    if (idx >= n_rt * nb) return;
+    const int rt = idx / nb, sb = idx - rt * nb;
+    const int n = lane & 31, kg = lane >> 5;
+    int row = rt * 32 + n;
+    if (row >= n_rows) row = n_rows - 1;
+    const uint8_t *r = W + (size_t)row * row_bytes;
+    uint8_t *blk = planes + (size_t)idx * PL_BLOCK;
+#pragma unroll
+    for (int J = 0; J < 8; J++) {
+        uint32_t hv[4], lv[4];
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            uint32_t hx = 0, lx = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int e = 32 * J + 16 * kg + 4 * w + b;
+                int q;
+                if (TYPE == T_TQ2_0) q = (r[(size_t)sb * 64 + 32 * (e >> 7) + (e & 31)] >> (2 * ((e >> 5) & 3))) & 3;
+                else {
+                    int byte, t;
+                    tq1_elem(e, byte, t);
+                    q = tq1_trit(byte < 48 ? r[(size_t)sb * 48 + byte] : r[(size_t)nb * 48 + (size_t)sb * 4 + (byte - 48)], t);
+                }
+                const int p = q - 1;
+                hx |= (uint32_t)((p >> 6) & 0xff) << (8 * b); lx |= (uint32_t)(p & 63) << (8 * b);
+            }
+            hv[w] = hx; lv[w] = lx;
+        }
+        *reinterpret_cast<u32x4 *>(blk + (J * 2) * 1024 + lane * 16) = u32x4{hv[0], hv[1], hv[2], hv[3]};
+        *reinterpret_cast<u32x4 *>(blk + (J * 2 + 1) * 1024 + lane * 16) = u32x4{lv[0], lv[1], lv[2], lv[3]};
+    }
+    if (kg == 0) {
+        u32x4 m = {0, 0, 0, 0};
+        m.x = *reinterpret_cast<const uint16_t *>(r + (size_t)nb * (TYPE == T_TQ2_0 ? 64 : 52) + (size_t)sb * 2);
+        *reinterpret_cast<u32x4 *>(blk + 16384 + n * 16) = m;
+    }
+}
 // which fold a plane set takes: the block-sum ("mins") form with shift 5, or the signed form with shift 6
 __host__ __device__ constexpr bool planes_have_mins(int type) { return type == T_Q4_K || type == T_Q5_K || type == T_Q2_K; }
 
@@ -1734,7 +1778,7 @@ hipError_t launch_mmq_ksplit(int type, const uint8_t *W, size_t row_bytes, int n
 }
 
 size_t mmq_planes_bytes(int type, int64_t n_rows, int K) {
-    if ((type != T_Q4_K && type != T_Q5_K && type != T_Q6_K && type != T_Q2_K && type != T_Q3_K && type != T_IQ4_XS) || (K % 256) != 0) return 0;
+    if ((type != T_Q4_K && type != T_Q5_K && type != T_Q6_K && type != T_Q2_K && type != T_Q3_K && type != T_IQ4_XS && !type_is_ternary(type)) || (K % 256) != 0) return 0;
     return (size_t)((n_rows + 31) / 32) * (size_t)(K >> 8) * PL_BLOCK;
 }
 
@@ -1748,6 +1792,8 @@ hipError_t launch_mmq_expand(int type, const uint8_t *W, size_t row_bytes, int n
         case T_Q2_K: hipLaunchKernelGGL(mmq_expand_small_kernel<T_Q2_K>, grid, dim3(256), 0, st, W, row_bytes, n_rows, nb, n_rt, planes); break;
         case T_Q3_K: hipLaunchKernelGGL(mmq_expand_small_kernel<T_Q3_K>, grid, dim3(256), 0, st, W, row_bytes, n_rows, nb, n_rt, planes); break;
         case T_IQ4_XS: hipLaunchKernelGGL(mmq_expand_iq4xs_kernel, grid, dim3(256), 0, st, W, row_bytes, n_rows, nb, n_rt, planes); break;
+        case T_TQ1_0: hipLaunchKernelGGL(mmq_expand_ternary_kernel<T_TQ1_0>, grid, dim3(256), 0, st, W, row_bytes, n_rows, nb, n_rt, planes); break;
+        case T_TQ2_0: hipLaunchKernelGGL(mmq_expand_ternary_kernel<T_TQ2_0>, grid, dim3(256), 0, st, W, row_bytes, n_rows, nb, n_rt, planes); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -1820,7 +1866,7 @@ hipError_t launch_mmq_planes_swiglu(int type, const uint8_t *planes_gate, const 
 // the grouped (all experts, one launch) forms: `rows_max` = rows of the grouped arrays (tokens x experts used), meta = moe_group_kernel's counts and offsets
 bool mmq_planes_moe_ok(int type, int n_rows, int K) {
     static const bool env_on = !(getenv("MI355_MOE_GROUPED_LAUNCH") && getenv("MI355_MOE_GROUPED_LAUNCH")[0] == '0');
-    return env_on && (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_IQ4_XS) && mmq_planes_bytes(type, n_rows, K) != 0 && (n_rows % 128) == 0 && (K % 256) == 0;
+    return env_on && (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_IQ4_XS || type_is_ternary(type)) && mmq_planes_bytes(type, n_rows, K) != 0 && (n_rows % 128) == 0 && (K % 256) == 0;
 }
 hipError_t launch_mmq_planes_swiglu_moe(int type, const uint8_t *planes_gate, const uint8_t *planes_up, size_t plane_stride, int n_expert, const int32_t *meta,
                                         int n_rows, int K, int rows_max, const ActQuant &q, float *out, int ld_out, hipStream_t st) {

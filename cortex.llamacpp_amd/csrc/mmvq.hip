@@ -402,6 +402,91 @@ template <> struct Item<T_IQ4_XS> {
     }
 };
 
+// ---- TQ2_0 : device row planes [qs nb*64][d nb*2].  The code bytes are laid out as Q2_K's (byte m of half n: elements 128 n + 32 l + m in bits 2 l ..), so
+// the lane role is the register ring's for Q2_K: lane (c, h) takes bytes 16 h .. + 15 of half c / 2 and the fields 2 (c & 1), + 1: elements 64 c + 16 h .. + 15
+// and + 32.  One scale, no mins: isum = dot(codes, a) - sum a with the two 16-sums of Q8_K (ggml_vec_dot_tq2_0_q8_K) ----------
+template <> struct Item<T_TQ2_0> {
+    uint4 hdr;                        // x: d (f16)
+    static constexpr int EPP = 2048;
+    uint4 q;
+    float d;
+    int sb;
+    bool valid;
+    __device__ __forceinline__ void load(const uint8_t *row, int K, int pass, int lane) {
+        const int nb = K >> 8;
+        sb = pass * 8 + (lane >> 3);
+        valid = sb < nb;
+        if (valid) {
+            const int v = lane & 7;
+            q = ld16w(row + (size_t)sb * 64 + 32 * (v >> 2) + 16 * (v & 1));
+            hdr.x = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 64 + (size_t)sb * 2);
+        }
+    }
+    __device__ __forceinline__ void prep(int lane) {
+        if (valid) d = h2f((uint16_t)hdr.x);
+    }
+    __device__ __forceinline__ void ints(const ActLds &A, int t, int lane, int &isum, int &msum) const {
+        const int v = lane & 7, c = v >> 1, h = v & 1;
+        const int8_t *a = A.qs + (size_t)t * A.K + sb * 256 + 64 * c + 16 * h;
+        const uint4 lo = ld16(a), hi = ld16(a + 32);
+        const int s0 = 4 * (c & 1), s1 = s0 + 2;
+        int dl = 0, dh = 0;
+        dl = dot4((q.x >> s0) & 0x03030303u, lo.x, dl); dh = dot4((q.x >> s1) & 0x03030303u, hi.x, dh);
+        dl = dot4((q.y >> s0) & 0x03030303u, lo.y, dl); dh = dot4((q.y >> s1) & 0x03030303u, hi.y, dh);
+        dl = dot4((q.z >> s0) & 0x03030303u, lo.z, dl); dh = dot4((q.z >> s1) & 0x03030303u, hi.z, dh);
+        dl = dot4((q.w >> s0) & 0x03030303u, lo.w, dl); dh = dot4((q.w >> s1) & 0x03030303u, hi.w, dh);
+        const int16_t *bs = A.bs + (size_t)t * (A.K >> 4) + sb * 16 + 4 * c + h;
+        isum = dl + dh - ((int)bs[0] + (int)bs[2]); msum = 0;
+    }
+    __device__ __forceinline__ float dot(const ActLds &A, int t, int lane) const {
+        if (!valid) return 0.0f;
+        int isum, msum;
+        ints(A, t, lane, isum, msum);
+        const float yd = A.d[(size_t)t * (A.K >> 8) + sb];
+        return (d * yd) * (float)isum;
+    }
+};
+
+// ---- TQ1_0 : device row planes [qs nb*48][qh nb*4][d nb*2], five trits to a byte as in the file.  Lane v of a super-block owns elements 32 v .. 32 v + 31
+// (tq1_lane_dot in quant_dev.h: which pieces and trit positions that is); isum = dot(codes, a) - sum a (ggml_vec_dot_tq1_0_q8_K) ----------
+template <> struct Item<T_TQ1_0> {
+    uint4 hdr;                        // x: the four qh bytes, y: d (f16)
+    static constexpr int EPP = 2048;
+    uint4 q0, q1;
+    float d;
+    int sb;
+    bool valid;
+    __device__ __forceinline__ void load(const uint8_t *row, int K, int pass, int lane) {
+        const int nb = K >> 8;
+        sb = pass * 8 + (lane >> 3);
+        valid = sb < nb;
+        if (valid) {
+            const int v = lane & 7;
+            q0 = ld16w(row + (size_t)sb * 48 + tq1_piece0(v));
+            q1 = ld16w(row + (size_t)sb * 48 + tq1_piece1(v));
+            hdr.x = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 48 + (size_t)sb * 4);
+            hdr.y = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 52 + (size_t)sb * 2);
+        }
+    }
+    __device__ __forceinline__ void prep(int lane) {
+        if (valid) d = h2f((uint16_t)hdr.y);
+    }
+    __device__ __forceinline__ void ints(const ActLds &A, int t, int lane, int &isum, int &msum) const {
+        const int v = lane & 7;
+        const int8_t *a = A.qs + (size_t)t * A.K + sb * 256 + 32 * v;
+        const uint4 lo = ld16(a), hi = ld16(a + 16);
+        const int16_t *bs = A.bs + (size_t)t * (A.K >> 4) + sb * 16 + 2 * v;
+        isum = tq1_lane_dot(q0, q1, hdr.x, v, lo, hi) - ((int)bs[0] + (int)bs[1]); msum = 0;
+    }
+    __device__ __forceinline__ float dot(const ActLds &A, int t, int lane) const {
+        if (!valid) return 0.0f;
+        int isum, msum;
+        ints(A, t, lane, isum, msum);
+        const float yd = A.d[(size_t)t * (A.K >> 8) + sb];
+        return (d * yd) * (float)isum;
+    }
+};
+
 // ---- Q8_0 : device row planes [qs K][d K/32 f16] -------------------------------------------------
 // 32-element formats with a nibble field (Q4_0, Q5_0, IQ4_NL; activation Q8_0): two lanes per block as for Q8_0, lane half h = (e >> 4) & 1 takes
 // nibble h of the block's 16 code bytes (element j in the low nibbles, j + 16 in the high ones).  Integer sums exact:
@@ -764,6 +849,8 @@ __global__ __launch_bounds__(BS) void mmvq_kernel(const MMVQArgs a) {
         case T_Q5_1: run_segment<T_Q5_1, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_MXFP4: run_segment<T_MXFP4, NT, BS>(a, a.seg[s], smem, bis); break;
         case T_IQ4_XS: run_segment<T_IQ4_XS, NT, BS>(a, a.seg[s], smem, bis); break;
+        case T_TQ1_0: run_segment<T_TQ1_0, NT, BS>(a, a.seg[s], smem, bis); break;
+        case T_TQ2_0: run_segment<T_TQ2_0, NT, BS>(a, a.seg[s], smem, bis); break;
         default: break;
     }
 }
@@ -899,6 +986,8 @@ __global__ __launch_bounds__(256, 2) void mmvq_tiled_kernel(const MMVQArgs a) {
         case T_Q5_1: run_tiled<T_Q5_1, NT>(a, a.seg[s], smem, bis); break;
         case T_MXFP4: run_tiled<T_MXFP4, NT>(a, a.seg[s], smem, bis); break;
         case T_IQ4_XS: run_tiled<T_IQ4_XS, NT>(a, a.seg[s], smem, bis); break;
+        case T_TQ1_0: run_tiled<T_TQ1_0, NT>(a, a.seg[s], smem, bis); break;
+        case T_TQ2_0: run_tiled<T_TQ2_0, NT>(a, a.seg[s], smem, bis); break;
         default: break;
     }
 }
@@ -1073,6 +1162,8 @@ hipError_t launch_mmvq_ints(MMVQArgs a, int32_t *isum, int32_t *msum, hipStream_
         case T_Q5_1: hipLaunchKernelGGL(mmvq_ints_kernel<T_Q5_1>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_MXFP4: hipLaunchKernelGGL(mmvq_ints_kernel<T_MXFP4>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         case T_IQ4_XS: hipLaunchKernelGGL(mmvq_ints_kernel<T_IQ4_XS>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
+        case T_TQ1_0: hipLaunchKernelGGL(mmvq_ints_kernel<T_TQ1_0>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
+        case T_TQ2_0: hipLaunchKernelGGL(mmvq_ints_kernel<T_TQ2_0>, dim3(blocks), dim3(256), lds, st, a, isum, msum); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

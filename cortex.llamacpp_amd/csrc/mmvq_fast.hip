@@ -68,6 +68,31 @@ __global__ __launch_bounds__(NT) void mmvq_fast_kernel(const MMVQArgs a) {
     }
 }
 
+// TQ1_0 / TQ2_0 launches: the same kernel with the ternary decoders only (a launch is ternary in every segment or in none, mmvq_fast_applicable), so the
+// kernel above holds no code of theirs and keeps its registers
+template <int KB, int NT, int FUSE>
+__global__ __launch_bounds__(NT) void mmvq_fast_ternary_kernel(const MMVQArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr int NW = NT / 64;
+    int s = 0;
+    if (a.n_seg > 1 && (int)blockIdx.x >= a.seg_block0[1]) s = 1;
+    if (a.n_seg > 2 && (int)blockIdx.x >= a.seg_block0[2]) s = 2;
+    int nblk = a.seg_block0[s + 1] - a.seg_block0[s];
+    int bl = (int)blockIdx.x - a.seg_block0[s];
+    int sel_j = 0;
+    if (a.n_sel > 1) {                       // the selected experts of one token share the launch: an even share of workgroups each
+        const int per = nblk / a.n_sel;
+        sel_j = bl / per < a.n_sel ? bl / per : a.n_sel - 1;
+        bl -= sel_j * per;
+        nblk = sel_j == a.n_sel - 1 ? nblk - sel_j * per : per;
+    }
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gw = bl * NW + wave;
+    const int nw = nblk * NW;
+    if (a.seg[s].type == T_TQ1_0) run_fast<T_TQ1_0, KB, NT, FUSE>(a, a.seg[s], smem, gw, nw, NoSync(), sel_j);
+    else if (a.seg[s].type == T_TQ2_0) run_fast<T_TQ2_0, KB, NT, FUSE>(a, a.seg[s], smem, gw, nw, NoSync(), sel_j);
+}
+
 }  // namespace
 
 bool mmvq_fast_applicable(const MMVQArgs &a) {
@@ -77,7 +102,8 @@ bool mmvq_fast_applicable(const MMVQArgs &a) {
     const int n = a.epi == EPI_SWIGLU ? 2 : a.n_seg;
     for (int s = 0; s < n; s++) {
         const int t = a.seg[s].type;
-        if (t != T_Q4_K && t != T_Q5_K && t != T_Q6_K && t != T_Q2_K && t != T_Q3_K && t != T_IQ4_XS && !act_is_q80(t)) return false;
+        if (type_is_ternary(t) != type_is_ternary(a.seg[0].type)) return false;   // (the ternary types have a kernel of their own: all segments or none)
+        if (t != T_Q4_K && t != T_Q5_K && t != T_Q6_K && t != T_Q2_K && t != T_Q3_K && t != T_IQ4_XS && !type_is_ternary(t) && !act_is_q80(t)) return false;
         // segments may mix K-quants and Q8_0 (8-expert files keep attn_k / attn_v in Q8_0): every workgroup stages the
         // activation in the format of ITS segment; pre-quantised planes must exist in that format
         if (a.fuse_mode == 0) {
@@ -139,11 +165,13 @@ hipError_t launch_mmvq_fast(MMVQArgs a, hipStream_t st) {
     // persistent grid, one workgroup per CU.  8 waves per CU measured better than 12 on the whole decode step
     // (tools/profile_decode.py: 2.05 vs 2.13 ms / token); MI355_MMVQ_NT=768 selects the 12-wave form for K <= 4096
     int nt = 512;
-    if (kb <= 2 && g_fast_nt == 768) nt = 768;
+    const bool tern = type_is_ternary(a.seg[0].type);          // (their kernel: the 8-wave form only)
+    if (kb <= 2 && g_fast_nt == 768 && !tern) nt = 768;
     const size_t lds = mmvq_fast_plan(a, num_cu(), nt / 64);
     if (!lds) return hipErrorInvalidValue;
     const int blocks = a.seg_block0[3];
-#define FAST(KBV, NTV, FZ) hipLaunchKernelGGL((mmvq_fast_kernel<KBV, NTV, FZ>), dim3(blocks), dim3(NTV), lds, st, a)
+#define FAST(KBV, NTV, FZ) do { if constexpr (NTV == 512) { if (tern) { hipLaunchKernelGGL((mmvq_fast_ternary_kernel<KBV, 512, FZ>), dim3(blocks), dim3(512), lds, st, a); break; } } \
+                                hipLaunchKernelGGL((mmvq_fast_kernel<KBV, NTV, FZ>), dim3(blocks), dim3(NTV), lds, st, a); } while (0)
 #define FAST_F(KBV, NTV) do { if (a.fuse_mode == 0) FAST(KBV, NTV, 0); else if (a.fuse_mode == 1) FAST(KBV, NTV, 1); else FAST(KBV, NTV, 2); } while (0)
     switch (kb) {
         case 1: if (nt == 768) FAST_F(1, 768); else FAST_F(1, 512); break;

@@ -335,6 +335,46 @@ template <> struct Raw<T_IQ4_XS> {
     }
 };
 
+// ---------------------------------------------------------------- TQ2_0 (device row planes: qs | d)
+// the code bytes are laid out as Q2_K's, so the lane role and the activation slice are Q2_K's: lane (c, h) takes bytes 16 h .. + 15 of half c / 2 and the
+// fields 2 (c & 1), + 1; codes 0..2 (3 where a hostile byte says so) for weights (code - 1) d: dot(codes, a) minus the two 16-sums of the slice
+template <> struct Raw<T_TQ2_0> {
+    u32x4_t q;
+    uint32_t dh16;
+    __device__ __forceinline__ float probe() const { return (float)(q.x ^ q.y ^ q.z ^ q.w ^ dh16); }
+    __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
+        q = ldw(row + (size_t)sb * 64 + (L.c >> 1) * 32 + L.h * 16);
+        dh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 64 + (size_t)sb * 2);
+    }
+    __device__ __forceinline__ float dot(const ActSlice &A, const LaneRole &L) const {
+        const int s0 = 4 * (L.c & 1), s1 = s0 + 2;
+        int dl = 0, dh = 0;
+        dl = dot4((q.x >> s0) & 0x03030303u, A.lo.x, dl); dh = dot4((q.x >> s1) & 0x03030303u, A.hi.x, dh);
+        dl = dot4((q.y >> s0) & 0x03030303u, A.lo.y, dl); dh = dot4((q.y >> s1) & 0x03030303u, A.hi.y, dh);
+        dl = dot4((q.z >> s0) & 0x03030303u, A.lo.z, dl); dh = dot4((q.z >> s1) & 0x03030303u, A.hi.z, dh);
+        dl = dot4((q.w >> s0) & 0x03030303u, A.lo.w, dl); dh = dot4((q.w >> s1) & 0x03030303u, A.hi.w, dh);
+        return (h2f((uint16_t)dh16) * A.yd) * (float)(dl + dh - (A.bs_lo + A.bs_hi));
+    }
+};
+
+// ---------------------------------------------------------------- TQ1_0 (device row planes: qs | qh | d, five trits to a byte as in the file)
+// IQ4_XS's slice (lane v: codes 32 v .. 32 v + 31) with the two 16-sums kept; which pieces and trit positions those elements are: tq1_lane_dot, quant_dev.h
+template <> struct Raw<T_TQ1_0> {
+    u32x4_t q0, q1;
+    uint32_t qh, dh16;
+    __device__ __forceinline__ float probe() const { return (float)(q0.x ^ q0.y ^ q0.z ^ q0.w ^ q1.x ^ q1.y ^ q1.z ^ q1.w ^ qh ^ dh16); }
+    __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
+        q0 = ldw(row + (size_t)sb * 48 + tq1_piece0(L.v));
+        q1 = ldw(row + (size_t)sb * 48 + tq1_piece1(L.v));
+        qh = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 48 + (size_t)sb * 4);
+        dh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 52 + (size_t)sb * 2);
+    }
+    __device__ __forceinline__ float dot(const ActSlice &A, const LaneRole &L) const {
+        const int s = tq1_lane_dot(q0, q1, qh, L.v, A.lo, A.hi);
+        return (h2f((uint16_t)dh16) * A.yd) * (float)(s - (A.bs_lo + A.bs_hi));
+    }
+};
+
 template <int TYPE> __device__ __forceinline__ LaneRole make_role(int lane) {
     LaneRole L;
     if (role_wide<TYPE>()) { L.sbl = lane >> 2; L.c = lane & 3; L.v = 2 * L.c; L.h = 0; }
@@ -367,6 +407,11 @@ __device__ __forceinline__ ActSlice read_slice(const ActL &A, int sb, const Lane
         const int8_t *a = A.qs + sb * 256 + 32 * L.v;
         s.lo = lds16(a); s.hi = lds16(a + 16);
         s.bs_lo = 0; s.bs_hi = 0;
+    } else if (TYPE == T_TQ1_0) {      // sub-block v's 32 codes and their two 16-sums
+        const int8_t *a = A.qs + sb * 256 + 32 * L.v;
+        s.lo = lds16(a); s.hi = lds16(a + 16);
+        const int16_t *b = A.bs + sb * 16 + 2 * L.v;
+        s.bs_lo = b[0]; s.bs_hi = b[1];
     } else if (TYPE == T_Q6_K) {
         const int8_t *a = A.qs + sb * 256 + 128 * L.n + 16 * L.w;
         s.lo = lds16(a); s.hi = lds16(a + 64);
@@ -409,6 +454,11 @@ __device__ __forceinline__ ActSlice global_slice(const MMVQArgs &a, int sb, cons
         const int qo = sb * 256 + 32 * L.v;
         s.lo = cld16<COH>(a.aq, qo); s.hi = cld16<COH>(a.aq, qo + 16);
         s.bs_lo = 0; s.bs_hi = 0;
+    } else if (TYPE == T_TQ1_0) {
+        const int qo = sb * 256 + 32 * L.v;
+        s.lo = cld16<COH>(a.aq, qo); s.hi = cld16<COH>(a.aq, qo + 16);
+        const int bo = (sb * 16 + 2 * L.v) * 2;
+        s.bs_lo = cld2s<COH>(a.abs, bo); s.bs_hi = cld2s<COH>(a.abs, bo + 2);
     } else if (TYPE == T_Q6_K) {
         const int qo = sb * 256 + 128 * L.n + 16 * L.w;
         s.lo = cld16<COH>(a.aq, qo); s.hi = cld16<COH>(a.aq, qo + 64);

@@ -40,7 +40,7 @@ namespace mi355 {
 namespace {
 
 // ---- one mat-vec per launch
-template <int KB, int FUSE, bool MOE>
+template <int KB, int FUSE, bool MOE, bool TERN = false>
 __device__ __forceinline__ void stream_body(const MMVQArgs &ka) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 #ifdef MI355_STREAM_PROBE
@@ -78,7 +78,7 @@ __device__ __forceinline__ void stream_body(const MMVQArgs &ka) {
         ST_STAMP(5);
         return;
     }
-    consumer_dispatch<KB, FUSE>(a, smem, wave - ST_NL, 0u, st_layout(KB));
+    consumer_dispatch<KB, FUSE, 0, false, TERN>(a, smem, wave - ST_NL, 0u, st_layout(KB));
 }
 // ---- the STREAM-BOUND roles (gate | up, the output head): the launch ends when its stream does, so the stream's first request is what counts (round 5).
 // The launch's geometry is packed once more into the kernel's FIRST 14 argument dwords - scalars the hardware preloads into SGPRs (build.py:
@@ -214,6 +214,10 @@ MI355_ST_KERNEL(mmvq_stream_gate_up)
 MI355_ST_KERNEL(mmvq_stream_ffn_down)
 MI355_ST_KERNEL(mmvq_stream_head)
 #undef MI355_ST_KERNEL
+// TQ1_0 / TQ2_0 launches, whatever their role: the same body with the ternary decoders only (a launch is ternary in every segment or in none,
+// mmvq_stream_applicable), so the kernels above hold no code of theirs
+template <int KB, int FUSE, bool MOE = false>
+__global__ __launch_bounds__(ST_NT) void mmvq_stream_ternary(const MMVQArgs ka) { stream_body<KB, FUSE, MOE, true>(ka); }
 
 }  // namespace
 
@@ -254,7 +258,8 @@ bool mmvq_stream_applicable(const MMVQArgs &a) {
     for (int s = 0; s < (swiglu ? 2 : n); s++) {
         const MMVQSeg &g = a.seg[s];
         const int t = g.type;
-        if (t != T_Q4_K && t != T_Q5_K && t != T_Q6_K && t != T_Q8_0 && t != T_Q2_K && t != T_Q3_K && t != T_Q4_0 && t != T_Q5_0 && t != T_IQ4_NL && t != T_IQ4_XS && !nib32_has_min(t) && t != T_MXFP4) return false;
+        if (type_is_ternary(t) != type_is_ternary(a.seg[0].type)) return false;  // (the ternary types have a kernel of their own: all segments or none)
+        if (t != T_Q4_K && t != T_Q5_K && t != T_Q6_K && t != T_Q8_0 && t != T_Q2_K && t != T_Q3_K && t != T_Q4_0 && t != T_Q5_0 && t != T_IQ4_NL && t != T_IQ4_XS && !nib32_has_min(t) && t != T_MXFP4 && !type_is_ternary(t)) return false;
         if (g.expert_sel && (s != 0 && !(swiglu && s == 1))) return false;      // experts on segment 0 (and the up tensor of its pair) only
         if ((g.row_bytes % 16) != 0 || g.row_bytes < 512) return false;         // (512: a Q2_K row of K = 2048 - TinyLlama's hidden size in the smoke model's file - is 672 B)
         if (g.row_bytes > (size_t)ST_MAX_STEP) return false;
@@ -408,6 +413,39 @@ hipError_t launch_mmvq_stream(MMVQArgs a, hipStream_t st) {
         if (e != hipSuccess) return e;                                                                                   \
         hipLaunchKernelGGL((mmvq_stream_kernel<KBV, FZ, true>), dim3(blocks), dim3(ST_NT), lds, st, a);                 \
     } while (0)
+    if (type_is_ternary(a.seg[0].type)) {                        // one kernel name for every role, no preloaded-argument forms; the (K, prologue) forms of the other types
+#define STREAM_TM(KBV, FZ)                                                                                               \
+    do {                                                                                                                 \
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mmvq_stream_ternary<KBV, FZ, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (e != hipSuccess) return e;                                                                                   \
+        hipLaunchKernelGGL((mmvq_stream_ternary<KBV, FZ, true>), dim3(blocks), dim3(ST_NT), lds, st, a);                \
+    } while (0)
+#define STREAM_TF(KBV) do { if (a.fuse_mode == 0) STREAM_K(mmvq_stream_ternary, KBV, 0); else if (a.fuse_mode == 1) STREAM_K(mmvq_stream_ternary, KBV, 1); else STREAM_K(mmvq_stream_ternary, KBV, 2); } while (0)
+#define STREAM_TW(KBV) do { if (a.fuse_mode == 2) STREAM_K(mmvq_stream_ternary, KBV, 2); else if (a.fuse_mode == 0) STREAM_K(mmvq_stream_ternary, KBV, 0); else return hipErrorInvalidValue; } while (0)
+        if (a.n_sel > 1 || a.seg[0].expert_sel) {
+            if (a.fuse_mode == 1 && kb == 1) STREAM_TM(1, 1);
+            else if (a.fuse_mode == 1 && kb == 2) STREAM_TM(2, 1);
+            else if (a.fuse_mode == 2 && kb == 2) STREAM_TM(2, 2);
+            else if (a.fuse_mode == 2 && kb == 4) STREAM_TM(4, 2);
+            else if (a.fuse_mode == 2 && kb == 7) STREAM_TM(7, 2);
+            else return hipErrorInvalidValue;
+            goto STREAM_DONE;
+        }
+        switch (kb) {
+            case 1: STREAM_TF(1); break;
+            case 2: STREAM_TF(2); break;
+            case 3: STREAM_TF(3); break;
+            case 4: STREAM_TF(4); break;
+            case 6: STREAM_TW(6); break;
+            case 7: STREAM_TW(7); break;
+            case 10: STREAM_TW(10); break;
+            default: return hipErrorInvalidValue;
+        }
+#undef STREAM_TW
+#undef STREAM_TF
+#undef STREAM_TM
+        goto STREAM_DONE;
+    }
     if (a.n_sel > 1 || a.seg[0].expert_sel) {
         if (a.fuse_mode == 1 && kb == 1) STREAM_MOE(1, 1);
         else if (a.fuse_mode == 1 && kb == 2) STREAM_MOE(2, 1);

@@ -174,6 +174,16 @@ template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_IQ4_XS> &r, c
     r.sh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 132u + (unsigned)sb * 2u));
     r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 134u + (unsigned)sb * 2u));
 }
+template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_TQ2_0> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
+    r.q = lds16(RO(row_off + (unsigned)sb * 64u + (unsigned)(L.c >> 1) * 32u + (unsigned)L.h * 16u));
+    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 64u + (unsigned)sb * 2u));
+}
+template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_TQ1_0> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
+    r.q0 = lds16(RO(row_off + (unsigned)sb * 48u + tq1_piece0(L.v)));
+    r.q1 = lds16(RO(row_off + (unsigned)sb * 48u + tq1_piece1(L.v)));
+    r.qh = *reinterpret_cast<const uint32_t *>(RO(row_off + (unsigned)nb * 48u + (unsigned)sb * 4u));
+    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 52u + (unsigned)sb * 2u));
+}
 #undef RO
 
 // ---- LDS layout (bytes from smem): sync words | reduction scratch | ring | activation of the current mat-vec
@@ -757,7 +767,9 @@ __device__ __forceinline__ void consumer_op(const StOp &a, uint8_t *smem, int c,
 }
 // forms that exist: SwiGLU pairs only with the fused RMSNorm prologue (gate/up), row pairs up to K = 8192, single rows
 // from K = 6144 (mmvq_stream_applicable agrees)
-template <int KB, int FUSE, int ENG = 0, bool EARLY = false>
+// TERN: the kernel of the ternary types (TQ1_0, TQ2_0) - a launch of their own (mmvq_stream.hip mmvq_stream_ternary), so that every other kernel keeps the
+// registers it had without their decoders
+template <int KB, int FUSE, int ENG = 0, bool EARLY = false, bool TERN = false>
 __device__ __forceinline__ void consumer_dispatch(const StOp &a, uint8_t *smem, int c, unsigned g0, const StLayout &lay, const EngIO &io = EngIO(), const EarlyAct<KB> *ea = nullptr) {
 #define RUN(TY)                                                                                               \
     do {                                                                                                      \
@@ -765,6 +777,12 @@ __device__ __forceinline__ void consumer_dispatch(const StOp &a, uint8_t *smem, 
         else if (a.pair) { if constexpr (KB <= 4 || ENG == 0) consumer_op<TY, KB, FUSE, false, true, ENG, EARLY>(a, smem, c, g0, lay, io, ea); } \
         else { if constexpr (KB >= 3) consumer_op<TY, KB, FUSE, false, false, ENG, EARLY>(a, smem, c, g0, lay, io, ea); } \
     } while (0)
+    if constexpr (TERN) {
+        if constexpr (ENG == 0) {                              // every form IQ4_XS takes
+            if (a.type == T_TQ1_0) RUN(T_TQ1_0);
+            else if (a.type == T_TQ2_0) RUN(T_TQ2_0);
+        }
+    } else
     switch (a.type) {
         case T_Q4_K: RUN(T_Q4_K); break;
         case T_Q5_K: RUN(T_Q5_K); break;

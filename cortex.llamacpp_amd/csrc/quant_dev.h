@@ -135,6 +135,47 @@ __device__ __forceinline__ int iq4xs_scale(uint32_t scales_l, uint32_t scales_h,
     return (int)(((scales_l >> (4 * ib)) & 0xfu) | (((scales_h >> (2 * ib)) & 3u) << 4)) - 32;
 }
 
+// TQ1_0: a byte b holds five trits, trit n = ((uint8)(b * 3^n) * 3) >> 8 (the product wraps to 8 bits first), defined for all 256 byte values
+__device__ __forceinline__ int tq1_trit(uint32_t b, int n) {
+    const uint32_t p = n == 0 ? 1u : n == 1 ? 3u : n == 2 ? 9u : n == 3 ? 27u : 81u;
+    return (int)((((b * p) & 0xffu) * 3u) >> 8);
+}
+// the same trit of the four bytes of a word, one code (0..2) per byte, p = 3^n: the bytes are multiplied two at a time in 16-bit lanes (255 * 81 and
+// 255 * 3 stay below 2^16, so a lane never carries into its neighbour; 0x00ff00ff and p are 24-bit operands: v_mul_u32_u24).  12 VALU operations per four weights
+__device__ __forceinline__ uint32_t tq1_codes4(uint32_t w, uint32_t p) {
+    const uint32_t e = __umul24(__umul24(w & 0x00ff00ffu, p) & 0x00ff00ffu, 3u);            // bytes 0, 2: the trit sits in bits 8..9 of its lane
+    const uint32_t o = __umul24(__umul24((w >> 8) & 0x00ff00ffu, p) & 0x00ff00ffu, 3u);     // bytes 1, 3
+    return ((e >> 8) & 0x00030003u) | (o & 0x03000300u);
+}
+// byte and trit index of element r (0..255) of a TQ1_0 block: qs[0..31] hold elements 32 n + m, qs[32..47] elements 160 + 16 n + m, qh[0..3] elements 240 + 4 n + j
+__device__ __forceinline__ void tq1_elem(int r, int &byte, int &n) {
+    if (r < 160) { n = r >> 5; byte = r & 31; }
+    else if (r < 240) { n = (r - 160) >> 4; byte = 32 + ((r - 160) & 15); }
+    else { n = (r - 240) >> 2; byte = 48 + ((r - 240) & 3); }
+}
+// The mat-vec lane role of TQ1_0 (mmvq.hip, mmvq_fast_dev.h, the weight stream: one role, so the three agree bit for bit).  Lane v (0..7) of a super-block
+// owns elements 32 v .. 32 v + 31, which the packing puts in ONE trit position of 16-byte pieces of the block:
+//   v = 0..4 : trit v of qs[0..31]                                          q0 = qs[0..15], q1 = qs[16..31]
+//   v = 5, 6 : trits 2 (v - 5) and 2 (v - 5) + 1 of qs[32..47]              q0 = q1 = qs[32..47]
+//   v = 7    : trit 4 of qs[32..47], then trits 0..3 of the four qh bytes   q0 = qs[32..47], the qh word four times
+// lo / hi: the activation codes 32 v .. + 15 and 32 v + 16 .. + 31.  Returns dot(codes, a) with codes 0..2; the caller subtracts the sum of the 32 a.
+__device__ __forceinline__ unsigned tq1_piece0(int v) { return v < 5 ? 0u : 32u; }
+__device__ __forceinline__ unsigned tq1_piece1(int v) { return v < 5 ? 16u : 32u; }
+template <class V4>
+__device__ __forceinline__ int tq1_lane_dot(const V4 &q0, const V4 &q1, uint32_t qh, int v, const V4 &lo, const V4 &hi) {
+    const uint32_t p0 = (uint32_t)(0x510901511b090301ull >> (8 * v)) & 0xffu;       // 3^n of the lane's first trit position, per v
+    const uint32_t p1 = (uint32_t)(0x011b03511b090301ull >> (8 * v)) & 0xffu;       // ... of its second one (v = 7: 3^0, the first of qh's)
+    const bool tail = v == 7;
+    int s = 0;
+    s = dot4(tq1_codes4(q0.x, p0), lo.x, s); s = dot4(tq1_codes4(q0.y, p0), lo.y, s);
+    s = dot4(tq1_codes4(q0.z, p0), lo.z, s); s = dot4(tq1_codes4(q0.w, p0), lo.w, s);
+    s = dot4(tq1_codes4(tail ? qh : q1.x, p1), hi.x, s);
+    s = dot4(tq1_codes4(tail ? qh : q1.y, tail ? 3u : p1), hi.y, s);
+    s = dot4(tq1_codes4(tail ? qh : q1.z, tail ? 9u : p1), hi.z, s);
+    s = dot4(tq1_codes4(tail ? qh : q1.w, tail ? 27u : p1), hi.w, s);
+    return s;
+}
+
 __device__ __forceinline__ float dequant_elem(int type, const uint8_t *row, int K, int e) {
     switch (type) {
         case T_F32: return reinterpret_cast<const float *>(row)[e];
@@ -206,6 +247,18 @@ __device__ __forceinline__ float dequant_elem(int type, const uint8_t *row, int 
             const uint32_t sh = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 132 + (size_t)sb * 2);
             const float d = h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 134 + (size_t)sb * 2));
             return __fmul_rn(__fmul_rn(d, (float)iq4xs_scale(sl, sh, ib)), (float)iq4nl_value(nib));
+        }
+        case T_TQ2_0: {   // element 128 h + 32 l + m: bits 2 l .. 2 l + 1 of qs[32 h + m]; dequantize_row_tq2_0: y = (q - 1) * d (a product: - 0.0 where it gives one)
+            const int nb = K >> 8, sb = e >> 8, r = e & 255;
+            const int q = (row[(size_t)sb * 64 + 32 * (r >> 7) + (r & 31)] >> (2 * ((r >> 5) & 3))) & 3;
+            return __fmul_rn((float)(q - 1), h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 64 + (size_t)sb * 2)));
+        }
+        case T_TQ1_0: {
+            const int nb = K >> 8, sb = e >> 8;
+            int byte, n;
+            tq1_elem(e & 255, byte, n);
+            const uint32_t b = byte < 48 ? row[(size_t)sb * 48 + byte] : row[(size_t)nb * 48 + (size_t)sb * 4 + (byte - 48)];
+            return __fmul_rn((float)(tq1_trit(b, n) - 1), h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 52 + (size_t)sb * 2)));
         }
         case T_Q6_K: {
             const int nb = K >> 8, sb = e >> 8, r = e & 255, n = r >> 7, rr = r & 127, k = rr >> 5, l = rr & 31;

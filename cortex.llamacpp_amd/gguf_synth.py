@@ -24,9 +24,10 @@ Q4_1, Q5_1 = 3, 7
 IQ4_XS = 23
 BF16 = 30
 MXFP4 = 39
-TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K", Q2_K: "q2_K", Q3_K: "q3_K", Q5_0: "q5_0", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", BF16: "bf16", Q4_1: "q4_1", Q5_1: "q5_1", MXFP4: "mxfp4"}
-BLOCK_ELEMS = {F32: 1, F16: 1, Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q2_K: 256, Q3_K: 256, Q5_0: 32, IQ4_NL: 32, IQ4_XS: 256, BF16: 1, Q4_1: 32, Q5_1: 32, MXFP4: 32}
-BLOCK_BYTES = {F32: 4, F16: 2, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q2_K: 84, Q3_K: 110, Q5_0: 22, IQ4_NL: 18, IQ4_XS: 136, BF16: 2, Q4_1: 20, Q5_1: 24, MXFP4: 17}
+TQ1_0, TQ2_0 = 34, 35
+TYPE_NAME = {F32: "f32", F16: "f16", Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K", Q2_K: "q2_K", Q3_K: "q3_K", Q5_0: "q5_0", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", BF16: "bf16", Q4_1: "q4_1", Q5_1: "q5_1", MXFP4: "mxfp4", TQ1_0: "tq1_0", TQ2_0: "tq2_0"}
+BLOCK_ELEMS = {F32: 1, F16: 1, Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q2_K: 256, Q3_K: 256, Q5_0: 32, IQ4_NL: 32, IQ4_XS: 256, BF16: 1, Q4_1: 32, Q5_1: 32, MXFP4: 32, TQ1_0: 256, TQ2_0: 256}
+BLOCK_BYTES = {F32: 4, F16: 2, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q2_K: 84, Q3_K: 110, Q5_0: 22, IQ4_NL: 18, IQ4_XS: 136, BF16: 2, Q4_1: 20, Q5_1: 24, MXFP4: 17, TQ1_0: 54, TQ2_0: 66}
 
 DT_Q4_0 = np.dtype([("d", "<f2"), ("qs", "u1", 16)])
 DT_Q8_0 = np.dtype([("d", "<f2"), ("qs", "i1", 32)])
@@ -44,7 +45,14 @@ DT_MXFP4 = np.dtype([("e", "u1"), ("qs", "u1", 16)])
 KVALUES_MXFP4 = np.array([0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12], np.int8)      # the e2m1 values doubled
 # IQ4_XS: 6-bit sub-block scales ls (low nibbles in scales_l, high bit pairs in scales_h), weight = d * (ls - 32) * kvalues_iq4nl[nibble]
 DT_IQ4_XS = np.dtype([("d", "<f2"), ("scales_h", "<u2"), ("scales_l", "u1", 4), ("qs", "u1", 128)])
-BLOCK_DTYPE = {Q4_0: DT_Q4_0, Q8_0: DT_Q8_0, Q4_K: DT_Q4_K, Q5_K: DT_Q5_K, Q6_K: DT_Q6_K, Q2_K: DT_Q2_K, Q3_K: DT_Q3_K, Q5_0: DT_Q5_0, IQ4_NL: DT_Q4_0, IQ4_XS: DT_IQ4_XS, Q4_1: DT_Q4_1, Q5_1: DT_Q5_1, MXFP4: DT_MXFP4}
+# the ternary types: 256 codes 0..2 per block and one f16 scale, weight = (code - 1) * d.  TQ2_0: element 128 h + 32 l + m is bits 2 l .. 2 l + 1 of qs[32 h + m].
+# TQ1_0: five trits to a byte (four in a qh byte), trit n of byte b = ((b * 3^n mod 256) * 3) >> 8; qs[0..31] hold elements 32 n + m, qs[32..47] elements
+# 160 + 16 n + m, qh[0..3] elements 240 + 4 n + j (tq1_element_map).  Restated from upstream's generic-scalar code as remembered; its source is not available
+# where this was written, so the layout cannot be pinned against it here.
+DT_TQ1_0 = np.dtype([("qs", "u1", 48), ("qh", "u1", 4), ("d", "<f2")])
+DT_TQ2_0 = np.dtype([("qs", "u1", 64), ("d", "<f2")])
+POW3 = np.array([1, 3, 9, 27, 81], np.uint32)
+BLOCK_DTYPE = {Q4_0: DT_Q4_0, Q8_0: DT_Q8_0, Q4_K: DT_Q4_K, Q5_K: DT_Q5_K, Q6_K: DT_Q6_K, Q2_K: DT_Q2_K, Q3_K: DT_Q3_K, Q5_0: DT_Q5_0, IQ4_NL: DT_Q4_0, IQ4_XS: DT_IQ4_XS, Q4_1: DT_Q4_1, Q5_1: DT_Q5_1, MXFP4: DT_MXFP4, TQ1_0: DT_TQ1_0, TQ2_0: DT_TQ2_0}
 for _t, _dt in BLOCK_DTYPE.items():
     assert _dt.itemsize == BLOCK_BYTES[_t], (_t, _dt.itemsize)
 
@@ -53,7 +61,8 @@ for _t, _dt in BLOCK_DTYPE.items():
 _UNIT_STD = {Q4_0: 4.6, Q8_0: 73.9, Q4_K: 258.0, Q5_K: 527.0, Q6_K: 1367.0, Q2_K: 13.9, Q3_K: 43.3, Q5_0: 9.23, IQ4_NL: 67.2,
              IQ4_XS: 1246.3,   # (Q5_0: codes 0..31 minus 16; IQ4_NL: the sixteen code-book levels; IQ4_XS: (ls - 32) * level, ls 0..63: sqrt(341.5 * 4548))
              Q4_1: 4.61, Q5_1: 9.23,   # (codes uniform 0..15 / 0..31 around the minimum below: sqrt((16^2 - 1) / 12), sqrt((32^2 - 1) / 12))
-             MXFP4: 5.85}              # (the sixteen levels, uniform: sqrt(2 * 274 / 16))
+             MXFP4: 5.85,              # (the sixteen levels, uniform: sqrt(2 * 274 / 16))
+             TQ1_0: float(np.sqrt(2.0 / 3.0)), TQ2_0: float(np.sqrt(2.0 / 3.0))}    # (trits - 1, 0, 1 uniform)
 # dmin/d ratio that centres the weights of a random block on zero
 _DMIN_RATIO = {Q4_K: 7.5, Q5_K: 15.5, Q2_K: 1.5}
 # m/d ratio doing the same for the per-block minimum of Q4_1 / Q5_1 (weight = q d + m: minus the mean code)
@@ -82,6 +91,11 @@ def random_blocks(rng: np.random.Generator, t: int, n_elems: int, std: float) ->
     if t == BF16:                                            # the f32 draws that F16 rounds to half, rounded to bf16 instead
         return round_bf16(rng.standard_normal(n_elems, dtype=np.float32) * np.float32(std)).view(np.uint8)
     nb = n_elems // BLOCK_ELEMS[t]
+    if t in (TQ1_0, TQ2_0):                                  # well-formed codes: uniform trits (never TQ2_0's code 3 nor a TQ1_0 byte that no five trits encode)
+        blk = pack_ternary(t, rng.integers(0, 3, size=(nb, 256), dtype=np.uint8))
+        d = (rng.uniform(0.5, 1.5, size=nb) * (std / _UNIT_STD[t])).astype(np.float32)
+        blk["d"] = d.astype("<f2")
+        return blk.view(np.uint8).reshape(-1)
     raw = rng.integers(0, 256, size=nb * BLOCK_BYTES[t], dtype=np.uint8)
     blk = raw.view(BLOCK_DTYPE[t])
     if t == MXFP4:
@@ -97,6 +111,70 @@ def random_blocks(rng: np.random.Generator, t: int, n_elems: int, std: float) ->
     if t in _MIN_RATIO:
         blk["m"] = (d * _MIN_RATIO[t]).astype("<f2")
     return raw
+
+
+def tq1_element_map():
+    """(byte, n) of each of the 256 elements of a TQ1_0 block: byte indexes qs (0..47) then qh (48..51), n is the trit position in that byte."""
+    e = np.arange(256)
+    byte = np.where(e < 160, e % 32, np.where(e < 240, 32 + (e - 160) % 16, 48 + (e - 240) % 4))
+    n = np.where(e < 160, e // 32, np.where(e < 240, (e - 160) // 16, (e - 240) // 4))
+    return byte, n
+
+
+def pack_ternary(t: int, codes: np.ndarray) -> np.ndarray:
+    """codes [nb][256] (0..2; TQ2_0 also takes 3) as blocks of type t with d = 0.  TQ1_0 as quantize_row_tq1_0_ref packs: a byte's trits are accumulated
+    most significant first (q = q * 3 + trit, the trit of position 0 first), a qh byte takes four and is multiplied by 3 once more, and the byte stored is
+    (q * 256 + 242) / 243."""
+    codes = np.ascontiguousarray(codes).astype(np.uint32).reshape(-1, 256)
+    blk = np.zeros(codes.shape[0], BLOCK_DTYPE[t])
+    if t == TQ2_0:
+        c = codes.reshape(-1, 2, 4, 32)                     # [block][h][l][m]
+        blk["qs"] = (c[:, :, 0] | (c[:, :, 1] << 2) | (c[:, :, 2] << 4) | (c[:, :, 3] << 6)).reshape(-1, 64).astype(np.uint8)
+        return blk
+    assert t == TQ1_0 and codes.max(initial=0) <= 2
+    byte, n = tq1_element_map()
+    q = np.zeros((codes.shape[0], 52), np.uint32)
+    for pos in range(5):                                     # position 0 is the most significant digit
+        sel = n == pos
+        q[:, byte[sel]] = q[:, byte[sel]] * 3 + codes[:, sel]
+    q[:, 48:] *= 3                                           # four trits only: the fifth digit is zero
+    packed = ((q * 256 + 242) // 243).astype(np.uint8)
+    blk["qs"], blk["qh"] = packed[:, :48], packed[:, 48:]
+    return blk
+
+
+def unpack_ternary(t: int, raw: np.ndarray) -> np.ndarray:
+    """The codes [nb][256] of blocks of type t by the formats' formulas - defined for every byte value (TQ2_0: 0..3, TQ1_0: 0..2)."""
+    blk = np.ascontiguousarray(raw).view(np.uint8).reshape(-1).view(BLOCK_DTYPE[t])
+    if t == TQ2_0:
+        qs = blk["qs"].reshape(-1, 2, 1, 32)
+        return ((qs >> (2 * np.arange(4, dtype=np.uint8)).reshape(1, 1, 4, 1)) & 3).reshape(-1, 256).astype(np.uint8)
+    assert t == TQ1_0
+    byte, n = tq1_element_map()
+    b = np.concatenate([blk["qs"], blk["qh"]], axis=1).astype(np.uint32)[:, byte]
+    return ((((b * POW3[n][None, :]) & 0xff) * 3) >> 8).astype(np.uint8)
+
+
+def _quantize_ternary(t: int, x: np.ndarray) -> np.ndarray:
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 256)
+    d = np.abs(x).max(axis=1).astype(np.float32)
+    with np.errstate(divide="ignore"):
+        inv = np.where(d != 0, np.float32(1.0) / d, np.float32(0.0)).astype(np.float32)
+    v = (x * inv[:, None]).astype(np.float32)
+    xi = (np.sign(v) * np.floor(np.abs(v) + np.float32(0.5))).astype(np.int32) + 1          # lroundf: halves away from zero
+    blk = pack_ternary(t, xi.astype(np.uint32) & 3)
+    blk["d"] = d.astype("<f2")
+    return blk.view(np.uint8).reshape(-1)
+
+
+def quantize_tq1_0(x: np.ndarray) -> np.ndarray:
+    """x (f32, a multiple of 256 values) as TQ1_0 blocks (raw bytes) by quantize_row_tq1_0_ref: d = max |x|, id = d ? 1 / d : 0, trit = lroundf(x * id) + 1."""
+    return _quantize_ternary(TQ1_0, x)
+
+
+def quantize_tq2_0(x: np.ndarray) -> np.ndarray:
+    """As quantize_tq1_0 with TQ2_0's two-bit fields (quantize_row_tq2_0_ref: q |= (xi & 3) << 2 n)."""
+    return _quantize_ternary(TQ2_0, x)
 
 
 def quantize_min32(t: int, x: np.ndarray) -> np.ndarray:
@@ -350,7 +428,7 @@ CONFIGS = {
     "tiny-w320": LlamaConfig("tiny-w320", 320, 2, 5, 1, 608, 512, 1e6, 1e-6, 1024, arch="qwen2", qkv_bias=True),
 }
 
-FTYPE_ID = {"f16": 1, "bf16": 32, "q4_0": 2, "q4_1": 3, "q5_0": 8, "q5_1": 9, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18, "mxfp4": 38, "mxfp4_moe": 38}
+FTYPE_ID = {"f16": 1, "bf16": 32, "q4_0": 2, "q4_1": 3, "q5_0": 8, "q5_1": 9, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18, "mxfp4": 38, "mxfp4_moe": 38, "tq1_0": 36, "tq2_0": 37}
 
 
 def use_more_bits(i: int, n: int) -> bool:
@@ -369,7 +447,7 @@ def _row_len(cfg: LlamaConfig, kind: str) -> int:
 # llama-quantize's fallback for a tensor whose rows are not a whole number of 256-element super-blocks: the 32-element type nearest in bits per weight.
 # (Upstream's source is not available where this was written: the table is restated from its documented behaviour - the message "tensor cols not divisible
 # by 256, required for q4_K - using fallback quantization q5_0" - and cannot be pinned against it here.)
-FALLBACK_32 = {Q4_K: Q5_0, Q5_K: Q5_1, Q6_K: Q8_0, Q2_K: IQ4_NL, Q3_K: IQ4_NL, IQ4_XS: IQ4_NL}
+FALLBACK_32 = {Q4_K: Q5_0, Q5_K: Q5_1, Q6_K: Q8_0, Q2_K: IQ4_NL, Q3_K: IQ4_NL, IQ4_XS: IQ4_NL, TQ1_0: Q4_0, TQ2_0: Q4_0}
 
 
 def tensor_type(cfg: LlamaConfig, ftype: str, kind: str, il: int) -> int:
@@ -430,6 +508,16 @@ def mix_tensor_type(cfg: LlamaConfig, ftype: str, kind: str, il: int) -> int:
         if (kind == "attn_v" and cfg.n_head // cfg.n_head_kv >= 4) or (kind == "ffn_down" and il < max(1, cfg.n_layer // 8)):
             return Q5_K
         return IQ4_NL if _row_len(cfg, kind) % 256 else IQ4_XS
+    if ftype in ("tq1_0", "tq2_0"):
+        # LLAMA_FTYPE_MOSTLY_TQ1_0 / TQ2_0 as remembered from llama-quantize (unpinned like the fallback table): token_embd Q4_K, output Q6_K, every other 2-D
+        # weight the ternary type, expert tensors included; a tensor whose rows are not a multiple of 256 falls back to Q4_0 (by this rule itself, as the
+        # IQ4_XS mix does, so tensor_type and the mix agree on the older configs)
+        if kind == "token_embd":
+            return Q4_K
+        if kind == "output":
+            return Q6_K
+        t = TQ1_0 if ftype == "tq1_0" else TQ2_0
+        return FALLBACK_32[t] if _row_len(cfg, kind) % 256 else t
     if ftype in ("q3_k_s", "q3_k_l", "q4_k_s", "q5_k_s", "q6_k"):
         # the other mixes the reference publishes (.github/workflows/convert-model-all-quant.yml:106-152), by llama-quantize's rules for the llama
         # architecture: output Q6_K everywhere; Q3_K_S: everything else Q3_K; Q3_K_L: attn_v, ffn_down, attn_output Q5_K, the rest Q3_K; Q4_K_S: Q4_K

@@ -64,6 +64,8 @@ size_t ggml_type_row_bytes(int type, int64_t n) {
         case 23: be = 256; bb = 136; break; // iq4_xs
         case 30: be = 1; bb = 2; break;     // bf16
         case 39: be = 32; bb = 17; break;   // mxfp4
+        case 34: be = 256; bb = 54; break;  // tq1_0
+        case 35: be = 256; bb = 66; break;  // tq2_0
         case 12: be = 256; bb = 144; break; // q4_K
         case 13: be = 256; bb = 176; break; // q5_K
         case 14: be = 256; bb = 210; break; // q6_K
@@ -79,6 +81,7 @@ const char *ggml_type_name(int type) {
         case 6: return "q5_0"; case 7: return "q5_1"; case 8: return "q8_0"; case 10: return "q2_K";
         case 11: return "q3_K"; case 12: return "q4_K"; case 13: return "q5_K"; case 14: return "q6_K";
         case 15: return "q8_K"; case 23: return "iq4_xs"; case 30: return "bf16"; case 39: return "mxfp4";
+        case 34: return "tq1_0"; case 35: return "tq2_0";
     }
     return "unknown";
 }

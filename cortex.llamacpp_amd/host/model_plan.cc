@@ -189,7 +189,12 @@ bool Planner::type_refused(const std::string &name, const GGUFTensorInfo &ti) {
                           P > 1 ? "a row split (split_mode \"row\" / tp_size > 1) of mxfp4 tensors is not supported: load the file on one device" : nullptr;
         if (why) return !refuse("tensor " + name + " has type mxfp4: " + why);
     }
-    if (P > 1 && type_row_split_unsupported(ti.type))    // (Q4_1, Q5_1, IQ4_XS; an mxfp4 tensor has been refused above in its own words)
+    if (type_is_ternary(ti.type)) {
+        // tq1_0 / tq2_0 are types of the 2-D and expert weights of the decoder graphs, as mxfp4 is (a row split is refused below in the words of the other types)
+        const char *why = ti.n_dims == 1 ? "norm and bias vectors must be f32" : hp.encoder ? "the encoder graph is not supported with ternary tensors" : nullptr;
+        if (why) return !refuse("tensor " + name + " has type " + ggml_type_name(ti.type) + ": " + why);
+    }
+    if (P > 1 && type_row_split_unsupported(ti.type))    // (Q4_1, Q5_1, IQ4_XS, TQ1_0, TQ2_0; an mxfp4 tensor has been refused above in its own words)
         return !refuse(std::string("row split (split_mode \"row\" / tp_size > 1) of ") + ggml_type_name(ti.type) + " tensors is not supported (tensor " + name + "): load the file on one device");
     if (ti.type == T_BF16) {
         // bf16 is a type of the dense 2-D weights (and of token_embd / output): the norm and bias vectors are read as f32 by the kernels, the routed experts,
@@ -257,7 +262,7 @@ void Planner::plan_tensor(const std::string &name, DevTensor &dst, bool required
     dst.K = ti->ne[0];
     dst.N = ti->ne[1];
     dst.n_expert = ti->ne[2];
-    // a row is a whole number of its type's blocks: 256 elements for the K-quants and IQ4_XS, 32 for Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL / MXFP4
+    // a row is a whole number of its type's blocks: 256 elements for the K-quants, IQ4_XS, TQ1_0 and TQ2_0, 32 for Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL / MXFP4
     // (llama-quantize writes a tensor whose rows are no multiple of 256 in one of the latter)
     const int64_t row_unit = std::max<int64_t>(ggml_block_elems(dst.type), 1);
     if (dst.K % row_unit) {

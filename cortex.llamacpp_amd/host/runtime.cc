@@ -691,7 +691,7 @@ hipError_t Context::ensure_prep(const ActQuant &aq, int K, int T) {
     return hipSuccess;
 }
 
-// Q2_K / Q3_K / IQ4_XS tensors reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
+// Q2_K / Q3_K / IQ4_XS / TQ1_0 / TQ2_0 tensors reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
 // (the types with an exact Q8_0-layout copy: act_is_q80 without Q8_0 itself, which needs none)
 static bool q80_copy(const DevTensor &w, int K, int T) {
     return type_has_q80_copy(w.type) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
@@ -717,7 +717,7 @@ hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *
         if (q80_copy(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs0)      // prompt processing of Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4 tensors: their exact Q8_0-layout copy
             return launch_mmq_q80(w.planes, mmq_q80_copy_row_bytes(w.type, K), (int)w.N, K, T, aq, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_q80_copy_form(w.type));
         if (planes_small(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs) {
-            // prompt processing of Q2_K / Q3_K / IQ4_XS tensors: their plane sets (expanded at load in the Q4_K / Q6_K plane formats, mmq.hip) on the same kernels
+            // prompt processing of Q2_K / Q3_K / IQ4_XS / TQ1_0 / TQ2_0 tensors: their plane sets (expanded at load in the Q4_K / Q6_K plane formats, mmq.hip) on the same kernels
             if (w.type == T_Q2_K && !bh_over_) HIP_TRY(ensure_prep(aq, K, T));
             return launch_mmq_planes(w.type, w.planes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_ws_);
         }
@@ -769,8 +769,9 @@ hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs,
         return hipSuccess;
     }
     bool all_mmq = true, all_ks = true;
-    // (IQ4_XS: through its plane set, the signed format - Q | K | V of the IQ4_XS mixes run as one launch like the K-quants')
-    for (int i = 0; i < n; i++) { all_mmq &= mmq_applicable(ws[i]->type, K, T) || (ws[i]->type == T_IQ4_XS && planes_small(*ws[i], K, T)); all_ks &= mmq_ksplit_applicable(ws[i]->type, K, T); }
+    // (IQ4_XS, TQ1_0, TQ2_0: through their plane sets, the signed format - Q | K | V of those mixes run as one launch like the K-quants')
+    auto signed_planes_only = [](int t) { return t == T_IQ4_XS || type_is_ternary(t); };
+    for (int i = 0; i < n; i++) { all_mmq &= mmq_applicable(ws[i]->type, K, T) || (signed_planes_only(ws[i]->type) && planes_small(*ws[i], K, T)); all_ks &= mmq_ksplit_applicable(ws[i]->type, K, T); }
     if (all_ks && pending_fuse_.mode == 0 && n <= 3) {         // batched decode step: Q, K, V in one launch
         HIP_TRY(ensure_prep(aq, K, T));
         MMQSeg sg[3];
@@ -781,7 +782,7 @@ hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs,
         HIP_TRY(ensure_prep(aq, K, T));
         // Q | K | V (or Q | K) as one launch over the concatenated rows where their plane sets are adjacent in the arena and
         // of one plane format (Q4_K and Q5_K share it; the Q6_K attn_v of the "more bits" layers runs on its own)
-        auto mins = [](int t) { return t != T_Q6_K && t != T_IQ4_XS; };
+        auto mins = [&](int t) { return t != T_Q6_K && !signed_planes_only(t); };
         auto adjacent = [&](int i) { return ws[i]->planes && ws[i - 1]->planes && ws[i]->planes == ws[i - 1]->planes + ws[i - 1]->planes_bytes &&
                                             (ws[i - 1]->N % 32) == 0 && ws[i]->n_expert == 1; };
         int nf = 1;

@@ -44,7 +44,7 @@ enum mi355_status {
 /* ggml type ids as stored in GGUF (upstream ggml.h enum ggml_type; used at llama_engine.cc:272-281) */
 enum mi355_type {
     MI355_TYPE_F32 = 0, MI355_TYPE_F16 = 1, MI355_TYPE_Q4_0 = 2, MI355_TYPE_Q8_0 = 8,
-    MI355_TYPE_Q4_K = 12, MI355_TYPE_Q5_K = 13, MI355_TYPE_Q6_K = 14, MI355_TYPE_Q8_K = 15, MI355_TYPE_IQ4_XS = 23, MI355_TYPE_BF16 = 30,
+    MI355_TYPE_Q4_K = 12, MI355_TYPE_Q5_K = 13, MI355_TYPE_Q6_K = 14, MI355_TYPE_Q8_K = 15, MI355_TYPE_IQ4_XS = 23, MI355_TYPE_BF16 = 30, MI355_TYPE_TQ1_0 = 34, MI355_TYPE_TQ2_0 = 35,
 };
 
 /* ------------------------------------------------------------------ backend */
@@ -215,7 +215,10 @@ MI355_API int mi355_op_swiglu_quant(const float *gate, const float *up, int64_t 
  * sum of a - the block contributes (d * d8) * isum + m * (d8 * msum).  With "mmq_planes" 1 and T >= 32 the tensor's Q8_0-layout copy runs on the
  * matrix cores, in the form "mmq_q80_tiles" forces (1 | 2 | 4 token tiles per wave; 0: the launcher's choice).
  * MXFP4 (type 39, Q8_0 activations): as Q4_1 / Q5_1 for K, the one-token form and the copy; isum is the block's sum of level * a, msum is 0 - the block
- * contributes (d * d8) * isum with d from its E8M0 byte. */
+ * contributes (d * d8) * isum with d from its E8M0 byte.
+ * TQ1_0 / TQ2_0 (types 34 / 35, the ternary formats, Q8_K activations, K % 256 == 0): isum is the super-block's sum of (q - 1) * a with q the code 0..2 (the
+ * formats' formulas rule for every byte value: a TQ2_0 code of 3 is weight + 2 d), msum is 0 - the super-block contributes (d * d8) * isum.  One token runs on
+ * the weight stream or the register ring, 2 .. 31 on the generic mat-vec, T >= 32 on the plane kernels with "mmq_planes" 1 (planes only, as Q2_K / Q3_K / IQ4_XS). */
 MI355_API int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T,
                                float *y, int32_t *isum, int32_t *msum);
 /* Test hook: y = resid + W . x (resid, y: [T][N]) on the launches that take a residual in their epilogue through this entry point: the Q8_0 prompt kernel
@@ -235,7 +238,7 @@ MI355_API int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out);
  * T a multiple of it).  use_graph 1: the launches are captured into a graph and replayed. */
 MI355_API int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, const float *const *bias,
                                     const float *resid, int32_t epi, int32_t path, int32_t tokens_per_launch, int32_t use_graph, float *const *y);
-/* ffn_gate and ffn_up (one K-quant type or IQ4_XS, N rows each, N % 32 == 0) against the same T activation rows with SwiGLU in the
+/* ffn_gate and ffn_up (one K-quant type, IQ4_XS, TQ1_0 or TQ2_0, N rows each, N % 32 == 0) against the same T activation rows with SwiGLU in the
  * epilogue, as the prompt path launches them (mmq_planes2_swiglu_kernel): y[t][n] = silu(Wg[n] . x[t]) * (Wu[n] . x[t]).
  * Shapes too small for that launch are refused unless the debug option "mmq_tiles" = 4 forces the kernel.
  * The 32-element formats (any N, K % 32 == 0) run as a layer of such a file does: T >= 32 on the Q8_0 prompt kernel (Q8_0 tensors directly, the others with
@@ -353,7 +356,7 @@ typedef void (*mi355_log_callback)(int level, const char *line, void *user);
 MI355_API void mi355_engine_set_log_callback(mi355_engine *e, mi355_log_callback cb, void *user);
 
 /* Test / tool switches of the per-op entry points: "mmq_planes" (1: mi355_op_mul_mat with T >= 32 expands the weight
- * into MFMA planes first, as a loaded model does; 0: expands on the fly inside the kernel - Q2_K / Q3_K / IQ4_XS have
+ * into MFMA planes first, as a loaded model does; 0: expands on the fly inside the kernel - Q2_K / Q3_K / IQ4_XS / TQ1_0 / TQ2_0 have
  * no on-the-fly form and take the mat-vec then), "mmq_tiles" (0 | 1 | 2
  * token tiles per wave), "mmq_q80_tiles" (test hook: 0 | 1 | 2 | 4 token tiles per wave of the Q8_0 prompt kernel whatever the shape; every form gives the same bits), "mmq_ksplit" (1: 8 <= T <= 64 uses the K-split small-batch kernel, as the runtime does; 0: the
  * kernels the other T ranges use); and of contexts created afterwards: "decode_mega" (1: single-token steps of a dense
