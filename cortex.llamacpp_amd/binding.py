@@ -116,6 +116,12 @@ SYMBOLS = {
     "mi355_op_soft_max": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp]),
     "mi355_op_moe_route": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
     "mi355_op_moe_router": (C.c_int, [_i32, _vp, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mi355_op_argmax_rows": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp]),
+    "mi355_op_topk_rows": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mi355_op_moe_group": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "mi355_op_moe_gather_act": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mi355_op_moe_combine": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "mi355_op_gather_rows_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp]),
     "mi355_op_flash_attn": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32, _vp]),
     "mi355_op_attn_step": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _i64, _vp, _i32,
                                      _vp, _vp, _vp, _vp]),
@@ -380,6 +386,88 @@ class Backend:
         self._chk(self.lib.mi355_op_moe_router(t, _ptr(gate_inp), n_expert, K, _ptr(x), T, k, int(fused), _ptr(f), _ptr(logits), _ptr(ids), _ptr(w)),
                   "op_moe_router")
         return logits, ids, w
+
+    def argmax_rows(self, x: np.ndarray, launches=None, cap_rows=None) -> np.ndarray:
+        """Row arg-max of x [rows][n] (mi355_op_argmax_rows): `launches` splits the rows into consecutive launches on one scratch of cap_rows rows
+        (default: one launch of all rows)."""
+        x = np.ascontiguousarray(x, np.float32)
+        x = x.reshape(1, -1) if x.ndim == 1 else x
+        la = np.ascontiguousarray([x.shape[0]] if launches is None else launches, np.int32).reshape(-1)
+        cap = int(la.max() if cap_rows is None else cap_rows)
+        assert int(la.sum()) == x.shape[0]
+        out = np.full(x.shape[0], -1, np.int32)
+        self._chk(self.lib.mi355_op_argmax_rows(_ptr(x), x.shape[1], _ptr(la), la.size, cap, _ptr(out)), "op_argmax_rows")
+        return out
+
+    @staticmethod
+    def topk_decode(keys: np.ndarray):
+        """(tokens int32, logits f32) of top-k keys: the inverse of the order-preserving image, as Context::topk_rows applies it."""
+        keys = np.asarray(keys, np.uint64)
+        u = (keys >> np.uint64(32)).astype(np.uint32)
+        u = np.where(u >> np.uint32(31), u ^ np.uint32(0x80000000), u ^ np.uint32(0xffffffff)).astype(np.uint32)
+        toks = (np.uint32(0xffffffff) - (keys & np.uint64(0xffffffff)).astype(np.uint32)).astype(np.uint32).view(np.int32)
+        return toks, u.view(np.float32)
+
+    def topk_rows(self, base: np.ndarray, rows, k: int, adjs=None, adj_n=None):
+        """The k best of logits rows base[rows[r]] after adjustments adjs[r] = (tok [m], bias [m], cnt [m], repeat, freq, present) (None: no adjustment;
+        adj_n overrides the entry counts handed over): returns (tokens [n_rows][k], logits [n_rows][k], raw keys [n_rows][k] uint64)."""
+        base = np.ascontiguousarray(base, np.float32)
+        base = base.reshape(1, -1) if base.ndim == 1 else base
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        R, A = rows.size, 192
+        an = np.zeros(R, np.int32); tok = np.zeros((R, A), np.int32); bias = np.zeros((R, A), np.float32); cnt = np.zeros((R, A), np.int32)
+        rep = np.ones(R, np.float32); freq = np.zeros(R, np.float32); pres = np.zeros(R, np.float32)
+        for r, a in enumerate(adjs or []):
+            if a is None:
+                continue
+            m = min(len(a[0]), A)
+            an[r] = len(a[0])
+            tok[r, :m] = np.asarray(a[0], np.int32)[:m]; bias[r, :m] = np.asarray(a[1], np.float32)[:m]; cnt[r, :m] = np.asarray(a[2], np.int32)[:m]
+            rep[r], freq[r], pres[r] = a[3], a[4], a[5]
+        if adj_n is not None:
+            an = np.ascontiguousarray(adj_n, np.int32).reshape(R)
+        keys = np.zeros((R, max(int(k), 1)), np.uint64)
+        self._chk(self.lib.mi355_op_topk_rows(_ptr(base), base.shape[1], base.shape[0], _ptr(rows), R, int(k), _ptr(an), _ptr(tok), _ptr(bias), _ptr(cnt),
+                                              _ptr(rep), _ptr(freq), _ptr(pres), _ptr(keys)), "op_topk_rows")
+        toks, logits = self.topk_decode(keys)
+        return toks, logits, keys
+
+    def moe_group(self, ids: np.ndarray, n_expert: int):
+        """Grouping of the selections ids [T][k] by expert (mi355_op_moe_group): (meta [2 n_expert + 1], slot_of [T * k], tok_of [T * k])."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        T, k = ids.shape
+        meta = np.full(2 * max(int(n_expert), 0) + 1, -1, np.int32); slot_of = np.full(T * k, -1, np.int32); tok_of = np.full(T * k, -1, np.int32)
+        self._chk(self.lib.mi355_op_moe_group(_ptr(ids), T, k, int(n_expert), _ptr(meta), _ptr(slot_of), _ptr(tok_of)), "op_moe_group")
+        return meta, slot_of, tok_of
+
+    def moe_gather_act(self, planes, tok_of, K: int, guard: int = 0xA5):
+        """grouped row r = row tok_of[r] of every plane given (mi355_op_moe_gather_act).  planes: (qs, d, bsums, qs0, d0) as byte arrays [T][row bytes], the
+        Q8_K triple or the Q8_0 pair may be None.  Returns the five output planes as uint8 [n_rows + 1][row bytes] (None where not given): they are filled
+        with `guard` before the launch, so the last row, and every byte the kernel does not write, comes back as that."""
+        tok_of = np.ascontiguousarray(tok_of, np.int32).reshape(-1)
+        src = [None if p is None else np.ascontiguousarray(p).view(np.uint8).reshape(np.asarray(p).shape[0], -1) for p in planes]
+        T = next(p.shape[0] for p in src if p is not None)
+        out = [None if p is None else np.full((tok_of.size + 1, p.shape[1]), guard, np.uint8) for p in src]
+        self._chk(self.lib.mi355_op_moe_gather_act(*[_ptr(p) for p in src], T, int(K), _ptr(tok_of), tok_of.size, *[_ptr(p) for p in out]), "op_moe_gather_act")
+        return out
+
+    def moe_combine(self, x: np.ndarray, eo: np.ndarray, w: np.ndarray, slot_of=None) -> np.ndarray:
+        """x [T][E] + the weighted expert outputs in rank order (mi355_op_moe_combine): eo [k][T][E], or with slot_of [T * k] the grouped rows [T * k][E]."""
+        x = np.ascontiguousarray(x, np.float32); eo = np.ascontiguousarray(eo, np.float32); w = np.ascontiguousarray(w, np.float32)
+        T, E = x.shape
+        k = w.shape[1]
+        assert w.shape[0] == T and eo.size == T * k * E
+        s = None if slot_of is None else np.ascontiguousarray(slot_of, np.int32).reshape(T * k)
+        y = np.zeros_like(x)
+        self._chk(self.lib.mi355_op_moe_combine(_ptr(x), _ptr(eo), _ptr(w), T, E, k, int(s is not None), _ptr(s), _ptr(y)), "op_moe_combine")
+        return y
+
+    def gather_rows_f32(self, src: np.ndarray, rows) -> np.ndarray:
+        src = np.ascontiguousarray(src, np.float32)
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        dst = np.zeros((rows.size, src.shape[1]), np.float32)
+        self._chk(self.lib.mi355_op_gather_rows_f32(_ptr(src), src.shape[0], src.shape[1], _ptr(rows), rows.size, _ptr(dst)), "op_gather_rows_f32")
+        return dst
 
     def flash_attn(self, q: np.ndarray, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows: np.ndarray, type_v: int,
                    v_rows: np.ndarray, cell_pos, q_pos, scale: float) -> np.ndarray:

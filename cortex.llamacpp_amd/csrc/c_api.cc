@@ -1001,6 +1001,139 @@ int mi355_op_moe_router(int32_t type, const void *gate_inp, int32_t n_expert, in
     return di.down(ids, ns) && dw.down(w, ns) ? MI355_OK : MI355_ERR_HIP;
 }
 
+// ---- the kernels that produce indices (csrc/misc.hip), one test entry each
+int mi355_op_argmax_rows(const float *x, int64_t n, const int32_t *launches, int32_t n_launch, int32_t cap_rows, int32_t *out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (n < 1 || n > INT32_MAX || n_launch < 1 || cap_rows < 1 || cap_rows > 65535) { fail("argmax_rows: bad shape"); return MI355_ERR_ARG; }
+    size_t rows = 0;
+    for (int i = 0; i < n_launch; i++) {
+        if (launches[i] < 1 || launches[i] > cap_rows) { fail("argmax_rows: launch " + std::to_string(i) + " outside [1, cap_rows]"); return MI355_ERR_ARG; }
+        rows += (size_t)launches[i];
+    }
+    DevBuf dx(rows * (size_t)n * 4), dout(rows * 4), ds((size_t)cap_rows * 129 * 4);      // (DevBuf zero-fills: the ticket words start at 0, once)
+    if (!dx.up(x, rows * (size_t)n * 4) || !dout.p || !ds.p) return MI355_ERR_OOM;
+    hipError_t e = hipSuccess;
+    size_t r0 = 0;
+    for (int i = 0; i < n_launch && e == hipSuccess; i++) {                               // back to back on one scratch: no synchronisation in between
+        e = launch_argmax_rows(dx.as<float>() + r0 * (size_t)n, (int)n, launches[i], dout.as<int32_t>() + r0, ds.as<float>(), cap_rows, nullptr);
+        r0 += (size_t)launches[i];
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "argmax_rows");
+    return dout.down(out, rows * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_topk_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t n_rows, int32_t k, const int32_t *adj_n,
+                       const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_cnt, const float *repeat, const float *freq, const float *present,
+                       uint64_t *keys_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (n < 1 || n > INT32_MAX || n_base_rows < 1 || n_rows < 1 || n_rows > 65535) { fail("topk_rows: bad shape"); return MI355_ERR_ARG; }
+    if (k < 1 || k > TOPK_MAX_K || k > n) { fail("topk_rows: k outside [1, min(n, " + std::to_string(TOPK_MAX_K) + ")]"); return MI355_ERR_ARG; }
+    std::vector<TopkAdj> adjs((size_t)n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        if (rows[r] < 0 || rows[r] >= n_base_rows) { fail("topk_rows: rows[" + std::to_string(r) + "] outside the base"); return MI355_ERR_ARG; }
+        if (adj_n[r] < 0 || adj_n[r] > TOPK_MAX_ADJ) { fail("topk_rows: adj_n[" + std::to_string(r) + "] outside [0, " + std::to_string(TOPK_MAX_ADJ) + "]"); return MI355_ERR_ARG; }
+        TopkAdj &a = adjs[(size_t)r];
+        memset(&a, 0, sizeof a);
+        a.n = adj_n[r]; a.repeat = repeat[r]; a.freq = freq[r]; a.present = present[r];
+        const size_t o = (size_t)r * TOPK_MAX_ADJ;
+        memcpy(a.tok, adj_tok + o, (size_t)a.n * sizeof(int)); memcpy(a.bias, adj_bias + o, (size_t)a.n * sizeof(float)); memcpy(a.cnt, adj_cnt + o, (size_t)a.n * sizeof(int));
+    }
+    const size_t nb = (size_t)n_base_rows * (size_t)n * 4, nk = (size_t)n_rows * TOPK_MAX_K * 8;
+    DevBuf db(nb), dr((size_t)n_rows * 4), da((size_t)n_rows * sizeof(TopkAdj)), ds(topk_scratch_bytes((int)n) * (size_t)n_rows), dk(nk);
+    if (!db.up(base, nb) || !dr.up(rows, (size_t)n_rows * 4) || !da.up(adjs.data(), (size_t)n_rows * sizeof(TopkAdj)) || !ds.p || !dk.p) return MI355_ERR_OOM;
+    hipError_t e = launch_topk_rows(db.as<float>(), (int)n, n_rows, dr.as<int>(), k, da.as<TopkAdj>(), ds.p, dk.as<unsigned long long>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "topk_rows");
+    std::vector<uint64_t> keys((size_t)n_rows * TOPK_MAX_K);
+    if (!dk.down(keys.data(), nk)) return MI355_ERR_HIP;
+    for (int r = 0; r < n_rows; r++) memcpy(keys_out + (size_t)r * k, keys.data() + (size_t)r * TOPK_MAX_K, (size_t)k * 8);
+    return MI355_OK;
+}
+
+int mi355_op_moe_group(const int32_t *ids, int64_t T, int32_t k, int32_t n_expert, int32_t *meta, int32_t *slot_of, int32_t *tok_of) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (n_expert < 1 || n_expert > 256) { fail("moe_group: n_expert outside [1, 256]"); return MI355_ERR_ARG; }
+    if (T < 1 || k < 1 || T * (int64_t)k > 60 * 1024) { fail("moe_group: T * k outside [1, 61440]"); return MI355_ERR_ARG; }
+    const size_t ns = (size_t)T * k;
+    for (size_t i = 0; i < ns; i++)
+        if (ids[i] < 0 || ids[i] >= n_expert) { fail("moe_group: ids[" + std::to_string(i) + "] outside [0, n_expert)"); return MI355_ERR_ARG; }
+    DevBuf di(ns * 4), dm(((size_t)2 * n_expert + 1) * 4), dslot(ns * 4), dtok(ns * 4);
+    if (!di.up(ids, ns * 4) || !dm.p || !dslot.p || !dtok.p) return MI355_ERR_OOM;
+    hipError_t e = launch_moe_group(di.as<int32_t>(), (int)T, k, n_expert, dm.as<int32_t>(), dslot.as<int32_t>(), dtok.as<int32_t>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "moe_group");
+    return dm.down(meta, ((size_t)2 * n_expert + 1) * 4) && dslot.down(slot_of, ns * 4) && dtok.down(tok_of, ns * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_moe_gather_act(const int8_t *qs, const float *d, const int16_t *bsums, const int8_t *qs0, const uint16_t *d0, int64_t T, int64_t K,
+                            const int32_t *tok_of, int64_t n_rows, int8_t *qs_out, float *d_out, int16_t *bsums_out, int8_t *qs0_out, uint16_t *d0_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (T < 1 || n_rows < 1 || K < 1 || K > INT32_MAX || n_rows > INT32_MAX) { fail("moe_gather_act: bad shape"); return MI355_ERR_ARG; }
+    if (K % 256) { fail("moe_gather_act: K is not a multiple of 256"); return MI355_ERR_ARG; }
+    const bool q8k = qs != nullptr, q80 = qs0 != nullptr;
+    if ((!q8k && !q80) || (q8k && (!d || !bsums || !qs_out || !d_out || !bsums_out)) || (q80 && (!d0 || !qs0_out || !d0_out))) {
+        fail("moe_gather_act: an activation form needs all its planes, in and out"); return MI355_ERR_ARG;
+    }
+    for (int64_t r = 0; r < n_rows; r++)
+        if (tok_of[r] < 0 || tok_of[r] >= T) { fail("moe_gather_act: tok_of[" + std::to_string(r) + "] outside [0, T)"); return MI355_ERR_ARG; }
+    // plane p: bytes per row, source rows, destination rows (+ the guard row the caller filled)
+    const size_t rb[5] = {(size_t)K, (size_t)(K / 256) * 4, (size_t)(K / 16) * 2, (size_t)K, (size_t)(K / 32) * 2};
+    const void *in[5] = {qs, d, bsums, qs0, d0};
+    void *out[5] = {qs_out, d_out, bsums_out, qs0_out, d0_out};
+    const bool on[5] = {q8k, q8k, q8k, q80, q80};
+    std::unique_ptr<DevBuf> s[5], o[5];
+    for (int p = 0; p < 5; p++) {
+        if (!on[p]) continue;
+        s[p].reset(new DevBuf(rb[p] * (size_t)T));
+        o[p].reset(new DevBuf(rb[p] * (size_t)(n_rows + 1)));
+        if (!s[p]->up(in[p], rb[p] * (size_t)T) || !o[p]->up(out[p], rb[p] * (size_t)(n_rows + 1))) return MI355_ERR_OOM;
+    }
+    DevBuf dt((size_t)n_rows * 4);
+    if (!dt.up(tok_of, (size_t)n_rows * 4)) return MI355_ERR_OOM;
+    ActQuant src, dst;
+    if (q8k) { src.qs = s[0]->as<int8_t>(); src.d = s[1]->as<float>(); src.bsums = s[2]->as<int16_t>(); dst.qs = o[0]->as<int8_t>(); dst.d = o[1]->as<float>(); dst.bsums = o[2]->as<int16_t>(); }
+    if (q80) { src.qs0 = s[3]->as<int8_t>(); src.d0 = s[4]->as<uint16_t>(); dst.qs0 = o[3]->as<int8_t>(); dst.d0 = o[4]->as<uint16_t>(); }
+    hipError_t e = launch_moe_gather_act(src, dt.as<int32_t>(), (int)n_rows, (int)K, dst, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "moe_gather_act");
+    for (int p = 0; p < 5; p++)
+        if (on[p] && !o[p]->down(out[p], rb[p] * (size_t)(n_rows + 1))) return MI355_ERR_HIP;
+    return MI355_OK;
+}
+
+int mi355_op_moe_combine(const float *x, const float *eo, const float *w, int64_t T, int32_t E, int32_t k, int32_t grouped, const int32_t *slot_of, float *y_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (T < 1 || E < 1 || k < 1 || T * (int64_t)E > INT32_MAX || T * (int64_t)k > INT32_MAX) { fail("moe_combine: bad shape"); return MI355_ERR_ARG; }
+    if (grouped && !slot_of) { fail("moe_combine: the grouped form needs slot_of"); return MI355_ERR_ARG; }
+    const size_t ns = (size_t)T * k, nx = (size_t)T * E * 4;
+    if (grouped)
+        for (size_t i = 0; i < ns; i++)
+            if (slot_of[i] < 0 || (size_t)slot_of[i] >= ns) { fail("moe_combine: slot_of[" + std::to_string(i) + "] outside [0, T * k)"); return MI355_ERR_ARG; }
+    DevBuf dx(nx), de(nx * (size_t)k), dw(ns * 4), dslot(ns * 4);
+    if (!dx.up(x, nx) || !de.up(eo, nx * (size_t)k) || !dw.up(w, ns * 4) || !dslot.p) return MI355_ERR_OOM;
+    if (grouped && !dslot.up(slot_of, ns * 4)) return MI355_ERR_OOM;
+    hipError_t e = grouped ? launch_moe_scatter_combine(dx.as<float>(), de.as<float>(), dw.as<float>(), dslot.as<int32_t>(), (int)T, E, k, nullptr)
+                           : launch_moe_combine(dx.as<float>(), de.as<float>(), dw.as<float>(), (int)T, E, k, (size_t)T * E, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "moe_combine");
+    return dx.down(y_out, nx) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_gather_rows_f32(const float *src, int64_t n_src_rows, int64_t n, const int32_t *rows, int64_t n_rows, float *dst) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (n_src_rows < 1 || n < 1 || n_rows < 1 || n > INT32_MAX || n_rows > 65535) { fail("gather_rows_f32: bad shape"); return MI355_ERR_ARG; }
+    for (int64_t r = 0; r < n_rows; r++)
+        if (rows[r] < 0 || rows[r] >= n_src_rows) { fail("gather_rows_f32: rows[" + std::to_string(r) + "] outside the source"); return MI355_ERR_ARG; }
+    const size_t nsrc = (size_t)n_src_rows * (size_t)n * 4, nd = (size_t)n_rows * (size_t)n * 4;
+    DevBuf ds(nsrc), dr((size_t)n_rows * 4), dd(nd);
+    if (!ds.up(src, nsrc) || !dr.up(rows, (size_t)n_rows * 4) || !dd.p) return MI355_ERR_OOM;
+    hipError_t e = launch_gather_rows_f32(ds.as<float>(), dr.as<int32_t>(), (int)n_rows, (int)n, dd.as<float>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "gather_rows_f32");
+    return dd.down(dst, nd) ? MI355_OK : MI355_ERR_HIP;
+}
+
 int mi355_op_flash_attn(const float *q, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
                         const void *v, int32_t n_cells, const int32_t *cell_pos, const int32_t *q_pos, float scale, float *out) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;

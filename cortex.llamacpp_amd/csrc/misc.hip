@@ -177,7 +177,7 @@ hipError_t launch_get_rows(int type, const uint8_t *table, int64_t K, const int3
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------- argmax per row (lowest index wins ties), two stages
+// ---------------------------------------------------------------- argmax per row (lowest index wins ties, NaN never wins, a row of NaNs gives 0), two stages
 constexpr int ARGMAX_PARTS = 64;
 __device__ __forceinline__ void argmax_block_reduce(float &best, int &idx, float *bv, int *bi) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void argmax_part_kernel(const float *x, int n,
         const int oi = __shfl_xor(i2, o, 64);
         if (ov > b2 || (ov == b2 && oi < i2)) { b2 = ov; i2 = oi; }
     }
-    if (tid == 0) out[row] = i2;
+    if (tid == 0) out[row] = i2 == 0x7fffffff ? 0 : i2;        // no comparable entry (every value NaN): token 0, not an id outside the vocabulary
 }
 // scratch: cap_rows ticket words (zero between launches) | cap_rows * 64 part values | cap_rows * 64 part indices.  The ticket words sit at the HEAD of the
 // scratch, at an address that does not depend on `rows`: behind the parts they moved with the row count, and a launch with fewer rows than its predecessor
@@ -249,6 +249,7 @@ hipError_t launch_argmax_rows(const float *x, int n, int rows, int32_t *out, flo
 typedef unsigned long long topk_key;
 __device__ __forceinline__ topk_key topk_make_key(float v, int tok) {
     unsigned u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0;                                 // -0.0 == +0.0 under the host's `better`: one image, so zeros tie on the token id
     u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;                  // order-preserving image of the float
     return ((topk_key)u << 32) | (topk_key)(0xffffffffu - (unsigned)tok);
 }

@@ -264,6 +264,33 @@ MI355_API int mi355_op_moe_route(const float *logits, int64_t T, int32_t n_exper
    (nullable), ids [T][k], w [T][k] */
 MI355_API int mi355_op_moe_router(int32_t type, const void *gate_inp, int32_t n_expert, int64_t K, const float *x, int64_t T, int32_t k, int32_t fused,
                                   const int32_t *forced, float *logits, int32_t *ids, float *w);
+/* ---- test entries of the kernels that produce indices: exact by construction, so their tests compare for equality.
+ * Row arg-max (the token of a greedy step): x holds sum(launches) rows of n floats; ONE scratch of cap_rows * 129 words is zeroed once, then launch i takes the
+ * next launches[i] rows (1 <= launches[i] <= cap_rows) - n_launch launches back to back on that scratch, no synchronisation between them.  out[row]: the
+ * lowest index of the largest value; NaN entries never win; a row without a comparable entry gives 0. */
+MI355_API int mi355_op_argmax_rows(const float *x, int64_t n, const int32_t *launches, int32_t n_launch, int32_t cap_rows, int32_t *out);
+/* The k best candidates of n_rows logits rows (the front end of a sampled step): row r is base row rows[r] ([n_base_rows][n] f32) after its adjustments -
+ * adj_n[r] entries (0 .. 192) of the flat [n_rows][192] arrays adj_tok / adj_bias / adj_cnt, no token twice in a row's list: l = l + bias; if cnt > 0:
+ * l = l <= 0 ? l * repeat[r] : l / repeat[r]; l -= cnt * freq[r] + present[r].  Order: higher logit first, lower token id among equal logits (-0.0 == +0.0).
+ * keys_out [n_rows][k], k <= min(n, 128): (order-preserving image of the f32 logit) << 32 | (0xffffffff - token).  No NaN inputs. */
+MI355_API int mi355_op_topk_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t n_rows, int32_t k, const int32_t *adj_n,
+                                 const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_cnt, const float *repeat, const float *freq,
+                                 const float *present, uint64_t *keys_out);
+/* Grouping of the T * k selections ids [T][k] of a prompt batch by expert (T * k <= 61440, n_expert <= 256): a counting sort, stable in (token, rank) order.
+ * meta [2 * n_expert + 1]: counts | exclusive offsets | total; slot_of [T * k]: grouped row of pair t * k + j; tok_of [T * k]: token of a grouped row. */
+MI355_API int mi355_op_moe_group(const int32_t *ids, int64_t T, int32_t k, int32_t n_expert, int32_t *meta, int32_t *slot_of, int32_t *tok_of);
+/* grouped row r = activation row tok_of[r], plane by plane: the Q8_K triple (qs [T][K] | d [T][K / 256] | bsums [T][K / 16]) and / or the Q8_0 pair (qs0 [T][K]
+ * | d0 [T][K / 32]); the planes of a form that is not wanted are NULL, in and out.  K % 256 == 0.  Every output plane holds n_rows + 1 rows: it is uploaded
+ * before the launch and read back whole, so the last row is a guard that must come back as it went in. */
+MI355_API int mi355_op_moe_gather_act(const int8_t *qs, const float *d, const int16_t *bsums, const int8_t *qs0, const uint16_t *d0, int64_t T, int64_t K,
+                                      const int32_t *tok_of, int64_t n_rows, int8_t *qs_out, float *d_out, int16_t *bsums_out, int8_t *qs0_out,
+                                      uint16_t *d0_out);
+/* y = x + sum_j eo_j * w[t][j] (x [T][E], w [T][k]; the ranks added in order, then the residual).  grouped = 0: eo [k][T][E]; grouped = 1: eo [T * k][E] in
+ * grouped rows, rank j of token t at row slot_of[t * k + j]. */
+MI355_API int mi355_op_moe_combine(const float *x, const float *eo, const float *w, int64_t T, int32_t E, int32_t k, int32_t grouped, const int32_t *slot_of,
+                                   float *y_out);
+/* dst [n_rows][n] = src [n_src_rows][n] rows rows[0 .. n_rows) (the output rows handed to the head) */
+MI355_API int mi355_op_gather_rows_f32(const float *src, int64_t n_src_rows, int64_t n, const int32_t *rows, int64_t n_rows, float *dst);
 /* flash_attn_ext for T query tokens: K/V given as ggml-layout rows [n_cells][n_head_kv*head_dim] of type_k/type_v;
  * visibility: cell c is visible to token t iff cell_pos[c] >= 0 && cell_pos[c] <= q_pos[t]. */
 MI355_API int mi355_op_flash_attn(const float *q, int64_t T, int32_t n_head, int32_t n_head_kv, int32_t head_dim,

@@ -51,6 +51,22 @@ def test_no_cpu_fallback(pkg):
         assert rc == -100, form
     rc = lib.mi355_op_k_shift(1, 1, 32, 32, 0, 1, zero.ctypes.data, 1e4, 1.0, None, 0.0, 1.0, 0.0, 0.0, cache.ctypes.data)
     assert rc == -100
+    # the test entries of the index kernels: one row of 256, one selection, one expert
+    one = np.ones(1, np.int32)
+    f = np.zeros(192, np.float32)
+    adj = np.zeros(192, np.int32)
+    key = np.zeros(1, np.uint64)
+    b = np.zeros(2 * 256, np.uint8)
+    assert lib.mi355_op_argmax_rows(x.ctypes.data, 256, one.ctypes.data, 1, 1, zero.ctypes.data) == -100
+    assert lib.mi355_op_topk_rows(x.ctypes.data, 256, 1, zero.ctypes.data, 1, 1, zero.ctypes.data, adj.ctypes.data, f.ctypes.data, adj.ctypes.data,
+                                  f.ctypes.data, f.ctypes.data, f.ctypes.data, key.ctypes.data) == -100
+    assert lib.mi355_op_moe_group(zero.ctypes.data, 1, 1, 1, adj.ctypes.data, adj.ctypes.data, adj.ctypes.data) == -100
+    assert lib.mi355_op_moe_gather_act(None, None, None, b.ctypes.data, b.ctypes.data, 1, 256, zero.ctypes.data, 1, None, None, None, b.ctypes.data,
+                                       b.ctypes.data) == -100
+    y = np.zeros(256, np.float32)
+    for grouped in (0, 1):
+        assert lib.mi355_op_moe_combine(x.ctypes.data, x.ctypes.data, x.ctypes.data, 1, 256, 1, grouped, zero.ctypes.data, y.ctypes.data) == -100
+    assert lib.mi355_op_gather_rows_f32(x.ctypes.data, 1, 256, zero.ctypes.data, 1, y.ctypes.data) == -100
 
 
 def test_product_does_not_touch_oracle():
