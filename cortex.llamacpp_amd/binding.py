@@ -6,15 +6,10 @@ import os
 
 import numpy as np
 
+from .gguf_synth import (BF16, F16, F32, IQ4_NL, IQ4_XS, MXFP4, Q2_K, Q3_K, Q4_0, Q4_1, Q4_K, Q5_0, Q5_1, Q5_K, Q6_K, Q8_0, Q8_K,  # noqa: F401  (the ggml type ids)
+                         TQ1_0, TQ2_0)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 2, 8, 12, 13, 14, 15
-Q2_K, Q3_K = 10, 11
-Q5_0, IQ4_NL = 6, 20
-Q4_1, Q5_1 = 3, 7
-IQ4_XS = 23
-BF16 = 30
-TQ1_0, TQ2_0 = 34, 35
-MXFP4 = 39
 
 
 class MI355Error(RuntimeError):
@@ -112,6 +107,7 @@ SYMBOLS = {
     "mi355_op_rope": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _f32, _f32, _vp, _i32]),
     "mi355_op_rope_yarn": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _f32, _f32, _vp, _i32, _f32, _f32, _f32, _f32]),
     "mi355_op_get_rows": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "mi355_op_repack_rows": (C.c_int, [_i32, _vp, _i64, _i64, _vp]),
     "mi355_op_swiglu": (C.c_int, [_vp, _vp, _i64, _vp]),
     "mi355_op_soft_max": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp]),
     "mi355_op_moe_route": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
@@ -352,6 +348,13 @@ class Backend:
         ids = np.ascontiguousarray(ids, np.int32)
         out = np.zeros((ids.size, K), np.float32)
         self._chk(self.lib.mi355_op_get_rows(t, _ptr(table), K, n_rows, _ptr(ids), ids.size, _ptr(out)), "op_get_rows")
+        return out
+
+    def repack_rows(self, t: int, rows: np.ndarray, K: int, n_rows: int, drow: int) -> np.ndarray:
+        """The device rows of n_rows ggml rows, (n_rows, drow) bytes: what the upload makes of them, padding bytes left at the guard value 0xA5."""
+        rows = np.ascontiguousarray(rows.view(np.uint8).reshape(-1))
+        out = np.zeros((n_rows, drow), np.uint8)
+        self._chk(self.lib.mi355_op_repack_rows(t, _ptr(rows), K, n_rows, _ptr(out)), "op_repack_rows")
         return out
 
     def swiglu(self, g: np.ndarray, u: np.ndarray) -> np.ndarray:

@@ -448,7 +448,7 @@ void cache_planes_from_rows(int type, const void *rows, int G, int D, int n_cell
         for (int c = 0; c < n_cells; c++)
             for (int g = 0; g < G; g++) memcpy(&codes[(((size_t)g * n_cells + c) * D) * 2], src + (size_t)c * rb + (size_t)g * D * 2, (size_t)D * 2);
     } else {
-        const int bb = type == T_Q8_0 ? 34 : 18, cb = type == T_Q8_0 ? 32 : 16;
+        const int bb = ggml_block_bytes(type), cb = bb - 2;
         codes.resize((size_t)G * n_cells * (D / 32) * cb);
         scales.resize((size_t)G * n_cells * (D / 32));
         for (int c = 0; c < n_cells; c++)
@@ -469,7 +469,7 @@ bool cache_row_to_ggml(int type, DevBuf &codes, DevBuf &scales, int G, int D, in
         if (type == T_F16) {
             if (hipMemcpy(o8 + (size_t)g * D * 2, (uint8_t *)codes.p + rowi * D * 2, (size_t)D * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
         } else {
-            const int bb = type == T_Q8_0 ? 34 : 18, cb = type == T_Q8_0 ? 32 : 16;
+            const int bb = ggml_block_bytes(type), cb = bb - 2;
             std::vector<uint8_t> c((size_t)(D / 32) * cb);
             std::vector<uint16_t> sc((size_t)D / 32);
             if (hipMemcpy(c.data(), (uint8_t *)codes.p + rowi * (D / 32) * cb, c.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
@@ -514,7 +514,7 @@ int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n, int64_t r
     if ((act_type != MI355_TYPE_Q8_K && act_type != MI355_TYPE_Q8_0) || n <= 0 || rows <= 0 || n % (act_type == MI355_TYPE_Q8_K ? 256 : 32)) { fail("bad args"); return MI355_ERR_ARG; }
     DevBuf dx((size_t)n * rows * 4);
     ActBufs ab((size_t)n, (size_t)rows + 1);
-    const size_t ob = act_type == MI355_TYPE_Q8_K ? (size_t)(n / 256) * 292 * rows : (size_t)(n / 32) * 34 * rows;
+    const size_t ob = act_type == MI355_TYPE_Q8_K ? ggml_row_bytes(T_Q8_K, n) * rows : ggml_row_bytes(T_Q8_0, n) * rows;
     DevBuf dout(ob);
     if (!dx.up(x, (size_t)n * rows * 4) || !ab.ok() || !dout.p || !q80_guard_set(ab, (size_t)n, (size_t)rows)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
     hipError_t e = launch_quantize(dx.as<float>(), (int)n, (int)rows, ab.q, act_type == MI355_TYPE_Q8_K, act_type == MI355_TYPE_Q8_0, nullptr);
@@ -531,7 +531,7 @@ int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n, int64_t r
 int mi355_op_rms_norm_quant(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y_f32, void *out_blocks) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     if (!x || !w || !out_blocks || n <= 0 || T <= 0 || n % 32) { fail("bad args"); return MI355_ERR_ARG; }
-    DevBuf dx((size_t)n * T * 4), dw((size_t)n * 4), dy((size_t)n * T * 4), dout((size_t)(n / 32) * 34 * T);
+    DevBuf dx((size_t)n * T * 4), dw((size_t)n * 4), dy((size_t)n * T * 4), dout(ggml_row_bytes(T_Q8_0, n) * T);
     ActBufs ab((size_t)n, (size_t)T + 1);
     if (!dx.up(x, (size_t)n * T * 4) || !dw.up(w, (size_t)n * 4) || !dy.p || !dout.p || !ab.ok() || !q80_guard_set(ab, (size_t)n, (size_t)T)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
     hipError_t e = launch_rmsnorm_quant(dx.as<float>(), dw.as<float>(), (int)n, (int)T, eps, y_f32 ? dy.as<float>() : nullptr, &ab.q, false, true, nullptr);
@@ -540,14 +540,14 @@ int mi355_op_rms_norm_quant(const float *x, const float *w, int64_t n, int64_t T
     if (e != hipSuccess) return hip_fail(e, "rms_norm_quant");
     if (!q80_guard_intact(ab, (size_t)n, (size_t)T)) { fail("rms_norm_quant: the quantiser wrote past the last row"); return MI355_ERR_HIP; }
     if (y_f32 && !dy.down(y_f32, (size_t)n * T * 4)) return MI355_ERR_HIP;
-    return dout.down(out_blocks, (size_t)(n / 32) * 34 * T) ? MI355_OK : MI355_ERR_HIP;
+    return dout.down(out_blocks, ggml_row_bytes(T_Q8_0, n) * T) ? MI355_OK : MI355_ERR_HIP;
 }
 
 // silu(gate) * up and the Q8_0 quantisation of the result in one launch (a prompt batch's step between ffn_gate | ffn_up and ffn_down).  n: any multiple of 32.
 int mi355_op_swiglu_quant(const float *gate, const float *up, int64_t n, int64_t T, void *out_blocks) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     if (!gate || !up || !out_blocks || n <= 0 || T <= 0 || n % 32) { fail("bad args"); return MI355_ERR_ARG; }
-    DevBuf dg((size_t)n * T * 4), du((size_t)n * T * 4), dout((size_t)(n / 32) * 34 * T);
+    DevBuf dg((size_t)n * T * 4), du((size_t)n * T * 4), dout(ggml_row_bytes(T_Q8_0, n) * T);
     ActBufs ab((size_t)n, (size_t)T + 1);
     if (!dg.up(gate, (size_t)n * T * 4) || !du.up(up, (size_t)n * T * 4) || !dout.p || !ab.ok() || !q80_guard_set(ab, (size_t)n, (size_t)T)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
     hipError_t e = launch_swiglu_quant(dg.as<float>(), du.as<float>(), (int)n, (int)T, ab.q, false, true, nullptr, nullptr, nullptr);
@@ -555,7 +555,7 @@ int mi355_op_swiglu_quant(const float *gate, const float *up, int64_t n, int64_t
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "swiglu_quant");
     if (!q80_guard_intact(ab, (size_t)n, (size_t)T)) { fail("swiglu_quant: the quantiser wrote past the last row"); return MI355_ERR_HIP; }
-    return dout.down(out_blocks, (size_t)(n / 32) * 34 * T) ? MI355_OK : MI355_ERR_HIP;
+    return dout.down(out_blocks, ggml_row_bytes(T_Q8_0, n) * T) ? MI355_OK : MI355_ERR_HIP;
 }
 
 int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) {
@@ -947,6 +947,20 @@ int mi355_op_get_rows(int32_t type, const void *table, int64_t K, int64_t n_rows
     return dd.down(dst, (size_t)n_ids * K * 4) ? MI355_OK : MI355_ERR_HIP;
 }
 
+int mi355_op_repack_rows(int32_t type, const void *src_rows, int64_t K, int64_t n_rows, void *dst) {
+    const int be = ggml_block_elems(type);
+    if (be == 0 || K <= 0 || n_rows <= 0 || K % be) return MI355_ERR_ARG;
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
+    DevBuf src(grow * n_rows), dev(drow * n_rows);
+    if (!src.up(src_rows, grow * n_rows) || !dev.p) return MI355_ERR_OOM;
+    hipError_t e = hipMemset(dev.p, Q80_GUARD, drow * n_rows);
+    if (e == hipSuccess) e = launch_repack_rows(type, src.as<uint8_t>(), dev.as<uint8_t>(), K, n_rows, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "repack_rows");
+    return dev.down(dst, drow * n_rows) ? MI355_OK : MI355_ERR_HIP;
+}
+
 int mi355_op_swiglu(const float *gate, const float *up, int64_t n, float *y) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     DevBuf g((size_t)n * 4), u((size_t)n * 4), o((size_t)n * 4);
@@ -1155,7 +1169,7 @@ int mi355_op_flash_attn(const float *q, int64_t T, int32_t H, int32_t G, int32_t
             for (int c = 0; c < n_cells; c++)
                 for (int g = 0; g < G; g++)
                     for (int b = 0; b < D / 32; b++) {
-                        const uint8_t *blk = src + (size_t)c * rb + ((size_t)g * (D / 32) + b) * 34;
+                        const uint8_t *blk = src + (size_t)c * rb + ((size_t)g * (D / 32) + b) * ggml_block_bytes(T_Q8_0);
                         memcpy(&scales[((size_t)g * n_cells + c) * (D / 32) + b], blk, 2);
                         memcpy(&codes[((size_t)g * n_cells + c) * D + (size_t)b * 32], blk + 2, 32);
                     }
@@ -1165,7 +1179,7 @@ int mi355_op_flash_attn(const float *q, int64_t T, int32_t H, int32_t G, int32_t
             for (int c = 0; c < n_cells; c++)
                 for (int g = 0; g < G; g++)
                     for (int b = 0; b < D / 32; b++) {
-                        const uint8_t *blk = src + (size_t)c * rb + ((size_t)g * (D / 32) + b) * 18;
+                        const uint8_t *blk = src + (size_t)c * rb + ((size_t)g * (D / 32) + b) * ggml_block_bytes(T_Q4_0);
                         memcpy(&scales[((size_t)g * n_cells + c) * (D / 32) + b], blk, 2);
                         memcpy(&codes[((size_t)g * n_cells + c) * (D / 2) + (size_t)b * 16], blk + 2, 16);
                     }

@@ -7,157 +7,75 @@
 namespace mi355 {
 
 // ---------------------------------------------------------------- ggml rows -> device rows
-__global__ void repack_q6k_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
-    const int row = blockIdx.y, sb = blockIdx.x, i = threadIdx.x;   // 256 threads, 210 used
-    if (i >= 210) return;
-    const uint8_t v = src[((size_t)row * nb + sb) * 210 + i];
-    uint8_t *d = dst + (size_t)row * dst_row;
-    if (i < 128) d[(size_t)sb * 128 + i] = v;
-    else if (i < 192) d[(size_t)nb * 128 + (size_t)sb * 64 + (i - 128)] = v;
-    else if (i < 208) d[(size_t)nb * 192 + (size_t)sb * 16 + (i - 192)] = v;
-    else d[(size_t)nb * 208 + (size_t)sb * 2 + (i - 208)] = v;
+// One kernel body for every repacked type, driven by its row of kTypeLayouts (ggml_types.h): byte i of block b belongs to the plane whose field holds i and
+// goes to plane_off(plane) + b * field bytes + (i - field start).  A 256-element block takes a workgroup of its own, one thread per byte; 32-element blocks go
+// eight to a workgroup, 32 threads each (Q8_0's 34 bytes: two of them take a second byte).  The layout is a compile-time constant, so every offset folds.
+struct PlaneOrder { int p[4]; };
+constexpr PlaneOrder planes_in_block_order(int t) {                            // the type's planes sorted by where their fields start in the block
+    PlaneOrder o{{0, 1, 2, 3}};
+    const TypeLayout &L = type_layout(t);
+    for (int a = 0; a < L.n_planes; a++)
+        for (int c = a + 1; c < L.n_planes; c++)
+            if (L.planes[o.p[c]].off < L.planes[o.p[a]].off) { const int x = o.p[a]; o.p[a] = o.p[c]; o.p[c] = x; }
+    return o;
 }
-__global__ void repack_q80_kernel(const uint8_t *src, uint8_t *dst, int nblk, int K, size_t dst_row) {
-    const int row = blockIdx.y;
-    const int b = blockIdx.x * 8 + (threadIdx.x >> 5), j = threadIdx.x & 31;
-    if (b >= nblk) return;
-    const uint8_t *s = src + ((size_t)row * nblk + b) * 34;
-    uint8_t *d = dst + (size_t)row * dst_row;
-    d[(size_t)b * 32 + j] = s[2 + j];
-    if (j < 2) d[(size_t)K + (size_t)b * 2 + j] = s[j];
-}
-// Q2_K block: scales 16 | qs 64 | d 2 | dmin 2 -> planes qs | scales | (d, dmin);  Q3_K block: hmask 32 | qs 64 | scales 12 | d 2 -> hmask | qs | scales | d
-__global__ void repack_q2k_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
-    const int row = blockIdx.y, sb = blockIdx.x, i = threadIdx.x;   // 128 threads, 84 used
-    if (i >= 84) return;
-    const uint8_t v = src[((size_t)row * nb + sb) * 84 + i];
-    uint8_t *d = dst + (size_t)row * dst_row;
-    if (i < 16) d[(size_t)nb * 64 + (size_t)sb * 16 + i] = v;
-    else if (i < 80) d[(size_t)sb * 64 + (i - 16)] = v;
-    else d[(size_t)nb * 80 + (size_t)sb * 4 + (i - 80)] = v;
-}
-__global__ void repack_q3k_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
-    const int row = blockIdx.y, sb = blockIdx.x, i = threadIdx.x;   // 128 threads, 110 used
-    if (i >= 110) return;
-    const uint8_t v = src[((size_t)row * nb + sb) * 110 + i];
-    uint8_t *d = dst + (size_t)row * dst_row;
-    if (i < 32) d[(size_t)sb * 32 + i] = v;
-    else if (i < 96) d[(size_t)nb * 32 + (size_t)sb * 64 + (i - 32)] = v;
-    else if (i < 108) d[(size_t)nb * 96 + (size_t)sb * 12 + (i - 96)] = v;
-    else d[(size_t)nb * 108 + (size_t)sb * 2 + (i - 108)] = v;
-}
-// IQ4_XS block: d 2 | scales_h 2 | scales_l 4 | qs 128 -> planes qs | scales_l | scales_h | d
-__global__ void repack_iq4xs_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
-    const int row = blockIdx.y, sb = blockIdx.x, i = threadIdx.x;   // 192 threads, 136 used
-    if (i >= 136) return;
-    const uint8_t v = src[((size_t)row * nb + sb) * 136 + i];
-    uint8_t *d = dst + (size_t)row * dst_row;
-    if (i < 2) d[(size_t)nb * 134 + (size_t)sb * 2 + i] = v;
-    else if (i < 4) d[(size_t)nb * 132 + (size_t)sb * 2 + (i - 2)] = v;
-    else if (i < 8) d[(size_t)nb * 128 + (size_t)sb * 4 + (i - 4)] = v;
-    else d[(size_t)sb * 128 + (i - 8)] = v;
-}
-// TQ2_0 block: qs 64 | d 2 -> planes qs | d;  TQ1_0 block: qs 48 | qh 4 | d 2 -> planes qs | qh | d (the packed trits as the file holds them)
-__global__ void repack_tq2_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
-    const int row = blockIdx.y, sb = blockIdx.x, i = threadIdx.x;   // 128 threads, 66 used
-    if (i >= 66) return;
-    const uint8_t v = src[((size_t)row * nb + sb) * 66 + i];
-    uint8_t *d = dst + (size_t)row * dst_row;
-    if (i < 64) d[(size_t)sb * 64 + i] = v;
-    else d[(size_t)nb * 64 + (size_t)sb * 2 + (i - 64)] = v;
-}
-__global__ void repack_tq1_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
-    const int row = blockIdx.y, sb = blockIdx.x, i = threadIdx.x;   // 64 threads, 54 used
-    if (i >= 54) return;
-    const uint8_t v = src[((size_t)row * nb + sb) * 54 + i];
-    uint8_t *d = dst + (size_t)row * dst_row;
-    if (i < 48) d[(size_t)sb * 48 + i] = v;
-    else if (i < 52) d[(size_t)nb * 48 + (size_t)sb * 4 + (i - 48)] = v;
-    else d[(size_t)nb * 52 + (size_t)sb * 2 + (i - 52)] = v;
-}
-// 32-element blocks with a 16-byte nibble field: Q4_0 / IQ4_NL (d | qs), Q5_0 (d | qh | qs), Q4_1 (d | m | qs), Q5_1 (d | m | qh | qs)
-// -> planes qs | [qh] | d | [m]; MXFP4 (e | qs) -> planes qs | e (one scale byte per block)
-__global__ void repack_nib32_kernel(const uint8_t *src, uint8_t *dst, int nblk, int K, size_t dst_row, int bsz) {
-    const int row = blockIdx.y;
-    const int b = blockIdx.x * 8 + (threadIdx.x >> 5), j = threadIdx.x & 31;
-    if (b >= nblk || j >= bsz) return;
-    const uint8_t v = src[((size_t)row * nblk + b) * bsz + j];
-    uint8_t *d = dst + (size_t)row * dst_row;
-    const size_t half = (size_t)K >> 1;
-    if (bsz == 17) {    // MXFP4: e | qs
-        if (j < 1) d[half + (size_t)b] = v; else d[(size_t)b * 16 + (j - 1)] = v;
-    } else if (bsz == 18) {
-        if (j < 2) d[half + (size_t)b * 2 + j] = v; else d[(size_t)b * 16 + (j - 2)] = v;
-    } else if (bsz == 22) {
-        if (j < 2) d[half + (size_t)nblk * 4 + (size_t)b * 2 + j] = v;
-        else if (j < 6) d[half + (size_t)b * 4 + (j - 2)] = v;
-        else d[(size_t)b * 16 + (j - 6)] = v;
-    } else if (bsz == 20) {
-        if (j < 2) d[half + (size_t)b * 2 + j] = v;
-        else if (j < 4) d[half + (size_t)nblk * 2 + (size_t)b * 2 + (j - 2)] = v;
-        else d[(size_t)b * 16 + (j - 4)] = v;
-    } else {    // 24
-        if (j < 2) d[half + (size_t)nblk * 4 + (size_t)b * 2 + j] = v;
-        else if (j < 4) d[half + (size_t)nblk * 6 + (size_t)b * 2 + (j - 2)] = v;
-        else if (j < 8) d[half + (size_t)b * 4 + (j - 4)] = v;
-        else d[(size_t)b * 16 + (j - 8)] = v;
+template <int TYPE> struct RepackShape {
+    static constexpr int BB = ggml_block_bytes(TYPE), NP = type_layout(TYPE).n_planes;
+    static constexpr int BPW = ggml_block_elems(TYPE) == 32 ? 8 : 1;            // blocks per workgroup
+    static constexpr int TPB = ggml_block_elems(TYPE) == 32 ? 32 : (BB + 63) / 64 * 64;   // threads per block
+};
+// the fields in block order, an else-if chain as a hand-written kernel has it: the first one that ends behind byte i holds it
+template <int TYPE, int K> __device__ __forceinline__ void repack_store(uint8_t *d, int nb, int b, int i, uint8_t v) {
+    if constexpr (K < RepackShape<TYPE>::NP) {
+        constexpr int P = planes_in_block_order(TYPE).p[K];
+        constexpr BlockField f = type_layout(TYPE).planes[P];
+        if (i < f.off + f.bytes) d[plane_off<TYPE, P>((size_t)nb) + (size_t)b * f.bytes + (i - f.off)] = v;
+        else repack_store<TYPE, K + 1>(d, nb, b, i, v);
     }
+}
+template <int TYPE>
+__global__ void repack_kernel(const uint8_t *src, uint8_t *dst, int nb, size_t dst_row) {
+    using S = RepackShape<TYPE>;
+    const int row = blockIdx.y, b = blockIdx.x * S::BPW + threadIdx.x / S::TPB;
+    if (b >= nb) return;
+    const uint8_t *s = src + ((size_t)row * nb + b) * S::BB;
+    uint8_t *d = dst + (size_t)row * dst_row;
+#pragma unroll
+    for (int i = threadIdx.x % S::TPB; i < S::BB; i += S::TPB) repack_store<TYPE, 0>(d, nb, b, i, s[i]);
+}
+template <int TYPE>
+static void repack_chunk(const uint8_t *src, uint8_t *dst, int nb, int nr, size_t drow, hipStream_t st) {
+    using S = RepackShape<TYPE>;
+    hipLaunchKernelGGL(repack_kernel<TYPE>, dim3((nb + S::BPW - 1) / S::BPW, nr), dim3(S::BPW * S::TPB), 0, st, src, dst, nb, drow);
 }
 hipError_t launch_repack_rows(int type, const uint8_t *src, uint8_t *dst, int64_t K, int64_t n_rows, hipStream_t st) {
-    const size_t drow = dev_row_bytes(type, K);
-    if (type_has_q80_copy(type)) {
-        const int nblk = (int)(K >> 5);
-        for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
-            const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);
-            hipLaunchKernelGGL(repack_nib32_kernel, dim3((nblk + 7) / 8, nr), dim3(256), 0, st,
-                               src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, nblk, (int)K, drow, ggml_block_bytes(type));
-        }
-        return hipGetLastError();
+    const size_t drow = dev_row_bytes(type, K), srow = ggml_row_bytes(type, K);
+    void (*chunk)(const uint8_t *, uint8_t *, int, int, size_t, hipStream_t) = nullptr;
+    switch (type) {
+        case T_Q4_0: chunk = repack_chunk<T_Q4_0>; break;
+        case T_IQ4_NL: chunk = repack_chunk<T_IQ4_NL>; break;
+        case T_Q4_1: chunk = repack_chunk<T_Q4_1>; break;
+        case T_Q5_0: chunk = repack_chunk<T_Q5_0>; break;
+        case T_Q5_1: chunk = repack_chunk<T_Q5_1>; break;
+        case T_Q8_0: chunk = repack_chunk<T_Q8_0>; break;
+        case T_MXFP4: chunk = repack_chunk<T_MXFP4>; break;
+        case T_Q2_K: chunk = repack_chunk<T_Q2_K>; break;
+        case T_Q3_K: chunk = repack_chunk<T_Q3_K>; break;
+        case T_Q6_K: chunk = repack_chunk<T_Q6_K>; break;
+        case T_IQ4_XS: chunk = repack_chunk<T_IQ4_XS>; break;
+        case T_TQ1_0: chunk = repack_chunk<T_TQ1_0>; break;
+        case T_TQ2_0: chunk = repack_chunk<T_TQ2_0>; break;
     }
-    if (type == T_Q2_K || type == T_Q3_K) {
-        for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
+    if (chunk) {
+        const int nb = (int)(K / ggml_block_elems(type));
+        for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {               // a grid's y extent
             const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);
-            if (type == T_Q2_K) hipLaunchKernelGGL(repack_q2k_kernel, dim3((unsigned)(K >> 8), nr), dim3(128), 0, st,
-                                                   src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
-            else hipLaunchKernelGGL(repack_q3k_kernel, dim3((unsigned)(K >> 8), nr), dim3(128), 0, st,
-                                    src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
+            chunk(src + (size_t)r0 * srow, dst + (size_t)r0 * drow, nb, nr, drow, st);
         }
-    } else if (type == T_IQ4_XS) {
-        for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
-            const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);
-            hipLaunchKernelGGL(repack_iq4xs_kernel, dim3((unsigned)(K >> 8), nr), dim3(192), 0, st,
-                               src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
-        }
-    } else if (type_is_ternary(type)) {
-        for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
-            const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);
-            if (type == T_TQ2_0) hipLaunchKernelGGL(repack_tq2_kernel, dim3((unsigned)(K >> 8), nr), dim3(128), 0, st,
-                                                    src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
-            else hipLaunchKernelGGL(repack_tq1_kernel, dim3((unsigned)(K >> 8), nr), dim3(64), 0, st,
-                                    src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
-        }
-    } else if (type == T_Q6_K) {
-        for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
-            const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);
-            hipLaunchKernelGGL(repack_q6k_kernel, dim3((unsigned)(K >> 8), nr), dim3(256), 0, st,
-                               src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, (int)(K >> 8), drow);
-        }
-    } else if (type == T_Q8_0) {
-        const int nblk = (int)(K >> 5);
-        for (int64_t r0 = 0; r0 < n_rows; r0 += 65535) {
-            const int nr = (int)((n_rows - r0) < 65535 ? (n_rows - r0) : 65535);
-            hipLaunchKernelGGL(repack_q80_kernel, dim3((nblk + 7) / 8, nr), dim3(256), 0, st,
-                               src + (size_t)r0 * ggml_row_bytes(type, K), dst + (size_t)r0 * drow, nblk, (int)K, drow);
-        }
-    } else {
-        if (drow == ggml_row_bytes(type, K)) {
-            hipError_t e = hipMemcpyAsync(dst, src, drow * (size_t)n_rows, hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return e;
-        } else {
-            hipError_t e = hipMemcpy2DAsync(dst, drow, src, ggml_row_bytes(type, K), ggml_row_bytes(type, K), (size_t)n_rows,
-                                            hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return e;
-        }
+    } else {                                                            // rows that are uploaded as the file holds them, padded to 16
+        const hipError_t e = drow == srow ? hipMemcpyAsync(dst, src, drow * (size_t)n_rows, hipMemcpyDeviceToDevice, st)
+                                          : hipMemcpy2DAsync(dst, drow, src, srow, srow, (size_t)n_rows, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return e;
     }
     return hipGetLastError();
 }

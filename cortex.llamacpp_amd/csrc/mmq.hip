@@ -167,10 +167,10 @@ template <> struct RowSB<T_Q6_K> {
     __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, int kg) {
         l0 = ldg16(row + (size_t)sb * 128 + 16 * kg);      l1 = ldg16(row + (size_t)sb * 128 + 32 + 16 * kg);
         l2 = ldg16(row + (size_t)sb * 128 + 64 + 16 * kg); l3 = ldg16(row + (size_t)sb * 128 + 96 + 16 * kg);
-        h0 = ldg16(row + (size_t)nb * 128 + (size_t)sb * 64 + 16 * kg);
-        h1 = ldg16(row + (size_t)nb * 128 + (size_t)sb * 64 + 32 + 16 * kg);
-        scv = ldg16(row + (size_t)nb * 192 + (size_t)sb * 16);
-        d16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 208 + (size_t)sb * 2);
+        h0 = ldg16(row + plane_off<T_Q6_K, q6k::P_QH>((size_t)nb) + (size_t)sb * 64 + 16 * kg);
+        h1 = ldg16(row + plane_off<T_Q6_K, q6k::P_QH>((size_t)nb) + (size_t)sb * 64 + 32 + 16 * kg);
+        scv = ldg16(row + plane_off<T_Q6_K, q6k::P_SCALES>((size_t)nb) + (size_t)sb * 16);
+        d16 = *reinterpret_cast<const uint16_t *>(row + plane_off<T_Q6_K, q6k::P_D>((size_t)nb) + (size_t)sb * 2);
     }
     __device__ __forceinline__ float d() const { return h2f((uint16_t)d16); }
     // signed scale of 16-group g, replicated into both 16-bit lanes
@@ -721,14 +721,14 @@ __global__ __launch_bounds__(256) void mmq_expand_small_kernel(const uint8_t *W,
     if (row >= n_rows) row = n_rows - 1;
     const uint8_t *r = W + (size_t)row * row_bytes;
     uint8_t *blk = planes + (size_t)idx * PL_BLOCK;
-    const size_t qs_off = TYPE == T_Q2_K ? 0 : (size_t)nb * 32;
+    const size_t qs_off = TYPE == T_Q2_K ? plane_off<T_Q2_K, q2k::P_QS>((size_t)nb) : plane_off<T_Q3_K, q3k::P_QS>((size_t)nb);
     // this lane's code bytes: l = 16 kg .. 16 kg + 15 of both 32-byte halves
     const u32x4 q0 = ldg16(r + qs_off + (size_t)sb * 64 + 16 * kg), q1 = ldg16(r + qs_off + (size_t)sb * 64 + 32 + 16 * kg);
     u32x4 hm = {0, 0, 0, 0};
     int sc[16];
     uint32_t mn_lo = 0, mn_hi = 0;
     if (TYPE == T_Q2_K) {
-        const uint8_t *scp = r + (size_t)nb * 64 + (size_t)sb * 16;
+        const uint8_t *scp = r + plane_off<T_Q2_K, q2k::P_SCALES>((size_t)nb) + (size_t)sb * 16;
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             const int b = scp[i];
@@ -737,7 +737,7 @@ __global__ __launch_bounds__(256) void mmq_expand_small_kernel(const uint8_t *W,
         }
     } else {
         hm = ldg16(r + (size_t)sb * 32 + 16 * kg);
-        const uint8_t *scp = r + (size_t)nb * 96 + (size_t)sb * 12;
+        const uint8_t *scp = r + plane_off<T_Q3_K, q3k::P_SCALES>((size_t)nb) + (size_t)sb * 12;
 #pragma unroll
         for (int i = 0; i < 16; i++) {   // 6-bit scale i: low 4 bits = nibble i of bytes 0-7 (low nibbles 0-7, high nibbles 8-15), high 2 bits = bit pair i / 4 of byte 8 + i % 4
             const int low = i < 8 ? (scp[i] & 15) : (scp[i - 8] >> 4);
@@ -773,8 +773,8 @@ __global__ __launch_bounds__(256) void mmq_expand_small_kernel(const uint8_t *W,
     }
     if (kg == 0) {
         u32x4 m = {0, 0, 0, 0};
-        if (TYPE == T_Q2_K) { m.x = *reinterpret_cast<const uint32_t *>(r + (size_t)nb * 80 + (size_t)sb * 4); m.y = mn_lo; m.z = mn_hi; m.w = 1u; }
-        else m.x = *reinterpret_cast<const uint16_t *>(r + (size_t)nb * 108 + (size_t)sb * 2);
+        if (TYPE == T_Q2_K) { m.x = *reinterpret_cast<const uint32_t *>(r + plane_off<T_Q2_K, q2k::P_DM>((size_t)nb) + (size_t)sb * 4); m.y = mn_lo; m.z = mn_hi; m.w = 1u; }
+        else m.x = *reinterpret_cast<const uint16_t *>(r + plane_off<T_Q3_K, q3k::P_D>((size_t)nb) + (size_t)sb * 2);
         *reinterpret_cast<u32x4 *>(blk + 16384 + n * 16) = m;
     }
 }
@@ -791,8 +791,8 @@ __global__ __launch_bounds__(256) void mmq_expand_iq4xs_kernel(const uint8_t *W,
     if (row >= n_rows) row = n_rows - 1;
     const uint8_t *r = W + (size_t)row * row_bytes;
     uint8_t *blk = planes + (size_t)idx * PL_BLOCK;
-    const uint32_t sl = *reinterpret_cast<const uint32_t *>(r + (size_t)nb * 128 + (size_t)sb * 4);
-    const uint32_t sh = *reinterpret_cast<const uint16_t *>(r + (size_t)nb * 132 + (size_t)sb * 2);
+    const uint32_t sl = *reinterpret_cast<const uint32_t *>(r + plane_off<T_IQ4_XS, iq4xs::P_SCALES_L>((size_t)nb) + (size_t)sb * 4);
+    const uint32_t sh = *reinterpret_cast<const uint16_t *>(r + plane_off<T_IQ4_XS, iq4xs::P_SCALES_H>((size_t)nb) + (size_t)sb * 2);
 #pragma unroll
     for (int J = 0; J < 8; J++) {
         const u32x4 qv = ldg16(r + (size_t)sb * 128 + 16 * J);
@@ -814,7 +814,7 @@ __global__ __launch_bounds__(256) void mmq_expand_iq4xs_kernel(const uint8_t *W,
     }
     if (kg == 0) {
         u32x4 m = {0, 0, 0, 0};
-        m.x = *reinterpret_cast<const uint16_t *>(r + (size_t)nb * 134 + (size_t)sb * 2);
+        m.x = *reinterpret_cast<const uint16_t *>(r + plane_off<T_IQ4_XS, iq4xs::P_D>((size_t)nb) + (size_t)sb * 2);
         *reinterpret_cast<u32x4 *>(blk + 16384 + n * 16) = m;
     }
 }
@@ -846,7 +846,7 @@ __global__ __launch_bounds__(256) void mmq_expand_ternary_kernel(const uint8_t *
                 else {
                     int byte, t;
                     tq1_elem(e, byte, t);
-                    q = tq1_trit(byte < 48 ? r[(size_t)sb * 48 + byte] : r[(size_t)nb * 48 + (size_t)sb * 4 + (byte - 48)], t);
+                    q = tq1_trit(byte < 48 ? r[(size_t)sb * 48 + byte] : r[plane_off<T_TQ1_0, tq1::P_QH>((size_t)nb) + (size_t)sb * 4 + (byte - 48)], t);
                 }
                 const int p = q - 1;
                 hx |= (uint32_t)((p >> 6) & 0xff) << (8 * b); lx |= (uint32_t)(p & 63) << (8 * b);

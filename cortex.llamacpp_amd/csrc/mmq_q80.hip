@@ -219,7 +219,8 @@ __global__ __launch_bounds__(256) void expand_nib32_q80_kernel(int type, const u
                                                                size_t dst_row) {
     const int row = blockIdx.y;
     const int nblk = K >> 5;
-    const size_t half = (size_t)K >> 1;
+    // the type is a run-time value here, so the source row's planes are spelled out: qs | [qh] | d | [m], MXFP4 qs | e (kTypeLayouts, ggml_types.h)
+    const size_t half = (size_t)K >> 1;                          // plane 1: qh (Q5_0, Q5_1), e (MXFP4), else d
     const uint8_t *r = W + (size_t)row * row_bytes;
     uint8_t *o = dst + (size_t)row * dst_row;
     for (int e = blockIdx.x * 256 + threadIdx.x; e < K; e += gridDim.x * 256) {
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(256) void expand_nib32_q80_kernel(int type, const u
         o[e] = (uint8_t)(int8_t)code;
         if (j == 0 && nib32_has_e8(type)) o[(size_t)K + (size_t)b] = r[half + (size_t)b];
         else if (j == 0) {
-            const uint16_t *dp = reinterpret_cast<const uint16_t *>(r + nib32_d_off(type, (size_t)K));
+            const uint16_t *dp = reinterpret_cast<const uint16_t *>(r + nib32_d_off(type, (size_t)K));   // plane d; m follows it
             *reinterpret_cast<uint16_t *>(o + (size_t)K + (size_t)b * 2) = dp[b];
             if (nib32_has_min(type)) *reinterpret_cast<uint16_t *>(o + (size_t)K + (size_t)nblk * 2 + (size_t)b * 2) = dp[nblk + b];
         }

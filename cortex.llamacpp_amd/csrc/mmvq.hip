@@ -196,11 +196,11 @@ template <> struct Item<T_Q6_K> {
         if (valid) {
             const int v = lane & 7, n = v >> 2, w = v & 3;
             ql = ld16w(row + (size_t)sb * 128 + v * 16);
-            qh = ld16w(row + (size_t)nb * 128 + (size_t)sb * 64 + n * 32 + (w & 1) * 16);
-            const int8_t *sc = reinterpret_cast<const int8_t *>(row + (size_t)nb * 192 + (size_t)sb * 16 + 8 * n + w);
+            qh = ld16w(row + plane_off<T_Q6_K, q6k::P_QH>((size_t)nb) + (size_t)sb * 64 + n * 32 + (w & 1) * 16);
+            const int8_t *sc = reinterpret_cast<const int8_t *>(row + plane_off<T_Q6_K, q6k::P_SCALES>((size_t)nb) + (size_t)sb * 16 + 8 * n + w);
             hdr.x = (uint32_t)(int)sc[0];
             hdr.y = (uint32_t)(int)sc[4];
-            hdr.z = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 208 + (size_t)sb * 2);
+            hdr.z = *reinterpret_cast<const uint16_t *>(row + plane_off<T_Q6_K, q6k::P_D>((size_t)nb) + (size_t)sb * 2);
         }
     }
     __device__ __forceinline__ void prep(int lane) {
@@ -261,8 +261,8 @@ template <> struct Item<T_Q2_K> {
         if (valid) {
             const int v = lane & 7;
             q = ld8w(row + (size_t)sb * 64 + 32 * (v >> 2) + 8 * (v & 3));
-            hdr = ld16w(row + (size_t)nb * 64 + (size_t)sb * 16);
-            dm = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 80 + (size_t)sb * 4);
+            hdr = ld16w(row + plane_off<T_Q2_K, q2k::P_SCALES>((size_t)nb) + (size_t)sb * 16);
+            dm = *reinterpret_cast<const uint32_t *>(row + plane_off<T_Q2_K, q2k::P_DM>((size_t)nb) + (size_t)sb * 4);
         }
     }
     __device__ __forceinline__ void prep(int lane) {
@@ -313,10 +313,10 @@ template <> struct Item<T_Q3_K> {
         if (valid) {
             const int v = lane & 7;
             hm = ld8w(row + (size_t)sb * 32 + 8 * (v & 3));
-            q = ld8w(row + (size_t)nb * 32 + (size_t)sb * 64 + 32 * (v >> 2) + 8 * (v & 3));
-            const uint32_t *s = reinterpret_cast<const uint32_t *>(row + (size_t)nb * 96 + (size_t)sb * 12);
+            q = ld8w(row + plane_off<T_Q3_K, q3k::P_QS>((size_t)nb) + (size_t)sb * 64 + 32 * (v >> 2) + 8 * (v & 3));
+            const uint32_t *s = reinterpret_cast<const uint32_t *>(row + plane_off<T_Q3_K, q3k::P_SCALES>((size_t)nb) + (size_t)sb * 12);
             hdr.x = s[0]; hdr.y = s[1]; hdr.z = s[2];
-            hdr.w = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 108 + (size_t)sb * 2);
+            hdr.w = *reinterpret_cast<const uint16_t *>(row + plane_off<T_Q3_K, q3k::P_D>((size_t)nb) + (size_t)sb * 2);
         }
     }
     __device__ __forceinline__ void prep(int lane) {
@@ -373,9 +373,9 @@ template <> struct Item<T_IQ4_XS> {
         valid = sb < nb;
         if (valid) {
             q = ld16w(row + (size_t)sb * 128 + 16 * (lane & 7));
-            hdr.x = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 128 + (size_t)sb * 4);
-            hdr.y = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 132 + (size_t)sb * 2);
-            hdr.z = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 134 + (size_t)sb * 2);
+            hdr.x = *reinterpret_cast<const uint32_t *>(row + plane_off<T_IQ4_XS, iq4xs::P_SCALES_L>((size_t)nb) + (size_t)sb * 4);
+            hdr.y = *reinterpret_cast<const uint16_t *>(row + plane_off<T_IQ4_XS, iq4xs::P_SCALES_H>((size_t)nb) + (size_t)sb * 2);
+            hdr.z = *reinterpret_cast<const uint16_t *>(row + plane_off<T_IQ4_XS, iq4xs::P_D>((size_t)nb) + (size_t)sb * 2);
         }
     }
     __device__ __forceinline__ void prep(int lane) {
@@ -419,7 +419,7 @@ template <> struct Item<T_TQ2_0> {
         if (valid) {
             const int v = lane & 7;
             q = ld16w(row + (size_t)sb * 64 + 32 * (v >> 2) + 16 * (v & 1));
-            hdr.x = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 64 + (size_t)sb * 2);
+            hdr.x = *reinterpret_cast<const uint16_t *>(row + plane_off<T_TQ2_0, tq2::P_D>((size_t)nb) + (size_t)sb * 2);
         }
     }
     __device__ __forceinline__ void prep(int lane) {
@@ -464,8 +464,8 @@ template <> struct Item<T_TQ1_0> {
             const int v = lane & 7;
             q0 = ld16w(row + (size_t)sb * 48 + tq1_piece0(v));
             q1 = ld16w(row + (size_t)sb * 48 + tq1_piece1(v));
-            hdr.x = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 48 + (size_t)sb * 4);
-            hdr.y = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 52 + (size_t)sb * 2);
+            hdr.x = *reinterpret_cast<const uint32_t *>(row + plane_off<T_TQ1_0, tq1::P_QH>((size_t)nb) + (size_t)sb * 4);
+            hdr.y = *reinterpret_cast<const uint16_t *>(row + plane_off<T_TQ1_0, tq1::P_D>((size_t)nb) + (size_t)sb * 2);
         }
     }
     __device__ __forceinline__ void prep(int lane) {
@@ -508,7 +508,8 @@ template <int TYPE> struct ItemNib32 {
         valid = e < K;
         if (valid) {
             const int b = e >> 5;
-            const size_t half = (size_t)K >> 1;
+            const size_t half = (size_t)K >> 1;                    // where plane 1 starts (qh, e, else d)
+            // (the offsets are spelled out: written as plane_off<TYPE, ..>() they compile to other code.  Planes qs | [qh] | d | [m]; MXFP4 qs | e - kTypeLayouts, ggml_types.h)
             q = ld16w(row + (size_t)b * 16);
             if (TYPE == T_Q5_0) {
                 qh = *reinterpret_cast<const uint32_t *>(row + half + (size_t)b * 4);
@@ -589,7 +590,7 @@ template <> struct Item<T_Q8_0> {
         valid = e < K;
         if (valid) {
             q = ld16w(row + e);
-            hdr.x = *reinterpret_cast<const uint16_t *>(row + K + (e >> 5) * 2);
+            hdr.x = *reinterpret_cast<const uint16_t *>(row + K + (e >> 5) * 2);   // plane d (q80::P_D) behind the K code bytes, spelled out from K
         }
     }
     __device__ __forceinline__ void prep(int lane) {

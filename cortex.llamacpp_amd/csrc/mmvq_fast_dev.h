@@ -136,11 +136,11 @@ template <> struct Raw<T_Q6_K> {
     __device__ __forceinline__ float probe() const { return (float)(ql.x ^ ql.y ^ ql.z ^ ql.w ^ qh.x ^ qh.y ^ qh.z ^ qh.w ^ (uint32_t)sc_lo ^ (uint32_t)sc_hi ^ dh16); }
     __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
         ql = ldw(row + (size_t)sb * 128 + L.v * 16);
-        qh = ldw(row + (size_t)nb * 128 + (size_t)sb * 64 + L.n * 32 + (L.w & 1) * 16);
-        const int8_t *sc = reinterpret_cast<const int8_t *>(row + (size_t)nb * 192 + (size_t)sb * 16 + 8 * L.n + L.w);
+        qh = ldw(row + plane_off<T_Q6_K, q6k::P_QH>((size_t)nb) + (size_t)sb * 64 + L.n * 32 + (L.w & 1) * 16);
+        const int8_t *sc = reinterpret_cast<const int8_t *>(row + plane_off<T_Q6_K, q6k::P_SCALES>((size_t)nb) + (size_t)sb * 16 + 8 * L.n + L.w);
         sc_lo = sc[0];
         sc_hi = sc[4];
-        dh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 208 + (size_t)sb * 2);
+        dh16 = *reinterpret_cast<const uint16_t *>(row + plane_off<T_Q6_K, q6k::P_D>((size_t)nb) + (size_t)sb * 2);
     }
     __device__ __forceinline__ float dot(const ActSlice &A, const LaneRole &L) const {
         const float d = h2f((uint16_t)dh16);
@@ -169,9 +169,9 @@ template <> struct Raw<T_Q2_K> {
     __device__ __forceinline__ float probe() const { return (float)(q.x ^ q.y ^ q.z ^ q.w ^ dd ^ sc_lo ^ sc_hi); }
     __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
         q = ldw(row + (size_t)sb * 64 + (L.c >> 1) * 32 + L.h * 16);
-        const uint8_t *sc = row + (size_t)nb * 64 + (size_t)sb * 16 + 4 * L.c + L.h;
+        const uint8_t *sc = row + plane_off<T_Q2_K, q2k::P_SCALES>((size_t)nb) + (size_t)sb * 16 + 4 * L.c + L.h;
         sc_lo = sc[0]; sc_hi = sc[2];
-        dd = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 80 + (size_t)sb * 4);
+        dd = *reinterpret_cast<const uint32_t *>(row + plane_off<T_Q2_K, q2k::P_DM>((size_t)nb) + (size_t)sb * 4);
     }
     __device__ __forceinline__ float dot(const ActSlice &A, const LaneRole &L) const {
         const float d = h2f((uint16_t)(dd & 0xffff)), dmin = h2f((uint16_t)(dd >> 16));
@@ -196,10 +196,10 @@ template <> struct Raw<T_Q3_K> {
     __device__ __forceinline__ float probe() const { return (float)(q.x ^ q.y ^ q.z ^ q.w ^ hm.x ^ hm.y ^ hm.z ^ hm.w ^ s0w ^ s1w ^ s2w ^ dh16); }
     __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
         hm = ldw(row + (size_t)sb * 32 + L.h * 16);
-        q = ldw(row + (size_t)nb * 32 + (size_t)sb * 64 + (L.c >> 1) * 32 + L.h * 16);
-        const uint32_t *sc = reinterpret_cast<const uint32_t *>(row + (size_t)nb * 96 + (size_t)sb * 12);
+        q = ldw(row + plane_off<T_Q3_K, q3k::P_QS>((size_t)nb) + (size_t)sb * 64 + (L.c >> 1) * 32 + L.h * 16);
+        const uint32_t *sc = reinterpret_cast<const uint32_t *>(row + plane_off<T_Q3_K, q3k::P_SCALES>((size_t)nb) + (size_t)sb * 12);
         s0w = sc[0]; s1w = sc[1]; s2w = sc[2];
-        dh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 108 + (size_t)sb * 2);
+        dh16 = *reinterpret_cast<const uint16_t *>(row + plane_off<T_Q3_K, q3k::P_D>((size_t)nb) + (size_t)sb * 2);
     }
     __device__ __forceinline__ int scale(int is) const {       // 6-bit scale is (0..15) minus 32
         const uint32_t lw = (is & 4) ? s1w : s0w;              // bytes 0-3 / 4-7 hold the low nibbles of scales 0-7 and, in their high nibbles, of 8-15
@@ -237,7 +237,7 @@ template <> struct Raw<T_Q8_0> {
         const uint8_t *b = row + (size_t)sb * 256 + L.v * 32;
         q0 = ldw(b);
         q1 = ldw(b + 16);
-        dh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 256 + ((size_t)sb * 8 + L.v) * 2);
+        dh16 = *reinterpret_cast<const uint16_t *>(row + plane_off<T_Q8_0, q80::P_D>((size_t)nb * 8) + ((size_t)sb * 8 + L.v) * 2);
     }
     __device__ __forceinline__ float dot(const ActSlice &A, const LaneRole &L) const {
         int s = 0;
@@ -257,7 +257,8 @@ template <int TYPE> struct RawNib32 {
     uint32_t qh, dh16, mh16;      // mh16: the block minimum (Q4_1 / Q5_1 only)
     __device__ __forceinline__ float probe() const { return (float)(q.x ^ q.y ^ q.z ^ q.w ^ dh16); }
     __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
-        const size_t blk = (size_t)sb * 8 + L.v, half = (size_t)nb * 128, nblk = (size_t)nb * 8;
+        const size_t blk = (size_t)sb * 8 + L.v, half = (size_t)nb * 128, nblk = (size_t)nb * 8;   // half: where plane 1 starts (qh, e, else d)
+        // (the offsets are spelled out: written as plane_off<TYPE, ..>() they compile to other code.  Planes qs | [qh] | d | [m]; MXFP4 qs | e - kTypeLayouts, ggml_types.h)
         q = ldw(row + blk * 16);
         if (TYPE == T_Q5_0) {
             qh = *reinterpret_cast<const uint32_t *>(row + half + blk * 4);
@@ -321,9 +322,9 @@ template <> struct Raw<T_IQ4_XS> {
     __device__ __forceinline__ float probe() const { return (float)(q.x ^ q.y ^ q.z ^ q.w ^ sl ^ sh16 ^ dh16); }
     __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
         q = ldw(row + (size_t)sb * 128 + L.v * 16);
-        sl = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 128 + (size_t)sb * 4);
-        sh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 132 + (size_t)sb * 2);
-        dh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 134 + (size_t)sb * 2);
+        sl = *reinterpret_cast<const uint32_t *>(row + plane_off<T_IQ4_XS, iq4xs::P_SCALES_L>((size_t)nb) + (size_t)sb * 4);
+        sh16 = *reinterpret_cast<const uint16_t *>(row + plane_off<T_IQ4_XS, iq4xs::P_SCALES_H>((size_t)nb) + (size_t)sb * 2);
+        dh16 = *reinterpret_cast<const uint16_t *>(row + plane_off<T_IQ4_XS, iq4xs::P_D>((size_t)nb) + (size_t)sb * 2);
     }
     __device__ __forceinline__ float dot(const ActSlice &A, const LaneRole &L) const {
         int s = 0;
@@ -344,7 +345,7 @@ template <> struct Raw<T_TQ2_0> {
     __device__ __forceinline__ float probe() const { return (float)(q.x ^ q.y ^ q.z ^ q.w ^ dh16); }
     __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
         q = ldw(row + (size_t)sb * 64 + (L.c >> 1) * 32 + L.h * 16);
-        dh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 64 + (size_t)sb * 2);
+        dh16 = *reinterpret_cast<const uint16_t *>(row + plane_off<T_TQ2_0, tq2::P_D>((size_t)nb) + (size_t)sb * 2);
     }
     __device__ __forceinline__ float dot(const ActSlice &A, const LaneRole &L) const {
         const int s0 = 4 * (L.c & 1), s1 = s0 + 2;
@@ -366,8 +367,8 @@ template <> struct Raw<T_TQ1_0> {
     __device__ __forceinline__ void load(const uint8_t *row, int nb, int sb, const LaneRole &L) {
         q0 = ldw(row + (size_t)sb * 48 + tq1_piece0(L.v));
         q1 = ldw(row + (size_t)sb * 48 + tq1_piece1(L.v));
-        qh = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 48 + (size_t)sb * 4);
-        dh16 = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 52 + (size_t)sb * 2);
+        qh = *reinterpret_cast<const uint32_t *>(row + plane_off<T_TQ1_0, tq1::P_QH>((size_t)nb) + (size_t)sb * 4);
+        dh16 = *reinterpret_cast<const uint16_t *>(row + plane_off<T_TQ1_0, tq1::P_D>((size_t)nb) + (size_t)sb * 2);
     }
     __device__ __forceinline__ float dot(const ActSlice &A, const LaneRole &L) const {
         const int s = tq1_lane_dot(q0, q1, qh, L.v, A.lo, A.hi);

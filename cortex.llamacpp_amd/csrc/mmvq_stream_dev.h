@@ -96,7 +96,7 @@ template <bool IL> __device__ __forceinline__ const uint8_t *ring_at(const uint8
     const unsigned o = IL ? base + ((x >> 12) << 13) + (x & 4095u) : base + x;
     return ring + (o & ST_MASK);
 }
-#define RO(x) ring_at<IL>(ring, base, (x))
+#define RO(...) ring_at<IL>(ring, base, (__VA_ARGS__))
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q4_K> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
     const unsigned b = row_off + (unsigned)sb * 144u;
     r.hdr = lds16(RO(b));
@@ -113,38 +113,39 @@ template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q5_K> &r, con
 }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q6_K> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
     r.ql = lds16(RO(row_off + (unsigned)sb * 128u + (unsigned)L.v * 16u));
-    r.qh = lds16(RO(row_off + (unsigned)nb * 128u + (unsigned)sb * 64u + (unsigned)L.n * 32u + (unsigned)(L.w & 1) * 16u));
-    const unsigned so = row_off + (unsigned)nb * 192u + (unsigned)sb * 16u + 8u * (unsigned)L.n + (unsigned)L.w;
+    r.qh = lds16(RO(row_off + plane_off<T_Q6_K, q6k::P_QH>((unsigned)nb) + (unsigned)sb * 64u + (unsigned)L.n * 32u + (unsigned)(L.w & 1) * 16u));
+    const unsigned so = row_off + plane_off<T_Q6_K, q6k::P_SCALES>((unsigned)nb) + (unsigned)sb * 16u + 8u * (unsigned)L.n + (unsigned)L.w;
     r.sc_lo = *reinterpret_cast<const int8_t *>(RO(so));
     r.sc_hi = *reinterpret_cast<const int8_t *>(RO(so + 4u));
-    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 208u + (unsigned)sb * 2u));
+    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + plane_off<T_Q6_K, q6k::P_D>((unsigned)nb) + (unsigned)sb * 2u));
 }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q8_0> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
     const unsigned b = row_off + (unsigned)sb * 256u + (unsigned)L.v * 32u;
     r.q0 = lds16(RO(b));
     r.q1 = lds16(RO(b + 16u));
-    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 256u + ((unsigned)sb * 8u + (unsigned)L.v) * 2u));
+    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + plane_off<T_Q8_0, q80::P_D>((unsigned)nb * 8u) + ((unsigned)sb * 8u + (unsigned)L.v) * 2u));
 }
 // Q2_K / Q3_K device rows (planes: qs | scales | d, dmin  and  hmask | qs | scales | d) and the 32-element formats (nibbles | [qh] | scales): the fields of
 // Raw<>::load in mmvq_fast_dev.h, read out of the ring
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q2_K> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
     r.q = lds16(RO(row_off + (unsigned)sb * 64u + (unsigned)(L.c >> 1) * 32u + (unsigned)L.h * 16u));
-    const unsigned so = row_off + (unsigned)nb * 64u + (unsigned)sb * 16u + 4u * (unsigned)L.c + (unsigned)L.h;
+    const unsigned so = row_off + plane_off<T_Q2_K, q2k::P_SCALES>((unsigned)nb) + (unsigned)sb * 16u + 4u * (unsigned)L.c + (unsigned)L.h;
     r.sc_lo = *RO(so);
     r.sc_hi = *RO(so + 2u);
-    r.dd = *reinterpret_cast<const uint32_t *>(RO(row_off + (unsigned)nb * 80u + (unsigned)sb * 4u));
+    r.dd = *reinterpret_cast<const uint32_t *>(RO(row_off + plane_off<T_Q2_K, q2k::P_DM>((unsigned)nb) + (unsigned)sb * 4u));
 }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q3_K> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
     r.hm = lds16(RO(row_off + (unsigned)sb * 32u + (unsigned)L.h * 16u));
-    r.q = lds16(RO(row_off + (unsigned)nb * 32u + (unsigned)sb * 64u + (unsigned)(L.c >> 1) * 32u + (unsigned)L.h * 16u));
-    const unsigned so = row_off + (unsigned)nb * 96u + (unsigned)sb * 12u;
+    r.q = lds16(RO(row_off + plane_off<T_Q3_K, q3k::P_QS>((unsigned)nb) + (unsigned)sb * 64u + (unsigned)(L.c >> 1) * 32u + (unsigned)L.h * 16u));
+    const unsigned so = row_off + plane_off<T_Q3_K, q3k::P_SCALES>((unsigned)nb) + (unsigned)sb * 12u;
     r.s0w = *reinterpret_cast<const uint32_t *>(RO(so));
     r.s1w = *reinterpret_cast<const uint32_t *>(RO(so + 4u));
     r.s2w = *reinterpret_cast<const uint32_t *>(RO(so + 8u));
-    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 108u + (unsigned)sb * 2u));
+    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + plane_off<T_Q3_K, q3k::P_D>((unsigned)nb) + (unsigned)sb * 2u));
 }
 template <bool IL, int TYPE> __device__ __forceinline__ void ring_load_nib32(RawNib32<TYPE> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
-    const unsigned blk = (unsigned)sb * 8u + (unsigned)L.v, half = (unsigned)nb * 128u, nblk = (unsigned)nb * 8u;
+    const unsigned blk = (unsigned)sb * 8u + (unsigned)L.v, half = (unsigned)nb * 128u, nblk = (unsigned)nb * 8u;   // half: where plane 1 starts (qh, e, else d)
+    // (the offsets are spelled out: written as plane_off<TYPE, ..>() they compile to other code.  Planes qs | [qh] | d | [m]; MXFP4 qs | e - kTypeLayouts, ggml_types.h)
     r.q = lds16(RO(row_off + blk * 16u));
     if (TYPE == T_Q5_0) {
         r.qh = *reinterpret_cast<const uint32_t *>(RO(row_off + half + blk * 4u));
@@ -170,19 +171,19 @@ template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_Q5_1> &r, con
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_MXFP4> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) { ring_load_nib32<IL, T_MXFP4>(r, ring, base, row_off, nb, sb, L); }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_IQ4_XS> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
     r.q = lds16(RO(row_off + (unsigned)sb * 128u + (unsigned)L.v * 16u));
-    r.sl = *reinterpret_cast<const uint32_t *>(RO(row_off + (unsigned)nb * 128u + (unsigned)sb * 4u));
-    r.sh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 132u + (unsigned)sb * 2u));
-    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 134u + (unsigned)sb * 2u));
+    r.sl = *reinterpret_cast<const uint32_t *>(RO(row_off + plane_off<T_IQ4_XS, iq4xs::P_SCALES_L>((unsigned)nb) + (unsigned)sb * 4u));
+    r.sh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + plane_off<T_IQ4_XS, iq4xs::P_SCALES_H>((unsigned)nb) + (unsigned)sb * 2u));
+    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + plane_off<T_IQ4_XS, iq4xs::P_D>((unsigned)nb) + (unsigned)sb * 2u));
 }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_TQ2_0> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
     r.q = lds16(RO(row_off + (unsigned)sb * 64u + (unsigned)(L.c >> 1) * 32u + (unsigned)L.h * 16u));
-    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 64u + (unsigned)sb * 2u));
+    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + plane_off<T_TQ2_0, tq2::P_D>((unsigned)nb) + (unsigned)sb * 2u));
 }
 template <bool IL> __device__ __forceinline__ void ring_load(Raw<T_TQ1_0> &r, const uint8_t *ring, unsigned base, unsigned row_off, int nb, int sb, const LaneRole &L) {
     r.q0 = lds16(RO(row_off + (unsigned)sb * 48u + tq1_piece0(L.v)));
     r.q1 = lds16(RO(row_off + (unsigned)sb * 48u + tq1_piece1(L.v)));
-    r.qh = *reinterpret_cast<const uint32_t *>(RO(row_off + (unsigned)nb * 48u + (unsigned)sb * 4u));
-    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + (unsigned)nb * 52u + (unsigned)sb * 2u));
+    r.qh = *reinterpret_cast<const uint32_t *>(RO(row_off + plane_off<T_TQ1_0, tq1::P_QH>((unsigned)nb) + (unsigned)sb * 4u));
+    r.dh16 = *reinterpret_cast<const uint16_t *>(RO(row_off + plane_off<T_TQ1_0, tq1::P_D>((unsigned)nb) + (unsigned)sb * 2u));
 }
 #undef RO
 

@@ -181,6 +181,8 @@ __device__ __forceinline__ float dequant_elem(int type, const uint8_t *row, int 
         case T_F32: return reinterpret_cast<const float *>(row)[e];
         case T_F16: return h2f(reinterpret_cast<const uint16_t *>(row)[e]);
         case T_BF16: return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t *>(row)[e] << 16);   // the upper half of an f32: exact for every bit pattern
+        // the 32-element types: the type is a run-time value and the offsets come from K, not from a block count, so they are spelled out - written as
+        // plane_off<>() they compile to other code.  Planes (kTypeLayouts, ggml_types.h): Q8_0 qs [K] | d; the nibble types qs [K / 2] | [qh] | d | [m]; MXFP4 qs | e
         case T_Q8_0: {
             const float d = h2f(*reinterpret_cast<const uint16_t *>(row + K + (e >> 5) * 2));
             return __fmul_rn((float)(int8_t)row[e], d);
@@ -226,45 +228,45 @@ __device__ __forceinline__ float dequant_elem(int type, const uint8_t *row, int 
         }
         case T_Q2_K: {   // element (n, j, l) of block sb: bits 2 j .. 2 j + 1 of qs[32 n + l]; sub-block is = 8 n + 2 j + l / 16
             const int nb = K >> 8, sb = e >> 8, r = e & 255, n = r >> 7, j = (r >> 5) & 3, l = r & 31, is = 8 * n + 2 * j + (l >> 4);
-            const uint8_t q = row[(size_t)sb * 64 + 32 * n + l], sc = row[(size_t)nb * 64 + (size_t)sb * 16 + is];
-            const uint16_t *dm = reinterpret_cast<const uint16_t *>(row + (size_t)nb * 80 + (size_t)sb * 4);
+            const uint8_t q = row[(size_t)sb * 64 + 32 * n + l], sc = row[plane_off<T_Q2_K, q2k::P_SCALES>((size_t)nb) + (size_t)sb * 16 + is];
+            const uint16_t *dm = reinterpret_cast<const uint16_t *>(row + plane_off<T_Q2_K, q2k::P_DM>((size_t)nb) + (size_t)sb * 4);
             const float dl = __fmul_rn(h2f(dm[0]), (float)(sc & 0xf)), ml = __fmul_rn(h2f(dm[1]), (float)(sc >> 4));
             return __fsub_rn(__fmul_rn(dl, (float)((q >> (2 * j)) & 3)), ml);
         }
         case T_Q3_K: {
             const int nb = K >> 8, sb = e >> 8, r = e & 255, n = r >> 7, j = (r >> 5) & 3, l = r & 31, is = 8 * n + 2 * j + (l >> 4);
-            const uint8_t q = row[(size_t)nb * 32 + (size_t)sb * 64 + 32 * n + l], hm = row[(size_t)sb * 32 + l];
-            const uint8_t *s12 = row + (size_t)nb * 96 + (size_t)sb * 12;
+            const uint8_t q = row[plane_off<T_Q3_K, q3k::P_QS>((size_t)nb) + (size_t)sb * 64 + 32 * n + l], hm = row[(size_t)sb * 32 + l];
+            const uint8_t *s12 = row + plane_off<T_Q3_K, q3k::P_SCALES>((size_t)nb) + (size_t)sb * 12;
             const int low = is < 8 ? (s12[is] & 0xf) : (s12[is - 8] >> 4), high = (s12[8 + (is & 3)] >> (2 * (is >> 2))) & 3;
-            const float d = h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 108 + (size_t)sb * 2));
+            const float d = h2f(*reinterpret_cast<const uint16_t *>(row + plane_off<T_Q3_K, q3k::P_D>((size_t)nb) + (size_t)sb * 2));
             const int code = (int)((q >> (2 * j)) & 3) - (((hm >> (4 * n + j)) & 1) ? 0 : 4);
             return __fmul_rn(__fmul_rn(d, (float)((low | (high << 4)) - 32)), (float)code);
         }
         case T_IQ4_XS: {   // element j of sub-block ib: nibble j / 16 of qs[16 ib + j % 16]; dequantize_row_iq4_xs: dl = d * (ls - 32), y = dl * level
             const int nb = K >> 8, sb = e >> 8, r = e & 255, ib = r >> 5, j = r & 31;
             const int nib = (row[(size_t)sb * 128 + 16 * ib + (j & 15)] >> (4 * (j >> 4))) & 0x0f;
-            const uint32_t sl = *reinterpret_cast<const uint32_t *>(row + (size_t)nb * 128 + (size_t)sb * 4);
-            const uint32_t sh = *reinterpret_cast<const uint16_t *>(row + (size_t)nb * 132 + (size_t)sb * 2);
-            const float d = h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 134 + (size_t)sb * 2));
+            const uint32_t sl = *reinterpret_cast<const uint32_t *>(row + plane_off<T_IQ4_XS, iq4xs::P_SCALES_L>((size_t)nb) + (size_t)sb * 4);
+            const uint32_t sh = *reinterpret_cast<const uint16_t *>(row + plane_off<T_IQ4_XS, iq4xs::P_SCALES_H>((size_t)nb) + (size_t)sb * 2);
+            const float d = h2f(*reinterpret_cast<const uint16_t *>(row + plane_off<T_IQ4_XS, iq4xs::P_D>((size_t)nb) + (size_t)sb * 2));
             return __fmul_rn(__fmul_rn(d, (float)iq4xs_scale(sl, sh, ib)), (float)iq4nl_value(nib));
         }
         case T_TQ2_0: {   // element 128 h + 32 l + m: bits 2 l .. 2 l + 1 of qs[32 h + m]; dequantize_row_tq2_0: y = (q - 1) * d (a product: - 0.0 where it gives one)
             const int nb = K >> 8, sb = e >> 8, r = e & 255;
             const int q = (row[(size_t)sb * 64 + 32 * (r >> 7) + (r & 31)] >> (2 * ((r >> 5) & 3))) & 3;
-            return __fmul_rn((float)(q - 1), h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 64 + (size_t)sb * 2)));
+            return __fmul_rn((float)(q - 1), h2f(*reinterpret_cast<const uint16_t *>(row + plane_off<T_TQ2_0, tq2::P_D>((size_t)nb) + (size_t)sb * 2)));
         }
         case T_TQ1_0: {
             const int nb = K >> 8, sb = e >> 8;
             int byte, n;
             tq1_elem(e & 255, byte, n);
-            const uint32_t b = byte < 48 ? row[(size_t)sb * 48 + byte] : row[(size_t)nb * 48 + (size_t)sb * 4 + (byte - 48)];
-            return __fmul_rn((float)(tq1_trit(b, n) - 1), h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 52 + (size_t)sb * 2)));
+            const uint32_t b = byte < 48 ? row[(size_t)sb * 48 + byte] : row[plane_off<T_TQ1_0, tq1::P_QH>((size_t)nb) + (size_t)sb * 4 + (byte - 48)];
+            return __fmul_rn((float)(tq1_trit(b, n) - 1), h2f(*reinterpret_cast<const uint16_t *>(row + plane_off<T_TQ1_0, tq1::P_D>((size_t)nb) + (size_t)sb * 2)));
         }
         case T_Q6_K: {
             const int nb = K >> 8, sb = e >> 8, r = e & 255, n = r >> 7, rr = r & 127, k = rr >> 5, l = rr & 31;
-            const uint8_t *ql = row + (size_t)sb * 128 + n * 64, *qh = row + (size_t)nb * 128 + (size_t)sb * 64 + n * 32;
-            const int8_t *sc = reinterpret_cast<const int8_t *>(row + (size_t)nb * 192 + (size_t)sb * 16 + n * 8);
-            const float d = h2f(*reinterpret_cast<const uint16_t *>(row + (size_t)nb * 208 + (size_t)sb * 2));
+            const uint8_t *ql = row + (size_t)sb * 128 + n * 64, *qh = row + plane_off<T_Q6_K, q6k::P_QH>((size_t)nb) + (size_t)sb * 64 + n * 32;
+            const int8_t *sc = reinterpret_cast<const int8_t *>(row + plane_off<T_Q6_K, q6k::P_SCALES>((size_t)nb) + (size_t)sb * 16 + n * 8);
+            const float d = h2f(*reinterpret_cast<const uint16_t *>(row + plane_off<T_Q6_K, q6k::P_D>((size_t)nb) + (size_t)sb * 2));
             const int lo = (k & 1) ? ql[l + 32] : ql[l];
             const int nib = (k & 2) ? (lo >> 4) : (lo & 0x0f);
             const int q = (nib | (((qh[l] >> (2 * k)) & 3) << 4)) - 32;

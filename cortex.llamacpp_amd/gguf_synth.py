@@ -16,8 +16,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-# ggml type ids
+# ggml type ids: the package's one list of them (binding.py takes them from here; tests pin them to csrc/ggml_types.h)
 F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 2, 8, 12, 13, 14
+Q8_K = 15   # an activation format, never a file type
 Q2_K, Q3_K = 10, 11
 Q5_0, IQ4_NL = 6, 20
 Q4_1, Q5_1 = 3, 7

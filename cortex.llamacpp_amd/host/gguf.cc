@@ -48,44 +48,6 @@ void read_scalar(Reader &r, uint32_t type, GGUFValue &v) {
 }
 }  // namespace
 
-size_t ggml_type_row_bytes(int type, int64_t n) {
-    int be = 0, bb = 0;
-    switch (type) {
-        case 0: be = 1; bb = 4; break;      // f32
-        case 1: be = 1; bb = 2; break;      // f16
-        case 2: be = 32; bb = 18; break;    // q4_0
-        case 3: be = 32; bb = 20; break;    // q4_1
-        case 6: be = 32; bb = 22; break;    // q5_0
-        case 7: be = 32; bb = 24; break;    // q5_1
-        case 8: be = 32; bb = 34; break;    // q8_0
-        case 10: be = 256; bb = 84; break;  // q2_K
-        case 11: be = 256; bb = 110; break; // q3_K
-        case 20: be = 32; bb = 18; break;   // iq4_nl
-        case 23: be = 256; bb = 136; break; // iq4_xs
-        case 30: be = 1; bb = 2; break;     // bf16
-        case 39: be = 32; bb = 17; break;   // mxfp4
-        case 34: be = 256; bb = 54; break;  // tq1_0
-        case 35: be = 256; bb = 66; break;  // tq2_0
-        case 12: be = 256; bb = 144; break; // q4_K
-        case 13: be = 256; bb = 176; break; // q5_K
-        case 14: be = 256; bb = 210; break; // q6_K
-        default: return 0;
-    }
-    if (n % be) return 0;
-    return (size_t)(n / be) * bb;
-}
-
-const char *ggml_type_name(int type) {
-    switch (type) {
-        case 0: return "f32"; case 1: return "f16"; case 2: return "q4_0"; case 3: return "q4_1";
-        case 6: return "q5_0"; case 7: return "q5_1"; case 8: return "q8_0"; case 10: return "q2_K";
-        case 11: return "q3_K"; case 12: return "q4_K"; case 13: return "q5_K"; case 14: return "q6_K";
-        case 15: return "q8_K"; case 23: return "iq4_xs"; case 30: return "bf16"; case 39: return "mxfp4";
-        case 34: return "tq1_0"; case 35: return "tq2_0";
-    }
-    return "unknown";
-}
-
 GGUFFile::~GGUFFile() {
     if (map_) munmap(map_, file_size);
     if (fd_ >= 0) close(fd_);

@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "../csrc/ggml_types.h"   // ggml_type_name, the block sizes
+
 namespace mi355 {
 
 enum GGUFValueType : uint32_t {
@@ -63,7 +65,11 @@ class GGUFFile {
     std::map<std::string, size_t> index_;
 };
 
-size_t ggml_type_row_bytes(int type, int64_t n);   // 0 if unsupported
-const char *ggml_type_name(int type);
+// bytes of a row of n elements in the file; 0 for a type a file cannot hold (Q8_K is an activation format), for a row that is not a whole number of blocks,
+// and for an unknown id
+inline size_t ggml_type_row_bytes(int type, int64_t n) {
+    const int be = ggml_block_elems(type);
+    return (type == T_Q8_K || be == 0 || n % be) ? 0 : ggml_row_bytes(type, n);
+}
 
 }  // namespace mi355

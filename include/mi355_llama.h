@@ -253,6 +253,9 @@ MI355_API int mi355_op_rope_yarn(float *x, int32_t n_head, int32_t head_dim, int
                                  float ext_factor, float attn_factor, float corr_lo, float corr_hi);
 MI355_API int mi355_op_get_rows(int32_t type, const void *table, int64_t row_elems, int64_t n_rows_table,
                                 const int32_t *ids, int64_t n_ids, float *dst);
+// the upload's regrouping alone: n_rows ggml rows of row_elems elements -> n_rows * ((row bytes + 15) & ~15) bytes of device rows in dst, whose padding
+// bytes hold 0xA5.  MI355_ERR_ARG for an unknown type, a row that is not a whole number of blocks, non-positive sizes.
+MI355_API int mi355_op_repack_rows(int32_t type, const void *src_rows, int64_t row_elems, int64_t n_rows, void *dst);
 MI355_API int mi355_op_swiglu(const float *gate, const float *up, int64_t n, float *y);
 MI355_API int mi355_op_soft_max(const float *x, const float *mask, int64_t n, int64_t rows, float scale, float *y);
 /* build_moe_ffn's expert selection: softmax over n_expert router logits per token, the k largest (first index wins ties), weights

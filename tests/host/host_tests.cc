@@ -1438,6 +1438,71 @@ static int plan_cli(const char *gguf, int tp_rank, int tp_size, bool tp_group) {
     return 0;
 }
 
+// ---------------------------------------------------------------- the type table (csrc/ggml_types.h) against the numbers it replaced
+// What host/gguf.cc's two switches answered before the table, written out: {id, name, block elements, block bytes as a file type (0: none)}.
+static void test_type_row_bytes_and_names() {
+    struct Old { int id; const char *name; int be, bb; };
+    const Old old[] = {{0, "f32", 1, 4}, {1, "f16", 1, 2}, {2, "q4_0", 32, 18}, {3, "q4_1", 32, 20}, {6, "q5_0", 32, 22}, {7, "q5_1", 32, 24}, {8, "q8_0", 32, 34},
+                       {10, "q2_K", 256, 84}, {11, "q3_K", 256, 110}, {12, "q4_K", 256, 144}, {13, "q5_K", 256, 176}, {14, "q6_K", 256, 210}, {15, "q8_K", 256, 0},
+                       {20, "iq4_nl", 32, 18},                          // the one intended change: this id answered "unknown" for its name
+                       {23, "iq4_xs", 256, 136}, {30, "bf16", 1, 2}, {34, "tq1_0", 256, 54}, {35, "tq2_0", 256, 66}, {39, "mxfp4", 32, 17}};
+    for (int id = -1; id < 64; id++) {
+        const Old *o = nullptr;
+        for (const Old &x : old) if (x.id == id) o = &x;
+        CHECK(std::string(ggml_type_name(id)) == (o ? o->name : "unknown"));
+        for (int64_t n : {0, 1, 31, 32, 255, 256, 300, 768, 4096}) {
+            const size_t want = o && o->bb && n % o->be == 0 ? (size_t)(n / o->be) * o->bb : 0;
+            CHECK(ggml_type_row_bytes(id, n) == want);
+        }
+        CHECK((ggml_block_elems(id) == 0) == (o == nullptr) && (ggml_block_bytes(id) == 0) == (o == nullptr));
+        CHECK(ggml_row_bytes(id, 768) == (o ? (size_t)(768 / o->be) * (o->id == 15 ? 292 : o->bb) : 0));
+    }
+    CHECK(std::string(ggml_type_name(20)) == "iq4_nl" && std::string(ggml_type_name(99)) == "unknown" && ggml_type_row_bytes(99, 256) == 0);
+}
+
+// Every plane of every repacked type at three blocks, from the layout comment the table replaced ([field: bytes per block] in device order).
+static void test_plane_offsets() {
+    struct Old { int id; int n; size_t off[5]; };                       // off[n]: the row's unpadded size
+    const Old old[] = {
+        {T_Q6_K, 4, {0, 3 * 128, 3 * 192, 3 * 208, 3 * 210}},           // [ql: nb*128][qh: nb*64][scales: nb*16][d: nb*2]
+        {T_Q8_0, 2, {0, 96, 102}},                                      // [qs: K][d: K/32*2]
+        {T_Q2_K, 3, {0, 3 * 64, 3 * 80, 3 * 84}},                       // [qs: nb*64][scales: nb*16][d, dmin: nb*4]
+        {T_Q3_K, 4, {0, 3 * 32, 3 * 96, 3 * 108, 3 * 110}},             // [hmask: nb*32][qs: nb*64][scales: nb*12][d: nb*2]
+        {T_Q4_0, 2, {0, 48, 54}},                                       // [qs: K/2][d: K/32*2]
+        {T_IQ4_NL, 2, {0, 48, 54}},
+        {T_Q5_0, 3, {0, 48, 60, 66}},                                   // [qs: K/2][qh: K/32*4][d: K/32*2]
+        {T_Q4_1, 3, {0, 48, 54, 60}},                                   // [qs: K/2][d: K/32*2][m: K/32*2]
+        {T_Q5_1, 4, {0, 48, 60, 66, 72}},                               // [qs: K/2][qh: K/32*4][d: K/32*2][m: K/32*2]
+        {T_MXFP4, 2, {0, 48, 51}},                                      // [qs: K/2][e: K/32]
+        {T_IQ4_XS, 4, {0, 384, 396, 402, 408}},                         // [qs: nb*128][scales_l: nb*4][scales_h: nb*2][d: nb*2]
+        {T_TQ2_0, 2, {0, 3 * 64, 3 * 66}},                              // [qs: nb*64][d: nb*2]
+        {T_TQ1_0, 3, {0, 3 * 48, 3 * 52, 3 * 54}},                      // [qs: nb*48][qh: nb*4][d: nb*2]
+    };
+    int repacked = 0;
+    for (int id = 0; id < 64; id++) {
+        const Old *o = nullptr;
+        for (const Old &x : old) if (x.id == id) o = &x;
+        CHECK(type_is_repacked(id) == (o != nullptr));
+        CHECK(type_layout(id).n_planes == (o ? o->n : 0));
+        if (!o) continue;
+        repacked++;
+        for (int p = 0; p <= o->n; p++) CHECK(plane_off(id, p, 3) == o->off[p]);
+        CHECK(dev_row_bytes(id, 3 * ggml_block_elems(id)) == ((o->off[o->n] + 15) & ~(size_t)15));
+    }
+    CHECK(repacked == 13);
+    // the named indices say which plane is which
+    CHECK(plane_off(T_Q6_K, q6k::P_QH, 3) == 384 && plane_off(T_Q6_K, q6k::P_SCALES, 3) == 576 && plane_off(T_Q6_K, q6k::P_D, 3) == 624);
+    CHECK(plane_off(T_Q2_K, q2k::P_SCALES, 3) == 192 && plane_off(T_Q2_K, q2k::P_DM, 3) == 240);
+    CHECK(plane_off(T_Q3_K, q3k::P_QS, 3) == 96 && plane_off(T_Q3_K, q3k::P_SCALES, 3) == 288 && plane_off(T_Q3_K, q3k::P_D, 3) == 324);
+    CHECK(plane_off(T_IQ4_XS, iq4xs::P_SCALES_L, 3) == 384 && plane_off(T_IQ4_XS, iq4xs::P_SCALES_H, 3) == 396 && plane_off(T_IQ4_XS, iq4xs::P_D, 3) == 402);
+    CHECK(plane_off(T_TQ1_0, tq1::P_QH, 3) == 144 && plane_off(T_TQ1_0, tq1::P_D, 3) == 156 && plane_off(T_TQ2_0, tq2::P_D, 3) == 192);
+    CHECK(plane_off(T_Q8_0, q80::P_D, 3) == 96 && plane_off(T_MXFP4, mxfp4::P_E, 3) == 48);
+    CHECK(plane_off(T_Q5_0, nib32::P_QH, 3) == 48 && plane_off(T_Q5_1, nib32::P_QH, 3) == 48);
+    CHECK(plane_off(T_Q4_0, nib32_p_d(T_Q4_0), 3) == 48 && plane_off(T_IQ4_NL, nib32_p_d(T_IQ4_NL), 3) == 48 && plane_off(T_Q5_0, nib32_p_d(T_Q5_0), 3) == 60);
+    CHECK(plane_off(T_Q4_1, nib32_p_d(T_Q4_1), 3) == 48 && plane_off(T_Q4_1, nib32_p_m(T_Q4_1), 3) == 54);
+    CHECK(plane_off(T_Q5_1, nib32_p_d(T_Q5_1), 3) == 60 && plane_off(T_Q5_1, nib32_p_m(T_Q5_1), 3) == 66);
+}
+
 static const char *volatile g_stage = "start";
 
 int main(int argc, char **argv) {
@@ -1451,6 +1516,8 @@ int main(int argc, char **argv) {
     signal(SIGTERM, [](int) { const char *m = g_stage; if (write(2, "hung in: ", 9) < 0 || write(2, m, strlen(m)) < 0 || write(2, "\n", 1) < 0) {} _exit(124); });
 #define STAGE(f) do { g_stage = #f; f(); } while (0)
     STAGE(test_json);
+    STAGE(test_type_row_bytes_and_names);
+    STAGE(test_plane_offsets);
     STAGE(test_vocab);
     STAGE(test_vocab_wordpiece);
     STAGE(test_sampler);
