@@ -123,6 +123,14 @@ SYMBOLS = {
                                      _vp, _vp, _vp, _vp]),
     "mi355_op_attn_decode_neox": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _f32, _i32,
                                             _vp, _vp, _vp]),
+    "mi355_op_flash_attn_seq": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _vp]),
+    "mi355_op_flash_attn_plan": (C.c_int, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "mi355_op_attn_step_seq": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _f32, _i32, _vp,
+                                         _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "mi355_op_attn_decode_neox_seq": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp,
+                                                _f32, _i32, _vp, _vp, _vp]),
+    "mi355_op_attn_batch_step": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _f32,
+                                           _i32, _vp, _vp]),
     "mi355_op_kv_store": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "mi355_op_k_shift": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _f32, _f32, _vp, _f32, _f32, _f32, _f32, _vp]),
     "mi355_bench_hbm_read": (C.c_double, [_sz, C.c_int]),
@@ -473,36 +481,64 @@ class Backend:
         return dst
 
     def flash_attn(self, q: np.ndarray, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows: np.ndarray, type_v: int,
-                   v_rows: np.ndarray, cell_pos, q_pos, scale: float) -> np.ndarray:
+                   v_rows: np.ndarray, cell_pos, q_pos, scale: float, cell_seq=None, q_seq=None, n_kv=None) -> np.ndarray:
+        """flash_attn_ext over a caller-supplied cache (mi355_op_flash_attn).  With cell_seq (uint64 [n_cells] bit masks), q_seq ([T], 0 .. 63) or n_kv (cells
+        the kernels scan; the launch stays sized for all of them) it is mi355_op_flash_attn_seq; what is left out is mask 1, sequence 0, every cell."""
         q = np.ascontiguousarray(q, np.float32)
         q_pos = np.ascontiguousarray(q_pos, np.int32).reshape(-1)
         cell_pos = np.ascontiguousarray(cell_pos, np.int32)
         k_rows = np.ascontiguousarray(k_rows.view(np.uint8))
         v_rows = np.ascontiguousarray(v_rows.view(np.uint8))
         out = np.zeros((q_pos.size, n_head, hd), np.float32)
-        self._chk(self.lib.mi355_op_flash_attn(_ptr(q), q_pos.size, n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v,
-                                               _ptr(v_rows), cell_pos.size, _ptr(cell_pos), _ptr(q_pos), scale, _ptr(out)),
-                  "op_flash_attn")
+        if cell_seq is None and q_seq is None and n_kv is None:
+            self._chk(self.lib.mi355_op_flash_attn(_ptr(q), q_pos.size, n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v,
+                                                   _ptr(v_rows), cell_pos.size, _ptr(cell_pos), _ptr(q_pos), scale, _ptr(out)),
+                      "op_flash_attn")
+            return out
+        cs = np.ones(cell_pos.size, np.uint64) if cell_seq is None else np.ascontiguousarray(cell_seq, np.uint64).reshape(-1)
+        qs = np.zeros(q_pos.size, np.int32) if q_seq is None else np.ascontiguousarray(q_seq, np.int32).reshape(-1)
+        assert cs.size == cell_pos.size and qs.size == q_pos.size
+        self._chk(self.lib.mi355_op_flash_attn_seq(_ptr(q), q_pos.size, n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v, _ptr(v_rows), cell_pos.size,
+                                                   _ptr(cell_pos), _ptr(cs), _ptr(q_pos), _ptr(qs), int(cell_pos.size if n_kv is None else n_kv), scale, _ptr(out)),
+                  "op_flash_attn_seq")
         return out
 
+    def flash_attn_plan(self, T: int, n_head: int, n_head_kv: int, hd: int, type_k: int, type_v: int, n_cells: int):
+        """(key splits of the split kernel, key splits of the matrix-core prompt kernel, whether the prompt kernel takes the call) for a flash_attn call."""
+        o = np.zeros(3, np.int32)
+        self._chk(self.lib.mi355_op_flash_attn_plan(int(T), n_head, n_head_kv, hd, type_k, type_v, int(n_cells), _ptr(o)), "op_flash_attn_plan")
+        return int(o[0]), int(o[1]), bool(o[2])
+
     def attn_step(self, q, k_new, v_new, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows, type_v: int, v_rows, cell_pos, tok_pos: int,
-                  tok_cell: int, rope_base: float, n_rot: int, scale: float, type_o: int, W_o, n_embd: int, resid, fused: bool, k_row_bytes: int, v_row_bytes: int):
-        """One single-token attention block (mi355_op_attn_step): returns (att [H * D], out [n_embd], k_row, v_row)."""
+                  tok_cell: int, rope_base: float, n_rot: int, scale: float, type_o: int, W_o, n_embd: int, resid, fused: bool, k_row_bytes: int, v_row_bytes: int,
+                  cell_seq=None, tok_seq: int = 0, use_lists: bool = False):
+        """One single-token attention block (mi355_op_attn_step): returns (att [H * D], out [n_embd], k_row, v_row).  cell_seq / tok_seq / use_lists: the cells'
+        sequence masks, the token's sequence and the chunk-list walk (mi355_op_attn_step_seq)."""
         q = np.ascontiguousarray(q, np.float32); k_new = np.ascontiguousarray(k_new, np.float32); v_new = np.ascontiguousarray(v_new, np.float32)
         cell_pos = np.ascontiguousarray(cell_pos, np.int32)
         k_rows = np.ascontiguousarray(k_rows.view(np.uint8)); v_rows = np.ascontiguousarray(v_rows.view(np.uint8))
         W_o = np.ascontiguousarray(W_o.view(np.uint8)); resid = np.ascontiguousarray(resid, np.float32)
         att = np.zeros(n_head * hd, np.float32); out = np.zeros(n_embd, np.float32)
         kr = np.zeros(k_row_bytes, np.uint8); vr = np.zeros(v_row_bytes, np.uint8)
-        self._chk(self.lib.mi355_op_attn_step(_ptr(q), _ptr(k_new), _ptr(v_new), n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v, _ptr(v_rows), cell_pos.size,
-                                              _ptr(cell_pos), int(tok_pos), int(tok_cell), float(rope_base), int(n_rot), float(scale), type_o, _ptr(W_o), n_embd,
-                                              _ptr(resid), int(bool(fused)), _ptr(att), _ptr(out), _ptr(kr), _ptr(vr)), "op_attn_step")
+        if cell_seq is None and tok_seq == 0 and not use_lists:
+            self._chk(self.lib.mi355_op_attn_step(_ptr(q), _ptr(k_new), _ptr(v_new), n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v, _ptr(v_rows), cell_pos.size,
+                                                  _ptr(cell_pos), int(tok_pos), int(tok_cell), float(rope_base), int(n_rot), float(scale), type_o, _ptr(W_o), n_embd,
+                                                  _ptr(resid), int(bool(fused)), _ptr(att), _ptr(out), _ptr(kr), _ptr(vr)), "op_attn_step")
+            return att, out, kr, vr
+        cs = None if cell_seq is None else np.ascontiguousarray(cell_seq, np.uint64).reshape(-1)
+        assert cs is None or cs.size == cell_pos.size
+        self._chk(self.lib.mi355_op_attn_step_seq(_ptr(q), _ptr(k_new), _ptr(v_new), n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v, _ptr(v_rows), cell_pos.size,
+                                                  _ptr(cell_pos), _ptr(cs), int(tok_pos), int(tok_seq), int(tok_cell), int(bool(use_lists)), float(rope_base), int(n_rot),
+                                                  float(scale), type_o, _ptr(W_o), n_embd, _ptr(resid), int(bool(fused)), _ptr(att), _ptr(out), _ptr(kr), _ptr(vr)),
+                  "op_attn_step_seq")
         return att, out, kr, vr
 
     def attn_decode_neox(self, q, k_new, v_new, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows, type_v: int, v_rows, cell_pos, tok_pos: int,
-                         tok_cell: int, rope_base: float, scale: float, q_norm, k_norm, eps: float, mode: int, k_row_bytes: int, v_row_bytes: int):
+                         tok_cell: int, rope_base: float, scale: float, q_norm, k_norm, eps: float, mode: int, k_row_bytes: int, v_row_bytes: int,
+                         cell_seq=None, tok_seq: int = 0, use_lists: bool = False):
         """The decode attention of one token with NEOX rope and optional per-head q / k RMSNorm weights (mi355_op_attn_decode_neox; q_norm / k_norm: [hd]
-        f32 or None): returns (att [H * D], k_row, v_row).  mode 1: single-launch step, 0: store-fused batched form, 2: generic rope_kv_store path."""
+        f32 or None): returns (att [H * D], k_row, v_row).  mode 1: single-launch step, 0: store-fused batched form, 2: generic rope_kv_store path.
+        cell_seq / tok_seq / use_lists as attn_step (mi355_op_attn_decode_neox_seq)."""
         q = np.ascontiguousarray(q, np.float32); k_new = np.ascontiguousarray(k_new, np.float32); v_new = np.ascontiguousarray(v_new, np.float32)
         cell_pos = np.ascontiguousarray(cell_pos, np.int32)
         k_rows = np.ascontiguousarray(k_rows.view(np.uint8)); v_rows = np.ascontiguousarray(v_rows.view(np.uint8))
@@ -510,11 +546,39 @@ class Backend:
         kn = None if k_norm is None else np.ascontiguousarray(k_norm, np.float32)
         att = np.zeros(n_head * hd, np.float32)
         kr = np.zeros(k_row_bytes, np.uint8); vr = np.zeros(v_row_bytes, np.uint8)
-        self._chk(self.lib.mi355_op_attn_decode_neox(_ptr(q), _ptr(k_new), _ptr(v_new), n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v, _ptr(v_rows),
-                                                     cell_pos.size, _ptr(cell_pos), int(tok_pos), int(tok_cell), float(rope_base), float(scale),
-                                                     None if qn is None else _ptr(qn), None if kn is None else _ptr(kn), float(eps), int(mode),
-                                                     _ptr(att), _ptr(kr), _ptr(vr)), "op_attn_decode_neox")
+        if cell_seq is None and tok_seq == 0 and not use_lists:
+            self._chk(self.lib.mi355_op_attn_decode_neox(_ptr(q), _ptr(k_new), _ptr(v_new), n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v, _ptr(v_rows),
+                                                         cell_pos.size, _ptr(cell_pos), int(tok_pos), int(tok_cell), float(rope_base), float(scale),
+                                                         None if qn is None else _ptr(qn), None if kn is None else _ptr(kn), float(eps), int(mode),
+                                                         _ptr(att), _ptr(kr), _ptr(vr)), "op_attn_decode_neox")
+            return att, kr, vr
+        cs = None if cell_seq is None else np.ascontiguousarray(cell_seq, np.uint64).reshape(-1)
+        assert cs is None or cs.size == cell_pos.size
+        self._chk(self.lib.mi355_op_attn_decode_neox_seq(_ptr(q), _ptr(k_new), _ptr(v_new), n_head, n_head_kv, hd, type_k, _ptr(k_rows), type_v, _ptr(v_rows),
+                                                         cell_pos.size, _ptr(cell_pos), _ptr(cs), int(tok_pos), int(tok_seq), int(tok_cell), int(bool(use_lists)),
+                                                         float(rope_base), float(scale), _ptr(qn), _ptr(kn), float(eps), int(mode), _ptr(att), _ptr(kr), _ptr(vr)),
+                  "op_attn_decode_neox_seq")
         return att, kr, vr
+
+    def attn_batch_step(self, mode: int, q, k_new, v_new, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows, type_v: int, v_rows, n_kv: int, cell_pos,
+                        cell_seq, tok_pos, tok_seq, tok_cell, rope_base: float, n_rot: int, neox: bool, scale: float, want_q8k: bool = False):
+        """The attention of one batched single-token step (mi355_op_attn_batch_step; mode 0: store inside the attention launch, 1: the same on chunk lists,
+        2: small-batch store + attention on the lists, 3: generic store + attention).  k_rows / v_rows: the whole cache before the step [n_cells][row bytes];
+        returns (att [T][H * D], the whole K cache after the step, the whole V cache, the Q8_K blocks [T][292 * H * D / 256] or None).  Inputs are not modified."""
+        tok_pos = np.ascontiguousarray(tok_pos, np.int32).reshape(-1)
+        tok_seq = np.ascontiguousarray(tok_seq, np.int32).reshape(-1); tok_cell = np.ascontiguousarray(tok_cell, np.int32).reshape(-1)
+        T = tok_pos.size
+        q = np.ascontiguousarray(q, np.float32).reshape(T, n_head * hd)
+        k_new = np.ascontiguousarray(k_new, np.float32).reshape(T, n_head_kv * hd); v_new = np.ascontiguousarray(v_new, np.float32).reshape(T, n_head_kv * hd)
+        cell_pos = np.ascontiguousarray(cell_pos, np.int32).reshape(-1); cell_seq = np.ascontiguousarray(cell_seq, np.uint64).reshape(-1)
+        kc = np.array(k_rows, order="C", copy=True).view(np.uint8); vc = np.array(v_rows, order="C", copy=True).view(np.uint8)
+        assert tok_seq.size == T and tok_cell.size == T and kc.ndim == 2 and vc.ndim == 2 and kc.shape[0] == vc.shape[0] == cell_pos.size == cell_seq.size
+        att = np.zeros((T, n_head * hd), np.float32)
+        blk = np.zeros((T, 292 * (n_head * hd // 256)), np.uint8) if want_q8k else None
+        self._chk(self.lib.mi355_op_attn_batch_step(_ptr(q), _ptr(k_new), _ptr(v_new), T, n_head, n_head_kv, hd, type_k, _ptr(kc), type_v, _ptr(vc), cell_pos.size,
+                                                    int(n_kv), _ptr(cell_pos), _ptr(cell_seq), _ptr(tok_pos), _ptr(tok_seq), _ptr(tok_cell), float(rope_base),
+                                                    int(n_rot), int(bool(neox)), float(scale), int(mode), _ptr(att), _ptr(blk)), "op_attn_batch_step")
+        return att, kc, vc, blk
 
     def kv_store(self, form: int, q, k, v, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows, type_v: int, v_rows, tok_pos, tok_cell, rope_base: float,
                  n_rot=None, neox: bool = False, freq_scale: float = 1.0, freq_factors=None, q_norm=None, k_norm=None, eps: float = 0.0):

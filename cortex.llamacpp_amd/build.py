@@ -28,7 +28,7 @@ def sources(experiments: bool) -> list:
 
 
 SRC = sources(EXPERIMENTS)
-HDRS = ["csrc/dev_common.h", "csrc/ggml_types.h", "csrc/kernels.h", "csrc/quant_dev.h", "csrc/mmvq_fast_dev.h", "csrc/mmvq_stream_dev.h", "csrc/attn_decode_dev.h", "host/gguf.h", "host/model_plan.h", "host/runtime.h", "host/tp_comm.h", "host/json.h", "host/vocab.h",
+HDRS = ["csrc/dev_common.h", "csrc/ggml_types.h", "csrc/kernels.h", "csrc/quant_dev.h", "csrc/mmvq_fast_dev.h", "csrc/mmvq_stream_dev.h", "csrc/attn_decode_dev.h", "host/gguf.h", "host/model_plan.h", "host/runtime.h", "host/attn_chunks.h", "host/tp_comm.h", "host/json.h", "host/vocab.h",
         "host/sampling.h", "host/grammar.h", "host/log.h", "host/backend_iface.h", "host/server_context.h", "host/engine.h", "host/hip_backend.h", "host/clip.h", "host/parallel_rows.h", "host/tp_split.h", "host/shm_exchange.h",
         "../include/mi355_llama.h"]
 LIB = os.path.join(HERE, "lib", "libmi355_llama.so")

@@ -514,12 +514,15 @@ __global__ __launch_bounds__(256) void flash_attn_split_kernel(const AttnArgs a)
 
 // Merge the KV splits.  Workgroup = (256 consecutive output elements = 256/D heads, token t).
 //  1. wave w < heads-per-block: lane = split; M = max m, weight_s = exp(m_s - M) / sum_s exp(m_s - M) l_s  -> LDS
+//     The sum runs over the partials that carry weight, packed to the front in slot order: where a partial sits in the wave's sum tree must not depend on
+//     how many empty slots lie before it - a step on per-token chunk lists leaves the chunks without a visible cell out, the same step scanning every chunk
+//     publishes them as (-inf, 0), and both must merge to the same bits.  Without an empty slot the packed order is the slot order.
 //  2. every thread owns one output element and sums its split partials (independent loads, all in flight)
 //  3. wave 0 re-reads the 256 merged values from LDS (4 per lane) and, when asked, quantises them for the attn_output
 //     mat-vec (saves a launch on the decode path).
 __global__ __launch_bounds__(256) void flash_attn_combine_kernel(const float *part, float *out, int H, int D, int splits,
                                                                  ActQuant q, int want_q8k, int want_q80, const int32_t *tok_nsplits, int8_t *bh, int8_t *bl) {
-    extern __shared__ float wgt[];                 // [hpb][splits]
+    extern __shared__ float wgt[];                 // [hpb][splits] weights, then [hpb][splits] w * l of the partials that carry weight, packed
     __shared__ __attribute__((aligned(16))) float merged[256];
     const int t = blockIdx.y, b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int E = H * D, nblk = E >> 8;
@@ -537,7 +540,8 @@ __global__ __launch_bounds__(256) void flash_attn_combine_kernel(const float *pa
             const float m = sidx < splits ? p[(size_t)sidx * (D + 2) + D] : -INFINITY;
             M = fmaxf(M, wave_max(m));
         }
-        float den = 0.0f;
+        float *wl = wgt + (size_t)hpb * stride_s + (size_t)wave * stride_s;
+        int n_live = 0;
         for (int s0 = 0; s0 < splits; s0 += 64) {
             const int sidx = s0 + lane;
             float w = 0.0f, l = 0.0f;
@@ -547,8 +551,12 @@ __global__ __launch_bounds__(256) void flash_attn_combine_kernel(const float *pa
                 w = (m == -INFINITY) ? 0.0f : expf(m - M);
                 wgt[wave * stride_s + sidx] = w;
             }
-            den += wave_sum(w * l);
+            const unsigned long long live = __ballot(w != 0.0f);
+            if (w != 0.0f) wl[n_live + __popcll(live & ((1ull << lane) - 1ull))] = w * l;
+            n_live += __popcll(live);
         }
+        float den = 0.0f;
+        for (int s0 = 0; s0 < n_live; s0 += 64) den += wave_sum(s0 + lane < n_live ? wl[s0 + lane] : 0.0f);
         const float inv = 1.0f / den;
         for (int sidx = lane; sidx < splits; sidx += 64) wgt[wave * stride_s + sidx] *= inv;
     }
@@ -589,6 +597,14 @@ __global__ __launch_bounds__(256) void flash_attn_combine_kernel(const float *pa
             if (ok && (lane & 7) == 0) q.d0[(size_t)t * (E >> 5) + b * 8 + (lane >> 3)] = f2h(dd);
         }
     }
+}
+
+// dynamic LDS of the merge: two floats per head of the block and split (head_dim 64 at the longest context the decode attention takes: just above the 64 KB
+// a kernel gets without asking)
+static size_t combine_lds(int D, int splits) {
+    const size_t b = (size_t)(256 / D) * (size_t)splits * 8;
+    if (b + 1024 > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&flash_attn_combine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+    return b;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -783,7 +799,7 @@ hipError_t launch_flash_attn_decode(const AttnArgs &a, const float *cs_table, Ro
     const int nblk = (a.H * a.D + 255) >> 8;          // (the last block partial where H * D ends inside it)
     ActQuant qq;
     if (a.out_q) qq = *a.out_q;
-    hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, a.T), dim3(256), (size_t)(256 / a.D) * a.splits * 4, st, a.part, a.out, a.H, a.D, a.splits,
+    hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, a.T), dim3(256), combine_lds(a.D, a.splits), st, a.part, a.out, a.H, a.D, a.splits,
                        qq, (int)(a.out_q && a.out_q8k), (int)(a.out_q && a.out_q80), a.tok_nchunks, a.out_q ? a.out_bh : nullptr, a.out_q ? a.out_bl : nullptr);
     return hipGetLastError();
 }
@@ -875,7 +891,7 @@ hipError_t launch_flash_attn_decode_fused(const AttnArgs &a, const float *cs_tab
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || counters) return e;
     const int nblk = (a.H * a.D + 255) >> 8;          // (the last block partial where H * D ends inside it)
-    hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, 1), dim3(256), (size_t)(256 / a.D) * a.splits * 4, st, a.part, a.out, a.H, a.D, a.splits,
+    hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, 1), dim3(256), combine_lds(a.D, a.splits), st, a.part, a.out, a.H, a.D, a.splits,
                        fz.q, fz.want_q8k, fz.want_q80, (const int32_t *)nullptr, (int8_t *)nullptr, (int8_t *)nullptr);
     return hipGetLastError();
 }
@@ -959,7 +975,7 @@ hipError_t launch_flash_attn_combine(const AttnArgs &a, int splits, hipStream_t 
                                 (int)(a.out_q && a.out_q80), a.out_q ? a.out_bh : nullptr, a.out_q ? a.out_bl : nullptr);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, a.T), dim3(256), (size_t)(256 / a.D) * splits * 4, st, a.part, a.out, a.H, a.D, splits,
+    hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, a.T), dim3(256), combine_lds(a.D, splits), st, a.part, a.out, a.H, a.D, splits,
                        qq, (int)(a.out_q && a.out_q8k), (int)(a.out_q && a.out_q80), (const int32_t *)nullptr, a.out_q ? a.out_bh : nullptr, a.out_q ? a.out_bl : nullptr);
     return hipGetLastError();
 }
@@ -1145,7 +1161,7 @@ hipError_t launch_flash_attn(const AttnArgs &a, hipStream_t st) {
     const int nblk = (a.H * a.D + 255) >> 8;          // (the last block partial where H * D ends inside it)
     ActQuant qq;
     if (a.out_q) qq = *a.out_q;
-    hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, a.T), dim3(256), (size_t)(256 / a.D) * a.splits * 4, st, a.part, a.out, a.H, a.D, a.splits,
+    hipLaunchKernelGGL(flash_attn_combine_kernel, dim3(nblk, a.T), dim3(256), combine_lds(a.D, a.splits), st, a.part, a.out, a.H, a.D, a.splits,
                        qq, (int)(a.out_q && a.out_q8k), (int)(a.out_q && a.out_q80), a.tok_nchunks, a.out_q ? a.out_bh : nullptr, a.out_q ? a.out_bl : nullptr);
     return hipGetLastError();
 }

@@ -16,6 +16,7 @@
 #include "../host/hip_backend.h"
 #include "../host/log.h"
 #include "../host/runtime.h"
+#include "../host/attn_chunks.h"
 #include "../host/tp_comm.h"
 #include "../host/tp_split.h"
 #include "../host/vocab.h"
@@ -501,6 +502,25 @@ bool cache_rows_from_planes(int type, DevBuf &codes, DevBuf &scales, int G, int 
             }
     return true;
 }
+// The per-token chunk lists of a test entry's step, built by the function the runtime builds its own with (host/attn_chunks.h) and laid out as Context keeps
+// them: [64][stride] lists, then [64] counts.  grid: the chunk slots the launch gets (a.splits).
+struct ChunkLists {
+    std::unique_ptr<DevBuf> dev;
+    int stride = 0, lmax = 0, grid = 0;
+    bool make(int n_kv, int n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *tok_seq, int T) {
+        stride = (n_cells + ATTN_CHUNK_CELLS - 1) / ATTN_CHUNK_CELLS;
+        std::vector<int32_t> h((size_t)64 * (stride + 1), 0);
+        lmax = build_attn_chunk_lists(n_kv, n_cells, [&](int i, int32_t &p, uint64_t &m) { p = cell_pos[i]; m = cell_seq[i]; }, tok_seq, T, stride, h.data(),
+                                      h.data() + (size_t)64 * stride);
+        grid = attn_chunk_grid(lmax, stride);
+        dev.reset(new DevBuf(h.size() * 4));
+        return dev->up(h.data(), h.size() * 4);
+    }
+    void apply(AttnArgs &a) const {
+        a.tok_chunks = dev->as<int32_t>(); a.tok_nchunks = dev->as<int32_t>() + (size_t)64 * stride; a.chunk_stride = stride;
+        a.splits = grid;
+    }
+};
 int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y);
 }  // namespace
 
@@ -1148,57 +1168,31 @@ int mi355_op_gather_rows_f32(const float *src, int64_t n_src_rows, int64_t n, co
     return dd.down(dst, nd) ? MI355_OK : MI355_ERR_HIP;
 }
 
-int mi355_op_flash_attn(const float *q, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
-                        const void *v, int32_t n_cells, const int32_t *cell_pos, const int32_t *q_pos, float scale, float *out) {
+// flash_attn_ext over a caller-supplied cache and cell table (test entry): launch_flash_attn as a prompt batch or a generic step runs it.  cell_seq: the cells'
+// sequence bit masks, q_seq: each query's sequence (0 .. 63); a query sees cell c < n_kv where cell_pos[c] >= 0, cell_pos[c] <= q_pos and bit q_seq of
+// cell_seq[c] is set.  n_kv (1 .. n_cells) is what the kernels read from the device as the number of cells to scan; the grid, the splits and the workspace
+// are sized for n_cells, as a step of a context whose high-water mark lies below the bound its launches were sized for.
+int mi355_op_flash_attn_seq(const float *q, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v, const void *v,
+                            int32_t n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *q_pos, const int32_t *q_seq, int32_t n_kv,
+                            float scale, float *out) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if ((D != 64 && D != 128) || H % G) { fail("unsupported head geometry"); return MI355_ERR_ARG; }
-    // Build cache planes by running the store kernel on dequantised rows is not possible bit-exactly, so the
-    // planes are filled from the ggml-layout rows directly on the host.
-    const size_t kv_dim = (size_t)G * D;
-    auto fill = [&](int type, const void *rows, std::vector<uint8_t> &codes, std::vector<uint16_t> &scales) {
-        const uint8_t *src = (const uint8_t *)rows;
-        const size_t rb = ggml_row_bytes(type, (int64_t)kv_dim);
-        if (type == T_F16) {
-            codes.resize((size_t)G * n_cells * D * 2);
-            for (int c = 0; c < n_cells; c++)
-                for (int g = 0; g < G; g++)
-                    memcpy(&codes[(((size_t)g * n_cells + c) * D) * 2], src + (size_t)c * rb + (size_t)g * D * 2, (size_t)D * 2);
-        } else if (type == T_Q8_0) {
-            codes.resize((size_t)G * n_cells * D);
-            scales.resize((size_t)G * n_cells * (D / 32));
-            for (int c = 0; c < n_cells; c++)
-                for (int g = 0; g < G; g++)
-                    for (int b = 0; b < D / 32; b++) {
-                        const uint8_t *blk = src + (size_t)c * rb + ((size_t)g * (D / 32) + b) * ggml_block_bytes(T_Q8_0);
-                        memcpy(&scales[((size_t)g * n_cells + c) * (D / 32) + b], blk, 2);
-                        memcpy(&codes[((size_t)g * n_cells + c) * D + (size_t)b * 32], blk + 2, 32);
-                    }
-        } else {
-            codes.resize((size_t)G * n_cells * D / 2);
-            scales.resize((size_t)G * n_cells * (D / 32));
-            for (int c = 0; c < n_cells; c++)
-                for (int g = 0; g < G; g++)
-                    for (int b = 0; b < D / 32; b++) {
-                        const uint8_t *blk = src + (size_t)c * rb + ((size_t)g * (D / 32) + b) * ggml_block_bytes(T_Q4_0);
-                        memcpy(&scales[((size_t)g * n_cells + c) * (D / 32) + b], blk, 2);
-                        memcpy(&codes[((size_t)g * n_cells + c) * (D / 2) + (size_t)b * 16], blk + 2, 16);
-                    }
-        }
-    };
+    if ((D != 64 && D != 128) || G < 1 || H < 1 || H % G || T < 1 || n_cells < 1) { fail("unsupported head geometry"); return MI355_ERR_ARG; }
+    if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("bad cache type"); return MI355_ERR_ARG; }
+    if (!q || !k || !v || !cell_pos || !cell_seq || !q_pos || !q_seq || !out) { fail("flash_attn: null argument"); return MI355_ERR_ARG; }
+    if (n_kv < 1 || n_kv > n_cells) { fail("flash_attn: n_kv outside [1, n_cells]"); return MI355_ERR_ARG; }
+    for (int64_t t = 0; t < T; t++)
+        if (q_seq[t] < 0 || q_seq[t] > 63) { fail("flash_attn: q_seq[" + std::to_string(t) + "] outside [0, 63]"); return MI355_ERR_ARG; }
     std::vector<uint8_t> kc, vc;
     std::vector<uint16_t> ks, vs;
-    fill(type_k, k, kc, ks);
-    fill(type_v, v, vc, vs);
+    cache_planes_from_rows(type_k, k, G, D, n_cells, kc, ks);
+    cache_planes_from_rows(type_v, v, G, D, n_cells, vc, vs);
     DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dv(vc.size()), dvs(vs.size() * 2 + 16);
     DevBuf dq((size_t)T * H * D * 4), dout((size_t)T * H * D * 4), dcp((size_t)n_cells * 4), dcs((size_t)n_cells * 8), dtp((size_t)T * 4), dts((size_t)T * 4), dn(16);
-    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dq.up(q, (size_t)T * H * D * 4)) return MI355_ERR_OOM;
+    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dq.up(q, (size_t)T * H * D * 4) || !dout.p || !dks.p || !dvs.p) return MI355_ERR_OOM;
     if (!ks.empty()) dks.up(ks.data(), ks.size() * 2);
     if (!vs.empty()) dvs.up(vs.data(), vs.size() * 2);
-    std::vector<uint64_t> seqm((size_t)n_cells, 1ull);
-    std::vector<int32_t> tseq((size_t)T, 0);
-    int32_t nkv = n_cells;
-    dcp.up(cell_pos, (size_t)n_cells * 4); dcs.up(seqm.data(), (size_t)n_cells * 8); dtp.up(q_pos, (size_t)T * 4); dts.up(tseq.data(), (size_t)T * 4);
-    dn.up(&nkv, 4);
+    if (!dcp.up(cell_pos, (size_t)n_cells * 4) || !dcs.up(cell_seq, (size_t)n_cells * 8) || !dtp.up(q_pos, (size_t)T * 4) || !dts.up(q_seq, (size_t)T * 4) ||
+        !dn.up(&n_kv, 4)) return MI355_ERR_OOM;
     AttnArgs a{};
     a.q = dq.as<float>(); a.out = dout.as<float>();
     a.kv.k = dk.as<uint8_t>(); a.kv.kd = dks.as<uint16_t>(); a.kv.v = dv.as<uint8_t>(); a.kv.vd = dvs.as<uint16_t>();
@@ -1208,6 +1202,7 @@ int mi355_op_flash_attn(const float *q, int64_t T, int32_t H, int32_t G, int32_t
     a.splits = flash_attn_pick_splits((int)T, G, n_cells);
     a.pf_splits = flash_attn_prefill_splits((int)T, H, G, D, n_cells);
     DevBuf part(flash_attn_workspace_floats((int)T, H, D, std::max(a.splits, a.pf_splits)) * 4);
+    if (!part.p) return MI355_ERR_OOM;
     a.part = part.as<float>();
     hipError_t e = launch_flash_attn(a, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1215,15 +1210,42 @@ int mi355_op_flash_attn(const float *q, int64_t T, int32_t H, int32_t G, int32_t
     return dout.down(out, (size_t)T * H * D * 4) ? MI355_OK : MI355_ERR_HIP;
 }
 
+// ... with one sequence: every cell in sequence 0, every query of sequence 0, the whole table scanned
+int mi355_op_flash_attn(const float *q, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
+                        const void *v, int32_t n_cells, const int32_t *cell_pos, const int32_t *q_pos, float scale, float *out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (T < 1 || n_cells < 1) { fail("unsupported head geometry"); return MI355_ERR_ARG; }
+    std::vector<uint64_t> seqm((size_t)n_cells, 1ull);
+    std::vector<int32_t> tseq((size_t)T, 0);
+    return mi355_op_flash_attn_seq(q, T, H, G, D, type_k, k, type_v, v, n_cells, cell_pos, seqm.data(), q_pos, tseq.data(), n_cells, scale, out);
+}
+
+// How launch_flash_attn would split the keys of such a call: out[0] = flash_attn_pick_splits (the split kernel), out[1] = flash_attn_prefill_splits (the
+// matrix-core prompt kernel), out[2] = 1 where the prompt kernel takes the call (test entry: a test states which splits its case runs with through this)
+int mi355_op_flash_attn_plan(int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, int32_t type_v, int32_t n_cells, int32_t *out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if ((D != 64 && D != 128) || G < 1 || H < 1 || H % G || T < 1 || T > INT32_MAX || n_cells < 1 || !out) { fail("unsupported head geometry"); return MI355_ERR_ARG; }
+    AttnArgs a{};
+    a.type_k = type_k; a.type_v = type_v; a.T = (int)T; a.H = H; a.G = G; a.D = D; a.n_ctx = n_cells; a.n_kv_max = n_cells;
+    out[0] = flash_attn_pick_splits((int)T, G, n_cells);
+    out[1] = flash_attn_prefill_splits((int)T, H, G, D, n_cells);
+    out[2] = flash_attn_prefill_applicable(a) && !(fa_v_acc_f16_enabled() && type_k == T_F16 && type_v == T_F16) ? 1 : 0;
+    return MI355_OK;
+}
+
 // The attention block of ONE single-token step exactly as the decode path launches it (test entry): rope of q
 // and of the token's K row, the K / V row quantised into the cache, attention over the visible cells, merge of the chunk partials, Q8_K quantisation and the
 // attn_output mat-vec with its residual.  fused = 1: attn_out.hip (one launch); 0: the single-launch decode attention + the weight-stream mat-vec.
 // k / v: the cache BEFORE the step as ggml-layout rows [n_cells][G * D] (the row at tok_cell is overwritten); cell_pos[tok_cell] must already be tok_pos.
-int mi355_op_attn_step(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
-                       const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos, int32_t tok_cell, float rope_base, int32_t n_rot, float scale,
-                       int32_t type_o, const void *W_o, int64_t E, const float *resid, int32_t fused, float *att_out, float *out, void *k_row_out, void *v_row_out) {
+// cell_seq (null: every cell in sequence 0 only) / tok_seq: the cells' sequence bit masks and the token's sequence, so that the cache may hold other sequences'
+// cells; use_lists: the launch walks the token's chunk list (host/attn_chunks.h) as a step of a context with several sequences does.
+int mi355_op_attn_step_seq(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
+                           const void *v, int32_t n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, int32_t tok_pos, int32_t tok_seq, int32_t tok_cell,
+                           int32_t use_lists, float rope_base, int32_t n_rot, float scale, int32_t type_o, const void *W_o, int64_t E, const float *resid,
+                           int32_t fused, float *att_out, float *out, void *k_row_out, void *v_row_out) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     if ((D != 64 && D != 128) || G < 1 || H % G || n_cells < 1 || tok_cell < 0 || tok_cell >= n_cells) { fail("bad geometry"); return MI355_ERR_ARG; }
+    if (tok_seq < 0 || tok_seq > 63) { fail("tok_seq outside [0, 63]"); return MI355_ERR_ARG; }
     const int64_t K = (int64_t)H * D;
     const size_t kv_dim = (size_t)G * D;
     auto fill = [&](int type, const void *rows, std::vector<uint8_t> &codes, std::vector<uint16_t> &scales) { cache_planes_from_rows(type, rows, G, D, n_cells, codes, scales); };
@@ -1243,8 +1265,11 @@ int mi355_op_attn_step(const float *q, const float *k_new, const float *v_new, i
     if (!ks.empty()) dks.up(ks.data(), ks.size() * 2);
     if (!vs.empty()) dvs.up(vs.data(), vs.size() * 2);
     std::vector<uint64_t> seqm((size_t)n_cells, 1ull);
-    const int32_t tseq = 0, nkv = n_cells;
+    if (cell_seq) seqm.assign(cell_seq, cell_seq + n_cells);
+    const int32_t tseq = tok_seq, nkv = n_cells;
     const unsigned one = 1u;
+    ChunkLists cl;
+    if (use_lists && !cl.make(n_cells, n_cells, cell_pos, seqm.data(), &tseq, 1)) return MI355_ERR_OOM;
     dcp.up(cell_pos, (size_t)n_cells * 4); dcs.up(seqm.data(), (size_t)n_cells * 8); dtp.up(&tok_pos, 4); dts.up(&tseq, 4); dn.up(&nkv, 4); dcell.up(&tok_cell, 4);
     dserial.up(&one, 4);
     hipError_t e = launch_repack_rows(type_o, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, E, nullptr);
@@ -1264,6 +1289,7 @@ int mi355_op_attn_step(const float *q, const float *k_new, const float *v_new, i
     so.W = wdev.as<uint8_t>(); so.out = dout.as<float>(); so.resid = dres.as<float>(); so.type = type_o; so.n_rows = (int)E; so.ld_out = (int)E; so.row_bytes = drow;
     if (fused) {
         a.splits = attn_out_fused_splits(a);
+        if (use_lists) cl.apply(a);
         DevBuf part(flash_attn_workspace_floats(1, H, D, a.splits) * 4);
         a.part = part.as<float>();
         if (!attn_out_fused_applicable(a, ra, so, (int)K, EPI_ADD)) { fail("attn_out.hip has no form for this shape"); return MI355_ERR_ARG; }
@@ -1275,6 +1301,7 @@ int mi355_op_attn_step(const float *q, const float *k_new, const float *v_new, i
         if (e != hipSuccess) return hip_fail(e, "attn_out_fused");
     } else {
         a.splits = flash_attn_decode_splits(n_cells);
+        if (use_lists) cl.apply(a);
         DevBuf part(flash_attn_workspace_floats(1, H, D, a.splits) * 4);
         a.part = part.as<float>();
         if (!flash_attn_decode_fused_applicable(a, ra)) { fail("the single-launch decode attention has no form for this shape"); return MI355_ERR_ARG; }
@@ -1295,16 +1322,26 @@ int mi355_op_attn_step(const float *q, const float *k_new, const float *v_new, i
     return MI355_OK;
 }
 
+int mi355_op_attn_step(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
+                       const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos, int32_t tok_cell, float rope_base, int32_t n_rot, float scale,
+                       int32_t type_o, const void *W_o, int64_t E, const float *resid, int32_t fused, float *att_out, float *out, void *k_row_out, void *v_row_out) {
+    return mi355_op_attn_step_seq(q, k_new, v_new, H, G, D, type_k, k, type_v, v, n_cells, cell_pos, nullptr, tok_pos, 0, tok_cell, 0, rope_base, n_rot, scale, type_o,
+                                  W_o, E, resid, fused, att_out, out, k_row_out, v_row_out);
+}
+
 // The decode attention of ONE token of a qwen2 / qwen3 file as the decode path launches it (test entry): NEOX rope of q and of the token's K row - each head
 // RMS-normalised and multiplied by q_norm / k_norm first where they are given (qwen3; null: no norm, the qwen2 path) - the K / V row quantised into the cache,
 // attention over the visible cells and the merge of the chunk partials.  mode 1: the single-launch form of a single-token step (tickets, the last workgroup
 // merges); 0: the store-fused form of a batched step (K / V stored inside the attention launch, merged by its own launch); 2: the generic path of prompt
 // batches (rope_kv_store, then the split attention on the rotated q).  Cache arguments and outputs as mi355_op_attn_step.
-int mi355_op_attn_decode_neox(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
-                              const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos, int32_t tok_cell, float rope_base, float scale,
-                              const float *q_norm, const float *k_norm, float eps, int32_t mode, float *att_out, void *k_row_out, void *v_row_out) {
+// cell_seq (null: every cell in sequence 0 only), tok_seq, use_lists (modes 0 and 1 only): as mi355_op_attn_step_seq.
+int mi355_op_attn_decode_neox_seq(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
+                                  const void *v, int32_t n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, int32_t tok_pos, int32_t tok_seq, int32_t tok_cell,
+                                  int32_t use_lists, float rope_base, float scale, const float *q_norm, const float *k_norm, float eps, int32_t mode, float *att_out,
+                                  void *k_row_out, void *v_row_out) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     if ((D != 64 && D != 128) || G < 1 || H % G || n_cells < 1 || tok_cell < 0 || tok_cell >= n_cells || mode < 0 || mode > 2) { fail("bad geometry / mode"); return MI355_ERR_ARG; }
+    if (tok_seq < 0 || tok_seq > 63 || (use_lists && mode == 2)) { fail("tok_seq outside [0, 63], or chunk lists asked of the generic path"); return MI355_ERR_ARG; }
     if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("bad cache type"); return MI355_ERR_ARG; }
     const size_t K = (size_t)H * D, kv_dim = (size_t)G * D;
     std::vector<uint8_t> kc, vc;
@@ -1319,7 +1356,10 @@ int mi355_op_attn_decode_neox(const float *q, const float *k_new, const float *v
     if (!ks.empty()) dks.up(ks.data(), ks.size() * 2);
     if (!vs.empty()) dvs.up(vs.data(), vs.size() * 2);
     std::vector<uint64_t> seqm((size_t)n_cells, 1ull);
-    const int32_t tseq = 0, nkv = n_cells;
+    if (cell_seq) seqm.assign(cell_seq, cell_seq + n_cells);
+    const int32_t tseq = tok_seq, nkv = n_cells;
+    ChunkLists cl;
+    if (use_lists && !cl.make(n_cells, n_cells, cell_pos, seqm.data(), &tseq, 1)) return MI355_ERR_OOM;
     dcp.up(cell_pos, (size_t)n_cells * 4); dcs.up(seqm.data(), (size_t)n_cells * 8); dtp.up(&tok_pos, 4); dts.up(&tseq, 4); dn.up(&nkv, 4); dcell.up(&tok_cell, 4);
     RopeArgs ra{};
     ra.n_rot = D; ra.freq_base = rope_base; ra.freq_scale = 1.0f; ra.freq_factors = nullptr; ra.neox = 1;
@@ -1345,6 +1385,7 @@ int mi355_op_attn_decode_neox(const float *q, const float *k_new, const float *v
         if (e != hipSuccess) return hip_fail(e, "flash_attn");
     } else {
         a.splits = flash_attn_decode_splits(n_cells);
+        if (use_lists) cl.apply(a);
         DevBuf part(flash_attn_workspace_floats(1, H, D, a.splits) * 4);
         a.part = part.as<float>();
         if (!flash_attn_decode_applicable(a, ra) || (mode == 1 && !flash_attn_decode_fused_applicable(a, ra))) { fail("the decode attention has no form for this shape"); return MI355_ERR_ARG; }
@@ -1356,6 +1397,13 @@ int mi355_op_attn_decode_neox(const float *q, const float *k_new, const float *v
     if (att_out && !datt.down(att_out, K * 4)) return MI355_ERR_HIP;
     if (!cache_row_to_ggml(type_k, dk, dks, G, D, n_cells, tok_cell, k_row_out) || !cache_row_to_ggml(type_v, dv, dvs, G, D, n_cells, tok_cell, v_row_out)) return MI355_ERR_HIP;
     return MI355_OK;
+}
+
+int mi355_op_attn_decode_neox(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
+                              const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos, int32_t tok_cell, float rope_base, float scale,
+                              const float *q_norm, const float *k_norm, float eps, int32_t mode, float *att_out, void *k_row_out, void *v_row_out) {
+    return mi355_op_attn_decode_neox_seq(q, k_new, v_new, H, G, D, type_k, k, type_v, v, n_cells, cell_pos, nullptr, tok_pos, 0, tok_cell, 0, rope_base, scale, q_norm,
+                                         k_norm, eps, mode, att_out, k_row_out, v_row_out);
 }
 
 // The K / V cache write of a batch on its own (test entry): the four launches that rotate K and write K / V rows into the cache,
@@ -1406,6 +1454,96 @@ int mi355_op_kv_store(int32_t form, float *q, const float *k, const float *v, in
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "kv_store");
     if (form != 3 && !dq.down(q, (size_t)T * q_dim * 4)) return MI355_ERR_HIP;
+    if (!cache_rows_from_planes(type_k, dk, dks, G, D, n_cells, k_cache) || !cache_rows_from_planes(type_v, dv, dvs, G, D, n_cells, v_cache)) return MI355_ERR_HIP;
+    return MI355_OK;
+}
+
+// The attention of ONE batched single-token step - T tokens, up to 64, as a continuous-batching step holds them - in each form Context::attn_core launches it
+// (test entry).  q [T][H * D] un-rotated, k_new / v_new [T][G * D]; k_cache / v_cache: the whole cache as ggml-layout rows [n_cells][G * D], in and out;
+// cell_pos / cell_seq [n_cells] with the new cells already set (cell_pos[tok_cell[t]] = tok_pos[t], bit tok_seq[t] of cell_seq[tok_cell[t]]); n_kv: cells to
+// scan (what the device reads), every launch is sized for n_cells.
+//   mode 0: K rope + K / V store inside the attention launch (launch_flash_attn_decode with the new rows), every chunk of the cache scanned;
+//   mode 1: the same launch on the per-token chunk lists of host/attn_chunks.h;
+//   mode 2: launch_kv_store_fast, then launch_flash_attn_decode without the store, on the lists;
+//   mode 3: the generic path, launch_rope_kv_store + launch_flash_attn.
+// att_out [T][H * D]; q8k_out (nullable; H * D a multiple of 256): the Q8_K blocks of the T rows that the merge wrote for attn_output, as ggml block_q8_K.
+// A shape or mode without a kernel is refused before anything is launched: more than 64 tokens, a token in several or in another token's sequence (modes 0
+// and 1: no token may read another's new cell), what flash_attn_decode_applicable (modes 0 - 2) or kv_store_fast_applicable (the lists, mode 2) reject.
+int mi355_op_attn_batch_step(const float *q, const float *k_new, const float *v_new, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, void *k_cache,
+                             int32_t type_v, void *v_cache, int32_t n_cells, int32_t n_kv, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *tok_pos,
+                             const int32_t *tok_seq, const int32_t *tok_cell, float rope_base, int32_t n_rot, int32_t neox, float scale, int32_t mode,
+                             float *att_out, void *q8k_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!q || !k_new || !v_new || !k_cache || !v_cache || !cell_pos || !cell_seq || !tok_pos || !tok_seq || !tok_cell || !att_out) { fail("attn_batch_step: null argument"); return MI355_ERR_ARG; }
+    if (mode < 0 || mode > 3) { fail("attn_batch_step: mode outside [0, 3]"); return MI355_ERR_ARG; }
+    if (T < 1 || T > 64) { fail("attn_batch_step: a batched step holds 1 .. 64 tokens"); return MI355_ERR_ARG; }
+    if ((D != 64 && D != 128) || G < 1 || H < 1 || H % G || H / G > 8 || n_cells < 1 || n_kv < 1 || n_kv > n_cells || n_rot < 2 || n_rot > D || n_rot % 2) { fail("attn_batch_step: bad geometry"); return MI355_ERR_ARG; }
+    if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("attn_batch_step: bad cache type"); return MI355_ERR_ARG; }
+    const size_t K = (size_t)H * D, kv_dim = (size_t)G * D;
+    if (q8k_out && K % 256) { fail("attn_batch_step: Q8_K rows need n_head * head_dim to be a multiple of 256"); return MI355_ERR_ARG; }
+    uint64_t seen = 0;
+    for (int64_t t = 0; t < T; t++) {
+        if (tok_seq[t] < 0 || tok_seq[t] > 63) { fail("attn_batch_step: tok_seq[" + std::to_string(t) + "] outside [0, 63]"); return MI355_ERR_ARG; }
+        if (tok_cell[t] < 0 || tok_cell[t] >= n_kv) { fail("attn_batch_step: tok_cell[" + std::to_string(t) + "] outside the scanned cells"); return MI355_ERR_ARG; }
+        const uint64_t bit = 1ull << tok_seq[t];
+        if (mode < 2 && ((seen & bit) || cell_seq[tok_cell[t]] != bit)) { fail("attn_batch_step: the store-fused launch needs every token in one sequence of its own"); return MI355_ERR_ARG; }
+        seen |= bit;
+    }
+    RopeArgs ra{};
+    ra.n_rot = n_rot; ra.freq_base = rope_base; ra.freq_scale = 1.0f; ra.freq_factors = nullptr; ra.neox = neox ? 1 : 0;
+    AttnArgs a{};
+    a.type_k = type_k; a.type_v = type_v; a.T = (int)T; a.H = H; a.G = G; a.D = D; a.n_ctx = n_cells; a.n_kv_max = n_cells; a.scale = scale;
+    if (mode < 3 && !flash_attn_decode_applicable(a, ra)) { fail("attn_batch_step: the decode attention has no form for this shape"); return MI355_ERR_ARG; }
+    if ((mode == 1 || mode == 2) && !kv_store_fast_applicable(G, D, type_k, type_v, ra)) { fail("attn_batch_step: the small-batch store has no form for these arguments (no chunk lists either)"); return MI355_ERR_ARG; }
+    if (mode == 3 && ((size_t)n_rot + kv_dim) * 4 > 48 * 1024) { fail("attn_batch_step: n_head_kv * head_dim too wide for the generic store's LDS"); return MI355_ERR_ARG; }
+    std::vector<uint8_t> kc, vc;
+    std::vector<uint16_t> ks, vs;
+    cache_planes_from_rows(type_k, k_cache, G, D, n_cells, kc, ks);
+    cache_planes_from_rows(type_v, v_cache, G, D, n_cells, vc, vs);
+    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dv(vc.size()), dvs(vs.size() * 2 + 16);
+    DevBuf dq((size_t)T * K * 4), dkn((size_t)T * kv_dim * 4), dvn((size_t)T * kv_dim * 4), datt((size_t)T * K * 4), dcp((size_t)n_cells * 4), dcs((size_t)n_cells * 8);
+    DevBuf dtp((size_t)T * 4), dts((size_t)T * 4), dcell((size_t)T * 4), dn(16), dcsb((size_t)T * n_rot * 4 + 64), dblk(q8k_out ? ggml_row_bytes(T_Q8_K, (int64_t)K) * T : 16);
+    ActBufs ab(q8k_out ? K : 256, (size_t)T + 1);
+    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dks.p || !dvs.p || !dq.up(q, (size_t)T * K * 4) || !dkn.up(k_new, (size_t)T * kv_dim * 4) ||
+        !dvn.up(v_new, (size_t)T * kv_dim * 4) || !datt.p || !dcp.up(cell_pos, (size_t)n_cells * 4) || !dcs.up(cell_seq, (size_t)n_cells * 8) ||
+        !dtp.up(tok_pos, (size_t)T * 4) || !dts.up(tok_seq, (size_t)T * 4) || !dcell.up(tok_cell, (size_t)T * 4) || !dn.up(&n_kv, 4) || !dcsb.p || !dblk.p || !ab.ok()) {
+        fail("device alloc/copy failed"); return MI355_ERR_OOM;
+    }
+    if (!ks.empty() && !dks.up(ks.data(), ks.size() * 2)) return MI355_ERR_OOM;
+    if (!vs.empty() && !dvs.up(vs.data(), vs.size() * 2)) return MI355_ERR_OOM;
+    ChunkLists cl;
+    if ((mode == 1 || mode == 2) && !cl.make(n_kv, n_cells, cell_pos, cell_seq, tok_seq, (int)T)) return MI355_ERR_OOM;
+    a.q = dq.as<float>(); a.out = datt.as<float>();
+    a.kv.k = dk.as<uint8_t>(); a.kv.kd = dks.as<uint16_t>(); a.kv.v = dv.as<uint8_t>(); a.kv.vd = dvs.as<uint16_t>();
+    a.cell_pos = dcp.as<int32_t>(); a.cell_seq = dcs.as<uint64_t>(); a.tok_pos = dtp.as<int32_t>(); a.tok_seq = dts.as<int32_t>(); a.n_kv_dev = dn.as<int32_t>();
+    if (q8k_out) { a.out_q = &ab.q; a.out_q8k = true; a.out_q80 = false; }
+    if (mode == 3) {
+        a.splits = flash_attn_pick_splits((int)T, G, n_cells);
+        a.pf_splits = flash_attn_prefill_splits((int)T, H, G, D, n_cells);
+    } else {
+        a.splits = flash_attn_decode_splits(n_cells);
+        if (mode != 0) cl.apply(a);
+    }
+    DevBuf part(flash_attn_workspace_floats((int)T, H, D, std::max(a.splits, a.pf_splits)) * 4);
+    if (!part.p) return MI355_ERR_OOM;
+    a.part = part.as<float>();
+    hipError_t e = launch_rope_table(dtp.as<int32_t>(), (int)T, ra, dcsb.as<float>(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "rope_table");
+    if (mode == 3) {
+        e = launch_rope_kv_store(dq.as<float>(), dkn.as<float>(), dvn.as<float>(), (int)T, H, G, D, dtp.as<int32_t>(), dcell.as<int32_t>(), ra, a.kv, type_k, type_v, n_cells,
+                                 dcsb.as<float>(), nullptr);
+        if (e == hipSuccess) e = launch_flash_attn(a, nullptr);
+    } else if (mode == 2) {
+        e = launch_kv_store_fast(dkn.as<float>(), dvn.as<float>(), (int)T, G, D, dcsb.as<float>(), ra, dcell.as<int32_t>(), a.kv, type_k, type_v, n_cells, nullptr);
+        if (e == hipSuccess) e = launch_flash_attn_decode(a, dcsb.as<float>(), ra, nullptr);
+    } else {
+        e = launch_flash_attn_decode(a, dcsb.as<float>(), ra, nullptr, dkn.as<float>(), dvn.as<float>(), dcell.as<int32_t>());
+    }
+    if (e == hipSuccess && q8k_out) e = launch_pack_q8k_blocks(ab.q, (int)K, (int)T, dblk.as<uint8_t>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "attn_batch_step");
+    if (!datt.down(att_out, (size_t)T * K * 4)) return MI355_ERR_HIP;
+    if (q8k_out && !dblk.down(q8k_out, ggml_row_bytes(T_Q8_K, (int64_t)K) * T)) return MI355_ERR_HIP;
     if (!cache_rows_from_planes(type_k, dk, dks, G, D, n_cells, k_cache) || !cache_rows_from_planes(type_v, dv, dvs, G, D, n_cells, v_cache)) return MI355_ERR_HIP;
     return MI355_OK;
 }

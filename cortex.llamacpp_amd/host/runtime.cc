@@ -5,6 +5,7 @@
 
 #include <dlfcn.h>
 #include "tp_comm.h"
+#include "attn_chunks.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1792,20 +1793,8 @@ int Context::decode_ubatch(int n, const int32_t *tokens, const int32_t *pos, con
         lists_usable = n <= 64 && flash_attn_decode_applicable(aa, ra) && kv_store_fast_applicable(aa.G, aa.D, cp.type_k, cp.type_v, ra);
     }
     if ((n >= 2 || cp.n_seq_max > 1) && lists_usable) {
-        const int nch = (n_kv_ + 63) / 64;
-        std::vector<uint64_t> seq_of_chunk((size_t)nch, 0ull);
-        for (int i = 0; i < n_kv_ && i < (int)cells_.size(); i++)
-            if (cells_[(size_t)i].pos >= 0) seq_of_chunk[(size_t)(i >> 6)] |= cells_[(size_t)i].seqs;
-        int32_t *cnt = h_chunks_ + (size_t)64 * chunk_stride_;
-        for (int t = 0; t < n; t++) {
-            int32_t *lst = h_chunks_ + (size_t)t * chunk_stride_;
-            int c = 0;
-            const uint64_t bit = 1ull << (seq[t] & 63);
-            for (int ch = 0; ch < nch; ch++) if (seq_of_chunk[(size_t)ch] & bit) lst[c++] = ch;
-            cnt[t] = c;
-            chunk_lmax_ = std::max(chunk_lmax_, c);
-        }
-        if (chunk_lmax_ < 1) chunk_lmax_ = 1;
+        chunk_lmax_ = build_attn_chunk_lists(n_kv_, (int)cells_.size(), [&](int i, int32_t &p, uint64_t &m) { p = cells_[(size_t)i].pos; m = cells_[(size_t)i].seqs; },
+                                             seq, n, chunk_stride_, h_chunks_, h_chunks_ + (size_t)64 * chunk_stride_);
         if (hipMemcpyAsync(d_chunks_, h_chunks_, (size_t)64 * (chunk_stride_ + 1) * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "chunk list upload failed"; return -1; }
     }
     // rocprofv3 --pmc does not keep copy-engine transfers ordered with the kernels it serialises (observed: kernels reading
@@ -1828,7 +1817,7 @@ int Context::decode_ubatch(int n, const int32_t *tokens, const int32_t *pos, con
         int bucket = std::min((int)cp.n_ctx, (n_kv_ + 255) & ~255);
         chunk_cap_ = 0;
         if (chunk_lmax_ > 0) {                                 // chunk lists: the grid is sized by the list length, in steps of 4
-            chunk_cap_ = std::min(chunk_stride_, (chunk_lmax_ + 3) & ~3);
+            chunk_cap_ = attn_chunk_grid(chunk_lmax_, chunk_stride_);
             bucket = -chunk_cap_;                              // separate key space from the cell-count buckets
         }
         auto git = graphs_.find(bucket);

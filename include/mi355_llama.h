@@ -330,6 +330,37 @@ MI355_API int mi355_op_kv_store(int32_t form, float *q, const float *k, const fl
                                 int32_t n_rot, int32_t neox, int32_t type_k, int32_t type_v, int32_t n_cells, const int32_t *tok_pos, const int32_t *tok_cell,
                                 float rope_base, float freq_scale, const float *freq_factors, const float *q_norm, const float *k_norm, float eps,
                                 void *k_cache, void *v_cache);
+/* The three attention entries above with more than one sequence in the cache (test entries).  cell_seq [n_cells]: the cells' sequence bit masks (uint64, bit s =
+ * sequence s); q_seq [T] / tok_seq: the query's sequence, 0 .. 63 (MI355_ERR_ARG outside).  A query sees cell c iff c < n_kv, cell_pos[c] >= 0, cell_pos[c] <=
+ * its position and bit q_seq of cell_seq[c] is set.  mi355_op_flash_attn_seq: n_kv (1 .. n_cells) is the cell count the kernels read from the device, while
+ * the grid, the splits and the workspace are sized for n_cells.  mi355_op_flash_attn is this call with masks of 1, sequence 0 and n_kv = n_cells.
+ * mi355_op_attn_step_seq / mi355_op_attn_decode_neox_seq: cell_seq may be NULL (every cell in sequence 0); use_lists != 0 gives the launch the token's
+ * chunk list - the 64-cell chunks that hold a cell of its sequence - as a context with several sequences does (not with mode 2 of the NEOX entry). */
+MI355_API int mi355_op_flash_attn_seq(const float *q, int64_t T, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t type_k, const void *k, int32_t type_v,
+                                      const void *v, int32_t n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *q_pos, const int32_t *q_seq,
+                                      int32_t n_kv, float scale, float *out);
+/* out[0]: the key splits the split kernel would run such a call with, out[1]: those of the matrix-core prompt kernel, out[2]: 1 where the prompt kernel takes it. */
+MI355_API int mi355_op_flash_attn_plan(int64_t T, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t type_k, int32_t type_v, int32_t n_cells, int32_t *out);
+MI355_API int mi355_op_attn_step_seq(const float *q, const float *k_new, const float *v_new, int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t type_k,
+                                     const void *k, int32_t type_v, const void *v, int32_t n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, int32_t tok_pos,
+                                     int32_t tok_seq, int32_t tok_cell, int32_t use_lists, float rope_base, int32_t n_rot, float scale, int32_t type_o, const void *W_o,
+                                     int64_t n_embd, const float *resid, int32_t fused, float *att_out, float *out, void *k_row_out, void *v_row_out);
+MI355_API int mi355_op_attn_decode_neox_seq(const float *q, const float *k_new, const float *v_new, int32_t n_head, int32_t n_head_kv, int32_t head_dim,
+                                            int32_t type_k, const void *k, int32_t type_v, const void *v, int32_t n_cells, const int32_t *cell_pos,
+                                            const uint64_t *cell_seq, int32_t tok_pos, int32_t tok_seq, int32_t tok_cell, int32_t use_lists, float rope_base,
+                                            float scale, const float *q_norm, const float *k_norm, float eps, int32_t mode, float *att_out, void *k_row_out,
+                                            void *v_row_out);
+/* The attention of ONE batched single-token step of T <= 64 tokens (test entry): q [T][n_head * head_dim] un-rotated, k_new / v_new [T][n_head_kv * head_dim];
+ * k_cache / v_cache: the whole cache as ggml-layout rows, read before and written back whole after the step; cell_pos / cell_seq with the new cells already
+ * set; n_kv: cells to scan (tok_cell < n_kv <= n_cells).  mode 0: K rope and the K / V store inside the attention launch, every chunk scanned; 1: the same on
+ * per-token chunk lists; 2: the small-batch store, then the attention without the store, on the lists; 3: the generic store + attention.  att_out [T][n_head *
+ * head_dim]; q8k_out (may be NULL): the ggml block_q8_K rows the merge wrote for attn_output.  MI355_ERR_ARG, and nothing launched, for a shape or mode
+ * without a kernel: T > 64, tokens that share a sequence or sit in several (modes 0 and 1), a cache type, head geometry or rope the decode attention (modes
+ * 0 - 2) or the small-batch store (modes 1 and 2) does not take. */
+MI355_API int mi355_op_attn_batch_step(const float *q, const float *k_new, const float *v_new, int64_t T, int32_t n_head, int32_t n_head_kv, int32_t head_dim,
+                                       int32_t type_k, void *k_cache, int32_t type_v, void *v_cache, int32_t n_cells, int32_t n_kv, const int32_t *cell_pos,
+                                       const uint64_t *cell_seq, const int32_t *tok_pos, const int32_t *tok_seq, const int32_t *tok_cell, float rope_base,
+                                       int32_t n_rot, int32_t neox, float scale, int32_t mode, float *att_out, void *q8k_out);
 /* The K-shift of llama_kv_cache_seq_add on its own (test entry): every row of k_cache (layout as above) whose delta[cell] != 0 is dequantised, rotated by
  * delta[cell] positions and quantised again, in one launch; rows with delta 0 are not touched.  The YaRN parameters as mi355_op_rope_yarn takes them. */
 MI355_API int mi355_op_k_shift(int32_t type_k, int32_t n_head_kv, int32_t head_dim, int32_t n_rot, int32_t neox, int32_t n_cells, const int32_t *delta,

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "../../cortex.llamacpp_amd/host/attn_chunks.h"
 #include "../../cortex.llamacpp_amd/host/engine.h"
 #include "../../cortex.llamacpp_amd/host/gguf.h"
 #include "../../cortex.llamacpp_amd/host/json.h"
@@ -1503,6 +1504,54 @@ static void test_plane_offsets() {
     CHECK(plane_off(T_Q5_1, nib32_p_d(T_Q5_1), 3) == 60 && plane_off(T_Q5_1, nib32_p_m(T_Q5_1), 3) == 66);
 }
 
+// host/attn_chunks.h: the per-token chunk lists of a batched step against a restatement that asks, per (token, chunk), whether any cell of the chunk is occupied
+// and carries the token's sequence bit.  Cell tables with holes, cells shared by two sequences, a sequence without a cell, sequence 63, cells past n_kv.
+static void test_attn_chunk_lists() {
+    std::mt19937_64 rng(20240611);
+    struct Tab { int n_cells, n_kv, n_have; };
+    const Tab tabs[] = {{1, 1, 1}, {63, 63, 63}, {64, 64, 64}, {65, 65, 65}, {200, 130, 200}, {384, 377, 384}, {384, 377, 300}, {1000, 999, 1000}, {4480, 4471, 4480}};
+    for (const Tab &tb : tabs) {
+        for (int variant = 0; variant < 4; variant++) {
+            std::vector<int32_t> pos((size_t)tb.n_cells, -1);
+            std::vector<uint64_t> seqs((size_t)tb.n_cells, 0ull);
+            const int ids[4] = {0, 1, 5, 63};                                      // sequence 7 never owns a cell
+            for (int i = 0; i < tb.n_cells; i++) {
+                const int region = variant == 0 ? (i * 3) / std::max(tb.n_cells, 1) : variant == 1 ? i % 3 : variant == 2 ? (i / 50) % 4 : (int)(rng() % 4);
+                seqs[(size_t)i] = 1ull << ids[region];
+                if (variant >= 1 && i < 40) seqs[(size_t)i] = (1ull << 0) | (1ull << 63);   // a shared prefix
+                pos[(size_t)i] = (int32_t)(rng() % 1000);
+                if (rng() % 10 == 0) pos[(size_t)i] = -1;                           // holes: their stale masks must not count
+                if (variant == 2 && (i / 64) % 2 == 1) pos[(size_t)i] = -1;         // whole chunks empty
+            }
+            const int32_t tok_seq[6] = {63, 0, 7, 5, 1, 0};
+            const int n_tok = 6, stride = (tb.n_cells + 63) / 64;
+            std::vector<int32_t> lists((size_t)64 * stride, -7), counts(64, -7);
+            const int lmax = build_attn_chunk_lists(tb.n_kv, tb.n_have, [&](int i, int32_t &p, uint64_t &m) { p = pos[(size_t)i]; m = seqs[(size_t)i]; }, tok_seq, n_tok,
+                                                    stride, lists.data(), counts.data());
+            int want_lmax = 0;
+            for (int t = 0; t < n_tok; t++) {
+                std::vector<int32_t> want;
+                for (int ch = 0; ch * 64 < tb.n_kv; ch++) {
+                    bool any = false;
+                    for (int i = ch * 64; i < std::min({ch * 64 + 64, tb.n_kv, tb.n_have}); i++)
+                        any = any || (pos[(size_t)i] >= 0 && ((seqs[(size_t)i] >> tok_seq[t]) & 1ull));
+                    if (any) want.push_back(ch);
+                }
+                CHECK(counts[(size_t)t] == (int)want.size());
+                for (size_t i = 0; i < want.size() && (int)i < counts[(size_t)t]; i++) CHECK(lists[(size_t)t * stride + i] == want[i]);
+                for (int i = (int)want.size(); i < stride; i++) CHECK(lists[(size_t)t * stride + i] == -7);   // nothing written past the list
+                want_lmax = std::max(want_lmax, (int)want.size());
+            }
+            CHECK(counts[2] == 0);                                                  // the sequence without a cell
+            for (int t = n_tok; t < 64; t++) CHECK(counts[(size_t)t] == -7);
+            CHECK(lmax == std::max(want_lmax, 1));
+            const int grid = attn_chunk_grid(lmax, stride);
+            CHECK(grid >= lmax && grid <= stride && (grid % 4 == 0 || grid == stride) && grid - lmax < 4);
+        }
+    }
+    CHECK(attn_chunk_grid(1, 70) == 4 && attn_chunk_grid(4, 70) == 4 && attn_chunk_grid(5, 70) == 8 && attn_chunk_grid(69, 70) == 70 && attn_chunk_grid(1, 2) == 2);
+}
+
 static const char *volatile g_stage = "start";
 
 int main(int argc, char **argv) {
@@ -1518,6 +1567,7 @@ int main(int argc, char **argv) {
     STAGE(test_json);
     STAGE(test_type_row_bytes_and_names);
     STAGE(test_plane_offsets);
+    STAGE(test_attn_chunk_lists);
     STAGE(test_vocab);
     STAGE(test_vocab_wordpiece);
     STAGE(test_sampler);
