@@ -87,6 +87,14 @@ SYMBOLS = {
     "mi355_set_embeddings": (None, [_vp, _i32]),
     "mi355_get_embeddings_ith": (C.POINTER(C.c_float), [_vp, _i32]),
     "mi355_synchronize": (None, [_vp]),
+    "mi355_adapter_lora_init": (_vp, [_vp, _cp]),
+    "mi355_adapter_lora_free": (None, [_vp]),
+    "mi355_adapter_lora_alpha": (_f32, [_vp]),
+    "mi355_adapter_lora_n_pairs": (_i32, [_vp]),
+    "mi355_set_adapter_lora": (_i32, [_vp, _vp, _f32]),
+    "mi355_rm_adapter_lora": (_i32, [_vp, _vp]),
+    "mi355_clear_adapter_lora": (None, [_vp]),
+    "mi355_op_lora_delta": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "mi355_kv_cache_clear": (None, [_vp]),
     "mi355_kv_cache_seq_rm": (_i32, [_vp, _i32, _i32, _i32]),
     "mi355_kv_cache_seq_cp": (None, [_vp, _i32, _i32, _i32, _i32]),
@@ -442,6 +450,24 @@ class Backend:
                                               _ptr(rep), _ptr(freq), _ptr(pres), _ptr(keys)), "op_topk_rows")
         toks, logits = self.topk_decode(keys)
         return toks, logits, keys
+
+    def lora_delta(self, segs, x: np.ndarray):
+        """The adapter kernels once (mi355_op_lora_delta): segs = 1 .. 3 of (A [r][K], B [N][r], scale, out [T][ld_out]) over the rows x [T][K]; A and B both
+        float32 or both float16.  Returns the new out arrays (copies): out[t][n] + scale * B[n] . (A x[t]) for n < N, the rest as it was."""
+        x = np.ascontiguousarray(x, np.float32)
+        T, K = x.shape
+        n = len(segs)
+        As = [np.ascontiguousarray(sg[0]) for sg in segs]
+        Bs = [np.ascontiguousarray(sg[1]) for sg in segs]
+        outs = [np.array(sg[3], np.float32, order="C", copy=True).reshape(T, -1) for sg in segs]
+        types = np.array([{np.dtype(np.float32): F32, np.dtype(np.float16): F16}.get(a.dtype, -1) for a in As], np.int32)
+        r = np.array([a.shape[0] if a.ndim == 2 else 0 for a in As], np.int32)
+        N = np.array([b.shape[0] for b in Bs], np.int64)
+        scale = np.array([sg[2] for sg in segs], np.float32)
+        ld = np.array([o.shape[1] for o in outs], np.int64)
+        pa = (C.c_void_p * n)(*[a.ctypes.data for a in As]); pb = (C.c_void_p * n)(*[b.ctypes.data for b in Bs]); po = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        self._chk(self.lib.mi355_op_lora_delta(n, _ptr(types), pa, pb, _ptr(r), _ptr(N), _ptr(scale), _ptr(x), K, T, _ptr(ld), po), "op_lora_delta")
+        return outs
 
     def moe_group(self, ids: np.ndarray, n_expert: int):
         """Grouping of the selections ids [T][k] by expert (mi355_op_moe_group): (meta [2 n_expert + 1], slot_of [T * k], tok_of [T * k])."""
@@ -826,6 +852,25 @@ class Model:
             self.h = None
 
 
+class LoraAdapter:
+    """A LoRA adapter GGUF file loaded onto a model (mi355_adapter_lora_init); set on a context with Context.set_adapter_lora."""
+
+    def __init__(self, model: Model, path: str):
+        self.lib = model.lib
+        self.model = model
+        self.h = self.lib.mi355_adapter_lora_init(model.h, path.encode())
+        if not self.h:
+            raise MI355Error(f"mi355_adapter_lora_init({path}) failed: {_err(self.lib)}")
+        self.alpha = float(self.lib.mi355_adapter_lora_alpha(self.h))
+        self.n_pairs = int(self.lib.mi355_adapter_lora_n_pairs(self.h))
+
+    def close(self):
+        """Free the device copy; no context may still have the adapter set."""
+        if self.h:
+            self.lib.mi355_adapter_lora_free(self.h)
+            self.h = None
+
+
 class Context:
     def __init__(self, model: Model, n_ctx: int = 512, n_batch: int = 2048, n_ubatch: int = 512, n_seq_max: int = 1,
                  type_k: int = F16, type_v: int = F16, flash_attn: bool = True, use_graphs: bool = True,
@@ -910,6 +955,17 @@ class Context:
         """Block until the logits row is host-visible (no numpy copy)."""
         if not self.lib.mi355_get_logits_ith(self.h, i):
             raise MI355Error(f"no logits for that batch row: {_err(self.lib)}")
+
+    def set_adapter_lora(self, adapter: LoraAdapter, scale: float = 1.0) -> None:
+        """llama_set_adapter_lora: apply the adapter from the next step on (set again: a new scale)."""
+        if self.lib.mi355_set_adapter_lora(self.h, adapter.h, float(scale)) != 0:
+            raise MI355Error(f"mi355_set_adapter_lora failed: {_err(self.lib)}")
+
+    def rm_adapter_lora(self, adapter: LoraAdapter) -> bool:
+        return self.lib.mi355_rm_adapter_lora(self.h, adapter.h) == 0
+
+    def clear_adapter_lora(self) -> None:
+        self.lib.mi355_clear_adapter_lora(self.h)
 
     def set_embeddings(self, on: bool = True) -> None:
         self.lib.mi355_set_embeddings(self.h, int(on))

@@ -38,6 +38,7 @@ struct mi355_engine {
     std::atomic<mi355_release_fn> release{nullptr};     // mi355_engine_set_release_callback
 };
 struct mi355_clip { ClipModel m; };
+struct mi355_adapter_lora { LoraAdapter *a; };
 struct mi355_context {
     Context *c;
     std::vector<const char *> prof_names;
@@ -268,6 +269,41 @@ int64_t mi355_debug_qkv_attn_plan(int32_t type_q, int32_t type_k, int32_t type_v
 void mi355_set_embeddings(mi355_context *ctx, int32_t enabled) { ctx->c->embeddings_enabled = enabled != 0 || ctx->c->model->hp.encoder; }
 float *mi355_get_embeddings_ith(mi355_context *ctx, int32_t i) { return ctx->c->embeddings_ith(i); }
 void mi355_synchronize(mi355_context *ctx) { ctx->c->synchronize(); }
+
+// ---- LoRA adapters (llama_adapter_lora_init / llama_set_adapter_lora and their kin)
+mi355_adapter_lora *mi355_adapter_lora_init(mi355_model *model, const char *path) {
+    if (!model || !path) { fail("null model or path"); return nullptr; }
+    MI355_GUARD(return nullptr,
+        std::string err;
+        int status = 0;
+        LoraAdapter *a = lora_load(model->m, path, err, status);
+        if (!a) { fail(err); return nullptr; }
+        mi355_adapter_lora *h = new (std::nothrow) mi355_adapter_lora;
+        if (!h) { lora_free(a); fail("out of host memory"); return nullptr; }
+        h->a = a;
+        return h;
+    )
+}
+void mi355_adapter_lora_free(mi355_adapter_lora *adapter) {
+    if (!adapter) return;
+    lora_free(adapter->a);
+    delete adapter;
+}
+float mi355_adapter_lora_alpha(const mi355_adapter_lora *adapter) { return adapter ? adapter->a->alpha : 0.0f; }
+int32_t mi355_adapter_lora_n_pairs(const mi355_adapter_lora *adapter) { return adapter ? (int32_t)adapter->a->pairs.size() : 0; }
+int32_t mi355_set_adapter_lora(mi355_context *ctx, mi355_adapter_lora *adapter, float scale) {
+    if (!ctx || !adapter) { fail("null context or adapter"); return MI355_ERR_ARG; }
+    MI355_GUARD(return MI355_ERR_ARG,
+        if (ctx->c->set_adapter_lora(adapter->a, scale) != 0) { fail(ctx->c->last_error); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
+int32_t mi355_rm_adapter_lora(mi355_context *ctx, mi355_adapter_lora *adapter) {
+    if (!ctx || !adapter) { fail("null context or adapter"); return MI355_ERR_ARG; }
+    if (ctx->c->rm_adapter_lora(adapter->a) != 0) { fail(ctx->c->last_error); return -1; }
+    return MI355_OK;
+}
+void mi355_clear_adapter_lora(mi355_context *ctx) { if (ctx) ctx->c->clear_adapter_lora(); }
 
 // ---- LLaVA image path (host/clip.h)
 mi355_clip *mi355_clip_model_load(const char *path, int32_t main_gpu) {
@@ -910,6 +946,41 @@ int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const int64_t *N,
     if (e != hipSuccess) return hip_fail(e, "mul_mat_bf16");
     for (int s = 0; s < n_out; s++)
         if (!dy[(size_t)s]->down(y[s], (size_t)N[s] * T * 4)) return MI355_ERR_HIP;
+    return MI355_OK;
+}
+
+// launch_lora_delta once: out[s][t][n] += scale[s] * B[s][n] . (A[s] x[t]) for n_seg segments over the rows x [T][K]; out[s] is [T][ld_out[s]], read and written
+// back whole (the columns beyond N[s] come back as they went in unless the kernel wrote there)
+int mi355_op_lora_delta(int32_t n_seg, const int32_t *type, const void *const *A, const void *const *B, const int32_t *r, const int64_t *N, const float *scale,
+                        const float *x, int64_t K, int64_t T, const int64_t *ld_out, float *const *out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (n_seg < 1 || n_seg > 3 || !type || !A || !B || !r || !N || !scale || !x || !ld_out || !out || K < 32 || K % 32 || K > (1 << 20) || T < 1 || T > 65536) { fail("bad args"); return MI355_ERR_ARG; }
+    for (int s = 0; s < n_seg; s++)
+        if ((type[s] != T_F32 && type[s] != T_F16) || r[s] < 1 || r[s] > LORA_MAX_R || N[s] < 1 || N[s] > (1 << 24) || ld_out[s] < N[s] || !A[s] || !B[s] || !out[s]) {
+            fail("bad segment (F32 / F16 pairs, rank 1 .. 512, ld_out >= N)");
+            return MI355_ERR_ARG;
+        }
+    std::vector<std::unique_ptr<DevBuf>> bufs;
+    auto dev = [&](const void *src, size_t bytes) -> void * {
+        bufs.emplace_back(new DevBuf(bytes));
+        return bufs.back()->up(src, bytes) ? bufs.back()->p : nullptr;
+    };
+    LoraSeg segs[3];
+    float *xd = (float *)dev(x, (size_t)T * K * 4);
+    bool ok = xd != nullptr;
+    for (int s = 0; s < n_seg && ok; s++) {
+        const size_t es = type[s] == T_F16 ? 2 : 4;
+        segs[s] = LoraSeg{dev(A[s], (size_t)r[s] * K * es), dev(B[s], (size_t)N[s] * r[s] * es), type[s], r[s], (int)N[s], scale[s],
+                          (float *)dev(out[s], (size_t)T * ld_out[s] * 4), (int)ld_out[s]};
+        ok = segs[s].A && segs[s].B && segs[s].out;
+    }
+    DevBuf scratch(lora_scratch_floats((int)T) * 4);
+    if (!ok || !scratch.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_lora_delta(segs, n_seg, xd, (int)K, (int)K, (int)T, scratch.as<float>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lora_delta");
+    for (int s = 0; s < n_seg; s++)
+        if (hipMemcpy(out[s], segs[s].out, (size_t)T * ld_out[s] * 4, hipMemcpyDeviceToHost) != hipSuccess) return MI355_ERR_HIP;
     return MI355_OK;
 }
 

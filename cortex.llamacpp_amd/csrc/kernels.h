@@ -281,6 +281,24 @@ bool mmbf16_applicable(int type, int n_rows, int K, int T, const void *W, const 
 hipError_t launch_mmbf16(const uint8_t *W, int n_rows, int K, const void *xb, int T, float *y, int ld_out, const float *resid, const float *bias, float scale, bool do_scale,
                          hipStream_t st);
 
+// ---------------------------------------------------------------- run-time LoRA adapters (lora.hip)
+// out[t][n] += scale * B[n] . (A x[t]) for up to three tensors over one activation (Q | K | V, gate | up): A [r][K] and B [N][r], both F32 or both F16
+// (ggml's CPU arithmetic: an F16 pair rounds x, and t = A x, to f16; every sum is f32).  x: f32 rows [T][ld_x], 16-byte aligned, K % 32 == 0, ld_x % 4 == 0.
+// T <= LORA_FUSED_MAX_T: one launch; more tokens: two launches with t in `scratch` (lora_scratch_floats(T) floats, the caller's).  The same call twice
+// gives the same bits; nothing outside out[t][0 .. N) is written.  hipErrorInvalidValue, and nothing launched, for arguments outside this.
+constexpr int LORA_MAX_R = 512, LORA_FUSED_MAX_T = 8;
+struct LoraSeg {
+    const void *A, *B;
+    int type;             // T_F32 or T_F16
+    int r, N;
+    float scale;
+    float *out;           // out[t * ld_out + n]
+    int ld_out;
+};
+size_t lora_scratch_floats(int T);
+bool lora_delta_args_ok(const LoraSeg *segs, int n_seg, const float *x, int ld_x, int K, int T);
+hipError_t launch_lora_delta(const LoraSeg *segs, int n_seg, const float *x, int ld_x, int K, int T, float *scratch, hipStream_t st);
+
 // MoE router: softmax over n_expert <= 256 logits per token, top-k (first index wins ties), weights renormalised; one wave per token
 // forced (nullable, tests): [T][k] expert ids to take instead of the k most probable (weights = this side's probabilities of them, renormalised)
 hipError_t launch_moe_route(const float *logits, int T, int n_expert, int k, int32_t *ids, float *w, hipStream_t st, const int32_t *forced = nullptr);

@@ -429,7 +429,7 @@ CONFIGS = {
     "tiny-w320": LlamaConfig("tiny-w320", 320, 2, 5, 1, 608, 512, 1e6, 1e-6, 1024, arch="qwen2", qkv_bias=True),
 }
 
-FTYPE_ID = {"f16": 1, "bf16": 32, "q4_0": 2, "q4_1": 3, "q5_0": 8, "q5_1": 9, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18, "mxfp4": 38, "mxfp4_moe": 38, "tq1_0": 36, "tq2_0": 37}
+FTYPE_ID = {"f32": 0, "f16": 1, "bf16": 32, "q4_0": 2, "q4_1": 3, "q5_0": 8, "q5_1": 9, "iq4_nl": 25, "iq4_xs": 30, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q2_k": 10, "q3_k_s": 11, "q3_k_m": 12, "q3_k_l": 13, "q4_k_s": 14, "q5_k_s": 16, "q6_k": 18, "mxfp4": 38, "mxfp4_moe": 38, "tq1_0": 36, "tq2_0": 37}
 
 
 def use_more_bits(i: int, n: int) -> bool:
@@ -462,6 +462,8 @@ def tensor_type(cfg: LlamaConfig, ftype: str, kind: str, il: int) -> int:
 
 def mix_tensor_type(cfg: LlamaConfig, ftype: str, kind: str, il: int) -> int:
     """ggml type of a 2-D weight per llama-quantize's `*_K_M` mix, before the row-length fallback."""
+    if ftype == "f32":                                       # LLAMA_FTYPE_ALL_F32
+        return F32
     if ftype == "f16":
         return F16
     if ftype == "bf16":                                      # LLAMA_FTYPE_MOSTLY_BF16: every 2-D weight
@@ -733,6 +735,47 @@ def write_synthetic_llama(path: str, cfg: LlamaConfig | str, ftype: str = "q4_k_
             return random_blocks(rng, t, n, gain / np.sqrt(fan_in))
 
         w.add_tensor(name, ne, t, gen)
+    return w.write(path)
+
+
+# ---------------------------------------------------------------- LoRA adapter files (convert_lora_to_gguf.py output)
+LORA_KINDS = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")
+
+
+def lora_pairs(cfg: LlamaConfig, rank: int, targets):
+    """[(base tensor name, K, N)] of an adapter on `targets`: kinds ("attn_q" ... "ffn_down": that tensor of every layer; "output": output.weight, the
+    embedding table's shape when the config ties them) or whole tensor names ("blk.1.attn_v.weight"), in the order given, layers innermost."""
+    shapes = {name: ne for name, ne, _, _ in model_tensors(cfg, "f16") if len(ne) >= 2}
+    shapes.setdefault("output.weight", shapes["token_embd.weight"])
+    out = []
+    for tgt in targets:
+        names = [f"blk.{il}.{tgt}.weight" for il in range(cfg.n_layer)] if tgt in LORA_KINDS else ["output.weight"] if tgt == "output" else [tgt]
+        for name in names:
+            out.append((name, shapes[name][0], shapes[name][1]))
+    return out
+
+
+def write_synthetic_lora(path: str, cfg: LlamaConfig | str, rank: int = 8, alpha: float = 16.0, targets=("attn_q", "attn_v"), dtype: str = "f16",
+                         seed: int = 0x10A, std: float = 0.05) -> int:
+    """Write a llama.cpp-shaped LoRA adapter for a synthetic base: general.type "adapter", adapter.type "lora", adapter.lora.alpha and, per target, the pair
+    <name>.lora_a (ne [K, rank], std 1 / sqrt(K)) and <name>.lora_b (ne [rank, N], std `std`), both `dtype` ("f16" / "f32").  With an activation of unit
+    scale the delta is about alpha / rank * std * sqrt(rank) of the base tensor's own product.  Returns the file size in bytes."""
+    if isinstance(cfg, str):
+        cfg = CONFIGS[cfg]
+    t = {"f16": F16, "f32": F32}[dtype]
+    w = GGUFWriter()
+    w.add("general.architecture", "str", cfg.arch)
+    w.add("general.type", "str", "adapter")
+    w.add("general.name", "str", cfg.name + " adapter (synthetic)")
+    w.add("adapter.type", "str", "lora")
+    w.add("adapter.lora.alpha", "f32", float(alpha))
+    for idx, (name, K, N) in enumerate(lora_pairs(cfg, rank, targets)):
+        for half, ne, sd in ((".lora_a", (K, rank), 1.0 / np.sqrt(K)), (".lora_b", (rank, N), std)):
+            def gen(idx=idx, half=half, ne=ne, sd=sd):
+                rng = np.random.default_rng([seed, idx, half == ".lora_b"])
+                return random_blocks(rng, t, int(np.prod(ne)), sd)
+
+            w.add_tensor(name + half, ne, t, gen)
     return w.write(path)
 
 

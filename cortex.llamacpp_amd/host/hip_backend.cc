@@ -168,6 +168,10 @@ int cache_type_from_str(const std::string &s) {   // llama_engine.cc:29-55 (IsVa
 
 std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, std::string &err) {
     // "split_mode": "row" - this process becomes rank 0 of a row split it forms itself (tp_split.cc); the shard it loads comes back through here without the key
+    // "lora": [path | {"path": ..., "scale": 1}] - adapters loaded onto the model and set on its context before the first step (what common_init_from_params does
+    // with params.lora_adapters).  The ranks of a row split hold slices of the base tensors: refused by name.
+    const Json &lora = body["lora"];
+    if (!lora.is_null() && tp_split_requested(body)) { err = "lora: adapters are not supported with \"split_mode\": \"row\" (load the model on one device)"; return nullptr; }
     if (tp_split_requested(body)) return make_split_backend(body, info, err);
     std::string path = body.value<std::string>("llama_model_path", "");
     if (path.empty()) path = body.value<std::string>("model_path", "");
@@ -231,6 +235,19 @@ std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, 
     cp.logits_to_host = body.value<bool>("logits_to_host", false);
     std::unique_ptr<Context> ctx(new Context(model.get(), cp));
     if (!ctx->init(err)) return nullptr;
+    if (!lora.is_null()) {
+        if (!lora.is_array()) { err = "lora: expected a list of adapter paths or {\"path\", \"scale\"} objects"; return nullptr; }
+        for (const Json &item : lora.items()) {
+            const std::string apath = item.is_string() ? item.as_string() : item["path"].str_or("");
+            if (apath.empty() || (!item.is_string() && !item.is_object())) { err = "lora: expected a list of adapter paths or {\"path\", \"scale\"} objects"; return nullptr; }
+            const float scale = item.is_object() ? item.value<float>("scale", 1.0f) : 1.0f;
+            std::string aerr;
+            LoraAdapter *ad = lora_load(model.get(), apath, aerr, status);      // (the model owns it from here on)
+            if (!ad) { err = "lora: " + apath + ": " + aerr; return nullptr; }
+            if (ctx->set_adapter_lora(ad, scale) != 0) { err = "lora: " + apath + ": " + ctx->last_error; return nullptr; }
+            log_line(LOG_INFO, "LoRA adapter %s: %d tensor pairs, alpha %g, scale %g", apath.c_str(), (int)ad->pairs.size(), (double)ad->alpha, (double)scale);
+        }
+    }
 
     info.vram = model->device_bytes + ctx->device_bytes;
     info.ram = model->host_bytes;

@@ -41,7 +41,54 @@ const std::string &last_error_string() { return g_err; }
 
 // ------------------------------------------------------------------------------------------ model
 Model::~Model() {
+    while (!adapters.empty()) lora_free(adapters.back());
     for (uint8_t *p : arenas) (void)hipFree(p);
+}
+
+// ---- LoRA adapters: the file is checked on the host (lora.cc), then every pair is copied to the device as the file holds it
+LoraAdapter *lora_load(Model *m, const std::string &path, std::string &err, int &status) {
+    status = 0;
+    GGUFFile f;
+    err = f.open(path);
+    if (!err.empty()) { status = err.rfind("cannot", 0) == 0 ? -101 : -102; return nullptr; }
+    LoraPlan plan;
+    if (!plan_lora(f, *m, plan, err, status)) return nullptr;
+    std::unique_ptr<LoraAdapter> a(new LoraAdapter());
+    a->model = m; a->path = path; a->alpha = plan.alpha;
+    a->index.assign((size_t)(m->hp.n_layer + 1) * LORA_N_TARGETS, -1);
+    size_t total = 0;
+    for (const LoraPairPlan &p : plan.pairs) total += ((p.a->bytes + 255) & ~(size_t)255) + ((p.b->bytes + 255) & ~(size_t)255);
+    if (hipSetDevice(m->device) != hipSuccess) { err = "hipSetDevice failed"; status = -100; return nullptr; }
+    if (hipMalloc(&a->arena, total) != hipSuccess) { err = "hipMalloc of " + std::to_string(total) + " adapter bytes failed"; status = -104; return nullptr; }
+    size_t off = 0;
+    for (const LoraPairPlan &p : plan.pairs) {
+        LoraPair d{p.layer, p.target, p.type, p.r, p.K, p.N, a->arena + off, nullptr};
+        off += (p.a->bytes + 255) & ~(size_t)255;
+        d.B = a->arena + off;
+        off += (p.b->bytes + 255) & ~(size_t)255;
+        if (hipMemcpy(const_cast<uint8_t *>(d.A), p.a->data, p.a->bytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(const_cast<uint8_t *>(d.B), p.b->data, p.b->bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            err = "upload of adapter pair " + p.base + " failed"; status = -105;
+            (void)hipFree(a->arena);
+            return nullptr;
+        }
+        a->index[(size_t)(p.layer + 1) * LORA_N_TARGETS + (size_t)p.target] = (int)a->pairs.size();
+        a->pairs.push_back(d);
+    }
+    a->device_bytes = total;
+    m->device_bytes += total;
+    m->adapters.push_back(a.get());
+    return a.release();
+}
+
+void lora_free(LoraAdapter *a) {
+    if (!a) return;
+    if (Model *m = a->model) {
+        m->adapters.erase(std::remove(m->adapters.begin(), m->adapters.end(), a), m->adapters.end());
+        m->device_bytes -= a->device_bytes;
+    }
+    if (a->arena) (void)hipFree(a->arena);
+    delete a;
 }
 
 // the rotary parameters every kernel that rotates takes (with_ff: the per-pair frequency factors of rope_freqs.weight, when the file has them)
@@ -468,6 +515,67 @@ bool Context::init(std::string &err) {
 }
 
 // ------------------------------------------------------------------------------------------ KV cells
+// ---- the active adapters.  A change of the set or of a scale changes what the captured steps would have to launch: the stream is drained and they are dropped.
+bool Context::lora_changed() {
+    (void)hipSetDevice(model->device);
+    (void)hipStreamSynchronize(stream_);
+    if (holds_fused_) fused_release();
+    for (auto &ge : graphs_) (void)hipGraphExecDestroy(ge.second);
+    graphs_.clear();
+    graph_exec_ = nullptr;
+    if (!lora_.empty() && !lora_t_ && lora_scratch_floats((int)cp.n_ubatch) > 0) {
+        lora_t_ = (float *)dalloc(lora_scratch_floats((int)cp.n_ubatch) * sizeof(float));
+        if (!lora_t_) { lora_.clear(); last_error = "out of device memory for the adapter scratch"; return false; }
+    }
+    return true;
+}
+
+int Context::set_adapter_lora(LoraAdapter *a, float scale) {
+    if (!a || a->model != model) { last_error = "the adapter was not loaded onto this context's model"; return -1; }
+    bool found = false;
+    for (ActiveLora &al : lora_) if (al.a == a) { al.scale = scale; found = true; }
+    if (!found) lora_.push_back({a, scale});
+    return lora_changed() ? 0 : -1;
+}
+
+int Context::rm_adapter_lora(LoraAdapter *a) {
+    for (size_t i = 0; i < lora_.size(); i++)
+        if (lora_[i].a == a) {
+            lora_.erase(lora_.begin() + (long)i);
+            (void)lora_changed();
+            return 0;
+        }
+    last_error = "the adapter is not set on this context";
+    return -1;
+}
+
+void Context::clear_adapter_lora() {
+    if (lora_.empty()) return;
+    lora_.clear();
+    (void)lora_changed();
+}
+
+bool Context::lora_on(int layer, int target) const {
+    for (const ActiveLora &al : lora_) if (al.a->find(layer, target)) return true;
+    return false;
+}
+
+hipError_t Context::lora_add(int layer, const int *targets, float *const *outs, const int *lds, int n, const float *x, int ld_x, int K, int T) {
+    bool any = false;
+    for (const ActiveLora &al : lora_) {
+        LoraSeg segs[3];
+        int ns = 0;
+        for (int i = 0; i < n && i < 3; i++)
+            if (const LoraPair *p = al.a->find(layer, targets[i]))
+                segs[ns++] = LoraSeg{p->A, p->B, p->type, p->r, (int)p->N, lora_scale(al.scale, al.a->alpha, p->r), outs[i], lds[i]};
+        if (ns == 0) continue;
+        HIP_TRY(launch_lora_delta(segs, ns, x, ld_x, K, T, lora_t_, stream_));
+        any = true;
+    }
+    if (any) prof_mark("lora");
+    return hipSuccess;
+}
+
 void Context::kv_clear() {
     for (auto &c : cells_) c = KVCell();
     head_ = 0;
@@ -1160,7 +1268,10 @@ Context::AttnPlan Context::plan_attn(int il, const Step &st) const {
     AttnPlan p{};
     p.ra = layer_rope(st.ra_step, L, hp.eps);   // (qwen3: with the layer's q / k norm weights; every kernel either applies them or refuses)
     p.qkv_float = !type_is_quant(L.wq.type) || !type_is_quant(L.wk.type) || !type_is_quant(L.wv.type);
-    p.qkv_prologue = !p.qkv_float && can_fuse(E, T);
+    // an adapter on attn_q / attn_k / attn_v: the norm runs as a launch of its own and leaves its f32 rows in xn_ for the deltas; one on attn_output: the
+    // projection runs as a launch of its own behind the attention, which leaves its f32 rows in att_
+    p.qkv_lora = lora_on(il, LORA_Q) || lora_on(il, LORA_K) || lora_on(il, LORA_V);
+    p.qkv_prologue = !p.qkv_float && can_fuse(E, T) && !p.qkv_lora;
     AttnArgs &aa = p.aa;
     aa = attn_args(il, T, st.n_kv_max, d_pos_);
     const bool o_q = type_is_quant(L.wo.type);
@@ -1183,7 +1294,7 @@ Context::AttnPlan Context::plan_attn(int il, const Step &st) const {
     p.ao_seg = make_seg(L.wo, st.out, E, st.resid, nullptr);
     p.ao_epi = st.resid ? EPI_ADD : EPI_STORE;
     p.af = aa;
-    if (p.decode_attn && p.fused_step && st.attn_mode == 2 && !st.engine && il < 255 && !attn_out_off_ && !attn_out_skip_step_ && !(st.tp && tp_uses_host())) {
+    if (p.decode_attn && p.fused_step && st.attn_mode == 2 && !st.engine && il < 255 && !attn_out_off_ && !attn_out_skip_step_ && !(st.tp && tp_uses_host()) && !lora_on(il, LORA_O)) {
         p.af.splits = attn_out_fused_splits(p.af);
         if (st.chunk_lists) p.af.splits = aa.splits;
         p.ao_form = attn_out_fused_applicable(p.af, p.ra, p.ao_seg, (int)L.wo.K, p.ao_epi);
@@ -1214,7 +1325,7 @@ hipError_t Context::attn_qkv(int il, const Step &st, const AttnPlan &p) {
         const bool need_k = (type_is_quant(L.wq.type) && !act_is_q80(L.wq.type)) || (type_is_quant(L.wk.type) && !act_is_q80(L.wk.type)) || (type_is_quant(L.wv.type) && !act_is_q80(L.wv.type));
         const bool need_0 = act_is_q80(L.wq.type) || act_is_q80(L.wk.type) || act_is_q80(L.wv.type);
         const bool pl = need_k && T >= 3;                      // the batched kernels will want the block-sum planes
-        HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.attn_norm.data, E, T, hp.eps, p.qkv_float ? xn_ : nullptr, &aq_e_, need_k, need_0, stream_,
+        HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.attn_norm.data, E, T, hp.eps, p.qkv_float || p.qkv_lora ? xn_ : nullptr, &aq_e_, need_k, need_0, stream_,
                                      pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
         prep_owner_ = nullptr;
         if (pl) prep_written(aq_e_, E, T);
@@ -1226,6 +1337,10 @@ hipError_t Context::attn_qkv(int il, const Step &st, const AttnPlan &p) {
     bool bias_done = false;                                      // (a bf16 layer adds the biases in its launch's epilogue: the same f32 add)
     HIP_TRY(linear_multi(ws, outs, 3, aq_e_, xn_, T, bias, &bias_done));
     pending_fuse_ = Fuse();
+    if (p.qkv_lora) {                                            // before the biases, the rope, the q / k norm and the KV store read q_, k_, v_
+        const int targets[3] = {LORA_Q, LORA_K, LORA_V}, lds[3] = {(int)L.wq.N, (int)L.wk.N, (int)L.wv.N};
+        HIP_TRY(lora_add(il, targets, outs, lds, 3, xn_, E, E, T));
+    }
     if (!bias_done && (bias[0] || bias[1] || bias[2]))          // qwen2-style attention biases: all T rows of the three projections in one launch
         HIP_TRY(launch_add_qkv_bias(q_, k_, v_, bias[0], bias[1], bias[2], hp.n_head * hp.head_dim, hp.n_head_kv * hp.head_dim, T, stream_));
     prof_mark("qkv");
@@ -1283,7 +1398,13 @@ hipError_t Context::attn_core(int il, const Step &st, const AttnPlan &p) {
 hipError_t Context::attn_output(int il, const Step &st, const AttnPlan &p) {
     const LayerWeights &L = model->layers[(size_t)il];
     if (p.ao_form) return hipSuccess;
-    return linear(L.wo, aq_o_, att_, (int)L.wo.K, st.T, st.out, model->hp.n_embd, st.resid, p.ao_epi);
+    HIP_TRY(linear(L.wo, aq_o_, att_, (int)L.wo.K, st.T, st.out, model->hp.n_embd, st.resid, p.ao_epi));
+    if (lora_on(il, LORA_O)) {                                   // onto the rows that already hold the residual
+        const int target = LORA_O, ld = model->hp.n_embd;
+        float *out = st.out;
+        HIP_TRY(lora_add(il, &target, &out, &ld, 1, att_, (int)L.wo.K, (int)L.wo.K, st.T));
+    }
+    return hipSuccess;
 }
 
 // "SwiGLU, then quantise for a quantised ffn_down", in one pass: aq_ff_ from gate | up's result.  combined: ffn_ already holds silu(gate) * up (the
@@ -1309,13 +1430,16 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
     const bool gq = type_is_quant(L.gate.type), uq = type_is_quant(L.up.type);
     const bool fk = (gq && !act_is_q80(L.gate.type)) || (uq && !act_is_q80(L.up.type));
     const bool f0 = act_is_q80(L.gate.type) || act_is_q80(L.up.type);
-    const bool fuse_ffn = gq && uq && L.gate.type == L.up.type && can_fuse(E, T);
+    // an adapter on ffn_gate / ffn_up: both projections store their rows (the last branch below), the deltas are added from xn_, then SwiGLU; one on ffn_down:
+    // ffn_ must hold silu(gate) * up in f32 - the same branch, without the quantising shortcut
+    const bool lora_gu = lora_on(il, LORA_GATE) || lora_on(il, LORA_UP), lora_any = lora_gu || lora_on(il, LORA_DOWN);
+    const bool fuse_ffn = gq && uq && L.gate.type == L.up.type && can_fuse(E, T) && !lora_any;
     Fuse fz;
     if (fuse_ffn) {
         fz.mode = 1; fz.x = x_; fz.w = (const float *)L.ffn_norm.data; fz.eps = hp.eps;
     } else {
         const bool pl = fk && T >= 3;
-        HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.ffn_norm.data, E, T, hp.eps, (!gq || !uq) ? xn_ : nullptr, &aq_e_, fk, f0, stream_,
+        HIP_TRY(launch_rmsnorm_quant(x_, (const float *)L.ffn_norm.data, E, T, hp.eps, (!gq || !uq || lora_gu) ? xn_ : nullptr, &aq_e_, fk, f0, stream_,
                                      pl ? mmq_bh_ : nullptr, pl ? mmq_bl_ : nullptr));
         prep_owner_ = nullptr;
         if (pl) prep_written(aq_e_, E, T);
@@ -1328,7 +1452,18 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
                          (planes_small(L.gate, E, T) && planes_small(L.up, E, T)) || (q80_copy(L.gate, E, T) && q80_copy(L.up, E, T));
     const bool ffn_ks = mmq_ksplit_preferred(L.gate.type, (int)L.gate.N, E, T, L.gate.planes != nullptr, true) &&
                         mmq_ksplit_preferred(L.up.type, (int)L.up.N, E, T, L.up.planes != nullptr, true) && !fuse_ffn;
-    if (gq && uq && L.gate.type == L.up.type && !ffn_mmq) {
+    if (lora_any) {
+        HIP_TRY(linear(L.gate, aq_e_, xn_, E, T, ffn_, FF, nullptr, EPI_STORE));
+        HIP_TRY(linear(L.up, aq_e_, xn_, E, T, ffn_u_, FF, nullptr, EPI_STORE));
+        if (lora_gu) {
+            const int targets[2] = {LORA_GATE, LORA_UP}, lds[2] = {FF, FF};
+            float *outs[2] = {ffn_, ffn_u_};
+            HIP_TRY(lora_add(il, targets, outs, lds, 2, xn_, E, E, T));
+        }
+        quantised = T > 1 && down_q && !lora_on(il, LORA_DOWN);
+        if (quantised) HIP_TRY(quantise_for_down(il, T, false, false));
+        else HIP_TRY(launch_swiglu(ffn_, ffn_u_, ffn_, (int64_t)T * FF, stream_));
+    } else if (gq && uq && L.gate.type == L.up.type && !ffn_mmq) {
         MMVQSeg segs[2] = {make_seg(L.gate, ffn_, FF, nullptr, nullptr), make_seg(L.up, ffn_u_, FF, nullptr, nullptr)};
         HIP_TRY(mmvq_tokens(segs, 2, E, T, EPI_SWIGLU, aq_e_, stream_, fz));
     } else if (L.gate.type == T_BF16 && L.up.type == T_BF16 && L.gate.N == L.up.N) {
@@ -1377,7 +1512,8 @@ hipError_t Context::ffn_down(int il, const Step &st, bool quantised, int *n_matv
     // quantise inside the down-projection's prologue (once per CU, overlapped with its first weight loads)
     // (the widths listed are the ones the register-ring and weight-stream kernels take; the generic mat-vec's fused prologue would refuse others)
     // (... and an n_ff that ends inside a 256-group: the generic mat-vec's prologue, Q8_0 activations)
-    const bool fuse_down = st.fuse_down_env && T == 1 && type_is_quant(L.down.type) &&
+    const bool lora_down = lora_on(il, LORA_DOWN);               // ffn_ holds f32 rows: the projection quantises them in a launch of its own, the delta is added behind it
+    const bool fuse_down = !lora_down && st.fuse_down_env && T == 1 && type_is_quant(L.down.type) &&
                            (((FF % 256) == 0 && mmvq_fast_kb_ok((FF + 2047) / 2048)) || ((FF % 256) != 0 && (FF % 32) == 0 && FF <= 8192 && act_is_q80(L.down.type)));
     if (fuse_down && !st.tp && L.down_lo.valid() && L.down_hi.valid()) {
         // the column halves of ffn_down, each quantising its half of the SwiGLU output in its prologue: x += W_lo a_lo; x += W_hi a_hi
@@ -1400,6 +1536,11 @@ hipError_t Context::ffn_down(int il, const Step &st, bool quantised, int *n_matv
     }
     HIP_TRY(linear(L.down, aq_ff_, ffn_, FF, T, st.out, E, st.resid, epi));
     pending_fuse_ = Fuse();
+    if (lora_down) {
+        const int target = LORA_DOWN;
+        float *out = st.out;
+        HIP_TRY(lora_add(il, &target, &out, &E, 1, ffn_, FF, FF, T));
+    }
     return hipSuccess;
 }
 
@@ -1624,7 +1765,7 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
     att_splits_ = flash_attn_pick_splits(T, hp.n_head_kv, st.n_kv_max);
 
     // single-token step on a dense K-quant model: all layers in one launch (decode_mega.hip)
-    bool mega = T == 1 && !profile_ && !debug_taps_ && !ub_embd_ && mega_prepare();
+    bool mega = T == 1 && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && mega_prepare();
     AttnArgs ma{};
     if (mega) {
         ma = attn_args(0, 1, st.n_kv_max, d_pos_);             // (the kernel takes each layer's cache from its own descriptor)
@@ -1634,7 +1775,7 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
         mega = flash_attn_decode_fused_applicable(ma, st.ra_step);      // (more than 64 chunks: the per-launch path merges them)
     }
     // ... or one persistent launch per layer for the mat-vecs between two attention calls (decode_engine.hip)
-    st.engine = T == 1 && !mega && !profile_ && !debug_taps_ && !ub_embd_ && engine_prepare();
+    st.engine = T == 1 && !mega && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && engine_prepare();
     last_layers_engine_ = st.engine;
     // cos / sin table, cell metadata and the tokens' embedding rows: one launch
     HIP_TRY(launch_step_setup_embed(d_pos_, T, st.ra_step, rope_cs_, d_cell_pos_, d_cell_seq_, d_cell_, d_seqmask_, mega ? d_mega_sync_ : nullptr,
@@ -1688,15 +1829,16 @@ hipError_t Context::run_output(int n_out, int out_base) {
         return hipSuccess;
     }
     const bool oq = type_is_quant(model->output.type);
+    const bool lora_head = lora_on(-1, LORA_OUTPUT);             // the norm as a launch of its own, its f32 rows in xn_; the delta is added onto the device row
     // a single-token step whose logits row is wanted on the host: the head's launch stores it into the pinned row itself (the row crosses PCIe under the
     // launch; a copy node behind it cost 9 - 12 us of every step, tools/host_gap.py)
     static const bool zc_env = !(getenv("MI355_LOGITS_ZERO_COPY") && getenv("MI355_LOGITS_ZERO_COPY")[0] == '0');
-    logits_on_host_ = zc_env && oq && cur_T_ == 1 && n_out == 1 && cp.logits_to_host && !hp.tp_exchange && h_logits_ != nullptr;
-    if (oq && can_fuse(E, n_out)) {
+    logits_on_host_ = zc_env && oq && cur_T_ == 1 && n_out == 1 && cp.logits_to_host && !hp.tp_exchange && h_logits_ != nullptr && !lora_head;
+    if (oq && can_fuse(E, n_out) && !lora_head) {
         pending_fuse_.mode = 1; pending_fuse_.x = xo; pending_fuse_.w = (const float *)model->out_norm.data; pending_fuse_.eps = hp.eps;
     } else {
         prep_owner_ = nullptr;
-        HIP_TRY(launch_rmsnorm_quant(xo, (const float *)model->out_norm.data, E, n_out, hp.eps, oq ? nullptr : xn_, &aq_e_,
+        HIP_TRY(launch_rmsnorm_quant(xo, (const float *)model->out_norm.data, E, n_out, hp.eps, oq && !lora_head ? nullptr : xn_, &aq_e_,
                                      oq && !act_is_q80(model->output.type), act_is_q80(model->output.type), stream_));
         prof_mark("norm_quant");
     }
@@ -1723,6 +1865,10 @@ hipError_t Context::run_output(int n_out, int out_base) {
     } else {
         if (logits_on_host_) pending_fuse_.out_host = h_logits_ + (size_t)out_base * V;
         HIP_TRY(linear(model->output, aq_e_, xn_, E, n_out, lg, V, nullptr, EPI_STORE));
+        if (lora_head) {
+            const int target = LORA_OUTPUT;
+            HIP_TRY(lora_add(-1, &target, &lg, &V, 1, xn_, E, E, n_out));
+        }
     }
     pending_fuse_ = Fuse();
     prof_mark("lm_head");

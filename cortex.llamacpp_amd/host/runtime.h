@@ -15,13 +15,16 @@
 
 #include "../csrc/kernels.h"
 #include "gguf.h"
+#include "lora.h"
 #include "model_plan.h"
 
 namespace mi355 {
 
 // the model as its file describes it (ModelLayout: hyper-parameters and tensors, model_plan.h) plus what holding it on a device adds
+struct LoraAdapter;
 struct Model : ModelLayout {
     std::unique_ptr<GGUFFile> file;
+    std::vector<LoraAdapter *> adapters;   // loaded onto this model (lora_load); their device bytes are part of device_bytes; freed with the model at the latest
     std::string path, desc;
     int device = 0;
     std::vector<uint8_t *> arenas;      // hipMalloc'd blocks
@@ -35,6 +38,25 @@ struct Model : ModelLayout {
 // tp_size > 1: load rank tp_rank's slice of every projection (rows of attn_q/k/v, ffn_gate/up and output; the matching
 // super-block columns of attn_output and ffn_down), cut on head and 256-element boundaries
 Model *model_load(const std::string &path, int main_gpu, std::string &err, int &status, int prefill_planes = -1, int tp_rank = 0, int tp_size = 1);
+
+// A LoRA adapter file loaded onto a model (llama_adapter_lora_init): every pair checked by plan_lora (lora.h) and copied to the device in the file's type,
+// lora_a as r rows of K, lora_b as N rows of r.  The model owns it; a context holds the active set and the scales (Context::set_adapter_lora).
+struct LoraPair { int layer, target, type, r; int64_t K, N; const uint8_t *A, *B; };
+struct LoraAdapter {
+    Model *model = nullptr;
+    std::string path;
+    float alpha = 0.0f;
+    std::vector<LoraPair> pairs;
+    std::vector<int> index;                // [(layer + 1) * LORA_N_TARGETS + target] -> pair or -1 (layer -1: output.weight)
+    uint8_t *arena = nullptr;
+    uint64_t device_bytes = 0;
+    const LoraPair *find(int layer, int target) const {
+        const size_t i = (size_t)(layer + 1) * LORA_N_TARGETS + (size_t)target;
+        return i < index.size() && index[i] >= 0 ? &pairs[(size_t)index[i]] : nullptr;
+    }
+};
+LoraAdapter *lora_load(Model *m, const std::string &path, std::string &err, int &status);
+void lora_free(LoraAdapter *a);            // (no context may still have it set)
 
 struct KVCell {
     int32_t pos = -1;
@@ -94,6 +116,12 @@ class Context {
     int topk_rows(int n, const int *is, const int *ks, const TopkAdj *adjs, int32_t *toks, float *logits);   // n rows at once; outputs [n][TOPK_MAX_K]
     void synchronize();
 
+    // llama_set_adapter_lora / llama_rm_adapter_lora / llama_clear_adapter_lora: the adapters this context's steps apply, in the order they were first set
+    // (setting one again changes its scale).  Every change drains the stream and drops the captured steps.  0, or -1 with last_error set.
+    int set_adapter_lora(LoraAdapter *a, float scale);
+    int rm_adapter_lora(LoraAdapter *a);
+    void clear_adapter_lora();
+
     void kv_clear();
     bool kv_seq_rm(int seq, int p0, int p1);
     void kv_seq_cp(int src, int dst, int p0, int p1);
@@ -146,6 +174,7 @@ class Context {
         bool o_planes;                 // the attention writes the block-sum planes of its quantised output too
         bool decode_attn, fused_step;  // the decode attention kernel; its one-launch single-token form
         bool ao_form, qkv_in_attn;     // attn_output inside the attention launch; Q | K | V too
+        bool qkv_lora;                 // an active adapter has a pair on attn_q, attn_k or attn_v: the deltas are added from xn_ behind the projections
     };
     Step step_constants(int T, int n_kv_cap) const;
     AttnArgs attn_args(int il, int T, int n_kv_max, const int32_t *tok_pos) const;
@@ -174,6 +203,14 @@ class Context {
     hipError_t linear_multi(const DevTensor *const *ws, float *const *outs, int n, const ActQuant &aq, const float *x_f32, int T, const float *const *bias = nullptr,
                             bool *bias_done = nullptr);
     hipError_t linear_bf16(const DevTensor *const *ws, float *const *outs, const float *const *bias, int n, int K, int T, int ld_out, const float *resid, int epi);
+    // active adapters (set_adapter_lora): a block with an adapted tensor takes its unfused branch and adds the deltas from its f32 operand
+    struct ActiveLora { LoraAdapter *a; float scale; };
+    std::vector<ActiveLora> lora_;
+    float *lora_t_ = nullptr;          // t = A x of a prompt micro-batch (kernels.h lora_scratch_floats(n_ubatch))
+    bool lora_on(int layer, int target) const;
+    bool lora_changed();
+    // outs[i] (leading dimension lds[i]) += the deltas of (layer, targets[i]) from the rows x [T][ld_x], adapter by adapter in the order they were set
+    hipError_t lora_add(int layer, const int *targets, float *const *outs, const int *lds, int n, const float *x, int ld_x, int K, int T);
     void prof_mark(const char *name);
     void prof_begin();
     void prof_end();

@@ -181,6 +181,23 @@ MI355_API void    mi355_set_embeddings(mi355_context *ctx, int32_t enabled);
 MI355_API float  *mi355_get_embeddings_ith(mi355_context *ctx, int32_t i);
 MI355_API void    mi355_synchronize(mi355_context *ctx);
 
+/* ------------------------------------------------------------------ LoRA adapters
+ * llama_adapter_lora_init / llama_adapter_lora_free / llama_set_adapter_lora / llama_rm_adapter_lora / llama_clear_adapter_lora (what common_init_from_params
+ * does with params.lora_adapters).  A convert_lora_to_gguf.py file: general.type "adapter", adapter.type "lora", the base model's general.architecture,
+ * adapter.lora.alpha, pairs <base tensor>.lora_a [K, r] / .lora_b [r, N], both F32 or both F16, r 1 .. 512, on blk.N.{attn_q,attn_k,attn_v,attn_output,
+ * ffn_gate,ffn_up,ffn_down}.weight and output.weight of a decoder model held on one device.  Applied at run time, never merged:
+ *   y = W x + sum over the set adapters of scale * alpha / r * B (A x)      (scale alone when alpha is 0), in the order the adapters were set.
+ * init: NULL + mi355_last_error on a refusal.  The model owns the device copy (counted in mi355_model_other_buffer); free an adapter only once no context
+ * has it set.  set (again: a new scale) / rm / clear drain the context and drop its captured steps.  rm: -1 when the adapter was not set. */
+typedef struct mi355_adapter_lora mi355_adapter_lora;
+MI355_API mi355_adapter_lora *mi355_adapter_lora_init(mi355_model *model, const char *path);
+MI355_API void    mi355_adapter_lora_free(mi355_adapter_lora *adapter);
+MI355_API float   mi355_adapter_lora_alpha(const mi355_adapter_lora *adapter);
+MI355_API int32_t mi355_adapter_lora_n_pairs(const mi355_adapter_lora *adapter);
+MI355_API int32_t mi355_set_adapter_lora(mi355_context *ctx, mi355_adapter_lora *adapter, float scale);
+MI355_API int32_t mi355_rm_adapter_lora(mi355_context *ctx, mi355_adapter_lora *adapter);
+MI355_API void    mi355_clear_adapter_lora(mi355_context *ctx);
+
 /* KV cache bookkeeping (ctx.cc:287; 661,1547; 1288,1540,1542; 1290) */
 MI355_API void    mi355_kv_cache_clear(mi355_context *ctx);
 MI355_API int32_t mi355_kv_cache_seq_rm(mi355_context *ctx, mi355_seq_id seq, mi355_pos p0, mi355_pos p1); /* 1 = ok */
@@ -244,6 +261,12 @@ MI355_API int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const i
  * The 32-element formats (any N, K % 32 == 0) run as a layer of such a file does: T >= 32 on the Q8_0 prompt kernel (Q8_0 tensors directly, the others with
  * "mmq_planes" 1 through their two Q8_0-layout copies) and the SwiGLU pass, else the mat-vec with SwiGLU in its epilogue.  F16: two products and the SwiGLU pass. */
 MI355_API int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y);
+/* The adapter kernels (csrc/lora.hip) once: out[s][t][n] += scale[s] * B[s][n] . (A[s] x[t]) for n_seg = 1 .. 3 segments that share the rows x [T][K].
+ * type[s]: F32 or F16 (both halves); A[s] [r][K], B[s] [N][r]; out[s] is [T][ld_out[s]], in and out - the columns beyond N[s] must come back untouched.
+ * ggml's CPU arithmetic: an F16 pair rounds x, and t = A x, to f16; every sum is f32.  T <= 8 is one launch, more tokens two.
+ * MI355_ERR_ARG, nothing launched: r outside 1 .. 512, K no multiple of 32, another type, ld_out < N. */
+MI355_API int mi355_op_lora_delta(int32_t n_seg, const int32_t *type, const void *const *A, const void *const *B, const int32_t *r, const int64_t *N, const float *scale,
+                                  const float *x, int64_t K, int64_t T, const int64_t *ld_out, float *const *out);
 MI355_API int mi355_op_rms_norm_mul(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y);
 MI355_API int mi355_op_rope(float *x, int32_t n_head, int32_t head_dim, int32_t n_rot, const int32_t *pos, int64_t T,
                             float freq_base, float freq_scale, const float *freq_factors, int32_t neox);
