@@ -99,6 +99,12 @@ SYMBOLS = {
     "mi355_kv_cache_seq_rm": (_i32, [_vp, _i32, _i32, _i32]),
     "mi355_kv_cache_seq_cp": (None, [_vp, _i32, _i32, _i32, _i32]),
     "mi355_kv_cache_seq_add": (None, [_vp, _i32, _i32, _i32, _i32]),
+    "mi355_state_seq_get_size": (_sz, [_vp, _i32]),
+    "mi355_state_seq_get_data": (_sz, [_vp, _vp, _sz, _i32]),
+    "mi355_state_seq_set_data": (_sz, [_vp, _vp, _sz, _i32]),
+    "mi355_state_seq_save_file": (_sz, [_vp, _cp, _i32, _vp, _sz]),
+    "mi355_state_seq_load_file": (_sz, [_vp, _cp, _i32, _vp, _sz, C.POINTER(C.c_size_t)]),
+    "mi355_debug_state_seq_timing": (None, [_vp, _vp]),
     "mi355_kv_cache_used_cells": (_i32, [_vp]),
     "mi355_debug_enable_taps": (None, [_vp, _i32]),
     "mi355_debug_layer_out": (_i32, [_vp, _i32, _vp, _sz]),
@@ -141,6 +147,8 @@ SYMBOLS = {
                                            _i32, _vp, _vp]),
     "mi355_op_kv_store": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "mi355_op_k_shift": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _f32, _f32, _vp, _f32, _f32, _f32, _f32, _vp]),
+    "mi355_op_kv_state_pack": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "mi355_op_kv_state_unpack": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "mi355_bench_hbm_read": (C.c_double, [_sz, C.c_int]),
     "mi355_profile_last_decode": (_i32, [_vp, C.POINTER(_cp), C.POINTER(_f32), _i32]),
     "mi355_profile_enable": (None, [_vp, _i32]),
@@ -163,6 +171,7 @@ SYMBOLS = {
     "mi355_engine_handle_embedding": (None, [_vp, _cp, ENGINE_CB, _vp]),
     "mi355_engine_is_supported": (_i32, [_vp, _cp]),
     "mi355_engine_stop_inferencing": (None, [_vp, _cp]),
+    "mi355_engine_prompt_cache_stats": (C.c_int, [_vp, _cp, _vp]),
     "mi355_engine_load": (None, [_vp, _cp, _cp, _i32, _cp, _i32, _i32]),
     "mi355_engine_unload": (None, [_vp]),
     "mi355_engine_set_file_logger": (None, [_vp, _i32, _cp]),
@@ -635,6 +644,34 @@ class Backend:
                                             _ptr(ff), float(ext_factor), float(attn_factor), float(corr_lo), float(corr_hi), _ptr(kc)), "op_k_shift")
         return kc
 
+    @staticmethod
+    def _layer_ptrs(layers):
+        arr = (C.c_void_p * len(layers))(*[a.ctypes.data for a in layers])
+        return arr
+
+    def kv_state_pack(self, type_k: int, type_v: int, n_head_kv: int, hd: int, k_layers, v_layers, cells) -> np.ndarray:
+        """The gather kernel of a sequence's state on its own (mi355_op_kv_state_pack): k_layers / v_layers hold one [n_cells][row bytes] cache per layer;
+        returns, per layer, the K rows of the listed cells in list order and then their V rows, as one uint8 array."""
+        cells = np.ascontiguousarray(cells, np.int32).reshape(-1)
+        kl = [np.ascontiguousarray(a).view(np.uint8) for a in k_layers]; vl = [np.ascontiguousarray(a).view(np.uint8) for a in v_layers]
+        assert len(kl) == len(vl) and all(a.ndim == 2 and a.shape[0] == kl[0].shape[0] for a in kl + vl)
+        out = np.zeros(sum(a.shape[1] for a in kl + vl) * cells.size, np.uint8)
+        self._chk(self.lib.mi355_op_kv_state_pack(type_k, type_v, len(kl), n_head_kv, hd, kl[0].shape[0], self._layer_ptrs(kl), self._layer_ptrs(vl), _ptr(cells),
+                                                  cells.size, _ptr(out)), "op_kv_state_pack")
+        return out
+
+    def kv_state_unpack(self, type_k: int, type_v: int, n_head_kv: int, hd: int, k_layers, v_layers, cells, rows):
+        """The scatter kernel (mi355_op_kv_state_unpack): `rows` (the layout kv_state_pack returns) written into the listed cells of the given caches; returns
+        (K caches, V caches) after the launch, one array per layer.  The inputs are not modified."""
+        cells = np.ascontiguousarray(cells, np.int32).reshape(-1)
+        rows = np.ascontiguousarray(rows, np.uint8).reshape(-1)
+        kl = [np.array(a, order="C", copy=True).view(np.uint8) for a in k_layers]; vl = [np.array(a, order="C", copy=True).view(np.uint8) for a in v_layers]
+        assert len(kl) == len(vl) and all(a.ndim == 2 and a.shape[0] == kl[0].shape[0] for a in kl + vl)
+        assert rows.size == sum(a.shape[1] for a in kl + vl) * cells.size
+        self._chk(self.lib.mi355_op_kv_state_unpack(type_k, type_v, len(kl), n_head_kv, hd, kl[0].shape[0], _ptr(rows), _ptr(cells), cells.size,
+                                                    self._layer_ptrs(kl), self._layer_ptrs(vl)), "op_kv_state_unpack")
+        return kl, vl
+
     def hbm_read_gbps(self, nbytes: int = 1 << 30, iters: int = 10) -> float:
         return float(self.lib.mi355_bench_hbm_read(nbytes, iters))
 
@@ -1017,6 +1054,47 @@ class Context:
     def kv_seq_add(self, seq, p0, p1, delta):
         self.lib.mi355_kv_cache_seq_add(self.h, seq, p0, p1, delta)
 
+    def state_seq_size(self, seq: int = 0) -> int:
+        return int(self.lib.mi355_state_seq_get_size(self.h, int(seq)))
+
+    def state_seq_get(self, seq: int = 0) -> bytes:
+        """llama_state_seq_get_data: the sequence's cells as a blob (header, positions, per-layer K / V rows; a pending K-shift is applied first)."""
+        buf = np.zeros(self.state_seq_size(seq), np.uint8)
+        n = int(self.lib.mi355_state_seq_get_data(self.h, _ptr(buf), buf.size, int(seq)))
+        if n == 0:
+            raise MI355Error(f"mi355_state_seq_get_data refused: {_err(self.lib)}")
+        return buf[:n].tobytes()
+
+    def state_seq_set(self, seq: int, blob) -> int:
+        """llama_state_seq_set_data: replaces what `seq` holds with the blob's cells; returns the bytes consumed, raises with the library's reason on a refusal."""
+        buf = np.frombuffer(bytes(blob), np.uint8)
+        n = int(self.lib.mi355_state_seq_set_data(self.h, buf.ctypes.data if buf.size else None, buf.size, int(seq)))
+        if n == 0:
+            raise MI355Error(f"mi355_state_seq_set_data refused: {_err(self.lib)}")
+        return n
+
+    def state_seq_save_file(self, path: str, seq: int, tokens) -> int:
+        tokens = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        n = int(self.lib.mi355_state_seq_save_file(self.h, os.fsencode(path), int(seq), _ptr(tokens), tokens.size))
+        if n == 0:
+            raise MI355Error(f"mi355_state_seq_save_file refused: {_err(self.lib)}")
+        return n
+
+    def state_seq_load_file(self, path: str, seq: int, max_tokens: int = 1 << 20) -> np.ndarray:
+        """llama_state_seq_load_file: restores the file's sequence into `seq`; returns the tokens stored with it."""
+        toks = np.zeros(max_tokens, np.int32)
+        n_tok = C.c_size_t(0)
+        n = int(self.lib.mi355_state_seq_load_file(self.h, os.fsencode(path), int(seq), _ptr(toks), toks.size, C.byref(n_tok)))
+        if n == 0:
+            raise MI355Error(f"mi355_state_seq_load_file refused: {_err(self.lib)}")
+        return toks[:n_tok.value].copy()
+
+    def state_seq_timing(self):
+        """(pack ms, device-to-host copy ms, unpack ms) of the last state_seq_get / state_seq_set; the first call switches the timing on."""
+        out = np.zeros(3, np.float32)
+        self.lib.mi355_debug_state_seq_timing(self.h, _ptr(out))
+        return tuple(float(x) for x in out)
+
     def kv_used(self) -> int:
         return int(self.lib.mi355_kv_cache_used_cells(self.h))
 
@@ -1116,6 +1194,14 @@ class Engine:
 
     def is_supported(self, feature: str) -> bool:
         return bool(self.lib.mi355_engine_is_supported(self.h, feature.encode()))
+
+    def prompt_cache_stats(self, model_id: str) -> dict:
+        """The counters of the model's host-RAM prompt cache (load key "cache_ram")."""
+        out = (C.c_int64 * 6)()
+        rc = self.lib.mi355_engine_prompt_cache_stats(self.h, model_id.encode(), out)
+        if rc < 0:
+            raise MI355Error(f"mi355_engine_prompt_cache_stats failed ({rc}): {_err(self.lib)}")
+        return dict(zip(("entries", "bytes", "saves", "restores", "tokens_restored", "evictions"), (int(v) for v in out)))
 
     def stop_inferencing(self, model_id: str) -> None:
         self.lib.mi355_engine_stop_inferencing(self.h, model_id.encode())

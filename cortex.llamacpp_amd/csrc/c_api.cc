@@ -23,6 +23,7 @@
 
 namespace mi355 {
 const std::string &last_error_string();
+void set_state_stage_max(size_t bytes);       // host/runtime.cc: the staging bound of Context::state_seq_get / set (tests)
 }
 
 using namespace mi355;
@@ -405,6 +406,91 @@ void mi355_kv_cache_seq_add(mi355_context *ctx, mi355_seq_id seq, mi355_pos p0, 
     ctx->c->kv_seq_add(seq, p0, p1, delta);
 }
 int32_t mi355_kv_cache_used_cells(const mi355_context *ctx) { return ctx->c->kv_used_cells(); }
+
+// ---- a sequence's KV state (llama_state_seq_*): the blob is Context::state_seq_get's (host/runtime.h); 0 = refused, the reason in mi355_last_error
+size_t mi355_state_seq_get_size(mi355_context *ctx, mi355_seq_id seq) {
+    if (!ctx || !ctx->c) { fail("state_seq_get_size: null context"); return 0; }
+    return ctx->c->state_seq_size(seq);
+}
+size_t mi355_state_seq_get_data(mi355_context *ctx, uint8_t *dst, size_t cap, mi355_seq_id seq) {
+    if (!ctx || !ctx->c) { fail("state_seq_get_data: null context"); return 0; }
+    MI355_GUARD(return 0,
+        const size_t n = ctx->c->state_seq_get(seq, dst, cap);
+        if (!n) fail(ctx->c->last_error);
+        return n;
+    )
+}
+size_t mi355_state_seq_set_data(mi355_context *ctx, const uint8_t *src, size_t len, mi355_seq_id dst) {
+    if (!ctx || !ctx->c) { fail("state_seq_set_data: null context"); return 0; }
+    MI355_GUARD(return 0,
+        const size_t n = ctx->c->state_seq_set(dst, src, len);
+        if (!n) fail(ctx->c->last_error);
+        return n;
+    )
+}
+// the file: 4 words {magic "M5KF", version, n_tokens, 0}, the blob's length (8 bytes), the tokens, the blob
+static const uint32_t STATE_FILE_MAGIC = 0x464b354du, STATE_FILE_VERSION = 1;
+static const size_t STATE_FILE_HEADER = 24;
+size_t mi355_state_seq_save_file(mi355_context *ctx, const char *path, mi355_seq_id seq, const mi355_token *tokens, size_t n_tokens) {
+    if (!ctx || !ctx->c) { fail("state_seq_save_file: null context"); return 0; }
+    if (!path || (n_tokens && !tokens) || n_tokens > 0x7fffffffu) { fail("state_seq_save_file: null path / tokens"); return 0; }
+    MI355_GUARD(return 0,
+        const size_t blob = ctx->c->state_seq_size(seq);
+        std::vector<uint8_t> buf(STATE_FILE_HEADER + n_tokens * 4 + blob);
+        const size_t got = blob ? ctx->c->state_seq_get(seq, buf.data() + STATE_FILE_HEADER + n_tokens * 4, blob) : 0;
+        if (!got) { fail(blob ? ctx->c->last_error : std::string("state_seq_save_file: this context has no sequence state")); return 0; }
+        const uint32_t head[4] = {STATE_FILE_MAGIC, STATE_FILE_VERSION, (uint32_t)n_tokens, 0};
+        const uint64_t blob_len = got;
+        memcpy(buf.data(), head, 16);
+        memcpy(buf.data() + 16, &blob_len, 8);
+        if (n_tokens) memcpy(buf.data() + STATE_FILE_HEADER, tokens, n_tokens * 4);
+        buf.resize(STATE_FILE_HEADER + n_tokens * 4 + got);
+        // a reader never sees a half-written file: the bytes go to a temporary name beside the target, which is then renamed over it
+        const std::string tmp = std::string(path) + ".tmp";
+        FILE *f = fopen(tmp.c_str(), "wb");
+        if (!f) { fail("state_seq_save_file: cannot create " + tmp); return 0; }
+        const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+        if (fclose(f) != 0 || !ok) { remove(tmp.c_str()); fail("state_seq_save_file: write to " + tmp + " failed"); return 0; }
+        if (rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); fail(std::string("state_seq_save_file: cannot rename to ") + path); return 0; }
+        return buf.size();
+    )
+}
+size_t mi355_state_seq_load_file(mi355_context *ctx, const char *path, mi355_seq_id dst_seq, mi355_token *tokens_out, size_t cap, size_t *n_tokens_out) {
+    if (!ctx || !ctx->c) { fail("state_seq_load_file: null context"); return 0; }
+    if (!path) { fail("state_seq_load_file: null path"); return 0; }
+    if (n_tokens_out) *n_tokens_out = 0;
+    MI355_GUARD(return 0,
+        FILE *f = fopen(path, "rb");
+        if (!f) { fail(std::string("state_seq_load_file: cannot open ") + path); return 0; }
+        struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{f};
+        uint8_t hb[STATE_FILE_HEADER];
+        if (fread(hb, 1, sizeof hb, f) != sizeof hb) { fail("state_seq_load_file: truncated file: no header"); return 0; }
+        uint32_t head[4];
+        uint64_t blob_len = 0;
+        memcpy(head, hb, 16); memcpy(&blob_len, hb + 16, 8);
+        if (head[0] != STATE_FILE_MAGIC) { fail("state_seq_load_file: magic mismatch: the file has " + std::to_string(head[0]) + ", a state file has " + std::to_string(STATE_FILE_MAGIC)); return 0; }
+        if (head[1] != STATE_FILE_VERSION) { fail("state_seq_load_file: version mismatch: the file has " + std::to_string(head[1]) + ", this build reads " + std::to_string(STATE_FILE_VERSION)); return 0; }
+        const size_t n_tok = head[2];
+        if (fseek(f, 0, SEEK_END) != 0) { fail("state_seq_load_file: seek failed"); return 0; }
+        const long flen = ftell(f);
+        const uint64_t want = (uint64_t)STATE_FILE_HEADER + (uint64_t)n_tok * 4 + blob_len;
+        if (flen < 0 || (uint64_t)flen != want) { fail("state_seq_load_file: file length mismatch: the file has " + std::to_string(flen) + " bytes, its header asks for " + std::to_string(want)); return 0; }
+        if (n_tok > cap || (n_tok && !tokens_out)) { fail("state_seq_load_file: token buffer of " + std::to_string(cap) + ", the file holds " + std::to_string(n_tok)); return 0; }
+        if (fseek(f, (long)STATE_FILE_HEADER, SEEK_SET) != 0) { fail("state_seq_load_file: seek failed"); return 0; }
+        std::vector<mi355_token> toks(n_tok);
+        std::vector<uint8_t> blob((size_t)blob_len);
+        if ((n_tok && fread(toks.data(), 4, n_tok, f) != n_tok) || fread(blob.data(), 1, blob.size(), f) != blob.size()) { fail("state_seq_load_file: read failed"); return 0; }
+        if (!ctx->c->state_seq_set(dst_seq, blob.data(), blob.size())) { fail(ctx->c->last_error); return 0; }
+        if (n_tok) memcpy(tokens_out, toks.data(), n_tok * 4);
+        if (n_tokens_out) *n_tokens_out = n_tok;
+        return (size_t)want;
+    )
+}
+void mi355_debug_state_seq_timing(mi355_context *ctx, float out_ms[3]) {
+    if (!ctx || !ctx->c) return;
+    ctx->c->state_timing = true;
+    if (out_ms) { out_ms[0] = ctx->c->state_ms_pack; out_ms[1] = ctx->c->state_ms_copy; out_ms[2] = ctx->c->state_ms_unpack; }
+}
 
 void mi355_debug_enable_taps(mi355_context *ctx, int32_t enabled) { ctx->c->set_debug_taps(enabled != 0); }
 int32_t mi355_debug_layer_out(mi355_context *ctx, int32_t il, float *dst, size_t dst_floats) { return ctx->c->debug_layer_out(il, dst, dst_floats); }
@@ -1645,6 +1731,74 @@ int mi355_op_k_shift(int32_t type_k, int32_t G, int32_t D, int32_t n_rot, int32_
     return cache_rows_from_planes(type_k, dk, dks, G, D, n_cells, k_cache) ? MI355_OK : MI355_ERR_HIP;
 }
 
+// The gather / scatter kernels of a sequence's state on their own (test entries): a cache of n_layer layers crosses the boundary as ggml-layout rows per layer and is
+// uploaded into device planes; `cells` is checked here, as Context::state_seq_get / set check their own lists before they launch.
+namespace {
+struct StateOpCache {
+    std::vector<std::unique_ptr<DevBuf>> bufs;       // per layer: K codes, K scales, V codes, V scales
+    std::vector<KVLayerView> views;
+    std::unique_ptr<DevBuf> table, cells, rows;
+    size_t row_bytes = 0;
+    int init(int type_k, int type_v, int n_layer, int G, int D, int n_cells, const void *const *k_rows, const void *const *v_rows, const int32_t *cell_list, int n, bool distinct) {
+        if (!k_rows || !v_rows || !cell_list || n_layer < 1 || n_layer > 1024 || G < 1 || D < 32 || D % 32 || n_cells < 1 || n < 1 || n > n_cells) { fail("kv_state: bad geometry / null argument"); return MI355_ERR_ARG; }
+        if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("kv_state: bad cache type"); return MI355_ERR_ARG; }
+        std::vector<char> seen((size_t)n_cells, 0);
+        for (int i = 0; i < n; i++) {
+            if (cell_list[i] < 0 || cell_list[i] >= n_cells) { fail("kv_state: cells[" + std::to_string(i) + "] outside the cache"); return MI355_ERR_ARG; }
+            if (distinct && seen[(size_t)cell_list[i]]) { fail("kv_state: cells[" + std::to_string(i) + "] listed twice"); return MI355_ERR_ARG; }
+            seen[(size_t)cell_list[i]] = 1;
+        }
+        views.resize((size_t)n_layer);
+        for (int il = 0; il < n_layer; il++) {
+            if (!k_rows[il] || !v_rows[il]) { fail("kv_state: null layer"); return MI355_ERR_ARG; }
+            std::vector<uint8_t> kc, vc;
+            std::vector<uint16_t> ks, vs;
+            cache_planes_from_rows(type_k, k_rows[il], G, D, n_cells, kc, ks);
+            cache_planes_from_rows(type_v, v_rows[il], G, D, n_cells, vc, vs);
+            DevBuf *b[4] = {new DevBuf(kc.size()), new DevBuf(ks.size() * 2 + 16), new DevBuf(vc.size()), new DevBuf(vs.size() * 2 + 16)};
+            for (DevBuf *p : b) bufs.emplace_back(p);
+            if (!b[0]->up(kc.data(), kc.size()) || !b[2]->up(vc.data(), vc.size()) || !b[1]->p || !b[3]->p || (!ks.empty() && !b[1]->up(ks.data(), ks.size() * 2)) ||
+                (!vs.empty() && !b[3]->up(vs.data(), vs.size() * 2))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+            views[(size_t)il].k = b[0]->as<uint8_t>(); views[(size_t)il].kd = b[1]->as<uint16_t>(); views[(size_t)il].v = b[2]->as<uint8_t>(); views[(size_t)il].vd = b[3]->as<uint16_t>();
+        }
+        row_bytes = (size_t)n_layer * n * (kv_state_row_bytes(type_k, G, D) + kv_state_row_bytes(type_v, G, D));
+        table.reset(new DevBuf(views.size() * sizeof(KVLayerView)));
+        cells.reset(new DevBuf((size_t)n * 4));
+        rows.reset(new DevBuf(row_bytes));
+        if (!table->up(views.data(), views.size() * sizeof(KVLayerView)) || !cells->up(cell_list, (size_t)n * 4) || !rows->p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+        return MI355_OK;
+    }
+};
+}  // namespace
+
+int mi355_op_kv_state_pack(int32_t type_k, int32_t type_v, int32_t n_layer, int32_t G, int32_t D, int32_t n_cells, const void *const *k_rows, const void *const *v_rows,
+                           const int32_t *cells, int32_t n, void *out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!out) { fail("kv_state_pack: null output"); return MI355_ERR_ARG; }
+    StateOpCache c;
+    if (const int rc = c.init(type_k, type_v, n_layer, G, D, n_cells, k_rows, v_rows, cells, n, false)) return rc;
+    hipError_t e = launch_kv_state_pack(c.table->as<KVLayerView>(), n_layer, type_k, type_v, G, D, n_cells, c.cells->as<int32_t>(), n, c.rows->as<uint8_t>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "kv_state_pack");
+    return c.rows->down(out, c.row_bytes) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_kv_state_unpack(int32_t type_k, int32_t type_v, int32_t n_layer, int32_t G, int32_t D, int32_t n_cells, const void *in, const int32_t *cells, int32_t n,
+                             void *const *k_rows, void *const *v_rows) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!in) { fail("kv_state_unpack: null input"); return MI355_ERR_ARG; }
+    StateOpCache c;
+    if (const int rc = c.init(type_k, type_v, n_layer, G, D, n_cells, k_rows, v_rows, cells, n, true)) return rc;
+    if (!c.rows->up(in, c.row_bytes)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_kv_state_unpack(c.table->as<KVLayerView>(), n_layer, type_k, type_v, G, D, n_cells, c.cells->as<int32_t>(), n, c.rows->as<uint8_t>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "kv_state_unpack");
+    for (int il = 0; il < n_layer; il++)
+        if (!cache_rows_from_planes(type_k, *c.bufs[(size_t)il * 4], *c.bufs[(size_t)il * 4 + 1], G, D, n_cells, k_rows[il]) ||
+            !cache_rows_from_planes(type_v, *c.bufs[(size_t)il * 4 + 2], *c.bufs[(size_t)il * 4 + 3], G, D, n_cells, v_rows[il])) return MI355_ERR_HIP;
+    return MI355_OK;
+}
+
 int mi355_debug_set_option(const char *name, int32_t value) {
     if (!name) return MI355_ERR_ARG;
     if (!strcmp(name, "mmq_planes")) { g_op_mmq_planes = value != 0; return MI355_OK; }
@@ -1670,6 +1824,7 @@ int mi355_debug_set_option(const char *name, int32_t value) {
     if (!strcmp(name, "moe_q80_grouped")) { set_moe_q80_grouped(value != 0); return MI355_OK; }
     if (!strcmp(name, "fa_v_acc_f16")) { set_fa_v_acc_f16(value); return MI355_OK; }              // f16 cache: the CPU path's fp16 V accumulation (parity mode)
     if (!strcmp(name, "raise_stream_error")) { debug_raise_stream_error((unsigned)value); return MI355_OK; }   // tests: what a timed-out in-kernel wait does
+    if (!strcmp(name, "state_stage_kib")) { set_state_stage_max((size_t)(value > 0 ? value : 0) * 1024); return MI355_OK; }   // tests: sequence states through a small staging block, in chunks (0: the default 64 MiB; contexts that have not moved a state yet)
     if (!strcmp(name, "tp_null_group")) { tp_set_null_group(0, value); return MI355_OK; }
     fail(std::string("unknown option ") + name);
     return MI355_ERR_ARG;
@@ -1830,6 +1985,13 @@ MI355_ENGINE_FWD(mi355_engine_handle_embedding, HandleEmbedding)
 void mi355_engine_set_release_callback(mi355_engine *e, void (*release)(void *user)) { if (e) e->release.store(release); }
 int32_t mi355_engine_is_supported(mi355_engine *e, const char *feature) { return e && feature && e->eng.IsSupported(feature) ? 1 : 0; }
 void mi355_engine_stop_inferencing(mi355_engine *e, const char *model_id) { if (e && model_id) e->eng.StopInferencing(model_id); }
+int mi355_engine_prompt_cache_stats(mi355_engine *e, const char *model_id, int64_t out[6]) {
+    if (!e || !model_id || !out) { fail("prompt_cache_stats: null argument"); return MI355_ERR_ARG; }
+    MI355_GUARD(return MI355_ERR_ARG,
+        if (!e->eng.PromptCacheStats(model_id, out)) { fail(std::string("prompt_cache_stats: no model ") + model_id); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
 void mi355_engine_load(mi355_engine *e, const char *engine_path, const char *deps_path, int32_t is_custom_engine_path, const char *log_path, int32_t max_log_lines,
                        int32_t log_level) {
     if (!e) return;

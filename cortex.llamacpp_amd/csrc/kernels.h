@@ -472,6 +472,18 @@ int flash_attn_pick_splits(int T, int G, int n_kv_max);
 // re-rotate cached K rows after seq_add (K-shift): for each cell with delta[c] != 0
 hipError_t launch_k_shift(KVLayerView kv, int type_k, int G, int D, int n_ctx, const int32_t *delta, RopeArgs ra, hipStream_t st);
 
+// ---------------------------------------------------------------- a sequence's cells as portable rows (kv_state.hip)
+// The portable form of n cells: per layer, K rows [n][G * D] and then V rows likewise, each in the ggml layout of its cache type (f16 halves, 34-byte q8_0 blocks,
+// 18-byte q4_0 blocks - what mi355_op_flash_attn takes for k / v); row i is cell cells_dev[i].  pack gathers the rows out of the planes, unpack scatters them into
+// the listed cells and writes no other byte of any plane.  One launch for all layers; layers_dev: n_layer views in device memory; cells_dev: n indices in
+// [0, n_ctx), for unpack all different (the caller checks both); rows: n_layer * n * (row_bytes_k + row_bytes_v) bytes at an even address.  n == 0: nothing is launched.
+size_t kv_state_row_bytes(int type, int G, int D);
+int kv_state_tile_cells(int type_k, int type_v, int G, int D);    // cells of the list one workgroup moves
+hipError_t launch_kv_state_pack(const KVLayerView *layers_dev, int n_layer, int type_k, int type_v, int G, int D, int n_ctx, const int32_t *cells_dev, int n, uint8_t *rows,
+                                hipStream_t st);
+hipError_t launch_kv_state_unpack(const KVLayerView *layers_dev, int n_layer, int type_k, int type_v, int G, int D, int n_ctx, const int32_t *cells_dev, int n,
+                                  const uint8_t *rows, hipStream_t st);
+
 // cell metadata update inside the decode graph: cell_pos[cell] = pos, cell_seq[cell] = mask
 hipError_t launch_kv_meta_set(int32_t *cell_pos, uint64_t *cell_seq, const int32_t *tok_cell, const int32_t *tok_pos,
                               const uint64_t *tok_seqmask, int T, hipStream_t st, unsigned *zero_word = nullptr);

@@ -82,6 +82,11 @@ class IBackend {
     virtual bool kv_seq_rm(int seq, int p0, int p1) = 0;
     virtual void kv_seq_add(int seq, int p0, int p1, int delta) = 0;
     virtual void kv_seq_cp(int src, int dst, int p0, int p1) = 0;
+    // llama_state_seq_get_size / get_data / set_data (runtime.h Context::state_seq_*): a sequence's KV cells as a blob.  The defaults are a backend that has
+    // none: size 0, get / set fail (return 0) - the slot loop's host-RAM prompt cache is then off.
+    virtual size_t state_seq_size(int seq) { (void)seq; return 0; }
+    virtual size_t state_seq_get(int seq, uint8_t *dst, size_t cap) { (void)seq; (void)dst; (void)cap; return 0; }
+    virtual size_t state_seq_set(int seq, const uint8_t *src, size_t len) { (void)seq; (void)src; (void)len; return 0; }
 };
 
 }  // namespace mi355

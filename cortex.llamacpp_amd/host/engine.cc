@@ -201,6 +201,12 @@ bool LlamaEngine::LoadModelImpl(const Json &body, std::string &err) {   // :547-
     sp.cont_batching = body.value<bool>("cont_batching", true);               // :625-627
     sp.n_predict = body.value<int>("n_predict", -1);
     sp.model_alias = model_id;
+    // "cache_ram": MiB of host memory for KV states of conversations that lost their slot (upstream's --cache-ram; prompt_cache.h); 0 = off, negative = no limit
+    sp.cache_ram_mib = body.value<int>("cache_ram", 0);
+    if (sp.cache_ram_mib != 0 && si->backend->state_seq_size(0) == 0) {
+        log_line(LOG_WARN, "cache_ram: this backend has no sequence state (a row-split or an embedding model): the prompt cache is off");
+        sp.cache_ram_mib = 0;
+    }
     si->user_prompt = body.value<std::string>("user_prompt", "USER: ");       // :662-669
     si->ai_prompt = body.value<std::string>("ai_prompt", "ASSISTANT: ");
     si->system_prompt = body.value<std::string>("system_prompt", "ASSISTANT's RULE: ");
@@ -291,6 +297,14 @@ bool LlamaEngine::CheckModelLoaded(const Callback &cb, const std::string &model_
 void LlamaEngine::StopInferencing(const std::string &model_id) {   // :502-508
     std::lock_guard<std::mutex> lk(stop_mutex_);
     force_stop_.insert(model_id);
+}
+
+bool LlamaEngine::PromptCacheStats(const std::string &model_id, int64_t out[6]) {
+    std::lock_guard<std::mutex> lk(map_mutex_);
+    auto it = server_map_.find(model_id);
+    if (it == server_map_.end() || !it->second->ctx) return false;
+    it->second->ctx->PromptCacheStats(out);
+    return true;
 }
 
 // base64 of the raw little-endian f32 bytes (encoding_format = "base64"; llama_utils::base64Encode / FloatVectorToBytes)

@@ -1,6 +1,7 @@
 // hip_backend.cc — see hip_backend.h.  Key mapping follows src/llama_engine.cc:587-660:
 //   llama_model_path | model_path, ngl (300), ctx_len (2048), n_batch (2048), n_ubatch (= n_batch), n_parallel (1),
 //   cache_type f16|q8_0|q4_0 (invalid -> f16), flash_attn (true; forced on by a quantised cache), embedding.
+//   ("cache_ram", the host-RAM prompt cache, is the slot loop's: engine.cc reads it and asks this backend for a sequence's state through state_seq_*.)
 #include "hip_backend.h"
 
 #include <exception>
@@ -119,6 +120,9 @@ class HipBackend : public IBackend {
     bool kv_seq_rm(int seq, int p0, int p1) override { return ctx_->kv_seq_rm(seq, p0, p1); }
     void kv_seq_add(int seq, int p0, int p1, int delta) override { ctx_->kv_seq_add(seq, p0, p1, delta); }
     void kv_seq_cp(int src, int dst, int p0, int p1) override { ctx_->kv_seq_cp(src, dst, p0, p1); }
+    size_t state_seq_size(int seq) override { return ctx_->state_seq_size(seq); }
+    size_t state_seq_get(int seq, uint8_t *dst, size_t cap) override { return ctx_->state_seq_get(seq, dst, cap); }
+    size_t state_seq_set(int seq, const uint8_t *src, size_t len) override { return ctx_->state_seq_set(seq, src, len); }
 
   private:
     static uint64_t bytes_key(const uint8_t *b, size_t n) {           // FNV-1a over the bytes

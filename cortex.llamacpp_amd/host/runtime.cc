@@ -696,6 +696,180 @@ void Context::apply_k_shift() {
     has_shift_ = false;
 }
 
+// ------------------------------------------------------------------------------------------ a sequence's state (llama_state_seq_*; runtime.h)
+namespace {
+size_t g_state_stage_max = (size_t)64 << 20;             // device staging of the portable rows: a long sequence goes through it in chunks of cells
+struct EventPair {                                        // state_timing: one launch / copy between two events of its own
+    hipEvent_t a = nullptr, b = nullptr;
+    bool on;
+    explicit EventPair(bool enable) : on(enable) { if (on && (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)) on = false; }
+    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    void begin(hipStream_t st) { if (on) (void)hipEventRecord(a, st); }
+    void end(hipStream_t st, float &acc) {
+        if (!on) return;
+        float ms = 0.0f;
+        if (hipEventRecord(b, st) == hipSuccess && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) acc += ms;
+    }
+};
+}  // namespace
+
+void set_state_stage_max(size_t bytes) { g_state_stage_max = bytes ? bytes : (size_t)64 << 20; }   // tests: contexts that have not moved a state yet chunk at this size
+
+const char *Context::state_refusal() const {
+    if (model->hp.encoder) return "an encoder context has no KV cache, so no sequence state";
+    if (model->hp.tp_size > 1) return "a rank of a row split holds a slice of every KV row, so no sequence state (load the model on one device)";
+    return nullptr;
+}
+size_t Context::state_cell_bytes() const {
+    const HParams &hp = model->hp;
+    return (size_t)hp.n_layer * (kv_state_row_bytes(cp.type_k, hp.n_head_kv, hp.head_dim) + kv_state_row_bytes(cp.type_v, hp.n_head_kv, hp.head_dim));
+}
+size_t Context::state_seq_size(int seq) const {
+    if (state_refusal() || seq < 0 || seq >= 64) return 0;
+    size_t n = 0;
+    for (const KVCell &c : cells_) n += (c.pos >= 0 && (c.seqs & (1ull << seq))) ? 1 : 0;
+    return STATE_HEADER_BYTES + 4 * n + n * state_cell_bytes();
+}
+bool Context::state_prepare() {
+    if (d_state_stage_) return true;
+    const size_t per = state_cell_bytes();
+    state_stage_bytes_ = std::max(per, std::min(g_state_stage_max, per * (size_t)cp.n_ctx));
+    uint8_t *stage = (uint8_t *)dalloc(state_stage_bytes_);
+    d_state_cells_ = (int32_t *)dalloc((size_t)cp.n_ctx * 4);
+    d_state_layers_ = (KVLayerView *)dalloc(kv_.size() * sizeof(KVLayerView));
+    if (!stage || !d_state_cells_ || !d_state_layers_ ||
+        hipMemcpy(d_state_layers_, kv_.data(), kv_.size() * sizeof(KVLayerView), hipMemcpyHostToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {               // (the zero-fills of dalloc ran on the null stream: see init)
+        last_error = "sequence state: staging allocation failed";
+        return false;
+    }
+    d_state_stage_ = stage;
+    return true;
+}
+
+size_t Context::state_seq_get(int seq, uint8_t *dst, size_t cap) {
+    if (const char *why = state_refusal()) { last_error = std::string("state_seq_get: ") + why; return 0; }
+    if (seq < 0 || seq >= 64) { last_error = "state_seq_get: seq id " + std::to_string(seq) + " out of range [0, 64)"; return 0; }
+    if (hipSetDevice(model->device) != hipSuccess) { last_error = "state_seq_get: hipSetDevice failed"; return 0; }
+    if (has_shift_) apply_k_shift();                           // the blob holds K as rotated for the positions it records
+    const HParams &hp = model->hp;
+    std::vector<std::pair<int32_t, int32_t>> pc;               // (position, cell)
+    for (size_t i = 0; i < cells_.size(); i++)
+        if (cells_[i].pos >= 0 && (cells_[i].seqs & (1ull << seq))) pc.emplace_back(cells_[i].pos, (int32_t)i);
+    std::sort(pc.begin(), pc.end());
+    const size_t n = pc.size(), per = state_cell_bytes(), need = STATE_HEADER_BYTES + 4 * n + n * per;
+    if (!dst || cap < need) { last_error = "state_seq_get: a buffer of " + std::to_string(cap) + " bytes, sequence " + std::to_string(seq) + " needs " + std::to_string(need); return 0; }
+    const uint32_t head[8] = {STATE_MAGIC, STATE_VERSION, (uint32_t)cp.type_k, (uint32_t)cp.type_v, (uint32_t)hp.n_layer, (uint32_t)hp.n_head_kv, (uint32_t)hp.head_dim, (uint32_t)n};
+    memcpy(dst, head, sizeof head);
+    std::vector<int32_t> cells(n);
+    for (size_t i = 0; i < n; i++) { memcpy(dst + STATE_HEADER_BYTES + 4 * i, &pc[i].first, 4); cells[i] = pc[i].second; }
+    if (n == 0) return need;
+    if (!state_prepare()) return 0;
+    const size_t rbk = kv_state_row_bytes(cp.type_k, hp.n_head_kv, hp.head_dim), rbv = kv_state_row_bytes(cp.type_v, hp.n_head_kv, hp.head_dim);
+    uint8_t *rows = dst + STATE_HEADER_BYTES + 4 * n;
+    state_ms_pack = state_ms_copy = 0.0f;
+    EventPair ev(state_timing);
+    hipError_t e = hipMemcpyAsync(d_state_cells_, cells.data(), n * 4, hipMemcpyHostToDevice, stream_);
+    const size_t chunk = std::max<size_t>(1, state_stage_bytes_ / per);
+    for (size_t off = 0; off < n && e == hipSuccess; off += chunk) {
+        const size_t nc = std::min(chunk, n - off);
+        ev.begin(stream_);
+        e = launch_kv_state_pack(d_state_layers_, hp.n_layer, cp.type_k, cp.type_v, hp.n_head_kv, hp.head_dim, (int)cp.n_ctx, d_state_cells_ + off, (int)nc, d_state_stage_, stream_);
+        ev.end(stream_, state_ms_pack);
+        ev.begin(stream_);
+        if (e == hipSuccess && nc == n) e = hipMemcpyAsync(rows, d_state_stage_, n * per, hipMemcpyDeviceToHost, stream_);     // one chunk: the staging block IS the row section
+        else
+            for (int il = 0; il < hp.n_layer && e == hipSuccess; il++) {
+                const uint8_t *s = d_state_stage_ + (size_t)il * nc * (rbk + rbv);
+                uint8_t *d = rows + (size_t)il * n * (rbk + rbv);
+                e = hipMemcpyAsync(d + off * rbk, s, nc * rbk, hipMemcpyDeviceToHost, stream_);
+                if (e == hipSuccess) e = hipMemcpyAsync(d + n * rbk + off * rbv, s + nc * rbk, nc * rbv, hipMemcpyDeviceToHost, stream_);
+            }
+        ev.end(stream_, state_ms_copy);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);          // the next chunk packs into the same block
+    }
+    if (e == hipSuccess) fused_release();                  // (the stream has just been drained)
+    if (e != hipSuccess) { last_error = std::string("state_seq_get: ") + hipGetErrorString(e); return 0; }
+    return need;
+}
+
+size_t Context::state_seq_set(int seq, const uint8_t *src, size_t len) {
+    if (const char *why = state_refusal()) { last_error = std::string("state_seq_set: ") + why; return 0; }
+    if (seq < 0 || seq >= 64) { last_error = "state_seq_set: seq id " + std::to_string(seq) + " out of range [0, 64)"; return 0; }
+    if (!src || len < STATE_HEADER_BYTES) { last_error = "state_seq_set: truncated blob: " + std::to_string(src ? len : 0) + " bytes, the header alone has " + std::to_string(STATE_HEADER_BYTES); return 0; }
+    const HParams &hp = model->hp;
+    uint32_t head[8];
+    memcpy(head, src, sizeof head);
+    const char *names[7] = {"magic", "version", "type_k", "type_v", "n_layer", "n_head_kv", "head_dim"};
+    const uint32_t want[7] = {STATE_MAGIC, STATE_VERSION, (uint32_t)cp.type_k, (uint32_t)cp.type_v, (uint32_t)hp.n_layer, (uint32_t)hp.n_head_kv, (uint32_t)hp.head_dim};
+    for (int i = 0; i < 7; i++)
+        if (head[i] != want[i]) { last_error = std::string("state_seq_set: ") + names[i] + " mismatch: the blob has " + std::to_string(head[i]) + ", the context has " + std::to_string(want[i]); return 0; }
+    const size_t n = head[7], per = state_cell_bytes();
+    // the sequence's region (alloc_cells): the whole cache for a single-sequence context
+    const int NC = (int)cells_.size(), NS = (int)cp.n_seq_max;
+    size_t region = (size_t)NC;
+    if (NS > 1) {
+        int R = std::max(1, NC / NS);
+        if (R >= 64) R &= ~63;
+        const int s = std::min(seq, NS - 1);
+        region = (size_t)(s == NS - 1 ? NC - s * R : R);
+    }
+    if (n > region) { last_error = "state_seq_set: n mismatch: the blob has " + std::to_string(n) + " cells, the region of sequence " + std::to_string(seq) + " has " + std::to_string(region); return 0; }
+    const size_t need = STATE_HEADER_BYTES + 4 * n + n * per;
+    if (len < need) { last_error = "state_seq_set: truncated blob: " + std::to_string(len) + " bytes, its header asks for " + std::to_string(need); return 0; }
+    std::vector<int32_t> pos(n);
+    if (n) memcpy(pos.data(), src + STATE_HEADER_BYTES, 4 * n);
+    for (size_t i = 0; i < n; i++) {
+        if (pos[i] < 0) { last_error = "state_seq_set: negative position " + std::to_string(pos[i]) + " at index " + std::to_string(i); return 0; }
+        if (i && pos[i] <= pos[i - 1]) { last_error = "state_seq_set: positions not ascending at index " + std::to_string(i) + ": " + std::to_string(pos[i - 1]) + " then " + std::to_string(pos[i]); return 0; }
+    }
+    const uint64_t bit = 1ull << seq;
+    size_t avail = 0;                                          // free cells, and cells nothing but this sequence holds
+    for (const KVCell &c : cells_) avail += (c.pos < 0 || c.seqs == bit) ? 1 : 0;
+    if (n > avail) { last_error = "state_seq_set: no cells: the blob has " + std::to_string(n) + ", the cache can free " + std::to_string(avail); return 0; }
+    if (hipSetDevice(model->device) != hipSuccess) { last_error = "state_seq_set: hipSetDevice failed"; return 0; }
+    // from here on the destination is rewritten: whatever goes wrong leaves it empty
+    kv_seq_rm(seq, -1, -1);
+    region_next_.clear();                                      // the region's lowest free cells first: a pure function of the cell table
+    meta_dirty_ = true;
+    if (n == 0) return need;
+    std::vector<uint64_t> masks(n, bit);
+    std::vector<int> got;
+    if (!alloc_cells((int)n, masks.data(), got)) { last_error = "state_seq_set: no cells: the cache has no room for " + std::to_string(n); return 0; }
+    if (!state_prepare()) return 0;
+    const size_t rbk = kv_state_row_bytes(cp.type_k, hp.n_head_kv, hp.head_dim), rbv = kv_state_row_bytes(cp.type_v, hp.n_head_kv, hp.head_dim);
+    const uint8_t *rows = src + STATE_HEADER_BYTES + 4 * n;
+    std::vector<int32_t> cells(got.begin(), got.end());
+    state_ms_unpack = 0.0f;
+    EventPair ev(state_timing);
+    hipError_t e = hipMemcpyAsync(d_state_cells_, cells.data(), n * 4, hipMemcpyHostToDevice, stream_);
+    const size_t chunk = std::max<size_t>(1, state_stage_bytes_ / per);
+    for (size_t off = 0; off < n && e == hipSuccess; off += chunk) {
+        const size_t nc = std::min(chunk, n - off);
+        if (nc == n) e = hipMemcpyAsync(d_state_stage_, rows, n * per, hipMemcpyHostToDevice, stream_);
+        else
+            for (int il = 0; il < hp.n_layer && e == hipSuccess; il++) {
+                uint8_t *d = d_state_stage_ + (size_t)il * nc * (rbk + rbv);
+                const uint8_t *s = rows + (size_t)il * n * (rbk + rbv);
+                e = hipMemcpyAsync(d, s + off * rbk, nc * rbk, hipMemcpyHostToDevice, stream_);
+                if (e == hipSuccess) e = hipMemcpyAsync(d + nc * rbk, s + n * rbk + off * rbv, nc * rbv, hipMemcpyHostToDevice, stream_);
+            }
+        ev.begin(stream_);
+        if (e == hipSuccess)
+            e = launch_kv_state_unpack(d_state_layers_, hp.n_layer, cp.type_k, cp.type_v, hp.n_head_kv, hp.head_dim, (int)cp.n_ctx, d_state_cells_ + off, (int)nc, d_state_stage_, stream_);
+        ev.end(stream_, state_ms_unpack);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);          // the next chunk is copied into the same block
+    }
+    if (e == hipSuccess) fused_release();                  // (the stream has just been drained)
+    if (e != hipSuccess) { last_error = std::string("state_seq_set: ") + hipGetErrorString(e); return 0; }
+    for (size_t i = 0; i < n; i++) {
+        KVCell &c = cells_[(size_t)got[i]];
+        c.pos = pos[i]; c.seqs = bit; c.delta = 0;
+    }
+    meta_dirty_ = true;
+    return need;
+}
+
 // ------------------------------------------------------------------------------------------ profiling
 void Context::prof_begin() {
     if (!profile_) return;

@@ -128,6 +128,21 @@ class Context {
     void kv_seq_add(int seq, int p0, int p1, int delta);
     int kv_used_cells() const;
 
+    // llama_state_seq_get_size / get_data / set_data: the cells of one sequence as a blob another context of the same geometry and cache types can take.
+    //   header: 8 little-endian 32-bit words - magic "M5KV", version, type_k, type_v, n_layer, n_head_kv, head_dim, n (cells)
+    //   n int32 positions, ascending; then per layer K rows [n][n_head_kv * head_dim] and V rows likewise, ggml layout of the cache type (kernels.h, kv_state.hip)
+    // size = 32 + 4 n + n_layer * n * (row_bytes_k + row_bytes_v), from the host's cell table alone.  get applies a pending K-shift first, so K is rotated for the
+    // positions the blob records; it returns the bytes written, 0 with last_error set when refused (cap too small, an encoder, a rank of a row split).
+    // set removes everything `seq` holds, allocates n cells for it (alloc_cells: the region's lowest free cells, in position order), scatters the rows and marks
+    // the cell table dirty; it returns the bytes consumed, or 0 with last_error naming the field and both values - the sequence is then left empty.
+    static constexpr uint32_t STATE_MAGIC = 0x564b354du, STATE_VERSION = 1, STATE_HEADER_BYTES = 32;
+    size_t state_seq_size(int seq) const;
+    size_t state_seq_get(int seq, uint8_t *dst, size_t cap);
+    size_t state_seq_set(int seq, const uint8_t *src, size_t len);
+    // measurement (profiles/): the pack launch, the copy to the host and the unpack launch of the last get / set, each from its own pair of events (ms)
+    float state_ms_pack = 0, state_ms_copy = 0, state_ms_unpack = 0;
+    bool state_timing = false;
+
     int debug_layer_out(int il, float *dst, size_t cap);
     void set_debug_taps(bool on) { debug_taps_ = on; }
     void set_profile(bool on) { profile_ = on; }
@@ -151,6 +166,15 @@ class Context {
     bool alloc_cells(int n, const uint64_t *seqmask, std::vector<int> &out);
     std::vector<int> region_next_;     // per sequence: where its next cell is looked for first
     void apply_k_shift();
+    // state_seq_get / set: a bounded device staging block (at most 64 MiB of portable rows, the cells of a sequence go through it in chunks), the cell list and
+    // the per-layer plane table the two kernels read; allocated on first use, freed with the context
+    uint8_t *d_state_stage_ = nullptr;
+    size_t state_stage_bytes_ = 0;
+    int32_t *d_state_cells_ = nullptr;
+    KVLayerView *d_state_layers_ = nullptr;
+    bool state_prepare();
+    const char *state_refusal() const;
+    size_t state_cell_bytes() const;      // portable bytes of one cell over all layers
     // ---- the layer forward pass: run_layers is the loop (set-up, the whole-step early return, then per layer attention block -> attn_output -> feed-forward
     // block -> tap); each block states its choice of launch form once, and bench_weight_sweep issues a step's mat-vecs through the same functions
     struct Step {                      // what one run_layers call fixes for all its layers (step_constants)

@@ -135,6 +135,8 @@ void LlamaServerContext::Initialize() {    // :244-282
         slots[(size_t)i].Reset();
     }
     b_token_.assign((size_t)n_ctx, 0); b_pos_.assign((size_t)n_ctx, 0); b_seq_.assign((size_t)n_ctx, 0); b_logits_.assign((size_t)n_ctx, 0);
+    // the host-RAM prompt cache: only where it was asked for and the backend can move a sequence's state ("cache_ram" 0: no state call is ever made)
+    if (params.cache_ram_mib != 0 && !prompt_cache_ && be_->state_seq_size(0) != 0) prompt_cache_.reset(new PromptCache(params.cache_ram_mib));
     model_loaded_external = true;
     bgr_thread_ = std::thread(&LlamaServerContext::DoBackgroundTasks, this);
 }
@@ -154,6 +156,50 @@ void LlamaServerContext::ReleaseResources() {   // :366-380
         if (bgr_thread_.joinable()) bgr_thread_.join();
         { std::lock_guard<std::mutex> lk(mutex_results_); }
         condition_results_.notify_all();
+        if (prompt_cache_) prompt_cache_->clear();        // (the loop thread is gone: the stored states go with the model)
+    }
+}
+
+void LlamaServerContext::PromptCacheStats(int64_t out[6]) const {
+    for (int i = 0; i < 6; i++) out[i] = 0;
+    if (prompt_cache_) prompt_cache_->stats(out);
+}
+
+// The slot is about to take a new prompt, and n_past says how much of it the slot's own sequence already holds.  A conversation that lands on a slot which has
+// since served another one would be prefilled from its first token again: its state may be in the store (it was saved when the other conversation arrived).
+void LlamaServerContext::PromptCacheVisit(LlamaClientSlot &slot) {
+    PromptCache &pc = *prompt_cache_;
+    const std::vector<int32_t> &prompt = slot.prompt_tokens;
+    const size_t own = (size_t)slot.n_past;
+    size_t best = 0;
+    int idx = pc.lookup(prompt, best);
+    const bool want_restore = idx >= 0 && best >= own + (size_t)PromptCache::kMinGain;
+    if (want_restore) pc.touch(idx);                       // (the save below must not evict the entry this prompt came for)
+    // save: the prompt keeps `own` of the slot's cached tokens and drops the rest
+    if (slot.cache_tokens.size() >= own + (size_t)PromptCache::kMinSave && !pc.covers(slot.cache_tokens)) {
+        const size_t size = be_->state_seq_size(slot.id);
+        std::vector<uint8_t> blob(size);
+        if (size && be_->state_seq_get(slot.id, blob.data(), blob.size()) == size) pc.store(slot.cache_tokens, std::move(blob));
+    }
+    if (!want_restore) return;
+    idx = pc.lookup(prompt, best);                         // (the store has changed: entries replaced or evicted)
+    if (idx < 0 || best < own + (size_t)PromptCache::kMinGain) return;
+    const PromptCache::Entry &e = pc.entry(idx);
+    const size_t before = be_->state_seq_size(slot.id);
+    if (be_->state_seq_set(slot.id, e.blob.data(), e.blob.size()) == e.blob.size()) {
+        pc.touch(idx);
+        pc.restored(best);
+        slot.cache_tokens = e.tokens;
+        slot.n_past = (int32_t)best;
+        return;
+    }
+    // refused (another geometry, no cells): the entry is of no use, and the slot goes on with its own sequence as if the store had held nothing -
+    // unless the attempt got as far as emptying it
+    pc.drop(idx);
+    if (be_->state_seq_size(slot.id) != before) {
+        be_->kv_seq_rm(slot.id, -1, -1);
+        slot.cache_tokens.clear();
+        slot.n_past = 0;
     }
 }
 
@@ -763,6 +809,7 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
                 } else {
                     for (int32_t t : prompt_tokens) slot.smpl->accept(t, false);
                     slot.n_past = (int32_t)common_part(slot.cache_tokens, prompt_tokens);
+                    if (prompt_cache_ && !slot.embedding) PromptCacheVisit(slot);
                 }
                 if (slot.n_past == slot.num_prompt_tokens && slot.n_past > 0) slot.n_past--;   // evaluate at least one token
                 slot.num_prompt_tokens_processed = 0;

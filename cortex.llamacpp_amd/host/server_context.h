@@ -17,6 +17,7 @@
 
 #include "backend_iface.h"
 #include "json.h"
+#include "prompt_cache.h"
 #include "sampling.h"
 
 namespace mi355 {
@@ -44,6 +45,7 @@ struct ServerParams {            // the subset of common_params the loop reads
     int32_t n_keep = 0;
     int32_t n_parallel = 1;
     bool cont_batching = true;
+    int64_t cache_ram_mib = 0;   // /loadmodel "cache_ram": MiB of host memory for the prompt cache (prompt_cache.h); 0 = off, the loop then makes no state call at all; < 0 = no limit
     std::string model_alias;
     SamplingParams sampling;
 };
@@ -114,6 +116,8 @@ class LlamaServerContext {
     TaskResult NextResult(int task_id);                                                // (:325-352), blocks
     void RequestCancel(int task_id);                                                   // (:354-364)
     void KvCacheClear();
+    // the host-RAM prompt cache's counters (prompt_cache.h: entries, bytes held, saves, restores, tokens restored, evictions); all zero while it is off
+    void PromptCacheStats(int64_t out[6]) const;
 
     // one scheduler tick, exposed for tests (the background thread calls it forever)
     bool UpdateSlots();
@@ -157,6 +161,10 @@ class LlamaServerContext {
   private:
     Json ProbsToJson(const std::vector<CompletionTokenOutput> &probs) const;
     void DoBackgroundTasks();
+    // a new prompt's first visit, behind n_past = common_part(cache_tokens, prompt): saves the slot's sequence when the prompt would drop it, restores a stored
+    // sequence that holds more of the prompt than the slot does (sets cache_tokens and n_past)
+    void PromptCacheVisit(LlamaClientSlot &slot);
+    std::unique_ptr<PromptCache> prompt_cache_;       // null: "cache_ram" 0, or a backend without sequence states
 
     IBackend *be_;
     int id_gen_ = 0;

@@ -205,6 +205,25 @@ MI355_API void    mi355_kv_cache_seq_cp(mi355_context *ctx, mi355_seq_id src, mi
 MI355_API void    mi355_kv_cache_seq_add(mi355_context *ctx, mi355_seq_id seq, mi355_pos p0, mi355_pos p1, mi355_pos delta);
 MI355_API int32_t mi355_kv_cache_used_cells(const mi355_context *ctx);
 
+/* ------------------------------------------------------------------ a sequence's KV state
+ * llama_state_seq_get_size / get_data / set_data and llama_state_seq_save_file / load_file.  The blob is this project's own format, versioned:
+ *   8 little-endian 32-bit words - magic "M5KV", version 1, type_k, type_v, n_layer, n_head_kv, head_dim, n (cells) - then n int32 positions, ascending,
+ *   then per layer K rows [n][n_head_kv * head_dim] and V rows likewise in the ggml layout of the cache type (f16 halves, 34-byte q8_0 / 18-byte q4_0 blocks);
+ *   size = 32 + 4 n + n_layer * n * (row_bytes_k + row_bytes_v).
+ * get_data applies a pending K-shift first and returns the bytes written.  set_data checks the header against the context, removes what dst holds, gives it n
+ * fresh cells (its region's lowest free ones, in position order) and returns the bytes consumed.  0 = refused, mi355_last_error names the field and both
+ * values; a refused set_data leaves dst as it was, or empty - never half-written.  Encoder contexts and the ranks of a row split have no sequence state.
+ * The file: 4 words - magic "M5KF", version 1, n_tokens, 0 - an 8-byte blob length, the tokens, the blob; written to a temporary name and renamed; load_file
+ * checks the file's length against its header before it reads a row.  Both return the file's bytes, 0 = refused. */
+MI355_API size_t mi355_state_seq_get_size(mi355_context *ctx, mi355_seq_id seq);
+MI355_API size_t mi355_state_seq_get_data(mi355_context *ctx, uint8_t *dst, size_t cap, mi355_seq_id seq);
+MI355_API size_t mi355_state_seq_set_data(mi355_context *ctx, const uint8_t *src, size_t len, mi355_seq_id dst);
+MI355_API size_t mi355_state_seq_save_file(mi355_context *ctx, const char *path, mi355_seq_id seq, const mi355_token *tokens, size_t n_tokens);
+MI355_API size_t mi355_state_seq_load_file(mi355_context *ctx, const char *path, mi355_seq_id dst_seq, mi355_token *tokens_out, size_t cap, size_t *n_tokens_out);
+/* measurement aid: the pack launch, the device-to-host copy and the unpack launch of the context's last get_data / set_data, from events of their own (ms);
+ * timing is switched on by the first call and costs a stream synchronisation per launch from then on */
+MI355_API void    mi355_debug_state_seq_timing(mi355_context *ctx, float out_ms[3]);
+
 /* debugging taps for parity tests (enable before decode): residual stream after layer `il` for the last
  * decoded micro-batch, copied to dst[n_tokens * n_embd]; returns n_tokens or < 0 */
 MI355_API void    mi355_debug_enable_taps(mi355_context *ctx, int32_t enabled);
@@ -389,6 +408,14 @@ MI355_API int mi355_op_attn_batch_step(const float *q, const float *k_new, const
 MI355_API int mi355_op_k_shift(int32_t type_k, int32_t n_head_kv, int32_t head_dim, int32_t n_rot, int32_t neox, int32_t n_cells, const int32_t *delta,
                                float rope_base, float freq_scale, const float *freq_factors, float ext_factor, float attn_factor, float corr_lo,
                                float corr_hi, void *k_cache);
+/* The two kernels behind mi355_state_seq_get_data / set_data on their own (test entries): a cache of n_layer layers, each given as ggml-layout rows
+ * k_rows[layer] / v_rows[layer] [n_cells][n_head_kv * head_dim] (layout as above) and uploaded into device planes; cells: n indices in [0, n_cells).
+ * pack: out receives, per layer, the K rows of the listed cells in list order and then their V rows - the row section of a state blob.
+ * unpack: the rows `in` (that layout) are written into the listed cells (all different) and the whole cache comes back in k_rows / v_rows. */
+MI355_API int mi355_op_kv_state_pack(int32_t type_k, int32_t type_v, int32_t n_layer, int32_t n_head_kv, int32_t head_dim, int32_t n_cells,
+                                     const void *const *k_rows, const void *const *v_rows, const int32_t *cells, int32_t n, void *out);
+MI355_API int mi355_op_kv_state_unpack(int32_t type_k, int32_t type_v, int32_t n_layer, int32_t n_head_kv, int32_t head_dim, int32_t n_cells, const void *in,
+                                       const int32_t *cells, int32_t n, void *const *k_rows, void *const *v_rows);
 
 /* ------------------------------------------------------------------ tokenizer
  * llama_tokenize / llama_token_to_piece as reached through common_tokenize / common_token_to_piece
@@ -424,6 +451,10 @@ MI355_API void mi355_engine_handle_chat_completion(mi355_engine *e, const char *
 MI355_API void mi355_engine_handle_embedding(mi355_engine *e, const char *body_json, mi355_engine_callback cb, void *user);
 MI355_API int32_t mi355_engine_is_supported(mi355_engine *e, const char *feature);
 MI355_API void mi355_engine_stop_inferencing(mi355_engine *e, const char *model_id);
+/* The host-RAM prompt cache of a model loaded with "cache_ram": N (MiB of host memory; 0 / absent = off, negative = no limit; upstream's --cache-ram): KV states of
+   conversations that lost their slot, restored when their prompt comes back.  out: entries, bytes held, saves, restores, tokens restored, evictions - all zero
+   while the cache is off.  < 0: no such model. */
+MI355_API int mi355_engine_prompt_cache_stats(mi355_engine *e, const char *model_id, int64_t out[6]);
 /* EngineI::Load(EngineLoadOption) / Unload(EngineUnloadOption) (base/cortex-common/enginei.h:14-35; LlamaEngine: src/llama_engine.cc:289-303): Load =
    SetFileLogger(max_log_lines, log_path) + SetLogLevel(log_level).  Paths as UTF-8 strings (std::filesystem::path::string()), log_level = the value of
    trantor::Logger::LogLevel (kTrace 0, kDebug 1, kInfo 2, kWarn 3, kError 4, kFatal 5). */
