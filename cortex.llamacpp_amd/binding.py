@@ -78,6 +78,9 @@ SYMBOLS = {
     "mi355_greedy_steps": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp]),
     "mi355_get_logits_ith": (C.POINTER(C.c_float), [_vp, _i32]),
     "mi355_get_argmax_ith": (_i32, [_vp, _i32]),
+    "mi355_get_argmax_prob_ith": (_i32, [_vp, _i32, _vp]),
+    "mi355_spec_verify": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "mi355_speculative_steps": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "mi355_get_topk_ith": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "mi355_debug_mega_steps": (C.c_int64, [_vp]),
     "mi355_debug_engine_steps": (C.c_int64, [_vp]),
@@ -127,6 +130,8 @@ SYMBOLS = {
     "mi355_op_moe_route": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
     "mi355_op_moe_router": (C.c_int, [_i32, _vp, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mi355_op_argmax_rows": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp]),
+    "mi355_op_argmax_prob_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
+    "mi355_op_spec_verify": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "mi355_op_topk_rows": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_moe_group": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_moe_gather_act": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -172,6 +177,7 @@ SYMBOLS = {
     "mi355_engine_is_supported": (_i32, [_vp, _cp]),
     "mi355_engine_stop_inferencing": (None, [_vp, _cp]),
     "mi355_engine_prompt_cache_stats": (C.c_int, [_vp, _cp, _vp]),
+    "mi355_engine_spec_stats": (C.c_int, [_vp, _cp, _vp]),
     "mi355_engine_load": (None, [_vp, _cp, _cp, _i32, _cp, _i32, _i32]),
     "mi355_engine_unload": (None, [_vp]),
     "mi355_engine_set_file_logger": (None, [_vp, _i32, _cp]),
@@ -426,6 +432,28 @@ class Backend:
         out = np.full(x.shape[0], -1, np.int32)
         self._chk(self.lib.mi355_op_argmax_rows(_ptr(x), x.shape[1], _ptr(la), la.size, cap, _ptr(out)), "op_argmax_rows")
         return out
+
+    def argmax_prob_rows(self, x: np.ndarray):
+        """(arg-max int32 [rows], its softmax probability f32 [rows]) of x [rows][n] (mi355_op_argmax_prob_rows)."""
+        x = np.ascontiguousarray(x, np.float32)
+        x = x.reshape(1, -1) if x.ndim == 1 else x
+        idx = np.full(x.shape[0], -1, np.int32); p = np.full(x.shape[0], -1.0, np.float32)
+        self._chk(self.lib.mi355_op_argmax_prob_rows(_ptr(x), x.shape[1], x.shape[0], _ptr(idx), _ptr(p)), "op_argmax_prob_rows")
+        return idx, p
+
+    def spec_verify(self, logits: np.ndarray, rows, group_start, draft):
+        """Greedy acceptance (mi355_op_spec_verify): launch row r = logits[rows[r]]; group g owns launch rows group_start[g] .. group_start[g + 1] - 1; draft
+        runs parallel to the launch rows.  Returns (ids int32 [R], n_accept int32 [G])."""
+        logits = np.ascontiguousarray(logits, np.float32)
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        gs = np.ascontiguousarray(group_start, np.int32).reshape(-1)
+        draft = np.ascontiguousarray(draft, np.int32).reshape(-1)
+        R, G = rows.size, gs.size - 1
+        assert draft.size == R
+        ids = np.full(R, -1, np.int32); acc = np.full(max(G, 1), -1, np.int32)
+        self._chk(self.lib.mi355_op_spec_verify(_ptr(logits), logits.shape[1], logits.shape[0], _ptr(rows), R, _ptr(gs), G, _ptr(draft), _ptr(ids), _ptr(acc)),
+                  "op_spec_verify")
+        return ids, acc[:G]
 
     @staticmethod
     def topk_decode(keys: np.ndarray):
@@ -1016,6 +1044,39 @@ class Context:
     def argmax(self, i: int = -1) -> int:
         return int(self.lib.mi355_get_argmax_ith(self.h, i))
 
+    def argmax_prob(self, i: int = -1):
+        """(arg-max token, its softmax probability over the whole vocabulary) of batch row i, from the device logits (mi355_get_argmax_prob_ith)."""
+        p = C.c_float(0.0)
+        t = int(self.lib.mi355_get_argmax_prob_ith(self.h, i, C.byref(p)))
+        if t < 0:
+            raise MI355Error(f"mi355_get_argmax_prob_ith failed: {_err(self.lib)}")
+        return t, float(p.value)
+
+    def spec_verify(self, group_start, draft):
+        """Greedy acceptance over the last decode's rows (mi355_spec_verify): group g owns batch rows group_start[g] .. group_start[g + 1] - 1, all flagged; draft
+        runs parallel to them (a group's last entry is ignored).  Returns (ids int32 [R], n_accept int32 [G])."""
+        gs = np.ascontiguousarray(group_start, np.int32).reshape(-1)
+        draft = np.ascontiguousarray(draft, np.int32).reshape(-1)
+        G = gs.size - 1
+        R = int(gs[-1] - gs[0]) if G >= 1 else 0
+        if G < 1 or R < 1 or draft.size != R:
+            raise ValueError("spec_verify: group_start [G + 1] and draft [R] with R = group_start[G] - group_start[0]")
+        ids = np.full(R, -1, np.int32); acc = np.full(G, -1, np.int32)
+        r = self.lib.mi355_spec_verify(self.h, G, _ptr(gs), _ptr(draft), _ptr(ids), _ptr(acc))
+        if r != R:
+            raise MI355Error(f"mi355_spec_verify failed: {_err(self.lib)}")
+        return ids, acc
+
+    def speculative_steps(self, draft_ctx: "Context", first: int, pos0: int, n: int, n_max: int = 16, n_min: int = 0, p_min: float = 0.75, seq: int = 0):
+        """n greedy tokens with draft_ctx's model drafting up to n_max per round (mi355_speculative_steps); both contexts hold `seq` over [0, pos0).
+        Returns (tokens int32 [n], stats int64 [4]: rounds, drafted, accepted, plain steps)."""
+        out = np.empty(n, np.int32); stats = np.zeros(4, np.int64)
+        done = self.lib.mi355_speculative_steps(self.h, draft_ctx.h, int(first), int(pos0), int(seq), int(n), int(n_max), int(n_min), float(p_min),
+                                                out.ctypes.data, stats.ctypes.data)
+        if done != n:
+            raise MI355Error(f"mi355_speculative_steps stopped after {done} of {n}: {_err(self.lib)}")
+        return out, stats
+
     def mega_steps(self) -> int:
         """Single-token steps that ran as one whole-step launch (diagnosis)."""
         return int(self.lib.mi355_debug_mega_steps(self.h))
@@ -1202,6 +1263,14 @@ class Engine:
         if rc < 0:
             raise MI355Error(f"mi355_engine_prompt_cache_stats failed ({rc}): {_err(self.lib)}")
         return dict(zip(("entries", "bytes", "saves", "restores", "tokens_restored", "evictions"), (int(v) for v in out)))
+
+    def spec_stats(self, model_id: str) -> dict:
+        """The speculative-decoding counters of a model loaded with "model_draft"."""
+        out = (C.c_int64 * 4)()
+        rc = self.lib.mi355_engine_spec_stats(self.h, model_id.encode(), out)
+        if rc < 0:
+            raise MI355Error(f"mi355_engine_spec_stats failed ({rc}): {_err(self.lib)}")
+        return dict(zip(("rounds", "drafted", "accepted", "plain_steps"), (int(v) for v in out)))
 
     def stop_inferencing(self, model_id: str) -> None:
         self.lib.mi355_engine_stop_inferencing(self.h, model_id.encode())

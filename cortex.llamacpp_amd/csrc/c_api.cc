@@ -246,6 +246,113 @@ float *mi355_get_logits_ith(mi355_context *ctx, int32_t i) {
     return p;
 }
 int32_t mi355_get_argmax_ith(mi355_context *ctx, int32_t i) { return ctx->c->argmax_ith(i); }
+
+// ---- speculative decoding: the device-side decisions (csrc/spec.hip) and the round built on them
+static int no_context(const char *what) {
+    if (!g_backend_ok && mi355_backend_init() != MI355_OK) return MI355_ERR_NO_DEVICE;
+    fail(std::string(what) + ": null context or argument");
+    return MI355_ERR_ARG;
+}
+int32_t mi355_get_argmax_prob_ith(mi355_context *ctx, int32_t i, float *p) {
+    if (!ctx) return no_context("get_argmax_prob_ith");
+    MI355_GUARD(return MI355_ERR_ARG,
+        const int32_t t = ctx->c->argmax_prob_ith(i, p);
+        if (t < 0) fail(ctx->c->last_error.empty() ? "arg-max failed" : ctx->c->last_error);
+        return t;
+    )
+}
+int32_t mi355_spec_verify(mi355_context *ctx, int32_t n_groups, const int32_t *group_start, const mi355_token *draft, mi355_token *ids_out, int32_t *n_accept_out) {
+    if (!ctx) return no_context("spec_verify");
+    MI355_GUARD(return MI355_ERR_ARG,
+        const int r = ctx->c->spec_verify(n_groups, group_start, draft, ids_out, n_accept_out);
+        if (r < 0) { fail(ctx->c->last_error.empty() ? "spec_verify failed" : ctx->c->last_error); return MI355_ERR_ARG; }
+        return r;
+    )
+}
+// The greedy loop with a draft model beside the target (the round: DESIGN.md §4.9).  `p` is the position of `last`, the newest emitted token, which neither
+// context has decoded yet; the draft context holds [0, dpos) and `pend` is what it has still to see (positions dpos .. p).
+int32_t mi355_speculative_steps(mi355_context *ctx_tgt, mi355_context *ctx_dft, mi355_token first, mi355_pos pos0, mi355_seq_id seq, int32_t n, int32_t n_max,
+                                int32_t n_min, float p_min, mi355_token *out_tokens, int64_t *stats) {
+    if (!ctx_tgt || !ctx_dft) return no_context("speculative_steps");
+    if (n < 0 || pos0 < 0 || n_max < 1 || n_max > SPEC_MAX_DRAFT || n_min < 0 || ctx_tgt == ctx_dft) {
+        fail("speculative_steps: n >= 0, pos0 >= 0, 1 <= n_max <= 16, n_min >= 0 and two different contexts"); return MI355_ERR_ARG;
+    }
+    if (ctx_tgt->c->model->hp.n_vocab != ctx_dft->c->model->hp.n_vocab) { fail("speculative_steps: the two models have different vocabulary sizes"); return MI355_ERR_ARG; }
+    MI355_GUARD(return MI355_ERR_ARG,
+        Context *T = ctx_tgt->c, *D = ctx_dft->c;
+        int64_t st[4] = {0, 0, 0, 0};                                  // rounds, drafted, accepted, plain steps
+        if (stats) memcpy(stats, st, sizeof st);
+        int32_t sid = seq;
+        int32_t *sp = &sid;
+        int32_t n_seq[SPEC_MAX_DRAFT + 2], pos[SPEC_MAX_DRAFT + 2], toks[SPEC_MAX_DRAFT + 2], ids[SPEC_MAX_DRAFT + 1], draft[SPEC_MAX_DRAFT + 1];
+        int32_t *seqs[SPEC_MAX_DRAFT + 2];
+        int8_t flags[SPEC_MAX_DRAFT + 2];
+        for (int j = 0; j < SPEC_MAX_DRAFT + 2; j++) { n_seq[j] = 1; seqs[j] = sp; }
+        auto decode = [&](Context *c, int cnt, bool all_rows) -> bool {
+            for (int j = 0; j < cnt; j++) flags[j] = all_rows || j == cnt - 1;
+            const int rc = c->decode(cnt, toks, pos, n_seq, seqs, flags);
+            if (rc != 0) fail(rc < 0 ? c->last_error : std::string("speculative_steps: no KV cells left for the batch"));
+            return rc == 0;
+        };
+        const int room = (int)std::min(T->cp.n_ctx / T->cp.n_seq_max, D->cp.n_ctx / D->cp.n_seq_max);
+        std::vector<int32_t> pend;
+        int32_t last = first, p = pos0, dpos = pos0, done = 0;
+        while (done < n) {
+            const int k_cap = std::max(0, std::min((int)n_max, room - p - 1));
+            int k = 0;
+            pend.push_back(last);                                      // positions dpos .. p
+            if (k_cap > 0) {
+                // 1. the draft context catches up; 2. it drafts while it is sure enough
+                if (pend.size() > (size_t)SPEC_MAX_DRAFT + 2) { fail("speculative_steps: the draft context fell behind"); break; }
+                for (size_t j = 0; j < pend.size(); j++) { toks[j] = pend[j]; pos[j] = dpos + (int32_t)j; }
+                if (!decode(D, (int)pend.size(), false)) break;
+                dpos = p + 1;
+                pend.clear();
+                bool bad = false;
+                for (;;) {
+                    float pr = 0.0f;
+                    const int32_t t = D->argmax_prob_ith(-1, &pr);
+                    if (t < 0) { fail(D->last_error); bad = true; break; }
+                    if (pr < p_min) break;
+                    draft[k++] = t;
+                    if (k == k_cap) break;
+                    toks[0] = t; pos[0] = dpos;
+                    if (!decode(D, 1, false)) { bad = true; break; }
+                    dpos++;
+                }
+                if (bad) break;
+                if (k < n_min) k = 0;                                  // 3. too short a draft is not worth a batch
+            }
+            // 4. the target decodes the last token and the drafts as one batch, every row flagged
+            int a = 0;
+            toks[0] = last; pos[0] = p;
+            for (int j = 0; j < k; j++) { toks[j + 1] = draft[j]; pos[j + 1] = p + 1 + j; }
+            if (!decode(T, k + 1, true)) break;
+            if (k > 0) {
+                const int32_t gs[2] = {0, k + 1};
+                draft[k] = -1;
+                if (T->spec_verify(1, gs, draft, ids, &a) < 0) { fail(T->last_error); break; }
+            } else {
+                ids[0] = T->argmax_ith(0);
+                if (ids[0] < 0) { fail(T->last_error.empty() ? "arg-max failed" : T->last_error); break; }
+                st[3]++;
+            }
+            // 5. emit ids[0 .. a], cut at n; 6. both caches keep what was emitted and nothing behind it
+            const int m = std::min(a + 1, (int)(n - done));
+            st[0]++; st[1] += k; st[2] += m - 1;                      // accepted: the drafts that were emitted (the cut of the last round takes its share)
+            for (int j = 0; j < m; j++) if (out_tokens) out_tokens[done + j] = ids[j];
+            done += m;
+            const int32_t keep = p + m;                                // the new last token's position: not decoded anywhere yet
+            if (k + 1 > m) T->kv_seq_rm(seq, keep, -1);               // (a context that holds nothing there is left alone: its cell table stays clean)
+            if (dpos > keep) { D->kv_seq_rm(seq, keep, -1); dpos = keep; }
+            for (int32_t q = dpos + (int32_t)pend.size(); q < keep; q++) pend.push_back(q == p ? last : ids[q - p - 1]);     // accepted drafts the draft context has not decoded
+            last = ids[m - 1];
+            p = keep;
+        }
+        if (stats) memcpy(stats, st, sizeof st);
+        return done;
+    )
+}
 int32_t mi355_get_topk_ith(mi355_context *ctx, int32_t i, int32_t k, int32_t n_adj, const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_count,
                            float penalty_repeat, float penalty_freq, float penalty_present, int32_t *toks_out, float *logits_out) {
     if (!ctx || !toks_out || !logits_out || n_adj < 0 || n_adj > TOPK_MAX_ADJ || (n_adj > 0 && (!adj_tok || !adj_bias || !adj_count))) { fail("bad arguments"); return -1; }
@@ -1214,6 +1321,40 @@ int mi355_op_argmax_rows(const float *x, int64_t n, const int32_t *launches, int
     return dout.down(out, rows * 4) ? MI355_OK : MI355_ERR_HIP;
 }
 
+int mi355_op_argmax_prob_rows(const float *x, int64_t n, int32_t rows, int32_t *idx_out, float *p_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!x || !idx_out || !p_out || n < 1 || n > SPEC_MAX_N || rows < 1 || rows > 65535) { fail("argmax_prob_rows: bad shape"); return MI355_ERR_ARG; }
+    const size_t nb = (size_t)rows * (size_t)n * 4;
+    DevBuf dx(nb), di((size_t)rows * 4), dp((size_t)rows * 4), ds(argmax_prob_scratch_words(rows) * 4);
+    if (!dx.up(x, nb) || !di.p || !dp.p || !ds.p) return MI355_ERR_OOM;
+    hipError_t e = launch_argmax_prob_rows(dx.as<float>(), (int)n, nullptr, rows, di.as<int32_t>(), dp.as<float>(), ds.as<float>(), rows, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "argmax_prob_rows");
+    return di.down(idx_out, (size_t)rows * 4) && dp.down(p_out, (size_t)rows * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t R, const int32_t *group_start, int32_t G,
+                         const int32_t *draft, int32_t *ids_out, int32_t *n_accept_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!logits || !rows || !group_start || !draft || !ids_out || !n_accept_out || n < 1 || n > SPEC_MAX_N || n_base_rows < 1 || R < 1 || R > SPEC_MAX_ROWS || G < 1 ||
+        G > SPEC_MAX_GROUPS) { fail("spec_verify: bad shape (R <= 1088, G <= 64)"); return MI355_ERR_ARG; }
+    for (int r = 0; r < R; r++)
+        if (rows[r] < 0 || rows[r] >= n_base_rows) { fail("spec_verify: rows[" + std::to_string(r) + "] outside the base"); return MI355_ERR_ARG; }
+    if (group_start[0] != 0 || group_start[G] != R) { fail("spec_verify: the groups do not cover rows 0 .. R - 1"); return MI355_ERR_ARG; }
+    for (int g = 0; g < G; g++) {
+        const int k1 = group_start[g + 1] - group_start[g];
+        if (k1 < 1 || k1 > SPEC_MAX_DRAFT + 1) { fail("spec_verify: group " + std::to_string(g) + " outside 1 .. 17 rows"); return MI355_ERR_ARG; }
+    }
+    const size_t nb = (size_t)n_base_rows * (size_t)n * 4;
+    DevBuf db(nb), dr((size_t)R * 4), dg((size_t)(G + 1) * 4), dd((size_t)R * 4), di((size_t)R * 4), da((size_t)G * 4), ds(spec_verify_scratch_words(R) * 4);
+    if (!db.up(logits, nb) || !dr.up(rows, (size_t)R * 4) || !dg.up(group_start, (size_t)(G + 1) * 4) || !dd.up(draft, (size_t)R * 4) || !di.p || !da.p || !ds.p) return MI355_ERR_OOM;
+    hipError_t e = launch_spec_verify(db.as<float>(), (int)n, dr.as<int32_t>(), R, dg.as<int32_t>(), G, dd.as<int32_t>(), di.as<int32_t>(), da.as<int32_t>(), ds.as<float>(), R,
+                                      nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "spec_verify");
+    return di.down(ids_out, (size_t)R * 4) && da.down(n_accept_out, (size_t)G * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
 int mi355_op_topk_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t n_rows, int32_t k, const int32_t *adj_n,
                        const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_cnt, const float *repeat, const float *freq, const float *present,
                        uint64_t *keys_out) {
@@ -1989,6 +2130,13 @@ int mi355_engine_prompt_cache_stats(mi355_engine *e, const char *model_id, int64
     if (!e || !model_id || !out) { fail("prompt_cache_stats: null argument"); return MI355_ERR_ARG; }
     MI355_GUARD(return MI355_ERR_ARG,
         if (!e->eng.PromptCacheStats(model_id, out)) { fail(std::string("prompt_cache_stats: no model ") + model_id); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
+int mi355_engine_spec_stats(mi355_engine *e, const char *model_id, int64_t out[4]) {
+    if (!e || !model_id || !out) { fail("spec_stats: null argument"); return MI355_ERR_ARG; }
+    MI355_GUARD(return MI355_ERR_ARG,
+        if (!e->eng.SpecStats(model_id, out)) { fail(std::string("spec_stats: no model ") + model_id); return MI355_ERR_ARG; }
         return MI355_OK;
     )
 }

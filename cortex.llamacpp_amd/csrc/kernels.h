@@ -213,6 +213,20 @@ hipError_t launch_get_rows(int type, const uint8_t *table_dev, int64_t K, const 
 // out[row] = the lowest index of the row's largest value; a NaN entry never wins, and a row with no comparable entry (every value NaN) gives 0.
 // scratch: cap_rows * 129 words, zero-filled once: [cap_rows ticket words | cap_rows * 64 part values | cap_rows * 64 part indices]; rows <= cap_rows
 hipError_t launch_argmax_rows(const float *x, int n, int rows, int32_t *out, float *scratch, int cap_rows, hipStream_t st);
+// ---- speculative decoding (spec.hip): the per-round decisions without a logits row on the host.  Both share launch_argmax_rows' index rule.
+constexpr int SPEC_MAX_ROWS = 64 * 17, SPEC_MAX_GROUPS = 64, SPEC_MAX_DRAFT = 16, SPEC_MAX_N = 1 << 30;
+// idx_out[r], p_out[r]: the arg-max of row r of the launch (base row rows_dev[r]; rows_dev == nullptr: row r) and its softmax probability
+// 1 / sum_j exp(x_j - max) over the non-NaN entries (f32, a fixed summation order: the same bits run to run); p = 0 where the maximum is not finite.
+// scratch: argmax_prob_scratch_words(cap_rows) words, zero-filled once (ticket words at the head)
+size_t argmax_prob_scratch_words(int cap_rows);
+hipError_t launch_argmax_prob_rows(const float *x, int n, const int32_t *rows_dev, int rows, int32_t *idx_out, float *p_out, float *scratch, int cap_rows,
+                                   hipStream_t st);
+// ids_out[r]: the arg-max of base row rows_dev[r], r < R <= SPEC_MAX_ROWS; n_accept_out[g], g < G <= SPEC_MAX_GROUPS: how many leading rows j of group g
+// (rows group_start_dev[g] .. group_start_dev[g + 1] - 1, the last one excepted) have ids[j] == draft_dev[j].  One launch.
+// scratch: spec_verify_scratch_words(cap_rows) words, zero-filled once
+size_t spec_verify_scratch_words(int cap_rows);
+hipError_t launch_spec_verify(const float *base, int n, const int32_t *rows_dev, int R, const int32_t *group_start_dev, int G, const int32_t *draft_dev,
+                              int32_t *ids_out, int32_t *n_accept_out, float *scratch, int cap_rows, hipStream_t st);
 // ---- device-side sampling front end (reference call site common_sampler_sample, src/llama_server_context.cc:1679-1698): the k best
 // candidates of a logits row after logit_bias and the repetition / frequency / presence penalties, so that k (token, logit) pairs cross to the host
 // instead of the 513 KB row.  Order = the host sampler's (host/sampling.cc `better`): higher logit first, lower token id on ties; -0.0 and +0.0 tie

@@ -618,8 +618,9 @@ def weight_bytes_per_token(cfg: LlamaConfig, ftype: str) -> int:
 
 
 def write_synthetic_llama(path: str, cfg: LlamaConfig | str, ftype: str = "q4_k_m", seed: int = 0xC0FFEE,
-                          with_vocab: bool = True, gain: float = 1.0) -> int:
-    """Write a synthetic llama-arch GGUF; returns the file size in bytes."""
+                          with_vocab: bool = True, gain: float = 1.0, blocks=None) -> int:
+    """Write a synthetic llama-arch GGUF; returns the file size in bytes.  blocks (optional): a callable (rng, type, n_elems, std) -> raw bytes that takes
+    random_blocks' place for the 2-D weights, e.g. to write a second file whose weights are a coarser rounding of this one's (a draft model for a target)."""
     if isinstance(cfg, str):
         cfg = CONFIGS[cfg]
     w = GGUFWriter()
@@ -730,9 +731,10 @@ def write_synthetic_llama(path: str, cfg: LlamaConfig | str, ftype: str = "q4_k_
                 return rng.uniform(0.25, 2.0, size=n).astype("<f4").view(np.uint8)
             if len(ne) == 1:  # norm weights
                 return rng.uniform(0.9, 1.1, size=n).astype("<f4").view(np.uint8)
+            draw = blocks or random_blocks
             if name == "token_embd.weight":
-                return random_blocks(rng, t, n, 1.0)
-            return random_blocks(rng, t, n, gain / np.sqrt(fan_in))
+                return draw(rng, t, n, 1.0)
+            return draw(rng, t, n, gain / np.sqrt(fan_in))
 
         w.add_tensor(name, ne, t, gen)
     return w.write(path)

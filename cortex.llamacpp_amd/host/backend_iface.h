@@ -60,6 +60,23 @@ class IBackend {
             r.ok = topk_ith(r.i, r.k, r.tok, r.bias, r.cnt, r.repeat, r.freq, r.present, r.out_tok.data(), r.out_logit.data()) == r.k;
         }
     }
+    // ---- speculative decoding: a draft model beside this one (/loadmodel "model_draft").  The defaults are a backend without one.
+    virtual bool has_draft() const { return false; }
+    // The draft model's proposal for what follows tokens[0 .. n_tokens) of sequence seq.  The backend remembers what its draft context holds per sequence: it
+    // keeps the common prefix, removes the rest, ingests the missing tokens as one batch and drafts greedily until n_max tokens or the first one whose
+    // probability is below p_min (not drafted).  Returns the number written to out [n_max] (0: nothing to propose, or the draft failed).
+    virtual int spec_draft(int seq, const int32_t *tokens, int n_tokens, int n_max, float p_min, int32_t *out) {
+        (void)seq; (void)tokens; (void)n_tokens; (void)n_max; (void)p_min; (void)out;
+        return 0;
+    }
+    // Greedy acceptance over rows of the last decode: group g owns batch rows group_start[g] .. group_start[g + 1] - 1 (adjacent groups, every row flagged;
+    // k_g drafted tokens -> k_g + 1 rows); draft [R] runs parallel to the rows.  ids [R]: each row's arg-max; n_accept [n_groups].  false: no such front end.
+    virtual bool spec_verify(int n_groups, const int32_t *group_start, const int32_t *draft, int32_t *ids, int32_t *n_accept) {
+        (void)n_groups; (void)group_start; (void)draft; (void)ids; (void)n_accept;
+        return false;
+    }
+    // the draft context forgets positions >= p0 of sequence seq (the roll-back of a round; the end of a request)
+    virtual void draft_seq_rm(int seq, int p0) { (void)seq; (void)p0; }
     virtual int topk_max_k() const { return 0; }      // 0: no device front end
     virtual int topk_max_adj() const { return 0; }
     // llama_set_embeddings / llama_get_embeddings_ith (llama_server_context.cc:299, 1042-1044)

@@ -207,6 +207,10 @@ bool LlamaEngine::LoadModelImpl(const Json &body, std::string &err) {   // :547-
         log_line(LOG_WARN, "cache_ram: this backend has no sequence state (a row-split or an embedding model): the prompt cache is off");
         sp.cache_ram_mib = 0;
     }
+    // "model_draft" (the backend factory loads it): how far the draft model runs ahead - upstream's --draft-max / --draft-min / --draft-p-min
+    sp.draft_max = std::min(16, std::max(1, body.value<int>("draft_max", 16)));
+    sp.draft_min = std::max(0, body.value<int>("draft_min", 0));
+    sp.draft_p_min = body.value<float>("draft_p_min", 0.75f);
     si->user_prompt = body.value<std::string>("user_prompt", "USER: ");       // :662-669
     si->ai_prompt = body.value<std::string>("ai_prompt", "ASSISTANT: ");
     si->system_prompt = body.value<std::string>("system_prompt", "ASSISTANT's RULE: ");
@@ -297,6 +301,14 @@ bool LlamaEngine::CheckModelLoaded(const Callback &cb, const std::string &model_
 void LlamaEngine::StopInferencing(const std::string &model_id) {   // :502-508
     std::lock_guard<std::mutex> lk(stop_mutex_);
     force_stop_.insert(model_id);
+}
+
+bool LlamaEngine::SpecStats(const std::string &model_id, int64_t out[4]) {
+    std::lock_guard<std::mutex> lk(map_mutex_);
+    auto it = server_map_.find(model_id);
+    if (it == server_map_.end() || !it->second->ctx) return false;
+    it->second->ctx->SpecStats(out);
+    return true;
 }
 
 bool LlamaEngine::PromptCacheStats(const std::string &model_id, int64_t out[6]) {

@@ -56,6 +56,7 @@ class LlamaEngine {
     void StopInferencing(const std::string &model_id);
     // the counters of a loaded model's host-RAM prompt cache (load key "cache_ram"; prompt_cache.h); false: no such model
     bool PromptCacheStats(const std::string &model_id, int64_t out[6]);
+    bool SpecStats(const std::string &model_id, int64_t out[4]);      // speculative decoding of a model loaded with "model_draft": rounds, drafted, accepted, plain steps
     // enginei.h:14-35: EngineLoadOption {engine_path, deps_path, is_custom_engine_path, log_path, max_log_lines, log_level} / Load / Unload, and
     // SetFileLogger / SetLogLevel (:69-71), as LlamaEngine implements them (llama_engine.cc:289-303, 502-548): Load = SetFileLogger + SetLogLevel
     struct EngineLoadOption { std::string engine_path, deps_path, log_path; bool is_custom_engine_path = false; int max_log_lines = 0; int log_level = 2; };

@@ -26,7 +26,7 @@ class HipBackend : public IBackend {
   public:
     HipBackend(std::unique_ptr<Model> m, std::unique_ptr<Context> c, Vocab v, bool device_sampling)
         : model_(std::move(m)), ctx_(std::move(c)), vocab_(std::move(v)), device_sampling_(device_sampling) {}
-    ~HipBackend() override { ctx_.reset(); model_.reset(); }
+    ~HipBackend() override { dctx_.reset(); dmodel_.reset(); ctx_.reset(); model_.reset(); }
 
     int n_ctx() const override { return (int)ctx_->cp.n_ctx; }
     int n_batch() const override { return (int)ctx_->cp.n_batch; }
@@ -43,6 +43,50 @@ class HipBackend : public IBackend {
         return ctx_->decode(b.n_tokens, b.token, b.pos, n_seq_id_.data(), seq_ptr_.data(), b.logits);
     }
     void set_clip(std::unique_ptr<ClipModel> c) { clip_ = std::move(c); }
+    // ---- the draft model of a speculating server ("model_draft"): its own context, logits left on the device
+    void set_draft(std::unique_ptr<Model> m, std::unique_ptr<Context> c) { dmodel_ = std::move(m); dctx_ = std::move(c); }
+    bool has_draft() const override { return dctx_ != nullptr; }
+    int spec_draft(int seq, const int32_t *tokens, int n_tokens, int n_max, float p_min, int32_t *out) override {
+        if (!dctx_ || n_tokens < 1 || n_max < 1 || seq < 0 || seq >= 64) return 0;
+        std::vector<int32_t> &held = draft_held_[(size_t)seq];
+        size_t common = 0;
+        while (common < held.size() && common < (size_t)n_tokens && held[common] == tokens[common]) common++;
+        if (common == (size_t)n_tokens) common--;                       // the last token is decoded again: its logits are what the draft starts from
+        if (common < held.size()) { dctx_->kv_seq_rm(seq, (int)common, -1); held.resize(common); }
+        auto fail = [&]() { dctx_->kv_seq_rm(seq, -1, -1); held.clear(); return 0; };
+        int32_t sid = seq, *sp = &sid;
+        const int nb = (int)dctx_->cp.n_batch;
+        for (int i0 = (int)common; i0 < n_tokens; i0 += nb) {            // the missing tokens, one batch (cut at n_batch), the last row flagged
+            const int n = std::min(nb, n_tokens - i0);
+            d_pos_.resize((size_t)n); d_nseq_.assign((size_t)n, 1); d_seqp_.assign((size_t)n, sp); d_flags_.assign((size_t)n, 0);
+            for (int j = 0; j < n; j++) d_pos_[(size_t)j] = i0 + j;
+            d_flags_[(size_t)n - 1] = 1;
+            if (dctx_->decode(n, tokens + i0, d_pos_.data(), d_nseq_.data(), d_seqp_.data(), d_flags_.data()) != 0) return fail();
+        }
+        held.assign(tokens, tokens + n_tokens);
+        int k = 0;
+        for (;;) {
+            float p = 0.0f;
+            const int32_t t = dctx_->argmax_prob_ith(-1, &p);
+            if (t < 0) return fail();
+            if (p < p_min) break;
+            out[k++] = t;
+            if (k == n_max) break;
+            int32_t pos = (int32_t)held.size(), one = 1;
+            const int8_t flag = 1;
+            if (dctx_->decode(1, &t, &pos, &one, &sp, &flag) != 0) return fail();
+            held.push_back(t);
+        }
+        return k;
+    }
+    bool spec_verify(int n_groups, const int32_t *group_start, const int32_t *draft, int32_t *ids, int32_t *n_accept) override {
+        return ctx_->spec_verify(n_groups, group_start, draft, ids, n_accept) > 0;
+    }
+    void draft_seq_rm(int seq, int p0) override {
+        if (!dctx_ || seq < 0 || seq >= 64 || p0 < 0) return;
+        std::vector<int32_t> &held = draft_held_[(size_t)seq];
+        if (held.size() > (size_t)p0) { dctx_->kv_seq_rm(seq, p0, -1); held.resize((size_t)p0); }
+    }
     bool multimodal() const override { return clip_ != nullptr; }
     // (the bytes are a request's: whatever goes wrong with them - a picture too large to hold included - is that request's error, not the loop thread's end)
     // (the picture decoded here is kept for image_embed: a request's image is checked when the request arrives and embedded when its slot first visits the
@@ -116,7 +160,10 @@ class HipBackend : public IBackend {
     bool is_encoder() const override { return model_->hp.encoder; }
     void set_embeddings(bool on) override { ctx_->embeddings_enabled = on || ctx_->model->hp.encoder; }
     const float *embeddings_ith(int i) override { return ctx_->embeddings_ith(i); }
-    void kv_clear() override { ctx_->kv_clear(); }
+    void kv_clear() override {
+        ctx_->kv_clear();
+        if (dctx_) { dctx_->kv_clear(); for (auto &h : draft_held_) h.clear(); }
+    }
     bool kv_seq_rm(int seq, int p0, int p1) override { return ctx_->kv_seq_rm(seq, p0, p1); }
     void kv_seq_add(int seq, int p0, int p1, int delta) override { ctx_->kv_seq_add(seq, p0, p1, delta); }
     void kv_seq_cp(int src, int dst, int p0, int p1) override { ctx_->kv_seq_cp(src, dst, p0, p1); }
@@ -150,6 +197,12 @@ class HipBackend : public IBackend {
     size_t decoded_bytes_ = 0;
     std::unique_ptr<Model> model_;
     std::unique_ptr<Context> ctx_;
+    std::unique_ptr<Model> dmodel_;                     // the draft model and its one context (n_seq_max, ctx_len and cache type of the target's)
+    std::unique_ptr<Context> dctx_;
+    std::vector<int32_t> draft_held_[64];               // per sequence: the tokens the draft context holds, positions 0 ..
+    std::vector<int32_t> d_pos_, d_nseq_;
+    std::vector<int32_t *> d_seqp_;
+    std::vector<int8_t> d_flags_;
     Vocab vocab_;
     bool device_sampling_ = true;
     std::unique_ptr<ClipModel> clip_;
@@ -176,6 +229,8 @@ std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, 
     // with params.lora_adapters).  The ranks of a row split hold slices of the base tensors: refused by name.
     const Json &lora = body["lora"];
     if (!lora.is_null() && tp_split_requested(body)) { err = "lora: adapters are not supported with \"split_mode\": \"row\" (load the model on one device)"; return nullptr; }
+    if (!body["model_draft"].is_null() && !body["mmproj"].is_null()) { err = "model_draft: speculative decoding is not supported beside a multimodal projector (mmproj)"; return nullptr; }
+    if (!body["model_draft"].is_null() && tp_split_requested(body)) { err = "model_draft: speculative decoding is not supported with \"split_mode\": \"row\""; return nullptr; }
     if (tp_split_requested(body)) return make_split_backend(body, info, err);
     std::string path = body.value<std::string>("llama_model_path", "");
     if (path.empty()) path = body.value<std::string>("model_path", "");
@@ -253,12 +308,46 @@ std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, 
         }
     }
 
+    // "model_draft": a small model of the same vocabulary that proposes tokens for this one to check (upstream's --model-draft)
+    std::unique_ptr<Model> dmodel;
+    std::unique_ptr<Context> dctx;
+    if (!body["model_draft"].is_null()) {
+        const std::string dpath = body["model_draft"].str_or("");
+        if (dpath.empty()) { err = "model_draft: expected the path of a draft model file"; return nullptr; }
+        if (model->hp.encoder) { err = "model_draft: an embedding (encoder) model cannot speculate"; return nullptr; }
+        std::string derr;
+        int dstatus = 0;
+        dmodel.reset(model_load(dpath, body.value<int>("main_gpu", 0), derr, dstatus, 0));
+        if (!dmodel) { err = "model_draft: " + dpath + ": " + derr; return nullptr; }
+        if (dmodel->hp.encoder) { err = "model_draft: " + dpath + " is an embedding (encoder) model"; return nullptr; }
+        Vocab dvocab;
+        if (!dvocab.load(*dmodel->file, derr)) { err = "model_draft: tokenizer: " + derr; return nullptr; }
+        // (the rule of upstream's common_speculative_are_compatible, as remembered: DESIGN.md §9)
+        if (vocab.model() != dvocab.model() || vocab.bos() != dvocab.bos() || vocab.eos() != dvocab.eos()) {
+            err = "model_draft: the draft model's tokenizer (type, bos or eos) differs from the target's"; return nullptr;
+        }
+        if (dmodel->hp.n_vocab != dvocab.n_tokens()) { err = "model_draft: the draft model's tokenizer size does not match its embedding table"; return nullptr; }
+        // (stricter than upstream's "at most 128 apart": a drafted id has to be a row of the target's embedding table, and the target's id one of the draft's)
+        if (vocab.n_tokens() != dvocab.n_tokens()) {
+            err = "model_draft: vocabulary sizes " + std::to_string(vocab.n_tokens()) + " and " + std::to_string(dvocab.n_tokens()) + " differ (they must be equal)"; return nullptr;
+        }
+        for (int t = 5; t < vocab.n_tokens(); t++)
+            if (vocab.token_to_piece(t, true) != dvocab.token_to_piece(t, true)) { err = "model_draft: token " + std::to_string(t) + " differs between the two vocabularies"; return nullptr; }
+        ContextParams dcp = cp;
+        dcp.logits_to_host = false;
+        dctx.reset(new Context(dmodel.get(), dcp));
+        if (!dctx->init(derr)) { err = "model_draft: " + derr; return nullptr; }
+        log_line(LOG_INFO, "draft model %s loaded for speculative decoding", dpath.c_str());
+    }
+
     info.vram = model->device_bytes + ctx->device_bytes;
+    if (dmodel) info.vram += dmodel->device_bytes + dctx->device_bytes;
     info.ram = model->host_bytes;
     info.model_size = model->file_tensor_bytes;
     if (clip) info.vram += clip->device_bytes;
     std::unique_ptr<HipBackend> be(new HipBackend(std::move(model), std::move(ctx), std::move(vocab), body.value<bool>("device_sampling", true)));
     be->set_clip(std::move(clip));
+    if (dctx) be->set_draft(std::move(dmodel), std::move(dctx));
     return be;
 }
 

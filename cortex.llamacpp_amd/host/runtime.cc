@@ -330,6 +330,7 @@ Context::~Context() {
     if (h_mega_flag_) (void)hipHostFree(h_mega_flag_);
     if (h_topk_) (void)hipHostFree(h_topk_);
     if (h_topk_adj_) (void)hipHostFree(h_topk_adj_);
+    if (h_spec_) (void)hipHostFree(h_spec_);
     if (d_topk_adj_) (void)hipFree(d_topk_adj_);
     if (topk_scratch_) { (void)hipFree(topk_scratch_); topk_scratch_ = nullptr; }
     if (h_moe_meta_) (void)hipHostFree(h_moe_meta_);
@@ -2364,6 +2365,71 @@ int32_t Context::argmax_ith(int i) {
         argmax_fetched_ = true;
     }
     return h_argmax_[out_row_of_batch_[(size_t)i]];
+}
+
+// ---- speculative decoding (csrc/spec.hip): both read d_logits_, which every decode fills whatever logits_to_host says (the head's launch stores the device
+// row also when it writes the pinned one itself, logits_on_host_), and leave their few words in pinned memory: one launch, one synchronisation
+bool Context::spec_prepare() {
+    if (spec_scratch_) return true;
+    if (hipSetDevice(model->device) != hipSuccess) return false;
+    const size_t words = argmax_prob_scratch_words(1) + spec_verify_scratch_words(SPEC_MAX_ROWS), in_words = 2 * (size_t)SPEC_MAX_ROWS + SPEC_MAX_GROUPS + 1;
+    const size_t host_words = in_words + SPEC_MAX_ROWS + SPEC_MAX_GROUPS + 2;
+    (void)hipStreamSynchronize(stream_);
+    // each block is allocated once: a failure leaves what succeeded in place (dalloc's blocks are the context's) and the next call asks only for the rest;
+    // spec_scratch_ is set last, so it says that all three are there
+    if (!h_spec_ && hipHostMalloc((void **)&h_spec_, host_words * 4, hipHostMallocDefault) != hipSuccess) { h_spec_ = nullptr; last_error = "speculative-decoding workspace allocation failed"; return false; }
+    if (!d_spec_in_) d_spec_in_ = (int32_t *)dalloc(in_words * 4);
+    float *scratch = d_spec_in_ ? (float *)dalloc(words * 4) : nullptr;   // (zero-filled: the ticket words)
+    if (!scratch) { last_error = "speculative-decoding workspace allocation failed"; return false; }
+    spec_scratch_ = scratch;
+    (void)hipDeviceSynchronize();                                      // the null-stream zero-fills (see init)
+    return true;
+}
+
+int32_t Context::argmax_prob_ith(int i, float *p) {
+    if (last_was_embd_) { last_error = "argmax_prob: embeddings mode computes no logits"; return -1; }
+    if (i < 0) i += (int)out_row_of_batch_.size();
+    if (i < 0 || i >= (int)out_row_of_batch_.size() || out_row_of_batch_[(size_t)i] < 0) { last_error = "argmax_prob: no logits for that batch row"; return -1; }
+    if (!spec_prepare()) return -1;
+    const int V = model->hp.n_vocab;
+    int32_t *h_idx = h_spec_ + 2 * SPEC_MAX_ROWS + SPEC_MAX_GROUPS + 1 + SPEC_MAX_ROWS + SPEC_MAX_GROUPS;
+    float *h_p = reinterpret_cast<float *>(h_idx + 1);
+    if (launch_argmax_prob_rows(d_logits_ + (size_t)out_row_of_batch_[(size_t)i] * V, V, nullptr, 1, h_idx, h_p, spec_scratch_, 1, stream_) != hipSuccess) {
+        last_error = "argmax_prob launch failed"; return -1;
+    }
+    if (hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
+    argmax_fetched_ = true;
+    if (p) *p = *h_p;
+    return *h_idx;
+}
+
+int Context::spec_verify(int n_groups, const int32_t *group_start, const int32_t *draft, int32_t *ids_out, int32_t *n_accept_out) {
+    if (last_was_embd_) { last_error = "spec_verify: embeddings mode computes no logits"; return -1; }
+    if (model->hp.tp_size > 1) { last_error = "spec_verify: not on a rank of a row split"; return -1; }
+    if (n_groups < 1 || n_groups > SPEC_MAX_GROUPS || !group_start || !draft || !ids_out || !n_accept_out) { last_error = "spec_verify: bad arguments (1 .. 64 groups)"; return -1; }
+    const int b0 = group_start[0], R = group_start[n_groups] - b0;
+    if (b0 < 0 || R < 1 || R > SPEC_MAX_ROWS || group_start[n_groups] > (int)out_row_of_batch_.size()) { last_error = "spec_verify: the groups do not lie inside the last batch"; return -1; }
+    for (int g = 0; g < n_groups; g++) {
+        const int rows = group_start[g + 1] - group_start[g];
+        if (rows < 1 || rows > SPEC_MAX_DRAFT + 1) { last_error = "spec_verify: group " + std::to_string(g) + " has " + std::to_string(rows) + " rows (1 .. 17)"; return -1; }
+    }
+    for (int r = 0; r < R; r++)
+        if (out_row_of_batch_[(size_t)(b0 + r)] < 0) { last_error = "spec_verify: batch row " + std::to_string(b0 + r) + " was not flagged for logits"; return -1; }
+    if (!spec_prepare()) return -1;
+    // rows | group starts (relative to the launch's first row) | drafts: one staged copy
+    int32_t *h_rows = h_spec_, *h_gs = h_rows + R, *h_draft = h_gs + n_groups + 1;
+    for (int r = 0; r < R; r++) { h_rows[r] = out_row_of_batch_[(size_t)(b0 + r)]; h_draft[r] = draft[r]; }
+    for (int g = 0; g <= n_groups; g++) h_gs[g] = group_start[g] - b0;
+    int32_t *h_ids = h_spec_ + 2 * SPEC_MAX_ROWS + SPEC_MAX_GROUPS + 1, *h_acc = h_ids + SPEC_MAX_ROWS;
+    const size_t in_words = 2 * (size_t)R + (size_t)n_groups + 1;
+    if (hipMemcpyAsync(d_spec_in_, h_spec_, in_words * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "spec_verify staging failed"; return -1; }
+    if (launch_spec_verify(d_logits_, model->hp.n_vocab, d_spec_in_, R, d_spec_in_ + R, n_groups, d_spec_in_ + R + n_groups + 1, h_ids, h_acc,
+                           spec_scratch_ + argmax_prob_scratch_words(1), SPEC_MAX_ROWS, stream_) != hipSuccess) { last_error = "spec_verify launch failed"; return -1; }
+    if (hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
+    argmax_fetched_ = true;
+    memcpy(ids_out, h_ids, (size_t)R * 4);
+    memcpy(n_accept_out, h_acc, (size_t)n_groups * 4);
+    return R;
 }
 
 // n rows of the last batch in ONE set of launches and ONE synchronisation (a scheduler tick asks for all its sampling slots together: row by row, each

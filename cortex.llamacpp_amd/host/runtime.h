@@ -107,6 +107,14 @@ class Context {
     // produced for the flagged tokens of the last decode while embeddings_enabled is set (then no logits are computed)
     float *embeddings_ith(int i);
     int32_t argmax_ith(int i);
+    // speculative decoding (csrc/spec.hip), both from the device logits of the last decode, whatever logits_to_host says:
+    // the arg-max of batch row i and its softmax probability over the whole vocabulary (argmax_ith's preconditions; -1 with last_error set)
+    int32_t argmax_prob_ith(int i, float *p);
+    // greedy acceptance: group g owns batch rows group_start[g] .. group_start[g + 1] - 1 of the last decode (k_g drafted tokens -> k_g + 1 rows, every one
+    // flagged); draft [R] runs parallel to those R rows (a group's last entry is ignored).  ids_out [R]: each row's arg-max; n_accept_out [n_groups]: the drafts
+    // the model agrees with, from the group's first row on.  One launch, one synchronisation.  Returns R, or -1 with last_error set (a row not flagged,
+    // embeddings mode, a rank of a row split).
+    int spec_verify(int n_groups, const int32_t *group_start, const int32_t *draft, int32_t *ids_out, int32_t *n_accept_out);
     // test hook (mixture-of-experts files): the NEXT decode call (one micro-batch of T tokens) takes these experts, ids [n_layer][T][n_expert_used], instead of
     // its router's selection; the weights stay this side's probabilities of them.  One call, then routing is free again.  No graphs while it is armed.
     int force_moe_ids(const int32_t *ids, int n_layer, int T, int k);
@@ -335,6 +343,9 @@ class Context {
     void *topk_scratch_ = nullptr;                     // launch_topk_rows workspace (own allocation, sized for topk_rows_cap_ rows on first use)
     uint8_t *d_topk_adj_ = nullptr, *h_topk_adj_ = nullptr;   // [cap] TopkAdj + [cap] row numbers: device copy and its pinned staging
     int topk_rows_cap_ = 0;
+    float *spec_scratch_ = nullptr;                    // argmax_prob_ith / spec_verify: part and ticket words of the two kernels (first use)
+    int32_t *d_spec_in_ = nullptr, *h_spec_ = nullptr; // rows | group starts | drafts on the device; pinned: their staging, then ids | accepted | (index, p)
+    bool spec_prepare();
     unsigned long long *h_topk_ = nullptr;             // pinned: the winning keys
     Fuse pending_fuse_;
     int att_splits_ = 1;

@@ -203,6 +203,14 @@ void LlamaServerContext::PromptCacheVisit(LlamaClientSlot &slot) {
     }
 }
 
+void LlamaServerContext::SpecStats(int64_t out[4]) const {
+    for (int i = 0; i < 4; i++) out[i] = spec_stats_[i].load();
+}
+// a generating slot speculates when the backend has a draft model and the request asks for nothing a drafted row cannot give: no grammar, no n_probs, no images
+bool LlamaServerContext::SlotSpeculates(const LlamaClientSlot &slot) const {
+    return be_->has_draft() && !slot.embedding && slot.smpl && !slot.smpl->has_grammar() && slot.sparams.n_probs == 0 && slot.images.empty() && !slot.spec_tokens.empty();
+}
+
 void LlamaServerContext::DoBackgroundTasks() {  // :1239-1246
     while (model_loaded_external) UpdateSlots();
     KvCacheClear();
@@ -714,6 +722,8 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
                 for (size_t i = (size_t)(slot.params.n_keep + 1 + n_discard); i < slot.cache_tokens.size(); i++) slot.cache_tokens[i - (size_t)n_discard] = slot.cache_tokens[i];
                 slot.cache_tokens.resize(slot.cache_tokens.size() - (size_t)n_discard);
             }
+            if (!slot.spec_tokens.empty() && slot.spec_tokens.size() >= (size_t)(slot.params.n_keep + 1 + n_discard))      // (the draft context rebuilds from the common prefix)
+                slot.spec_tokens.erase(slot.spec_tokens.begin() + slot.params.n_keep + 1, slot.spec_tokens.begin() + slot.params.n_keep + 1 + n_discard);
             slot.n_past -= n_discard;
             slot.truncated = true;
         }
@@ -730,10 +740,30 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
         }
         if (slot.state == SlotState::kIdle) continue;
         slot.i_batch = n_tokens;
+        slot.spec_draft.clear();
+        slot.spec_tick = false;
+        if (SlotSpeculates(slot)) {
+            // the draft model continues the sequence: at most draft_max tokens, room for them in the context (n_past + k + 1 <= n_ctx - 1), in what the request
+            // may still emit, and in the batch (a row is kept for every slot behind this one)
+            slot.spec_tokens.push_back(slot.sampled);
+            int k = std::min((int)params.draft_max, slot.n_ctx - slot.n_past - 2);
+            const int n_predict = slot.params.n_predict != -1 ? slot.params.n_predict : params.n_predict;
+            if (n_predict != -1) k = std::min(k, n_predict - slot.n_decoded - 1);
+            k = std::min(k, (int)b_token_.size() - n_tokens - 1 - (int)(&slots.back() - &slot));
+            k = std::min(k, 16);
+            if (k >= 1) {
+                slot.spec_draft.resize((size_t)k);
+                const int got = be_->spec_draft(slot.id, slot.spec_tokens.data(), (int)slot.spec_tokens.size(), k, params.draft_p_min, slot.spec_draft.data());
+                slot.spec_draft.resize((size_t)std::max(0, std::min(got, k)));
+                if ((int)slot.spec_draft.size() < params.draft_min) slot.spec_draft.clear();
+            }
+            slot.spec_tick = true;                          // (counted where the chunk that holds its rows has been decoded)
+        }
         batch_add(slot.sampled, slot.n_past, slot.id, true);
         slot.n_decoded += 1;
         slot.n_past += 1;
         if (slot.params.cache_prompt) slot.cache_tokens.push_back(slot.sampled);
+        for (size_t j = 0; j < slot.spec_draft.size(); j++) batch_add(slot.spec_draft[j], slot.n_past + (int32_t)j, slot.id, true);   // (n_past, n_decoded: as each is emitted)
     }
     int32_t n_batch = be_->n_batch();
     bool embd_tick = false, tick_mode_set = n_tokens > 0;      // a tick that already carries generated tokens is a generation tick
@@ -858,6 +888,8 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
                 if (n_tokens > 0) b_logits_[(size_t)n_tokens - 1] = 1;
                 slot.n_decoded = 0;
                 slot.i_batch = n_tokens - 1;
+                slot.spec_draft.clear();
+                if (be_->has_draft() && slot.images.empty() && !slot.embedding) slot.spec_tokens = prompt_tokens; else slot.spec_tokens.clear();
             }
         }
     }
@@ -907,12 +939,82 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
         std::vector<int32_t> ids(gen.size(), -1);
         std::vector<const float *> rows(gen.size(), nullptr);
         const int n_vocab_now = be_->n_vocab();
+        // speculating slots: the tokens each emits this tick (spec_emit[gi]; empty = the slot takes the plain path below, its row is i_batch).  A slot whose
+        // drafted rows were cut off by the chunk (the n_batch / 2 retry) takes no drafts this tick: its stray rows leave with the tick's roll-back.
+        std::vector<std::vector<int32_t>> spec_emit(gen.size());
+        std::vector<char> spec_walked(gen.size(), 0);
+        std::vector<int> spec_k(gen.size(), 0);
+        for (size_t gi = 0; gi < gen.size(); gi++) {
+            if (!gen[gi]->spec_draft.empty() && gen[gi]->i_batch + (int)gen[gi]->spec_draft.size() < i + nt) spec_k[gi] = (int)gen[gi]->spec_draft.size();
+            if (!gen[gi]->spec_tick) continue;
+            // the counters, as mi355_speculative_steps keeps them: every tick of a speculating slot is a round, with spec_k drafted tokens - or a plain step too
+            // (nothing drafted, or the drafts cut off by the chunk); accepted counts the drafts that were emitted (phase 2)
+            gen[gi]->spec_tick = false;
+            spec_stats_[0]++; spec_stats_[1] += spec_k[gi];
+            if (spec_k[gi] == 0) spec_stats_[3]++;
+        }
+        // plain greedy: every run of adjacent rows that holds a speculating slot goes through ONE spec_verify call (a slot without drafts is a group of one row)
+        for (size_t g0 = 0; g0 < gen.size();) {
+            size_t g1 = g0;
+            int next_row = gen[g0]->i_batch;
+            bool any = false;
+            std::vector<int32_t> gs{next_row - i}, dr;
+            while (g1 < gen.size() && gen[g1]->i_batch == next_row) {
+                for (int j = 0; j < spec_k[g1]; j++) dr.push_back(gen[g1]->spec_draft[(size_t)j]);
+                dr.push_back(-1);
+                next_row += spec_k[g1] + 1;
+                gs.push_back(next_row - i);
+                any = any || (spec_k[g1] > 0 && gen[g1]->smpl->is_plain_greedy());
+                g1++;
+            }
+            if (any && g1 - g0 <= 64) {
+                std::vector<int32_t> vids(dr.size(), -1), acc(g1 - g0, 0);
+                if (be_->spec_verify((int)(g1 - g0), gs.data(), dr.data(), vids.data(), acc.data()))
+                    for (size_t gi = g0; gi < g1; gi++)
+                        if (spec_k[gi] > 0 && gen[gi]->smpl->is_plain_greedy()) {
+                            const int r0 = gs[gi - g0] - gs[0], a = std::max(0, std::min(acc[gi - g0], spec_k[gi]));
+                            spec_emit[gi].assign(vids.begin() + r0, vids.begin() + r0 + a + 1);
+                        }
+            }
+            g0 = std::max(g1, g0 + 1);
+        }
+        // any other sampler (and plain greedy on a backend without spec_verify): sample row by row, accept, stop at the first token that is not the draft's
+        for (size_t gi = 0; gi < gen.size(); gi++) {
+            if (spec_k[gi] == 0 || !spec_emit[gi].empty()) continue;
+            LlamaClientSlot &slot = *gen[gi];
+            spec_walked[gi] = 1;
+            for (int j = 0; j <= spec_k[gi]; j++) {
+                const int r = slot.i_batch - i + j;
+                int32_t id = slot.smpl->is_plain_greedy() ? be_->argmax_ith(r) : -1;
+                if (id >= 0) slot.smpl->set_greedy_result(id);
+                Sampler::FrontPlan fp;
+                // the device top-k front, as the same request takes it without a draft: k candidates cross, not the row (the plan depends on the tokens accepted
+                // so far, so the rows go one by one)
+                if (id < 0 && be_->topk_max_k() > 0 && slot.smpl->plan_front(n_vocab_now, be_->topk_max_k(), be_->topk_max_adj(), fp)) {
+                    const SamplingParams &sp = slot.smpl->params();
+                    std::vector<int32_t> tk((size_t)fp.k);
+                    std::vector<float> tl((size_t)fp.k);
+                    if (be_->topk_ith(r, fp.k, fp.tok, fp.bias, fp.cnt, sp.penalty_repeat, sp.penalty_freq, sp.penalty_present, tk.data(), tl.data()) == fp.k) {
+                        std::vector<TokenProb> c((size_t)fp.k);
+                        for (int q = 0; q < fp.k; q++) c[(size_t)q] = TokenProb{tk[(size_t)q], tl[(size_t)q]};
+                        id = slot.smpl->finish(c);
+                    }
+                }
+                if (id < 0) { const float *row = be_->logits_ith(r); id = row ? slot.smpl->sample(row, n_vocab_now) : -1; }   // (a chain that needs the whole row)
+                if (id < 0) break;
+                slot.smpl->accept(id);
+                spec_emit[gi].push_back(id);
+                if (j < spec_k[gi] && id != slot.spec_draft[(size_t)j]) break;
+            }
+            if (spec_emit[gi].empty()) spec_emit[gi].push_back(-1);      // (no logits: phase 2 reports it)
+        }
         // device-side head of the chain (logit_bias -> penalties -> top_k): k candidates per slot cross instead of the row, all the
         // tick's sampling slots in one request to the backend
         std::vector<IBackend::TopkRequest> front;
         std::vector<size_t> front_slot;
         for (size_t gi = 0; gi < gen.size(); gi++) {
             LlamaClientSlot &slot = *gen[gi];
+            if (!spec_emit[gi].empty()) continue;           // (this tick's tokens are known already)
             if (slot.smpl->is_plain_greedy()) {             // device-side greedy front end: no pass over the vocabulary on the host
                 ids[gi] = be_->argmax_ith(slot.i_batch - i);
                 if (ids[gi] >= 0) { slot.smpl->set_greedy_result(ids[gi]); continue; }
@@ -942,7 +1044,7 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
             }
         }
         for (size_t gi = 0; gi < gen.size(); gi++)
-            if (ids[gi] < 0) rows[gi] = be_->logits_ith(gen[gi]->i_batch - i);
+            if (ids[gi] < 0 && spec_emit[gi].empty()) rows[gi] = be_->logits_ith(gen[gi]->i_batch - i);
         const int n_vocab = be_->n_vocab();
         const std::function<void(int)> sample_one = [&](int gi) {
             if (ids[(size_t)gi] < 0 && rows[(size_t)gi]) ids[(size_t)gi] = gen[(size_t)gi]->smpl->sample(rows[(size_t)gi], n_vocab);
@@ -953,7 +1055,30 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
         // phase 2: in slot order, exactly as the reference's loop (:1665-1704)
         for (size_t gi = 0; gi < gen.size(); gi++) {
             LlamaClientSlot &slot = *gen[gi];
-            const int32_t id = ids[gi];
+            if (!spec_emit[gi].empty() && spec_emit[gi][0] >= 0) {
+                // a speculating slot emits its tokens in order, each as the tick that would have produced it: the draft in front of it has become part of
+                // the sequence (n_past, n_decoded, the token lists), and a token that ends the generation ends the walk
+                for (size_t j = 0; j < spec_emit[gi].size(); j++) {
+                    const int32_t tok = spec_emit[gi][j];
+                    if (j > 0) {
+                        slot.n_decoded += 1; slot.n_past += 1;
+                        if (slot.params.cache_prompt) slot.cache_tokens.push_back(slot.spec_draft[j - 1]);
+                        slot.spec_tokens.push_back(slot.spec_draft[j - 1]);
+                        spec_stats_[2]++;
+                    }
+                    if (!spec_walked[gi]) { slot.smpl->set_greedy_result(tok); slot.smpl->accept(tok); }
+                    if (slot.n_decoded == 1) {
+                        slot.t_start_genereration = time_us();
+                        slot.t_prompt_processing = (double)(slot.t_start_genereration - slot.t_start_process_prompt) / 1e3;
+                    }
+                    CompletionTokenOutput result;
+                    result.tok = tok;
+                    if (!ProcessToken(result, slot)) { slot.Release(); SendFinalResponse(slot); break; }
+                }
+                slot.i_batch = -1;
+                continue;
+            }
+            const int32_t id = spec_emit[gi].empty() ? ids[gi] : -1;
             if (id < 0) { slot.Release(); SendError(slot, "no logits"); slot.i_batch = -1; continue; }
             CompletionTokenOutput result;
             slot.smpl->accept(id);
@@ -973,6 +1098,13 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
         const int64_t t_e = time_us();
         t_decode_us_ += (double)(t_s0 - t_d0); t_sample_us_ += (double)(t_p0 - t_s0); t_post_us_ += (double)(t_e - t_p0);
         n_ticks_++; n_tick_tokens_ += nt;
+    }
+    // the roll-back of the tick's speculation: both caches keep what each slot's sequence now holds (n_past positions) and nothing behind it
+    for (auto &slot : slots) {
+        if (slot.spec_draft.empty()) continue;
+        be_->kv_seq_rm(slot.id, slot.n_past, -1);
+        be_->draft_seq_rm(slot.id, slot.n_past);
+        slot.spec_draft.clear();
     }
     return true;
 }

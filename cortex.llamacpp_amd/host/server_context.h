@@ -46,6 +46,9 @@ struct ServerParams {            // the subset of common_params the loop reads
     int32_t n_parallel = 1;
     bool cont_batching = true;
     int64_t cache_ram_mib = 0;   // /loadmodel "cache_ram": MiB of host memory for the prompt cache (prompt_cache.h); 0 = off, the loop then makes no state call at all; < 0 = no limit
+    // /loadmodel "draft_max" / "draft_min" / "draft_p_min": speculative decoding with the backend's draft model (read only when it has one)
+    int32_t draft_max = 16, draft_min = 0;
+    float draft_p_min = 0.75f;
     std::string model_alias;
     SamplingParams sampling;
 };
@@ -74,6 +77,10 @@ struct LlamaClientSlot {
     std::string generated_text;
     int32_t sampled = 0;
     std::vector<int32_t> cache_tokens;
+    // speculative decoding (a backend with a draft model): every token of the sequence, positions 0 .. n_past - 1 (what the draft model is asked to continue),
+    // and this tick's drafted tokens, which follow `sampled` in the batch
+    std::vector<int32_t> spec_tokens, spec_draft;
+    bool spec_tick = false;         // this tick asked the draft model (counted as a round or a plain step once its chunk is decoded)
     std::vector<CompletionTokenOutput> generated_token_probs;
     std::vector<SlotImage> images;  // multimodal request: in prompt order
     std::string input_suffix;       // the text behind the last image
@@ -118,6 +125,9 @@ class LlamaServerContext {
     void KvCacheClear();
     // the host-RAM prompt cache's counters (prompt_cache.h: entries, bytes held, saves, restores, tokens restored, evictions); all zero while it is off
     void PromptCacheStats(int64_t out[6]) const;
+    // speculative decoding, the counters of mi355_speculative_steps: rounds (ticks of a speculating slot), drafted, accepted (drafts that were emitted), plain
+    // steps (rounds without a drafted token).  For one request: tokens_predicted = rounds + accepted.
+    void SpecStats(int64_t out[4]) const;
 
     // one scheduler tick, exposed for tests (the background thread calls it forever)
     bool UpdateSlots();
@@ -165,6 +175,8 @@ class LlamaServerContext {
     // sequence that holds more of the prompt than the slot does (sets cache_tokens and n_past)
     void PromptCacheVisit(LlamaClientSlot &slot);
     std::unique_ptr<PromptCache> prompt_cache_;       // null: "cache_ram" 0, or a backend without sequence states
+    bool SlotSpeculates(const LlamaClientSlot &slot) const;
+    std::atomic<int64_t> spec_stats_[4] = {{0}, {0}, {0}, {0}};
 
     IBackend *be_;
     int id_gen_ = 0;

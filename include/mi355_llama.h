@@ -149,6 +149,27 @@ MI355_API int32_t mi355_greedy_steps(mi355_context *ctx, mi355_token first, mi35
 MI355_API float  *mi355_get_logits_ith(mi355_context *ctx, int32_t i);
 /* device-side greedy front end: argmax token of row i without copying the row */
 MI355_API int32_t mi355_get_argmax_ith(mi355_context *ctx, int32_t i);
+/* ---- speculative decoding (the reference's server takes a draft model as --model-draft).  Everything below reads the device logits of the
+ * last mi355_decode, also with logits_to_host = 0, and moves a few words to the host, never a row.
+ * The arg-max token of row i (mi355_get_argmax_ith's rule and preconditions) and, in *p, its softmax probability over the WHOLE vocabulary,
+ * 1 / sum_j exp(x_j - max) in f32 (0 where the row's maximum is not finite).  < 0 on failure. */
+MI355_API int32_t mi355_get_argmax_prob_ith(mi355_context *ctx, int32_t i, float *p);
+/* Greedy acceptance over the rows of the last mi355_decode: group g owns batch rows group_start[g] .. group_start[g + 1] - 1, k_g + 1 rows for k_g <= 16
+ * drafted tokens, all of them flagged; the groups are adjacent, R = group_start[n_groups] - group_start[0] <= 1088 rows, n_groups <= 64.  draft [R] runs
+ * parallel to those rows (the entry of a group's last row is ignored).  ids_out [R]: each row's arg-max; n_accept_out [n_groups]: the largest a <= k_g with
+ * ids == draft on the group's first a rows.  One launch, one synchronisation, 4 (R + n_groups) bytes back.  Returns R; < 0 with mi355_last_error set when a
+ * row was not flagged, in embeddings mode, or on a rank of a row split. */
+MI355_API int32_t mi355_spec_verify(mi355_context *ctx, int32_t n_groups, const int32_t *group_start, const mi355_token *draft, mi355_token *ids_out,
+                                    int32_t *n_accept_out);
+/* mi355_greedy_steps with a draft model's context beside the target's.  Both hold sequence `seq` over positions [0, pos0); `first` goes to pos0.  A round:
+ * the draft context decodes what it has not seen (the last emitted token; two tokens after a round that accepted n_max drafts), then drafts greedily through
+ * mi355_get_argmax_prob_ith until n_max <= 16 tokens or the first probability below p_min (that token is not drafted); fewer than n_min drafts are dropped; the
+ * target decodes [last, drafts] with every row flagged and mi355_spec_verify says how many hold (no drafts: a plain step); the agreed drafts and the target's
+ * next token are emitted and both caches forget everything behind them.  Exactly n tokens: the last round is cut, its surplus KV removed too.  The tokens
+ * are those of mi355_greedy_steps on the target wherever its arg-max does not hinge on batch-size rounding.  stats (nullable) [4]: rounds, drafted, accepted
+ * (drafts that were emitted: n = rounds + accepted), plain steps (rounds without a draft).  Returns the tokens written (n, or fewer with the reason in mi355_last_error). */
+MI355_API int32_t mi355_speculative_steps(mi355_context *ctx_tgt, mi355_context *ctx_dft, mi355_token first, mi355_pos pos0, mi355_seq_id seq, int32_t n,
+                                          int32_t n_max, int32_t n_min, float p_min, mi355_token *out_tokens, int64_t *stats);
 /* device-side sampling front end beyond greedy (stands in for the head of common_sampler_sample's chain, reference call site
    src/llama_server_context.cc:1679-1698): the k <= 128 best candidates of row i after logit_bias and the repetition / frequency / presence penalties,
    best first (higher logit; lower token id on ties) - k (token, logit) pairs cross to the host instead of the whole row.  adj_tok / adj_bias / adj_count:
@@ -314,6 +335,13 @@ MI355_API int mi355_op_moe_router(int32_t type, const void *gate_inp, int32_t n_
  * next launches[i] rows (1 <= launches[i] <= cap_rows) - n_launch launches back to back on that scratch, no synchronisation between them.  out[row]: the
  * lowest index of the largest value; NaN entries never win; a row without a comparable entry gives 0. */
 MI355_API int mi355_op_argmax_rows(const float *x, int64_t n, const int32_t *launches, int32_t n_launch, int32_t cap_rows, int32_t *out);
+/* The two kernels of a speculative round (csrc/spec.hip), the arg-max rule above in both.  x [rows][n]: idx_out [rows] and p_out [rows], the arg-max's softmax
+ * probability 1 / sum_j exp(x_j - max) over the non-NaN entries (f32, a fixed summation order; 0 where the maximum is not finite). */
+MI355_API int mi355_op_argmax_prob_rows(const float *x, int64_t n, int32_t rows, int32_t *idx_out, float *p_out);
+/* logits [n_base_rows][n]; launch row r = base row rows[r], r < R <= 1088; group g < G <= 64 owns launch rows group_start[g] .. group_start[g + 1] - 1
+ * (1 .. 17 rows; group_start[0] = 0, group_start[G] = R); draft [R].  ids_out [R], n_accept_out [G] as mi355_spec_verify gives them. */
+MI355_API int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t R, const int32_t *group_start, int32_t G,
+                                   const int32_t *draft, int32_t *ids_out, int32_t *n_accept_out);
 /* The k best candidates of n_rows logits rows (the front end of a sampled step): row r is base row rows[r] ([n_base_rows][n] f32) after its adjustments -
  * adj_n[r] entries (0 .. 192) of the flat [n_rows][192] arrays adj_tok / adj_bias / adj_cnt, no token twice in a row's list: l = l + bias; if cnt > 0:
  * l = l <= 0 ? l * repeat[r] : l / repeat[r]; l -= cnt * freq[r] + present[r].  Order: higher logit first, lower token id among equal logits (-0.0 == +0.0).
@@ -455,6 +483,11 @@ MI355_API void mi355_engine_stop_inferencing(mi355_engine *e, const char *model_
    conversations that lost their slot, restored when their prompt comes back.  out: entries, bytes held, saves, restores, tokens restored, evictions - all zero
    while the cache is off.  < 0: no such model. */
 MI355_API int mi355_engine_prompt_cache_stats(mi355_engine *e, const char *model_id, int64_t out[6]);
+/* Speculative decoding of a model loaded with "model_draft": PATH (a draft model of the same vocabulary; "draft_max" 1 .. 16, default 16; "draft_min", default 0;
+   "draft_p_min", default 0.75): requests without a grammar, n_probs or images take the draft model's proposals and check them in one batched step.  out, as
+   mi355_speculative_steps counts them: rounds (ticks of a speculating slot), drafted, accepted (drafts that were emitted), plain steps (rounds without a drafted
+   token) - all zero without a draft model.  < 0: no such model. */
+MI355_API int mi355_engine_spec_stats(mi355_engine *e, const char *model_id, int64_t out[4]);
 /* EngineI::Load(EngineLoadOption) / Unload(EngineUnloadOption) (base/cortex-common/enginei.h:14-35; LlamaEngine: src/llama_engine.cc:289-303): Load =
    SetFileLogger(max_log_lines, log_path) + SetLogLevel(log_level).  Paths as UTF-8 strings (std::filesystem::path::string()), log_level = the value of
    trantor::Logger::LogLevel (kTrace 0, kDebug 1, kInfo 2, kWarn 3, kError 4, kFatal 5). */
