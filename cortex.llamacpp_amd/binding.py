@@ -117,6 +117,7 @@ SYMBOLS = {
     "mi355_op_mul_mat": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "mi355_op_mul_mat_add": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "mi355_op_mul_mat_fused": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _vp, _f32, _vp]),
+    "mi355_op_mat_vec_step": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, _f32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "mi355_op_f32_to_bf16": (C.c_int, [_vp, _i64, _vp]),
     "mi355_op_mul_mat_bf16": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mi355_op_ffn_gate_up": (C.c_int, [_i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
@@ -296,6 +297,42 @@ class Backend:
         y = np.zeros(N, np.float32)
         self._chk(self.lib.mi355_op_mul_mat_fused(t, _ptr(W), N, K, _ptr(x), _ptr(nw), eps, _ptr(y)), "op_mul_mat_fused")
         return y
+
+    MAT_VEC_KERNELS = ("base", "ring", "stream", "tiled")
+    MAT_VEC_ROLES = ("stream", "qkv", "gate_up", "ffn_down", "head")
+
+    def mat_vec_step(self, types, Ws, Ns, K: int, x: np.ndarray, epi: int = 0, resid=None, fuse: int = 0, norm_w=None, eps: float = 0.0,
+                     want_host_copy: bool = False, expert_ids=None, n_expert: int = 1, ld_pad: int = 0):
+        """One mat-vec launch of a decode step as the model issues it (see mi355_op_mat_vec_step).  Returns (ys, y_host, path): ys the whole out buffers
+        [rows][N + ld_pad] (one for epi 2), y_host the pinned second copy or None, path one dict per launch issued: tokens, kernel, and for the weight
+        stream role (moe / ternary launches: "moe" / "ternary"), kb, fast_ok, down_early."""
+        n = len(Ws)
+        Ws = [np.ascontiguousarray(w.view(np.uint8).reshape(-1)) for w in Ws]
+        tarr = np.asarray(types, np.int32)
+        Narr = np.asarray(Ns, np.int64)
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+        n_sel = 0 if expert_ids is None else len(expert_ids)
+        ids = None if expert_ids is None else np.ascontiguousarray(expert_ids, np.int32)
+        T = 1 if n_sel else x.shape[0]
+        R = n_sel if n_sel else T
+        ys = [np.zeros((R, int(N) + ld_pad), np.float32) for N in (Narr[:1] if epi == 2 else Narr)]
+        r = None if resid is None else np.ascontiguousarray(resid, np.float32).reshape(R, int(Narr[0]) + ld_pad)
+        nw = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32).reshape(K)
+        yh = np.zeros(int(Narr[0]), np.float32) if want_host_copy else None
+        path = np.zeros(40, np.int32)
+        parr = lambda xs: (C.c_void_p * len(xs))(*[None if a is None else a.ctypes.data for a in xs])
+        wp, yp = parr(Ws), parr(ys + [None] * (n - len(ys)))
+        self._chk(self.lib.mi355_op_mat_vec_step(n, _ptr(tarr), wp, _ptr(Narr), K, _ptr(x), T, epi, _ptr(r), fuse, _ptr(nw), eps, int(want_host_copy), n_sel,
+                                                 n_expert, _ptr(ids), ld_pad, yp, _ptr(yh), _ptr(path)), "op_mat_vec_step")
+        launches = []
+        for p in path.reshape(5, 8):
+            if p[0] == 0:
+                break
+            d = {"T": int(p[0]), "kernel": self.MAT_VEC_KERNELS[p[1]]}
+            if p[1] == 2:
+                d.update(role="ternary" if p[7] else "moe" if p[6] else self.MAT_VEC_ROLES[p[2]], kb=int(p[3]), fast_ok=bool(p[4]), down_early=bool(p[5]))
+            launches.append(d)
+        return ys, yh, launches
 
     def mul_mat(self, t: int, W: np.ndarray, N: int, K: int, x: np.ndarray, want_ints: bool = False):
         W = np.ascontiguousarray(W.view(np.uint8).reshape(-1))

@@ -1053,6 +1053,97 @@ int mi355_op_mul_mat_fused(int32_t type, const void *W, int64_t N, int64_t K, co
     return dy.down(y, (size_t)N * 4) ? MI355_OK : MI355_ERR_HIP;
 }
 
+// A decode step's mat-vec launch as the model issues it (make_seg / single_token_desc / mmvq_tokens of host/runtime.cc): up to three weight tensors over one
+// activation, the epilogue, the prologue, the host copy, the selected-experts form.  Every output buffer is 0xFF bytes before the launch and comes back whole.
+int mi355_op_mat_vec_step(int32_t n_seg, const int32_t *types, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, int32_t epi,
+                          const float *resid, int32_t fuse, const float *norm_w, float eps, int32_t want_host_copy, int32_t n_sel, int32_t n_expert,
+                          const int32_t *expert_ids, int64_t ld_pad, float *const *y, float *y_host, int32_t *path) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    const bool sel = n_sel > 0;
+    if (n_seg < 1 || n_seg > 3 || !types || !W || !N || !x || !y || !path || K <= 0 || T < 1 || T > 17 || ld_pad < 0 || ld_pad > 64 || fuse < 0 || fuse > 2 ||
+        (epi != EPI_STORE && epi != EPI_ADD && epi != EPI_SWIGLU) || (epi == EPI_ADD && (n_seg != 1 || !resid)) || (epi == EPI_SWIGLU && (n_seg != 2 || N[0] != N[1])) ||
+        (fuse != 0 && T != 1) || (fuse == 1 && !norm_w) || (want_host_copy && (!y_host || T != 1)) ||
+        (sel && (n_sel < 2 || n_sel > 8 || n_expert < 1 || !expert_ids || T != 1 || epi == EPI_ADD || want_host_copy || (epi == EPI_SWIGLU ? 1 : n_seg) != 1))) {
+        fail("mat_vec_step: bad arguments"); return MI355_ERR_ARG;
+    }
+    for (int j = 0; j < n_sel; j++) if (expert_ids[j] < 0 || expert_ids[j] >= n_expert) { fail("mat_vec_step: expert id out of range"); return MI355_ERR_ARG; }
+    const int64_t NE = sel ? n_expert : 1;
+    const int64_t R = sel ? n_sel : T;                            // rows of every out buffer
+    const int64_t XR = sel && fuse == 2 ? n_sel : T;              // rows of x: the selected experts' ffn_down quantises one row per expert
+    bool need_q8k = false, need_q80 = false;
+    std::vector<std::unique_ptr<DevBuf>> dw, dy;
+    std::vector<DevTensor> wt((size_t)n_seg);
+    for (int s = 0; s < n_seg; s++) {
+        const size_t grow = ggml_row_bytes(types[s], K), drow = dev_row_bytes(types[s], K);
+        if (!type_is_quant(types[s]) || !grow || N[s] < 1 || !W[s] || (!y[s] && !(epi == EPI_SWIGLU && s == 1)) || ((act_is_q80(types[s]) ? K % 32 : K % 256) != 0)) { fail("mat_vec_step: bad segment"); return MI355_ERR_ARG; }
+        (act_is_q80(types[s]) ? need_q80 : need_q8k) = true;
+        const int64_t rows = N[s] * NE;
+        DevBuf wsrc(grow * rows);
+        dw.emplace_back(new DevBuf(drow * rows));
+        dy.emplace_back(new DevBuf((size_t)R * (N[s] + ld_pad) * 4));
+        if (!wsrc.up(W[s], grow * rows) || !dw.back()->p || !dy.back()->p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+        hipError_t e = launch_repack_rows(types[s], wsrc.as<uint8_t>(), dw.back()->as<uint8_t>(), K, rows, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemset(dy.back()->p, 0xFF, (size_t)R * (N[s] + ld_pad) * 4);
+        if (e != hipSuccess) return hip_fail(e, "mat_vec_step (set-up)");
+        DevTensor &w = wt[(size_t)s];
+        w.type = types[s]; w.K = K; w.N = N[s]; w.n_expert = NE; w.data = dw.back()->as<uint8_t>(); w.row_bytes = drow; w.bytes = drow * (size_t)rows;
+    }
+    const int64_t ld0 = N[0] + ld_pad;
+    DevBuf dx((size_t)K * XR * 4), dnw((size_t)K * 4), dres(resid ? (size_t)R * ld0 * 4 : 16), dids(sel ? (size_t)n_sel * 4 : 16);
+    ActBufs ab((size_t)K, (size_t)T);
+    if (!dx.up(x, (size_t)K * XR * 4) || !dnw.p || (norm_w && !dnw.up(norm_w, (size_t)K * 4)) || !dres.p || (resid && !dres.up(resid, (size_t)R * ld0 * 4)) || !dids.p ||
+        (sel && !dids.up(expert_ids, (size_t)n_sel * 4)) || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    float *host = nullptr;
+    if (want_host_copy) {
+        if (hipHostMalloc((void **)&host, (size_t)N[0] * 4, hipHostMallocDefault) != hipSuccess) { fail("pinned alloc failed"); return MI355_ERR_OOM; }
+        memset(host, 0xFF, (size_t)N[0] * 4);
+    }
+    hipDeviceProp_t prop;
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) set_num_cu(prop.multiProcessorCount);
+    unsigned *ew = install_stream_error_word();
+    hipError_t e = hipSuccess;
+    if (fuse == 0) e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, need_q8k, need_q80, nullptr);
+    MMVQTrace trace;
+    const int32_t *esel = sel ? dids.as<int32_t>() : nullptr;
+    MMVQSeg segs[3];
+    for (int s = 0; s < n_seg; s++) segs[s] = make_seg(wt[(size_t)s], dy[(size_t)s]->as<float>(), (int)(N[s] + ld_pad), s == 0 && resid ? dres.as<float>() : nullptr, esel);
+    if (e == hipSuccess) {
+        if (sel) {                                                // (the two descriptions of Context::moe_selected_desc)
+            MMVQArgs a = single_token_desc(n_seg, (int)K, epi, fuse, fuse ? dx.as<float>() : nullptr, fuse == 1 ? dnw.as<float>() : nullptr, fuse == 1 ? eps : 0.0f, ab.q);
+            a.n_sel = n_sel; a.sel_out_stride = (int)ld0;
+            if (fuse == 2) a.sel_nx_stride = (int)K;
+            for (int s = 0; s < n_seg; s++) a.seg[s] = segs[s];
+            trace.note(a);
+            e = launch_mmvq(a, nullptr);
+        } else {
+            Fuse fz;
+            fz.mode = fuse; fz.x = fuse ? dx.as<float>() : nullptr; fz.w = fuse == 1 ? dnw.as<float>() : nullptr; fz.eps = eps; fz.out_host = host;
+            e = mmvq_tokens(segs, n_seg, (int)K, (int)T, epi, ab.q, nullptr, fz, &trace);
+        }
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    int rc = MI355_OK;
+    if (e != hipSuccess) rc = hip_fail(e, "mat_vec_step");
+    if (rc == MI355_OK && ew && __atomic_exchange_n(ew, 0u, __ATOMIC_RELAXED)) { fail("mat_vec_step: a weight-stream kernel raised the stream error word"); rc = MI355_ERR_HIP; }
+    for (int i = 0; i < 40; i++) path[i] = 0;
+    for (size_t i = 0; i < trace.recs.size() && i < 5; i++) {
+        const MMVQTrace::Rec &r = trace.recs[i];
+        int32_t *p = path + i * 8;
+        p[0] = r.T; p[1] = r.kernel;
+        if (r.kernel == MMVQ_KERNEL_STREAM) { p[2] = r.form.role; p[3] = r.form.kb; p[4] = r.form.fast_ok; p[5] = r.form.down_early; p[6] = r.form.moe; p[7] = r.form.ternary; }
+    }
+    const int n_out = epi == EPI_SWIGLU ? 1 : n_seg;
+    for (int s = 0; s < n_out && rc == MI355_OK; s++)
+        if (!dy[(size_t)s]->down(y[s], (size_t)R * (N[s] + ld_pad) * 4)) rc = MI355_ERR_HIP;
+    if (host) {
+        if (rc == MI355_OK) memcpy(y_host, host, (size_t)N[0] * 4);
+        (void)hipHostFree(host);
+    }
+    return rc;
+}
+
 int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     if (n <= 0 || n % 8) { fail("f32_to_bf16: n must be a positive multiple of 8"); return MI355_ERR_ARG; }

@@ -57,6 +57,11 @@ struct MMVQArgs {
 };
 
 hipError_t launch_mmvq(MMVQArgs a, hipStream_t st);
+// the kernel launch_mmvq takes for a launch (host logic, stated once: the launcher calls it): the weight stream, the register ring, the tiled kernel of 8- and
+// 16-token chunks, else the generic kernel
+enum { MMVQ_KERNEL_BASE = 0, MMVQ_KERNEL_RING = 1, MMVQ_KERNEL_STREAM = 2, MMVQ_KERNEL_TILED = 3 };
+// copy_behind (nullable): set where a.out_host is filled by a copy behind the kernel instead of by the kernel itself
+int mmvq_kernel_choice(const MMVQArgs &a, bool *copy_behind = nullptr);
 // single-token fast path (mmvq_fast.hip): persistent, software-pipelined; K % 2048 == 0, K-quant types
 void mmvq_fast_set_threads(int nt);
 // contraction lengths the register-ring mat-vec is instantiated for, in passes of 2048 (the last pass may be partial): 1-4 hidden sizes up to 8192, the rest
@@ -73,6 +78,12 @@ void mmvq_set_stream(bool on);                            // tests: route single
 bool mmvq_stream_applicable(const MMVQArgs &a);
 void mmvq_stream_set_anyorder_for_timing(bool on);   // tools/exp_stream.hip only: barrier-less dispatch, results undefined
 hipError_t launch_mmvq_stream(MMVQArgs a, hipStream_t st);
+// the form launch_mmvq_stream takes for a launch mmvq_stream_applicable accepts (host logic, stated once: the launcher works it out with the same function): the
+// role its shape gives it, the pass count, and which of the preloaded-argument kernels it starts (fast_ok: gate | up and the head; down_early: ffn_down at 6 / 7
+// passes).  moe / ternary launches take kernels of their own whatever the role.  `a` as launch_mmvq_stream gets it (unplanned).
+enum { ST_ROLE_ANY = 0, ST_ROLE_QKV = 1, ST_ROLE_GATE_UP = 2, ST_ROLE_DOWN = 3, ST_ROLE_HEAD = 4 };
+struct MMVQStreamForm { int role, kb; bool fast_ok, down_early, moe, ternary; };
+MMVQStreamForm mmvq_stream_form(const MMVQArgs &a);
 
 // workgroup ranges per segment for a grid of `blocks` workgroups, in proportion to the segments' bytes (what launch_mmvq_stream works out for its own launch)
 void mmvq_stream_plan(MMVQArgs &a, int blocks);

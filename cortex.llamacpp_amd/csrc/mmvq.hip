@@ -1034,16 +1034,32 @@ static void launch_nt(const MMVQArgs &a, int blocks, int bs, size_t lds, hipStre
 static bool g_stream_on = !(getenv("MI355_MMVQ_STREAM") && getenv("MI355_MMVQ_STREAM")[0] == '0');
 void mmvq_set_stream(bool on) { g_stream_on = on; }
 
+// the kernel a launch takes (kernels.h): launch_mmvq's own decision, and what the per-op test entry reports
+int mmvq_kernel_choice(const MMVQArgs &a, bool *copy_behind) {
+    static const bool fast_on = !(getenv("MI355_MMVQ_FAST") && getenv("MI355_MMVQ_FAST")[0] == '0');   // diagnosis switch
+    // single-token steps: the weight-stream kernel (LDS-DMA loader / consumer waves) where it has a form, else the register ring
+    if (fast_on && g_stream_on && mmvq_stream_applicable(a)) return MMVQ_KERNEL_STREAM;
+    if (a.out_host) {
+        // only the weight stream stores the second copy itself: any other kernel is followed by a copy of the finished row (same contract, one node more) - the
+        // kernel is that of the launch without the copy
+        MMVQArgs b = a;
+        b.out_host = nullptr;
+        if (copy_behind) *copy_behind = true;
+        return mmvq_kernel_choice(b, nullptr);
+    }
+    if (fast_on && mmvq_fast_applicable(a)) return MMVQ_KERNEL_RING;
+    if ((a.T == 16 || a.T == 8) && a.fuse_mode == 0) return MMVQ_KERNEL_TILED;
+    return MMVQ_KERNEL_BASE;
+}
+
 // host launcher: a.T tokens (1, 2 or 4 per launch; larger T is chunked by the caller).
 // EPI_SWIGLU: seg[0] = ffn_gate, seg[1] = ffn_up (same type), out = silu(gate) * up into seg[0].out.
 hipError_t launch_mmvq(MMVQArgs a, hipStream_t st) {
     static const bool fast_init = (mmvq_fast_set_threads(getenv("MI355_MMVQ_NT") ? atoi(getenv("MI355_MMVQ_NT")) : 0), true);
     (void)fast_init;
-    static const bool fast_on = !(getenv("MI355_MMVQ_FAST") && getenv("MI355_MMVQ_FAST")[0] == '0');   // diagnosis switch
-    // single-token steps: the weight-stream kernel (LDS-DMA loader / consumer waves) where it has a form, else the register ring
-    if (fast_on && g_stream_on && mmvq_stream_applicable(a)) return launch_mmvq_stream(a, st);
-    if (a.out_host) {
-        // only the weight stream stores the second copy itself: any other kernel is followed by a copy of the finished row (same contract, one node more)
+    bool copy_behind = false;
+    const int choice = mmvq_kernel_choice(a, &copy_behind);
+    if (copy_behind) {
         float *oh = a.out_host;
         a.out_host = nullptr;
         if (a.n_seg != 1 || a.T != 1) return hipErrorInvalidValue;
@@ -1051,8 +1067,9 @@ hipError_t launch_mmvq(MMVQArgs a, hipStream_t st) {
         if (e != hipSuccess) return e;
         return hipMemcpyAsync(oh, a.seg[0].out, (size_t)a.seg[0].n_rows * 4, hipMemcpyDeviceToHost, st);
     }
-    if (fast_on && mmvq_fast_applicable(a)) return launch_mmvq_fast(a, st);
-    if ((a.T == 16 || a.T == 8) && a.fuse_mode == 0) {
+    if (choice == MMVQ_KERNEL_STREAM) return launch_mmvq_stream(a, st);
+    if (choice == MMVQ_KERNEL_RING) return launch_mmvq_fast(a, st);
+    if (choice == MMVQ_KERNEL_TILED) {
         bool moe = false;
         for (int s = 0; s < a.n_seg; s++) moe |= a.seg[s].expert_sel != nullptr;
         if (!moe) return launch_tiled(a, st);

@@ -336,15 +336,15 @@ static StFast st_fast_pack(const MMVQArgs &a, int blocks) {
     return f;
 }
 
-hipError_t launch_mmvq_stream(MMVQArgs a, hipStream_t st) {
-    if (!mmvq_stream_applicable(a)) return hipErrorInvalidValue;
-    const int kb = (a.K + 2047) >> 11;
-    mmvq_stream_plan(a, num_cu());
-    const int blocks = a.seg_block0[3];
-    const size_t lds = (size_t)st_layout(kb).total;
+// the form of a PLANNED launch (a.n_seg is 1 for a SwiGLU pair: mmvq_stream_plan) on a grid of `blocks` workgroups; fp: the packed geometry where fast_ok
+static MMVQStreamForm stream_form_planned(const MMVQArgs &a, int blocks, StFast &fp) {
+    enum { ROLE_ANY = ST_ROLE_ANY, ROLE_QKV = ST_ROLE_QKV, ROLE_GATE_UP = ST_ROLE_GATE_UP, ROLE_DOWN = ST_ROLE_DOWN, ROLE_HEAD = ST_ROLE_HEAD };
+    MMVQStreamForm f{};
+    f.kb = (a.K + 2047) >> 11;
+    f.moe = a.n_sel > 1 || a.seg[0].expert_sel;
+    f.ternary = type_is_ternary(a.seg[0].type);
     // the role of the launch in a decode step, told from its shape (only the kernel's NAME depends on it): Q | K | V = two or three segments behind the fused
     // RMSNorm; gate | up = the SwiGLU pair; ffn_down = one segment that quantises its input and adds the residual; the head = one long segment behind the norm
-    enum { ROLE_ANY, ROLE_QKV, ROLE_GATE_UP, ROLE_DOWN, ROLE_HEAD };
     int role = ROLE_ANY;
     if (a.n_sel <= 1 && !a.seg[0].expert_sel) {
         if (a.fuse_mode == 1 && a.epi == EPI_SWIGLU) role = ROLE_GATE_UP;
@@ -352,14 +352,37 @@ hipError_t launch_mmvq_stream(MMVQArgs a, hipStream_t st) {
         else if (a.fuse_mode == 1 && a.epi == EPI_STORE && a.n_seg == 1 && a.seg[0].n_rows >= 16384) role = ROLE_HEAD;
         else if (a.fuse_mode == 2 && a.epi == EPI_ADD && a.n_seg == 1) role = ROLE_DOWN;
     }
-    const char *const role_name = role == ROLE_QKV ? "qkv" : role == ROLE_GATE_UP ? "gate_up" : role == ROLE_DOWN ? "ffn_down" : role == ROLE_HEAD ? "head" : "stream";
-    (void)role_name;
+    f.role = role;
     // the stream-bound roles start their stream from preloaded geometry where the packing fits (stream_body_fast)
     static const bool fast_off = getenv("MI355_STREAM_FAST_START") && getenv("MI355_STREAM_FAST_START")[0] == '0';
-    const StFast fp = (role == ROLE_GATE_UP || role == ROLE_HEAD) && !fast_off && !g_stream_anyorder ? st_fast_pack(a, blocks) : StFast{};
-    const bool fast_ok = (fp.kf >> 31) != 0;
+    fp = (role == ROLE_GATE_UP || role == ROLE_HEAD) && !fast_off && !g_stream_anyorder ? st_fast_pack(a, blocks) : StFast{};
+    f.fast_ok = (fp.kf >> 31) != 0 && !f.ternary;                 // (the ternary kernel has no preloaded-argument forms)
     static const bool down_early_off = getenv("MI355_STREAM_DOWN_EARLY") && getenv("MI355_STREAM_DOWN_EARLY")[0] == '0';
-    const bool down_early = !down_early_off && !g_stream_anyorder && a.nx && !a.out_host;
+    // (ffn_down's early activation requests: the 6- and 7-pass forms only)
+    f.down_early = role == ROLE_DOWN && !f.ternary && (f.kb == 6 || f.kb == 7) && !down_early_off && !g_stream_anyorder && a.nx && !a.out_host;
+    return f;
+}
+
+MMVQStreamForm mmvq_stream_form(const MMVQArgs &unplanned) {
+    MMVQArgs a = unplanned;
+    mmvq_stream_plan(a, num_cu());
+    StFast fp;
+    return stream_form_planned(a, a.seg_block0[3], fp);
+}
+
+hipError_t launch_mmvq_stream(MMVQArgs a, hipStream_t st) {
+    if (!mmvq_stream_applicable(a)) return hipErrorInvalidValue;
+    const int kb = (a.K + 2047) >> 11;
+    mmvq_stream_plan(a, num_cu());
+    const int blocks = a.seg_block0[3];
+    const size_t lds = (size_t)st_layout(kb).total;
+    enum { ROLE_ANY = ST_ROLE_ANY, ROLE_QKV = ST_ROLE_QKV, ROLE_GATE_UP = ST_ROLE_GATE_UP, ROLE_DOWN = ST_ROLE_DOWN, ROLE_HEAD = ST_ROLE_HEAD };
+    StFast fp;
+    const MMVQStreamForm form = stream_form_planned(a, blocks, fp);
+    const int role = form.role;
+    const char *const role_name = role == ROLE_QKV ? "qkv" : role == ROLE_GATE_UP ? "gate_up" : role == ROLE_DOWN ? "ffn_down" : role == ROLE_HEAD ? "head" : "stream";
+    (void)role_name;
+    const bool fast_ok = form.fast_ok, down_early = form.down_early;
 #define STREAM_K(KERNEL, KBV, FZ)                                                                                        \
     do {                                                                                                                 \
         /* (per launch: the attribute is per device, and a process may hold contexts on several) */                      \

@@ -381,7 +381,7 @@ bool Context::init(std::string &err) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, model->device) == hipSuccess) set_num_cu(prop.multiProcessorCount);
     err_epoch_seen_ = stream_error_epoch();
-    if (unsigned *ew = stream_error_word()) { mmvq_stream_set_error_word(ew); decode_engine_set_error_word(ew); attn_out_set_error_word(ew); tp_p2p_set_error_word(ew); }   // (per device: the pointer lives in device globals)
+    (void)install_stream_error_word();
 
     const size_t T = cp.n_ubatch, E = hp.n_embd, FF = hp.n_ff, G = hp.n_head_kv, D = hp.head_dim, NC = cp.n_ctx;
     cells_.assign(NC, KVCell());
@@ -917,7 +917,7 @@ void Context::prof_end() {
 
 // ------------------------------------------------------------------------------------------ linear layers
 
-static MMVQSeg make_seg(const DevTensor &w, float *out, int ld_out, const float *resid, const int32_t *esel) {
+MMVQSeg make_seg(const DevTensor &w, float *out, int ld_out, const float *resid, const int32_t *esel) {
     MMVQSeg s{};
     s.W = w.data; s.out = out; s.resid = resid; s.type = w.type; s.n_rows = (int)w.N; s.ld_out = ld_out; s.row_bytes = w.row_bytes;
     s.expert_sel = esel; s.expert_stride = w.row_bytes * (size_t)w.N;
@@ -933,7 +933,7 @@ static void chunk_act(MMVQArgs &a, const ActQuant &aq, int K, int t0) {
 }
 
 // a single-token mat-vec launch's description without its segments: the activation codes, the epilogue, the fused activation prologue (Fuse::mode)
-static MMVQArgs single_token_desc(int n_seg, int K, int epi, int fuse, const float *nx, const float *nw, float eps, const ActQuant &aq) {
+MMVQArgs single_token_desc(int n_seg, int K, int epi, int fuse, const float *nx, const float *nw, float eps, const ActQuant &aq) {
     MMVQArgs a{};
     a.n_seg = n_seg; a.K = K; a.T = 1; a.epi = epi;
     a.fuse_mode = fuse; a.nx = nx; a.nw = nw; a.neps = eps;
@@ -942,13 +942,20 @@ static MMVQArgs single_token_desc(int n_seg, int K, int epi, int fuse, const flo
 }
 
 // up to 3 quantised weight tensors sharing one activation (fused Q/K/V), or one tensor with an epilogue
-// (any whole number of super-blocks: the register-ring kernel's prologue stops at the row's end inside its last pass; the weight stream wants K % 1024 == 0
-// and leaves the other hidden sizes - Qwen2-7B's 3584, Llama-30B's 6656 - to the register ring)
+// (any whole number of super-blocks: the prologues of the register ring and of the weight stream stop at the row's end inside the last pass, so hidden sizes
+// like Qwen2-7B's 3584 and Llama-30B's 6656 - 14 and 26 super-blocks - stream too: mmvq_stream_applicable, tests/test_gpu_matvec_step.py k3584_* / k6656_*)
 // (a width that is no multiple of 256 - whole 32-element blocks, so every quantised tensor over it takes Q8_0 activations - goes to the generic mat-vec,
 // whose prologue takes a row that ends inside a 256-group: a step of such a file has as many launches as any other on that path)
 static bool can_fuse(int K, int T) { return T == 1 && K <= 8192 && (K & 31) == 0; }
 
-static hipError_t mmvq_tokens(MMVQSeg *segs, int n_seg, int K, int T, int epi, const ActQuant &aq, hipStream_t st, const Fuse &fz = Fuse()) {
+void MMVQTrace::note(const MMVQArgs &a) {
+    Rec r{};
+    r.T = a.T; r.kernel = mmvq_kernel_choice(a);
+    if (r.kernel == MMVQ_KERNEL_STREAM) r.form = mmvq_stream_form(a);
+    recs.push_back(r);
+}
+
+hipError_t mmvq_tokens(MMVQSeg *segs, int n_seg, int K, int T, int epi, const ActQuant &aq, hipStream_t st, const Fuse &fz, MMVQTrace *trace) {
     for (int t0 = 0; t0 < T;) {
         const int rem = T - t0, nt = rem >= 16 ? 16 : rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1;
         MMVQArgs a{};
@@ -961,6 +968,7 @@ static hipError_t mmvq_tokens(MMVQSeg *segs, int n_seg, int K, int T, int epi, c
             if (segs[s].resid) a.seg[s].resid = segs[s].resid + (size_t)t0 * segs[s].ld_out;
         }
         chunk_act(a, aq, K, t0);
+        if (trace) trace->note(a);
         hipError_t e = launch_mmvq(a, st);
         if (e != hipSuccess) return e;
         t0 += nt;
@@ -1211,6 +1219,12 @@ void set_decode_engine(int on) { g_decode_engine = on < 0 ? -1 : on ? 1 : 0; }
 static unsigned *stream_error_word() {
     static unsigned *w = [] { unsigned *p = nullptr; if (hipHostMalloc((void **)&p, 64, hipHostMallocDefault) != hipSuccess) p = nullptr; if (p) *p = 0u; return p; }();
     return w;
+}
+
+unsigned *install_stream_error_word() {
+    unsigned *ew = stream_error_word();
+    if (ew) { mmvq_stream_set_error_word(ew); decode_engine_set_error_word(ew); attn_out_set_error_word(ew); tp_p2p_set_error_word(ew); }   // (per device: the pointer lives in device globals)
+    return ew;
 }
 
 // The word is one per process (the kernels find it through a device global), but a process may hold several contexts (the engine's server_map_): the

@@ -81,6 +81,20 @@ struct Fuse {   // fused activation prologue of the single-token mat-vec (mmvq.h
     float *out_host = nullptr;   // the launch also stores its results here (pinned host memory; the output head of a single-token step) - weight stream only
 };
 
+// The mat-vec launches as a step issues them, shared with the per-op test entry (c_api.cc mi355_op_mat_vec_step) so that model and test run one piece of code:
+// a weight tensor as a launch segment; a single-token launch's description without its segments; T tokens as launches of 16 / 8 / 4 / 2 / 1.
+// trace (nullable): one record per launch issued - its token count and the kernel launch_mmvq takes for it (kernels.h mmvq_kernel_choice / mmvq_stream_form).
+struct MMVQTrace {
+    struct Rec { int T, kernel; MMVQStreamForm form; };
+    std::vector<Rec> recs;
+    void note(const MMVQArgs &a);
+};
+MMVQSeg make_seg(const DevTensor &w, float *out, int ld_out, const float *resid, const int32_t *esel);
+MMVQArgs single_token_desc(int n_seg, int K, int epi, int fuse, const float *nx, const float *nw, float eps, const ActQuant &aq);
+hipError_t mmvq_tokens(MMVQSeg *segs, int n_seg, int K, int T, int epi, const ActQuant &aq, hipStream_t st, const Fuse &fz = Fuse(), MMVQTrace *trace = nullptr);
+// the process's sticky error word installed in the device globals of the current device (what Context::init does); nullptr where it could not be allocated
+unsigned *install_stream_error_word();
+
 void set_moe_q80_grouped(bool on);  // tests / tools: MXFP4 expert tensors, prompt batches: one launch for all experts (default) or one per expert - the same bits
 void set_moe_group_min(int tokens);   // tests: batch size from which a mixture-of-experts feed-forward is grouped by expert
 void set_attn_store_fuse(bool on);   // tests: 0 = batched steps store K / V in their own launch before the attention

@@ -285,6 +285,20 @@ MI355_API int mi355_op_mul_mat_add(int32_t type, const void *W, int64_t N, int64
  * norm_w set: RMSNorm(x) * norm_w, then Q8_0 (Q | K | V, ffn_gate | ffn_up, the head); norm_w null: Q8_0 of x (ffn_down).  y[N] has the bits of the
  * quantiser's launch followed by mi355_op_mul_mat. */
 MI355_API int mi355_op_mul_mat_fused(int32_t type, const void *W, int64_t N, int64_t K, const float *x, const float *norm_w, float eps, float *y);
+/* Test hook: one mat-vec launch of a decode step, issued through the code the model issues it with (host/runtime.cc make_seg, single_token_desc, mmvq_tokens).
+ *   n_seg 1..3 weight tensors W[s] (ggml rows, quantised type types[s], N[s] rows of K) over the same activation x [T][K], 1 <= T <= 17 (launches of 16 / 8 / 4 / 2 / 1);
+ *   epi 0: y[s][t][n] = W[s][n] . a[t];  1 (one tensor): resid + that, resid [T][N[0] + ld_pad];  2 (two tensors, ffn_gate | ffn_up): y[0] = silu(y0) * y1;
+ *   fuse 0: a = the quantiser's launch over x;  1 (T == 1): RMSNorm(x, eps) * norm_w quantised in the launch's prologue;  2 (T == 1): x quantised there;
+ *   want_host_copy (T == 1, one tensor): y_host[N[0]] is the launch's second copy in pinned host memory;
+ *   n_sel 2..8 (T == 1; one tensor, or the SwiGLU pair): W[s] holds n_expert tensors back to back, expert_ids[n_sel] is read on the device, y[s] is
+ *   [n_sel][N[s] + ld_pad], and with fuse 2 x is [n_sel][K] (every expert quantises its own row) - the two launches of a mixture-of-experts step.
+ * Every y[s] is a whole out buffer, rows N[s] + ld_pad wide, filled with 0xFF bytes before the launch (y_host likewise): an unwritten result reads as NaN, a
+ * write past N[s] shows in the pad columns.  path[40]: 8 words per launch issued, in order - tokens, kernel (0 generic, 1 register ring, 2 weight stream,
+ * 3 tiled), and for the weight stream its role (0 any, 1 qkv, 2 gate_up, 3 ffn_down, 4 head), passes of 2048, fast_ok, down_early, moe, ternary; zero beyond.
+ * MI355_ERR_HIP where a launch fails or a weight-stream kernel raises the process's stream error word. */
+MI355_API int mi355_op_mat_vec_step(int32_t n_seg, const int32_t *types, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, int32_t epi,
+                                    const float *resid, int32_t fuse, const float *norm_w, float eps, int32_t want_host_copy, int32_t n_sel, int32_t n_expert,
+                                    const int32_t *expert_ids, int64_t ld_pad, float *const *y, float *y_host, int32_t *path);
 /* ggml's f32 -> bf16 rounding as the bf16 kernels' activation pass does it (nearest, ties to even; NaN quieted; subnormals kept); n % 8 == 0 */
 MI355_API int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out);
 /* Up to three BF16 tensors W[s] ([N[s]][K] bf16 rows, K % 8 == 0; the matrix cores want K % 16 == 0) against the same T rows of x, as a decoder layer launches them:

@@ -67,6 +67,15 @@ def test_no_cpu_fallback(pkg):
     for grouped in (0, 1):
         assert lib.mi355_op_moe_combine(x.ctypes.data, x.ctypes.data, x.ctypes.data, 1, 256, 1, grouped, zero.ctypes.data, y.ctypes.data) == -100
     assert lib.mi355_op_gather_rows_f32(x.ctypes.data, 1, 256, zero.ctypes.data, 1, y.ctypes.data) == -100
+    # the decode step's mat-vec launch: one Q8_0 row of 256 (8 blocks of 34 bytes)
+    import ctypes as C
+    w = np.zeros(8 * 34, np.uint8)
+    t8 = np.full(1, 8, np.int32)
+    n1 = np.ones(1, np.int64)
+    path = np.zeros(40, np.int32)
+    wp, yp = (C.c_void_p * 1)(w.ctypes.data), (C.c_void_p * 1)(y.ctypes.data)
+    assert lib.mi355_op_mat_vec_step(1, t8.ctypes.data, wp, n1.ctypes.data, 256, x.ctypes.data, 1, 0, None, 0, None, 0.0, 0, 0, 1, None, 0, yp, None,
+                                     path.ctypes.data) == -100
 
 
 def test_product_does_not_touch_oracle():
