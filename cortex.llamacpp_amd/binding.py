@@ -38,6 +38,15 @@ class Batch(C.Structure):
                 ("seq_id", C.POINTER(C.POINTER(C.c_int32))), ("logits", C.POINTER(C.c_int8))]
 
 
+class PplStats(C.Structure):           # mi355_ppl_stats
+    _fields_ = [("n_chunks", C.c_int64), ("count", C.c_int64), ("top1", C.c_int64), ("dead", C.c_int64), ("same_top", C.c_int64),
+                ("has_base", C.c_int32), ("stopped", C.c_int32),
+                ("nll", C.c_double), ("nll2", C.c_double), ("nll_base", C.c_double), ("nll2_base", C.c_double), ("kl", C.c_double), ("kl2", C.c_double)]
+
+
+PPL_CALLBACK = C.CFUNCTYPE(C.c_int32, C.POINTER(PplStats), C.c_void_p)
+
+
 # every symbol include/mi355_llama.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _u32, _u64, _f32, _sz, _cp = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t, C.c_char_p
 ENGINE_CB = C.CFUNCTYPE(None, C.c_char_p, C.c_char_p, C.c_void_p)
@@ -80,6 +89,9 @@ SYMBOLS = {
     "mi355_get_argmax_ith": (_i32, [_vp, _i32]),
     "mi355_get_argmax_prob_ith": (_i32, [_vp, _i32, _vp]),
     "mi355_spec_verify": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "mi355_get_token_logprobs": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "mi355_logits_kl": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "mi355_perplexity": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mi355_speculative_steps": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "mi355_get_topk_ith": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "mi355_debug_mega_steps": (C.c_int64, [_vp]),
@@ -133,6 +145,8 @@ SYMBOLS = {
     "mi355_op_argmax_rows": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp]),
     "mi355_op_argmax_prob_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "mi355_op_spec_verify": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "mi355_op_token_logprob_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "mi355_op_logits_kl_rows": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
     "mi355_op_topk_rows": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_moe_group": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_moe_gather_act": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -491,6 +505,34 @@ class Backend:
         self._chk(self.lib.mi355_op_spec_verify(_ptr(logits), logits.shape[1], logits.shape[0], _ptr(rows), R, _ptr(gs), G, _ptr(draft), _ptr(ids), _ptr(acc)),
                   "op_spec_verify")
         return ids, acc[:G]
+
+    def token_logprob_rows(self, base: np.ndarray, targets, rows=None):
+        """(log-probability f32 [R], rank int32 [R]) of targets[r] in base[rows[r]] (rows None: row r) over the whole row (mi355_op_token_logprob_rows)."""
+        base = np.ascontiguousarray(base, np.float32)
+        base = base.reshape(1, -1) if base.ndim == 1 else base
+        targets = np.ascontiguousarray(targets, np.int32).reshape(-1)
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32).reshape(-1)
+        R = targets.size
+        assert rows is None or rows.size == R
+        lp = np.full(R, 7.0, np.float32); rank = np.full(R, -7, np.int32)
+        self._chk(self.lib.mi355_op_token_logprob_rows(_ptr(base), base.shape[1], base.shape[0], None if rows is None else _ptr(rows), _ptr(targets), R, _ptr(lp),
+                                                       _ptr(rank)), "op_token_logprob_rows")
+        return lp, rank
+
+    def logits_kl_rows(self, p: np.ndarray, q: np.ndarray, rows_p=None, rows_q=None):
+        """(KL(P || Q) f32 [R], same_top int32 [R]) of the pairs (p[rows_p[r]], q[rows_q[r]]) (None: row r) (mi355_op_logits_kl_rows)."""
+        p = np.ascontiguousarray(p, np.float32); q = np.ascontiguousarray(q, np.float32)
+        p = p.reshape(1, -1) if p.ndim == 1 else p
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        assert p.shape[1] == q.shape[1]
+        rows_p = None if rows_p is None else np.ascontiguousarray(rows_p, np.int32).reshape(-1)
+        rows_q = None if rows_q is None else np.ascontiguousarray(rows_q, np.int32).reshape(-1)
+        R = rows_p.size if rows_p is not None else rows_q.size if rows_q is not None else min(p.shape[0], q.shape[0])
+        assert (rows_p is None or rows_p.size == R) and (rows_q is None or rows_q.size == R)
+        kl = np.full(R, 7.0, np.float32); top = np.full(R, -7, np.int32)
+        self._chk(self.lib.mi355_op_logits_kl_rows(_ptr(p), p.shape[0], _ptr(q), q.shape[0], p.shape[1], None if rows_p is None else _ptr(rows_p),
+                                                   None if rows_q is None else _ptr(rows_q), R, _ptr(kl), _ptr(top)), "op_logits_kl_rows")
+        return kl, top
 
     @staticmethod
     def topk_decode(keys: np.ndarray):
@@ -1103,6 +1145,72 @@ class Context:
         if r != R:
             raise MI355Error(f"mi355_spec_verify failed: {_err(self.lib)}")
         return ids, acc
+
+    def token_logprobs(self, batch_rows, targets):
+        """(log-probability f32 [n], rank int32 [n]) of targets[r] in row batch_rows[r] of the last decode, over the whole vocabulary, from the device logits
+        (mi355_get_token_logprobs).  rank 0: the target is the row's arg-max.  A dead row gives NaN and -1."""
+        rows = np.ascontiguousarray(batch_rows, np.int32).reshape(-1)
+        tg = np.ascontiguousarray(targets, np.int32).reshape(-1)
+        if rows.size < 1 or rows.size != tg.size:
+            raise ValueError("token_logprobs: batch_rows [n] and targets [n], n >= 1")
+        lp = np.zeros(rows.size, np.float32); rank = np.zeros(rows.size, np.int32)
+        if self.lib.mi355_get_token_logprobs(self.h, rows.size, _ptr(rows), _ptr(tg), _ptr(lp), _ptr(rank)) != rows.size:
+            raise MI355Error(f"mi355_get_token_logprobs failed: {_err(self.lib)}")
+        return lp, rank
+
+    def logits_kl(self, base: "Context", rows_base, rows):
+        """(KL(base || self) f32 [n], same_top int32 [n]) of row rows_base[r] of base's last decode against row rows[r] of this context's (mi355_logits_kl)."""
+        rb = np.ascontiguousarray(rows_base, np.int32).reshape(-1)
+        rs = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        if rb.size < 1 or rb.size != rs.size:
+            raise ValueError("logits_kl: rows_base [n] and rows [n], n >= 1")
+        kl = np.zeros(rb.size, np.float32); top = np.zeros(rb.size, np.int32)
+        if self.lib.mi355_logits_kl(self.h, base.h, rb.size, _ptr(rb), _ptr(rs), _ptr(kl), _ptr(top)) != rb.size:
+            raise MI355Error(f"mi355_logits_kl failed: {_err(self.lib)}")
+        return kl, top
+
+    def perplexity(self, tokens, n_chunk: int, bos: int = -1, seq: int = 0, base: "Context" = None, callback=None) -> dict:
+        """The llama-perplexity procedure over `tokens` in chunks of n_chunk (mi355_perplexity): a dict of the mi355_ppl_stats fields plus "logprobs" (f32, one per
+        scored position, NaN for a dead row), with a base context also "kls", and the derived "ppl" / "ppl_base" / "mean_kl".  callback(stats dict) runs after
+        every chunk; a true return stops the run."""
+        tk = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        n_chunk = int(n_chunk)
+        per = max(0, n_chunk - 1 - n_chunk // 2)
+        n_out = max(1, (tk.size // max(n_chunk, 1)) * per)
+        lp = np.full(n_out, np.nan, np.float32)
+        kl = np.full(n_out, np.nan, np.float32) if base is not None else None
+        st = PplStats()
+
+        def as_dict(s):
+            return {name: getattr(s, name) for name, _ in PplStats._fields_}
+
+        raised = []
+
+        def tramp(sp, _user):
+            try:
+                return 1 if callback(as_dict(sp.contents)) else 0
+            except BaseException as ex:          # (an exception must not cross the C frames)
+                raised.append(ex)
+                return 1
+
+        cb = PPL_CALLBACK(tramp) if callback is not None else None
+        r = self.lib.mi355_perplexity(self.h, base.h if base is not None else None, _ptr(tk), tk.size, n_chunk, int(bos), int(seq), _ptr(lp),
+                                      _ptr(kl) if kl is not None else None, C.cast(cb, C.c_void_p) if cb is not None else None, None, C.byref(st))
+        if raised:
+            raise raised[0]
+        if r != 0:
+            raise MI355Error(f"mi355_perplexity failed: {_err(self.lib)}")
+        out = as_dict(st)
+        n_scored = int(st.n_chunks) * per
+        out["logprobs"] = lp[:n_scored]
+        if kl is not None:
+            out["kls"] = kl[:n_scored]
+        if st.count > 0:
+            out["ppl"] = float(np.exp(st.nll / st.count))
+            if base is not None:
+                out["ppl_base"] = float(np.exp(st.nll_base / st.count))
+                out["mean_kl"] = st.kl / st.count
+        return out
 
     def speculative_steps(self, draft_ctx: "Context", first: int, pos0: int, n: int, n_max: int = 16, n_min: int = 0, p_min: float = 0.75, seq: int = 0):
         """n greedy tokens with draft_ctx's model drafting up to n_max per round (mi355_speculative_steps); both contexts hold `seq` over [0, pos0).

@@ -269,6 +269,49 @@ int32_t mi355_spec_verify(mi355_context *ctx, int32_t n_groups, const int32_t *g
         return r;
     )
 }
+// ---- perplexity and KL divergence (csrc/logprob.hip)
+int32_t mi355_get_token_logprobs(mi355_context *ctx, int32_t n, const int32_t *batch_rows, const mi355_token *targets, float *logprob_out, int32_t *rank_out) {
+    if (!ctx) return no_context("get_token_logprobs");
+    MI355_GUARD(return MI355_ERR_ARG,
+        const int r = ctx->c->token_logprobs(n, batch_rows, targets, logprob_out, rank_out);
+        if (r < 0) { fail(ctx->c->last_error.empty() ? "token_logprobs failed" : ctx->c->last_error); return MI355_ERR_ARG; }
+        return r;
+    )
+}
+int32_t mi355_logits_kl(mi355_context *ctx, mi355_context *ctx_base, int32_t n, const int32_t *rows_base, const int32_t *rows, float *kl_out, int32_t *same_top_out) {
+    if (!ctx || !ctx_base) return no_context("logits_kl");
+    MI355_GUARD(return MI355_ERR_ARG,
+        const int r = ctx->c->logits_kl(*ctx_base->c, n, rows_base, rows, kl_out, same_top_out);
+        if (r < 0) { fail(ctx->c->last_error.empty() ? "logits_kl failed" : ctx->c->last_error); return MI355_ERR_ARG; }
+        return r;
+    )
+}
+namespace {
+struct PplCallback { mi355_ppl_callback cb; void *user; };
+void ppl_stats_out(const Context::PplStats &s, mi355_ppl_stats *o) {
+    o->n_chunks = s.n_chunks; o->count = s.count; o->top1 = s.top1; o->dead = s.dead; o->same_top = s.same_top;
+    o->has_base = s.has_base; o->stopped = s.stopped;
+    o->nll = s.nll; o->nll2 = s.nll2; o->nll_base = s.nll_base; o->nll2_base = s.nll2_base; o->kl = s.kl; o->kl2 = s.kl2;
+}
+int ppl_trampoline(const Context::PplStats &s, void *p) {
+    const PplCallback *c = static_cast<const PplCallback *>(p);
+    mi355_ppl_stats o;
+    ppl_stats_out(s, &o);
+    return c->cb(&o, c->user);
+}
+}  // namespace
+int32_t mi355_perplexity(mi355_context *ctx, mi355_context *ctx_base, const mi355_token *tokens, int64_t n_tokens, int32_t n_chunk, mi355_token bos, mi355_seq_id seq,
+                         float *logprob_out, float *kl_out, mi355_ppl_callback cb, void *user, mi355_ppl_stats *stats) {
+    if (!ctx || !tokens || !stats) return no_context("perplexity");
+    MI355_GUARD(return MI355_ERR_ARG,
+        PplCallback pc{cb, user};
+        Context::PplStats st;
+        const int r = ctx->c->perplexity(tokens, n_tokens, n_chunk, bos, seq, ctx_base ? ctx_base->c : nullptr, logprob_out, kl_out, cb ? ppl_trampoline : nullptr, &pc, st);
+        ppl_stats_out(st, stats);
+        if (r < 0) { fail(ctx->c->last_error.empty() ? "perplexity failed" : ctx->c->last_error); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
 // The greedy loop with a draft model beside the target (the round: DESIGN.md §4.9).  `p` is the position of `last`, the newest emitted token, which neither
 // context has decoded yet; the draft context holds [0, dpos) and `pend` is what it has still to see (positions dpos .. p).
 int32_t mi355_speculative_steps(mi355_context *ctx_tgt, mi355_context *ctx_dft, mi355_token first, mi355_pos pos0, mi355_seq_id seq, int32_t n, int32_t n_max,
@@ -1444,6 +1487,46 @@ int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, co
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "spec_verify");
     return di.down(ids_out, (size_t)R * 4) && da.down(n_accept_out, (size_t)G * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_token_logprob_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, const int32_t *targets, int32_t R, float *logprob_out,
+                                int32_t *rank_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!base || !targets || !logprob_out || !rank_out || n < 1 || n > SPEC_MAX_N || n_base_rows < 1 || R < 1 || R > 65535 || (!rows && R > n_base_rows)) {
+        fail("token_logprob_rows: bad shape"); return MI355_ERR_ARG;
+    }
+    for (int r = 0; r < R; r++) {
+        if (rows && (rows[r] < 0 || rows[r] >= n_base_rows)) { fail("token_logprob_rows: rows[" + std::to_string(r) + "] outside the base"); return MI355_ERR_ARG; }
+        if (targets[r] < 0 || targets[r] >= n) { fail("token_logprob_rows: targets[" + std::to_string(r) + "] outside [0, n)"); return MI355_ERR_ARG; }
+    }
+    const size_t nb = (size_t)n_base_rows * (size_t)n * 4;
+    DevBuf db(nb), dr((size_t)R * 4), dt((size_t)R * 4), dl((size_t)R * 4), dk((size_t)R * 4), ds(token_logprob_scratch_words(R) * 4);
+    if (!db.up(base, nb) || (rows && !dr.up(rows, (size_t)R * 4)) || !dt.up(targets, (size_t)R * 4) || !dr.p || !dl.p || !dk.p || !ds.p) return MI355_ERR_OOM;
+    hipError_t e = launch_token_logprob_rows(db.as<float>(), (int)n, rows ? dr.as<int32_t>() : nullptr, dt.as<int32_t>(), R, dl.as<float>(), dk.as<int32_t>(), ds.as<float>(),
+                                             R, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "token_logprob_rows");
+    return dl.down(logprob_out, (size_t)R * 4) && dk.down(rank_out, (size_t)R * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_logits_kl_rows(const float *p, int32_t n_p_rows, const float *q, int32_t n_q_rows, int64_t n, const int32_t *rows_p, const int32_t *rows_q, int32_t R,
+                            float *kl_out, int32_t *same_top_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!p || !q || !kl_out || !same_top_out || n < 1 || n > SPEC_MAX_N || n_p_rows < 1 || n_q_rows < 1 || R < 1 || R > 65535 || (!rows_p && R > n_p_rows) ||
+        (!rows_q && R > n_q_rows)) { fail("logits_kl_rows: bad shape"); return MI355_ERR_ARG; }
+    for (int r = 0; r < R; r++)
+        if ((rows_p && (rows_p[r] < 0 || rows_p[r] >= n_p_rows)) || (rows_q && (rows_q[r] < 0 || rows_q[r] >= n_q_rows))) {
+            fail("logits_kl_rows: row " + std::to_string(r) + " outside its base"); return MI355_ERR_ARG;
+        }
+    const size_t nbp = (size_t)n_p_rows * (size_t)n * 4, nbq = (size_t)n_q_rows * (size_t)n * 4;
+    DevBuf dp(nbp), dq(nbq), drp((size_t)R * 4), drq((size_t)R * 4), dk((size_t)R * 4), dt((size_t)R * 4), ds(logits_kl_scratch_words(R) * 4);
+    if (!dp.up(p, nbp) || !dq.up(q, nbq) || (rows_p && !drp.up(rows_p, (size_t)R * 4)) || (rows_q && !drq.up(rows_q, (size_t)R * 4)) || !drp.p || !drq.p || !dk.p || !dt.p ||
+        !ds.p) return MI355_ERR_OOM;
+    hipError_t e = launch_logits_kl_rows(dp.as<float>(), dq.as<float>(), (int)n, rows_p ? drp.as<int32_t>() : nullptr, rows_q ? drq.as<int32_t>() : nullptr, R, dk.as<float>(),
+                                         dt.as<int32_t>(), ds.as<float>(), R, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "logits_kl_rows");
+    return dk.down(kl_out, (size_t)R * 4) && dt.down(same_top_out, (size_t)R * 4) ? MI355_OK : MI355_ERR_HIP;
 }
 
 int mi355_op_topk_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t n_rows, int32_t k, const int32_t *adj_n,

@@ -238,6 +238,22 @@ hipError_t launch_argmax_prob_rows(const float *x, int n, const int32_t *rows_de
 size_t spec_verify_scratch_words(int cap_rows);
 hipError_t launch_spec_verify(const float *base, int n, const int32_t *rows_dev, int R, const int32_t *group_start_dev, int G, const int32_t *draft_dev,
                               int32_t *ids_out, int32_t *n_accept_out, float *scratch, int cap_rows, hipStream_t st);
+// ---- perplexity and KL divergence (logprob.hip): argmax_prob's shape and index rule, n <= SPEC_MAX_N, rows <= cap_rows and <= 65535 per
+// launch.  Everything in f32, summation orders fixed: the same bits run to run.
+// Row r = base row rows_dev[r] (nullptr: row r), target t = targets_dev[r] in [0, n): logprob_out[r] = x_t - M - log(S), M the row maximum and
+// S = sum exp(x_j - M) over the non-NaN entries; rank_out[r] = how many non-NaN entries beat the target under the arg-max rule (greater, or equal at a lower
+// index).  M not finite or x_t NaN: logprob NaN, rank -1.  x_t = -inf under a finite M: -inf and the count.
+// scratch: token_logprob_scratch_words(cap_rows) words, zero-filled once (ticket words at the head)
+size_t token_logprob_scratch_words(int cap_rows);
+hipError_t launch_token_logprob_rows(const float *base, int n, const int32_t *rows_dev, const int32_t *targets_dev, int R, float *logprob_out, int32_t *rank_out,
+                                     float *scratch, int cap_rows, hipStream_t st);
+// Row pair r = (x = base_p row rows_p_dev[r], y = base_q row rows_q_dev[r]) (nullptr: row r): kl_out[r] = KL(P || Q) = A / S_p - (lse_p - lse_q) with
+// A = sum_j exp(x_j - M_p) (x_j - y_j) and lse = M + log S formed by one operation sequence for both rows (identical rows: exactly 0); not clamped at 0.
+// same_top_out[r] = 1 where both rows have the same arg-max, else 0.  A non-finite entry in either row: kl NaN, same_top -1.
+// scratch: logits_kl_scratch_words(cap_rows) words, zero-filled once
+size_t logits_kl_scratch_words(int cap_rows);
+hipError_t launch_logits_kl_rows(const float *base_p, const float *base_q, int n, const int32_t *rows_p_dev, const int32_t *rows_q_dev, int R, float *kl_out,
+                                 int32_t *same_top_out, float *scratch, int cap_rows, hipStream_t st);
 // ---- device-side sampling front end (reference call site common_sampler_sample, src/llama_server_context.cc:1679-1698): the k best
 // candidates of a logits row after logit_bias and the repetition / frequency / presence penalties, so that k (token, logit) pairs cross to the host
 // instead of the 513 KB row.  Order = the host sampler's (host/sampling.cc `better`): higher logit first, lower token id on ties; -0.0 and +0.0 tie

@@ -331,6 +331,7 @@ Context::~Context() {
     if (h_topk_) (void)hipHostFree(h_topk_);
     if (h_topk_adj_) (void)hipHostFree(h_topk_adj_);
     if (h_spec_) (void)hipHostFree(h_spec_);
+    if (h_lp_) (void)hipHostFree(h_lp_);
     if (d_topk_adj_) (void)hipFree(d_topk_adj_);
     if (topk_scratch_) { (void)hipFree(topk_scratch_); topk_scratch_ = nullptr; }
     if (h_moe_meta_) (void)hipHostFree(h_moe_meta_);
@@ -2444,6 +2445,194 @@ int Context::spec_verify(int n_groups, const int32_t *group_start, const int32_t
     memcpy(ids_out, h_ids, (size_t)R * 4);
     memcpy(n_accept_out, h_acc, (size_t)n_groups * 4);
     return R;
+}
+
+// ---- perplexity and KL divergence (csrc/logprob.hip): d_logits_ again; a launch takes at most n_ubatch rows (the scratch's size), a call
+// queues as many launches as its rows need, the kernels write their two words per row straight into pinned memory, and ONE synchronisation ends the call
+bool Context::logprob_prepare(int n) {
+    if (hipSetDevice(model->device) != hipSuccess) { last_error = "logprob: cannot select the device"; return false; }
+    const int cap = (int)std::min<uint32_t>(std::max<uint32_t>(cp.n_ubatch, 1), 65535);
+    if (!lp_scratch_) {
+        (void)hipStreamSynchronize(stream_);
+        lp_scratch_ = (float *)dalloc((token_logprob_scratch_words(cap) + logits_kl_scratch_words(cap)) * 4);   // (zero-filled: the ticket words)
+        (void)hipDeviceSynchronize();                                  // the null-stream zero-fill (see init)
+        if (!lp_scratch_) { last_error = "logprob workspace allocation failed"; return false; }
+    }
+    if (n > lp_cap_) {
+        (void)hipStreamSynchronize(stream_);
+        const int want = std::max(n, cap);
+        if (h_lp_) { (void)hipHostFree(h_lp_); h_lp_ = nullptr; }
+        lp_cap_ = 0;
+        if (d_lp_in_) {                                                // (the stream is idle: the block it outgrew goes back, as decode does with d_logits_)
+            (void)hipFree(d_lp_in_);
+            allocs_.erase(std::find(allocs_.begin(), allocs_.end(), (void *)d_lp_in_));
+            d_lp_in_ = nullptr;
+        }
+        d_lp_in_ = (int32_t *)dalloc((size_t)want * 2 * 4);
+        if (!d_lp_in_ || hipHostMalloc((void **)&h_lp_, (size_t)want * 4 * 4, hipHostMallocDefault) != hipSuccess) { h_lp_ = nullptr; last_error = "logprob workspace allocation failed"; return false; }
+        lp_cap_ = want;
+        (void)hipDeviceSynchronize();
+    }
+    return true;
+}
+
+// batch rows -> rows of d_logits_, every one flagged
+bool Context::logprob_rows(const char *what, int n, const int32_t *batch_rows, int32_t *dst) {
+    const int nb = (int)out_row_of_batch_.size();
+    for (int r = 0; r < n; r++) {
+        int i = batch_rows[r];
+        if (i < 0) i += nb;
+        if (i < 0 || i >= nb || out_row_of_batch_[(size_t)i] < 0) { last_error = std::string(what) + ": batch row " + std::to_string(batch_rows[r]) + " was not flagged for logits"; return false; }
+        dst[r] = out_row_of_batch_[(size_t)i];
+    }
+    return true;
+}
+
+int Context::token_logprobs(int n, const int32_t *batch_rows, const int32_t *targets, float *logprob_out, int32_t *rank_out) {
+    if (last_was_embd_) { last_error = "token_logprobs: embeddings mode computes no logits"; return -1; }
+    if (model->hp.tp_size > 1) { last_error = "token_logprobs: not on a rank of a row split"; return -1; }
+    if (n < 1 || !batch_rows || !targets || !logprob_out) { last_error = "token_logprobs: bad arguments"; return -1; }
+    const int V = model->hp.n_vocab;
+    for (int r = 0; r < n; r++)
+        if (targets[r] < 0 || targets[r] >= V) { last_error = "token_logprobs: target " + std::to_string(targets[r]) + " outside [0, " + std::to_string(V) + ")"; return -1; }
+    std::vector<int32_t> rows((size_t)n);
+    if (!logprob_rows("token_logprobs", n, batch_rows, rows.data())) return -1;
+    if (!logprob_prepare(n)) return -1;
+    // pinned: rows | targets, then logprob | rank
+    int32_t *h_rows = h_lp_, *h_tgt = h_lp_ + n, *h_rank = h_lp_ + 2 * (size_t)lp_cap_ + n;
+    float *h_out = reinterpret_cast<float *>(h_lp_ + 2 * (size_t)lp_cap_);
+    memcpy(h_rows, rows.data(), (size_t)n * 4);
+    memcpy(h_tgt, targets, (size_t)n * 4);
+    if (hipMemcpyAsync(d_lp_in_, h_lp_, (size_t)n * 2 * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "token_logprobs staging failed"; return -1; }
+    const int cap = (int)std::min<uint32_t>(std::max<uint32_t>(cp.n_ubatch, 1), 65535);
+    for (int r0 = 0; r0 < n; r0 += cap) {
+        const int R = std::min(cap, n - r0);
+        if (launch_token_logprob_rows(d_logits_, V, d_lp_in_ + r0, d_lp_in_ + n + r0, R, h_out + r0, h_rank + r0, lp_scratch_, cap, stream_) != hipSuccess) {
+            (void)hipStreamSynchronize(stream_);
+            last_error = "token_logprobs launch failed"; return -1;
+        }
+    }
+    if (hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
+    argmax_fetched_ = true;
+    memcpy(logprob_out, h_out, (size_t)n * 4);
+    if (rank_out) memcpy(rank_out, h_rank, (size_t)n * 4);
+    return n;
+}
+
+int Context::logits_kl(Context &base, int n, const int32_t *rows_base, const int32_t *rows_self, float *kl_out, int32_t *same_top_out) {
+    if (&base == this) { last_error = "logits_kl: the base and the model under test are the same context"; return -1; }
+    if (last_was_embd_ || base.last_was_embd_) { last_error = "logits_kl: embeddings mode computes no logits"; return -1; }
+    if (model->hp.tp_size > 1 || base.model->hp.tp_size > 1) { last_error = "logits_kl: not on a rank of a row split"; return -1; }
+    if (base.model->hp.n_vocab != model->hp.n_vocab) {
+        last_error = "logits_kl: n_vocab differs (base " + std::to_string(base.model->hp.n_vocab) + ", this " + std::to_string(model->hp.n_vocab) + ")"; return -1;
+    }
+    if (base.model->device != model->device) { last_error = "logits_kl: the two contexts are on different devices"; return -1; }
+    if (n < 1 || !rows_base || !rows_self || !kl_out) { last_error = "logits_kl: bad arguments"; return -1; }
+    std::vector<int32_t> rp((size_t)n), rq((size_t)n);
+    if (!base.logprob_rows("logits_kl (base)", n, rows_base, rp.data())) { last_error = base.last_error; return -1; }
+    if (!logprob_rows("logits_kl", n, rows_self, rq.data())) return -1;
+    if (!logprob_prepare(n)) return -1;
+    // the base's rows are final before this stream reads them; its step is checked like any of its own reads would
+    if (hipStreamSynchronize(base.stream_) != hipSuccess || !base.mega_check() || !base.stream_check()) { last_error = base.last_error.empty() ? "logits_kl: the base context's step failed" : base.last_error; return -1; }
+    int32_t *h_top = h_lp_ + 2 * (size_t)lp_cap_ + n;
+    float *h_out = reinterpret_cast<float *>(h_lp_ + 2 * (size_t)lp_cap_);
+    memcpy(h_lp_, rp.data(), (size_t)n * 4);
+    memcpy(h_lp_ + n, rq.data(), (size_t)n * 4);
+    if (hipMemcpyAsync(d_lp_in_, h_lp_, (size_t)n * 2 * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "logits_kl staging failed"; return -1; }
+    const int cap = (int)std::min<uint32_t>(std::max<uint32_t>(cp.n_ubatch, 1), 65535);
+    float *scratch = lp_scratch_ + token_logprob_scratch_words(cap);
+    for (int r0 = 0; r0 < n; r0 += cap) {
+        const int R = std::min(cap, n - r0);
+        if (launch_logits_kl_rows(base.d_logits_, d_logits_, model->hp.n_vocab, d_lp_in_ + r0, d_lp_in_ + n + r0, R, h_out + r0, h_top + r0, scratch, cap, stream_) != hipSuccess) {
+            (void)hipStreamSynchronize(stream_);
+            last_error = "logits_kl launch failed"; return -1;
+        }
+    }
+    if (hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
+    argmax_fetched_ = true;
+    memcpy(kl_out, h_out, (size_t)n * 4);
+    if (same_top_out) memcpy(same_top_out, h_top, (size_t)n * 4);
+    return n;
+}
+
+int Context::perplexity(const int32_t *tokens, int64_t n_tokens, int n_chunk, int32_t bos, int seq, Context *base, float *logprob_out, float *kl_out,
+                        int (*cb)(const PplStats &, void *), void *user, PplStats &st) {
+    st = PplStats();
+    st.has_base = base ? 1 : 0;
+    if (!tokens || n_tokens < 0) { last_error = "perplexity: bad arguments"; return -1; }
+    if (seq < 0 || seq >= 64) { last_error = "perplexity: seq id " + std::to_string(seq) + " out of range [0, 64)"; return -1; }
+    if (n_chunk < 2 || (uint32_t)n_chunk > cp.n_ctx || (base && (uint32_t)n_chunk > base->cp.n_ctx)) {
+        last_error = "perplexity: n_chunk " + std::to_string(n_chunk) + " outside [2, n_ctx " + std::to_string(base ? std::min(cp.n_ctx, base->cp.n_ctx) : cp.n_ctx) + "]"; return -1;
+    }
+    if (base == this) { last_error = "perplexity: the base and the model under test are the same context"; return -1; }
+    if (base && base->model->hp.n_vocab != model->hp.n_vocab) { last_error = "perplexity: n_vocab differs between the base and the model under test"; return -1; }
+    if (base && base->model->device != model->device) { last_error = "perplexity: the two contexts are on different devices"; return -1; }
+    if (bos >= model->hp.n_vocab) { last_error = "perplexity: bos outside the vocabulary"; return -1; }
+    const int64_t n_chunks = n_tokens / n_chunk;
+    const int first = n_chunk / 2, per = n_chunk - 1 - first;          // scored positions first .. n_chunk - 2
+    const int piece_max = (int)std::min(cp.n_ubatch, base ? base->cp.n_ubatch : cp.n_ubatch);
+    std::vector<int32_t> tk((size_t)n_chunk), pos((size_t)piece_max), nseq((size_t)piece_max, 1), rows, tgt;
+    std::vector<int8_t> flags((size_t)piece_max);
+    std::vector<int32_t *> seqs((size_t)piece_max);
+    std::vector<float> lp, lpb, kl;
+    std::vector<int32_t> rank, top;
+    int32_t sid = seq;
+    for (auto &p : seqs) p = &sid;
+    int rc = 0;
+    for (int64_t c = 0; c < n_chunks && rc == 0; c++) {
+        kv_seq_rm(seq, 0, -1);
+        if (base) base->kv_seq_rm(seq, 0, -1);
+        memcpy(tk.data(), tokens + c * n_chunk, (size_t)n_chunk * 4);
+        if (bos >= 0) tk[0] = bos;
+        int64_t at = c * per;
+        PplStats cur = st;                                             // a chunk enters the stats whole or not at all
+        for (int i0 = 0; i0 < n_chunk && rc == 0; i0 += piece_max) {
+            const int n = std::min(piece_max, n_chunk - i0);
+            rows.clear(); tgt.clear();
+            for (int i = 0; i < n; i++) {
+                const int p = i0 + i;
+                pos[(size_t)i] = p;
+                flags[(size_t)i] = p >= first && p <= n_chunk - 2;
+                if (flags[(size_t)i]) { rows.push_back(i); tgt.push_back(tk[(size_t)p + 1]); }
+            }
+            const int d = decode(n, tk.data() + i0, pos.data(), nseq.data(), seqs.data(), flags.data());
+            if (d != 0) { if (d > 0) last_error = "perplexity: no KV slot for the chunk"; rc = -1; break; }
+            if (base) {
+                const int db = base->decode(n, tk.data() + i0, pos.data(), nseq.data(), seqs.data(), flags.data());
+                if (db != 0) { last_error = db > 0 ? "perplexity: no KV slot for the chunk in the base context" : base->last_error; rc = -1; break; }
+            }
+            const int R = (int)rows.size();
+            if (R == 0) continue;
+            lp.resize((size_t)R); rank.resize((size_t)R);
+            if (token_logprobs(R, rows.data(), tgt.data(), lp.data(), rank.data()) < 0) { rc = -1; break; }
+            if (base) {
+                lpb.resize((size_t)R); kl.resize((size_t)R); top.resize((size_t)R);
+                if (base->token_logprobs(R, rows.data(), tgt.data(), lpb.data(), nullptr) < 0) { last_error = base->last_error; rc = -1; break; }
+                if (logits_kl(*base, R, rows.data(), rows.data(), kl.data(), top.data()) < 0) { rc = -1; break; }
+            }
+            for (int r = 0; r < R; r++, at++) {
+                const bool dead = lp[(size_t)r] != lp[(size_t)r] || (base && (lpb[(size_t)r] != lpb[(size_t)r] || kl[(size_t)r] != kl[(size_t)r]));
+                if (logprob_out) logprob_out[at] = dead ? NAN : lp[(size_t)r];
+                if (kl_out) kl_out[at] = dead || !base ? NAN : kl[(size_t)r];
+                if (dead) { cur.dead++; continue; }
+                const double nll = -(double)lp[(size_t)r];
+                cur.count++; cur.nll += nll; cur.nll2 += nll * nll;
+                cur.top1 += rank[(size_t)r] == 0 ? 1 : 0;
+                if (base) {
+                    const double nb = -(double)lpb[(size_t)r], k = (double)kl[(size_t)r];
+                    cur.nll_base += nb; cur.nll2_base += nb * nb; cur.kl += k; cur.kl2 += k * k;
+                    cur.same_top += top[(size_t)r] == 1 ? 1 : 0;
+                }
+            }
+        }
+        if (rc != 0) break;
+        st = cur;
+        st.n_chunks = c + 1;
+        if (cb && cb(st, user) != 0) { st.stopped = 1; break; }
+    }
+    kv_seq_rm(seq, 0, -1);
+    if (base) base->kv_seq_rm(seq, 0, -1);
+    return rc;
 }
 
 // n rows of the last batch in ONE set of launches and ONE synchronisation (a scheduler tick asks for all its sampling slots together: row by row, each

@@ -129,6 +129,30 @@ class Context {
     // the model agrees with, from the group's first row on.  One launch, one synchronisation.  Returns R, or -1 with last_error set (a row not flagged,
     // embeddings mode, a rank of a row split).
     int spec_verify(int n_groups, const int32_t *group_start, const int32_t *draft, int32_t *ids_out, int32_t *n_accept_out);
+    // perplexity and KL divergence (csrc/logprob.hip), from the device logits of the last decode like the two above; a few words per row come
+    // back through pinned memory, one synchronisation per call, the rows stay where logits_ith finds them.  Each returns n, or -1 with last_error set
+    // (embeddings mode, a batch row that was not flagged, a target outside the vocabulary, a rank of a row split; logits_kl also: another n_vocab, another
+    // device, the same context on both sides).
+    // logprob_out[r] = log softmax(row batch_rows[r])[targets[r]] over the whole vocabulary; rank_out[r] (nullable) = the entries that beat the target
+    // (0: it is the arg-max).  A dead row (kernels.h) gives NaN and -1.
+    int token_logprobs(int n, const int32_t *batch_rows, const int32_t *targets, float *logprob_out, int32_t *rank_out);
+    // kl_out[r] = KL(P || Q), P = row rows_base[r] of `base`'s last decode, Q = row rows_self[r] of this context's; same_top_out[r] (nullable) = 1 where both
+    // have the same arg-max.  A row with a non-finite entry: NaN and -1.  base's stream is drained on the host before the launch on this one's.
+    int logits_kl(Context &base, int n, const int32_t *rows_base, const int32_t *rows_self, float *kl_out, int32_t *same_top_out);
+    // The llama-perplexity procedure (restated from memory of llama.cpp's perplexity(): unpinned).  n_chunks = n_tokens / n_chunk, the tail is
+    // dropped.  Per chunk: `seq` is cleared, the first token becomes bos (if bos >= 0), the chunk is decoded at positions 0 .. n_chunk - 1 in pieces of at most
+    // n_ubatch tokens with positions n_chunk / 2 .. n_chunk - 2 flagged, and after each piece the flagged rows are scored against the tokens that follow them.
+    // With a base context the same pieces run there too and every scored row also gives the base's log-probability and KL(base || this).  Sums in double; a row
+    // any of whose figures is NaN is counted in `dead` and in nothing else.  logprob_out / kl_out (nullable): n_chunks * (n_chunk - 1 - n_chunk / 2) entries in
+    // scoring order, NaN for dead rows.  cb (nullable) sees the running stats after every chunk; non-zero stops the run (stats.stopped = 1).  `seq` is removed
+    // from both caches on return.  0, or -1 with last_error set; the stats then cover the chunks that were scored whole.
+    struct PplStats {
+        int64_t n_chunks = 0, count = 0, top1 = 0, dead = 0, same_top = 0;
+        int32_t has_base = 0, stopped = 0;
+        double nll = 0, nll2 = 0, nll_base = 0, nll2_base = 0, kl = 0, kl2 = 0;
+    };
+    int perplexity(const int32_t *tokens, int64_t n_tokens, int n_chunk, int32_t bos, int seq, Context *base, float *logprob_out, float *kl_out,
+                   int (*cb)(const PplStats &, void *), void *user, PplStats &out);
     // test hook (mixture-of-experts files): the NEXT decode call (one micro-batch of T tokens) takes these experts, ids [n_layer][T][n_expert_used], instead of
     // its router's selection; the weights stay this side's probabilities of them.  One call, then routing is free again.  No graphs while it is armed.
     int force_moe_ids(const int32_t *ids, int n_layer, int T, int k);
@@ -360,6 +384,13 @@ class Context {
     float *spec_scratch_ = nullptr;                    // argmax_prob_ith / spec_verify: part and ticket words of the two kernels (first use)
     int32_t *d_spec_in_ = nullptr, *h_spec_ = nullptr; // rows | group starts | drafts on the device; pinned: their staging, then ids | accepted | (index, p)
     bool spec_prepare();
+    // token_logprobs / logits_kl: the two kernels' part and ticket words, sized for n_ubatch rows per launch (first use); rows | targets (or rows | rows) of a
+    // call on the device and their pinned staging followed by the results, both grown to the largest call
+    float *lp_scratch_ = nullptr;
+    int32_t *d_lp_in_ = nullptr, *h_lp_ = nullptr;
+    int lp_cap_ = 0;
+    bool logprob_prepare(int n);
+    bool logprob_rows(const char *what, int n, const int32_t *batch_rows, int32_t *dst);
     unsigned long long *h_topk_ = nullptr;             // pinned: the winning keys
     Fuse pending_fuse_;
     int att_splits_ = 1;

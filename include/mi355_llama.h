@@ -170,6 +170,35 @@ MI355_API int32_t mi355_spec_verify(mi355_context *ctx, int32_t n_groups, const 
  * (drafts that were emitted: n = rounds + accepted), plain steps (rounds without a draft).  Returns the tokens written (n, or fewer with the reason in mi355_last_error). */
 MI355_API int32_t mi355_speculative_steps(mi355_context *ctx_tgt, mi355_context *ctx_dft, mi355_token first, mi355_pos pos0, mi355_seq_id seq, int32_t n,
                                           int32_t n_max, int32_t n_min, float p_min, mi355_token *out_tokens, int64_t *stats);
+/* ---- perplexity and KL divergence (what upstream's llama-perplexity prints).  Like the block above these read the device logits of the last
+ * mi355_decode, with logits_to_host 0 or 1, and bring a few words per row to the host; a later mi355_get_logits_ith still returns the same rows.
+ * logprob_out [n]: log softmax(row batch_rows[r])[targets[r]] over the WHOLE vocabulary, x_t - max - log(sum_j exp(x_j - max)) in f32; rank_out (nullable) [n]:
+ * how many entries beat the target under the arg-max rule (0: the target is what mi355_get_argmax_ith returns).  A row whose maximum is not finite, or whose
+ * target logit is NaN, gives NaN and -1.  Returns n; < 0 with mi355_last_error set in embeddings mode, for a row that was not flagged, a target outside
+ * [0, n_vocab) or on a rank of a row split. */
+MI355_API int32_t mi355_get_token_logprobs(mi355_context *ctx, int32_t n, const int32_t *batch_rows, const mi355_token *targets, float *logprob_out,
+                                           int32_t *rank_out);
+/* kl_out [n]: KL(P || Q) in nats, P = row rows_base[r] of ctx_base's last decode (the f16 / Q8_0 model), Q = row rows[r] of ctx's (the model under test);
+ * not clamped at 0, exactly 0 for identical rows.  same_top_out (nullable) [n]: 1 where both rows have the same arg-max.  A row with a non-finite entry gives
+ * NaN and -1.  Refused as above, and when the two contexts differ in n_vocab or device or are one context. */
+MI355_API int32_t mi355_logits_kl(mi355_context *ctx, mi355_context *ctx_base, int32_t n, const int32_t *rows_base, const int32_t *rows, float *kl_out,
+                                  int32_t *same_top_out);
+/* The llama-perplexity procedure on the C side (restated from memory of llama.cpp's perplexity(): not pinned to a source line).  n_chunks = n_tokens / n_chunk
+ * (2 <= n_chunk <= n_ctx of every context involved; the tail is dropped).  Per chunk: sequence `seq` is cleared, the chunk's first token is replaced by bos
+ * (-1: none), the chunk is decoded in pieces of at most n_ubatch tokens with positions n_chunk / 2 .. n_chunk - 2 flagged, and every flagged row is scored
+ * against the token that follows it.  With ctx_base (nullable) the same pieces are decoded there and every row also gives the base's log-probability and
+ * KL(base || ctx).  A row any of whose figures is NaN counts in `dead` alone.  logprob_out / kl_out (nullable): n_chunks * (n_chunk - 1 - n_chunk / 2)
+ * floats in scoring order, NaN for dead rows.  cb (nullable) receives the running stats after every chunk and stops the run by returning non-zero.  The
+ * sequence is removed from both caches on return.  perplexity = exp(nll / count). */
+typedef struct mi355_ppl_stats {
+    int64_t n_chunks, count, top1, dead, same_top;   /* chunks scored; rows scored; rows whose target was the arg-max; rows skipped; rows with base's arg-max */
+    int32_t has_base, stopped;
+    double  nll, nll2;                                /* sum and sum of squares of -logprob */
+    double  nll_base, nll2_base, kl, kl2;             /* with ctx_base: the same for the base model; sum and sum of squares of the per-row KL */
+} mi355_ppl_stats;
+typedef int32_t (*mi355_ppl_callback)(const mi355_ppl_stats *running, void *user);
+MI355_API int32_t mi355_perplexity(mi355_context *ctx, mi355_context *ctx_base, const mi355_token *tokens, int64_t n_tokens, int32_t n_chunk, mi355_token bos,
+                                   mi355_seq_id seq, float *logprob_out, float *kl_out, mi355_ppl_callback cb, void *user, mi355_ppl_stats *stats);
 /* device-side sampling front end beyond greedy (stands in for the head of common_sampler_sample's chain, reference call site
    src/llama_server_context.cc:1679-1698): the k <= 128 best candidates of row i after logit_bias and the repetition / frequency / presence penalties,
    best first (higher logit; lower token id on ties) - k (token, logit) pairs cross to the host instead of the whole row.  adj_tok / adj_bias / adj_count:
@@ -352,6 +381,13 @@ MI355_API int mi355_op_argmax_rows(const float *x, int64_t n, const int32_t *lau
 /* The two kernels of a speculative round (csrc/spec.hip), the arg-max rule above in both.  x [rows][n]: idx_out [rows] and p_out [rows], the arg-max's softmax
  * probability 1 / sum_j exp(x_j - max) over the non-NaN entries (f32, a fixed summation order; 0 where the maximum is not finite). */
 MI355_API int mi355_op_argmax_prob_rows(const float *x, int64_t n, int32_t rows, int32_t *idx_out, float *p_out);
+/* The two kernels of csrc/logprob.hip.  base [n_base_rows][n]; launch row r = base row rows[r] (rows NULL: row r), r < R <= 65535; targets [R] in [0, n).
+ * logprob_out [R], rank_out [R] as mi355_get_token_logprobs gives them. */
+MI355_API int mi355_op_token_logprob_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, const int32_t *targets, int32_t R,
+                                          float *logprob_out, int32_t *rank_out);
+/* p [n_p_rows][n], q [n_q_rows][n]; pair r = (p row rows_p[r], q row rows_q[r]) (NULL: row r).  kl_out [R], same_top_out [R] as mi355_logits_kl gives them. */
+MI355_API int mi355_op_logits_kl_rows(const float *p, int32_t n_p_rows, const float *q, int32_t n_q_rows, int64_t n, const int32_t *rows_p, const int32_t *rows_q,
+                                      int32_t R, float *kl_out, int32_t *same_top_out);
 /* logits [n_base_rows][n]; launch row r = base row rows[r], r < R <= 1088; group g < G <= 64 owns launch rows group_start[g] .. group_start[g + 1] - 1
  * (1 .. 17 rows; group_start[0] = 0, group_start[G] = R); draft [R].  ids_out [R], n_accept_out [G] as mi355_spec_verify gives them. */
 MI355_API int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t R, const int32_t *group_start, int32_t G,
