@@ -151,6 +151,7 @@ SYMBOLS = {
     "mi355_op_moe_group": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_moe_gather_act": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_moe_combine": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "mi355_op_moe_mul_mat_grouped": (C.c_int, [_i32, _i32, _vp, _vp, _i32, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "mi355_op_gather_rows_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp]),
     "mi355_op_flash_attn": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32, _vp]),
     "mi355_op_attn_step": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _i64, _vp, _i32,
@@ -614,6 +615,21 @@ class Backend:
         y = np.zeros_like(x)
         self._chk(self.lib.mi355_op_moe_combine(_ptr(x), _ptr(eo), _ptr(w), T, E, k, int(s is not None), _ptr(s), _ptr(y)), "op_moe_combine")
         return y
+
+    def moe_mul_mat_grouped(self, t: int, form: int, Ws, n_expert: int, N: int, K: int, x: np.ndarray, counts, ld_out=None, guard_rows: int = 2, R=None):
+        """One grouped-expert launch of a prompt batch (mi355_op_moe_mul_mat_grouped).  form 0: planes, one projection; 1: planes, gate | up with SwiGLU;
+        2 / 3: the Q8_0-layout copies, one / two segments.  Ws: one or two arrays of n_expert tensors back to back (ggml rows); x [R][K] grouped rows; counts
+        [n_expert].  Returns the whole out buffers [R + guard_rows][ld_out] (two for form 3): what the launch did not write holds 0xFF bytes."""
+        Ws = [np.ascontiguousarray(w.view(np.uint8).reshape(-1)) for w in Ws]
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        assert counts.size == n_expert and all(w.size % n_expert == 0 for w in Ws)
+        R = x.shape[0] if R is None else int(R)
+        ld = int(N) if ld_out is None else int(ld_out)
+        ys = [np.zeros((R + guard_rows, ld), np.float32) for _ in range(2 if form == 3 else 1)]
+        self._chk(self.lib.mi355_op_moe_mul_mat_grouped(t, form, _ptr(Ws[0]), _ptr(Ws[1]) if len(Ws) > 1 else None, int(n_expert), int(N), int(K), _ptr(x), _ptr(counts),
+                                                        R, ld, guard_rows, _ptr(ys[0]), _ptr(ys[1]) if len(ys) > 1 else None), "op_moe_mul_mat_grouped")
+        return ys
 
     def gather_rows_f32(self, src: np.ndarray, rows) -> np.ndarray:
         src = np.ascontiguousarray(src, np.float32)

@@ -1626,6 +1626,79 @@ int mi355_op_moe_combine(const float *x, const float *eo, const float *w, int64_
     return dx.down(y_out, nx) ? MI355_OK : MI355_ERR_HIP;
 }
 
+// One grouped-expert launch of a prompt batch as Context::moe_grouped_planes / moe_grouped_q80 issue it (host/runtime.cc): the weights expanded expert by expert
+// at the loader's stride (expand_prefill_planes), the grouped rows quantised, meta in moe_group_kernel's layout, rows_max = R.  Every out buffer is 0xFF bytes
+// before the launch and comes back whole, guard rows included.
+int mi355_op_moe_mul_mat_grouped(int32_t type, int32_t form, const void *W0, const void *W1, int32_t n_expert, int64_t N, int64_t K, const float *x,
+                                 const int32_t *counts, int64_t R, int64_t ld_out, int64_t guard_rows, float *y0, float *y1) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    const bool planes = form == 0 || form == 1, two_w = form == 1 || form == 3, two_y = form == 3;
+    if (form < 0 || form > 3 || !W0 || (two_w && !W1) || !x || !counts || !y0 || (two_y && !y1) || n_expert < 1 || n_expert > 256 || N < 1 || K < 1 || R < 1 ||
+        R > 60 * 1024 || N > INT32_MAX || K > INT32_MAX || ld_out < N || ld_out > INT32_MAX || guard_rows < 0 || guard_rows > 1024) {
+        fail("moe_mul_mat_grouped: bad arguments"); return MI355_ERR_ARG;
+    }
+    if (planes ? !mmq_planes_moe_ok(type, (int)N, (int)K) : !mmq_q80_moe_ok(type, (int)N, (int)K)) {
+        fail(planes ? "moe_mul_mat_grouped: the grouped plane launch takes Q4_K / Q5_K / Q6_K / IQ4_XS / TQ1_0 / TQ2_0, N % 128 == 0, K % 256 == 0"
+                    : "moe_mul_mat_grouped: the grouped Q8_0-copy launch takes MXFP4, N % 128 == 0, K % 32 == 0, 32 <= K <= 16384");
+        return MI355_ERR_ARG;
+    }
+    std::vector<int32_t> meta((size_t)2 * n_expert + 1);
+    int64_t sum = 0;
+    for (int e = 0; e < n_expert; e++) {
+        if (counts[e] < 0) { fail("moe_mul_mat_grouped: counts[" + std::to_string(e) + "] is negative"); return MI355_ERR_ARG; }
+        meta[(size_t)e] = counts[e];
+        meta[(size_t)n_expert + e] = (int32_t)sum;
+        sum += counts[e];
+        if (sum > R) break;
+    }
+    if (sum != R) { fail("moe_mul_mat_grouped: the counts do not add up to R"); return MI355_ERR_ARG; }
+    meta[(size_t)2 * n_expert] = (int32_t)R;
+    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
+    const size_t pb = planes ? mmq_planes_bytes(type, N, (int)K) : mmq_q80_copy_bytes(type, N, (int)K);
+    const size_t stride = (pb + 255) & ~(size_t)255;             // (the loader's: every expert's set starts on 256 bytes)
+    const int n_w = two_w ? 2 : 1, n_y = two_y ? 2 : 1;
+    const size_t yb = (size_t)(R + guard_rows) * (size_t)ld_out * 4;
+    std::unique_ptr<DevBuf> pl[2], dy[2];
+    {
+        DevBuf wsrc(grow * (size_t)N * n_expert), wdev(drow * (size_t)N * n_expert);
+        if (!wsrc.p || !wdev.p) { fail("device alloc failed"); return MI355_ERR_OOM; }
+        for (int i = 0; i < n_w; i++) {
+            pl[i].reset(new DevBuf(stride * (size_t)n_expert));
+            if (!pl[i]->p || !wsrc.up(i ? W1 : W0, grow * (size_t)N * n_expert)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+            hipError_t e = launch_repack_rows(type, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, N * n_expert, nullptr);
+            for (int64_t ex = 0; ex < n_expert && e == hipSuccess; ex++) {
+                const uint8_t *src = wdev.as<uint8_t>() + (size_t)ex * drow * (size_t)N;
+                uint8_t *dst = pl[i]->as<uint8_t>() + (size_t)ex * stride;
+                e = planes ? launch_mmq_expand(type, src, drow, (int)N, (int)K, dst, nullptr) : launch_expand_q80_copy(type, src, drow, (int)N, (int)K, dst, nullptr);
+            }
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            if (e != hipSuccess) return hip_fail(e, "moe_mul_mat_grouped (weights)");
+        }
+    }
+    DevBuf dx((size_t)K * R * 4), dmeta(meta.size() * 4);
+    ActBufs ab((size_t)K, (size_t)R);
+    if (!dx.up(x, (size_t)K * R * 4) || !dmeta.up(meta.data(), meta.size() * 4) || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    for (int i = 0; i < n_y; i++) {
+        dy[i].reset(new DevBuf(yb));
+        if (!dy[i]->p || hipMemset(dy[i]->p, 0xFF, yb) != hipSuccess) { fail("device alloc failed"); return MI355_ERR_OOM; }
+    }
+    hipError_t e = launch_quantize(dx.as<float>(), (int)K, (int)R, ab.q, planes, !planes, nullptr);
+    if (e == hipSuccess) {
+        if (form == 0) e = launch_mmq_planes_moe(type, pl[0]->as<uint8_t>(), stride, n_expert, dmeta.as<int32_t>(), (int)N, (int)K, (int)R, ab.q, dy[0]->as<float>(), (int)ld_out, nullptr);
+        else if (form == 1) e = launch_mmq_planes_swiglu_moe(type, pl[0]->as<uint8_t>(), pl[1]->as<uint8_t>(), stride, n_expert, dmeta.as<int32_t>(), (int)N, (int)K, (int)R, ab.q,
+                                                             dy[0]->as<float>(), (int)ld_out, nullptr);
+        else {
+            const uint8_t *w[2] = {pl[0]->as<uint8_t>(), two_w ? pl[1]->as<uint8_t>() : nullptr};
+            float *o[2] = {dy[0]->as<float>(), two_y ? dy[1]->as<float>() : nullptr};
+            e = launch_mmq_q80_moe(type, w, o, n_w, stride, n_expert, dmeta.as<int32_t>(), (int)N, (int)K, (int)R, ab.q, (int)ld_out, nullptr);
+        }
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "moe_mul_mat_grouped");
+    if (!dy[0]->down(y0, yb) || (two_y && !dy[1]->down(y1, yb))) return MI355_ERR_HIP;
+    return MI355_OK;
+}
+
 int mi355_op_gather_rows_f32(const float *src, int64_t n_src_rows, int64_t n, const int32_t *rows, int64_t n_rows, float *dst) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     if (n_src_rows < 1 || n < 1 || n_rows < 1 || n > INT32_MAX || n_rows > 65535) { fail("gather_rows_f32: bad shape"); return MI355_ERR_ARG; }

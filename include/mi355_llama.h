@@ -412,6 +412,19 @@ MI355_API int mi355_op_moe_gather_act(const int8_t *qs, const float *d, const in
  * grouped rows, rank j of token t at row slot_of[t * k + j]. */
 MI355_API int mi355_op_moe_combine(const float *x, const float *eo, const float *w, int64_t T, int32_t E, int32_t k, int32_t grouped, const int32_t *slot_of,
                                    float *y_out);
+/* Test hook: ONE grouped-expert launch of a prompt batch (ggml_mul_mat_id over rows sorted by expert), issued as the model issues it.
+ *   form 0: the plane sets, one projection (ffn_down):          y0[r][n] = W0[e(r)][n] . a[r]
+ *   form 1: the plane sets, ffn_gate | ffn_up with SwiGLU:      y0[r][n] = silu(W0[e(r)][n] . a[r]) * (W1[e(r)][n] . a[r])
+ *   form 2 / 3: the Q8_0-layout copies, one / two segments:     y0 as form 0, and y1 the same over W1
+ * W0 / W1: n_expert tensors back to back in GGUF row layout, [n_expert][N][row bytes]; x [R][K] f32, the grouped rows; counts[n_expert] rows per expert in
+ * expert order, R their sum (expert e owns rows [sum of counts before e, + counts[e])).  The entry repacks the rows, expands every expert at the loader's
+ * stride, quantises x (Q8_K for the plane forms, Q8_0 for the copies), builds meta (counts | exclusive offsets | total) and makes the launch with rows_max = R;
+ * the copy forms take the tile "mmq_q80_tiles" forces, else the launcher's choice.  Every out buffer is [R + guard_rows][ld_out] (ld_out >= N), filled with
+ * 0xFF bytes before the launch and returned whole: an unwritten result reads as NaN, a write past N or past row R shows in the pad columns / guard rows.
+ * MI355_ERR_ARG, nothing launched: a shape the launch's own predicate refuses (planes: Q4_K / Q5_K / Q6_K / IQ4_XS / TQ1_0 / TQ2_0, N % 128 == 0,
+ * K % 256 == 0; copies: MXFP4, N % 128 == 0, K % 32 == 0, K <= 16384), n_expert outside 1 .. 256, a negative count, counts that do not add up to R. */
+MI355_API int mi355_op_moe_mul_mat_grouped(int32_t type, int32_t form, const void *W0, const void *W1, int32_t n_expert, int64_t N, int64_t K, const float *x,
+                                           const int32_t *counts, int64_t R, int64_t ld_out, int64_t guard_rows, float *y0, float *y1);
 /* dst [n_rows][n] = src [n_src_rows][n] rows rows[0 .. n_rows) (the output rows handed to the head) */
 MI355_API int mi355_op_gather_rows_f32(const float *src, int64_t n_src_rows, int64_t n, const int32_t *rows, int64_t n_rows, float *dst);
 /* flash_attn_ext for T query tokens: K/V given as ggml-layout rows [n_cells][n_head_kv*head_dim] of type_k/type_v;

@@ -67,6 +67,13 @@ def test_no_cpu_fallback(pkg):
     for grouped in (0, 1):
         assert lib.mi355_op_moe_combine(x.ctypes.data, x.ctypes.data, x.ctypes.data, 1, 256, 1, grouped, zero.ctypes.data, y.ctypes.data) == -100
     assert lib.mi355_op_gather_rows_f32(x.ctypes.data, 1, 256, zero.ctypes.data, 1, y.ctypes.data) == -100
+    # the grouped-expert launch, every form: one expert of 128 Q4_K / MXFP4 rows of 256, one grouped row
+    wq = np.zeros(128 * 144, np.uint8)
+    yg = np.zeros(3 * 128, np.float32)
+    for form, t in ((0, 12), (1, 12), (2, 39), (3, 39)):
+        assert lib.mi355_op_moe_mul_mat_grouped(t, form, wq.ctypes.data, wq.ctypes.data, 1, 128, 256, x.ctypes.data, one.ctypes.data, 1, 128, 2, yg.ctypes.data,
+                                                yg.ctypes.data) == -100, form
+        assert lib.mi355_op_moe_mul_mat_grouped(t, form, None, None, 1, 128, 256, None, None, 1, 128, 2, None, None) == -100, form
     # the decode step's mat-vec launch: one Q8_0 row of 256 (8 blocks of 34 bytes)
     import ctypes as C
     w = np.zeros(8 * 34, np.uint8)

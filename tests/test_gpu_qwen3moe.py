@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 KV = {"f16": 1, "q8_0": 8, "q4_0": 2}
 # the end-to-end tolerances of tests/test_gpu_model.py and tests/test_gpu_qwen3.py: every layer and step within FLIP_TOL
 FLIP_TOL = 3e-2
+TIGHT_TOL = 2e-5         # two forms of one launch sequence: f32 round-off on most tokens (tests/test_gpu_model.py)
 F32, F16 = 0, 1
 
 
@@ -213,6 +214,49 @@ def test_qwen3moe_prompt_forms_agree(be, pkg, tmp_models):
     finally:
         be.set_option("moe_group_min", 8)
         m.close()
+
+
+def test_grouped_plane_launch_against_the_mat_vec_loop(be, pkg, tmp_models):
+    """96 tokens with the expert ids forced so that layer 1's batches are of 288 rows (expert 5, three ranks of every token: two 256-token tiles, the second of
+    32 rows), 33 (expert 9), 32 (expert 7), 1 (expert 11), a spread of small ones, and none at all for most of the low experts: every expert's batch in one
+    launch per projection against the per-(token, rank) mat-vec loop (moe_group_min above the batch), compared as the two forms of
+    test_moe_prompt_batches_grouped_by_expert (tests/test_gpu_model.py) are - per layer the median over the tokens of the per-token error within TIGHT_TOL,
+    the logits within FLIP_TOL."""
+    path = make(pkg, tmp_models, "tiny-qwen3moe", "q4_k_m")
+    m = pkg.Model(path)
+    T, KU, NE = 96, 8, 128
+    rng = np.random.default_rng(96)
+    ids = np.stack([np.stack([rng.permutation(NE)[:KU] for _ in range(T)]) for _ in range(m.n_layer)]).astype(np.int32)
+    L1 = ids[1]
+    L1[:, 0:3] = 5
+    L1[:32, 3], L1[32:65, 3], L1[65:, 3] = 7, 9, 12 + np.arange(T - 65) % 8
+    L1[:, 4] = 20 + np.arange(T) % 50
+    L1[0, 4] = 11
+    L1[:, 5:] = 70 + (np.arange(T)[:, None] * 3 + np.arange(3)[None, :]) % 58
+    counts = np.bincount(L1.reshape(-1), minlength=NE)
+    assert counts[5] == 288 and counts[9] == 33 and counts[7] == 32 and counts[11] == 1 and (counts == 0).sum() >= 4 and counts.sum() == T * KU
+    toks = rng.integers(0, m.n_vocab, T)
+    outs = {}
+    try:
+        for mode, gmin in (("grouped", 8), ("loop", 1 << 20)):
+            be.set_option("moe_group_min", gmin)
+            c = pkg.Context(m, n_ctx=256, type_k=KV["q8_0"], type_v=KV["q8_0"])
+            c.enable_taps(True)
+            c.force_moe_ids(ids)
+            assert c.decode(toks, np.arange(T)) == 0
+            outs[mode] = (c.logits().copy(), [c.layer_out(il, T).copy() for il in range(m.n_layer)])
+            c.close()
+    finally:
+        be.set_option("moe_group_min", 8)
+    n_layer = m.n_layer
+    m.close()
+    for il in range(n_layer):
+        g, l = outs["grouped"][1][il].reshape(T, -1), outs["loop"][1][il].reshape(T, -1)
+        assert np.isfinite(g).all() and np.abs(g).max() > 0
+        tok = np.abs(g - l).max(axis=1) / max(1.0, float(np.abs(l).max()))
+        print(f"layer {il}: per-token error median {float(np.median(tok)):.3g} max {float(tok.max()):.3g}")
+        assert float(np.median(tok)) <= TIGHT_TOL, (il, tok)
+    assert rel_err(outs["grouped"][0], outs["loop"][0]) <= FLIP_TOL
 
 
 @pytest.mark.parametrize("cfg,kv", [("tiny-qwen3moe", "q8_0"), ("tiny-qwen3moe-30b-2l", "f16")])
