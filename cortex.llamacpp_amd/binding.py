@@ -130,6 +130,8 @@ SYMBOLS = {
     "mi355_op_mul_mat_add": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "mi355_op_mul_mat_fused": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _vp, _f32, _vp]),
     "mi355_op_mat_vec_step": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, _f32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "mi355_op_prompt_mul_mat": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _f32, _i32, _i64, _vp, _vp]),
+    "mi355_op_act_q8k_planes": (C.c_int, [_i32, _vp, _vp, _vp, _f32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_f32_to_bf16": (C.c_int, [_vp, _i64, _vp]),
     "mi355_op_mul_mat_bf16": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mi355_op_ffn_gate_up": (C.c_int, [_i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
@@ -166,6 +168,8 @@ SYMBOLS = {
                                                 _f32, _i32, _vp, _vp, _vp]),
     "mi355_op_attn_batch_step": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _f32,
                                            _i32, _vp, _vp]),
+    "mi355_op_attn_batch_step_planes": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _f32,
+                                           _i32, _vp, _vp, _vp, _vp]),
     "mi355_op_kv_store": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp]),
     "mi355_op_k_shift": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _f32, _f32, _vp, _f32, _f32, _f32, _f32, _vp]),
     "mi355_op_kv_state_pack": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
@@ -348,6 +352,44 @@ class Backend:
                 d.update(role="ternary" if p[7] else "moe" if p[6] else self.MAT_VEC_ROLES[p[2]], kb=int(p[3]), fast_ok=bool(p[4]), down_early=bool(p[5]))
             launches.append(d)
         return ys, yh, launches
+
+    def prompt_mul_mat(self, types, Ws, Ns, K: int, x: np.ndarray, epi: int = 0, resid=None, in_place: bool = False, prologue: int = 0, norm_w=None,
+                       eps: float = 0.0, form: int = 0, ld_pad: int = 0, check: bool = True):
+        """One mat-mul launch of a dense prompt batch as the model issues it (see mi355_op_prompt_mul_mat).  x: [T][K], for prologue 2 [2][T][K] (gate, up).
+        Returns (ys, path, rc): ys the whole out buffers [T][N + ld_pad] (one for epi 2), path a dict (kernel 1 K-split / 2 planes 256 x 32 / 3 planes
+        128 x 128 / 4 LDS / 5 on the fly, token_tiles, n_split, mixed, swiglu, prep), rc the entry's return code (check=False: returned, not raised)."""
+        n = len(Ws)
+        Ws = [np.ascontiguousarray(w.view(np.uint8).reshape(-1)) for w in Ws]
+        tarr = np.asarray(types, np.int32)
+        Narr = np.asarray(Ns, np.int64)
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+        T = x.shape[0] // 2 if prologue == 2 else x.shape[0]
+        ys = [np.zeros((T, int(N) + ld_pad), np.float32) for N in (Narr[:1] if epi == 2 else Narr)]
+        r = None if resid is None else np.ascontiguousarray(resid, np.float32).reshape(T, int(Narr[0]) + ld_pad)
+        nw = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32).reshape(K)
+        path = np.zeros(8, np.int32)
+        parr = lambda xs: (C.c_void_p * len(xs))(*[None if a is None else a.ctypes.data for a in xs])
+        wp, yp = parr(Ws), parr(ys + [None] * (n - len(ys)))
+        rc = self.lib.mi355_op_prompt_mul_mat(n, _ptr(tarr), wp, _ptr(Narr), K, _ptr(x), T, epi, _ptr(r), int(bool(in_place)), prologue, _ptr(nw), eps, form, ld_pad,
+                                              yp, _ptr(path))
+        if check:
+            self._chk(rc, "op_prompt_mul_mat")
+        keys = ("kernel", "token_tiles", "n_split", "mixed", "swiglu", "prep")
+        return ys, {k: int(v) for k, v in zip(keys, path)}, int(rc)
+
+    def act_q8k_planes(self, producer: int, x: np.ndarray, x2=None, norm_w=None, eps: float = 0.0, want_f32: bool = False):
+        """One producer of the MFMA kernels' activation (mi355_op_act_q8k_planes; 0 launch_quantize, 1 launch_rmsnorm_quant, 2 launch_swiglu_quant) over the
+        rows x [T][n].  Returns (blocks [T][292 * n / 256] uint8, bh, bl, prep_bh, prep_bl [T][n / 16] int8, f32 rows or None)."""
+        x = np.ascontiguousarray(x, np.float32)
+        T, n = x.shape
+        x2 = None if x2 is None else np.ascontiguousarray(x2, np.float32).reshape(T, n)
+        nw = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32).reshape(n)
+        blk = np.zeros((T, 292 * (n // 256)), np.uint8)
+        bh, bl, ph, pl = (np.zeros((T, n // 16), np.int8) for _ in range(4))
+        yf = np.zeros((T, n), np.float32) if want_f32 else None
+        self._chk(self.lib.mi355_op_act_q8k_planes(producer, _ptr(x), _ptr(x2), _ptr(nw), eps, n, T, _ptr(blk), _ptr(bh), _ptr(bl), _ptr(ph), _ptr(pl), _ptr(yf)),
+                  "op_act_q8k_planes")
+        return blk, bh, bl, ph, pl, yf
 
     def mul_mat(self, t: int, W: np.ndarray, N: int, K: int, x: np.ndarray, want_ints: bool = False):
         W = np.ascontiguousarray(W.view(np.uint8).reshape(-1))
@@ -719,7 +761,7 @@ class Backend:
         return att, kr, vr
 
     def attn_batch_step(self, mode: int, q, k_new, v_new, n_head: int, n_head_kv: int, hd: int, type_k: int, k_rows, type_v: int, v_rows, n_kv: int, cell_pos,
-                        cell_seq, tok_pos, tok_seq, tok_cell, rope_base: float, n_rot: int, neox: bool, scale: float, want_q8k: bool = False):
+                        cell_seq, tok_pos, tok_seq, tok_cell, rope_base: float, n_rot: int, neox: bool, scale: float, want_q8k: bool = False, want_planes: bool = False):
         """The attention of one batched single-token step (mi355_op_attn_batch_step; mode 0: store inside the attention launch, 1: the same on chunk lists,
         2: small-batch store + attention on the lists, 3: generic store + attention).  k_rows / v_rows: the whole cache before the step [n_cells][row bytes];
         returns (att [T][H * D], the whole K cache after the step, the whole V cache, the Q8_K blocks [T][292 * H * D / 256] or None).  Inputs are not modified."""
@@ -732,7 +774,14 @@ class Backend:
         kc = np.array(k_rows, order="C", copy=True).view(np.uint8); vc = np.array(v_rows, order="C", copy=True).view(np.uint8)
         assert tok_seq.size == T and tok_cell.size == T and kc.ndim == 2 and vc.ndim == 2 and kc.shape[0] == vc.shape[0] == cell_pos.size == cell_seq.size
         att = np.zeros((T, n_head * hd), np.float32)
-        blk = np.zeros((T, 292 * (n_head * hd // 256)), np.uint8) if want_q8k else None
+        blk = np.zeros((T, 292 * (n_head * hd // 256)), np.uint8) if want_q8k or want_planes else None
+        if want_planes:          # (... and the merge's bh / bl block-sum planes [T][H * D / 16] int8 behind the four results: mi355_op_attn_batch_step_planes)
+            bh, bl = np.zeros((T, n_head * hd // 16), np.int8), np.zeros((T, n_head * hd // 16), np.int8)
+            self._chk(self.lib.mi355_op_attn_batch_step_planes(_ptr(q), _ptr(k_new), _ptr(v_new), T, n_head, n_head_kv, hd, type_k, _ptr(kc), type_v, _ptr(vc),
+                                                               cell_pos.size, int(n_kv), _ptr(cell_pos), _ptr(cell_seq), _ptr(tok_pos), _ptr(tok_seq), _ptr(tok_cell),
+                                                               float(rope_base), int(n_rot), int(bool(neox)), float(scale), int(mode), _ptr(att), _ptr(blk), _ptr(bh),
+                                                               _ptr(bl)), "op_attn_batch_step_planes")
+            return att, kc, vc, blk, bh, bl
         self._chk(self.lib.mi355_op_attn_batch_step(_ptr(q), _ptr(k_new), _ptr(v_new), T, n_head, n_head_kv, hd, type_k, _ptr(kc), type_v, _ptr(vc), cell_pos.size,
                                                     int(n_kv), _ptr(cell_pos), _ptr(cell_seq), _ptr(tok_pos), _ptr(tok_seq), _ptr(tok_cell), float(rope_base),
                                                     int(n_rot), int(bool(neox)), float(scale), int(mode), _ptr(att), _ptr(blk)), "op_attn_batch_step")

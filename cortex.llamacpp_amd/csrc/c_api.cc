@@ -1187,6 +1187,171 @@ int mi355_op_mat_vec_step(int32_t n_seg, const int32_t *types, const void *const
     return rc;
 }
 
+// One mat-mul launch of a dense prompt batch or a batched decode step as the model issues it (Context::linear, linear_multi and the gate | up block of
+// host/runtime.cc): the producer of the activation and of its bh / bl planes, the launcher, the epilogue, the residual in place.  Every out buffer is 0xFF bytes
+// before the launch and comes back whole; a refused launch leaves them so and launches nothing.
+int mi355_op_prompt_mul_mat(int32_t n_seg, const int32_t *types, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, int32_t epi,
+                            const float *resid, int32_t in_place, int32_t prologue, const float *norm_w, float eps, int32_t form, int64_t ld_pad,
+                            float *const *y, int32_t *path) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (n_seg < 1 || n_seg > 3 || !types || !W || !N || !x || !y || !path || K <= 0 || K % 256 || K > 65536 || T < 3 || T > 600 || ld_pad < 0 || ld_pad > 64) {
+        fail("prompt_mul_mat: bad arguments"); return MI355_ERR_ARG;
+    }
+    const int n_out = epi == EPI_SWIGLU ? 1 : n_seg;
+    for (int s = 0; s < n_seg; s++) if (N[s] < 1 || N[s] > (1 << 20) || !W[s] || (s < n_out && !y[s])) { fail("prompt_mul_mat: bad segment"); return MI355_ERR_ARG; }
+    for (int i = 0; i < 8; i++) path[i] = 0;
+    for (int s = 0; s < n_out; s++) memset(y[s], 0xFF, (size_t)T * (N[s] + ld_pad) * 4);       // what a refusal or a failure hands back
+    auto refuse = [](const char *why) { fail(std::string("prompt_mul_mat: ") + why); return MI355_ERR_ARG; };
+    if (epi != EPI_STORE && epi != EPI_ADD && epi != EPI_SWIGLU) return refuse("epi outside 0..2");
+    if (epi == EPI_ADD && n_seg != 1) return refuse("a residual takes one tensor");
+    if (epi == EPI_ADD && !resid) return refuse("epi 1 without resid");
+    if (epi != EPI_ADD && (resid || in_place)) return refuse("resid / in_place without epi 1");
+    if (epi == EPI_SWIGLU && (n_seg != 2 || N[0] != N[1])) return refuse("the SwiGLU pair is two tensors of one N");
+    if (epi == EPI_SWIGLU && types[0] != types[1]) return refuse("the SwiGLU pair is two tensors of one type");
+    if (prologue < 0 || prologue > 3 || (prologue == 1 && !norm_w)) return refuse("bad prologue");
+    if (form < 0 || form > 3) return refuse("form outside 0..3");
+    if (form == 3 && n_seg != 1) return refuse("the expansion on the fly takes one tensor");
+    int64_t n_all = 0;
+    for (int s = 0; s < n_seg; s++) {
+        const int t = types[s];
+        const bool kq = t == T_Q4_K || t == T_Q5_K || t == T_Q6_K, small = t == T_Q2_K || t == T_Q3_K || t == T_IQ4_XS;
+        if (!kq && !(small && n_seg == 1 && (form == 0 || form == 2))) return refuse("a tensor type this launcher has no form for");
+        n_all += N[s];
+    }
+    hipDeviceProp_t prop;
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) set_num_cu(prop.multiProcessorCount);
+    // ---- device copies: rows in the device layout, the plane sets back to back in one arena (forms 0 and 2), out buffers, activation, workspace
+    const bool want_planes = form == 0 || form == 2;
+    size_t arena_bytes = 0;
+    std::vector<size_t> poff((size_t)n_seg, 0);
+    for (int s = 0; s < n_seg; s++) { poff[(size_t)s] = arena_bytes; arena_bytes += mmq_planes_bytes(types[s], N[s], (int)K); }
+    DevBuf arena(want_planes ? arena_bytes : 16);
+    std::vector<std::unique_ptr<DevBuf>> dw, dy;
+    std::vector<DevTensor> wt((size_t)n_seg);
+    const size_t ws_bytes = (size_t)4 * T * n_all * sizeof(float);     // (the K-split partial sums: up to four splits of every segment)
+    DevBuf wsb(ws_bytes), dx((size_t)K * T * 4 * (prologue == 2 ? 2 : 1)), dnw((size_t)K * 4), bh(mmq_prep_bytes((int)K, (int)T)), bl(mmq_prep_bytes((int)K, (int)T));
+    ActBufs ab((size_t)K, (size_t)T);
+    if (!arena.p || !wsb.p || !dx.up(x, dx.n) || !dnw.p || (norm_w && !dnw.up(norm_w, (size_t)K * 4)) || !bh.p || !bl.p || !ab.ok() ||
+        hipMemset(bh.p, 0xFF, bh.n) != hipSuccess || hipMemset(bl.p, 0xFF, bl.n) != hipSuccess) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    for (int s = 0; s < n_seg; s++) {
+        const size_t grow = ggml_row_bytes(types[s], K), drow = dev_row_bytes(types[s], K);
+        dw.emplace_back(new DevBuf(drow * N[s]));
+        dy.emplace_back(new DevBuf((size_t)T * (N[s] + ld_pad) * 4));
+        if (!grow || !dw.back()->p || !dy.back()->p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+        DevTensor &w = wt[(size_t)s];
+        w.type = types[s]; w.K = K; w.N = N[s]; w.n_expert = 1; w.data = dw.back()->as<uint8_t>(); w.row_bytes = drow; w.bytes = drow * (size_t)N[s];
+        if (want_planes) { w.planes = arena.as<uint8_t>() + poff[(size_t)s]; w.planes_bytes = mmq_planes_bytes(types[s], N[s], (int)K); }
+    }
+    MMQWorkspace wsp; wsp.p = wsb.as<float>(); wsp.bytes = ws_bytes;
+    // ---- which launch: the model's choice (form 0), or the launcher named; what the launcher would refuse is refused here, before anything is launched
+    int rows[3], lds[3], tys[3];
+    float *outs[3];
+    const DevTensor *wp[3];
+    for (int s = 0; s < n_seg; s++) { rows[s] = (int)N[s]; lds[s] = (int)(N[s] + ld_pad); tys[s] = types[s]; outs[s] = dy[(size_t)s]->as<float>(); wp[s] = &wt[(size_t)s]; }
+    int kind = form, n_fused = n_seg;
+    bool swiglu = epi == EPI_SWIGLU;
+    if (form == 0) {
+        const PromptMatmul pm = prompt_mul_mat_choice(epi == EPI_SWIGLU ? PM_ROLE_GATE_UP : n_seg == 1 ? PM_ROLE_ONE : PM_ROLE_MULTI, wp, n_seg, (int)K, (int)T, wsp);
+        if (pm.form == PM_NONE) return refuse("the model has no MFMA launch for these tensors and this batch");
+        if (epi == EPI_SWIGLU && !pm.swiglu) return refuse("the model runs SwiGLU behind this launch, in a pass of its own");
+        kind = pm.form; n_fused = pm.n_fused;
+    }
+    MMQPlanesForm pf{};
+    if (kind == PM_KSPLIT) {
+        for (int s = 0; s < n_seg; s++) if (!mmq_ksplit_applicable(types[s], (int)K, (int)T)) return refuse("the K-split kernel does not take this type or batch");
+    } else if (kind == PM_PLANES) {
+        for (int s = 0; s < n_seg; s++) if (!mmq_applicable(types[s], (int)K, (int)T) && !(type_is_planes_only(types[s]) && T >= 32)) return refuse("the plane kernels take batches of 32 tokens and more");
+        if (swiglu) {
+            if (!mmq_planes_swiglu_ok(types[0], types[1], rows[0], (int)K, (int)T)) return refuse("launch_mmq_planes_swiglu does not take this shape");
+            pf.kernel = MMQ_PLANES_LDS; pf.n_split = 1; pf.mixed = false;
+        } else {
+            if (form == 0 && n_fused < 2) n_fused = 1;              // (no two plane sets fuse: every tensor on its own, path describes the first)
+            if (!mmq_planes_form(types[0], rows, n_fused, (int)K, (int)T, epi == EPI_ADD, wsp, tys, &pf)) return refuse("launch_mmq_planes_multi refuses these segments");
+        }
+    } else {
+        if (!mmq_applicable(types[0], (int)K, (int)T)) return refuse("launch_mmq does not take this type or batch");
+    }
+    // ---- set-up: the rows in the device layout, their plane sets, the out buffers 0xFF
+    for (int s = 0; s < n_seg; s++) {
+        const size_t grow = ggml_row_bytes(types[s], K);
+        DevTensor &w = wt[(size_t)s];
+        DevBuf wsrc(grow * N[s]);
+        if (!wsrc.up(W[s], grow * N[s])) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+        hipError_t e = launch_repack_rows(types[s], wsrc.as<uint8_t>(), w.data, K, N[s], nullptr);
+        if (e == hipSuccess && want_planes) e = launch_mmq_expand(types[s], w.data, w.row_bytes, (int)N[s], (int)K, w.planes, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemset(dy[(size_t)s]->p, 0xFF, dy[(size_t)s]->n);
+        if (e != hipSuccess) return hip_fail(e, "prompt_mul_mat (set-up)");
+    }
+    // ---- the residual: in place it sits in the out buffer, as attn_output and ffn_down have it
+    const size_t rbytes = (size_t)T * (N[0] + ld_pad) * 4;
+    DevBuf dres(epi == EPI_ADD && !in_place ? rbytes : 16);
+    const float *rs = nullptr;
+    if (epi == EPI_ADD) {
+        DevBuf &rb = in_place ? *dy[0] : dres;
+        if (!rb.up(resid, rbytes)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+        rs = rb.as<float>();
+    }
+    // ---- the activation and its block-sum planes
+    hipError_t e;
+    if (prologue == 0) {
+        e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, true, false, nullptr);
+        if (e == hipSuccess) e = launch_mmq_prep(ab.q, (int)K, (int)T, bh.as<int8_t>(), bl.as<int8_t>(), nullptr);
+    } else if (prologue == 1) e = launch_rmsnorm_quant(dx.as<float>(), dnw.as<float>(), (int)K, (int)T, eps, nullptr, &ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
+    else if (prologue == 2) e = launch_swiglu_quant(dx.as<float>(), dx.as<float>() + (size_t)T * K, (int)K, (int)T, ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
+    else e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
+    if (e != hipSuccess) return hip_fail(e, "prompt_mul_mat (activation)");
+    // ---- the launch
+    const int8_t *pbh = bh.as<int8_t>(), *pbl = bl.as<int8_t>();
+    if (kind == PM_KSPLIT) {
+        MMQSeg sg[3];
+        for (int s = 0; s < n_seg; s++) sg[s] = MMQSeg{wt[(size_t)s].data, wt[(size_t)s].row_bytes, rows[s], types[s], outs[s], lds[s], s == 0 ? rs : nullptr, 0};
+        e = launch_mmq_ksplit_multi(sg, n_seg, (int)K, (int)T, ab.q, pbh, pbl, swiglu, nullptr);
+        path[0] = 1; path[1] = mmq_ksplit_token_tiles((int)T); path[2] = 1;
+    } else if (kind == PM_PLANES && swiglu) {
+        e = launch_mmq_planes_swiglu(types[0], wt[0].planes, wt[1].planes, rows[0], (int)K, (int)T, ab.q, outs[0], lds[0], nullptr);
+        path[0] = pf.kernel; path[2] = 1;
+    } else if (kind == PM_PLANES) {
+        e = launch_mmq_planes_multi(types[0], wt[0].planes, rows, outs, lds, n_fused, (int)K, (int)T, ab.q, pbh, pbl, rs, nullptr, wsp, tys);
+        for (int s = n_fused; s < n_seg && e == hipSuccess; s++)     // (form 0: the tensors the fused launch left out, each on its plane set as Context::linear_multi runs them)
+            e = launch_mmq_planes(types[s], wt[(size_t)s].planes, rows[s], (int)K, (int)T, ab.q, pbh, pbl, outs[s], lds[s], nullptr, nullptr, wsp);
+        path[0] = pf.kernel; path[2] = pf.n_split; path[3] = pf.mixed ? 1 : 0;
+    } else {
+        e = launch_mmq(types[0], wt[0].data, wt[0].row_bytes, rows[0], (int)K, (int)T, ab.q, pbh, pbl, outs[0], lds[0], rs, nullptr);
+        path[0] = 5; path[2] = 1;
+    }
+    path[4] = swiglu ? 1 : 0; path[5] = prologue == 0 ? 1 : 0;
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "prompt_mul_mat");
+    for (int s = 0; s < n_out; s++)
+        if (!dy[(size_t)s]->down(y[s], (size_t)T * (N[s] + ld_pad) * 4)) return MI355_ERR_HIP;
+    return MI355_OK;
+}
+
+// One producer of the MFMA kernels' activation, with Q8_K and the bh / bl planes as the model calls it; launch_mmq_prep's planes of the same rows beside them
+int mi355_op_act_q8k_planes(int32_t producer, const float *x, const float *x2, const float *norm_w, float eps, int64_t n, int64_t T, void *out_blocks,
+                            int8_t *out_bh, int8_t *out_bl, int8_t *prep_bh, int8_t *prep_bl, float *y_f32) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (producer < 0 || producer > 2 || !x || (producer == 1 && !norm_w) || (producer == 2 && !x2) || (producer != 1 && y_f32) || !out_blocks || !out_bh || !out_bl ||
+        !prep_bh || !prep_bl || n <= 0 || n % 256 || n > (1 << 20) || T <= 0 || T > 4096) { fail("act_q8k_planes: bad arguments"); return MI355_ERR_ARG; }
+    const size_t xb = (size_t)n * T * 4, pb = mmq_prep_bytes((int)n, (int)T), ob = ggml_row_bytes(T_Q8_K, n) * T;
+    DevBuf dx(xb), dx2(producer == 2 ? xb : 16), dw((size_t)n * 4), dyf(y_f32 ? xb : 16), dout(ob), bh(pb), bl(pb), ph(pb), pl(pb);
+    ActBufs ab((size_t)n, (size_t)T);
+    if (!dx.up(x, xb) || !dx2.p || (producer == 2 && !dx2.up(x2, xb)) || !dw.p || (producer == 1 && !dw.up(norm_w, (size_t)n * 4)) || !dyf.p || !dout.p || !bh.p || !bl.p ||
+        !ph.p || !pl.p || !ab.ok() || hipMemset(bh.p, 0xFF, pb) != hipSuccess || hipMemset(bl.p, 0xFF, pb) != hipSuccess) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e;
+    if (producer == 0) e = launch_quantize(dx.as<float>(), (int)n, (int)T, ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
+    else if (producer == 1) e = launch_rmsnorm_quant(dx.as<float>(), dw.as<float>(), (int)n, (int)T, eps, y_f32 ? dyf.as<float>() : nullptr, &ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
+    else e = launch_swiglu_quant(dx.as<float>(), dx2.as<float>(), (int)n, (int)T, ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
+    if (e == hipSuccess) e = launch_mmq_prep(ab.q, (int)n, (int)T, ph.as<int8_t>(), pl.as<int8_t>(), nullptr);
+    if (e == hipSuccess) e = launch_pack_q8k_blocks(ab.q, (int)n, (int)T, dout.as<uint8_t>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "act_q8k_planes");
+    if (y_f32 && !dyf.down(y_f32, xb)) return MI355_ERR_HIP;
+    return dout.down(out_blocks, ob) && bh.down(out_bh, pb) && bl.down(out_bl, pb) && ph.down(prep_bh, pb) && pl.down(prep_bl, pb) ? MI355_OK : MI355_ERR_HIP;
+}
+
 int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
     if (n <= 0 || n % 8) { fail("f32_to_bf16: n must be a positive multiple of 8"); return MI355_ERR_ARG; }
@@ -2018,7 +2183,17 @@ int mi355_op_attn_batch_step(const float *q, const float *k_new, const float *v_
                              int32_t type_v, void *v_cache, int32_t n_cells, int32_t n_kv, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *tok_pos,
                              const int32_t *tok_seq, const int32_t *tok_cell, float rope_base, int32_t n_rot, int32_t neox, float scale, int32_t mode,
                              float *att_out, void *q8k_out) {
+    return mi355_op_attn_batch_step_planes(q, k_new, v_new, T, H, G, D, type_k, k_cache, type_v, v_cache, n_cells, n_kv, cell_pos, cell_seq, tok_pos, tok_seq, tok_cell,
+                                           rope_base, n_rot, neox, scale, mode, att_out, q8k_out, nullptr, nullptr);
+}
+// bh_out / bl_out (both or neither, with q8k_out): the merge also writes the block sums of its Q8_K rows as the int8 planes of the MFMA kernels (AttnArgs out_bh /
+// out_bl, what Context::attn_core sets for a K-quant attn_output); the planes are 0xFF bytes before the launch
+int mi355_op_attn_batch_step_planes(const float *q, const float *k_new, const float *v_new, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, void *k_cache,
+                                    int32_t type_v, void *v_cache, int32_t n_cells, int32_t n_kv, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *tok_pos,
+                                    const int32_t *tok_seq, const int32_t *tok_cell, float rope_base, int32_t n_rot, int32_t neox, float scale, int32_t mode,
+                                    float *att_out, void *q8k_out, int8_t *bh_out, int8_t *bl_out) {
     if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if ((bh_out != nullptr) != (bl_out != nullptr) || (bh_out && !q8k_out)) { fail("attn_batch_step: bh_out / bl_out come together and with q8k_out"); return MI355_ERR_ARG; }
     if (!q || !k_new || !v_new || !k_cache || !v_cache || !cell_pos || !cell_seq || !tok_pos || !tok_seq || !tok_cell || !att_out) { fail("attn_batch_step: null argument"); return MI355_ERR_ARG; }
     if (mode < 0 || mode > 3) { fail("attn_batch_step: mode outside [0, 3]"); return MI355_ERR_ARG; }
     if (T < 1 || T > 64) { fail("attn_batch_step: a batched step holds 1 .. 64 tokens"); return MI355_ERR_ARG; }
@@ -2049,6 +2224,9 @@ int mi355_op_attn_batch_step(const float *q, const float *k_new, const float *v_
     DevBuf dq((size_t)T * K * 4), dkn((size_t)T * kv_dim * 4), dvn((size_t)T * kv_dim * 4), datt((size_t)T * K * 4), dcp((size_t)n_cells * 4), dcs((size_t)n_cells * 8);
     DevBuf dtp((size_t)T * 4), dts((size_t)T * 4), dcell((size_t)T * 4), dn(16), dcsb((size_t)T * n_rot * 4 + 64), dblk(q8k_out ? ggml_row_bytes(T_Q8_K, (int64_t)K) * T : 16);
     ActBufs ab(q8k_out ? K : 256, (size_t)T + 1);
+    const size_t pb = bh_out ? (size_t)T * (K / 16) : 0;
+    DevBuf dbh(pb ? pb : 16), dbl(pb ? pb : 16);
+    if (!dbh.p || !dbl.p || hipMemset(dbh.p, 0xFF, dbh.n) != hipSuccess || hipMemset(dbl.p, 0xFF, dbl.n) != hipSuccess) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
     if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dks.p || !dvs.p || !dq.up(q, (size_t)T * K * 4) || !dkn.up(k_new, (size_t)T * kv_dim * 4) ||
         !dvn.up(v_new, (size_t)T * kv_dim * 4) || !datt.p || !dcp.up(cell_pos, (size_t)n_cells * 4) || !dcs.up(cell_seq, (size_t)n_cells * 8) ||
         !dtp.up(tok_pos, (size_t)T * 4) || !dts.up(tok_seq, (size_t)T * 4) || !dcell.up(tok_cell, (size_t)T * 4) || !dn.up(&n_kv, 4) || !dcsb.p || !dblk.p || !ab.ok()) {
@@ -2062,6 +2240,7 @@ int mi355_op_attn_batch_step(const float *q, const float *k_new, const float *v_
     a.kv.k = dk.as<uint8_t>(); a.kv.kd = dks.as<uint16_t>(); a.kv.v = dv.as<uint8_t>(); a.kv.vd = dvs.as<uint16_t>();
     a.cell_pos = dcp.as<int32_t>(); a.cell_seq = dcs.as<uint64_t>(); a.tok_pos = dtp.as<int32_t>(); a.tok_seq = dts.as<int32_t>(); a.n_kv_dev = dn.as<int32_t>();
     if (q8k_out) { a.out_q = &ab.q; a.out_q8k = true; a.out_q80 = false; }
+    if (bh_out) { a.out_bh = dbh.as<int8_t>(); a.out_bl = dbl.as<int8_t>(); }
     if (mode == 3) {
         a.splits = flash_attn_pick_splits((int)T, G, n_cells);
         a.pf_splits = flash_attn_prefill_splits((int)T, H, G, D, n_cells);
@@ -2089,6 +2268,7 @@ int mi355_op_attn_batch_step(const float *q, const float *k_new, const float *v_
     if (e != hipSuccess) return hip_fail(e, "attn_batch_step");
     if (!datt.down(att_out, (size_t)T * K * 4)) return MI355_ERR_HIP;
     if (q8k_out && !dblk.down(q8k_out, ggml_row_bytes(T_Q8_K, (int64_t)K) * T)) return MI355_ERR_HIP;
+    if (bh_out && (!dbh.down(bh_out, pb) || !dbl.down(bl_out, pb))) return MI355_ERR_HIP;
     if (!cache_rows_from_planes(type_k, dk, dks, G, D, n_cells, k_cache) || !cache_rows_from_planes(type_v, dv, dvs, G, D, n_cells, v_cache)) return MI355_ERR_HIP;
     return MI355_OK;
 }

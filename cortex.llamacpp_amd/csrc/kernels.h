@@ -174,6 +174,11 @@ hipError_t launch_mmq_planes_multi(int type, const uint8_t *planes, const int *s
 // seg_types (per segment; nullptr = all `type`): Q4_K / Q5_K segments beside Q6_K ones in ONE launch where this says so (segments end on
 // 128-row tiles and the launch takes the 128 x 256 kernel)
 bool mmq_planes_mixed_ok(const int *seg_rows, int n_seg, int K, int T, MMQWorkspace wsp);
+// the kernel launch_mmq_planes_multi takes for its arguments (host logic, stated once: the launcher calls it): the tile form, the K split of the 128 x 256
+// LDS kernel (1 for the other two) and whether the segments mix the two plane formats.  false: the launcher refuses the arguments (hipErrorInvalidValue).
+enum { MMQ_PLANES_256X32 = 2, MMQ_PLANES_128X128 = 3, MMQ_PLANES_LDS = 4 };
+struct MMQPlanesForm { int kernel, n_split; bool mixed; };
+bool mmq_planes_form(int type, const int *seg_rows, int n_seg, int K, int T, bool has_resid, MMQWorkspace wsp, const int *seg_types, MMQPlanesForm *f);
 // ffn_gate and ffn_up (one plane type, n_rows rows each) in one launch with SwiGLU in the epilogue: out[t][row] = silu(gate . x) * (up . x)
 bool mmq_planes_swiglu_ok(int type_gate, int type_up, int n_rows, int K, int T);
 hipError_t launch_mmq_planes_swiglu(int type, const uint8_t *planes_gate, const uint8_t *planes_up, int n_rows, int K, int T, const ActQuant &q,
@@ -181,6 +186,7 @@ hipError_t launch_mmq_planes_swiglu(int type, const uint8_t *planes_gate, const 
 bool mmq_ksplit_applicable(int type, int K, int T);
 // ... and preferred over the planes kernels for a tensor of n_rows rows (has_planes: its pre-expanded planes exist)
 bool mmq_ksplit_preferred(int type, int n_rows, int K, int T, bool has_planes, bool pair = false);
+int mmq_ksplit_token_tiles(int T);                         // 32-token tiles per workgroup of the K-split kernel (1 up to 32 tokens, else 2)
 hipError_t launch_mmq_ksplit_multi(const MMQSeg *segs, int n_seg, int K, int T, const ActQuant &q, const int8_t *bh, const int8_t *bl,
                                    bool swiglu, hipStream_t st);
 hipError_t launch_mmq_ksplit(int type, const uint8_t *W, size_t row_bytes, int n_rows, int K, int T, const ActQuant &q,

@@ -1739,6 +1739,8 @@ bool mmq_ksplit_preferred(int type, int n_rows, int K, int T, bool has_planes, b
     return true;
 }
 
+int mmq_ksplit_token_tiles(int T) { return T <= 32 ? 1 : 2; }
+
 // segs: up to 3 tensors sharing the activation; swiglu: segs = {gate, up} of one type and shape, out = silu(gate.x) * (up.x) into segs[0].out
 hipError_t launch_mmq_ksplit_multi(const MMQSeg *segs, int n_seg, int K, int T, const ActQuant &q, const int8_t *bh, const int8_t *bl,
                                    bool swiglu, hipStream_t st) {
@@ -1753,7 +1755,7 @@ hipError_t launch_mmq_ksplit_multi(const MMQSeg *segs, int n_seg, int K, int T, 
         a.seg[i].tile0 = tiles;
         if (!swiglu || i == 0) tiles += (segs[i].n_rows + 31) / 32;
     }
-    const int mt = T <= 32 ? 1 : 2;
+    const int mt = mmq_ksplit_token_tiles(T);
     const dim3 grid((unsigned)tiles, (unsigned)((T + 32 * mt - 1) / (32 * mt)));
 #define KS(MTV, SW)                                                                                                  \
     {                                                                                                                \
@@ -1903,23 +1905,18 @@ hipError_t launch_mmq_planes_moe(int type, const uint8_t *planes, size_t plane_s
     return hipGetLastError();
 }
 
-hipError_t launch_mmq_planes_multi(int type, const uint8_t *planes, const int *seg_rows, float *const *outs, const int *lds_out, int n_seg, int K, int T,
-                                   const ActQuant &q, const int8_t *bh, const int8_t *bl, const float *resid, hipStream_t st, MMQWorkspace wsp,
-                                   const int *seg_types) {
-    if (n_seg < 1 || n_seg > 3 || (n_seg > 1 && resid)) return hipErrorInvalidValue;
-    PlanesOut po{};
-    po.n_seg = n_seg;
+// The form launch_mmq_planes_multi takes for a launch (host logic, stated once: the launcher calls it).  false: the launcher refuses the arguments.
+bool mmq_planes_form(int type, const int *seg_rows, int n_seg, int K, int T, bool has_resid, MMQWorkspace wsp, const int *seg_types, MMQPlanesForm *f) {
+    if (n_seg < 1 || n_seg > 3 || (n_seg > 1 && has_resid)) return false;
     int n_rows = 0;
     bool mixed = false;
     for (int i = 0; i < n_seg; i++) {
-        if (i + 1 < n_seg && (seg_rows[i] % 32) != 0) return hipErrorInvalidValue;
+        if (i + 1 < n_seg && (seg_rows[i] % 32) != 0) return false;
         n_rows += seg_rows[i];
-        po.out[i] = outs[i]; po.ld[i] = lds_out[i]; po.row_end[i] = n_rows;
         const int ti = seg_types ? seg_types[i] : type;
-        if (planes_have_mins(ti)) po.mins_mask |= 1u << i;
         mixed = mixed || planes_have_mins(ti) != planes_have_mins(type);
     }
-    if (mixed && !mmq_planes_mixed_ok(seg_rows, n_seg, K, T, wsp)) return hipErrorInvalidValue;
+    if (mixed && !mmq_planes_mixed_ok(seg_rows, n_seg, K, T, wsp)) return false;
     static const int env_mt = getenv("MI355_MMQ_MT") ? atoi(getenv("MI355_MMQ_MT")) : 0;
     // 128 x 128 workgroup tiles (two token tiles per wave) when that still yields ~2 workgroups per CU, else 256 x 32
     // tiles, which quadruple the workgroup count (measured on the 8B shapes: gate/up 297 vs 383 us, N = 4096 tensors
@@ -1929,11 +1926,31 @@ hipError_t launch_mmq_planes_multi(int type, const uint8_t *planes, const int *s
     if (n_seg > 1 && T > 32 && wg2 * 4 >= 3L * num_cu()) mt = 2;       // concatenated Q | K | V: 192 workgroups of 128 x 128 beat 384 of 256 x 32 (59 vs 71 us)
     if (env_mt == 1 || env_mt == 2) mt = env_mt;
     if (g_mmq_mt == 1 || g_mmq_mt == 2) mt = g_mmq_mt;
-    const bool mins = planes_have_mins(type);
     // both operands through LDS (128 rows x 256 tokens per workgroup) once that grid covers most of the chip; tensors with
     // too few rows for that split K over 2..4 workgroups (partial sums in the caller's workspace, added up in split order)
     bool p2 = false;
     const int n_split = planes2_split(n_rows, K, T, wsp, &p2);
+    f->kernel = p2 ? MMQ_PLANES_LDS : mt == 2 ? MMQ_PLANES_128X128 : MMQ_PLANES_256X32;
+    f->n_split = p2 ? n_split : 1;
+    f->mixed = mixed;
+    return true;
+}
+
+hipError_t launch_mmq_planes_multi(int type, const uint8_t *planes, const int *seg_rows, float *const *outs, const int *lds_out, int n_seg, int K, int T,
+                                   const ActQuant &q, const int8_t *bh, const int8_t *bl, const float *resid, hipStream_t st, MMQWorkspace wsp,
+                                   const int *seg_types) {
+    MMQPlanesForm form;
+    if (!mmq_planes_form(type, seg_rows, n_seg, K, T, resid != nullptr, wsp, seg_types, &form)) return hipErrorInvalidValue;
+    PlanesOut po{};
+    po.n_seg = n_seg;
+    int n_rows = 0;
+    for (int i = 0; i < n_seg; i++) {
+        n_rows += seg_rows[i];
+        po.out[i] = outs[i]; po.ld[i] = lds_out[i]; po.row_end[i] = n_rows;
+        if (planes_have_mins(seg_types ? seg_types[i] : type)) po.mins_mask |= 1u << i;
+    }
+    const bool mixed = form.mixed, mins = planes_have_mins(type), p2 = form.kernel == MMQ_PLANES_LDS;
+    const int mt = form.kernel == MMQ_PLANES_128X128 ? 2 : 1, n_split = form.n_split;
     if (p2) {
         const int nrt = (n_rows + P2_ROWS - 1) / P2_ROWS, ntt = (T + P2_TOK - 1) / P2_TOK;
         const dim3 grid((unsigned)(((nrt + 7) / 8) * ntt * n_split * 8));

@@ -991,6 +991,59 @@ static bool q80_copy(const DevTensor &w, int K, int T) {
 }
 static bool planes_small(const DevTensor &w, int K, int T) { return type_is_planes_only(w.type) && w.planes && T >= 32 && (K % 256) == 0; }
 
+PromptMatmul prompt_mul_mat_choice(int role, const DevTensor *const *ws, int n, int K, int T, MMQWorkspace wsp) {
+    PromptMatmul pm;
+    if (role == PM_ROLE_ONE) {
+        const DevTensor &w = *ws[0];
+        if (mmq_ksplit_preferred(w.type, (int)w.N, K, T, w.planes != nullptr)) {   // batched decode steps, short prompts, expert batches: MFMA, K split
+            pm.form = PM_KSPLIT; pm.n_fused = 1; pm.need_prep = w.type != T_Q6_K;
+        } else if (mmq_applicable(w.type, K, T)) {                                  // prompt processing: MFMA path
+            pm.form = w.planes ? PM_PLANES : PM_FLY; pm.n_fused = 1; pm.need_prep = w.type != T_Q6_K || !w.planes;
+        } else if (planes_small(w, K, T)) {
+            // prompt processing of Q2_K / Q3_K / IQ4_XS / TQ1_0 / TQ2_0 tensors: their plane sets (expanded at load in the Q4_K / Q6_K plane formats, mmq.hip) on the same kernels
+            pm.form = PM_PLANES; pm.n_fused = 1; pm.planes_only = true; pm.need_prep = w.type == T_Q2_K;
+        }
+        return pm;
+    }
+    if (role == PM_ROLE_MULTI) {
+        bool all_mmq = true, all_ks = true;
+        // (IQ4_XS, TQ1_0, TQ2_0: through their plane sets, the signed format - Q | K | V of those mixes run as one launch like the K-quants')
+        auto signed_planes_only = [](int t) { return t == T_IQ4_XS || type_is_ternary(t); };
+        for (int i = 0; i < n; i++) { all_mmq &= mmq_applicable(ws[i]->type, K, T) || (signed_planes_only(ws[i]->type) && planes_small(*ws[i], K, T)); all_ks &= mmq_ksplit_applicable(ws[i]->type, K, T); }
+        if (all_ks && n <= 3) {                                  // batched decode step: Q, K, V in one launch
+            pm.form = PM_KSPLIT; pm.n_fused = n; pm.need_prep = true;
+            return pm;
+        }
+        if (!all_mmq) return pm;
+        // Q | K | V (or Q | K) as one launch over the concatenated rows where their plane sets are adjacent in the arena and
+        // of one plane format (Q4_K and Q5_K share it; the Q6_K attn_v of the "more bits" layers runs on its own)
+        auto mins = [&](int t) { return t != T_Q6_K && !signed_planes_only(t); };
+        auto adjacent = [&](int i) { return ws[i]->planes && ws[i - 1]->planes && ws[i]->planes == ws[i - 1]->planes + ws[i - 1]->planes_bytes &&
+                                            (ws[i - 1]->N % 32) == 0 && ws[i]->n_expert == 1; };
+        int nf = 1;
+        while (nf < n && nf < 3 && adjacent(nf) && mins(ws[nf]->type) == mins(ws[0]->type)) nf++;
+        // the "more bits" layers (Q6_K attn_v beside Q4_K / Q5_K attn_q, attn_k): still one launch where the 128 x 256 kernel takes it
+        int nm = nf;
+        while (nm < n && nm < 3 && adjacent(nm)) nm++;
+        if (nm > nf) {
+            int rows[3];
+            for (int i = 0; i < nm; i++) rows[i] = (int)ws[i]->N;
+            if (mmq_planes_mixed_ok(rows, nm, K, T, wsp)) nf = nm;
+        }
+        pm.form = PM_PLANES; pm.n_fused = nf >= 2 ? nf : 0; pm.need_prep = true;
+        return pm;
+    }
+    // PM_ROLE_GATE_UP: ws = {ffn_gate, ffn_up}
+    const DevTensor &g = *ws[0], &u = *ws[1];
+    if (mmq_ksplit_preferred(g.type, (int)g.N, K, T, g.planes != nullptr, true) && mmq_ksplit_preferred(u.type, (int)u.N, K, T, u.planes != nullptr, true)) {
+        pm.form = PM_KSPLIT; pm.n_fused = 2; pm.need_prep = g.type != T_Q6_K || u.type != T_Q6_K;     // batched decode step: gate and up in one launch
+        pm.swiglu = T <= 32 && g.type == u.type && g.N == u.N;   // SwiGLU in the epilogue
+    } else if (g.planes && u.planes && g.N == u.N && (mmq_applicable(g.type, K, T) || planes_small(g, K, T)) && mmq_planes_swiglu_ok(g.type, u.type, (int)g.N, K, T)) {
+        pm.form = PM_PLANES; pm.n_fused = 2; pm.swiglu = true;   // prompt batch on the LDS kernel: gate and up in one launch, SwiGLU in the epilogue
+    }
+    return pm;
+}
+
 hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *x_f32, int K, int T, float *out, int ld_out,
                            const float *resid, int epi) {
     if (type_is_quant(w.type)) {
@@ -998,22 +1051,17 @@ hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *
             return launch_mmq_q80(w.data, w.row_bytes, (int)w.N, K, T, aq, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
         // (bh_over_ / bl_over_: the caller prepared the block-sum planes of a larger batch that aq's rows are a slice of - the expert loop)
         const int8_t *bh = bh_over_ ? bh_over_ : mmq_bh_, *bl = bh_over_ ? bl_over_ : mmq_bl_;
-        if (mmq_ksplit_preferred(w.type, (int)w.N, K, T, w.planes != nullptr) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU) {   // batched decode steps, short prompts, expert batches: MFMA, K split
-            if (w.type != T_Q6_K && !bh_over_) HIP_TRY(ensure_prep(aq, K, T));
-            return launch_mmq_ksplit(w.type, w.data, w.row_bytes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
-        }
-        if (mmq_applicable(w.type, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU) {   // prompt processing: MFMA path
-            if ((w.type != T_Q6_K || !w.planes) && !bh_over_) HIP_TRY(ensure_prep(aq, K, T));
-            if (w.planes) return launch_mmq_planes(w.type, w.planes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_ws_);
+        // the K-quants' MFMA launches: the K-split kernel, the plane sets, the expansion on the fly (prompt_mul_mat_choice; the planes-only types want Q8_K rows)
+        const DevTensor *w1 = &w;
+        const PromptMatmul pm = pending_fuse_.mode == 0 && epi != EPI_SWIGLU ? prompt_mul_mat_choice(PM_ROLE_ONE, &w1, 1, K, T, mmq_ws_) : PromptMatmul();
+        if (pm.form != PM_NONE && !(pm.planes_only && !aq.qs)) {
+            if (pm.need_prep && !bh_over_) HIP_TRY(ensure_prep(aq, K, T));
+            if (pm.form == PM_KSPLIT) return launch_mmq_ksplit(w.type, w.data, w.row_bytes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
+            if (pm.form == PM_PLANES) return launch_mmq_planes(w.type, w.planes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_ws_);
             return launch_mmq(w.type, w.data, w.row_bytes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
         }
         if (q80_copy(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs0)      // prompt processing of Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4 tensors: their exact Q8_0-layout copy
             return launch_mmq_q80(w.planes, mmq_q80_copy_row_bytes(w.type, K), (int)w.N, K, T, aq, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_q80_copy_form(w.type));
-        if (planes_small(w, K, T) && pending_fuse_.mode == 0 && epi != EPI_SWIGLU && aq.qs) {
-            // prompt processing of Q2_K / Q3_K / IQ4_XS / TQ1_0 / TQ2_0 tensors: their plane sets (expanded at load in the Q4_K / Q6_K plane formats, mmq.hip) on the same kernels
-            if (w.type == T_Q2_K && !bh_over_) HIP_TRY(ensure_prep(aq, K, T));
-            return launch_mmq_planes(w.type, w.planes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_ws_);
-        }
         MMVQSeg s = make_seg(w, out, ld_out, resid, nullptr);
         return mmvq_tokens(&s, 1, K, T, epi, aq, stream_, pending_fuse_);
     }
@@ -1061,39 +1109,24 @@ hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs,
         if (bias_done) *bias_done = true;
         return hipSuccess;
     }
-    bool all_mmq = true, all_ks = true;
-    // (IQ4_XS, TQ1_0, TQ2_0: through their plane sets, the signed format - Q | K | V of those mixes run as one launch like the K-quants')
-    auto signed_planes_only = [](int t) { return t == T_IQ4_XS || type_is_ternary(t); };
-    for (int i = 0; i < n; i++) { all_mmq &= mmq_applicable(ws[i]->type, K, T) || (signed_planes_only(ws[i]->type) && planes_small(*ws[i], K, T)); all_ks &= mmq_ksplit_applicable(ws[i]->type, K, T); }
-    if (all_ks && pending_fuse_.mode == 0 && n <= 3) {         // batched decode step: Q, K, V in one launch
+    // Q | K | V of a batched decode step in one K-split launch; of a prompt batch as one launch over the concatenated plane sets where those are adjacent
+    // (prompt_mul_mat_choice), the rest each on its own
+    const PromptMatmul pm = pending_fuse_.mode == 0 ? prompt_mul_mat_choice(PM_ROLE_MULTI, ws, n, K, T, mmq_ws_) : PromptMatmul();
+    if (pm.form == PM_KSPLIT) {
         HIP_TRY(ensure_prep(aq, K, T));
         MMQSeg sg[3];
         for (int i = 0; i < n; i++) sg[i] = MMQSeg{ws[i]->data, ws[i]->row_bytes, (int)ws[i]->N, ws[i]->type, outs[i], (int)ws[i]->N, nullptr, 0};
         return launch_mmq_ksplit_multi(sg, n, K, T, aq, mmq_bh_, mmq_bl_, false, stream_);
     }
-    if (all_mmq && pending_fuse_.mode == 0) {
+    if (pm.form == PM_PLANES) {
         HIP_TRY(ensure_prep(aq, K, T));
-        // Q | K | V (or Q | K) as one launch over the concatenated rows where their plane sets are adjacent in the arena and
-        // of one plane format (Q4_K and Q5_K share it; the Q6_K attn_v of the "more bits" layers runs on its own)
-        auto mins = [&](int t) { return t != T_Q6_K && !signed_planes_only(t); };
-        auto adjacent = [&](int i) { return ws[i]->planes && ws[i - 1]->planes && ws[i]->planes == ws[i - 1]->planes + ws[i - 1]->planes_bytes &&
-                                            (ws[i - 1]->N % 32) == 0 && ws[i]->n_expert == 1; };
-        int nf = 1;
-        while (nf < n && nf < 3 && adjacent(nf) && mins(ws[nf]->type) == mins(ws[0]->type)) nf++;
-        // the "more bits" layers (Q6_K attn_v beside Q4_K / Q5_K attn_q, attn_k): still one launch where the 128 x 256 kernel takes it
-        int nm = nf;
-        while (nm < n && nm < 3 && adjacent(nm)) nm++;
-        if (nm > nf) {
-            int rows[3];
-            for (int i = 0; i < nm; i++) rows[i] = (int)ws[i]->N;
-            if (mmq_planes_mixed_ok(rows, nm, K, T, mmq_ws_)) nf = nm;
-        }
+        const int nf = pm.n_fused;
         if (nf >= 2) {
             int rows[3], ldo[3], types[3];
             float *o[3];
             for (int i = 0; i < nf; i++) { rows[i] = (int)ws[i]->N; ldo[i] = (int)ws[i]->N; o[i] = outs[i]; types[i] = ws[i]->type; }
             HIP_TRY(launch_mmq_planes_multi(ws[0]->type, ws[0]->planes, rows, o, ldo, nf, K, T, aq, mmq_bh_, mmq_bl_, nullptr, stream_, mmq_ws_, types));
-        } else nf = 0;
+        }
         for (int i = nf; i < n; i++) {
             if (ws[i]->planes) HIP_TRY(launch_mmq_planes(ws[i]->type, ws[i]->planes, (int)ws[i]->N, K, T, aq, mmq_bh_, mmq_bl_, outs[i], (int)ws[i]->N, nullptr, stream_, mmq_ws_));
             else HIP_TRY(launch_mmq(ws[i]->type, ws[i]->data, ws[i]->row_bytes, (int)ws[i]->N, K, T, aq, mmq_bh_, mmq_bl_, outs[i], (int)ws[i]->N, nullptr, stream_));
@@ -1640,8 +1673,10 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
                          (mmq_applicable(L.gate.type, E, T) && mmq_applicable(L.up.type, E, T)) ||
                          (mmq_ksplit_applicable(L.gate.type, E, T) && mmq_ksplit_applicable(L.up.type, E, T)) ||
                          (planes_small(L.gate, E, T) && planes_small(L.up, E, T)) || (q80_copy(L.gate, E, T) && q80_copy(L.up, E, T));
-    const bool ffn_ks = mmq_ksplit_preferred(L.gate.type, (int)L.gate.N, E, T, L.gate.planes != nullptr, true) &&
-                        mmq_ksplit_preferred(L.up.type, (int)L.up.N, E, T, L.up.planes != nullptr, true) && !fuse_ffn;
+    // gate | up as one MFMA launch: the K-split pair, or the plane sets with SwiGLU in the epilogue (prompt_mul_mat_choice)
+    const DevTensor *gu_w[2] = {&L.gate, &L.up};
+    const PromptMatmul gu_pm = fuse_ffn ? PromptMatmul() : prompt_mul_mat_choice(PM_ROLE_GATE_UP, gu_w, 2, E, T, mmq_ws_);
+    const bool ffn_ks = gu_pm.form == PM_KSPLIT;
     if (lora_any) {
         HIP_TRY(linear(L.gate, aq_e_, xn_, E, T, ffn_, FF, nullptr, EPI_STORE));
         HIP_TRY(linear(L.up, aq_e_, xn_, E, T, ffn_u_, FF, nullptr, EPI_STORE));
@@ -1666,16 +1701,15 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
         HIP_TRY(linear_bf16(gu, go, nullptr, 2, E, T, 0, nullptr, quantised ? EPI_STORE : EPI_SWIGLU));
         if (quantised) HIP_TRY(quantise_for_down(il, T, false, false));
     } else if (ffn_ks) {                                   // batched decode step: gate and up in one launch
-        if (L.gate.type != T_Q6_K || L.up.type != T_Q6_K) HIP_TRY(ensure_prep(aq_e_, E, T));
+        if (gu_pm.need_prep) HIP_TRY(ensure_prep(aq_e_, E, T));
         MMQSeg sg[2] = {{L.gate.data, L.gate.row_bytes, (int)L.gate.N, L.gate.type, ffn_, FF, nullptr, 0},
                         {L.up.data, L.up.row_bytes, (int)L.up.N, L.up.type, ffn_u_, FF, nullptr, 0}};
-        const bool pair = T <= 32 && L.gate.type == L.up.type && L.gate.N == L.up.N;     // SwiGLU in the epilogue
+        const bool pair = gu_pm.swiglu;                          // SwiGLU in the epilogue
         HIP_TRY(launch_mmq_ksplit_multi(sg, 2, E, T, aq_e_, mmq_bh_, mmq_bl_, pair, stream_));
         quantised = !pair && down_q;
         if (quantised) HIP_TRY(quantise_for_down(il, T, false, true));
         else if (!pair) HIP_TRY(launch_swiglu(ffn_, ffn_u_, ffn_, (int64_t)T * FF, stream_));
-    } else if (T > 1 && !fuse_ffn && L.gate.planes && L.up.planes && L.gate.N == L.up.N && (mmq_applicable(L.gate.type, E, T) || planes_small(L.gate, E, T)) &&
-               mmq_planes_swiglu_ok(L.gate.type, L.up.type, (int)L.gate.N, E, T)) {
+    } else if (T > 1 && gu_pm.form == PM_PLANES) {
         // prompt batch on the LDS kernel: gate and up in one launch, 64 rows of each per workgroup, SwiGLU in the epilogue (one
         // f32 result of T x FF instead of two); the quantiser for the down projection then reads half as much
         HIP_TRY(launch_mmq_planes_swiglu(L.gate.type, L.gate.planes, L.up.planes, (int)L.gate.N, E, T, aq_e_, ffn_, FF, stream_));

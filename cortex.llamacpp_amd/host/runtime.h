@@ -92,6 +92,19 @@ struct MMVQTrace {
 MMVQSeg make_seg(const DevTensor &w, float *out, int ld_out, const float *resid, const int32_t *esel);
 MMVQArgs single_token_desc(int n_seg, int K, int epi, int fuse, const float *nx, const float *nw, float eps, const ActQuant &aq);
 hipError_t mmvq_tokens(MMVQSeg *segs, int n_seg, int K, int T, int epi, const ActQuant &aq, hipStream_t st, const Fuse &fz = Fuse(), MMVQTrace *trace = nullptr);
+// Which MFMA launch the K-quant (and planes-only) tensors of a prompt batch or a batched decode step take: the order of predicates that Context::linear
+// (PM_ROLE_ONE), Context::linear_multi (PM_ROLE_MULTI) and the dense gate | up block (PM_ROLE_GATE_UP, ws = {gate, up}) test, stated once and shared with the
+// per-op test entry (c_api.cc mi355_op_prompt_mul_mat).  PM_NONE: none of them - the caller goes on to its other paths.
+enum { PM_NONE = 0, PM_KSPLIT = 1, PM_PLANES = 2, PM_FLY = 3 };
+enum { PM_ROLE_ONE = 0, PM_ROLE_MULTI = 1, PM_ROLE_GATE_UP = 2 };
+struct PromptMatmul {
+    int form = PM_NONE;        // PM_ROLE_MULTI + PM_PLANES: of the fused launch; every other tensor takes its plane set, or the expansion on the fly without one
+    int n_fused = 0;           // tensors in the launch (PM_ROLE_MULTI + PM_PLANES: 0 where no two plane sets are adjacent - every tensor on its own)
+    bool swiglu = false;       // SwiGLU in the launch's epilogue
+    bool planes_only = false;  // a planes-only type (Q2_K, Q3_K, IQ4_XS, ternary): the launch wants Q8_K rows
+    bool need_prep = false;    // the launch reads the bh / bl block-sum planes (launch_mmq_prep, or a producer that wrote them)
+};
+PromptMatmul prompt_mul_mat_choice(int role, const DevTensor *const *ws, int n, int K, int T, MMQWorkspace wsp);
 // the process's sticky error word installed in the device globals of the current device (what Context::init does); nullptr where it could not be allocated
 unsigned *install_stream_error_word();
 

@@ -328,6 +328,31 @@ MI355_API int mi355_op_mul_mat_fused(int32_t type, const void *W, int64_t N, int
 MI355_API int mi355_op_mat_vec_step(int32_t n_seg, const int32_t *types, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, int32_t epi,
                                     const float *resid, int32_t fuse, const float *norm_w, float eps, int32_t want_host_copy, int32_t n_sel, int32_t n_expert,
                                     const int32_t *expert_ids, int64_t ld_pad, float *const *y, float *y_host, int32_t *path);
+/* Test hook: one mat-mul launch of a dense prompt batch (or of a batched decode step) as the model issues it: mmq.hip's K-split, plane and LDS-plane kernels.
+ *   n_seg 1..3 weight tensors W[s] (ggml rows of type types[s]: Q4_K, Q5_K, Q6_K; one tensor on the plane kernels also Q2_K, Q3_K, IQ4_XS; N[s] rows of K,
+ *   K % 256 == 0) over one activation of 3 <= T <= 600 rows;
+ *   epi 0: y[s][t][n] = W[s][n] . a[t];  1 (one tensor): resid + that, resid [T][N[0] + ld_pad], and with in_place the residual buffer IS the out buffer, as
+ *   attn_output and ffn_down run;  2 (two tensors of one type and N: ffn_gate | ffn_up): y[0] = silu(y0) * y1, y[1] is not written (may be NULL);
+ *   prologue 0: a = launch_quantize(x), then launch_mmq_prep;  1: launch_rmsnorm_quant(x, norm_w, eps) writing the bh / bl block-sum planes itself;
+ *   2: launch_swiglu_quant(g, u) likewise, x = g [T][K] then u [T][K];  3: launch_quantize writing bh / bl.  x is [T][K] otherwise;
+ *   form 0: the launch the model chooses (host/runtime.cc prompt_mul_mat_choice; every tensor has its plane set, adjacent in one arena);  1: the K-split kernel
+ *   (launch_mmq_ksplit_multi; epi 2: its SwiGLU pair);  2: the plane sets, expanded into one arena (launch_mmq_planes_multi with seg_types, the K-split
+ *   workspace and the residual; epi 2: launch_mmq_planes_swiglu);  3: the expansion on the fly (launch_mmq, one tensor).  mi355_debug_set_option "mmq_tiles"
+ *   1 / 2 / 4 and "mmq_split" pick the tile form and the K split as everywhere.
+ * Every y[s] is a whole out buffer [T][N[s] + ld_pad], 0xFF bytes before the launch except where in_place put the residual there: an unwritten result reads as
+ * NaN, a write past N[s] shows in the pad columns.  MI355_ERR_ARG where the arguments or the chosen launcher's row rules refuse the launch: nothing is launched
+ * and the buffers come back as 0xFF bytes.  path[8]: [0] the kernel (1 K-split, 2 planes 256 x 32, 3 planes 128 x 128, 4 the 128 x 256 LDS kernel, 5 on the
+ * fly), [1] 32-token tiles per workgroup of the K-split kernel (else 0), [2] the K split (n_split), [3] mixed plane formats, [4] SwiGLU epilogue, [5] whether
+ * launch_mmq_prep was issued, [6], [7] zero.  (form 0 with tensors whose plane sets do not all fuse: path describes the fused launch, the others follow alone.) */
+MI355_API int mi355_op_prompt_mul_mat(int32_t n_seg, const int32_t *types, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, int32_t epi,
+                                      const float *resid, int32_t in_place, int32_t prologue, const float *norm_w, float eps, int32_t form, int64_t ld_pad,
+                                      float *const *y, int32_t *path);
+/* Test hook: one producer of the quantised activation of the MFMA kernels, called with Q8_K and the bh / bl block-sum planes (bsum = 64 * bh + bl) as the model
+ * calls it: producer 0 launch_quantize(x);  1 launch_rmsnorm_quant(x, norm_w, eps);  2 launch_swiglu_quant(x, x2).  x (and x2) [T][n], n % 256 == 0.
+ * out_blocks: T rows of n / 256 ggml block_q8_K;  out_bh / out_bl: [T][n / 16] int8 each, 0xFF bytes before the launch;  prep_bh / prep_bl: what launch_mmq_prep
+ * makes of the same rows;  y_f32 (producer 1, may be NULL): the f32 rows the blocks were made from. */
+MI355_API int mi355_op_act_q8k_planes(int32_t producer, const float *x, const float *x2, const float *norm_w, float eps, int64_t n, int64_t T, void *out_blocks,
+                                      int8_t *out_bh, int8_t *out_bl, int8_t *prep_bh, int8_t *prep_bl, float *y_f32);
 /* ggml's f32 -> bf16 rounding as the bf16 kernels' activation pass does it (nearest, ties to even; NaN quieted; subnormals kept); n % 8 == 0 */
 MI355_API int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out);
 /* Up to three BF16 tensors W[s] ([N[s]][K] bf16 rows, K % 8 == 0; the matrix cores want K % 16 == 0) against the same T rows of x, as a decoder layer launches them:
@@ -494,6 +519,13 @@ MI355_API int mi355_op_attn_batch_step(const float *q, const float *k_new, const
                                        int32_t type_k, void *k_cache, int32_t type_v, void *v_cache, int32_t n_cells, int32_t n_kv, const int32_t *cell_pos,
                                        const uint64_t *cell_seq, const int32_t *tok_pos, const int32_t *tok_seq, const int32_t *tok_cell, float rope_base,
                                        int32_t n_rot, int32_t neox, float scale, int32_t mode, float *att_out, void *q8k_out);
+/* The same step, which mi355_op_attn_batch_step forwards to, with the merge also writing the block sums of its Q8_K rows as the bh / bl planes of the MFMA
+ * kernels, as the model has it do for a K-quant attn_output: bh_out / bl_out (both or neither; they need q8k_out) [T][n_head * head_dim / 16] int8 each,
+ * 0xFF bytes before the launch. */
+MI355_API int mi355_op_attn_batch_step_planes(const float *q, const float *k_new, const float *v_new, int64_t T, int32_t n_head, int32_t n_head_kv, int32_t head_dim,
+                                              int32_t type_k, void *k_cache, int32_t type_v, void *v_cache, int32_t n_cells, int32_t n_kv, const int32_t *cell_pos,
+                                              const uint64_t *cell_seq, const int32_t *tok_pos, const int32_t *tok_seq, const int32_t *tok_cell, float rope_base,
+                                              int32_t n_rot, int32_t neox, float scale, int32_t mode, float *att_out, void *q8k_out, int8_t *bh_out, int8_t *bl_out);
 /* The K-shift of llama_kv_cache_seq_add on its own (test entry): every row of k_cache (layout as above) whose delta[cell] != 0 is dequantised, rotated by
  * delta[cell] positions and quantised again, in one launch; rows with delta 0 are not touched.  The YaRN parameters as mi355_op_rope_yarn takes them. */
 MI355_API int mi355_op_k_shift(int32_t type_k, int32_t n_head_kv, int32_t head_dim, int32_t n_rot, int32_t neox, int32_t n_cells, const int32_t *delta,

@@ -83,6 +83,20 @@ def test_no_cpu_fallback(pkg):
     wp, yp = (C.c_void_p * 1)(w.ctypes.data), (C.c_void_p * 1)(y.ctypes.data)
     assert lib.mi355_op_mat_vec_step(1, t8.ctypes.data, wp, n1.ctypes.data, 256, x.ctypes.data, 1, 0, None, 0, None, 0.0, 0, 0, 1, None, 0, yp, None,
                                      path.ctypes.data) == -100
+    # the prompt batch's mat-mul launch: one Q4_K row of 256 (a block of 144 bytes) over three tokens; the producers of its activation; the batched
+    # attention step with the merge's block-sum planes
+    t12 = np.full(1, 12, np.int32)
+    x3 = np.zeros(3 * 256, np.float32)
+    y3 = np.zeros(3, np.float32)
+    wp, yp = (C.c_void_p * 1)(wq.ctypes.data), (C.c_void_p * 1)(y3.ctypes.data)
+    for form in range(4):
+        assert lib.mi355_op_prompt_mul_mat(1, t12.ctypes.data, wp, n1.ctypes.data, 256, x3.ctypes.data, 3, 0, None, 0, 0, None, 0.0, form, 0, yp, path.ctypes.data) == -100
+    planes = np.zeros(16, np.int8)
+    for producer in range(3):
+        assert lib.mi355_op_act_q8k_planes(producer, x.ctypes.data, x.ctypes.data, x.ctypes.data, 1e-5, 256, 1, out.ctypes.data, planes.ctypes.data,
+                                           planes.ctypes.data, planes.ctypes.data, planes.ctypes.data, None) == -100
+    assert lib.mi355_op_attn_batch_step_planes(None, None, None, 1, 8, 1, 32, 1, None, 1, None, 1, 1, None, None, None, None, None, 1e4, 32, 0, 1.0, 0, None, None,
+                                               None, None) == -100
 
 
 def test_product_does_not_touch_oracle():
