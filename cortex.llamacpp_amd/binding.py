@@ -92,6 +92,12 @@ SYMBOLS = {
     "mi355_get_token_logprobs": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "mi355_logits_kl": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "mi355_perplexity": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mi355_imatrix_begin": (_i32, [_vp, _i32]),
+    "mi355_imatrix_end": (_i32, [_vp]),
+    "mi355_imatrix_clear": (_i32, [_vp]),
+    "mi355_imatrix_n_entries": (_i32, [_vp]),
+    "mi355_imatrix_entry": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
+    "mi355_imatrix_get": (_i32, [_vp, _i32, _vp, _vp]),
     "mi355_speculative_steps": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "mi355_get_topk_ith": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "mi355_debug_mega_steps": (C.c_int64, [_vp]),
@@ -149,6 +155,7 @@ SYMBOLS = {
     "mi355_op_spec_verify": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "mi355_op_token_logprob_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
     "mi355_op_logits_kl_rows": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "mi355_op_imatrix_accum": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
     "mi355_op_topk_rows": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_moe_group": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_moe_gather_act": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -576,6 +583,26 @@ class Backend:
         self._chk(self.lib.mi355_op_logits_kl_rows(_ptr(p), p.shape[0], _ptr(q), q.shape[0], p.shape[1], None if rows_p is None else _ptr(rows_p),
                                                    None if rows_q is None else _ptr(rows_q), R, _ptr(kl), _ptr(top)), "op_logits_kl_rows")
         return kl, top
+
+    def imatrix_accum(self, x: np.ndarray, sum2: np.ndarray, counts: np.ndarray, x2=None, K=None, R=None, row_src=None, counts_per_mat=None):
+        """The importance-matrix collector launch (mi355_op_imatrix_accum) on rows x [n_src_rows][ld] (x2: the SwiGLU producer's second operand): returns
+        (sum2 [n_mat + 1][K], counts [n_mat]) = the running totals given plus this launch; the last row of sum2 is a guard row.  K defaults to ld, R to the
+        rows of row_src or of x; counts_per_mat [n_mat] cuts the launch rows into one run per matrix (None: one matrix).  The inputs are not modified."""
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.ndim == 2
+        x2 = None if x2 is None else np.ascontiguousarray(x2, np.float32)
+        assert x2 is None or x2.shape == x.shape
+        row_src = None if row_src is None else np.ascontiguousarray(row_src, np.int32).reshape(-1)
+        cpm = None if counts_per_mat is None else np.ascontiguousarray(counts_per_mat, np.int32).reshape(-1)
+        ld = x.shape[1]
+        K = ld if K is None else int(K)
+        R = int(R) if R is not None else (row_src.size if row_src is not None else x.shape[0])
+        out = np.array(sum2, np.float32, copy=True, order="C")
+        cnt = np.array(counts, np.int32, copy=True, order="C").reshape(-1)
+        n_mat = cnt.size
+        assert out.shape == (n_mat + 1, K) and (cpm is None or cpm.size == n_mat) and (row_src is None or row_src.size >= R)
+        self._chk(self.lib.mi355_op_imatrix_accum(_ptr(x), _ptr(x2), ld, K, R, _ptr(row_src), x.shape[0], _ptr(cpm), n_mat, _ptr(out), _ptr(cnt)), "op_imatrix_accum")
+        return out, cnt
 
     @staticmethod
     def topk_decode(keys: np.ndarray):
@@ -1275,6 +1302,36 @@ class Context:
             if base is not None:
                 out["ppl_base"] = float(np.exp(st.nll_base / st.count))
                 out["mean_kl"] = st.kl / st.count
+        return out
+
+    def imatrix_begin(self, process_output: bool = False) -> None:
+        """Start collecting the importance matrix on every decode of this context (mi355_imatrix_begin)."""
+        if self.lib.mi355_imatrix_begin(self.h, int(bool(process_output))) != 0:
+            raise MI355Error(f"mi355_imatrix_begin failed: {_err(self.lib)}")
+
+    def imatrix_end(self) -> None:
+        """Stop collecting and free the accumulators; the steps are again what they were before imatrix_begin."""
+        if self.lib.mi355_imatrix_end(self.h) != 0:
+            raise MI355Error(f"mi355_imatrix_end failed: {_err(self.lib)}")
+
+    def imatrix_clear(self) -> None:
+        """Zero the sums and counts; collection stays on."""
+        if self.lib.mi355_imatrix_clear(self.h) != 0:
+            raise MI355Error(f"mi355_imatrix_clear failed: {_err(self.lib)}")
+
+    def imatrix_entries(self) -> dict:
+        """{tensor name: (sum2 f32 [n_mat][ne0], counts int32 [n_mat])} of everything collected since imatrix_begin / imatrix_clear, in layer order."""
+        out = {}
+        buf = C.create_string_buffer(256)
+        for i in range(int(self.lib.mi355_imatrix_n_entries(self.h))):
+            ne0, n_mat = C.c_int32(0), C.c_int32(0)
+            if self.lib.mi355_imatrix_entry(self.h, i, C.cast(buf, C.c_void_p), 256, C.cast(C.byref(ne0), C.c_void_p), C.cast(C.byref(n_mat), C.c_void_p)) < 0:
+                raise MI355Error(f"mi355_imatrix_entry failed: {_err(self.lib)}")
+            sum2 = np.zeros((n_mat.value, ne0.value), np.float32)
+            counts = np.zeros(n_mat.value, np.int32)
+            if self.lib.mi355_imatrix_get(self.h, i, _ptr(sum2), _ptr(counts)) != 0:
+                raise MI355Error(f"mi355_imatrix_get failed: {_err(self.lib)}")
+            out[buf.value.decode()] = (sum2, counts)
         return out
 
     def speculative_steps(self, draft_ctx: "Context", first: int, pos0: int, n: int, n_max: int = 16, n_min: int = 0, p_min: float = 0.75, seq: int = 0):

@@ -20,7 +20,7 @@ EXPERIMENTS = os.environ.get("MI355_BUILD_EXPERIMENTS", "0") == "1"
 
 def sources(experiments: bool) -> list:
     return [
-        "csrc/mmvq.hip", "csrc/mmvq_fast.hip", "csrc/mmvq_stream.hip", "csrc/mmq.hip", "csrc/mmq_q80.hip", "csrc/act.hip", "csrc/misc.hip", "csrc/spec.hip", "csrc/logprob.hip", "csrc/mmf.hip", "csrc/mmf_bf16.hip", "csrc/mmv_bf16.hip", "csrc/attn.hip", "csrc/attn_out.hip", "csrc/attn_prefill.hip", "csrc/clip.hip", "csrc/lora.hip", "csrc/kv_state.hip",
+        "csrc/mmvq.hip", "csrc/mmvq_fast.hip", "csrc/mmvq_stream.hip", "csrc/mmq.hip", "csrc/mmq_q80.hip", "csrc/act.hip", "csrc/misc.hip", "csrc/spec.hip", "csrc/logprob.hip", "csrc/imatrix.hip", "csrc/mmf.hip", "csrc/mmf_bf16.hip", "csrc/mmv_bf16.hip", "csrc/attn.hip", "csrc/attn_out.hip", "csrc/attn_prefill.hip", "csrc/clip.hip", "csrc/lora.hip", "csrc/kv_state.hip",
     ] + (["csrc/decode_engine.hip", "csrc/decode_mega.hip"] if experiments else ["csrc/experiments_absent.cc"]) + [
         "host/gguf.cc", "host/model_plan.cc", "host/lora.cc", "host/runtime.cc", "host/tp_comm.cc", "host/vocab.cc", "host/sampling.cc", "host/grammar.cc", "host/json_schema.cc", "host/log.cc", "host/server_context.cc", "host/engine.cc",
         "host/hip_backend.cc", "host/tp_split.cc", "host/clip.cc", "host/image_decode.cc", "csrc/c_api.cc",

@@ -233,8 +233,7 @@ __global__ __launch_bounds__(256) void swiglu_quant_kernel(const float *__restri
         const bool ok = !TAIL || e0 < n;
         float4 a = float4{0.0f, 0.0f, 0.0f, 0.0f}, c = a;   // (silu(0) * 0 = 0: a lane without data carries zeros)
         if (ok) { a = *reinterpret_cast<const float4 *>(g + (size_t)row * n + e0); c = *reinterpret_cast<const float4 *>(u + (size_t)row * n + e0); }
-        const float vv[4] = {(a.x / (1.0f + expf(-a.x))) * c.x, (a.y / (1.0f + expf(-a.y))) * c.y, (a.z / (1.0f + expf(-a.z))) * c.z,
-                             (a.w / (1.0f + expf(-a.w))) * c.w};
+        const float vv[4] = {swiglu_f32(a.x, c.x), swiglu_f32(a.y, c.y), swiglu_f32(a.z, c.z), swiglu_f32(a.w, c.w)};
         if (!TAIL && want_q8k) {
             uint32_t packed; int bs; float dq;
             wave_quant_q8k(vv, lane, packed, bs, dq);
@@ -266,10 +265,7 @@ hipError_t launch_swiglu_quant(const float *g, const float *u, int n, int T, con
 // ---------------------------------------------------------------- elementwise
 __global__ void swiglu_kernel(const float *g, const float *u, float *y, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const float a = g[i];
-        y[i] = (a / (1.0f + expf(-a))) * u[i];
-    }
+    if (i < n) y[i] = swiglu_f32(g[i], u[i]);
 }
 hipError_t launch_swiglu(const float *g, const float *u, float *y, int64_t n, hipStream_t st) {
     hipLaunchKernelGGL(swiglu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, u, y, n);

@@ -286,6 +286,48 @@ int32_t mi355_logits_kl(mi355_context *ctx, mi355_context *ctx_base, int32_t n, 
         return r;
     )
 }
+// ---- importance matrix (Context::imatrix_*)
+int32_t mi355_imatrix_begin(mi355_context *ctx, int32_t process_output) {
+    if (!ctx) return no_context("imatrix_begin");
+    MI355_GUARD(return MI355_ERR_ARG,
+        if (ctx->c->imatrix_begin(process_output != 0) != 0) { fail(ctx->c->last_error.empty() ? "imatrix_begin failed" : ctx->c->last_error); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
+int32_t mi355_imatrix_end(mi355_context *ctx) {
+    if (!ctx) return no_context("imatrix_end");
+    MI355_GUARD(return MI355_ERR_ARG,
+        if (ctx->c->imatrix_end() != 0) { fail(ctx->c->last_error); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
+int32_t mi355_imatrix_clear(mi355_context *ctx) {
+    if (!ctx) return no_context("imatrix_clear");
+    MI355_GUARD(return MI355_ERR_ARG,
+        if (ctx->c->imatrix_clear() != 0) { fail(ctx->c->last_error); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
+int32_t mi355_imatrix_n_entries(const mi355_context *ctx) { return ctx ? ctx->c->imatrix_n_entries() : 0; }
+int32_t mi355_imatrix_entry(const mi355_context *ctx, int32_t i, char *name_buf, int32_t cap, int32_t *ne0, int32_t *n_mat) {
+    if (!ctx) return no_context("imatrix_entry");
+    MI355_GUARD(return MI355_ERR_ARG,
+        std::string name;
+        int k = 0, m = 0;
+        if (!ctx->c->imatrix_entry(i, name, k, m)) { fail("imatrix_entry: no entry " + std::to_string(i)); return MI355_ERR_ARG; }
+        if (name_buf && cap > 0) { snprintf(name_buf, (size_t)cap, "%s", name.c_str()); }
+        if (ne0) *ne0 = k;
+        if (n_mat) *n_mat = m;
+        return (int32_t)name.size();
+    )
+}
+int32_t mi355_imatrix_get(mi355_context *ctx, int32_t i, float *sum2, int32_t *counts) {
+    if (!ctx) return no_context("imatrix_get");
+    MI355_GUARD(return MI355_ERR_ARG,
+        if (ctx->c->imatrix_get(i, sum2, counts) != 0) { fail(ctx->c->last_error.empty() ? "imatrix_get failed" : ctx->c->last_error); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
 namespace {
 struct PplCallback { mi355_ppl_callback cb; void *user; };
 void ppl_stats_out(const Context::PplStats &s, mi355_ppl_stats *o) {
@@ -1692,6 +1734,39 @@ int mi355_op_logits_kl_rows(const float *p, int32_t n_p_rows, const float *q, in
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "logits_kl_rows");
     return dk.down(kl_out, (size_t)R * 4) && dt.down(same_top_out, (size_t)R * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_imatrix_accum(const float *x, const float *x2, int64_t ld, int64_t K, int32_t R, const int32_t *row_src, int32_t n_src_rows, const int32_t *counts_per_mat,
+                           int32_t n_mat, float *sum2_io, int32_t *count_io) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!x || !sum2_io || !count_io || K < 32 || (K & 31) || K > INT32_MAX / 2 || ld < K || (ld & 3) || ld > INT32_MAX / 2 || R < 1 || R > IMX_MAX_ROWS || n_src_rows < 1 ||
+        n_mat < 1 || n_mat > 256 || (n_mat > 1 && !counts_per_mat) || (!row_src && R > n_src_rows)) { fail("imatrix_accum: bad shape"); return MI355_ERR_ARG; }
+    for (int r = 0; row_src && r < R; r++)
+        if (row_src[r] < 0 || row_src[r] >= n_src_rows) { fail("imatrix_accum: row_src[" + std::to_string(r) + "] outside the source rows"); return MI355_ERR_ARG; }
+    // meta as launch_moe_group leaves it: counts | exclusive offsets | total
+    std::vector<int32_t> meta;
+    if (counts_per_mat) {
+        meta.assign((size_t)2 * n_mat + 1, 0);
+        int64_t run = 0;
+        for (int m = 0; m < n_mat; m++) {
+            if (counts_per_mat[m] < 0) { fail("imatrix_accum: negative count"); return MI355_ERR_ARG; }
+            meta[(size_t)m] = counts_per_mat[m]; meta[(size_t)n_mat + m] = (int32_t)std::min<int64_t>(run, R);
+            run += counts_per_mat[m];
+        }
+        if (run != R) { fail("imatrix_accum: the counts do not add up to R"); return MI355_ERR_ARG; }
+        meta[(size_t)2 * n_mat] = R;
+    }
+    const size_t nx = (size_t)n_src_rows * (size_t)ld * 4, ns = (size_t)(n_mat + 1) * (size_t)K * 4;
+    const size_t slab_floats = imatrix_scratch_floats((int)K, R, n_mat);
+    DevBuf dx(nx), dx2(x2 ? nx : 16), dr((size_t)R * 4), dm(meta.empty() ? 16 : meta.size() * 4), dsum(ns), dcnt((size_t)n_mat * 4), dslab(slab_floats * 4);
+    if (!dx.up(x, nx) || (x2 && !dx2.up(x2, nx)) || (row_src && !dr.up(row_src, (size_t)R * 4)) || (!meta.empty() && !dm.up(meta.data(), meta.size() * 4)) ||
+        !dsum.up(sum2_io, ns) || !dcnt.up(count_io, (size_t)n_mat * 4) || !dx2.p || !dr.p || !dm.p || !dslab.p) return MI355_ERR_OOM;
+    hipError_t e = launch_imatrix_accum(dx.as<float>(), x2 ? dx2.as<float>() : nullptr, (int)ld, (int)K, R, row_src ? dr.as<int32_t>() : nullptr,
+                                        meta.empty() ? nullptr : dm.as<int32_t>(), n_mat, dsum.as<float>(), dcnt.as<int32_t>(), dslab.as<float>(), slab_floats, nullptr);
+    if (e == hipErrorInvalidValue) { fail("imatrix_accum: the launcher refuses this shape"); return MI355_ERR_ARG; }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "imatrix_accum");
+    return dsum.down(sum2_io, ns) && dcnt.down(count_io, (size_t)n_mat * 4) ? MI355_OK : MI355_ERR_HIP;
 }
 
 int mi355_op_topk_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t n_rows, int32_t k, const int32_t *adj_n,

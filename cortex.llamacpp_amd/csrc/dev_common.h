@@ -61,6 +61,9 @@ template <bool COH> __device__ __forceinline__ void cst2(void *p, unsigned short
 // the compiler computed every phase's lane constants once at the top and kept them in scratch.
 __device__ __forceinline__ int tid_now() { int t = (int)threadIdx.x; asm volatile("" : "+v"(t)); return t; }
 
+// silu(g) * u as the SwiGLU launches of act.hip and the importance-matrix collector (imatrix.hip) compute it: one expression, the same bits in all of them
+__device__ __forceinline__ float swiglu_f32(float g, float u) { return (g / (1.0f + expf(-g))) * u; }
+
 template <int CTRL> __device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
 template <int CTRL> __device__ __forceinline__ float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
 constexpr int DPP_QP_1032 = 0xB1;    // quad_perm [1,0,3,2]

@@ -367,6 +367,21 @@ hipError_t launch_moe_gather_act(const ActQuant &src, const int32_t *tok_of, int
 // x[t][d] += sum_j y[slot_of[t*k + j]][d] * w[t][j]   (same order of operations as launch_moe_combine)
 hipError_t launch_moe_scatter_combine(float *x, const float *y, const float *w, const int32_t *slot_of, int T, int E, int k, hipStream_t st);
 
+// ---- importance-matrix collector (imatrix.hip): sum2[m][j] += sum over the rows r of matrix m of v[r][j]^2 and count[m] += rows of m, j < K.
+//   v = x[s][j], or swiglu(x[s][j], x2[s][j]) when x2 is given (launch_swiglu's values, bit for bit); s = row_src[r] (nullptr: r); rows [s][ld], ld >= K.
+//   meta == nullptr: one matrix (n_mat = 1) owns all R rows.  meta = launch_moe_group's array for n_mat experts (counts | exclusive offsets | total), read on
+//   the device: launch rows [offset[e], offset[e] + count[e]) are expert e's; an expert without rows leaves its row of sum2 and its count as they were.
+// K a multiple of 32, ld a multiple of 4, x / x2 16-byte aligned, 1 <= R <= IMX_MAX_ROWS, 1 <= n_mat <= 256; anything else: hipErrorInvalidValue, nothing launched.
+// No atomics: fixed row slices into f32 slabs, then the slabs in slice order onto the running total (two launches); the same bits run to run.
+// slabs: slab_floats floats, 16-byte aligned; contents do not matter.  imatrix_scratch_floats(K, R, n_mat) holds every launch of this K and n_mat with at most R
+// rows (the slab count is not monotone in the rows); a launch whose slabs do not fit in slab_floats: hipErrorInvalidValue, nothing launched.
+constexpr int IMX_MAX_ROWS = 60 * 1024;      // (launch_moe_group's limit on T * k)
+int imatrix_slice_rows(int R);
+size_t imatrix_scratch_floats(int K, int R, int n_mat);
+bool imatrix_accum_ok(const float *x, const float *x2, int ld, int K, int R, const int32_t *meta, int n_mat);
+hipError_t launch_imatrix_accum(const float *x, const float *x2, int ld, int K, int R, const int32_t *row_src, const int32_t *meta, int n_mat, float *sum2,
+                                int32_t *count, float *slabs, size_t slab_floats, hipStream_t st);
+
 // ---------------------------------------------------------------- attention side (attn.hip)
 // words between two merge-ticket counters / hand-over flags of the decode attention kernels (attn_decode_dev.h, attn_out.hip): one 128-byte line each
 constexpr int ATT_SYNC_STRIDE = 32;

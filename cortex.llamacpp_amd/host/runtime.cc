@@ -578,6 +578,130 @@ hipError_t Context::lora_add(int layer, const int *targets, float *const *outs, 
     return hipSuccess;
 }
 
+// ---- importance-matrix collection (runtime.h).  begin lays out one device block: every accumulator's f32 [n_mat][K] rows, then every
+// int32 [n_mat] count, then a slab scratch that holds any launch of up to a micro-batch's rows (imatrix_scratch_floats: the largest batch does not need the most slabs).
+int Context::imatrix_begin(bool process_output) {
+    const HParams &hp = model->hp;
+    if (imx_on_) { last_error = "imatrix_begin: collection is already on (imatrix_end first)"; return -1; }
+    if (hp.encoder) { last_error = "imatrix_begin: an encoder model is not collected (its blocks have no route that keeps the f32 rows)"; return -1; }
+    if (hp.tp_size > 1) { last_error = "imatrix_begin: not on a rank of a row split (a rank sees a slice of every contraction)"; return -1; }
+    const bool moe = hp.n_expert > 0;
+    const int E = hp.n_embd, FF = hp.n_ff, NE = hp.n_expert, T = (int)cp.n_ubatch, GR = T * std::max(1, hp.n_expert_used);
+    if (moe) {
+        const LayerWeights &L0 = model->layers[0];
+        if (!aq_eg_.qs || !moe_meta_ || !moe_tok_) { last_error = "imatrix_begin: this context has no grouped-expert buffers (n_ubatch < 8): the per-expert rows exist only on the grouped route"; return -1; }
+        if (!(type_is_quant(L0.gate_exps.type) && type_is_quant(L0.up_exps.type) && type_is_quant(L0.down_exps.type))) { last_error = "imatrix_begin: float expert tensors never take the grouped route the collector reads"; return -1; }
+        if (NE > 256 || GR > IMX_MAX_ROWS) { last_error = "imatrix_begin: more experts or grouped rows than the collector takes"; return -1; }
+    }
+    if (hipSetDevice(model->device) != hipSuccess) { last_error = "imatrix_begin: cannot select the device"; return -1; }
+    std::vector<ImxAcc> acc((size_t)hp.n_layer * IMX_SLOTS + 1);
+    std::vector<ImxName> names;
+    size_t slab_floats = 0;
+    bool widths_ok = true;
+    auto site = [&](int idx, int K, int n_mat, int rows, std::initializer_list<const DevTensor *> ws) {
+        acc[(size_t)idx].K = K; acc[(size_t)idx].n_mat = n_mat;
+        if (K < 32 || (K & 31)) widths_ok = false;
+        slab_floats = std::max(slab_floats, imatrix_scratch_floats(K, rows, n_mat));
+        for (const DevTensor *w : ws) names.push_back({w->name, idx});
+    };
+    for (int il = 0; il < hp.n_layer; il++) {
+        const LayerWeights &L = model->layers[(size_t)il];
+        const int b = il * IMX_SLOTS;
+        site(b + IMX_QKV, E, 1, T, {&L.wq, &L.wk, &L.wv});
+        site(b + IMX_O, (int)L.wo.K, 1, T, {&L.wo});
+        if (moe) {
+            site(b + IMX_ROUTER, E, 1, T, {&L.gate_inp});
+            site(b + IMX_FFN_IN, E, NE, GR, {&L.gate_exps, &L.up_exps});
+            site(b + IMX_FFN_DOWN, FF, NE, GR, {&L.down_exps});
+        } else {
+            site(b + IMX_FFN_IN, E, 1, T, {&L.gate, &L.up});
+            site(b + IMX_FFN_DOWN, FF, 1, T, {&L.down});
+        }
+    }
+    if (process_output) site(hp.n_layer * IMX_SLOTS, E, 1, T, {!model->output.name.empty() ? &model->output : &model->tok_embd});
+    if (!widths_ok) { last_error = "imatrix_begin: a projection's row length is no multiple of 32"; return -1; }
+    size_t sum_floats = 0, n_counts = 0;
+    for (const ImxAcc &a : acc) { sum_floats += (size_t)a.K * a.n_mat; n_counts += (size_t)a.n_mat; }
+    const size_t acc_bytes = (sum_floats * 4 + n_counts * 4 + 255) & ~(size_t)255;
+    (void)hipStreamSynchronize(stream_);
+    if (holds_fused_) fused_release();
+    for (auto &ge : graphs_) (void)hipGraphExecDestroy(ge.second);     // (as a change of the adapter set does: no captured step outlives a change of routes)
+    graphs_.clear();
+    graph_exec_ = nullptr;
+    const uint64_t before = device_bytes;
+    imx_block_ = (uint8_t *)dalloc(acc_bytes + slab_floats * 4);       // (zero-filled)
+    if (!imx_block_) { last_error = "imatrix_begin: out of device memory for the accumulators"; return -1; }
+    (void)hipDeviceSynchronize();                                      // the null-stream zero-fill (see init)
+    imx_block_bytes_ = (size_t)(device_bytes - before);
+    imx_acc_bytes_ = acc_bytes;
+    float *fp = reinterpret_cast<float *>(imx_block_);
+    int32_t *ip = reinterpret_cast<int32_t *>(imx_block_ + sum_floats * 4);
+    for (ImxAcc &a : acc) {
+        if (a.K == 0) continue;
+        a.sum2 = fp; fp += (size_t)a.K * a.n_mat;
+        a.count = ip; ip += a.n_mat;
+    }
+    imx_slabs_ = reinterpret_cast<float *>(imx_block_ + acc_bytes);
+    imx_slab_floats_ = slab_floats;
+    imx_acc_ = std::move(acc);
+    imx_names_ = std::move(names);
+    imx_output_ = process_output;
+    imx_on_ = true;
+    return 0;
+}
+
+int Context::imatrix_end() {
+    if (!imx_on_) { last_error = "imatrix_end: collection is not on"; return -1; }
+    (void)hipSetDevice(model->device);
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(imx_block_);
+    allocs_.erase(std::find(allocs_.begin(), allocs_.end(), (void *)imx_block_));
+    device_bytes -= imx_block_bytes_;
+    imx_block_ = nullptr; imx_slabs_ = nullptr; imx_block_bytes_ = imx_acc_bytes_ = imx_slab_floats_ = 0;
+    imx_acc_.clear(); imx_names_.clear();
+    imx_on_ = imx_output_ = false;
+    return 0;
+}
+
+int Context::imatrix_clear() {
+    if (!imx_on_) { last_error = "imatrix_clear: collection is not on"; return -1; }
+    if (hipSetDevice(model->device) != hipSuccess || hipMemsetAsync(imx_block_, 0, imx_acc_bytes_, stream_) != hipSuccess ||
+        hipStreamSynchronize(stream_) != hipSuccess) { last_error = "imatrix_clear: zero-fill failed"; return -1; }
+    return 0;
+}
+
+bool Context::imatrix_entry(int i, std::string &name, int &ne0, int &n_mat) const {
+    if (i < 0 || i >= (int)imx_names_.size()) return false;
+    const ImxAcc &a = imx_acc_[(size_t)imx_names_[(size_t)i].acc];
+    name = imx_names_[(size_t)i].name; ne0 = a.K; n_mat = a.n_mat;
+    return true;
+}
+
+int Context::imatrix_get(int i, float *sum2, int32_t *counts) {
+    if (!imx_on_ || i < 0 || i >= (int)imx_names_.size() || !sum2 || !counts) { last_error = "imatrix_get: collection is not on, or no such entry"; return -1; }
+    const ImxAcc &a = imx_acc_[(size_t)imx_names_[(size_t)i].acc];
+    const size_t n = (size_t)a.K * a.n_mat;
+    if (hipSetDevice(model->device) != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
+    if (hipMemcpy(sum2, a.sum2, n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(counts, a.count, (size_t)a.n_mat * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+        last_error = "imatrix_get: copy failed"; return -1;
+    }
+    for (size_t j = 0; j < n; j++)
+        if (!(sum2[j] >= 0.0f && sum2[j] < INFINITY)) {      // (llama-imatrix aborts on it: the file would poison a quantisation)
+            last_error = "imatrix_get: non-finite sum in " + imx_names_[(size_t)i].name + " (matrix " + std::to_string(j / (size_t)a.K) + ", column " + std::to_string(j % (size_t)a.K) + ")";
+            return -1;
+        }
+    return 0;
+}
+
+hipError_t Context::imx_collect(int il, int slot, const float *x, const float *x2, int K, int R, const int32_t *row_src, const int32_t *meta) {
+    const ImxAcc &a = imx_acc_[il < 0 ? (size_t)model->hp.n_layer * IMX_SLOTS : (size_t)il * IMX_SLOTS + (size_t)slot];
+    if (a.K != K || !a.sum2) return hipErrorInvalidValue;
+    prof_mark("rows");                                // (the launches since the last mark produced the rows: their time is not the collector's)
+    HIP_TRY(launch_imatrix_accum(x, x2, K, K, R, row_src, meta, a.n_mat, a.sum2, a.count, imx_slabs_, imx_slab_floats_, stream_));
+    prof_mark(x2 ? "imatrix_glu" : "imatrix");       // (the producer form has a role of its own: it tells which grouped-expert form fed ffn_down_exps)
+    return hipSuccess;
+}
+
 void Context::kv_clear() {
     for (auto &c : cells_) c = KVCell();
     head_ = 0;
@@ -1493,7 +1617,7 @@ Context::AttnPlan Context::plan_attn(int il, const Step &st) const {
     p.qkv_float = !type_is_quant(L.wq.type) || !type_is_quant(L.wk.type) || !type_is_quant(L.wv.type);
     // an adapter on attn_q / attn_k / attn_v: the norm runs as a launch of its own and leaves its f32 rows in xn_ for the deltas; one on attn_output: the
     // projection runs as a launch of its own behind the attention, which leaves its f32 rows in att_
-    p.qkv_lora = lora_on(il, LORA_Q) || lora_on(il, LORA_K) || lora_on(il, LORA_V);
+    p.qkv_lora = f32_rows(il, LORA_Q) || f32_rows(il, LORA_K) || f32_rows(il, LORA_V);     // (or the importance-matrix collector reads them)
     p.qkv_prologue = !p.qkv_float && can_fuse(E, T) && !p.qkv_lora;
     AttnArgs &aa = p.aa;
     aa = attn_args(il, T, st.n_kv_max, d_pos_);
@@ -1517,7 +1641,7 @@ Context::AttnPlan Context::plan_attn(int il, const Step &st) const {
     p.ao_seg = make_seg(L.wo, st.out, E, st.resid, nullptr);
     p.ao_epi = st.resid ? EPI_ADD : EPI_STORE;
     p.af = aa;
-    if (p.decode_attn && p.fused_step && st.attn_mode == 2 && !st.engine && il < 255 && !attn_out_off_ && !attn_out_skip_step_ && !(st.tp && tp_uses_host()) && !lora_on(il, LORA_O)) {
+    if (p.decode_attn && p.fused_step && st.attn_mode == 2 && !st.engine && il < 255 && !attn_out_off_ && !attn_out_skip_step_ && !(st.tp && tp_uses_host()) && !f32_rows(il, LORA_O)) {
         p.af.splits = attn_out_fused_splits(p.af);
         if (st.chunk_lists) p.af.splits = aa.splits;
         p.ao_form = attn_out_fused_applicable(p.af, p.ra, p.ao_seg, (int)L.wo.K, p.ao_epi);
@@ -1553,6 +1677,7 @@ hipError_t Context::attn_qkv(int il, const Step &st, const AttnPlan &p) {
         prep_owner_ = nullptr;
         if (pl) prep_written(aq_e_, E, T);
         prof_mark("norm_quant");
+        if (imx_on_) HIP_TRY(imx_collect(il, IMX_QKV, xn_, nullptr, E, T, nullptr, nullptr));
     }
     const DevTensor *ws[3] = {&L.wq, &L.wk, &L.wv};
     float *outs[3] = {q_, k_, v_};
@@ -1622,6 +1747,7 @@ hipError_t Context::attn_output(int il, const Step &st, const AttnPlan &p) {
     const LayerWeights &L = model->layers[(size_t)il];
     if (p.ao_form) return hipSuccess;
     HIP_TRY(linear(L.wo, aq_o_, att_, (int)L.wo.K, st.T, st.out, model->hp.n_embd, st.resid, p.ao_epi));
+    if (imx_on_) HIP_TRY(imx_collect(il, IMX_O, att_, nullptr, (int)L.wo.K, st.T, nullptr, nullptr));
     if (lora_on(il, LORA_O)) {                                   // onto the rows that already hold the residual
         const int target = LORA_O, ld = model->hp.n_embd;
         float *out = st.out;
@@ -1655,7 +1781,7 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
     const bool f0 = act_is_q80(L.gate.type) || act_is_q80(L.up.type);
     // an adapter on ffn_gate / ffn_up: both projections store their rows (the last branch below), the deltas are added from xn_, then SwiGLU; one on ffn_down:
     // ffn_ must hold silu(gate) * up in f32 - the same branch, without the quantising shortcut
-    const bool lora_gu = lora_on(il, LORA_GATE) || lora_on(il, LORA_UP), lora_any = lora_gu || lora_on(il, LORA_DOWN);
+    const bool lora_gu = f32_rows(il, LORA_GATE) || f32_rows(il, LORA_UP), lora_any = lora_gu || f32_rows(il, LORA_DOWN);      // (an adapter, or the collector)
     const bool fuse_ffn = gq && uq && L.gate.type == L.up.type && can_fuse(E, T) && !lora_any;
     Fuse fz;
     if (fuse_ffn) {
@@ -1667,6 +1793,7 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
         prep_owner_ = nullptr;
         if (pl) prep_written(aq_e_, E, T);
         prof_mark("norm_quant");
+        if (imx_on_) HIP_TRY(imx_collect(il, IMX_FFN_IN, xn_, nullptr, E, T, nullptr, nullptr));
     }
     const bool down_q = type_is_quant(L.down.type) && (FF % 32) == 0;      // SwiGLU and the quantisation for ffn_down can share a pass
     const bool ffn_mmq = (mmq_q80_applicable(L.gate.type, E, T) && mmq_q80_applicable(L.up.type, E, T)) ||
@@ -1685,9 +1812,10 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
             float *outs[2] = {ffn_, ffn_u_};
             HIP_TRY(lora_add(il, targets, outs, lds, 2, xn_, E, E, T));
         }
-        quantised = T > 1 && down_q && !lora_on(il, LORA_DOWN);
+        quantised = T > 1 && down_q && !f32_rows(il, LORA_DOWN);
         if (quantised) HIP_TRY(quantise_for_down(il, T, false, false));
         else HIP_TRY(launch_swiglu(ffn_, ffn_u_, ffn_, (int64_t)T * FF, stream_));
+        if (imx_on_) HIP_TRY(imx_collect(il, IMX_FFN_DOWN, ffn_, nullptr, FF, T, nullptr, nullptr));      // ffn_ holds silu(gate) * up in f32
     } else if (gq && uq && L.gate.type == L.up.type && !ffn_mmq) {
         MMVQSeg segs[2] = {make_seg(L.gate, ffn_, FF, nullptr, nullptr), make_seg(L.up, ffn_u_, FF, nullptr, nullptr)};
         HIP_TRY(mmvq_tokens(segs, 2, E, T, EPI_SWIGLU, aq_e_, stream_, fz));
@@ -1736,7 +1864,7 @@ hipError_t Context::ffn_down(int il, const Step &st, bool quantised, int *n_matv
     // quantise inside the down-projection's prologue (once per CU, overlapped with its first weight loads)
     // (the widths listed are the ones the register-ring and weight-stream kernels take; the generic mat-vec's fused prologue would refuse others)
     // (... and an n_ff that ends inside a 256-group: the generic mat-vec's prologue, Q8_0 activations)
-    const bool lora_down = lora_on(il, LORA_DOWN);               // ffn_ holds f32 rows: the projection quantises them in a launch of its own, the delta is added behind it
+    const bool lora_down = f32_rows(il, LORA_DOWN);              // ffn_ holds f32 rows: the projection quantises them in a launch of its own, the delta is added behind it
     const bool fuse_down = !lora_down && st.fuse_down_env && T == 1 && type_is_quant(L.down.type) &&
                            (((FF % 256) == 0 && mmvq_fast_kb_ok((FF + 2047) / 2048)) || ((FF % 256) != 0 && (FF % 32) == 0 && FF <= 8192 && act_is_q80(L.down.type)));
     if (fuse_down && !st.tp && L.down_lo.valid() && L.down_hi.valid()) {
@@ -1800,6 +1928,7 @@ hipError_t Context::moe_grouped_one_launch(int il, int T) {
     prep_owner_ = nullptr;
     const size_t ps_gu = L.gate_exps.planes_bytes / (size_t)L.gate_exps.n_expert, ps_d = L.down_exps.planes_bytes / (size_t)L.down_exps.n_expert;
     HIP_TRY(launch_mmq_planes_swiglu_moe(L.gate_exps.type, L.gate_exps.planes, L.up_exps.planes, ps_gu, NE, moe_meta_, (int)L.gate_exps.N, E, GR, aq_eg_, ffn_g_, FF, stream_));
+    if (imx_on_) HIP_TRY(imx_collect(il, IMX_FFN_DOWN, ffn_g_, nullptr, FF, GR, nullptr, moe_meta_));     // the epilogue left silu(gate) * up
     HIP_TRY(launch_quantize(ffn_g_, FF, GR, aq_ffg_, true, false, stream_));
     HIP_TRY(launch_mmq_planes_moe(L.down_exps.type, L.down_exps.planes, ps_d, NE, moe_meta_, (int)L.down_exps.N, FF, GR, aq_ffg_, y_g_, E, stream_));
     return launch_moe_scatter_combine(x_, y_g_, moe_w_, moe_slot_, T, E, KU, stream_);
@@ -1816,6 +1945,7 @@ hipError_t Context::moe_grouped_q80(int il, int T) {
     const uint8_t *w_gu[2] = {L.gate_exps.planes, L.up_exps.planes}, *w_d[1] = {L.down_exps.planes};
     float *o_gu[2] = {ffn_g_, ffn_ug_}, *o_d[1] = {y_g_};
     HIP_TRY(launch_mmq_q80_moe(L.gate_exps.type, w_gu, o_gu, 2, L.gate_exps.planes_bytes / (size_t)L.gate_exps.n_expert, NE, moe_meta_, (int)L.gate_exps.N, E, GR, aq_eg_, FF, stream_));
+    if (imx_on_) HIP_TRY(imx_collect(il, IMX_FFN_DOWN, ffn_g_, ffn_ug_, FF, GR, nullptr, moe_meta_));
     HIP_TRY(launch_swiglu_quant(ffn_g_, ffn_ug_, FF, GR, aq_ffg_, false, true, stream_, nullptr, nullptr));
     HIP_TRY(launch_mmq_q80_moe(L.down_exps.type, w_d, o_d, 1, L.down_exps.planes_bytes / (size_t)L.down_exps.n_expert, NE, moe_meta_, (int)L.down_exps.N, FF, GR, aq_ffg_, E, stream_));
     return launch_moe_scatter_combine(x_, y_g_, moe_w_, moe_slot_, T, E, KU, stream_);
@@ -1869,6 +1999,7 @@ hipError_t Context::moe_grouped_per_expert(int il, int T, bool q80_any) {
     }
     bh_over_ = bl_over_ = nullptr;
     HIP_TRY(e_exp);
+    if (imx_on_) HIP_TRY(imx_collect(il, IMX_FFN_DOWN, ffn_g_, ffn_ug_, FF, GR, nullptr, moe_meta_));
     HIP_TRY(launch_swiglu_quant(ffn_g_, ffn_ug_, FF, GR, aq_ffg_, !act_is_q80(L.down_exps.type), act_is_q80(L.down_exps.type), stream_,
                                 pl_d ? mmq_bh_ : nullptr, pl_d ? mmq_bl_ : nullptr));
     prep_owner_ = nullptr;
@@ -1944,10 +2075,12 @@ hipError_t Context::ffn_moe(int il, const Step &st) {
     }
     prof_mark("moe_route");
     const bool exps_q = type_is_quant(L.gate_exps.type) && type_is_quant(L.up_exps.type) && type_is_quant(L.down_exps.type);
-    if (exps_q && T >= g_moe_group_min && aq_eg_.qs) {
+    if (imx_on_) HIP_TRY(imx_collect(il, IMX_ROUTER, xn_, nullptr, E, T, nullptr, nullptr));
+    if (exps_q && (T >= g_moe_group_min || imx_on_) && aq_eg_.qs) {       // (the collector reads the grouped rows: grouped at every T)
         // ggml_mul_mat_id on a batch: group the (token, rank) pairs by expert, one contiguous activation batch per
         // expert (its weights are read once per batch, through the same batched kernels as the dense projections)
         HIP_TRY(launch_moe_group(moe_ids_, T, KU, hp.n_expert, moe_meta_, moe_slot_, moe_tok_, stream_));
+        if (imx_on_) HIP_TRY(imx_collect(il, IMX_FFN_IN, xn_, nullptr, E, T * KU, moe_tok_, moe_meta_));    // a grouped row's token's row, per expert
         const bool one_launch = T >= 32 && L.gate_exps.planes && L.up_exps.planes && L.down_exps.planes && L.gate_exps.type == L.up_exps.type &&
                                 L.gate_exps.N == L.up_exps.N && mmq_planes_moe_ok(L.gate_exps.type, (int)L.gate_exps.N, E) &&
                                 mmq_planes_moe_ok(L.down_exps.type, (int)L.down_exps.N, FF) && (L.gate_exps.N % 64) == 0;
@@ -1989,7 +2122,7 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
     att_splits_ = flash_attn_pick_splits(T, hp.n_head_kv, st.n_kv_max);
 
     // single-token step on a dense K-quant model: all layers in one launch (decode_mega.hip)
-    bool mega = T == 1 && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && mega_prepare();
+    bool mega = T == 1 && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && !imx_on_ && mega_prepare();
     AttnArgs ma{};
     if (mega) {
         ma = attn_args(0, 1, st.n_kv_max, d_pos_);             // (the kernel takes each layer's cache from its own descriptor)
@@ -1999,7 +2132,7 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
         mega = flash_attn_decode_fused_applicable(ma, st.ra_step);      // (more than 64 chunks: the per-launch path merges them)
     }
     // ... or one persistent launch per layer for the mat-vecs between two attention calls (decode_engine.hip)
-    st.engine = T == 1 && !mega && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && engine_prepare();
+    st.engine = T == 1 && !mega && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && !imx_on_ && engine_prepare();
     last_layers_engine_ = st.engine;
     // cos / sin table, cell metadata and the tokens' embedding rows: one launch
     HIP_TRY(launch_step_setup_embed(d_pos_, T, st.ra_step, rope_cs_, d_cell_pos_, d_cell_seq_, d_cell_, d_seqmask_, mega ? d_mega_sync_ : nullptr,
@@ -2053,18 +2186,21 @@ hipError_t Context::run_output(int n_out, int out_base) {
         return hipSuccess;
     }
     const bool oq = type_is_quant(model->output.type);
-    const bool lora_head = lora_on(-1, LORA_OUTPUT);             // the norm as a launch of its own, its f32 rows in xn_; the delta is added onto the device row
+    const bool imx_head = imx_on_ && imx_output_;
+    const bool lora_head = lora_on(-1, LORA_OUTPUT);              // the delta is added onto the device row
+    const bool head_rows = lora_head || imx_head;                 // either reads the norm's f32 rows: the norm as a launch of its own, its rows in xn_
     // a single-token step whose logits row is wanted on the host: the head's launch stores it into the pinned row itself (the row crosses PCIe under the
     // launch; a copy node behind it cost 9 - 12 us of every step, tools/host_gap.py)
     static const bool zc_env = !(getenv("MI355_LOGITS_ZERO_COPY") && getenv("MI355_LOGITS_ZERO_COPY")[0] == '0');
-    logits_on_host_ = zc_env && oq && cur_T_ == 1 && n_out == 1 && cp.logits_to_host && !hp.tp_exchange && h_logits_ != nullptr && !lora_head;
-    if (oq && can_fuse(E, n_out) && !lora_head) {
+    logits_on_host_ = zc_env && oq && cur_T_ == 1 && n_out == 1 && cp.logits_to_host && !hp.tp_exchange && h_logits_ != nullptr && !head_rows;
+    if (oq && can_fuse(E, n_out) && !head_rows) {
         pending_fuse_.mode = 1; pending_fuse_.x = xo; pending_fuse_.w = (const float *)model->out_norm.data; pending_fuse_.eps = hp.eps;
     } else {
         prep_owner_ = nullptr;
-        HIP_TRY(launch_rmsnorm_quant(xo, (const float *)model->out_norm.data, E, n_out, hp.eps, oq && !lora_head ? nullptr : xn_, &aq_e_,
+        HIP_TRY(launch_rmsnorm_quant(xo, (const float *)model->out_norm.data, E, n_out, hp.eps, oq && !head_rows ? nullptr : xn_, &aq_e_,
                                      oq && !act_is_q80(model->output.type), act_is_q80(model->output.type), stream_));
         prof_mark("norm_quant");
+        if (imx_head) HIP_TRY(imx_collect(-1, IMX_QKV, xn_, nullptr, E, n_out, nullptr, nullptr));
     }
     float *lg = d_logits_ + (size_t)out_base * V;
     const int VL = hp.n_vocab_local, P = hp.tp_size;
@@ -2180,7 +2316,7 @@ int Context::decode_ubatch(int n, const int32_t *tokens, const int32_t *pos, con
     // such a step in flight (runtime.h fused_acquire); otherwise this step takes the wait-free launches, eagerly (the captured graphs hold the fused kernel)
     attn_out_skip_step_ = n == 1 && !attn_out_off_ && !model->hp.encoder && !fused_acquire();
     if (attn_out_skip_step_) fused_skipped_steps++;
-    bool graph_ok = cp.use_graphs && n == 1 && n_out == 1 && out_base == 0 && !profile_ && !debug_taps_ && !embeddings_enabled && moe_forced_T_ == 0 && !ub_embd_ && !attn_out_skip_step_;
+    bool graph_ok = cp.use_graphs && n == 1 && n_out == 1 && out_base == 0 && !profile_ && !debug_taps_ && !embeddings_enabled && moe_forced_T_ == 0 && !ub_embd_ && !attn_out_skip_step_ && !imx_on_;
     hipError_t e = hipSuccess;
     if (graph_ok) {
         // the attention grid is sized for an upper bound of occupied cells; one captured graph per 256-cell bucket

@@ -166,6 +166,24 @@ class Context {
     };
     int perplexity(const int32_t *tokens, int64_t n_tokens, int n_chunk, int32_t bos, int seq, Context *base, float *logprob_out, float *kl_out,
                    int (*cb)(const PplStats &, void *), void *user, PplStats &out);
+    // importance matrix (csrc/imatrix.hip; what llama-imatrix records).  Between begin and end every micro-batch of every decode adds, for
+    // every weight matrix it multiplies, the per-input-column sum of squares of the f32 rows the projection consumes and the number of rows - per expert for
+    // the expert tensors.  While it is on the layer blocks take the routes that leave those rows in memory (the ones an adapter on every target forces; a
+    // mixture-of-experts feed-forward is grouped at every batch size), and the single-launch step, the layer engine and the captured graphs are not used;
+    // after end the steps are what they were.  Entries carry GGUF tensor names; tensors that share an input (attn_q / attn_k / attn_v, ffn_gate / ffn_up)
+    // share an accumulator and report the same values.  process_output: also the output head, from the final-norm rows of the flagged tokens.
+    // begin: 0, or -1 with last_error set (already on, an encoder, a rank of a row split, a width that is no multiple of 32, a mixture-of-experts context
+    // without grouped buffers or with float expert tensors, out of device memory).  The accumulators, counts and slab scratch are device memory of the
+    // context (device_bytes) from begin to end.
+    int imatrix_begin(bool process_output);
+    int imatrix_end();
+    int imatrix_clear();                       // zeroes sums and counts, keeps collecting
+    bool imatrix_on() const { return imx_on_; }
+    int imatrix_n_entries() const { return (int)imx_names_.size(); }
+    // entry i: its tensor name, row length ne0 and number of matrices (1, or n_expert); false for an index outside the list
+    bool imatrix_entry(int i, std::string &name, int &ne0, int &n_mat) const;
+    // sum2 [n_mat][ne0], counts [n_mat] of entry i: one synchronisation, then the copies.  0, or -1 with last_error set (a non-finite sum names the tensor)
+    int imatrix_get(int i, float *sum2, int32_t *counts);
     // test hook (mixture-of-experts files): the NEXT decode call (one micro-batch of T tokens) takes these experts, ids [n_layer][T][n_expert_used], instead of
     // its router's selection; the weights stay this side's probabilities of them.  One call, then routing is free again.  No graphs while it is armed.
     int force_moe_ids(const int32_t *ids, int n_layer, int T, int k);
@@ -294,6 +312,21 @@ class Context {
     bool lora_changed();
     // outs[i] (leading dimension lds[i]) += the deltas of (layer, targets[i]) from the rows x [T][ld_x], adapter by adapter in the order they were set
     hipError_t lora_add(int layer, const int *targets, float *const *outs, const int *lds, int n, const float *x, int ld_x, int K, int T);
+    // importance-matrix collection (imatrix_begin): one accumulator per (layer, site) plus the head's, in one device block with the slab scratch behind them
+    enum { IMX_QKV = 0, IMX_O = 1, IMX_FFN_IN = 2, IMX_FFN_DOWN = 3, IMX_ROUTER = 4, IMX_SLOTS = 5 };   // FFN_IN / FFN_DOWN: per expert on a mixture-of-experts file
+    struct ImxAcc { int K = 0, n_mat = 0; float *sum2 = nullptr; int32_t *count = nullptr; };
+    struct ImxName { std::string name; int acc; };
+    std::vector<ImxAcc> imx_acc_;      // [n_layer * IMX_SLOTS + 1] (the last: the head); K = 0: no such site
+    std::vector<ImxName> imx_names_;   // the entries, in layer order
+    bool imx_on_ = false, imx_output_ = false;
+    uint8_t *imx_block_ = nullptr;
+    size_t imx_block_bytes_ = 0, imx_acc_bytes_ = 0;
+    float *imx_slabs_ = nullptr;
+    size_t imx_slab_floats_ = 0;       // the scratch's capacity: launch_imatrix_accum refuses a launch that needs more
+    // "f32 rows wanted": the operand rows of (layer, target) must exist in f32 - an adapter adds its delta from them, the collector squares them
+    bool f32_rows(int layer, int target) const { return imx_on_ || lora_on(layer, target); }
+    // rows x (and x2: the SwiGLU producer) [..][K] into the accumulator of (il, slot) (il < 0: the head); R launch rows through row_src, cut by meta
+    hipError_t imx_collect(int il, int slot, const float *x, const float *x2, int K, int R, const int32_t *row_src, const int32_t *meta);
     void prof_mark(const char *name);
     void prof_begin();
     void prof_end();

@@ -199,6 +199,27 @@ typedef struct mi355_ppl_stats {
 typedef int32_t (*mi355_ppl_callback)(const mi355_ppl_stats *running, void *user);
 MI355_API int32_t mi355_perplexity(mi355_context *ctx, mi355_context *ctx_base, const mi355_token *tokens, int64_t n_tokens, int32_t n_chunk, mi355_token bos,
                                    mi355_seq_id seq, float *logprob_out, float *kl_out, mi355_ppl_callback cb, void *user, mi355_ppl_stats *stats);
+/* ---- importance matrix (what upstream's llama-imatrix records for llama-quantize --imatrix).  Between begin and end every micro-batch of
+ * every mi355_decode of this context adds, for every weight matrix it multiplies, the per-input-column sum of squares of the f32 rows the projection consumes
+ * and the number of rows (per expert for the *_exps tensors), on the device.  While it is on, the steps take the launches that leave those rows in memory
+ * (the ones an adapter on every target forces; no whole-step launch, layer engine or captured graph; a mixture-of-experts feed-forward grouped by expert at
+ * every batch size), so logits may differ from a plain run in the last digits; after end the steps are what they were before begin, bit for bit.
+ * process_output != 0 also collects the output head (output.weight, or token_embd.weight for a tied head) from the final-norm rows of the flagged tokens.
+ * begin returns MI355_OK, or MI355_ERR_ARG with the reason in mi355_last_error: collection already on, an encoder model, a rank of a row split, a
+ * mixture-of-experts context without grouped buffers (n_ubatch < 8) or with float expert tensors, a row length that is no multiple of 32, out of memory.
+ * The accumulators, counts and scratch are device memory from begin to end (counted in mi355_context_device_bytes).  clear zeroes sums and counts and keeps
+ * collecting. */
+MI355_API int32_t mi355_imatrix_begin(mi355_context *ctx, int32_t process_output);
+MI355_API int32_t mi355_imatrix_end(mi355_context *ctx);
+MI355_API int32_t mi355_imatrix_clear(mi355_context *ctx);
+/* The entries while collection is on, in layer order, named after the GGUF tensor multiplied (blk.N.attn_q.weight ...).  Tensors with one input (attn_q /
+ * attn_k / attn_v; ffn_gate / ffn_up; ffn_gate_exps / ffn_up_exps) are separate entries with the same values.  entry: the name into name_buf (cap bytes,
+ * always terminated), the row length ne0 and the number of matrices n_mat (1, or n_expert); returns the name's length, < 0 for an index outside the list. */
+MI355_API int32_t mi355_imatrix_n_entries(const mi355_context *ctx);
+MI355_API int32_t mi355_imatrix_entry(const mi355_context *ctx, int32_t i, char *name_buf, int32_t cap, int32_t *ne0, int32_t *n_mat);
+/* sum2 [n_mat][ne0] and counts [n_mat] of entry i: one synchronisation, then the copies.  A sum that is not finite returns MI355_ERR_ARG with the tensor's
+ * name in mi355_last_error (upstream aborts on it). */
+MI355_API int32_t mi355_imatrix_get(mi355_context *ctx, int32_t i, float *sum2, int32_t *counts);
 /* device-side sampling front end beyond greedy (stands in for the head of common_sampler_sample's chain, reference call site
    src/llama_server_context.cc:1679-1698): the k <= 128 best candidates of row i after logit_bias and the repetition / frequency / presence penalties,
    best first (higher logit; lower token id on ties) - k (token, logit) pairs cross to the host instead of the whole row.  adj_tok / adj_bias / adj_count:
@@ -413,6 +434,14 @@ MI355_API int mi355_op_token_logprob_rows(const float *base, int64_t n, int32_t 
 /* p [n_p_rows][n], q [n_q_rows][n]; pair r = (p row rows_p[r], q row rows_q[r]) (NULL: row r).  kl_out [R], same_top_out [R] as mi355_logits_kl gives them. */
 MI355_API int mi355_op_logits_kl_rows(const float *p, int32_t n_p_rows, const float *q, int32_t n_q_rows, int64_t n, const int32_t *rows_p, const int32_t *rows_q,
                                       int32_t R, float *kl_out, int32_t *same_top_out);
+/* The collector launch of csrc/imatrix.hip.  x (and x2, nullable) [n_src_rows][ld] f32, ld >= K, ld a multiple of 4, K a multiple of 32; launch row r < R reads
+ * source row row_src[r] (NULL: row r) and contributes v = x, or silu(x) * x2 with x2 (mi355_op_swiglu's values).  counts_per_mat [n_mat] (NULL with n_mat = 1:
+ * all rows) cuts the launch rows into consecutive runs, one per matrix, and must add up to R; the entry builds the counts | offsets | total array the model's
+ * grouping launch writes.  sum2_io [n_mat + 1][K]: row m += the column sums of squares of matrix m's rows, the last row is a guard that comes back as it went
+ * in; count_io [n_mat] += the counts.  A matrix without rows keeps its row and count.  R <= 61440, n_mat <= 256.  MI355_ERR_ARG, and nothing launched or
+ * written, for any other shape. */
+MI355_API int mi355_op_imatrix_accum(const float *x, const float *x2, int64_t ld, int64_t K, int32_t R, const int32_t *row_src, int32_t n_src_rows,
+                                     const int32_t *counts_per_mat, int32_t n_mat, float *sum2_io, int32_t *count_io);
 /* logits [n_base_rows][n]; launch row r = base row rows[r], r < R <= 1088; group g < G <= 64 owns launch rows group_start[g] .. group_start[g + 1] - 1
  * (1 .. 17 rows; group_start[0] = 0, group_start[G] = R); draft [R].  ids_out [R], n_accept_out [G] as mi355_spec_verify gives them. */
 MI355_API int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t R, const int32_t *group_start, int32_t G,
