@@ -156,6 +156,9 @@ SYMBOLS = {
     "mi355_op_token_logprob_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
     "mi355_op_logits_kl_rows": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
     "mi355_op_imatrix_accum": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "mi355_quantize_chunk": (C.c_int, [_i32, _i32, _vp, _i64, _i64, _vp, _vp]),
+    "mi355_quantize_supported": (C.c_int, [_i32]),
+    "mi355_quantize_last_times": (C.c_int, [_vp, _vp, _vp]),
     "mi355_op_topk_rows": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_moe_group": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_moe_gather_act": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -603,6 +606,31 @@ class Backend:
         assert out.shape == (n_mat + 1, K) and (cpm is None or cpm.size == n_mat) and (row_src is None or row_src.size >= R)
         self._chk(self.lib.mi355_op_imatrix_accum(_ptr(x), _ptr(x2), ld, K, R, _ptr(row_src), x.shape[0], _ptr(cpm), n_mat, _ptr(out), _ptr(cnt)), "op_imatrix_accum")
         return out, cnt
+
+    def quantize_rows(self, dst_type: int, x: np.ndarray, imatrix=None, src_type=None) -> np.ndarray:
+        """The quantiser (mi355_quantize_chunk): rows x [n_rows][n_per_row] - float32, float16, or uint16 holding bf16 bits with src_type=30 - to ggml-layout
+        blocks of dst_type, uint8 [n_rows][row bytes]; imatrix: None or n_per_row column weights.  A type or shape the entry refuses raises MI355Error."""
+        x = np.ascontiguousarray(x)
+        if src_type is None:
+            src_type = {np.dtype(np.float32): 0, np.dtype(np.float16): 1}.get(x.dtype)
+            if src_type is None:
+                x, src_type = np.ascontiguousarray(x, np.float32), 0
+        assert x.ndim == 2 and x.dtype == {0: np.float32, 1: np.float16, 30: np.uint16}.get(src_type, x.dtype)
+        n_rows, n = x.shape
+        im = None if imatrix is None else np.ascontiguousarray(imatrix, np.float32).reshape(-1)
+        assert im is None or im.size == n
+        from .gguf_synth import BLOCK_BYTES, BLOCK_ELEMS
+        be, bb = BLOCK_ELEMS.get(dst_type, 1), BLOCK_BYTES.get(dst_type, 1)
+        out = np.zeros((n_rows, n // be * bb if n % be == 0 else 1), np.uint8)
+        self._chk(self.lib.mi355_quantize_chunk(dst_type, src_type, _ptr(x), n, n_rows, _ptr(im), _ptr(out)), "quantize_chunk")
+        return out
+
+    def quantize_last_times(self):
+        """(upload, kernel, download) milliseconds of this thread's last quantize_rows (mi355_quantize_last_times)"""
+        t = np.zeros(3, np.float32)
+        p = t.ctypes.data
+        self._chk(self.lib.mi355_quantize_last_times(C.c_void_p(p), C.c_void_p(p + 4), C.c_void_p(p + 8)), "quantize_last_times")
+        return float(t[0]), float(t[1]), float(t[2])
 
     @staticmethod
     def topk_decode(keys: np.ndarray):

@@ -20,7 +20,7 @@ EXPERIMENTS = os.environ.get("MI355_BUILD_EXPERIMENTS", "0") == "1"
 
 def sources(experiments: bool) -> list:
     return [
-        "csrc/mmvq.hip", "csrc/mmvq_fast.hip", "csrc/mmvq_stream.hip", "csrc/mmq.hip", "csrc/mmq_q80.hip", "csrc/act.hip", "csrc/misc.hip", "csrc/spec.hip", "csrc/logprob.hip", "csrc/imatrix.hip", "csrc/mmf.hip", "csrc/mmf_bf16.hip", "csrc/mmv_bf16.hip", "csrc/attn.hip", "csrc/attn_out.hip", "csrc/attn_prefill.hip", "csrc/clip.hip", "csrc/lora.hip", "csrc/kv_state.hip",
+        "csrc/mmvq.hip", "csrc/mmvq_fast.hip", "csrc/mmvq_stream.hip", "csrc/mmq.hip", "csrc/mmq_q80.hip", "csrc/act.hip", "csrc/misc.hip", "csrc/spec.hip", "csrc/logprob.hip", "csrc/imatrix.hip", "csrc/quantize.hip", "csrc/mmf.hip", "csrc/mmf_bf16.hip", "csrc/mmv_bf16.hip", "csrc/attn.hip", "csrc/attn_out.hip", "csrc/attn_prefill.hip", "csrc/clip.hip", "csrc/lora.hip", "csrc/kv_state.hip",
     ] + (["csrc/decode_engine.hip", "csrc/decode_mega.hip"] if experiments else ["csrc/experiments_absent.cc"]) + [
         "host/gguf.cc", "host/model_plan.cc", "host/lora.cc", "host/runtime.cc", "host/tp_comm.cc", "host/vocab.cc", "host/sampling.cc", "host/grammar.cc", "host/json_schema.cc", "host/log.cc", "host/server_context.cc", "host/engine.cc",
         "host/hip_backend.cc", "host/tp_split.cc", "host/clip.cc", "host/image_decode.cc", "csrc/c_api.cc",
@@ -50,6 +50,9 @@ EXTRA = {
     # the generic mat-vec kernel holds every weight type's decoder and reads its argument struct in more places than the 300 up to which the compiler still
     # reads a by-value struct in place: beyond them it copies the struct to scratch first (csrc/mmvq.hip mmvq_kernel)
     "csrc/mmvq.hip": ["-mllvm", "-instcombine-max-copied-from-constant-users=2000"],
+    # the quantiser is checked bit for bit against a numpy restatement (tests/quantize_ref.py): no fused multiply-add, IEEE f32 division and square root, f32
+    # subnormals kept - stated here whatever FLAGS and the compiler's defaults say (csrc/quantize.hip)
+    "csrc/quantize.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero"],
 }
 
 

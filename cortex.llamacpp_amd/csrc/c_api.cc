@@ -5,6 +5,7 @@
 #include <memory>
 #include <new>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1767,6 +1768,74 @@ int mi355_op_imatrix_accum(const float *x, const float *x2, int64_t ld, int64_t 
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "imatrix_accum");
     return dsum.down(sum2_io, ns) && dcnt.down(count_io, (size_t)n_mat * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_quantize_supported(int32_t dst_type) { return quantize_dst_supported(dst_type) ? 1 : 0; }
+
+// what the last mi355_quantize_chunk of this thread spent: upload and download by the host's clock (the copies block), the launch between two events
+static thread_local float t_quant_ms[3] = {-1.0f, -1.0f, -1.0f};
+int mi355_quantize_last_times(float *upload_ms, float *kernel_ms, float *download_ms) {
+    if (t_quant_ms[0] < 0.0f) { fail("quantize_last_times: no completed mi355_quantize_chunk on this thread"); return MI355_ERR_ARG; }
+    if (upload_ms) *upload_ms = t_quant_ms[0];
+    if (kernel_ms) *kernel_ms = t_quant_ms[1];
+    if (download_ms) *download_ms = t_quant_ms[2];
+    return MI355_OK;
+}
+
+int mi355_quantize_chunk(int32_t dst_type, int32_t src_type, const void *src, int64_t n_per_row, int64_t n_rows, const float *imatrix, void *dst) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!quantize_dst_supported(dst_type)) { fail("quantize_chunk: destination type " + std::to_string(dst_type) + " is not built"); return MI355_ERR_ARG; }
+    if (!quantize_src_supported(src_type)) { fail("quantize_chunk: source type " + std::to_string(src_type) + " is not F32, F16 or BF16"); return MI355_ERR_ARG; }
+    if (!src || !dst) { fail("quantize_chunk: null pointer"); return MI355_ERR_ARG; }
+    if (n_rows < 1) { fail("quantize_chunk: n_rows < 1"); return MI355_ERR_ARG; }
+    if (n_per_row < 1 || n_per_row % ggml_block_elems(dst_type)) {
+        fail("quantize_chunk: n_per_row " + std::to_string(n_per_row) + " is not a whole number of " + ggml_type_name(dst_type) + " blocks of " +
+             std::to_string(ggml_block_elems(dst_type)));
+        return MI355_ERR_ARG;
+    }
+    if (n_rows > ((int64_t)1 << 36) / n_per_row) { fail("quantize_chunk: more than 2^36 elements in one call"); return MI355_ERR_ARG; }
+    for (int64_t j = 0; imatrix && j < n_per_row; j++)
+        if (!(imatrix[j] >= 0.0f) || std::isinf(imatrix[j])) { fail("quantize_chunk: imatrix[" + std::to_string(j) + "] is negative or not finite"); return MI355_ERR_ARG; }
+    const size_t es = src_type == T_F32 ? 4 : 2, n = (size_t)n_per_row * (size_t)n_rows, rb = ggml_row_bytes(dst_type, n_per_row), nb = rb * (size_t)n_rows;
+    DevBuf dsrc(n * es), dim((size_t)n_per_row * 4), dout(nb + rb), dflag(16);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) { if (ev0) (void)hipEventDestroy(ev0); return MI355_ERR_HIP; }
+    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev_guard{ev0, ev1};
+    const auto c0 = std::chrono::steady_clock::now();
+    if (!dsrc.up(src, n * es) || (imatrix && !dim.up(imatrix, (size_t)n_per_row * 4)) || !dim.p || !dout.p || !dflag.p) return MI355_ERR_OOM;
+    if (hipMemset(dout.as<uint8_t>() + nb, Q80_GUARD, rb) != hipSuccess) return MI355_ERR_HIP;
+    const auto c1 = std::chrono::steady_clock::now();
+    (void)hipEventRecord(ev0, nullptr);
+    hipError_t e = launch_quantize_rows(dst_type, src_type, dsrc.p, n_per_row, n_rows, imatrix ? dim.as<float>() : nullptr, dout.p, dflag.as<int32_t>(), nullptr);
+    if (e == hipErrorInvalidValue) { fail("quantize_chunk: the launcher refuses this shape"); return MI355_ERR_ARG; }
+    (void)hipEventRecord(ev1, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "quantize_chunk");
+    float kernel_ms = 0.0f;
+    (void)hipEventElapsedTime(&kernel_ms, ev0, ev1);
+    const auto c2 = std::chrono::steady_clock::now();
+    int32_t flag = 0;
+    std::vector<uint8_t> guard(rb);
+    if (!dflag.down(&flag, 4) || hipMemcpy(guard.data(), dout.as<uint8_t>() + nb, rb, hipMemcpyDeviceToHost) != hipSuccess) return MI355_ERR_HIP;
+    for (uint8_t b : guard)
+        if (b != Q80_GUARD) { fail("quantize_chunk: the guard row behind the output was written"); return MI355_ERR_HIP; }
+    if (flag) {                                  // which row: the host looks, the error path can afford it
+        int64_t row = -1;
+        for (int64_t i = 0; i < (int64_t)n && row < 0; i++) {
+            uint32_t u;
+            if (src_type == T_F32) memcpy(&u, (const uint8_t *)src + (size_t)i * 4, 4);
+            else { uint16_t h; memcpy(&h, (const uint8_t *)src + (size_t)i * 2, 2); u = src_type == T_F16 ? ((uint32_t)(h & 0x7c00u) == 0x7c00u ? 0x7f800000u : 0u) : (uint32_t)h << 16; }
+            if ((u & 0x7f800000u) == 0x7f800000u) row = i / n_per_row;
+        }
+        fail("quantize_chunk: row " + std::to_string(row) + " holds a non-finite value");
+        return MI355_ERR_ARG;
+    }
+    if (!dout.down(dst, nb)) return MI355_ERR_HIP;
+    const auto c3 = std::chrono::steady_clock::now();
+    t_quant_ms[0] = std::chrono::duration<float, std::milli>(c1 - c0).count();
+    t_quant_ms[1] = kernel_ms;
+    t_quant_ms[2] = std::chrono::duration<float, std::milli>(c3 - c2).count();
+    return MI355_OK;
 }
 
 int mi355_op_topk_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t n_rows, int32_t k, const int32_t *adj_n,

@@ -382,6 +382,15 @@ bool imatrix_accum_ok(const float *x, const float *x2, int ld, int K, int R, con
 hipError_t launch_imatrix_accum(const float *x, const float *x2, int ld, int K, int R, const int32_t *row_src, const int32_t *meta, int n_mat, float *sum2,
                                 int32_t *count, float *slabs, size_t slab_floats, hipStream_t st);
 
+// ---- quantiser (quantize.hip): n_rows rows of n_per_row elements (src_type T_F32 / T_F16 / T_BF16, contiguous, 16-byte aligned) -> ggml-layout
+//   blocks of dst_type (T_Q8_0, T_Q5_0, T_Q5_1, T_Q2_K .. T_Q6_K), n_per_row a whole number of its blocks; imatrix: nullptr or n_per_row f32 column weights
+//   (16-byte aligned).  The bytes are those of tests/quantize_ref.py and do not depend on how the rows are cut into launches.  A non-finite source value is
+//   taken as 0 and sets *nonfinite_flag (an int32 the caller zeroed) to 1.  Any other type, shape or alignment: hipErrorInvalidValue, nothing launched.
+bool quantize_dst_supported(int dst_type);
+bool quantize_src_supported(int src_type);
+hipError_t launch_quantize_rows(int dst_type, int src_type, const void *src, int64_t n_per_row, int64_t n_rows, const float *imatrix, void *dst,
+                                int32_t *nonfinite_flag, hipStream_t st);
+
 // ---------------------------------------------------------------- attention side (attn.hip)
 // words between two merge-ticket counters / hand-over flags of the decode attention kernels (attn_decode_dev.h, attn_out.hip): one 128-byte line each
 constexpr int ATT_SYNC_STRIDE = 32;

@@ -442,6 +442,17 @@ MI355_API int mi355_op_logits_kl_rows(const float *p, int32_t n_p_rows, const fl
  * written, for any other shape. */
 MI355_API int mi355_op_imatrix_accum(const float *x, const float *x2, int64_t ld, int64_t K, int32_t R, const int32_t *row_src, int32_t n_src_rows,
                                      const int32_t *counts_per_mat, int32_t n_mat, float *sum2_io, int32_t *count_io);
+/* The quantiser (csrc/quantize.hip; the counterpart of ggml_quantize_chunk).  src: n_rows rows of n_per_row elements of src_type (0 F32, 1 F16, 30 BF16), host
+ * memory; dst: n_rows rows of dst_type blocks (8 Q8_0, 6 Q5_0, 7 Q5_1, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K), host memory; imatrix: NULL or n_per_row
+ * column weights.  One upload, one launch, one synchronisation, one download; a guard row behind the output on the device is checked after the launch.
+ * MI355_ERR_ARG with mi355_last_error naming the cause: an unsupported type on either side, n_per_row not a whole number of destination blocks, n_rows < 1,
+ * a negative or non-finite imatrix value, a non-finite source value (the message names the first such row; dst is not written). */
+MI355_API int mi355_quantize_chunk(int32_t dst_type, int32_t src_type, const void *src, int64_t n_per_row, int64_t n_rows, const float *imatrix, void *dst);
+/* 1 if mi355_quantize_chunk writes dst_type, else 0.  Needs no device. */
+MI355_API int mi355_quantize_supported(int32_t dst_type);
+/* Milliseconds of the calling thread's last successful mi355_quantize_chunk: the upload (allocation included) and the guard check + download by the host's
+ * clock, the launch between two events on its stream.  Any pointer may be NULL.  MI355_ERR_ARG before the first such call. */
+MI355_API int mi355_quantize_last_times(float *upload_ms, float *kernel_ms, float *download_ms);
 /* logits [n_base_rows][n]; launch row r = base row rows[r], r < R <= 1088; group g < G <= 64 owns launch rows group_start[g] .. group_start[g + 1] - 1
  * (1 .. 17 rows; group_start[0] = 0, group_start[G] = R); draft [R].  ids_out [R], n_accept_out [G] as mi355_spec_verify gives them. */
 MI355_API int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t R, const int32_t *group_start, int32_t G,
