@@ -159,6 +159,15 @@ SYMBOLS = {
     "mi355_quantize_chunk": (C.c_int, [_i32, _i32, _vp, _i64, _i64, _vp, _vp]),
     "mi355_quantize_supported": (C.c_int, [_i32]),
     "mi355_quantize_last_times": (C.c_int, [_vp, _vp, _vp]),
+    "mi355_op_clip_attn": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mi355_op_mul_mat_f16_xh": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _f32, _i32, _vp, _i32, _i32, _vp]),
+    "mi355_op_layer_norm": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _f32, _i32, _vp, _vp]),
+    "mi355_op_clip_gelu": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
+    "mi355_op_clip_im2col": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
+    "mi355_op_clip_embed": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "mi355_op_clip_bias": (C.c_int, [_vp, _vp, _i32, _i32, _f32, _i32]),
+    "mi355_op_f32_to_f16": (C.c_int, [_vp, _i64, _vp]),
+    "mi355_op_add_qkv_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32]),
     "mi355_op_topk_rows": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_moe_group": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_moe_gather_act": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -606,6 +615,99 @@ class Backend:
         assert out.shape == (n_mat + 1, K) and (cpm is None or cpm.size == n_mat) and (row_src is None or row_src.size >= R)
         self._chk(self.lib.mi355_op_imatrix_accum(_ptr(x), _ptr(x2), ld, K, R, _ptr(row_src), x.shape[0], _ptr(cpm), n_mat, _ptr(out), _ptr(cnt)), "op_imatrix_accum")
         return out, cnt
+
+    # ---- the LLaVA image encoder's launches, one at a time (include/mi355_llama.h; tests/test_gpu_clip_ops.py).  f16 outputs come back as np.float16.
+    def clip_attn_rc(self, q: np.ndarray, k: np.ndarray, v: np.ndarray, T: int, H: int, D: int, n_img: int = 1, want_h: bool = True):
+        """The tower's attention within each of n_img images of T rows (q pre-scaled; q, k, v [n_img * T][H * D]).  Returns (rc, out, out_h or None, path):
+        path 1 matrix cores, 2 LDS-tiled, 3 one wave per query, 0 refused (rc != 0, nothing launched)."""
+        q, k, v = (np.ascontiguousarray(a, np.float32).reshape(n_img * T, H * D) for a in (q, k, v))
+        out = np.zeros_like(q)
+        out_h = np.zeros(q.shape, np.float16) if want_h else None
+        path = np.full(1, -1, np.int32)
+        rc = self.lib.mi355_op_clip_attn(_ptr(q), _ptr(k), _ptr(v), T, H, D, n_img, _ptr(out), _ptr(out_h), _ptr(path))
+        return int(rc), out, out_h, int(path[0])
+
+    def clip_attn(self, q, k, v, T: int, H: int, D: int, n_img: int = 1, want_h: bool = True):
+        rc, out, out_h, path = self.clip_attn_rc(q, k, v, T, H, D, n_img, want_h)
+        self._chk(rc, "op_clip_attn")
+        return out, out_h, path
+
+    def mul_mat_f16_xh_rc(self, W: np.ndarray, x: np.ndarray, ld_out=None, bias=None, scale=None, resid=None, in_place: bool = False, form: int = 0, y_init=None):
+        """y = resid + (W . f16(x) + bias) * scale; W [N][K] float16, x [T][K].  Returns (rc, y [T][ld_out]): y starts as y_init (zeros without one; with
+        in_place, as resid, which the launch then reads and writes in the one buffer), so the columns past N show whether the launch left them alone."""
+        W = np.ascontiguousarray(W, np.float16)
+        N, K = W.shape
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+        T = x.shape[0]
+        ld = N if ld_out is None else int(ld_out)
+        b = None if bias is None else np.ascontiguousarray(bias, np.float32).reshape(N)
+        r = None if resid is None else np.ascontiguousarray(resid, np.float32).reshape(T, ld)
+        y = np.array(r if in_place else (np.zeros((T, ld), np.float32) if y_init is None else y_init), np.float32, copy=True, order="C").reshape(T, ld)
+        rc = self.lib.mi355_op_mul_mat_f16_xh(_ptr(W.view(np.uint16)), N, K, _ptr(x), T, ld, _ptr(b), 1.0 if scale is None else float(scale), int(scale is not None),
+                                              None if in_place else _ptr(r), int(in_place), form, _ptr(y))
+        return int(rc), y
+
+    def mul_mat_f16_xh(self, W, x, **kw) -> np.ndarray:
+        rc, y = self.mul_mat_f16_xh_rc(W, x, **kw)
+        self._chk(rc, "op_mul_mat_f16_xh")
+        return y
+
+    def layer_norm(self, x: np.ndarray, w: np.ndarray, b: np.ndarray, eps: float, want_h: bool = True, in_place: bool = False):
+        """LayerNorm with weight and bias over the rows of x [T][n] -> (y, y_h or None)."""
+        x = np.ascontiguousarray(x, np.float32)
+        T, n = x.shape
+        w, b = np.ascontiguousarray(w, np.float32).reshape(n), np.ascontiguousarray(b, np.float32).reshape(n)
+        y = np.zeros_like(x)
+        y_h = np.zeros(x.shape, np.float16) if want_h else None
+        self._chk(self.lib.mi355_op_layer_norm(_ptr(x), _ptr(w), _ptr(b), n, T, eps, int(in_place), _ptr(y), _ptr(y_h)), "op_layer_norm")
+        return y, y_h
+
+    def clip_gelu(self, x: np.ndarray, quick: bool, want_h: bool = True):
+        """ggml's f16-table GELU / quick-GELU -> (y, y_h or None)."""
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.zeros_like(x)
+        y_h = np.zeros(x.shape, np.float16) if want_h else None
+        self._chk(self.lib.mi355_op_clip_gelu(_ptr(x), x.size, int(quick), _ptr(y), _ptr(y_h)), "op_clip_gelu")
+        return y, y_h
+
+    def clip_im2col(self, img: np.ndarray, P: int, ld: int, fill: float = 0.0) -> np.ndarray:
+        """img [3][S][S] -> patches [(S / P)^2][ld]; the device buffer holds `fill` everywhere before the launch."""
+        img = np.ascontiguousarray(img, np.float32)
+        S = img.shape[-1]
+        out = np.full(((S // P) ** 2, ld), fill, np.float32)
+        self._chk(self.lib.mi355_op_clip_im2col(_ptr(img), S, P, ld, _ptr(out)), "op_clip_im2col")
+        return out
+
+    def clip_embed(self, patch: np.ndarray, cls: np.ndarray, pos: np.ndarray) -> np.ndarray:
+        """[class ; patches] + positions: patch [T - 1][E], cls [E], pos [T][E] -> [T][E]."""
+        pos = np.ascontiguousarray(pos, np.float32)
+        T, E = pos.shape
+        patch, cls = np.ascontiguousarray(patch, np.float32).reshape(T - 1, E), np.ascontiguousarray(cls, np.float32).reshape(E)
+        out = np.zeros_like(pos)
+        self._chk(self.lib.mi355_op_clip_embed(_ptr(patch), _ptr(cls), _ptr(pos), E, T, _ptr(out)), "op_clip_embed")
+        return out
+
+    def clip_bias(self, x: np.ndarray, b: np.ndarray, scale=None) -> np.ndarray:
+        """(x + b) [* scale] over the rows of x [T][n]."""
+        y = np.array(x, np.float32, copy=True, order="C")
+        T, n = y.shape
+        b = np.ascontiguousarray(b, np.float32).reshape(n)
+        self._chk(self.lib.mi355_op_clip_bias(_ptr(y), _ptr(b), n, T, 1.0 if scale is None else float(scale), int(scale is not None)), "op_clip_bias")
+        return y
+
+    def f32_to_f16(self, x: np.ndarray) -> np.ndarray:
+        """f16 (round to nearest even) of the f32 values, as the f16 GEMM's activation rows are made; x.size % 4 == 0."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros(x.shape, np.float16)
+        self._chk(self.lib.mi355_op_f32_to_f16(_ptr(x), x.size, _ptr(out)), "op_f32_to_f16")
+        return out
+
+    def add_qkv_bias(self, q, k, v, bq, bk, bv, nq: int, nkv: int, T: int):
+        """q [T][nq] += bq, k / v [T][nkv] += bk / bv in one launch; None skips.  Returns copies (None where None went in)."""
+        xs = [None if a is None else np.array(a, np.float32, copy=True, order="C") for a in (q, k, v)]
+        bs = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (bq, bk, bv)]
+        self._chk(self.lib.mi355_op_add_qkv_bias(_ptr(xs[0]), _ptr(xs[1]), _ptr(xs[2]), _ptr(bs[0]), _ptr(bs[1]), _ptr(bs[2]), nq, nkv, T), "op_add_qkv_bias")
+        return xs
 
     def quantize_rows(self, dst_type: int, x: np.ndarray, imatrix=None, src_type=None) -> np.ndarray:
         """The quantiser (mi355_quantize_chunk): rows x [n_rows][n_per_row] - float32, float16, or uint16 holding bf16 bits with src_type=30 - to ggml-layout

@@ -2511,6 +2511,147 @@ int mi355_op_kv_state_unpack(int32_t type_k, int32_t type_v, int32_t n_layer, in
     return MI355_OK;
 }
 
+// ------------------------------------------------------------------ the LLaVA image encoder's launches, one at a time (tests/test_gpu_clip_ops.py)
+// The tower's attention.  The kernel is named by the function the launcher asks (clip_attn_choice): a refusal returns here, before anything is launched.
+int mi355_op_clip_attn(const float *q, const float *k, const float *v, int64_t T, int32_t H, int32_t D, int32_t n_img, float *out, uint16_t *out_h, int32_t *path) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!q || !k || !v || !out || !path || T < 1 || T > (1 << 20) || H < 1 || D < 4 || D % 4 || n_img < 1) { fail("clip_attn: bad args"); return MI355_ERR_ARG; }
+    const ClipAttnChoice ch = clip_attn_choice((int)T, D);
+    *path = ch.path;
+    if (ch.path == CLIP_ATTN_REFUSED) { fail("clip_attn: no kernel for this head size and row count"); return MI355_ERR_ARG; }
+    const size_t n = (size_t)n_img * T * H * D;
+    DevBuf dq(n * 4), dk(n * 4), dv(n * 4), dout(n * 4), dh(n * 2);
+    if (!dq.up(q, n * 4) || !dk.up(k, n * 4) || !dv.up(v, n * 4) || !dout.p || !dh.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_clip_attn(dq.as<float>(), dk.as<float>(), dv.as<float>(), (int)T, H, D, dout.as<float>(), out_h ? dh.p : nullptr, n_img, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "clip_attn");
+    if (out_h && !dh.down(out_h, n * 2)) return MI355_ERR_HIP;
+    return dout.down(out, n * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_mul_mat_f16_xh(const uint16_t *W, int64_t N, int64_t K, const float *x, int64_t T, int64_t ld_out, const float *bias, float scale, int32_t do_scale,
+                            const float *resid, int32_t in_place, int32_t form, float *y_io) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!W || !x || !y_io || N < 1 || K < 8 || K % 8 || T < 1 || ld_out < N || (form != 0 && form != 1) || (in_place && resid) ||
+        (form == 1 && (ld_out != N || (do_scale && !bias)))) { fail("mul_mat_f16_xh: bad args"); return MI355_ERR_ARG; }
+    const size_t yb = (size_t)T * ld_out * 4;
+    DevBuf dw((size_t)N * K * 2), dx((size_t)T * K * 4), dxh((size_t)T * K * 2), dy(yb), dr(resid ? yb : 0), db(bias ? (size_t)N * 4 : 0), tmp(form == 1 ? yb : 0);
+    if (!dw.up(W, (size_t)N * K * 2) || !dx.up(x, (size_t)T * K * 4) || !dxh.p || !dy.up(y_io, yb) || (resid && !dr.up(resid, yb)) || (bias && !db.up(bias, (size_t)N * 4)) || !tmp.p) {
+        fail("device alloc/copy failed");
+        return MI355_ERR_OOM;
+    }
+    const float *rs = in_place ? dy.as<float>() : resid ? dr.as<float>() : nullptr, *bs = bias ? db.as<float>() : nullptr;
+    hipError_t e = hipSuccess;
+    if (form == 0) {
+        e = launch_f32_to_f16(dx.as<float>(), dxh.p, (size_t)T * K, nullptr);
+        if (e == hipSuccess) e = launch_mmf16_xh(dw.as<uint8_t>(), (int)N, (int)K, dxh.p, (int)T, dy.as<float>(), (int)ld_out, rs, bs, scale, do_scale != 0, nullptr);
+    } else {                                                    // host/clip.cc, MI355_CLIP_XH=0: the product into scratch when a residual follows
+        float *dst = rs ? tmp.as<float>() : dy.as<float>();
+        e = launch_mmf16(dw.as<uint8_t>(), (int)N, (int)K, dx.as<float>(), (int)T, dst, (int)N, nullptr, nullptr);
+        if (e == hipSuccess && bs) e = launch_clip_bias(dst, bs, (int)N, (int)T, scale, do_scale != 0, nullptr);
+        if (e == hipSuccess && rs) e = launch_add(rs, dst, dy.as<float>(), (int64_t)T * N, nullptr);
+    }
+    const hipError_t es = hipDeviceSynchronize();
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "mul_mat_f16_xh");
+    return dy.down(y_io, yb) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_layer_norm(const float *x, const float *w, const float *b, int64_t n, int64_t T, float eps, int32_t in_place, float *y, uint16_t *y_h) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!x || !w || !b || !y || n < 1 || T < 1) { fail("layer_norm: bad args"); return MI355_ERR_ARG; }
+    const size_t nb = (size_t)n * T * 4;
+    DevBuf dx(nb), dw((size_t)n * 4), db((size_t)n * 4), dy(in_place ? 0 : nb), dh(nb / 2);
+    if (!dx.up(x, nb) || !dw.up(w, (size_t)n * 4) || !db.up(b, (size_t)n * 4) || !dy.p || !dh.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    float *o = in_place ? dx.as<float>() : dy.as<float>();
+    hipError_t e = y_h ? launch_layer_norm_h(dx.as<float>(), dw.as<float>(), db.as<float>(), (int)n, (int)T, eps, o, dh.p, nullptr)
+                       : launch_layer_norm(dx.as<float>(), dw.as<float>(), db.as<float>(), (int)n, (int)T, eps, o, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "layer_norm");
+    if (y_h && !dh.down(y_h, nb / 2)) return MI355_ERR_HIP;
+    return hipMemcpy(y, o, nb, hipMemcpyDeviceToHost) == hipSuccess ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_clip_gelu(const float *x, int64_t n, int32_t quick, float *y, uint16_t *y_h) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!x || !y || n < 1) { fail("clip_gelu: bad args"); return MI355_ERR_ARG; }
+    DevBuf dx((size_t)n * 4), dh((size_t)n * 2);
+    if (!dx.up(x, (size_t)n * 4) || !dh.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_clip_gelu(dx.as<float>(), (size_t)n, quick != 0, y_h ? dh.p : nullptr, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "clip_gelu");
+    if (y_h && !dh.down(y_h, (size_t)n * 2)) return MI355_ERR_HIP;
+    return dx.down(y, (size_t)n * 4) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_clip_im2col(const float *img, int32_t S, int32_t P, int32_t ld, float *patches_io) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!img || !patches_io || P < 1 || S < P || S % P || ld < 3 * P * P) { fail("clip_im2col: bad args"); return MI355_ERR_ARG; }
+    const size_t ib = (size_t)3 * S * S * 4, pb = (size_t)(S / P) * (S / P) * ld * 4;
+    DevBuf di(ib), dp(pb);
+    if (!di.up(img, ib) || !dp.up(patches_io, pb)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_clip_im2col(di.as<float>(), S, P, ld, dp.as<float>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "clip_im2col");
+    return dp.down(patches_io, pb) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_clip_embed(const float *patch, const float *cls, const float *pos, int32_t E, int32_t T, float *emb) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!patch || !cls || !pos || !emb || E < 1 || T < 2) { fail("clip_embed: bad args"); return MI355_ERR_ARG; }
+    const size_t rb = (size_t)E * 4;
+    DevBuf dpa(rb * (T - 1)), dc(rb), dpo(rb * T), de(rb * T);
+    if (!dpa.up(patch, rb * (T - 1)) || !dc.up(cls, rb) || !dpo.up(pos, rb * T) || !de.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_clip_embed(dpa.as<float>(), dc.as<float>(), dpo.as<float>(), E, T, de.as<float>(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "clip_embed");
+    return de.down(emb, rb * T) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_clip_bias(float *x_io, const float *b, int32_t n, int32_t T, float scale, int32_t do_scale) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!x_io || !b || n < 1 || T < 1) { fail("clip_bias: bad args"); return MI355_ERR_ARG; }
+    const size_t nb = (size_t)n * T * 4;
+    DevBuf dx(nb), db((size_t)n * 4);
+    if (!dx.up(x_io, nb) || !db.up(b, (size_t)n * 4)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_clip_bias(dx.as<float>(), db.as<float>(), n, T, scale, do_scale != 0, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "clip_bias");
+    return dx.down(x_io, nb) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_f32_to_f16(const float *x, int64_t n, uint16_t *out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!x || !out || n < 4 || n % 4) { fail("f32_to_f16: n must be a positive multiple of 4"); return MI355_ERR_ARG; }
+    DevBuf dx((size_t)n * 4), dy((size_t)n * 2);
+    if (!dx.up(x, (size_t)n * 4) || !dy.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
+    hipError_t e = launch_f32_to_f16(dx.as<float>(), dy.p, (size_t)n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "f32_to_f16");
+    return dy.down(out, (size_t)n * 2) ? MI355_OK : MI355_ERR_HIP;
+}
+
+int mi355_op_add_qkv_bias(float *q_io, float *k_io, float *v_io, const float *bq, const float *bk, const float *bv, int32_t nq, int32_t nkv, int32_t T) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (nq < 1 || nkv < 0 || T < 1 || (bq && !q_io) || (bk && !k_io) || (bv && !v_io) || ((bk || bv) && nkv < 1)) { fail("add_qkv_bias: bad args"); return MI355_ERR_ARG; }
+    float *const xs[3] = {q_io, k_io, v_io};
+    const float *const bs[3] = {bq, bk, bv};
+    std::unique_ptr<DevBuf> dx[3], db[3];
+    for (int s = 0; s < 3; s++) {
+        const size_t n = s == 0 ? (size_t)nq : (size_t)nkv;
+        if (xs[s]) { dx[s].reset(new DevBuf(n * T * 4)); if (!dx[s]->up(xs[s], n * T * 4)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; } }
+        if (bs[s]) { db[s].reset(new DevBuf(n * 4)); if (!db[s]->up(bs[s], n * 4)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; } }
+    }
+    auto xp = [&](int s) { return dx[s] ? dx[s]->as<float>() : nullptr; };
+    auto bp = [&](int s) { return db[s] ? db[s]->as<float>() : nullptr; };
+    hipError_t e = launch_add_qkv_bias(xp(0), xp(1), xp(2), bp(0), bp(1), bp(2), nq, nkv, T, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "add_qkv_bias");
+    for (int s = 0; s < 3; s++)
+        if (xs[s] && !dx[s]->down(xs[s], (s == 0 ? (size_t)nq : (size_t)nkv) * T * 4)) return MI355_ERR_HIP;
+    return MI355_OK;
+}
+
 int mi355_debug_set_option(const char *name, int32_t value) {
     if (!name) return MI355_ERR_ARG;
     if (!strcmp(name, "mmq_planes")) { g_op_mmq_planes = value != 0; return MI355_OK; }

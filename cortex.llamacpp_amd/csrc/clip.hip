@@ -361,29 +361,41 @@ static hipError_t launch_clip_attn_tiled(const float *q, const float *k, const f
     hipLaunchKernelGGL(clip_attn_tiled_kernel<D>, dim3((unsigned)((T + 39) / 40), (unsigned)H, (unsigned)n_img), dim3(256), lds, st, q, k, v, T, H, out, outh);
     return hipGetLastError();
 }
-// out_h (optional): the output rows once more, rounded to f16.  n_img images of T rows each, one after the other in every buffer: attention within an image.
-hipError_t launch_clip_attn(const float *q, const float *k, const float *v, int T, int H, int D, float *out, void *out_h, int n_img, hipStream_t st) {
-    _Float16 *outh = reinterpret_cast<_Float16 *>(out_h);
-    const char *sw = getenv("MI355_CLIP_ATTN_TILED");           // (read at every launch - a few dozen an image - so that a test can compare the kernels)
+// Which kernel launch_clip_attn runs for T rows of head size D, and the LDS it asks for - the launcher and the test entry (mi355_op_clip_attn) both ask here.
+// MI355_CLIP_ATTN_TILED=0: the one-wave-per-query kernel only; MI355_CLIP_ATTN_MFMA=0: the f32 VALU kernels only (both read at every call - a few dozen an image
+// - so that a test can compare the kernels).  A workgroup may hold 160 KiB of LDS, the one-wave kernel's four probability rows stay within 64 KiB.
+ClipAttnChoice clip_attn_choice(int T, int D) {
+    const char *sw = getenv("MI355_CLIP_ATTN_TILED");
     const bool tiled = !(sw && atoi(sw) == 0);
-    const char *sm_ = getenv("MI355_CLIP_ATTN_MFMA");           // "0": the f32 VALU kernels only
+    const char *sm_ = getenv("MI355_CLIP_ATTN_MFMA");
+    if (T < 1) return {CLIP_ATTN_REFUSED, 0};
     if (tiled && D == 64 && !(sm_ && atoi(sm_) == 0)) {
         const size_t Tp = (size_t)(T + 127) / 128 * 128, lds = ((size_t)32 * 65 + (size_t)128 * 65 + (size_t)32 * (Tp + 1)) * sizeof(float);
-        if (lds <= 160 * 1024) return launch_clip_attn_mfma(q, k, v, T, H, n_img, out, outh, lds, st);
+        if (lds <= 160 * 1024) return {CLIP_ATTN_MFMA, lds};
     }
     if (tiled && (D == 32 || D == 64 || D == 128)) {
         const size_t Tp = (size_t)(T + 63) / 64 * 64, lds = ((size_t)40 * D + (size_t)64 * (D + 4) + (size_t)40 * Tp) * sizeof(float);
-        if (lds <= 160 * 1024) {
-            switch (D) {
-                case 32: return launch_clip_attn_tiled<32>(q, k, v, T, H, n_img, out, outh, lds, st);
-                case 64: return launch_clip_attn_tiled<64>(q, k, v, T, H, n_img, out, outh, lds, st);
-                default: return launch_clip_attn_tiled<128>(q, k, v, T, H, n_img, out, outh, lds, st);
-            }
+        if (lds <= 160 * 1024) return {CLIP_ATTN_TILED, lds};
+    }
+    const size_t lds = (size_t)4 * T * sizeof(float);
+    if ((D != 32 && D != 64 && D != 80 && D != 128) || lds > 64 * 1024) return {CLIP_ATTN_REFUSED, 0};
+    return {CLIP_ATTN_WAVE, lds};
+}
+// out_h (optional): the output rows once more, rounded to f16.  n_img images of T rows each, one after the other in every buffer: attention within an image.
+hipError_t launch_clip_attn(const float *q, const float *k, const float *v, int T, int H, int D, float *out, void *out_h, int n_img, hipStream_t st) {
+    _Float16 *outh = reinterpret_cast<_Float16 *>(out_h);
+    const ClipAttnChoice ch = clip_attn_choice(T, D);
+    const size_t lds = ch.lds;
+    if (ch.path == CLIP_ATTN_REFUSED) return hipErrorInvalidValue;
+    if (ch.path == CLIP_ATTN_MFMA) return launch_clip_attn_mfma(q, k, v, T, H, n_img, out, outh, lds, st);
+    if (ch.path == CLIP_ATTN_TILED) {
+        switch (D) {
+            case 32: return launch_clip_attn_tiled<32>(q, k, v, T, H, n_img, out, outh, lds, st);
+            case 64: return launch_clip_attn_tiled<64>(q, k, v, T, H, n_img, out, outh, lds, st);
+            default: return launch_clip_attn_tiled<128>(q, k, v, T, H, n_img, out, outh, lds, st);
         }
     }
     const dim3 grid((unsigned)((T + 3) / 4), (unsigned)H);
-    const size_t lds = (size_t)4 * T * sizeof(float);
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
     for (int im = 0; im < n_img; im++) {
         const size_t o = (size_t)im * T * H * D;
         switch (D) {

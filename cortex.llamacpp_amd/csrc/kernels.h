@@ -287,8 +287,13 @@ hipError_t launch_clip_embed(const float *patch, const float *cls, const float *
 hipError_t launch_clip_bias(float *x, const float *b, int n, int T, float scale, bool do_scale, hipStream_t st);  // x = (x + b) [* scale]
 // (out_h / xh, optional: the result once more, rounded to f16 - what the f16 GEMM that consumes it reads)
 hipError_t launch_clip_attn(const float *q, const float *k, const float *v, int T, int H, int D, float *out, void *out_h, int n_img, hipStream_t st);     // unmasked, q pre-scaled; n_img images of T rows
+// the kernel launch_clip_attn picks for T rows of head size D (head size, MI355_CLIP_ATTN_TILED / MI355_CLIP_ATTN_MFMA and the LDS each kernel needs), stated once
+enum { CLIP_ATTN_REFUSED = 0, CLIP_ATTN_MFMA = 1, CLIP_ATTN_TILED = 2, CLIP_ATTN_WAVE = 3 };   // no kernel (launch_clip_attn: hipErrorInvalidValue) | f32 matrix cores | LDS-tiled | one wave per query
+struct ClipAttnChoice { int path; size_t lds; };
+ClipAttnChoice clip_attn_choice(int T, int D);
 hipError_t launch_clip_gelu(float *x, size_t n, bool quick, void *xh, hipStream_t st);                            // ggml's f16-table GELU / quick-GELU
 bool mmf16_applicable(int type, int n_rows, int K, int T, const void *W, const void *x, const void *y);
+// (both f16 launchers: K % 16 == 0 - a matrix-core step takes 16 of k - hipErrorInvalidValue and nothing launched otherwise)
 hipError_t launch_mmf16(const uint8_t *W, int n_rows, int K, const float *x, int T, float *y, int ld_out, const float *resid, hipStream_t st);
 // the same with the activation rows rounded to f16 beforehand (once per row instead of once per workgroup that reads it): xh [T][K] halves
 hipError_t launch_f32_to_f16(const float *x, void *y, size_t n, hipStream_t st);

@@ -222,14 +222,18 @@ static hipError_t launch_mmf16_t(const uint8_t *W, int n_rows, int K, const void
     }
     return hipGetLastError();
 }
+// (K % 16: both kernels consume k in matrix-core steps of 16 - with K % 16 == 8 the direct kernel would read eight halves past every row, and past the buffer on
+// the last one, and the LDS kernel would multiply the row's last eight columns twice)
 hipError_t launch_mmf16(const uint8_t *W, int n_rows, int K, const float *x, int T, float *y, int ld_out, const float *resid, hipStream_t st) {
+    if (K < 16 || K % 16) return hipErrorInvalidValue;
     return launch_mmf16_t<false>(W, n_rows, K, x, T, y, ld_out, resid, nullptr, 1.0f, false, st);
 }
 // the same product with the activation rows already rounded to f16 (launch_f32_to_f16): [T][K] halves; y = resid + (W x + bias) * scale, every part optional
 hipError_t launch_mmf16_xh(const uint8_t *W, int n_rows, int K, const void *xh, int T, float *y, int ld_out, const float *resid, const float *bias, float scale, bool do_scale,
                            hipStream_t st) {
+    if (K < 16 || K % 16) return hipErrorInvalidValue;
     const char *sw = getenv("MI355_MMF16_LDS");                 // "0": the direct-from-global kernel (A/B and tests)
-    if (!(sw && atoi(sw) == 0) && (K % 8) == 0) {
+    if (!(sw && atoi(sw) == 0)) {
         hipLaunchKernelGGL(mmf16_lds_kernel, dim3((unsigned)((n_rows + 63) / 64), (unsigned)((T + 63) / 64)), dim3(256), 0, st, reinterpret_cast<const _Float16 *>(W), n_rows, K,
                            reinterpret_cast<const _Float16 *>(xh), T, y, ld_out, resid, bias, scale, (int)do_scale);
         return hipGetLastError();

@@ -453,6 +453,36 @@ MI355_API int mi355_quantize_supported(int32_t dst_type);
 /* Milliseconds of the calling thread's last successful mi355_quantize_chunk: the upload (allocation included) and the guard check + download by the host's
  * clock, the launch between two events on its stream.  Any pointer may be NULL.  MI355_ERR_ARG before the first such call. */
 MI355_API int mi355_quantize_last_times(float *upload_ms, float *kernel_ms, float *download_ms);
+/* ---- the LLaVA image encoder's launches (csrc/clip.hip, csrc/mmf.hip, csrc/act.hip), one at a time: each entry uploads its inputs, issues the one launch
+ * host/clip.cc issues, and downloads the result.  Half-precision outputs are raw f16 bits; every *_h output may be NULL (the launch then gets no f16 pointer).
+ *
+ * The tower's full attention within each of n_img images of T rows: q (pre-scaled), k, v, out [n_img][T][H * D].  *path: the kernel launch_clip_attn's choice
+ * function names for (T, D) under MI355_CLIP_ATTN_TILED / MI355_CLIP_ATTN_MFMA: 1 f32 matrix cores, 2 LDS-tiled, 3 one wave per query, 0 refused - then
+ * MI355_ERR_ARG and nothing is launched (no kernel for the head size, or T past the kernel's LDS). */
+MI355_API int mi355_op_clip_attn(const float *q, const float *k, const float *v, int64_t T, int32_t H, int32_t D, int32_t n_img, float *out, uint16_t *out_h,
+                                 int32_t *path);
+/* y = resid + (W . f16(x) + bias) * scale against an f16 tensor W [N][K] (bits), x [T][K]; bias [N], the scale (do_scale) and resid [T][ld_out] each optional.
+ * y_io [T][ld_out], ld_out >= N: uploaded before the launch and read back whole, so the columns past N must come back as they went in.  in_place 1: y_io holds
+ * the residual rows on entry and the launch gets the one device buffer as resid and y (resid must be NULL).
+ * form 0: launch_f32_to_f16, then launch_mmf16_xh with the epilogue fused (MI355_MMF16_LDS=0: the direct kernel; MI355_MMF16_TILE=128: its large tile);
+ * form 1: the unfused chain launch_mmf16, launch_clip_bias, launch_add (ld_out == N; a scale only with a bias, as host/clip.cc has it).
+ * K % 16 != 0: the launchers refuse (MI355_ERR_HIP) before any matrix launch. */
+MI355_API int mi355_op_mul_mat_f16_xh(const uint16_t *W, int64_t N, int64_t K, const float *x, int64_t T, int64_t ld_out, const float *bias, float scale,
+                                      int32_t do_scale, const float *resid, int32_t in_place, int32_t form, float *y_io);
+/* LayerNorm with weight and bias over T rows of n; in_place 1: the launch reads and writes one device buffer. */
+MI355_API int mi355_op_layer_norm(const float *x, const float *w, const float *b, int64_t n, int64_t T, float eps, int32_t in_place, float *y, uint16_t *y_h);
+/* ggml's f16-table GELU (quick 0) / quick-GELU (quick 1) of n values */
+MI355_API int mi355_op_clip_gelu(const float *x, int64_t n, int32_t quick, float *y, uint16_t *y_h);
+/* img [3][S][S] -> patches_io [(S / P)^2][ld], ld >= 3 P P: uploaded first and read back whole (the launch writes every column, zeros past 3 P P) */
+MI355_API int mi355_op_clip_im2col(const float *img, int32_t S, int32_t P, int32_t ld, float *patches_io);
+/* emb [T][E]: row 0 = cls + pos[0], row t = patch[t - 1] + pos[t]; patch [T - 1][E], pos [T][E] */
+MI355_API int mi355_op_clip_embed(const float *patch, const float *cls, const float *pos, int32_t E, int32_t T, float *emb);
+/* x_io [T][n] = (x + b) [* scale] */
+MI355_API int mi355_op_clip_bias(float *x_io, const float *b, int32_t n, int32_t T, float scale, int32_t do_scale);
+/* round-to-nearest-even f32 -> f16 bits, n % 4 == 0 */
+MI355_API int mi355_op_f32_to_f16(const float *x, int64_t n, uint16_t *out);
+/* q_io [T][nq] += bq, k_io / v_io [T][nkv] += bk / bv in one launch; a NULL bias skips its segment (its rows may then be NULL too) */
+MI355_API int mi355_op_add_qkv_bias(float *q_io, float *k_io, float *v_io, const float *bq, const float *bk, const float *bv, int32_t nq, int32_t nkv, int32_t T);
 /* logits [n_base_rows][n]; launch row r = base row rows[r], r < R <= 1088; group g < G <= 64 owns launch rows group_start[g] .. group_start[g + 1] - 1
  * (1 .. 17 rows; group_start[0] = 0, group_start[G] = R); draft [R].  ids_out [R], n_accept_out [G] as mi355_spec_verify gives them. */
 MI355_API int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t R, const int32_t *group_start, int32_t G,

@@ -97,6 +97,20 @@ def test_no_cpu_fallback(pkg):
                                            planes.ctypes.data, planes.ctypes.data, planes.ctypes.data, None) == -100
     assert lib.mi355_op_attn_batch_step_planes(None, None, None, 1, 8, 1, 32, 1, None, 1, None, 1, 1, None, None, None, None, None, 1e4, 32, 0, 1.0, 0, None, None,
                                                None, None) == -100
+    # the image encoder's launches: one 32-wide head over four rows; 32 f16 rows of 16 over eight tokens; a 2 x 2 patch grid
+    h16 = np.zeros(256, np.uint16)
+    assert lib.mi355_op_clip_attn(x.ctypes.data, x.ctypes.data, x.ctypes.data, 4, 1, 32, 1, y.ctypes.data, h16.ctypes.data, path.ctypes.data) == -100
+    w16 = np.zeros(32 * 16, np.uint16)
+    for form in (0, 1):
+        assert lib.mi355_op_mul_mat_f16_xh(w16.ctypes.data, 32, 16, x.ctypes.data, 8, 32, None, 1.0, 0, None, 0, form, y.ctypes.data) == -100, form
+    assert lib.mi355_op_mul_mat_f16_xh(w16.ctypes.data, 16, 24, x.ctypes.data, 8, 16, None, 1.0, 0, None, 0, 0, y.ctypes.data) == -100
+    assert lib.mi355_op_layer_norm(x.ctypes.data, x.ctypes.data, x.ctypes.data, 16, 4, 1e-5, 0, y.ctypes.data, h16.ctypes.data) == -100
+    assert lib.mi355_op_clip_gelu(x.ctypes.data, 256, 0, y.ctypes.data, h16.ctypes.data) == -100
+    assert lib.mi355_op_clip_im2col(x.ctypes.data, 4, 2, 16, y.ctypes.data) == -100
+    assert lib.mi355_op_clip_embed(x.ctypes.data, x.ctypes.data, x.ctypes.data, 16, 4, y.ctypes.data) == -100
+    assert lib.mi355_op_clip_bias(y.ctypes.data, x.ctypes.data, 16, 4, 1.0, 0) == -100
+    assert lib.mi355_op_f32_to_f16(x.ctypes.data, 256, h16.ctypes.data) == -100
+    assert lib.mi355_op_add_qkv_bias(y.ctypes.data, None, None, x.ctypes.data, None, None, 16, 0, 4) == -100
 
 
 def test_product_does_not_touch_oracle():
