@@ -1,4 +1,4 @@
-// c_api.cc — the C-ABI declared in include/mi355_llama.h, over host/runtime.{h,cc}.
+// c_api.cc — the product C-ABI declared in include/mi355_llama.h, over host/runtime.{h,cc}.  The per-op test entries (mi355_op_*) are in op_entries_*.cc.
 #include "../../include/mi355_llama.h"
 
 #include <atomic>
@@ -12,12 +12,12 @@
 #include <string>
 #include <vector>
 
+#include "op_support.h"
 #include "../host/clip.h"
 #include "../host/engine.h"
 #include "../host/hip_backend.h"
 #include "../host/log.h"
 #include "../host/runtime.h"
-#include "../host/attn_chunks.h"
 #include "../host/tp_comm.h"
 #include "../host/tp_split.h"
 #include "../host/vocab.h"
@@ -47,18 +47,12 @@ struct mi355_context {
 };
 
 static thread_local std::string t_err;
-static int g_op_mmq_planes = 1, g_op_mmq_ksplit = 1;
 static bool g_backend_ok = false;
 
-static void fail(const std::string &s) { t_err = s; }
-
-// No C++ exception may cross the C ABI (the reference's own rule for its plugin boundary, enginei.h): allocation failures
-// and anything else thrown below an entry point become that entry point's error return and a last_error message.
-#define MI355_GUARD(on_error, ...)                                              \
-    try { __VA_ARGS__ }                                                         \
-    catch (const std::bad_alloc &) { fail("out of host memory"); on_error; }    \
-    catch (const std::exception &ex) { fail(std::string("internal error: ") + ex.what()); on_error; } \
-    catch (...) { fail("internal error"); on_error; }
+// what op_support.h declares for the per-op test entries (op_entries_*.cc): the error string, the device check, the switches of mi355_debug_set_option
+int mi355::g_op_mmq_planes = 1, mi355::g_op_mmq_ksplit = 1;
+void mi355::fail(const std::string &s) { t_err = s; }
+bool mi355::need_device() { return g_backend_ok || mi355_backend_init() == MI355_OK; }
 
 extern "C" {
 
@@ -715,1060 +709,9 @@ double mi355_bench_weight_sweep2(mi355_context *ctx, int iters, uint64_t *bytes_
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ per-op wrappers
-namespace {
-struct DevBuf {
-    void *p = nullptr;
-    size_t n = 0;
-    explicit DevBuf(size_t bytes) : n(bytes) { if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) p = nullptr; else (void)hipMemset(p, 0, bytes ? bytes : 16); }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <typename T> T *as() { return reinterpret_cast<T *>(p); }
-    bool up(const void *src, size_t bytes) { return p && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess; }
-    bool down(void *dst, size_t bytes) { return p && hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
-};
-bool need_device() {
-    if (g_backend_ok) return true;
-    return mi355_backend_init() == MI355_OK;
-}
-struct ActBufs {
-    DevBuf qs, d, bs, qs0, d0;
-    ActQuant q;
-    ActBufs(size_t K, size_t T) : qs(T * K), d(T * (K / 256 + 1) * 4), bs(T * (K / 16 + 1) * 2), qs0(T * K), d0(T * (K / 32 + 1) * 2) {
-        q.qs = qs.as<int8_t>(); q.d = d.as<float>(); q.bsums = bs.as<int16_t>(); q.qs0 = qs0.as<int8_t>(); q.d0 = d0.as<uint16_t>();
-    }
-    bool ok() const { return qs.p && d.p && bs.p && qs0.p && d0.p; }
-};
-// The quantiser hooks give the planes one row more than they ask for, filled with a pattern first and checked afterwards: a kernel that walks past the end
-// of a row (its partial last 256-group) or of the last row lands there.
-const int Q80_GUARD = 0xA5;
-bool q80_guard_set(ActBufs &ab, size_t n, size_t rows) {
-    return hipMemset(ab.q.qs0 + rows * n, Q80_GUARD, n) == hipSuccess && hipMemset(ab.q.d0 + rows * (n / 32), Q80_GUARD, (n / 32) * 2) == hipSuccess;
-}
-bool q80_guard_intact(ActBufs &ab, size_t n, size_t rows) {
-    std::vector<uint8_t> g(n + (n / 32) * 2);
-    if (hipMemcpy(g.data(), ab.q.qs0 + rows * n, n, hipMemcpyDeviceToHost) != hipSuccess) return false;
-    if (hipMemcpy(g.data() + n, ab.q.d0 + rows * (n / 32), (n / 32) * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
-    for (uint8_t b : g) if (b != Q80_GUARD) return false;
-    return true;
-}
-int hip_fail(hipError_t e, const char *what) {
-    fail(std::string(what) + ": " + hipGetErrorString(e));
-    return MI355_ERR_HIP;
-}
-// ggml-layout cache rows [n_cells][G * D] (f16, q8_0 or q4_0 blocks) -> the device's head-major planes: codes [G][n_cells][...] and f16 block scales
-void cache_planes_from_rows(int type, const void *rows, int G, int D, int n_cells, std::vector<uint8_t> &codes, std::vector<uint16_t> &scales) {
-    const uint8_t *src = (const uint8_t *)rows;
-    const size_t rb = ggml_row_bytes(type, (int64_t)G * D);
-    if (type == T_F16) {
-        codes.resize((size_t)G * n_cells * D * 2);
-        for (int c = 0; c < n_cells; c++)
-            for (int g = 0; g < G; g++) memcpy(&codes[(((size_t)g * n_cells + c) * D) * 2], src + (size_t)c * rb + (size_t)g * D * 2, (size_t)D * 2);
-    } else {
-        const int bb = ggml_block_bytes(type), cb = bb - 2;
-        codes.resize((size_t)G * n_cells * (D / 32) * cb);
-        scales.resize((size_t)G * n_cells * (D / 32));
-        for (int c = 0; c < n_cells; c++)
-            for (int g = 0; g < G; g++)
-                for (int b = 0; b < D / 32; b++) {
-                    const uint8_t *blk = src + (size_t)c * rb + ((size_t)g * (D / 32) + b) * bb;
-                    memcpy(&scales[((size_t)g * n_cells + c) * (D / 32) + b], blk, 2);
-                    memcpy(&codes[(((size_t)g * n_cells + c) * (D / 32) + b) * cb], blk + 2, (size_t)cb);
-                }
-    }
-}
-// ... and back: the cache row at `cell` in ggml block layout (dst: G * D elements' worth; null: nothing to do)
-bool cache_row_to_ggml(int type, DevBuf &codes, DevBuf &scales, int G, int D, int n_cells, int cell, void *dst) {
-    if (!dst) return true;
-    uint8_t *o8 = (uint8_t *)dst;
-    for (int g = 0; g < G; g++) {
-        const size_t rowi = (size_t)g * n_cells + cell;
-        if (type == T_F16) {
-            if (hipMemcpy(o8 + (size_t)g * D * 2, (uint8_t *)codes.p + rowi * D * 2, (size_t)D * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
-        } else {
-            const int bb = ggml_block_bytes(type), cb = bb - 2;
-            std::vector<uint8_t> c((size_t)(D / 32) * cb);
-            std::vector<uint16_t> sc((size_t)D / 32);
-            if (hipMemcpy(c.data(), (uint8_t *)codes.p + rowi * (D / 32) * cb, c.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
-            if (hipMemcpy(sc.data(), (uint8_t *)scales.p + rowi * (D / 32) * 2, sc.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
-            for (int b = 0; b < D / 32; b++) {
-                uint8_t *blk = o8 + ((size_t)g * (D / 32) + b) * bb;
-                memcpy(blk, &sc[(size_t)b], 2);
-                memcpy(blk + 2, &c[(size_t)b * cb], (size_t)cb);
-            }
-        }
-    }
-    return true;
-}
-// ... and the whole cache: every cell of the device's planes back into ggml-layout rows [n_cells][G * D] (the inverse of cache_planes_from_rows)
-bool cache_rows_from_planes(int type, DevBuf &codes, DevBuf &scales, int G, int D, int n_cells, void *rows) {
-    uint8_t *dst = (uint8_t *)rows;
-    const size_t rb = ggml_row_bytes(type, (int64_t)G * D);
-    const int cb = type == T_F16 ? 64 : type == T_Q8_0 ? 32 : 16, bb = type == T_F16 ? 64 : cb + 2;   // code bytes of 32 elements; bytes of their ggml block
-    std::vector<uint8_t> c((size_t)G * n_cells * (D / 32) * cb);
-    std::vector<uint16_t> sc(type == T_F16 ? 0 : (size_t)G * n_cells * (D / 32));
-    if (!codes.down(c.data(), c.size()) || (!sc.empty() && !scales.down(sc.data(), sc.size() * 2))) return false;
-    for (int cell = 0; cell < n_cells; cell++)
-        for (int g = 0; g < G; g++)
-            for (int b = 0; b < D / 32; b++) {
-                const size_t bi = ((size_t)g * n_cells + cell) * (D / 32) + b;
-                uint8_t *blk = dst + (size_t)cell * rb + ((size_t)g * (D / 32) + b) * bb;
-                if (type != T_F16) { memcpy(blk, &sc[bi], 2); blk += 2; }
-                memcpy(blk, &c[bi * cb], (size_t)cb);
-            }
-    return true;
-}
-// The per-token chunk lists of a test entry's step, built by the function the runtime builds its own with (host/attn_chunks.h) and laid out as Context keeps
-// them: [64][stride] lists, then [64] counts.  grid: the chunk slots the launch gets (a.splits).
-struct ChunkLists {
-    std::unique_ptr<DevBuf> dev;
-    int stride = 0, lmax = 0, grid = 0;
-    bool make(int n_kv, int n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *tok_seq, int T) {
-        stride = (n_cells + ATTN_CHUNK_CELLS - 1) / ATTN_CHUNK_CELLS;
-        std::vector<int32_t> h((size_t)64 * (stride + 1), 0);
-        lmax = build_attn_chunk_lists(n_kv, n_cells, [&](int i, int32_t &p, uint64_t &m) { p = cell_pos[i]; m = cell_seq[i]; }, tok_seq, T, stride, h.data(),
-                                      h.data() + (size_t)64 * stride);
-        grid = attn_chunk_grid(lmax, stride);
-        dev.reset(new DevBuf(h.size() * 4));
-        return dev->up(h.data(), h.size() * 4);
-    }
-    void apply(AttnArgs &a) const {
-        a.tok_chunks = dev->as<int32_t>(); a.tok_nchunks = dev->as<int32_t>() + (size_t)64 * stride; a.chunk_stride = stride;
-        a.splits = grid;
-    }
-};
-int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y);
-}  // namespace
-
 extern "C" double hbm_read_probe(size_t bytes, int iters);
 
 extern "C" {
-
-int mi355_op_quantize_act(int32_t act_type, const float *x, int64_t n, int64_t rows, void *out_blocks) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    // Q8_0: any whole number of 32-element blocks; a Q8_K block is 256 elements
-    if ((act_type != MI355_TYPE_Q8_K && act_type != MI355_TYPE_Q8_0) || n <= 0 || rows <= 0 || n % (act_type == MI355_TYPE_Q8_K ? 256 : 32)) { fail("bad args"); return MI355_ERR_ARG; }
-    DevBuf dx((size_t)n * rows * 4);
-    ActBufs ab((size_t)n, (size_t)rows + 1);
-    const size_t ob = act_type == MI355_TYPE_Q8_K ? ggml_row_bytes(T_Q8_K, n) * rows : ggml_row_bytes(T_Q8_0, n) * rows;
-    DevBuf dout(ob);
-    if (!dx.up(x, (size_t)n * rows * 4) || !ab.ok() || !dout.p || !q80_guard_set(ab, (size_t)n, (size_t)rows)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_quantize(dx.as<float>(), (int)n, (int)rows, ab.q, act_type == MI355_TYPE_Q8_K, act_type == MI355_TYPE_Q8_0, nullptr);
-    if (e == hipSuccess) e = act_type == MI355_TYPE_Q8_K ? launch_pack_q8k_blocks(ab.q, (int)n, (int)rows, dout.as<uint8_t>(), nullptr)
-                                                         : launch_pack_q80_blocks(ab.q, (int)n, (int)rows, dout.as<uint8_t>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "quantize_act");
-    if (act_type == MI355_TYPE_Q8_0 && !q80_guard_intact(ab, (size_t)n, (size_t)rows)) { fail("quantize_act: the quantiser wrote past the last row"); return MI355_ERR_HIP; }
-    return dout.down(out_blocks, ob) ? MI355_OK : MI355_ERR_HIP;
-}
-
-// RMSNorm * weight and the Q8_0 quantisation of its rows in one launch, as a layer's norm_quant step runs it: the per-row kernel, from 32 rows on the wide
-// prompt-batch one.  out_blocks: T rows of n / 32 ggml block_q8_0; y_f32 (optional): the f32 rows the blocks were made from.  n: any multiple of 32.
-int mi355_op_rms_norm_quant(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y_f32, void *out_blocks) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!x || !w || !out_blocks || n <= 0 || T <= 0 || n % 32) { fail("bad args"); return MI355_ERR_ARG; }
-    DevBuf dx((size_t)n * T * 4), dw((size_t)n * 4), dy((size_t)n * T * 4), dout(ggml_row_bytes(T_Q8_0, n) * T);
-    ActBufs ab((size_t)n, (size_t)T + 1);
-    if (!dx.up(x, (size_t)n * T * 4) || !dw.up(w, (size_t)n * 4) || !dy.p || !dout.p || !ab.ok() || !q80_guard_set(ab, (size_t)n, (size_t)T)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_rmsnorm_quant(dx.as<float>(), dw.as<float>(), (int)n, (int)T, eps, y_f32 ? dy.as<float>() : nullptr, &ab.q, false, true, nullptr);
-    if (e == hipSuccess) e = launch_pack_q80_blocks(ab.q, (int)n, (int)T, dout.as<uint8_t>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "rms_norm_quant");
-    if (!q80_guard_intact(ab, (size_t)n, (size_t)T)) { fail("rms_norm_quant: the quantiser wrote past the last row"); return MI355_ERR_HIP; }
-    if (y_f32 && !dy.down(y_f32, (size_t)n * T * 4)) return MI355_ERR_HIP;
-    return dout.down(out_blocks, ggml_row_bytes(T_Q8_0, n) * T) ? MI355_OK : MI355_ERR_HIP;
-}
-
-// silu(gate) * up and the Q8_0 quantisation of the result in one launch (a prompt batch's step between ffn_gate | ffn_up and ffn_down).  n: any multiple of 32.
-int mi355_op_swiglu_quant(const float *gate, const float *up, int64_t n, int64_t T, void *out_blocks) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!gate || !up || !out_blocks || n <= 0 || T <= 0 || n % 32) { fail("bad args"); return MI355_ERR_ARG; }
-    DevBuf dg((size_t)n * T * 4), du((size_t)n * T * 4), dout(ggml_row_bytes(T_Q8_0, n) * T);
-    ActBufs ab((size_t)n, (size_t)T + 1);
-    if (!dg.up(gate, (size_t)n * T * 4) || !du.up(up, (size_t)n * T * 4) || !dout.p || !ab.ok() || !q80_guard_set(ab, (size_t)n, (size_t)T)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_swiglu_quant(dg.as<float>(), du.as<float>(), (int)n, (int)T, ab.q, false, true, nullptr, nullptr, nullptr);
-    if (e == hipSuccess) e = launch_pack_q80_blocks(ab.q, (int)n, (int)T, dout.as<uint8_t>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "swiglu_quant");
-    if (!q80_guard_intact(ab, (size_t)n, (size_t)T)) { fail("swiglu_quant: the quantiser wrote past the last row"); return MI355_ERR_HIP; }
-    return dout.down(out_blocks, ggml_row_bytes(T_Q8_0, n) * T) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    // the 32-element formats: any whole number of blocks (the K-quants below: their plane sets, whole 256-blocks); f16 as two products and the SwiGLU pass
-    if (act_is_q80(type) || type == T_F16) return op_ffn_gate_up_nib32(type, Wg, Wu, N, K, x, T, y);
-    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    const size_t pb = mmq_planes_bytes(type, N, (int)K);
-    if (!grow || K % 256 || !pb || N % 32) { fail("bad type / K / N"); return MI355_ERR_ARG; }
-    if (!mmq_planes_swiglu_ok(type, type, (int)N, (int)K, (int)T)) { fail("shape does not take the SwiGLU launch (set mmq_tiles = 4 to force it)"); return MI355_ERR_ARG; }
-    DevBuf wsrc(grow * N), wdev(drow * N), pg(pb), pu(pb), dx((size_t)K * T * 4), dy((size_t)N * T * 4);
-    ActBufs ab((size_t)K, (size_t)T);
-    if (!wsrc.p || !wdev.p || !pg.p || !pu.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        if (!wsrc.up(i ? Wu : Wg, grow * N)) { fail("device copy failed"); return MI355_ERR_OOM; }
-        e = launch_repack_rows(type, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, N, nullptr);
-        if (e == hipSuccess) e = launch_mmq_expand(type, wdev.as<uint8_t>(), drow, (int)N, (int)K, (i ? pu : pg).as<uint8_t>(), nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
-    if (e == hipSuccess) e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, true, false, nullptr);
-    if (e == hipSuccess) e = launch_mmq_planes_swiglu(type, pg.as<uint8_t>(), pu.as<uint8_t>(), (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "ffn_gate_up");
-    return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-}  // extern "C"
-
-namespace {
-int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y, int32_t *isum, int32_t *msum) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    // the K-quants, IQ4_XS, TQ1_0 and TQ2_0: whole 256-blocks; the 32-element formats and f16 take any whole number of 32-element blocks
-    if (!grow || K <= 0 || ((act_is_q80(type) || type == T_F16) ? K % 32 : K % 256)) { fail("bad type / K"); return MI355_ERR_ARG; }
-    DevBuf wsrc(grow * N), wdev(drow * N), dx((size_t)K * T * 4), dy((size_t)N * T * 4), dres(resid ? (size_t)N * T * 4 : 16);
-    ActBufs ab((size_t)K, (size_t)T);
-    if (!wsrc.up(W, grow * N) || !wdev.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !ab.ok() || !dres.p || (resid && !dres.up(resid, (size_t)N * T * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    const float *rs = resid ? dres.as<float>() : nullptr;
-    hipError_t e = launch_repack_rows(type, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, N, nullptr);
-    if (e != hipSuccess) return hip_fail(e, "repack");
-    const bool quant = type_is_quant(type);
-    if (resid && !(quant && ((mmq_q80_applicable(type, (int)K, (int)T)) || (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes)))) {
-        fail("resid: only the Q8_0 prompt kernel's launches take one here"); return MI355_ERR_ARG;
-    }
-    if (quant) {
-        e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, !act_is_q80(type), act_is_q80(type), nullptr);
-        if (e != hipSuccess) return hip_fail(e, "quantize");
-        if (mmq_q80_applicable(type, (int)K, (int)T)) {
-            e = launch_mmq_q80(wdev.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, rs, nullptr);
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (e != hipSuccess) return hip_fail(e, "mmq_q80");
-        } else
-        if (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes) {   // Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4 prompt batches: exact Q8_0-layout copy
-            DevBuf cp(mmq_q80_copy_bytes(type, N, (int)K));
-            if (!cp.p) return MI355_ERR_OOM;
-            e = launch_expand_q80_copy(type, wdev.as<uint8_t>(), drow, (int)N, (int)K, cp.as<uint8_t>(), nullptr);
-            if (e == hipSuccess) e = launch_mmq_q80(cp.as<uint8_t>(), mmq_q80_copy_row_bytes(type, (int)K), (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, rs, nullptr, mmq_q80_copy_form(type));
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (e != hipSuccess) return hip_fail(e, "mmq_q80 (copy)");
-        } else
-        if (g_op_mmq_ksplit && mmq_ksplit_applicable(type, (int)K, (int)T)) {
-            DevBuf bh(mmq_prep_bytes((int)K, (int)T)), bl(mmq_prep_bytes((int)K, (int)T));
-            if (!bh.p || !bl.p) return MI355_ERR_OOM;
-            e = launch_mmq_prep(ab.q, (int)K, (int)T, bh.as<int8_t>(), bl.as<int8_t>(), nullptr);
-            if (e == hipSuccess) e = launch_mmq_ksplit(type, wdev.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, bh.as<int8_t>(), bl.as<int8_t>(), dy.as<float>(), (int)N, nullptr, nullptr);
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (e != hipSuccess) return hip_fail(e, "mmq_ksplit");
-        } else
-        if (mmq_applicable(type, (int)K, (int)T) || (type_is_planes_only(type) && T >= 32 && g_op_mmq_planes)) {   // (Q2_K / Q3_K / IQ4_XS / TQ1_0 / TQ2_0: planes only)
-            DevBuf bh(mmq_prep_bytes((int)K, (int)T)), bl(mmq_prep_bytes((int)K, (int)T));
-            if (!bh.p || !bl.p) return MI355_ERR_OOM;
-            e = launch_mmq_prep(ab.q, (int)K, (int)T, bh.as<int8_t>(), bl.as<int8_t>(), nullptr);
-            if (g_op_mmq_planes) {
-                DevBuf pl(mmq_planes_bytes(type, N, (int)K));
-                if (!pl.p) return MI355_ERR_OOM;
-                if (e == hipSuccess) e = launch_mmq_expand(type, wdev.as<uint8_t>(), drow, (int)N, (int)K, pl.as<uint8_t>(), nullptr);
-                // K-split partial sums: only tensors with few rows split (a large N x T never does, and gets no workspace)
-                const size_t ws_bytes = (size_t)4 * T * N * sizeof(float) <= ((size_t)256 << 20) ? (size_t)4 * T * N * sizeof(float) : 0;
-                DevBuf wsb(ws_bytes ? ws_bytes : 16);
-                if (!wsb.p) return MI355_ERR_OOM;
-                MMQWorkspace wsp; wsp.p = ws_bytes ? wsb.as<float>() : nullptr; wsp.bytes = ws_bytes;
-                if (e == hipSuccess) e = launch_mmq_planes(type, pl.as<uint8_t>(), (int)N, (int)K, (int)T, ab.q, bh.as<int8_t>(), bl.as<int8_t>(), dy.as<float>(), (int)N, nullptr, nullptr, wsp);
-                if (e == hipSuccess) e = hipDeviceSynchronize();
-                if (e == hipSuccess) e = hipDeviceSynchronize();
-            } else
-            if (e == hipSuccess) e = launch_mmq(type, wdev.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, bh.as<int8_t>(), bl.as<int8_t>(), dy.as<float>(), (int)N, nullptr, nullptr);
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (e != hipSuccess) return hip_fail(e, "mmq");
-        } else
-        for (int64_t t0 = 0; t0 < T;) {
-            const int64_t rem = T - t0;
-            const int nt = rem >= 16 ? 16 : rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1;
-            MMVQArgs a{};
-            a.n_seg = 1; a.K = (int)K; a.T = nt; a.epi = EPI_STORE;
-            a.seg[0].W = wdev.as<uint8_t>(); a.seg[0].out = dy.as<float>() + t0 * N; a.seg[0].type = type; a.seg[0].n_rows = (int)N;
-            a.seg[0].ld_out = (int)N; a.seg[0].row_bytes = drow;
-            a.aq = ab.q.qs + t0 * K; a.ad = ab.q.d + t0 * (K / 256); a.abs = ab.q.bsums + t0 * (K / 16);
-            a.aq0 = ab.q.qs0 + t0 * K; a.ad0 = ab.q.d0 + t0 * (K / 32);
-            // Q4_1 / Q5_1 / MXFP4, one token: quantised in the mat-vec's prologue, as a decode step's ffn_down and head are - the weight stream takes Q8_0-activation
-            // types only in that form (row pairs, single rows), the register ring with "mmvq_stream" 0; the same blocks, so the same result
-            if (nt == 1 && (nib32_has_min(type) || nib32_has_e8(type)) && (K % 256) == 0) { a.fuse_mode = 2; a.nx = dx.as<float>() + t0 * K; }
-            e = launch_mmvq(a, nullptr);
-            if (e != hipSuccess) return hip_fail(e, "mmvq");
-            t0 += nt;
-        }
-        if (isum && msum) {
-            const int64_t nblk = act_is_q80(type) ? K / 32 : K / 256;
-            DevBuf di((size_t)N * nblk * 4), dm((size_t)N * nblk * 4);
-            for (int64_t t = 0; t < T; t++) {
-                MMVQArgs a{};
-                a.n_seg = 1; a.K = (int)K; a.T = 1; a.epi = EPI_STORE;
-                a.seg[0].W = wdev.as<uint8_t>(); a.seg[0].type = type; a.seg[0].n_rows = (int)N; a.seg[0].row_bytes = drow;
-                a.aq = ab.q.qs + t * K; a.ad = ab.q.d + t * (K / 256); a.abs = ab.q.bsums + t * (K / 16);
-                a.aq0 = ab.q.qs0 + t * K; a.ad0 = ab.q.d0 + t * (K / 32);
-                e = launch_mmvq_ints(a, di.as<int32_t>(), dm.as<int32_t>(), nullptr);
-                if (e == hipSuccess) e = hipDeviceSynchronize();
-                if (e != hipSuccess) return hip_fail(e, "mmvq_ints");
-                di.down(isum + t * N * nblk, (size_t)N * nblk * 4);
-                dm.down(msum + t * N * nblk, (size_t)N * nblk * 4);
-            }
-        }
-    } else {
-        if (type == T_BF16) {
-            // (the model path's choice for a bf16 tensor: the rows rounded to bf16 once, then the matrix cores from 8 tokens on, else the weight stream)
-            DevBuf xb((size_t)K * T * 2);
-            if (!xb.p) return MI355_ERR_OOM;
-            e = launch_f32_to_bf16(dx.as<float>(), xb.p, (size_t)K * T, nullptr);
-            if (e == hipSuccess) {
-                if (mmbf16_applicable(type, (int)N, (int)K, (int)T, wdev.p, xb.p, dy.p) && (N & 3) == 0)
-                    e = launch_mmbf16(wdev.as<uint8_t>(), (int)N, (int)K, xb.p, (int)T, dy.as<float>(), (int)N, nullptr, nullptr, 1.0f, false, nullptr);
-                else {
-                    MMVBF16Args a{};
-                    a.n_seg = 1; a.K = (int)K; a.epi = EPI_STORE; a.xb = xb.as<uint16_t>();
-                    a.seg[0] = MMVBF16Seg{wdev.as<uint8_t>(), dy.as<float>(), nullptr, (int)N, (int)N, drow};
-                    e = launch_mmv_bf16_tokens(a, (int)T, nullptr);
-                }
-            }
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (e != hipSuccess) return hip_fail(e, "mul_mat (bf16)");
-        } else
-        // (the model path's choice: batches against f16 tensors on the matrix cores, everything else one wave per row and token)
-        if (mmf16_applicable(type, (int)N, (int)K, (int)T, wdev.p, dx.p, dy.p) && (N & 3) == 0)
-            e = launch_mmf16(wdev.as<uint8_t>(), (int)N, (int)K, dx.as<float>(), (int)T, dy.as<float>(), (int)N, nullptr, nullptr);
-        else
-            e = launch_mmv_float(type, wdev.as<uint8_t>(), (int)N, (int)K, dx.as<float>(), (int)T, dy.as<float>(), (int)N, nullptr, nullptr);
-        if (e != hipSuccess) return hip_fail(e, "mmv_float");
-    }
-    e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "mul_mat");
-    return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-// ffn_gate | ffn_up of a Q4_1 / Q5_1 / MXFP4 layer with SwiGLU, as Context::ffn_gate_up runs them: prompt batches through the two tensors' Q8_0-layout copies
-// and the SwiGLU pass ("mmq_planes" 1, T >= 32), else the mat-vec with SwiGLU in its epilogue in chunks of 16, 8, 4, 2, 1 tokens
-int op_ffn_gate_up_nib32(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) {
-    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    if (!grow || K <= 0 || K % 32 || N <= 0 || T <= 0) { fail("bad type / K"); return MI355_ERR_ARG; }
-    DevBuf wsrc(grow * N), wg(drow * N), wu(drow * N), dx((size_t)K * T * 4), dy((size_t)N * T * 4), du((size_t)N * T * 4);
-    ActBufs ab((size_t)K, (size_t)T);
-    if (!wsrc.p || !wg.p || !wu.p || !dx.up(x, (size_t)K * T * 4) || !dy.p || !du.p || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        if (!wsrc.up(i ? Wu : Wg, grow * N)) { fail("device copy failed"); return MI355_ERR_OOM; }
-        e = launch_repack_rows(type, wsrc.as<uint8_t>(), (i ? wu : wg).as<uint8_t>(), K, N, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
-    if (type == T_F16) {                                          // (Context::ffn_dense_gate_up's float branch: two products, then SwiGLU)
-        for (int i = 0; i < 2 && e == hipSuccess; i++) {
-            const uint8_t *w = (i ? wu : wg).as<uint8_t>();
-            float *o = (i ? du : dy).as<float>();
-            if (mmf16_applicable(type, (int)N, (int)K, (int)T, w, dx.p, o) && (N & 3) == 0) e = launch_mmf16(w, (int)N, (int)K, dx.as<float>(), (int)T, o, (int)N, nullptr, nullptr);
-            else e = launch_mmv_float(type, w, (int)N, (int)K, dx.as<float>(), (int)T, o, (int)N, nullptr, nullptr);
-        }
-        if (e == hipSuccess) e = launch_swiglu(dy.as<float>(), du.as<float>(), dy.as<float>(), N * T, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) return hip_fail(e, "ffn_gate_up (f16)");
-        return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
-    }
-    if (e == hipSuccess) e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, false, true, nullptr);
-    if (e != hipSuccess) return hip_fail(e, "ffn_gate_up (set-up)");
-    if (type == T_Q8_0 && mmq_q80_applicable(type, (int)K, (int)T)) {      // the prompt kernel on the weights themselves
-        e = launch_mmq_q80(wg.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, nullptr, nullptr);
-        if (e == hipSuccess) e = launch_mmq_q80(wu.as<uint8_t>(), drow, (int)N, (int)K, (int)T, ab.q, du.as<float>(), (int)N, nullptr, nullptr);
-        if (e == hipSuccess) e = launch_swiglu(dy.as<float>(), du.as<float>(), dy.as<float>(), N * T, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    } else
-    if (type != T_Q8_0 && g_op_mmq_planes && mmq_q80_applicable(T_Q8_0, (int)K, (int)T)) {
-        const size_t cb = mmq_q80_copy_bytes(type, N, (int)K), crow = mmq_q80_copy_row_bytes(type, (int)K);
-        DevBuf cg(cb), cu(cb);
-        if (!cg.p || !cu.p) return MI355_ERR_OOM;
-        e = launch_expand_q80_copy(type, wg.as<uint8_t>(), drow, (int)N, (int)K, cg.as<uint8_t>(), nullptr);
-        if (e == hipSuccess) e = launch_expand_q80_copy(type, wu.as<uint8_t>(), drow, (int)N, (int)K, cu.as<uint8_t>(), nullptr);
-        if (e == hipSuccess) e = launch_mmq_q80(cg.as<uint8_t>(), crow, (int)N, (int)K, (int)T, ab.q, dy.as<float>(), (int)N, nullptr, nullptr, mmq_q80_copy_form(type));
-        if (e == hipSuccess) e = launch_mmq_q80(cu.as<uint8_t>(), crow, (int)N, (int)K, (int)T, ab.q, du.as<float>(), (int)N, nullptr, nullptr, mmq_q80_copy_form(type));
-        if (e == hipSuccess) e = launch_swiglu(dy.as<float>(), du.as<float>(), dy.as<float>(), N * T, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    } else {
-        for (int64_t t0 = 0; t0 < T && e == hipSuccess;) {
-            const int64_t rem = T - t0;
-            const int nt = rem >= 16 ? 16 : rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1;
-            MMVQArgs a{};
-            a.n_seg = 2; a.K = (int)K; a.T = nt; a.epi = EPI_SWIGLU;
-            for (int i = 0; i < 2; i++) {
-                a.seg[i].W = (i ? wu : wg).as<uint8_t>(); a.seg[i].out = (i ? du : dy).as<float>() + t0 * N; a.seg[i].type = type; a.seg[i].n_rows = (int)N;
-                a.seg[i].ld_out = (int)N; a.seg[i].row_bytes = drow;
-            }
-            a.aq0 = ab.q.qs0 + t0 * K; a.ad0 = ab.q.d0 + t0 * (K / 32);
-            e = launch_mmvq(a, nullptr);
-            t0 += nt;
-        }
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
-    if (e != hipSuccess) return hip_fail(e, "ffn_gate_up");
-    return dy.down(y, (size_t)N * T * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-}  // namespace
-
-extern "C" {
-
-int mi355_op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, float *y, int32_t *isum, int32_t *msum) {
-    return op_mul_mat(type, W, N, K, x, T, nullptr, y, isum, msum);
-}
-int mi355_op_mul_mat_add(int32_t type, const void *W, int64_t N, int64_t K, const float *x, int64_t T, const float *resid, float *y) {
-    if (!resid) { fail("mul_mat_add: resid is null"); return MI355_ERR_ARG; }
-    return op_mul_mat(type, W, N, K, x, T, resid, y, nullptr, nullptr);
-}
-
-// One token's mat-vec with the activation made in the launch's prologue, as a decode step's launches take it: norm_w set - RMSNorm(x) * norm_w, then Q8_0
-// (fuse mode 1: Q | K | V, ffn_gate | ffn_up, the head); norm_w null - Q8_0 of x (mode 2: ffn_down).  The 32-element weight formats, K any multiple of 32 up
-// to 8192.  The result has the bits of the quantiser's launch followed by mi355_op_mul_mat's.
-int mi355_op_mul_mat_fused(int32_t type, const void *W, int64_t N, int64_t K, const float *x, const float *norm_w, float eps, float *y) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    if (!act_is_q80(type) || !grow || !W || !x || !y || N <= 0 || K <= 0 || K % 32 || K > 8192) { fail("bad type / K"); return MI355_ERR_ARG; }
-    DevBuf wsrc(grow * N), wdev(drow * N), dx((size_t)K * 4), dw((size_t)K * 4), dy((size_t)N * 4);
-    if (!wsrc.up(W, grow * N) || !wdev.p || !dx.up(x, (size_t)K * 4) || !dw.p || !dy.p || (norm_w && !dw.up(norm_w, (size_t)K * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_repack_rows(type, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, N, nullptr);
-    MMVQArgs a{};
-    a.n_seg = 1; a.K = (int)K; a.T = 1; a.epi = EPI_STORE;
-    a.seg[0].W = wdev.as<uint8_t>(); a.seg[0].out = dy.as<float>(); a.seg[0].type = type; a.seg[0].n_rows = (int)N; a.seg[0].ld_out = (int)N; a.seg[0].row_bytes = drow;
-    a.fuse_mode = norm_w ? 1 : 2; a.nx = dx.as<float>(); a.nw = norm_w ? dw.as<float>() : nullptr; a.neps = eps;
-    if (e == hipSuccess) e = launch_mmvq(a, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "mul_mat_fused");
-    return dy.down(y, (size_t)N * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-// A decode step's mat-vec launch as the model issues it (make_seg / single_token_desc / mmvq_tokens of host/runtime.cc): up to three weight tensors over one
-// activation, the epilogue, the prologue, the host copy, the selected-experts form.  Every output buffer is 0xFF bytes before the launch and comes back whole.
-int mi355_op_mat_vec_step(int32_t n_seg, const int32_t *types, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, int32_t epi,
-                          const float *resid, int32_t fuse, const float *norm_w, float eps, int32_t want_host_copy, int32_t n_sel, int32_t n_expert,
-                          const int32_t *expert_ids, int64_t ld_pad, float *const *y, float *y_host, int32_t *path) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    const bool sel = n_sel > 0;
-    if (n_seg < 1 || n_seg > 3 || !types || !W || !N || !x || !y || !path || K <= 0 || T < 1 || T > 17 || ld_pad < 0 || ld_pad > 64 || fuse < 0 || fuse > 2 ||
-        (epi != EPI_STORE && epi != EPI_ADD && epi != EPI_SWIGLU) || (epi == EPI_ADD && (n_seg != 1 || !resid)) || (epi == EPI_SWIGLU && (n_seg != 2 || N[0] != N[1])) ||
-        (fuse != 0 && T != 1) || (fuse == 1 && !norm_w) || (want_host_copy && (!y_host || T != 1)) ||
-        (sel && (n_sel < 2 || n_sel > 8 || n_expert < 1 || !expert_ids || T != 1 || epi == EPI_ADD || want_host_copy || (epi == EPI_SWIGLU ? 1 : n_seg) != 1))) {
-        fail("mat_vec_step: bad arguments"); return MI355_ERR_ARG;
-    }
-    for (int j = 0; j < n_sel; j++) if (expert_ids[j] < 0 || expert_ids[j] >= n_expert) { fail("mat_vec_step: expert id out of range"); return MI355_ERR_ARG; }
-    const int64_t NE = sel ? n_expert : 1;
-    const int64_t R = sel ? n_sel : T;                            // rows of every out buffer
-    const int64_t XR = sel && fuse == 2 ? n_sel : T;              // rows of x: the selected experts' ffn_down quantises one row per expert
-    bool need_q8k = false, need_q80 = false;
-    std::vector<std::unique_ptr<DevBuf>> dw, dy;
-    std::vector<DevTensor> wt((size_t)n_seg);
-    for (int s = 0; s < n_seg; s++) {
-        const size_t grow = ggml_row_bytes(types[s], K), drow = dev_row_bytes(types[s], K);
-        if (!type_is_quant(types[s]) || !grow || N[s] < 1 || !W[s] || (!y[s] && !(epi == EPI_SWIGLU && s == 1)) || ((act_is_q80(types[s]) ? K % 32 : K % 256) != 0)) { fail("mat_vec_step: bad segment"); return MI355_ERR_ARG; }
-        (act_is_q80(types[s]) ? need_q80 : need_q8k) = true;
-        const int64_t rows = N[s] * NE;
-        DevBuf wsrc(grow * rows);
-        dw.emplace_back(new DevBuf(drow * rows));
-        dy.emplace_back(new DevBuf((size_t)R * (N[s] + ld_pad) * 4));
-        if (!wsrc.up(W[s], grow * rows) || !dw.back()->p || !dy.back()->p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-        hipError_t e = launch_repack_rows(types[s], wsrc.as<uint8_t>(), dw.back()->as<uint8_t>(), K, rows, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemset(dy.back()->p, 0xFF, (size_t)R * (N[s] + ld_pad) * 4);
-        if (e != hipSuccess) return hip_fail(e, "mat_vec_step (set-up)");
-        DevTensor &w = wt[(size_t)s];
-        w.type = types[s]; w.K = K; w.N = N[s]; w.n_expert = NE; w.data = dw.back()->as<uint8_t>(); w.row_bytes = drow; w.bytes = drow * (size_t)rows;
-    }
-    const int64_t ld0 = N[0] + ld_pad;
-    DevBuf dx((size_t)K * XR * 4), dnw((size_t)K * 4), dres(resid ? (size_t)R * ld0 * 4 : 16), dids(sel ? (size_t)n_sel * 4 : 16);
-    ActBufs ab((size_t)K, (size_t)T);
-    if (!dx.up(x, (size_t)K * XR * 4) || !dnw.p || (norm_w && !dnw.up(norm_w, (size_t)K * 4)) || !dres.p || (resid && !dres.up(resid, (size_t)R * ld0 * 4)) || !dids.p ||
-        (sel && !dids.up(expert_ids, (size_t)n_sel * 4)) || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    float *host = nullptr;
-    if (want_host_copy) {
-        if (hipHostMalloc((void **)&host, (size_t)N[0] * 4, hipHostMallocDefault) != hipSuccess) { fail("pinned alloc failed"); return MI355_ERR_OOM; }
-        memset(host, 0xFF, (size_t)N[0] * 4);
-    }
-    hipDeviceProp_t prop;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) set_num_cu(prop.multiProcessorCount);
-    unsigned *ew = install_stream_error_word();
-    hipError_t e = hipSuccess;
-    if (fuse == 0) e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, need_q8k, need_q80, nullptr);
-    MMVQTrace trace;
-    const int32_t *esel = sel ? dids.as<int32_t>() : nullptr;
-    MMVQSeg segs[3];
-    for (int s = 0; s < n_seg; s++) segs[s] = make_seg(wt[(size_t)s], dy[(size_t)s]->as<float>(), (int)(N[s] + ld_pad), s == 0 && resid ? dres.as<float>() : nullptr, esel);
-    if (e == hipSuccess) {
-        if (sel) {                                                // (the two descriptions of Context::moe_selected_desc)
-            MMVQArgs a = single_token_desc(n_seg, (int)K, epi, fuse, fuse ? dx.as<float>() : nullptr, fuse == 1 ? dnw.as<float>() : nullptr, fuse == 1 ? eps : 0.0f, ab.q);
-            a.n_sel = n_sel; a.sel_out_stride = (int)ld0;
-            if (fuse == 2) a.sel_nx_stride = (int)K;
-            for (int s = 0; s < n_seg; s++) a.seg[s] = segs[s];
-            trace.note(a);
-            e = launch_mmvq(a, nullptr);
-        } else {
-            Fuse fz;
-            fz.mode = fuse; fz.x = fuse ? dx.as<float>() : nullptr; fz.w = fuse == 1 ? dnw.as<float>() : nullptr; fz.eps = eps; fz.out_host = host;
-            e = mmvq_tokens(segs, n_seg, (int)K, (int)T, epi, ab.q, nullptr, fz, &trace);
-        }
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    int rc = MI355_OK;
-    if (e != hipSuccess) rc = hip_fail(e, "mat_vec_step");
-    if (rc == MI355_OK && ew && __atomic_exchange_n(ew, 0u, __ATOMIC_RELAXED)) { fail("mat_vec_step: a weight-stream kernel raised the stream error word"); rc = MI355_ERR_HIP; }
-    for (int i = 0; i < 40; i++) path[i] = 0;
-    for (size_t i = 0; i < trace.recs.size() && i < 5; i++) {
-        const MMVQTrace::Rec &r = trace.recs[i];
-        int32_t *p = path + i * 8;
-        p[0] = r.T; p[1] = r.kernel;
-        if (r.kernel == MMVQ_KERNEL_STREAM) { p[2] = r.form.role; p[3] = r.form.kb; p[4] = r.form.fast_ok; p[5] = r.form.down_early; p[6] = r.form.moe; p[7] = r.form.ternary; }
-    }
-    const int n_out = epi == EPI_SWIGLU ? 1 : n_seg;
-    for (int s = 0; s < n_out && rc == MI355_OK; s++)
-        if (!dy[(size_t)s]->down(y[s], (size_t)R * (N[s] + ld_pad) * 4)) rc = MI355_ERR_HIP;
-    if (host) {
-        if (rc == MI355_OK) memcpy(y_host, host, (size_t)N[0] * 4);
-        (void)hipHostFree(host);
-    }
-    return rc;
-}
-
-// One mat-mul launch of a dense prompt batch or a batched decode step as the model issues it (Context::linear, linear_multi and the gate | up block of
-// host/runtime.cc): the producer of the activation and of its bh / bl planes, the launcher, the epilogue, the residual in place.  Every out buffer is 0xFF bytes
-// before the launch and comes back whole; a refused launch leaves them so and launches nothing.
-int mi355_op_prompt_mul_mat(int32_t n_seg, const int32_t *types, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, int32_t epi,
-                            const float *resid, int32_t in_place, int32_t prologue, const float *norm_w, float eps, int32_t form, int64_t ld_pad,
-                            float *const *y, int32_t *path) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n_seg < 1 || n_seg > 3 || !types || !W || !N || !x || !y || !path || K <= 0 || K % 256 || K > 65536 || T < 3 || T > 600 || ld_pad < 0 || ld_pad > 64) {
-        fail("prompt_mul_mat: bad arguments"); return MI355_ERR_ARG;
-    }
-    const int n_out = epi == EPI_SWIGLU ? 1 : n_seg;
-    for (int s = 0; s < n_seg; s++) if (N[s] < 1 || N[s] > (1 << 20) || !W[s] || (s < n_out && !y[s])) { fail("prompt_mul_mat: bad segment"); return MI355_ERR_ARG; }
-    for (int i = 0; i < 8; i++) path[i] = 0;
-    for (int s = 0; s < n_out; s++) memset(y[s], 0xFF, (size_t)T * (N[s] + ld_pad) * 4);       // what a refusal or a failure hands back
-    auto refuse = [](const char *why) { fail(std::string("prompt_mul_mat: ") + why); return MI355_ERR_ARG; };
-    if (epi != EPI_STORE && epi != EPI_ADD && epi != EPI_SWIGLU) return refuse("epi outside 0..2");
-    if (epi == EPI_ADD && n_seg != 1) return refuse("a residual takes one tensor");
-    if (epi == EPI_ADD && !resid) return refuse("epi 1 without resid");
-    if (epi != EPI_ADD && (resid || in_place)) return refuse("resid / in_place without epi 1");
-    if (epi == EPI_SWIGLU && (n_seg != 2 || N[0] != N[1])) return refuse("the SwiGLU pair is two tensors of one N");
-    if (epi == EPI_SWIGLU && types[0] != types[1]) return refuse("the SwiGLU pair is two tensors of one type");
-    if (prologue < 0 || prologue > 3 || (prologue == 1 && !norm_w)) return refuse("bad prologue");
-    if (form < 0 || form > 3) return refuse("form outside 0..3");
-    if (form == 3 && n_seg != 1) return refuse("the expansion on the fly takes one tensor");
-    int64_t n_all = 0;
-    for (int s = 0; s < n_seg; s++) {
-        const int t = types[s];
-        const bool kq = t == T_Q4_K || t == T_Q5_K || t == T_Q6_K, small = t == T_Q2_K || t == T_Q3_K || t == T_IQ4_XS;
-        if (!kq && !(small && n_seg == 1 && (form == 0 || form == 2))) return refuse("a tensor type this launcher has no form for");
-        n_all += N[s];
-    }
-    hipDeviceProp_t prop;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) set_num_cu(prop.multiProcessorCount);
-    // ---- device copies: rows in the device layout, the plane sets back to back in one arena (forms 0 and 2), out buffers, activation, workspace
-    const bool want_planes = form == 0 || form == 2;
-    size_t arena_bytes = 0;
-    std::vector<size_t> poff((size_t)n_seg, 0);
-    for (int s = 0; s < n_seg; s++) { poff[(size_t)s] = arena_bytes; arena_bytes += mmq_planes_bytes(types[s], N[s], (int)K); }
-    DevBuf arena(want_planes ? arena_bytes : 16);
-    std::vector<std::unique_ptr<DevBuf>> dw, dy;
-    std::vector<DevTensor> wt((size_t)n_seg);
-    const size_t ws_bytes = (size_t)4 * T * n_all * sizeof(float);     // (the K-split partial sums: up to four splits of every segment)
-    DevBuf wsb(ws_bytes), dx((size_t)K * T * 4 * (prologue == 2 ? 2 : 1)), dnw((size_t)K * 4), bh(mmq_prep_bytes((int)K, (int)T)), bl(mmq_prep_bytes((int)K, (int)T));
-    ActBufs ab((size_t)K, (size_t)T);
-    if (!arena.p || !wsb.p || !dx.up(x, dx.n) || !dnw.p || (norm_w && !dnw.up(norm_w, (size_t)K * 4)) || !bh.p || !bl.p || !ab.ok() ||
-        hipMemset(bh.p, 0xFF, bh.n) != hipSuccess || hipMemset(bl.p, 0xFF, bl.n) != hipSuccess) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    for (int s = 0; s < n_seg; s++) {
-        const size_t grow = ggml_row_bytes(types[s], K), drow = dev_row_bytes(types[s], K);
-        dw.emplace_back(new DevBuf(drow * N[s]));
-        dy.emplace_back(new DevBuf((size_t)T * (N[s] + ld_pad) * 4));
-        if (!grow || !dw.back()->p || !dy.back()->p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-        DevTensor &w = wt[(size_t)s];
-        w.type = types[s]; w.K = K; w.N = N[s]; w.n_expert = 1; w.data = dw.back()->as<uint8_t>(); w.row_bytes = drow; w.bytes = drow * (size_t)N[s];
-        if (want_planes) { w.planes = arena.as<uint8_t>() + poff[(size_t)s]; w.planes_bytes = mmq_planes_bytes(types[s], N[s], (int)K); }
-    }
-    MMQWorkspace wsp; wsp.p = wsb.as<float>(); wsp.bytes = ws_bytes;
-    // ---- which launch: the model's choice (form 0), or the launcher named; what the launcher would refuse is refused here, before anything is launched
-    int rows[3], lds[3], tys[3];
-    float *outs[3];
-    const DevTensor *wp[3];
-    for (int s = 0; s < n_seg; s++) { rows[s] = (int)N[s]; lds[s] = (int)(N[s] + ld_pad); tys[s] = types[s]; outs[s] = dy[(size_t)s]->as<float>(); wp[s] = &wt[(size_t)s]; }
-    int kind = form, n_fused = n_seg;
-    bool swiglu = epi == EPI_SWIGLU;
-    if (form == 0) {
-        const PromptMatmul pm = prompt_mul_mat_choice(epi == EPI_SWIGLU ? PM_ROLE_GATE_UP : n_seg == 1 ? PM_ROLE_ONE : PM_ROLE_MULTI, wp, n_seg, (int)K, (int)T, wsp);
-        if (pm.form == PM_NONE) return refuse("the model has no MFMA launch for these tensors and this batch");
-        if (epi == EPI_SWIGLU && !pm.swiglu) return refuse("the model runs SwiGLU behind this launch, in a pass of its own");
-        kind = pm.form; n_fused = pm.n_fused;
-    }
-    MMQPlanesForm pf{};
-    if (kind == PM_KSPLIT) {
-        for (int s = 0; s < n_seg; s++) if (!mmq_ksplit_applicable(types[s], (int)K, (int)T)) return refuse("the K-split kernel does not take this type or batch");
-    } else if (kind == PM_PLANES) {
-        for (int s = 0; s < n_seg; s++) if (!mmq_applicable(types[s], (int)K, (int)T) && !(type_is_planes_only(types[s]) && T >= 32)) return refuse("the plane kernels take batches of 32 tokens and more");
-        if (swiglu) {
-            if (!mmq_planes_swiglu_ok(types[0], types[1], rows[0], (int)K, (int)T)) return refuse("launch_mmq_planes_swiglu does not take this shape");
-            pf.kernel = MMQ_PLANES_LDS; pf.n_split = 1; pf.mixed = false;
-        } else {
-            if (form == 0 && n_fused < 2) n_fused = 1;              // (no two plane sets fuse: every tensor on its own, path describes the first)
-            if (!mmq_planes_form(types[0], rows, n_fused, (int)K, (int)T, epi == EPI_ADD, wsp, tys, &pf)) return refuse("launch_mmq_planes_multi refuses these segments");
-        }
-    } else {
-        if (!mmq_applicable(types[0], (int)K, (int)T)) return refuse("launch_mmq does not take this type or batch");
-    }
-    // ---- set-up: the rows in the device layout, their plane sets, the out buffers 0xFF
-    for (int s = 0; s < n_seg; s++) {
-        const size_t grow = ggml_row_bytes(types[s], K);
-        DevTensor &w = wt[(size_t)s];
-        DevBuf wsrc(grow * N[s]);
-        if (!wsrc.up(W[s], grow * N[s])) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-        hipError_t e = launch_repack_rows(types[s], wsrc.as<uint8_t>(), w.data, K, N[s], nullptr);
-        if (e == hipSuccess && want_planes) e = launch_mmq_expand(types[s], w.data, w.row_bytes, (int)N[s], (int)K, w.planes, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemset(dy[(size_t)s]->p, 0xFF, dy[(size_t)s]->n);
-        if (e != hipSuccess) return hip_fail(e, "prompt_mul_mat (set-up)");
-    }
-    // ---- the residual: in place it sits in the out buffer, as attn_output and ffn_down have it
-    const size_t rbytes = (size_t)T * (N[0] + ld_pad) * 4;
-    DevBuf dres(epi == EPI_ADD && !in_place ? rbytes : 16);
-    const float *rs = nullptr;
-    if (epi == EPI_ADD) {
-        DevBuf &rb = in_place ? *dy[0] : dres;
-        if (!rb.up(resid, rbytes)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-        rs = rb.as<float>();
-    }
-    // ---- the activation and its block-sum planes
-    hipError_t e;
-    if (prologue == 0) {
-        e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, true, false, nullptr);
-        if (e == hipSuccess) e = launch_mmq_prep(ab.q, (int)K, (int)T, bh.as<int8_t>(), bl.as<int8_t>(), nullptr);
-    } else if (prologue == 1) e = launch_rmsnorm_quant(dx.as<float>(), dnw.as<float>(), (int)K, (int)T, eps, nullptr, &ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
-    else if (prologue == 2) e = launch_swiglu_quant(dx.as<float>(), dx.as<float>() + (size_t)T * K, (int)K, (int)T, ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
-    else e = launch_quantize(dx.as<float>(), (int)K, (int)T, ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
-    if (e != hipSuccess) return hip_fail(e, "prompt_mul_mat (activation)");
-    // ---- the launch
-    const int8_t *pbh = bh.as<int8_t>(), *pbl = bl.as<int8_t>();
-    if (kind == PM_KSPLIT) {
-        MMQSeg sg[3];
-        for (int s = 0; s < n_seg; s++) sg[s] = MMQSeg{wt[(size_t)s].data, wt[(size_t)s].row_bytes, rows[s], types[s], outs[s], lds[s], s == 0 ? rs : nullptr, 0};
-        e = launch_mmq_ksplit_multi(sg, n_seg, (int)K, (int)T, ab.q, pbh, pbl, swiglu, nullptr);
-        path[0] = 1; path[1] = mmq_ksplit_token_tiles((int)T); path[2] = 1;
-    } else if (kind == PM_PLANES && swiglu) {
-        e = launch_mmq_planes_swiglu(types[0], wt[0].planes, wt[1].planes, rows[0], (int)K, (int)T, ab.q, outs[0], lds[0], nullptr);
-        path[0] = pf.kernel; path[2] = 1;
-    } else if (kind == PM_PLANES) {
-        e = launch_mmq_planes_multi(types[0], wt[0].planes, rows, outs, lds, n_fused, (int)K, (int)T, ab.q, pbh, pbl, rs, nullptr, wsp, tys);
-        for (int s = n_fused; s < n_seg && e == hipSuccess; s++)     // (form 0: the tensors the fused launch left out, each on its plane set as Context::linear_multi runs them)
-            e = launch_mmq_planes(types[s], wt[(size_t)s].planes, rows[s], (int)K, (int)T, ab.q, pbh, pbl, outs[s], lds[s], nullptr, nullptr, wsp);
-        path[0] = pf.kernel; path[2] = pf.n_split; path[3] = pf.mixed ? 1 : 0;
-    } else {
-        e = launch_mmq(types[0], wt[0].data, wt[0].row_bytes, rows[0], (int)K, (int)T, ab.q, pbh, pbl, outs[0], lds[0], rs, nullptr);
-        path[0] = 5; path[2] = 1;
-    }
-    path[4] = swiglu ? 1 : 0; path[5] = prologue == 0 ? 1 : 0;
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "prompt_mul_mat");
-    for (int s = 0; s < n_out; s++)
-        if (!dy[(size_t)s]->down(y[s], (size_t)T * (N[s] + ld_pad) * 4)) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-// One producer of the MFMA kernels' activation, with Q8_K and the bh / bl planes as the model calls it; launch_mmq_prep's planes of the same rows beside them
-int mi355_op_act_q8k_planes(int32_t producer, const float *x, const float *x2, const float *norm_w, float eps, int64_t n, int64_t T, void *out_blocks,
-                            int8_t *out_bh, int8_t *out_bl, int8_t *prep_bh, int8_t *prep_bl, float *y_f32) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (producer < 0 || producer > 2 || !x || (producer == 1 && !norm_w) || (producer == 2 && !x2) || (producer != 1 && y_f32) || !out_blocks || !out_bh || !out_bl ||
-        !prep_bh || !prep_bl || n <= 0 || n % 256 || n > (1 << 20) || T <= 0 || T > 4096) { fail("act_q8k_planes: bad arguments"); return MI355_ERR_ARG; }
-    const size_t xb = (size_t)n * T * 4, pb = mmq_prep_bytes((int)n, (int)T), ob = ggml_row_bytes(T_Q8_K, n) * T;
-    DevBuf dx(xb), dx2(producer == 2 ? xb : 16), dw((size_t)n * 4), dyf(y_f32 ? xb : 16), dout(ob), bh(pb), bl(pb), ph(pb), pl(pb);
-    ActBufs ab((size_t)n, (size_t)T);
-    if (!dx.up(x, xb) || !dx2.p || (producer == 2 && !dx2.up(x2, xb)) || !dw.p || (producer == 1 && !dw.up(norm_w, (size_t)n * 4)) || !dyf.p || !dout.p || !bh.p || !bl.p ||
-        !ph.p || !pl.p || !ab.ok() || hipMemset(bh.p, 0xFF, pb) != hipSuccess || hipMemset(bl.p, 0xFF, pb) != hipSuccess) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e;
-    if (producer == 0) e = launch_quantize(dx.as<float>(), (int)n, (int)T, ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
-    else if (producer == 1) e = launch_rmsnorm_quant(dx.as<float>(), dw.as<float>(), (int)n, (int)T, eps, y_f32 ? dyf.as<float>() : nullptr, &ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
-    else e = launch_swiglu_quant(dx.as<float>(), dx2.as<float>(), (int)n, (int)T, ab.q, true, false, nullptr, bh.as<int8_t>(), bl.as<int8_t>());
-    if (e == hipSuccess) e = launch_mmq_prep(ab.q, (int)n, (int)T, ph.as<int8_t>(), pl.as<int8_t>(), nullptr);
-    if (e == hipSuccess) e = launch_pack_q8k_blocks(ab.q, (int)n, (int)T, dout.as<uint8_t>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "act_q8k_planes");
-    if (y_f32 && !dyf.down(y_f32, xb)) return MI355_ERR_HIP;
-    return dout.down(out_blocks, ob) && bh.down(out_bh, pb) && bl.down(out_bl, pb) && ph.down(prep_bh, pb) && pl.down(prep_bl, pb) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_f32_to_bf16(const float *x, int64_t n, uint16_t *out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n <= 0 || n % 8) { fail("f32_to_bf16: n must be a positive multiple of 8"); return MI355_ERR_ARG; }
-    DevBuf dx((size_t)n * 4), dy((size_t)n * 2);
-    if (!dx.up(x, (size_t)n * 4) || !dy.p) return MI355_ERR_OOM;
-    hipError_t e = launch_f32_to_bf16(dx.as<float>(), dy.p, (size_t)n, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "f32_to_bf16");
-    return dy.down(out, (size_t)n * 2) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_mul_mat_bf16(int32_t n_seg, const void *const *W, const int64_t *N, int64_t K, const float *x, int64_t T, const float *const *bias, const float *resid,
-                          int32_t epi, int32_t path, int32_t tokens_per_launch, int32_t use_graph, float *const *y) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n_seg < 1 || n_seg > 3 || !W || !N || !x || !y || K < 8 || K % 8 || (path == 2 && K % 16) || T < 1 || (epi != EPI_STORE && epi != EPI_ADD && epi != EPI_SWIGLU) || path < 0 || path > 2 ||
-        (epi == EPI_ADD && (n_seg != 1 || !resid)) || (epi == EPI_SWIGLU && (n_seg != 2 || N[0] != N[1])) ||
-        (tokens_per_launch != 0 && tokens_per_launch != 1 && tokens_per_launch != 2 && tokens_per_launch != 4 && tokens_per_launch != 8 && tokens_per_launch != 16)) {
-        fail("mul_mat_bf16: bad arguments"); return MI355_ERR_ARG;
-    }
-    const size_t row = (size_t)K * 2;
-    const int n_out = epi == EPI_SWIGLU ? 1 : n_seg;
-    std::vector<std::unique_ptr<DevBuf>> dw, db, dy;
-    for (int s = 0; s < n_seg; s++) {
-        if (N[s] < 1 || !W[s]) { fail("mul_mat_bf16: bad segment"); return MI355_ERR_ARG; }
-        dw.emplace_back(new DevBuf(row * (size_t)N[s]));
-        db.emplace_back(new DevBuf(bias && bias[s] ? (size_t)N[s] * 4 : 16));
-        dy.emplace_back(new DevBuf((size_t)N[s] * T * 4));
-        if (!dw.back()->up(W[s], row * (size_t)N[s]) || !dy.back()->p || !db.back()->p) return MI355_ERR_OOM;
-        if (bias && bias[s] && !db.back()->up(bias[s], (size_t)N[s] * 4)) return MI355_ERR_OOM;
-    }
-    DevBuf dx((size_t)K * T * 4), xb((size_t)K * T * 2), dr(resid ? (size_t)N[0] * T * 4 : 16);
-    if (!dx.up(x, (size_t)K * T * 4) || !xb.p || !dr.p || (resid && !dr.up(resid, (size_t)N[0] * T * 4))) return MI355_ERR_OOM;
-    hipStream_t st = nullptr;
-    if (hipStreamCreate(&st) != hipSuccess) return MI355_ERR_HIP;
-    auto run = [&]() -> hipError_t {
-        hipError_t e = launch_f32_to_bf16(dx.as<float>(), xb.p, (size_t)K * T, st);
-        if (e != hipSuccess) return e;
-        bool mfma = path == 2;
-        if (path == 0) {                                      // the model path's choice (Context::linear_bf16)
-            mfma = true;
-            for (int s = 0; s < n_seg; s++) mfma = mfma && mmbf16_applicable(T_BF16, (int)N[s], (int)K, (int)T, dw[(size_t)s]->p, xb.p, dy[(size_t)s]->p) && (N[s] & 3) == 0;
-        }
-        if (mfma) {
-            for (int s = 0; s < n_seg && e == hipSuccess; s++)
-                e = launch_mmbf16(dw[(size_t)s]->as<uint8_t>(), (int)N[s], (int)K, xb.p, (int)T, dy[(size_t)s]->as<float>(), (int)N[s], epi == EPI_ADD ? dr.as<float>() : nullptr,
-                                  bias && bias[s] ? db[(size_t)s]->as<float>() : nullptr, 1.0f, false, st);
-            if (e == hipSuccess && epi == EPI_SWIGLU) e = launch_swiglu(dy[0]->as<float>(), dy[1]->as<float>(), dy[0]->as<float>(), (int64_t)T * N[0], st);
-            return e;
-        }
-        MMVBF16Args a{};
-        a.n_seg = n_seg; a.K = (int)K; a.epi = epi; a.resid = epi == EPI_ADD ? dr.as<float>() : nullptr; a.xb = xb.as<uint16_t>();
-        for (int s = 0; s < n_seg; s++)
-            a.seg[s] = MMVBF16Seg{dw[(size_t)s]->as<uint8_t>(), dy[(size_t)s]->as<float>(), bias && bias[s] ? db[(size_t)s]->as<float>() : nullptr, (int)N[s], (int)N[s], row};
-        if (tokens_per_launch == 0) return launch_mmv_bf16_tokens(a, (int)T, st);
-        for (int64_t t0 = 0; t0 < T && e == hipSuccess; t0 += tokens_per_launch) {       // (tests: a fixed launch width; T must be a multiple of it)
-            if (T - t0 < tokens_per_launch) return hipErrorInvalidValue;
-            MMVBF16Args c = a;
-            c.T = tokens_per_launch; c.xb = a.xb + t0 * K;
-            if (a.resid) c.resid = a.resid + t0 * N[0];
-            for (int s = 0; s < n_seg; s++) c.seg[s].out = a.seg[s].out + t0 * N[s];
-            e = launch_mmv_bf16(c, st);
-        }
-        return e;
-    };
-    hipError_t e = hipSuccess;
-    if (use_graph) {                                          // captured once, replayed twice: what a decode step's graph does with these launches
-        hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
-        e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            const hipError_t er = run();
-            const hipError_t ec = hipStreamEndCapture(st, &g);
-            e = er != hipSuccess ? er : ec;
-        }
-        if (e == hipSuccess) e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-        for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipGraphLaunch(ge, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (ge) (void)hipGraphExecDestroy(ge);
-        if (g) (void)hipGraphDestroy(g);
-    } else {
-        e = run();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    (void)hipStreamDestroy(st);
-    if (e != hipSuccess) return hip_fail(e, "mul_mat_bf16");
-    for (int s = 0; s < n_out; s++)
-        if (!dy[(size_t)s]->down(y[s], (size_t)N[s] * T * 4)) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-// launch_lora_delta once: out[s][t][n] += scale[s] * B[s][n] . (A[s] x[t]) for n_seg segments over the rows x [T][K]; out[s] is [T][ld_out[s]], read and written
-// back whole (the columns beyond N[s] come back as they went in unless the kernel wrote there)
-int mi355_op_lora_delta(int32_t n_seg, const int32_t *type, const void *const *A, const void *const *B, const int32_t *r, const int64_t *N, const float *scale,
-                        const float *x, int64_t K, int64_t T, const int64_t *ld_out, float *const *out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n_seg < 1 || n_seg > 3 || !type || !A || !B || !r || !N || !scale || !x || !ld_out || !out || K < 32 || K % 32 || K > (1 << 20) || T < 1 || T > 65536) { fail("bad args"); return MI355_ERR_ARG; }
-    for (int s = 0; s < n_seg; s++)
-        if ((type[s] != T_F32 && type[s] != T_F16) || r[s] < 1 || r[s] > LORA_MAX_R || N[s] < 1 || N[s] > (1 << 24) || ld_out[s] < N[s] || !A[s] || !B[s] || !out[s]) {
-            fail("bad segment (F32 / F16 pairs, rank 1 .. 512, ld_out >= N)");
-            return MI355_ERR_ARG;
-        }
-    std::vector<std::unique_ptr<DevBuf>> bufs;
-    auto dev = [&](const void *src, size_t bytes) -> void * {
-        bufs.emplace_back(new DevBuf(bytes));
-        return bufs.back()->up(src, bytes) ? bufs.back()->p : nullptr;
-    };
-    LoraSeg segs[3];
-    float *xd = (float *)dev(x, (size_t)T * K * 4);
-    bool ok = xd != nullptr;
-    for (int s = 0; s < n_seg && ok; s++) {
-        const size_t es = type[s] == T_F16 ? 2 : 4;
-        segs[s] = LoraSeg{dev(A[s], (size_t)r[s] * K * es), dev(B[s], (size_t)N[s] * r[s] * es), type[s], r[s], (int)N[s], scale[s],
-                          (float *)dev(out[s], (size_t)T * ld_out[s] * 4), (int)ld_out[s]};
-        ok = segs[s].A && segs[s].B && segs[s].out;
-    }
-    DevBuf scratch(lora_scratch_floats((int)T) * 4);
-    if (!ok || !scratch.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_lora_delta(segs, n_seg, xd, (int)K, (int)K, (int)T, scratch.as<float>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "lora_delta");
-    for (int s = 0; s < n_seg; s++)
-        if (hipMemcpy(out[s], segs[s].out, (size_t)T * ld_out[s] * 4, hipMemcpyDeviceToHost) != hipSuccess) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-int mi355_op_rms_norm_mul(const float *x, const float *w, int64_t n, int64_t T, float eps, float *y) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n <= 0 || T <= 0 || n % 32) { fail("n must be a multiple of 32"); return MI355_ERR_ARG; }
-    DevBuf dx((size_t)n * T * 4), dw((size_t)n * 4), dy((size_t)n * T * 4);
-    if (!dx.up(x, (size_t)n * T * 4) || !dw.up(w, (size_t)n * 4) || !dy.p) return MI355_ERR_OOM;
-    hipError_t e = launch_rmsnorm_quant(dx.as<float>(), dw.as<float>(), (int)n, (int)T, eps, dy.as<float>(), nullptr, false, false, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "rms_norm");
-    return dy.down(y, (size_t)n * T * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_rope(float *x, int32_t n_head, int32_t head_dim, int32_t n_rot, const int32_t *pos, int64_t T,
-                  float freq_base, float freq_scale, const float *freq_factors, int32_t neox) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    const size_t nb = (size_t)T * n_head * head_dim * 4;
-    DevBuf dx(nb), dp((size_t)T * 4), dff(freq_factors ? (size_t)n_rot * 2 : 16);
-    if (!dx.up(x, nb) || !dp.up(pos, (size_t)T * 4)) return MI355_ERR_OOM;
-    if (freq_factors) dff.up(freq_factors, (size_t)(n_rot / 2) * 4);
-    RopeArgs ra{n_rot, freq_base, freq_scale, freq_factors ? dff.as<float>() : nullptr, neox};
-    hipError_t e = launch_rope_inplace(dx.as<float>(), (int)T, n_head, head_dim, dp.as<int32_t>(), ra, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "rope");
-    return dx.down(x, nb) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_rope_yarn(float *x, int32_t n_head, int32_t head_dim, int32_t n_rot, const int32_t *pos, int64_t T,
-                       float freq_base, float freq_scale, const float *freq_factors, int32_t neox,
-                       float ext_factor, float attn_factor, float corr_lo, float corr_hi) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    const size_t nb = (size_t)T * n_head * head_dim * 4;
-    DevBuf dx(nb), dp((size_t)T * 4), dff(freq_factors ? (size_t)n_rot * 2 : 16);
-    if (!dx.up(x, nb) || !dp.up(pos, (size_t)T * 4)) return MI355_ERR_OOM;
-    if (freq_factors) dff.up(freq_factors, (size_t)(n_rot / 2) * 4);
-    RopeArgs ra{n_rot, freq_base, freq_scale, freq_factors ? dff.as<float>() : nullptr, neox};
-    ra.ext_factor = ext_factor; ra.attn_factor = attn_factor; ra.corr_lo = corr_lo; ra.corr_hi = corr_hi;
-    hipError_t e = launch_rope_inplace(dx.as<float>(), (int)T, n_head, head_dim, dp.as<int32_t>(), ra, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "rope_yarn");
-    return dx.down(x, nb) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_get_rows(int32_t type, const void *table, int64_t K, int64_t n_rows, const int32_t *ids, int64_t n_ids, float *dst) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    if (!grow) return MI355_ERR_ARG;
-    DevBuf src(grow * n_rows), dev(drow * n_rows), di((size_t)n_ids * 4), dd((size_t)n_ids * K * 4);
-    if (!src.up(table, grow * n_rows) || !dev.p || !di.up(ids, (size_t)n_ids * 4) || !dd.p) return MI355_ERR_OOM;
-    hipError_t e = launch_repack_rows(type, src.as<uint8_t>(), dev.as<uint8_t>(), K, n_rows, nullptr);
-    if (e == hipSuccess) e = launch_get_rows(type, dev.as<uint8_t>(), K, di.as<int32_t>(), (int)n_ids, dd.as<float>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "get_rows");
-    return dd.down(dst, (size_t)n_ids * K * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_repack_rows(int32_t type, const void *src_rows, int64_t K, int64_t n_rows, void *dst) {
-    const int be = ggml_block_elems(type);
-    if (be == 0 || K <= 0 || n_rows <= 0 || K % be) return MI355_ERR_ARG;
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    DevBuf src(grow * n_rows), dev(drow * n_rows);
-    if (!src.up(src_rows, grow * n_rows) || !dev.p) return MI355_ERR_OOM;
-    hipError_t e = hipMemset(dev.p, Q80_GUARD, drow * n_rows);
-    if (e == hipSuccess) e = launch_repack_rows(type, src.as<uint8_t>(), dev.as<uint8_t>(), K, n_rows, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "repack_rows");
-    return dev.down(dst, drow * n_rows) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_swiglu(const float *gate, const float *up, int64_t n, float *y) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    DevBuf g((size_t)n * 4), u((size_t)n * 4), o((size_t)n * 4);
-    if (!g.up(gate, (size_t)n * 4) || !u.up(up, (size_t)n * 4) || !o.p) return MI355_ERR_OOM;
-    hipError_t e = launch_swiglu(g.as<float>(), u.as<float>(), o.as<float>(), n, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "swiglu");
-    return o.down(y, (size_t)n * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_soft_max(const float *x, const float *mask, int64_t n, int64_t rows, float scale, float *y) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    const size_t nb = (size_t)n * rows * 4;
-    DevBuf dx(nb), dm(nb), dy(nb);
-    if (!dx.up(x, nb) || !dy.p) return MI355_ERR_OOM;
-    if (mask) dm.up(mask, nb);
-    hipError_t e = launch_soft_max(dx.as<float>(), mask ? dm.as<float>() : nullptr, dy.as<float>(), (int)n, (int)rows, scale, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "soft_max");
-    return dy.down(y, nb) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_moe_route(const float *logits, int64_t T, int32_t n_expert, int32_t k, int32_t *ids, float *w) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (T <= 0 || n_expert <= 0 || n_expert > 256 || k <= 0 || k > 64 || k > n_expert) { fail("moe_route: bad shape"); return MI355_ERR_ARG; }
-    DevBuf dl((size_t)T * n_expert * 4), di((size_t)T * k * 4), dw((size_t)T * k * 4);
-    if (!dl.up(logits, (size_t)T * n_expert * 4) || !di.p || !dw.p) return MI355_ERR_OOM;
-    hipError_t e = launch_moe_route(dl.as<float>(), (int)T, n_expert, k, di.as<int32_t>(), dw.as<float>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "moe_route");
-    return di.down(ids, (size_t)T * k * 4) && dw.down(w, (size_t)T * k * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_moe_router(int32_t type, const void *gate_inp, int32_t n_expert, int64_t K, const float *x, int64_t T, int32_t k, int32_t fused,
-                        const int32_t *forced, float *logits, int32_t *ids, float *w) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if ((type != T_F32 && type != T_F16) || T <= 0 || K <= 0 || n_expert <= 0 || n_expert > 256 || k <= 0 || k > 64 || k > n_expert) {
-        fail("moe_router: bad type or shape"); return MI355_ERR_ARG;
-    }
-    const size_t wb = (size_t)n_expert * K * (type == T_F32 ? 4 : 2), nl = (size_t)T * n_expert * 4, ns = (size_t)T * k * 4;
-    DevBuf dW(wb), dx((size_t)T * K * 4), dl(nl), di(ns), dw(ns), df(forced ? ns : 16);
-    if (!dW.up(gate_inp, wb) || !dx.up(x, (size_t)T * K * 4) || !dl.p || !di.p || !dw.p) return MI355_ERR_OOM;
-    if (forced && !df.up(forced, ns)) return MI355_ERR_OOM;
-    const int32_t *fd = forced ? df.as<int32_t>() : nullptr;
-    // fused: the one-launch router the single-token and prompt steps take for f32 / f16 gate_inp; else mmv_float, then the selection on its logits
-    hipError_t e = fused ? launch_moe_router(type, dW.as<uint8_t>(), n_expert, (int)K, dx.as<float>(), (int)T, k, dl.as<float>(), di.as<int32_t>(), dw.as<float>(), nullptr, fd)
-                         : launch_mmv_float(type, dW.as<uint8_t>(), n_expert, (int)K, dx.as<float>(), (int)T, dl.as<float>(), n_expert, nullptr, nullptr);
-    if (!fused && e == hipSuccess) e = launch_moe_route(dl.as<float>(), (int)T, n_expert, k, di.as<int32_t>(), dw.as<float>(), nullptr, fd);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "moe_router");
-    if (logits && !dl.down(logits, nl)) return MI355_ERR_HIP;
-    return di.down(ids, ns) && dw.down(w, ns) ? MI355_OK : MI355_ERR_HIP;
-}
-
-// ---- the kernels that produce indices (csrc/misc.hip), one test entry each
-int mi355_op_argmax_rows(const float *x, int64_t n, const int32_t *launches, int32_t n_launch, int32_t cap_rows, int32_t *out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n < 1 || n > INT32_MAX || n_launch < 1 || cap_rows < 1 || cap_rows > 65535) { fail("argmax_rows: bad shape"); return MI355_ERR_ARG; }
-    size_t rows = 0;
-    for (int i = 0; i < n_launch; i++) {
-        if (launches[i] < 1 || launches[i] > cap_rows) { fail("argmax_rows: launch " + std::to_string(i) + " outside [1, cap_rows]"); return MI355_ERR_ARG; }
-        rows += (size_t)launches[i];
-    }
-    DevBuf dx(rows * (size_t)n * 4), dout(rows * 4), ds((size_t)cap_rows * 129 * 4);      // (DevBuf zero-fills: the ticket words start at 0, once)
-    if (!dx.up(x, rows * (size_t)n * 4) || !dout.p || !ds.p) return MI355_ERR_OOM;
-    hipError_t e = hipSuccess;
-    size_t r0 = 0;
-    for (int i = 0; i < n_launch && e == hipSuccess; i++) {                               // back to back on one scratch: no synchronisation in between
-        e = launch_argmax_rows(dx.as<float>() + r0 * (size_t)n, (int)n, launches[i], dout.as<int32_t>() + r0, ds.as<float>(), cap_rows, nullptr);
-        r0 += (size_t)launches[i];
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "argmax_rows");
-    return dout.down(out, rows * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_argmax_prob_rows(const float *x, int64_t n, int32_t rows, int32_t *idx_out, float *p_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!x || !idx_out || !p_out || n < 1 || n > SPEC_MAX_N || rows < 1 || rows > 65535) { fail("argmax_prob_rows: bad shape"); return MI355_ERR_ARG; }
-    const size_t nb = (size_t)rows * (size_t)n * 4;
-    DevBuf dx(nb), di((size_t)rows * 4), dp((size_t)rows * 4), ds(argmax_prob_scratch_words(rows) * 4);
-    if (!dx.up(x, nb) || !di.p || !dp.p || !ds.p) return MI355_ERR_OOM;
-    hipError_t e = launch_argmax_prob_rows(dx.as<float>(), (int)n, nullptr, rows, di.as<int32_t>(), dp.as<float>(), ds.as<float>(), rows, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "argmax_prob_rows");
-    return di.down(idx_out, (size_t)rows * 4) && dp.down(p_out, (size_t)rows * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t R, const int32_t *group_start, int32_t G,
-                         const int32_t *draft, int32_t *ids_out, int32_t *n_accept_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!logits || !rows || !group_start || !draft || !ids_out || !n_accept_out || n < 1 || n > SPEC_MAX_N || n_base_rows < 1 || R < 1 || R > SPEC_MAX_ROWS || G < 1 ||
-        G > SPEC_MAX_GROUPS) { fail("spec_verify: bad shape (R <= 1088, G <= 64)"); return MI355_ERR_ARG; }
-    for (int r = 0; r < R; r++)
-        if (rows[r] < 0 || rows[r] >= n_base_rows) { fail("spec_verify: rows[" + std::to_string(r) + "] outside the base"); return MI355_ERR_ARG; }
-    if (group_start[0] != 0 || group_start[G] != R) { fail("spec_verify: the groups do not cover rows 0 .. R - 1"); return MI355_ERR_ARG; }
-    for (int g = 0; g < G; g++) {
-        const int k1 = group_start[g + 1] - group_start[g];
-        if (k1 < 1 || k1 > SPEC_MAX_DRAFT + 1) { fail("spec_verify: group " + std::to_string(g) + " outside 1 .. 17 rows"); return MI355_ERR_ARG; }
-    }
-    const size_t nb = (size_t)n_base_rows * (size_t)n * 4;
-    DevBuf db(nb), dr((size_t)R * 4), dg((size_t)(G + 1) * 4), dd((size_t)R * 4), di((size_t)R * 4), da((size_t)G * 4), ds(spec_verify_scratch_words(R) * 4);
-    if (!db.up(logits, nb) || !dr.up(rows, (size_t)R * 4) || !dg.up(group_start, (size_t)(G + 1) * 4) || !dd.up(draft, (size_t)R * 4) || !di.p || !da.p || !ds.p) return MI355_ERR_OOM;
-    hipError_t e = launch_spec_verify(db.as<float>(), (int)n, dr.as<int32_t>(), R, dg.as<int32_t>(), G, dd.as<int32_t>(), di.as<int32_t>(), da.as<int32_t>(), ds.as<float>(), R,
-                                      nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "spec_verify");
-    return di.down(ids_out, (size_t)R * 4) && da.down(n_accept_out, (size_t)G * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_token_logprob_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, const int32_t *targets, int32_t R, float *logprob_out,
-                                int32_t *rank_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!base || !targets || !logprob_out || !rank_out || n < 1 || n > SPEC_MAX_N || n_base_rows < 1 || R < 1 || R > 65535 || (!rows && R > n_base_rows)) {
-        fail("token_logprob_rows: bad shape"); return MI355_ERR_ARG;
-    }
-    for (int r = 0; r < R; r++) {
-        if (rows && (rows[r] < 0 || rows[r] >= n_base_rows)) { fail("token_logprob_rows: rows[" + std::to_string(r) + "] outside the base"); return MI355_ERR_ARG; }
-        if (targets[r] < 0 || targets[r] >= n) { fail("token_logprob_rows: targets[" + std::to_string(r) + "] outside [0, n)"); return MI355_ERR_ARG; }
-    }
-    const size_t nb = (size_t)n_base_rows * (size_t)n * 4;
-    DevBuf db(nb), dr((size_t)R * 4), dt((size_t)R * 4), dl((size_t)R * 4), dk((size_t)R * 4), ds(token_logprob_scratch_words(R) * 4);
-    if (!db.up(base, nb) || (rows && !dr.up(rows, (size_t)R * 4)) || !dt.up(targets, (size_t)R * 4) || !dr.p || !dl.p || !dk.p || !ds.p) return MI355_ERR_OOM;
-    hipError_t e = launch_token_logprob_rows(db.as<float>(), (int)n, rows ? dr.as<int32_t>() : nullptr, dt.as<int32_t>(), R, dl.as<float>(), dk.as<int32_t>(), ds.as<float>(),
-                                             R, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "token_logprob_rows");
-    return dl.down(logprob_out, (size_t)R * 4) && dk.down(rank_out, (size_t)R * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_logits_kl_rows(const float *p, int32_t n_p_rows, const float *q, int32_t n_q_rows, int64_t n, const int32_t *rows_p, const int32_t *rows_q, int32_t R,
-                            float *kl_out, int32_t *same_top_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!p || !q || !kl_out || !same_top_out || n < 1 || n > SPEC_MAX_N || n_p_rows < 1 || n_q_rows < 1 || R < 1 || R > 65535 || (!rows_p && R > n_p_rows) ||
-        (!rows_q && R > n_q_rows)) { fail("logits_kl_rows: bad shape"); return MI355_ERR_ARG; }
-    for (int r = 0; r < R; r++)
-        if ((rows_p && (rows_p[r] < 0 || rows_p[r] >= n_p_rows)) || (rows_q && (rows_q[r] < 0 || rows_q[r] >= n_q_rows))) {
-            fail("logits_kl_rows: row " + std::to_string(r) + " outside its base"); return MI355_ERR_ARG;
-        }
-    const size_t nbp = (size_t)n_p_rows * (size_t)n * 4, nbq = (size_t)n_q_rows * (size_t)n * 4;
-    DevBuf dp(nbp), dq(nbq), drp((size_t)R * 4), drq((size_t)R * 4), dk((size_t)R * 4), dt((size_t)R * 4), ds(logits_kl_scratch_words(R) * 4);
-    if (!dp.up(p, nbp) || !dq.up(q, nbq) || (rows_p && !drp.up(rows_p, (size_t)R * 4)) || (rows_q && !drq.up(rows_q, (size_t)R * 4)) || !drp.p || !drq.p || !dk.p || !dt.p ||
-        !ds.p) return MI355_ERR_OOM;
-    hipError_t e = launch_logits_kl_rows(dp.as<float>(), dq.as<float>(), (int)n, rows_p ? drp.as<int32_t>() : nullptr, rows_q ? drq.as<int32_t>() : nullptr, R, dk.as<float>(),
-                                         dt.as<int32_t>(), ds.as<float>(), R, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "logits_kl_rows");
-    return dk.down(kl_out, (size_t)R * 4) && dt.down(same_top_out, (size_t)R * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_imatrix_accum(const float *x, const float *x2, int64_t ld, int64_t K, int32_t R, const int32_t *row_src, int32_t n_src_rows, const int32_t *counts_per_mat,
-                           int32_t n_mat, float *sum2_io, int32_t *count_io) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!x || !sum2_io || !count_io || K < 32 || (K & 31) || K > INT32_MAX / 2 || ld < K || (ld & 3) || ld > INT32_MAX / 2 || R < 1 || R > IMX_MAX_ROWS || n_src_rows < 1 ||
-        n_mat < 1 || n_mat > 256 || (n_mat > 1 && !counts_per_mat) || (!row_src && R > n_src_rows)) { fail("imatrix_accum: bad shape"); return MI355_ERR_ARG; }
-    for (int r = 0; row_src && r < R; r++)
-        if (row_src[r] < 0 || row_src[r] >= n_src_rows) { fail("imatrix_accum: row_src[" + std::to_string(r) + "] outside the source rows"); return MI355_ERR_ARG; }
-    // meta as launch_moe_group leaves it: counts | exclusive offsets | total
-    std::vector<int32_t> meta;
-    if (counts_per_mat) {
-        meta.assign((size_t)2 * n_mat + 1, 0);
-        int64_t run = 0;
-        for (int m = 0; m < n_mat; m++) {
-            if (counts_per_mat[m] < 0) { fail("imatrix_accum: negative count"); return MI355_ERR_ARG; }
-            meta[(size_t)m] = counts_per_mat[m]; meta[(size_t)n_mat + m] = (int32_t)std::min<int64_t>(run, R);
-            run += counts_per_mat[m];
-        }
-        if (run != R) { fail("imatrix_accum: the counts do not add up to R"); return MI355_ERR_ARG; }
-        meta[(size_t)2 * n_mat] = R;
-    }
-    const size_t nx = (size_t)n_src_rows * (size_t)ld * 4, ns = (size_t)(n_mat + 1) * (size_t)K * 4;
-    const size_t slab_floats = imatrix_scratch_floats((int)K, R, n_mat);
-    DevBuf dx(nx), dx2(x2 ? nx : 16), dr((size_t)R * 4), dm(meta.empty() ? 16 : meta.size() * 4), dsum(ns), dcnt((size_t)n_mat * 4), dslab(slab_floats * 4);
-    if (!dx.up(x, nx) || (x2 && !dx2.up(x2, nx)) || (row_src && !dr.up(row_src, (size_t)R * 4)) || (!meta.empty() && !dm.up(meta.data(), meta.size() * 4)) ||
-        !dsum.up(sum2_io, ns) || !dcnt.up(count_io, (size_t)n_mat * 4) || !dx2.p || !dr.p || !dm.p || !dslab.p) return MI355_ERR_OOM;
-    hipError_t e = launch_imatrix_accum(dx.as<float>(), x2 ? dx2.as<float>() : nullptr, (int)ld, (int)K, R, row_src ? dr.as<int32_t>() : nullptr,
-                                        meta.empty() ? nullptr : dm.as<int32_t>(), n_mat, dsum.as<float>(), dcnt.as<int32_t>(), dslab.as<float>(), slab_floats, nullptr);
-    if (e == hipErrorInvalidValue) { fail("imatrix_accum: the launcher refuses this shape"); return MI355_ERR_ARG; }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "imatrix_accum");
-    return dsum.down(sum2_io, ns) && dcnt.down(count_io, (size_t)n_mat * 4) ? MI355_OK : MI355_ERR_HIP;
-}
 
 int mi355_quantize_supported(int32_t dst_type) { return quantize_dst_supported(dst_type) ? 1 : 0; }
 
@@ -1797,28 +740,32 @@ int mi355_quantize_chunk(int32_t dst_type, int32_t src_type, const void *src, in
     for (int64_t j = 0; imatrix && j < n_per_row; j++)
         if (!(imatrix[j] >= 0.0f) || std::isinf(imatrix[j])) { fail("quantize_chunk: imatrix[" + std::to_string(j) + "] is negative or not finite"); return MI355_ERR_ARG; }
     const size_t es = src_type == T_F32 ? 4 : 2, n = (size_t)n_per_row * (size_t)n_rows, rb = ggml_row_bytes(dst_type, n_per_row), nb = rb * (size_t)n_rows;
-    DevBuf dsrc(n * es), dim((size_t)n_per_row * 4), dout(nb + rb), dflag(16);
+    OpBufs b;
+    uint8_t *dsrc = b.alloc(n * es), *dout = b.alloc(nb + rb);
+    float *dim = b.alloc<float>((size_t)n_per_row * 4);
+    int32_t *dflag = b.alloc<int32_t>(16);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) { if (ev0) (void)hipEventDestroy(ev0); return MI355_ERR_HIP; }
+    if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) { if (ev0) (void)hipEventDestroy(ev0); fail("quantize_chunk: no timing events"); return MI355_ERR_HIP; }
     struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev_guard{ev0, ev1};
     const auto c0 = std::chrono::steady_clock::now();
-    if (!dsrc.up(src, n * es) || (imatrix && !dim.up(imatrix, (size_t)n_per_row * 4)) || !dim.p || !dout.p || !dflag.p) return MI355_ERR_OOM;
-    if (hipMemset(dout.as<uint8_t>() + nb, Q80_GUARD, rb) != hipSuccess) return MI355_ERR_HIP;
+    b.copy_in(dsrc, src, n * es);
+    if (imatrix) b.copy_in(dim, imatrix, (size_t)n_per_row * 4);
+    b.check(dout && hipMemset(dout + nb, Q80_GUARD, rb) == hipSuccess);
+    if (!b.ok()) return oom();
     const auto c1 = std::chrono::steady_clock::now();
     (void)hipEventRecord(ev0, nullptr);
-    hipError_t e = launch_quantize_rows(dst_type, src_type, dsrc.p, n_per_row, n_rows, imatrix ? dim.as<float>() : nullptr, dout.p, dflag.as<int32_t>(), nullptr);
+    hipError_t e = launch_quantize_rows(dst_type, src_type, dsrc, n_per_row, n_rows, imatrix ? dim : nullptr, dout, dflag, nullptr);
     if (e == hipErrorInvalidValue) { fail("quantize_chunk: the launcher refuses this shape"); return MI355_ERR_ARG; }
     (void)hipEventRecord(ev1, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "quantize_chunk");
+    if (const int rc = finish(e, "quantize_chunk")) return rc;
     float kernel_ms = 0.0f;
     (void)hipEventElapsedTime(&kernel_ms, ev0, ev1);
     const auto c2 = std::chrono::steady_clock::now();
     int32_t flag = 0;
     std::vector<uint8_t> guard(rb);
-    if (!dflag.down(&flag, 4) || hipMemcpy(guard.data(), dout.as<uint8_t>() + nb, rb, hipMemcpyDeviceToHost) != hipSuccess) return MI355_ERR_HIP;
-    for (uint8_t b : guard)
-        if (b != Q80_GUARD) { fail("quantize_chunk: the guard row behind the output was written"); return MI355_ERR_HIP; }
+    if (!b.down(&flag, dflag, 4).down(guard.data(), dout + nb, rb).ok()) return b.done("quantize_chunk");
+    for (uint8_t g : guard)
+        if (g != Q80_GUARD) { fail("quantize_chunk: the guard row behind the output was written"); return MI355_ERR_HIP; }
     if (flag) {                                  // which row: the host looks, the error path can afford it
         int64_t row = -1;
         for (int64_t i = 0; i < (int64_t)n && row < 0; i++) {
@@ -1830,825 +777,11 @@ int mi355_quantize_chunk(int32_t dst_type, int32_t src_type, const void *src, in
         fail("quantize_chunk: row " + std::to_string(row) + " holds a non-finite value");
         return MI355_ERR_ARG;
     }
-    if (!dout.down(dst, nb)) return MI355_ERR_HIP;
+    if (!b.down(dst, dout, nb).ok()) return b.done("quantize_chunk");
     const auto c3 = std::chrono::steady_clock::now();
     t_quant_ms[0] = std::chrono::duration<float, std::milli>(c1 - c0).count();
     t_quant_ms[1] = kernel_ms;
     t_quant_ms[2] = std::chrono::duration<float, std::milli>(c3 - c2).count();
-    return MI355_OK;
-}
-
-int mi355_op_topk_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t n_rows, int32_t k, const int32_t *adj_n,
-                       const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_cnt, const float *repeat, const float *freq, const float *present,
-                       uint64_t *keys_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n < 1 || n > INT32_MAX || n_base_rows < 1 || n_rows < 1 || n_rows > 65535) { fail("topk_rows: bad shape"); return MI355_ERR_ARG; }
-    if (k < 1 || k > TOPK_MAX_K || k > n) { fail("topk_rows: k outside [1, min(n, " + std::to_string(TOPK_MAX_K) + ")]"); return MI355_ERR_ARG; }
-    std::vector<TopkAdj> adjs((size_t)n_rows);
-    for (int r = 0; r < n_rows; r++) {
-        if (rows[r] < 0 || rows[r] >= n_base_rows) { fail("topk_rows: rows[" + std::to_string(r) + "] outside the base"); return MI355_ERR_ARG; }
-        if (adj_n[r] < 0 || adj_n[r] > TOPK_MAX_ADJ) { fail("topk_rows: adj_n[" + std::to_string(r) + "] outside [0, " + std::to_string(TOPK_MAX_ADJ) + "]"); return MI355_ERR_ARG; }
-        TopkAdj &a = adjs[(size_t)r];
-        memset(&a, 0, sizeof a);
-        a.n = adj_n[r]; a.repeat = repeat[r]; a.freq = freq[r]; a.present = present[r];
-        const size_t o = (size_t)r * TOPK_MAX_ADJ;
-        memcpy(a.tok, adj_tok + o, (size_t)a.n * sizeof(int)); memcpy(a.bias, adj_bias + o, (size_t)a.n * sizeof(float)); memcpy(a.cnt, adj_cnt + o, (size_t)a.n * sizeof(int));
-    }
-    const size_t nb = (size_t)n_base_rows * (size_t)n * 4, nk = (size_t)n_rows * TOPK_MAX_K * 8;
-    DevBuf db(nb), dr((size_t)n_rows * 4), da((size_t)n_rows * sizeof(TopkAdj)), ds(topk_scratch_bytes((int)n) * (size_t)n_rows), dk(nk);
-    if (!db.up(base, nb) || !dr.up(rows, (size_t)n_rows * 4) || !da.up(adjs.data(), (size_t)n_rows * sizeof(TopkAdj)) || !ds.p || !dk.p) return MI355_ERR_OOM;
-    hipError_t e = launch_topk_rows(db.as<float>(), (int)n, n_rows, dr.as<int>(), k, da.as<TopkAdj>(), ds.p, dk.as<unsigned long long>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "topk_rows");
-    std::vector<uint64_t> keys((size_t)n_rows * TOPK_MAX_K);
-    if (!dk.down(keys.data(), nk)) return MI355_ERR_HIP;
-    for (int r = 0; r < n_rows; r++) memcpy(keys_out + (size_t)r * k, keys.data() + (size_t)r * TOPK_MAX_K, (size_t)k * 8);
-    return MI355_OK;
-}
-
-int mi355_op_moe_group(const int32_t *ids, int64_t T, int32_t k, int32_t n_expert, int32_t *meta, int32_t *slot_of, int32_t *tok_of) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n_expert < 1 || n_expert > 256) { fail("moe_group: n_expert outside [1, 256]"); return MI355_ERR_ARG; }
-    if (T < 1 || k < 1 || T * (int64_t)k > 60 * 1024) { fail("moe_group: T * k outside [1, 61440]"); return MI355_ERR_ARG; }
-    const size_t ns = (size_t)T * k;
-    for (size_t i = 0; i < ns; i++)
-        if (ids[i] < 0 || ids[i] >= n_expert) { fail("moe_group: ids[" + std::to_string(i) + "] outside [0, n_expert)"); return MI355_ERR_ARG; }
-    DevBuf di(ns * 4), dm(((size_t)2 * n_expert + 1) * 4), dslot(ns * 4), dtok(ns * 4);
-    if (!di.up(ids, ns * 4) || !dm.p || !dslot.p || !dtok.p) return MI355_ERR_OOM;
-    hipError_t e = launch_moe_group(di.as<int32_t>(), (int)T, k, n_expert, dm.as<int32_t>(), dslot.as<int32_t>(), dtok.as<int32_t>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "moe_group");
-    return dm.down(meta, ((size_t)2 * n_expert + 1) * 4) && dslot.down(slot_of, ns * 4) && dtok.down(tok_of, ns * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_moe_gather_act(const int8_t *qs, const float *d, const int16_t *bsums, const int8_t *qs0, const uint16_t *d0, int64_t T, int64_t K,
-                            const int32_t *tok_of, int64_t n_rows, int8_t *qs_out, float *d_out, int16_t *bsums_out, int8_t *qs0_out, uint16_t *d0_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (T < 1 || n_rows < 1 || K < 1 || K > INT32_MAX || n_rows > INT32_MAX) { fail("moe_gather_act: bad shape"); return MI355_ERR_ARG; }
-    if (K % 256) { fail("moe_gather_act: K is not a multiple of 256"); return MI355_ERR_ARG; }
-    const bool q8k = qs != nullptr, q80 = qs0 != nullptr;
-    if ((!q8k && !q80) || (q8k && (!d || !bsums || !qs_out || !d_out || !bsums_out)) || (q80 && (!d0 || !qs0_out || !d0_out))) {
-        fail("moe_gather_act: an activation form needs all its planes, in and out"); return MI355_ERR_ARG;
-    }
-    for (int64_t r = 0; r < n_rows; r++)
-        if (tok_of[r] < 0 || tok_of[r] >= T) { fail("moe_gather_act: tok_of[" + std::to_string(r) + "] outside [0, T)"); return MI355_ERR_ARG; }
-    // plane p: bytes per row, source rows, destination rows (+ the guard row the caller filled)
-    const size_t rb[5] = {(size_t)K, (size_t)(K / 256) * 4, (size_t)(K / 16) * 2, (size_t)K, (size_t)(K / 32) * 2};
-    const void *in[5] = {qs, d, bsums, qs0, d0};
-    void *out[5] = {qs_out, d_out, bsums_out, qs0_out, d0_out};
-    const bool on[5] = {q8k, q8k, q8k, q80, q80};
-    std::unique_ptr<DevBuf> s[5], o[5];
-    for (int p = 0; p < 5; p++) {
-        if (!on[p]) continue;
-        s[p].reset(new DevBuf(rb[p] * (size_t)T));
-        o[p].reset(new DevBuf(rb[p] * (size_t)(n_rows + 1)));
-        if (!s[p]->up(in[p], rb[p] * (size_t)T) || !o[p]->up(out[p], rb[p] * (size_t)(n_rows + 1))) return MI355_ERR_OOM;
-    }
-    DevBuf dt((size_t)n_rows * 4);
-    if (!dt.up(tok_of, (size_t)n_rows * 4)) return MI355_ERR_OOM;
-    ActQuant src, dst;
-    if (q8k) { src.qs = s[0]->as<int8_t>(); src.d = s[1]->as<float>(); src.bsums = s[2]->as<int16_t>(); dst.qs = o[0]->as<int8_t>(); dst.d = o[1]->as<float>(); dst.bsums = o[2]->as<int16_t>(); }
-    if (q80) { src.qs0 = s[3]->as<int8_t>(); src.d0 = s[4]->as<uint16_t>(); dst.qs0 = o[3]->as<int8_t>(); dst.d0 = o[4]->as<uint16_t>(); }
-    hipError_t e = launch_moe_gather_act(src, dt.as<int32_t>(), (int)n_rows, (int)K, dst, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "moe_gather_act");
-    for (int p = 0; p < 5; p++)
-        if (on[p] && !o[p]->down(out[p], rb[p] * (size_t)(n_rows + 1))) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-int mi355_op_moe_combine(const float *x, const float *eo, const float *w, int64_t T, int32_t E, int32_t k, int32_t grouped, const int32_t *slot_of, float *y_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (T < 1 || E < 1 || k < 1 || T * (int64_t)E > INT32_MAX || T * (int64_t)k > INT32_MAX) { fail("moe_combine: bad shape"); return MI355_ERR_ARG; }
-    if (grouped && !slot_of) { fail("moe_combine: the grouped form needs slot_of"); return MI355_ERR_ARG; }
-    const size_t ns = (size_t)T * k, nx = (size_t)T * E * 4;
-    if (grouped)
-        for (size_t i = 0; i < ns; i++)
-            if (slot_of[i] < 0 || (size_t)slot_of[i] >= ns) { fail("moe_combine: slot_of[" + std::to_string(i) + "] outside [0, T * k)"); return MI355_ERR_ARG; }
-    DevBuf dx(nx), de(nx * (size_t)k), dw(ns * 4), dslot(ns * 4);
-    if (!dx.up(x, nx) || !de.up(eo, nx * (size_t)k) || !dw.up(w, ns * 4) || !dslot.p) return MI355_ERR_OOM;
-    if (grouped && !dslot.up(slot_of, ns * 4)) return MI355_ERR_OOM;
-    hipError_t e = grouped ? launch_moe_scatter_combine(dx.as<float>(), de.as<float>(), dw.as<float>(), dslot.as<int32_t>(), (int)T, E, k, nullptr)
-                           : launch_moe_combine(dx.as<float>(), de.as<float>(), dw.as<float>(), (int)T, E, k, (size_t)T * E, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "moe_combine");
-    return dx.down(y_out, nx) ? MI355_OK : MI355_ERR_HIP;
-}
-
-// One grouped-expert launch of a prompt batch as Context::moe_grouped_planes / moe_grouped_q80 issue it (host/runtime.cc): the weights expanded expert by expert
-// at the loader's stride (expand_prefill_planes), the grouped rows quantised, meta in moe_group_kernel's layout, rows_max = R.  Every out buffer is 0xFF bytes
-// before the launch and comes back whole, guard rows included.
-int mi355_op_moe_mul_mat_grouped(int32_t type, int32_t form, const void *W0, const void *W1, int32_t n_expert, int64_t N, int64_t K, const float *x,
-                                 const int32_t *counts, int64_t R, int64_t ld_out, int64_t guard_rows, float *y0, float *y1) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    const bool planes = form == 0 || form == 1, two_w = form == 1 || form == 3, two_y = form == 3;
-    if (form < 0 || form > 3 || !W0 || (two_w && !W1) || !x || !counts || !y0 || (two_y && !y1) || n_expert < 1 || n_expert > 256 || N < 1 || K < 1 || R < 1 ||
-        R > 60 * 1024 || N > INT32_MAX || K > INT32_MAX || ld_out < N || ld_out > INT32_MAX || guard_rows < 0 || guard_rows > 1024) {
-        fail("moe_mul_mat_grouped: bad arguments"); return MI355_ERR_ARG;
-    }
-    if (planes ? !mmq_planes_moe_ok(type, (int)N, (int)K) : !mmq_q80_moe_ok(type, (int)N, (int)K)) {
-        fail(planes ? "moe_mul_mat_grouped: the grouped plane launch takes Q4_K / Q5_K / Q6_K / IQ4_XS / TQ1_0 / TQ2_0, N % 128 == 0, K % 256 == 0"
-                    : "moe_mul_mat_grouped: the grouped Q8_0-copy launch takes MXFP4, N % 128 == 0, K % 32 == 0, 32 <= K <= 16384");
-        return MI355_ERR_ARG;
-    }
-    std::vector<int32_t> meta((size_t)2 * n_expert + 1);
-    int64_t sum = 0;
-    for (int e = 0; e < n_expert; e++) {
-        if (counts[e] < 0) { fail("moe_mul_mat_grouped: counts[" + std::to_string(e) + "] is negative"); return MI355_ERR_ARG; }
-        meta[(size_t)e] = counts[e];
-        meta[(size_t)n_expert + e] = (int32_t)sum;
-        sum += counts[e];
-        if (sum > R) break;
-    }
-    if (sum != R) { fail("moe_mul_mat_grouped: the counts do not add up to R"); return MI355_ERR_ARG; }
-    meta[(size_t)2 * n_expert] = (int32_t)R;
-    const size_t grow = ggml_row_bytes(type, K), drow = dev_row_bytes(type, K);
-    const size_t pb = planes ? mmq_planes_bytes(type, N, (int)K) : mmq_q80_copy_bytes(type, N, (int)K);
-    const size_t stride = (pb + 255) & ~(size_t)255;             // (the loader's: every expert's set starts on 256 bytes)
-    const int n_w = two_w ? 2 : 1, n_y = two_y ? 2 : 1;
-    const size_t yb = (size_t)(R + guard_rows) * (size_t)ld_out * 4;
-    std::unique_ptr<DevBuf> pl[2], dy[2];
-    {
-        DevBuf wsrc(grow * (size_t)N * n_expert), wdev(drow * (size_t)N * n_expert);
-        if (!wsrc.p || !wdev.p) { fail("device alloc failed"); return MI355_ERR_OOM; }
-        for (int i = 0; i < n_w; i++) {
-            pl[i].reset(new DevBuf(stride * (size_t)n_expert));
-            if (!pl[i]->p || !wsrc.up(i ? W1 : W0, grow * (size_t)N * n_expert)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-            hipError_t e = launch_repack_rows(type, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, N * n_expert, nullptr);
-            for (int64_t ex = 0; ex < n_expert && e == hipSuccess; ex++) {
-                const uint8_t *src = wdev.as<uint8_t>() + (size_t)ex * drow * (size_t)N;
-                uint8_t *dst = pl[i]->as<uint8_t>() + (size_t)ex * stride;
-                e = planes ? launch_mmq_expand(type, src, drow, (int)N, (int)K, dst, nullptr) : launch_expand_q80_copy(type, src, drow, (int)N, (int)K, dst, nullptr);
-            }
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (e != hipSuccess) return hip_fail(e, "moe_mul_mat_grouped (weights)");
-        }
-    }
-    DevBuf dx((size_t)K * R * 4), dmeta(meta.size() * 4);
-    ActBufs ab((size_t)K, (size_t)R);
-    if (!dx.up(x, (size_t)K * R * 4) || !dmeta.up(meta.data(), meta.size() * 4) || !ab.ok()) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    for (int i = 0; i < n_y; i++) {
-        dy[i].reset(new DevBuf(yb));
-        if (!dy[i]->p || hipMemset(dy[i]->p, 0xFF, yb) != hipSuccess) { fail("device alloc failed"); return MI355_ERR_OOM; }
-    }
-    hipError_t e = launch_quantize(dx.as<float>(), (int)K, (int)R, ab.q, planes, !planes, nullptr);
-    if (e == hipSuccess) {
-        if (form == 0) e = launch_mmq_planes_moe(type, pl[0]->as<uint8_t>(), stride, n_expert, dmeta.as<int32_t>(), (int)N, (int)K, (int)R, ab.q, dy[0]->as<float>(), (int)ld_out, nullptr);
-        else if (form == 1) e = launch_mmq_planes_swiglu_moe(type, pl[0]->as<uint8_t>(), pl[1]->as<uint8_t>(), stride, n_expert, dmeta.as<int32_t>(), (int)N, (int)K, (int)R, ab.q,
-                                                             dy[0]->as<float>(), (int)ld_out, nullptr);
-        else {
-            const uint8_t *w[2] = {pl[0]->as<uint8_t>(), two_w ? pl[1]->as<uint8_t>() : nullptr};
-            float *o[2] = {dy[0]->as<float>(), two_y ? dy[1]->as<float>() : nullptr};
-            e = launch_mmq_q80_moe(type, w, o, n_w, stride, n_expert, dmeta.as<int32_t>(), (int)N, (int)K, (int)R, ab.q, (int)ld_out, nullptr);
-        }
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "moe_mul_mat_grouped");
-    if (!dy[0]->down(y0, yb) || (two_y && !dy[1]->down(y1, yb))) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-int mi355_op_gather_rows_f32(const float *src, int64_t n_src_rows, int64_t n, const int32_t *rows, int64_t n_rows, float *dst) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (n_src_rows < 1 || n < 1 || n_rows < 1 || n > INT32_MAX || n_rows > 65535) { fail("gather_rows_f32: bad shape"); return MI355_ERR_ARG; }
-    for (int64_t r = 0; r < n_rows; r++)
-        if (rows[r] < 0 || rows[r] >= n_src_rows) { fail("gather_rows_f32: rows[" + std::to_string(r) + "] outside the source"); return MI355_ERR_ARG; }
-    const size_t nsrc = (size_t)n_src_rows * (size_t)n * 4, nd = (size_t)n_rows * (size_t)n * 4;
-    DevBuf ds(nsrc), dr((size_t)n_rows * 4), dd(nd);
-    if (!ds.up(src, nsrc) || !dr.up(rows, (size_t)n_rows * 4) || !dd.p) return MI355_ERR_OOM;
-    hipError_t e = launch_gather_rows_f32(ds.as<float>(), dr.as<int32_t>(), (int)n_rows, (int)n, dd.as<float>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "gather_rows_f32");
-    return dd.down(dst, nd) ? MI355_OK : MI355_ERR_HIP;
-}
-
-// flash_attn_ext over a caller-supplied cache and cell table (test entry): launch_flash_attn as a prompt batch or a generic step runs it.  cell_seq: the cells'
-// sequence bit masks, q_seq: each query's sequence (0 .. 63); a query sees cell c < n_kv where cell_pos[c] >= 0, cell_pos[c] <= q_pos and bit q_seq of
-// cell_seq[c] is set.  n_kv (1 .. n_cells) is what the kernels read from the device as the number of cells to scan; the grid, the splits and the workspace
-// are sized for n_cells, as a step of a context whose high-water mark lies below the bound its launches were sized for.
-int mi355_op_flash_attn_seq(const float *q, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v, const void *v,
-                            int32_t n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *q_pos, const int32_t *q_seq, int32_t n_kv,
-                            float scale, float *out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if ((D != 64 && D != 128) || G < 1 || H < 1 || H % G || T < 1 || n_cells < 1) { fail("unsupported head geometry"); return MI355_ERR_ARG; }
-    if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("bad cache type"); return MI355_ERR_ARG; }
-    if (!q || !k || !v || !cell_pos || !cell_seq || !q_pos || !q_seq || !out) { fail("flash_attn: null argument"); return MI355_ERR_ARG; }
-    if (n_kv < 1 || n_kv > n_cells) { fail("flash_attn: n_kv outside [1, n_cells]"); return MI355_ERR_ARG; }
-    for (int64_t t = 0; t < T; t++)
-        if (q_seq[t] < 0 || q_seq[t] > 63) { fail("flash_attn: q_seq[" + std::to_string(t) + "] outside [0, 63]"); return MI355_ERR_ARG; }
-    std::vector<uint8_t> kc, vc;
-    std::vector<uint16_t> ks, vs;
-    cache_planes_from_rows(type_k, k, G, D, n_cells, kc, ks);
-    cache_planes_from_rows(type_v, v, G, D, n_cells, vc, vs);
-    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dv(vc.size()), dvs(vs.size() * 2 + 16);
-    DevBuf dq((size_t)T * H * D * 4), dout((size_t)T * H * D * 4), dcp((size_t)n_cells * 4), dcs((size_t)n_cells * 8), dtp((size_t)T * 4), dts((size_t)T * 4), dn(16);
-    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dq.up(q, (size_t)T * H * D * 4) || !dout.p || !dks.p || !dvs.p) return MI355_ERR_OOM;
-    if (!ks.empty()) dks.up(ks.data(), ks.size() * 2);
-    if (!vs.empty()) dvs.up(vs.data(), vs.size() * 2);
-    if (!dcp.up(cell_pos, (size_t)n_cells * 4) || !dcs.up(cell_seq, (size_t)n_cells * 8) || !dtp.up(q_pos, (size_t)T * 4) || !dts.up(q_seq, (size_t)T * 4) ||
-        !dn.up(&n_kv, 4)) return MI355_ERR_OOM;
-    AttnArgs a{};
-    a.q = dq.as<float>(); a.out = dout.as<float>();
-    a.kv.k = dk.as<uint8_t>(); a.kv.kd = dks.as<uint16_t>(); a.kv.v = dv.as<uint8_t>(); a.kv.vd = dvs.as<uint16_t>();
-    a.type_k = type_k; a.type_v = type_v; a.T = (int)T; a.H = H; a.G = G; a.D = D; a.n_ctx = n_cells;
-    a.cell_pos = dcp.as<int32_t>(); a.cell_seq = dcs.as<uint64_t>(); a.tok_pos = dtp.as<int32_t>(); a.tok_seq = dts.as<int32_t>();
-    a.n_kv_dev = dn.as<int32_t>(); a.n_kv_max = n_cells; a.scale = scale;
-    a.splits = flash_attn_pick_splits((int)T, G, n_cells);
-    a.pf_splits = flash_attn_prefill_splits((int)T, H, G, D, n_cells);
-    DevBuf part(flash_attn_workspace_floats((int)T, H, D, std::max(a.splits, a.pf_splits)) * 4);
-    if (!part.p) return MI355_ERR_OOM;
-    a.part = part.as<float>();
-    hipError_t e = launch_flash_attn(a, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "flash_attn");
-    return dout.down(out, (size_t)T * H * D * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-// ... with one sequence: every cell in sequence 0, every query of sequence 0, the whole table scanned
-int mi355_op_flash_attn(const float *q, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
-                        const void *v, int32_t n_cells, const int32_t *cell_pos, const int32_t *q_pos, float scale, float *out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (T < 1 || n_cells < 1) { fail("unsupported head geometry"); return MI355_ERR_ARG; }
-    std::vector<uint64_t> seqm((size_t)n_cells, 1ull);
-    std::vector<int32_t> tseq((size_t)T, 0);
-    return mi355_op_flash_attn_seq(q, T, H, G, D, type_k, k, type_v, v, n_cells, cell_pos, seqm.data(), q_pos, tseq.data(), n_cells, scale, out);
-}
-
-// How launch_flash_attn would split the keys of such a call: out[0] = flash_attn_pick_splits (the split kernel), out[1] = flash_attn_prefill_splits (the
-// matrix-core prompt kernel), out[2] = 1 where the prompt kernel takes the call (test entry: a test states which splits its case runs with through this)
-int mi355_op_flash_attn_plan(int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, int32_t type_v, int32_t n_cells, int32_t *out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if ((D != 64 && D != 128) || G < 1 || H < 1 || H % G || T < 1 || T > INT32_MAX || n_cells < 1 || !out) { fail("unsupported head geometry"); return MI355_ERR_ARG; }
-    AttnArgs a{};
-    a.type_k = type_k; a.type_v = type_v; a.T = (int)T; a.H = H; a.G = G; a.D = D; a.n_ctx = n_cells; a.n_kv_max = n_cells;
-    out[0] = flash_attn_pick_splits((int)T, G, n_cells);
-    out[1] = flash_attn_prefill_splits((int)T, H, G, D, n_cells);
-    out[2] = flash_attn_prefill_applicable(a) && !(fa_v_acc_f16_enabled() && type_k == T_F16 && type_v == T_F16) ? 1 : 0;
-    return MI355_OK;
-}
-
-// The attention block of ONE single-token step exactly as the decode path launches it (test entry): rope of q
-// and of the token's K row, the K / V row quantised into the cache, attention over the visible cells, merge of the chunk partials, Q8_K quantisation and the
-// attn_output mat-vec with its residual.  fused = 1: attn_out.hip (one launch); 0: the single-launch decode attention + the weight-stream mat-vec.
-// k / v: the cache BEFORE the step as ggml-layout rows [n_cells][G * D] (the row at tok_cell is overwritten); cell_pos[tok_cell] must already be tok_pos.
-// cell_seq (null: every cell in sequence 0 only) / tok_seq: the cells' sequence bit masks and the token's sequence, so that the cache may hold other sequences'
-// cells; use_lists: the launch walks the token's chunk list (host/attn_chunks.h) as a step of a context with several sequences does.
-int mi355_op_attn_step_seq(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
-                           const void *v, int32_t n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, int32_t tok_pos, int32_t tok_seq, int32_t tok_cell,
-                           int32_t use_lists, float rope_base, int32_t n_rot, float scale, int32_t type_o, const void *W_o, int64_t E, const float *resid,
-                           int32_t fused, float *att_out, float *out, void *k_row_out, void *v_row_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if ((D != 64 && D != 128) || G < 1 || H % G || n_cells < 1 || tok_cell < 0 || tok_cell >= n_cells) { fail("bad geometry"); return MI355_ERR_ARG; }
-    if (tok_seq < 0 || tok_seq > 63) { fail("tok_seq outside [0, 63]"); return MI355_ERR_ARG; }
-    const int64_t K = (int64_t)H * D;
-    const size_t kv_dim = (size_t)G * D;
-    auto fill = [&](int type, const void *rows, std::vector<uint8_t> &codes, std::vector<uint16_t> &scales) { cache_planes_from_rows(type, rows, G, D, n_cells, codes, scales); };
-    if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("bad cache type"); return MI355_ERR_ARG; }
-    std::vector<uint8_t> kc, vc;
-    std::vector<uint16_t> ks, vs;
-    fill(type_k, k, kc, ks);
-    fill(type_v, v, vc, vs);
-    const size_t grow = ggml_row_bytes(type_o, K), drow = dev_row_bytes(type_o, K);
-    if (!grow || K % 256) { fail("bad attn_output type / K"); return MI355_ERR_ARG; }
-    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dv(vc.size()), dvs(vs.size() * 2 + 16);
-    DevBuf dq((size_t)K * 4), dkn(kv_dim * 4), dvn(kv_dim * 4), datt((size_t)K * 4), dcp((size_t)n_cells * 4), dcs((size_t)n_cells * 8), dtp(16), dts(16), dn(16), dcell(16);
-    DevBuf wsrc(grow * E), wdev(drow * E), dres((size_t)E * 4), dout((size_t)E * 4), dcnt(64 * ATT_SYNC_STRIDE * 4), dflags(64 * ATT_SYNC_STRIDE * 4), dserial(64), dcsb((size_t)std::max(n_rot, 4) * 4 + 64);
-    ActBufs ab((size_t)K, 1);
-    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dq.up(q, (size_t)K * 4) || !dkn.up(k_new, kv_dim * 4) || !dvn.up(v_new, kv_dim * 4) ||
-        !wsrc.up(W_o, grow * E) || !wdev.p || !dres.up(resid, (size_t)E * 4) || !dout.p || !ab.ok() || !datt.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    if (!ks.empty()) dks.up(ks.data(), ks.size() * 2);
-    if (!vs.empty()) dvs.up(vs.data(), vs.size() * 2);
-    std::vector<uint64_t> seqm((size_t)n_cells, 1ull);
-    if (cell_seq) seqm.assign(cell_seq, cell_seq + n_cells);
-    const int32_t tseq = tok_seq, nkv = n_cells;
-    const unsigned one = 1u;
-    ChunkLists cl;
-    if (use_lists && !cl.make(n_cells, n_cells, cell_pos, seqm.data(), &tseq, 1)) return MI355_ERR_OOM;
-    dcp.up(cell_pos, (size_t)n_cells * 4); dcs.up(seqm.data(), (size_t)n_cells * 8); dtp.up(&tok_pos, 4); dts.up(&tseq, 4); dn.up(&nkv, 4); dcell.up(&tok_cell, 4);
-    dserial.up(&one, 4);
-    hipError_t e = launch_repack_rows(type_o, wsrc.as<uint8_t>(), wdev.as<uint8_t>(), K, E, nullptr);
-    if (e != hipSuccess) return hip_fail(e, "repack");
-    RopeArgs ra{};
-    ra.n_rot = n_rot; ra.freq_base = rope_base; ra.freq_scale = 1.0f; ra.freq_factors = nullptr; ra.neox = 0;
-    e = launch_rope_table(dtp.as<int32_t>(), 1, ra, dcsb.as<float>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "rope_table");
-    AttnArgs a{};
-    a.q = dq.as<float>(); a.out = datt.as<float>();
-    a.kv.k = dk.as<uint8_t>(); a.kv.kd = dks.as<uint16_t>(); a.kv.v = dv.as<uint8_t>(); a.kv.vd = dvs.as<uint16_t>();
-    a.type_k = type_k; a.type_v = type_v; a.T = 1; a.H = H; a.G = G; a.D = D; a.n_ctx = n_cells;
-    a.cell_pos = dcp.as<int32_t>(); a.cell_seq = dcs.as<uint64_t>(); a.tok_pos = dtp.as<int32_t>(); a.tok_seq = dts.as<int32_t>();
-    a.n_kv_dev = dn.as<int32_t>(); a.n_kv_max = n_cells; a.scale = scale;
-    a.out_q = &ab.q; a.out_q8k = true; a.out_q80 = false;
-    MMVQSeg so{};
-    so.W = wdev.as<uint8_t>(); so.out = dout.as<float>(); so.resid = dres.as<float>(); so.type = type_o; so.n_rows = (int)E; so.ld_out = (int)E; so.row_bytes = drow;
-    if (fused) {
-        a.splits = attn_out_fused_splits(a);
-        if (use_lists) cl.apply(a);
-        DevBuf part(flash_attn_workspace_floats(1, H, D, a.splits) * 4);
-        a.part = part.as<float>();
-        if (!attn_out_fused_applicable(a, ra, so, (int)K, EPI_ADD)) { fail("attn_out.hip has no form for this shape"); return MI355_ERR_ARG; }
-        DevBuf dgran(attn_out_granule_words((int)K) * 8);
-        if (!dgran.p) return MI355_ERR_OOM;
-        e = launch_attn_out_fused(a, dcsb.as<float>(), ra, dkn.as<float>(), dvn.as<float>(), dcell.as<int32_t>(), dcnt.as<unsigned>(), dflags.as<unsigned>(),
-                                  dgran.as<unsigned long long>(), 3, dserial.as<unsigned>(), so, (int)K, EPI_ADD, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) return hip_fail(e, "attn_out_fused");
-    } else {
-        a.splits = flash_attn_decode_splits(n_cells);
-        if (use_lists) cl.apply(a);
-        DevBuf part(flash_attn_workspace_floats(1, H, D, a.splits) * 4);
-        a.part = part.as<float>();
-        if (!flash_attn_decode_fused_applicable(a, ra)) { fail("the single-launch decode attention has no form for this shape"); return MI355_ERR_ARG; }
-        e = launch_flash_attn_decode_fused(a, dcsb.as<float>(), ra, dkn.as<float>(), dvn.as<float>(), dcell.as<int32_t>(), dcnt.as<unsigned>(), nullptr);
-        if (e != hipSuccess) return hip_fail(e, "flash_attn_decode_fused");
-        MMVQArgs m{};
-        m.n_seg = 1; m.K = (int)K; m.T = 1; m.epi = EPI_ADD; m.seg[0] = so;
-        m.aq = ab.q.qs; m.ad = ab.q.d; m.abs = ab.q.bsums; m.aq0 = ab.q.qs0; m.ad0 = ab.q.d0;
-        e = launch_mmvq(m, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) return hip_fail(e, "attn_output mat-vec");
-    }
-    if (att_out && !datt.down(att_out, (size_t)K * 4)) return MI355_ERR_HIP;
-    if (out && !dout.down(out, (size_t)E * 4)) return MI355_ERR_HIP;
-    // the cache row the step wrote, back in ggml block layout
-    auto row_back = [&](int type, DevBuf &codes, DevBuf &scales, void *dst) -> bool { return cache_row_to_ggml(type, codes, scales, G, D, n_cells, tok_cell, dst); };
-    if (!row_back(type_k, dk, dks, k_row_out) || !row_back(type_v, dv, dvs, v_row_out)) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-int mi355_op_attn_step(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
-                       const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos, int32_t tok_cell, float rope_base, int32_t n_rot, float scale,
-                       int32_t type_o, const void *W_o, int64_t E, const float *resid, int32_t fused, float *att_out, float *out, void *k_row_out, void *v_row_out) {
-    return mi355_op_attn_step_seq(q, k_new, v_new, H, G, D, type_k, k, type_v, v, n_cells, cell_pos, nullptr, tok_pos, 0, tok_cell, 0, rope_base, n_rot, scale, type_o,
-                                  W_o, E, resid, fused, att_out, out, k_row_out, v_row_out);
-}
-
-// The decode attention of ONE token of a qwen2 / qwen3 file as the decode path launches it (test entry): NEOX rope of q and of the token's K row - each head
-// RMS-normalised and multiplied by q_norm / k_norm first where they are given (qwen3; null: no norm, the qwen2 path) - the K / V row quantised into the cache,
-// attention over the visible cells and the merge of the chunk partials.  mode 1: the single-launch form of a single-token step (tickets, the last workgroup
-// merges); 0: the store-fused form of a batched step (K / V stored inside the attention launch, merged by its own launch); 2: the generic path of prompt
-// batches (rope_kv_store, then the split attention on the rotated q).  Cache arguments and outputs as mi355_op_attn_step.
-// cell_seq (null: every cell in sequence 0 only), tok_seq, use_lists (modes 0 and 1 only): as mi355_op_attn_step_seq.
-int mi355_op_attn_decode_neox_seq(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
-                                  const void *v, int32_t n_cells, const int32_t *cell_pos, const uint64_t *cell_seq, int32_t tok_pos, int32_t tok_seq, int32_t tok_cell,
-                                  int32_t use_lists, float rope_base, float scale, const float *q_norm, const float *k_norm, float eps, int32_t mode, float *att_out,
-                                  void *k_row_out, void *v_row_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if ((D != 64 && D != 128) || G < 1 || H % G || n_cells < 1 || tok_cell < 0 || tok_cell >= n_cells || mode < 0 || mode > 2) { fail("bad geometry / mode"); return MI355_ERR_ARG; }
-    if (tok_seq < 0 || tok_seq > 63 || (use_lists && mode == 2)) { fail("tok_seq outside [0, 63], or chunk lists asked of the generic path"); return MI355_ERR_ARG; }
-    if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("bad cache type"); return MI355_ERR_ARG; }
-    const size_t K = (size_t)H * D, kv_dim = (size_t)G * D;
-    std::vector<uint8_t> kc, vc;
-    std::vector<uint16_t> ks, vs;
-    cache_planes_from_rows(type_k, k, G, D, n_cells, kc, ks);
-    cache_planes_from_rows(type_v, v, G, D, n_cells, vc, vs);
-    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dv(vc.size()), dvs(vs.size() * 2 + 16), dqn((size_t)D * 4), dkn_w((size_t)D * 4);
-    DevBuf dq(K * 4), dkn(kv_dim * 4), dvn(kv_dim * 4), datt(K * 4), dcp((size_t)n_cells * 4), dcs((size_t)n_cells * 8), dtp(16), dts(16), dn(16), dcell(16);
-    DevBuf dcnt(64 * ATT_SYNC_STRIDE * 4), dcsb((size_t)D * 4 + 64);
-    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dq.up(q, K * 4) || !dkn.up(k_new, kv_dim * 4) || !dvn.up(v_new, kv_dim * 4) || !datt.p ||
-        (q_norm && !dqn.up(q_norm, (size_t)D * 4)) || (k_norm && !dkn_w.up(k_norm, (size_t)D * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    if (!ks.empty()) dks.up(ks.data(), ks.size() * 2);
-    if (!vs.empty()) dvs.up(vs.data(), vs.size() * 2);
-    std::vector<uint64_t> seqm((size_t)n_cells, 1ull);
-    if (cell_seq) seqm.assign(cell_seq, cell_seq + n_cells);
-    const int32_t tseq = tok_seq, nkv = n_cells;
-    ChunkLists cl;
-    if (use_lists && !cl.make(n_cells, n_cells, cell_pos, seqm.data(), &tseq, 1)) return MI355_ERR_OOM;
-    dcp.up(cell_pos, (size_t)n_cells * 4); dcs.up(seqm.data(), (size_t)n_cells * 8); dtp.up(&tok_pos, 4); dts.up(&tseq, 4); dn.up(&nkv, 4); dcell.up(&tok_cell, 4);
-    RopeArgs ra{};
-    ra.n_rot = D; ra.freq_base = rope_base; ra.freq_scale = 1.0f; ra.freq_factors = nullptr; ra.neox = 1;
-    ra.q_norm = q_norm ? dqn.as<float>() : nullptr; ra.k_norm = k_norm ? dkn_w.as<float>() : nullptr; ra.qk_eps = eps;
-    hipError_t e = launch_rope_table(dtp.as<int32_t>(), 1, ra, dcsb.as<float>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "rope_table");
-    AttnArgs a{};
-    a.q = dq.as<float>(); a.out = datt.as<float>();
-    a.kv.k = dk.as<uint8_t>(); a.kv.kd = dks.as<uint16_t>(); a.kv.v = dv.as<uint8_t>(); a.kv.vd = dvs.as<uint16_t>();
-    a.type_k = type_k; a.type_v = type_v; a.T = 1; a.H = H; a.G = G; a.D = D; a.n_ctx = n_cells;
-    a.cell_pos = dcp.as<int32_t>(); a.cell_seq = dcs.as<uint64_t>(); a.tok_pos = dtp.as<int32_t>(); a.tok_seq = dts.as<int32_t>();
-    a.n_kv_dev = dn.as<int32_t>(); a.n_kv_max = n_cells; a.scale = scale;
-    if (mode == 2) {
-        e = launch_rope_kv_store(dq.as<float>(), dkn.as<float>(), dvn.as<float>(), 1, H, G, D, dtp.as<int32_t>(), dcell.as<int32_t>(), ra, a.kv, type_k, type_v, n_cells,
-                                 dcsb.as<float>(), nullptr);
-        if (e != hipSuccess) return hip_fail(e, "rope_kv_store");
-        a.splits = flash_attn_pick_splits(1, G, n_cells);
-        a.pf_splits = flash_attn_prefill_splits(1, H, G, D, n_cells);
-        DevBuf part(flash_attn_workspace_floats(1, H, D, std::max(a.splits, a.pf_splits)) * 4);
-        a.part = part.as<float>();
-        e = launch_flash_attn(a, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) return hip_fail(e, "flash_attn");
-    } else {
-        a.splits = flash_attn_decode_splits(n_cells);
-        if (use_lists) cl.apply(a);
-        DevBuf part(flash_attn_workspace_floats(1, H, D, a.splits) * 4);
-        a.part = part.as<float>();
-        if (!flash_attn_decode_applicable(a, ra) || (mode == 1 && !flash_attn_decode_fused_applicable(a, ra))) { fail("the decode attention has no form for this shape"); return MI355_ERR_ARG; }
-        if (mode == 1) e = launch_flash_attn_decode_fused(a, dcsb.as<float>(), ra, dkn.as<float>(), dvn.as<float>(), dcell.as<int32_t>(), dcnt.as<unsigned>(), nullptr);
-        else e = launch_flash_attn_decode(a, dcsb.as<float>(), ra, nullptr, dkn.as<float>(), dvn.as<float>(), dcell.as<int32_t>());
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) return hip_fail(e, "flash_attn_decode");
-    }
-    if (att_out && !datt.down(att_out, K * 4)) return MI355_ERR_HIP;
-    if (!cache_row_to_ggml(type_k, dk, dks, G, D, n_cells, tok_cell, k_row_out) || !cache_row_to_ggml(type_v, dv, dvs, G, D, n_cells, tok_cell, v_row_out)) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-int mi355_op_attn_decode_neox(const float *q, const float *k_new, const float *v_new, int32_t H, int32_t G, int32_t D, int32_t type_k, const void *k, int32_t type_v,
-                              const void *v, int32_t n_cells, const int32_t *cell_pos, int32_t tok_pos, int32_t tok_cell, float rope_base, float scale,
-                              const float *q_norm, const float *k_norm, float eps, int32_t mode, float *att_out, void *k_row_out, void *v_row_out) {
-    return mi355_op_attn_decode_neox_seq(q, k_new, v_new, H, G, D, type_k, k, type_v, v, n_cells, cell_pos, nullptr, tok_pos, 0, tok_cell, 0, rope_base, scale, q_norm,
-                                         k_norm, eps, mode, att_out, k_row_out, v_row_out);
-}
-
-// The K / V cache write of a batch on its own (test entry): the four launches that rotate K and write K / V rows into the cache,
-// on a caller-supplied cache that crosses the boundary whole, in and out, as ggml-layout rows.  form 0: launch_rope_kv_store computing its angles, 1: on the
-// table of launch_rope_table, 2: launch_rope_q_kv_store_fast, 3: launch_kv_store_fast.  A form that has no kernel for the arguments is refused, never launched.
-int mi355_op_kv_store(int32_t form, float *q, const float *k, const float *v, int64_t T, int32_t H, int32_t G, int32_t D, int32_t n_rot, int32_t neox,
-                      int32_t type_k, int32_t type_v, int32_t n_cells, const int32_t *tok_pos, const int32_t *tok_cell, float rope_base, float freq_scale,
-                      const float *freq_factors, const float *q_norm, const float *k_norm, float eps, void *k_cache, void *v_cache) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (form < 0 || form > 3 || !k || !v || !tok_pos || !tok_cell || !k_cache || !v_cache || (form != 3 && !q)) { fail("bad form / null argument"); return MI355_ERR_ARG; }
-    if (T < 1 || T > 4096 || H < 1 || G < 1 || D < 32 || D % 32 || n_rot < 2 || n_rot > D || n_rot % 2 || n_cells < 1) { fail("bad geometry"); return MI355_ERR_ARG; }
-    if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("bad cache type"); return MI355_ERR_ARG; }
-    for (int64_t t = 0; t < T; t++)
-        if (tok_cell[t] < 0 || tok_cell[t] >= n_cells) { fail("tok_cell outside the cache"); return MI355_ERR_ARG; }
-    const size_t q_dim = (size_t)H * D, kv_dim = (size_t)G * D;
-    if (form < 2 && ((size_t)n_rot + kv_dim) * 4 > 48 * 1024) { fail("n_head_kv * head_dim too wide for the generic kernel's LDS"); return MI355_ERR_ARG; }
-    if (form < 2 && (q_norm || k_norm) && (n_rot != D || (D != 64 && D != 128))) { fail("the q / k norm works on whole heads of 64 or 128"); return MI355_ERR_ARG; }
-    std::vector<uint8_t> kc, vc;
-    std::vector<uint16_t> ks, vs;
-    cache_planes_from_rows(type_k, k_cache, G, D, n_cells, kc, ks);
-    cache_planes_from_rows(type_v, v_cache, G, D, n_cells, vc, vs);
-    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dv(vc.size()), dvs(vs.size() * 2 + 16), dqn((size_t)D * 4), dkn_w((size_t)D * 4), dff((size_t)n_rot * 2 + 16);
-    DevBuf dq((size_t)T * q_dim * 4), dkn((size_t)T * kv_dim * 4), dvn((size_t)T * kv_dim * 4), dtp((size_t)T * 4), dcell((size_t)T * 4), dcsb((size_t)T * n_rot * 4 + 64);
-    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dks.p || !dvs.p || !dq.p || (q && !dq.up(q, (size_t)T * q_dim * 4)) ||
-        !dkn.up(k, (size_t)T * kv_dim * 4) || !dvn.up(v, (size_t)T * kv_dim * 4) || !dtp.up(tok_pos, (size_t)T * 4) || !dcell.up(tok_cell, (size_t)T * 4) || !dcsb.p ||
-        (q_norm && !dqn.up(q_norm, (size_t)D * 4)) || (k_norm && !dkn_w.up(k_norm, (size_t)D * 4)) ||
-        (freq_factors && !dff.up(freq_factors, (size_t)(n_rot / 2) * 4))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    if (!ks.empty() && !dks.up(ks.data(), ks.size() * 2)) return MI355_ERR_OOM;
-    if (!vs.empty() && !dvs.up(vs.data(), vs.size() * 2)) return MI355_ERR_OOM;
-    RopeArgs ra{};
-    ra.n_rot = n_rot; ra.freq_base = rope_base; ra.freq_scale = freq_scale; ra.freq_factors = freq_factors ? dff.as<float>() : nullptr; ra.neox = neox ? 1 : 0;
-    ra.q_norm = q_norm ? dqn.as<float>() : nullptr; ra.k_norm = k_norm ? dkn_w.as<float>() : nullptr; ra.qk_eps = eps;
-    if (form == 2 && !rope_q_kv_store_fast_applicable(H, G, D, type_k, type_v, ra)) { fail("the vectorised prompt store has no form for these arguments"); return MI355_ERR_ARG; }
-    if (form == 3 && !kv_store_fast_applicable(G, D, type_k, type_v, ra)) { fail("the small-batch decode store has no form for these arguments"); return MI355_ERR_ARG; }
-    KVLayerView kv{};
-    kv.k = dk.as<uint8_t>(); kv.kd = dks.as<uint16_t>(); kv.v = dv.as<uint8_t>(); kv.vd = dvs.as<uint16_t>();
-    hipError_t e = hipSuccess;
-    if (form != 0) e = launch_rope_table(dtp.as<int32_t>(), (int)T, ra, dcsb.as<float>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "rope_table");
-    if (form < 2)
-        e = launch_rope_kv_store(dq.as<float>(), dkn.as<float>(), dvn.as<float>(), (int)T, H, G, D, dtp.as<int32_t>(), dcell.as<int32_t>(), ra, kv, type_k, type_v, n_cells,
-                                 form == 1 ? dcsb.as<float>() : nullptr, nullptr);
-    else if (form == 2)
-        e = launch_rope_q_kv_store_fast(dq.as<float>(), dkn.as<float>(), dvn.as<float>(), (int)T, H, G, D, dcsb.as<float>(), ra, dcell.as<int32_t>(), kv, type_k, type_v,
-                                        n_cells, nullptr);
-    else
-        e = launch_kv_store_fast(dkn.as<float>(), dvn.as<float>(), (int)T, G, D, dcsb.as<float>(), ra, dcell.as<int32_t>(), kv, type_k, type_v, n_cells, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "kv_store");
-    if (form != 3 && !dq.down(q, (size_t)T * q_dim * 4)) return MI355_ERR_HIP;
-    if (!cache_rows_from_planes(type_k, dk, dks, G, D, n_cells, k_cache) || !cache_rows_from_planes(type_v, dv, dvs, G, D, n_cells, v_cache)) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-// The attention of ONE batched single-token step - T tokens, up to 64, as a continuous-batching step holds them - in each form Context::attn_core launches it
-// (test entry).  q [T][H * D] un-rotated, k_new / v_new [T][G * D]; k_cache / v_cache: the whole cache as ggml-layout rows [n_cells][G * D], in and out;
-// cell_pos / cell_seq [n_cells] with the new cells already set (cell_pos[tok_cell[t]] = tok_pos[t], bit tok_seq[t] of cell_seq[tok_cell[t]]); n_kv: cells to
-// scan (what the device reads), every launch is sized for n_cells.
-//   mode 0: K rope + K / V store inside the attention launch (launch_flash_attn_decode with the new rows), every chunk of the cache scanned;
-//   mode 1: the same launch on the per-token chunk lists of host/attn_chunks.h;
-//   mode 2: launch_kv_store_fast, then launch_flash_attn_decode without the store, on the lists;
-//   mode 3: the generic path, launch_rope_kv_store + launch_flash_attn.
-// att_out [T][H * D]; q8k_out (nullable; H * D a multiple of 256): the Q8_K blocks of the T rows that the merge wrote for attn_output, as ggml block_q8_K.
-// A shape or mode without a kernel is refused before anything is launched: more than 64 tokens, a token in several or in another token's sequence (modes 0
-// and 1: no token may read another's new cell), what flash_attn_decode_applicable (modes 0 - 2) or kv_store_fast_applicable (the lists, mode 2) reject.
-int mi355_op_attn_batch_step(const float *q, const float *k_new, const float *v_new, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, void *k_cache,
-                             int32_t type_v, void *v_cache, int32_t n_cells, int32_t n_kv, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *tok_pos,
-                             const int32_t *tok_seq, const int32_t *tok_cell, float rope_base, int32_t n_rot, int32_t neox, float scale, int32_t mode,
-                             float *att_out, void *q8k_out) {
-    return mi355_op_attn_batch_step_planes(q, k_new, v_new, T, H, G, D, type_k, k_cache, type_v, v_cache, n_cells, n_kv, cell_pos, cell_seq, tok_pos, tok_seq, tok_cell,
-                                           rope_base, n_rot, neox, scale, mode, att_out, q8k_out, nullptr, nullptr);
-}
-// bh_out / bl_out (both or neither, with q8k_out): the merge also writes the block sums of its Q8_K rows as the int8 planes of the MFMA kernels (AttnArgs out_bh /
-// out_bl, what Context::attn_core sets for a K-quant attn_output); the planes are 0xFF bytes before the launch
-int mi355_op_attn_batch_step_planes(const float *q, const float *k_new, const float *v_new, int64_t T, int32_t H, int32_t G, int32_t D, int32_t type_k, void *k_cache,
-                                    int32_t type_v, void *v_cache, int32_t n_cells, int32_t n_kv, const int32_t *cell_pos, const uint64_t *cell_seq, const int32_t *tok_pos,
-                                    const int32_t *tok_seq, const int32_t *tok_cell, float rope_base, int32_t n_rot, int32_t neox, float scale, int32_t mode,
-                                    float *att_out, void *q8k_out, int8_t *bh_out, int8_t *bl_out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if ((bh_out != nullptr) != (bl_out != nullptr) || (bh_out && !q8k_out)) { fail("attn_batch_step: bh_out / bl_out come together and with q8k_out"); return MI355_ERR_ARG; }
-    if (!q || !k_new || !v_new || !k_cache || !v_cache || !cell_pos || !cell_seq || !tok_pos || !tok_seq || !tok_cell || !att_out) { fail("attn_batch_step: null argument"); return MI355_ERR_ARG; }
-    if (mode < 0 || mode > 3) { fail("attn_batch_step: mode outside [0, 3]"); return MI355_ERR_ARG; }
-    if (T < 1 || T > 64) { fail("attn_batch_step: a batched step holds 1 .. 64 tokens"); return MI355_ERR_ARG; }
-    if ((D != 64 && D != 128) || G < 1 || H < 1 || H % G || H / G > 8 || n_cells < 1 || n_kv < 1 || n_kv > n_cells || n_rot < 2 || n_rot > D || n_rot % 2) { fail("attn_batch_step: bad geometry"); return MI355_ERR_ARG; }
-    if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("attn_batch_step: bad cache type"); return MI355_ERR_ARG; }
-    const size_t K = (size_t)H * D, kv_dim = (size_t)G * D;
-    if (q8k_out && K % 256) { fail("attn_batch_step: Q8_K rows need n_head * head_dim to be a multiple of 256"); return MI355_ERR_ARG; }
-    uint64_t seen = 0;
-    for (int64_t t = 0; t < T; t++) {
-        if (tok_seq[t] < 0 || tok_seq[t] > 63) { fail("attn_batch_step: tok_seq[" + std::to_string(t) + "] outside [0, 63]"); return MI355_ERR_ARG; }
-        if (tok_cell[t] < 0 || tok_cell[t] >= n_kv) { fail("attn_batch_step: tok_cell[" + std::to_string(t) + "] outside the scanned cells"); return MI355_ERR_ARG; }
-        const uint64_t bit = 1ull << tok_seq[t];
-        if (mode < 2 && ((seen & bit) || cell_seq[tok_cell[t]] != bit)) { fail("attn_batch_step: the store-fused launch needs every token in one sequence of its own"); return MI355_ERR_ARG; }
-        seen |= bit;
-    }
-    RopeArgs ra{};
-    ra.n_rot = n_rot; ra.freq_base = rope_base; ra.freq_scale = 1.0f; ra.freq_factors = nullptr; ra.neox = neox ? 1 : 0;
-    AttnArgs a{};
-    a.type_k = type_k; a.type_v = type_v; a.T = (int)T; a.H = H; a.G = G; a.D = D; a.n_ctx = n_cells; a.n_kv_max = n_cells; a.scale = scale;
-    if (mode < 3 && !flash_attn_decode_applicable(a, ra)) { fail("attn_batch_step: the decode attention has no form for this shape"); return MI355_ERR_ARG; }
-    if ((mode == 1 || mode == 2) && !kv_store_fast_applicable(G, D, type_k, type_v, ra)) { fail("attn_batch_step: the small-batch store has no form for these arguments (no chunk lists either)"); return MI355_ERR_ARG; }
-    if (mode == 3 && ((size_t)n_rot + kv_dim) * 4 > 48 * 1024) { fail("attn_batch_step: n_head_kv * head_dim too wide for the generic store's LDS"); return MI355_ERR_ARG; }
-    std::vector<uint8_t> kc, vc;
-    std::vector<uint16_t> ks, vs;
-    cache_planes_from_rows(type_k, k_cache, G, D, n_cells, kc, ks);
-    cache_planes_from_rows(type_v, v_cache, G, D, n_cells, vc, vs);
-    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dv(vc.size()), dvs(vs.size() * 2 + 16);
-    DevBuf dq((size_t)T * K * 4), dkn((size_t)T * kv_dim * 4), dvn((size_t)T * kv_dim * 4), datt((size_t)T * K * 4), dcp((size_t)n_cells * 4), dcs((size_t)n_cells * 8);
-    DevBuf dtp((size_t)T * 4), dts((size_t)T * 4), dcell((size_t)T * 4), dn(16), dcsb((size_t)T * n_rot * 4 + 64), dblk(q8k_out ? ggml_row_bytes(T_Q8_K, (int64_t)K) * T : 16);
-    ActBufs ab(q8k_out ? K : 256, (size_t)T + 1);
-    const size_t pb = bh_out ? (size_t)T * (K / 16) : 0;
-    DevBuf dbh(pb ? pb : 16), dbl(pb ? pb : 16);
-    if (!dbh.p || !dbl.p || hipMemset(dbh.p, 0xFF, dbh.n) != hipSuccess || hipMemset(dbl.p, 0xFF, dbl.n) != hipSuccess) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    if (!dk.up(kc.data(), kc.size()) || !dv.up(vc.data(), vc.size()) || !dks.p || !dvs.p || !dq.up(q, (size_t)T * K * 4) || !dkn.up(k_new, (size_t)T * kv_dim * 4) ||
-        !dvn.up(v_new, (size_t)T * kv_dim * 4) || !datt.p || !dcp.up(cell_pos, (size_t)n_cells * 4) || !dcs.up(cell_seq, (size_t)n_cells * 8) ||
-        !dtp.up(tok_pos, (size_t)T * 4) || !dts.up(tok_seq, (size_t)T * 4) || !dcell.up(tok_cell, (size_t)T * 4) || !dn.up(&n_kv, 4) || !dcsb.p || !dblk.p || !ab.ok()) {
-        fail("device alloc/copy failed"); return MI355_ERR_OOM;
-    }
-    if (!ks.empty() && !dks.up(ks.data(), ks.size() * 2)) return MI355_ERR_OOM;
-    if (!vs.empty() && !dvs.up(vs.data(), vs.size() * 2)) return MI355_ERR_OOM;
-    ChunkLists cl;
-    if ((mode == 1 || mode == 2) && !cl.make(n_kv, n_cells, cell_pos, cell_seq, tok_seq, (int)T)) return MI355_ERR_OOM;
-    a.q = dq.as<float>(); a.out = datt.as<float>();
-    a.kv.k = dk.as<uint8_t>(); a.kv.kd = dks.as<uint16_t>(); a.kv.v = dv.as<uint8_t>(); a.kv.vd = dvs.as<uint16_t>();
-    a.cell_pos = dcp.as<int32_t>(); a.cell_seq = dcs.as<uint64_t>(); a.tok_pos = dtp.as<int32_t>(); a.tok_seq = dts.as<int32_t>(); a.n_kv_dev = dn.as<int32_t>();
-    if (q8k_out) { a.out_q = &ab.q; a.out_q8k = true; a.out_q80 = false; }
-    if (bh_out) { a.out_bh = dbh.as<int8_t>(); a.out_bl = dbl.as<int8_t>(); }
-    if (mode == 3) {
-        a.splits = flash_attn_pick_splits((int)T, G, n_cells);
-        a.pf_splits = flash_attn_prefill_splits((int)T, H, G, D, n_cells);
-    } else {
-        a.splits = flash_attn_decode_splits(n_cells);
-        if (mode != 0) cl.apply(a);
-    }
-    DevBuf part(flash_attn_workspace_floats((int)T, H, D, std::max(a.splits, a.pf_splits)) * 4);
-    if (!part.p) return MI355_ERR_OOM;
-    a.part = part.as<float>();
-    hipError_t e = launch_rope_table(dtp.as<int32_t>(), (int)T, ra, dcsb.as<float>(), nullptr);
-    if (e != hipSuccess) return hip_fail(e, "rope_table");
-    if (mode == 3) {
-        e = launch_rope_kv_store(dq.as<float>(), dkn.as<float>(), dvn.as<float>(), (int)T, H, G, D, dtp.as<int32_t>(), dcell.as<int32_t>(), ra, a.kv, type_k, type_v, n_cells,
-                                 dcsb.as<float>(), nullptr);
-        if (e == hipSuccess) e = launch_flash_attn(a, nullptr);
-    } else if (mode == 2) {
-        e = launch_kv_store_fast(dkn.as<float>(), dvn.as<float>(), (int)T, G, D, dcsb.as<float>(), ra, dcell.as<int32_t>(), a.kv, type_k, type_v, n_cells, nullptr);
-        if (e == hipSuccess) e = launch_flash_attn_decode(a, dcsb.as<float>(), ra, nullptr);
-    } else {
-        e = launch_flash_attn_decode(a, dcsb.as<float>(), ra, nullptr, dkn.as<float>(), dvn.as<float>(), dcell.as<int32_t>());
-    }
-    if (e == hipSuccess && q8k_out) e = launch_pack_q8k_blocks(ab.q, (int)K, (int)T, dblk.as<uint8_t>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "attn_batch_step");
-    if (!datt.down(att_out, (size_t)T * K * 4)) return MI355_ERR_HIP;
-    if (q8k_out && !dblk.down(q8k_out, ggml_row_bytes(T_Q8_K, (int64_t)K) * T)) return MI355_ERR_HIP;
-    if (bh_out && (!dbh.down(bh_out, pb) || !dbl.down(bl_out, pb))) return MI355_ERR_HIP;
-    if (!cache_rows_from_planes(type_k, dk, dks, G, D, n_cells, k_cache) || !cache_rows_from_planes(type_v, dv, dvs, G, D, n_cells, v_cache)) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-// The K-shift on its own (test entry): one launch_k_shift over a caller-supplied K cache that crosses the boundary whole, in and out.
-int mi355_op_k_shift(int32_t type_k, int32_t G, int32_t D, int32_t n_rot, int32_t neox, int32_t n_cells, const int32_t *delta, float rope_base, float freq_scale,
-                     const float *freq_factors, float ext_factor, float attn_factor, float corr_lo, float corr_hi, void *k_cache) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!delta || !k_cache || G < 1 || D < 32 || D % 32 || n_rot < 2 || n_rot > D || n_rot % 2 || n_cells < 1) { fail("bad geometry / null argument"); return MI355_ERR_ARG; }
-    if (type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) { fail("bad cache type"); return MI355_ERR_ARG; }
-    if (((size_t)n_rot + (size_t)G * D) * 4 > 48 * 1024) { fail("n_head_kv * head_dim too wide for the kernel's LDS"); return MI355_ERR_ARG; }
-    std::vector<uint8_t> kc;
-    std::vector<uint16_t> ks;
-    cache_planes_from_rows(type_k, k_cache, G, D, n_cells, kc, ks);
-    DevBuf dk(kc.size()), dks(ks.size() * 2 + 16), dd((size_t)n_cells * 4), dff((size_t)n_rot * 2 + 16);
-    if (!dk.up(kc.data(), kc.size()) || !dks.p || !dd.up(delta, (size_t)n_cells * 4) || (freq_factors && !dff.up(freq_factors, (size_t)(n_rot / 2) * 4))) {
-        fail("device alloc/copy failed"); return MI355_ERR_OOM;
-    }
-    if (!ks.empty() && !dks.up(ks.data(), ks.size() * 2)) return MI355_ERR_OOM;
-    RopeArgs ra{};
-    ra.n_rot = n_rot; ra.freq_base = rope_base; ra.freq_scale = freq_scale; ra.freq_factors = freq_factors ? dff.as<float>() : nullptr; ra.neox = neox ? 1 : 0;
-    ra.ext_factor = ext_factor; ra.attn_factor = attn_factor; ra.corr_lo = corr_lo; ra.corr_hi = corr_hi;
-    KVLayerView kv{};
-    kv.k = dk.as<uint8_t>(); kv.kd = dks.as<uint16_t>();
-    hipError_t e = launch_k_shift(kv, type_k, G, D, n_cells, dd.as<int32_t>(), ra, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "k_shift");
-    return cache_rows_from_planes(type_k, dk, dks, G, D, n_cells, k_cache) ? MI355_OK : MI355_ERR_HIP;
-}
-
-// The gather / scatter kernels of a sequence's state on their own (test entries): a cache of n_layer layers crosses the boundary as ggml-layout rows per layer and is
-// uploaded into device planes; `cells` is checked here, as Context::state_seq_get / set check their own lists before they launch.
-namespace {
-struct StateOpCache {
-    std::vector<std::unique_ptr<DevBuf>> bufs;       // per layer: K codes, K scales, V codes, V scales
-    std::vector<KVLayerView> views;
-    std::unique_ptr<DevBuf> table, cells, rows;
-    size_t row_bytes = 0;
-    int init(int type_k, int type_v, int n_layer, int G, int D, int n_cells, const void *const *k_rows, const void *const *v_rows, const int32_t *cell_list, int n, bool distinct) {
-        if (!k_rows || !v_rows || !cell_list || n_layer < 1 || n_layer > 1024 || G < 1 || D < 32 || D % 32 || n_cells < 1 || n < 1 || n > n_cells) { fail("kv_state: bad geometry / null argument"); return MI355_ERR_ARG; }
-        if ((type_k != T_F16 && type_k != T_Q8_0 && type_k != T_Q4_0) || (type_v != T_F16 && type_v != T_Q8_0 && type_v != T_Q4_0)) { fail("kv_state: bad cache type"); return MI355_ERR_ARG; }
-        std::vector<char> seen((size_t)n_cells, 0);
-        for (int i = 0; i < n; i++) {
-            if (cell_list[i] < 0 || cell_list[i] >= n_cells) { fail("kv_state: cells[" + std::to_string(i) + "] outside the cache"); return MI355_ERR_ARG; }
-            if (distinct && seen[(size_t)cell_list[i]]) { fail("kv_state: cells[" + std::to_string(i) + "] listed twice"); return MI355_ERR_ARG; }
-            seen[(size_t)cell_list[i]] = 1;
-        }
-        views.resize((size_t)n_layer);
-        for (int il = 0; il < n_layer; il++) {
-            if (!k_rows[il] || !v_rows[il]) { fail("kv_state: null layer"); return MI355_ERR_ARG; }
-            std::vector<uint8_t> kc, vc;
-            std::vector<uint16_t> ks, vs;
-            cache_planes_from_rows(type_k, k_rows[il], G, D, n_cells, kc, ks);
-            cache_planes_from_rows(type_v, v_rows[il], G, D, n_cells, vc, vs);
-            DevBuf *b[4] = {new DevBuf(kc.size()), new DevBuf(ks.size() * 2 + 16), new DevBuf(vc.size()), new DevBuf(vs.size() * 2 + 16)};
-            for (DevBuf *p : b) bufs.emplace_back(p);
-            if (!b[0]->up(kc.data(), kc.size()) || !b[2]->up(vc.data(), vc.size()) || !b[1]->p || !b[3]->p || (!ks.empty() && !b[1]->up(ks.data(), ks.size() * 2)) ||
-                (!vs.empty() && !b[3]->up(vs.data(), vs.size() * 2))) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-            views[(size_t)il].k = b[0]->as<uint8_t>(); views[(size_t)il].kd = b[1]->as<uint16_t>(); views[(size_t)il].v = b[2]->as<uint8_t>(); views[(size_t)il].vd = b[3]->as<uint16_t>();
-        }
-        row_bytes = (size_t)n_layer * n * (kv_state_row_bytes(type_k, G, D) + kv_state_row_bytes(type_v, G, D));
-        table.reset(new DevBuf(views.size() * sizeof(KVLayerView)));
-        cells.reset(new DevBuf((size_t)n * 4));
-        rows.reset(new DevBuf(row_bytes));
-        if (!table->up(views.data(), views.size() * sizeof(KVLayerView)) || !cells->up(cell_list, (size_t)n * 4) || !rows->p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-        return MI355_OK;
-    }
-};
-}  // namespace
-
-int mi355_op_kv_state_pack(int32_t type_k, int32_t type_v, int32_t n_layer, int32_t G, int32_t D, int32_t n_cells, const void *const *k_rows, const void *const *v_rows,
-                           const int32_t *cells, int32_t n, void *out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!out) { fail("kv_state_pack: null output"); return MI355_ERR_ARG; }
-    StateOpCache c;
-    if (const int rc = c.init(type_k, type_v, n_layer, G, D, n_cells, k_rows, v_rows, cells, n, false)) return rc;
-    hipError_t e = launch_kv_state_pack(c.table->as<KVLayerView>(), n_layer, type_k, type_v, G, D, n_cells, c.cells->as<int32_t>(), n, c.rows->as<uint8_t>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "kv_state_pack");
-    return c.rows->down(out, c.row_bytes) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_kv_state_unpack(int32_t type_k, int32_t type_v, int32_t n_layer, int32_t G, int32_t D, int32_t n_cells, const void *in, const int32_t *cells, int32_t n,
-                             void *const *k_rows, void *const *v_rows) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!in) { fail("kv_state_unpack: null input"); return MI355_ERR_ARG; }
-    StateOpCache c;
-    if (const int rc = c.init(type_k, type_v, n_layer, G, D, n_cells, k_rows, v_rows, cells, n, true)) return rc;
-    if (!c.rows->up(in, c.row_bytes)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_kv_state_unpack(c.table->as<KVLayerView>(), n_layer, type_k, type_v, G, D, n_cells, c.cells->as<int32_t>(), n, c.rows->as<uint8_t>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "kv_state_unpack");
-    for (int il = 0; il < n_layer; il++)
-        if (!cache_rows_from_planes(type_k, *c.bufs[(size_t)il * 4], *c.bufs[(size_t)il * 4 + 1], G, D, n_cells, k_rows[il]) ||
-            !cache_rows_from_planes(type_v, *c.bufs[(size_t)il * 4 + 2], *c.bufs[(size_t)il * 4 + 3], G, D, n_cells, v_rows[il])) return MI355_ERR_HIP;
-    return MI355_OK;
-}
-
-// ------------------------------------------------------------------ the LLaVA image encoder's launches, one at a time (tests/test_gpu_clip_ops.py)
-// The tower's attention.  The kernel is named by the function the launcher asks (clip_attn_choice): a refusal returns here, before anything is launched.
-int mi355_op_clip_attn(const float *q, const float *k, const float *v, int64_t T, int32_t H, int32_t D, int32_t n_img, float *out, uint16_t *out_h, int32_t *path) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!q || !k || !v || !out || !path || T < 1 || T > (1 << 20) || H < 1 || D < 4 || D % 4 || n_img < 1) { fail("clip_attn: bad args"); return MI355_ERR_ARG; }
-    const ClipAttnChoice ch = clip_attn_choice((int)T, D);
-    *path = ch.path;
-    if (ch.path == CLIP_ATTN_REFUSED) { fail("clip_attn: no kernel for this head size and row count"); return MI355_ERR_ARG; }
-    const size_t n = (size_t)n_img * T * H * D;
-    DevBuf dq(n * 4), dk(n * 4), dv(n * 4), dout(n * 4), dh(n * 2);
-    if (!dq.up(q, n * 4) || !dk.up(k, n * 4) || !dv.up(v, n * 4) || !dout.p || !dh.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_clip_attn(dq.as<float>(), dk.as<float>(), dv.as<float>(), (int)T, H, D, dout.as<float>(), out_h ? dh.p : nullptr, n_img, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "clip_attn");
-    if (out_h && !dh.down(out_h, n * 2)) return MI355_ERR_HIP;
-    return dout.down(out, n * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_mul_mat_f16_xh(const uint16_t *W, int64_t N, int64_t K, const float *x, int64_t T, int64_t ld_out, const float *bias, float scale, int32_t do_scale,
-                            const float *resid, int32_t in_place, int32_t form, float *y_io) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!W || !x || !y_io || N < 1 || K < 8 || K % 8 || T < 1 || ld_out < N || (form != 0 && form != 1) || (in_place && resid) ||
-        (form == 1 && (ld_out != N || (do_scale && !bias)))) { fail("mul_mat_f16_xh: bad args"); return MI355_ERR_ARG; }
-    const size_t yb = (size_t)T * ld_out * 4;
-    DevBuf dw((size_t)N * K * 2), dx((size_t)T * K * 4), dxh((size_t)T * K * 2), dy(yb), dr(resid ? yb : 0), db(bias ? (size_t)N * 4 : 0), tmp(form == 1 ? yb : 0);
-    if (!dw.up(W, (size_t)N * K * 2) || !dx.up(x, (size_t)T * K * 4) || !dxh.p || !dy.up(y_io, yb) || (resid && !dr.up(resid, yb)) || (bias && !db.up(bias, (size_t)N * 4)) || !tmp.p) {
-        fail("device alloc/copy failed");
-        return MI355_ERR_OOM;
-    }
-    const float *rs = in_place ? dy.as<float>() : resid ? dr.as<float>() : nullptr, *bs = bias ? db.as<float>() : nullptr;
-    hipError_t e = hipSuccess;
-    if (form == 0) {
-        e = launch_f32_to_f16(dx.as<float>(), dxh.p, (size_t)T * K, nullptr);
-        if (e == hipSuccess) e = launch_mmf16_xh(dw.as<uint8_t>(), (int)N, (int)K, dxh.p, (int)T, dy.as<float>(), (int)ld_out, rs, bs, scale, do_scale != 0, nullptr);
-    } else {                                                    // host/clip.cc, MI355_CLIP_XH=0: the product into scratch when a residual follows
-        float *dst = rs ? tmp.as<float>() : dy.as<float>();
-        e = launch_mmf16(dw.as<uint8_t>(), (int)N, (int)K, dx.as<float>(), (int)T, dst, (int)N, nullptr, nullptr);
-        if (e == hipSuccess && bs) e = launch_clip_bias(dst, bs, (int)N, (int)T, scale, do_scale != 0, nullptr);
-        if (e == hipSuccess && rs) e = launch_add(rs, dst, dy.as<float>(), (int64_t)T * N, nullptr);
-    }
-    const hipError_t es = hipDeviceSynchronize();
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return hip_fail(e, "mul_mat_f16_xh");
-    return dy.down(y_io, yb) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_layer_norm(const float *x, const float *w, const float *b, int64_t n, int64_t T, float eps, int32_t in_place, float *y, uint16_t *y_h) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!x || !w || !b || !y || n < 1 || T < 1) { fail("layer_norm: bad args"); return MI355_ERR_ARG; }
-    const size_t nb = (size_t)n * T * 4;
-    DevBuf dx(nb), dw((size_t)n * 4), db((size_t)n * 4), dy(in_place ? 0 : nb), dh(nb / 2);
-    if (!dx.up(x, nb) || !dw.up(w, (size_t)n * 4) || !db.up(b, (size_t)n * 4) || !dy.p || !dh.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    float *o = in_place ? dx.as<float>() : dy.as<float>();
-    hipError_t e = y_h ? launch_layer_norm_h(dx.as<float>(), dw.as<float>(), db.as<float>(), (int)n, (int)T, eps, o, dh.p, nullptr)
-                       : launch_layer_norm(dx.as<float>(), dw.as<float>(), db.as<float>(), (int)n, (int)T, eps, o, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "layer_norm");
-    if (y_h && !dh.down(y_h, nb / 2)) return MI355_ERR_HIP;
-    return hipMemcpy(y, o, nb, hipMemcpyDeviceToHost) == hipSuccess ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_clip_gelu(const float *x, int64_t n, int32_t quick, float *y, uint16_t *y_h) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!x || !y || n < 1) { fail("clip_gelu: bad args"); return MI355_ERR_ARG; }
-    DevBuf dx((size_t)n * 4), dh((size_t)n * 2);
-    if (!dx.up(x, (size_t)n * 4) || !dh.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_clip_gelu(dx.as<float>(), (size_t)n, quick != 0, y_h ? dh.p : nullptr, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "clip_gelu");
-    if (y_h && !dh.down(y_h, (size_t)n * 2)) return MI355_ERR_HIP;
-    return dx.down(y, (size_t)n * 4) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_clip_im2col(const float *img, int32_t S, int32_t P, int32_t ld, float *patches_io) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!img || !patches_io || P < 1 || S < P || S % P || ld < 3 * P * P) { fail("clip_im2col: bad args"); return MI355_ERR_ARG; }
-    const size_t ib = (size_t)3 * S * S * 4, pb = (size_t)(S / P) * (S / P) * ld * 4;
-    DevBuf di(ib), dp(pb);
-    if (!di.up(img, ib) || !dp.up(patches_io, pb)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_clip_im2col(di.as<float>(), S, P, ld, dp.as<float>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "clip_im2col");
-    return dp.down(patches_io, pb) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_clip_embed(const float *patch, const float *cls, const float *pos, int32_t E, int32_t T, float *emb) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!patch || !cls || !pos || !emb || E < 1 || T < 2) { fail("clip_embed: bad args"); return MI355_ERR_ARG; }
-    const size_t rb = (size_t)E * 4;
-    DevBuf dpa(rb * (T - 1)), dc(rb), dpo(rb * T), de(rb * T);
-    if (!dpa.up(patch, rb * (T - 1)) || !dc.up(cls, rb) || !dpo.up(pos, rb * T) || !de.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_clip_embed(dpa.as<float>(), dc.as<float>(), dpo.as<float>(), E, T, de.as<float>(), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "clip_embed");
-    return de.down(emb, rb * T) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_clip_bias(float *x_io, const float *b, int32_t n, int32_t T, float scale, int32_t do_scale) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!x_io || !b || n < 1 || T < 1) { fail("clip_bias: bad args"); return MI355_ERR_ARG; }
-    const size_t nb = (size_t)n * T * 4;
-    DevBuf dx(nb), db((size_t)n * 4);
-    if (!dx.up(x_io, nb) || !db.up(b, (size_t)n * 4)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_clip_bias(dx.as<float>(), db.as<float>(), n, T, scale, do_scale != 0, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "clip_bias");
-    return dx.down(x_io, nb) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_f32_to_f16(const float *x, int64_t n, uint16_t *out) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (!x || !out || n < 4 || n % 4) { fail("f32_to_f16: n must be a positive multiple of 4"); return MI355_ERR_ARG; }
-    DevBuf dx((size_t)n * 4), dy((size_t)n * 2);
-    if (!dx.up(x, (size_t)n * 4) || !dy.p) { fail("device alloc/copy failed"); return MI355_ERR_OOM; }
-    hipError_t e = launch_f32_to_f16(dx.as<float>(), dy.p, (size_t)n, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "f32_to_f16");
-    return dy.down(out, (size_t)n * 2) ? MI355_OK : MI355_ERR_HIP;
-}
-
-int mi355_op_add_qkv_bias(float *q_io, float *k_io, float *v_io, const float *bq, const float *bk, const float *bv, int32_t nq, int32_t nkv, int32_t T) {
-    if (!need_device()) return MI355_ERR_NO_DEVICE;
-    if (nq < 1 || nkv < 0 || T < 1 || (bq && !q_io) || (bk && !k_io) || (bv && !v_io) || ((bk || bv) && nkv < 1)) { fail("add_qkv_bias: bad args"); return MI355_ERR_ARG; }
-    float *const xs[3] = {q_io, k_io, v_io};
-    const float *const bs[3] = {bq, bk, bv};
-    std::unique_ptr<DevBuf> dx[3], db[3];
-    for (int s = 0; s < 3; s++) {
-        const size_t n = s == 0 ? (size_t)nq : (size_t)nkv;
-        if (xs[s]) { dx[s].reset(new DevBuf(n * T * 4)); if (!dx[s]->up(xs[s], n * T * 4)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; } }
-        if (bs[s]) { db[s].reset(new DevBuf(n * 4)); if (!db[s]->up(bs[s], n * 4)) { fail("device alloc/copy failed"); return MI355_ERR_OOM; } }
-    }
-    auto xp = [&](int s) { return dx[s] ? dx[s]->as<float>() : nullptr; };
-    auto bp = [&](int s) { return db[s] ? db[s]->as<float>() : nullptr; };
-    hipError_t e = launch_add_qkv_bias(xp(0), xp(1), xp(2), bp(0), bp(1), bp(2), nq, nkv, T, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "add_qkv_bias");
-    for (int s = 0; s < 3; s++)
-        if (xs[s] && !dx[s]->down(xs[s], (s == 0 ? (size_t)nq : (size_t)nkv) * T * 4)) return MI355_ERR_HIP;
     return MI355_OK;
 }
 

@@ -1,6 +1,6 @@
 // host/attn_chunks.h — per-token chunk lists of a batched single-token step (AttnArgs::tok_chunks / tok_nchunks, kernels.h).
-// Host code only, no HIP: Context::decode_ubatch builds the lists with it before every step that uses them, the attention test entry of c_api.cc builds the
-// lists it launches with, and tests/host/host_tests.cc checks it against a restatement.
+// Host code only, no HIP: Context::decode_ubatch builds the lists with it before every step that uses them, the attention test entries (csrc/op_entries_attn.cc, through
+// op_support.h ChunkLists) build the lists they launch with, and tests/host/host_tests.cc checks it against a restatement.
 #pragma once
 #include <algorithm>
 #include <cstdint>

@@ -81,7 +81,7 @@ struct Fuse {   // fused activation prologue of the single-token mat-vec (mmvq.h
     float *out_host = nullptr;   // the launch also stores its results here (pinned host memory; the output head of a single-token step) - weight stream only
 };
 
-// The mat-vec launches as a step issues them, shared with the per-op test entry (c_api.cc mi355_op_mat_vec_step) so that model and test run one piece of code:
+// The mat-vec launches as a step issues them, shared with the per-op test entry (csrc/op_entries_matmul.cc mi355_op_mat_vec_step) so that model and test run one piece of code:
 // a weight tensor as a launch segment; a single-token launch's description without its segments; T tokens as launches of 16 / 8 / 4 / 2 / 1.
 // trace (nullable): one record per launch issued - its token count and the kernel launch_mmvq takes for it (kernels.h mmvq_kernel_choice / mmvq_stream_form).
 struct MMVQTrace {
@@ -94,7 +94,7 @@ MMVQArgs single_token_desc(int n_seg, int K, int epi, int fuse, const float *nx,
 hipError_t mmvq_tokens(MMVQSeg *segs, int n_seg, int K, int T, int epi, const ActQuant &aq, hipStream_t st, const Fuse &fz = Fuse(), MMVQTrace *trace = nullptr);
 // Which MFMA launch the K-quant (and planes-only) tensors of a prompt batch or a batched decode step take: the order of predicates that Context::linear
 // (PM_ROLE_ONE), Context::linear_multi (PM_ROLE_MULTI) and the dense gate | up block (PM_ROLE_GATE_UP, ws = {gate, up}) test, stated once and shared with the
-// per-op test entry (c_api.cc mi355_op_prompt_mul_mat).  PM_NONE: none of them - the caller goes on to its other paths.
+// per-op test entry (csrc/op_entries_matmul.cc mi355_op_prompt_mul_mat).  PM_NONE: none of them - the caller goes on to its other paths.
 enum { PM_NONE = 0, PM_KSPLIT = 1, PM_PLANES = 2, PM_FLY = 3 };
 enum { PM_ROLE_ONE = 0, PM_ROLE_MULTI = 1, PM_ROLE_GATE_UP = 2 };
 struct PromptMatmul {

@@ -113,6 +113,22 @@ def test_no_cpu_fallback(pkg):
     assert lib.mi355_op_add_qkv_bias(y.ctypes.data, None, None, x.ctypes.data, None, None, 16, 0, 4) == -100
 
 
+def test_every_op_entry_checks_the_device_first(pkg):
+    """Every per-op test entry answers MI355_ERR_NO_DEVICE before it looks at an argument: each mi355_op_* symbol is called with zeros and null pointers made
+    from its declared argtypes, which is safe only because the device check comes first - and this test keeps it first."""
+    lib = pkg.load_library()
+    if lib.mi355_device_count() > 0:
+        pytest.skip("GPU present")
+    names = sorted(n for n in pkg.binding.SYMBOLS if n.startswith("mi355_op_"))
+    assert len(names) > 50
+    for name in names:
+        restype, argtypes = pkg.binding.SYMBOLS[name]
+        assert restype is not None, name
+        rc = getattr(lib, name)(*[t() for t in argtypes])
+        assert rc == -100, name
+        assert lib.mi355_last_error(), name
+
+
 def test_product_does_not_touch_oracle():
     """The product path (package + C-ABI sources) must never import / link / call the oracle."""
     pkg_dir = os.path.join(ROOT, "cortex.llamacpp_amd")
