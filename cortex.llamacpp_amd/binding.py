@@ -115,6 +115,10 @@ SYMBOLS = {
     "mi355_set_adapter_lora": (_i32, [_vp, _vp, _f32]),
     "mi355_rm_adapter_lora": (_i32, [_vp, _vp]),
     "mi355_clear_adapter_lora": (None, [_vp]),
+    "mi355_apply_adapter_cvec": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32]),
+    "mi355_control_vector_load": (_i64, [_vp, _vp, _i32, _vp, _sz, _vp]),
+    "mi355_cvec_direction": (C.c_int, [_i32, _vp, _i64, _i32, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "mi355_op_add_row_vec": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "mi355_op_lora_delta": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "mi355_kv_cache_clear": (None, [_vp]),
     "mi355_kv_cache_seq_rm": (_i32, [_vp, _i32, _i32, _i32]),
@@ -279,6 +283,23 @@ def _ptr(a):
 
 def _err(lib) -> str:
     return (lib.mi355_last_error() or b"").decode("utf-8", "replace")
+
+
+def control_vector_load(lib, items):
+    """mi355_control_vector_load on a loaded library (host arithmetic, no device): items = [(path, scale), ...] -> (data f32, n_embd)."""
+    items = [(it, 1.0) if isinstance(it, (str, os.PathLike)) else it for it in items]
+    n = len(items)
+    paths = (C.c_char_p * max(n, 1))(*[os.fspath(p).encode() for p, _ in items])
+    scales = np.array([s for _, s in items] or [0.0], np.float32)
+    ne = C.c_int32(0)
+    need = int(lib.mi355_control_vector_load(C.cast(paths, C.c_void_p), _ptr(scales), n, None, 0, C.cast(C.byref(ne), C.c_void_p)))
+    if need < 0:
+        raise MI355Error(f"mi355_control_vector_load failed ({need}): {_err(lib)}")
+    out = np.zeros(need, np.float32)
+    got = int(lib.mi355_control_vector_load(C.cast(paths, C.c_void_p), _ptr(scales), n, _ptr(out), need, None))
+    if got != need:
+        raise MI355Error(f"mi355_control_vector_load failed ({got}): {_err(lib)}")
+    return out, int(ne.value)
 
 
 class Backend:
@@ -726,6 +747,34 @@ class Backend:
         out = np.zeros((n_rows, n // be * bb if n % be == 0 else 1), np.uint8)
         self._chk(self.lib.mi355_quantize_chunk(dst_type, src_type, _ptr(x), n, n_rows, _ptr(im), _ptr(out)), "quantize_chunk")
         return out
+
+    def add_row_vec(self, x: np.ndarray, v: np.ndarray) -> np.ndarray:
+        """The control vector's add once (mi355_op_add_row_vec): x [T][E] + v [E]; returns [T + 1][E], the last row the guard row behind the rows (0xA5 bytes)."""
+        x = np.ascontiguousarray(x, np.float32)
+        v = np.ascontiguousarray(v, np.float32).reshape(-1)
+        T, E = x.shape
+        assert v.size == E
+        y = np.zeros((T + 1, E), np.float32)
+        self._chk(self.lib.mi355_op_add_row_vec(_ptr(x), _ptr(v), E, T, _ptr(y)), "op_add_row_vec")
+        return y
+
+    def load_control_vectors(self, items):
+        """common_control_vector_load (mi355_control_vector_load): items = [(path, scale), ...] -> (data f32 [n_layers_named * n_embd], n_embd)."""
+        return control_vector_load(self.lib, items)
+
+    def cvec_direction(self, rows: np.ndarray, init=None, method: str = "pca", n_iter: int = 1000, n_batch: int = 100, tol: float = 1e-7, dir_out=None):
+        """The direction of rows [R][E] (mi355_cvec_direction): (dir f32 [E], iterations, last distance).  dir_out: an array to receive it (tests)."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        assert rows.ndim == 2
+        R, E = rows.shape
+        ini = None if init is None else np.ascontiguousarray(init, np.float32).reshape(-1)
+        assert ini is None or ini.size == E
+        out = np.zeros(E, np.float32) if dir_out is None else dir_out
+        assert out.dtype == np.float32 and out.size == E and out.flags.c_contiguous
+        it = np.zeros(1, np.int32); dist = np.zeros(1, np.float32)
+        self._chk(self.lib.mi355_cvec_direction({"pca": 0, "mean": 1}.get(method, -1) if isinstance(method, str) else int(method), _ptr(rows), R, E, _ptr(ini),
+                                                int(n_iter), int(n_batch), float(tol), _ptr(out), _ptr(it), _ptr(dist)), "cvec_direction")
+        return out, int(it[0]), float(dist[0])
 
     def quantize_last_times(self):
         """(upload, kernel, download) milliseconds of this thread's last quantize_rows (mi355_quantize_last_times)"""
@@ -1332,6 +1381,20 @@ class Context:
 
     def clear_adapter_lora(self) -> None:
         self.lib.mi355_clear_adapter_lora(self.h)
+
+    def apply_cvec(self, data, il_start: int, il_end: int, n_embd: int | None = None) -> None:
+        """llama_apply_adapter_cvec: data = the vectors of layers 1, 2, ... back to back ([n][n_embd] or flat); layers il_start .. il_end take theirs from the
+        next step on.  None clears."""
+        if data is None:
+            return self.clear_cvec()
+        d = np.ascontiguousarray(data, np.float32)
+        ne = int(n_embd if n_embd is not None else (d.shape[-1] if d.ndim == 2 else self.model.n_embd))
+        if self.lib.mi355_apply_adapter_cvec(self.h, _ptr(d), d.size, ne, int(il_start), int(il_end)) != 0:
+            raise MI355Error(f"mi355_apply_adapter_cvec failed: {_err(self.lib)}")
+
+    def clear_cvec(self) -> None:
+        if self.lib.mi355_apply_adapter_cvec(self.h, None, 0, 0, 0, 0) != 0:
+            raise MI355Error(f"mi355_apply_adapter_cvec (clear) failed: {_err(self.lib)}")
 
     def set_embeddings(self, on: bool = True) -> None:
         self.lib.mi355_set_embeddings(self.h, int(on))

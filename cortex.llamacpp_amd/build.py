@@ -20,9 +20,9 @@ EXPERIMENTS = os.environ.get("MI355_BUILD_EXPERIMENTS", "0") == "1"
 
 def sources(experiments: bool) -> list:
     return [
-        "csrc/mmvq.hip", "csrc/mmvq_fast.hip", "csrc/mmvq_stream.hip", "csrc/mmq.hip", "csrc/mmq_q80.hip", "csrc/act.hip", "csrc/misc.hip", "csrc/spec.hip", "csrc/logprob.hip", "csrc/imatrix.hip", "csrc/quantize.hip", "csrc/mmf.hip", "csrc/mmf_bf16.hip", "csrc/mmv_bf16.hip", "csrc/attn.hip", "csrc/attn_out.hip", "csrc/attn_prefill.hip", "csrc/clip.hip", "csrc/lora.hip", "csrc/kv_state.hip",
+        "csrc/mmvq.hip", "csrc/mmvq_fast.hip", "csrc/mmvq_stream.hip", "csrc/mmq.hip", "csrc/mmq_q80.hip", "csrc/act.hip", "csrc/misc.hip", "csrc/spec.hip", "csrc/logprob.hip", "csrc/imatrix.hip", "csrc/quantize.hip", "csrc/mmf.hip", "csrc/mmf_bf16.hip", "csrc/mmv_bf16.hip", "csrc/attn.hip", "csrc/attn_out.hip", "csrc/attn_prefill.hip", "csrc/clip.hip", "csrc/lora.hip", "csrc/kv_state.hip", "csrc/cvec.hip",
     ] + (["csrc/decode_engine.hip", "csrc/decode_mega.hip"] if experiments else ["csrc/experiments_absent.cc"]) + [
-        "host/gguf.cc", "host/model_plan.cc", "host/lora.cc", "host/runtime.cc", "host/tp_comm.cc", "host/vocab.cc", "host/sampling.cc", "host/grammar.cc", "host/json_schema.cc", "host/log.cc", "host/server_context.cc", "host/engine.cc",
+        "host/gguf.cc", "host/model_plan.cc", "host/lora.cc", "host/cvec.cc", "host/runtime.cc", "host/tp_comm.cc", "host/vocab.cc", "host/sampling.cc", "host/grammar.cc", "host/json_schema.cc", "host/log.cc", "host/server_context.cc", "host/engine.cc",
         "host/hip_backend.cc", "host/tp_split.cc", "host/clip.cc", "host/image_decode.cc", "csrc/c_api.cc",
         # the per-op test entries (mi355_op_*), by kernel family
         "csrc/op_entries_act.cc", "csrc/op_entries_matmul.cc", "csrc/op_entries_select.cc", "csrc/op_entries_attn.cc", "csrc/op_entries_clip.cc",
@@ -30,7 +30,7 @@ def sources(experiments: bool) -> list:
 
 
 SRC = sources(EXPERIMENTS)
-HDRS = ["csrc/dev_common.h", "csrc/ggml_types.h", "csrc/kernels.h", "csrc/spec_dev.h", "csrc/quant_dev.h", "csrc/mmvq_fast_dev.h", "csrc/mmvq_stream_dev.h", "csrc/attn_decode_dev.h", "csrc/op_support.h", "host/gguf.h", "host/model_plan.h", "host/lora.h", "host/runtime.h", "host/attn_chunks.h", "host/tp_comm.h", "host/json.h", "host/vocab.h",
+HDRS = ["csrc/dev_common.h", "csrc/ggml_types.h", "csrc/kernels.h", "csrc/spec_dev.h", "csrc/quant_dev.h", "csrc/mmvq_fast_dev.h", "csrc/mmvq_stream_dev.h", "csrc/attn_decode_dev.h", "csrc/op_support.h", "host/gguf.h", "host/model_plan.h", "host/lora.h", "host/cvec.h", "host/runtime.h", "host/attn_chunks.h", "host/tp_comm.h", "host/json.h", "host/vocab.h",
         "host/sampling.h", "host/grammar.h", "host/log.h", "host/backend_iface.h", "host/prompt_cache.h", "host/server_context.h", "host/engine.h", "host/hip_backend.h", "host/clip.h", "host/parallel_rows.h", "host/tp_split.h", "host/shm_exchange.h",
         "../include/mi355_llama.h"]
 LIB = os.path.join(HERE, "lib", "libmi355_llama.so")

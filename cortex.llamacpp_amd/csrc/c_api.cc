@@ -14,6 +14,7 @@
 
 #include "op_support.h"
 #include "../host/clip.h"
+#include "../host/cvec.h"
 #include "../host/engine.h"
 #include "../host/hip_backend.h"
 #include "../host/log.h"
@@ -493,6 +494,32 @@ int32_t mi355_rm_adapter_lora(mi355_context *ctx, mi355_adapter_lora *adapter) {
 }
 void mi355_clear_adapter_lora(mi355_context *ctx) { if (ctx) ctx->c->clear_adapter_lora(); }
 
+// ---- control vectors (llama_apply_adapter_cvec, common_control_vector_load)
+int32_t mi355_apply_adapter_cvec(mi355_context *ctx, const float *data, size_t len, int32_t n_embd, int32_t il_start, int32_t il_end) {
+    if (!ctx) return no_context("apply_adapter_cvec");
+    MI355_GUARD(return MI355_ERR_ARG,
+        if (ctx->c->apply_cvec(data, len, n_embd, il_start, il_end) != 0) { fail(ctx->c->last_error.empty() ? "apply_adapter_cvec failed" : ctx->c->last_error); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
+int64_t mi355_control_vector_load(const char *const *paths, const float *scales, int32_t n, float *out, size_t cap_floats, int32_t *n_embd_out) {
+    if (!paths || n < 1) { fail("control_vector_load: no file given"); return MI355_ERR_ARG; }
+    MI355_GUARD(return MI355_ERR_OOM,
+        std::vector<ControlVectorFile> files;
+        for (int32_t i = 0; i < n; i++) {
+            if (!paths[i]) { fail("control_vector_load: null path"); return MI355_ERR_ARG; }
+            files.push_back({paths[i], scales ? scales[i] : 1.0f});
+        }
+        std::vector<float> data;
+        int n_embd = 0;
+        std::string err;
+        if (!control_vector_load(files, data, n_embd, err)) { fail("control_vector_load: " + err); return MI355_ERR_FORMAT; }
+        if (n_embd_out) *n_embd_out = n_embd;
+        if (out && cap_floats >= data.size()) memcpy(out, data.data(), data.size() * sizeof(float));
+        return (int64_t)data.size();
+    )
+}
+
 // ---- LLaVA image path (host/clip.h)
 mi355_clip *mi355_clip_model_load(const char *path, int32_t main_gpu) {
     if (!path) { fail("clip_model_load: no path"); return nullptr; }
@@ -783,6 +810,81 @@ int mi355_quantize_chunk(int32_t dst_type, int32_t src_type, const void *src, in
     t_quant_ms[1] = kernel_ms;
     t_quant_ms[2] = std::chrono::duration<float, std::milli>(c3 - c2).count();
     return MI355_OK;
+}
+
+// The direction of a layer's difference rows (csrc/cvec.hip): upload, iterate, download.  Every refusal comes before dir_out is written.
+int mi355_cvec_direction(int32_t method, const float *rows, int64_t n_rows, int32_t n_embd, const float *init, int32_t n_iter, int32_t n_batch, float tol,
+                         float *dir_out, int32_t *iters_out, float *dist_out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    const bool pca = method == 0;
+    if (method != 0 && method != 1) { fail("cvec_direction: method " + std::to_string(method) + " is neither 0 (pca) nor 1 (mean)"); return MI355_ERR_ARG; }
+    if (!rows || !dir_out || (pca && !init)) { fail("cvec_direction: null pointer"); return MI355_ERR_ARG; }
+    if (n_rows < 1 || n_rows > CVEC_MAX_ROWS) { fail("cvec_direction: n_rows " + std::to_string(n_rows) + " is outside 1 .. 2^20"); return MI355_ERR_ARG; }
+    if (n_embd < 32 || n_embd % 32 || n_embd > CVEC_MAX_E) { fail("cvec_direction: n_embd " + std::to_string(n_embd) + " is not a multiple of 32 in 32 .. 65536"); return MI355_ERR_ARG; }
+    if (pca && (n_iter < 1 || n_batch < 1)) { fail("cvec_direction: n_iter and n_batch must be at least 1"); return MI355_ERR_ARG; }
+    if (pca && std::isnan(tol)) { fail("cvec_direction: tol is not a number"); return MI355_ERR_ARG; }
+    const int R = (int)n_rows, E = n_embd;
+    const size_t n = (size_t)R * (size_t)E;
+    bool any = false;
+    for (size_t i = 0; i < n; i++) {
+        if (!std::isfinite(rows[i])) { fail("cvec_direction: row " + std::to_string(i / (size_t)E) + " holds a non-finite value"); return MI355_ERR_ARG; }
+        any = any || rows[i] != 0.0f;
+    }
+    if (!any) { fail("cvec_direction: every row is zero"); return MI355_ERR_ARG; }
+    if (pca) {
+        bool init_any = false;
+        for (int j = 0; j < E; j++) {
+            if (!std::isfinite(init[j])) { fail("cvec_direction: init holds a non-finite value"); return MI355_ERR_ARG; }
+            init_any = init_any || init[j] != 0.0f;
+        }
+        if (!init_any) { fail("cvec_direction: init is the zero vector"); return MI355_ERR_ARG; }
+    }
+    MI355_GUARD(return MI355_ERR_OOM,
+        const size_t eb = (size_t)E * 4;
+        OpBufs b;
+        const float *dD = b.upload(rows, n * 4);
+        float *db = b.alloc<float>(2 * eb), *dy = b.alloc<float>((size_t)R * 4), *dslab = b.alloc<float>(cvec_scratch_floats(R, E) * 4), *ddist = b.alloc<float>(64);
+        if (pca) b.copy_in(db, init, eb);
+        b.check(db && hipMemset((uint8_t *)db + eb, Q80_GUARD, eb) == hipSuccess);          // the guard rows behind the direction and the distance word
+        b.check(ddist && hipMemset((uint8_t *)ddist + 4, Q80_GUARD, 60) == hipSuccess);
+        if (!b.ok()) return oom();
+        int iters = 0;
+        float dist = 0.0f;
+        auto read_dist = [&]() -> int {
+            if (const int rc = finish(hipSuccess, "cvec_direction")) return rc;
+            if (!b.down(&dist, ddist, 4).ok()) return b.done("cvec_direction");
+            if (dist == -1.0f) { fail(pca ? "cvec_direction: the iteration reached the zero vector (the start vector is orthogonal to every row)" : "cvec_direction: the rows' mean is the zero vector"); return MI355_ERR_ARG; }
+            if (dist < 0.0f) { fail("cvec_direction: the rows are too large for f32 sums of squares"); return MI355_ERR_ARG; }
+            return MI355_OK;
+        };
+        if (pca) {
+            while (iters < n_iter) {
+                const hipError_t e = launch_cvec_pca_step(dD, R, E, db, dy, dslab, ddist, nullptr);
+                if (e != hipSuccess) return e == hipErrorInvalidValue ? (fail("cvec_direction: the launcher refuses this shape"), (int)MI355_ERR_ARG) : hip_fail(e, "cvec_direction");
+                iters++;
+                if (iters % n_batch == 0 || iters == n_iter) {
+                    if (const int rc = read_dist()) return rc;
+                    if (dist < tol) break;
+                }
+            }
+        } else {
+            const hipError_t e = launch_cvec_mean_step(dD, R, E, db, dslab, ddist, nullptr);
+            if (e != hipSuccess) return e == hipErrorInvalidValue ? (fail("cvec_direction: the launcher refuses this shape"), (int)MI355_ERR_ARG) : hip_fail(e, "cvec_direction");
+            if (const int rc = read_dist()) return rc;
+        }
+        if (const int rc = finish(launch_cvec_orient(dD, R, E, db, dy, nullptr), "cvec_direction")) return rc;
+        std::vector<float> res((size_t)E);
+        std::vector<uint8_t> guard(eb + 60);
+        if (!b.down(res.data(), db, eb).down(guard.data(), (uint8_t *)db + eb, eb).down(guard.data() + eb, (uint8_t *)ddist + 4, 60).ok()) return b.done("cvec_direction");
+        for (uint8_t g : guard)
+            if (g != Q80_GUARD) { fail("cvec_direction: the guard region behind the outputs was written"); return MI355_ERR_HIP; }
+        for (float v : res)
+            if (!std::isfinite(v)) { fail("cvec_direction: the direction holds a non-finite value"); return MI355_ERR_HIP; }
+        memcpy(dir_out, res.data(), eb);
+        if (iters_out) *iters_out = iters;
+        if (dist_out) *dist_out = dist;
+        return MI355_OK;
+    )
 }
 
 int mi355_debug_set_option(const char *name, int32_t value) {

@@ -396,6 +396,25 @@ bool quantize_src_supported(int src_type);
 hipError_t launch_quantize_rows(int dst_type, int src_type, const void *src, int64_t n_per_row, int64_t n_rows, const float *imatrix, void *dst,
                                 int32_t *nonfinite_flag, hipStream_t st);
 
+// ---- control vectors (cvec.hip)
+// x[t][j] = fl32(x[t][j] + v[j]) for the T rows of x [T][E]: one f32 addition per element, 16-byte loads and stores.  E a multiple of 32, x and v 16-byte
+// aligned, T >= 1; anything else: hipErrorInvalidValue, nothing launched.
+hipError_t launch_add_row_vec(float *x, const float *v, int E, int T, hipStream_t st);
+// One iteration of the power method on D^T D for the rows D [R][E] (f32, contiguous, 16-byte aligned, E % 32 == 0, 1 <= R <= CVEC_MAX_ROWS), as three launches
+// without an atomic and without a kernel that waits for another; every summation order is fixed by (R, E):
+//   y = D b (a wave per row);  slabs = the row slices of D^T y (cvec_slice_rows(R) rows each, at most CVEC_MAX_SLICES);  z = the slabs in slice order,
+//   b <- z / |z| in place, *dist = |b_new - b_old|.  z == 0 leaves b as it was and writes *dist = -1.
+// y: R floats; slabs: cvec_scratch_floats(R, E) floats; dist: one float.  b == nullptr in launch_cvec_mean_step: the weights are 1 and z is scaled by 1 / R
+// (the mean direction; b receives it, *dist = -1 where the rows sum to zero and 0 otherwise).
+constexpr int CVEC_MAX_ROWS = 1 << 20, CVEC_MAX_SLICES = 32, CVEC_MAX_E = 1 << 16;
+int cvec_slice_rows(int R);
+size_t cvec_scratch_floats(int R, int E);
+bool cvec_pca_args_ok(const float *D, int R, int E);
+hipError_t launch_cvec_pca_step(const float *D, int R, int E, float *b, float *y, float *slabs, float *dist, hipStream_t st);
+hipError_t launch_cvec_mean_step(const float *D, int R, int E, float *b, float *slabs, float *dist, hipStream_t st);
+// b <- -b where sum over the rows of D[r] . b < 0 (two launches: y = D b, then its sum in a fixed order)
+hipError_t launch_cvec_orient(const float *D, int R, int E, float *b, float *y, hipStream_t st);
+
 // ---------------------------------------------------------------- attention side (attn.hip)
 // words between two merge-ticket counters / hand-over flags of the decode attention kernels (attn_decode_dev.h, attn_out.hip): one 128-byte line each
 constexpr int ATT_SYNC_STRIDE = 32;

@@ -181,4 +181,18 @@ int mi355_op_gather_rows_f32(const float *src, int64_t n_src_rows, int64_t n, co
     return b.down(dst, dd, nd).done("gather_rows_f32");
 }); }
 
+int mi355_op_add_row_vec(const float *x, const float *v, int32_t E, int32_t T, float *y) { return op_entry([&]() -> int {
+    if (!x || !v || !y || E < 1 || T < 1) { fail("add_row_vec: bad args"); return MI355_ERR_ARG; }
+    const size_t rb = (size_t)E * 4, nb = rb * (size_t)T;
+    OpBufs b;
+    float *dx = b.alloc<float>(nb + rb);  const float *dv = b.upload(v, rb);
+    b.copy_in(dx, x, nb);
+    b.check(dx && hipMemset((uint8_t *)dx + nb, Q80_GUARD, rb) == hipSuccess);        // the guard row behind the T rows
+    if (!b.ok()) return oom();
+    const hipError_t e = launch_add_row_vec(dx, dv, E, T, nullptr);
+    if (e == hipErrorInvalidValue) { fail("add_row_vec: the launcher refuses this shape (E % 32)"); return MI355_ERR_ARG; }
+    if (const int rc = finish(e, "add_row_vec")) return rc;
+    return b.down(y, dx, nb + rb).done("add_row_vec");
+}); }
+
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <mutex>
 
 #include "clip.h"
+#include "cvec.h"
 #include "log.h"
 
 #include <sys/stat.h>
@@ -229,6 +230,10 @@ std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, 
     // with params.lora_adapters).  The ranks of a row split hold slices of the base tensors: refused by name.
     const Json &lora = body["lora"];
     if (!lora.is_null() && tp_split_requested(body)) { err = "lora: adapters are not supported with \"split_mode\": \"row\" (load the model on one device)"; return nullptr; }
+    // "control_vectors": [path | {"path": ..., "scale": 1}] with "control_vector_layer_range": [start, end] - upstream's --control-vector /
+    // --control-vector-scaled / --control-vector-layer-range: the files are loaded, summed and applied to the context before the first step
+    const Json &cvecs = body["control_vectors"];
+    if (!cvecs.is_null() && tp_split_requested(body)) { err = "control_vectors: control vectors are not supported with \"split_mode\": \"row\" (load the model on one device)"; return nullptr; }
     if (!body["model_draft"].is_null() && !body["mmproj"].is_null()) { err = "model_draft: speculative decoding is not supported beside a multimodal projector (mmproj)"; return nullptr; }
     if (!body["model_draft"].is_null() && tp_split_requested(body)) { err = "model_draft: speculative decoding is not supported with \"split_mode\": \"row\""; return nullptr; }
     if (tp_split_requested(body)) return make_split_backend(body, info, err);
@@ -306,6 +311,34 @@ std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, 
             if (ctx->set_adapter_lora(ad, scale) != 0) { err = "lora: " + apath + ": " + ctx->last_error; return nullptr; }
             log_line(LOG_INFO, "LoRA adapter %s: %d tensor pairs, alpha %g, scale %g", apath.c_str(), (int)ad->pairs.size(), (double)ad->alpha, (double)scale);
         }
+    }
+
+    if (!cvecs.is_null()) {
+        static const char *shape = "control_vectors: expected a list of file paths or {\"path\", \"scale\"} objects";
+        if (model->hp.encoder || body.value<bool>("embedding", false)) { err = "control_vectors: an embedding (encoder) model takes no control vector"; return nullptr; }
+        if (!cvecs.is_array()) { err = shape; return nullptr; }
+        std::vector<ControlVectorFile> files;
+        for (const Json &item : cvecs.items()) {
+            const std::string vpath = item.is_string() ? item.as_string() : item["path"].str_or("");
+            if (vpath.empty() || (!item.is_string() && !item.is_object())) { err = shape; return nullptr; }
+            files.push_back({vpath, item.is_object() ? item.value<float>("scale", 1.0f) : 1.0f});
+        }
+        if (files.empty()) { err = shape; return nullptr; }
+        std::vector<float> data;
+        int vec_embd = 0;
+        std::string verr2;
+        if (!control_vector_load(files, data, vec_embd, verr2)) { err = "control_vectors: " + verr2; return nullptr; }
+        // (upstream: a start or an end <= 0 means 1 and n_layer)
+        int il_start = 1, il_end = (int)model->hp.n_layer;
+        const Json &range = body["control_vector_layer_range"];
+        if (!range.is_null()) {
+            if (!range.is_array() || range.items().size() != 2) { err = "control_vector_layer_range: expected [start, end]"; return nullptr; }
+            const int a = (int)range.items()[0].as_int(0), b = (int)range.items()[1].as_int(0);
+            if (a > 0) il_start = a;
+            if (b > 0) il_end = b;
+        }
+        if (ctx->apply_cvec(data.data(), data.size(), vec_embd, il_start, il_end) != 0) { err = "control_vectors: " + ctx->last_error; return nullptr; }
+        log_line(LOG_INFO, "control vector: %d file(s), %d layer(s) of %d, applied to layers %d .. %d", (int)files.size(), (int)(data.size() / (size_t)vec_embd), vec_embd, il_start, il_end);
     }
 
     // "model_draft": a small model of the same vocabulary that proposes tokens for this one to check (upstream's --model-draft)

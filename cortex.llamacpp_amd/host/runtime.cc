@@ -518,13 +518,17 @@ bool Context::init(std::string &err) {
 
 // ------------------------------------------------------------------------------------------ KV cells
 // ---- the active adapters.  A change of the set or of a scale changes what the captured steps would have to launch: the stream is drained and they are dropped.
-bool Context::lora_changed() {
+void Context::drop_captured_steps() {
     (void)hipSetDevice(model->device);
     (void)hipStreamSynchronize(stream_);
     if (holds_fused_) fused_release();
     for (auto &ge : graphs_) (void)hipGraphExecDestroy(ge.second);
     graphs_.clear();
     graph_exec_ = nullptr;
+}
+
+bool Context::lora_changed() {
+    drop_captured_steps();
     if (!lora_.empty() && !lora_t_ && lora_scratch_floats((int)cp.n_ubatch) > 0) {
         lora_t_ = (float *)dalloc(lora_scratch_floats((int)cp.n_ubatch) * sizeof(float));
         if (!lora_t_) { lora_.clear(); last_error = "out of device memory for the adapter scratch"; return false; }
@@ -578,6 +582,50 @@ hipError_t Context::lora_add(int layer, const int *targets, float *const *outs, 
     return hipSuccess;
 }
 
+// ---- the control vector (runtime.h).  Every refusal comes before the first change: a refused call leaves the context as it was.
+int Context::apply_cvec(const float *data, size_t len, int n_embd, int il_start, int il_end) {
+    const HParams &hp = model->hp;
+    if (hp.encoder) { last_error = "apply_cvec: an encoder model takes no control vector"; return -1; }
+    if (hp.tp_size > 1) { last_error = "apply_cvec: not on a rank of a row split (load the model on one device)"; return -1; }
+    if (!data) {                                                       // clear
+        if (!cvec_on_) return 0;
+        drop_captured_steps();
+        cvec_on_ = false;
+        std::fill(cvec_present_.begin(), cvec_present_.end(), (uint8_t)0);
+        return 0;
+    }
+    if (n_embd != hp.n_embd) { last_error = "apply_cvec: n_embd " + std::to_string(n_embd) + " is not the model's " + std::to_string(hp.n_embd); return -1; }
+    if (len % (size_t)n_embd) { last_error = "apply_cvec: len " + std::to_string(len) + " is not a multiple of n_embd " + std::to_string(n_embd); return -1; }
+    if (il_start > il_end) { last_error = "apply_cvec: il_start " + std::to_string(il_start) + " > il_end " + std::to_string(il_end); return -1; }
+    if (n_embd % 32) { last_error = "apply_cvec: n_embd is no multiple of 32"; return -1; }
+    const size_t E = (size_t)n_embd, n_have = std::min(len / E, (size_t)std::max(0, hp.n_layer - 1));      // vectors of layers 1 .. n_have
+    for (size_t i = 0; i < len; i++)
+        if (!std::isfinite(data[i])) { last_error = "apply_cvec: the vector of layer " + std::to_string(i / E + 1) + " holds a non-finite value"; return -1; }
+    if (hipSetDevice(model->device) != hipSuccess) { last_error = "apply_cvec: cannot select the device"; return -1; }
+    drop_captured_steps();
+    if (!cvec_) {
+        cvec_ = (float *)dalloc((size_t)hp.n_layer * E * sizeof(float));       // (zero-filled)
+        if (!cvec_) { last_error = "apply_cvec: out of device memory for the vectors"; return -1; }
+        (void)hipDeviceSynchronize();                                          // the null-stream zero-fill (see init)
+    }
+    if (n_have && hipMemcpy(cvec_ + E, data, n_have * E * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        cvec_on_ = false; last_error = "apply_cvec: the copy to the device failed"; return -1;
+    }
+    cvec_present_.assign((size_t)hp.n_layer, (uint8_t)0);
+    for (size_t il = 1; il <= n_have; il++) cvec_present_[il] = 1;
+    cvec_start_ = il_start; cvec_end_ = il_end;
+    cvec_on_ = true;
+    return 0;
+}
+
+// layer il's vector onto its completed rows, where it has one inside the range
+hipError_t Context::cvec_add(int il, int T) {
+    if (!cvec_on_ || il < 1 || il < cvec_start_ || il > cvec_end_ || !cvec_present_[(size_t)il]) return hipSuccess;
+    HIP_TRY(launch_add_row_vec(x_, cvec_ + (size_t)il * model->hp.n_embd, model->hp.n_embd, T, stream_));
+    prof_mark("cvec");
+    return hipSuccess;
+}
+
 // ---- importance-matrix collection (runtime.h).  begin lays out one device block: every accumulator's f32 [n_mat][K] rows, then every
 // int32 [n_mat] count, then a slab scratch that holds any launch of up to a micro-batch's rows (imatrix_scratch_floats: the largest batch does not need the most slabs).
 int Context::imatrix_begin(bool process_output) {
@@ -623,11 +671,7 @@ int Context::imatrix_begin(bool process_output) {
     size_t sum_floats = 0, n_counts = 0;
     for (const ImxAcc &a : acc) { sum_floats += (size_t)a.K * a.n_mat; n_counts += (size_t)a.n_mat; }
     const size_t acc_bytes = (sum_floats * 4 + n_counts * 4 + 255) & ~(size_t)255;
-    (void)hipStreamSynchronize(stream_);
-    if (holds_fused_) fused_release();
-    for (auto &ge : graphs_) (void)hipGraphExecDestroy(ge.second);     // (as a change of the adapter set does: no captured step outlives a change of routes)
-    graphs_.clear();
-    graph_exec_ = nullptr;
+    drop_captured_steps();                                             // (as a change of the adapter set does: no captured step outlives a change of routes)
     const uint64_t before = device_bytes;
     imx_block_ = (uint8_t *)dalloc(acc_bytes + slab_floats * 4);       // (zero-filled)
     if (!imx_block_) { last_error = "imatrix_begin: out of device memory for the accumulators"; return -1; }
@@ -2122,7 +2166,7 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
     att_splits_ = flash_attn_pick_splits(T, hp.n_head_kv, st.n_kv_max);
 
     // single-token step on a dense K-quant model: all layers in one launch (decode_mega.hip)
-    bool mega = T == 1 && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && !imx_on_ && mega_prepare();
+    bool mega = T == 1 && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && !imx_on_ && !cvec_on_ && mega_prepare();
     AttnArgs ma{};
     if (mega) {
         ma = attn_args(0, 1, st.n_kv_max, d_pos_);             // (the kernel takes each layer's cache from its own descriptor)
@@ -2132,7 +2176,7 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
         mega = flash_attn_decode_fused_applicable(ma, st.ra_step);      // (more than 64 chunks: the per-launch path merges them)
     }
     // ... or one persistent launch per layer for the mat-vecs between two attention calls (decode_engine.hip)
-    st.engine = T == 1 && !mega && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && !imx_on_ && engine_prepare();
+    st.engine = T == 1 && !mega && !profile_ && !debug_taps_ && !ub_embd_ && lora_.empty() && !imx_on_ && !cvec_on_ && engine_prepare();
     last_layers_engine_ = st.engine;
     // cos / sin table, cell metadata and the tokens' embedding rows: one launch
     HIP_TRY(launch_step_setup_embed(d_pos_, T, st.ra_step, rope_cs_, d_cell_pos_, d_cell_seq_, d_cell_, d_seqmask_, mega ? d_mega_sync_ : nullptr,
@@ -2157,6 +2201,7 @@ hipError_t Context::run_layers(int T, int n_kv_cap) {
             prof_mark("attn_out");
             HIP_TRY(ffn_block(il, st));
         }
+        HIP_TRY(cvec_add(il, T));
         HIP_TRY(tap_layer(il, T));
     }
     return hipSuccess;

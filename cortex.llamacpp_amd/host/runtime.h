@@ -198,6 +198,14 @@ class Context {
     int set_adapter_lora(LoraAdapter *a, float scale);
     int rm_adapter_lora(LoraAdapter *a);
     void clear_adapter_lora();
+    // llama_apply_adapter_cvec: data holds the vectors of layers 1, 2, ... back to back, layer il at n_embd * (il - 1) and present when
+    // n_embd * il <= len.  From the next step on every layer il with il_start <= il <= il_end whose vector is present ends with x[t][:] += v_il[:] on all rows
+    // of the batch (csrc/cvec.hip launch_add_row_vec, a launch of its own before the tap); layer 0 never has one.  While a vector is applied the single-launch
+    // step and the layer engine are not used; graphs are.  data == nullptr clears: the steps are again what they were.  Both drain the stream and drop the
+    // captured steps.  0, or -1 with last_error set and nothing changed (an encoder, a rank of a row split, another n_embd, len no multiple of n_embd, a
+    // non-finite value, il_start > il_end, out of device memory).  The [n_layer][n_embd] f32 buffer is device memory of the context from the first apply on.
+    int apply_cvec(const float *data, size_t len, int n_embd, int il_start, int il_end);
+    bool cvec_applied() const { return cvec_on_; }
 
     void kv_clear();
     bool kv_seq_rm(int seq, int p0, int p1);
@@ -310,6 +318,13 @@ class Context {
     float *lora_t_ = nullptr;          // t = A x of a prompt micro-batch (kernels.h lora_scratch_floats(n_ubatch))
     bool lora_on(int layer, int target) const;
     bool lora_changed();
+    void drop_captured_steps();        // a change of routes: the stream is drained, the fused step's hold released, every captured graph destroyed
+    // the applied control vector (apply_cvec): rows [n_layer][n_embd], which of them the caller's buffer held, the layer range
+    float *cvec_ = nullptr;
+    std::vector<uint8_t> cvec_present_;
+    int cvec_start_ = 0, cvec_end_ = -1;
+    bool cvec_on_ = false;
+    hipError_t cvec_add(int il, int T);
     // outs[i] (leading dimension lds[i]) += the deltas of (layer, targets[i]) from the rows x [T][ld_x], adapter by adapter in the order they were set
     hipError_t lora_add(int layer, const int *targets, float *const *outs, const int *lds, int n, const float *x, int ld_x, int K, int T);
     // importance-matrix collection (imatrix_begin): one accumulator per (layer, site) plus the head's, in one device block with the slab scratch behind them

@@ -269,6 +269,31 @@ MI355_API int32_t mi355_set_adapter_lora(mi355_context *ctx, mi355_adapter_lora 
 MI355_API int32_t mi355_rm_adapter_lora(mi355_context *ctx, mi355_adapter_lora *adapter);
 MI355_API void    mi355_clear_adapter_lora(mi355_context *ctx);
 
+/* Control vectors (unpinned: upstream's source is not in the reference tree, the semantics are llama_apply_adapter_cvec's as remembered).
+ * data: the vectors of layers 1, 2, ... back to back, `len` floats; layer il is at n_embd * (il - 1) and present when n_embd * il <= len.  From the next step on
+ * every layer il_start <= il <= il_end with a present vector ends with x[t][:] = fl32(x[t][:] + v_il[:]) on every row of the batch: one extra launch per steered
+ * layer, inside the captured graph where the step is captured.  Layer 0 never has a vector.  data == NULL clears (the other arguments are not read): the steps
+ * are bit for bit what they were before.  Apply and clear drain the context and drop its captured steps.
+ * MI355_OK, or MI355_ERR_ARG with mi355_last_error naming the cause and the context unchanged: a NULL context, an encoder model, a rank of a row split, an
+ * n_embd that is not the model's, len not a multiple of n_embd, a non-finite value, il_start > il_end. */
+MI355_API int32_t mi355_apply_adapter_cvec(mi355_context *ctx, const float *data, size_t len, int32_t n_embd, int32_t il_start, int32_t il_end);
+/* common_control_vector_load: n GGUF files of F32 one-dimensional tensors direction.N (N >= 1, one length n_embd), file i accumulated as scales[i] * tensor into
+ * layer N's slot, the files summed.  Returns the number of floats of the result, n_embd * (the highest layer named), laid out as mi355_apply_adapter_cvec takes
+ * it, and writes them to `out` when cap_floats holds them (out may be NULL to ask for the size); *n_embd_out (nullable) = n_embd.  MI355_ERR_ARG (a NULL list,
+ * n < 1) or MI355_ERR_FORMAT with mi355_last_error naming file and tensor: a file that does not open, direction.0, a direction tensor that is not F32 or not
+ * one-dimensional, different lengths within or between files, no direction tensor at all.  Host arithmetic; needs no device. */
+MI355_API int64_t mi355_control_vector_load(const char *const *paths, const float *scales, int32_t n, float *out, size_t cap_floats, int32_t *n_embd_out);
+/* What llama-cvector-generator computes per layer (csrc/cvec.hip), on host pointers: the direction of rows [n_rows][n_embd] (f32).  method 0 (pca): the first
+ * principal direction by the power method on rows^T rows from the start vector init [n_embd], three launches an iteration with no atomics and every summation
+ * order fixed by the shape, so the same arguments give the same bytes; the host reads |b_new - b_old| every n_batch iterations and stops when it is < tol or
+ * after n_iter.  method 1 (mean): the normalised mean row (init, n_iter, n_batch, tol are not read).  The sign is chosen so that sum over the rows of row . dir
+ * >= 0.  dir_out [n_embd] unit length; iters_out (nullable) iterations run; dist_out (nullable) the last distance read.  A guard region behind the device
+ * outputs is checked.  MI355_ERR_ARG with the cause named and dir_out untouched: a NULL pointer, an unknown method, n_rows < 1 (or > 2^20), n_embd % 32
+ * (or > 65536), n_iter < 1 or n_batch < 1 (pca), a non-finite input, a zero init (pca), all-zero rows, an iteration that reaches the zero vector (init is
+ * orthogonal to every row; rows whose mean is zero). */
+MI355_API int mi355_cvec_direction(int32_t method, const float *rows, int64_t n_rows, int32_t n_embd, const float *init, int32_t n_iter, int32_t n_batch, float tol,
+                                   float *dir_out, int32_t *iters_out, float *dist_out);
+
 /* KV cache bookkeeping (ctx.cc:287; 661,1547; 1288,1540,1542; 1290) */
 MI355_API void    mi355_kv_cache_clear(mi355_context *ctx);
 MI355_API int32_t mi355_kv_cache_seq_rm(mi355_context *ctx, mi355_seq_id seq, mi355_pos p0, mi355_pos p1); /* 1 = ok */
@@ -483,6 +508,9 @@ MI355_API int mi355_op_clip_bias(float *x_io, const float *b, int32_t n, int32_t
 MI355_API int mi355_op_f32_to_f16(const float *x, int64_t n, uint16_t *out);
 /* q_io [T][nq] += bq, k_io / v_io [T][nkv] += bk / bv in one launch; a NULL bias skips its segment (its rows may then be NULL too) */
 MI355_API int mi355_op_add_qkv_bias(float *q_io, float *k_io, float *v_io, const float *bq, const float *bk, const float *bv, int32_t nq, int32_t nkv, int32_t T);
+/* the control vector's row-broadcast add (csrc/cvec.hip launch_add_row_vec): y [T + 1][E]; rows 0 .. T - 1 = x[t] + v, row T = the guard row that lay behind
+ * them on the device, every byte 0xA5 if the launch stayed inside its rows */
+MI355_API int mi355_op_add_row_vec(const float *x, const float *v, int32_t E, int32_t T, float *y);
 /* logits [n_base_rows][n]; launch row r = base row rows[r], r < R <= 1088; group g < G <= 64 owns launch rows group_start[g] .. group_start[g + 1] - 1
  * (1 .. 17 rows; group_start[0] = 0, group_start[G] = R); draft [R].  ids_out [R], n_accept_out [G] as mi355_spec_verify gives them. */
 MI355_API int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t R, const int32_t *group_start, int32_t G,
