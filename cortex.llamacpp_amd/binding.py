@@ -397,7 +397,7 @@ class Backend:
                        eps: float = 0.0, form: int = 0, ld_pad: int = 0, check: bool = True):
         """One mat-mul launch of a dense prompt batch as the model issues it (see mi355_op_prompt_mul_mat).  x: [T][K], for prologue 2 [2][T][K] (gate, up).
         Returns (ys, path, rc): ys the whole out buffers [T][N + ld_pad] (one for epi 2), path a dict (kernel 1 K-split / 2 planes 256 x 32 / 3 planes
-        128 x 128 / 4 LDS / 5 on the fly, token_tiles, n_split, mixed, swiglu, prep), rc the entry's return code (check=False: returned, not raised)."""
+        128 x 128 / 4 LDS / 5 on the fly / 6 the packed-trit kernel of TQ1_0 / TQ2_0 segments under set_option("mmq_ternary_direct", 1), token_tiles, n_split, mixed, swiglu, prep), rc the entry's return code (check=False: returned, not raised)."""
         n = len(Ws)
         Ws = [np.ascontiguousarray(w.view(np.uint8).reshape(-1)) for w in Ws]
         tarr = np.asarray(types, np.int32)

@@ -51,7 +51,7 @@ static thread_local std::string t_err;
 static bool g_backend_ok = false;
 
 // what op_support.h declares for the per-op test entries (op_entries_*.cc): the error string, the device check, the switches of mi355_debug_set_option
-int mi355::g_op_mmq_planes = 1, mi355::g_op_mmq_ksplit = 1;
+int mi355::g_op_mmq_planes = 1, mi355::g_op_mmq_ksplit = 1, mi355::g_op_mmq_ternary_direct = 0;
 void mi355::fail(const std::string &s) { t_err = s; }
 bool mi355::need_device() { return g_backend_ok || mi355_backend_init() == MI355_OK; }
 
@@ -890,6 +890,8 @@ int mi355_cvec_direction(int32_t method, const float *rows, int64_t n_rows, int3
 int mi355_debug_set_option(const char *name, int32_t value) {
     if (!name) return MI355_ERR_ARG;
     if (!strcmp(name, "mmq_planes")) { g_op_mmq_planes = value != 0; return MI355_OK; }
+    if (!strcmp(name, "mmq_ternary_direct")) { g_op_mmq_ternary_direct = value != 0; return MI355_OK; }   // the op entries: TQ1_0 / TQ2_0 prompt batches on mmq_ternary.hip (the model's route) instead of the plane set
+    if (!strcmp(name, "mmq_ternary_tiles")) { mmq_ternary_set_tiles(value); return MI355_OK; }
     if (!strcmp(name, "mmq_tiles")) { mmq_set_tiles(value); return MI355_OK; }
     if (!strcmp(name, "mmq_q80_tiles")) { mmq_q80_set_tiles(value); return MI355_OK; }
     if (!strcmp(name, "mmq_split")) { mmq_set_split(value); return MI355_OK; }

@@ -166,6 +166,16 @@ bool mmq_q80_moe_ok(int type, int n_rows, int K);
 hipError_t launch_mmq_q80_moe(int type, const uint8_t *const *W, float *const *outs, int n_seg, size_t expert_stride, int n_expert, const int32_t *meta, int n_rows,
                               int K, int rows_max, const ActQuant &q, int ld_out, hipStream_t st);
 void mmq_q80_set_tiles(int mt);      // tests: 1 / 2 / 4 token tiles per wave whatever the shape; 0: the launcher's choice
+// prompt batches against TQ1_0 / TQ2_0 weights straight from the device rows' packed trits (mmq_ternary.hip): int8 MFMA per 256-element super-block against the
+// Q8_K codes, one f32 term per super-block in ascending order - the same bits whatever the tile, the batch or the form.  No plane set, no block-sum planes.
+// The shapes, stated once (the runtime and the op entries both ask): a ternary type, K a multiple of 256, T >= 32 (below it the mat-vec kernels stay)
+bool mmq_ternary_applicable(int type, int K, int T);
+struct MMQTernarySeg { const uint8_t *W; int n_rows; float *out; int ld_out; };      // device rows (dev_row_bytes(type, K) apart), out[t * ld_out + row]
+// 1..3 tensors of one type over one activation in one launch (Q | K | V); resid (one tensor): out = resid + y; swiglu: segs = {ffn_gate, ffn_up} of one row
+// count, segs[0].out = silu(gate . x) * (up . x).  isum (one tensor, tests): the kernel's integer sums, [T][n_rows][K / 256].
+hipError_t launch_mmq_ternary(int type, const MMQTernarySeg *segs, int n_seg, int K, int T, const ActQuant &q, const float *resid, bool swiglu, hipStream_t st,
+                              int32_t *isum = nullptr);
+void mmq_ternary_set_tiles(int mt);  // tests: 1 / 2 / 4 token tiles per wave whatever the shape (SwiGLU: at most 2); 0: the launcher's choice
 // up to three tensors of one plane format (Q4_K / Q5_K together, or Q6_K) whose plane sets are contiguous in memory, as one
 // launch over the concatenated rows; seg_rows[i] rows go to outs[i] (leading dimension lds_out[i])
 hipError_t launch_mmq_planes_multi(int type, const uint8_t *planes, const int *seg_rows, float *const *outs, const int *lds_out, int n_seg, int K, int T,

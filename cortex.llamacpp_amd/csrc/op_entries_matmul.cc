@@ -33,15 +33,23 @@ int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x
     const uint8_t *wdev = w.t.data;
     const size_t drow = w.t.row_bytes;
     const bool quant = type_is_quant(type);
-    if (resid && !(quant && ((mmq_q80_applicable(type, (int)K, (int)T)) || (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes)))) {
-        fail("resid: only the Q8_0 prompt kernel's launches take one here"); return MI355_ERR_ARG;
+    const bool tern_direct = g_op_mmq_ternary_direct && mmq_ternary_applicable(type, (int)K, (int)T);      // ("mmq_ternary_direct" 1: the model's route for a dense ternary tensor)
+    if (resid && !tern_direct && !(quant && ((mmq_q80_applicable(type, (int)K, (int)T)) || (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes)))) {
+        fail("resid: only the Q8_0 prompt kernel's launches and the direct ternary launch take one here"); return MI355_ERR_ARG;
     }
     hipError_t e;
     const char *what;
     if (quant) {
         e = launch_quantize(dx, (int)K, (int)T, ab.q, !act_is_q80(type), act_is_q80(type), nullptr);
         if (e != hipSuccess) return hip_fail(e, "quantize");
-        if (mmq_q80_applicable(type, (int)K, (int)T)) {
+        int32_t *tern_ints = nullptr;
+        if (tern_direct) {
+            what = "mmq_ternary";
+            if (isum && msum) tern_ints = b.alloc<int32_t>((size_t)T * N * (K / 256) * 4);      // the kernel's own integer sums, every token in the one launch
+            if (!b.ok()) return oom();
+            const MMQTernarySeg sg{wdev, (int)N, dy, (int)N};
+            e = launch_mmq_ternary(type, &sg, 1, (int)K, (int)T, ab.q, rs, false, nullptr, tern_ints);
+        } else if (mmq_q80_applicable(type, (int)K, (int)T)) {
             what = "mmq_q80";
             e = launch_mmq_q80(wdev, drow, (int)N, (int)K, (int)T, ab.q, dy, (int)N, rs, nullptr);
         } else if (mmq_q80_copy_bytes(type, N, (int)K) && mmq_q80_applicable(T_Q8_0, (int)K, (int)T) && g_op_mmq_planes) {   // Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4 prompt batches: exact Q8_0-layout copy
@@ -83,7 +91,10 @@ int op_mul_mat(int32_t type, const void *W, int64_t N, int64_t K, const float *x
             });
         }
         if (const int rc = finish(e, what)) return rc;
-        if (isum && msum) {
+        if (tern_ints) {                                           // (no min term: msum is zero, as launch_mmvq_ints reports these types)
+            b.down(isum, tern_ints, (size_t)T * N * (K / 256) * 4);
+            memset(msum, 0, (size_t)T * N * (K / 256) * 4);
+        } else if (isum && msum) {
             const int64_t nblk = act_is_q80(type) ? K / 32 : K / 256;
             int32_t *di = b.alloc<int32_t>((size_t)N * nblk * 4), *dm = b.alloc<int32_t>((size_t)N * nblk * 4);
             if (!b.ok()) return oom();
@@ -184,6 +195,20 @@ extern "C" {
 int mi355_op_ffn_gate_up(int32_t type, const void *Wg, const void *Wu, int64_t N, int64_t K, const float *x, int64_t T, float *y) { return op_entry([&]() -> int {
     // the 32-element formats: any whole number of blocks (the K-quants below: their plane sets, whole 256-blocks); f16 as two products and the SwiGLU pass
     if (act_is_q80(type) || type == T_F16) return op_ffn_gate_up_nib32(type, Wg, Wu, N, K, x, T, y);
+    if (g_op_mmq_ternary_direct && mmq_ternary_applicable(type, (int)K, (int)T) && N >= 1) {      // the model's launch for a dense ternary layer: any N
+        OpBufs b;
+        TestWeight wg(b, type, K, N), wu(b, type, K, N);
+        const float *dx = b.upload(x, (size_t)K * T * 4);  float *dy = b.alloc<float>((size_t)N * T * 4);
+        ActBufs ab(b, (size_t)K, (size_t)T);
+        if (!b.ok()) return oom();
+        if (const int rc = wg.load(Wg, "ffn_gate_up (set-up)")) return rc;
+        if (const int rc = wu.load(Wu, "ffn_gate_up (set-up)")) return rc;
+        const MMQTernarySeg sg[2] = {{wg.t.data, (int)N, dy, (int)N}, {wu.t.data, (int)N, nullptr, 0}};
+        hipError_t e = launch_quantize(dx, (int)K, (int)T, ab.q, true, false, nullptr);
+        if (e == hipSuccess) e = launch_mmq_ternary(type, sg, 2, (int)K, (int)T, ab.q, nullptr, true, nullptr);
+        if (const int rc = finish(e, "ffn_gate_up (mmq_ternary)")) return rc;
+        return b.down(y, dy, (size_t)N * T * 4).done("ffn_gate_up");
+    }
     const size_t pb = mmq_planes_bytes(type, N, (int)K);
     if (!ggml_row_bytes(type, K) || K % 256 || !pb || N % 32) { fail("bad type / K / N"); return MI355_ERR_ARG; }
     if (!mmq_planes_swiglu_ok(type, type, (int)N, (int)K, (int)T)) { fail("shape does not take the SwiGLU launch (set mmq_tiles = 4 to force it)"); return MI355_ERR_ARG; }
@@ -329,6 +354,37 @@ int mi355_op_prompt_mul_mat(int32_t n_seg, const int32_t *types, const void *con
     if (prologue < 0 || prologue > 3 || (prologue == 1 && !norm_w)) return refuse("bad prologue");
     if (form < 0 || form > 3) return refuse("form outside 0..3");
     if (form == 3 && n_seg != 1) return refuse("the expansion on the fly takes one tensor");
+    bool all_tern = g_op_mmq_ternary_direct != 0;
+    for (int s = 0; s < n_seg; s++) all_tern &= type_is_ternary(types[s]);
+    if (all_tern) {
+        // "mmq_ternary_direct" 1: dense ternary tensors as the model holds them - no plane set - through prompt_mul_mat_choice; path[0] = 6, the kernel on the packed trits
+        if (form != 0 || prologue != 0 || in_place) return refuse("ternary segments: form 0, prologue 0, no in-place residual");
+        use_device_cu_count();
+        OpBufs b;
+        const float *dx = b.upload(x, (size_t)K * T * 4);
+        ActBufs ab(b, (size_t)K, (size_t)T);
+        std::vector<TestWeight> w;
+        const DevTensor *wp[3];
+        MMQTernarySeg sg[3];
+        float *outs[3] = {};
+        for (int s = 0; s < n_seg; s++) w.emplace_back(b, types[s], K, N[s]);
+        for (int s = 0; s < n_seg; s++) {
+            wp[s] = &w[(size_t)s].t;
+            if (s < n_out) outs[s] = b.alloc<float>((size_t)T * (N[s] + ld_pad) * 4, 0xFF);
+            sg[s] = MMQTernarySeg{wp[s]->data, (int)N[s], outs[s], s < n_out ? (int)(N[s] + ld_pad) : 0};
+        }
+        const float *rs = epi == EPI_ADD ? b.upload(resid, (size_t)T * (N[0] + ld_pad) * 4) : nullptr;
+        if (!b.ok()) return oom();
+        const PromptMatmul pm = prompt_mul_mat_choice(epi == EPI_SWIGLU ? PM_ROLE_GATE_UP : n_seg == 1 ? PM_ROLE_ONE : PM_ROLE_MULTI, wp, n_seg, (int)K, (int)T, MMQWorkspace());
+        if (pm.form != PM_TERNARY || pm.n_fused != n_seg) return refuse("the model does not run these tensors as one launch of the ternary kernel");
+        for (int s = 0; s < n_seg; s++) if (const int rc = w[(size_t)s].load(W[s], "prompt_mul_mat (set-up)")) return rc;
+        hipError_t e = launch_quantize(dx, (int)K, (int)T, ab.q, true, false, nullptr);
+        if (e == hipSuccess) e = launch_mmq_ternary(types[0], sg, n_seg, (int)K, (int)T, ab.q, rs, epi == EPI_SWIGLU, nullptr);
+        path[0] = 6; path[2] = 1; path[4] = epi == EPI_SWIGLU ? 1 : 0;
+        if (const int rc = finish(e, "prompt_mul_mat (mmq_ternary)")) return rc;
+        for (int s = 0; s < n_out; s++) b.down(y[s], outs[s], (size_t)T * (N[s] + ld_pad) * 4);
+        return b.done("prompt_mul_mat");
+    }
     int64_t n_all = 0;
     for (int s = 0; s < n_seg; s++) {
         const int t = types[s];

@@ -15,10 +15,10 @@
 
 namespace mi355 {
 
-// ---- c_api.cc: the one thread-local string behind mi355_last_error, the device check, the two switches mi355_debug_set_option sets for the mat-mul entries
+// ---- c_api.cc: the one thread-local string behind mi355_last_error, the device check, the switches mi355_debug_set_option sets for the mat-mul entries
 void fail(const std::string &s);
 bool need_device();
-extern int g_op_mmq_planes, g_op_mmq_ksplit;
+extern int g_op_mmq_planes, g_op_mmq_ksplit, g_op_mmq_ternary_direct;
 
 // No C++ exception may cross the C ABI (the reference's own rule for its plugin boundary, enginei.h): allocation failures
 // and anything else thrown below an entry point become that entry point's error return and a last_error message.

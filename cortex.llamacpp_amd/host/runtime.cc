@@ -160,6 +160,13 @@ static void alias_tensors(Model &m) {
     }
 }
 
+// a dense ternary tensor gets no plane set: its prompt batches read the packed trits (mmq_ternary.hip).  Expert tensors keep the grouped plane launch.
+bool tq_direct_enabled() {
+    static const bool off = getenv("MI355_TQ_DIRECT") && getenv("MI355_TQ_DIRECT")[0] == '0';
+    return !off;
+}
+static bool tq_direct_tensor(const DevTensor &w) { return tq_direct_enabled() && w.n_expert == 1 && mmq_ternary_applicable(w.type, (int)w.K, 32); }
+
 // prompt-processing copy of the per-layer projection weights: both int8 MFMA operand planes of every K-step,
 // expanded once here (2 B per weight) so that the prefill kernel spends nothing per weight (mmq.hip).  288 GB of HBM
 // is what makes this the default; it is skipped (the prefill kernel then expands on the fly) when memory is short.
@@ -169,7 +176,7 @@ static bool expand_prefill_planes(Model &m, int prefill_planes, std::string &err
     std::vector<DevTensor *> want;
     for (auto &L : m.layers)
         for (DevTensor *d : {&L.wq, &L.wk, &L.wv, &L.wo, &L.gate, &L.up, &L.down, &L.gate_exps, &L.up_exps, &L.down_exps})
-            if (d->valid() && (mmq_planes_bytes(d->type, d->N, (int)d->K) || mmq_q80_copy_bytes(d->type, d->N, (int)d->K))) want.push_back(d);
+            if (d->valid() && (mmq_planes_bytes(d->type, d->N, (int)d->K) || mmq_q80_copy_bytes(d->type, d->N, (int)d->K)) && !tq_direct_tensor(*d)) want.push_back(d);
     // (an *_exps tensor holds one plane set per expert, back to back: a prompt batch runs one contraction per expert)
     // (K-quants: the two int8 MFMA planes; Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1 / MXFP4: an exact Q8_0-layout copy for the Q8_0 prompt kernel, with a min plane for Q4_1 / Q5_1 and E8M0 scale bytes for MXFP4)
     auto planes_of = [](const DevTensor *d) {
@@ -1152,15 +1159,23 @@ hipError_t Context::ensure_prep(const ActQuant &aq, int K, int T) {
     return hipSuccess;
 }
 
-// Q2_K / Q3_K / IQ4_XS / TQ1_0 / TQ2_0 tensors reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
+// Q2_K / Q3_K / IQ4_XS tensors, and TQ1_0 / TQ2_0 expert tensors, reach the matrix cores only through their plane sets (no expand-on-the-fly kernel): prompt batches of 32 tokens and more
 // (the types with an exact Q8_0-layout copy: act_is_q80 without Q8_0 itself, which needs none)
 static bool q80_copy(const DevTensor &w, int K, int T) {
     return type_has_q80_copy(w.type) && w.planes && w.n_expert == 1 && mmq_q80_applicable(T_Q8_0, K, T);
 }
+// a dense ternary tensor that was given no plane set (tq_direct_tensor at load; the op entries' weights likewise): the kernel on its packed trits
+static bool tq_direct(const DevTensor &w, int K, int T) { return tq_direct_enabled() && w.n_expert == 1 && !w.planes && mmq_ternary_applicable(w.type, K, T); }
 static bool planes_small(const DevTensor &w, int K, int T) { return type_is_planes_only(w.type) && w.planes && T >= 32 && (K % 256) == 0; }
 
 PromptMatmul prompt_mul_mat_choice(int role, const DevTensor *const *ws, int n, int K, int T, MMQWorkspace wsp) {
     PromptMatmul pm;
+    bool all_tq = n <= 3;
+    for (int i = 0; i < n; i++) all_tq &= tq_direct(*ws[i], K, T) && ws[i]->type == ws[0]->type;
+    if (all_tq && (role != PM_ROLE_GATE_UP || ws[0]->N == ws[1]->N)) {        // (gate | up of different row counts: each on its own through Context::linear)
+        pm.form = PM_TERNARY; pm.n_fused = n; pm.planes_only = true; pm.swiglu = role == PM_ROLE_GATE_UP;
+        return pm;
+    }
     if (role == PM_ROLE_ONE) {
         const DevTensor &w = *ws[0];
         if (mmq_ksplit_preferred(w.type, (int)w.N, K, T, w.planes != nullptr)) {   // batched decode steps, short prompts, expert batches: MFMA, K split
@@ -1223,6 +1238,10 @@ hipError_t Context::linear(const DevTensor &w, const ActQuant &aq, const float *
         const DevTensor *w1 = &w;
         const PromptMatmul pm = pending_fuse_.mode == 0 && epi != EPI_SWIGLU ? prompt_mul_mat_choice(PM_ROLE_ONE, &w1, 1, K, T, mmq_ws_) : PromptMatmul();
         if (pm.form != PM_NONE && !(pm.planes_only && !aq.qs)) {
+            if (pm.form == PM_TERNARY) {
+                const MMQTernarySeg sg{w.data, (int)w.N, out, ld_out};
+                return launch_mmq_ternary(w.type, &sg, 1, K, T, aq, epi == EPI_ADD ? resid : nullptr, false, stream_);
+            }
             if (pm.need_prep && !bh_over_) HIP_TRY(ensure_prep(aq, K, T));
             if (pm.form == PM_KSPLIT) return launch_mmq_ksplit(w.type, w.data, w.row_bytes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_);
             if (pm.form == PM_PLANES) return launch_mmq_planes(w.type, w.planes, (int)w.N, K, T, aq, bh, bl, out, ld_out, epi == EPI_ADD ? resid : nullptr, stream_, mmq_ws_);
@@ -1280,6 +1299,11 @@ hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs,
     // Q | K | V of a batched decode step in one K-split launch; of a prompt batch as one launch over the concatenated plane sets where those are adjacent
     // (prompt_mul_mat_choice), the rest each on its own
     const PromptMatmul pm = pending_fuse_.mode == 0 ? prompt_mul_mat_choice(PM_ROLE_MULTI, ws, n, K, T, mmq_ws_) : PromptMatmul();
+    if (pm.form == PM_TERNARY && aq.qs) {                        // Q | K | V of a ternary layer: one launch over the three tensors' packed rows
+        MMQTernarySeg sg[3];
+        for (int i = 0; i < n; i++) sg[i] = MMQTernarySeg{ws[i]->data, (int)ws[i]->N, outs[i], (int)ws[i]->N};
+        return launch_mmq_ternary(ws[0]->type, sg, n, K, T, aq, nullptr, false, stream_);
+    }
     if (pm.form == PM_KSPLIT) {
         HIP_TRY(ensure_prep(aq, K, T));
         MMQSeg sg[3];
@@ -1302,7 +1326,7 @@ hipError_t Context::linear_multi(const DevTensor *const *ws, float *const *outs,
         return hipSuccess;
     }
     bool any_mmq = false;
-    for (int i = 0; i < n; i++) any_mmq |= mmq_applicable(ws[i]->type, K, T) || mmq_q80_applicable(ws[i]->type, K, T) || planes_small(*ws[i], K, T) || q80_copy(*ws[i], K, T);
+    for (int i = 0; i < n; i++) any_mmq |= mmq_applicable(ws[i]->type, K, T) || mmq_q80_applicable(ws[i]->type, K, T) || planes_small(*ws[i], K, T) || q80_copy(*ws[i], K, T) || tq_direct(*ws[i], K, T);
     if (all_q && n <= 3 && !(any_mmq && pending_fuse_.mode == 0)) {
         MMVQSeg segs[3];
         for (int i = 0; i < n; i++) segs[i] = make_seg(*ws[i], outs[i], (int)ws[i]->N, nullptr, nullptr);
@@ -1843,7 +1867,8 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
     const bool ffn_mmq = (mmq_q80_applicable(L.gate.type, E, T) && mmq_q80_applicable(L.up.type, E, T)) ||
                          (mmq_applicable(L.gate.type, E, T) && mmq_applicable(L.up.type, E, T)) ||
                          (mmq_ksplit_applicable(L.gate.type, E, T) && mmq_ksplit_applicable(L.up.type, E, T)) ||
-                         (planes_small(L.gate, E, T) && planes_small(L.up, E, T)) || (q80_copy(L.gate, E, T) && q80_copy(L.up, E, T));
+                         (planes_small(L.gate, E, T) && planes_small(L.up, E, T)) || (q80_copy(L.gate, E, T) && q80_copy(L.up, E, T)) ||
+                         (tq_direct(L.gate, E, T) && tq_direct(L.up, E, T));
     // gate | up as one MFMA launch: the K-split pair, or the plane sets with SwiGLU in the epilogue (prompt_mul_mat_choice)
     const DevTensor *gu_w[2] = {&L.gate, &L.up};
     const PromptMatmul gu_pm = fuse_ffn ? PromptMatmul() : prompt_mul_mat_choice(PM_ROLE_GATE_UP, gu_w, 2, E, T, mmq_ws_);
@@ -1881,6 +1906,12 @@ hipError_t Context::ffn_dense_gate_up(int il, const Step &st, bool &quantised) {
         quantised = !pair && down_q;
         if (quantised) HIP_TRY(quantise_for_down(il, T, false, true));
         else if (!pair) HIP_TRY(launch_swiglu(ffn_, ffn_u_, ffn_, (int64_t)T * FF, stream_));
+    } else if (gu_pm.form == PM_TERNARY) {
+        // prompt batch of a ternary layer: gate and up rows of one tile in one workgroup of the packed-trit kernel, SwiGLU in the epilogue
+        const MMQTernarySeg sg[2] = {{L.gate.data, (int)L.gate.N, ffn_, FF}, {L.up.data, (int)L.up.N, nullptr, 0}};
+        HIP_TRY(launch_mmq_ternary(L.gate.type, sg, 2, E, T, aq_e_, nullptr, true, stream_));
+        quantised = down_q;
+        if (quantised) HIP_TRY(quantise_for_down(il, T, true, false));
     } else if (T > 1 && gu_pm.form == PM_PLANES) {
         // prompt batch on the LDS kernel: gate and up in one launch, 64 rows of each per workgroup, SwiGLU in the epilogue (one
         // f32 result of T x FF instead of two); the quantiser for the down projection then reads half as much

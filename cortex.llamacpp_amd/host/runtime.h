@@ -95,7 +95,8 @@ hipError_t mmvq_tokens(MMVQSeg *segs, int n_seg, int K, int T, int epi, const Ac
 // Which MFMA launch the K-quant (and planes-only) tensors of a prompt batch or a batched decode step take: the order of predicates that Context::linear
 // (PM_ROLE_ONE), Context::linear_multi (PM_ROLE_MULTI) and the dense gate | up block (PM_ROLE_GATE_UP, ws = {gate, up}) test, stated once and shared with the
 // per-op test entry (csrc/op_entries_matmul.cc mi355_op_prompt_mul_mat).  PM_NONE: none of them - the caller goes on to its other paths.
-enum { PM_NONE = 0, PM_KSPLIT = 1, PM_PLANES = 2, PM_FLY = 3 };
+// PM_TERNARY: a dense TQ1_0 / TQ2_0 tensor without a plane set, on the kernel that reads its packed trits (csrc/mmq_ternary.hip): n_fused tensors in one launch
+enum { PM_NONE = 0, PM_KSPLIT = 1, PM_PLANES = 2, PM_FLY = 3, PM_TERNARY = 4 };
 enum { PM_ROLE_ONE = 0, PM_ROLE_MULTI = 1, PM_ROLE_GATE_UP = 2 };
 struct PromptMatmul {
     int form = PM_NONE;        // PM_ROLE_MULTI + PM_PLANES: of the fused launch; every other tensor takes its plane set, or the expansion on the fly without one
@@ -108,6 +109,9 @@ PromptMatmul prompt_mul_mat_choice(int role, const DevTensor *const *ws, int n, 
 // the process's sticky error word installed in the device globals of the current device (what Context::init does); nullptr where it could not be allocated
 unsigned *install_stream_error_word();
 
+// dense ternary tensors: no plane set at load, prompt batches on mmq_ternary.hip (default); MI355_TQ_DIRECT=0 (read once) restores the plane route - a fallback
+// and an A/B handle
+bool tq_direct_enabled();
 void set_moe_q80_grouped(bool on);  // tests / tools: MXFP4 expert tensors, prompt batches: one launch for all experts (default) or one per expert - the same bits
 void set_moe_group_min(int tokens);   // tests: batch size from which a mixture-of-experts feed-forward is grouped by expert
 void set_attn_store_fuse(bool on);   // tests: 0 = batched steps store K / V in their own launch before the attention
