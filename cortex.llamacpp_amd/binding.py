@@ -100,6 +100,9 @@ SYMBOLS = {
     "mi355_imatrix_get": (_i32, [_vp, _i32, _vp, _vp]),
     "mi355_speculative_steps": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "mi355_get_topk_ith": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
+    "mi355_sample_rows": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mi355_sampled_steps": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mi355_debug_sample_rows_calls": (_i64, [_vp]),
     "mi355_debug_mega_steps": (C.c_int64, [_vp]),
     "mi355_debug_engine_steps": (C.c_int64, [_vp]),
     "mi355_debug_fused_skipped_steps": (C.c_int64, [_vp]),
@@ -173,6 +176,8 @@ SYMBOLS = {
     "mi355_op_f32_to_f16": (C.c_int, [_vp, _i64, _vp]),
     "mi355_op_add_qkv_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32]),
     "mi355_op_topk_rows": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mi355_op_sample_rows": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mi355_op_philox_u": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, _i32, _vp]),
     "mi355_op_moe_group": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_moe_gather_act": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_moe_combine": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
@@ -221,6 +226,7 @@ SYMBOLS = {
     "mi355_engine_stop_inferencing": (None, [_vp, _cp]),
     "mi355_engine_prompt_cache_stats": (C.c_int, [_vp, _cp, _vp]),
     "mi355_engine_spec_stats": (C.c_int, [_vp, _cp, _vp]),
+    "mi355_engine_sampler_stats": (C.c_int, [_vp, _cp, _vp]),
     "mi355_engine_load": (None, [_vp, _cp, _cp, _i32, _cp, _i32, _i32]),
     "mi355_engine_unload": (None, [_vp]),
     "mi355_engine_set_file_logger": (None, [_vp, _i32, _cp]),
@@ -283,6 +289,24 @@ def _ptr(a):
 
 def _err(lib) -> str:
     return (lib.mi355_last_error() or b"").decode("utf-8", "replace")
+
+
+# mi355_sampler_params, field for field, and what a field that is not given stands for (every cut off, temperature 1)
+SAMPLER_DTYPE = np.dtype([("top_k", "<i4"), ("min_keep", "<i4"), ("top_p", "<f4"), ("min_p", "<f4"), ("typ_p", "<f4"), ("temp", "<f4"), ("penalty_repeat", "<f4"),
+                          ("penalty_freq", "<f4"), ("penalty_present", "<f4"), ("stream", "<u4"), ("seed", "<u8")], align=True)
+SAMPLER_DEFAULTS = dict(top_k=0, min_keep=0, top_p=1.0, min_p=0.0, typ_p=1.0, temp=1.0, penalty_repeat=1.0, penalty_freq=0.0, penalty_present=0.0, stream=0, seed=0)
+
+
+def sampler_params(params, n: int) -> np.ndarray:
+    """n mi355_sampler_params records from one dict (for every row) or a list of n dicts"""
+    rows = [params] * n if isinstance(params, dict) else list(params)
+    assert len(rows) == n and SAMPLER_DTYPE.itemsize == 48
+    out = np.zeros(n, SAMPLER_DTYPE)
+    for r, p in enumerate(rows):
+        assert set(p) <= set(SAMPLER_DEFAULTS), set(p) - set(SAMPLER_DEFAULTS)
+        for f, v in {**SAMPLER_DEFAULTS, **p}.items():
+            out[r][f] = v
+    return out
 
 
 def control_vector_load(lib, items):
@@ -815,6 +839,28 @@ class Backend:
                                               _ptr(rep), _ptr(freq), _ptr(pres), _ptr(keys)), "op_topk_rows")
         toks, logits = self.topk_decode(keys)
         return toks, logits, keys
+
+    def sample_rows_op(self, cand_tok, cand_logit, params, u=None, kept: bool = True):
+        """The sampler tail alone (mi355_op_sample_rows) over candidates [R][k], best first; params: one dict of SAMPLER_FIELDS per row (or one for all); u
+        [R]: the draws' u instead of Philox.  Returns (tokens [R], n_kept [R], probs [R], kept_tok [R][128], kept_p [R][128]) - the last two None without kept."""
+        tok = np.ascontiguousarray(cand_tok, np.int32); lg = np.ascontiguousarray(cand_logit, np.float32)
+        tok = tok.reshape(1, -1) if tok.ndim == 1 else tok
+        lg = lg.reshape(tok.shape)
+        R, k = tok.shape
+        sp = sampler_params(params, R)
+        uu = None if u is None else np.ascontiguousarray(u, np.float64).reshape(R)
+        out_t = np.zeros(R, np.int32); out_n = np.zeros(R, np.int32); out_p = np.zeros(R, np.float32)
+        kt = np.zeros((R, 128), np.int32) if kept else None
+        kp = np.zeros((R, 128), np.float32) if kept else None
+        self._chk(self.lib.mi355_op_sample_rows(_ptr(tok), _ptr(lg), R, k, _ptr(sp), _ptr(uu) if uu is not None else None, _ptr(out_t), _ptr(out_n), _ptr(out_p),
+                                                _ptr(kt) if kept else None, _ptr(kp) if kept else None), "op_sample_rows")
+        return out_t, out_n, out_p, kt, kp
+
+    def philox_u(self, seed: int, counter0: int, stream: int, n: int) -> np.ndarray:
+        """The device sampler's u sequence: u of (seed, counter0 + i, stream) for i < n (mi355_op_philox_u)."""
+        out = np.zeros(n, np.float32)
+        self._chk(self.lib.mi355_op_philox_u(int(seed), int(counter0), int(stream), int(n), _ptr(out)), "op_philox_u")
+        return out
 
     def lora_delta(self, segs, x: np.ndarray):
         """The adapter kernels once (mi355_op_lora_delta): segs = 1 .. 3 of (A [r][K], B [N][r], scale, out [T][ld_out]) over the rows x [T][K]; A and B both
@@ -1360,6 +1406,38 @@ class Context:
             raise MI355Error(f"mi355_greedy_steps stopped after {done} of {n}: {_err(self.lib)}")
         return out
 
+    def sample_rows(self, rows, params, draw_counter, adjs=None):
+        """The whole sampler chain on the device for batch rows `rows` of the last decode (mi355_sample_rows): params as sample_rows_op takes them,
+        draw_counter [n], adjs[r] = (tok [m], bias [m], count [m]) or None.  Returns (tokens [n] int32, probs [n] f32)."""
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        n, A = rows.size, 192
+        sp = sampler_params(params, n)
+        dc = np.ascontiguousarray(np.broadcast_to(np.asarray(draw_counter, np.uint64), (n,)))
+        an = np.zeros(n, np.int32); tok = np.zeros((n, A), np.int32); bias = np.zeros((n, A), np.float32); cnt = np.zeros((n, A), np.int32)
+        for r, a in enumerate(adjs or []):
+            if a is None:
+                continue
+            m = min(len(a[0]), A)
+            an[r] = len(a[0])                                  # (more than the arrays hold: handed over as it is, for the entry to refuse)
+            tok[r, :m] = a[0][:m]; bias[r, :m] = a[1][:m]; cnt[r, :m] = a[2][:m]
+        out_t = np.zeros(n, np.int32); out_p = np.zeros(n, np.float32)
+        rc = self.lib.mi355_sample_rows(self.h, n, _ptr(rows), _ptr(sp), _ptr(an), _ptr(tok), _ptr(bias), _ptr(cnt), _ptr(dc), _ptr(out_t), _ptr(out_p))
+        if rc != n:
+            raise MI355Error(f"mi355_sample_rows failed ({rc}): {_err(self.lib)}")
+        return out_t, out_p
+
+    def sampled_steps(self, first: int, pos0: int, n: int, params: dict, seq: int = 0):
+        """n sampled single-token steps in one C call (mi355_sampled_steps): step i draws with counter i.  Returns (tokens [n], probs [n])."""
+        sp = sampler_params(params, 1)
+        out_t = np.zeros(n, np.int32); out_p = np.zeros(n, np.float32)
+        done = self.lib.mi355_sampled_steps(self.h, int(first), int(pos0), int(seq), int(n), _ptr(sp), _ptr(out_t), _ptr(out_p))
+        if done != n:
+            raise MI355Error(f"mi355_sampled_steps stopped after {done} of {n}: {_err(self.lib)}")
+        return out_t, out_p
+
+    def sample_rows_calls(self) -> int:
+        return int(self.lib.mi355_debug_sample_rows_calls(self.h))
+
     def logits(self, i: int = -1) -> np.ndarray:
         p = self.lib.mi355_get_logits_ith(self.h, i)
         if not p:
@@ -1731,6 +1809,14 @@ class Engine:
         if rc < 0:
             raise MI355Error(f"mi355_engine_spec_stats failed ({rc}): {_err(self.lib)}")
         return dict(zip(("rounds", "drafted", "accepted", "plain_steps"), (int(v) for v in out)))
+
+    def sampler_stats(self, model_id: str) -> dict:
+        """Slot ticks sampled by the device sampler (load key "device_sampler") and by every other path."""
+        out = (C.c_int64 * 2)()
+        rc = self.lib.mi355_engine_sampler_stats(self.h, model_id.encode(), out)
+        if rc < 0:
+            raise MI355Error(f"mi355_engine_sampler_stats failed ({rc}): {_err(self.lib)}")
+        return dict(device=int(out[0]), other=int(out[1]))
 
     def stop_inferencing(self, model_id: str) -> None:
         self.lib.mi355_engine_stop_inferencing(self.h, model_id.encode())

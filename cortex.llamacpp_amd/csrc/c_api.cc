@@ -444,6 +444,71 @@ int32_t mi355_get_topk_ith(mi355_context *ctx, int32_t i, int32_t k, int32_t n_a
     if (r < 0) fail(ctx->c->last_error.empty() ? "top-k failed" : ctx->c->last_error);
     return r;
 }
+// ---- the whole sampler chain on the device (csrc/sample.hip)
+static SampleParams tail_params(const mi355_sampler_params &p, uint64_t counter) {
+    return SampleParams{p.top_k, p.min_keep, p.top_p, p.min_p, p.typ_p, p.temp, p.stream, 0u, p.seed, counter};
+}
+int32_t mi355_sample_rows(mi355_context *ctx, int32_t n, const int32_t *batch_rows, const mi355_sampler_params *params, const int32_t *adj_n, const int32_t *adj_tok,
+                          const float *adj_bias, const int32_t *adj_count, const uint64_t *draw_counter, mi355_token *tokens_out, float *probs_out) {
+    if (!ctx) return no_context("sample_rows");
+    if (n < 1 || !batch_rows || !params || !draw_counter || !tokens_out || !probs_out || (adj_n && (!adj_tok || !adj_bias || !adj_count))) {
+        fail("sample_rows: null pointer or n < 1"); return MI355_ERR_ARG;
+    }
+    MI355_GUARD(return MI355_ERR_ARG,
+        std::vector<SampleParams> sp((size_t)n);
+        std::vector<TopkAdj> adjs((size_t)n);
+        for (int r = 0; r < n; r++) {
+            sp[(size_t)r] = tail_params(params[r], draw_counter[r]);
+            TopkAdj &a = adjs[(size_t)r];
+            a.n = adj_n ? adj_n[r] : 0; a.repeat = params[r].penalty_repeat; a.freq = params[r].penalty_freq; a.present = params[r].penalty_present;
+            if (a.n < 0 || a.n > TOPK_MAX_ADJ) { fail("sample_rows: adj_n " + std::to_string(a.n) + " outside [0, " + std::to_string(TOPK_MAX_ADJ) + "]"); return MI355_ERR_ARG; }
+            const size_t o = (size_t)r * TOPK_MAX_ADJ;
+            for (int j = 0; j < a.n; j++) { a.tok[j] = adj_tok[o + j]; a.bias[j] = adj_bias[o + j]; a.cnt[j] = adj_count[o + j]; }
+        }
+        if (ctx->c->sample_rows(n, batch_rows, sp.data(), adjs.data(), tokens_out, probs_out) != n) {
+            fail(ctx->c->last_error.empty() ? "sample_rows failed" : ctx->c->last_error);
+            return MI355_ERR_ARG;
+        }
+        return n;
+    )
+}
+int32_t mi355_sampled_steps(mi355_context *ctx, mi355_token first, mi355_pos pos0, mi355_seq_id seq, int32_t n, const mi355_sampler_params *params,
+                            mi355_token *out_tokens, float *out_probs) {
+    if (!ctx) return no_context("sampled_steps");
+    if (n < 0 || !params) { fail("sampled_steps: null params or n < 0"); return MI355_ERR_ARG; }
+    MI355_GUARD(return MI355_ERR_ARG,
+        int32_t tok = first, one = 1, sid = seq;
+        int32_t *sp = &sid;
+        const int8_t flag = 1;
+        const int row = 0;
+        const bool penalties = params->penalty_repeat != 1.0f || params->penalty_freq != 0.0f || params->penalty_present != 0.0f;
+        std::vector<int32_t> window;                                   // the last 64 emitted tokens (the host sampler's default penalty_last_n)
+        std::unique_ptr<TopkAdj> adj(new TopkAdj());
+        for (int32_t i = 0; i < n; i++) {
+            int32_t pos = pos0 + i;
+            const int rc = ctx->c->decode(1, &tok, &pos, &one, &sp, &flag);
+            if (rc != 0) { if (rc < 0) fail(ctx->c->last_error); else fail("sampled_steps: no KV slot"); return i; }
+            adj->n = 0; adj->repeat = params->penalty_repeat; adj->freq = params->penalty_freq; adj->present = params->penalty_present;
+            if (penalties)
+                for (int32_t t : window) {
+                    int j = 0;
+                    while (j < adj->n && adj->tok[j] != t) j++;
+                    if (j == adj->n) { adj->tok[j] = t; adj->bias[j] = 0.0f; adj->cnt[j] = 0; adj->n++; }
+                    adj->cnt[j]++;
+                }
+            const SampleParams tp = tail_params(*params, (uint64_t)i);
+            float p = 0.0f;
+            if (ctx->c->sample_rows(1, &row, &tp, adj.get(), &tok, &p) != 1) { fail(ctx->c->last_error.empty() ? "sampled_steps: sampling failed" : ctx->c->last_error); return i; }
+            if (tok < 0) { fail("sampled_steps: the row's best logit is not finite"); return i; }
+            if (out_tokens) out_tokens[i] = tok;
+            if (out_probs) out_probs[i] = p;
+            window.push_back(tok);
+            if (window.size() > 64) window.erase(window.begin());
+        }
+        return n;
+    )
+}
+int64_t mi355_debug_sample_rows_calls(const mi355_context *ctx) { return ctx->c->sample_rows_calls; }
 int64_t mi355_debug_mega_steps(const mi355_context *ctx) { return ctx->c->mega_steps; }
 int64_t mi355_debug_engine_steps(const mi355_context *ctx) { return ctx->c->engine_steps; }
 int64_t mi355_debug_fused_skipped_steps(const mi355_context *ctx) { return ctx->c->fused_skipped_steps; }
@@ -1086,6 +1151,13 @@ int mi355_engine_spec_stats(mi355_engine *e, const char *model_id, int64_t out[4
     if (!e || !model_id || !out) { fail("spec_stats: null argument"); return MI355_ERR_ARG; }
     MI355_GUARD(return MI355_ERR_ARG,
         if (!e->eng.SpecStats(model_id, out)) { fail(std::string("spec_stats: no model ") + model_id); return MI355_ERR_ARG; }
+        return MI355_OK;
+    )
+}
+int mi355_engine_sampler_stats(mi355_engine *e, const char *model_id, int64_t out[2]) {
+    if (!e || !model_id || !out) { fail("sampler_stats: null argument"); return MI355_ERR_ARG; }
+    MI355_GUARD(return MI355_ERR_ARG,
+        if (!e->eng.SamplerStats(model_id, out)) { fail(std::string("sampler_stats: no model ") + model_id); return MI355_ERR_ARG; }
         return MI355_OK;
     )
 }

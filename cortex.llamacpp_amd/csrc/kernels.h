@@ -288,6 +288,25 @@ size_t topk_scratch_bytes(int n);       // workspace PER ROW of n logits
 // into keys_out[r * TOPK_MAX_K + 0..k) (device or pinned host memory), key = (order-preserving image of the f32 logit) << 32 | (0xffffffff - token)
 hipError_t launch_topk_rows(const float *base, int n, int n_rows, const int *rows_dev, int k, const TopkAdj *adjs_dev, void *scratch, unsigned long long *keys_out,
                             hipStream_t st);
+// ---- device-side sampler tail (sample.hip): the rest of host/sampling.cc's chain (Sampler::finish) over launch_topk_rows' keys and the draw,
+// one wave per row, so that one token per row crosses to the host.  top_k cut -> typical-p -> top_p -> min_p -> temperature -> softmax -> draw; every cut keeps
+// max(min_keep, 1) candidates; temp <= 0: candidate 0, no draw.  The arithmetic is f64 (128 candidates per row: the cost is the launch).
+struct SampleParams {                   // one per row, in device memory
+    int top_k, min_keep;                // top_k <= 0: all k candidates
+    float top_p, min_p, typ_p, temp;
+    unsigned stream, pad;               // Philox4x32-10: key = seed, counter = (counter lo, counter hi, stream, 0); u = (word 0 >> 8) * 2^-24
+    unsigned long long seed, counter;
+};
+// what launch_sample_rows refuses, by name (nullptr: nothing): "R", "k", "top_p", "min_p", "typ_p" (NaN or outside [0, 1]), "min_keep" (< 0)
+const char *sample_rows_refusal(int R, int k, const SampleParams *params_host);
+// keys [R][TOPK_MAX_K] as launch_topk_rows leaves them, k of each row valid.  params_host / params_dev: the same R records on both sides (the host's are
+// checked: hipErrorInvalidValue and nothing launched for what sample_rows_refusal names or a null pointer).  u_dev (nullable) [R]: the draw's u instead of
+// Philox (f64: the op tests aim at single candidates).  tokens_out / probs_out [R] (device or pinned host memory): the token and its final probability; a row whose best logit is not finite: -1 and 0.
+// n_kept_out (nullable) [R]; kept_tok / kept_p (nullable, both or neither) [R][TOPK_MAX_K]: the candidates that reached the draw, best first.
+hipError_t launch_sample_rows(const unsigned long long *keys, int R, int k, const SampleParams *params_host, const SampleParams *params_dev, const double *u_dev,
+                              int32_t *tokens_out, float *probs_out, int32_t *n_kept_out, int32_t *kept_tok, float *kept_p, hipStream_t st);
+// out[i] (device or pinned host memory) = the u of (seed, counter0 + i, stream), i < n
+hipError_t launch_philox_u(unsigned long long seed, unsigned long long counter0, unsigned stream, int n, float *out, hipStream_t st);
 
 // f32 / f16 weight mat-vec (router, unquantised models): y[t][r] = dot(W[r], x[t])
 // batches against F16 weights on the matrix cores (mmf.hip): y[t][n] (+ resid) = sum_k W[n][k] * f16(x[t][k]); the same products as launch_mmv_float, f32 accumulation

@@ -60,6 +60,19 @@ class IBackend {
             r.ok = topk_ith(r.i, r.k, r.tok, r.bias, r.cnt, r.repeat, r.freq, r.present, r.out_tok.data(), r.out_logit.data()) == r.k;
         }
     }
+    // the whole chain on the device (/loadmodel "device_sampler"): the front as above, then the tail and the draw, for every such slot of a
+    // tick in one call.  false: the backend has no device sampler, or the call failed - the slots then take the host chain.
+    struct SampleRequest {
+        TopkRequest front;                 // i and the adjustments (k is not read: the tail's top_k decides)
+        int top_k = 0, min_keep = 0;
+        float top_p = 1.0f, min_p = 0.0f, typ_p = 1.0f, temp = 1.0f;
+        uint64_t seed = 0, counter = 0;
+        uint32_t stream = 0;
+        int32_t out_tok = -1;
+        float out_p = 0.0f;
+    };
+    virtual bool device_sampler() const { return false; }
+    virtual bool sample_batch(std::vector<SampleRequest> &reqs) { (void)reqs; return false; }
     // ---- speculative decoding: a draft model beside this one (/loadmodel "model_draft").  The defaults are a backend without one.
     virtual bool has_draft() const { return false; }
     // The draft model's proposal for what follows tokens[0 .. n_tokens) of sequence seq.  The backend remembers what its draft context holds per sequence: it

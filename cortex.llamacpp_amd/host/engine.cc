@@ -311,6 +311,14 @@ bool LlamaEngine::SpecStats(const std::string &model_id, int64_t out[4]) {
     return true;
 }
 
+bool LlamaEngine::SamplerStats(const std::string &model_id, int64_t out[2]) {
+    std::lock_guard<std::mutex> lk(map_mutex_);
+    auto it = server_map_.find(model_id);
+    if (it == server_map_.end() || !it->second->ctx) return false;
+    it->second->ctx->SamplerStats(out);
+    return true;
+}
+
 bool LlamaEngine::PromptCacheStats(const std::string &model_id, int64_t out[6]) {
     std::lock_guard<std::mutex> lk(map_mutex_);
     auto it = server_map_.find(model_id);

@@ -340,6 +340,8 @@ Context::~Context() {
     if (h_spec_) (void)hipHostFree(h_spec_);
     if (h_lp_) (void)hipHostFree(h_lp_);
     if (d_topk_adj_) (void)hipFree(d_topk_adj_);
+    if (h_samp_) (void)hipHostFree(h_samp_);
+    if (d_samp_) (void)hipFree(d_samp_);
     if (topk_scratch_) { (void)hipFree(topk_scratch_); topk_scratch_ = nullptr; }
     if (h_moe_meta_) (void)hipHostFree(h_moe_meta_);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -2881,6 +2883,40 @@ int Context::perplexity(const int32_t *tokens, int64_t n_tokens, int n_chunk, in
     return rc;
 }
 
+// the front's workspace and inputs: the device selected, everything grown to n rows, the adjustments and row numbers (rows of d_logits_) queued on the stream
+bool Context::topk_stage(int n, const int *rows, const TopkAdj *adjs) {
+    if (hipSetDevice(model->device) != hipSuccess) return false;
+    const int V = model->hp.n_vocab;
+    if (n > topk_rows_cap_) {
+        (void)hipStreamSynchronize(stream_);
+        if (topk_scratch_) (void)hipFree(topk_scratch_);
+        if (d_topk_adj_) (void)hipFree(d_topk_adj_);
+        if (h_topk_) (void)hipHostFree(h_topk_);
+        if (h_topk_adj_) (void)hipHostFree(h_topk_adj_);
+        topk_scratch_ = nullptr; d_topk_adj_ = nullptr; h_topk_ = nullptr; h_topk_adj_ = nullptr; topk_rows_cap_ = 0;
+        const int cap = std::max(n, std::min(64, (int)cp.n_seq_max));
+        const size_t adj_bytes = (size_t)cap * sizeof(TopkAdj) + (size_t)cap * sizeof(int);
+        if (hipMalloc(&topk_scratch_, topk_scratch_bytes(V) * (size_t)cap) != hipSuccess || hipMalloc((void **)&d_topk_adj_, adj_bytes) != hipSuccess ||
+            hipHostMalloc((void **)&h_topk_, (size_t)cap * TOPK_MAX_K * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void **)&h_topk_adj_, adj_bytes, hipHostMallocDefault) != hipSuccess) { last_error = "top-k workspace allocation failed"; return false; }
+        topk_rows_cap_ = cap;
+    }
+    // adjustments and row numbers: one staged copy
+    TopkAdj *ha = reinterpret_cast<TopkAdj *>(h_topk_adj_);
+    int *hr = reinterpret_cast<int *>(h_topk_adj_ + (size_t)topk_rows_cap_ * sizeof(TopkAdj));
+    for (int r = 0; r < n; r++) {
+        TopkAdj &d = ha[r];
+        const TopkAdj &a = adjs[r];
+        d.n = a.n; d.repeat = a.repeat; d.freq = a.freq; d.present = a.present;
+        memcpy(d.tok, a.tok, (size_t)a.n * sizeof(int)); memcpy(d.bias, a.bias, (size_t)a.n * sizeof(float)); memcpy(d.cnt, a.cnt, (size_t)a.n * sizeof(int));
+        hr[r] = rows[r];
+    }
+    const size_t rows_off = (size_t)topk_rows_cap_ * sizeof(TopkAdj);
+    if (hipMemcpyAsync(d_topk_adj_, h_topk_adj_, (size_t)n * sizeof(TopkAdj), hipMemcpyHostToDevice, stream_) != hipSuccess ||
+        hipMemcpyAsync(d_topk_adj_ + rows_off, h_topk_adj_ + rows_off, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "top-k staging failed"; return false; }
+    return true;
+}
+
 // n rows of the last batch in ONE set of launches and ONE synchronisation (a scheduler tick asks for all its sampling slots together: row by row, each
 // with its own launch + sync, 32 slots cost more than copying 32 rows to the host did).  toks / logits: [n][TOPK_MAX_K]; ks[r] of each row are valid.
 int Context::topk_rows(int n, const int *is, const int *ks, const TopkAdj *adjs, int32_t *toks, float *logits) {
@@ -2896,34 +2932,8 @@ int Context::topk_rows(int n, const int *is, const int *ks, const TopkAdj *adjs,
         rows[(size_t)r] = out_row_of_batch_[(size_t)i];
         kmax = std::max(kmax, ks[r]);
     }
-    if (hipSetDevice(model->device) != hipSuccess) return -1;
-    if (n > topk_rows_cap_) {
-        (void)hipStreamSynchronize(stream_);
-        if (topk_scratch_) (void)hipFree(topk_scratch_);
-        if (d_topk_adj_) (void)hipFree(d_topk_adj_);
-        if (h_topk_) (void)hipHostFree(h_topk_);
-        if (h_topk_adj_) (void)hipHostFree(h_topk_adj_);
-        topk_scratch_ = nullptr; d_topk_adj_ = nullptr; h_topk_ = nullptr; h_topk_adj_ = nullptr; topk_rows_cap_ = 0;
-        const int cap = std::max(n, std::min(64, (int)cp.n_seq_max));
-        const size_t adj_bytes = (size_t)cap * sizeof(TopkAdj) + (size_t)cap * sizeof(int);
-        if (hipMalloc(&topk_scratch_, topk_scratch_bytes(V) * (size_t)cap) != hipSuccess || hipMalloc((void **)&d_topk_adj_, adj_bytes) != hipSuccess ||
-            hipHostMalloc((void **)&h_topk_, (size_t)cap * TOPK_MAX_K * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void **)&h_topk_adj_, adj_bytes, hipHostMallocDefault) != hipSuccess) { last_error = "top-k workspace allocation failed"; return -1; }
-        topk_rows_cap_ = cap;
-    }
-    // adjustments and row numbers: one staged copy
-    TopkAdj *ha = reinterpret_cast<TopkAdj *>(h_topk_adj_);
-    int *hr = reinterpret_cast<int *>(h_topk_adj_ + (size_t)topk_rows_cap_ * sizeof(TopkAdj));
-    for (int r = 0; r < n; r++) {
-        TopkAdj &d = ha[r];
-        const TopkAdj &a = adjs[r];
-        d.n = a.n; d.repeat = a.repeat; d.freq = a.freq; d.present = a.present;
-        memcpy(d.tok, a.tok, (size_t)a.n * sizeof(int)); memcpy(d.bias, a.bias, (size_t)a.n * sizeof(float)); memcpy(d.cnt, a.cnt, (size_t)a.n * sizeof(int));
-        hr[r] = rows[(size_t)r];
-    }
+    if (!topk_stage(n, rows.data(), adjs)) return -1;
     const size_t rows_off = (size_t)topk_rows_cap_ * sizeof(TopkAdj);
-    if (hipMemcpyAsync(d_topk_adj_, h_topk_adj_, (size_t)n * sizeof(TopkAdj), hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        hipMemcpyAsync(d_topk_adj_ + rows_off, h_topk_adj_ + rows_off, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "top-k staging failed"; return -1; }
     if (launch_topk_rows(d_logits_, V, n, reinterpret_cast<const int *>(d_topk_adj_ + rows_off), kmax, reinterpret_cast<const TopkAdj *>(d_topk_adj_), topk_scratch_, h_topk_,
                          stream_) != hipSuccess) { last_error = "top-k launch failed"; return -1; }
     if (hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
@@ -2947,6 +2957,59 @@ int Context::topk_ith(int i, int k, const TopkAdj &adj, int32_t *toks, float *lo
     memcpy(toks, t, (size_t)k * sizeof(int32_t));
     memcpy(logits, l, (size_t)k * sizeof(float));
     return k;
+}
+
+// The whole chain on the device (csrc/sample.hip): the front's keys stay in device memory, the tail reads them in the next launch of the same
+// stream and writes a token and a probability per row into pinned memory - two launches, one synchronisation, 8 n bytes back.
+int Context::sample_rows(int n, const int *is, const SampleParams *sp, const TopkAdj *adjs, int32_t *toks_out, float *probs_out) {
+    if (last_was_embd_) { last_error = "sample_rows: embeddings mode computes no logits"; return -1; }
+    if (model->hp.tp_size > 1) { last_error = "sample_rows: not on a rank of a row split"; return -1; }
+    if (n < 1 || !is || !sp || !adjs || !toks_out || !probs_out) { last_error = "sample_rows: bad arguments (null pointer or n < 1)"; return -1; }
+    const int V = model->hp.n_vocab, nb = (int)out_row_of_batch_.size();
+    int kmax = 0;
+    std::vector<int> rows((size_t)n);
+    for (int r = 0; r < n; r++) {
+        int i = is[r];
+        if (i < 0) i += nb;
+        if (i < 0 || i >= nb || out_row_of_batch_[(size_t)i] < 0) { last_error = "sample_rows: batch row " + std::to_string(is[r]) + " was not flagged for logits"; return -1; }
+        if (sp[r].top_k < 1 || sp[r].top_k > TOPK_MAX_K) { last_error = "sample_rows: top_k " + std::to_string(sp[r].top_k) + " outside [1, " + std::to_string(TOPK_MAX_K) + "]"; return -1; }
+        if (adjs[r].n < 0 || adjs[r].n > TOPK_MAX_ADJ) { last_error = "sample_rows: adj_n " + std::to_string(adjs[r].n) + " outside [0, " + std::to_string(TOPK_MAX_ADJ) + "]"; return -1; }
+        rows[(size_t)r] = out_row_of_batch_[(size_t)i];
+        kmax = std::max(kmax, std::min(std::max(sp[r].top_k, sp[r].min_keep), TOPK_MAX_K));
+    }
+    kmax = std::min(kmax, V);
+    if (const char *word = sample_rows_refusal(n, kmax, sp)) { last_error = std::string("sample_rows: ") + word + " outside what the sampler takes"; return -1; }
+    if (!topk_stage(n, rows.data(), adjs)) return -1;
+    if (samp_cap_ < topk_rows_cap_) {
+        (void)hipStreamSynchronize(stream_);
+        if (d_samp_) (void)hipFree(d_samp_);
+        if (h_samp_) (void)hipHostFree(h_samp_);
+        d_samp_ = nullptr; h_samp_ = nullptr; samp_cap_ = 0;
+        const size_t cap = (size_t)topk_rows_cap_;
+        if (hipMalloc((void **)&d_samp_, cap * (TOPK_MAX_K * 8 + sizeof(SampleParams))) != hipSuccess ||
+            hipHostMalloc((void **)&h_samp_, cap * (sizeof(SampleParams) + 8), hipHostMallocDefault) != hipSuccess) { last_error = "sample_rows: workspace allocation failed"; return -1; }
+        samp_cap_ = topk_rows_cap_;
+    }
+    const size_t cap = (size_t)samp_cap_;
+    unsigned long long *d_keys = reinterpret_cast<unsigned long long *>(d_samp_);
+    SampleParams *d_sp = reinterpret_cast<SampleParams *>(d_samp_ + cap * TOPK_MAX_K * 8), *h_sp = reinterpret_cast<SampleParams *>(h_samp_);
+    int32_t *h_tok = reinterpret_cast<int32_t *>(h_samp_ + cap * sizeof(SampleParams));
+    float *h_p = reinterpret_cast<float *>(h_tok + cap);
+    memcpy(h_sp, sp, (size_t)n * sizeof(SampleParams));
+    if (hipMemcpyAsync(d_sp, h_sp, (size_t)n * sizeof(SampleParams), hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "sample_rows: staging failed"; return -1; }
+    const size_t rows_off = (size_t)topk_rows_cap_ * sizeof(TopkAdj);
+    if (launch_topk_rows(d_logits_, V, n, reinterpret_cast<const int *>(d_topk_adj_ + rows_off), kmax, reinterpret_cast<const TopkAdj *>(d_topk_adj_), topk_scratch_, d_keys,
+                         stream_) != hipSuccess ||
+        launch_sample_rows(d_keys, n, kmax, h_sp, d_sp, nullptr, h_tok, h_p, nullptr, nullptr, nullptr, stream_) != hipSuccess) {
+        (void)hipStreamSynchronize(stream_);
+        last_error = "sample_rows: launch failed"; return -1;
+    }
+    if (hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
+    argmax_fetched_ = true;
+    sample_rows_calls++;
+    memcpy(toks_out, h_tok, (size_t)n * 4);
+    memcpy(probs_out, h_p, (size_t)n * 4);
+    return n;
 }
 
 int Context::debug_layer_out(int il, float *dst, size_t cap) {

@@ -195,6 +195,11 @@ class Context {
     // first; returns the count written (k) or < 0
     int topk_ith(int i, int k, const TopkAdj &adj, int32_t *toks, float *logits);
     int topk_rows(int n, const int *is, const int *ks, const TopkAdj *adjs, int32_t *toks, float *logits);   // n rows at once; outputs [n][TOPK_MAX_K]
+    // the whole sampler chain on the device: the top-k front over batch rows is[r] with adjs[r], then launch_sample_rows over its keys with
+    // sp[r] - two launches, one synchronisation, a token and its probability per row back.  Returns n, or -1 with last_error set (embeddings mode, a row
+    // that was not flagged, a rank of a row split, top_k outside [1, 128], what sample_rows_refusal names).
+    int sample_rows(int n, const int *is, const SampleParams *sp, const TopkAdj *adjs, int32_t *toks_out, float *probs_out);
+    int64_t sample_rows_calls = 0;             // diagnosis: calls of sample_rows that reached the device
     void synchronize();
 
     // llama_set_adapter_lora / llama_rm_adapter_lora / llama_clear_adapter_lora: the adapters this context's steps apply, in the order they were first set
@@ -446,6 +451,9 @@ class Context {
     void *topk_scratch_ = nullptr;                     // launch_topk_rows workspace (own allocation, sized for topk_rows_cap_ rows on first use)
     uint8_t *d_topk_adj_ = nullptr, *h_topk_adj_ = nullptr;   // [cap] TopkAdj + [cap] row numbers: device copy and its pinned staging
     int topk_rows_cap_ = 0;
+    bool topk_stage(int n, const int *rows, const TopkAdj *adjs);   // device selected, the workspace grown to n rows, adjustments and row numbers queued
+    uint8_t *d_samp_ = nullptr, *h_samp_ = nullptr;    // sample_rows, [topk_rows_cap_] each: keys | params on the device; pinned: params, then tokens | probabilities
+    int samp_cap_ = 0;
     float *spec_scratch_ = nullptr;                    // argmax_prob_ith / spec_verify: part and ticket words of the two kernels (first use)
     int32_t *d_spec_in_ = nullptr, *h_spec_ = nullptr; // rows | group starts | drafts on the device; pinned: their staging, then ids | accepted | (index, p)
     bool spec_prepare();

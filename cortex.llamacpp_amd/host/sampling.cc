@@ -14,6 +14,7 @@ void Sampler::reset() {
     uint32_t seed = p_.seed;
     if (seed == 0xFFFFFFFFu) seed = std::random_device{}();
     rng_.seed(seed);
+    dev_seed_ = seed; n_draws_ = 0;
     mu_ = 2.0f * p_.mirostat_tau;
     if (gm_) gm_->reset();
 }

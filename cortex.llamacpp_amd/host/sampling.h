@@ -63,6 +63,18 @@ class Sampler {
     // asked for): the caller may then take the device-side argmax instead of reading the row
     bool is_plain_greedy() const;
     void set_greedy_result(int32_t tok) { cand_.assign(1, TokenProb{tok, 1.0f}); }
+    // the device sampler (csrc/sample.hip) can run the rest of the chain and the draw as well: no grammar, mirostat, n_probs or dynatemp,
+    // top_k within [1, max_k], and top_p, min_p and typ_p inside [0, 1] (the launcher refuses a whole call for one value outside; the host chain reads such a
+    // value as "off", so that request alone stays there).  Its RNG is the device's: device_seed() is the Philox key (the request's seed; a random one for
+    // seed -1, fixed at reset) and device_draw() the draw counter, which set_device_result() advances: one per token the device sampled.
+    bool device_tail_ok(int max_k) const {
+        const auto unit = [](float v) { return v >= 0.0f && v <= 1.0f; };   // (false for NaN)
+        return !gm_ && p_.mirostat != 1 && p_.mirostat != 2 && p_.n_probs <= 0 && !(p_.dynatemp_range > 0.0f) && p_.top_k >= 1 && p_.top_k <= max_k && p_.min_keep <= max_k &&
+               unit(p_.top_p) && unit(p_.min_p) && unit(p_.typ_p);
+    }
+    uint64_t device_seed() const { return dev_seed_; }
+    uint64_t device_draw() const { return n_draws_; }
+    void set_device_result(int32_t tok, float p) { cand_.assign(1, TokenProb{tok, p}); n_draws_++; }
     // candidates of the last sample(), sorted by probability (descending), probabilities after the chain
     const std::vector<TokenProb> &candidates() const { return cand_; }
     const SamplingParams &params() const { return p_; }
@@ -77,6 +89,7 @@ class Sampler {
     std::vector<int32_t> prev_;     // ring of accepted tokens (penalty window)
     std::vector<TokenProb> cand_;
     std::mt19937 rng_;
+    uint64_t dev_seed_ = 0, n_draws_ = 0;
     std::vector<float> probs_;       // (scratch of the draw)
     float mu_ = 0.0f;               // mirostat: running surprise target (starts at 2 tau)
 };

@@ -1008,13 +1008,42 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
             }
             if (spec_emit[gi].empty()) spec_emit[gi].push_back(-1);      // (no logits: phase 2 reports it)
         }
+        // "device_sampler" (DESIGN.md §4.14): the slots whose whole chain the device can run - no grammar, mirostat, n_probs or dynatemp, top_k within the
+        // front's limit - go through ONE sample_batch call and bring back a token each; a slot that does not qualify, or a call that fails, takes the paths below.
+        // The Philox stream is 0 for every slot: a request's draws depend on its seed and its draw counter, never on the slot it was given
+        size_t n_dev = 0;
+        if (be_->device_sampler()) {
+            std::vector<IBackend::SampleRequest> dev;
+            std::vector<size_t> dev_slot;
+            for (size_t gi = 0; gi < gen.size(); gi++) {
+                LlamaClientSlot &slot = *gen[gi];
+                const SamplingParams &sp = slot.smpl->params();
+                Sampler::FrontPlan fp;
+                if (!spec_emit[gi].empty() || !(sp.temp > 0.0f) || !slot.smpl->device_tail_ok(be_->topk_max_k()) ||
+                    !slot.smpl->plan_front(n_vocab_now, be_->topk_max_k(), be_->topk_max_adj(), fp)) continue;
+                IBackend::SampleRequest rq;
+                rq.front.i = slot.i_batch - i; rq.front.k = fp.k; rq.front.tok = std::move(fp.tok); rq.front.bias = std::move(fp.bias); rq.front.cnt = std::move(fp.cnt);
+                rq.front.repeat = sp.penalty_repeat; rq.front.freq = sp.penalty_freq; rq.front.present = sp.penalty_present;
+                rq.top_k = sp.top_k; rq.min_keep = std::max(sp.min_keep, 0); rq.top_p = sp.top_p; rq.min_p = sp.min_p; rq.typ_p = sp.typ_p; rq.temp = sp.temp;
+                rq.seed = slot.smpl->device_seed(); rq.counter = slot.smpl->device_draw(); rq.stream = 0;
+                dev.push_back(std::move(rq));
+                dev_slot.push_back(gi);
+            }
+            if (!dev.empty() && be_->sample_batch(dev))
+                for (size_t di = 0; di < dev.size(); di++) {
+                    if (dev[di].out_tok < 0) continue;
+                    ids[dev_slot[di]] = dev[di].out_tok;
+                    gen[dev_slot[di]]->smpl->set_device_result(dev[di].out_tok, dev[di].out_p);
+                    sampler_stats_[0]++; n_dev++;
+                }
+        }
         // device-side head of the chain (logit_bias -> penalties -> top_k): k candidates per slot cross instead of the row, all the
         // tick's sampling slots in one request to the backend
         std::vector<IBackend::TopkRequest> front;
         std::vector<size_t> front_slot;
         for (size_t gi = 0; gi < gen.size(); gi++) {
             LlamaClientSlot &slot = *gen[gi];
-            if (!spec_emit[gi].empty()) continue;           // (this tick's tokens are known already)
+            if (!spec_emit[gi].empty() || ids[gi] >= 0) continue;   // (this tick's tokens are known already)
             if (slot.smpl->is_plain_greedy()) {             // device-side greedy front end: no pass over the vocabulary on the host
                 ids[gi] = be_->argmax_ith(slot.i_batch - i);
                 if (ids[gi] >= 0) { slot.smpl->set_greedy_result(ids[gi]); continue; }
@@ -1051,6 +1080,7 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
         };
         if (!sample_pool_) sample_pool_.reset(new SamplePool((int)std::min<unsigned>(7u, std::max(1u, std::thread::hardware_concurrency()) - 1u)));
         sample_pool_->run((int)gen.size(), sample_one);
+        sampler_stats_[1] += (int64_t)(gen.size() - n_dev);
         const int64_t t_p0 = time_us();
         // phase 2: in slot order, exactly as the reference's loop (:1665-1704)
         for (size_t gi = 0; gi < gen.size(); gi++) {

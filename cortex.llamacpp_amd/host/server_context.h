@@ -128,6 +128,8 @@ class LlamaServerContext {
     // speculative decoding, the counters of mi355_speculative_steps: rounds (ticks of a speculating slot), drafted, accepted (drafts that were emitted), plain
     // steps (rounds without a drafted token).  For one request: tokens_predicted = rounds + accepted.
     void SpecStats(int64_t out[4]) const;
+    // slot ticks whose token came from the backend's device sampler ("device_sampler"), slot ticks that took any other path
+    void SamplerStats(int64_t out[2]) const { out[0] = sampler_stats_[0].load(); out[1] = sampler_stats_[1].load(); }
 
     // one scheduler tick, exposed for tests (the background thread calls it forever)
     bool UpdateSlots();
@@ -177,6 +179,7 @@ class LlamaServerContext {
     std::unique_ptr<PromptCache> prompt_cache_;       // null: "cache_ram" 0, or a backend without sequence states
     bool SlotSpeculates(const LlamaClientSlot &slot) const;
     std::atomic<int64_t> spec_stats_[4] = {{0}, {0}, {0}, {0}};
+    std::atomic<int64_t> sampler_stats_[2] = {{0}, {0}};
 
     IBackend *be_;
     int id_gen_ = 0;

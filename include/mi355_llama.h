@@ -227,6 +227,33 @@ MI355_API int32_t mi355_imatrix_get(mi355_context *ctx, int32_t i, float *sum2, 
 MI355_API int32_t mi355_get_topk_ith(mi355_context *ctx, int32_t i, int32_t k, int32_t n_adj, const int32_t *adj_tok, const float *adj_bias,
                                      const int32_t *adj_count, float penalty_repeat, float penalty_freq, float penalty_present,
                                      int32_t *toks_out, float *logits_out);
+/* ---- the whole sampler chain on the device: mi355_get_topk_ith's front, then the rest of the chain and the draw in one more launch.
+ * Chain: logit_bias -> penalties -> top_k (1 .. 128) -> typical-p -> top_p -> min_p -> temperature -> softmax -> draw; every cut keeps max(min_keep, 1)
+ * candidates; temp <= 0 gives the front's best candidate and draws nothing.  The draw: Philox4x32-10 with the seed as key and (draw counter, stream) as counter,
+ * u = (word 0 >> 8) * 2^-24, the first kept candidate whose running probability exceeds u.  Reproducible per (seed, stream, counter); NOT the sequence of the
+ * host sampler's std::mt19937 for the same seed. */
+typedef struct mi355_sampler_params {
+    int32_t  top_k, min_keep;
+    float    top_p, min_p, typ_p, temp;
+    float    penalty_repeat, penalty_freq, penalty_present;
+    uint32_t stream;                      /* rows that share a seed take different streams */
+    uint64_t seed;
+} mi355_sampler_params;
+/* n rows of the last mi355_decode (device logits, also with logits_to_host = 0): row batch_rows[r] with params[r], draw counter draw_counter[r] and its
+ * adjusted tokens, adj_n[r] <= 192 entries of the flat [n][192] arrays adj_tok / adj_bias / adj_count (all nullable when no row has any; as mi355_get_topk_ith).
+ * The front's launches, the tail's launch, one synchronisation; tokens_out [n] and probs_out [n] (the token's probability after the chain) come back, 8 n bytes; a row
+ * whose best logit is not finite gives -1.  Returns n; MI355_ERR_ARG with the word in mi355_last_error for: embeddings mode, a row that was not flagged, a rank
+ * of a row split, top_k outside [1, 128], top_p / min_p / typ_p NaN or outside [0, 1], min_keep < 0, adj_n outside [0, 192], null pointers. */
+MI355_API int32_t mi355_sample_rows(mi355_context *ctx, int32_t n, const int32_t *batch_rows, const mi355_sampler_params *params, const int32_t *adj_n,
+                                    const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_count, const uint64_t *draw_counter,
+                                    mi355_token *tokens_out, float *probs_out);
+/* The sampled twin of mi355_greedy_steps: step i decodes the previous token at pos0 + i, samples row 0 through mi355_sample_rows with draw counter i and feeds
+ * the token back.  The penalty window (the last 64 emitted tokens, at most 192 distinct) is kept on the C side.  out_tokens / out_probs (nullable) [n].  Returns
+ * the steps done (n, or fewer with the reason in mi355_last_error). */
+MI355_API int32_t mi355_sampled_steps(mi355_context *ctx, mi355_token first, mi355_pos pos0, mi355_seq_id seq, int32_t n, const mi355_sampler_params *params,
+                                      mi355_token *out_tokens, float *out_probs);
+/* diagnosis: calls of mi355_sample_rows (and of the slot loop's device sampler) this context served */
+MI355_API int64_t mi355_debug_sample_rows_calls(const mi355_context *ctx);
 /* diagnosis: single-token steps this context ran as ONE launch (decode_mega.hip; see mi355_debug_set_option "decode_mega") */
 MI355_API int64_t mi355_debug_mega_steps(const mi355_context *ctx);
 /* diagnosis: single-token steps this context ran through the layer engine (decode_engine.hip: one persistent launch per layer for the mat-vecs between two
@@ -522,6 +549,13 @@ MI355_API int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_bas
 MI355_API int mi355_op_topk_rows(const float *base, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t n_rows, int32_t k, const int32_t *adj_n,
                                  const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_cnt, const float *repeat, const float *freq,
                                  const float *present, uint64_t *keys_out);
+/* The sampler tail alone (csrc/sample.hip): R rows of k <= 128 candidates, cand_tok / cand_logit [R][k] best first, params [R] (the penalties are not read).
+ * u (nullable) [R], f64 so that a test can aim at any candidate's interval: the draw's u instead of Philox (whose counter here is draw 0 of params' stream).  tokens_out / n_kept_out / probs_out [R];
+ * kept_tok_out / kept_p_out (nullable, both or neither) [R][128]: the candidates that reached the draw and their probabilities, best first, n_kept of them. */
+MI355_API int mi355_op_sample_rows(const int32_t *cand_tok, const float *cand_logit, int32_t R, int32_t k, const mi355_sampler_params *params, const double *u,
+                                   int32_t *tokens_out, int32_t *n_kept_out, float *probs_out, int32_t *kept_tok_out, float *kept_p_out);
+/* out [n]: the device's u for (seed, counter0 + i, stream) */
+MI355_API int mi355_op_philox_u(uint64_t seed, uint64_t counter0, uint32_t stream, int32_t n, float *out);
 /* Grouping of the T * k selections ids [T][k] of a prompt batch by expert (T * k <= 61440, n_expert <= 256): a counting sort, stable in (token, rank) order.
  * meta [2 * n_expert + 1]: counts | exclusive offsets | total; slot_of [T * k]: grouped row of pair t * k + j; tok_of [T * k]: token of a grouped row. */
 MI355_API int mi355_op_moe_group(const int32_t *ids, int64_t T, int32_t k, int32_t n_expert, int32_t *meta, int32_t *slot_of, int32_t *tok_of);
@@ -681,6 +715,9 @@ MI355_API int mi355_engine_prompt_cache_stats(mi355_engine *e, const char *model
    mi355_speculative_steps counts them: rounds (ticks of a speculating slot), drafted, accepted (drafts that were emitted), plain steps (rounds without a drafted
    token) - all zero without a draft model.  < 0: no such model. */
 MI355_API int mi355_engine_spec_stats(mi355_engine *e, const char *model_id, int64_t out[4]);
+/* The device sampler of a model loaded with "device_sampler": true: out = slot ticks whose token came through mi355_sample_rows' path,
+   slot ticks that took any other path (host chain, greedy arg-max, speculative rounds) - the first stays zero without the key.  < 0: no such model. */
+MI355_API int mi355_engine_sampler_stats(mi355_engine *e, const char *model_id, int64_t out[2]);
 /* EngineI::Load(EngineLoadOption) / Unload(EngineUnloadOption) (base/cortex-common/enginei.h:14-35; LlamaEngine: src/llama_engine.cc:289-303): Load =
    SetFileLogger(max_log_lines, log_path) + SetLogLevel(log_level).  Paths as UTF-8 strings (std::filesystem::path::string()), log_level = the value of
    trantor::Logger::LogLevel (kTrace 0, kDebug 1, kInfo 2, kWarn 3, kError 4, kFatal 5). */
