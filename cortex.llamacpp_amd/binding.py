@@ -166,6 +166,9 @@ SYMBOLS = {
     "mi355_quantize_chunk": (C.c_int, [_i32, _i32, _vp, _i64, _i64, _vp, _vp]),
     "mi355_quantize_supported": (C.c_int, [_i32]),
     "mi355_quantize_last_times": (C.c_int, [_vp, _vp, _vp]),
+    "mi355_lora_merge_rows": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i32, _i32, _vp]),
+    "mi355_lora_merge_supported": (C.c_int, [_i32]),
+    "mi355_lora_merge_last_times": (C.c_int, [_vp, _vp, _vp]),
     "mi355_op_clip_attn": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_mul_mat_f16_xh": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _f32, _i32, _vp, _i32, _i32, _vp]),
     "mi355_op_layer_norm": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _f32, _i32, _vp, _vp]),
@@ -273,8 +276,8 @@ def load_library(path: str | None = None):
         raise MI355Error(f"{p} not found: build it with `python cortex.llamacpp_amd/build.py` (hipcc, gfx950)")
     lib = C.CDLL(p)
     for name, (res, args) in SYMBOLS.items():
-        if name.startswith("mi355_debug_") and os.environ.get("MI355_LLAMA_LIB") and not hasattr(lib, name):
-            continue                     # (tools/ab_libs.sh: an older build of the library under MI355_LLAMA_LIB may lack a diagnosis getter)
+        if name.startswith(("mi355_debug_", "mi355_lora_merge_")) and os.environ.get("MI355_LLAMA_LIB") and not hasattr(lib, name):
+            continue                     # (tools/ab_libs.sh: an older build of the library under MI355_LLAMA_LIB may lack a diagnosis getter, or the merge)
         fn = getattr(lib, name)          # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -295,6 +298,10 @@ def _err(lib) -> str:
 SAMPLER_DTYPE = np.dtype([("top_k", "<i4"), ("min_keep", "<i4"), ("top_p", "<f4"), ("min_p", "<f4"), ("typ_p", "<f4"), ("temp", "<f4"), ("penalty_repeat", "<f4"),
                           ("penalty_freq", "<f4"), ("penalty_present", "<f4"), ("stream", "<u4"), ("seed", "<u8")], align=True)
 SAMPLER_DEFAULTS = dict(top_k=0, min_keep=0, top_p=1.0, min_p=0.0, typ_p=1.0, temp=1.0, penalty_repeat=1.0, penalty_freq=0.0, penalty_present=0.0, stream=0, seed=0)
+
+
+# mi355_lora_merge_adapter, field for field
+LORA_MERGE_DTYPE = np.dtype([("a", "<u8"), ("b", "<u8"), ("r", "<i4"), ("pair_type", "<i4"), ("scale", "<f4")], align=True)
 
 
 def sampler_params(params, n: int) -> np.ndarray:
@@ -771,6 +778,38 @@ class Backend:
         out = np.zeros((n_rows, n // be * bb if n % be == 0 else 1), np.uint8)
         self._chk(self.lib.mi355_quantize_chunk(dst_type, src_type, _ptr(x), n, n_rows, _ptr(im), _ptr(out)), "quantize_chunk")
         return out
+
+    def lora_merge_rows(self, base_type: int, base_rows: np.ndarray, adapters, out_type: int = F16) -> np.ndarray:
+        """The merged-LoRA export's rows (mi355_lora_merge_rows): base_rows [n_rows][...] - the rows as the GGUF file holds them: float32 / float16 arrays, uint16
+        bf16 bits, or uint8 block bytes - plus sum_i scale_i * B_i A_i for adapters = [(A [r][K], B [n_rows][r], scale), ...], each pair float16 or float32;
+        -> float16 or float32 [n_rows][K].  A type, rank or shape the entry refuses raises MI355Error; so does a library built before the entry existed."""
+        from .gguf_synth import BLOCK_BYTES, BLOCK_ELEMS
+        if not hasattr(self.lib, "mi355_lora_merge_rows"):
+            raise MI355Error("this build of the library has no mi355_lora_merge_rows")
+        w = np.ascontiguousarray(base_rows)
+        assert w.ndim == 2
+        n_rows = w.shape[0]
+        row_bytes = w.shape[1] * w.dtype.itemsize
+        bb = BLOCK_BYTES.get(base_type, 1)
+        K = row_bytes // bb * BLOCK_ELEMS.get(base_type, 1) if row_bytes % bb == 0 else 0
+        recs = np.zeros(max(len(adapters), 1), LORA_MERGE_DTYPE)
+        keep = []
+        for i, (a, b, scale) in enumerate(adapters):
+            dt = a.dtype if a.dtype in (np.float16, np.float32) else np.dtype(np.float32)
+            a, b = np.ascontiguousarray(a, dt), np.ascontiguousarray(b, dt)
+            assert a.ndim == 2 and b.ndim == 2 and a.shape[0] == b.shape[1] and a.shape[1] == K and b.shape[0] == n_rows, (a.shape, b.shape, n_rows, K)
+            keep += [a, b]
+            recs[i] = (a.ctypes.data, b.ctypes.data, a.shape[0], F16 if dt == np.float16 else F32, scale)
+        out = np.zeros((n_rows, K), np.float16 if out_type == F16 else np.float32)
+        self._chk(self.lib.mi355_lora_merge_rows(base_type, _ptr(w), n_rows, K, _ptr(recs), len(adapters), out_type, _ptr(out)), "lora_merge_rows")
+        return out
+
+    def lora_merge_last_times(self):
+        """(upload, kernel, download) milliseconds of this thread's last lora_merge_rows (mi355_lora_merge_last_times)"""
+        t = np.zeros(3, np.float32)
+        p = t.ctypes.data
+        self._chk(self.lib.mi355_lora_merge_last_times(C.c_void_p(p), C.c_void_p(p + 4), C.c_void_p(p + 8)), "lora_merge_last_times")
+        return float(t[0]), float(t[1]), float(t[2])
 
     def add_row_vec(self, x: np.ndarray, v: np.ndarray) -> np.ndarray:
         """The control vector's add once (mi355_op_add_row_vec): x [T][E] + v [E]; returns [T + 1][E], the last row the guard row behind the rows (0xA5 bytes)."""

@@ -877,6 +877,81 @@ int mi355_quantize_chunk(int32_t dst_type, int32_t src_type, const void *src, in
     return MI355_OK;
 }
 
+int mi355_lora_merge_supported(int32_t base_type) { return lora_merge_base_supported(base_type) ? 1 : 0; }
+
+static thread_local float t_merge_ms[3] = {-1.0f, -1.0f, -1.0f};
+int mi355_lora_merge_last_times(float *upload_ms, float *kernel_ms, float *download_ms) {
+    if (t_merge_ms[0] < 0.0f) { fail("lora_merge_last_times: no completed mi355_lora_merge_rows on this thread"); return MI355_ERR_ARG; }
+    if (upload_ms) *upload_ms = t_merge_ms[0];
+    if (kernel_ms) *kernel_ms = t_merge_ms[1];
+    if (download_ms) *download_ms = t_merge_ms[2];
+    return MI355_OK;
+}
+
+// Base rows + adapters -> merged rows (csrc/lora_merge.hip): upload, one launch, download.  Every refusal comes before out is written.
+int mi355_lora_merge_rows(int32_t base_type, const void *base, int64_t n_rows, int64_t n_per_row, const mi355_lora_merge_adapter *adapters, int32_t n_adapters,
+                          int32_t out_type, void *out) {
+    if (!need_device()) return MI355_ERR_NO_DEVICE;
+    if (!lora_merge_base_supported(base_type)) {
+        fail("lora_merge_rows: base type " + std::to_string(base_type) + " (" + ggml_type_name(base_type) + ") is not one of f32, f16, bf16, q8_0, q4_K, q5_K, q6_K");
+        return MI355_ERR_ARG;
+    }
+    if (out_type != T_F16 && out_type != T_F32) { fail("lora_merge_rows: out type " + std::to_string(out_type) + " is neither F16 (1) nor F32 (0)"); return MI355_ERR_ARG; }
+    if (!base || !out || !adapters) { fail("lora_merge_rows: null pointer"); return MI355_ERR_ARG; }
+    if (n_adapters < 1 || n_adapters > LORA_MERGE_MAX_AD) { fail("lora_merge_rows: n_adapters " + std::to_string(n_adapters) + " is outside 1 .. 8"); return MI355_ERR_ARG; }
+    if (n_per_row < 8 || n_per_row % 8 || n_per_row % ggml_block_elems(base_type) || n_per_row > ((int64_t)1 << 30)) {
+        fail("lora_merge_rows: n_per_row " + std::to_string(n_per_row) + " is not a whole number of " + ggml_type_name(base_type) + " blocks of " +
+             std::to_string(ggml_block_elems(base_type)) + " and a multiple of 8");
+        return MI355_ERR_ARG;
+    }
+    if (n_rows < 1 || n_rows > ((int64_t)1 << 36) / n_per_row || n_rows > ((int64_t)1 << 22)) { fail("lora_merge_rows: n_rows " + std::to_string(n_rows) + " is outside 1 .. 2^22, or more than 2^36 elements in one call"); return MI355_ERR_ARG; }
+    for (int i = 0; i < n_adapters; i++) {
+        const mi355_lora_merge_adapter &d = adapters[i];
+        if (d.pair_type != T_F16 && d.pair_type != T_F32) { fail("lora_merge_rows: adapter " + std::to_string(i) + ": pair type " + std::to_string(d.pair_type) + " is neither F16 (1) nor F32 (0)"); return MI355_ERR_ARG; }
+        if (d.r < 1 || d.r > LORA_MAX_R) { fail("lora_merge_rows: adapter " + std::to_string(i) + ": rank " + std::to_string(d.r) + " is outside 1 .. 512"); return MI355_ERR_ARG; }
+        if (!d.a || !d.b) { fail("lora_merge_rows: adapter " + std::to_string(i) + ": null pointer"); return MI355_ERR_ARG; }
+        if (!std::isfinite(d.scale)) { fail("lora_merge_rows: adapter " + std::to_string(i) + ": the scale is not finite"); return MI355_ERR_ARG; }
+    }
+    MI355_GUARD(return MI355_ERR_OOM,
+        const size_t wb = ggml_row_bytes(base_type, n_per_row) * (size_t)n_rows, orow = (size_t)n_per_row * (out_type == T_F16 ? 2 : 4), ob = orow * (size_t)n_rows;
+        OpBufs b;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) { if (ev0) (void)hipEventDestroy(ev0); fail("lora_merge_rows: no timing events"); return MI355_ERR_HIP; }
+        struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev_guard{ev0, ev1};
+        const auto c0 = std::chrono::steady_clock::now();
+        const uint8_t *dw = b.upload(base, wb);
+        uint8_t *dout = b.alloc(ob + orow);
+        LoraMergeAdapter ads[LORA_MERGE_MAX_AD];
+        for (int i = 0; i < n_adapters; i++) {
+            const size_t es = adapters[i].pair_type == T_F16 ? 2 : 4, r = (size_t)adapters[i].r;
+            ads[i].A = b.upload(adapters[i].a, r * (size_t)n_per_row * es);
+            ads[i].B = b.upload(adapters[i].b, r * (size_t)n_rows * es);
+            ads[i].type = adapters[i].pair_type; ads[i].r = adapters[i].r; ads[i].scale = adapters[i].scale;
+        }
+        b.check(dout && hipMemset(dout + ob, Q80_GUARD, orow) == hipSuccess);
+        if (!b.ok()) return oom();
+        const auto c1 = std::chrono::steady_clock::now();
+        (void)hipEventRecord(ev0, nullptr);
+        hipError_t e = launch_lora_merge(base_type, dw, n_rows, n_per_row, ads, n_adapters, out_type, dout, nullptr);
+        if (e == hipErrorInvalidValue) { fail("lora_merge_rows: the launcher refuses this shape"); return MI355_ERR_ARG; }
+        (void)hipEventRecord(ev1, nullptr);
+        if (const int rc = finish(e, "lora_merge_rows")) return rc;
+        float kernel_ms = 0.0f;
+        (void)hipEventElapsedTime(&kernel_ms, ev0, ev1);
+        const auto c2 = std::chrono::steady_clock::now();
+        std::vector<uint8_t> guard(orow);
+        if (!b.down(guard.data(), dout + ob, orow).ok()) return b.done("lora_merge_rows");
+        for (uint8_t g : guard)
+            if (g != Q80_GUARD) { fail("lora_merge_rows: the guard row behind the output was written"); return MI355_ERR_HIP; }
+        if (!b.down(out, dout, ob).ok()) return b.done("lora_merge_rows");
+        const auto c3 = std::chrono::steady_clock::now();
+        t_merge_ms[0] = std::chrono::duration<float, std::milli>(c1 - c0).count();
+        t_merge_ms[1] = kernel_ms;
+        t_merge_ms[2] = std::chrono::duration<float, std::milli>(c3 - c2).count();
+        return MI355_OK;
+    )
+}
+
 // The direction of a layer's difference rows (csrc/cvec.hip): upload, iterate, download.  Every refusal comes before dir_out is written.
 int mi355_cvec_direction(int32_t method, const float *rows, int64_t n_rows, int32_t n_embd, const float *init, int32_t n_iter, int32_t n_batch, float tol,
                          float *dir_out, int32_t *iters_out, float *dist_out) {

@@ -380,6 +380,20 @@ size_t lora_scratch_floats(int T);
 bool lora_delta_args_ok(const LoraSeg *segs, int n_seg, const float *x, int ld_x, int K, int T);
 hipError_t launch_lora_delta(const LoraSeg *segs, int n_seg, const float *x, int ld_x, int K, int T, float *scratch, hipStream_t st);
 
+// ---- merged-LoRA export (lora_merge.hip): out[n][k] = round(deq(W)[n][k] + sum_i scale_i * sum_j B_i[n][j] * A_i[j][k]) for 1 .. 8 adapters.
+//   W: N rows of K elements of base_type in ggml FILE layout (F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K), K a whole number of its blocks and a multiple of 8;
+//   A_i [r][K], B_i [N][r], both T_F16 or both T_F32, 1 <= r <= LORA_MAX_R; out [N][K] of out_type T_F16 or T_F32.  Every pointer 16-byte aligned.  The same
+//   call gives the same bits, nothing outside out[0 .. N)[0 .. K) is written.  hipErrorInvalidValue, and nothing launched, for arguments outside this.
+constexpr int LORA_MERGE_MAX_AD = 8;
+struct LoraMergeAdapter {
+    const void *A, *B;
+    int type;             // T_F32 or T_F16
+    int r;
+    float scale;
+};
+bool lora_merge_base_supported(int base_type);
+hipError_t launch_lora_merge(int base_type, const void *W, int64_t N, int64_t K, const LoraMergeAdapter *ads, int n_ad, int out_type, void *out, hipStream_t st);
+
 // MoE router: softmax over n_expert <= 256 logits per token, top-k (first index wins ties), weights renormalised; one wave per token
 // forced (nullable, tests): [T][k] expert ids to take instead of the k most probable (weights = this side's probabilities of them, renormalised)
 hipError_t launch_moe_route(const float *logits, int T, int n_expert, int k, int32_t *ids, float *w, hipStream_t st, const int32_t *forced = nullptr);

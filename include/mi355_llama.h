@@ -505,6 +505,25 @@ MI355_API int mi355_quantize_supported(int32_t dst_type);
 /* Milliseconds of the calling thread's last successful mi355_quantize_chunk: the upload (allocation included) and the guard check + download by the host's
  * clock, the launch between two events on its stream.  Any pointer may be NULL.  MI355_ERR_ARG before the first such call. */
 MI355_API int mi355_quantize_last_times(float *upload_ms, float *kernel_ms, float *download_ms);
+/* The merged-LoRA export's rows (csrc/lora_merge.hip; what llama-export-lora computes per tensor):
+ *   out[n][k] = round( dequantised base[n][k] + sum_i scale_i * sum_j b_i[n][j] * a_i[j][k] )
+ * base: n_rows rows of n_per_row elements of base_type (0 F32, 1 F16, 30 BF16, 8 Q8_0, 12 Q4_K, 13 Q5_K, 14 Q6_K) as a GGUF file holds them, host memory;
+ * adapters: 1 .. 8 of them, a [r][n_per_row] and b [n_rows][r] both of pair_type (1 F16 or 0 F32), 1 <= r <= 512; out: n_rows x n_per_row of out_type (1 F16 or
+ * 0 F32), host memory.  The sum is f32 on the matrix cores, the base is added exactly and the result rounded once.  One upload, one launch, one
+ * synchronisation, one download; a guard row behind the output on the device is checked after the launch.  MI355_ERR_ARG with mi355_last_error naming the
+ * argument at fault: "base type", "out type", "pair type", "rank", "n_per_row" (not a whole number of the base type's blocks, or no multiple of 8), "n_rows",
+ * "n_adapters" or a null pointer; out is not written. */
+typedef struct mi355_lora_merge_adapter {
+    const void *a, *b;
+    int32_t r, pair_type;
+    float scale;
+} mi355_lora_merge_adapter;
+MI355_API int mi355_lora_merge_rows(int32_t base_type, const void *base, int64_t n_rows, int64_t n_per_row, const mi355_lora_merge_adapter *adapters,
+                                    int32_t n_adapters, int32_t out_type, void *out);
+/* 1 if mi355_lora_merge_rows reads base_type, else 0.  Needs no device. */
+MI355_API int mi355_lora_merge_supported(int32_t base_type);
+/* Milliseconds of the calling thread's last successful mi355_lora_merge_rows, as mi355_quantize_last_times gives them. */
+MI355_API int mi355_lora_merge_last_times(float *upload_ms, float *kernel_ms, float *download_ms);
 /* ---- the LLaVA image encoder's launches (csrc/clip.hip, csrc/mmf.hip, csrc/act.hip), one at a time: each entry uploads its inputs, issues the one launch
  * host/clip.cc issues, and downloads the result.  Half-precision outputs are raw f16 bits; every *_h output may be NULL (the launch then gets no f16 pointer).
  *
