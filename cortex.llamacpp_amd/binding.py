@@ -102,6 +102,7 @@ SYMBOLS = {
     "mi355_get_topk_ith": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "mi355_sample_rows": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_sampled_steps": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mi355_sample_rows_vocab": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_debug_sample_rows_calls": (_i64, [_vp]),
     "mi355_debug_mega_steps": (C.c_int64, [_vp]),
     "mi355_debug_engine_steps": (C.c_int64, [_vp]),
@@ -180,6 +181,7 @@ SYMBOLS = {
     "mi355_op_add_qkv_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32]),
     "mi355_op_topk_rows": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_sample_rows": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mi355_op_sample_vocab": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_op_philox_u": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, _i32, _vp]),
     "mi355_op_moe_group": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_moe_gather_act": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -314,6 +316,19 @@ def sampler_params(params, n: int) -> np.ndarray:
         for f, v in {**SAMPLER_DEFAULTS, **p}.items():
             out[r][f] = v
     return out
+
+
+def adj_arrays(adjs, n: int):
+    """(adj_n [n], tok, bias, count [n][192]) of adjs[r] = (tok [m], bias [m], count [m]) or None; an m above 192 is handed over as it is, for the entry to refuse"""
+    A = 192
+    an = np.zeros(n, np.int32); tok = np.zeros((n, A), np.int32); bias = np.zeros((n, A), np.float32); cnt = np.zeros((n, A), np.int32)
+    for r, a in enumerate(adjs or []):
+        if a is None:
+            continue
+        m = min(len(a[0]), A)
+        an[r] = len(a[0])
+        tok[r, :m] = a[0][:m]; bias[r, :m] = a[1][:m]; cnt[r, :m] = a[2][:m]
+    return an, tok, bias, cnt
 
 
 def control_vector_load(lib, items):
@@ -895,6 +910,21 @@ class Backend:
                                                 _ptr(kt) if kept else None, _ptr(kp) if kept else None), "op_sample_rows")
         return out_t, out_n, out_p, kt, kp
 
+    def sample_vocab_op(self, rows, params, u=None, adjs=None, mu=None):
+        """The whole-row chain alone (mi355_op_sample_vocab) over logits rows [R][n]; params and u as sample_rows_op takes them (the penalties are read),
+        adjs[r] = (tok [m], bias [m], count [m]) or None, mu [R]: a finite value = mirostat 2 for that row.  Returns (tokens [R], n_kept [R], probs [R])."""
+        x = np.ascontiguousarray(rows, np.float32)
+        x = x.reshape(1, -1) if x.ndim == 1 else x
+        R, n = x.shape
+        sp = sampler_params(params, R)
+        an, tok, bias, cnt = adj_arrays(adjs, R)
+        uu = None if u is None else np.ascontiguousarray(u, np.float64).reshape(R)
+        mm = None if mu is None else np.ascontiguousarray(mu, np.float32).reshape(R)
+        out_t = np.zeros(R, np.int32); out_n = np.zeros(R, np.int32); out_p = np.zeros(R, np.float32)
+        self._chk(self.lib.mi355_op_sample_vocab(_ptr(x), n, R, _ptr(an), _ptr(tok), _ptr(bias), _ptr(cnt), _ptr(sp), _ptr(uu) if uu is not None else None,
+                                                 _ptr(mm) if mm is not None else None, _ptr(out_t), _ptr(out_n), _ptr(out_p)), "op_sample_vocab")
+        return out_t, out_n, out_p
+
     def philox_u(self, seed: int, counter0: int, stream: int, n: int) -> np.ndarray:
         """The device sampler's u sequence: u of (seed, counter0 + i, stream) for i < n (mi355_op_philox_u)."""
         out = np.zeros(n, np.float32)
@@ -1463,6 +1493,21 @@ class Context:
         rc = self.lib.mi355_sample_rows(self.h, n, _ptr(rows), _ptr(sp), _ptr(an), _ptr(tok), _ptr(bias), _ptr(cnt), _ptr(dc), _ptr(out_t), _ptr(out_p))
         if rc != n:
             raise MI355Error(f"mi355_sample_rows failed ({rc}): {_err(self.lib)}")
+        return out_t, out_p
+
+    def sample_rows_vocab(self, rows, params, draw_counter, adjs=None, mu=None):
+        """sample_rows over the whole vocabulary row (mi355_sample_rows_vocab): any top_k, and the mirostat-2 chain for a row with a finite mu[r]."""
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        n = rows.size
+        sp = sampler_params(params, n)
+        dc = np.ascontiguousarray(np.broadcast_to(np.asarray(draw_counter, np.uint64), (n,)))
+        an, tok, bias, cnt = adj_arrays(adjs, n)
+        mm = None if mu is None else np.ascontiguousarray(mu, np.float32).reshape(n)
+        out_t = np.zeros(n, np.int32); out_p = np.zeros(n, np.float32)
+        rc = self.lib.mi355_sample_rows_vocab(self.h, n, _ptr(rows), _ptr(sp), _ptr(an), _ptr(tok), _ptr(bias), _ptr(cnt), _ptr(dc),
+                                              _ptr(mm) if mm is not None else None, _ptr(out_t), _ptr(out_p))
+        if rc != n:
+            raise MI355Error(f"mi355_sample_rows_vocab failed ({rc}): {_err(self.lib)}")
         return out_t, out_p
 
     def sampled_steps(self, first: int, pos0: int, n: int, params: dict, seq: int = 0):

@@ -448,6 +448,20 @@ int32_t mi355_get_topk_ith(mi355_context *ctx, int32_t i, int32_t k, int32_t n_a
 static SampleParams tail_params(const mi355_sampler_params &p, uint64_t counter) {
     return SampleParams{p.top_k, p.min_keep, p.top_p, p.min_p, p.typ_p, p.temp, p.stream, 0u, p.seed, counter};
 }
+// the rows' records of mi355_sample_rows / mi355_sample_rows_vocab; false (and the message) for an adj_n outside the front's limit
+static bool sample_rows_args(const char *what, int32_t n, const mi355_sampler_params *params, const int32_t *adj_n, const int32_t *adj_tok, const float *adj_bias,
+                             const int32_t *adj_count, const uint64_t *draw_counter, std::vector<SampleParams> &sp, std::vector<TopkAdj> &adjs) {
+    sp.resize((size_t)n); adjs.resize((size_t)n);
+    for (int r = 0; r < n; r++) {
+        sp[(size_t)r] = tail_params(params[r], draw_counter[r]);
+        TopkAdj &a = adjs[(size_t)r];
+        a.n = adj_n ? adj_n[r] : 0; a.repeat = params[r].penalty_repeat; a.freq = params[r].penalty_freq; a.present = params[r].penalty_present;
+        if (a.n < 0 || a.n > TOPK_MAX_ADJ) { fail(std::string(what) + ": adj_n " + std::to_string(a.n) + " outside [0, " + std::to_string(TOPK_MAX_ADJ) + "]"); return false; }
+        const size_t o = (size_t)r * TOPK_MAX_ADJ;
+        for (int j = 0; j < a.n; j++) { a.tok[j] = adj_tok[o + j]; a.bias[j] = adj_bias[o + j]; a.cnt[j] = adj_count[o + j]; }
+    }
+    return true;
+}
 int32_t mi355_sample_rows(mi355_context *ctx, int32_t n, const int32_t *batch_rows, const mi355_sampler_params *params, const int32_t *adj_n, const int32_t *adj_tok,
                           const float *adj_bias, const int32_t *adj_count, const uint64_t *draw_counter, mi355_token *tokens_out, float *probs_out) {
     if (!ctx) return no_context("sample_rows");
@@ -455,18 +469,29 @@ int32_t mi355_sample_rows(mi355_context *ctx, int32_t n, const int32_t *batch_ro
         fail("sample_rows: null pointer or n < 1"); return MI355_ERR_ARG;
     }
     MI355_GUARD(return MI355_ERR_ARG,
-        std::vector<SampleParams> sp((size_t)n);
-        std::vector<TopkAdj> adjs((size_t)n);
-        for (int r = 0; r < n; r++) {
-            sp[(size_t)r] = tail_params(params[r], draw_counter[r]);
-            TopkAdj &a = adjs[(size_t)r];
-            a.n = adj_n ? adj_n[r] : 0; a.repeat = params[r].penalty_repeat; a.freq = params[r].penalty_freq; a.present = params[r].penalty_present;
-            if (a.n < 0 || a.n > TOPK_MAX_ADJ) { fail("sample_rows: adj_n " + std::to_string(a.n) + " outside [0, " + std::to_string(TOPK_MAX_ADJ) + "]"); return MI355_ERR_ARG; }
-            const size_t o = (size_t)r * TOPK_MAX_ADJ;
-            for (int j = 0; j < a.n; j++) { a.tok[j] = adj_tok[o + j]; a.bias[j] = adj_bias[o + j]; a.cnt[j] = adj_count[o + j]; }
-        }
+        std::vector<SampleParams> sp;
+        std::vector<TopkAdj> adjs;
+        if (!sample_rows_args("sample_rows", n, params, adj_n, adj_tok, adj_bias, adj_count, draw_counter, sp, adjs)) return MI355_ERR_ARG;
         if (ctx->c->sample_rows(n, batch_rows, sp.data(), adjs.data(), tokens_out, probs_out) != n) {
             fail(ctx->c->last_error.empty() ? "sample_rows failed" : ctx->c->last_error);
+            return MI355_ERR_ARG;
+        }
+        return n;
+    )
+}
+int32_t mi355_sample_rows_vocab(mi355_context *ctx, int32_t n, const int32_t *batch_rows, const mi355_sampler_params *params, const int32_t *adj_n, const int32_t *adj_tok,
+                                const float *adj_bias, const int32_t *adj_count, const uint64_t *draw_counter, const float *mirostat_mu, mi355_token *tokens_out,
+                                float *probs_out) {
+    if (!ctx) return no_context("sample_rows_vocab");
+    if (n < 1 || !batch_rows || !params || !draw_counter || !tokens_out || !probs_out || (adj_n && (!adj_tok || !adj_bias || !adj_count))) {
+        fail("sample_rows_vocab: null pointer or n < 1"); return MI355_ERR_ARG;
+    }
+    MI355_GUARD(return MI355_ERR_ARG,
+        std::vector<SampleParams> sp;
+        std::vector<TopkAdj> adjs;
+        if (!sample_rows_args("sample_rows_vocab", n, params, adj_n, adj_tok, adj_bias, adj_count, draw_counter, sp, adjs)) return MI355_ERR_ARG;
+        if (ctx->c->sample_rows_vocab(n, batch_rows, sp.data(), adjs.data(), mirostat_mu, tokens_out, probs_out) != n) {
+            fail(ctx->c->last_error.empty() ? "sample_rows_vocab failed" : ctx->c->last_error);
             return MI355_ERR_ARG;
         }
         return n;

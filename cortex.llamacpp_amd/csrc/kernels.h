@@ -305,6 +305,17 @@ const char *sample_rows_refusal(int R, int k, const SampleParams *params_host);
 // n_kept_out (nullable) [R]; kept_tok / kept_p (nullable, both or neither) [R][TOPK_MAX_K]: the candidates that reached the draw, best first.
 hipError_t launch_sample_rows(const unsigned long long *keys, int R, int k, const SampleParams *params_host, const SampleParams *params_dev, const double *u_dev,
                               int32_t *tokens_out, float *probs_out, int32_t *n_kept_out, int32_t *kept_tok, float *kept_p, hipStream_t st);
+// ---- the chain over a whole vocabulary row (sample_vocab.hip): top_k off (<= 0) or above TOPK_MAX_K, and mirostat 2.  A radix selection
+// of the prefix boundary by count or by mass: no sort, the row stays on the device.  Order, adjustments and Philox as above; typ_p must be 1.
+constexpr int SAMPLE_VOCAB_MAX_N = 262144;
+// what launch_sample_vocab refuses, by name (nullptr: nothing): "R", "n", "top_p", "min_p" (NaN or outside [0, 1]), "typ_p" (not 1), "min_keep" (< 0)
+const char *sample_vocab_refusal(int R, int n, const SampleParams *params_host);
+// R rows of n logits: row r of the launch = base row rows_dev[r] (nullptr: r) with adjustments adjs_dev[r], never written.  mu_dev (nullable) [R]: a finite
+// value sends the row through the mirostat-2 chain (temperature, softmax over the row, the prefix whose surprise -log2 p <= mu, draw; top_k / top_p / min_p not
+// read), NaN through the plain one.  u_dev, tokens_out, probs_out (the token's probability under the kept distribution), n_kept_out (nullable): as launch_sample_rows'.
+hipError_t launch_sample_vocab(const float *base, int n, int R, const int *rows_dev, const TopkAdj *adjs_dev, const SampleParams *params_host,
+                               const SampleParams *params_dev, const float *mu_dev, const double *u_dev, int32_t *tokens_out, float *probs_out, int32_t *n_kept_out,
+                               hipStream_t st);
 // out[i] (device or pinned host memory) = the u of (seed, counter0 + i, stream), i < n
 hipError_t launch_philox_u(unsigned long long seed, unsigned long long counter0, unsigned stream, int n, float *out, hipStream_t st);
 

@@ -2,6 +2,7 @@
 // reference's LlamaServerContext consumes (SURVEY.md §8b "inner boundary").  The product implementation is HipBackend
 // (hip_backend.cc, over the C-ABI objects); host-logic unit tests plug in a deterministic fake.
 #pragma once
+#include <cmath>
 
 #include <cstdint>
 #include <string>
@@ -61,13 +62,15 @@ class IBackend {
         }
     }
     // the whole chain on the device (/loadmodel "device_sampler"): the front as above, then the tail and the draw, for every such slot of a
-    // tick in one call.  false: the backend has no device sampler, or the call failed - the slots then take the host chain.
+    // tick in one call (its whole_row requests in one launch of their own).  false: the backend has no device sampler, or the call failed - the slots then take the host chain.
     struct SampleRequest {
         TopkRequest front;                 // i and the adjustments (k is not read: the tail's top_k decides)
         int top_k = 0, min_keep = 0;
         float top_p = 1.0f, min_p = 0.0f, typ_p = 1.0f, temp = 1.0f;
         uint64_t seed = 0, counter = 0;
         uint32_t stream = 0;
+        bool whole_row = false;            // the whole-row kernel: any top_k, and the mirostat-2 chain when mu is finite
+        float mu = NAN;
         int32_t out_tok = -1;
         float out_p = 0.0f;
     };

@@ -158,21 +158,30 @@ class HipBackend : public IBackend {
     void set_device_sampler(bool on) { device_sampler_ = on; }
     bool device_sampler() const override { return device_sampler_ && device_sampling_; }
     bool sample_batch(std::vector<SampleRequest> &reqs) override {
-        const int n = (int)reqs.size();
-        if (n == 0 || !device_sampler()) return false;
-        adjs_.resize((size_t)n); is_.resize((size_t)n); sp_.resize((size_t)n);
-        out_t_.resize((size_t)n); out_l_.resize((size_t)n);
-        for (int r = 0; r < n; r++) {
-            const SampleRequest &q = reqs[(size_t)r];
-            TopkAdj &a = adjs_[(size_t)r];
-            if (q.front.tok.size() > (size_t)TOPK_MAX_ADJ) return false;
-            a.n = (int)q.front.tok.size(); a.repeat = q.front.repeat; a.freq = q.front.freq; a.present = q.front.present;
-            for (int j = 0; j < a.n; j++) { a.tok[j] = q.front.tok[(size_t)j]; a.bias[j] = q.front.bias[(size_t)j]; a.cnt[j] = q.front.cnt[(size_t)j]; }
-            is_[(size_t)r] = q.front.i;
-            sp_[(size_t)r] = SampleParams{q.top_k, q.min_keep, q.top_p, q.min_p, q.typ_p, q.temp, q.stream, 0u, q.seed, q.counter};
+        if (reqs.empty() || !device_sampler()) return false;
+        // the tick's rows split between the two kernels: the front + tail (whole_row = false) and the whole-row selection, one call each
+        for (const bool whole : {false, true}) {
+            std::vector<size_t> at;
+            for (size_t r = 0; r < reqs.size(); r++) if (reqs[r].whole_row == whole) at.push_back(r);
+            const int n = (int)at.size();
+            if (n == 0) continue;
+            adjs_.resize((size_t)n); is_.resize((size_t)n); sp_.resize((size_t)n); mu_.resize((size_t)n);
+            out_t_.resize((size_t)n); out_l_.resize((size_t)n);
+            for (int r = 0; r < n; r++) {
+                const SampleRequest &q = reqs[at[(size_t)r]];
+                TopkAdj &a = adjs_[(size_t)r];
+                if (q.front.tok.size() > (size_t)TOPK_MAX_ADJ) return false;
+                a.n = (int)q.front.tok.size(); a.repeat = q.front.repeat; a.freq = q.front.freq; a.present = q.front.present;
+                for (int j = 0; j < a.n; j++) { a.tok[j] = q.front.tok[(size_t)j]; a.bias[j] = q.front.bias[(size_t)j]; a.cnt[j] = q.front.cnt[(size_t)j]; }
+                is_[(size_t)r] = q.front.i;
+                sp_[(size_t)r] = SampleParams{q.top_k, q.min_keep, q.top_p, q.min_p, q.typ_p, q.temp, q.stream, 0u, q.seed, q.counter};
+                mu_[(size_t)r] = q.mu;
+            }
+            const int got = whole ? ctx_->sample_rows_vocab(n, is_.data(), sp_.data(), adjs_.data(), mu_.data(), out_t_.data(), out_l_.data())
+                                  : ctx_->sample_rows(n, is_.data(), sp_.data(), adjs_.data(), out_t_.data(), out_l_.data());
+            if (got != n) return false;
+            for (int r = 0; r < n; r++) { reqs[at[(size_t)r]].out_tok = out_t_[(size_t)r]; reqs[at[(size_t)r]].out_p = out_l_[(size_t)r]; }
         }
-        if (ctx_->sample_rows(n, is_.data(), sp_.data(), adjs_.data(), out_t_.data(), out_l_.data()) != n) return false;
-        for (int r = 0; r < n; r++) { reqs[(size_t)r].out_tok = out_t_[(size_t)r]; reqs[(size_t)r].out_p = out_l_[(size_t)r]; }
         return true;
     }
     int topk_max_k() const override { return device_sampling_ ? TOPK_MAX_K : 0; }
@@ -228,6 +237,7 @@ class HipBackend : public IBackend {
     bool device_sampling_ = true;
     bool device_sampler_ = false;                       // "device_sampler": the rest of the chain and the draw on the device too (csrc/sample.hip)
     std::vector<SampleParams> sp_;
+    std::vector<float> mu_;
     std::unique_ptr<ClipModel> clip_;
     std::vector<int32_t> n_seq_id_, seq_store_, pos_store_;
     std::vector<int8_t> no_logits_;

@@ -2959,6 +2959,24 @@ int Context::topk_ith(int i, int k, const TopkAdj &adj, int32_t *toks, float *lo
     return k;
 }
 
+// the samplers' workspace grown to the front's row capacity (after topk_stage) and the n parameter records queued on the stream
+bool Context::samp_stage(int n, const SampleParams *sp) {
+    if (samp_cap_ < topk_rows_cap_) {
+        (void)hipStreamSynchronize(stream_);
+        if (d_samp_) (void)hipFree(d_samp_);
+        if (h_samp_) (void)hipHostFree(h_samp_);
+        d_samp_ = nullptr; h_samp_ = nullptr; samp_cap_ = 0;
+        const size_t cap = (size_t)topk_rows_cap_;
+        if (hipMalloc((void **)&d_samp_, cap * (TOPK_MAX_K * 8 + sizeof(SampleParams))) != hipSuccess ||
+            hipHostMalloc((void **)&h_samp_, cap * (sizeof(SampleParams) + 12), hipHostMallocDefault) != hipSuccess) { last_error = "sample_rows: workspace allocation failed"; return false; }
+        samp_cap_ = topk_rows_cap_;
+    }
+    SampleParams *d_sp = reinterpret_cast<SampleParams *>(d_samp_ + (size_t)samp_cap_ * TOPK_MAX_K * 8), *h_sp = reinterpret_cast<SampleParams *>(h_samp_);
+    memcpy(h_sp, sp, (size_t)n * sizeof(SampleParams));
+    if (hipMemcpyAsync(d_sp, h_sp, (size_t)n * sizeof(SampleParams), hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "sample_rows: staging failed"; return false; }
+    return true;
+}
+
 // The whole chain on the device (csrc/sample.hip): the front's keys stay in device memory, the tail reads them in the next launch of the same
 // stream and writes a token and a probability per row into pinned memory - two launches, one synchronisation, 8 n bytes back.
 int Context::sample_rows(int n, const int *is, const SampleParams *sp, const TopkAdj *adjs, int32_t *toks_out, float *probs_out) {
@@ -2979,30 +2997,58 @@ int Context::sample_rows(int n, const int *is, const SampleParams *sp, const Top
     }
     kmax = std::min(kmax, V);
     if (const char *word = sample_rows_refusal(n, kmax, sp)) { last_error = std::string("sample_rows: ") + word + " outside what the sampler takes"; return -1; }
-    if (!topk_stage(n, rows.data(), adjs)) return -1;
-    if (samp_cap_ < topk_rows_cap_) {
-        (void)hipStreamSynchronize(stream_);
-        if (d_samp_) (void)hipFree(d_samp_);
-        if (h_samp_) (void)hipHostFree(h_samp_);
-        d_samp_ = nullptr; h_samp_ = nullptr; samp_cap_ = 0;
-        const size_t cap = (size_t)topk_rows_cap_;
-        if (hipMalloc((void **)&d_samp_, cap * (TOPK_MAX_K * 8 + sizeof(SampleParams))) != hipSuccess ||
-            hipHostMalloc((void **)&h_samp_, cap * (sizeof(SampleParams) + 8), hipHostMallocDefault) != hipSuccess) { last_error = "sample_rows: workspace allocation failed"; return -1; }
-        samp_cap_ = topk_rows_cap_;
-    }
+    if (!topk_stage(n, rows.data(), adjs) || !samp_stage(n, sp)) return -1;
     const size_t cap = (size_t)samp_cap_;
     unsigned long long *d_keys = reinterpret_cast<unsigned long long *>(d_samp_);
     SampleParams *d_sp = reinterpret_cast<SampleParams *>(d_samp_ + cap * TOPK_MAX_K * 8), *h_sp = reinterpret_cast<SampleParams *>(h_samp_);
     int32_t *h_tok = reinterpret_cast<int32_t *>(h_samp_ + cap * sizeof(SampleParams));
     float *h_p = reinterpret_cast<float *>(h_tok + cap);
-    memcpy(h_sp, sp, (size_t)n * sizeof(SampleParams));
-    if (hipMemcpyAsync(d_sp, h_sp, (size_t)n * sizeof(SampleParams), hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "sample_rows: staging failed"; return -1; }
     const size_t rows_off = (size_t)topk_rows_cap_ * sizeof(TopkAdj);
     if (launch_topk_rows(d_logits_, V, n, reinterpret_cast<const int *>(d_topk_adj_ + rows_off), kmax, reinterpret_cast<const TopkAdj *>(d_topk_adj_), topk_scratch_, d_keys,
                          stream_) != hipSuccess ||
         launch_sample_rows(d_keys, n, kmax, h_sp, d_sp, nullptr, h_tok, h_p, nullptr, nullptr, nullptr, stream_) != hipSuccess) {
         (void)hipStreamSynchronize(stream_);
         last_error = "sample_rows: launch failed"; return -1;
+    }
+    if (hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
+    argmax_fetched_ = true;
+    sample_rows_calls++;
+    memcpy(toks_out, h_tok, (size_t)n * 4);
+    memcpy(probs_out, h_p, (size_t)n * 4);
+    return n;
+}
+
+// The chains the front cannot serve - top_k off or above TOPK_MAX_K, mirostat 2 - over the whole row (csrc/sample_vocab.hip): one launch, one
+// synchronisation, 8 n bytes back.  mu (nullable) [n]: a finite value sends its row through the mirostat-2 chain.  The keys' place in the workspace holds mu.
+int Context::sample_rows_vocab(int n, const int *is, const SampleParams *sp, const TopkAdj *adjs, const float *mu, int32_t *toks_out, float *probs_out) {
+    if (last_was_embd_) { last_error = "sample_rows_vocab: embeddings mode computes no logits"; return -1; }
+    if (model->hp.tp_size > 1) { last_error = "sample_rows_vocab: not on a rank of a row split"; return -1; }
+    if (n < 1 || !is || !sp || !adjs || !toks_out || !probs_out) { last_error = "sample_rows_vocab: bad arguments (null pointer or n < 1)"; return -1; }
+    const int V = model->hp.n_vocab, nb = (int)out_row_of_batch_.size();
+    std::vector<int> rows((size_t)n);
+    for (int r = 0; r < n; r++) {
+        int i = is[r];
+        if (i < 0) i += nb;
+        if (i < 0 || i >= nb || out_row_of_batch_[(size_t)i] < 0) { last_error = "sample_rows_vocab: batch row " + std::to_string(is[r]) + " was not flagged for logits"; return -1; }
+        if (adjs[r].n < 0 || adjs[r].n > TOPK_MAX_ADJ) { last_error = "sample_rows_vocab: adj_n " + std::to_string(adjs[r].n) + " outside [0, " + std::to_string(TOPK_MAX_ADJ) + "]"; return -1; }
+        rows[(size_t)r] = out_row_of_batch_[(size_t)i];
+    }
+    if (const char *word = sample_vocab_refusal(n, V, sp)) { last_error = std::string("sample_rows_vocab: ") + word + " outside what the sampler takes"; return -1; }
+    if (!topk_stage(n, rows.data(), adjs) || !samp_stage(n, sp)) return -1;
+    const size_t cap = (size_t)samp_cap_;
+    float *d_mu = reinterpret_cast<float *>(d_samp_);
+    SampleParams *d_sp = reinterpret_cast<SampleParams *>(d_samp_ + cap * TOPK_MAX_K * 8), *h_sp = reinterpret_cast<SampleParams *>(h_samp_);
+    int32_t *h_tok = reinterpret_cast<int32_t *>(h_samp_ + cap * sizeof(SampleParams));
+    float *h_p = reinterpret_cast<float *>(h_tok + cap), *h_mu = h_p + cap;
+    if (mu) {
+        memcpy(h_mu, mu, (size_t)n * 4);
+        if (hipMemcpyAsync(d_mu, h_mu, (size_t)n * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) { last_error = "sample_rows_vocab: staging failed"; return -1; }
+    }
+    const size_t rows_off = (size_t)topk_rows_cap_ * sizeof(TopkAdj);
+    if (launch_sample_vocab(d_logits_, V, n, reinterpret_cast<const int *>(d_topk_adj_ + rows_off), reinterpret_cast<const TopkAdj *>(d_topk_adj_), h_sp, d_sp,
+                            mu ? d_mu : nullptr, nullptr, h_tok, h_p, nullptr, stream_) != hipSuccess) {
+        (void)hipStreamSynchronize(stream_);
+        last_error = "sample_rows_vocab: launch failed"; return -1;
     }
     if (hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
     argmax_fetched_ = true;

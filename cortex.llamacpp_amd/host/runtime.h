@@ -199,7 +199,10 @@ class Context {
     // sp[r] - two launches, one synchronisation, a token and its probability per row back.  Returns n, or -1 with last_error set (embeddings mode, a row
     // that was not flagged, a rank of a row split, top_k outside [1, 128], what sample_rows_refusal names).
     int sample_rows(int n, const int *is, const SampleParams *sp, const TopkAdj *adjs, int32_t *toks_out, float *probs_out);
-    int64_t sample_rows_calls = 0;             // diagnosis: calls of sample_rows that reached the device
+    // the chains the front cannot serve (top_k <= 0 or > 128, mirostat 2 for a row with a finite mu[r]; mu nullable) over the whole row: launch_sample_vocab,
+    // one synchronisation, a token and its probability per row back.  Refuses what sample_rows does apart from top_k, and typ_p != 1.
+    int sample_rows_vocab(int n, const int *is, const SampleParams *sp, const TopkAdj *adjs, const float *mu, int32_t *toks_out, float *probs_out);
+    int64_t sample_rows_calls = 0;             // diagnosis: calls of sample_rows / sample_rows_vocab that reached the device
     void synchronize();
 
     // llama_set_adapter_lora / llama_rm_adapter_lora / llama_clear_adapter_lora: the adapters this context's steps apply, in the order they were first set
@@ -454,6 +457,7 @@ class Context {
     bool topk_stage(int n, const int *rows, const TopkAdj *adjs);   // device selected, the workspace grown to n rows, adjustments and row numbers queued
     uint8_t *d_samp_ = nullptr, *h_samp_ = nullptr;    // sample_rows, [topk_rows_cap_] each: keys | params on the device; pinned: params, then tokens | probabilities
     int samp_cap_ = 0;
+    bool samp_stage(int n, const SampleParams *sp);
     float *spec_scratch_ = nullptr;                    // argmax_prob_ith / spec_verify: part and ticket words of the two kernels (first use)
     int32_t *d_spec_in_ = nullptr, *h_spec_ = nullptr; // rows | group starts | drafts on the device; pinned: their staging, then ids | accepted | (index, p)
     bool spec_prepare();

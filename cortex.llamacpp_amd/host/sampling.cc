@@ -219,6 +219,11 @@ bool Sampler::plan_front(int n_vocab, int max_k, int max_adj, FrontPlan &pl) con
     const size_t k = front_k(n_vocab);
     if (k > (size_t)max_k) return false;
     pl.k = (int)k;
+    return plan_adjust(n_vocab, max_adj, pl);
+}
+
+// the adjusted tokens of this sampler's state, as sample_chain's override list holds them: the biased tokens, then the penalty window's
+bool Sampler::plan_adjust(int n_vocab, int max_adj, FrontPlan &pl) const {
     pl.tok.clear(); pl.bias.clear(); pl.cnt.clear();
     auto slot = [&](int32_t t) -> int {
         for (size_t i = 0; i < pl.tok.size(); i++) if (pl.tok[i] == t) return (int)i;
@@ -235,6 +240,13 @@ bool Sampler::plan_front(int n_vocab, int max_k, int max_adj, FrontPlan &pl) con
     if (!prev_.empty() && (p_.penalty_repeat != 1.0f || p_.penalty_freq != 0.0f || p_.penalty_present != 0.0f))
         for (int32_t t : prev_) if (t >= 0 && t < n_vocab) pl.cnt[(size_t)slot(t)]++;
     return pl.tok.size() <= (size_t)max_adj;
+}
+
+// the mirostat-2 branch's last lines for a token the device drew with probability p among the kept candidates
+void Sampler::set_device_result_mirostat(int32_t tok, float p) {
+    const float observed = -log2f(std::max(p, 1e-37f));
+    mu_ -= p_.mirostat_eta * (observed - p_.mirostat_tau);
+    set_device_result(tok, p);
 }
 
 // the rest of the chain on the candidates the head produced ((token, adjusted logit), best first)

@@ -72,6 +72,20 @@ class Sampler {
         return !gm_ && p_.mirostat != 1 && p_.mirostat != 2 && p_.n_probs <= 0 && !(p_.dynatemp_range > 0.0f) && p_.top_k >= 1 && p_.top_k <= max_k && p_.min_keep <= max_k &&
                unit(p_.top_p) && unit(p_.min_p) && unit(p_.typ_p);
     }
+    // ... and the whole-row kernel (csrc/sample_vocab.hip) the chains the front cannot serve: temp > 0, no grammar, n_probs, dynatemp or
+    // typical-p, and either mirostat 2 or a plain chain whose top_k is off (<= 0) or above max_k.  plan_adjust says what to send (false: more than max_adj
+    // adjusted tokens, or two biases on one token).  A mirostat-2 row goes with device_mu(); set_device_result_mirostat() takes the token and its probability
+    // under the kept distribution and moves mu as the host branch does.
+    bool device_vocab_ok(int max_k) const {
+        const auto unit = [](float v) { return v >= 0.0f && v <= 1.0f; };
+        if (gm_ || !(p_.temp > 0.0f) || p_.mirostat == 1 || p_.n_probs > 0 || p_.dynatemp_range > 0.0f || !(p_.typ_p == 1.0f)) return false;
+        if (p_.mirostat == 2) return true;
+        return (p_.top_k <= 0 || p_.top_k > max_k) && unit(p_.top_p) && unit(p_.min_p);
+    }
+    bool plan_adjust(int n_vocab, int max_adj, FrontPlan &pl) const;
+    bool device_mirostat() const { return p_.mirostat == 2; }
+    float device_mu() const { return mu_; }
+    void set_device_result_mirostat(int32_t tok, float p);
     uint64_t device_seed() const { return dev_seed_; }
     uint64_t device_draw() const { return n_draws_; }
     void set_device_result(int32_t tok, float p) { cand_.assign(1, TokenProb{tok, p}); n_draws_++; }

@@ -1008,8 +1008,9 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
             }
             if (spec_emit[gi].empty()) spec_emit[gi].push_back(-1);      // (no logits: phase 2 reports it)
         }
-        // "device_sampler" (DESIGN.md §4.14): the slots whose whole chain the device can run - no grammar, mirostat, n_probs or dynatemp, top_k within the
-        // front's limit - go through ONE sample_batch call and bring back a token each; a slot that does not qualify, or a call that fails, takes the paths below.
+        // "device_sampler" (DESIGN.md §4.14): the slots whose whole chain the device can run - no grammar, mirostat 1, n_probs or dynatemp - go through ONE
+        // sample_batch call and bring back a token each: top_k within the front's limit through the front and the tail, top_k off or above it (no typical-p)
+        // and mirostat 2 through the whole-row kernel (§4.14.1).  A slot that does not qualify, or a call that fails, takes the paths below.
         // The Philox stream is 0 for every slot: a request's draws depend on its seed and its draw counter, never on the slot it was given
         size_t n_dev = 0;
         if (be_->device_sampler()) {
@@ -1019,12 +1020,18 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
                 LlamaClientSlot &slot = *gen[gi];
                 const SamplingParams &sp = slot.smpl->params();
                 Sampler::FrontPlan fp;
-                if (!spec_emit[gi].empty() || !(sp.temp > 0.0f) || !slot.smpl->device_tail_ok(be_->topk_max_k()) ||
-                    !slot.smpl->plan_front(n_vocab_now, be_->topk_max_k(), be_->topk_max_adj(), fp)) continue;
+                if (!spec_emit[gi].empty() || !(sp.temp > 0.0f)) continue;
                 IBackend::SampleRequest rq;
+                if (slot.smpl->device_tail_ok(be_->topk_max_k()) && slot.smpl->plan_front(n_vocab_now, be_->topk_max_k(), be_->topk_max_adj(), fp)) {
+                    rq.top_k = sp.top_k; rq.top_p = sp.top_p; rq.min_p = sp.min_p; rq.typ_p = sp.typ_p;
+                } else if (slot.smpl->device_vocab_ok(be_->topk_max_k()) && slot.smpl->plan_adjust(n_vocab_now, be_->topk_max_adj(), fp)) {
+                    rq.whole_row = true;
+                    if (slot.smpl->device_mirostat()) rq.mu = slot.smpl->device_mu();             // (the cuts are not read in that chain: left off)
+                    else { rq.top_k = sp.top_k; rq.top_p = sp.top_p; rq.min_p = sp.min_p; }
+                } else continue;
                 rq.front.i = slot.i_batch - i; rq.front.k = fp.k; rq.front.tok = std::move(fp.tok); rq.front.bias = std::move(fp.bias); rq.front.cnt = std::move(fp.cnt);
                 rq.front.repeat = sp.penalty_repeat; rq.front.freq = sp.penalty_freq; rq.front.present = sp.penalty_present;
-                rq.top_k = sp.top_k; rq.min_keep = std::max(sp.min_keep, 0); rq.top_p = sp.top_p; rq.min_p = sp.min_p; rq.typ_p = sp.typ_p; rq.temp = sp.temp;
+                rq.min_keep = std::max(sp.min_keep, 0); rq.temp = sp.temp;
                 rq.seed = slot.smpl->device_seed(); rq.counter = slot.smpl->device_draw(); rq.stream = 0;
                 dev.push_back(std::move(rq));
                 dev_slot.push_back(gi);
@@ -1033,7 +1040,8 @@ bool LlamaServerContext::UpdateSlots() {   // :1248-1710
                 for (size_t di = 0; di < dev.size(); di++) {
                     if (dev[di].out_tok < 0) continue;
                     ids[dev_slot[di]] = dev[di].out_tok;
-                    gen[dev_slot[di]]->smpl->set_device_result(dev[di].out_tok, dev[di].out_p);
+                    if (dev[di].whole_row && std::isfinite(dev[di].mu)) gen[dev_slot[di]]->smpl->set_device_result_mirostat(dev[di].out_tok, dev[di].out_p);
+                    else gen[dev_slot[di]]->smpl->set_device_result(dev[di].out_tok, dev[di].out_p);
                     sampler_stats_[0]++; n_dev++;
                 }
         }

@@ -247,6 +247,15 @@ typedef struct mi355_sampler_params {
 MI355_API int32_t mi355_sample_rows(mi355_context *ctx, int32_t n, const int32_t *batch_rows, const mi355_sampler_params *params, const int32_t *adj_n,
                                     const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_count, const uint64_t *draw_counter,
                                     mi355_token *tokens_out, float *probs_out);
+/* The chains the 128-candidate front cannot serve, over the whole vocabulary row (csrc/sample_vocab.hip): a selection of the prefix boundary
+ * by count or by mass - no sort, and the row stays on the device.  Arguments, order, adjustments, draw and outputs as mi355_sample_rows', with top_k unrestricted
+ * (<= 0 or >= n_vocab: off).  mirostat_mu (nullable) [n]: a row with a finite mu takes the mirostat-2 chain - temperature, softmax over the row, the prefix whose
+ * surprise -log2 p does not exceed mu (at least one candidate), draw; top_k / top_p / min_p are not read - and probs_out is the token's probability under the kept
+ * distribution, from which the caller updates mu; NaN or a null array: the plain chain.  One launch, one synchronisation, 8 n bytes back.  MI355_ERR_ARG with the
+ * word in mi355_last_error for typ_p != 1 ("typ_p") and for everything mi355_sample_rows refuses apart from top_k. */
+MI355_API int32_t mi355_sample_rows_vocab(mi355_context *ctx, int32_t n, const int32_t *batch_rows, const mi355_sampler_params *params, const int32_t *adj_n,
+                                          const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_count, const uint64_t *draw_counter,
+                                          const float *mirostat_mu, mi355_token *tokens_out, float *probs_out);
 /* The sampled twin of mi355_greedy_steps: step i decodes the previous token at pos0 + i, samples row 0 through mi355_sample_rows with draw counter i and feeds
  * the token back.  The penalty window (the last 64 emitted tokens, at most 192 distinct) is kept on the C side.  out_tokens / out_probs (nullable) [n].  Returns
  * the steps done (n, or fewer with the reason in mi355_last_error). */
@@ -573,6 +582,12 @@ MI355_API int mi355_op_topk_rows(const float *base, int64_t n, int32_t n_base_ro
  * kept_tok_out / kept_p_out (nullable, both or neither) [R][128]: the candidates that reached the draw and their probabilities, best first, n_kept of them. */
 MI355_API int mi355_op_sample_rows(const int32_t *cand_tok, const float *cand_logit, int32_t R, int32_t k, const mi355_sampler_params *params, const double *u,
                                    int32_t *tokens_out, int32_t *n_kept_out, float *probs_out, int32_t *kept_tok_out, float *kept_p_out);
+/* The whole-row chain alone (csrc/sample_vocab.hip) on caller-supplied rows [R][n], n <= 262144: adjustments as mi355_op_topk_rows' (adj_n nullable: none;
+ * repeat / freq / present from params[r]), params [R], u (nullable) [R] as mi355_op_sample_rows', mirostat_mu (nullable) [R] as mi355_sample_rows_vocab's.
+ * tokens_out / n_kept_out / probs_out [R]: the token, how many candidates reached the draw, the token's probability among them. */
+MI355_API int mi355_op_sample_vocab(const float *rows, int64_t n, int32_t R, const int32_t *adj_n, const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_cnt,
+                                    const mi355_sampler_params *params, const double *u, const float *mirostat_mu, int32_t *tokens_out, int32_t *n_kept_out,
+                                    float *probs_out);
 /* out [n]: the device's u for (seed, counter0 + i, stream) */
 MI355_API int mi355_op_philox_u(uint64_t seed, uint64_t counter0, uint32_t stream, int32_t n, float *out);
 /* Grouping of the T * k selections ids [T][k] of a prompt batch by expert (T * k <= 61440, n_expert <= 256): a counting sort, stable in (token, rank) order.
