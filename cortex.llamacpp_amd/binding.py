@@ -167,6 +167,10 @@ SYMBOLS = {
     "mi355_quantize_chunk": (C.c_int, [_i32, _i32, _vp, _i64, _i64, _vp, _vp]),
     "mi355_quantize_supported": (C.c_int, [_i32]),
     "mi355_quantize_last_times": (C.c_int, [_vp, _vp, _vp]),
+    "mi355_dequantize_rows": (C.c_int, [C.c_int, _vp, _i64, _i64, C.c_int, _vp]),
+    "mi355_quant_error_rows": (C.c_int, [C.c_int, _vp, C.c_int, _vp, _i64, _i64, _vp, _vp]),
+    "mi355_quant_error_supported": (C.c_int, [C.c_int]),
+    "mi355_quant_error_last_times": (C.c_int, [_vp, _vp, _vp]),
     "mi355_lora_merge_rows": (C.c_int, [_i32, _vp, _i64, _i64, _vp, _i32, _i32, _vp]),
     "mi355_lora_merge_supported": (C.c_int, [_i32]),
     "mi355_lora_merge_last_times": (C.c_int, [_vp, _vp, _vp]),
@@ -793,6 +797,44 @@ class Backend:
         out = np.zeros((n_rows, n // be * bb if n % be == 0 else 1), np.uint8)
         self._chk(self.lib.mi355_quantize_chunk(dst_type, src_type, _ptr(x), n, n_rows, _ptr(im), _ptr(out)), "quantize_chunk")
         return out
+
+    @staticmethod
+    def _file_rows(rows: np.ndarray, t: int, n_per_row: int):
+        """rows of ggml type t as a GGUF file holds them (any dtype and shape) -> (their bytes, the number of rows); 0 rows where t is not a weight type or
+        n_per_row not whole blocks of it (the entry refuses either by name)."""
+        from .gguf_synth import BLOCK_BYTES, BLOCK_ELEMS
+        raw = np.ascontiguousarray(rows).reshape(-1).view(np.uint8)
+        be, bb = BLOCK_ELEMS.get(t, 0), BLOCK_BYTES.get(t, 0)
+        rb = n_per_row // be * bb if be and n_per_row > 0 and n_per_row % be == 0 else 0
+        return raw, raw.size // rb if rb else 0
+
+    def dequantize_rows(self, blocks: np.ndarray, src_type: int, n_per_row: int, dst: str = "f32") -> np.ndarray:
+        """The weights of a file back as floats (mi355_dequantize_rows): rows of src_type - any of the 18 weight types, as the file holds them - to float32
+        (the f32 ggml's dequantize_row_* gives) or, dst="f16", float16 [n_rows][n_per_row].  A type or shape the entry refuses raises MI355Error."""
+        assert dst in ("f32", "f16"), dst
+        raw, n_rows = self._file_rows(blocks, src_type, n_per_row)
+        out = np.zeros((max(n_rows, 1), max(n_per_row, 1)), np.float16 if dst == "f16" else np.float32)
+        self._chk(self.lib.mi355_dequantize_rows(src_type, _ptr(raw), n_per_row, max(n_rows, 1), F16 if dst == "f16" else F32, _ptr(out)), "dequantize_rows")
+        return out
+
+    def quant_error_rows(self, ref: np.ndarray, ref_type: int, blocks: np.ndarray, q_type: int, n_per_row: int, col_weights=None) -> np.ndarray:
+        """Per row {sum e^2, sum w^2, sum c e^2, max |e|} as float64 [n_rows][4] (mi355_quant_error_rows): w the rows of ref (ref_type: F32 / F16 / BF16 rows or
+        the blocks of another quantisation), e = w - the rows of blocks (q_type) decoded, c = col_weights (n_per_row values) or 1."""
+        (r, nr), (q, nq) = self._file_rows(ref, ref_type, n_per_row), self._file_rows(blocks, q_type, n_per_row)
+        assert not (nr and nq) or nr == nq, (nr, nq)
+        n_rows = max(nr, nq, 1)
+        cw = None if col_weights is None else np.ascontiguousarray(col_weights, np.float32).reshape(-1)
+        assert cw is None or cw.size == n_per_row
+        out = np.zeros((n_rows, 4), np.float64)
+        self._chk(self.lib.mi355_quant_error_rows(ref_type, _ptr(r), q_type, _ptr(q), n_per_row, n_rows, _ptr(cw), _ptr(out)), "quant_error_rows")
+        return out
+
+    def quant_error_last_times(self):
+        """(upload, kernel, download) milliseconds of this thread's last dequantize_rows / quant_error_rows (mi355_quant_error_last_times)"""
+        t = np.zeros(3, np.float32)
+        p = t.ctypes.data
+        self._chk(self.lib.mi355_quant_error_last_times(C.c_void_p(p), C.c_void_p(p + 4), C.c_void_p(p + 8)), "quant_error_last_times")
+        return float(t[0]), float(t[1]), float(t[2])
 
     def lora_merge_rows(self, base_type: int, base_rows: np.ndarray, adapters, out_type: int = F16) -> np.ndarray:
         """The merged-LoRA export's rows (mi355_lora_merge_rows): base_rows [n_rows][...] - the rows as the GGUF file holds them: float32 / float16 arrays, uint16

@@ -902,6 +902,119 @@ int mi355_quantize_chunk(int32_t dst_type, int32_t src_type, const void *src, in
     return MI355_OK;
 }
 
+// ---- decode and compare (csrc/quant_error.hip)
+int mi355_quant_error_supported(int type) { return quant_error_type_supported(type) ? 1 : 0; }
+
+static thread_local float t_qerr_ms[3] = {-1.0f, -1.0f, -1.0f};
+int mi355_quant_error_last_times(float *upload_ms, float *kernel_ms, float *download_ms) {
+    if (t_qerr_ms[0] < 0.0f) { fail("quant_error_last_times: no completed mi355_dequantize_rows or mi355_quant_error_rows on this thread"); return MI355_ERR_ARG; }
+    if (upload_ms) *upload_ms = t_qerr_ms[0];
+    if (kernel_ms) *kernel_ms = t_qerr_ms[1];
+    if (download_ms) *download_ms = t_qerr_ms[2];
+    return MI355_OK;
+}
+
+// the refusals the two entries share: `what` names the entry, `role` the argument ("source type", "reference type", "quantised type")
+static bool qerr_type_ok(const char *what, const char *role, int type, int64_t n_per_row) {
+    if (type == T_Q8_K) { fail(std::string(what) + ": " + role + " q8_K is an activation format, not a weight type"); return false; }
+    if (!quant_error_type_supported(type)) { fail(std::string(what) + ": " + role + " " + std::to_string(type) + " is not a weight type this build decodes"); return false; }
+    if (n_per_row < 1 || n_per_row % ggml_block_elems(type) || n_per_row % 4) {
+        fail(std::string(what) + ": n_per_row " + std::to_string(n_per_row) + " is not a whole number of " + ggml_type_name(type) + " blocks of " +
+             std::to_string(ggml_block_elems(type)) + " and a multiple of 4");
+        return false;
+    }
+    return true;
+}
+
+// the launch between two events, the copies by the host's clock (as mi355_quantize_chunk times itself)
+struct QerrTimer {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now(), c1, c2;
+    bool ok() { return hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess; }
+    ~QerrTimer() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+    void uploaded() { c1 = std::chrono::steady_clock::now(); (void)hipEventRecord(ev0, nullptr); }
+    void launched() { (void)hipEventRecord(ev1, nullptr); }
+    void synced() { c2 = std::chrono::steady_clock::now(); }
+    void downloaded() {
+        float k = 0.0f;
+        (void)hipEventElapsedTime(&k, ev0, ev1);
+        t_qerr_ms[0] = std::chrono::duration<float, std::milli>(c1 - c0).count();
+        t_qerr_ms[1] = k;
+        t_qerr_ms[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - c2).count();
+    }
+};
+
+int mi355_dequantize_rows(int src_type, const void *blocks, int64_t n_per_row, int64_t n_rows, int dst_type, void *dst) {
+    return op_entry([&]() -> int {
+        const char *what = "dequantize_rows";
+        if (!qerr_type_ok(what, "source type", src_type, n_per_row)) return MI355_ERR_ARG;
+        if (dst_type != T_F32 && dst_type != T_F16) { fail("dequantize_rows: destination type " + std::to_string(dst_type) + " is neither F32 (0) nor F16 (1)"); return MI355_ERR_ARG; }
+        if (!blocks || !dst) { fail("dequantize_rows: null pointer"); return MI355_ERR_ARG; }
+        if (n_rows <= 0) { fail("dequantize_rows: n_rows <= 0"); return MI355_ERR_ARG; }
+        if (n_rows > ((int64_t)1 << 36) / n_per_row) { fail("dequantize_rows: more than 2^36 elements in one call"); return MI355_ERR_ARG; }
+        const size_t sb = ggml_row_bytes(src_type, n_per_row) * (size_t)n_rows, orow = (size_t)n_per_row * (dst_type == T_F16 ? 2 : 4), ob = orow * (size_t)n_rows;
+        OpBufs b;
+        QerrTimer tm;
+        if (!tm.ok()) { fail("dequantize_rows: no timing events"); return MI355_ERR_HIP; }
+        const uint8_t *dsrc = b.upload(blocks, sb, 16);
+        uint8_t *dout = b.alloc(ob + orow);
+        b.check(dout && hipMemset(dout + ob, Q80_GUARD, orow) == hipSuccess);
+        if (!b.ok()) return oom();
+        tm.uploaded();
+        const hipError_t e = launch_dequantize_rows(src_type, dsrc, n_per_row, n_rows, dst_type, dout, nullptr);
+        if (e == hipErrorInvalidValue) { fail("dequantize_rows: the launcher refuses this shape"); return MI355_ERR_ARG; }
+        tm.launched();
+        if (const int rc = finish(e, what)) return rc;
+        tm.synced();
+        std::vector<uint8_t> guard(orow);
+        if (!b.down(guard.data(), dout + ob, orow).ok()) return b.done(what);
+        for (uint8_t g : guard)
+            if (g != Q80_GUARD) { fail("dequantize_rows: the guard row behind the output was written"); return MI355_ERR_HIP; }
+        if (!b.down(dst, dout, ob).ok()) return b.done(what);
+        tm.downloaded();
+        return MI355_OK;
+    });
+}
+
+int mi355_quant_error_rows(int ref_type, const void *ref, int q_type, const void *blocks, int64_t n_per_row, int64_t n_rows, const float *col_weights, double *out) {
+    return op_entry([&]() -> int {
+        const char *what = "quant_error_rows";
+        if (!qerr_type_ok(what, "reference type", ref_type, n_per_row) || !qerr_type_ok(what, "quantised type", q_type, n_per_row)) return MI355_ERR_ARG;
+        if (!ref || !blocks || !out) { fail("quant_error_rows: null pointer"); return MI355_ERR_ARG; }
+        if (n_rows <= 0) { fail("quant_error_rows: n_rows <= 0"); return MI355_ERR_ARG; }
+        if (n_rows > ((int64_t)1 << 36) / n_per_row) { fail("quant_error_rows: more than 2^36 elements in one call"); return MI355_ERR_ARG; }
+        for (int64_t j = 0; col_weights && j < n_per_row; j++)
+            if (!(col_weights[j] >= 0.0f) || std::isinf(col_weights[j])) { fail("quant_error_rows: col_weights[" + std::to_string(j) + "] is negative or not finite"); return MI355_ERR_ARG; }
+        const size_t rows = (size_t)n_rows, ob = rows * 4 * sizeof(double), guard_b = 4 * sizeof(double);
+        OpBufs b;
+        QerrTimer tm;
+        if (!tm.ok()) { fail("quant_error_rows: no timing events"); return MI355_ERR_HIP; }
+        const uint8_t *dref = b.upload(ref, ggml_row_bytes(ref_type, n_per_row) * rows, 16), *dq = b.upload(blocks, ggml_row_bytes(q_type, n_per_row) * rows, 16);
+        const float *dcw = col_weights ? b.upload(col_weights, (size_t)n_per_row * 4) : nullptr;
+        double *dpart = b.alloc<double>(quant_error_partial_doubles(n_per_row, n_rows) * sizeof(double));
+        int32_t *dflag = b.alloc<int32_t>(rows * 4);
+        uint8_t *dout = b.alloc(ob + guard_b);
+        b.check(dout && hipMemset(dout + ob, Q80_GUARD, guard_b) == hipSuccess);
+        if (!b.ok()) return oom();
+        tm.uploaded();
+        const hipError_t e = launch_quant_error_rows(ref_type, dref, q_type, dq, n_per_row, n_rows, dcw, dpart, dflag, reinterpret_cast<double *>(dout), nullptr);
+        if (e == hipErrorInvalidValue) { fail("quant_error_rows: the launcher refuses this shape"); return MI355_ERR_ARG; }
+        tm.launched();
+        if (const int rc = finish(e, what)) return rc;
+        tm.synced();
+        std::vector<int32_t> flags(rows);
+        uint8_t guard[4 * sizeof(double)];
+        if (!b.down(flags.data(), dflag, rows * 4).down(guard, dout + ob, guard_b).ok()) return b.done(what);
+        for (uint8_t g : guard)
+            if (g != Q80_GUARD) { fail("quant_error_rows: the guard row behind the output was written"); return MI355_ERR_HIP; }
+        for (size_t r = 0; r < rows; r++)
+            if (flags[r]) { fail("quant_error_rows: row " + std::to_string(r) + " of the reference holds a non-finite value"); return MI355_ERR_ARG; }
+        if (!b.down(out, dout, ob).ok()) return b.done(what);
+        tm.downloaded();
+        return MI355_OK;
+    });
+}
+
 int mi355_lora_merge_supported(int32_t base_type) { return lora_merge_base_supported(base_type) ? 1 : 0; }
 
 static thread_local float t_merge_ms[3] = {-1.0f, -1.0f, -1.0f};

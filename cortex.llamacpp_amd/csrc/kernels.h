@@ -450,6 +450,19 @@ bool quantize_src_supported(int src_type);
 hipError_t launch_quantize_rows(int dst_type, int src_type, const void *src, int64_t n_per_row, int64_t n_rows, const float *imatrix, void *dst,
                                 int32_t *nonfinite_flag, hipStream_t st);
 
+// ---- decode and compare (quant_error.hip): rows as a GGUF file holds them (ggml blocks, contiguous, no plane set) of any of the 18 weight
+//   types of kTypeLayouts (not Q8_K), n_per_row a whole number of the type's blocks and a multiple of 4.  Every pointer 16-byte aligned, and every block
+//   buffer readable up to the next multiple of 16 bytes behind its last block.  Any other type, shape or alignment: hipErrorInvalidValue, nothing launched.
+bool quant_error_type_supported(int t);
+// blocks of src_type -> dst_type (T_F32, or T_F16 rounded to nearest even) rows: the f32 of ggml's dequantize_row_*
+hipError_t launch_dequantize_rows(int src_type, const void *blocks, int64_t n_per_row, int64_t n_rows, int dst_type, void *dst, hipStream_t st);
+// out[row] = {sum e^2, sum w^2, sum c_j e_j^2, max |e|} in f64, w the reference row (any of the types), e = w - the row of q_type, c = col_weights (n_per_row
+// f32) or 1 with nullptr.  partial: quant_error_partial_doubles(n_per_row, n_rows) doubles of scratch; row_flags: n_rows int32 the caller zeroed, 1 where the
+// reference row holds a non-finite value (taken as 0).  Two launches, no atomics; the bits do not depend on how the rows are cut into calls.
+size_t quant_error_partial_doubles(int64_t n_per_row, int64_t n_rows);
+hipError_t launch_quant_error_rows(int ref_type, const void *ref, int q_type, const void *blocks, int64_t n_per_row, int64_t n_rows, const float *col_weights,
+                                   double *partial, int32_t *row_flags, double *out, hipStream_t st);
+
 // ---- control vectors (cvec.hip)
 // x[t][j] = fl32(x[t][j] + v[j]) for the T rows of x [T][E]: one f32 addition per element, 16-byte loads and stores.  E a multiple of 32, x and v 16-byte
 // aligned, T >= 1; anything else: hipErrorInvalidValue, nothing launched.

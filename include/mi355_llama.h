@@ -514,6 +514,25 @@ MI355_API int mi355_quantize_supported(int32_t dst_type);
 /* Milliseconds of the calling thread's last successful mi355_quantize_chunk: the upload (allocation included) and the guard check + download by the host's
  * clock, the launch between two events on its stream.  Any pointer may be NULL.  MI355_ERR_ARG before the first such call. */
 MI355_API int mi355_quantize_last_times(float *upload_ms, float *kernel_ms, float *download_ms);
+/* Decode and compare (csrc/quant_error.hip; what llama-quantize-stats measures).  A weight type is any of the 18 a GGUF file may hold here: 0 F32, 1 F16,
+ * 30 BF16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS, 34 TQ1_0, 35 TQ2_0, 39 MXFP4; rows are
+ * host memory in the file's own layout (ggml blocks), n_per_row a whole number of the type's blocks and a multiple of 4.  Each entry: one upload, its launches,
+ * one synchronisation, a guard row behind the output checked, one download.  MI355_ERR_ARG with mi355_last_error naming the cause: an unknown type, Q8_K (an
+ * activation format), n_per_row not whole blocks of the type, a null pointer, n_rows <= 0; the output is not written.
+ *
+ * blocks: n_rows rows of src_type -> dst: n_rows x n_per_row of dst_type, 0 F32 - the f32 ggml's dequantize_row_* gives, bit for bit - or 1 F16, that value
+ * rounded to nearest even. */
+MI355_API int mi355_dequantize_rows(int src_type, const void *blocks, int64_t n_per_row, int64_t n_rows, int dst_type, void *dst);
+/* Per row r, out[r] = {sum e^2, sum w^2, sum c_j e_j^2, max |e|} in f64: w the row of ref (ref_type: any weight type - F32 / F16 / BF16 source rows, or the
+ * blocks of another quantisation), e = w - the row of blocks (q_type) decoded, c = col_weights (n_per_row values, not negative, finite) or 1 with NULL.  The
+ * terms are f64 of the f32 values, the order of the sums is fixed by n_per_row: the same rows give the same bits however they are cut into calls.  A
+ * non-finite reference value: MI355_ERR_ARG, the message names the first such row, out is not written. */
+MI355_API int mi355_quant_error_rows(int ref_type, const void *ref, int q_type, const void *blocks, int64_t n_per_row, int64_t n_rows, const float *col_weights,
+                                     double *out);
+/* 1 if the two entries above decode `type`, else 0.  Needs no device. */
+MI355_API int mi355_quant_error_supported(int type);
+/* Milliseconds of the calling thread's last successful mi355_dequantize_rows or mi355_quant_error_rows, as mi355_quantize_last_times gives them. */
+MI355_API int mi355_quant_error_last_times(float *upload_ms, float *kernel_ms, float *download_ms);
 /* The merged-LoRA export's rows (csrc/lora_merge.hip; what llama-export-lora computes per tensor):
  *   out[n][k] = round( dequantised base[n][k] + sum_i scale_i * sum_j b_i[n][j] * a_i[j][k] )
  * base: n_rows rows of n_per_row elements of base_type (0 F32, 1 F16, 30 BF16, 8 Q8_0, 12 Q4_K, 13 Q5_K, 14 Q6_K) as a GGUF file holds them, host memory;
