@@ -1,5 +1,5 @@
 // quantize.hip — the quantiser (what upstream's ggml_quantize_chunk does for the types of the published mixes): f32 / f16 / bf16 rows ->
-// ggml-layout blocks of Q8_0, Q5_0, Q5_1, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, with or without an importance matrix.  The arithmetic is tests/quantize_ref.py's, step
+// ggml-layout blocks of Q8_0, Q5_0, Q5_1, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, TQ1_0, TQ2_0, with or without an importance matrix.  The arithmetic is tests/quantize_ref.py's, step
 // for step: that file is the specification, this one follows it (same products, same summation trees, IEEE division and square root, no contraction).
 //
 // Shape of the work.  The rows are one flat run of elements (a row is a whole number of blocks).  A wave owns 256 adjacent elements: one super-block of a K
@@ -9,6 +9,11 @@
 // choices are uniform inside a group and need no vote.  The super-block step (the maxima of the scales, their quantisation, the recomputed codes) continues
 // the butterfly over the wave.  The codes then meet in LDS, where lanes assemble the block's bytes, and leave as 16-bit stores.
 // No atomics; a non-finite source value is computed as 0 and raises *nonfinite_flag (every writer stores the same 1).
+//
+// The ternary types TQ1_0 and TQ2_0 (ggml's quantize_row_tq1_0_ref / quantize_row_tq2_0_ref; the twin is tests/ternary_quantize_ref.py) have no search: the
+// super-block's scale is its largest magnitude and a code is the nearest of - 1, 0, 1 times it.  TQ2_0 packs the codes as Q2_K's qs; TQ1_0 writes five trits to
+// a byte in base 3, 52 lanes a byte each, in integers.  The bytes are the exact inverse of quant_error.hip's decoders.  The importance matrix is accepted and
+// ignored for these two types, as upstream does.
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -403,6 +408,31 @@ __global__ __launch_bounds__(QZ_WAVES * 64) void quantize_kernel(const void *__r
             }
         }
         __syncthreads();
+    } else if (DT == T_TQ1_0 || DT == T_TQ2_0) {
+        // one scale for the super-block, the largest magnitude itself; the inverse is taken of the f32, not of the f16 that is stored
+        const float amax = gmax<64>(fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3]))));
+        const float id = amax != 0.0f ? 1.0f / amax : 0.0f;
+        float L[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) L[i] = roundf(x[i] * id);              // lroundf: a half goes away from zero
+        put_codes(codes, lane, L, 1.0f);
+        if (lane == 0) put_u16(out, BB - 2, f2h(amax));
+        __syncthreads();
+        if (DT == T_TQ2_0) {
+            out[lane] = pack2(codes, lane);
+        } else if (lane < 52) {
+            // lane j builds byte j: qs[j] from elements j + 32 n, qs[32 + m] from 160 + m + 16 n, qh[m] from 240 + m + 4 n; the first trit is the most
+            // significant of five, a qh byte's absent fifth is 0.  The digit read back is ((byte * 3^n mod 256) * 3) >> 8, hence the ceiling of q 256 / 243
+            const int first = lane < 32 ? lane : lane < 48 ? 128 + lane : 192 + lane, step = lane < 32 ? 32 : lane < 48 ? 16 : 4;
+            uint32_t q = 0;
+#pragma unroll
+            for (int n = 0; n < 5; n++) {
+                const int e = first + step * n;
+                q = 3 * q + (e < 256 ? (uint32_t)codes[e] : 0u);
+            }
+            out[lane] = (uint8_t)((q * 256u + 242u) / 243u);
+        }
+        __syncthreads();
     }
 
     // the chunk's bytes leave: 16-bit words (a block's size is even; a Q3_K / Q6_K block is not a multiple of four)
@@ -430,7 +460,7 @@ template <int DT> hipError_t launch_dt(int src_type, const void *src, int64_t n_
 
 bool quantize_dst_supported(int dst_type) {
     switch (dst_type) {
-        case T_Q8_0: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: return true;
+        case T_Q8_0: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_TQ1_0: case T_TQ2_0: return true;
         default: return false;
     }
 }
@@ -451,6 +481,8 @@ hipError_t launch_quantize_rows(int dst_type, int src_type, const void *src, int
         case T_Q3_K: return launch_dt<T_Q3_K>(src_type, src, n_per_row, n_total, imatrix, dst, nonfinite_flag, st);
         case T_Q4_K: return launch_dt<T_Q4_K>(src_type, src, n_per_row, n_total, imatrix, dst, nonfinite_flag, st);
         case T_Q5_K: return launch_dt<T_Q5_K>(src_type, src, n_per_row, n_total, imatrix, dst, nonfinite_flag, st);
+        case T_TQ1_0: return launch_dt<T_TQ1_0>(src_type, src, n_per_row, n_total, imatrix, dst, nonfinite_flag, st);
+        case T_TQ2_0: return launch_dt<T_TQ2_0>(src_type, src, n_per_row, n_total, imatrix, dst, nonfinite_flag, st);
         default: return launch_dt<T_Q6_K>(src_type, src, n_per_row, n_total, imatrix, dst, nonfinite_flag, st);
     }
 }

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""Quantise an F32 / F16 / BF16 GGUF file on the device: what upstream's llama-quantize does for the ten mixes the reference publishes (the
-kernels are csrc/quantize.hip behind mi355_quantize_chunk, the arithmetic is restated from memory of ggml and not pinned to its source).
+"""Quantise an F32 / F16 / BF16 GGUF file on the device: what upstream's llama-quantize does for the ten mixes the reference publishes and for the two ternary
+ones (the kernels are csrc/quantize.hip behind mi355_quantize_chunk, the arithmetic is restated from memory of ggml and not pinned to its
+source).
 
   quantize.py [--imatrix FILE] [--pure] [--leave-output-tensor] [--json OUT] IN.gguf OUT.gguf TYPE
 
-TYPE: q2_k, q3_k_s, q3_k_m, q3_k_l, q4_k_s, q4_k_m, q5_k_s, q5_k_m, q6_k or q8_0.  Every 2-D *.weight tensor and every 3-D expert tensor takes the type
+TYPE: q2_k, q3_k_s, q3_k_m, q3_k_l, q4_k_s, q4_k_m, q5_k_s, q5_k_m, q6_k, q8_0, tq1_0 or tq2_0.  The ternary mixes (for a checkpoint trained to ternary
+weights: TriLM, BitNet-style files) keep token_embd in Q4_K and output in Q6_K, write every other tensor as TQ1_0 / TQ2_0 and take no account of an importance
+matrix there; a tensor of theirs whose rows are no multiple of 256 would fall back to Q4_0 and is refused by name.  Every 2-D *.weight tensor and every 3-D expert tensor takes the type
 gguf_synth.tensor_type gives it (the mix, then the 32-element fallback for rows that are no multiple of 256); 1-D tensors, the router (ffn_gate_inp), rope_freqs
 and an encoder's position / type tables are copied.  --pure gives every tensor the mix's base type; --leave-output-tensor copies output.weight.  --imatrix
 takes a file written by tools/imatrix.py (GGUF or legacy form): every layer tensor needs an entry of its row length; token_embd and output are quantised
@@ -32,7 +35,7 @@ _spec.loader.exec_module(imx)
 
 F32, F16, BF16 = 0, 1, 30
 SRC_DTYPE = {F32: np.dtype("<f4"), F16: np.dtype("<f2"), BF16: np.dtype("<u2")}
-MIXES = ("q2_k", "q3_k_s", "q3_k_m", "q3_k_l", "q4_k_s", "q4_k_m", "q5_k_s", "q5_k_m", "q6_k", "q8_0")
+MIXES = ("q2_k", "q3_k_s", "q3_k_m", "q3_k_l", "q4_k_s", "q4_k_m", "q5_k_s", "q5_k_m", "q6_k", "q8_0", "tq1_0", "tq2_0")
 CHUNK_BYTES = 256 << 20                  # source bytes of one device call
 COPIED = ("ffn_gate_inp.weight", "rope_freqs.weight", "token_types.weight", "position_embd.weight")
 _SC = {0: "<B", 1: "<b", 2: "<H", 3: "<h", 4: "<I", 5: "<i", 6: "<f", 7: "<?", 10: "<Q", 11: "<q", 12: "<d"}
@@ -119,7 +122,9 @@ def config_of(pkg, kv: dict, tensors):
 
 
 def base_type(gs, ftype: str) -> int:
-    return {"q2": gs.Q2_K, "q3": gs.Q3_K, "q4": gs.Q4_K, "q5": gs.Q5_K, "q6": gs.Q6_K, "q8": gs.Q8_0}[ftype[:2]]
+    if ftype in ("tq1_0", "tq2_0"):
+        return gs.TQ1_0 if ftype == "tq1_0" else gs.TQ2_0
+    return{"q2": gs.Q2_K, "q3": gs.Q3_K, "q4": gs.Q4_K, "q5": gs.Q5_K, "q6": gs.Q6_K, "q8": gs.Q8_0}[ftype[:2]]
 
 
 def kind_of(name: str):
@@ -179,6 +184,8 @@ def quantize_file(src: str, dst: str, ftype: str, imatrix=None, quantize_rows=No
                 nt = gs.FALLBACK_32[nt]
         if nt == gs.IQ4_NL:
             raise QuantizeError(f"{name}: rows of {ne[0]} are no multiple of 256 and the mix's type here falls back to IQ4_NL, which is not built")
+        if nt == gs.Q4_0:
+            raise QuantizeError(f"{name}: rows of {ne[0]} are no multiple of 256 and the mix's type here falls back to Q4_0, which is not built")
         if ne[0] % gs.BLOCK_ELEMS[nt]:
             raise QuantizeError(f"{name}: rows of {ne[0]} are no whole number of {gs.TYPE_NAME[nt]} blocks")
         n_mat = int(ne[2]) if len(ne) == 3 else 1

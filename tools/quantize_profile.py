@@ -4,7 +4,8 @@ tools/quantize.py, three passes each, every pass a process of its own under its 
 quantize_file (median of the passes [smallest, largest]); per destination type the launches' own time between two events, as source GB/s; the share of the
 wall time the uploads and the downloads take.  For scale, the numpy twin's seconds for one 2048 x 2048 tensor per type on this host.  There is no parent-commit
 counterpart and no threshold.  Synthetic weights: only the times mean anything.
-usage: quantize_profile.py [out.json]   (default profiles/quantize.json; the files go to $MI355_BENCH_DIR, default /tmp, as bench.py's)"""
+usage: quantize_profile.py [out.json [TYPE ...]]   (default profiles/quantize.json and the two mixes above; the files go to $MI355_BENCH_DIR, default /tmp, as
+bench.py's).  The entries `tq1_0` / `tq2_0` of profiles/quantize.json, and `q2_k_with_ternary` beside them, are one run with the types q2_k tq1_0 tq2_0."""
 import json
 import os
 import subprocess
@@ -27,6 +28,7 @@ def med(v):
 
 def main():
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "quantize.json")
+    ftypes = tuple(sys.argv[2:]) or FTYPES
     pkg = ge.load_pkg()
     gs = pkg.gguf_synth
     model_dir = os.environ.get("MI355_BENCH_DIR", "/tmp")
@@ -40,7 +42,7 @@ def main():
                    "(reading through a memory map, the device calls, writing), without the interpreter's start and the library load; no threshold",
            "files": {}}
     dst = os.path.join(model_dir, "mi355-quantize-profile-out.gguf")
-    for ftype in FTYPES:
+    for ftype in ftypes:
         runs = []
         for p in range(PASSES):
             js = dst + ".json"
