@@ -99,6 +99,7 @@ SYMBOLS = {
     "mi355_imatrix_entry": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
     "mi355_imatrix_get": (_i32, [_vp, _i32, _vp, _vp]),
     "mi355_speculative_steps": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "mi355_lookup_steps": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mi355_get_topk_ith": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "mi355_sample_rows": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355_sampled_steps": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -161,6 +162,7 @@ SYMBOLS = {
     "mi355_op_argmax_rows": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp]),
     "mi355_op_argmax_prob_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "mi355_op_spec_verify": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "mi355_op_ngram_draft": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mi355_op_token_logprob_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
     "mi355_op_logits_kl_rows": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
     "mi355_op_imatrix_accum": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
@@ -638,6 +640,19 @@ class Backend:
         self._chk(self.lib.mi355_op_spec_verify(_ptr(logits), logits.shape[1], logits.shape[0], _ptr(rows), R, _ptr(gs), G, _ptr(draft), _ptr(ids), _ptr(acc)),
                   "op_spec_verify")
         return ids, acc[:G]
+
+    def ngram_draft(self, hist, lens, ngram_min: int = 2, ngram_max: int = 4, k: int = 16):
+        """The prompt-lookup draft of every history in one launch (mi355_op_ngram_draft): hist int32 [n_seq][cap], lens [n_seq].  Returns (draft int32
+        [n_seq][16], -1 behind each draft; n_draft int32 [n_seq]; match int32 [n_seq][2] = (m, e) of the winning repeat)."""
+        hist = np.ascontiguousarray(hist, np.int32)
+        hist = hist.reshape(1, -1) if hist.ndim == 1 else hist
+        lens = np.ascontiguousarray(lens, np.int32).reshape(-1)
+        n_seq, cap = hist.shape
+        assert lens.size == n_seq
+        draft = np.full((max(n_seq, 1), 16), -2, np.int32); nd = np.full(max(n_seq, 1), -2, np.int32); match = np.full((max(n_seq, 1), 2), -2, np.int32)
+        self._chk(self.lib.mi355_op_ngram_draft(_ptr(hist), n_seq, cap, _ptr(lens), int(ngram_min), int(ngram_max), int(k), _ptr(draft), _ptr(nd), _ptr(match)),
+                  "op_ngram_draft")
+        return draft, nd, match
 
     def token_logprob_rows(self, base: np.ndarray, targets, rows=None):
         """(log-probability f32 [R], rank int32 [R]) of targets[r] in base[rows[r]] (rows None: row r) over the whole row (mi355_op_token_logprob_rows)."""
@@ -1739,6 +1754,17 @@ class Context:
                                                 out.ctypes.data, stats.ctypes.data)
         if done != n:
             raise MI355Error(f"mi355_speculative_steps stopped after {done} of {n}: {_err(self.lib)}")
+        return out, stats
+
+    def lookup_steps(self, hist, first: int, pos0: int, n: int, ngram_min: int = 2, ngram_max: int = 4, n_max: int = 16, n_min: int = 0, seq: int = 0):
+        """n greedy tokens with drafts looked up in `hist` (normally the prompt this context holds over [0, pos0)), which grows on the device by `first` and
+        every emitted token (mi355_lookup_steps).  Returns (tokens int32 [n], stats int64 [4]: rounds, drafted, accepted, plain steps)."""
+        hist = np.ascontiguousarray(hist, np.int32).reshape(-1)
+        out = np.empty(n, np.int32); stats = np.zeros(4, np.int64)
+        done = self.lib.mi355_lookup_steps(self.h, hist.ctypes.data if hist.size else None, hist.size, int(first), int(pos0), int(seq), int(n), int(ngram_min),
+                                           int(ngram_max), int(n_max), int(n_min), out.ctypes.data, stats.ctypes.data)
+        if done != n:
+            raise MI355Error(f"mi355_lookup_steps stopped after {done} of {n}: {_err(self.lib)}")
         return out, stats
 
     def mega_steps(self) -> int:

@@ -434,6 +434,72 @@ int32_t mi355_speculative_steps(mi355_context *ctx_tgt, mi355_context *ctx_dft, 
         return done;
     )
 }
+// The greedy loop with drafts looked up in a token history on the device (csrc/lookup.hip; the round: DESIGN.md §4.9).  `p` is the position of `last`, the
+// newest emitted token, which the context has not decoded yet; the history ends with it.
+int32_t mi355_lookup_steps(mi355_context *ctx, const mi355_token *hist, int32_t n_hist, mi355_token first, mi355_pos pos0, mi355_seq_id seq, int32_t n,
+                           int32_t ngram_min, int32_t ngram_max, int32_t n_max, int32_t n_min, mi355_token *out_tokens, int64_t *stats) {
+    if (!ctx) return no_context("lookup_steps");
+    if (n < 0 || pos0 < 0 || n_hist < 0 || (n_hist > 0 && !hist) || n_max < 1 || n_max > SPEC_MAX_DRAFT || n_min < 0 || ngram_min < 1 || ngram_min > ngram_max ||
+        ngram_max > NG_MAX_NGRAM) {
+        fail("lookup_steps: n >= 0, pos0 >= 0, n_hist >= 0, 1 <= n_max <= 16, n_min >= 0, 1 <= ngram_min <= ngram_max <= 16"); return MI355_ERR_ARG;
+    }
+    Context *T = ctx->c;
+    if (T->embeddings_enabled) { fail("lookup_steps: embeddings mode computes no logits"); return MI355_ERR_ARG; }
+    if (T->model->hp.tp_size > 1) { fail("lookup_steps: not on a rank of a row split"); return MI355_ERR_ARG; }
+    if ((int64_t)n_hist + n > (int64_t)T->cp.n_ctx) { fail("lookup_steps: n_hist + n = " + std::to_string((int64_t)n_hist + n) + " tokens exceed n_ctx"); return MI355_ERR_ARG; }
+    MI355_GUARD(return MI355_ERR_ARG,
+        int64_t st[4] = {0, 0, 0, 0};                                  // rounds, drafted, accepted, plain steps
+        if (stats) memcpy(stats, st, sizeof st);
+        int32_t sid = seq;
+        int32_t *sp = &sid;
+        int32_t n_seq[SPEC_MAX_DRAFT + 1], pos[SPEC_MAX_DRAFT + 1], toks[SPEC_MAX_DRAFT + 1], ids[SPEC_MAX_DRAFT + 1], draft[SPEC_MAX_DRAFT + 1];
+        int32_t *seqs[SPEC_MAX_DRAFT + 1];
+        int8_t flags[SPEC_MAX_DRAFT + 1];
+        for (int j = 0; j < SPEC_MAX_DRAFT + 1; j++) { n_seq[j] = 1; seqs[j] = sp; flags[j] = 1; }
+        const int room = (int)(T->cp.n_ctx / T->cp.n_seq_max);
+        int32_t last = first, p = pos0, done = 0;
+        if (n > 0 && (T->lookup_set(seq, 0, hist, n_hist) != 0 || T->lookup_set(seq, -1, &first, 1) != 0)) { fail(T->last_error); return 0; }
+        while (done < n) {
+            // 1. the draft: what followed the most recent, longest repeat of the history's tail; 2. too short a draft is not worth a batch
+            const int k_cap = std::max(0, std::min((int)n_max, room - p - 1));
+            int k = 0;
+            if (k_cap > 0) {
+                k = T->lookup_draft(seq, ngram_min, ngram_max, k_cap, draft, nullptr);
+                if (k < 0) { fail(T->last_error); break; }
+                if (k < n_min) k = 0;
+            }
+            // 3. the target decodes the last token and the drafts as one batch, every row flagged
+            int a = 0;
+            toks[0] = last; pos[0] = p;
+            for (int j = 0; j < k; j++) { toks[j + 1] = draft[j]; pos[j + 1] = p + 1 + j; }
+            const int rc = T->decode(k + 1, toks, pos, n_seq, seqs, flags);
+            if (rc != 0) { fail(rc < 0 ? T->last_error : std::string("lookup_steps: no KV cells left for the batch")); break; }
+            const int m_cap = (int)(n - done);
+            if (k > 0) {
+                const int32_t gs[2] = {0, k + 1};
+                draft[k] = -1;
+                if (T->spec_verify(1, gs, draft, ids, &a) < 0) { fail(T->last_error); break; }
+            } else {
+                ids[0] = T->argmax_ith(0);
+                if (ids[0] < 0) { fail(T->last_error.empty() ? "arg-max failed" : T->last_error); break; }
+                st[3]++;
+            }
+            // 4. emit ids[0 .. a], cut at n: the history takes them from the verify launch's output where there was one; 5. the cache keeps nothing behind them
+            const int m = std::min(a + 1, m_cap);
+            if ((k > 0 ? T->lookup_take_verified(seq, 0, m) : T->lookup_set(seq, -1, ids, 1)) != 0) { fail(T->last_error); break; }
+            st[0]++; st[1] += k; st[2] += m - 1;
+            for (int j = 0; j < m; j++) if (out_tokens) out_tokens[done + j] = ids[j];
+            done += m;
+            const int32_t keep = p + m;
+            if (k + 1 > m) T->kv_seq_rm(seq, keep, -1);
+            last = ids[m - 1];
+            p = keep;
+        }
+        if (T->lookup_flush() != 0) { fail(T->last_error); return MI355_ERR_HIP; }
+        if (stats) memcpy(stats, st, sizeof st);
+        return done;
+    )
+}
 int32_t mi355_get_topk_ith(mi355_context *ctx, int32_t i, int32_t k, int32_t n_adj, const int32_t *adj_tok, const float *adj_bias, const int32_t *adj_count,
                            float penalty_repeat, float penalty_freq, float penalty_present, int32_t *toks_out, float *logits_out) {
     if (!ctx || !toks_out || !logits_out || n_adj < 0 || n_adj > TOPK_MAX_ADJ || (n_adj > 0 && (!adj_tok || !adj_bias || !adj_count))) { fail("bad arguments"); return -1; }

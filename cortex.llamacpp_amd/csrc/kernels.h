@@ -252,8 +252,22 @@ hipError_t launch_argmax_prob_rows(const float *x, int n, const int32_t *rows_de
 // (rows group_start_dev[g] .. group_start_dev[g + 1] - 1, the last one excepted) have ids[j] == draft_dev[j].  One launch.
 // scratch: spec_verify_scratch_words(cap_rows) words, zero-filled once
 size_t spec_verify_scratch_words(int cap_rows);
+// the ids of the last launch on that scratch, by launch row, where they stay on the device (what launch_lookup_append reads)
+const int32_t *spec_verify_ids_dev(const float *scratch, int cap_rows);
 hipError_t launch_spec_verify(const float *base, int n, const int32_t *rows_dev, int R, const int32_t *group_start_dev, int G, const int32_t *draft_dev,
                               int32_t *ids_out, int32_t *n_accept_out, float *scratch, int cap_rows, hipStream_t st);
+// ---- prompt-lookup drafting (lookup.hip): the draft is the continuation of the most recent, longest repeat of a history's tail.
+constexpr int NG_MAX_SEQ = 64, NG_MAX_PARTS = 64, NG_MAX_DRAFT = 16, NG_MAX_NGRAM = 16, NG_MAX_CAP = 1 << 24;
+// hist [n_seq][cap] int32 on the device, 16-byte aligned, cap % 4 == 0; len_dev [n_seq] (clamped to [0, cap] by the kernel); max_len: the longest of them as
+// the host knows it, which sizes the grid (ngram_draft_grid).  1 <= ngram_min <= ngram_max <= 16, 1 <= k <= 16.  Per sequence: draft_out [16] (-1 behind the
+// draft), n_draft_out, match_out [2] = (m, e) of the winner.  One launch.  scratch: ngram_draft_scratch_words() words, 8-byte aligned, zero-filled once.
+size_t ngram_draft_scratch_words();
+void ngram_draft_grid(int max_len, int &parts, int &tiles_per_part);
+hipError_t launch_ngram_draft(const int32_t *hist, int n_seq, int cap, const int32_t *len_dev, int max_len, int ngram_min, int ngram_max, int k,
+                              int32_t *draft_out, int32_t *n_draft_out, int32_t *match_out, float *scratch, hipStream_t st);
+// hist[seq][base .. base + n) = src[0 .. n) with base = at (at >= 0: the history is cut to `at` tokens first) or len_dev[seq] (at < 0); len_dev[seq] follows.
+// Tokens that do not fit under cap are dropped, the length stops at cap and *overflow becomes 1 (a word the kernel can write: device or pinned host memory).
+hipError_t launch_lookup_append(int32_t *hist, int n_seq, int cap, int32_t *len_dev, int seq, const int32_t *src, int n, int at, int32_t *overflow, hipStream_t st);
 // ---- perplexity and KL divergence (logprob.hip): argmax_prob's shape and index rule, n <= SPEC_MAX_N, rows <= cap_rows and <= 65535 per
 // launch.  Everything in f32, summation orders fixed: the same bits run to run.
 // Row r = base row rows_dev[r] (nullptr: row r), target t = targets_dev[r] in [0, n): logprob_out[r] = x_t - M - log(S), M the row maximum and

@@ -123,6 +123,7 @@ __global__ __launch_bounds__(256) void spec_verify_kernel(const float *base, int
     n_accept_out[tid] = a;
 }
 size_t spec_verify_scratch_words(int cap_rows) { return 4 + (size_t)cap_rows * (2 + 2 * SPEC_PARTS); }
+const int32_t *spec_verify_ids_dev(const float *scratch, int cap_rows) { return reinterpret_cast<const int32_t *>(scratch) + 4 + cap_rows; }
 hipError_t launch_spec_verify(const float *base, int n, const int32_t *rows_dev, int R, const int32_t *group_start_dev, int G, const int32_t *draft_dev,
                               int32_t *ids_out, int32_t *n_accept_out, float *scratch, int cap_rows, hipStream_t st) {
     if (n < 1 || n > SPEC_MAX_N || R < 1 || R > cap_rows || R > SPEC_MAX_ROWS || G < 1 || G > SPEC_MAX_GROUPS) return hipErrorInvalidValue;

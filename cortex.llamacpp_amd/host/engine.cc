@@ -207,7 +207,8 @@ bool LlamaEngine::LoadModelImpl(const Json &body, std::string &err) {   // :547-
         log_line(LOG_WARN, "cache_ram: this backend has no sequence state (a row-split or an embedding model): the prompt cache is off");
         sp.cache_ram_mib = 0;
     }
-    // "model_draft" (the backend factory loads it): how far the draft model runs ahead - upstream's --draft-max / --draft-min / --draft-p-min
+    // "model_draft" or "spec_type": "ngram" (the backend factory reads both): how far the drafter runs ahead - upstream's --draft-max / --draft-min /
+    // --draft-p-min (the last one is a draft model's alone)
     sp.draft_max = std::min(16, std::max(1, body.value<int>("draft_max", 16)));
     sp.draft_min = std::max(0, body.value<int>("draft_min", 0));
     sp.draft_p_min = body.value<float>("draft_p_min", 0.75f);

@@ -46,8 +46,27 @@ class HipBackend : public IBackend {
     void set_clip(std::unique_ptr<ClipModel> c) { clip_ = std::move(c); }
     // ---- the draft model of a speculating server ("model_draft"): its own context, logits left on the device
     void set_draft(std::unique_ptr<Model> m, std::unique_ptr<Context> c) { dmodel_ = std::move(m); dctx_ = std::move(c); }
-    bool has_draft() const override { return dctx_ != nullptr; }
+    // ---- ... or no draft model at all ("spec_type": "ngram"): the draft is looked up in the slot's own tokens, on the device (csrc/lookup.hip)
+    void set_lookup(int ngram_min, int ngram_max) { lookup_ = true; ngram_min_ = ngram_min; ngram_max_ = ngram_max; }
+    bool has_draft() const override { return dctx_ != nullptr || lookup_; }
+    // The device history of a slot follows its tokens: the common prefix stays, the history is cut where the two part (a new prompt: at 0) and only the new
+    // suffix is uploaded - one token a step while a request runs.  One launch per call; p_min is a draft model's and is not read.
+    int lookup_draft(int seq, const int32_t *tokens, int n_tokens, int n_max, int32_t *out) {
+        if (n_tokens < 1 || n_max < 1 || seq < 0 || seq >= 64 || n_tokens > ctx_->lookup_cap()) return 0;
+        std::vector<int32_t> &held = draft_held_[(size_t)seq];
+        size_t common = 0;
+        while (common < held.size() && common < (size_t)n_tokens && held[common] == tokens[common]) common++;
+        if (common < held.size() || common < (size_t)n_tokens) {
+            if (ctx_->lookup_set(seq, (int)common, tokens + common, n_tokens - (int)common) != 0) { held.clear(); return 0; }
+            held.resize(common);
+            held.insert(held.end(), tokens + common, tokens + n_tokens);
+        }
+        const int k = ctx_->lookup_draft(seq, ngram_min_, ngram_max_, std::min(n_max, NG_MAX_DRAFT), out, nullptr);
+        if (k < 0) { held.clear(); return 0; }
+        return k;
+    }
     int spec_draft(int seq, const int32_t *tokens, int n_tokens, int n_max, float p_min, int32_t *out) override {
+        if (lookup_) return lookup_draft(seq, tokens, n_tokens, n_max, out);
         if (!dctx_ || n_tokens < 1 || n_max < 1 || seq < 0 || seq >= 64) return 0;
         std::vector<int32_t> &held = draft_held_[(size_t)seq];
         size_t common = 0;
@@ -192,7 +211,7 @@ class HipBackend : public IBackend {
     const float *embeddings_ith(int i) override { return ctx_->embeddings_ith(i); }
     void kv_clear() override {
         ctx_->kv_clear();
-        if (dctx_) { dctx_->kv_clear(); for (auto &h : draft_held_) h.clear(); }
+        if (dctx_) { dctx_->kv_clear(); for (auto &h : draft_held_) h.clear(); }      // (a lookup history is not KV state: it follows the next call's tokens)
     }
     bool kv_seq_rm(int seq, int p0, int p1) override { return ctx_->kv_seq_rm(seq, p0, p1); }
     void kv_seq_add(int seq, int p0, int p1, int delta) override { ctx_->kv_seq_add(seq, p0, p1, delta); }
@@ -229,7 +248,9 @@ class HipBackend : public IBackend {
     std::unique_ptr<Context> ctx_;
     std::unique_ptr<Model> dmodel_;                     // the draft model and its one context (n_seq_max, ctx_len and cache type of the target's)
     std::unique_ptr<Context> dctx_;
-    std::vector<int32_t> draft_held_[64];               // per sequence: the tokens the draft context holds, positions 0 ..
+    std::vector<int32_t> draft_held_[64];               // per sequence: the tokens the draft context (or the lookup history on the device) holds, positions 0 ..
+    bool lookup_ = false;                               // "spec_type": "ngram"
+    int ngram_min_ = 2, ngram_max_ = 4;
     std::vector<int32_t> d_pos_, d_nseq_;
     std::vector<int32_t *> d_seqp_;
     std::vector<int8_t> d_flags_;
@@ -266,6 +287,19 @@ std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, 
     // --control-vector-scaled / --control-vector-layer-range: the files are loaded, summed and applied to the context before the first step
     const Json &cvecs = body["control_vectors"];
     if (!cvecs.is_null() && tp_split_requested(body)) { err = "control_vectors: control vectors are not supported with \"split_mode\": \"row\" (load the model on one device)"; return nullptr; }
+    // "spec_type": "ngram" - prompt-lookup drafting, speculative decoding without a draft model; "spec_ngram_min" / "spec_ngram_max": the
+    // shortest repeat of the tail that counts and the longest one looked for (upstream's lookup n-gram sizes)
+    const bool spec_ngram = !body["spec_type"].is_null();
+    int ngram_min = 2, ngram_max = 4;
+    if (spec_ngram) {
+        if (body["spec_type"].str_or("") != "ngram") { err = "spec_type: expected \"ngram\" (the only drafter without a draft model)"; return nullptr; }
+        if (!body["model_draft"].is_null()) { err = "spec_type: \"ngram\" drafts from the prompt and cannot be combined with model_draft"; return nullptr; }
+        if (tp_split_requested(body)) { err = "spec_type: speculative decoding is not supported with \"split_mode\": \"row\""; return nullptr; }
+        if (!body["mmproj"].is_null()) { err = "spec_type: speculative decoding is not supported beside a multimodal projector (mmproj)"; return nullptr; }
+        ngram_min = body.value<int>("spec_ngram_min", 2);
+        ngram_max = body.value<int>("spec_ngram_max", std::max(4, ngram_min));
+        if (ngram_min < 1 || ngram_min > ngram_max || ngram_max > NG_MAX_NGRAM) { err = "spec_type: 1 <= spec_ngram_min <= spec_ngram_max <= 16 expected"; return nullptr; }
+    }
     if (!body["model_draft"].is_null() && !body["mmproj"].is_null()) { err = "model_draft: speculative decoding is not supported beside a multimodal projector (mmproj)"; return nullptr; }
     if (!body["model_draft"].is_null() && tp_split_requested(body)) { err = "model_draft: speculative decoding is not supported with \"split_mode\": \"row\""; return nullptr; }
     if (tp_split_requested(body)) return make_split_backend(body, info, err);
@@ -317,6 +351,7 @@ std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, 
         if (v16 && cp.n_ctx < 4096) { cp.n_ctx = 4096; log_line(LOG_INFO, "Request %d for context length for llava-1.6", 4096); }
         else if (cp.n_ctx < 2048) { cp.n_ctx = 2048; log_line(LOG_INFO, "Request %d for context length for the image embedding", 2048); }
     }
+    if (spec_ngram && model->hp.encoder) { err = "spec_type: an embedding (encoder) model cannot speculate"; return nullptr; }
     cp.n_batch = (uint32_t)std::max(1, body.value<int>("n_batch", 2048));
     cp.n_ubatch = (uint32_t)std::max(1, body.value<int>("n_ubatch", (int)cp.n_batch));
     cp.n_batch = std::min(cp.n_batch, cp.n_ctx);
@@ -414,6 +449,7 @@ std::unique_ptr<IBackend> make_hip_backend(const Json &body, BackendInfo &info, 
     be->set_device_sampler(body.value<bool>("device_sampler", false));
     be->set_clip(std::move(clip));
     if (dctx) be->set_draft(std::move(dmodel), std::move(dctx));
+    if (spec_ngram) { be->set_lookup(ngram_min, ngram_max); log_line(LOG_INFO, "prompt-lookup drafting: n-grams of %d .. %d tokens", ngram_min, ngram_max); }
     return be;
 }
 

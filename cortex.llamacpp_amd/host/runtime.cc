@@ -338,6 +338,7 @@ Context::~Context() {
     if (h_topk_) (void)hipHostFree(h_topk_);
     if (h_topk_adj_) (void)hipHostFree(h_topk_adj_);
     if (h_spec_) (void)hipHostFree(h_spec_);
+    if (h_lookup_) (void)hipHostFree(h_lookup_);
     if (h_lp_) (void)hipHostFree(h_lp_);
     if (d_topk_adj_) (void)hipFree(d_topk_adj_);
     if (h_samp_) (void)hipHostFree(h_samp_);
@@ -2693,6 +2694,77 @@ int Context::spec_verify(int n_groups, const int32_t *group_start, const int32_t
     memcpy(ids_out, h_ids, (size_t)R * 4);
     memcpy(n_accept_out, h_acc, (size_t)n_groups * 4);
     return R;
+}
+
+// ---- prompt-lookup drafting (csrc/lookup.hip): the histories live on the device and grow there; the host keeps their lengths only
+bool Context::lookup_prepare(int seq) {
+    if (seq < 0 || seq >= (int)cp.n_seq_max || seq >= NG_MAX_SEQ) { last_error = "lookup: sequence " + std::to_string(seq) + " outside the context's n_seq_max"; return false; }
+    if (lookup_scratch_) return true;
+    if (hipSetDevice(model->device) != hipSuccess) { last_error = "lookup: cannot select the device"; return false; }
+    const size_t cap = (size_t)lookup_cap();
+    (void)hipStreamSynchronize(stream_);
+    if (!h_lookup_) {
+        if (hipHostMalloc((void **)&h_lookup_, (NG_MAX_DRAFT + 4) * 4, hipHostMallocDefault) != hipSuccess) { h_lookup_ = nullptr; last_error = "lookup workspace allocation failed"; return false; }
+        memset(h_lookup_, 0, (NG_MAX_DRAFT + 4) * 4);
+    }
+    if (!d_lookup_) d_lookup_ = (int32_t *)dalloc((cp.n_seq_max * cap + NG_MAX_SEQ + cap) * 4);
+    float *scratch = d_lookup_ ? (float *)dalloc(ngram_draft_scratch_words() * 4) : nullptr;    // (zero-filled: the ticket words, and every length)
+    if (!scratch) { last_error = "lookup workspace allocation failed"; return false; }
+    lookup_scratch_ = scratch;
+    (void)hipDeviceSynchronize();                                      // the null-stream zero-fills (see init)
+    return true;
+}
+
+int Context::lookup_set(int seq, int at, const int32_t *tokens, int n) {
+    if (!lookup_prepare(seq)) return -1;
+    const int cap = lookup_cap();
+    if (n < 0 || (n > 0 && !tokens) || at > cap) { last_error = "lookup_set: bad arguments"; return -1; }
+    int32_t *len = d_lookup_ + (size_t)cp.n_seq_max * cap, *stage = len + NG_MAX_SEQ;
+    const int base = at >= 0 ? at : lookup_len_[seq];
+    if (n > cap - base) { last_error = "lookup_set: " + std::to_string(base) + " + " + std::to_string(n) + " tokens do not fit a history of " + std::to_string(cap); return -1; }
+    // (the copy is ordered behind the appends that still read `stage`; the source is the caller's - a stack word, a slot's vector - so it has left before the
+    // call returns, whatever the runtime does with pageable memory)
+    if (n > 0 && (hipMemcpyAsync(stage, tokens, (size_t)n * 4, hipMemcpyHostToDevice, stream_) != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess)) {
+        last_error = "lookup_set: upload failed"; return -1;
+    }
+    if (launch_lookup_append(d_lookup_, (int)cp.n_seq_max, cap, len, seq, stage, n, at, h_lookup_ + NG_MAX_DRAFT + 3, stream_) != hipSuccess) { last_error = "lookup_set: launch failed"; return -1; }
+    lookup_len_[seq] = base + n;
+    return 0;
+}
+
+int Context::lookup_take_verified(int seq, int row0, int n) {
+    if (!lookup_prepare(seq)) return -1;
+    if (!spec_scratch_ || row0 < 0 || n < 1 || row0 + n > SPEC_MAX_ROWS) { last_error = "lookup_take_verified: no verify launch holds those rows"; return -1; }
+    const int cap = lookup_cap();
+    int32_t *len = d_lookup_ + (size_t)cp.n_seq_max * cap;
+    if (launch_lookup_append(d_lookup_, (int)cp.n_seq_max, cap, len, seq, spec_verify_ids_dev(spec_scratch_ + argmax_prob_scratch_words(1), SPEC_MAX_ROWS) + row0, n, -1,
+                             h_lookup_ + NG_MAX_DRAFT + 3, stream_) != hipSuccess) { last_error = "lookup_take_verified: launch failed"; return -1; }
+    lookup_len_[seq] = std::min(cap, lookup_len_[seq] + n);          // (past cap: the kernel's flag says so at the next lookup_draft)
+    return 0;
+}
+
+int Context::lookup_draft(int seq, int ngram_min, int ngram_max, int k, int32_t *out, int32_t *match) {
+    if (!lookup_prepare(seq)) return -1;
+    if (ngram_min < 1 || ngram_min > ngram_max || ngram_max > NG_MAX_NGRAM || k < 1 || k > NG_MAX_DRAFT || !out) {
+        last_error = "lookup_draft: 1 <= ngram_min <= ngram_max <= 16, 1 <= k <= 16"; return -1;
+    }
+    const int cap = lookup_cap();
+    const int32_t *len = d_lookup_ + (size_t)cp.n_seq_max * cap;
+    // one launch per call, over this sequence's row alone (the kernel takes up to 64 rows: batching a step's slots is open)
+    if (launch_ngram_draft(d_lookup_ + (size_t)seq * cap, 1, cap, len + seq, lookup_len_[seq], ngram_min, ngram_max, k, h_lookup_, h_lookup_ + NG_MAX_DRAFT,
+                           h_lookup_ + NG_MAX_DRAFT + 1, lookup_scratch_, stream_) != hipSuccess) { last_error = "lookup_draft: launch failed"; return -1; }
+    if (lookup_flush() != 0) return -1;
+    const int nd = h_lookup_[NG_MAX_DRAFT];
+    memcpy(out, h_lookup_, (size_t)nd * 4);
+    if (match) { match[0] = h_lookup_[NG_MAX_DRAFT + 1]; match[1] = h_lookup_[NG_MAX_DRAFT + 2]; }
+    return nd;
+}
+
+int Context::lookup_flush() {
+    if (!h_lookup_) return 0;
+    if (hipStreamSynchronize(stream_) != hipSuccess || !mega_check() || !stream_check()) return -1;
+    if (h_lookup_[NG_MAX_DRAFT + 3]) { h_lookup_[NG_MAX_DRAFT + 3] = 0; last_error = "lookup: a history outgrew its " + std::to_string(lookup_cap()) + " tokens"; return -1; }
+    return 0;
 }
 
 // ---- perplexity and KL divergence (csrc/logprob.hip): d_logits_ again; a launch takes at most n_ubatch rows (the scratch's size), a call

@@ -146,6 +146,16 @@ class Context {
     // the model agrees with, from the group's first row on.  One launch, one synchronisation.  Returns R, or -1 with last_error set (a row not flagged,
     // embeddings mode, a rank of a row split).
     int spec_verify(int n_groups, const int32_t *group_start, const int32_t *draft, int32_t *ids_out, int32_t *n_accept_out);
+    // prompt-lookup drafting (csrc/lookup.hip): one token history per sequence on the device, lookup_cap() tokens each, allocated on first use.
+    // lookup_set: the history of `seq` is cut to `at` tokens (at < 0: kept whole) and n host tokens are appended.  lookup_take_verified: n ids of the last
+    // spec_verify launch, from its row row0 on, are appended without leaving the device.  lookup_draft: the continuation of the most recent, longest repeat of
+    // the history's tail (at most k tokens into out [16]; match [2] = (m, e), may be null); it synchronises, and reports a history that outgrew lookup_cap().
+    // Each returns >= 0 (lookup_draft: the number of drafted tokens), or -1 with last_error set.
+    int lookup_cap() const { return (int)((cp.n_ctx + 1 + 3) & ~3u); }
+    int lookup_set(int seq, int at, const int32_t *tokens, int n);
+    int lookup_take_verified(int seq, int row0, int n);
+    int lookup_draft(int seq, int ngram_min, int ngram_max, int k, int32_t *out, int32_t *match);
+    int lookup_flush();                      // waits for the appends queued so far; -1 if one of them outgrew lookup_cap()
     // perplexity and KL divergence (csrc/logprob.hip), from the device logits of the last decode like the two above; a few words per row come
     // back through pinned memory, one synchronisation per call, the rows stay where logits_ith finds them.  Each returns n, or -1 with last_error set
     // (embeddings mode, a batch row that was not flagged, a target outside the vocabulary, a rank of a row split; logits_kl also: another n_vocab, another
@@ -461,6 +471,12 @@ class Context {
     float *spec_scratch_ = nullptr;                    // argmax_prob_ith / spec_verify: part and ticket words of the two kernels (first use)
     int32_t *d_spec_in_ = nullptr, *h_spec_ = nullptr; // rows | group starts | drafts on the device; pinned: their staging, then ids | accepted | (index, p)
     bool spec_prepare();
+    // lookup_*: histories [n_seq_max][lookup_cap()] | lengths [64] | an upload's staging [lookup_cap()]; the draft kernel's slots and tickets; pinned: draft
+    // [16] | n_draft | m | e | overflow.  lookup_len_: the lengths as the host knows them (they size the grid)
+    int32_t *d_lookup_ = nullptr, *h_lookup_ = nullptr;
+    float *lookup_scratch_ = nullptr;
+    int lookup_len_[64] = {};
+    bool lookup_prepare(int seq);
     // token_logprobs / logits_kl: the two kernels' part and ticket words, sized for n_ubatch rows per launch (first use); rows | targets (or rows | rows) of a
     // call on the device and their pinned staging followed by the results, both grown to the largest call
     float *lp_scratch_ = nullptr;

@@ -46,7 +46,7 @@ struct ServerParams {            // the subset of common_params the loop reads
     int32_t n_parallel = 1;
     bool cont_batching = true;
     int64_t cache_ram_mib = 0;   // /loadmodel "cache_ram": MiB of host memory for the prompt cache (prompt_cache.h); 0 = off, the loop then makes no state call at all; < 0 = no limit
-    // /loadmodel "draft_max" / "draft_min" / "draft_p_min": speculative decoding with the backend's draft model (read only when it has one)
+    // /loadmodel "draft_max" / "draft_min" / "draft_p_min": speculative decoding with the backend's draft model or prompt-lookup drafter (read only when it has one)
     int32_t draft_max = 16, draft_min = 0;
     float draft_p_min = 0.75f;
     std::string model_alias;

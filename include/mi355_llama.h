@@ -170,6 +170,16 @@ MI355_API int32_t mi355_spec_verify(mi355_context *ctx, int32_t n_groups, const 
  * (drafts that were emitted: n = rounds + accepted), plain steps (rounds without a draft).  Returns the tokens written (n, or fewer with the reason in mi355_last_error). */
 MI355_API int32_t mi355_speculative_steps(mi355_context *ctx_tgt, mi355_context *ctx_dft, mi355_token first, mi355_pos pos0, mi355_seq_id seq, int32_t n,
                                           int32_t n_max, int32_t n_min, float p_min, mi355_token *out_tokens, int64_t *stats);
+/* Prompt-lookup drafting: mi355_greedy_steps with drafts taken from a token history instead of a draft model.  `ctx` holds sequence `seq`
+ * over [0, pos0); `first` goes to pos0.  hist [n_hist] is the text that is searched - normally the prompt the context holds, but it is not tied to the KV
+ * cache and may carry reference text; it is uploaded once, and `first` and every emitted token are appended to it on the device.  A round: the history's
+ * tail is looked up (the longest repeat of its last ngram_min .. ngram_max <= 16 tokens, the most recent among equals) and up to n_max <= 16 tokens that
+ * followed the repeat are the draft; fewer than n_min are dropped; the target decodes [last, drafts] with every row flagged, mi355_spec_verify's kernel
+ * counts the agreeing drafts, and the agreed drafts with the target's next token go from the verify launch's output into the history (on the device) and to
+ * out_tokens; the cache forgets what lies behind them.  Exactly n tokens: the last round is cut.  stats (nullable) [4] as mi355_speculative_steps keeps them.
+ * Refused: embeddings mode, a rank of a row split, n_hist + n > n_ctx.  Returns the tokens written (n, or fewer with the reason in mi355_last_error). */
+MI355_API int32_t mi355_lookup_steps(mi355_context *ctx, const mi355_token *hist, int32_t n_hist, mi355_token first, mi355_pos pos0, mi355_seq_id seq, int32_t n,
+                                     int32_t ngram_min, int32_t ngram_max, int32_t n_max, int32_t n_min, mi355_token *out_tokens, int64_t *stats);
 /* ---- perplexity and KL divergence (what upstream's llama-perplexity prints).  Like the block above these read the device logits of the last
  * mi355_decode, with logits_to_host 0 or 1, and bring a few words per row to the host; a later mi355_get_logits_ith still returns the same rows.
  * logprob_out [n]: log softmax(row batch_rows[r])[targets[r]] over the WHOLE vocabulary, x_t - max - log(sum_j exp(x_j - max)) in f32; rank_out (nullable) [n]:
@@ -589,6 +599,12 @@ MI355_API int mi355_op_add_row_vec(const float *x, const float *v, int32_t E, in
  * (1 .. 17 rows; group_start[0] = 0, group_start[G] = R); draft [R].  ids_out [R], n_accept_out [G] as mi355_spec_verify gives them. */
 MI355_API int mi355_op_spec_verify(const float *logits, int64_t n, int32_t n_base_rows, const int32_t *rows, int32_t R, const int32_t *group_start, int32_t G,
                                    const int32_t *draft, int32_t *ids_out, int32_t *n_accept_out);
+/* The prompt-lookup draft of n_seq <= 64 histories in one launch (csrc/lookup.hip): hist [n_seq][cap], len [n_seq] in [0, cap].  For an end position e,
+ * 1 <= e < len, m(e) = how many tokens agree walking backwards from hist[e - 1] against hist[len - 1], at most ngram_max, the walk ending at index 0; the
+ * winner is the largest m, the largest e among equals.  m >= ngram_min: the draft is hist[e .. min(e + k, len)).  1 <= ngram_min <= ngram_max <= 16,
+ * 1 <= k <= 16.  draft_out [n_seq][16] (-1 behind the draft), n_draft_out [n_seq], match_out [n_seq][2] = (m, e). */
+MI355_API int mi355_op_ngram_draft(const int32_t *hist, int32_t n_seq, int32_t cap, const int32_t *len, int32_t ngram_min, int32_t ngram_max, int32_t k,
+                                   int32_t *draft_out, int32_t *n_draft_out, int32_t *match_out);
 /* The k best candidates of n_rows logits rows (the front end of a sampled step): row r is base row rows[r] ([n_base_rows][n] f32) after its adjustments -
  * adj_n[r] entries (0 .. 192) of the flat [n_rows][192] arrays adj_tok / adj_bias / adj_cnt, no token twice in a row's list: l = l + bias; if cnt > 0:
  * l = l <= 0 ? l * repeat[r] : l / repeat[r]; l -= cnt * freq[r] + present[r].  Order: higher logit first, lower token id among equal logits (-0.0 == +0.0).
